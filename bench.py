@@ -12,8 +12,15 @@ process has touched torch or the GPU, never an exec) and forwards rank 0's line;
 directly (RANK / WORLD_SIZE in the environment) it is one of those ranks.  Every rank owns E envs (weak scaling, no
 data-path collective) and the chosen control sequences are gathered with ONE RCCL all-gather per step.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including `roofline` and `cpu_baseline` objects, plus
-side objects for BASELINE's other configurations (`configs.C3`, `configs.C4`, `configs.C5_gru`, `single_env`).
+Prints ONE JSON line on rank 0 (contract in the task statement) with the `roofline` objects of the timed launches.  A plain
+run does only that: set up, warm up, time --steps steps, write --dump-outputs, print the line.  `--full` adds everything
+else: side objects for BASELINE's other configurations (`configs.C3`, `configs.C4`, `configs.C5_gru`, ...), `single_env`,
+the oracle check of every timed configuration (`verified`) and `cpu_baseline`.
+
+`--dump-outputs DIR` writes what the last timed step handed its caller, as float32 .npy files: `Q.npy` (the control to apply,
+[envs]) and `u_nom.npy` (the updated nominal sequences, [envs, horizon]); over several ranks, the envs of every rank in rank
+order (u_nom as the step's all-gather delivered it).  The inputs depend on the arguments alone, so two builds can be compared
+output for output.
 """
 import argparse
 import json
@@ -80,7 +87,17 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="launcher / collective plumbing only (CPU, gloo): no kernel runs and `value` is null; what the "
                          "CPU test of the N > 1 entry point uses")
+    ap.add_argument("--full", action="store_true",
+                    help="besides the headline: the side configurations (C3 / C4 / GRU / predictor_ODE and their env-group "
+                         "forms), the single-env latency, the oracle check of every timed configuration and the CPU baseline; "
+                         "the --no-* options above drop parts of it.  Off: the headline alone")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last one computed (Q, u_nom) as DIR/<name>.npy, float32")
     args = ap.parse_args(argv)
+    if args.steps is not None and args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.warmup is not None and args.warmup < 0:
+        ap.error("--warmup must not be negative")
     if args.predictor == "gru" and args.noise == "buffer":
         ap.error("--predictor gru takes --noise philox or buffer-ref (the tiled buffer layout is read by the ODE rollout "
                  "kernel only; cpmppi_step refuses the combination)")
@@ -707,6 +724,38 @@ class GroupedWorkload:
         self.groups.close()
 
 
+DUMP_LIMIT_BYTES = 60_000_000          # the arrays of --dump-outputs in all: below 64 MB with the .npy headers
+
+
+def dump_outputs(wl, out_dir):
+    """--dump-outputs: what the last timed step of `wl` handed its caller - Q[E] and the updated u_nom[E, H] - as float32
+    DIR/Q.npy and DIR/u_nom.npy, written by rank 0.  Over several ranks: the envs of every rank in rank order, u_nom as the
+    step's own all-gather delivered it, Q gathered here (outside the timed region).  Should the arrays exceed
+    DUMP_LIMIT_BYTES, a fixed, seeded sample of envs is written instead, their indices in DIR/env_index.npy (float64)."""
+    import numpy as np
+    import torch
+    import torch.distributed as dist
+    W, E, H = wl.ctx["world"], wl.E, wl.H
+    i_last = wl.next_step - 1
+    u, Q = wl.final_u_nom(i_last).reshape(E, H), wl.Q_out.reshape(E)
+    if wl.ctx["collective"]:
+        u = (wl.native.gathered[(i_last + 1) & 1][:, :E * H] if wl.native else wl.gathered[i_last & 1].view(W, E * H)).reshape(W * E, H)
+        dev = Q.device if wl.ctx["backend"] == "nccl" else "cpu"
+        Q_all = torch.empty(W * E, dtype=Q.dtype, device=dev)
+        dist.all_gather_into_tensor(Q_all, Q.to(dev).contiguous())
+        Q = Q_all
+    if wl.ctx["rank"] != 0:
+        return
+    arrays = {"Q": Q.cpu().numpy(), "u_nom": u.cpu().numpy()}
+    n = arrays["Q"].shape[0]
+    if n * (H + 1) * 4 > DUMP_LIMIT_BYTES:
+        idx = np.sort(np.random.Generator(np.random.SFC64(0)).choice(n, size=DUMP_LIMIT_BYTES // ((H + 1) * 4 + 8), replace=False))
+        arrays = {"Q": arrays["Q"][idx], "u_nom": arrays["u_nom"][idx], "env_index": idx.astype(np.float64)}
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a if a.dtype == np.float64 else a.astype(np.float32))
+
+
 def roofline_valu(r, E, N, H):
     return {"bound": "fp32-valu", "achieved": r["valu_tflops"], "peak": FP32_VALU_PEAK_TFLOPS, "unit": "TFLOP/s",
             "frac": r["valu_tflops"] / FP32_VALU_PEAK_TFLOPS, "algorithmic_flops_per_rollout": algorithmic_flops_per_rollout(H),
@@ -828,6 +877,12 @@ def main():
                        predictor_type=args.predictor_type)
     r = main_wl.run(args.steps, args.warmup)
     mark("headline_timed")
+    if args.dump_outputs:
+        dump_outputs(main_wl, args.dump_outputs)
+        mark("outputs_dumped")
+    if not args.full:
+        # a plain run is the headline alone: no side configuration, single env, oracle check or CPU baseline
+        args.no_extra_configs = args.no_single_env = args.no_verify = args.no_cpu_baseline = True
     cfg = main_wl.cfg
     # Verification against the oracle happens AFTER every timed region of the run (rank 0 only): the workloads are kept until
     # then.  (Not only a matter of principle: the C oracle's OpenMP pool, once started in this process, slows the host-paced
@@ -965,7 +1020,7 @@ def main():
         out = {
             "metric": f"MPPI rollouts/sec ({N} samples x {H}-step horizon)", "value": r["value"], "unit": "rollouts/s",
             "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": r["ms_per_step"],
-            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32", "data": "synthetic", "full": args.full,
             "config": {"workload": f"{args.config or 'C2'}-shape MPPI problems: {N} samples x {H}-step horizon x 10 Euler "
                                    f"substeps, {E} independent envs per GPU batched in one launch"
                                    + ("" if args.config in ("C3", "C4") else " (BASELINE configs[1] shape)"),

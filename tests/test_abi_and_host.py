@@ -8,6 +8,8 @@ import numpy as np
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# the reference checkout's YAML files, stored in its own layout (settings only)
+CHECKOUT = os.path.join(ROOT, "tests", "golden", "reference_checkout")
 
 
 def declared_functions():
@@ -149,10 +151,9 @@ def test_config_defaults_match_reference_yaml_values():
         cost_vector("no_such_cost")
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Control_Toolkit_ASF"), reason="reference checkout not mounted")
 def test_reading_a_reference_checkout_reproduces_the_defaults():
     from cartpolesimulation_amd.configs import MPPIConfig, PhysicalParameters, load_reference_yaml, mppi_config_from_yaml
-    phys, cfgs = load_reference_yaml("/root/reference")
+    phys, cfgs = load_reference_yaml(CHECKOUT)
     assert phys == PhysicalParameters()
     m = mppi_config_from_yaml(cfgs, seed=None)
     d = MPPIConfig()
@@ -185,10 +186,9 @@ def test_sfc64_knots_match_the_reference_sampler(golden_dir):
     assert np.array_equal(kn[0][:4], h["du_row0"][::10]) and np.array_equal(kn[-1][:4], h["du_row3499"][::10])
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Control_Toolkit_ASF"), reason="reference checkout not mounted")
 def test_controller_reads_a_checkout():
     from cartpolesimulation_amd.controller_mpc import controller_mpc
-    c = controller_mpc("CartPole", {"target_position": 0.0}, config_root="/root/reference", config=dict(num_rollouts=512))
+    c = controller_mpc("CartPole", {"target_position": 0.0}, config_root=CHECKOUT, config=dict(num_rollouts=512))
     assert c.config_optimizer["mpc_horizon"] == 35 and c.config_optimizer["num_rollouts"] == 512
     assert c.config_optimizer["cost_function_specification"] == "quadratic_boundary_grad_minimal"
     assert c.config_optimizer["cost_weights"]["db_weight_up"] == 10000 and c.has_optimizer

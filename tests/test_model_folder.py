@@ -192,7 +192,7 @@ def test_conversion_is_pinned_to_keras():
 
 
 # ---- .keras archives (zip of config.json + model.weights.h5) read without TensorFlow / h5py ---------------------------
-REF_KERAS = "/root/reference/GymlikeCartPole/Dense-7IN-32H1-32H2-1OUT-0/Dense-7IN-32H1-32H2-1OUT-0.keras"
+REF_KERAS = os.path.join(DENSE, "Dense-7IN-32H1-32H2-1OUT-0.keras")          # the reference folder's archive, stored verbatim
 
 
 def test_hdf5_reader_round_trip():
@@ -268,7 +268,6 @@ def test_model_folder_with_a_keras_archive_of_the_gru_predictor(tmp_path):
         MF.load_gru_model(d)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_KERAS), reason="the reference checkout is not on this machine")
 def test_reference_keras_archive_equals_its_own_c_export(golden_dir):
     """The pin of the reader: the reference's in-tree model folder holds one trained network twice — as a .keras archive
     (written by Keras 2.13 / h5py) and as C arrays written by the reference's own export (C_implementation/
@@ -283,10 +282,9 @@ def test_reference_keras_archive_equals_its_own_c_export(golden_dir):
         assert np.array_equal(arrays[2 * k], gold[f"kernel{k}"]) and np.array_equal(arrays[2 * k + 1], gold[f"bias{k}"])
 
 
-REF_CKPT = "/root/reference/GymlikeCartPole/Dense-7IN-32H1-32H2-1OUT-0/ckpt.ckpt"
+REF_CKPT = os.path.join(DENSE, "ckpt.ckpt")                                     # its TensorFlow checkpoint, stored verbatim
 
 
-@pytest.mark.skipif(not os.path.exists(REF_CKPT + ".index"), reason="the reference checkout is not on this machine")
 def test_reference_tf_checkpoint_equals_its_own_c_export(golden_dir):
     """The same pin for the other container: the in-tree folder's TensorFlow checkpoint (ckpt.ckpt.index + data shard,
     written by keras.Model.save_weights, Training.py:163), read with tf_bundle_min.py, reproduces the reference's C export

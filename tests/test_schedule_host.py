@@ -223,12 +223,11 @@ def test_control_disturbance_draws_are_the_references(g):
 
 def test_active_parameters_of_a_physical_parameters_file():
     """schedule.active_parameters: which blocks of cartpole_physical_parameters.yml's `cartpole:` section change a run.  The shipped
-    file (read from the reference checkout when it is mounted) has none: updaters 'constant', informer 'ON', disturbance amplitude 0."""
+    file (tests/golden/reference_checkout/, as the reference ships it) has none: updaters 'constant', informer 'ON', disturbance amplitude 0."""
     import yaml
-    ref = "/root/reference/cartpole_physical_parameters.yml"
-    if os.path.isfile(ref):
-        with open(ref) as fh:
-            assert SC.active_parameters(yaml.safe_load(fh)["cartpole"]) is None
+    ref = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_checkout", "cartpole_physical_parameters.yml")
+    with open(ref) as fh:
+        assert SC.active_parameters(yaml.safe_load(fh)["cartpole"]) is None
     sec = dict(seed=7, controlDisturbance_mode="additive", controlDisturbance=0.0, controlBias=0.0,
                L=dict(init_value=0.395, mode="constant"), m_pole=dict(init_value=0.087, mode="constant"),
                inform_controller_about_parameters_change=dict(mode="ON"))

@@ -6,7 +6,7 @@ R=${GRAFT_REPO_ROOT:-$(pwd)}
 for MATH in fast precise; do
   OUT=$R/gpurun_out/prof_gru/run_$(date +%H%M%S)_$MATH
   mkdir -p $OUT
-  B="bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-single-env --predictor gru --envs 256 --math $MATH"
+  B="bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-single-env --predictor gru --envs 256 --math $MATH"
   timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VALU SQ_WAVE_CYCLES --output-format csv -d $OUT/pmc1 -- python3 $B > $OUT/pmc1.log 2>&1
   timeout 600 rocprofv3 --pmc SQ_VALU_MFMA_COEXEC_CYCLES SQ_ACTIVE_INST_VALU SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_INSTS_MFMA SQ_INSTS_LDS --output-format csv -d $OUT/pmc2 -- python3 $B > $OUT/pmc2.log 2>&1
   timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $B > $OUT/stats.log 2>&1
