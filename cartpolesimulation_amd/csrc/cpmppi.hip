@@ -1453,8 +1453,8 @@ int cpmppi_step_gather(cpmppi_handle* h, const cpmppi_step_args* a, float* recv_
   return cpmppi_comm::enqueue_gather(h, in_place ? a->u_nom : a->u_nom_out, recv_all, (size_t)a->E * h->cfg.H);
 }
 
-static int step_impl(cpmppi_handle* h, const cpmppi_step_args* a, void* stream, uint32_t* host_ticket,
-                     const cpmppi_comm::GatherTicket* gather) {
+// every check of a step's argument block that needs no launch (cpmppi_groups_run_gather runs them for all groups before its first)
+static int check_step(cpmppi_handle* h, const cpmppi_step_args* a) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
   if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_step: null args");
   if (a->E == 0 || a->E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_step: E out of range");
@@ -1478,6 +1478,12 @@ static int step_impl(cpmppi_handle* h, const cpmppi_step_args* a, void* stream, 
     if ((h->prm.cost_id != CPMPPI_COST_QBGM && h->prm.cost_id != CPMPPI_COST_DEFAULT) || h->prm.qb_mode != 0u)
       return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_step: the GRU predictor supports quadratic_boundary_grad_minimal and default");
   }
+  return CPMPPI_OK;
+}
+
+static int step_impl(cpmppi_handle* h, const cpmppi_step_args* a, void* stream, uint32_t* host_ticket,
+                     const cpmppi_comm::GatherTicket* gather) {
+  if (const int rc = check_step(h, a); rc != CPMPPI_OK) return rc;
   CPMPPI_ON_DEVICE(h);
   StepPtrs p{};
   p.s0 = a->s0; p.u_nom = a->u_nom; p.u_prev = a->u_prev; p.x_t = a->target_position; p.te = a->target_equilibrium;
@@ -1979,7 +1985,8 @@ int cpmppi_reward_weighted_average(cpmppi_handle* h, uint32_t E, const float* S,
   return CPMPPI_OK;
 }
 
-int cpmppi_plant_step(cpmppi_handle* h, const cpmppi_plant_args* a, void* stream) {
+// every check of a plant step's argument block that needs no launch (see check_step)
+static int check_plant(cpmppi_handle* h, const cpmppi_plant_args* a) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
   if (!a || a->E == 0 || !a->s || !a->Q || !(a->dt_sim > 0.0f)) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_plant_step: bad argument");
   const uint32_t period_steps = a->period_steps ? a->period_steps : a->n_substeps;
@@ -2024,6 +2031,13 @@ int cpmppi_plant_step(cpmppi_handle* h, const cpmppi_plant_args* a, void* stream
       misaligned(a->Q_applied_out) ||
       (a->period_dev && ((uintptr_t)a->period_dev & 7u)))
     return fail(h, CPMPPI_ERR_ALIGN, "cpmppi_plant_step: misaligned");
+  return CPMPPI_OK;
+}
+
+int cpmppi_plant_step(cpmppi_handle* h, const cpmppi_plant_args* a, void* stream) {
+  if (const int rc = check_plant(h, a); rc != CPMPPI_OK) return rc;
+  const uint32_t period_steps = a->period_steps ? a->period_steps : a->n_substeps;
+  const uint32_t save_every = a->save_every ? a->save_every : period_steps;
   CPMPPI_ON_DEVICE(h);
   Params plant = h->prm;                  // the simulated system's own pole mass (see cpmppi_set_pole_mass)
   plant.m_pole = h->plant_m_pole;
@@ -2110,3 +2124,5 @@ int cpmppi_stream_destroy(void* stream) {
 int cpmppi_internal_step_ticket(cpmppi_handle* h, const cpmppi_step_args* a, void* stream, const cpmppi_comm::GatherTicket* ticket) {
   return step_impl(h, a, stream, nullptr, ticket);
 }
+int cpmppi_internal_check_step(cpmppi_handle* h, const cpmppi_step_args* a) { return check_step(h, a); }
+int cpmppi_internal_check_plant(cpmppi_handle* h, const cpmppi_plant_args* a) { return check_plant(h, a); }

@@ -134,6 +134,7 @@ struct CommState {
   bool two_blocks = false;              // env groups share the communicator (cpmppi_groups_comm_init): see begin_step_gather
   unsigned* published = nullptr;        // 8 bytes of signal memory: steps published, watched by hipStreamWaitValue32 (NULL = fallback)
   unsigned* err_host = nullptr;         // pinned, device-mapped host word: the error flag as the host reads it
+  bool incomplete = false;              // the error was raised by poison (a period enqueued in part), not by a device-side wait
   unsigned gather_index = 0;            // step_gathers enqueued so far
   unsigned pending_post = 0;            // fallback waiter: the completion count the next post_wait_kernel has to post (0 = none)
   unsigned long long timeout_ticks = 1000000000ull;   // 10 s of the 100 MHz device clock (cpmppi_comm_set_timeout)
@@ -224,12 +225,15 @@ __global__ void delay_kernel(unsigned long long ticks) {
   while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(64);
 }
 
-// words [4..9] of the flag block: what only the kernels' slow paths read (GatherSync in cpmppi_rollout.hpp) - the signal
-// memory's address (0 = fallback waiter), the pinned error word's address, the timeout in 100 MHz ticks
+// words [4..11] of the flag block: what only the kernels' slow paths read (GatherSync in cpmppi_rollout.hpp) - the signal
+// memory's address (0 = fallback waiter), the pinned error word's address, the timeout in 100 MHz ticks, and the OTHER block's
+// address (env groups: a finalize whose wait gives up raises the error in both blocks, as every other writer of it does; 0 = one block)
 constexpr int FLAG_WORDS = 16;
 hipError_t upload_slow_path_words(CommState* c) {
-  unsigned long long w[3] = {(unsigned long long)(uintptr_t)c->published, (unsigned long long)(uintptr_t)c->err_host, c->timeout_ticks};
+  unsigned long long w[4] = {(unsigned long long)(uintptr_t)c->published, (unsigned long long)(uintptr_t)c->err_host, c->timeout_ticks,
+                             c->two_blocks ? (unsigned long long)(uintptr_t)(c->flags + FLAG_WORDS) : 0ull};
   hipError_t e = hipMemcpy(c->flags + 4, w, sizeof(w), hipMemcpyHostToDevice);
+  if (c->two_blocks) w[3] = (unsigned long long)(uintptr_t)c->flags;
   if (e == hipSuccess) e = hipMemcpy(c->flags + FLAG_WORDS + 4, w, sizeof(w), hipMemcpyHostToDevice);
   return e;
 }
@@ -440,14 +444,24 @@ int cpmppi_comm_sync(cpmppi_handle* h) {
     // nominal sequences unwritten)
     // (first everything enqueued so far runs out - with the error still up, i.e. dropping its stores; then the error words AND the
     // arrival counters are reset: a period of env groups whose launches were only partly enqueued - cpmppi_groups_run_gather
-    // returning from a failed launch - leaves a count that would never reach its total)
+    // returning from a failed launch - leaves a count that would never reach its total.  The published step numbers go back to the
+    // last gather enqueued: such a period whose steps were ALL out published a number no gather waited for, and the next period,
+    // which takes that number again, would find it published before its own envs had written)
     (void)hipDeviceSynchronize();
+    const unsigned last = c->gather_index;
     for (unsigned* blk : {c->flags, c->flags + FLAG_WORDS}) {
       (void)hipMemset(blk + 3, 0, sizeof(unsigned));
       (void)hipMemset(blk, 0, sizeof(unsigned));
+      (void)hipMemcpy(blk + 1, &last, sizeof(last), hipMemcpyHostToDevice);
     }
+    if (c->published) __atomic_store_n(reinterpret_cast<volatile unsigned*>(c->published), last, __ATOMIC_RELEASE);
     (void)hipDeviceSynchronize();
     __atomic_store_n(c->err_host, 0u, __ATOMIC_RELEASE);
+    if (c->incomplete) {
+      c->incomplete = false;
+      return cpmppi_internal_fail(h, CPMPPI_ERR_COMM, "cpmppi_comm_sync: a call failed with a period's launches enqueued in part; that "
+                                                      "period was not gathered (the gathers before it were), its arrival count is reset");
+    }
     return cpmppi_internal_fail(h, CPMPPI_ERR_COMM, "cpmppi_comm_sync: a device-side wait between a step and an all-gather timed out "
                                                     "(cpmppi_comm_set_timeout); the steps since then did not write their nominal sequences");
   }
@@ -501,6 +515,14 @@ int cpmppi_debug_comm_orphan_wait(cpmppi_handle* h) {
   COMM_HIP(h, hipStreamWaitValue32(c->side, c->published, g + 1u, hipStreamWaitValueGte, 0xFFFFFFFFu));
   COMM_HIP(h, hipStreamWriteValue32(c->side, c->flags + 2, g + 1u, 0));     // (what follows a step's wait: its gather's completion)
   c->gather_index = g + 1u;
+  return CPMPPI_OK;
+}
+// tests only: the two flag blocks as they are now ([2][16] words: [0] envs finalized, [1] steps published, [2] gathers completed,
+// [3] error, ...) - read, never written
+int cpmppi_debug_comm_flags(cpmppi_handle* h, unsigned* out) {
+  if (!h || !out || !cpmppi_internal_comm(h)) return CPMPPI_ERR_BAD_ARG;
+  OnDevice guard(cpmppi_internal_device(h));
+  COMM_HIP(h, hipMemcpy(out, cpmppi_internal_comm(h)->flags, 2 * FLAG_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost));
   return CPMPPI_OK;
 }
 // tests only: launches with more than `envs` envs get the guard kernel (~0u = never: the round-5 behaviour)
@@ -603,15 +625,16 @@ int enqueue_guard(cpmppi_handle* h, const GatherTicket& t, unsigned envs, void* 
   return CPMPPI_OK;
 }
 
-// a step-gather that could not be enqueued completely (a launch of one env group failed after others had been enqueued): the
-// communicator is put into the error state - later waits and stores are skipped, the next call is refused, cpmppi_comm_sync drains,
-// resets the arrival counters and clears
+// a step-gather that could not be enqueued completely (a launch of one env group failed after others of its period had been
+// enqueued): its arrivals stay in the counter of its parity and would make the next period of that parity publish early.  The
+// error is raised for the HOST only: the next call is refused, and cpmppi_comm_sync drains, resets the arrival counters and
+// reports.  The device words stay clear on purpose - the periods enqueued before this one are complete and run, stamp and gather
+// as usual (raising the device error from here, at some point while they run, would drop some of their stores and stamps), and
+// the launches of the incomplete period wait for nothing that is not already enqueued.
 void poison(CommState* c) {
   if (!c) return;
+  c->incomplete = true;
   __atomic_store_n(c->err_host, 1u, __ATOMIC_RELEASE);
-  const unsigned one = 1u;
-  (void)hipMemcpy(c->flags + 3, &one, sizeof(one), hipMemcpyHostToDevice);
-  (void)hipMemcpy(c->flags + FLAG_WORDS + 3, &one, sizeof(one), hipMemcpyHostToDevice);
 }
 
 int share_between_groups(CommState* c) {
@@ -620,8 +643,8 @@ int share_between_groups(CommState* c) {
   if (c->published && !(w && strcmp(w, "stream-ops") == 0)) {
     (void)hipFree(c->published);
     c->published = nullptr;
-    if (upload_slow_path_words(c) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return CPMPPI_ERR_HIP;
   }
+  if (upload_slow_path_words(c) != hipSuccess || hipDeviceSynchronize() != hipSuccess) return CPMPPI_ERR_HIP;
   return CPMPPI_OK;
 }
 

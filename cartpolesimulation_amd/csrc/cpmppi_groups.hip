@@ -35,6 +35,9 @@ struct cpmppi_groups {
   uint32_t E = 0, env_offset = 0;
   hipEvent_t ev = nullptr;                 // fork / join
   std::string err;
+  // tests only (cpmppi_debug_groups_fail): the next run makes this call of group `fail_group` in period `fail_period` fail
+  int fail_what = 0;
+  uint32_t fail_group = 0, fail_period = 0;
 };
 
 namespace {
@@ -175,6 +178,9 @@ int run_impl(cpmppi_groups* g, const cpmppi_step_args* step, const cpmppi_plant_
     return gfail(g, CPMPPI_ERR_BAD_ARG, "cpmppi_groups_run: plant->period_dev is one shared device counter; the groups count their periods from plant->period");
   const cpmppi_config& c = g->cfg;
   const size_t N = c.N, H = c.H, P = (H + c.period - 1u) / c.period + 1u;
+  const int fail_what = g->fail_what;          // (a test's injected failure serves one call)
+  g->fail_what = 0;
+  auto injected = [&](int what, size_t i, uint32_t k) { return fail_what == what && g->fail_group == i && g->fail_period == k; };
   try {
   // per-group argument blocks: the caller's, moved to the group's first env
   std::vector<cpmppi_step_args> sa(g->g.size());
@@ -211,15 +217,30 @@ int run_impl(cpmppi_groups* g, const cpmppi_step_args* step, const cpmppi_plant_
       pa[i] = b;
     }
   }
+  // Everything the argument blocks can be checked for without a launch is checked for every group BEFORE the first one: a mistake
+  // in the caller's arguments is refused with nothing enqueued (the plant's period range for the LAST period of the call included),
+  // not discovered in the middle of a period whose other launches are already out.
+  for (size_t i = 0; i < g->g.size(); ++i) {
+    cpmppi_handle* h = g->g[i].h;
+    int rc = step ? cpmppi_internal_check_step(h, &sa[i]) : CPMPPI_OK;
+    if (rc == CPMPPI_OK && plant && periods) {
+      cpmppi_plant_args last = pa[i];
+      last.period = plant->period + (periods - 1u);
+      rc = cpmppi_internal_check_plant(h, &last);
+    }
+    if (rc != CPMPPI_OK) return gfail(g, rc, std::string("cpmppi_groups_run: group ") + std::to_string(i) + ": " + cpmppi_last_error(h));
+  }
   const bool alternate = comm && step->u_nom_out && step->u_nom_out != step->u_nom;
   for (uint32_t k = 0; k < periods; ++k) {
     cpmppi_comm::GatherTicket ticket{};
     float* out_all = nullptr;
     if (comm) {
       // a device-side wait gave up (a peer stalled beyond the timeout): say so now (as cpmppi_step_gather does)
+      // (or an earlier call failed with a period enqueued in part: poison)
       if (cpmppi_comm::comm_error_pending(g->g[0].h))
-        return gfail(g, CPMPPI_ERR_COMM, "cpmppi_groups_run_gather: an earlier step's device-side wait for an all-gather timed out; "
-                                         "cpmppi_comm_sync(cpmppi_groups_handle(g, 0)) reports and clears the condition");
+        return gfail(g, CPMPPI_ERR_COMM, "cpmppi_groups_run_gather: an earlier step's device-side wait for an all-gather timed out, or an "
+                                         "earlier call failed with a period enqueued in part; cpmppi_comm_sync(cpmppi_groups_handle(g, 0)) "
+                                         "reports and clears the condition");
       // ONE ticket per period, shared by the launches of every group: the step number all envs of the device publish together
       const bool swapped = alternate && (k & 1u);
       out_all = alternate ? (swapped ? step->u_nom : step->u_nom_out) : step->u_nom;
@@ -232,32 +253,42 @@ int run_impl(cpmppi_groups* g, const cpmppi_step_args* step, const cpmppi_plant_
           sa[i].u_nom_out = out_all + off;
         }
     }
+    // Once a step launch of this period is out, its envs' arrivals sit in the period's counter and will never be complete: every
+    // failure from then on poisons the communicator (the next call is refused; cpmppi_comm_sync reports it and resets the counter).
+    // A failure before that leaves the communicator as it was.
+    bool out = false;
+    auto failed = [&](int rc, const std::string& msg) {
+      if (comm && out) cpmppi_comm::poison(comm);
+      return gfail(g, rc, msg);
+    };
     for (size_t i = 0; i < g->g.size(); ++i) {
       cpmppi_handle* h = g->g[i].h;
+      const std::string where = std::string("cpmppi_groups_run: group ") + std::to_string(i) + ": ";
       if (step) {
         sa[i].offset = step->offset + k;
         if (comm) {
-          const int rg = cpmppi_comm::enqueue_guard(g->g[0].h, ticket, g->E, g->g[i].stream);
-          if (rg != CPMPPI_OK) return gfail(g, rg, std::string("cpmppi_groups_run_gather: ") + cpmppi_last_error(g->g[0].h));
+          const int rg = injected(2, i, k) ? cpmppi_internal_fail(g->g[0].h, CPMPPI_ERR_HIP, "injected guard failure (cpmppi_debug_groups_fail)")
+                                           : cpmppi_comm::enqueue_guard(g->g[0].h, ticket, g->E, g->g[i].stream);
+          if (rg != CPMPPI_OK) return failed(rg, where + cpmppi_last_error(g->g[0].h));
         }
-        const int rc = comm ? cpmppi_internal_step_ticket(h, &sa[i], g->g[i].stream, &ticket) : cpmppi_step(h, &sa[i], g->g[i].stream);
-        if (rc != CPMPPI_OK) {
-          if (comm && i > 0) cpmppi_comm::poison(comm);      // other groups' launches of this period are out: their arrivals will never be complete
-          return gfail(g, rc, std::string("cpmppi_groups_run: group ") + std::to_string(i) + ": " + cpmppi_last_error(h));
-        }
+        const int rc = injected(1, i, k) ? cpmppi_internal_fail(h, CPMPPI_ERR_HIP, "injected step failure (cpmppi_debug_groups_fail)")
+                       : comm ? cpmppi_internal_step_ticket(h, &sa[i], g->g[i].stream, &ticket) : cpmppi_step(h, &sa[i], g->g[i].stream);
+        if (rc != CPMPPI_OK) return failed(rc, where + cpmppi_last_error(h));
+        out = true;
       }
       if (plant) {
         pa[i].period = plant->period + k;
-        const int rc = cpmppi_plant_step(h, &pa[i], g->g[i].stream);
-        if (rc != CPMPPI_OK) return gfail(g, rc, std::string("cpmppi_groups_run: group ") + std::to_string(i) + ": " + cpmppi_last_error(h));
+        const int rc = injected(3, i, k) ? cpmppi_internal_fail(h, CPMPPI_ERR_HIP, "injected plant failure (cpmppi_debug_groups_fail)")
+                                         : cpmppi_plant_step(h, &pa[i], g->g[i].stream);
+        if (rc != CPMPPI_OK) return failed(rc, where + cpmppi_last_error(h));
       }
     }
     if (comm) {
       // side stream: wait until the LAST env of the LAST group has published this step -> all-gather of the device's whole
       // u_nom[E, H] -> post its completion.  (A launch of this period that failed above has returned already: the side stream
-      // is then left without this period's wait; cpmppi_comm_sync's escape covers a step that never publishes.)
+      // is then left without this period's wait, and gathers of the periods before it run as enqueued.)
       const int rc = cpmppi_comm::enqueue_gather(g->g[0].h, out_all, recv_all, (size_t)g->E * H);
-      if (rc != CPMPPI_OK) return gfail(g, rc, std::string("cpmppi_groups_run_gather: ") + cpmppi_last_error(g->g[0].h));
+      if (rc != CPMPPI_OK) return failed(rc, std::string("cpmppi_groups_run_gather: ") + cpmppi_last_error(g->g[0].h));
     }
   }
   return CPMPPI_OK;
@@ -279,6 +310,14 @@ int cpmppi_groups_run_gather(cpmppi_groups* g, const cpmppi_step_args* step, con
   if (!g) return CPMPPI_ERR_BAD_ARG;
   if (!recv_all) return gfail(g, CPMPPI_ERR_BAD_ARG, "cpmppi_groups_run_gather: recv_all is required");
   return run_impl(g, step, plant, periods, recv_all);
+}
+
+// tests only (not in cpmppi.h): the next cpmppi_groups_run(_gather) call fails at group `group`'s step (what = 1), gather guard (2)
+// or plant step (3) call of its period `period` - as a HIP launch error there would (0 = off)
+int cpmppi_debug_groups_fail(cpmppi_groups* g, int what, uint32_t group, uint32_t period) {
+  if (!g || what < 0 || what > 3) return CPMPPI_ERR_BAD_ARG;
+  g->fail_what = what; g->fail_group = group; g->fail_period = period;
+  return CPMPPI_OK;
 }
 
 // ONE communicator and ONE side stream for all env groups of the device; it lives in group 0's handle (cpmppi_comm_* calls take

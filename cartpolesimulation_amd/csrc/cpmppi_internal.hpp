@@ -21,13 +21,16 @@ int share_between_groups(CommState* c);      // the communicator serves env grou
 void abort_step_gather(CommState* c);
 int enqueue_gather(cpmppi_handle* h, const float* send, float* recv_all, size_t count);
 int enqueue_guard(cpmppi_handle* h, const GatherTicket& t, unsigned envs, void* stream);   // launch stream: gather_guard_kernel (many envs only)
-void poison(CommState* c);                   // a partly enqueued step-gather: error state until cpmppi_comm_sync
-int comm_error_pending(cpmppi_handle* h);    // a device-side wait of this handle has timed out (sticky until cpmppi_comm_sync)
+void poison(CommState* c);                   // a partly enqueued step-gather: error state until cpmppi_comm_sync (which resets the counters)
+int comm_error_pending(cpmppi_handle* h);    // a device-side wait timed out or a step-gather was poisoned (sticky until cpmppi_comm_sync)
 }  // namespace cpmppi_comm
 
 cpmppi_comm::CommState*& cpmppi_internal_comm(cpmppi_handle* h);
 // cpmppi_step whose finalize takes part in a step-gather described by `ticket` (cpmppi_step_gather; cpmppi_groups_run_gather, where
 // the ticket is shared by the launches of every group)
 int cpmppi_internal_step_ticket(cpmppi_handle* h, const cpmppi_step_args* a, void* stream, const cpmppi_comm::GatherTicket* ticket);
+// the checks cpmppi_step / cpmppi_plant_step make before they launch anything (CPMPPI_OK, or the error with the handle's message set)
+int cpmppi_internal_check_step(cpmppi_handle* h, const cpmppi_step_args* a);
+int cpmppi_internal_check_plant(cpmppi_handle* h, const cpmppi_plant_args* a);
 int cpmppi_internal_device(const cpmppi_handle* h);
 int cpmppi_internal_fail(cpmppi_handle* h, int code, const std::string& msg);

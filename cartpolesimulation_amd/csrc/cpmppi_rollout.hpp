@@ -68,12 +68,13 @@ struct GatherSync {
   uint32_t* flags;          // NULL = no gather follows this step.  The block also holds what only the slow paths need, so that
                             // the kernel argument stays four words: [4,5] pointer to the signal memory the side stream's
                             // hipStreamWaitValue32 watches (0: the waiter kernel polls flags[1]), [6,7] pointer to the pinned
-                            // host word that mirrors the error, [8,9] the 100 MHz ticks a wait may last (~0 = for ever)
+                            // host word that mirrors the error, [8,9] the 100 MHz ticks a wait may last (~0 = for ever), [10,11]
+                            // pointer to the communicator's other flag block (env groups; 0: none)
   uint32_t publish;         // the step number every env of this launch publishes once its nominal sequence is written
   uint32_t need;            // flags[2] must have reached this before the output buffer may be overwritten (0 = no wait)
   uint32_t envs;            // envs in this launch
 };
-constexpr int GS_PUBLISHED = 4, GS_ERR_HOST = 6, GS_TIMEOUT = 8, GS_WORDS = 16;
+constexpr int GS_PUBLISHED = 4, GS_ERR_HOST = 6, GS_TIMEOUT = 8, GS_OTHER = 10, GS_WORDS = 16;
 __device__ __forceinline__ uint64_t gs_word64(const uint32_t* flags, int i) {
   return (uint64_t)flags[i] | ((uint64_t)flags[i + 1] << 32);
 }
@@ -81,6 +82,7 @@ __device__ __forceinline__ uint64_t gs_word64(const uint32_t* flags, int i) {
 // flag >= need (wrap-safe), polled with system-scope loads (the side stream's hipStreamWriteValue32 is a write of the command
 // processor: not through this XCD's L2).  Returns false - after raising the error for device and host - when the wait
 // outlasts `timeout_ticks` or the error is already up: the caller then does NOT proceed to the stores the wait guards.
+// (Env groups: the error goes into BOTH flag blocks, so that the next step - of the other parity - drops its stores too.)
 __device__ __forceinline__ bool spin_until_reached(uint32_t* flag, uint32_t need, const GatherSync& gs) {
   uint32_t* err = gs.flags + 3;
   if ((int32_t)(__hip_atomic_load(flag, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_SYSTEM) - need) >= 0)
@@ -93,6 +95,8 @@ __device__ __forceinline__ bool spin_until_reached(uint32_t* flag, uint32_t need
     if (__hip_atomic_load(err, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) return false;
     if (__builtin_amdgcn_s_memrealtime() - t0 > gs_word64(gs.flags, GS_TIMEOUT)) {
       __hip_atomic_store(err, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      uint32_t* other = reinterpret_cast<uint32_t*>(gs_word64(gs.flags, GS_OTHER));
+      if (other) __hip_atomic_store(other + 3, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       uint32_t* err_host = reinterpret_cast<uint32_t*>(gs_word64(gs.flags, GS_ERR_HOST));
       if (err_host) __hip_atomic_store(err_host, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
       return false;

@@ -172,11 +172,20 @@ class NativeGather:
         cpmppi_step_gather per step since the communicator was made) and is complete; a False entry = a stale block to be ignored."""
         return self.stamps(i) == int(i + 1 if gather_number is None else gather_number)
 
+    def _events_only(self):
+        # the event-ordered gather sends count = E_local*H floats per rank; a stamped communicator's receive rows are
+        # E_local*H + GATHER_STAMP_FLOATS wide, so rows >= 1 and every stamp would land in the wrong place
+        if self.stamped:
+            raise ValueError("before_step / after_step (event-ordered gathers) need an unstamped NativeGather: stamped blocks come "
+                             "from cpmppi_step_gather only")
+
     def before_step(self, i):
+        self._events_only()
         e = self.engine
         e._check(e.lib.cpmppi_comm_wait(e._h, (i + 1) & 1, e._stream()))       # gather i-2 read the buffer step i writes
 
     def after_step(self, i):
+        self._events_only()
         e = self.engine
         b = (i + 1) & 1
         e._check(e.lib.cpmppi_comm_gather(e._h, b, self.u[b].data_ptr(), self.gathered[b].data_ptr(), e.E * e.H, e._stream()))

@@ -597,6 +597,17 @@ int cpmppi_stream_destroy(void* stream);
  *                          step->u_nom_out given, the two buffers alternate per period of the call (period 0 reads u_nom and writes
  *                          u_nom_out, period 1 the other way round, ...); NULL = in place.  recv_all holds the LAST period's gather
  *                          once cpmppi_comm_sync(cpmppi_groups_handle(g, 0)) has returned.
+ *                          Failures: (a) what the argument blocks can be checked for without a launch - every group's step and plant
+ *                          arguments, the plant period of the call's LAST period against ctrl_rows - is checked before the first
+ *                          launch: CPMPPI_ERR_BAD_ARG / _ALIGN with nothing enqueued and the communicator untouched.  (b) A failure in
+ *                          period k before any step launch of that period is out (group 0's guard or step call) returns its code;
+ *                          periods 0..k-1 are enqueued complete and gathered, the communicator stays usable.  (c) A failure once a step
+ *                          launch of period k is out (any later call of that period) returns its code and POISONS the communicator:
+ *                          periods 0..k-1 still run, stamp and gather as usual, period k is not gathered, the next
+ *                          cpmppi_groups_run_gather returns CPMPPI_ERR_COMM, and cpmppi_comm_sync returns CPMPPI_ERR_COMM once,
+ *                          after resetting the arrival counters and published step numbers that period left behind.  Some groups
+ *                          may have run period k: prepare the buffers again before going on.  (d) A device-side wait that times out
+ *                          drops the store of its step and of every later step of either parity, as for cpmppi_step_gather.
  * Errors as for the single-handle calls; text in cpmppi_groups_last_error. */
 typedef struct cpmppi_groups cpmppi_groups;
 int cpmppi_groups_create(const cpmppi_config* cfg, int device, uint32_t groups, uint32_t env_offset, cpmppi_groups** out);
