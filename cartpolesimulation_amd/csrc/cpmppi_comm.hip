@@ -301,37 +301,24 @@ void begin_step_gather(CommState* c, const float* out_buffer, GatherTicket* out)
 }
 void abort_step_gather(CommState*) {}
 
-struct OnDevice {                       // (the handle's device for the duration of a call; the caller's restored after)
-  int prev = -1;
-  bool switched = false;
-  explicit OnDevice(int dev) {
-    if (hipGetDevice(&prev) == hipSuccess && prev != dev) switched = (hipSetDevice(dev) == hipSuccess);
-  }
-  ~OnDevice() { if (switched) (void)hipSetDevice(prev); }
-};
-
 }  // namespace cpmppi_comm
 
 using namespace cpmppi_comm;
 
-#define COMM_HIP(h, call)                                                                                  \
-  do {                                                                                                     \
-    hipError_t e_ = (call);                                                                                \
-    if (e_ != hipSuccess)                                                                                  \
-      return cpmppi_internal_fail((h), CPMPPI_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); \
-  } while (0)
+// (a HIP call's error: CPMPPI_HIP, cpmppi_internal.hpp; every call runs on the handle's device: DeviceGuard, whose own
+// hipSetDevice error these calls leave unchecked)
 #define COMM_NCCL(h, call)                                                                                      \
   do {                                                                                                          \
     ncclResult_t r_ = (call);                                                                                   \
     if (r_ != ncclSuccess)                                                                                      \
-      return cpmppi_internal_fail((h), CPMPPI_ERR_COMM, std::string(#call) + ": " + g_rccl.GetErrorString(r_)); \
+      return fail((h), CPMPPI_ERR_COMM, std::string(#call) + ": " + g_rccl.GetErrorString(r_));                 \
   } while (0)
 
 extern "C" {
 
 int cpmppi_comm_unique_id(void* id_out, const char* rccl_path) {
-  if (!id_out) return cpmppi_internal_fail(nullptr, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_unique_id: null argument");
-  if (!load_rccl(rccl_path)) return cpmppi_internal_fail(nullptr, CPMPPI_ERR_COMM, g_rccl.err);
+  if (!id_out) return fail(nullptr, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_unique_id: null argument");
+  if (!load_rccl(rccl_path)) return fail(nullptr, CPMPPI_ERR_COMM, g_rccl.err);
   static_assert(sizeof(ncclUniqueId) == CPMPPI_COMM_ID_BYTES, "ncclUniqueId size");
   ncclUniqueId id;
   COMM_NCCL(nullptr, g_rccl.GetUniqueId(&id));
@@ -342,10 +329,10 @@ int cpmppi_comm_unique_id(void* id_out, const char* rccl_path) {
 int cpmppi_comm_init(cpmppi_handle* h, const void* id, int world, int rank, const char* rccl_path) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
   if (!id || world < 1 || rank < 0 || rank >= world)
-    return cpmppi_internal_fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_init: bad argument");
-  if (cpmppi_internal_comm(h)) return cpmppi_internal_fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_init: this handle has a communicator");
-  if (!load_rccl(rccl_path)) return cpmppi_internal_fail(h, CPMPPI_ERR_COMM, g_rccl.err);
-  OnDevice guard(cpmppi_internal_device(h));
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_init: bad argument");
+  if (h->comm) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_init: this handle has a communicator");
+  if (!load_rccl(rccl_path)) return fail(h, CPMPPI_ERR_COMM, g_rccl.err);
+  DeviceGuard guard(h->device);
   CommState* c = new CommState();
   c->world = world; c->rank = rank;
   ncclUniqueId uid;
@@ -354,7 +341,7 @@ int cpmppi_comm_init(cpmppi_handle* h, const void* id, int world, int rank, cons
   if (r != ncclSuccess) {
     c->comm = nullptr;
     destroy(c);
-    return cpmppi_internal_fail(h, CPMPPI_ERR_COMM, std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(r));
+    return fail(h, CPMPPI_ERR_COMM, std::string("ncclCommInitRank: ") + g_rccl.GetErrorString(r));
   }
   int lo = 0, hi = 0;
   hipError_t e = hipDeviceGetStreamPriorityRange(&lo, &hi);          // hi = the numerically lowest = greatest priority
@@ -381,7 +368,7 @@ int cpmppi_comm_init(cpmppi_handle* h, const void* id, int world, int rank, cons
     int can = 0;
     const char* w = getenv("CPMPPI_COMM_WAITER");
     const bool stream_ops = w && strcmp(w, "stream-ops") == 0;
-    if (stream_ops && hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, cpmppi_internal_device(h)) == hipSuccess && can == 1) {
+    if (stream_ops && hipDeviceGetAttribute(&can, hipDeviceAttributeCanUseStreamWaitValue, h->device) == hipSuccess && can == 1) {
       if (hipExtMallocWithFlags((void**)&c->published, 8, hipMallocSignalMemory) == hipSuccess) {
         *reinterpret_cast<volatile unsigned long long*>(c->published) = 0ull;
       } else {
@@ -394,47 +381,47 @@ int cpmppi_comm_init(cpmppi_handle* h, const void* id, int world, int rank, cons
   if (e == hipSuccess) e = hipDeviceSynchronize();
   if (e != hipSuccess) {
     destroy(c);
-    return cpmppi_internal_fail(h, CPMPPI_ERR_HIP, std::string("cpmppi_comm_init: ") + hipGetErrorString(e));
+    return fail(h, CPMPPI_ERR_HIP, std::string("cpmppi_comm_init: ") + hipGetErrorString(e));
   }
-  cpmppi_internal_comm(h) = c;
+  h->comm = c;
   return CPMPPI_OK;
 }
 
 int cpmppi_comm_gather(cpmppi_handle* h, uint32_t slot, const float* send, float* recv_all, size_t count, void* stream) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
-  CommState* c = cpmppi_internal_comm(h);
-  if (!c) return cpmppi_internal_fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_gather: no communicator (cpmppi_comm_init)");
+  CommState* c = h->comm;
+  if (!c) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_gather: no communicator (cpmppi_comm_init)");
   if (slot >= (uint32_t)SLOTS || !send || !recv_all || count == 0)
-    return cpmppi_internal_fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_gather: bad argument");
-  OnDevice guard(cpmppi_internal_device(h));
-  COMM_HIP(h, hipEventRecord(c->ready, (hipStream_t)stream));
-  COMM_HIP(h, hipStreamWaitEvent(c->side, c->ready, 0));
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_gather: bad argument");
+  DeviceGuard guard(h->device);
+  CPMPPI_HIP(h, hipEventRecord(c->ready, (hipStream_t)stream));
+  CPMPPI_HIP(h, hipStreamWaitEvent(c->side, c->ready, 0));
   COMM_NCCL(h, g_rccl.AllGather(send, recv_all, count, ncclFloat, c->comm, c->side));
-  COMM_HIP(h, hipEventRecord(c->done[slot], c->side));
+  CPMPPI_HIP(h, hipEventRecord(c->done[slot], c->side));
   c->pending[slot] = true;
   return CPMPPI_OK;
 }
 
 int cpmppi_comm_wait(cpmppi_handle* h, uint32_t slot, void* stream) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
-  CommState* c = cpmppi_internal_comm(h);
-  if (!c || slot >= (uint32_t)SLOTS) return cpmppi_internal_fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_wait: bad argument");
+  CommState* c = h->comm;
+  if (!c || slot >= (uint32_t)SLOTS) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_wait: bad argument");
   if (!c->pending[slot]) return CPMPPI_OK;
-  OnDevice guard(cpmppi_internal_device(h));
-  COMM_HIP(h, hipStreamWaitEvent((hipStream_t)stream, c->done[slot], 0));
+  DeviceGuard guard(h->device);
+  CPMPPI_HIP(h, hipStreamWaitEvent((hipStream_t)stream, c->done[slot], 0));
   c->pending[slot] = false;
   return CPMPPI_OK;
 }
 
 int cpmppi_comm_sync(cpmppi_handle* h) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
-  CommState* c = cpmppi_internal_comm(h);
+  CommState* c = h->comm;
   if (!c) return CPMPPI_OK;
-  OnDevice guard(cpmppi_internal_device(h));
+  DeviceGuard guard(h->device);
   if (c->pending_post != 0u) {          // fallback waiter: the last gather's completion has not been posted yet
     hipLaunchKernelGGL(post_wait_kernel, dim3(1), dim3(1), 0, c->side, c->flags, c->two_blocks ? c->flags + FLAG_WORDS : nullptr,
                        c->pending_post, 0u, c->err_host, c->timeout_ticks, (unsigned*)nullptr);
-    COMM_HIP(h, hipGetLastError());
+    CPMPPI_HIP(h, hipGetLastError());
     c->pending_post = 0u;
   }
   (void)drain_side_stream(c);          // (bounded: a side stream still waiting for a step that never publishes is released, with the error raised)
@@ -459,32 +446,32 @@ int cpmppi_comm_sync(cpmppi_handle* h) {
     __atomic_store_n(c->err_host, 0u, __ATOMIC_RELEASE);
     if (c->incomplete) {
       c->incomplete = false;
-      return cpmppi_internal_fail(h, CPMPPI_ERR_COMM, "cpmppi_comm_sync: a call failed with a period's launches enqueued in part; that "
-                                                      "period was not gathered (the gathers before it were), its arrival count is reset");
+      return fail(h, CPMPPI_ERR_COMM, "cpmppi_comm_sync: a call failed with a period's launches enqueued in part; that "
+                                      "period was not gathered (the gathers before it were), its arrival count is reset");
     }
-    return cpmppi_internal_fail(h, CPMPPI_ERR_COMM, "cpmppi_comm_sync: a device-side wait between a step and an all-gather timed out "
-                                                    "(cpmppi_comm_set_timeout); the steps since then did not write their nominal sequences");
+    return fail(h, CPMPPI_ERR_COMM, "cpmppi_comm_sync: a device-side wait between a step and an all-gather timed out "
+                                    "(cpmppi_comm_set_timeout); the steps since then did not write their nominal sequences");
   }
   return CPMPPI_OK;
 }
 
 int cpmppi_comm_set_timeout(cpmppi_handle* h, double seconds) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
-  CommState* c = cpmppi_internal_comm(h);
-  if (!c) return cpmppi_internal_fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_set_timeout: no communicator (cpmppi_comm_init)");
-  if (!(seconds == seconds)) return cpmppi_internal_fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_set_timeout: not a number");
+  CommState* c = h->comm;
+  if (!c) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_set_timeout: no communicator (cpmppi_comm_init)");
+  if (!(seconds == seconds)) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_set_timeout: not a number");
   c->timeout_ticks = (seconds <= 0.0 || seconds > 1.0e9) ? ~0ull : (unsigned long long)(seconds * 1.0e8 + 0.5);
-  OnDevice guard(cpmppi_internal_device(h));
-  COMM_HIP(h, upload_slow_path_words(c));          // (a synchronous copy: launches already enqueued keep the old value)
+  DeviceGuard guard(h->device);
+  CPMPPI_HIP(h, upload_slow_path_words(c));          // (a synchronous copy: launches already enqueued keep the old value)
   return CPMPPI_OK;
 }
 
 int cpmppi_comm_set_stamped(cpmppi_handle* h, int on) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
-  CommState* c = cpmppi_internal_comm(h);
-  if (!c) return cpmppi_internal_fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_set_stamped: no communicator (cpmppi_comm_init)");
+  CommState* c = h->comm;
+  if (!c) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_set_stamped: no communicator (cpmppi_comm_init)");
   if (c->gather_index != 0u && (on != 0) != c->stamped)
-    return cpmppi_internal_fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_set_stamped: the block layout cannot change once a step has been gathered");
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_set_stamped: the block layout cannot change once a step has been gathered");
   c->stamped = on != 0;
   return CPMPPI_OK;
 }
@@ -492,55 +479,55 @@ int cpmppi_comm_set_stamped(cpmppi_handle* h, int on) {
 // tests only (not in cpmppi.h): every later all-gather of cpmppi_step_gather is preceded by a spin of `microseconds` on the side
 // stream - a peer that joins the collective late
 int cpmppi_debug_comm_delay(cpmppi_handle* h, unsigned microseconds) {
-  if (!h || !cpmppi_internal_comm(h)) return CPMPPI_ERR_BAD_ARG;
-  cpmppi_internal_comm(h)->debug_delay_us = microseconds;
+  if (!h || !h->comm) return CPMPPI_ERR_BAD_ARG;
+  h->comm->debug_delay_us = microseconds;
   return CPMPPI_OK;
 }
 // tests only: the side stream is made to wait for a step that NO launch will ever publish (what a failed or aborted rollout
 // launch leaves behind) - cpmppi_comm_sync / cpmppi_comm_destroy must get out of it
 int cpmppi_debug_comm_orphan_wait(cpmppi_handle* h) {
-  if (!h || !cpmppi_internal_comm(h)) return CPMPPI_ERR_BAD_ARG;
-  CommState* c = cpmppi_internal_comm(h);
-  OnDevice guard(cpmppi_internal_device(h));
+  if (!h || !h->comm) return CPMPPI_ERR_BAD_ARG;
+  CommState* c = h->comm;
+  DeviceGuard guard(h->device);
   const unsigned g = c->gather_index;
   if (!c->published) {
     // the kernel form: the waiter gives up BY ITSELF after the handle's timeout and raises the error (no host-side escape needed)
     hipLaunchKernelGGL(post_wait_kernel, dim3(1), dim3(1), 0, c->side, c->flags, c->two_blocks ? c->flags + FLAG_WORDS : nullptr, c->pending_post,
                        g + 1u, c->err_host, c->timeout_ticks, (unsigned*)nullptr);
-    COMM_HIP(h, hipGetLastError());
+    CPMPPI_HIP(h, hipGetLastError());
     c->pending_post = g + 1u;
     c->gather_index = g + 1u;
     return CPMPPI_OK;
   }
-  COMM_HIP(h, hipStreamWaitValue32(c->side, c->published, g + 1u, hipStreamWaitValueGte, 0xFFFFFFFFu));
-  COMM_HIP(h, hipStreamWriteValue32(c->side, c->flags + 2, g + 1u, 0));     // (what follows a step's wait: its gather's completion)
+  CPMPPI_HIP(h, hipStreamWaitValue32(c->side, c->published, g + 1u, hipStreamWaitValueGte, 0xFFFFFFFFu));
+  CPMPPI_HIP(h, hipStreamWriteValue32(c->side, c->flags + 2, g + 1u, 0));     // (what follows a step's wait: its gather's completion)
   c->gather_index = g + 1u;
   return CPMPPI_OK;
 }
 // tests only: the two flag blocks as they are now ([2][16] words: [0] envs finalized, [1] steps published, [2] gathers completed,
 // [3] error, ...) - read, never written
 int cpmppi_debug_comm_flags(cpmppi_handle* h, unsigned* out) {
-  if (!h || !out || !cpmppi_internal_comm(h)) return CPMPPI_ERR_BAD_ARG;
-  OnDevice guard(cpmppi_internal_device(h));
-  COMM_HIP(h, hipMemcpy(out, cpmppi_internal_comm(h)->flags, 2 * FLAG_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost));
+  if (!h || !out || !h->comm) return CPMPPI_ERR_BAD_ARG;
+  DeviceGuard guard(h->device);
+  CPMPPI_HIP(h, hipMemcpy(out, h->comm->flags, 2 * FLAG_WORDS * sizeof(unsigned), hipMemcpyDeviceToHost));
   return CPMPPI_OK;
 }
 // tests only: launches with more than `envs` envs get the guard kernel (~0u = never: the round-5 behaviour)
 int cpmppi_debug_comm_guard_min_envs(cpmppi_handle* h, unsigned envs) {
-  if (!h || !cpmppi_internal_comm(h)) return CPMPPI_ERR_BAD_ARG;
-  cpmppi_internal_comm(h)->guard_min_envs = envs;
+  if (!h || !h->comm) return CPMPPI_ERR_BAD_ARG;
+  h->comm->guard_min_envs = envs;
   return CPMPPI_OK;
 }
 // tests only: 1 = stream memory operations order the side stream, 0 = the fallback waiter kernel
 int cpmppi_debug_comm_mode(cpmppi_handle* h) {
-  if (!h || !cpmppi_internal_comm(h)) return CPMPPI_ERR_BAD_ARG;
-  return cpmppi_internal_comm(h)->published ? 1 : 0;
+  if (!h || !h->comm) return CPMPPI_ERR_BAD_ARG;
+  return h->comm->published ? 1 : 0;
 }
 
 int cpmppi_comm_get_info(cpmppi_handle* h, cpmppi_comm_info* out) {
   if (!h || !out) return CPMPPI_ERR_BAD_ARG;
-  CommState* c = cpmppi_internal_comm(h);
-  if (!c) return cpmppi_internal_fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_get_info: no communicator (cpmppi_comm_init)");
+  CommState* c = h->comm;
+  if (!c) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_comm_get_info: no communicator (cpmppi_comm_init)");
   memset(out, 0, sizeof(*out));
   out->world = (uint32_t)c->world; out->rank = (uint32_t)c->rank;
   out->rccl_ranks = out->rccl_rank = -1;
@@ -556,9 +543,9 @@ int cpmppi_comm_get_info(cpmppi_handle* h, cpmppi_comm_info* out) {
 
 int cpmppi_comm_destroy(cpmppi_handle* h) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
-  CommState*& c = cpmppi_internal_comm(h);
+  CommState*& c = h->comm;
   if (c) {
-    OnDevice guard(cpmppi_internal_device(h));
+    DeviceGuard guard(h->device);
     destroy(c);
     c = nullptr;
   }
@@ -570,35 +557,35 @@ int cpmppi_comm_destroy(cpmppi_handle* h) {
 namespace cpmppi_comm {
 
 int comm_error_pending(cpmppi_handle* h) {
-  CommState* c = cpmppi_internal_comm(h);
+  CommState* c = h->comm;
   return (c && __atomic_load_n(c->err_host, __ATOMIC_ACQUIRE) != 0u) ? 1 : 0;
 }
 
 int enqueue_gather(cpmppi_handle* h, const float* send, float* recv_all, size_t count) {
-  CommState* c = cpmppi_internal_comm(h);
-  OnDevice guard(cpmppi_internal_device(h));
+  CommState* c = h->comm;
+  DeviceGuard guard(h->device);
   const unsigned g = c->gather_index;
   unsigned* other = c->two_blocks ? c->flags + FLAG_WORDS : nullptr;
   unsigned* stamp = c->stamped ? reinterpret_cast<unsigned*>(const_cast<float*>(send) + count) : nullptr;
   if (c->published) {
-    COMM_HIP(h, hipStreamWaitValue32(c->side, c->published, g + 1u, hipStreamWaitValueGte, 0xFFFFFFFFu));
+    CPMPPI_HIP(h, hipStreamWaitValue32(c->side, c->published, g + 1u, hipStreamWaitValueGte, 0xFFFFFFFFu));
     if (stamp) {                        // (right behind the wait: the step has just been published)
       hipLaunchKernelGGL(stamp_kernel, dim3(1), dim3(1), 0, c->side, c->flags, other, stamp, g + 1u);
-      COMM_HIP(h, hipGetLastError());
+      CPMPPI_HIP(h, hipGetLastError());
     }
   } else {
     hipLaunchKernelGGL(post_wait_kernel, dim3(1), dim3(1), 0, c->side, c->flags, other, c->pending_post, g + 1u, c->err_host, c->timeout_ticks, stamp);
-    COMM_HIP(h, hipGetLastError());
+    CPMPPI_HIP(h, hipGetLastError());
     c->pending_post = 0u;
   }
   if (c->debug_delay_us) {
     hipLaunchKernelGGL(delay_kernel, dim3(1), dim3(1), 0, c->side, (unsigned long long)c->debug_delay_us * 100ull);
-    COMM_HIP(h, hipGetLastError());
+    CPMPPI_HIP(h, hipGetLastError());
   }
   COMM_NCCL(h, g_rccl.AllGather(send, recv_all, count + (c->stamped ? CPMPPI_GATHER_STAMP_FLOATS : 0), ncclFloat, c->comm, c->side));
   if (c->published) {
-    COMM_HIP(h, hipStreamWriteValue32(c->side, c->flags + 2, g + 1u, 0));
-    if (other) COMM_HIP(h, hipStreamWriteValue32(c->side, other + 2, g + 1u, 0));
+    CPMPPI_HIP(h, hipStreamWriteValue32(c->side, c->flags + 2, g + 1u, 0));
+    if (other) CPMPPI_HIP(h, hipStreamWriteValue32(c->side, other + 2, g + 1u, 0));
   } else {
     c->pending_post = g + 1u;          // posted by the next step's post_wait_kernel, or by cpmppi_comm_sync
   }
@@ -616,12 +603,12 @@ int enqueue_gather(cpmppi_handle* h, const float* send, float* recv_all, size_t 
 // (One handle, one kernel in flight at a time: the stream-operation form stays, 76.3 vs 74.3 us.)
 // see gather_guard_kernel.  `envs`: the envs whose finalizing blocks would wait (of the launch; of all groups' launches together)
 int enqueue_guard(cpmppi_handle* h, const GatherTicket& t, unsigned envs, void* stream) {
-  CommState* c = cpmppi_internal_comm(h);
+  CommState* c = h->comm;
   if (!c || t.need == 0u || envs <= c->guard_min_envs) return CPMPPI_OK;
-  OnDevice guard(cpmppi_internal_device(h));
+  DeviceGuard guard(h->device);
   unsigned* other = c->two_blocks ? (t.flags == c->flags ? c->flags + FLAG_WORDS : c->flags) : nullptr;
   hipLaunchKernelGGL(gather_guard_kernel, dim3(1), dim3(1), 0, (hipStream_t)stream, t.flags, other, t.need, c->err_host, c->timeout_ticks);
-  COMM_HIP(h, hipGetLastError());
+  CPMPPI_HIP(h, hipGetLastError());
   return CPMPPI_OK;
 }
 

@@ -1155,7 +1155,7 @@ __device__ __forceinline__ QbgmFolded make_qbgm_folded(const Params& p, float te
 }
 
 // Everything the throughput build's rollout kernel derives from (Params, L[env], target_equilibrium[env], s0[env]) alone, formed
-// ONCE per env by fold_env_kernel (cpmppi.hip) instead of once per WAVE in the rollout kernel's prologue: ~300 vector instructions
+// ONCE per env by fold_env_kernel (cpmppi.hip, the hot-path unit) instead of once per WAVE in the rollout kernel's prologue: ~300 vector instructions
 // (double-precision folds, two IEEE divides, libm cosf) per wave of 128 rollouts = 1.5 % of the launch, read back with scalar loads.
 // Same device functions, same values.  136 bytes per env.
 struct EnvFold {
@@ -1166,6 +1166,11 @@ struct EnvFold {
   float nearlim;        // min(permissible_track_fraction, 1) * THL: below it quadratic_boundary_grad_minimal's boundary term is zero
 };
 static_assert(sizeof(EnvFold) == 136, "EnvFold: 34 words per env");
+
+// The GRU predictor's input / output normalisation (cpmppi_gru.hpp); here because the handle holds one by value.
+struct GruNorm {         // normalised = x*scale + shift ; order Q, angleD, angle_cos, angle_sin, position, positionD
+  float in_scale[6], in_shift[6], out_scale[5], out_shift[5];
+};
 
 // quadratic_boundary_grad_minimal's stage cost AND the MPPI correction term of one stage added to two running sums (FAST path of
 // the rollout kernel).  Same terms as stage_qbgm + mppi_correction; what differs is the grouping: every term is accumulated

@@ -62,15 +62,13 @@ const char* cpmppi_groups_last_error(const cpmppi_groups* g) { return g ? g->err
 
 void cpmppi_groups_destroy(cpmppi_groups* g) {
   if (!g) return;
-  int prev = -1;
-  const bool sw = hipGetDevice(&prev) == hipSuccess && prev != g->device && hipSetDevice(g->device) == hipSuccess;
+  DeviceGuard guard(g->device);
   for (auto& x : g->g) {
     if (x.stream) (void)hipStreamSynchronize(x.stream);
     if (x.h) cpmppi_destroy(x.h);
     if (x.stream) (void)cpmppi_stream_destroy(x.stream);
   }
   if (g->ev) (void)hipEventDestroy(g->ev);
-  if (sw) (void)hipSetDevice(prev);
   delete g;
 }
 
@@ -107,10 +105,8 @@ int cpmppi_groups_create(const cpmppi_config* cfg, int device, uint32_t groups, 
     }
     e0 += x.n;
   }
-  int prev = -1;
-  const bool sw = hipGetDevice(&prev) == hipSuccess && prev != device && hipSetDevice(device) == hipSuccess;
+  DeviceGuard guard(device);
   const hipError_t e = hipEventCreateWithFlags(&g->ev, hipEventDisableTiming);
-  if (sw) (void)hipSetDevice(prev);
   if (e != hipSuccess) {
     cpmppi_groups_destroy(g);
     return gfail(nullptr, CPMPPI_ERR_HIP, std::string("cpmppi_groups_create: hipEventCreate: ") + hipGetErrorString(e));
@@ -164,7 +160,7 @@ int run_impl(cpmppi_groups* g, const cpmppi_step_args* step, const cpmppi_plant_
   cpmppi_comm::CommState* comm = nullptr;
   if (recv_all) {
     if (!step) return gfail(g, CPMPPI_ERR_BAD_ARG, "cpmppi_groups_run_gather: a step argument block is required");
-    comm = cpmppi_internal_comm(g->g[0].h);
+    comm = g->g[0].h->comm;
     if (!comm) return gfail(g, CPMPPI_ERR_BAD_ARG, "cpmppi_groups_run_gather: no communicator (cpmppi_groups_comm_init)");
     if (step->predictor == CPMPPI_PREDICTOR_GRU && step->u_nom_out && step->u_nom_out != step->u_nom)
       return gfail(g, CPMPPI_ERR_BAD_ARG, "cpmppi_groups_run_gather: the GRU predictor steps in place");
@@ -222,11 +218,11 @@ int run_impl(cpmppi_groups* g, const cpmppi_step_args* step, const cpmppi_plant_
   // not discovered in the middle of a period whose other launches are already out.
   for (size_t i = 0; i < g->g.size(); ++i) {
     cpmppi_handle* h = g->g[i].h;
-    int rc = step ? cpmppi_internal_check_step(h, &sa[i]) : CPMPPI_OK;
+    int rc = step ? check_step(h, &sa[i]) : CPMPPI_OK;
     if (rc == CPMPPI_OK && plant && periods) {
       cpmppi_plant_args last = pa[i];
       last.period = plant->period + (periods - 1u);
-      rc = cpmppi_internal_check_plant(h, &last);
+      rc = check_plant(h, &last);
     }
     if (rc != CPMPPI_OK) return gfail(g, rc, std::string("cpmppi_groups_run: group ") + std::to_string(i) + ": " + cpmppi_last_error(h));
   }
@@ -267,18 +263,18 @@ int run_impl(cpmppi_groups* g, const cpmppi_step_args* step, const cpmppi_plant_
       if (step) {
         sa[i].offset = step->offset + k;
         if (comm) {
-          const int rg = injected(2, i, k) ? cpmppi_internal_fail(g->g[0].h, CPMPPI_ERR_HIP, "injected guard failure (cpmppi_debug_groups_fail)")
+          const int rg = injected(2, i, k) ? fail(g->g[0].h, CPMPPI_ERR_HIP, "injected guard failure (cpmppi_debug_groups_fail)")
                                            : cpmppi_comm::enqueue_guard(g->g[0].h, ticket, g->E, g->g[i].stream);
           if (rg != CPMPPI_OK) return failed(rg, where + cpmppi_last_error(g->g[0].h));
         }
-        const int rc = injected(1, i, k) ? cpmppi_internal_fail(h, CPMPPI_ERR_HIP, "injected step failure (cpmppi_debug_groups_fail)")
-                       : comm ? cpmppi_internal_step_ticket(h, &sa[i], g->g[i].stream, &ticket) : cpmppi_step(h, &sa[i], g->g[i].stream);
+        const int rc = injected(1, i, k) ? fail(h, CPMPPI_ERR_HIP, "injected step failure (cpmppi_debug_groups_fail)")
+                       : comm ? step_impl(h, &sa[i], g->g[i].stream, nullptr, &ticket) : cpmppi_step(h, &sa[i], g->g[i].stream);
         if (rc != CPMPPI_OK) return failed(rc, where + cpmppi_last_error(h));
         out = true;
       }
       if (plant) {
         pa[i].period = plant->period + k;
-        const int rc = injected(3, i, k) ? cpmppi_internal_fail(h, CPMPPI_ERR_HIP, "injected plant failure (cpmppi_debug_groups_fail)")
+        const int rc = injected(3, i, k) ? fail(h, CPMPPI_ERR_HIP, "injected plant failure (cpmppi_debug_groups_fail)")
                                          : cpmppi_plant_step(h, &pa[i], g->g[i].stream);
         if (rc != CPMPPI_OK) return failed(rc, where + cpmppi_last_error(h));
       }
@@ -326,7 +322,7 @@ int cpmppi_groups_comm_init(cpmppi_groups* g, const void* id, int world, int ran
   if (!g || g->g.empty()) return CPMPPI_ERR_BAD_ARG;
   const int rc = cpmppi_comm_init(g->g[0].h, id, world, rank, rccl_path);
   if (rc != CPMPPI_OK) return gfail(g, rc, std::string("cpmppi_groups_comm_init: ") + cpmppi_last_error(g->g[0].h));
-  if (cpmppi_comm::share_between_groups(cpmppi_internal_comm(g->g[0].h)) != CPMPPI_OK) {
+  if (cpmppi_comm::share_between_groups(g->g[0].h->comm) != CPMPPI_OK) {
     (void)cpmppi_comm_destroy(g->g[0].h);
     return gfail(g, CPMPPI_ERR_HIP, "cpmppi_groups_comm_init: could not switch the communicator to the env-group form");
   }

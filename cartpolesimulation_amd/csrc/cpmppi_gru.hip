@@ -1,0 +1,398 @@
+// cpmppi_gru.hip — the GRU predictor (BASELINE configs[4]): model upload, its predictor seam, and the fused MPPI step with it.
+// The cell and its mapping onto the matrix cores: cpmppi_gru.hpp (exact f32 MFMA chains) and cpmppi_gru16.hpp (f16 split).
+//
+// Kernel inventory
+//   gru_predict_kernel                      predictor seam with the neural predictor: trajectories [B,H+1,6], hidden states.
+//   gru_rollout_cost_kernel<COST,NOISE,F16> the fused MPPI step with the GRU predictor: same contract as rollout_cost_kernel
+//                                           (plugin costs); launched by step_impl through launch_gru_rollout.
+// Entry points: cpmppi_set_gru, cpmppi_gru_predict; -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write
+// g_gru_stamp_sum are this unit's).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <exception>
+#include <string>
+#include <vector>
+
+#include "cpmppi.h"
+#include "cpmppi_internal.hpp"
+#include "cpmppi_gru.hpp"
+#include "cpmppi_gru16.hpp"
+
+using namespace cpmppi_k;
+
+namespace {
+
+__device__ __forceinline__ void gru_load_image(float* __restrict__ lds, const float* __restrict__ image) {
+  for (int i = threadIdx.x; i < GRU_IMAGE_FLOATS; i += BLOCK) lds[i] = image[i];
+  __syncthreads();
+}
+
+// predictor seam with the neural predictor: s0[B,6], Q[B,H], h0[2,B,32] or NULL -> traj[B,H+1,6], h_out[2,B,32] or NULL
+// (one wave per SIMD: the exact-f32 MFMA chain of gru_step with all its fragment loads in flight wants more than 256 registers -
+// compiled for two waves per SIMD it spilled 38 of them to a 156-byte scratch slot; the seam is bound by the matrix pipe either way)
+__global__ __launch_bounds__(BLOCK, 1) void gru_predict_kernel(const GruNorm nm, const float* __restrict__ image, uint32_t B,
+                                                            uint32_t H, const float* __restrict__ s0,
+                                                            const float* __restrict__ Q, const float* __restrict__ h0,
+                                                            float* __restrict__ traj, float* __restrict__ h_out) {
+  extern __shared__ float lds[];
+  gru_load_image(lds, image);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, c = lane & 31u;
+  const size_t b = (size_t)blockIdx.x * GRU_ROLLOUTS_PER_BLOCK + wave * 32 + c;
+  const bool valid = b < B;
+  const size_t bb = valid ? b : 0;
+  const float* s = s0 + bb * 6;
+  f16v h1 = gru_load_hidden(h0 ? h0 + bb * 32 : nullptr, lane);
+  f16v h2 = gru_load_hidden(h0 ? h0 + ((size_t)B + bb) * 32 : nullptr, lane);
+  f16v x = gru_input_tile(nm, s, Q[bb * H], lane);
+  float* o = traj + bb * (size_t)(H + 1) * 6;
+  if (valid && lane < 32) for (int i = 0; i < 6; ++i) o[i] = s[i];
+  for (uint32_t k = 0; k < H; ++k) {
+    const f16v out = gru_step(lds, x, h1, h2, lane);
+    float st[6];
+    gru_output_state(nm, out, lane, st);
+    if (valid && lane < 32) {
+      o += 6;
+      for (int i = 0; i < 6; ++i) o[i] = st[i];
+    }
+    x = out;                                               // normalised outputs are fed back unchanged
+    if (lane >= 32 && k + 1 < H) x[1] = __builtin_fmaf(Q[bb * H + k + 1], nm.in_scale[0], nm.in_shift[0]);
+  }
+  if (h_out && valid) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      h_out[bb * 32 + gru_tile_row(v, lane >> 5)] = h1[v];
+      h_out[((size_t)B + bb) * 32 + gru_tile_row(v, lane >> 5)] = h2[v];
+    }
+  }
+}
+
+// Fused MPPI step with the GRU predictor: same contract as rollout_cost_kernel (plugin costs), h0[E,2,32] or NULL.
+template <int COST, int NOISE, bool F16>
+__global__ __launch_bounds__(BLOCK, CPMPPI_GRU_MIN_WAVES) void gru_rollout_cost_kernel(const Params p, const StepPtrs a, const GruNorm nm,
+                                                                 const float* __restrict__ image,
+                                                                 const float* __restrict__ h0) {
+  extern __shared__ float lds[];                           // GRU image, then [WAVES][W] weighted sums
+  __shared__ float red[2 * WAVES];
+  constexpr int IMAGE_FLOATS = F16 ? G16_IMAGE_BYTES / 4 : GRU_IMAGE_FLOATS;
+  for (int i = threadIdx.x; i < IMAGE_FLOATS; i += BLOCK) lds[i] = image[i];
+  __syncthreads();
+  float* bsum = lds + IMAGE_FLOATS;
+  const uint32_t env = blockIdx.x / a.nb, blk = blockIdx.x % a.nb;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = lane & 31u;
+  const uint32_t row0 = blk * GRU_ROLLOUTS_PER_BLOCK + wave * 32;
+  const uint32_t n = row0 + c;
+  const bool owner = lane < 32 && n < p.N;                 // the lane that accounts for rollout n
+  const uint32_t nn = n < p.N ? n : 0;
+  const uint32_t H = p.H;
+  const uint64_t step_offset = a.offset_dev ? (uint64_t)*a.offset_dev : a.offset;
+  const float x_t = a.x_t[env], te = a.te[env];
+  const float* __restrict__ s0 = a.s0 + (size_t)env * 6;
+  const float* __restrict__ un = a.u_nom + (size_t)env * H;
+  f16v h1 = gru_load_hidden(h0 ? h0 + (size_t)env * 64 : nullptr, lane);
+  f16v h2 = gru_load_hidden(h0 ? h0 + (size_t)env * 64 + 32 : nullptr, lane);
+
+  auto knot = [&](uint32_t j) __attribute__((always_inline)) -> float {
+    if constexpr (NOISE == NOISE_KNOTS) return a.noise[((size_t)env * p.N + nn) * p.P + j];
+    else return philox_knot(a.seed, step_offset, a.env_offset + env, nn, j, p.sigma);
+  };
+  float z_lo = 0.0f, z_hi = 0.0f;
+  if constexpr (NOISE != NOISE_DELTA_U) { z_lo = knot(0); z_hi = knot(1); }
+  uint32_t ii = 0, j = 0;
+
+  float st[6] = {s0[0], s0[1], s0[2], s0[3], s0[4], s0[5]};
+  float cost = 0.0f, corr = 0.0f;
+  float cosang = cosf(s0[0]);               // the plugins take cos(angle) of the given state at stage 0
+  f16v x;
+  GruCarry carry;
+  Gru16Carry carry16;
+  Gru16State gs;
+  const char* __restrict__ ldsb = reinterpret_cast<const char*>(lds);
+  if constexpr (F16) {
+    gs.h1 = h1; gs.h2 = h2;
+    gru16_carry_init(ldsb, gs, lane, carry16);
+  } else {
+    gru_carry_init(lds, h1, lane, carry);
+  }
+  const bool half1 = lane >= 32;
+#ifdef CPMPPI_GRU_STAMPS
+  unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0};
+  unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
+#endif
+  for (uint32_t k = 0; k < H; ++k) {
+    float du;
+    if constexpr (NOISE == NOISE_DELTA_U) du = a.noise[((size_t)env * p.N + nn) * H + k];
+    else if constexpr (F16 && NOISE == NOISE_PHILOX)      // FAST + own noise: one float32 FMA, as the ODE kernel and the sampler
+      du = interp_from_slope32(knot_slope32(z_lo, z_hi, 1.0f / (float)p.period), z_lo, ii);
+    else du = interp_knots(z_lo, z_hi, ii, p.period);
+    const float uk = shifted_nominal(p, un, k);
+    float ur = uk + du;
+    if (p.control_mode == CPMPPI_CONTROL_CLIP) ur = clamp_(ur, p.lo, p.hi);
+    if constexpr (COST == COST_QBGM) cost += stage_qbgm<float, F16>(p, st[4], cosang, st[1], ur, x_t, te);
+    else cost += stage_default<float, F16>(p, st[4], cosang, ur, x_t, te);
+    corr += mppi_correction<float>(p, p.correction_u == CPMPPI_CORRECTION_U_RUN ? ur : uk, du);
+    if (k == 0) x = gru_input_tile(nm, s0, ur, lane);
+    else if (half1) x[1] = __builtin_fmaf(ur, nm.in_scale[0], nm.in_shift[0]);
+    float out[5];
+    if constexpr (F16) {
+#ifdef CPMPPI_GRU_STAMPS
+      const f16v o = gru16_step(ldsb, x, gs, carry16, lane, stamp_acc, stamp_prev);
+#else
+      const f16v o = gru16_step(ldsb, x, gs, carry16, lane);
+#endif
+      out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3];
+      out[4] = __shfl(o[0], (int)(c + 32u), 64);           // positionD (row 4) lives on the partner lane-half
+      if (half1) out[4] = o[0];
+    } else {
+#ifdef CPMPPI_GRU_STAMPS
+      gru_step_pipelined(lds, x, h1, h2, carry, lane, out, stamp_acc, stamp_prev);
+#else
+      gru_step_pipelined(lds, x, h1, h2, carry, lane, out);
+#endif
+    }
+    gru_output_state_fast(nm, out, st, cosang);
+    // normalised outputs are fed back unchanged: rows 0..3 on lane-half 0, row 4 (and Q, row 5) on lane-half 1
+    x[0] = half1 ? out[4] : out[0];
+    x[1] = half1 ? 0.0f : out[1];
+    x[2] = half1 ? 0.0f : out[2];
+    x[3] = half1 ? 0.0f : out[3];
+    if constexpr (NOISE != NOISE_DELTA_U) {
+      if (++ii == p.period) {
+        ii = 0; ++j;
+        z_lo = z_hi;
+        if (j + 1 < p.P) z_hi = knot(j + 1);
+      }
+    }
+  }
+  st[0] = atan2f(st[3], st[2]);             // predictors_customization.py:121-127, needed for the terminal cost only
+#ifdef CPMPPI_GRU_STAMPS
+  if (lane == 0)
+    for (int i = 0; i < 6; ++i) atomicAdd(&g_gru_stamp_sum[i], stamp_acc[i]);
+  if (lane == 0) atomicAdd(&g_gru_stamp_sum[6], 1ull);
+#endif
+  const float term = (COST == COST_DEFAULT) ? terminal_indicator<float>(p, st[0], st[4], x_t) : 0.0f;
+  float S_total = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? (cost + term) : (cost + term) / (float)(H + 1);
+  S_total += corr;
+  if (a.S_out && owner) a.S_out[(size_t)env * p.N + n] = S_total;
+
+  const float m_w = wave_min(owner ? S_total : INFINITY);
+  if (lane == 0) red[wave] = m_w;
+  __syncthreads();
+  float m_b = red[0];
+#pragma unroll
+  for (int w = 1; w < WAVES; ++w) m_b = fminf(m_b, red[w]);
+  const float e = owner ? expf((-1.0f / p.LBD) * (S_total - m_b)) : 0.0f;
+  const float a_w = wave_sum(e);
+  if (lane == 0) red[WAVES + wave] = a_w;
+  const uint32_t W = a.W;
+  float* __restrict__ my_bsum = bsum + wave * W;
+  if constexpr (NOISE == NOISE_PHILOX) {
+    for (uint32_t jj = 0; jj < W; ++jj) {
+      const float v = wave_sum(e * philox_knot(a.seed, step_offset, a.env_offset + env, nn, jj, p.sigma));
+      if (lane == 0) my_bsum[jj] = v;
+    }
+  } else {
+    const float* __restrict__ src = a.noise + ((size_t)env * p.N + row0) * W;
+    const uint32_t rows = (row0 < p.N) ? ((p.N - row0 < 32u) ? p.N - row0 : 32u) : 0u;
+    for (uint32_t c0 = 0; c0 < W; c0 += 64) {
+      const uint32_t col = c0 + lane;
+      float acc = 0.0f;
+      const float* __restrict__ colp = src + (col < W ? col : 0u);
+      uint32_t r = 0;
+      for (; r + 8 <= rows; r += 8) {                      // eight independent row loads in flight (latency-bound pass)
+        float xr[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) xr[u] = colp[(size_t)(r + u) * W];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+          acc = __builtin_fmaf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), r + u)), xr[u], acc);
+      }
+      for (; r < rows; ++r)
+        acc = __builtin_fmaf(__int_as_float(__builtin_amdgcn_readlane(__float_as_int(e), r)), colp[(size_t)r * W], acc);
+      if (col < W) my_bsum[col] = acc;
+    }
+  }
+  __syncthreads();
+  float* __restrict__ outp = a.partial + ((size_t)env * a.nb + blk) * (2 + W);
+  if (tid == 0) {
+    float a_b = red[WAVES];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) a_b += red[WAVES + w];
+    outp[0] = m_b;
+    outp[1] = a_b;
+  }
+  for (uint32_t cc = tid; cc < W; cc += BLOCK) {
+    float v = bsum[cc];
+#pragma unroll
+    for (int w = 1; w < WAVES; ++w) v += bsum[w * W + cc];
+    outp[2 + cc] = v;
+  }
+}
+
+// FAST: float32-equivalent split products on the f16 matrix cores (cpmppi_gru16.hpp); PRECISE: exact f32 MFMA chains
+template <int COST, int NOISE>
+void launch_gru(cpmppi_handle* h, const cpmppi_step_args* a, const StepPtrs& p, hipStream_t s) {
+  const bool f16 = h->cfg.math_mode == CPMPPI_MATH_FAST && h->gru16_image != nullptr;
+  const size_t lds = ((f16 ? (size_t)G16_IMAGE_BYTES / 4 : (size_t)GRU_IMAGE_FLOATS) + (size_t)WAVES * p.W) * sizeof(float);
+  if (lds > 64 * 1024) {   // long horizons with a perturbation buffer: weights image + [WAVES][H] sums
+    allow_large_lds(&gru_rollout_cost_kernel<COST, NOISE, true>);
+    allow_large_lds(&gru_rollout_cost_kernel<COST, NOISE, false>);
+  }
+  const dim3 grid(a->E * p.nb);
+  if (f16) hipLaunchKernelGGL((gru_rollout_cost_kernel<COST, NOISE, true>), grid, dim3(BLOCK), lds, s, h->prm, p,
+                              h->gru_norm, (const float*)h->gru16_image, a->h0);
+  else hipLaunchKernelGGL((gru_rollout_cost_kernel<COST, NOISE, false>), grid, dim3(BLOCK), lds, s, h->prm, p,
+                          h->gru_norm, (const float*)h->gru_image, a->h0);
+}
+
+}  // namespace
+
+void launch_gru_rollout(cpmppi_handle* h, const cpmppi_step_args* a, const StepPtrs& p, hipStream_t s) {
+  const bool q = h->prm.cost_id == CPMPPI_COST_QBGM;
+  if (a->noise_kind == CPMPPI_NOISE_DELTA_U) { if (q) launch_gru<COST_QBGM, NOISE_DELTA_U>(h, a, p, s); else launch_gru<COST_DEFAULT, NOISE_DELTA_U>(h, a, p, s); }
+  else if (a->noise_kind == CPMPPI_NOISE_KNOTS) { if (q) launch_gru<COST_QBGM, NOISE_KNOTS>(h, a, p, s); else launch_gru<COST_DEFAULT, NOISE_KNOTS>(h, a, p, s); }
+  else { if (q) launch_gru<COST_QBGM, NOISE_PHILOX>(h, a, p, s); else launch_gru<COST_DEFAULT, NOISE_PHILOX>(h, a, p, s); }
+}
+
+extern "C" {
+
+int cpmppi_set_gru(cpmppi_handle* h, const cpmppi_gru_model* m) try {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!m || m->hidden != 32 || m->layers != 2 || m->inputs != 6 || m->outputs != 5)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_gru: only GRU-6IN-32H1-32H2-5OUT is built");
+  for (int l = 0; l < 2; ++l)
+    if (!m->w_ih[l] || !m->w_hh[l] || !m->b_ih[l] || !m->b_hh[l]) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_gru: null weights");
+  if (!m->w_out || !m->b_out) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_gru: null head weights");
+  std::vector<float> img((size_t)GRU_IMAGE_FLOATS, 0.0f);
+  auto frag = [&](int f) { return img.data() + (size_t)f * 64; };
+  // x-tile row r -> network input column: rows 0..4 = the 5 state features (inputs 1..5), row 5 = Q (input 0)
+  auto xcol = [](int r) { return r < 5 ? r + 1 : (r == 5 ? 0 : -1); };
+  for (int g = 0; g < 3; ++g) {
+    for (int s = 0; s < 4; ++s)
+      for (int l = 0; l < 64; ++l) {
+        const int col = xcol(gru_tile_row(s, l >> 5));
+        frag(GF_L1X + g * 4 + s)[l] = col < 0 ? 0.0f : m->w_ih[0][(size_t)(g * 32 + (l & 31)) * 6 + col];
+      }
+    for (int s = 0; s < 16; ++s)
+      for (int l = 0; l < 64; ++l) {
+        const int k = gru_tile_row(s, l >> 5);
+        const size_t row = (size_t)(g * 32 + (l & 31));
+        frag(GF_L1H + g * 16 + s)[l] = m->w_hh[0][row * 32 + k];
+        frag(GF_L2X + g * 16 + s)[l] = m->w_ih[1][row * 32 + k];
+        frag(GF_L2H + g * 16 + s)[l] = m->w_hh[1][row * 32 + k];
+      }
+  }
+  for (int layer = 0; layer < 2; ++layer) {
+    const int fb = layer == 0 ? GF_L1B : GF_L2B;
+    for (int l = 0; l < 32; ++l) {                           // lane-half 0 carries the bias (k = 0), half 1 zeros
+      frag(fb + 0)[l] = m->b_ih[layer][l] + m->b_hh[layer][l];
+      frag(fb + 1)[l] = m->b_ih[layer][32 + l] + m->b_hh[layer][32 + l];
+      frag(fb + 2)[l] = m->b_ih[layer][64 + l];
+      frag(fb + 3)[l] = m->b_hh[layer][64 + l];
+    }
+  }
+  for (int s = 0; s < 16; ++s)
+    for (int l = 0; l < 64; ++l)
+      frag(GF_DW + s)[l] = (l & 31) < 5 ? m->w_out[(size_t)(l & 31) * 32 + gru_tile_row(s, l >> 5)] : 0.0f;
+  for (int l = 0; l < 5; ++l) frag(GF_DB)[l] = m->b_out[l];
+  // plain vectors of the fused rollout kernel (biases as accumulator tiles, dense head on the VALU)
+  for (int layer = 0; layer < 2; ++layer)
+    for (int hf = 0; hf < 2; ++hf)
+      for (int v = 0; v < 16; ++v) {
+        const int r = gru_tile_row(v, hf);
+        float* b = img.data() + GV_BIAS + (size_t)layer * 4 * 32 + hf * 16 + v;
+        b[0 * 32] = m->b_ih[layer][r] + m->b_hh[layer][r];
+        b[1 * 32] = m->b_ih[layer][32 + r] + m->b_hh[layer][32 + r];
+        b[2 * 32] = m->b_ih[layer][64 + r];
+        b[3 * 32] = m->b_hh[layer][64 + r];
+      }
+  for (int hf = 0; hf < 2; ++hf)
+    for (int o = 0; o < 5; ++o)
+      for (int v = 0; v < 16; ++v)
+        img[GV_HEAD + (size_t)hf * 80 + o * 16 + v] = m->w_out[(size_t)o * 32 + gru_tile_row(v, hf)];
+  for (int o = 0; o < 5; ++o) img[GV_HEADB + o] = m->b_out[o];
+  for (int i = 0; i < 6; ++i) {
+    h->gru_norm.in_scale[i] = m->in_scale ? m->in_scale[i] : 1.0f;
+    h->gru_norm.in_shift[i] = m->in_shift ? m->in_shift[i] : 0.0f;
+  }
+  for (int i = 0; i < 5; ++i) {
+    h->gru_norm.out_scale[i] = m->out_scale ? m->out_scale[i] : 1.0f;
+    h->gru_norm.out_shift[i] = m->out_shift ? m->out_shift[i] : 0.0f;
+  }
+  // ---- f16 split image (cpmppi_gru16.hpp): fragment f holds, for lane l and t = 0..7, the weight of output row l%32
+  // against k-slot (block b, lane half l/32, t) = tile register v = 8b + t of that half
+  std::vector<unsigned char> img16((size_t)G16_IMAGE_BYTES, 0);
+  bool in_range = true;
+  auto put16 = [&](int f, int lane, int t, float w) {
+    const _Float16 hi = (_Float16)w;
+    const _Float16 lo = (_Float16)(w - (float)hi);
+    if (!(fabsf(w) < 60000.0f)) in_range = false;
+    reinterpret_cast<_Float16*>(img16.data() + (size_t)f * G16_FRAG_BYTES + lane * 16)[t] = hi;
+    reinterpret_cast<_Float16*>(img16.data() + (size_t)(f + 1) * G16_FRAG_BYTES + lane * 16)[t] = lo;
+  };
+  // gate rows pre-scaled so that the gates need no multiply before v_exp_f32 (gru16_gates): r, z by -log2(e), n by 2 log2(e)
+  const double LOG2E = 1.4426950408889634;
+  const double gate_scale[3] = {-LOG2E, -LOG2E, 2.0 * LOG2E};
+  auto sc = [&](int g, float w) { return (float)(gate_scale[g] * (double)w); };
+  for (int g = 0; g < 3; ++g)
+    for (int l = 0; l < 64; ++l)
+      for (int tt = 0; tt < 8; ++tt) {
+        const size_t row = (size_t)(g * 32 + (l & 31));
+        const int col = xcol(gru_tile_row(tt, l >> 5));                       // x tile registers 0..7
+        put16(HF_L1X + g * 2, l, tt, (col < 0 || tt >= 4) ? 0.0f : sc(g, m->w_ih[0][row * 6 + col]));
+        for (int b = 0; b < 2; ++b) {
+          const int k = gru_tile_row(8 * b + tt, l >> 5);
+          put16(HF_L1H + (g * 2 + b) * 2, l, tt, sc(g, m->w_hh[0][row * 32 + k]));
+          put16(HF_L2X + (g * 2 + b) * 2, l, tt, sc(g, m->w_ih[1][row * 32 + k]));
+          put16(HF_L2H + (g * 2 + b) * 2, l, tt, sc(g, m->w_hh[1][row * 32 + k]));
+        }
+      }
+  for (int b = 0; b < 2; ++b)
+    for (int l = 0; l < 64; ++l)
+      for (int tt = 0; tt < 8; ++tt)
+        put16(HF_HEAD + b * 2, l, tt, (l & 31) < 5 ? m->w_out[(size_t)(l & 31) * 32 + gru_tile_row(8 * b + tt, l >> 5)] : 0.0f);
+  if (!in_range) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_gru: weights beyond the f16 range");
+  {
+    float* bv = reinterpret_cast<float*>(img16.data() + G16_BIAS_OFF);
+    for (int i = 0; i < 8 * 32; ++i) {                                        // the same 8 gate-bias tiles, scaled alike
+      const int kind = (i / 32) % 4;                                          // r, z, n_x, n_h
+      bv[i] = (float)(gate_scale[kind < 2 ? kind : 2] * (double)img[GV_BIAS + i]);
+    }
+    for (int hf = 0; hf < 2; ++hf)
+      for (int v = 0; v < 16; ++v) {
+        const int r = gru_tile_row(v, hf);
+        bv[8 * 32 + hf * 16 + v] = r < 5 ? m->b_out[r] : 0.0f;
+      }
+  }
+  CPMPPI_ON_DEVICE(h);
+  if (!h->gru_image) CPMPPI_HIP(h, hipMalloc(&h->gru_image, img.size() * sizeof(float)));
+  CPMPPI_HIP(h, hipMemcpy(h->gru_image, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (!h->gru16_image) CPMPPI_HIP(h, hipMalloc(&h->gru16_image, img16.size()));
+  CPMPPI_HIP(h, hipMemcpy(h->gru16_image, img16.data(), img16.size(), hipMemcpyHostToDevice));
+  return CPMPPI_OK;
+} catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }   // (no C++ exception leaves the C ABI)
+
+int cpmppi_gru_predict(cpmppi_handle* h, uint32_t B, uint32_t horizon, const float* s0, const float* Q, const float* h0,
+                       float* traj_out, float* h_out, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_predict: no model set (cpmppi_set_gru)");
+  if (horizon == 0) horizon = h->cfg.H;
+  if (B == 0 || !s0 || !Q || !traj_out) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_predict: bad argument");
+  CPMPPI_ON_DEVICE(h);
+  hipLaunchKernelGGL(gru_predict_kernel, dim3((B + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK), dim3(BLOCK),
+                     (size_t)GRU_IMAGE_FLOATS * sizeof(float), (hipStream_t)stream, h->gru_norm,
+                     (const float*)h->gru_image, B, horizon, s0, Q, h0, traj_out, h_out);
+  return launched(h);
+}
+
+#ifdef CPMPPI_GRU_STAMPS
+int cpmppi_debug_gru_stamps(unsigned long long out[8], int reset) {
+  if (hipMemcpyFromSymbol(out, HIP_SYMBOL(g_gru_stamp_sum), 8 * sizeof(unsigned long long)) != hipSuccess) return -1;
+  if (reset) {
+    unsigned long long z[8] = {0};
+    if (hipMemcpyToSymbol(HIP_SYMBOL(g_gru_stamp_sum), z, sizeof(z)) != hipSuccess) return -1;
+  }
+  return 0;
+}
+#endif
+
+}  // extern "C"

@@ -18,6 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include "cpmppi_device.hpp"     // (GruNorm)
 
 namespace cpmppi {
 
@@ -42,10 +43,6 @@ constexpr int GV_BIAS = GF_COUNT * 64;          // 8 vectors (layer 1: r, z, n_x
 constexpr int GV_HEAD = GV_BIAS + 8 * 32;       // [2][5][16]: w_out[o][row(v, half)]
 constexpr int GV_HEADB = GV_HEAD + 2 * 5 * 16;  // b_out[5] (+3 pad)
 constexpr int GRU_IMAGE_FLOATS = GV_HEADB + 8;
-
-struct GruNorm {         // normalised = x*scale + shift ; order Q, angleD, angle_cos, angle_sin, position, positionD
-  float in_scale[6], in_shift[6], out_scale[5], out_shift[5];
-};
 
 // row of a 32x32 accumulator tile held by (register v, lane half hf)
 __host__ __device__ inline int gru_tile_row(int v, int hf) { return (v & 3) + 8 * (v >> 2) + 4 * hf; }

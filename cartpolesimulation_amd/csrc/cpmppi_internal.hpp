@@ -1,8 +1,21 @@
-// cpmppi_internal.hpp — what the translation units of libcpmppi.so share beside the public header: access to the few
-// handle fields the communicator unit (cpmppi_comm.hip) needs.  The handle's layout stays private to cpmppi.hip.
+// cpmppi_internal.hpp — where the translation units of libcpmppi.so meet beside the public header: the handle's layout, the
+// error and device helpers of every entry point, and the few host functions one unit calls in another.
+//   cpmppi.hip            the hot path: handle lifecycle, cpmppi_step / _step_gather / _step_host, the rollout launch dispatch,
+//                         profiling, streams
+//   cpmppi_seams.hip      sampler, tiling, predictor, trajectory cost and reward-weighted-average seams
+//   cpmppi_plant.hip      the simulated plant (cpmppi_plant_*)
+//   cpmppi_optim.hip      cost-only rollouts, the adjoint, Adam / SGD steps and CEM
+//   cpmppi_gru.hip        the GRU predictor (model upload, its seam, its fused rollout launch)
+//   cpmppi_comm.hip, cpmppi_groups.hip, cpmppi_io.hip   host code only: the collective, env groups, the recording writer
+//   cpmppi_rollout_*.hip  the instances of rollout_cost_kernel, each unit with its own compiler flags
+// Kernels stay in an anonymous namespace of the unit that launches them; units call each other through host functions only.
 #pragma once
+#include <hip/hip_runtime.h>
+#include <stdint.h>
 #include <string>
+#include <vector>
 #include "cpmppi.h"
+#include "cpmppi_rollout.hpp"      // (declares, never instantiates, rollout_cost_kernel: only cpmppi_rollout_*.hip define it)
 
 namespace cpmppi_comm {
 struct CommState;                                        // cpmppi_comm.hip
@@ -25,12 +38,116 @@ void poison(CommState* c);                   // a partly enqueued step-gather: e
 int comm_error_pending(cpmppi_handle* h);    // a device-side wait timed out or a step-gather was poisoned (sticky until cpmppi_comm_sync)
 }  // namespace cpmppi_comm
 
-cpmppi_comm::CommState*& cpmppi_internal_comm(cpmppi_handle* h);
-// cpmppi_step whose finalize takes part in a step-gather described by `ticket` (cpmppi_step_gather; cpmppi_groups_run_gather, where
-// the ticket is shared by the launches of every group)
-int cpmppi_internal_step_ticket(cpmppi_handle* h, const cpmppi_step_args* a, void* stream, const cpmppi_comm::GatherTicket* ticket);
-// the checks cpmppi_step / cpmppi_plant_step make before they launch anything (CPMPPI_OK, or the error with the handle's message set)
-int cpmppi_internal_check_step(cpmppi_handle* h, const cpmppi_step_args* a);
-int cpmppi_internal_check_plant(cpmppi_handle* h, const cpmppi_plant_args* a);
-int cpmppi_internal_device(const cpmppi_handle* h);
-int cpmppi_internal_fail(cpmppi_handle* h, int code, const std::string& msg);
+struct cpmppi_handle {
+  cpmppi_config cfg;
+  cpmppi::Params prm;
+  int device;
+  float* workspace;
+  size_t workspace_floats;
+  uint32_t nb;
+  std::string err;
+  // optional per-kernel timing with HIP events recorded on the launch stream (cpmppi_set_profiling)
+  uint32_t* counters = nullptr;        // [cfg.E] block-arrival tickets of the fused finalize
+  cpmppi::EnvFold* env_fold = nullptr; // [cfg.E] per-env constants of the throughput build (fold_env_kernel, rewritten before every such launch)
+  float* zeros_H = nullptr;            // [cfg.E, cfg.H] zeros: the nominal sequence of a cost-only launch
+  float* host_stage = nullptr;         // pinned [cfg.E * 10 + 16]: staging of cpmppi_step_host (state 6, target, equilibrium, L | Q | ticket)
+  uint32_t host_ticket_value = 0;      // what the ticket in that block reads once every launch so far has delivered
+  double host_t[4] = {0, 0, 0, 0};     // development aid (cpmppi_debug_host_times): sums of staging / launch / wait seconds, calls
+  uint32_t host_zero_copy_max = 64;    // up to this many envs cpmppi_step_host runs without copies and stream waits (CPMPPI_HOST_ZERO_COPY_MAX)
+  float* dev_stage = nullptr;          // device [cfg.E * 10], allocated on first use
+  float* gru_image = nullptr;          // device copy of the LDS fragment image (cpmppi_set_gru)
+  void* gru16_image = nullptr;         // device copy of the f16 split image (cpmppi_gru16.hpp)
+  float* grad_ckpt = nullptr;          // [H][6][E*N] check-points of cpmppi_rollout_cost_grad (allocated on first use)
+  size_t grad_ckpt_floats = 0;
+  cpmppi::GruNorm gru_norm;
+  bool fuse_finalize = true;           // ODE path: the env's last block finalizes in-kernel (CPMPPI_FUSE_FINALIZE=0 disables)
+  uint32_t profile_every = 0;          // 0 = off, 1 = every rollout kernel bracketed, n > 1 = one bracket around n steps
+  uint32_t profile_count = 0;
+  bool group_open = false;             // n > 1: the current group's closing event is still to come
+  std::vector<hipEvent_t> ev;          // triples per sampled step: before rollout, after it, after the trailing kernels
+  std::vector<uint8_t> ev_tail;        // per triple: was the third event recorded (a separate finalize / counter kernel ran)
+  size_t ev_used = 0;
+  cpmppi_comm::CommState* comm = nullptr;   // RCCL communicator + side stream of cpmppi_comm_* (cpmppi_comm.hip)
+  float plant_m_pole = 0.0f;           // the pole mass of the simulated PLANT (cfg.m_pole at creation; cpmppi_set_pole_mass does not touch it)
+  cpmppi_launch_info last_launch = {0, 0, 0, 0, 0, 0, 0};   // cpmppi_last_launch: the instantiation the last rollout launch used
+};
+
+// Sets the call's error message and returns `code`.  h == NULL: the calling thread's creation error, which
+// cpmppi_last_error(NULL) reads - one object, so this is defined once (cpmppi.hip).
+int fail(cpmppi_handle* h, int code, const std::string& msg);
+
+#define CPMPPI_HIP(h, call)                                                                        \
+  do {                                                                                             \
+    hipError_t e_ = (call);                                                                        \
+    if (e_ != hipSuccess)                                                                          \
+      return fail((h), CPMPPI_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_));         \
+  } while (0)
+
+// Every entry point runs on the handle's device and leaves the CALLER's current device as it found it (a process that
+// shares the HIP runtime with torch must not have its later raw HIP calls retargeted).
+struct DeviceGuard {
+  int prev = -1;
+  bool switched = false;
+  hipError_t err = hipSuccess;
+  explicit DeviceGuard(int dev) {
+    err = hipGetDevice(&prev);
+    if (err == hipSuccess && prev != dev) {
+      err = hipSetDevice(dev);
+      switched = (err == hipSuccess);
+    }
+  }
+  ~DeviceGuard() { if (switched) (void)hipSetDevice(prev); }
+  DeviceGuard(const DeviceGuard&) = delete;
+  DeviceGuard& operator=(const DeviceGuard&) = delete;
+};
+#define CPMPPI_ON_DEVICE(h)                                                                        \
+  DeviceGuard device_guard_((h)->device);                                                          \
+  if (device_guard_.err != hipSuccess)                                                             \
+    return fail((h), CPMPPI_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(device_guard_.err))
+
+inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
+
+// the end of an entry point that has just launched a kernel: CPMPPI_OK, or the launch's error
+inline int launched(cpmppi_handle* h) {
+  CPMPPI_HIP(h, hipGetLastError());
+  return CPMPPI_OK;
+}
+
+// a kernel whose dynamic LDS may exceed the default 64 KB opts in to SAMPLER_LDS_MAX
+template <class Kernel>
+void allow_large_lds(Kernel* kernel) {
+  (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)cpmppi_k::SAMPLER_LDS_MAX);
+}
+
+// GRU predictor (BASELINE configs[4]): 256 threads = 4 waves x 32 rollouts
+constexpr int GRU_ROLLOUTS_PER_BLOCK = 32 * cpmppi_k::WAVES;
+
+// Lane mapping: two rollouts per lane (packed float2) once the launch fills every SIMD with at least one such wave
+// (1024 SIMDs x 128 rollouts); one rollout per lane (shortest critical path) below.  Measured at 128 envs x 1024 x 50:
+// 76 us packed vs 90 us one per lane; at 64 envs the packed mapping would leave half the SIMDs empty.
+constexpr uint64_t PACKED_MIN_ROLLOUTS = 131072ull;
+inline uint32_t rollouts_per_lane(const cpmppi_handle* h, uint32_t E) {
+  if (h->cfg.math_mode != CPMPPI_MATH_FAST) return 1;
+  if (h->cfg.rollouts_per_lane != 0) return h->cfg.rollouts_per_lane;
+  return ((uint64_t)E * h->cfg.N >= PACKED_MIN_ROLLOUTS) ? 2 : 1;
+}
+
+// ---- host functions one unit calls in another -------------------------------------------------------------------------
+// cpmppi.hip.  check_step: every check of a step's argument block that needs no launch (cpmppi_groups_run_gather runs them for
+// all groups before its first launch).  step_impl: cpmppi_step, with the pinned ticket of cpmppi_step_host and / or the
+// step-gather whose finalize it takes part in (cpmppi_step_gather; cpmppi_groups_run_gather, where the ticket is shared by the
+// launches of every group).  launch_rollout: the rollout_cost_kernel instance for the handle's configuration; `prm` is the
+// kernel-argument block of THIS launch (the handle's, or a modified copy: cost-only launches).
+int check_step(cpmppi_handle* h, const cpmppi_step_args* a);
+int step_impl(cpmppi_handle* h, const cpmppi_step_args* a, void* stream, uint32_t* host_ticket,
+              const cpmppi_comm::GatherTicket* gather = nullptr);
+hipError_t launch_rollout(cpmppi_handle* h, const cpmppi::Params& prm, uint32_t rpl, uint32_t noise, dim3 grid, size_t lds,
+                          hipStream_t s, const cpmppi_k::StepPtrs& a_in);
+// cpmppi_plant.hip: every check of a plant step's argument block that needs no launch (see check_step)
+int check_plant(cpmppi_handle* h, const cpmppi_plant_args* a);
+// cpmppi_gru.hip: the fused GRU rollout kernel of a step (p.nb counted in GRU blocks); the caller checks the launch
+void launch_gru_rollout(cpmppi_handle* h, const cpmppi_step_args* a, const cpmppi_k::StepPtrs& p, hipStream_t s);
+// called by cpmppi_create: the LDS opt-ins of the kernels of cpmppi_seams.hip and cpmppi_optim.hip
+void allow_large_lds_seams();
+void allow_large_lds_optim();

@@ -183,10 +183,10 @@ int cpmppi_write_recordings(const char* const* paths, const char* preamble, size
                             int n_threads) {
   if (!paths || !preamble || !rec || rec->E == 0 || !rec->time || !rec->states || !rec->dd || !rec->Q || !rec->Q_ccrc ||
       !rec->target_position || !rec->target_equilibrium || !rec->L)
-    return cpmppi_internal_fail(nullptr, CPMPPI_ERR_BAD_ARG, "cpmppi_write_recordings: null argument");
+    return fail(nullptr, CPMPPI_ERR_BAD_ARG, "cpmppi_write_recordings: null argument");
   const uint32_t E = rec->E;
   for (uint32_t e = 0; e < E; ++e)
-    if (!paths[e]) return cpmppi_internal_fail(nullptr, CPMPPI_ERR_BAD_ARG, "cpmppi_write_recordings: null path");
+    if (!paths[e]) return fail(nullptr, CPMPPI_ERR_BAD_ARG, "cpmppi_write_recordings: null path");
   std::vector<char> written;
   try {                                          // (threads and row buffers: no C++ exception leaves the C ABI)
   {
@@ -194,7 +194,7 @@ int cpmppi_write_recordings(const char* const* paths, const char* preamble, size
     std::sort(names.begin(), names.end());
     const auto dup = std::adjacent_find(names.begin(), names.end());
     if (dup != names.end())
-      return cpmppi_internal_fail(nullptr, CPMPPI_ERR_BAD_ARG, "cpmppi_write_recordings: the same path twice: " + *dup);
+      return fail(nullptr, CPMPPI_ERR_BAD_ARG, "cpmppi_write_recordings: the same path twice: " + *dup);
   }
   const Job j{paths, preamble, preamble_len, rec};
   unsigned nt = n_threads > 0 ? (unsigned)n_threads : std::thread::hardware_concurrency();
@@ -237,7 +237,7 @@ int cpmppi_write_recordings(const char* const* paths, const char* preamble, size
   if (n_failed) {
     for (uint32_t e = 0; e < E; ++e)            // a failing call leaves nothing behind: a retry starts from a clean directory
       if (written[e]) remove(paths[e]);
-    return cpmppi_internal_fail(nullptr, CPMPPI_ERR_IO, msg + " (the recordings this call had written were removed)");
+    return fail(nullptr, CPMPPI_ERR_IO, msg + " (the recordings this call had written were removed)");
   }
   return CPMPPI_OK;
   } catch (const std::exception&) {              // out of host memory (every worker has been joined or was never started)

@@ -1,0 +1,383 @@
+// cpmppi_optim.hip — what the other optimizers of the reference need on the device: cost-only rollouts, the adjoint of
+// rollout + cost, Adam / SGD steps on input sequences, and CEM's sampler and elite update.   Contract: include/cpmppi.h.
+//
+// Kernel inventory
+//   rollout_grad_kernel<COST, INTEG>      rollout + plugin cost + its gradient w.r.t. the inputs (cpmppi_grad.hpp).
+//   adam_step_kernel, sgd_step_kernel     gradient steps with per-rollout norm clipping and the action limits.
+//   cem_sample_kernel, cem_gmm_sample_kernel   CEM's sampler: one Gaussian per env, or a mixture of K elite-centred ones.
+//   cem_update_kernel                     top-k (bitonic sort in LDS) -> mean and stdev of the elite.
+// cpmppi_rollout_cost launches rollout_cost_kernel through launch_rollout (cpmppi.hip).
+#include <hip/hip_runtime.h>
+#include <math.h>
+#include <string>
+
+#include "cpmppi.h"
+#include "cpmppi_internal.hpp"
+#include "cpmppi_grad.hpp"
+
+using namespace cpmppi_k;
+
+namespace {
+
+// ------------------------------------------------------------------------------------------------------------------
+// Rollout + plugin cost + its gradient w.r.t. the inputs (cpmppi_grad.hpp).  One lane = one (env, rollout) of the
+// flattened [E*N] axis (the gradient optimizers run 16-40 rollouts per env, config_optimizers.yml:60,75: a block per
+// env would idle), so per-env quantities are per-lane here.  Check-points ckpt[H][6][E*N] (lane-contiguous) hold the
+// state at every control step; sub[S][6][BLOCK] in LDS holds the sub-states of the control step being reversed.
+struct GradPtrs {
+  const float* s0; const float* Q; const float* x_t; const float* te; const float* L; const float* prev_in;
+  float* ckpt; float* S_out; float* grad; uint32_t E;
+};
+
+template <int COST, int INTEG = PREDICTOR_ODE_V0>
+__global__ __launch_bounds__(BLOCK) void rollout_grad_kernel(const Params p, const GradPtrs a) {
+  auto forward_substep = [&](State<float>& s, float uK, const EnvConst& e) __attribute__((always_inline)) {
+    if constexpr (INTEG == PREDICTOR_ODE) substep_cromer_plain(s, uK, p.t_step, p, e);
+    else substep_fast<float>(s, uK, p.t_step, p, e, p.THL);
+  };
+  extern __shared__ float sub_states[];            // [S][6][BLOCK]
+  const uint32_t tid = threadIdx.x;
+  const size_t B = (size_t)a.E * p.N;
+  const size_t g = (size_t)blockIdx.x * BLOCK + tid;
+  if (g >= B) return;                               // (no block-level barrier below)
+  const uint32_t env = (uint32_t)(g / p.N);
+  const uint32_t H = p.H, S = p.S;
+  const float t = p.t_step;
+  const EnvConst ec = make_env_const(p, a.L ? a.L[env] : p.L_default);
+  const float x_t = a.x_t[env], te = a.te[env];
+  const float* __restrict__ s0 = a.s0 + (size_t)env * 6;
+  const float* __restrict__ Q = a.Q + g * H;
+  const float cos0 = cosf(s0[0]), sin0 = sinf(s0[0]);   // the plugins take cos(angle) of the given state at stage 0
+  const float ub0 = a.prev_in ? a.prev_in[env] : 0.0f;
+  const bool clip = p.control_mode == CPMPPI_CONTROL_CLIP;
+  const float scale = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? 1.0f : 1.0f / (float)(H + 1);
+
+  // ---- forward, check-pointing every control step -------------------------------------------------------------
+  State<float> st{s0[0], s0[1], s0[2], s0[3], s0[4], s0[5]};
+  float cost = 0.0f, cosang = cos0, u_before = ub0;
+  for (uint32_t k = 0; k < H; ++k) {
+    float* __restrict__ ck = a.ckpt + ((size_t)k * 6) * B + g;
+    ck[0] = st.th; ck[B] = st.w; ck[2 * B] = st.c; ck[3 * B] = st.s; ck[4 * B] = st.x; ck[5 * B] = st.v;
+    float ur = Q[k];
+    if (clip) ur = clamp_(ur, p.lo, p.hi);
+    if constexpr (COST == COST_QBGM) cost += stage_qbgm<float, true>(p, st.x, cosang, st.w, ur, x_t, te);
+    else if constexpr (COST == COST_DEFAULT) cost += stage_default<float, true>(p, st.x, cosang, ur, x_t, te);
+    else cost += stage_qbg<float, true>(p, st.x, cosang, st.w, ur, u_before, x_t, te);
+    u_before = ur;
+    const float uK = ur * ec.uK_scale;
+    for (uint32_t s = 0; s < S; ++s) forward_substep(st, uK, ec);
+    cosang = st.c;
+  }
+  const float term = (COST == COST_DEFAULT) ? terminal_indicator<float>(p, st.th, st.x, x_t) : 0.0f;
+  if (a.S_out) a.S_out[g] = (cost + term) * scale;
+
+  // ---- backward --------------------------------------------------------------------------------------------------
+  Adjoint lam{0.0f, 0.0f, 0.0f, 0.0f};              // the terminal indicator has zero derivative
+  float carry = 0.0f;                               // d stage_{k+1} / d u_k through u_before (quadratic_boundary_grad)
+  float* __restrict__ my = sub_states + tid;
+  for (uint32_t k = H; k-- > 0;) {
+    const float* __restrict__ ck = a.ckpt + ((size_t)k * 6) * B + g;
+    const State<float> st0{ck[0], ck[B], ck[2 * B], ck[3 * B], ck[4 * B], ck[5 * B]};
+    const float q = Q[k];
+    const bool clipped = clip && (q < p.lo || q > p.hi);
+    const float ur = clip ? clamp_(q, p.lo, p.hi) : q;
+    const float uK = ur * ec.uK_scale;
+    State<float> s = st0;
+    for (uint32_t i = 0; i < S; ++i) {
+      float* __restrict__ d = my + (size_t)i * 6 * BLOCK;
+      d[0] = s.th; d[BLOCK] = s.w; d[2 * BLOCK] = s.c; d[3 * BLOCK] = s.s; d[4 * BLOCK] = s.x; d[5 * BLOCK] = s.v;
+      forward_substep(s, uK, ec);
+    }
+    float guK = 0.0f;
+    for (uint32_t i = S; i-- > 0;) {
+      const float* __restrict__ d = my + (size_t)i * 6 * BLOCK;
+      const State<float> si{d[0], d[BLOCK], d[2 * BLOCK], d[3 * BLOCK], d[4 * BLOCK], d[5 * BLOCK]};
+      substep_reverse<(INTEG == PREDICTOR_ODE)>(si, uK, t, p, ec, lam, guK);
+    }
+    // stage k: its own state and control
+    const float ca = (k == 0) ? cos0 : st0.c, sa = (k == 0) ? sin0 : st0.s;
+    float ub = ub0;
+    if (COST == COST_QBG && k > 0) { ub = Q[k - 1]; if (clip) ub = clamp_(ub, p.lo, p.hi); }
+    StageGrad sg;
+    if constexpr (COST == COST_QBGM) sg = stage_qbgm_grad(p, st0.x, ca, st0.w, ur, x_t, te);
+    else if constexpr (COST == COST_DEFAULT) sg = stage_default_grad(p, st0.x, ca, ur, x_t, te);
+    else sg = stage_qbg_grad(p, st0.x, ca, st0.w, ur, ub, x_t, te);
+    lam.x = __builtin_fmaf(scale, sg.x, lam.x);
+    lam.w = __builtin_fmaf(scale, sg.w, lam.w);
+    lam.th = __builtin_fmaf(scale * sg.cosang, -sa, lam.th);
+    const float gk = __builtin_fmaf(guK, ec.uK_scale, scale * sg.u + carry);
+    carry = scale * sg.u_before;
+    a.grad[g * H + k] = clipped ? 0.0f : gk;
+  }
+}
+
+// Adam on input sequences with per-rollout gradient-norm clipping (tf.clip_by_norm over the horizon) and the final
+// clip to the action limits; hyper-parameters config_optimizers.yml:52-58,69-73.  One lane = one (env, rollout) row.
+__global__ __launch_bounds__(BLOCK) void adam_step_kernel(size_t rows, uint32_t H, float* __restrict__ Q,
+                                                          const float* __restrict__ grad, float* __restrict__ m,
+                                                          float* __restrict__ v, float lr_t, float beta1, float beta2,
+                                                          float eps, float gradmax_clip, float lo, float hi) {
+  const size_t r = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (r >= rows) return;
+  const float* __restrict__ gr = grad + r * H;
+  float ss = 0.0f;
+  for (uint32_t k = 0; k < H; ++k) ss = __builtin_fmaf(gr[k], gr[k], ss);
+  const float nrm = sqrtf(ss);
+  const float sc = (gradmax_clip > 0.0f && nrm > gradmax_clip) ? gradmax_clip / nrm : 1.0f;
+  for (uint32_t k = 0; k < H; ++k) {
+    const size_t i = r * H + k;
+    const float gk = gr[k] * sc;
+    const float mk = beta1 * m[i] + (1.0f - beta1) * gk;
+    const float vk = beta2 * v[i] + (1.0f - beta2) * gk * gk;
+    m[i] = mk; v[i] = vk;
+    Q[i] = clamp_(Q[i] - lr_t * mk / (sqrtf(vk) + eps), lo, hi);
+  }
+}
+
+// Plain gradient step with the same per-rollout norm clipping and limit clip (cem-naive-grad-tf, config_optimizers.yml:21-31).
+__global__ __launch_bounds__(BLOCK) void sgd_step_kernel(size_t rows, uint32_t H, float* __restrict__ Q,
+                                                         const float* __restrict__ grad, float lr, float gradmax_clip,
+                                                         float lo, float hi) {
+  const size_t r = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (r >= rows) return;
+  const float* __restrict__ gr = grad + r * H;
+  float ss = 0.0f;
+  for (uint32_t k = 0; k < H; ++k) ss = __builtin_fmaf(gr[k], gr[k], ss);
+  const float nrm = sqrtf(ss);
+  const float sc = (gradmax_clip > 0.0f && nrm > gradmax_clip) ? gradmax_clip / nrm : 1.0f;
+  for (uint32_t k = 0; k < H; ++k) Q[r * H + k] = clamp_(Q[r * H + k] - lr * (gr[k] * sc), lo, hi);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// CEM (hyper-parameters Control_Toolkit_ASF/config_optimizers.yml:1-11 "cem-tf"): the same rollout +
+// cost kernel, a different sampler and a top-k reduction instead of the soft-min.
+// Q[e,n,k] = clip(mean[e,k] + stdev[e,k] * z), z ~ N(0,1) from Philox (rollout, env, step pair, offset).
+__global__ __launch_bounds__(BLOCK) void cem_sample_kernel(const Params p, uint32_t E, const float* __restrict__ mean,
+                                                           const float* __restrict__ stdev, uint64_t seed, uint64_t offset,
+                                                           uint32_t env_offset, float* __restrict__ Q) {
+  const size_t r = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (r >= (size_t)E * p.N) return;
+  const uint32_t env = (uint32_t)(r / p.N), n = (uint32_t)(r % p.N);
+  const float* m = mean + (size_t)env * p.H;
+  const float* sd = stdev + (size_t)env * p.H;
+  float* q = Q + r * p.H;
+  for (uint32_t k = 0; k < p.H; k += 2) {
+    float z0, z1;
+    philox_normal_pair(seed, offset, env_offset + env, n, k >> 1, z0, z1);
+    q[k] = fminf(fmaxf(__builtin_fmaf(sd[k], z0, m[k]), p.lo), p.hi);
+    if (k + 1 < p.H) q[k + 1] = fminf(fmaxf(__builtin_fmaf(sd[k + 1], z1, m[k + 1]), p.lo), p.hi);
+  }
+}
+
+// cem-gmm: samples from a mixture of K Gaussians with equal weights — component c of env e is centred on the elite
+// sequence centres[e, c, :] and shares the per-time-step stdev[e, :] — clipped to the control limits.  The component of
+// a rollout comes from the same Philox stream as its normals (counter word `pair` = 0x80000000: never a real pair index).
+__global__ __launch_bounds__(BLOCK) void cem_gmm_sample_kernel(const Params p, uint32_t E, const float* __restrict__ centres,
+                                                               uint32_t K, const float* __restrict__ stdev, uint64_t seed,
+                                                               uint64_t offset, uint32_t env_offset, float* __restrict__ Q,
+                                                               uint32_t* __restrict__ comp_out) {
+  const size_t r = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  if (r >= (size_t)E * p.N) return;
+  const uint32_t env = (uint32_t)(r / p.N), n = (uint32_t)(r % p.N);
+  uint32_t c0 = n, c1 = env_offset + env, c2 = 0x80000000u, c3 = (uint32_t)offset;
+  philox4x32_10(c0, c1, c2, c3, (uint32_t)seed, (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32));
+  const uint32_t comp = (uint32_t)(((uint64_t)c0 * K) >> 32);              // uniform over 0 .. K-1
+  if (comp_out) comp_out[r] = comp;
+  const float* m = centres + ((size_t)env * K + comp) * p.H;
+  const float* sd = stdev + (size_t)env * p.H;
+  float* q = Q + r * p.H;
+  for (uint32_t k = 0; k < p.H; k += 2) {
+    float z0, z1;
+    philox_normal_pair(seed, offset, env_offset + env, n, k >> 1, z0, z1);
+    q[k] = fminf(fmaxf(__builtin_fmaf(sd[k], z0, m[k]), p.lo), p.hi);
+    if (k + 1 < p.H) q[k + 1] = fminf(fmaxf(__builtin_fmaf(sd[k + 1], z1, m[k + 1]), p.lo), p.hi);
+  }
+}
+
+// One block per env: sort (S, index) ascending with a bitonic network in LDS (ties by index = stable argsort), then
+// mean and population standard deviation of the best_k input sequences per time-step, stdev floored at stdev_min.
+__global__ __launch_bounds__(BLOCK) void cem_update_kernel(const Params p, const float* __restrict__ S,
+                                                           const float* __restrict__ Q, uint32_t best_k, float stdev_min,
+                                                           uint32_t Np, float* __restrict__ mean_out,
+                                                           float* __restrict__ stdev_out, uint32_t* __restrict__ elite_out) {
+  extern __shared__ float cem_lds[];                     // keys[Np], idx[Np]
+  float* key = cem_lds;
+  uint32_t* idx = reinterpret_cast<uint32_t*>(cem_lds + Np);
+  const uint32_t env = blockIdx.x, tid = threadIdx.x;
+  for (uint32_t i = tid; i < Np; i += BLOCK) {
+    key[i] = i < p.N ? S[(size_t)env * p.N + i] : INFINITY;
+    idx[i] = i;
+  }
+  __syncthreads();
+  for (uint32_t k = 2; k <= Np; k <<= 1) {
+    for (uint32_t j = k >> 1; j > 0; j >>= 1) {
+      for (uint32_t i = tid; i < Np; i += BLOCK) {
+        const uint32_t l = i ^ j;
+        if (l > i) {
+          const bool up = (i & k) == 0;
+          const float ki = key[i], kl = key[l];
+          const uint32_t ii = idx[i], il = idx[l];
+          const bool gt = (ki > kl) || (ki == kl && ii > il);
+          if (gt == up) { key[i] = kl; key[l] = ki; idx[i] = il; idx[l] = ii; }
+        }
+      }
+      __syncthreads();
+    }
+  }
+  if (elite_out) for (uint32_t i = tid; i < best_k; i += BLOCK) elite_out[(size_t)env * best_k + i] = idx[i];
+  const float* Qe = Q + (size_t)env * p.N * p.H;
+  for (uint32_t k = tid; k < p.H; k += BLOCK) {
+    float m = 0.0f;
+    for (uint32_t i = 0; i < best_k; ++i) m += Qe[(size_t)idx[i] * p.H + k];
+    m /= (float)best_k;
+    float v = 0.0f;
+    for (uint32_t i = 0; i < best_k; ++i) { const float d = Qe[(size_t)idx[i] * p.H + k] - m; v = __builtin_fmaf(d, d, v); }
+    mean_out[(size_t)env * p.H + k] = m;
+    stdev_out[(size_t)env * p.H + k] = fmaxf(sqrtf(v / (float)best_k), stdev_min);
+  }
+}
+
+// rollout_grad_kernel for the handle's cost (the three costs it is built for: cpmppi_rollout_cost_grad's checks)
+template <int INTEG>
+void launch_grad(uint32_t cost_id, dim3 grid, size_t lds, hipStream_t st, const Params& p, const GradPtrs& a) {
+  switch (cost_id) {
+    case CPMPPI_COST_QBGM: hipLaunchKernelGGL((rollout_grad_kernel<COST_QBGM, INTEG>), grid, dim3(BLOCK), lds, st, p, a); break;
+    case CPMPPI_COST_DEFAULT: hipLaunchKernelGGL((rollout_grad_kernel<COST_DEFAULT, INTEG>), grid, dim3(BLOCK), lds, st, p, a); break;
+    default: hipLaunchKernelGGL((rollout_grad_kernel<COST_QBG, INTEG>), grid, dim3(BLOCK), lds, st, p, a); break;
+  }
+}
+
+}  // namespace
+
+void allow_large_lds_optim() {
+  // the adjoint kernel parks S x 6 x 256 sub-states in LDS (61 KB at S = 10; more substeps need the opt-in as well)
+  allow_large_lds(&rollout_grad_kernel<COST_QBGM>);
+  allow_large_lds(&rollout_grad_kernel<COST_DEFAULT>);
+  allow_large_lds(&rollout_grad_kernel<COST_QBG>);
+  allow_large_lds(&rollout_grad_kernel<COST_QBGM, PREDICTOR_ODE>);
+  allow_large_lds(&rollout_grad_kernel<COST_DEFAULT, PREDICTOR_ODE>);
+  allow_large_lds(&rollout_grad_kernel<COST_QBG, PREDICTOR_ODE>);
+  // the CEM top-k sorts N (padded to a power of two) 8-byte records in LDS: 128 KB at N = 16384
+  allow_large_lds(&cem_update_kernel);
+}
+
+extern "C" {
+
+int cpmppi_rollout_cost(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs, const float* target_position,
+                        const float* target_equilibrium, const float* L, float* S_out, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (E == 0 || E > h->cfg.E || !s0 || !inputs || !target_position || !target_equilibrium || !S_out)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost: bad argument");
+  if (h->prm.cost_id == CPMPPI_COST_LEGACY)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost: plugin costs only");
+  CPMPPI_ON_DEVICE(h);
+  Params prm = h->prm;
+  prm.shift_mode = CPMPPI_SHIFT_NONE;
+  prm.cc_weight = 0.0f;
+  StepPtrs p{};
+  p.s0 = s0; p.u_nom = h->zeros_H; p.u_prev = nullptr; p.x_t = target_position; p.te = target_equilibrium; p.L = L;
+  p.noise = inputs; p.prev_in = nullptr; p.seed = 0; p.offset = 0; p.offset_dev = nullptr; p.env_offset = 0; p.stash = 0;
+  const uint32_t rpl = rollouts_per_lane(h, E);
+  p.nb = (h->cfg.N + BLOCK * rpl - 1) / (BLOCK * rpl);
+  p.W = h->cfg.H;
+  p.S_out = S_out; p.partial = h->workspace; p.counter = nullptr; p.u_nom_out = nullptr; p.Q_out = nullptr;
+  hipError_t e = launch_rollout(h, prm, rpl, CPMPPI_NOISE_DELTA_U, dim3(E * p.nb), (size_t)WAVES * p.W * sizeof(float),
+                                (hipStream_t)stream, p);
+  CPMPPI_HIP(h, e);
+  return CPMPPI_OK;
+}
+
+int cpmppi_rollout_cost_grad(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs,
+                             const float* target_position, const float* target_equilibrium, const float* L,
+                             const float* previous_input, float* S_out, float* grad_out, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (E == 0 || E > h->cfg.E || !s0 || !inputs || !target_position || !target_equilibrium || !grad_out)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: bad argument");
+  if (h->prm.cost_id == CPMPPI_COST_LEGACY)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: plugin costs only");
+  if (h->prm.qb_mode != 0u)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: no adjoint for quadratic_boundary / quadratic_boundary_nonconvex "
+                                       "(built: quadratic_boundary_grad_minimal, default, quadratic_boundary_grad)");
+  if (h->cfg.math_mode != CPMPPI_MATH_FAST)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: the adjoint is written for the FAST arithmetic");
+  const size_t lds = (size_t)h->cfg.S * 6 * BLOCK * sizeof(float);
+  if (lds > 150 * 1024) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: S too large for the LDS sub-state buffer (<= 25)");
+  CPMPPI_ON_DEVICE(h);
+  const size_t B = (size_t)E * h->cfg.N;
+  const size_t need = (size_t)h->cfg.H * 6 * (size_t)h->cfg.E * h->cfg.N;
+  if (h->grad_ckpt_floats < need) {
+    if (h->grad_ckpt) (void)hipFree(h->grad_ckpt);
+    h->grad_ckpt = nullptr; h->grad_ckpt_floats = 0;
+    CPMPPI_HIP(h, hipMalloc(&h->grad_ckpt, need * sizeof(float)));
+    h->grad_ckpt_floats = need;
+  }
+  GradPtrs a{s0, inputs, target_position, target_equilibrium, L, previous_input, h->grad_ckpt, S_out, grad_out, E};
+  const auto launch = h->cfg.ode_predictor == CPMPPI_ODE_CROMER ? launch_grad<PREDICTOR_ODE> : launch_grad<PREDICTOR_ODE_V0>;
+  launch(h->prm.cost_id, dim3((unsigned)((B + BLOCK - 1) / BLOCK)), lds, (hipStream_t)stream, h->prm, a);
+  return launched(h);
+}
+
+int cpmppi_adam_step(cpmppi_handle* h, uint32_t E, float* Q, const float* grad, float* m, float* v, uint32_t iteration,
+                     float learning_rate, float beta1, float beta2, float epsilon, float gradmax_clip, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (E == 0 || E > h->cfg.E || !Q || !grad || !m || !v || iteration == 0)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_adam_step: bad argument (iteration counts from 1)");
+  CPMPPI_ON_DEVICE(h);
+  const size_t rows = (size_t)E * h->cfg.N;
+  // Keras Adam: lr_t = lr * sqrt(1 - beta2^t) / (1 - beta1^t), epsilon outside the square root
+  const double lr_t = (double)learning_rate * sqrt(1.0 - pow((double)beta2, (double)iteration)) /
+                      (1.0 - pow((double)beta1, (double)iteration));
+  hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)((rows + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream,
+                     rows, h->cfg.H, Q, grad, m, v, (float)lr_t, beta1, beta2, epsilon, gradmax_clip, h->prm.lo, h->prm.hi);
+  return launched(h);
+}
+
+int cpmppi_sgd_step(cpmppi_handle* h, uint32_t E, float* Q, const float* grad, float learning_rate, float gradmax_clip,
+                    void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (E == 0 || E > h->cfg.E || !Q || !grad) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_sgd_step: bad argument");
+  CPMPPI_ON_DEVICE(h);
+  const size_t rows = (size_t)E * h->cfg.N;
+  hipLaunchKernelGGL(sgd_step_kernel, dim3((unsigned)((rows + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream,
+                     rows, h->cfg.H, Q, grad, learning_rate, gradmax_clip, h->prm.lo, h->prm.hi);
+  return launched(h);
+}
+
+int cpmppi_cem_sample(cpmppi_handle* h, uint32_t E, const float* mean, const float* stdev, uint64_t seed, uint64_t offset,
+                      uint32_t env_offset, float* Q_out, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (E == 0 || E > h->cfg.E || !mean || !stdev || !Q_out) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_sample: bad argument");
+  CPMPPI_ON_DEVICE(h);
+  const size_t rows = (size_t)E * h->cfg.N;
+  hipLaunchKernelGGL(cem_sample_kernel, dim3((unsigned)((rows + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream,
+                     h->prm, E, mean, stdev, seed, offset, env_offset, Q_out);
+  return launched(h);
+}
+
+int cpmppi_cem_gmm_sample(cpmppi_handle* h, uint32_t E, const float* centres, uint32_t K, const float* stdev, uint64_t seed,
+                          uint64_t offset, uint32_t env_offset, float* Q_out, uint32_t* component_out, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (E == 0 || E > h->cfg.E || !centres || K == 0 || !stdev || !Q_out)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_gmm_sample: bad argument");
+  CPMPPI_ON_DEVICE(h);
+  const size_t rows = (size_t)E * h->cfg.N;
+  hipLaunchKernelGGL(cem_gmm_sample_kernel, dim3((unsigned)((rows + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream,
+                     h->prm, E, centres, K, stdev, seed, offset, env_offset, Q_out, component_out);
+  return launched(h);
+}
+
+int cpmppi_cem_update(cpmppi_handle* h, uint32_t E, const float* S, const float* Q, uint32_t best_k, float stdev_min,
+                      float* mean_out, float* stdev_out, uint32_t* elite_idx_out, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (E == 0 || !S || !Q || !mean_out || !stdev_out || best_k == 0 || best_k > h->cfg.N)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_update: bad argument (0 < best_k <= N)");
+  uint32_t Np = 1;
+  while (Np < h->cfg.N) Np <<= 1;
+  if ((size_t)Np * 8 > 160 * 1024 - 1024) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_update: N too large for the LDS sort (<= 16384)");
+  CPMPPI_ON_DEVICE(h);
+  hipLaunchKernelGGL(cem_update_kernel, dim3(E), dim3(BLOCK), (size_t)Np * 8, (hipStream_t)stream, h->prm, S, Q, best_k,
+                     stdev_min, Np, mean_out, stdev_out, elite_idx_out);
+  return launched(h);
+}
+
+}  // extern "C"

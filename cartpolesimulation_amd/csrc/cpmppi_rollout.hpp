@@ -1055,9 +1055,10 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
 }  // namespace cpmppi_k
 
 // Every instantiation of rollout_cost_kernel, by the translation unit that compiles it.  X(COST, FAST, NOISE, R, VARIANT).
-// The units define them with CPMPPI_DEFINE_ROLLOUT, cpmppi.hip declares ALL of them extern with CPMPPI_DECLARE_ROLLOUT —
-// an instantiation missing there would be compiled a second time in cpmppi.hip with that unit's flags, and the runtime
-// would launch whichever copy registered last.
+// The units define them with CPMPPI_DEFINE_ROLLOUT, cpmppi.hip (the hot-path unit, the only one that launches them) declares
+// ALL of them extern with CPMPPI_DECLARE_ROLLOUT — an instantiation missing there would be compiled a second time in
+// cpmppi.hip with that unit's flags, and the runtime would launch whichever copy registered last.  The other units include
+// this header (through cpmppi_internal.hpp) for StepPtrs, GatherSync and the constants only, and instantiate nothing of it.
 #define CPMPPI_FOR_COSTS(X, FAST, NOISE, R, V) \
   X(COST_QBGM, FAST, NOISE, R, V) X(COST_DEFAULT, FAST, NOISE, R, V) X(COST_LEGACY, FAST, NOISE, R, V) X(COST_QBG, FAST, NOISE, R, V)
 #define CPMPPI_FOR_NOISES(X, FAST, R, V)                                                        \
