@@ -142,17 +142,15 @@ hipError_t launch_rollout_noise(uint32_t noise, dim3 grid, size_t lds, hipStream
   return hipGetLastError();
 }
 
-// Which build of the kernel a launch gets (measured on MI355X, tools/kbench.py / tools/dev/r3_cross.sh):
+// Which build of the kernel a launch gets (measured on MI355X with tools/kbench.py; profiles/HISTORY.md, "Round 3 and earlier":
+// the 1.5 M crossover):
 //   one rollout per lane : latency build up to one wave per SIMD (1024 SIMDs x 64 lanes), throughput build above
 //   two rollouts per lane: mid-size build (phased horizon loop: quiet control steps and eventful ones in separate loops) up
 //                          to 1572864 rollouts - variant 3 (quiet step unrolled) while the launch has at most one wave
 //                          per SIMD, variant 2 above - and the throughput build beyond.  Phased mid-size vs throughput build,
 //                          envs x 1024 x 50: 256 envs 126 vs 133 us, 1024 envs 350 vs 355, 1536 envs 482 vs 495, 2048 envs
 //                          630 vs 636, 3072 envs 904 vs 890, 8192 envs 2.34 vs 2.29 ms
-#ifndef CPMPPI_MID_SIZE_MAX
-#define CPMPPI_MID_SIZE_MAX 1572864ull
-#endif
-constexpr uint64_t MID_SIZE_MAX_ROLLOUTS = CPMPPI_MID_SIZE_MAX;   // (a -D override exists for A/B builds only)
+constexpr uint64_t MID_SIZE_MAX_ROLLOUTS = 1572864ull;
 static uint64_t lone_form_max_waves() { return g_knobs.lone_form_max_waves; }
 // (round 5, tools/variant_sweep.py: between 65536 and 131072 rollouts - where the size rule still picks one rollout per lane - the
 // straight-line latency build beats the throughput build's loop: 48 x 2048 x 50 71.3 vs 79.8 us, 96 x 1024 x 50 74.9 vs 83.3)
@@ -173,14 +171,10 @@ hipError_t launch_rollout_math(uint32_t math, uint32_t ode, uint32_t rpl, uint32
   if (math == CPMPPI_MATH_FAST) {
     // the throughput build reads its per-env constants from a.env_fold: written here, on the same stream, first
     auto fold_first = [&]() -> hipError_t {
-#if CPMPPI_ENV_FOLD
       const uint32_t envs = grid.x / a.nb;
       hipLaunchKernelGGL(fold_env_kernel, dim3((envs + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, p, a.L, a.te, a.s0,
                          const_cast<EnvFold*>(a.env_fold), envs);
       return hipGetLastError();
-#else
-      return hipSuccess;
-#endif
     };
     if (rpl == 2) {
       const bool mid = (uint64_t)grid.x * BLOCK * 2 <= MID_SIZE_MAX_ROLLOUTS;

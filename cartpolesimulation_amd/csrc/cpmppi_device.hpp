@@ -77,6 +77,20 @@ static __device__ unsigned int g_wave_hw[16384][2];
 #define CPMPPI_DBG(i, n) ((void)0)
 #define CPMPPI_DBG_STAMP(slot) ((void)0)
 #endif
+// -DCPMPPI_SECTION_STAMPS on top of -DCPMPPI_DEBUG_COUNTERS: the stamp at a section boundary of a control step (g_wave_sec above)
+#if defined(CPMPPI_DEBUG_COUNTERS) && defined(CPMPPI_SECTION_STAMPS)
+// the state is pinned in front of the stamp (an opaque asm it passes through), so a section's arithmetic cannot drift
+// across its boundary
+#define CPMPPI_SEC(sec, i, ST)                                                                                          \
+  do {                                                                                                                 \
+    asm volatile("" : "+v"((ST).th), "+v"((ST).w), "+v"((ST).c), "+v"((ST).s), "+v"((ST).x), "+v"((ST).v));           \
+    const unsigned now_ = (unsigned)__builtin_amdgcn_s_memtime();                                                      \
+    (sec)[i] += now_ - (sec)[7];                                                                                       \
+    (sec)[7] = now_;                                                                                                   \
+  } while (0)
+#else
+#define CPMPPI_SEC(sec, i, ST) ((void)0)
+#endif
 
 constexpr float PI_F = 3.14159274101257324f;       // float32(np.pi)
 constexpr float TWO_PI_F = 6.28318548202514648f;   // float32(2*np.pi)
@@ -106,10 +120,6 @@ struct Params {
 // Per-env constants.  PRECISE keeps the reference's operands; FAST folds them (all wave-uniform).
 constexpr float ROT_LIMIT_LO = 0.125f;
 constexpr float ROT_LIMIT = 0.25f;
-#ifndef CPMPPI_SEED_LO
-#define CPMPPI_SEED_LO 1        // packed path: the carried pair is seeded from the degree-5/4 polynomials (|w t| <= 0.125)
-#endif
-constexpr float ROT_LIMIT_SEED = CPMPPI_SEED_LO ? ROT_LIMIT_LO : ROT_LIMIT;     // (see rot_pair_lo / rot_pair below)
 
 struct EnvConst {
   float L, Lh;
@@ -117,8 +127,10 @@ struct EnvConst {
   float mg, JinvLh, kmLh, kM, g_i, cT_i, inv_kLh, inv_halfL;
   float uK_scale;                    // (k+1) u_max: FAST forms (k+1) u = (k+1) u_max Q with one product
   float t1_i;                        // inv_kLh / m_pole: g_i s - cT_i w = t1_i (m_p g s - J/Lh w), the bracket xDD's numerator forms anyway
-  float tg_i, tcT_i, tinv_kLh;       // the same three angleDD coefficients times the substep length t
-  float wlim;                        // ROT_LIMIT_SEED / t: |w| beyond it leaves the carried rotation pair's seed range (packed path)
+  float tg_i, tcT_i, tinv_kLh;       // the same three angleDD coefficients times the substep length t (no reader since the form
+                                     // that folded t in was removed; kept: they are part of EnvFold's layout, which the
+                                     // throughput kernels' scalar loads address - without them seven units' code moves)
+  float wlim;                        // ROT_LIMIT_LO / t: |w| beyond it leaves the carried rotation pair's seed range (packed path)
 };
 
 __device__ __forceinline__ EnvConst make_env_const(const Params& p, float L) {
@@ -144,7 +156,7 @@ __device__ __forceinline__ EnvConst make_env_const(const Params& p, float L) {
   c.tg_i = (float)(t * (double)p.g * inv_kLh);
   c.tcT_i = (float)(t * ((double)p.J_fric / ((double)p.m_pole * Lh) * inv_kLh));
   c.tinv_kLh = (float)(t * inv_kLh);
-  c.wlim = ROT_LIMIT_SEED / p.t_step;
+  c.wlim = ROT_LIMIT_LO / p.t_step;
   return c;
 }
 
@@ -186,17 +198,7 @@ template <> __device__ __forceinline__ f2 splat<f2>(float x) { return f2{x, x}; 
 __device__ __forceinline__ float fma_(float a, float b, float c) { return __builtin_fmaf(a, b, c); }
 __device__ __forceinline__ f2 fma_(f2 a, f2 b, f2 c) { return __builtin_elementwise_fma(a, b, c); }
 __device__ __forceinline__ float rcp_(float a) { return __builtin_amdgcn_rcpf(a); }
-#ifndef CPMPPI_RCP_SHARED
-#define CPMPPI_RCP_SHARED 0     // float2: one v_rcp_f32 (a quarter-rate instruction) for both lanes, 1/(ab) * (b, a)
-#endif
-__device__ __forceinline__ f2 rcp_(f2 a) {
-#if CPMPPI_RCP_SHARED
-  const float r = __builtin_amdgcn_rcpf(a.x * a.y);
-  return f2{r, r} * a.yx;
-#else
-  return f2{__builtin_amdgcn_rcpf(a.x), __builtin_amdgcn_rcpf(a.y)};
-#endif
-}
+__device__ __forceinline__ f2 rcp_(f2 a) { return f2{__builtin_amdgcn_rcpf(a.x), __builtin_amdgcn_rcpf(a.y)}; }
 __device__ __forceinline__ float rint_(float a) { return __builtin_rintf(a); }
 __device__ __forceinline__ f2 rint_(f2 a) { return f2{__builtin_rintf(a.x), __builtin_rintf(a.y)}; }
 __device__ __forceinline__ float abs_(float a) { return __builtin_fabsf(a); }
@@ -227,37 +229,7 @@ __device__ __forceinline__ f2 cos_(f2 a) { return f2{cosf(a.x), cosf(a.y)}; }
 
 // ------------------------------------------------------------------------------------------------------------------
 // sincos on [-pi_f32, pi_f32] (the angle is wrapped every substep, so the argument never leaves this range).
-// Cody-Waite reduction to |r| <= pi/4 with q in {-2..2} (q*PIO2_HI is exact), then the classic single-precision
-// minimax polynomials; <= 1.5 ulp for both outputs over the range.
-template <class F>
-__device__ __forceinline__ void sincos_pi(F x, F& sn, F& cs) {
-  constexpr float TWO_OVER_PI = 0.636619746685028076f;
-  constexpr float PIO2_HI = 1.57079637050628662f;
-  constexpr float PIO2_LO = -4.37113900018624283e-8f;
-  const F q = rint_(x * splat<F>(TWO_OVER_PI));
-  F r = fma_(-q, splat<F>(PIO2_HI), x);
-  r = fma_(-q, splat<F>(PIO2_LO), r);
-  const F r2 = r * r;
-  F ps = fma_(r2, splat<F>(-1.9515295891e-4f), splat<F>(8.3321608736e-3f));
-  ps = fma_(ps, r2, splat<F>(-1.6666654611e-1f));
-  const F S = fma_(ps * r2, r, r);
-  F pc = fma_(r2, splat<F>(2.443315711809948e-5f), splat<F>(-1.388731625493765e-3f));
-  pc = fma_(pc, r2, splat<F>(4.166664568298827e-2f));
-  const F C = fma_(pc * r2, r2, fma_(splat<F>(-0.5f), r2, splat<F>(1.0f)));
-#pragma unroll
-  for (int i = 0; i < Width<F>::value; ++i) {
-    const int n = (int)get(q, i);
-    const bool swap = (n & 1) != 0;
-    const float s0 = swap ? get(C, i) : get(S, i);
-    const float c0 = swap ? get(S, i) : get(C, i);
-    const uint32_t sflip = ((uint32_t)n & 2u) << 30;
-    const uint32_t cflip = ((uint32_t)(n + 1) & 2u) << 30;
-    put(sn, i, __uint_as_float(__float_as_uint(s0) ^ sflip));
-    put(cs, i, __uint_as_float(__float_as_uint(c0) ^ cflip));
-  }
-}
-
-// Variant without per-lane quadrant selects: reduce by multiples of pi to |r| <= pi/2 (q in {-1,0,1}, q*PI_HI exact),
+// No per-lane quadrant selects: reduce by multiples of pi to |r| <= pi/2 (q in {-1,0,1}, q*PI_HI exact),
 // sin x = (-1)^q sin r, cos x = (-1)^q cos r; the sign is a multiply, so every instruction has a packed float2 form.
 // Polynomials: sin r = r + r z P3(z), cos r = 1 + z Q4(z), z = r^2, fitted on [-pi/2, pi/2] (Lawson-weighted
 // least squares, coefficients rounded to float32): relative error 1.2e-8 (sin), absolute 4.9e-9 (cos) before rounding.
@@ -285,26 +257,6 @@ __device__ __forceinline__ void sincos_pi_half(F x, F& sn, F& cs) {
   Q = fma_(Q, z, splat<F>(-0.5f));
   cs = fma_(z * sg, Q, sg);
 }
-
-#ifndef CPMPPI_SINCOS_MODE
-#define CPMPPI_SINCOS_MODE 1    // 0: pi/4 reduction + quadrant selects   1: pi/2 reduction + sign multiply
-#endif
-#ifndef CPMPPI_WRAP_MODE
-#if defined(CPMPPI_DEBUG_COUNTERS) && defined(CPMPPI_SECTION_STAMPS)
-// the state is pinned in front of the stamp (an opaque asm it passes through), so a section's arithmetic cannot drift
-// across its boundary
-#define CPMPPI_SEC(sec, i, ST)                                                                                          \
-  do {                                                                                                                 \
-    asm volatile("" : "+v"((ST).th), "+v"((ST).w), "+v"((ST).c), "+v"((ST).s), "+v"((ST).x), "+v"((ST).v));           \
-    const unsigned now_ = (unsigned)__builtin_amdgcn_s_memtime();                                                      \
-    (sec)[i] += now_ - (sec)[7];                                                                                       \
-    (sec)[7] = now_;                                                                                                   \
-  } while (0)
-#else
-#define CPMPPI_SEC(sec, i, ST) ((void)0)
-#endif
-#define CPMPPI_WRAP_MODE 1      // 0: the reference's two comparisons     1: theta - 2pi*rint(theta/2pi)
-#endif
 
 template <class F>
 struct State {
@@ -371,28 +323,6 @@ __device__ __forceinline__ void plant_substep(State<float>& st, float aDD, float
   st.w = w1; st.x = x1; st.v = v1;
 }
 
-#ifndef CPMPPI_NEWTON
-#define CPMPPI_NEWTON 0         // 0: num * v_rcp_f32(A) (<= 1.5 ulp; measured deviation identical)   1: + one Newton correction
-#endif
-#ifndef CPMPPI_FOLD_T
-#define CPMPPI_FOLD_T 0         // 1: fold t into the angleDD coefficients (-1 instruction; measured: 2.4x the deviation, so off)
-#endif
-#ifndef CPMPPI_T1_REUSE
-#define CPMPPI_T1_REUSE 1       // angleDD from the numerator's own bracket (-1 instruction per substep)
-#endif
-#ifndef CPMPPI_LATENCY_NEAR
-#define CPMPPI_LATENCY_NEAR 0   // one rollout per lane: the last substep tests the edge directly (no coarser "near" limit)
-#endif
-#ifndef CPMPPI_QBGM_FOLD
-#define CPMPPI_QBGM_FOLD 1      // FAST: folded factors in quadratic_boundary_grad_minimal's stage cost
-#endif
-#ifndef CPMPPI_HOIST_SPIN
-#define CPMPPI_HOIST_SPIN 1     // test |w t| once per control step (<= 0.1) instead of every substep (<= 0.125)
-#endif
-#ifndef CPMPPI_ROTATE
-#define CPMPPI_ROTATE 1         // 1: rotate (cos, sin) on intermediate substeps, full wrap + sincos at the control step's end
-#endif
-
 // ODE + simultaneous forward Euler of one substep with folded constants (FAST).  Outputs the un-wrapped new state.
 //   A    = (k+1)(m_c+m_p) - m_p c^2
 //   xDD  = [ c (m_p g s - J/Lh w) - (k+1) m_p Lh w^2 s - (k+1) M_fric v + (k+1) u ] / A
@@ -407,29 +337,16 @@ __device__ __forceinline__ void ode_euler_fast(const State<F>& st, F uK, float t
   num = fma_(-((w * w) * splat<F>(e.kmLh)), s, num);
   num = fma_(splat<F>(-e.kM), v, num);
   const F r = rcp_(A);                                  // A in [0.33, 0.43]: no scaling needed
-#if CPMPPI_NEWTON
-  const F q0 = num * r;
-  const F xDD = fma_(fma_(-A, q0, num), r, q0);
-#else
-  const F xDD = num * r;
-#endif
+  const F xDD = num * r;                                // (<= 1.5 ulp; one Newton correction on top measured the identical deviation: removed, see history)
   const F tt = splat<F>(t);
   th1 = fma_(w, tt, st.th);
-  // (do NOT fold "1 - cT*t" into one constant: its rounding error would bias w the same way every substep)
-#if CPMPPI_FOLD_T
-  // w + t*aDD with t folded into the three coefficients (each product still rounds relative to its own size)
-  w1 = fma_(splat<F>(e.tg_i), s, fma_(xDD * c, splat<F>(e.tinv_kLh), fma_(w, splat<F>(-e.tcT_i), w)));
-#elif CPMPPI_T1_REUSE
+  // (do NOT fold "1 - cT*t" into one constant: its rounding error would bias w the same way every substep; measured against
+  // the form that folded t into the three angleDD coefficients - one instruction fewer, 2.4x the deviation: removed, see history)
   // g s + T/(m_p Lh) is the bracket t1 = m_p g s - (J/Lh) w of xDD's numerator divided by m_p: one product instead of a
-  // product and an FMA per substep (same formula, one rounding placed differently)
+  // product and an FMA per substep (same formula, one rounding placed differently; -1 instruction per substep)
   const F aDD = fma_(xDD * c, splat<F>(e.inv_kLh), t1 * splat<F>(e.t1_i));
   w1 = fma_(aDD, tt, w);
   if (aDD_out) *aDD_out = aDD;
-#else
-  const F aDD = fma_(splat<F>(e.g_i), s, fma_(xDD * c, splat<F>(e.inv_kLh), -(w * splat<F>(e.cT_i))));
-  w1 = fma_(aDD, tt, w);
-  if (aDD_out) *aDD_out = aDD;
-#endif
   x1 = fma_(v, tt, st.x);
   v1 = fma_(xDD, tt, v);
 }
@@ -458,8 +375,8 @@ __device__ __forceinline__ F wrap_rint(F th) {
 // |d| = |w t| > 0.25 means an angular velocity beyond 125 rad/s at t = 2 ms; such a lane is evaluated with the exact
 // wrap + sincos on every substep (it practically never happens: a pole released from rest tops out near 20 rad/s).
 // (ROT_LIMIT_LO = 0.125, ROT_LIMIT = 0.25: defined ahead of EnvConst, which carries the seed's limit as an angular velocity)
-// Packed path: the range of |w t| within which a control step runs on the carried rotation pair, ROT_LIMIT_SEED.  Seeded from
-// rot_pair_lo (CPMPPI_SEED_LO; two instructions fewer per control step than the degree-7/6 pair; truncation below 1e-9 up to
+// Packed path: the range of |w t| within which a control step runs on the carried rotation pair is ROT_LIMIT_LO.  Seeded from
+// rot_pair_lo (two instructions fewer per control step than the degree-7/6 pair; truncation below 1e-9 up to
 // 0.125 rad per substep = 62 rad/s at t = 2 ms - a pole released from rest tops out near 20), lanes beyond take the exact sincos
 // on every substep.
 
@@ -618,9 +535,9 @@ __device__ __forceinline__ bool substep_fast(State<F>& st, F uK, float t, const 
 // wrap + sincos (substep_fast), so the states observed at control-step granularity carry at most S-1 rotations of drift
 // (~2e-7).  Lanes that bounce, or spin faster than 0.125 rad per substep, are re-evaluated in the cold branch
 // (rare_lane: a higher-degree rotation up to 0.25 rad per substep, the exact wrap + sincos beyond).
-// EVENTS: 1 = rare events behind a wave-uniform branch, 0 = none handled — only the wave mask of lanes that WOULD need it
-// is returned (the caller rolls the substeps back), 2 = the event arithmetic inline on every call.
-template <class F, bool CHECK_SPIN = true, int EVENTS = 1>
+// EVENTS: true = rare events behind a wave-uniform branch, false = none handled — only the wave mask of lanes that WOULD
+// need it is returned (tools/dev/lone_wave.hip: the substep's own cost).
+template <class F, bool EVENTS = true>
 __device__ __forceinline__ uint64_t substep_fast_rot(State<F>& st, F uK, float t, const Params& p, const EnvConst& e) {
   constexpr int W = Width<F>::value;
   F th1, w1, x1, v1;
@@ -634,9 +551,9 @@ __device__ __forceinline__ uint64_t substep_fast_rot(State<F>& st, F uK, float t
 #pragma unroll
   for (int i = 0; i < W; ++i) {
     fired |= __builtin_amdgcn_fcmpf(__builtin_fabsf(get(x1, i)), p.THL, 3);                        // 3 = ordered >=
-    if constexpr (CHECK_SPIN) fired |= __builtin_amdgcn_fcmpf(__builtin_fabsf(get(d, i)), ROT_LIMIT_LO, 2);   // 2 = ordered >
+    fired |= __builtin_amdgcn_fcmpf(__builtin_fabsf(get(d, i)), ROT_LIMIT_LO, 2);                  // 2 = ordered >
   }
-  if (EVENTS == 2 || (EVENTS == 1 && __builtin_expect(fired != 0, 0))) {
+  if (EVENTS && __builtin_expect(fired != 0, 0)) {
     CPMPPI_DBG(4, 1);
     // plain bounces of lanes inside the rotation range: masked, all lanes at once; everything else per lane (deep)
     F m;
@@ -644,7 +561,7 @@ __device__ __forceinline__ uint64_t substep_fast_rot(State<F>& st, F uK, float t
 #pragma unroll
     for (int i = 0; i < W; ++i) {
       const bool hit = __builtin_fabsf(get(x1, i)) >= p.THL;
-      const bool spin = CHECK_SPIN && __builtin_fabsf(get(d, i)) > ROT_LIMIT_LO;
+      const bool spin = __builtin_fabsf(get(d, i)) > ROT_LIMIT_LO;
       put(m, i, (hit && !spin) ? 1.0f : 0.0f);
       deep |= spin;
     }
@@ -658,7 +575,7 @@ __device__ __forceinline__ uint64_t substep_fast_rot(State<F>& st, F uK, float t
     if (__builtin_expect(__builtin_amdgcn_ballot_w64(deep) != 0, 0)) {
 #pragma unroll
       for (int i = 0; i < W; ++i) {
-        const bool spin = CHECK_SPIN && __builtin_fabsf(get(d, i)) > ROT_LIMIT_LO;
+        const bool spin = __builtin_fabsf(get(d, i)) > ROT_LIMIT_LO;
         if (spin || __builtin_fabsf(get(dl, i)) > ROT_LIMIT) {
           float thi = get(th0, i), wi = get(w0, i), xi = get(x0, i), vi = get(v0, i), ci = get(c0, i), si = get(s0, i);
           rare_lane(thi, wi, xi, vi, ci, si, !spin, get(st.c, i), get(st.s, i), get(d, i), t, p.THL, e.inv_halfL);
@@ -672,25 +589,12 @@ __device__ __forceinline__ uint64_t substep_fast_rot(State<F>& st, F uK, float t
   return fired;
 }
 
-#ifndef CPMPPI_EVENTFUL_LAST_INLINE
-#define CPMPPI_EVENTFUL_LAST_INLINE 1
-#endif
-#ifndef CPMPPI_LATENCY_UNROLL
-#define CPMPPI_LATENCY_UNROLL 1
-#endif
-#ifndef CPMPPI_ROLLBACK
-#define CPMPPI_ROLLBACK 1       // packed builds, quadratic_boundary_grad_minimal (control_step_fast): 0 = an edge test per substep,
-#endif                          // 1 = one per three substeps, the triple redone on an event (A/B switch)
-#ifndef CPMPPI_INCR_ROT
-#define CPMPPI_INCR_ROT 1       // packed path: (cos d, sin d) of d = w t advanced by d' - d = angleDD t^2 instead of re-evaluated
-#endif
-
 // Intermediate substep of the packed path with the rotation's (cos d, sin d) carried along: d = w t changes by
 // eps = angleDD t^2 (up to ~1e-3 for a fast-spinning pole) per substep, so
 //     (cd, sd) <- (cd - eps sd - eps^2/2, sd + eps cd)
 // replaces the two Taylor polynomials (4 instead of 7 instructions; truncation O(eps^3) in cd, eps^2 sd / 2 in sd:
 // <= 2e-7 at the range limit |sd| = 0.25, <= 1e-8 for ordinary angular velocities).  The pair is seeded from the
-// degree-7/6 polynomials at every control step, and the control step's last substep re-synchronises (cos, sin) exactly
+// degree-5/4 polynomials (rot_pair_lo) at every control step, and the control step's last substep re-synchronises (cos, sin) exactly
 // as before.  Rare lanes are handled PER LANE in the wave-uniform cold branch (rare_lane) — a lane that hits the track
 // edge bounces with the cosine it already carries, is rotated on by its new angular velocity and re-seeds its pair; a
 // lane whose |w t| exceeded ROT_LIMIT at the start of the control step or after a bounce (`beyond`: its edge limit
@@ -782,7 +686,7 @@ __device__ __forceinline__ uint64_t substep_fast_rot_carried(State<F>& st, F uK,
 // substeps 3, 6 and 9 decides: no rollout of the wave reached the edge -> the copy is the state (the common case: 9 x 27 + 3
 // vector instructions instead of 9 x 29); otherwise the triple is discarded and the loop with the per-substep test and the event
 // arithmetic integrates from that triple's entry state to the end of the control step.  A rollout's arithmetic is the same on
-// both routes (bit-identical results with the switch off).  Measured first with one test per control step: an event then wastes
+// both routes (bit-identical results against the form with an edge test per substep; removed, see history).  Measured first with one test per control step: an event then wastes
 // the whole step and SQ_INSTS_VALU did not move (profiles/HISTORY.md).
 // `at_edge` (in/out; required with SPIN_BRANCH): a wave one of whose rollouts ENDED the previous control step at or beyond the edge
 // does not speculate - a rollout caught there bounces on every substep, for tens of control steps (see bounce_masked).
@@ -794,7 +698,6 @@ __device__ __forceinline__ bool control_step_fast(State<F>& st, F uK, uint32_t S
   // at or beyond the track edge, or spin beyond the rotation range?  It bounces on the very next substep - and, caught
   // beyond the edge, on every one after it (cartpole_equations.py:341-347 flips v whichever way it points) - so the caller
   // integrates the next control step with the event arithmetic inline (control_step_fast_eventful).
-#if CPMPPI_ROTATE && CPMPPI_HOIST_SPIN
   if constexpr (Width<F>::value == 1) {
     // one rollout per lane is the small-launch (latency-bound) mapping: there the per-substep test, which overlaps with
     // the arithmetic, is faster than the shorter loop with its test at the head (single env: 70 us vs 80 us)
@@ -806,7 +709,6 @@ __device__ __forceinline__ bool control_step_fast(State<F>& st, F uK, uint32_t S
     // at 61 ns against the compiler's 64 - a lone wave issues these three-operand instructions at ~4.5 cycles each
     // whatever their order, so only fewer instructions would help)
     if (sec) CPMPPI_SEC(sec, 2, st);
-#if CPMPPI_LATENCY_UNROLL
     if (S == 10u) {
       // the reference's intermediate_steps = 10 as straight-line code: a wave that has its SIMD to itself pays ~50 cycles
       // for every TAKEN branch (the instruction buffer refills from the cache; how many depends on where the target
@@ -819,24 +721,20 @@ __device__ __forceinline__ bool control_step_fast(State<F>& st, F uK, uint32_t S
       // and branch per triple: 48.9 -> 51.8 us, 256 x 20 24.7 -> 25.9, 64 envs 52.6 -> 56.5.  Not for one rollout per lane.)
 #pragma unroll
       for (int sub = 0; sub < 9; ++sub) substep_fast_rot<F>(st, uK, t, p, e);
-    } else
-#endif
-    {
+    } else {
       for (uint32_t sub = 0; sub + 1 < S; ++sub) substep_fast_rot<F>(st, uK, t, p, e);
     }
     if (sec) CPMPPI_SEC(sec, 3, st);
-    const bool near_one = substep_fast<F, true, (CPMPPI_LATENCY_NEAR != 0)>(st, uK, t, p, e, nearlim);
+    const bool near_one = substep_fast<F, true, false>(st, uK, t, p, e, nearlim);     // (the edge itself: no coarser "near" limit)
     if (sec) CPMPPI_SEC(sec, 4, st);
     return near_one;
   }
-  // The seed needs |w t| <= ROT_LIMIT_SEED.  Tested once per control step: without a bounce w cannot leave the range within
+  // The seed needs |w t| <= ROT_LIMIT_LO.  Tested once per control step: without a bounce w cannot leave the range within
   // one control step by more than the polynomials' margin, and a lane that bounces is re-tested.  Lanes beyond the
   // range are flagged and take the exact sincos on every substep.
-#if CPMPPI_INCR_ROT
-  bool check = true;
   F xlim = splat<F>(p.THL);
   float xmax = 0.0f;                            // ROLLBACK: the lane's largest |x| over the substeps not yet tested
-  const float wlim = e.wlim;                    // = ROT_LIMIT_SEED / t: |w t| > the seed's range as one compare with a free abs modifier per lane
+  const float wlim = e.wlim;                    // = ROT_LIMIT_LO / t: |w t| > the seed's range as one compare with a free abs modifier per lane
   uint64_t spinning = 0;      // wave mask of lanes beyond the rotation range: the same compare as the select's (one v_cmp)
   if constexpr (SPIN_BRANCH && Width<F>::value == 2) {
     const float wmax = max_abs2_(get(st.w, 0), get(st.w, 1));
@@ -848,7 +746,7 @@ __device__ __forceinline__ bool control_step_fast(State<F>& st, F uK, uint32_t S
 #pragma unroll
       for (int i = 0; i < Width<F>::value; ++i) put(xlim, i, !(__builtin_fabsf(get(st.w, i)) > wlim) ? p.THL : -1.0f);
     }
-  } else if (check) {
+  } else {
 #pragma unroll
     for (int i = 0; i < Width<F>::value; ++i) {
       const bool within = !(__builtin_fabsf(get(st.w, i)) > wlim);
@@ -859,8 +757,7 @@ __device__ __forceinline__ bool control_step_fast(State<F>& st, F uK, uint32_t S
     }
   }
   F cd, sd;
-  if constexpr (CPMPPI_SEED_LO != 0) rot_pair_lo<F>(st.w * splat<F>(t), cd, sd);
-  else rot_pair<F>(st.w * splat<F>(t), cd, sd);
+  rot_pair_lo<F>(st.w * splat<F>(t), cd, sd);
   uint32_t left = S - 1u;                         // intermediate substeps the loop below still has to integrate
   if constexpr (ROLLBACK && Width<F>::value == 2) {
     // three tests per control step (after substeps 3, 6, 9; the reference's intermediate_steps = 10 only): an event discards at
@@ -904,53 +801,29 @@ __device__ __forceinline__ bool control_step_fast(State<F>& st, F uK, uint32_t S
   // one v_max3 test per triple, the discarded triple redone substep by substep with the event arithmetic inline - until
   // section stamps showed that build's median wave 17 % slower per control step than this plain loop, in every section:
   // DESIGN.md §4.  The phased horizon loop replaced it; the code is in the history.)
-  {
-    if (sec) { asm volatile("" : "+v"(cd), "+v"(sd), "+v"(xlim)); CPMPPI_SEC(sec, 2, st); }
-    if (QUIET_UNROLL && !ROLLBACK && S == 10u) {
-      // the quiet control step of the phased mid-size build in a launch of one wave per SIMD, the reference's
-      // intermediate_steps = 10: the nine substeps as straight-line code - a lone wave pays ~50 cycles per taken branch
-      // (see the one-rollout-per-lane mapping above), and the loop's back edge is one per substep
+  if (sec) { asm volatile("" : "+v"(cd), "+v"(sd), "+v"(xlim)); CPMPPI_SEC(sec, 2, st); }
+  if (QUIET_UNROLL && !ROLLBACK && S == 10u) {
+    // the quiet control step of the phased mid-size build in a launch of one wave per SIMD, the reference's
+    // intermediate_steps = 10: the nine substeps as straight-line code - a lone wave pays ~50 cycles per taken branch
+    // (see the one-rollout-per-lane mapping above), and the loop's back edge is one per substep
 #pragma unroll
-      for (int sub = 0; sub < 9; ++sub) substep_fast_rot_carried<F, false>(st, uK, t, p, e, cd, sd, xlim, check);
-    } else if (QUIET_UNROLL && ROLLBACK && S == 10u) {
-      // (the lone-wave build after a discarded triple: 9, 6 or 3 substeps left, whole triples as straight-line code)
-      for (; left != 0u; left -= 3u) {
+    for (int sub = 0; sub < 9; ++sub) substep_fast_rot_carried<F, false>(st, uK, t, p, e, cd, sd, xlim);
+  } else if (QUIET_UNROLL && ROLLBACK && S == 10u) {
+    // (the lone-wave build after a discarded triple: 9, 6 or 3 substeps left, whole triples as straight-line code)
+    for (; left != 0u; left -= 3u) {
 #pragma unroll
-        for (int sub = 0; sub < 3; ++sub) substep_fast_rot_carried<F, false>(st, uK, t, p, e, cd, sd, xlim, check);
-      }
-    } else {
-      for (; left != 0u; --left) substep_fast_rot_carried<F, false>(st, uK, t, p, e, cd, sd, xlim, check);
+      for (int sub = 0; sub < 3; ++sub) substep_fast_rot_carried<F, false>(st, uK, t, p, e, cd, sd, xlim);
     }
-    if (sec) CPMPPI_SEC(sec, 3, st);
+  } else {
+    for (; left != 0u; --left) substep_fast_rot_carried<F, false>(st, uK, t, p, e, cd, sd, xlim);
   }
-  const bool near_end = substep_fast<F>(st, uK, t, p, e, nearlim, check, at_edge) && check;
+  if (sec) CPMPPI_SEC(sec, 3, st);
+  const bool near_end = substep_fast<F>(st, uK, t, p, e, nearlim, true, at_edge);
   // phased horizon loop: a wave with a lane beyond the rotation range (it takes the event path on every substep, ~500
   // cycles each behind the branch) goes to the loop with the event arithmetic inline like one with a rollout at the edge
   if (at_edge != nullptr) *at_edge = *at_edge || spinning != 0;
   if (sec) CPMPPI_SEC(sec, 4, st);
   return near_end;
-#else
-  bool spin = false;
-#pragma unroll
-  for (int i = 0; i < Width<F>::value; ++i) spin |= __builtin_fabsf(get(st.w, i)) * t > 0.1f;
-  bool exact = __builtin_amdgcn_ballot_w64(spin) != 0;
-  uint32_t sub = 0;
-  if (__builtin_expect(!exact, 1)) {
-    while (sub + 1 < S) {
-      ++sub;
-      if (__builtin_expect(substep_fast_rot<F, false>(st, uK, t, p, e), 0)) break;
-    }
-  }
-  for (; sub < S; ++sub) substep_fast<F>(st, uK, t, p, e, p.THL);       // the last substep always; all remaining after a bounce
-  return true;
-#endif
-#elif CPMPPI_ROTATE
-  for (uint32_t sub = 0; sub + 1 < S; ++sub) substep_fast_rot<F>(st, uK, t, p, e);
-  return substep_fast<F>(st, uK, t, p, e, nearlim);
-#else
-  for (uint32_t sub = 0; sub < S; ++sub) substep_fast<F>(st, uK, t, p, e, p.THL);
-  return true;
-#endif
 }
 // A control step of a wave one of whose rollouts ENDED the previous step at or beyond the track edge (`at_edge`): the
 // event arithmetic inline on every intermediate substep, no test, no speculation (see control_step_fast).  Used by the
@@ -968,8 +841,7 @@ __device__ __forceinline__ bool control_step_fast_eventful(State<F>& st, F uK, u
     spinning |= ~__builtin_amdgcn_ballot_w64(within) & __builtin_amdgcn_ballot_w64(true);
   }
   F cd, sd;
-  if constexpr (CPMPPI_SEED_LO != 0) rot_pair_lo<F>(st.w * splat<F>(t), cd, sd);
-  else rot_pair<F>(st.w * splat<F>(t), cd, sd);
+  rot_pair_lo<F>(st.w * splat<F>(t), cd, sd);
   if (UNROLL && S == 10u) {                      // (launches of one wave per SIMD: no taken branch between the substeps)
 #pragma unroll
     for (int sub = 0; sub < 9; ++sub) substep_fast_rot_carried<F, true>(st, uK, t, p, e, cd, sd, xlim);
@@ -983,7 +855,7 @@ __device__ __forceinline__ bool control_step_fast_eventful(State<F>& st, F uK, u
     }
     for (; left != 0u; --left) substep_fast_rot_carried<F, true>(st, uK, t, p, e, cd, sd, xlim);
   }
-  const bool near_end = substep_fast<F, true, true, (CPMPPI_EVENTFUL_LAST_INLINE != 0)>(st, uK, t, p, e, nearlim, true, at_edge);
+  const bool near_end = substep_fast<F, true, true, true>(st, uK, t, p, e, nearlim, true, at_edge);
   *at_edge = *at_edge || spinning != 0;          // (stays in this loop while the pole keeps spinning)
   return near_end;
 }
@@ -1107,11 +979,11 @@ __device__ __forceinline__ F div_uniform(F x, float c) {
   else return x / splat<F>(c);
 }
 
-// near = false: the caller knows |x| < permissible_track_fraction * THL for every lane, i.e. the boundary term is exactly
-// zero and dd + 0 == dd: it is left out (wave-uniform branch), bit-identical.
-// FAST folds the wave-uniform factors of three terms (QbgmFolded, formed once per kernel in double): dd = (x - x*)^2 *
-// [w_dd / (2 THL)^2], cc = u^2 * [R w_cc], 1 - cos * te as one FMA - three instructions fewer per stage, each term within
-// 2 ulp of the reference's grouping (PRECISE keeps that grouping operation for operation).
+// The wave-uniform factors of quadratic_boundary_grad_minimal's terms, formed once per kernel (or per env) in double.
+// (c_dd = w_dd / (2 THL)^2 and c_cc = R w_cc served a FAST form of stage_qbgm that folded three terms - three instructions
+// fewer per stage, each term within 2 ulp of the reference's grouping - until stage_qbgm_acc took the rollout kernel's FAST
+// path over (removed, see history); the two words stay: they are part of EnvFold's layout, which the throughput kernels' scalar
+// loads address - without them fold_env_kernel and three rollout kernels come out with other code and register counts.)
 struct QbgmFolded {
   float c_dd, c_cc, neg_te;
   // stage_qbgm_acc (FAST, the rollout kernel): every term's weight with the horizon aggregation's scale (1 for sum, 1/(H+1)
@@ -1206,25 +1078,17 @@ __device__ __forceinline__ void stage_qbgm_acc(const QbgmFolded& f, F x, F cosan
   }
 }
 
+// near = false: the caller knows |x| < permissible_track_fraction * THL for every lane, i.e. the boundary term is exactly
+// zero and dd + 0 == dd: it is left out (wave-uniform branch), bit-identical.
 template <class F, bool FAST = false>
-__device__ __forceinline__ F stage_qbgm(const Params& p, F x, F cosang, F w_ang, F u, float x_t, float te, bool near = true,
-                                        const QbgmFolded* fold = nullptr) {
+__device__ __forceinline__ F stage_qbgm(const Params& p, F x, F cosang, F w_ang, F u, float x_t, float te, bool near = true) {
 #pragma clang fp contract(off)     // every product and sum rounds once, wherever the function is inlined
   const float THL = p.THL;
-  F dd, ep, cc;
-  if (FAST && fold != nullptr) {
-    const F dx = x - splat<F>(x_t);
-    dd = (dx * dx) * splat<F>(fold->c_dd);
-    const F e1 = fma_(cosang, splat<F>(fold->neg_te), splat<F>(1.0f));
-    ep = (e1 * e1) * splat<F>(p.w[2]);
-    cc = (u * u) * splat<F>(fold->c_cc);
-  } else {
-    const F d = div_uniform<FAST, F>(x - splat<F>(x_t), 2.0f * THL);
-    dd = (d * d) * splat<F>(p.w[0]);
-    const F e1 = splat<F>(1.0f) - cosang * splat<F>(te);
-    ep = (e1 * e1) * splat<F>(p.w[2]);
-    cc = ((u * u) * splat<F>(p.w[5])) * splat<F>(p.w[4]);
-  }
+  const F d = div_uniform<FAST, F>(x - splat<F>(x_t), 2.0f * THL);
+  const F dd = (d * d) * splat<F>(p.w[0]);
+  const F e1 = splat<F>(1.0f) - cosang * splat<F>(te);
+  const F ep = (e1 * e1) * splat<F>(p.w[2]);
+  const F cc = ((u * u) * splat<F>(p.w[5])) * splat<F>(p.w[4]);
   const F ekp = (w_ang * w_ang) * splat<F>(p.w[3]);
   if (!near) return dd + ep + ekp + cc;
   const float ptf = p.w[6];

@@ -68,7 +68,7 @@ __global__ __launch_bounds__(BLOCK, 1) void gru_predict_kernel(const GruNorm nm,
 
 // Fused MPPI step with the GRU predictor: same contract as rollout_cost_kernel (plugin costs), h0[E,2,32] or NULL.
 template <int COST, int NOISE, bool F16>
-__global__ __launch_bounds__(BLOCK, CPMPPI_GRU_MIN_WAVES) void gru_rollout_cost_kernel(const Params p, const StepPtrs a, const GruNorm nm,
+__global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_rollout_cost_kernel(const Params p, const StepPtrs a, const GruNorm nm,
                                                                  const float* __restrict__ image,
                                                                  const float* __restrict__ h0) {
   extern __shared__ float lds[];                           // GRU image, then [WAVES][W] weighted sums
@@ -329,7 +329,7 @@ int cpmppi_set_gru(cpmppi_handle* h, const cpmppi_gru_model* m) try {
     reinterpret_cast<_Float16*>(img16.data() + (size_t)f * G16_FRAG_BYTES + lane * 16)[t] = hi;
     reinterpret_cast<_Float16*>(img16.data() + (size_t)(f + 1) * G16_FRAG_BYTES + lane * 16)[t] = lo;
   };
-  // gate rows pre-scaled so that the gates need no multiply before v_exp_f32 (gru16_gates): r, z by -log2(e), n by 2 log2(e)
+  // gate rows pre-scaled so that the gates need no multiply before v_exp_f32 (gru16_gates_overlapped): r, z by -log2(e), n by 2 log2(e)
   const double LOG2E = 1.4426950408889634;
   const double gate_scale[3] = {-LOG2E, -LOG2E, 2.0 * LOG2E};
   auto sc = [&](int g, float w) { return (float)(gate_scale[g] * (double)w); };

@@ -110,20 +110,6 @@ __device__ __forceinline__ void gru16_hidden_products(const char* __restrict__ l
   }
 }
 
-// Gates on pre-activations that the image builder has pre-scaled: the r and z rows of every weight matrix and bias by
-// -log2(e), the n rows by 2 log2(e), so sigmoid(a) = 1 / (1 + 2^a') and tanh(y) = 1 - 2 / (2^y' + 1) need no multiply
-// in front of v_exp_f32.
-__device__ __forceinline__ void gru16_gates(const f16v& ar, const f16v& az, const f16v& anx, const f16v& anh, f16v& h) {
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    const float r = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(ar[v]));
-    const float z = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(az[v]));
-    const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(r, anh[v], anx[v]));
-    const float n = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
-    h[v] = __builtin_fmaf(z, h[v] - n, n);                    // (1-z)*n + z*h
-  }
-}
-
 // The gates of one layer (ar, az, anx, anh -> h in place) with the 18 MFMAs of ANOTHER layer's / step's hidden products
 // pr / pz / pn += W[fh ...] hs placed BETWEEN them in program order, one MFMA per gate element.
 // Why in program order: a wave issues in order, and a v_mfma_f32_32x32x16_f16 occupies the SIMD's matrix pipe for 32 cycles -
@@ -134,12 +120,9 @@ __device__ __forceinline__ void gru16_gates(const f16v& ar, const f16v& az, cons
 // is bound by the gate math and the products disappear under it (round 3 issued the 18 MFMAs in front of the gates behind a
 // scheduling barrier: 576 + ~1220 cycles per phase; now ~1220 + 18 x 8).  Accumulation order per accumulator is unchanged
 // (block 0: hi hi, hi lo, lo hi; block 1 likewise), so the results are bit-identical.  Fragments are fetched two MFMAs ahead.
-#ifndef CPMPPI_GRU_INTERLEAVE
-#define CPMPPI_GRU_INTERLEAVE 1
-#endif
-#ifndef CPMPPI_GRU_PACKED_GATES
-#define CPMPPI_GRU_PACKED_GATES 1
-#endif
+// The gates work on pre-activations that the image builder has pre-scaled: the r and z rows of every weight matrix and bias by
+// -log2(e), the n rows by 2 log2(e), so sigmoid(a) = 1 / (1 + 2^a') and tanh(y) = 1 - 2 / (2^y' + 1) need no multiply
+// in front of v_exp_f32.
 __device__ __forceinline__ void gru16_gates_overlapped(const f16v& ar, const f16v& az, const f16v& anx, const f16v& anh, f16v& h,
                                                        const char* __restrict__ lds, int fh, const HSplit hs[2], f16v& pr,
                                                        f16v& pz, f16v& pn, uint32_t lane) {
@@ -164,7 +147,6 @@ __device__ __forceinline__ void gru16_gates_overlapped(const f16v& ar, const f16
     w0 = w2; w1 = w3;
   }
   __builtin_amdgcn_sched_barrier(0);
-#if CPMPPI_GRU_PACKED_GATES
   // FOUR gate elements at a time as two register pairs: accumulator registers (v, v+1) are an aligned pair, so the seven plain
   // instructions of an element - 1 + 2^a (twice), r*anh + anx, e + 1, 1 - 2q, h - n, the blend - become seven v_pk_* for TWO
   // elements (the six transcendentals per element stay scalar): 152 -> 124 cycles of vector issue per pair.  Two pairs are
@@ -210,22 +192,6 @@ __device__ __forceinline__ void gru16_gates_overlapped(const f16v& ar, const f16
     w0 = na; w1 = nb;
     __builtin_amdgcn_sched_barrier(0);
   }
-#else
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    const int m = v + 2;
-    h8 wn = w1;
-    if (m + 2 < 18) wn = *frag_of(m + 2);
-    issue(m, w0);
-    const float r = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(ar[v]));
-    const float z = __builtin_amdgcn_rcpf(1.0f + __builtin_amdgcn_exp2f(az[v]));
-    const float e = __builtin_amdgcn_exp2f(__builtin_fmaf(r, anh[v], anx[v]));
-    const float n = __builtin_fmaf(-2.0f, __builtin_amdgcn_rcpf(e + 1.0f), 1.0f);
-    h[v] = __builtin_fmaf(z, h[v] - n, n);                    // (1-z)*n + z*h
-    w0 = w1; w1 = wn;
-    __builtin_amdgcn_sched_barrier(0);
-  }
-#endif
 }
 
 __device__ __forceinline__ void gru16_carry_init(const char* __restrict__ lds, Gru16State& s, uint32_t lane, Gru16Carry& c) {
@@ -258,13 +224,7 @@ __device__ __forceinline__ f16v gru16_step(const char* __restrict__ lds, const f
   __builtin_amdgcn_sched_barrier(0);
   GRU_STAMP(1);
   f16v br = gru16_bias(lds, 4, lane), bz = gru16_bias(lds, 5, lane), bnh = gru16_bias(lds, 7, lane);
-#if CPMPPI_GRU_INTERLEAVE
   gru16_gates_overlapped(ar, az, anx, anh, s.h1, lds, HF_L2H, s.h2s, br, bz, bnh, lane);   // gates 1 || W_hh2 h2(t-1)
-#else
-  gru16_hidden_products(lds, HF_L2H, s.h2s, br, bz, bnh, lane);        // W_hh2 h2(t-1): independent of the gates below
-  __builtin_amdgcn_sched_barrier(0);
-  gru16_gates(ar, az, anx, anh, s.h1);
-#endif
   gru16_resplit(s.h1, s.h1s);
   __builtin_amdgcn_sched_barrier(0);
   GRU_STAMP(2);
@@ -279,13 +239,7 @@ __device__ __forceinline__ f16v gru16_step(const char* __restrict__ lds, const f
   __builtin_amdgcn_sched_barrier(0);
   GRU_STAMP(3);
   c.ar = gru16_bias(lds, 0, lane); c.az = gru16_bias(lds, 1, lane); c.anh = gru16_bias(lds, 3, lane);
-#if CPMPPI_GRU_INTERLEAVE
   gru16_gates_overlapped(br, bz, bnx, bnh, s.h2, lds, HF_L1H, s.h1s, c.ar, c.az, c.anh, lane);   // gates 2 || W_hh1 h1(t) for step t+1
-#else
-  gru16_hidden_products(lds, HF_L1H, s.h1s, c.ar, c.az, c.anh, lane);  // W_hh1 h1(t) for step t+1
-  __builtin_amdgcn_sched_barrier(0);
-  gru16_gates(br, bz, bnx, bnh, s.h2);
-#endif
   gru16_resplit(s.h2, s.h2s);
   __builtin_amdgcn_sched_barrier(0);
   GRU_STAMP(4);

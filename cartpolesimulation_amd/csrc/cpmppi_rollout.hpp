@@ -16,48 +16,10 @@ using namespace cpmppi;
 
 constexpr int BLOCK = 256;
 constexpr int WAVES = BLOCK / 64;
-#ifndef CPMPPI_GRU_MIN_WAVES
-#define CPMPPI_GRU_MIN_WAVES 2      // waves per SIMD the GRU kernels are compiled for (register budget 512 / this)
-#endif
-#ifndef CPMPPI_MIN_WAVES
-#define CPMPPI_MIN_WAVES 1
-#endif
-#ifndef CPMPPI_DMA_TK
-#define CPMPPI_DMA_TK 8             // control steps per direct-to-LDS tile (two tiles per wave)
-#endif
-#ifndef CPMPPI_DMA_TK_THROUGHPUT
-#define CPMPPI_DMA_TK_THROUGHPUT 16 // ... in the throughput build (one tile per wave)
-#endif
-#ifndef CPMPPI_NOMINAL_IN_LANES
-#define CPMPPI_NOMINAL_IN_LANES 3   // FAST, bit v = build VARIANT v: nominal sequence held in lanes, fetched with v_readlane_b32 (latency + throughput builds)
-#endif
-#ifndef CPMPPI_EVENTFUL_UNROLL
-#define CPMPPI_EVENTFUL_UNROLL 1
-#endif
-#ifndef CPMPPI_ODE_TRACK_NEAR
-#define CPMPPI_ODE_TRACK_NEAR 1     // predictor_ODE: boundary-cost flag from one pair of compares per control step (A/B switch)
-#endif
-#ifndef CPMPPI_WAVE_PRIORITY
-#define CPMPPI_WAVE_PRIORITY 1
-#endif
-#ifndef CPMPPI_KNOT_SEGMENTS
-#define CPMPPI_KNOT_SEGMENTS 1      // throughput build, in-kernel interpolation: knot segments as an outer loop (A/B switch)
-#endif
-#ifndef CPMPPI_QBGM_ACC
-#define CPMPPI_QBGM_ACC 1           // FAST quadratic_boundary_grad_minimal: stage cost + correction accumulated with FMAs (A/B switch)
-#endif
-#ifndef CPMPPI_ENV_FOLD
-#define CPMPPI_ENV_FOLD 1           // throughput build: per-env constants from fold_env_kernel's block instead of each wave's prologue (A/B switch)
-#endif
-#ifndef CPMPPI_TILED_SCATTER
-#define CPMPPI_TILED_SCATTER 1      // tiled layout: the weighted column sums as a reduce-scatter over the wave (A/B switch)
-#endif
-#ifndef CPMPPI_ROLLBACK_PHASED
-#define CPMPPI_ROLLBACK_PHASED 1    // phased mid-size build: the quiet control step with one edge test per three substeps too (A/B switch)
-#endif
-#ifndef CPMPPI_SPIN_BRANCH
-#define CPMPPI_SPIN_BRANCH 1        // throughput build, two rollouts per lane: the spin test as one v_max + compare + branch (A/B switch)
-#endif
+constexpr int GRU_MIN_WAVES = 2;                 // waves per SIMD the GRU kernels are compiled for (register budget 512 / this)
+constexpr int MIN_WAVES = 1;                     // ... and the rollout kernels
+constexpr uint32_t DMA_TK_DEFAULT = 8;           // control steps per direct-to-LDS tile (two tiles per wave)
+constexpr uint32_t DMA_TK_THROUGHPUT = 16;       // ... in the throughput build (one tile per wave)
 constexpr size_t SAMPLER_LDS_MAX = 159 * 1024;   // gfx950: 160 KB of LDS per workgroup (sampler: [256][P+1] floats)
 
 // Device-side ordering between a step and the all-gather of its result (cpmppi_step_gather, cpmppi_comm.hip) without any
@@ -290,7 +252,7 @@ __device__ __forceinline__ void finalize_env(const Params& p, const float* parti
 // Euler, edge bounce, fmod wrap - the north-star path) or PREDICTOR_ODE (predictor_ODE: Euler-Cromer, no bounce, atan2 wrap;
 // cpmppi_device.hpp).  The second has no events, hence no phased loop: it is built in the latency and throughput forms only.
 template <int COST, bool FAST, int NOISE, int R, int VARIANT_, int INTEG = PREDICTOR_ODE_V0>
-__global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(const Params p, const StepPtrs a) {
+__global__ __launch_bounds__(BLOCK, MIN_WAVES) void rollout_cost_kernel(const Params p, const StepPtrs a) {
   static_assert(INTEG == PREDICTOR_ODE_V0 || VARIANT_ != 2, "predictor_ODE: latency / throughput builds and the lone-wave form of the latter");
   // VARIANT_ 3 = the mid-size build for launches of at most ONE wave per SIMD: VARIANT 2 with the quiet control step's nine
   // substeps as straight-line code (a lone wave pays ~50 cycles per taken branch: C4 80.1 -> 77.4 us; with two or more waves
@@ -303,7 +265,7 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
   // wave-private tiles (direct-to-LDS loads): two of 8 control steps in the latency / mid-size builds (the next tile streams
   // in under the current one), ONE of 16 in the throughput build (same LDS; every 128-byte line of a 200-byte row is then
   // requested about twice instead of four times, and the three other waves of the SIMD cover the wait)
-  constexpr uint32_t DMA_TK = (VARIANT == 1) ? CPMPPI_DMA_TK_THROUGHPUT : CPMPPI_DMA_TK;
+  constexpr uint32_t DMA_TK = (VARIANT == 1) ? DMA_TK_THROUGHPUT : DMA_TK_DEFAULT;
   constexpr uint32_t DMA_BUFS = (VARIANT == 1) ? 1u : 2u;
   __shared__ float tile[NOISE == NOISE_DELTA_U ? WAVES * DMA_BUFS * 64 * R * DMA_TK : 1];
   __shared__ float red[2 * WAVES];
@@ -311,13 +273,11 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
 
   const uint32_t env = blockIdx.x / a.nb, blk = blockIdx.x % a.nb;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6;
-#if CPMPPI_WAVE_PRIORITY
   // Small launches (one or two waves per SIMD) end with their slowest wave, and the all-gather of the previous step's result
   // runs UNDER this kernel on another stream (cpmppi_step_gather): a wave of that kernel sharing a SIMD with one of ours
   // takes issue slots from it for its whole duration.  Raised wave priority makes the arbiter serve the rollout wave first;
   // a lone rollout wave leaves more than half of the issue slots unused, so the guest still runs.
   if constexpr (VARIANT != 1 || LONE_WAVE) __builtin_amdgcn_s_setprio(3);
-#endif
 #ifdef CPMPPI_DEBUG_COUNTERS
   const unsigned long long dbg_t0 = __builtin_amdgcn_s_memtime();
   CPMPPI_DBG_STAMP(0);
@@ -335,7 +295,7 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
   // through the constant address space: the block is read-only for this kernel), everywhere else each wave forms them itself
   // (not default.py's cost fed with knots from memory, two rollouts per lane: with the block's 31 scalars live from the first
   // instruction that one instantiation runs out of SGPRs and spill lanes - 20 bytes of scratch; it keeps the in-kernel fold)
-  constexpr bool ENV_FOLD = CPMPPI_ENV_FOLD != 0 && FAST && VARIANT_ == 1 && INTEG == PREDICTOR_ODE_V0 &&
+  constexpr bool ENV_FOLD = FAST && VARIANT_ == 1 && INTEG == PREDICTOR_ODE_V0 &&
                             !(COST == COST_DEFAULT && NOISE == NOISE_KNOTS && R == 2);
   typedef const __attribute__((address_space(4))) float* env_fold_ptr;
   // (the builds that fold in-kernel do so where they always did - further down for te, cos and the cost's constants: the latency
@@ -380,8 +340,8 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
   // The phased mid-size build's quiet loop does the same (same cost only: the other costs' kernels grow by 10-25 registers,
   // past the 168 of three waves per SIMD) - there the compare -> scalar-branch hand-over a test costs a lone wave is paid three
   // times per control step instead of nine.
-  constexpr bool ROLLBACK_TP = VARIANT == 1 && R == 2 && CPMPPI_SPIN_BRANCH != 0 && CPMPPI_ROLLBACK != 0 && COST == COST_QBGM;
-  constexpr bool ROLLBACK = ROLLBACK_TP || (PHASED && CPMPPI_ROLLBACK != 0 && CPMPPI_ROLLBACK_PHASED != 0 && COST == COST_QBGM);
+  constexpr bool ROLLBACK_TP = VARIANT == 1 && R == 2 && COST == COST_QBGM;
+  constexpr bool ROLLBACK = ROLLBACK_TP || (PHASED && COST == COST_QBGM);
   const Params& ph = p;
   // (ROLLBACK kernels: three of the substep's wave-uniform constants are parked in vector registers - these kernels have twenty
   // to spare, while the scalar file is what they run out of: the Philox one was 20 bytes of scratch short)
@@ -410,10 +370,10 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
   // is the edge itself and the flag is unused.
   const QbgmFolded qf = ENV_FOLD ? qf_ : make_qbgm_folded(p, te);
   // quadratic_boundary_grad_minimal, FAST: stage cost and correction term accumulated term by term with FMAs (stage_qbgm_acc)
-  constexpr bool QBGM_ACC = FAST && COST == COST_QBGM && CPMPPI_QBGM_FOLD != 0 && CPMPPI_QBGM_ACC != 0;
+  constexpr bool QBGM_ACC = FAST && COST == COST_QBGM;
   // (not in the latency build: there the flag's compare -> scalar branch hand-over sits on the lone wave's critical path
   // once per control step - measured 56 -> 66 us for a single env - while the eight instructions it saves are hidden)
-  constexpr bool TRACK_NEAR = FAST && COST == COST_QBGM && VARIANT != 0 && (INTEG == PREDICTOR_ODE_V0 || CPMPPI_ODE_TRACK_NEAR != 0);
+  constexpr bool TRACK_NEAR = FAST && COST == COST_QBGM && VARIANT != 0;
   const float nearlim = (ENV_FOLD && TRACK_NEAR) ? nearlim_ : uniform_(TRACK_NEAR ? __builtin_fminf(p.w[6], 1.0f) * p.THL : p.THL);
   bool near = !TRACK_NEAR || !(__builtin_fabsf(s0[4]) < nearlim);
 
@@ -424,7 +384,8 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
   // (measured, round 3: 8192 envs 2.61 -> 2.47 ms per launch; single env with knots from memory 57.6 -> 54.9 us, with
   // Philox / a delta_u buffer +0.5 / +1 % - those keep the one-step-ahead load; mid-size build: C4 -1..-3 %, C3 and 256 envs
   // +2 %, not enabled)
-  constexpr bool NOMINAL_IN_LANES = FAST && ((((CPMPPI_NOMINAL_IN_LANES) >> VARIANT) & 1) != 0 || PHASED) && (VARIANT != 0 || NOISE == NOISE_KNOTS);
+  // (held in lanes: the throughput and phased builds, and the latency build's kernels that take their knots from memory)
+  constexpr bool NOMINAL_IN_LANES = FAST && (VARIANT == 1 || PHASED || (VARIANT == 0 && NOISE == NOISE_KNOTS));
   constexpr bool PREFETCH_NOMINAL = (VARIANT == 0) && !NOMINAL_IN_LANES;
   float uk_next = PREFETCH_NOMINAL ? shifted_nominal(p, un, 0) : 0.0f;
   float up_next = (VARIANT == 0 && COST == COST_LEGACY) ? up[0] : 0.0f;
@@ -500,7 +461,7 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
       }
       stage_qbgm_acc<F>(qf, st.x, cosang, st.w, ur, du, nom_mode, b_nom, x_t, near, cost, corr);
     } else if constexpr (COST == COST_QBGM) {
-      cost += stage_qbgm<F, FAST>(p, st.x, cosang, st.w, ur, x_t, te, near, (FAST && CPMPPI_QBGM_FOLD != 0) ? &qf : nullptr);
+      cost += stage_qbgm<F, FAST>(p, st.x, cosang, st.w, ur, x_t, te, near);     // (PRECISE only: FAST is QBGM_ACC)
       corr += mppi_correction<F>(p, p.correction_u == CPMPPI_CORRECTION_U_RUN ? ur : splat<F>(uk), du);
     } else if constexpr (COST == COST_DEFAULT) {
       cost += stage_default<F, FAST, (INTEG == PREDICTOR_ODE_V0)>(p, st.x, cosang, ur, x_t, te, u_before, qb_ccrc);
@@ -531,10 +492,10 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
       if (secp) { asm volatile("" : "+v"(uK), "+v"(cost), "+v"(corr)); CPMPPI_SEC(secp, 1, st); }
       bool near_next;
       if constexpr (PHASED) {
-        if constexpr (decltype(eventful)::value) near_next = control_step_fast_eventful<F, (LONE_WAVE && CPMPPI_EVENTFUL_UNROLL != 0)>(st, uK, p.S, p.t_step, ph, eh, nearlim, &at_edge);
+        if constexpr (decltype(eventful)::value) near_next = control_step_fast_eventful<F, LONE_WAVE>(st, uK, p.S, p.t_step, ph, eh, nearlim, &at_edge);
         else near_next = control_step_fast<F, LONE_WAVE, false, ROLLBACK>(st, uK, p.S, p.t_step, ph, eh, nearlim, secp, &at_edge);
       } else {
-        near_next = control_step_fast<F, false, (VARIANT == 1 && R == 2 && CPMPPI_SPIN_BRANCH != 0), ROLLBACK_TP>(st, uK, p.S, p.t_step, ph, eh, nearlim, secp, ROLLBACK_TP ? &at_edge : nullptr);
+        near_next = control_step_fast<F, false, (VARIANT == 1 && R == 2), ROLLBACK_TP>(st, uK, p.S, p.t_step, ph, eh, nearlim, secp, ROLLBACK_TP ? &at_edge : nullptr);
       }
       near = !TRACK_NEAR || near_next;
     } else {
@@ -787,7 +748,7 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
     };
     if constexpr (PHASED) {
       run_phased(horizon_step);
-    } else if constexpr (FAST && VARIANT == 1 && CPMPPI_KNOT_SEGMENTS != 0 && !(COST == COST_DEFAULT && NOISE == NOISE_PHILOX && R == 2)) {
+    } else if constexpr (FAST && VARIANT == 1 && !(COST == COST_DEFAULT && NOISE == NOISE_PHILOX && R == 2)) {
       // throughput build: the horizon as NESTED loops - knot segments outside, the `period` control steps between two knots
       // inside, where the segment's knot and slope are loop invariants.  The flat loop above refreshes the knots behind a
       // branch inside the loop body, and the register allocator lines the hot path up with that branch's assignment by
@@ -907,7 +868,6 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
       src2[i] = reinterpret_cast<const float4*>(a.noise) + ((size_t)env * G + g) * Hq * 64u + lane;
     }
     constexpr int QB = 4;
-#if CPMPPI_TILED_SCATTER
     // Round 4: the 16 column sums of a batch as a REDUCE-SCATTER over the wave instead of 16 full wave reductions.  Lane pairs at
     // distance 1, 2, 4, 8 each keep one half of their columns and hand the other half over (two selects + one add per column
     // pair: 8 + 4 + 2 + 1 pairs), after which a lane holds ONE column - number (lane & 15) of the batch - summed over its row of
@@ -954,34 +914,6 @@ __global__ __launch_bounds__(BLOCK, CPMPPI_MIN_WAVES) void rollout_cost_kernel(c
       const uint32_t k = 4u * q0 + (lane & 15u);   // the column this lane ended up with
       if (lane < 16u && k < W) my_bsum[k] = col;
     }
-#else
-    for (uint32_t q0 = 0; q0 < Hq; q0 += QB) {
-      float4 v[QB][R];
-#pragma unroll
-      for (int u = 0; u < QB; ++u) {
-        const uint32_t q = (q0 + u < Hq) ? q0 + u : Hq - 1u;
-#pragma unroll
-        for (int i = 0; i < R; ++i) v[u][i] = src2[i][(size_t)q * 64u];
-      }
-#pragma unroll
-      for (int u = 0; u < QB; ++u) {
-        float4 acc = {0.0f, 0.0f, 0.0f, 0.0f};
-#pragma unroll
-        for (int i = 0; i < R; ++i) {
-          acc.x = __builtin_fmaf(e[i], v[u][i].x, acc.x); acc.y = __builtin_fmaf(e[i], v[u][i].y, acc.y);
-          acc.z = __builtin_fmaf(e[i], v[u][i].z, acc.z); acc.w = __builtin_fmaf(e[i], v[u][i].w, acc.w);
-        }
-        acc.x = wave_sum(acc.x); acc.y = wave_sum(acc.y); acc.z = wave_sum(acc.z); acc.w = wave_sum(acc.w);
-        const uint32_t k = 4u * (q0 + u);
-        if (lane == 0 && q0 + u < Hq) {
-          my_bsum[k] = acc.x;
-          if (k + 1 < W) my_bsum[k + 1] = acc.y;
-          if (k + 2 < W) my_bsum[k + 2] = acc.z;
-          if (k + 3 < W) my_bsum[k + 3] = acc.w;
-        }
-      }
-    }
-#endif
   } else {
     // transposed pass: lane = column (time-step or knot), loop over the wave's rows, rows read coalesced (cache-hot)
     const float* __restrict__ src = a.noise + ((size_t)env * p.N + row0) * W;

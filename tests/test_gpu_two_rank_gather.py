@@ -188,7 +188,7 @@ def test_two_ranks_with_random_stalls_on_both_sides(tmp_path, mode):
     steps and catch up again, the finalizes wait for real - and still every gathered block on both ranks is bit for bit the
     single-process run, every block carries its step's stamp, nobody errs.  One handle per rank, and env groups under one communicator."""
     E, N, H = 4, 256, 16
-    # (a soak run: CPMPPI_TWO_RANK_STRESS="<steps>:<per mille>:<max us>:<seed>", e.g. 6000:300:1500:7 - tools/dev/r6_soak_two_rank.sh)
+    # (a soak run: CPMPPI_TWO_RANK_STRESS="<steps>:<per mille>:<max us>:<seed>", e.g. 6000:300:1500:7 - profiles/r6/soak_two_rank.txt)
     steps, pm, us, seed = (int(x) for x in os.environ.get("CPMPPI_TWO_RANK_STRESS", "400:200:300:83").split(":"))
     K, KB = (steps, 0) if mode == "steps" else (steps - steps // 4, steps // 4)
     kw = dict(envs=E, rollouts=N, horizon=H, steps=K, seed=seed, jitter=f"{pm}:{us}")

@@ -3,6 +3,8 @@
 `.hip_fatbin` section is unbundled and its AMDGPU metadata note read with llvm-readelf.
 
   python tools/code_objects.py [path/to/libcpmppi.so] [name-substring]
+  python tools/code_objects.py --diff a.so b.so     same device code?  one line per code object for its .text bytes, every
+                                                    difference of the kernels() tables; exit status 1 on any difference
 
 `kernels(path)` -> list of dicts {name, vgpr_count, agpr_count, sgpr_count, sgpr_spill_count, vgpr_spill_count,
 private_segment_fixed_size (scratch bytes per lane), group_segment_fixed_size (static LDS), unit (index of the code object)}.
@@ -65,7 +67,38 @@ def kernels(so_path, target="gfx950"):
     return res
 
 
+def section(elf, name=".text"):
+    """The bytes of section `name` of a device ELF image (whole images differ by the build paths they record)."""
+    with tempfile.TemporaryDirectory() as tmp:
+        src, out = os.path.join(tmp, "in.elf"), os.path.join(tmp, "section.bin")
+        open(src, "wb").write(elf)
+        subprocess.run([os.path.join(LLVM_BIN, "llvm-objcopy"), "--dump-section", f"{name}={out}", src,
+                        os.path.join(tmp, "discard.elf")], check=True)
+        return open(out, "rb").read()
+
+
+def diff(so_a, so_b, sections=(".text",)):
+    """Compare two libraries' gfx950 code objects section by section and kernel by kernel; the number of differences."""
+    objs_a, objs_b = code_objects(so_a), code_objects(so_b)
+    bad = int(len(objs_a) != len(objs_b))
+    print(f"code objects: {len(objs_a)} / {len(objs_b)}")
+    for unit, (ea, eb) in enumerate(zip(objs_a, objs_b)):
+        for name in sections:
+            sa, sb = section(ea, name), section(eb, name)
+            bad += sa != sb
+            print(f"u{unit} {name}: {'identical' if sa == sb else 'DIFFERENT'} ({len(sa)} / {len(sb)} bytes)")
+    ka, kb = ({(k["unit"], k["name"]): k for k in kernels(so)} for so in (so_a, so_b))
+    for key in sorted(set(ka) | set(kb)):
+        if ka.get(key) != kb.get(key):
+            bad += 1
+            print(f"u{key[0]} {key[1]}: {ka.get(key)} / {kb.get(key)}")
+    print(f"kernels: {len(ka)} / {len(kb)}; {'no difference' if not bad else str(bad) + ' differences'}")
+    return bad
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 4 and sys.argv[1] == "--diff":
+        sys.exit(1 if diff(sys.argv[2], sys.argv[3]) else 0)
     path = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] else os.path.join(ROOT, "cartpolesimulation_amd", "libcpmppi.so")
     flt = sys.argv[2] if len(sys.argv) > 2 else ""
     for k in kernels(path):

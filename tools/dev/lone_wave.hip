@@ -180,7 +180,7 @@ __global__ __launch_bounds__(256) void k1(const float* in, float* out, Params p,
     unsigned bad = 0;
     for (int i = 0; i < 1000; ++i) {
       substep_asm(sa, uK, ts, ak);
-      substep_fast_rot<float, false, 0>(sb, uK, t, ph, eh);
+      substep_fast_rot<float, false>(sb, uK, t, ph, eh);
       bad |= (__float_as_uint(sa.th) ^ __float_as_uint(sb.th)) | (__float_as_uint(sa.w) ^ __float_as_uint(sb.w)) | (__float_as_uint(sa.c) ^ __float_as_uint(sb.c)) |
              (__float_as_uint(sa.s) ^ __float_as_uint(sb.s)) | (__float_as_uint(sa.x) ^ __float_as_uint(sb.x)) | (__float_as_uint(sa.v) ^ __float_as_uint(sb.v));
       if ((i & 63) == 63) uK = -uK;
@@ -198,16 +198,16 @@ __global__ __launch_bounds__(256) void k1(const float* in, float* out, Params p,
     } else if constexpr (KIND == 1) {
       substep_fast_rot<float>(st, uK, t, ph, eh);
     } else if constexpr (KIND == 2) {
-      substep_fast_rot<float, false, 0>(st, uK, t, ph, eh);
+      substep_fast_rot<float, false>(st, uK, t, ph, eh);
     } else if constexpr (KIND == 4) {
       // three substeps without event handling, ONE test: max3 of the positions against the edge, max3 of the rotation
       // angles against the polynomial's range
       const float d0 = st.w * t;
-      substep_fast_rot<float, true, 0>(st, uK, t, ph, eh);
+      substep_fast_rot<float, false>(st, uK, t, ph, eh);
       const float xa = st.x, d1 = st.w * t;
-      substep_fast_rot<float, true, 0>(st, uK, t, ph, eh);
+      substep_fast_rot<float, false>(st, uK, t, ph, eh);
       const float xb = st.x, d2 = st.w * t;
-      substep_fast_rot<float, true, 0>(st, uK, t, ph, eh);
+      substep_fast_rot<float, false>(st, uK, t, ph, eh);
       const float mx = __builtin_fmaxf(__builtin_fabsf(xa), __builtin_fmaxf(__builtin_fabsf(xb), __builtin_fabsf(st.x)));
       const float md = __builtin_fmaxf(__builtin_fabsf(d0), __builtin_fmaxf(__builtin_fabsf(d1), __builtin_fabsf(d2)));
       const uint64_t fired = __builtin_amdgcn_fcmpf(mx, ph.THL, 3) | __builtin_amdgcn_fcmpf(md, ROT_LIMIT_LO, 2);
