@@ -117,6 +117,24 @@ _ENUMS = {
     "math_mode": {"precise": L.MATH_PRECISE, "fast": L.MATH_FAST},
 }
 ODE_PREDICTORS = {"ODE_v0": L.ODE_V0, "ODE": L.ODE_CROMER}
+_ODE_SPECIFICATIONS = {"ODE_v0": "ODE_v0", "ODE_v0_default": "ODE_v0", "ODE": "ODE", "ODE_default": "ODE"}
+
+
+def ode_predictor_type(spec, who):
+    """A ``predictor_specification`` (config_controllers.yml:3,14; a ``:suffix`` is ignored) -> ``MPPIConfig.predictor_type``.
+
+    "ODE" (and the config_predictors.yml entry named after it) is next_state_predictor_ODE (predictors_customization.py:25-69),
+    a DIFFERENT integrator from ODE_v0: Euler-Cromer, atan2 angle, no edge bounce - one control step already lies 1.6e-3 from
+    ODE_v0.  It is what the shipped config_controllers.yml:2-3 pair with `optimizer: rpgd`, and is served by
+    the kernels' predictor_ODE form (the adjoint kernel has that substep's reverse too), never by the ODE_v0 ones.
+    None -> None: what no specification means is the caller's to say.  Anything else: NotImplementedError(``who``), the
+    caller's own sentence about what it runs on."""
+    if spec is None:
+        return None
+    ptype = _ODE_SPECIFICATIONS.get(str(spec).split(":")[0])
+    if ptype is None:
+        raise NotImplementedError(who)
+    return ptype
 
 
 def cost_vector(name, overrides=None):
@@ -203,8 +221,8 @@ def mppi_config_from_yaml(cfgs, **overrides):
     spec = str(ctrl.get("predictor_specification") or "ODE_v0").split(":")[0]
     entries = cfgs["predictors"]["predictors"]
     entry = entries.get(spec) or {}
-    ptype = entry.get("predictor_type", spec)
-    if ptype in ODE_PREDICTORS:                      # (a neural / GP specification is the caller's to resolve: gru_model=...)
+    ptype = _ODE_SPECIFICATIONS.get(entry.get("predictor_type", spec))
+    if ptype is not None:                            # (a neural / GP specification is the caller's to resolve: gru_model=...)
         kw["predictor_type"] = ptype
         # the named entry's own substep count first (a custom entry such as `I_love_control_too: {predictor_type: ODE,
         # intermediate_steps: 2}`), "<type>_default" only when the entry has none

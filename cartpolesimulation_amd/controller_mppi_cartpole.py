@@ -17,12 +17,14 @@ Configuration: the keys of ``config_controllers.yml:9-30`` (section ``mppi-cartp
 ``config_root=<CartPoleSimulation checkout>`` to read them (and ``dt.control`` of ``config_data_gen.yml:27``,
 ``actuator_noise`` of ``cartpole_physical_parameters.yml:2``) from the YAML files the reference reads at import (:38-41).
 """
+import os
 import time as _time
 
 import numpy as np
 import torch
+import yaml
 
-from .configs import PhysicalParameters, legacy_mppi_config
+from .configs import PhysicalParameters, legacy_mppi_config, load_reference_yaml, ode_predictor_type
 from .controller_mpc import template_controller
 from .sampling import SAMPLING_TYPES, sample_delta_u_sfc64, sample_knots_sfc64
 
@@ -39,9 +41,6 @@ class controller_mppi_cartpole(template_controller):
         super().__init__(environment_name, initial_environment_attributes, control_limits)
         cfg = dict(DEFAULTS)
         if config_root is not None:
-            from .configs import load_reference_yaml
-            import os
-            import yaml
             yaml_phys, cfgs = load_reference_yaml(config_root)
             cfg.update(cfgs["controllers"]["mppi-cartpole"])
             dt = cfgs["data_gen"]["dt"]["control"]
@@ -55,13 +54,10 @@ class controller_mppi_cartpole(template_controller):
         if cfg["SAMPLING_TYPE"] not in SAMPLING_TYPES:
             raise ValueError(f"SAMPLING_TYPE must be one of {SAMPLING_TYPES}")
         spec = cfg["predictor_specification"]
-        if spec in ("ODE", "ODE_default"):
-            # the shipped YAML (config_controllers.yml:14) says "ODE": next_state_predictor_ODE (Euler-Cromer, no bounce)
-            self.predictor_type = "ODE"
-        elif spec in ("ODE_v0", "ODE_v0_default"):
-            self.predictor_type = "ODE_v0"
-        else:
-            raise NotImplementedError(f"predictor_specification {spec!r}: this controller runs on the ODE_v0 and ODE kernels")
+        refusal = f"predictor_specification {spec!r}: this controller runs on the ODE_v0 and ODE kernels"
+        if spec is None or ":" in str(spec):                  # (this controller takes the plain names only)
+            raise NotImplementedError(refusal)
+        self.predictor_type = ode_predictor_type(spec, refusal)
         self.config = cfg
         self.dt, self.p_Q = float(dt), float(actuator_noise)
         self.phys = phys or PhysicalParameters()

@@ -16,19 +16,37 @@ def _ptr(t):
     return C.c_void_p(t.data_ptr()) if t is not None else C.c_void_p(0)
 
 
+def is_dense(t, dtype=torch.float32, tail=None):
+    """The half of the argument check that needs no device: `t` is a contiguous `dtype` tensor [rows, *tail] (tail None: of any
+    shape)."""
+    return (torch.is_tensor(t) and t.dtype == dtype and t.is_contiguous()
+            and (tail is None or tuple(t.shape[1:]) == tuple(tail)))
+
+
+def device_tensor(name, t, dtype=torch.float32, tail=None, note=""):
+    """`t`, or ValueError: "<name> must be a contiguous float32 ROCm tensor [rows, 6]<note>" for dtype float32 and tail (6,)."""
+    if not (is_dense(t, dtype, tail) and t.is_cuda):
+        shape = "" if tail is None else " [rows%s]" % "".join(f", {x}" for x in tail)
+        raise ValueError(f"{name} must be a contiguous {str(dtype).replace('torch.', '')} ROCm tensor{shape}{note}")
+    return t
+
+
+def _same_shape(**tensors):
+    """adam_step / sgd_step: every argument a contiguous float32 tensor of the first one's shape."""
+    first = next(iter(tensors.values()))
+    if not all(is_dense(t) and t.shape == first.shape for t in tensors.values()):
+        raise ValueError(f"{', '.join(tensors)} must be contiguous float32 device tensors of one shape [E,N,H]")
+
+
+_IN_PLACE = " (it is updated in place)"
+
+
 class MPPIEngine:
     def __init__(self, E, mppi: MPPIConfig = None, phys: PhysicalParameters = None, device=0):
-        self.lib = _L.load()
         if not torch.cuda.is_available():
             raise RuntimeError("cartpolesimulation_amd needs an MI355X (gfx950) visible to PyTorch-ROCm; "
                                "there is no CPU fallback.")
-        self.mppi = mppi or MPPIConfig()
-        self.phys = phys or PhysicalParameters()
-        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
-        self.E, self.N, self.H = int(E), int(self.mppi.num_rollouts), int(self.mppi.mpc_horizon)
-        self.P = self.mppi.num_knots
-        self._cfg = build_c_config(self.E, self.mppi, self.phys)
-        self._m_pole = float(np.float32(self.phys.m_pole))
+        self._init_common(E, mppi, phys, device)
         self._h = C.c_void_p()
         rc = self.lib.cpmppi_create(C.byref(self._cfg), self.device.index, C.byref(self._h))
         if rc != 0:
@@ -39,6 +57,12 @@ class MPPIEngine:
         """An engine over a handle somebody else owns (an env group's: pipeline.EnvGroups / cpmppi_groups_create); `close()` then
         only forgets it."""
         self = cls.__new__(cls)
+        self._init_common(E, mppi, phys, device)
+        self._h = C.c_void_p(handle)
+        self._borrowed = True
+        return self
+
+    def _init_common(self, E, mppi, phys, device):
         self.lib = _L.load()
         self.mppi = mppi or MPPIConfig()
         self.phys = phys or PhysicalParameters()
@@ -47,9 +71,6 @@ class MPPIEngine:
         self.P = self.mppi.num_knots
         self._cfg = build_c_config(self.E, self.mppi, self.phys)
         self._m_pole = float(np.float32(self.phys.m_pole))
-        self._h = C.c_void_p(handle)
-        self._borrowed = True
-        return self
 
     # ------------------------------------------------------------------ plumbing
     def close(self):
@@ -98,6 +119,11 @@ class MPPIEngine:
             x = x.reshape(shape)
         return x
 
+    def _as_BH(self, Q):
+        """Control sequences [B,H], also accepted as [B,H,1] (the reference's predictor signature)."""
+        Q = self.tensor(Q)
+        return Q[:, :, 0].contiguous() if Q.dim() == 3 else Q
+
     def empty(self, *shape):
         return torch.empty(*shape, dtype=torch.float32, device=self.device)
 
@@ -107,9 +133,7 @@ class MPPIEngine:
     # ------------------------------------------------------------------ seams
     def predict(self, s0, Q, L=None, horizon=None):
         """predict_core: s0[B,6], Q[B,H] -> traj[B,H+1,6]."""
-        Q = self.tensor(Q)
-        if Q.dim() == 3:
-            Q = Q[:, :, 0].contiguous()
+        Q = self._as_BH(Q)
         B, H = Q.shape
         s0 = self.tensor(s0)
         if s0.dim() == 1:
@@ -127,9 +151,7 @@ class MPPIEngine:
     def trajectory_cost(self, traj, inputs, target_position, target_equilibrium, u_nom=None, u_prev=None,
                         want=("stage", "terminal", "total")):
         traj = self.tensor(traj)
-        inputs = self.tensor(inputs)
-        if inputs.dim() == 3:
-            inputs = inputs[:, :, 0].contiguous()
+        inputs = self._as_BH(inputs)
         B, H = inputs.shape
         if traj.shape != (B, H + 1, 6):
             raise ValueError(f"traj must be [{B},{H + 1},6], got {tuple(traj.shape)}")
@@ -242,9 +264,7 @@ class MPPIEngine:
         same launch records the control period: Q_log[row] = Q, states_log[row+1] = the advanced state; ``row_dev`` (an
         int64 device tensor: the step counter of ``step(offset_dev=...)``, already advanced) replaces ``row`` by its
         value - 1."""
-        if not (torch.is_tensor(s) and s.is_cuda and s.dtype == torch.float32 and s.is_contiguous()):
-            raise ValueError("s must be a contiguous float32 ROCm tensor (it is updated in place)")
-        E = s.shape[0]
+        E = device_tensor("s", s, note=_IN_PLACE).shape[0]
         Q = self.tensor(Q).reshape(E)
         L = self.tensor(L).reshape(E) if L is not None else None
         if states_log is None and Q_log is None:
@@ -252,16 +272,15 @@ class MPPIEngine:
                                                       float(dt_sim), self._stream()))
             return s
         for name, t, tail in (("states_log", states_log, (E, 6)), ("Q_log", Q_log, (E,))):
-            if t is not None and not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous()
-                                      and tuple(t.shape[1:]) == tail):
-                raise ValueError(f"{name} must be a contiguous float32 ROCm tensor [T, {', '.join(map(str, tail))}]")
+            if t is not None:
+                device_tensor(name, t, tail=tail)
         # control periods the logs can take; the kernel itself refuses to write outside them (device counter case)
         log_rows = min(([states_log.shape[0] - 1] if states_log is not None else []) + ([Q_log.shape[0]] if Q_log is not None else []))
         if row_dev is None:
             if not 0 <= row < log_rows:
                 raise IndexError(f"row {row} outside the logs")
-        elif not (torch.is_tensor(row_dev) and row_dev.is_cuda and row_dev.dtype == torch.int64):
-            raise ValueError("row_dev must be an int64 ROCm tensor")
+        else:
+            device_tensor("row_dev", row_dev, torch.int64)
         self._check(self.lib.cpmppi_plant_advance_record(self._h, E, _ptr(s), _ptr(Q), _ptr(L), int(n_substeps), float(dt_sim),
                                                          _ptr(states_log), _ptr(Q_log), int(max(log_rows, 0)), int(row),
                                                          _ptr(row_dev), self._stream()))
@@ -285,16 +304,10 @@ class MPPIEngine:
         the state ``latency`` seconds back (``state_history`` [>= latency / dt_sim + 2, E, 6], zeros with cos = 1 before the run),
         plus ``measurement_noise_table`` [calls,E,4], plus ``angle_offset_table`` [sched_rows,E] float64 on the angle (taken out again
         where ``informed_table`` [sched_rows,E] uint8 says so; None = everywhere)."""
-        if not (torch.is_tensor(s) and s.is_cuda and s.dtype == torch.float32 and s.is_contiguous()):
-            raise ValueError("s must be a contiguous float32 ROCm tensor (it is updated in place)")
-        E = s.shape[0]
+        E = device_tensor("s", s, note=_IN_PLACE).shape[0]
 
         def dev(name, t, tail, dtype=torch.float32):
-            if t is None:
-                return None
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == dtype and t.is_contiguous() and tuple(t.shape[1:]) == tail):
-                raise ValueError(f"{name} must be a contiguous {dtype} ROCm tensor [rows{''.join(', ' + str(x) for x in tail)}]")
-            return t
+            return None if t is None else device_tensor(name, t, dtype, tail)
 
         a = _L.cpmppi_plant_args()
         Q = self.tensor(Q).reshape(E)
@@ -303,9 +316,7 @@ class MPPIEngine:
         a.n_substeps, a.period_steps, a.dt_sim = int(n_substeps), int(period_steps if period_steps is not None else n_substeps), float(dt_sim)
         a.period = int(period)
         if period_dev is not None:
-            if not (torch.is_tensor(period_dev) and period_dev.is_cuda and period_dev.dtype == torch.int64):
-                raise ValueError("period_dev must be an int64 ROCm tensor")
-            a.period_dev = period_dev.data_ptr()
+            a.period_dev = device_tensor("period_dev", period_dev, torch.int64).data_ptr()
         states_log, dd_log, Q_log = dev("states_log", states_log, (E, 6)), dev("dd_log", dd_log, (E, 2)), dev("Q_log", Q_log, (E,))
         rows = [t.shape[0] for t in (states_log, dd_log) if t is not None]
         a.states_log = states_log.data_ptr() if states_log is not None else None
@@ -406,9 +417,7 @@ class MPPIEngine:
 
     def gru_predict(self, s0, Q, h0=None, return_hidden=False):
         """Neural predictor seam: s0[B,6] | [6], Q[B,H], h0[2,B,32] -> traj[B,H+1,6] (and final hidden [2,B,32])."""
-        Q = self.tensor(Q)
-        if Q.dim() == 3:
-            Q = Q[:, :, 0].contiguous()
+        Q = self._as_BH(Q)
         B, H = Q.shape
         s0 = self.tensor(s0)
         if s0.dim() == 1:
@@ -456,9 +465,7 @@ class MPPIEngine:
 
     def adam_step(self, Q, grad, m, v, iteration, learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, gradmax_clip=0.0):
         """One Adam iteration on Q[E,N,H] in place (m, v: caller-owned moments, zero before iteration 1)."""
-        for x in (Q, grad, m, v):
-            if not (isinstance(x, torch.Tensor) and x.is_contiguous() and x.dtype == torch.float32 and x.shape == Q.shape):
-                raise ValueError("Q, grad, m, v must be contiguous float32 device tensors of one shape [E,N,H]")
+        _same_shape(Q=Q, grad=grad, m=m, v=v)
         self._check(self.lib.cpmppi_adam_step(self._h, Q.shape[0], _ptr(Q), _ptr(grad), _ptr(m), _ptr(v), int(iteration),
                                               float(learning_rate), float(beta1), float(beta2), float(epsilon),
                                               float(gradmax_clip), self._stream()))
@@ -466,9 +473,7 @@ class MPPIEngine:
 
     def sgd_step(self, Q, grad, learning_rate, gradmax_clip=0.0):
         """Q <- clip(Q - lr * clip_by_norm(grad)) in place."""
-        for x in (Q, grad):
-            if not (isinstance(x, torch.Tensor) and x.is_contiguous() and x.dtype == torch.float32 and x.shape == Q.shape):
-                raise ValueError("Q, grad must be contiguous float32 device tensors of one shape [E,N,H]")
+        _same_shape(Q=Q, grad=grad)
         self._check(self.lib.cpmppi_sgd_step(self._h, Q.shape[0], _ptr(Q), _ptr(grad), float(learning_rate),
                                              float(gradmax_clip), self._stream()))
         return Q
@@ -541,9 +546,7 @@ class MPPIEngine:
         all-gather of the sequences it writes, ordered on the device, nothing but the kernel on the launch stream.
         Returns (Q_out[E], S_out or None).
         """
-        if not (torch.is_tensor(u_nom) and u_nom.is_cuda and u_nom.dtype == torch.float32 and u_nom.is_contiguous()):
-            raise ValueError("u_nom must be a contiguous float32 ROCm tensor (it is updated in place)")
-        E = u_nom.shape[0]
+        E = device_tensor("u_nom", u_nom, note=_IN_PLACE).shape[0]
         if u_nom.shape != (E, self.H) or E > self.E:
             raise ValueError(f"u_nom must be [E<={self.E},{self.H}], got {tuple(u_nom.shape)}")
         given = [x is not None for x in (delta_u, knots, seed, delta_u_tiled)]
@@ -551,29 +554,22 @@ class MPPIEngine:
             raise ValueError("give exactly one of delta_u, knots, seed, delta_u_tiled")
         a = _L.cpmppi_step_args()
         s0 = self.tensor(s0, (E, 6))
-        tp = self.tensor(target_position).reshape(-1)
-        te = self.tensor(target_equilibrium).reshape(-1)
-        tp = tp.expand(E).contiguous() if tp.numel() == 1 else tp
-        te = te.expand(E).contiguous() if te.numel() == 1 else te
-        Lt = None
-        if L is not None:
-            Lt = self.tensor(L).reshape(-1)
-            Lt = Lt.expand(E).contiguous() if Lt.numel() == 1 else Lt
+        tp, te = self._per_env(target_position, E), self._per_env(target_equilibrium, E)
+        Lt = self._per_env(L, E) if L is not None else None
         noise = None
         if delta_u_tiled is not None:
-            noise = delta_u_tiled
-            if not (torch.is_tensor(noise) and noise.is_cuda and noise.dtype == torch.float32 and noise.is_contiguous()
-                    and noise.numel() >= int(self.lib.cpmppi_tiled_floats(self._h, E))):
-                raise ValueError("delta_u_tiled must be a contiguous float32 ROCm tensor of cpmppi_tiled_floats(E) elements")
+            noise = device_tensor("delta_u_tiled", delta_u_tiled)
+            if noise.numel() < int(self.lib.cpmppi_tiled_floats(self._h, E)):
+                raise ValueError("delta_u_tiled must have cpmppi_tiled_floats(E) elements")
             a.noise_kind = _L.NOISE_DELTA_U_TILED
         elif delta_u is not None:
             noise = self.tensor(delta_u, (E, self.N, self.H))
-            a.noise_kind = L_NOISE[0]
+            a.noise_kind = _L.NOISE_DELTA_U
         elif knots is not None:
             noise = self.tensor(knots, (E, self.N, self.P))
-            a.noise_kind = L_NOISE[1]
+            a.noise_kind = _L.NOISE_KNOTS
         else:
-            a.noise_kind = L_NOISE[2]
+            a.noise_kind = _L.NOISE_PHILOX
             a.seed, a.offset, a.env_offset = int(seed), int(offset), int(env_offset)
         u_prev = self.tensor(u_prev, (E, self.H)) if u_prev is not None else None
         if Q_out is None:
@@ -593,13 +589,12 @@ class MPPIEngine:
         previous_input = self._per_env(previous_input, E) if previous_input is not None else None
         a.previous_input = previous_input.data_ptr() if previous_input is not None else None
         if u_nom_out is not None:
-            if not (torch.is_tensor(u_nom_out) and u_nom_out.is_cuda and u_nom_out.dtype == torch.float32
-                    and u_nom_out.is_contiguous() and u_nom_out.shape == u_nom.shape):
-                raise ValueError("u_nom_out must be a contiguous float32 ROCm tensor of u_nom's shape")
+            if device_tensor("u_nom_out", u_nom_out).shape != u_nom.shape:
+                raise ValueError("u_nom_out must have u_nom's shape")
             a.u_nom_out = u_nom_out.data_ptr()
         if offset_dev is not None:           # int64 device scalar: Philox step counter kept on the device (graph replay)
-            if not (torch.is_tensor(offset_dev) and offset_dev.is_cuda and offset_dev.dtype == torch.int64 and offset_dev.numel() == 1):
-                raise ValueError("offset_dev must be a one-element int64 ROCm tensor")
+            if device_tensor("offset_dev", offset_dev, torch.int64).numel() != 1:
+                raise ValueError("offset_dev must have one element")
             a.offset_dev = offset_dev.data_ptr()
         if _prepare:
             # every tensor the argument block points into is kept alive by the returned object
@@ -664,6 +659,3 @@ class PreparedStep:
         else:
             e._check(e.lib.cpmppi_step(e._h, C.byref(self.args), e._stream()))
         return self.Q_out, self.S_out
-
-
-L_NOISE = (_L.NOISE_DELTA_U, _L.NOISE_KNOTS, _L.NOISE_PHILOX)

@@ -7,67 +7,29 @@ stdev to the ``cem_best_k`` cheapest, floor stdev at ``cem_stdev_min``}; apply `
 mid-point of the limits) and stdev (append sqrt(0.5)).  Sampling, rollout, cost and the top-k refit all run on the GPU
 (cpmppi_cem_sample, cpmppi_rollout_cost, cpmppi_cem_update); ``num_envs`` problem instances advance in one launch.
 """
-import time as _time
+import math
 
-import numpy as np
 import torch
 
-from .configs import MPPIConfig, PhysicalParameters
-from .optimizer_mppi import _vec
+from ._optimizer_base import _OptimizerBase
 
 
-class optimizer_cem:
+class optimizer_cem(_OptimizerBase):
     optimizer_name = "cem"
+    _unknown_predictor = "the sampling optimizers run on the ODE_v0 and ODE predictors"
 
     def __init__(self, predictor=None, cost_function=None, control_limits=None, computation_library=None, seed=None,
                  mpc_horizon=35, mpc_timestep=0.02, cem_outer_it=3, cem_initial_action_stdev=0.5, num_rollouts=200,
                  cem_stdev_min=0.01, cem_best_k=40, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
                  math_mode="fast", intermediate_steps=10, phys=None, device=0, variable_parameters=None, **kwargs):
-        low, high = (-1.0, 1.0) if control_limits is None else (float(np.asarray(control_limits[0]).reshape(-1)[0]),
-                                                                  float(np.asarray(control_limits[1]).reshape(-1)[0]))
-        self.action_low, self.action_high = low, high
-        if seed is None:
-            import os
-            seed = (_time.time_ns() ^ os.getpid()) & 0x7FFFFFFFFFFFFFFF
-        self.seed = int(seed)
-        self.num_envs = int(num_envs)
+        super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
+                         variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
+                         intermediate_steps, control_mode="clip", shift_mode="none", math_mode=math_mode)
         self.cem_outer_it, self.cem_best_k = int(cem_outer_it), int(cem_best_k)
         self.cem_initial_action_stdev, self.cem_stdev_min = float(cem_initial_action_stdev), float(cem_stdev_min)
         self.warmup, self.warmup_iterations = bool(warmup), int(warmup_iterations)
-        if cost_function is not None and cost_function_specification is None:
-            cost_function_specification = getattr(cost_function, "cost_name", None)
-            cost_weights = cost_weights or getattr(cost_function, "weights", None)
-        self.variable_parameters = variable_parameters if variable_parameters is not None else \
-            getattr(cost_function, "variable_parameters", None)
-        self.cfg = MPPIConfig(seed=self.seed, mpc_horizon=int(mpc_horizon), mpc_timestep=float(mpc_timestep),
-                              num_rollouts=int(num_rollouts), intermediate_steps=int(intermediate_steps),
-                              cost_function_specification=cost_function_specification or "quadratic_boundary_grad_minimal",
-                              cost_weights=dict(cost_weights or {}), control_mode="clip", shift_mode="none",
-                              math_mode=math_mode, action_low=low, action_high=high)
-        self.phys = phys or PhysicalParameters()
-        self.device = device
-        self.num_rollouts, self.mpc_horizon = self.cfg.num_rollouts, self.cfg.mpc_horizon
-        self.optimizer_logging = optimizer_logging
-        self.logging_values = {}
-        self.engine = None
         self.step_counter = 0
-
-    def configure(self, dt=None, predictor_specification=None, num_envs=None, **kwargs):
-        from .engine import MPPIEngine
-        if dt is not None:
-            self.cfg.mpc_timestep = float(dt)
-        if num_envs is not None:
-            self.num_envs = int(num_envs)
-        spec = None if predictor_specification is None else str(predictor_specification).split(":")[0]
-        if spec in ("ODE", "ODE_default"):        # next_state_predictor_ODE: Euler-Cromer, no bounce (config_controllers.yml:3)
-            self.cfg.predictor_type = "ODE"
-        elif spec in ("ODE_v0", "ODE_v0_default"):
-            self.cfg.predictor_type = "ODE_v0"
-        elif spec is not None:
-            raise NotImplementedError("the sampling optimizers run on the ODE_v0 and ODE predictors")
-        self.engine = MPPIEngine(self.num_envs, self.cfg, self.phys, device=self.device)
-        self.optimizer_reset()
 
     def _refine(self, Q, s_t, tp, te, L):
         """Hook of the CEM + gradient hybrids: improve the samples before they are ranked."""
@@ -80,22 +42,16 @@ class optimizer_cem:
         self.step_counter = 0
         self._first = True
 
+    def _shift(self):
+        """Mean and stdev one control step on: the mid-point of the limits / sqrt(0.5) appended.  -> that mid-point."""
+        mid = 0.5 * (self.action_low + self.action_high)
+        self.dist_mue = torch.cat([self.dist_mue[:, 1:], torch.full_like(self.dist_mue[:, :1], mid)], dim=1).contiguous()
+        self.stdev = torch.cat([self.stdev[:, 1:], torch.full_like(self.stdev[:, :1], math.sqrt(0.5))], dim=1).contiguous()
+        return mid
+
     def step(self, s, time=None, as_tensor=False):
-        if self.engine is None:
-            self.configure()
+        s_t, single, E, tp, te, L = self._begin_step(s)
         eng = self.engine
-        eng.apply_pole_mass_of(self.variable_parameters)
-        s_t = eng.tensor(s)
-        single = s_t.dim() == 1
-        s_t = s_t.reshape(-1, 6)
-        E = s_t.shape[0]
-        if E != self.num_envs:
-            raise ValueError(f"optimizer configured for {self.num_envs} envs, got {E} states")
-        vp = self.variable_parameters
-        # (uploaded ONCE per control step: every sampler / cost / gradient launch of the iterations below reuses the tensors)
-        tp = eng.tensor(_vec(getattr(vp, "target_position", None), E, 0.0))
-        te = eng.tensor(_vec(getattr(vp, "target_equilibrium", None), E, 1.0))
-        L = eng.tensor(_vec(getattr(vp, "L", None), E, self.phys.L))
         iters = self.warmup_iterations if (self.warmup and self._first) else self.cem_outer_it
         self._first = False
         for _ in range(iters):
@@ -108,13 +64,8 @@ class optimizer_cem:
         if self.optimizer_logging:
             self.logging_values = {"Q_logged": u.cpu().numpy(), "J_logged": S.cpu().numpy(),
                                    "u_logged": self.dist_mue.cpu().numpy()}
-        mid = 0.5 * (self.action_low + self.action_high)
-        self.dist_mue = torch.cat([self.dist_mue[:, 1:], torch.full_like(self.dist_mue[:, :1], mid)], dim=1).contiguous()
-        self.stdev = torch.cat([self.stdev[:, 1:], torch.full_like(self.stdev[:, :1], float(np.sqrt(0.5)))], dim=1).contiguous()
-        if as_tensor:
-            return u
-        q = u.cpu().numpy()
-        return q[:1].copy() if single else q.reshape(E, 1).copy()
+        self._shift()
+        return self._result(u, single, as_tensor)
 
 
 class optimizer_cem_gmm(optimizer_cem):
@@ -131,21 +82,8 @@ class optimizer_cem_gmm(optimizer_cem):
         self.centres = self.dist_mue[:, None, :].contiguous()           # [E, 1, H]: one component until elites exist
 
     def step(self, s, time=None, as_tensor=False):
-        if self.engine is None:
-            self.configure()
+        s_t, single, E, tp, te, L = self._begin_step(s)
         eng = self.engine
-        eng.apply_pole_mass_of(self.variable_parameters)
-        s_t = eng.tensor(s)
-        single = s_t.dim() == 1
-        s_t = s_t.reshape(-1, 6)
-        E = s_t.shape[0]
-        if E != self.num_envs:
-            raise ValueError(f"optimizer configured for {self.num_envs} envs, got {E} states")
-        vp = self.variable_parameters
-        # (uploaded ONCE per control step: every sampler / cost / gradient launch of the iterations below reuses the tensors)
-        tp = eng.tensor(_vec(getattr(vp, "target_position", None), E, 0.0))
-        te = eng.tensor(_vec(getattr(vp, "target_equilibrium", None), E, 1.0))
-        L = eng.tensor(_vec(getattr(vp, "L", None), E, self.phys.L))
         ar = torch.arange(E, device=self.dist_mue.device)[:, None]
         for _ in range(self.cem_outer_it):
             Q = eng.cem_gmm_sample(self.centres, self.stdev, self.seed, offset=self.step_counter)
@@ -157,14 +95,9 @@ class optimizer_cem_gmm(optimizer_cem):
         if self.optimizer_logging:
             self.logging_values = {"Q_logged": u.cpu().numpy(), "J_logged": S.cpu().numpy(),
                                    "u_logged": self.centres[:, 0].cpu().numpy()}
-        mid = 0.5 * (self.action_low + self.action_high)
+        mid = self._shift()
         self.centres = torch.cat([self.centres[:, :, 1:], torch.full_like(self.centres[:, :, :1], mid)], dim=2).contiguous()
-        self.dist_mue = torch.cat([self.dist_mue[:, 1:], torch.full_like(self.dist_mue[:, :1], mid)], dim=1).contiguous()
-        self.stdev = torch.cat([self.stdev[:, 1:], torch.full_like(self.stdev[:, :1], float(np.sqrt(0.5)))], dim=1).contiguous()
-        if as_tensor:
-            return u
-        q = u.cpu().numpy()
-        return q[:1].copy() if single else q.reshape(E, 1).copy()
+        return self._result(u, single, as_tensor)
 
 
 class optimizer_cem_naive_grad(optimizer_cem):
@@ -221,22 +154,8 @@ class optimizer_random_action(optimizer_cem):
         super().__init__(*args, num_rollouts=num_rollouts, cem_outer_it=1, cem_best_k=1, **kwargs)
 
     def step(self, s, time=None, as_tensor=False):
-        import math
-        if self.engine is None:
-            self.configure()
+        s_t, single, E, tp, te, L = self._begin_step(s)
         eng = self.engine
-        eng.apply_pole_mass_of(self.variable_parameters)
-        s_t = eng.tensor(s)
-        single = s_t.dim() == 1
-        s_t = s_t.reshape(-1, 6)
-        E = s_t.shape[0]
-        if E != self.num_envs:
-            raise ValueError(f"optimizer configured for {self.num_envs} envs, got {E} states")
-        vp = self.variable_parameters
-        # (uploaded ONCE per control step: every sampler / cost / gradient launch of the iterations below reuses the tensors)
-        tp = eng.tensor(_vec(getattr(vp, "target_position", None), E, 0.0))
-        te = eng.tensor(_vec(getattr(vp, "target_equilibrium", None), E, 1.0))
-        L = eng.tensor(_vec(getattr(vp, "L", None), E, self.phys.L))
         # N(0,1) from the device Philox sampler (clip limits far away), mapped to U(low, high) through the normal CDF
         wide = eng.zeros(E, self.mpc_horizon)
         z = self._normal(wide, self.step_counter)
@@ -248,10 +167,7 @@ class optimizer_random_action(optimizer_cem):
         u = Q[torch.arange(E, device=S.device), best, 0].clone()
         if self.optimizer_logging:
             self.logging_values = {"Q_logged": u.cpu().numpy(), "J_logged": S.cpu().numpy()}
-        if as_tensor:
-            return u
-        q = u.cpu().numpy()
-        return q[:1].copy() if single else q.reshape(E, 1).copy()
+        return self._result(u, single, as_tensor)
 
     def _normal(self, zeros_EH, offset):
         # the sampler clips to the control limits, so draw with a small stdev and rescale: z = (x / 0.01), |x| <= 1 keeps

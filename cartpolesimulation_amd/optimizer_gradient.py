@@ -21,69 +21,33 @@ torch is used for the per-plan bookkeeping (gather of survivors, shift).  ``num_
 launch.
 """
 import math
-import time as _time
 
-import numpy as np
 import torch
 
-from .configs import MPPIConfig, PhysicalParameters
-from .optimizer_mppi import _vec
+from ._optimizer_base import _OptimizerBase
 
 
-class _GradientBase:
+class _GradientBase(_OptimizerBase):
     optimizer_name = "gradient"
+    _unknown_predictor = "the adjoint kernel differentiates the ODE_v0 and ODE predictors"
 
-    def _setup(self, cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, sample_stdev, period,
-               num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
-               variable_parameters, optimizer_logging, horizon_reduce):
-        low, high = (-1.0, 1.0) if control_limits is None else (float(np.asarray(control_limits[0]).reshape(-1)[0]),
-                                                                  float(np.asarray(control_limits[1]).reshape(-1)[0]))
-        self.action_low, self.action_high = low, high
-        if seed is None:
-            import os
-            seed = (_time.time_ns() ^ os.getpid()) & 0x7FFFFFFFFFFFFFFF
-        self.seed = int(seed)
-        self.num_envs = int(num_envs)
-        if cost_function is not None and cost_function_specification is None:
-            cost_function_specification = getattr(cost_function, "cost_name", None)
-            cost_weights = cost_weights or getattr(cost_function, "weights", None)
-        self.variable_parameters = variable_parameters if variable_parameters is not None else \
-            getattr(cost_function, "variable_parameters", None)
-        dt = float(mpc_timestep)
+    def __init__(self, cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, sample_stdev, period,
+                 num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
+                 variable_parameters, optimizer_logging, horizon_reduce):
         # the handle's sampler draws knots ~ N(0, SQRTRHOINV / sqrt(dt)): set it to the requested stdev
-        self.cfg = MPPIConfig(seed=self.seed, mpc_horizon=int(mpc_horizon), mpc_timestep=dt,
-                              num_rollouts=int(num_rollouts), intermediate_steps=int(intermediate_steps),
-                              cost_function_specification=cost_function_specification or "quadratic_boundary_grad_minimal",
-                              cost_weights=dict(cost_weights or {}), control_mode="clip", shift_mode="none",
-                              math_mode="fast", action_low=low, action_high=high, horizon_reduce=horizon_reduce,
-                              SQRTRHOINV=float(sample_stdev) * math.sqrt(dt),
-                              period_interpolation_inducing_points=int(period))
-        self.phys = phys or PhysicalParameters()
-        self.device = device
-        self.num_rollouts, self.mpc_horizon = self.cfg.num_rollouts, self.cfg.mpc_horizon
-        self.optimizer_logging = optimizer_logging
-        self.logging_values = {}
-        self.engine = None
+        super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
+                         variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
+                         intermediate_steps, control_mode="clip", shift_mode="none", math_mode="fast",
+                         horizon_reduce=horizon_reduce, SQRTRHOINV=float(sample_stdev) * math.sqrt(float(mpc_timestep)),
+                         period_interpolation_inducing_points=int(period))
         self.count = 0               # control steps taken
         self.draws = 0               # sampler launches (the Philox offset)
 
-    def configure(self, dt=None, predictor_specification=None, num_envs=None, **kwargs):
-        from .engine import MPPIEngine
-        if dt is not None and float(dt) != self.cfg.mpc_timestep:
+    def _set_timestep(self, dt):
+        if dt != self.cfg.mpc_timestep:          # the sampling stdev stays what the constructor was asked for
             s = self.cfg.SQRTRHOINV / math.sqrt(self.cfg.mpc_timestep)
-            self.cfg.mpc_timestep = float(dt)
-            self.cfg.SQRTRHOINV = s * math.sqrt(float(dt))
-        if num_envs is not None:
-            self.num_envs = int(num_envs)
-        spec = None if predictor_specification is None else str(predictor_specification).split(":")[0]
-        if spec in ("ODE", "ODE_default"):      # next_state_predictor_ODE (Euler-Cromer, no bounce): the shipped config_controllers.yml:2-3
-            self.cfg.predictor_type = "ODE"     # pairs it with `optimizer: rpgd`; the adjoint kernel has that substep's reverse too
-        elif spec in ("ODE_v0", "ODE_v0_default"):
-            self.cfg.predictor_type = "ODE_v0"
-        elif spec is not None:
-            raise NotImplementedError("the adjoint kernel differentiates the ODE_v0 and ODE predictors")
-        self.engine = MPPIEngine(self.num_envs, self.cfg, self.phys, device=self.device)
-        self.optimizer_reset()
+            self.cfg.mpc_timestep = dt
+            self.cfg.SQRTRHOINV = s * math.sqrt(dt)
 
     # -- sampling ------------------------------------------------------------------------------------------------
     def _draw(self):
@@ -103,13 +67,6 @@ class _GradientBase:
         self._first = True
 
     # -- one control step ----------------------------------------------------------------------------------------
-    def _targets(self, E):
-        vp = self.variable_parameters
-        self.engine.apply_pole_mass_of(vp)
-        t = self.engine.tensor      # (uploaded once per control step; every gradient / cost launch below reuses the tensors)
-        return (t(_vec(getattr(vp, "target_position", None), E, 0.0)), t(_vec(getattr(vp, "target_equilibrium", None), E, 1.0)),
-                t(_vec(getattr(vp, "L", None), E, self.phys.L)))
-
     def _descend(self, s_t, tp, te, L, iterations):
         eng = self.engine
         for _ in range(iterations):
@@ -140,20 +97,7 @@ class _GradientBase:
             self.logging_values = {"Q_logged": u.cpu().numpy(), "J_logged": S.cpu().numpy(),
                                    "u_logged": self.Q[rows, best].cpu().numpy()}
         self.count += 1
-        if as_tensor:
-            return u
-        q = u.cpu().numpy()
-        return q[:1].copy() if single else q.reshape(E, 1).copy()
-
-    def _state(self, s):
-        if self.engine is None:
-            self.configure()
-        s_t = self.engine.tensor(s)
-        single = s_t.dim() == 1
-        s_t = s_t.reshape(-1, 6)
-        if s_t.shape[0] != self.num_envs:
-            raise ValueError(f"optimizer configured for {self.num_envs} envs, got {s_t.shape[0]} states")
-        return s_t, single
+        return self._result(u, single, as_tensor)
 
 
 class optimizer_gradient(_GradientBase):
@@ -170,9 +114,9 @@ class optimizer_gradient(_GradientBase):
         self.adam_epsilon, self.gradmax_clip, self.rtol = float(adam_epsilon), float(gradmax_clip), float(rtol)
         self.gradient_steps, self.warmup, self.warmup_iterations = int(gradient_steps), bool(warmup), int(warmup_iterations)
         self.initial_action_stdev = float(initial_action_stdev)
-        self._setup(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, initial_action_stdev, 10,
-                    num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
-                    variable_parameters, optimizer_logging, horizon_reduce)
+        super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, initial_action_stdev,
+                         10, num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
+                         variable_parameters, optimizer_logging, horizon_reduce)
 
     def _draw(self):
         """Independent N(0, initial_action_stdev) per time-step, clipped (cpmppi_cem_sample)."""
@@ -184,8 +128,7 @@ class optimizer_gradient(_GradientBase):
         return Q
 
     def step(self, s, time=None, as_tensor=False):
-        s_t, single = self._state(s)
-        tp, te, L = self._targets(s_t.shape[0])
+        s_t, single, E, tp, te, L = self._begin_step(s)
         iters = self.warmup_iterations if (self.warmup and self._first) else self.gradient_steps
         self._first = False
         S = self._descend(s_t, tp, te, L, iters)
@@ -217,9 +160,9 @@ class optimizer_rpgd(_GradientBase):
         self.uniform_dist_min, self.uniform_dist_max = float(uniform_dist_min), float(uniform_dist_max)
         self.opt_keep_k = max(1, int(float(opt_keep_k_ratio) * int(num_rollouts)))
         stdev = self.sample_stdev if SAMPLING_DISTRIBUTION == "normal" else 1.0
-        self._setup(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, stdev,
-                    period_interpolation_inducing_points, num_envs, cost_function_specification, cost_weights,
-                    intermediate_steps, phys, device, variable_parameters, optimizer_logging, horizon_reduce)
+        super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, stdev,
+                         period_interpolation_inducing_points, num_envs, cost_function_specification, cost_weights,
+                         intermediate_steps, phys, device, variable_parameters, optimizer_logging, horizon_reduce)
 
     def _shape_samples(self, z):
         if self.distribution == "normal":
@@ -229,9 +172,7 @@ class optimizer_rpgd(_GradientBase):
         return lo + (hi - lo) * 0.5 * (1.0 + torch.erf(z * (1.0 / math.sqrt(2.0))))     # N(0,1) -> U(lo, hi)
 
     def step(self, s, time=None, as_tensor=False):
-        s_t, single = self._state(s)
-        E = s_t.shape[0]
-        tp, te, L = self._targets(E)
+        s_t, single, E, tp, te, L = self._begin_step(s)
         iters = self.warmup_iterations if (self.warmup and self._first) else self.outer_its
         self._first = False
         S = self._descend(s_t, tp, te, L, iters)

@@ -11,26 +11,20 @@ Differences from a drop-in that only replaced the arithmetic: ``num_envs`` indep
 in ONE launch (``step`` accepts ``s[6]`` or ``s[E,6]``), and perturbations come from a counter-based device RNG unless
 ``noise="sfc64"`` asks for numpy's SFC64 stream (bit-identical knots to the reference's sampler for a given seed).
 """
-import time as _time
-
 import numpy as np
 import torch
 
-from .configs import MPPIConfig, PhysicalParameters
+from ._optimizer_base import _OptimizerBase, _vec
+from .sampling import SAMPLING_TYPES, sample_delta_u_sfc64, sample_knots_sfc64
 
 # cost plugins with a control-change-rate term against the control applied last (Q_ccrc, CartPole/__init__.py:517-518)
 PREVIOUS_INPUT_COSTS = ("quadratic_boundary_grad", "quadratic_boundary", "quadratic_boundary_nonconvex")
 
 
-def _vec(x, E, default):
-    if x is None:
-        return np.full(E, default, dtype=np.float32)
-    x = np.asarray(x.cpu() if hasattr(x, "cpu") else x, dtype=np.float32).reshape(-1)
-    return np.full(E, x[0], dtype=np.float32) if x.size == 1 else x.astype(np.float32)
-
-
-class optimizer_mppi:
+class optimizer_mppi(_OptimizerBase):
     optimizer_name = "mppi"
+    _cost_name_attributes = ("cost_name", "cost_function_name")
+    _unknown_predictor = "built predictors: ODE_v0, ODE and GRU-6IN-32H1-32H2-5OUT-*"
 
     def __init__(self, predictor=None, cost_function=None, control_limits=None, computation_library=None, seed=None,
                  cc_weight=1.0, R=1.0, LBD=100.0, mpc_horizon=35, num_rollouts=3500, NU=1000.0, SQRTRHOINV=0.03,
@@ -40,50 +34,25 @@ class optimizer_mppi:
                  math_mode="fast", intermediate_steps=10, phys=None, device=0, variable_parameters=None, gru_model=None,
                  SAMPLING_TYPE="interpolated", predictor_type="ODE_v0", **kwargs):
         self.predictor, self.cost_function = predictor, cost_function
-        low, high = (-1.0, 1.0) if control_limits is None else (float(np.asarray(control_limits[0]).reshape(-1)[0]),
-                                                                  float(np.asarray(control_limits[1]).reshape(-1)[0]))
-        self.action_low, self.action_high = low, high
         self.lib = computation_library
-        if seed is None:                                   # others/globals_and_utils.py:198-214 (time xor pid)
-            import os
-            seed = (_time.time_ns() ^ os.getpid()) & 0x7FFFFFFFFFFFFFFF
-        self.seed = int(seed)
-        self.num_envs = int(num_envs)
         if noise not in ("philox", "sfc64"):
             raise ValueError("noise must be 'philox' (device RNG) or 'sfc64' (numpy stream, reference-identical knots)")
         self.noise = noise
         # config_controllers.yml:28 (mppi-cartpole SAMPLING_TYPE).  The device sampler implements "interpolated"; the other
         # modes exist on numpy's SFC64 stream (sampling.sample_delta_u_sfc64), i.e. with noise="sfc64"
-        from .sampling import SAMPLING_TYPES
         if SAMPLING_TYPE not in SAMPLING_TYPES:
             raise ValueError(f"SAMPLING_TYPE must be one of {SAMPLING_TYPES}")
         if SAMPLING_TYPE != "interpolated" and noise != "sfc64":
             raise ValueError(f"SAMPLING_TYPE={SAMPLING_TYPE!r} is built on the numpy SFC64 stream only: pass noise='sfc64'")
         self.sampling_type = SAMPLING_TYPE
-        if cost_function is not None and cost_function_specification is None:
-            cost_function_specification = getattr(cost_function, "cost_name", None) or \
-                getattr(cost_function, "cost_function_name", None)
-            cost_weights = cost_weights or getattr(cost_function, "weights", None)
-        self.variable_parameters = variable_parameters if variable_parameters is not None else \
-            getattr(cost_function, "variable_parameters", None)
-        self.cfg = MPPIConfig(seed=self.seed, mpc_horizon=int(mpc_horizon), mpc_timestep=float(mpc_timestep),
-                              num_rollouts=int(num_rollouts), cc_weight=cc_weight, R=R, LBD=LBD, NU=NU,
-                              SQRTRHOINV=SQRTRHOINV,
-                              period_interpolation_inducing_points=int(period_interpolation_inducing_points),
-                              intermediate_steps=int(intermediate_steps),
-                              cost_function_specification=cost_function_specification or
-                              "quadratic_boundary_grad_minimal",
-                              cost_weights=dict(cost_weights or {}), horizon_reduce=horizon_reduce,
-                              control_mode=control_mode, shift_mode=shift_mode, correction_u=correction_u,
-                              math_mode=math_mode, action_low=low, action_high=high, predictor_type=predictor_type)
-        self.phys = phys or PhysicalParameters()
-        self.device = device
-        self.num_rollouts, self.mpc_horizon = self.cfg.num_rollouts, self.cfg.mpc_horizon
-        self.optimizer_logging = optimizer_logging
+        super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
+                         variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
+                         intermediate_steps, cc_weight=cc_weight, R=R, LBD=LBD, NU=NU, SQRTRHOINV=SQRTRHOINV,
+                         period_interpolation_inducing_points=int(period_interpolation_inducing_points),
+                         horizon_reduce=horizon_reduce, control_mode=control_mode, shift_mode=shift_mode,
+                         correction_u=correction_u, math_mode=math_mode, predictor_type=predictor_type)
         self.calculate_optimal_trajectory = calculate_optimal_trajectory
-        self.logging_values = {}
         self.optimal_trajectory = None
-        self.engine = None
         self.u_nom = None
         self.step_counter = 0
         self.gru_model = gru_model           # dict of GRU-6IN-32H1-32H2-5OUT weights -> neural predictor in the loop
@@ -94,32 +63,19 @@ class optimizer_mppi:
 
     # ------------------------------------------------------------------
     def configure(self, dt=None, predictor_specification=None, num_envs=None, **kwargs):
-        from .engine import MPPIEngine
-        if dt is not None:
-            self.cfg.mpc_timestep = float(dt)
-        if num_envs is not None:
-            self.num_envs = int(num_envs)
         neural = predictor_specification is not None and str(predictor_specification).startswith("GRU-6IN-32H1-32H2-5OUT")
+        # (a GRU specification leaves the ODE integrator of the constructor alone: the network runs inside the fused kernel)
+        self._configure_problem(dt, None if neural else predictor_specification, num_envs)
         if isinstance(self.gru_model, (str, bytes)) or hasattr(self.gru_model, "__fspath__"):
             from .model_folder import load_gru_model          # an SI_Toolkit model folder (net-info, normalisation, weights)
             self.gru_model = load_gru_model(self.gru_model)
         if neural and self.gru_model is None:
             raise ValueError("a GRU predictor_specification needs gru_model=dict(weights) or a model folder path "
                              "(no GRU model files ship in-tree)")
-        spec = None if predictor_specification is None else str(predictor_specification).split(":")[0]
-        if spec in ("ODE", "ODE_default"):
-            # predictors_customization.py:25-69 is a DIFFERENT integrator (Euler-Cromer, atan2 angle, no edge bounce; one
-            # control step already lies 1.6e-3 from ODE_v0): the rollout kernel's predictor_ODE form - what the
-            # shipped config_controllers.yml:3,14 select
-            self.cfg.predictor_type = "ODE"
-        elif spec in ("ODE_v0", "ODE_v0_default"):
-            self.cfg.predictor_type = "ODE_v0"
-        elif not neural and spec is not None:
-            raise NotImplementedError("built predictors: ODE_v0, ODE and GRU-6IN-32H1-32H2-5OUT-*")
         if self.gru_model is not None and not (neural or predictor_specification is None):
             raise ValueError(f"gru_model was given but predictor_specification={predictor_specification!r} selects the ODE "
                              "predictor: the model would be ignored")
-        self.engine = MPPIEngine(self.num_envs, self.cfg, self.phys, device=self.device)
+        self.engine = self._new_engine()
         E, N, H = self.num_envs, self.num_rollouts, self.mpc_horizon
         if self.gru_model is not None and (neural or predictor_specification is None):
             self.engine.set_gru(self.gru_model)
@@ -165,22 +121,13 @@ class optimizer_mppi:
             self._h2d_done = torch.cuda.Event()
         else:
             self._h2d_done.synchronize()                      # (the previous upload has left the pinned block)
-        vp, hv = self.variable_parameters, self._hview
+        hv = self._hview
         hv[:6 * E] = s_np.reshape(-1)
-        hv[6 * E:7 * E] = _vec(getattr(vp, "target_position", None), E, 0.0)
-        hv[7 * E:8 * E] = _vec(getattr(vp, "target_equilibrium", None), E, 1.0)
-        hv[8 * E:9 * E] = _vec(getattr(vp, "L", None), E, self.phys.L)
+        hv[6 * E:7 * E], hv[7 * E:8 * E], hv[8 * E:9 * E] = self._attributes(E)
         self._dblock.copy_(self._hblock, non_blocking=True)
         self._h2d_done.record()
         d = self._dblock
         return d[:6 * E].view(E, 6), d[6 * E:7 * E], d[7 * E:8 * E], d[8 * E:9 * E]
-
-    def _attributes(self, E):
-        vp = self.variable_parameters
-        tp = _vec(getattr(vp, "target_position", None), E, 0.0)
-        te = _vec(getattr(vp, "target_equilibrium", None), E, 1.0)
-        L = _vec(getattr(vp, "L", None), E, self.phys.L)
-        return tp, te, L
 
     def _step_host_single(self, s):
         """One env, state on the host: the call `Q = controller.step(s, time, updated_attributes)` makes once per control
@@ -264,20 +211,12 @@ class optimizer_mppi:
                 raise ValueError(f"optimizer configured for {self.num_envs} envs, got {E} states")
             s_t, tp, te, L = self._upload(s_np, E)
         else:
-            s_t = eng.tensor(s)
-            single = s_t.dim() == 1
-            s_t = s_t.reshape(-1, 6)
-            E = s_t.shape[0]
-            if E != self.num_envs:
-                raise ValueError(f"optimizer configured for {self.num_envs} envs, got {E} states")
-            tp, te, L = self._attributes(E)
+            s_t, single, E, tp, te, L = self._begin_step(s)    # (its own pole-mass call finds the value unchanged)
         kw = {}
         if self.noise == "sfc64" and self.sampling_type != "interpolated":
-            from .sampling import sample_delta_u_sfc64
             kw["delta_u"] = sample_delta_u_sfc64(self._rng, E, self.num_rollouts, self.mpc_horizon, self.cfg.sigma,
                                                  self.sampling_type)
         elif self.noise == "sfc64":
-            from .sampling import sample_knots_sfc64
             kw["knots"] = sample_knots_sfc64(self._rng, E, self.num_rollouts, self.cfg)
         else:
             kw.update(seed=self.seed, offset=self.step_counter)
@@ -313,12 +252,9 @@ class optimizer_mppi:
                                    "u_logged": self.u_nom.cpu().numpy()}
         if self.calculate_optimal_trajectory:
             self.optimal_trajectory = eng.predict(s_t, self.u_nom, L=L).cpu().numpy()
-        if as_tensor:
-            return self.Q
+        if as_tensor or not self.Q.is_cuda:
+            return self._result(self.Q, single, as_tensor)
         # the single D2H copy float(controller.step(...)) forces (CartPole/__init__.py:509): into a pinned buffer, then wait
-        if not self.Q.is_cuda:
-            q = self.Q.numpy().copy()
-            return q[:1] if single else q.reshape(E, 1)
         if self._hq is None or self._hq.numel() != E:
             self._hq = torch.empty(E, dtype=torch.float32).pin_memory()
             self._q_done = torch.cuda.Event()

@@ -19,7 +19,7 @@ import torch
 
 from . import _lib as _L
 from .configs import MPPIConfig, PhysicalParameters
-from .engine import MPPIEngine
+from .engine import MPPIEngine, device_tensor
 
 
 def split_envs(E, groups):
@@ -137,8 +137,8 @@ class EnvGroups:
         themselves; `prepare` + `run` is the one-call form)."""
         E = self.E
         for name, t in (("s0", s0), ("u_nom", u_nom), ("target_position", target_position), ("target_equilibrium", target_equilibrium)):
-            if not (torch.is_tensor(t) and t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and t.shape[0] == E):
-                raise ValueError(f"{name} must be a contiguous float32 ROCm tensor with {E} rows")
+            if device_tensor(name, t).shape[0] != E:
+                raise ValueError(f"{name} must have {E} rows")
         if Q_out is None:
             Q_out = torch.empty(E, dtype=torch.float32, device=self.device)
         preps = []

@@ -12,7 +12,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
-from .configs import MPPIConfig, PhysicalParameters
+from .configs import MPPIConfig, PhysicalParameters, ode_predictor_type
 from .state_utilities import STATE_INDICES, STATE_VARIABLES, CONTROL_INPUTS, create_cartpole_state  # noqa: F401
 
 
@@ -21,13 +21,6 @@ def _engine(horizon, dt, intermediate_steps, phys, math_mode, device, predictor_
     cfg = MPPIConfig(num_rollouts=1, mpc_horizon=max(1, int(horizon)), mpc_timestep=float(dt),
                      intermediate_steps=int(intermediate_steps), math_mode=math_mode, predictor_type=predictor_type)
     return MPPIEngine(1, cfg, phys, device=device)
-
-
-def _apply_pole_mass(eng, variable_parameters):
-    """predictor_ODE reads variable_parameters.m_pole at every call (predictors_customization.py:55-58)."""
-    m = getattr(variable_parameters, "m_pole", None) if variable_parameters is not None else None
-    if m is not None:                      # (by value: the attribute may be mutated in place between calls)
-        eng.set_pole_mass(float(np.asarray(m.cpu() if hasattr(m, "cpu") else m, dtype=np.float32).reshape(-1)[0]))
 
 
 def _pole_length(variable_parameters, phys):
@@ -56,8 +49,7 @@ class next_state_predictor_ODE_v0:
         assert Q.ndim == 2
         assert s.ndim == 2
         L = _pole_length(self.variable_parameters, self.phys)
-        if self.predictor_type == "ODE":
-            _apply_pole_mass(self._eng, self.variable_parameters)
+        self._eng.apply_pole_mass_of(self.variable_parameters)
         out = self._eng.predict(s, Q[:, :1], L=L)[:, 1]
         return out if as_tensor else out.cpu().numpy()
 
@@ -102,8 +94,7 @@ class predictor_ODE_v0:
         s0 = eng.tensor(initial_state)
         if s0.dim() == 2 and s0.shape[0] == 1 and Q.shape[0] != 1:
             s0 = s0[0]
-        if self.predictor_type == "ODE":
-            _apply_pole_mass(eng, self.variable_parameters)
+        eng.apply_pole_mass_of(self.variable_parameters)
         out = eng.predict(s0, Q.contiguous(), L=_pole_length(self.variable_parameters, self.phys))
         return out if as_tensor else out.cpu().numpy()
 
@@ -149,16 +140,8 @@ class PredictorWrapper:
 
     def update_predictor_config_from_specification(self, predictor_specification=None, **kwargs):
         spec = predictor_specification or "ODE_v0"
-        name = str(spec).split(":")[0]
-        if name in ("ODE", "ODE_default"):
-            # predictors_customization.py:25-69: Euler-Cromer, atan2 angle, no edge bounce - a different integrator from
-            # ODE_v0 (1.6e-3 apart after one control step), served by the kernels' predictor_ODE form
-            ptype = "ODE"
-        elif name in ("ODE_v0", "ODE_v0_default"):
-            ptype = "ODE_v0"
-        else:
-            raise NotImplementedError(f"predictor_specification {spec!r}: the predictor seam serves ODE_v0 and ODE; the GRU "
-                                      "predictor runs inside the fused kernel (optimizer_mppi(gru_model=...))")
+        ptype = ode_predictor_type(spec, f"predictor_specification {spec!r}: the predictor seam serves ODE_v0 and ODE; the GRU "
+                                         "predictor runs inside the fused kernel (optimizer_mppi(gru_model=...))")
         self.predictor_config = {"predictor_type": ptype, "model_name": None,
                                  "intermediate_steps": self.predictor_config["intermediate_steps"]}
         self.predictor_type = ptype
