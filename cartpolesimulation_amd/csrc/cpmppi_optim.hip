@@ -196,16 +196,28 @@ __global__ __launch_bounds__(BLOCK) void cem_gmm_sample_kernel(const Params p, u
 
 // One block per env: sort (S, index) ascending with a bitonic network in LDS (ties by index = stable argsort), then
 // mean and population standard deviation of the best_k input sequences per time-step, stdev floored at stdev_min.
+// The order is numpy's: -inf < finite < +inf < NaN, -0.0 == +0.0 (ties by index), padding after everything - so that
+// idx[i] < N for every i < best_k <= N whatever S holds.  A float comparison is no order once a key is NaN (the network
+// would leave an arbitrary permutation, padded indices included), so the keys are order-preserving uint32 images of
+// the costs: -0.0 -> +0.0, every NaN -> 0x7FC00000, then all bits flipped if the sign bit is set, else the
+// sign bit set; the padding is 0xFFFFFFFF, which no image equals (the canonical NaN maps to 0xFFC00000).
+__device__ __forceinline__ uint32_t cem_sort_key(float s) {
+  uint32_t b = __float_as_uint(s);
+  if (b == 0x80000000u) b = 0u;                          // -0.0 -> +0.0 (on the bits: independent of the denormal mode)
+  if ((b & 0x7FFFFFFFu) > 0x7F800000u) b = 0x7FC00000u;  // every NaN -> the canonical one, above +inf's image
+  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+
 __global__ __launch_bounds__(BLOCK) void cem_update_kernel(const Params p, const float* __restrict__ S,
                                                            const float* __restrict__ Q, uint32_t best_k, float stdev_min,
                                                            uint32_t Np, float* __restrict__ mean_out,
                                                            float* __restrict__ stdev_out, uint32_t* __restrict__ elite_out) {
-  extern __shared__ float cem_lds[];                     // keys[Np], idx[Np]
-  float* key = cem_lds;
-  uint32_t* idx = reinterpret_cast<uint32_t*>(cem_lds + Np);
+  extern __shared__ uint32_t cem_lds[];                  // keys[Np], idx[Np]
+  uint32_t* key = cem_lds;
+  uint32_t* idx = cem_lds + Np;
   const uint32_t env = blockIdx.x, tid = threadIdx.x;
   for (uint32_t i = tid; i < Np; i += BLOCK) {
-    key[i] = i < p.N ? S[(size_t)env * p.N + i] : INFINITY;
+    key[i] = i < p.N ? cem_sort_key(S[(size_t)env * p.N + i]) : 0xFFFFFFFFu;
     idx[i] = i;
   }
   __syncthreads();
@@ -215,9 +227,10 @@ __global__ __launch_bounds__(BLOCK) void cem_update_kernel(const Params p, const
         const uint32_t l = i ^ j;
         if (l > i) {
           const bool up = (i & k) == 0;
-          const float ki = key[i], kl = key[l];
+          const uint32_t ki = key[i], kl = key[l];
           const uint32_t ii = idx[i], il = idx[l];
-          const bool gt = (ki > kl) || (ki == kl && ii > il);
+          // (key, index) lexicographically: one 64-bit comparison
+          const bool gt = (((uint64_t)ki << 32) | ii) > (((uint64_t)kl << 32) | il);
           if (gt == up) { key[i] = kl; key[l] = ki; idx[i] = il; idx[l] = ii; }
         }
       }

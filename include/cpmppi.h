@@ -322,7 +322,9 @@ int cpmppi_sgd_step(cpmppi_handle* h, uint32_t E, float* Q, const float* grad, f
 /* CEM (hyper-parameters: Control_Toolkit_ASF/config_optimizers.yml:1-11, section cem-tf).
  * cpmppi_cem_sample: Q[E,N,H] = clip(mean[E,H] + stdev[E,H] * z), z ~ N(0,1) from Philox(seed, offset, env, rollout).
  * cpmppi_cem_update: per env, the best_k sequences by cost (stable ascending order) -> their mean and population
- * standard deviation per time-step, the latter floored at stdev_min; elite_idx_out[E,best_k] (may be NULL). */
+ * standard deviation per time-step, the latter floored at stdev_min; elite_idx_out[E,best_k] (may be NULL).  The order is
+ * numpy's argsort(kind="stable"): -inf < finite < +inf < NaN, -0.0 equal to +0.0, equal costs (all NaNs among them) by
+ * index; every elite index is < N whatever S holds - a NaN cost is taken only once best_k exceeds the number of others. */
 int cpmppi_cem_sample(cpmppi_handle* h, uint32_t E, const float* mean, const float* stdev, uint64_t seed, uint64_t offset,
                       uint32_t env_offset, float* Q_out, void* stream);
 int cpmppi_cem_update(cpmppi_handle* h, uint32_t E, const float* S, const float* Q, uint32_t best_k, float stdev_min,

@@ -627,6 +627,64 @@ def cem_update(S, Q, best_k, stdev_min):
     return elite.mean(0).astype(f32), np.maximum(elite.std(0), stdev_min).astype(f32), idx
 
 
+# The device's top-k (cpmppi_optim.hip, cem_update_kernel) restated: a bitonic network over (key, index) records padded to a power
+# of two, parametrised by the comparator so that a test can show which comparators meet the contract above - the first best_k of a
+# STABLE ascending argsort, i.e. NaN after +inf (numpy's sort order), -0.0 == +0.0, padding after everything - and which do not.
+def topk_key_float(S, Np):
+    """The kernel's keys before the NaN fix: the costs themselves, padded with +inf."""
+    key = np.full(Np, np.inf, f32)
+    key[:len(S)] = S
+    return key
+
+
+def topk_gt_float(ki, ii, kl, il):
+    """(key, index) lexicographic on float keys: no order once a key is NaN (every comparison false)."""
+    return (ki > kl) | ((ki == kl) & (ii > il))
+
+
+def topk_key_ordered(S, Np):
+    """Order-preserving uint32 keys: canonicalise on the bits (-0.0 -> +0.0; every NaN -> 0x7FC00000, above +inf's image), flip all
+    bits of a negative float, set the sign bit of a non-negative one; padding 0xFFFFFFFF (above every image, the canonical NaN's
+    included)."""
+    b = np.ascontiguousarray(S, f32).view(np.uint32).copy()
+    b[b == 0x80000000] = 0
+    b[(b & 0x7FFFFFFF) > 0x7F800000] = 0x7FC00000
+    b = np.where(b & 0x80000000, ~b, b | np.uint32(0x80000000)).astype(np.uint32)
+    key = np.full(Np, 0xFFFFFFFF, np.uint32)
+    key[:len(S)] = b
+    return key
+
+
+def topk_gt_ordered(ki, ii, kl, il):
+    return (ki > kl) | ((ki == kl) & (ii > il))
+
+
+def bitonic_topk(S, best_k, make_key=topk_key_ordered, gt=topk_gt_ordered):
+    """S[N] -> the first best_k indices the kernel's sorting network leaves: same padding to Np = 2^ceil(log2 N), same (k, j) passes,
+    same direction rule `up = (i & k) == 0`, exchange when gt(i, l) == up.  May return indices >= N if the comparator lets padding in."""
+    N = len(S)
+    Np = 1
+    while Np < N:
+        Np <<= 1
+    key, idx = make_key(S, Np), np.arange(Np, dtype=np.uint32)
+    i = np.arange(Np)
+    k = 2
+    while k <= Np:
+        j = k >> 1
+        while j > 0:
+            l = i ^ j
+            lo = i[l > i]
+            hi = lo ^ j
+            with np.errstate(invalid="ignore"):
+                swap = gt(key[lo], idx[lo], key[hi], idx[hi]) == ((lo & k) == 0)
+            a, b = lo[swap], hi[swap]
+            key[a], key[b] = key[b].copy(), key[a].copy()
+            idx[a], idx[b] = idx[b].copy(), idx[a].copy()
+            j >>= 1
+        k <<= 1
+    return idx[:best_k].astype(np.int64)
+
+
 # --------------------------------------------------------------------------------------------------------------------
 # SURVEY §8f N4 — cost plugin quadratic_boundary_grad
 # (Control_Toolkit_ASF/Cost_Functions/CartPole/quadratic_boundary_grad.py:64-232; weights config_cost_function.yml:12-36)

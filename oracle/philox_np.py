@@ -74,3 +74,62 @@ def knots(seed, offset, env_offset, E, N, P, sigma):
     q = np.arange(nq, dtype=np.uint64)[None, None, :]
     z = standard_normal_quads(seed, offset, e, n, q).reshape(E, N, nq * 4)[:, :, :P]
     return (f32(sigma) * z.astype(f32)).astype(f32)
+
+
+# --------------------------------------------------------------------------------------------------------------------
+# The CEM samplers' stream (cpmppi_device.hpp, philox_normal_pair; cpmppi_optim.hip, cem_sample_kernel / cem_gmm_sample_kernel):
+# counter = (rollout, GLOBAL env index, step pair, low word of the offset), key = (seed_lo, seed_hi ^ high word of the offset) - NO
+# XOR constant on the low key word, and only words 0 and 1 of the block are used: time-steps 2 pair and 2 pair + 1 are
+# r (cos 2 pi u2, sin 2 pi u2), r = sqrt(-2 ln u1), with the 24-bit uniforms of _uniforms.
+GMM_COMPONENT_PAIR = 0x80000000                           # counter word 2 of the block that picks a rollout's mixture component
+
+
+def pair_words(seed, offset, env, rollout, pair):
+    """The Philox block behind time-steps 2 pair, 2 pair + 1 of (global env, rollout) at `offset` (philox_normal_pair)."""
+    seed, offset = int(seed), int(offset)
+    env, rollout, pair = np.broadcast_arrays(np.asarray(env, np.uint64), np.asarray(rollout, np.uint64), np.asarray(pair, np.uint64))
+    ctr = np.stack([rollout, env, pair, np.full(env.shape, offset & 0xFFFFFFFF, np.uint64)], axis=-1)
+    key = np.array([seed & 0xFFFFFFFF, ((seed >> 32) ^ (offset >> 32)) & 0xFFFFFFFF], np.uint64)
+    return philox4x32_10(ctr, key)
+
+
+def standard_normal_pairs(seed, offset, env, rollout, pair):
+    """-> [..., 2] float64: the two standard normals of a block (words 0 and 1), before any rounding."""
+    u1, u2, _, _ = _uniforms(pair_words(seed, offset, env, rollout, pair))
+    r = np.sqrt(-2.0 * np.log(u1))
+    return np.stack([r * np.cos(2 * np.pi * u2), r * np.sin(2 * np.pi * u2)], axis=-1)
+
+
+def _cem_normals(seed, offset, env_offset, E, N, H):
+    e = (np.arange(E, dtype=np.uint64) + np.uint64(env_offset))[:, None, None]
+    n = np.arange(N, dtype=np.uint64)[None, :, None]
+    j = np.arange((H + 1) // 2, dtype=np.uint64)[None, None, :]
+    return standard_normal_pairs(seed, offset, e, n, j).reshape(E, N, -1)[:, :, :H].astype(f32)      # (odd H: sin of the last pair unused)
+
+
+def cem_samples(mean, stdev, seed, offset, env_offset, N, lo=-1.0, hi=1.0):
+    """What cpmppi_cem_sample writes, in float64: [E, N, H] = clip(mean[e, k] + stdev[e, k] * float32(z), lo, hi)."""
+    mean, stdev = np.asarray(mean, np.float64), np.asarray(stdev, np.float64)
+    E, H = mean.shape
+    z = _cem_normals(seed, offset, env_offset, E, N, H).astype(np.float64)
+    return np.clip(mean[:, None, :] + stdev[:, None, :] * z, float(f32(lo)), float(f32(hi)))
+
+
+def gmm_components(seed, offset, env_offset, E, N, K):
+    """The mixture component of every rollout as cpmppi_cem_gmm_sample picks it: [E, N] = (word 0 * K) >> 32 of the block with counter
+    word 2 = GMM_COMPONENT_PAIR (never a real pair index).  Integer-exact."""
+    e = (np.arange(E, dtype=np.uint64) + np.uint64(env_offset))[:, None]
+    n = np.arange(N, dtype=np.uint64)[None, :]
+    w0 = pair_words(seed, offset, e, n, GMM_COMPONENT_PAIR)[..., 0].astype(np.uint64)
+    return ((w0 * np.uint64(K)) >> np.uint64(32)).astype(np.int64)
+
+
+def cem_gmm_samples(centres, stdev, seed, offset, env_offset, N, lo=-1.0, hi=1.0):
+    """What cpmppi_cem_gmm_sample writes, in float64: (Q [E, N, H], components [E, N]) - the centre of the rollout's component plus the
+    plain CEM sampler's noise for the same (seed, offset)."""
+    centres, stdev = np.asarray(centres, np.float64), np.asarray(stdev, np.float64)
+    E, K, H = centres.shape
+    comp = gmm_components(seed, offset, env_offset, E, N, K)
+    z = _cem_normals(seed, offset, env_offset, E, N, H).astype(np.float64)
+    Q = centres[np.arange(E)[:, None], comp] + stdev[:, None, :] * z
+    return np.clip(Q, float(f32(lo)), float(f32(hi))), comp

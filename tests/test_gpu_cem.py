@@ -1,4 +1,5 @@
-"""GPU: CEM over the same rollout + cost kernel — sampler, cost-only launch, top-k refit, optimizer."""
+"""GPU: CEM over the same rollout + cost kernel — sampler (statistics, and sample by sample against Philox),
+cost-only launch, top-k refit (and its edges: best_k = 1 / N, +-inf, +-0.0, ties, NaN), optimizer."""
 import numpy as np
 import pytest
 
@@ -179,3 +180,118 @@ def test_cem_gmm_sampler_and_optimizer():
         s = O.ode_v0_step(s[None], np.asarray(u, f32))[0]
     assert abs(s[O.ANGLE_IDX]) < 0.1 and abs(s[O.POSITION_IDX]) < 0.15
     assert ctrl.optimizer.centres.shape == (1, 40, 35) and torch.isfinite(ctrl.optimizer.stdev).all()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The samplers word for word against Philox (oracle/philox_np.py, pinned to Random123's vectors by tests/test_oracle_philox.py), and
+# the top-k at its edges.
+from oracle import philox_np as PH  # noqa: E402
+from test_gpu_philox import Z_ATOL  # noqa: E402  (the measured bound of the same v_log / v_sqrt / v_sin / v_cos chain)
+
+SEED, OFFSET, ENV_OFFSET = 2 ** 40 + 5, 2 ** 33 + 11, 123456        # a seed with a high word, an offset beyond 2^32, a large global env index
+LO, HI = -0.5, 0.8
+
+
+def report(capsys, text):
+    with capsys.disabled():
+        print("\n[optim] " + text)
+
+
+def sampler_bound(stdev):
+    """|Q_dev - oracle| per element: the normal's hardware error scaled by stdev[e, k], plus the rounding of the float32 fma result (half
+    an ulp below 4 = 2^-23; beyond that both sides sit on a limit).  The clamp is 1-Lipschitz: clipped elements need no exemption."""
+    return np.asarray(stdev, np.float64)[:, None, :] * Z_ATOL + 2.0 ** -23
+
+
+@pytest.mark.parametrize("E,N,H", [(3, 300, 35), (2, 64, 1)])     # odd H over two blocks (900 rows: four); the H = 1 tail
+def test_cem_sample_is_philox(E, N, H, capsys):
+    eng = make(E, N, H, action_low=LO, action_high=HI)
+    rng = np.random.Generator(np.random.SFC64(14))
+    mean = rng.uniform(-0.1, 0.4, (E, H)).astype(f32)
+    stdev = rng.uniform(0.15, 0.5, (E, H)).astype(f32)
+    if H == 1:                                                   # (128 samples: one env towards each limit)
+        mean, stdev = np.asarray([[0.45], [-0.15]], f32), np.asarray([[0.3], [0.3]], f32)
+    Q = eng.cem_sample(mean, stdev, SEED, OFFSET, ENV_OFFSET).cpu().numpy()
+    ref = PH.cem_samples(mean, stdev, SEED, OFFSET, ENV_OFFSET, N, LO, HI)
+    clipped = ((ref == ref.min()) | (ref == ref.max())).mean()
+    assert ref.min() == LO and ref.max() == float(f32(HI)) and 0.05 < clipped < 0.2        # about a tenth of the samples sit on a limit
+    err = np.abs(Q.astype(np.float64) - ref)
+    report(capsys, f"cem_sample {E}x{N}x{H}: worst |Q - philox| / bound {np.max(err / sampler_bound(stdev)):.3f}, worst abs {err.max():.2e}, "
+                   f"clipped share {clipped:.3f}")
+    assert np.all(err <= sampler_bound(stdev)), (err.max(), np.unravel_index(err.argmax(), err.shape))
+    assert Q.min() == f32(LO) and Q.max() == f32(HI)
+    # the global env index keys the stream: env 1 at env_offset a == env 0 at env_offset a + 1, bit for bit; other words, other samples
+    shifted = eng.cem_sample(mean[1:2].copy(), stdev[1:2].copy(), SEED, OFFSET, ENV_OFFSET + 1).cpu().numpy()
+    assert np.array_equal(shifted[0], Q[1])
+    assert not np.array_equal(eng.cem_sample(mean, stdev, SEED, OFFSET, 0).cpu().numpy(), Q)
+    assert not np.array_equal(eng.cem_sample(mean, stdev, SEED, OFFSET - 2 ** 33, ENV_OFFSET).cpu().numpy(), Q)
+    assert not np.array_equal(eng.cem_sample(mean, stdev, SEED - 2 ** 40, OFFSET, ENV_OFFSET).cpu().numpy(), Q)
+    eng.close()
+
+
+@pytest.mark.parametrize("K", [1, 3, 8])
+def test_cem_gmm_sample_is_philox(K, capsys):
+    E, N, H = 2, 300, 5
+    eng = make(E, N, H, action_low=LO, action_high=HI)
+    rng = np.random.Generator(np.random.SFC64(15 + K))
+    centres = rng.uniform(-0.3, 0.6, (E, K, H)).astype(f32)
+    stdev = rng.uniform(0.1, 0.4, (E, H)).astype(f32)
+    Qt, ct = eng.cem_gmm_sample(centres, stdev, SEED, OFFSET, ENV_OFFSET, return_components=True)
+    Q, comp = Qt.cpu().numpy(), ct.cpu().numpy()
+    ref, comp_ref = PH.cem_gmm_samples(centres, stdev, SEED, OFFSET, ENV_OFFSET, N, LO, HI)
+    assert np.array_equal(comp, comp_ref)                                            # every rollout's component, not only their histogram
+    assert set(np.unique(comp)) == set(range(K))
+    err = np.abs(Q.astype(np.float64) - ref)
+    report(capsys, f"cem_gmm_sample K={K}: components equal, worst |Q - philox| / bound {np.max(err / sampler_bound(stdev)):.3f}")
+    assert np.all(err <= sampler_bound(stdev)), (err.max(), np.unravel_index(err.argmax(), err.shape))
+    assert (ref == LO).any() and (ref == float(f32(HI))).any()
+    Q1, c1 = eng.cem_gmm_sample(centres[1:2].copy(), stdev[1:2].copy(), SEED, OFFSET, ENV_OFFSET + 1, return_components=True)
+    assert np.array_equal(c1.cpu().numpy()[0], comp[1]) and np.array_equal(Q1.cpu().numpy()[0], Q[1])
+    Q0, c0 = eng.cem_gmm_sample(centres, stdev, SEED, OFFSET, 0, return_components=True)
+    assert not np.array_equal(Q0.cpu().numpy(), Q) and (K == 1 or not np.array_equal(c0.cpu().numpy(), comp))
+    eng.close()
+
+
+def edge_costs(N, kind, seed):
+    """Three cost vectors [3, N] with the values a sort can get wrong: +-inf, +-0.0, ties - and, kind "nan", NaNs among them (one in env
+    0; several in env 1; in env 2 one with the sign bit set and a payload)."""
+    rng = np.random.Generator(np.random.SFC64(seed))
+    S = np.stack([(1e3 * rng.standard_normal(N)).astype(f32), rng.integers(-1, 3, N).astype(f32),
+                  (1e3 * rng.standard_normal(N)).astype(f32)])
+    specials = [[np.inf, -np.inf, 0.0, -0.0, np.inf, -0.0], [-0.0, 0.0, -0.0, np.inf, -np.inf, 0.0], [np.inf, np.inf, -np.inf, -np.inf, 0.0, -0.0]]
+    nans = [[np.nan], [np.nan, np.nan, np.nan], [np.nan, np.nan]]
+    for e in range(3):
+        vals = (nans[e] if kind == "nan" else []) + (specials[e] if N > 1 else [])
+        where = rng.choice(N, min(len(vals), N), replace=False)
+        S[e, where] = np.asarray(vals, f32)[:len(where)]
+    if kind == "nan":
+        S[2].view(np.uint32)[np.flatnonzero(np.isnan(S[2]))[0]] = 0xFFC12345
+        assert np.isnan(S).any(axis=1).all()
+    return S
+
+
+@pytest.mark.parametrize("kind", ["inf-zero-ties", "nan"])
+@pytest.mark.parametrize("N,H,best_ks", [(1, 3, (1,)), (37, 5, (1, 37)), (300, 4, (1, 40, 300)), (200, 300, (40, 200))])
+def test_cem_update_edges(N, H, best_ks, kind):
+    """best_k = 1 and = N; N = 1, N = 37 (padded to 64 < one block), N = 300 (padded to 512: two passes per lane), H = 300 (more time-steps
+    than lanes); costs with +-inf, +-0.0 and ties; and with NaN, which sorts last (oracle_np.cem_update = stable argsort; the network:
+    tests/test_oracle_topk.py): one NaN with best_k = 40, NaNs with best_k = N - every elite index < N, Q allocated exactly [E, N, H]."""
+    E = 3
+    eng = make(E, N, H)
+    rng = np.random.Generator(np.random.SFC64(16))
+    S = edge_costs(N, kind, 40 + N)
+    Q = rng.uniform(-1, 1, (E, N, H)).astype(f32)
+    Sd, Qd = eng.tensor(S), eng.tensor(Q)
+    assert np.array_equal(Sd.cpu().numpy().view(np.uint32), S.view(np.uint32))       # the costs reach the device bit for bit
+    for best_k in best_ks:
+        m, sd, el = eng.cem_update(Sd, Qd, best_k, 0.01, return_elites=True)
+        el = el.cpu().numpy()
+        assert el.min() >= 0 and el.max() < N
+        for e in range(E):
+            mr, sr, idx = O.cem_update(S[e], Q[e], best_k, 0.01)
+            assert np.array_equal(el[e], idx), (best_k, e)
+            np.testing.assert_allclose(m.cpu().numpy()[e], mr, atol=1e-6)
+            np.testing.assert_allclose(sd.cpu().numpy()[e], sr, atol=2e-6)
+        if kind == "nan" and best_k < N - 3:
+            assert not np.isnan(S[np.arange(E)[:, None], el]).any()                  # enough other costs: no NaN among the elite
+    eng.close()

@@ -1,5 +1,6 @@
 """GPU: gradient of rollout + plugin cost w.r.t. the inputs (cpmppi_rollout_cost_grad) against torch.autograd of the
-float64 oracle, the Adam step against numpy, and the gradient optimizers on top."""
+float64 oracle - at the gradient optimizers' own sizes and across blocks, with its refusals -, the Adam and SGD steps
+against numpy, and the gradient optimizers on top."""
 import numpy as np
 import pytest
 
@@ -171,3 +172,266 @@ def test_gradient_with_more_substeps_than_the_default_lds_budget():
     np.testing.assert_allclose(S.cpu().numpy()[0], J, rtol=5e-4)
     scale = np.abs(g).max(axis=1, keepdims=True) + 1e-6
     assert (np.abs(G.cpu().numpy()[0] - g) / scale).max() < 2e-3
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# Beyond one block.  600 rows in three blocks of 256 lanes: block 0 holds lanes of envs 0, 1 and 2 (env = g / N inside a block),
+# the last block has 88 live lanes (g >= B), the handle is built for 6 envs and called with 5 (check-point stride 5 N inside a 6 N
+# allocation), the action limits are not +-1, and L, previous_input, target_position and target_equilibrium differ per env.
+XB = dict(E_handle=6, E=5, N=120, H=12, lo=-0.5, hi=0.8)
+XB_COSTS = {"quadratic_boundary_grad_minimal": O.COST_QBGM, "quadratic_boundary_grad": 3}
+_xb_cache = {}
+
+
+def xb_inputs():
+    """Inputs of the cross-block cases (the same for every case): env 0 starts at the track edge (envs(edge=True): bounces under
+    predictor_ODE_v0, runs past the edge under predictor_ODE), the others near the middle of the track."""
+    E, N, H = XB["E"], XB["N"], XB["H"]
+    s0, tp, Lv, rng = envs(E, 33)
+    s0[0] = envs(E, 33, edge=True)[0][0]
+    Q = (0.3 * rng.standard_normal((E, N, H))).astype(f32)
+    Q[:, :3] *= 4.0                                              # rows with controls beyond both limits
+    Q[:, 3, ::2], Q[:, 4, 1::2] = -0.75, 0.9                     # and rows that sit beyond one limit at every other step
+    prev = np.asarray([0.2, -0.1, 0.0, 0.6, -0.4], dtype=f32)
+    # (target "down" for the two envs whose pole stays away from upright: under quadratic_boundary_grad with admissible_angle 0 the stage
+    # cost of te = -1 jumps by ~3000 where cos(angle) == 1, which float32 reaches for |angle| < 2.4e-4 and float64 never does)
+    te = np.asarray([1.0, 1.0, -1.0, -1.0, 1.0], dtype=f32)
+    return s0.astype(f32), Q, tp, te, Lv, prev
+
+
+def xb_reference(predictor_type, name):
+    """Float64 autograd of the oracle and the oracle's flags, once per case: (J [E,N], g [E,N,H], flagged [E,N], bounced)."""
+    key = (predictor_type, name)
+    if key not in _xb_cache:
+        s0, Q, tp, te, Lv, prev = xb_inputs()
+        cost_id, lo, hi = XB_COSTS[name], XB["lo"], XB["hi"]
+        J, g, fl, bounced = [], [], [], 0
+        for e in range(XB["E"]):
+            Je, ge = OT.cost_and_grad(cost_id, s0[e], Q[e], tp[e], te[e], L=Lv[e], previous_input=prev[e], qbg_weights=QBG_W,
+                                      clip=(lo, hi), integrator=predictor_type)
+            traj = O.predict_core(s0[e], np.clip(Q[e], f32(lo), f32(hi)), L=Lv[e], integrator=predictor_type)
+            # (envs(edge=True)'s check, plus what it misses at H = 12: the cart bounces BETWEEN two control-step samples and no sample
+            # reaches 0.197.  A bounce reverses the cart's velocity: >= 0.68 m/s within one control step here, where the ODE alone moves
+            # it by <= 0.16 m/s under these limits)
+            x, v = traj[:, :, O.POSITION_IDX], traj[:, :, O.POSITIOND_IDX]
+            reversed_at_edge = ((v[:, :-1] * v[:, 1:] < 0) & (np.abs(np.diff(v, axis=1)) > 0.4) & (np.abs(x[:, :-1]) > 0.19)).any(axis=1)
+            bounced += int(((np.abs(x).max(axis=1) >= 0.197) | reversed_at_edge).sum())
+            f = (PU.flag_discontinuities(traj) if predictor_type == "ODE_v0" else np.zeros(XB["N"], bool)) \
+                | PU.flag_indicators(traj, "qbgm" if cost_id == O.COST_QBGM else "qbg", tp[e])
+            f |= ((np.abs(Q[e] - f32(lo)) < 1e-3) | (np.abs(Q[e] - f32(hi)) < 1e-3)).any(axis=1)
+            if te[e] < 0:                                        # clear of the cos(angle) == cos(admissible_angle) threshold (see xb_inputs)
+                assert np.abs(traj[:, :, O.ANGLE_IDX]).min() > 0.1
+            J.append(Je); g.append(ge); fl.append(f)
+        for a in (J, g, fl):
+            for x in a:
+                x.setflags(write=False)
+        _xb_cache[key] = (np.stack(J), np.stack(g), np.stack(fl), bounced)
+    return _xb_cache[key]
+
+
+def report(capsys, text):
+    with capsys.disabled():
+        print("\n[optim] " + text)
+
+
+def test_cross_block_case_is_mostly_clear_of_branches():
+    """A condition on the inputs, from the oracle alone: at most a quarter of the 600 rollouts are flagged (env 0, at the edge, is -
+    all of it under predictor_ODE_v0), so the 5e-4 bound applies to the rest; and env 0 does bounce / leave the track."""
+    for predictor_type in ("ODE_v0", "ODE"):
+        for name in XB_COSTS:
+            _, g, flagged, bounced = xb_reference(predictor_type, name)
+            assert flagged.mean() <= 0.25 and bounced > 0
+            assert (np.abs(g).max(axis=2) > 0).all()                                # every rollout has a gradient scale of its own
+
+
+@pytest.mark.parametrize("predictor_type", ["ODE_v0", "ODE"])
+@pytest.mark.parametrize("name", list(XB_COSTS))
+def test_gradient_across_blocks(name, predictor_type, capsys):
+    """The adjoint kernel on three blocks (see XB) against float64 autograd, under the rules of test_gradient_vs_autograd: rollouts clear
+    of every branch within 5e-4 of their gradient scale, flagged ones within 2e-3 (5 % of them may miss), costs to rtol 5e-4, gradient
+    exactly 0 beyond either limit.  quadratic_boundary_grad couples step k to k + 1 through u_before (the kernel's `carry`).  Then
+    indexing alone: every env by itself through the same handle gives the same bits, and the defaults are L_default and zeros."""
+    E, N, H, lo, hi = XB["E"], XB["N"], XB["H"], XB["lo"], XB["hi"]
+    eng = make(XB["E_handle"], N, H, cost_function_specification=name, cost_weights=QBG_W if XB_COSTS[name] == 3 else None,
+               predictor_type=predictor_type, action_low=lo, action_high=hi)
+    s0, Q, tp, te, Lv, prev = xb_inputs()
+    J, g, flagged, bounced = xb_reference(predictor_type, name)
+    assert flagged.mean() <= 0.25
+    St, Gt = eng.rollout_cost_grad(s0, Q, tp, te, L=Lv, previous_input=prev)
+    S, G = St.cpu().numpy(), Gt.cpu().numpy()
+    beyond = (Q < f32(lo)) | (Q > f32(hi))
+    assert beyond.any(axis=2).sum() >= 5 * E and (Q < f32(lo)).any() and (Q > f32(hi)).any()
+    assert np.all(G[beyond] == 0.0) and np.all(g[beyond] == 0.0)
+    scale = np.abs(g).max(axis=2) + 1e-6
+    err = (np.abs(G - g).max(axis=2)) / scale
+    cost_err = np.abs(S - J) / np.abs(J)
+    n_fl, n_fl_off = int(flagged.sum()), int(((err >= 2e-3) & flagged).sum())
+    report(capsys, f"gradient across blocks {name} / {predictor_type}: worst clear {err[~flagged].max():.2e} (bound 5e-4), worst flagged "
+                   f"{err[flagged].max():.2e} (bound 2e-3, {n_fl_off} of {n_fl} outside, cap 5 %), flagged share {flagged.mean():.3f} "
+                   f"(bound 0.25), cost rel. {cost_err.max():.2e} (bound 5e-4), bounced {bounced}")
+    np.testing.assert_allclose(S, J, rtol=5e-4)
+    clear_off = int(((err >= 5e-4) & ~flagged).sum())
+    assert clear_off == 0, (f"{clear_off} of {int((~flagged).sum())} rollouts clear of every branch differ by more than 5e-4 "
+                            f"(worst {err[~flagged].max():.2e})")
+    assert n_fl_off <= int(np.ceil(0.05 * n_fl)), f"{n_fl_off} of {n_fl} flagged rollouts outside 2e-3"
+    assert bounced > 0
+    # isolation: lane arithmetic is per rollout, so an env alone through the same handle gives the same bits - only indexing differs
+    for e in range(E):
+        S1, G1 = eng.rollout_cost_grad(s0[e:e + 1], Q[e:e + 1], tp[e:e + 1], te[e:e + 1], L=Lv[e:e + 1], previous_input=prev[e:e + 1])
+        assert np.array_equal(S1.cpu().numpy()[0], S[e]) and np.array_equal(G1.cpu().numpy()[0], G[e]), f"env {e} alone"
+    # (the 5-env call did not depend on what the single-env ones left in the check-points)
+    S5, G5 = eng.rollout_cost_grad(s0, Q, tp, te, L=Lv, previous_input=prev)
+    assert np.array_equal(S5.cpu().numpy(), S) and np.array_equal(G5.cpu().numpy(), G)
+    # defaults: no L and no previous input = the handle's L and zeros
+    Sa, Ga = eng.rollout_cost_grad(s0, Q, tp, te)
+    Sb, Gb = eng.rollout_cost_grad(s0, Q, tp, te, L=np.full(E, eng.phys.L, f32), previous_input=np.zeros(E, f32))
+    assert np.array_equal(Sa.cpu().numpy(), Sb.cpu().numpy()) and np.array_equal(Ga.cpu().numpy(), Gb.cpu().numpy())
+    assert not np.array_equal(Sa.cpu().numpy(), S)
+    eng.close()
+
+
+@pytest.mark.parametrize("what,kw", [
+    ("legacy cost", dict(cost_function_specification="legacy_mppi_cartpole")),
+    ("quadratic_boundary", dict(cost_function_specification="quadratic_boundary")),
+    ("PRECISE math", dict(math_mode="precise")),
+    ("S > 25", dict(intermediate_steps=26))])
+def test_gradient_refusals_leave_the_handle_usable(what, kw):
+    """cpmppi_rollout_cost_grad has no adjoint for these four: each is refused with CpmppiError, before anything is launched, and the
+    handle goes on serving what it does support."""
+    from cartpolesimulation_amd._lib import CpmppiError
+    E, N, H = 2, 24, 5
+    eng = make(E, N, H, **kw)
+    s0, tp, Lv, rng = envs(E, 9)
+    te = np.ones(E, f32)
+    Q = (0.4 * rng.standard_normal((E, N, H))).astype(f32)
+    legacy = what == "legacy cost"
+    before = None if legacy else eng.rollout_cost(s0, Q, tp, te, L=Lv).cpu().numpy()
+    for _ in range(2):
+        with pytest.raises(CpmppiError, match="cpmppi_rollout_cost_grad"):
+            eng.rollout_cost_grad(s0, Q, tp, te, L=Lv)
+    if legacy:
+        with pytest.raises(CpmppiError):
+            eng.rollout_cost(s0, Q, tp, te, L=Lv)                                   # (plugin costs only, as well)
+    else:
+        after = eng.rollout_cost(s0, Q, tp, te, L=Lv).cpu().numpy()
+        assert np.isfinite(after).all() and np.array_equal(after, before)
+    gr = rng.standard_normal((E, N, H)).astype(f32)
+    Qd = eng.sgd_step(eng.tensor(Q.copy()), eng.tensor(gr), 0.1, 0.0).cpu().numpy()
+    np.testing.assert_allclose(Qd, np.clip(Q.astype(np.float64) - 0.1 * gr.astype(np.float64), -1, 1), atol=2e-6)
+    if what == "S > 25":                                                            # the largest S with an adjoint still launches and matches
+        ok = make(1, 8, 3, intermediate_steps=25)
+        S, G = ok.rollout_cost_grad(s0[:1], Q[:1, :8, :3].copy(), tp[:1], te[:1], L=Lv[:1])
+        J, g = OT.cost_and_grad(O.COST_QBGM, s0[0], Q[0, :8, :3], tp[0], 1.0, L=Lv[0], S=25)
+        np.testing.assert_allclose(S.cpu().numpy()[0], J, rtol=5e-4)
+        assert (np.abs(G.cpu().numpy()[0] - g) / (np.abs(g).max(axis=1, keepdims=True) + 1e-6)).max() < 2e-3
+        ok.close()
+    eng.close()
+
+
+# ---------------------------------------------------------------------------------------------------------------------------------
+# The update kernels on 600 rows (E, N, H = 3, 200, 7: three blocks, the last with 88 live lanes), asymmetric limits.
+def step_engine():
+    return make(3, 200, 7, action_low=-0.5, action_high=0.8)
+
+
+def step_gradients(rng, it, scales=(0.1, 1.0, 30.0)):
+    """[3,200,7] float32: per-row scales (the default: row norms below and above the clip norm 5), rows with an all-zero gradient."""
+    g = (rng.standard_normal((3, 200, 7)) * rng.choice(list(scales), (3, 200, 1))).astype(f32)
+    g[:, 7 + it] = 0.0                                           # norm exactly 0 (another row each iteration)
+    g[:, 150] = 0.0                                              # and one row with no gradient at any iteration
+    return g
+
+
+def clip_by_norm(g, c):
+    nrm = np.sqrt((g.astype(np.float64) ** 2).sum(-1, keepdims=True))
+    return g.astype(np.float64) * (np.minimum(1.0, c / np.maximum(nrm, 1e-300)) if c > 0 else 1.0), nrm
+
+
+@pytest.mark.parametrize("clipn,lr,big", [(5.0, 0.05, False), (0.0, 2e-4, True)])
+def test_sgd_step_vs_numpy(clipn, lr, big, capsys):
+    """cem-naive-grad's update, clip(Q - lr g min(1, c / |g|), lo, hi), against float64 numpy over three iterations: rows with |g| below
+    the clip norm, above it and exactly 0; clipping off (gradmax_clip = 0) with large gradients; |lr g| <= 1 throughout."""
+    E, N, H, lo, hi = 3, 200, 7, f32(-0.5), f32(0.8)
+    eng = step_engine()
+    rng = np.random.Generator(np.random.SFC64(31))
+    Q = rng.uniform(-0.45, 0.75, (E, N, H)).astype(f32)
+    Qd, worst = eng.tensor(Q.copy()), 0.0
+    scales = (40.0, 200.0, 800.0) if big else (0.1, 1.0, 30.0)
+    Q = Q.astype(np.float64)
+    for it in range(3):
+        g = step_gradients(rng, it, scales)
+        gc, nrm = clip_by_norm(g, clipn)
+        assert np.abs(lr * gc).max() <= 1.0 and (nrm == 0).sum() >= 2 * E
+        if clipn > 0:
+            assert (nrm[nrm > 0] < clipn).any() and (nrm > clipn).any()
+        else:
+            assert nrm[nrm > 0].min() > 5.0
+        eng.sgd_step(Qd, eng.tensor(g), lr, clipn)
+        Qn = np.clip(Q - lr * gc, lo, hi)
+        zero = (nrm == 0)[..., 0]
+        assert np.array_equal(Qd.cpu().numpy()[zero], Q[zero].astype(f32))           # no gradient: the row stays as it is
+        assert ((Qn == lo).any() and (Qn == hi).any()) or not big
+        worst = max(worst, np.abs(Qd.cpu().numpy() - Qn).max())
+        np.testing.assert_allclose(Qd.cpu().numpy(), Qn, atol=2e-6)
+        Q = Qd.cpu().numpy().astype(np.float64)                                      # (the next iteration starts from the device's float32)
+    report(capsys, f"sgd_step gradmax_clip {clipn}: worst |Q - numpy| {worst:.2e} (bound 2e-6)")
+    # E = 2 on the 3-env tensor: rows >= E N are not touched
+    keep = Qd.cpu().numpy().copy()
+    g = step_gradients(rng, 0, scales)
+    eng.sgd_step(Qd[:2], eng.tensor(g)[:2], lr, clipn)
+    out = Qd.cpu().numpy()
+    assert np.array_equal(out[2], keep[2]) and not np.array_equal(out[:2], keep[:2])
+    np.testing.assert_allclose(out[:2], np.clip(keep[:2].astype(np.float64) - lr * clip_by_norm(g[:2], clipn)[0], lo, hi), atol=2e-6)
+    eng.close()
+
+
+@pytest.mark.parametrize("clipn", [5.0, 0.0])
+def test_adam_step_across_blocks_vs_numpy(clipn, capsys):
+    """600 rows; m AND v compared; rows with an all-zero gradient (norm 0: no division by it) keep m = v = 0 and Q unchanged at
+    iteration 1 and stay finite; gradmax_clip = 0 switches the norm clipping off (row norms above 5 go through whole).  Gradient elements
+    stay O(1) in both cases, as in test_adam_step_vs_numpy: m sums terms of both signs, a float32 sum that cancels is off by an ulp of its
+    TERMS, and atol = 1e-7 is an ulp of terms below 1 (measured with |g| ~ 1e3 and clipping off: 2.6e-6 on m ~ 0.02 from terms ~ 100)."""
+    E, N, H, lo, hi = 3, 200, 7, f32(-0.5), f32(0.8)
+    eng = step_engine()
+    rng = np.random.Generator(np.random.SFC64(32))
+    Q0 = rng.uniform(-0.45, 0.75, (E, N, H)).astype(f32)
+    Qd, md, vd = eng.tensor(Q0.copy()), eng.zeros(E, N, H), eng.zeros(E, N, H)
+    Q, m, v = Q0.astype(np.float64), np.zeros((E, N, H)), np.zeros((E, N, H))
+    lr, b1, b2, eps = 0.05, f32(0.9), f32(0.999), f32(1e-8)
+    worst = dict(Q=0.0, m=0.0, v=0.0)
+    scales = (0.1, 1.0, 30.0) if clipn > 0 else (0.1, 0.5, 1.5)
+    for it in range(1, 4):
+        g = step_gradients(rng, it, scales)
+        gc, nrm = clip_by_norm(g, clipn)
+        assert (nrm > 5.0).any() and (nrm[nrm > 0] < 5.0).any() and np.abs((1 - float(b1)) * gc).max() < 1.0
+        eng.adam_step(Qd, eng.tensor(g), md, vd, it, lr, float(b1), float(b2), float(eps), clipn)
+        m = float(b1) * m + (1 - float(b1)) * gc
+        v = float(b2) * v + (1 - float(b2)) * gc * gc
+        lr_t = lr * np.sqrt(1 - float(b2) ** it) / (1 - float(b1) ** it)
+        Q = np.clip(Q - lr_t * m / (np.sqrt(v) + float(eps)), lo, hi)
+        Qh, mh, vh = Qd.cpu().numpy(), md.cpu().numpy(), vd.cpu().numpy()
+        assert np.isfinite(Qh).all() and np.isfinite(mh).all() and np.isfinite(vh).all()
+        if it == 1:
+            zero = (nrm == 0)[..., 0]
+            assert zero.sum() >= 2 * E
+            assert np.array_equal(Qh[zero], Q0[zero]) and np.all(mh[zero] == 0.0) and np.all(vh[zero] == 0.0)
+        worst["Q"] = max(worst["Q"], np.abs(Qh - Q).max())
+        np.testing.assert_allclose(Qh, Q, atol=2e-6)
+    assert np.array_equal(Qh[:, 150], Q0[:, 150]) and np.all(mh[:, 150] == 0.0) and np.all(vh[:, 150] == 0.0)   # never had a gradient
+    worst["m"] = (np.abs(mh - m) / np.maximum(np.abs(m), 1e-30))[np.abs(m) > 1e-2].max()
+    worst["v"] = (np.abs(vh - v) / np.maximum(np.abs(v), 1e-30))[np.abs(v) > 1e-2].max()
+    report(capsys, f"adam_step gradmax_clip {clipn}: worst |Q - numpy| {worst['Q']:.2e} (bound 2e-6), rel. m {worst['m']:.2e}, "
+                   f"rel. v {worst['v']:.2e} (bound 1e-5 + 1e-7 abs)")
+    np.testing.assert_allclose(mh, m, rtol=1e-5, atol=1e-7)
+    np.testing.assert_allclose(vh, v, rtol=1e-5, atol=1e-7)
+    # E = 2 on the 3-env tensors: env 2 of Q, m and v is not touched
+    g = step_gradients(rng, 0, scales)
+    gd = eng.tensor(g)
+    eng.adam_step(Qd[:2], gd[:2], md[:2], vd[:2], 4, lr, float(b1), float(b2), float(eps), clipn)
+    for dev, was in ((Qd, Qh), (md, mh), (vd, vh)):
+        now = dev.cpu().numpy()
+        assert np.array_equal(now[2], was[2]) and not np.array_equal(now[:2], was[:2])
+    gc = clip_by_norm(g[:2], clipn)[0]
+    np.testing.assert_allclose(md.cpu().numpy()[:2], float(b1) * mh[:2].astype(np.float64) + (1 - float(b1)) * gc, rtol=1e-5, atol=1e-7)
+    np.testing.assert_allclose(vd.cpu().numpy()[:2], float(b2) * vh[:2].astype(np.float64) + (1 - float(b2)) * gc * gc, rtol=1e-5, atol=1e-7)
+    eng.close()
