@@ -26,7 +26,7 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_abi_version", "cpmppi_stream_create", "cpmppi_stream_destroy", "cpmppi_comm_get_info",
            "cpmppi_groups_create", "cpmppi_groups_destroy", "cpmppi_groups_count", "cpmppi_groups_slice", "cpmppi_groups_handle",
            "cpmppi_groups_stream", "cpmppi_groups_fork", "cpmppi_groups_join", "cpmppi_groups_run", "cpmppi_groups_last_error",
-           "cpmppi_comm_set_stamped", "cpmppi_groups_comm_init", "cpmppi_groups_run_gather")
+           "cpmppi_comm_set_stamped", "cpmppi_groups_comm_init", "cpmppi_groups_run_gather", "cpmppi_set_pole_mass_rows")
 COMM_ID_BYTES, COMM_SLOTS, GATHER_STAMP_FLOATS = 128, 4, 4
 
 
@@ -130,6 +130,7 @@ def load():
     lib.cpmppi_get_config.argtypes = [vp, C.POINTER(cpmppi_config)]
     lib.cpmppi_set_cost_weights.argtypes = [vp, u32, C.POINTER(f), u32]
     lib.cpmppi_set_pole_mass.argtypes = [vp, f]
+    lib.cpmppi_set_pole_mass_rows.argtypes = [vp, vp, u32]
     lib.cpmppi_sample.argtypes = [vp, u32, u64, u64, u32, vp, vp, vp]
     lib.cpmppi_interpolate.argtypes = [vp, u32, vp, vp, vp]
     lib.cpmppi_predict.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]

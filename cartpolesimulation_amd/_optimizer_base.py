@@ -50,6 +50,10 @@ class _OptimizerBase:
         self.logging_values = {}
         self.engine = None
 
+    def _take_engine_flags(self, kwargs):
+        """The MPPIConfig switches that are no optimizer's own keyword (every constructor ends in **kwargs): per_env_pole_mass."""
+        self.cfg.per_env_pole_mass = bool(kwargs.get("per_env_pole_mass", False))
+
     # -- configure ------------------------------------------------------------------------------------------------
     def configure(self, dt=None, predictor_specification=None, num_envs=None, **kwargs):
         self._configure_problem(dt, predictor_specification, num_envs)
@@ -73,6 +77,11 @@ class _OptimizerBase:
         return MPPIEngine(self.num_envs, self.cfg, self.phys, device=self.device)
 
     # -- one control step -----------------------------------------------------------------------------------------
+    @property
+    def _mass_rows(self):
+        """apply_pole_mass_of's row count: a per-row pole mass has one entry per env."""
+        return {"rows": self.num_envs} if self.cfg.per_env_pole_mass else {}
+
     def _attributes(self, E):
         """-> target_position, target_equilibrium, L as float32 host vectors [E], read off variable_parameters."""
         vp = self.variable_parameters
@@ -85,7 +94,7 @@ class _OptimizerBase:
         if self.engine is None:
             self.configure()
         eng = self.engine
-        eng.apply_pole_mass_of(self.variable_parameters)      # (predictors_customization.py:55-58; only "ODE" reads it)
+        eng.apply_pole_mass_of(self.variable_parameters, **self._mass_rows)   # (predictors_customization.py:55-58; only "ODE" reads it)
         s_t = eng.tensor(s)
         single = s_t.dim() == 1
         s_t = s_t.reshape(-1, 6)

@@ -99,6 +99,8 @@ class MPPIConfig:
     predictor_type: str = "ODE_v0"       # "ODE_v0" | "ODE" (SI_Toolkit_ASF/config_predictors.yml:18-26; "ODE" = Euler-Cromer, no bounce)
     action_low: float = -1.0
     action_high: float = 1.0
+    per_env_pole_mass: bool = False      # predictor_type "ODE": a variable_parameters.m_pole that differs between rows is computed with
+                                         # per row (MPPIEngine.set_pole_mass_rows) instead of being refused
 
     @property
     def sigma(self):

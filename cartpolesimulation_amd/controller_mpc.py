@@ -114,7 +114,7 @@ class controller_mpc(template_controller):
         if neural or (spec is None and cfg.get("gru_model") is not None):
             self.predictor = None            # the network runs inside the fused kernel (optimizer_mppi.gru_model); no ODE seam object
         else:
-            self.predictor = PredictorWrapper(self.phys, device=self.device)
+            self.predictor = PredictorWrapper(self.phys, device=self.device, per_env_pole_mass=bool(cfg.get("per_env_pole_mass", False)))
             self.predictor.configure(batch_size=opt_probe.num_rollouts, horizon=opt_probe.mpc_horizon,
                                      dt=opt_probe.mpc_timestep, predictor_specification=spec or "ODE_v0",
                                      variable_parameters=self.variable_parameters)

@@ -2,7 +2,7 @@
 // kernel.   See include/cpmppi.h for the contract and cpmppi_internal.hpp for the other units of the library.
 //
 // Kernel inventory
-//   rollout_cost_kernel<COST,FAST,NOISE,R,VARIANT,INTEG>  (cpmppi_rollout.hpp, instantiated in cpmppi_rollout_*.hip; launched
+//   rollout_cost_kernel<COST,FAST,NOISE,R,VARIANT,INTEG> / rollout_cost_rows_kernel<...>  (cpmppi_rollout.hpp, instantiated in cpmppi_rollout_*.hip; launched
 //                                         here by launch_rollout) one lane = R rollouts, 6-float state + held control + running
 //                                         cost in VGPRs; per-env data wave-uniform (SGPR); block-level soft-min partials
 //                                         {min S, sum e, sum e*du[.]}; the env's last block finalizes in-kernel.
@@ -10,7 +10,7 @@
 //   finalize_kernel<KNOT_SPACE>           merges the per-block partials of one env (rescaled to the env-wide minimum),
 //                                         applies shift / update / clip, writes u_nom and Q (launches without the fused finalize).
 //   bump_counter_kernel                   advances a device-resident Philox step counter.
-// Entry points: cpmppi_create / _destroy / _get_config / _set_cost_weights / _set_pole_mass / _last_error / _last_launch /
+// Entry points: cpmppi_create / _destroy / _get_config / _set_cost_weights / _set_pole_mass / _set_pole_mass_rows / _last_error / _last_launch /
 // _version / _abi_version; cpmppi_step / _step_gather / _step_host; cpmppi_set_profiling / _get_profile,
 // cpmppi_debug_host_times; cpmppi_stream_create / _destroy.
 #include <hip/hip_runtime.h>
@@ -39,6 +39,9 @@ CPMPPI_THROUGHPUT_INSTANCES(CPMPPI_DECLARE_ROLLOUT)
 CPMPPI_ODE_LATENCY_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE)
 CPMPPI_ODE_THROUGHPUT_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE)
 CPMPPI_ODE_LONE_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE)
+CPMPPI_ODE_LATENCY_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE_ROWS)
+CPMPPI_ODE_THROUGHPUT_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE_ROWS)
+CPMPPI_ODE_LONE_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE_ROWS)
 }  // namespace cpmppi_k
 
 namespace {
@@ -119,11 +122,11 @@ hipError_t launch_rollout_noise(uint32_t noise, dim3 grid, size_t lds, hipStream
                                 const StepPtrs& a) {
   switch (noise) {
     case CPMPPI_NOISE_DELTA_U:
-      hipLaunchKernelGGL((rollout_cost_kernel<COST, FAST, NOISE_DELTA_U, R, V, INTEG>), grid, dim3(BLOCK), lds, s, p, a); break;
+      hipLaunchKernelGGL((rollout_kernel_for<COST, FAST, NOISE_DELTA_U, R, V, INTEG>()), grid, dim3(BLOCK), lds, s, p, a); break;
     case CPMPPI_NOISE_KNOTS:
-      hipLaunchKernelGGL((rollout_cost_kernel<COST, FAST, NOISE_KNOTS, R, V, INTEG>), grid, dim3(BLOCK), lds, s, p, a); break;
+      hipLaunchKernelGGL((rollout_kernel_for<COST, FAST, NOISE_KNOTS, R, V, INTEG>()), grid, dim3(BLOCK), lds, s, p, a); break;
     case CPMPPI_NOISE_DELTA_U_TILED:
-      hipLaunchKernelGGL((rollout_cost_kernel<COST, FAST, NOISE_TILED, R, V, INTEG>), grid, dim3(BLOCK), lds, s, p, a); break;
+      hipLaunchKernelGGL((rollout_kernel_for<COST, FAST, NOISE_TILED, R, V, INTEG>()), grid, dim3(BLOCK), lds, s, p, a); break;
     default: {
       // development aid (tools/dev/placement.py): CPMPPI_LDS_PAD=<bytes> of extra dynamic LDS per workgroup caps how many
       // workgroups the dispatcher can put on one CU (160 KB each)
@@ -131,12 +134,12 @@ hipError_t launch_rollout_noise(uint32_t noise, dim3 grid, size_t lds, hipStream
       if (pad) {
         static bool raised = false;
         if (!raised) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&rollout_cost_kernel<COST, FAST, NOISE_PHILOX, R, V, INTEG>),
+          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rollout_kernel_for<COST, FAST, NOISE_PHILOX, R, V, INTEG>()),
                                     hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + pad));
           raised = true;
         }
       }
-      hipLaunchKernelGGL((rollout_cost_kernel<COST, FAST, NOISE_PHILOX, R, V, INTEG>), grid, dim3(BLOCK), lds + pad, s, p, a); break;
+      hipLaunchKernelGGL((rollout_kernel_for<COST, FAST, NOISE_PHILOX, R, V, INTEG>()), grid, dim3(BLOCK), lds + pad, s, p, a); break;
     }
   }
   return hipGetLastError();
@@ -162,11 +165,18 @@ hipError_t launch_rollout_math(uint32_t math, uint32_t ode, uint32_t rpl, uint32
 #define CPMPPI_LAUNCH_V(FAST, R, V, ...) (*variant_out = (V), launch_rollout_noise<COST, FAST, R, V, ##__VA_ARGS__>(noise, grid, lds, s, p, a))
   if (ode == CPMPPI_ODE_CROMER) {
     // predictor_ODE has no events, hence no mid-size (phased) build: latency build up to one wave per SIMD with one rollout
-    // per lane, the throughput build otherwise
-    if (math != CPMPPI_MATH_FAST) return CPMPPI_LAUNCH_V(false, 1, 1, PREDICTOR_ODE);
-    if (rpl == 2)
-      return ((uint64_t)grid.x * WAVES <= 1024ull) ? CPMPPI_LAUNCH_V(true, 2, 3, PREDICTOR_ODE) : CPMPPI_LAUNCH_V(true, 2, 1, PREDICTOR_ODE);
-    return ((uint64_t)grid.x * BLOCK <= 65536ull) ? CPMPPI_LAUNCH_V(true, 1, 0, PREDICTOR_ODE) : CPMPPI_LAUNCH_V(true, 1, 1, PREDICTOR_ODE);
+    // per lane, the throughput build otherwise.  With a per-env pole mass registered (a.m_pole): the same builds' instantiations
+    // that read it
+#define CPMPPI_LAUNCH_ODE(INTEG_)                                                                                                 \
+    do {                                                                                                                          \
+      if (math != CPMPPI_MATH_FAST) return CPMPPI_LAUNCH_V(false, 1, 1, INTEG_);                                                  \
+      if (rpl == 2)                                                                                                               \
+        return ((uint64_t)grid.x * WAVES <= 1024ull) ? CPMPPI_LAUNCH_V(true, 2, 3, INTEG_) : CPMPPI_LAUNCH_V(true, 2, 1, INTEG_); \
+      return ((uint64_t)grid.x * BLOCK <= 65536ull) ? CPMPPI_LAUNCH_V(true, 1, 0, INTEG_) : CPMPPI_LAUNCH_V(true, 1, 1, INTEG_);  \
+    } while (0)
+    if (a.m_pole) CPMPPI_LAUNCH_ODE(PREDICTOR_ODE_ROWS);
+    CPMPPI_LAUNCH_ODE(PREDICTOR_ODE);
+#undef CPMPPI_LAUNCH_ODE
   }
   if (math == CPMPPI_MATH_FAST) {
     // the throughput build reads its per-env constants from a.env_fold: written here, on the same stream, first
@@ -206,6 +216,7 @@ hipError_t launch_rollout(cpmppi_handle* h, const Params& prm, uint32_t rpl, uin
   hipError_t e;
   StepPtrs a = a_in;
   a.env_fold = h->env_fold;
+  a.m_pole = h->m_pole_rows;                       // (NULL on every predictor_ODE_v0 handle: cpmppi_set_pole_mass_rows refuses those)
   switch (prm.cost_id) {
     case CPMPPI_COST_QBGM: e = launch_rollout_math<COST_QBGM>(h->cfg.math_mode, h->cfg.ode_predictor, rpl, noise, grid, lds, s, prm, a, &variant); break;
     case CPMPPI_COST_DEFAULT: e = launch_rollout_math<COST_DEFAULT>(h->cfg.math_mode, h->cfg.ode_predictor, rpl, noise, grid, lds, s, prm, a, &variant); break;
@@ -240,6 +251,8 @@ int check_step(cpmppi_handle* h, const cpmppi_step_args* a) {
     if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_step: predictor GRU requested but no model set (cpmppi_set_gru)");
     if ((h->prm.cost_id != CPMPPI_COST_QBGM && h->prm.cost_id != CPMPPI_COST_DEFAULT) || h->prm.qb_mode != 0u)
       return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_step: the GRU predictor supports quadratic_boundary_grad_minimal and default");
+  } else if (!pole_mass_rows_cover(h, a->E)) {     // (a GRU step does not read the pole mass)
+    return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_step", h, a->E));
   }
   return CPMPPI_OK;
 }
@@ -436,6 +449,25 @@ int cpmppi_set_pole_mass(cpmppi_handle* h, float m_pole) {
   // (plant_m_pole): a handle that serves as both must not change the plant by updating the controller's attribute.
   h->cfg.m_pole = m_pole;
   h->prm.m_pole = m_pole;
+  return CPMPPI_OK;
+}
+
+int cpmppi_set_pole_mass_rows(cpmppi_handle* h, const float* m_pole, uint32_t n) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!m_pole) {                                   // back to the handle's scalar
+    h->m_pole_rows = nullptr;
+    h->m_pole_rows_n = 0;
+    return CPMPPI_OK;
+  }
+  if (h->cfg.ode_predictor != CPMPPI_ODE_CROMER)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_pole_mass_rows: predictor_ODE_v0 does not read the pole mass attribute "
+                                       "(a per-row mass needs ode_predictor = CPMPPI_ODE_CROMER)");
+  if (n == 0) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_pole_mass_rows: n must be > 0 with a non-null array");
+  if (misaligned(m_pole)) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_pole_mass_rows: misaligned pointer");
+  // only the POINTER is taken: the kernels of every later launch read the values when they run, so a caller (or a captured graph
+  // with a copy node in front) may rewrite the array between launches without calling this again
+  h->m_pole_rows = m_pole;
+  h->m_pole_rows_n = n;
   return CPMPPI_OK;
 }
 

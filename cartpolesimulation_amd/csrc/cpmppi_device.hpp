@@ -160,6 +160,16 @@ __device__ __forceinline__ EnvConst make_env_const(const Params& p, float L) {
   return c;
 }
 
+// predictor_ODE's per-row controller-side pole mass (cpmppi_set_pole_mass_rows): the launch's argument block with the ROW's mass
+// in the handle's place.  The copy then goes where the launch's own block went - make_env_const* and the substep functions - so a
+// row computes, instruction for instruction, what a handle whose scalar mass is `m_pole` computes (only the fields those read
+// survive the copy; the costs never read the mass and keep the launch's block).
+__device__ __forceinline__ Params with_pole_mass(const Params& p, float m_pole) {
+  Params q = p;
+  q.m_pole = m_pole;
+  return q;
+}
+
 // For kernels where the env (hence L) is the same for the whole wave: pin every field to an SGPR.  Field by field — the
 // first version walked the struct through a float pointer, which kept it in a 28-byte private (scratch) slot per lane:
 // 117 MB of scratch stores per 8192-env launch.
@@ -867,7 +877,8 @@ __device__ __forceinline__ bool control_step_fast_eventful(State<F>& st, F uK, u
 // (CartPole/cartpole_equations.py:181-259): per substep the same _cartpole_ode (:232), then EULER-CROMER (:293-304:
 // velocities first, angle and position advance by the NEW velocities), NO edge bounce (:241-243 is commented out in the
 // reference), cos / sin of the integrated angle (:245-246) and angle = atan2(sin, cos) (:248, 307-308).
-enum : int { PREDICTOR_ODE_V0 = 0, PREDICTOR_ODE = 1 };
+enum : int { PREDICTOR_ODE_V0 = 0, PREDICTOR_ODE = 1,
+             PREDICTOR_ODE_ROWS = 2 };   // (the launch dispatch only: PREDICTOR_ODE with the pole mass read per env = rollout_cost_rows_kernel)
 
 // PRECISE: the reference's operand grouping with IEEE divides, libm cos / sin, no FMA contraction.  The angle this predictor
 // re-derives on every substep, atan2(sin, cos), is evaluated in double and rounded once: the device's atan2f is a ~2 ulp

@@ -68,6 +68,8 @@ struct cpmppi_handle {
   std::vector<uint8_t> ev_tail;        // per triple: was the third event recorded (a separate finalize / counter kernel ran)
   size_t ev_used = 0;
   cpmppi_comm::CommState* comm = nullptr;   // RCCL communicator + side stream of cpmppi_comm_* (cpmppi_comm.hip)
+  const float* m_pole_rows = nullptr;  // cpmppi_set_pole_mass_rows: the caller's DEVICE array of per-row controller-side pole masses (predictor_ODE), or NULL
+  uint32_t m_pole_rows_n = 0;          // ... and how many rows it holds
   float plant_m_pole = 0.0f;           // the pole mass of the simulated PLANT (cfg.m_pole at creation; cpmppi_set_pole_mass does not touch it)
   cpmppi_launch_info last_launch = {0, 0, 0, 0, 0, 0, 0};   // cpmppi_last_launch: the instantiation the last rollout launch used
 };
@@ -106,6 +108,14 @@ struct DeviceGuard {
     return fail((h), CPMPPI_ERR_HIP, std::string("hipSetDevice: ") + hipGetErrorString(device_guard_.err))
 
 inline bool misaligned(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 3u) != 0; }
+
+// cpmppi_set_pole_mass_rows: does the registered array (if any) hold a mass for every row of a launch of `rows` rows?  Every entry
+// point that integrates predictor_ODE asks before it launches; the second function words the refusal.
+inline bool pole_mass_rows_cover(const cpmppi_handle* h, uint32_t rows) { return !h->m_pole_rows || rows <= h->m_pole_rows_n; }
+inline std::string pole_mass_rows_short(const char* who, const cpmppi_handle* h, uint32_t rows) {
+  return std::string(who) + ": " + std::to_string(rows) + " rows, but cpmppi_set_pole_mass_rows registered " +
+         std::to_string(h->m_pole_rows_n) + " pole masses";
+}
 
 // the end of an entry point that has just launched a kernel: CPMPPI_OK, or the launch's error
 inline int launched(cpmppi_handle* h) {

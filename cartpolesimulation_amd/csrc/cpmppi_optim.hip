@@ -27,14 +27,11 @@ namespace {
 struct GradPtrs {
   const float* s0; const float* Q; const float* x_t; const float* te; const float* L; const float* prev_in;
   float* ckpt; float* S_out; float* grad; uint32_t E;
+  const float* m_pole;      // [E] predictor_ODE: the pole mass per env (cpmppi_set_pole_mass_rows), or NULL = the handle's
 };
 
 template <int COST, int INTEG = PREDICTOR_ODE_V0>
 __global__ __launch_bounds__(BLOCK) void rollout_grad_kernel(const Params p, const GradPtrs a) {
-  auto forward_substep = [&](State<float>& s, float uK, const EnvConst& e) __attribute__((always_inline)) {
-    if constexpr (INTEG == PREDICTOR_ODE) substep_cromer_plain(s, uK, p.t_step, p, e);
-    else substep_fast<float>(s, uK, p.t_step, p, e, p.THL);
-  };
   extern __shared__ float sub_states[];            // [S][6][BLOCK]
   const uint32_t tid = threadIdx.x;
   const size_t B = (size_t)a.E * p.N;
@@ -43,7 +40,16 @@ __global__ __launch_bounds__(BLOCK) void rollout_grad_kernel(const Params p, con
   const uint32_t env = (uint32_t)(g / p.N);
   const uint32_t H = p.H, S = p.S;
   const float t = p.t_step;
-  const EnvConst ec = make_env_const(p, a.L ? a.L[env] : p.L_default);
+  // `pi`: the block the integration and its adjoint compute with - predictor_ODE: the env's own pole mass in place (the costs
+  // never read the mass)
+  Params pm_;
+  if constexpr (INTEG == PREDICTOR_ODE) pm_ = with_pole_mass(p, a.m_pole ? a.m_pole[env] : p.m_pole);
+  const Params& pi = (INTEG == PREDICTOR_ODE) ? pm_ : p;
+  auto forward_substep = [&](State<float>& s, float uK, const EnvConst& e) __attribute__((always_inline)) {
+    if constexpr (INTEG == PREDICTOR_ODE) substep_cromer_plain(s, uK, p.t_step, pi, e);
+    else substep_fast<float>(s, uK, p.t_step, p, e, p.THL);
+  };
+  const EnvConst ec = make_env_const(pi, a.L ? a.L[env] : p.L_default);
   const float x_t = a.x_t[env], te = a.te[env];
   const float* __restrict__ s0 = a.s0 + (size_t)env * 6;
   const float* __restrict__ Q = a.Q + g * H;
@@ -92,7 +98,7 @@ __global__ __launch_bounds__(BLOCK) void rollout_grad_kernel(const Params p, con
     for (uint32_t i = S; i-- > 0;) {
       const float* __restrict__ d = my + (size_t)i * 6 * BLOCK;
       const State<float> si{d[0], d[BLOCK], d[2 * BLOCK], d[3 * BLOCK], d[4 * BLOCK], d[5 * BLOCK]};
-      substep_reverse<(INTEG == PREDICTOR_ODE)>(si, uK, t, p, ec, lam, guK);
+      substep_reverse<(INTEG == PREDICTOR_ODE)>(si, uK, t, pi, ec, lam, guK);
     }
     // stage k: its own state and control
     const float ca = (k == 0) ? cos0 : st0.c, sa = (k == 0) ? sin0 : st0.s;
@@ -283,6 +289,7 @@ int cpmppi_rollout_cost(cpmppi_handle* h, uint32_t E, const float* s0, const flo
     return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost: bad argument");
   if (h->prm.cost_id == CPMPPI_COST_LEGACY)
     return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost: plugin costs only");
+  if (!pole_mass_rows_cover(h, E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_rollout_cost", h, E));
   CPMPPI_ON_DEVICE(h);
   Params prm = h->prm;
   prm.shift_mode = CPMPPI_SHIFT_NONE;
@@ -313,6 +320,7 @@ int cpmppi_rollout_cost_grad(cpmppi_handle* h, uint32_t E, const float* s0, cons
                                        "(built: quadratic_boundary_grad_minimal, default, quadratic_boundary_grad)");
   if (h->cfg.math_mode != CPMPPI_MATH_FAST)
     return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: the adjoint is written for the FAST arithmetic");
+  if (!pole_mass_rows_cover(h, E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_rollout_cost_grad", h, E));
   const size_t lds = (size_t)h->cfg.S * 6 * BLOCK * sizeof(float);
   if (lds > 150 * 1024) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: S too large for the LDS sub-state buffer (<= 25)");
   CPMPPI_ON_DEVICE(h);
@@ -324,7 +332,7 @@ int cpmppi_rollout_cost_grad(cpmppi_handle* h, uint32_t E, const float* s0, cons
     CPMPPI_HIP(h, hipMalloc(&h->grad_ckpt, need * sizeof(float)));
     h->grad_ckpt_floats = need;
   }
-  GradPtrs a{s0, inputs, target_position, target_equilibrium, L, previous_input, h->grad_ckpt, S_out, grad_out, E};
+  GradPtrs a{s0, inputs, target_position, target_equilibrium, L, previous_input, h->grad_ckpt, S_out, grad_out, E, h->m_pole_rows};
   const auto launch = h->cfg.ode_predictor == CPMPPI_ODE_CROMER ? launch_grad<PREDICTOR_ODE> : launch_grad<PREDICTOR_ODE_V0>;
   launch(h->prm.cost_id, dim3((unsigned)((B + BLOCK - 1) / BLOCK)), lds, (hipStream_t)stream, h->prm, a);
   return launched(h);

@@ -162,12 +162,18 @@ __device__ __forceinline__ void predict_control_step(State<float>& st, float Qk,
 }
 
 template <bool FAST, bool STAGED, int INTEG = PREDICTOR_ODE_V0>
-__global__ __launch_bounds__(BLOCK) void predict_kernel(const Params p, uint32_t B, uint32_t H,
+__global__ __launch_bounds__(BLOCK) void predict_kernel(const Params p0, uint32_t B, uint32_t H,
                                                         const float* __restrict__ s0, const float* __restrict__ Q,
-                                                        const float* __restrict__ Lp, float* __restrict__ traj) {
+                                                        const float* __restrict__ Lp, float* __restrict__ traj,
+                                                        const float* __restrict__ Mp) {
+  // Mp[B]: predictor_ODE's pole mass per row (cpmppi_set_pole_mass_rows; NULL = the handle's) - a row integrates with its own
+  // copy of the argument block (with_pole_mass); predictor_ODE_v0 does not read the mass attribute
   if constexpr (!STAGED) {
     const size_t b = (size_t)blockIdx.x * BLOCK + threadIdx.x;
     if (b >= B) return;
+    Params pm_;
+    if constexpr (INTEG == PREDICTOR_ODE) pm_ = with_pole_mass(p0, Mp ? Mp[b] : p0.m_pole);
+    const Params& p = (INTEG == PREDICTOR_ODE) ? pm_ : p0;
     const EnvConst ec = make_env_const(p, Lp ? Lp[b] : p.L_default);
     const float* s = s0 + b * 6;
     State<float> st{s[0], s[1], s[2], s[3], s[4], s[5]};
@@ -186,6 +192,9 @@ __global__ __launch_bounds__(BLOCK) void predict_kernel(const Params p, uint32_t
   const bool valid = b_raw < B;
   const size_t b = valid ? b_raw : (size_t)B - 1;                 // (idle lanes of the last block shadow the last rollout)
   const size_t wave_b0 = (size_t)blockIdx.x * BLOCK + (size_t)wave * 64;
+  Params pm_;
+  if constexpr (INTEG == PREDICTOR_ODE) pm_ = with_pole_mass(p0, Mp ? Mp[b] : p0.m_pole);
+  const Params& p = (INTEG == PREDICTOR_ODE) ? pm_ : p0;
   const EnvConst ec = make_env_const(p, Lp ? Lp[b] : p.L_default);
   const float* s = s0 + b * 6;
   State<float> st{s[0], s[1], s[2], s[3], s[4], s[5]};
@@ -337,9 +346,9 @@ int launch_sample(cpmppi_handle* h, uint32_t E, uint64_t seed, uint64_t offset, 
 
 template <bool FAST, int INTEG>
 void launch_predict(bool staged, dim3 grid, hipStream_t st, const Params& p, uint32_t B, uint32_t H, const float* s0,
-                    const float* Q, const float* L, float* traj) {
-  if (staged) hipLaunchKernelGGL((predict_kernel<FAST, true, INTEG>), grid, dim3(BLOCK), 0, st, p, B, H, s0, Q, L, traj);
-  else hipLaunchKernelGGL((predict_kernel<FAST, false, INTEG>), grid, dim3(BLOCK), 0, st, p, B, H, s0, Q, L, traj);
+                    const float* Q, const float* L, float* traj, const float* m_pole) {
+  if (staged) hipLaunchKernelGGL((predict_kernel<FAST, true, INTEG>), grid, dim3(BLOCK), 0, st, p, B, H, s0, Q, L, traj, m_pole);
+  else hipLaunchKernelGGL((predict_kernel<FAST, false, INTEG>), grid, dim3(BLOCK), 0, st, p, B, H, s0, Q, L, traj, m_pole);
 }
 
 }  // namespace
@@ -404,6 +413,7 @@ int cpmppi_predict(cpmppi_handle* h, uint32_t B, uint32_t horizon, const float* 
   if (B == 0 || !s0 || !Q || !traj_out) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_predict: bad argument");
   if (misaligned(s0) || misaligned(Q) || misaligned(L) || misaligned(traj_out))
     return fail(h, CPMPPI_ERR_ALIGN, "cpmppi_predict: misaligned pointer");
+  if (!pole_mass_rows_cover(h, B)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_predict", h, B));
   CPMPPI_ON_DEVICE(h);
   // stores staged through LDS once the launch puts more than one wave on every SIMD (below that the direct stores'
   // shorter path wins: measured 59 vs 82 us at 1024 rollouts, 416 vs 280 us at 262144)
@@ -411,7 +421,7 @@ int cpmppi_predict(cpmppi_handle* h, uint32_t B, uint32_t horizon, const float* 
   const bool fast = h->cfg.math_mode == CPMPPI_MATH_FAST, cromer = h->cfg.ode_predictor == CPMPPI_ODE_CROMER;
   const auto launch = fast ? (cromer ? launch_predict<true, PREDICTOR_ODE> : launch_predict<true, PREDICTOR_ODE_V0>)
                            : (cromer ? launch_predict<false, PREDICTOR_ODE> : launch_predict<false, PREDICTOR_ODE_V0>);
-  launch(staged, dim3((B + BLOCK - 1) / BLOCK), (hipStream_t)stream, h->prm, B, horizon, s0, Q, L, traj_out);
+  launch(staged, dim3((B + BLOCK - 1) / BLOCK), (hipStream_t)stream, h->prm, B, horizon, s0, Q, L, traj_out, h->m_pole_rows);
   return launched(h);
 }
 

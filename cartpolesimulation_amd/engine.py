@@ -71,6 +71,7 @@ class MPPIEngine:
         self.P = self.mppi.num_knots
         self._cfg = build_c_config(self.E, self.mppi, self.phys)
         self._m_pole = float(np.float32(self.phys.m_pole))
+        self._m_rows = self._m_rows_own = None                  # set_pole_mass_rows: the registered tensor / the engine's own buffer
 
     # ------------------------------------------------------------------ plumbing
     def close(self):
@@ -169,9 +170,12 @@ class MPPIEngine:
         arr = (C.c_float * len(w))(*w)
         self._check(self.lib.cpmppi_set_cost_weights(self._h, cost_id, arr, len(w)))
 
-    def apply_pole_mass_of(self, variable_parameters):
+    def apply_pole_mass_of(self, variable_parameters, rows=None):
         """predictor_ODE takes the pole's mass from variable_parameters at every step (predictors_customization.py:55-58;
-        the simulator sends 'm_pole' with every controller.step, CartPole/__init__.py:516); predictor_ODE_v0 does not."""
+        the simulator sends 'm_pole' with every controller.step, CartPole/__init__.py:516); predictor_ODE_v0 does not.
+        With ``MPPIConfig.per_env_pole_mass`` an m_pole that differs between rows is computed with per row (set_pole_mass_rows;
+        ``rows``: how many the caller's next launch has - the predictors' batch, the optimizers' num_envs), as the reference's
+        predictor broadcasts it; a scalar or a uniform host array stays the handle's one mass and clears the rows."""
         if self.mppi.predictor_type != "ODE":
             return
         m = getattr(variable_parameters, "m_pole", None)
@@ -181,9 +185,19 @@ class MPPIEngine:
             if m is getattr(self, "_m_pole_obj", None):
                 return
             self._m_pole_obj = m                                # (arrays / tensors may be assigned in place: converted every time)
+        per_row = getattr(self.mppi, "per_env_pole_mass", False)
+        if per_row and torch.is_tensor(m) and m.is_cuda and m.numel() > 1:
+            self._m_pole_obj = None
+            return self.set_pole_mass_rows(m, rows)             # (registered as it is: no copy, no look at its values)
         a = np.asarray(m.cpu() if hasattr(m, "cpu") else m, dtype=np.float32).reshape(-1)
         if a.size == 0 or not np.all(a == a[0]):
-            raise NotImplementedError(f"m_pole must be the same for every env of a handle (got {a[:4]}...)")
+            if per_row and a.size:
+                self._m_pole_obj = None
+                return self.set_pole_mass_rows(a, rows)
+            raise NotImplementedError(f"m_pole must be the same for every env of a handle (got {a[:4]}...); "
+                                      "MPPIConfig(per_env_pole_mass=True) computes with a mass per row")
+        if per_row:
+            self.set_pole_mass_rows(None)
         self.set_pole_mass(float(a[0]))
 
     def set_pole_mass(self, m_pole):
@@ -192,6 +206,44 @@ class MPPIEngine:
         if m != self._m_pole:
             self._check(self.lib.cpmppi_set_pole_mass(self._h, m))
             self._m_pole = m
+
+    def set_pole_mass_rows(self, m, rows=None):
+        """cpmppi_set_pole_mass_rows: the pole mass predictor_ODE computes with PER ROW - per env for step / rollout_cost /
+        rollout_cost_grad / step_host, per rollout for predict - wherever that call's L would be indexed.  ``None``: back to the
+        handle's one mass (set_pole_mass).  A contiguous float32 tensor on the engine's device is registered AS IT IS - no copy, no
+        host synchronisation; every later launch reads its values when it runs, so it may be rewritten in place (stream-ordered)
+        and must outlive the launches; the engine keeps a reference.  Anything else (a host array, a list) is checked - finite,
+        > 0 - uploaded into a buffer of the engine's own and registered.  ``rows``: the row count the caller's launches will have;
+        an array of another length is refused here (the library refuses a launch with more rows than were registered)."""
+        if m is None:
+            if getattr(self, "_m_rows", None) is not None:
+                self._check(self.lib.cpmppi_set_pole_mass_rows(self._h, None, 0))
+                self._m_rows = None
+            return
+        if self.mppi.predictor_type != "ODE":
+            raise ValueError(f"a per-row pole mass is read by predictor_type 'ODE' only (this engine: {self.mppi.predictor_type!r}; "
+                             "predictor_ODE_v0 never reads the attribute)")
+        if rows is not None and int(np.prod(np.shape(m))) != int(rows):
+            raise ValueError(f"m_pole has {int(np.prod(np.shape(m)))} entries, the call has {int(rows)} rows")
+        if torch.is_tensor(m) and m.is_cuda:
+            if not (m.dtype == torch.float32 and m.is_contiguous() and m.dim() == 1 and m.numel() > 0 and m.device == self.device):
+                raise ValueError("m_pole rows on the device must be a contiguous float32 tensor [rows] on the engine's device")
+            t = m
+        else:
+            a = np.asarray(m.cpu() if torch.is_tensor(m) else m, dtype=np.float32)
+            if a.ndim != 1 or a.size == 0:
+                raise ValueError(f"m_pole rows must be a vector [rows], got shape {a.shape}")
+            if not (np.isfinite(a).all() and (a > 0).all()):
+                raise ValueError("every pole mass must be a positive, finite number")
+            own = getattr(self, "_m_rows_own", None)
+            if own is None or own.numel() != a.size:
+                own = self._m_rows_own = self.empty(a.size)
+            own.copy_(torch.from_numpy(np.ascontiguousarray(a)), non_blocking=False)
+            t = own
+        cur = getattr(self, "_m_rows", None)
+        if cur is None or cur.data_ptr() != t.data_ptr() or cur.numel() != t.numel():
+            self._check(self.lib.cpmppi_set_pole_mass_rows(self._h, _ptr(t), t.numel()))
+        self._m_rows = t
 
     def sample(self, seed, offset=0, env_offset=0, E=None, knots=True, delta_u=False):
         E = self.E if E is None else int(E)
@@ -513,8 +565,10 @@ class MPPIEngine:
         info = _L.cpmppi_launch_info()
         self._check(self.lib.cpmppi_last_launch(self._h, C.byref(info)))
         d = {n: int(getattr(info, n)) for n, _ in info._fields_}
-        d["kernel"] = ("rollout_cost_kernel<%d, %s, %d, %d, %d%s>" % (
-            d["cost_id"], "true" if d["math_mode"] == _L.MATH_FAST else "false", (0, 1, 2, 3)[d["noise_kind"]],
+        # (predictor "ODE" with a per-env pole mass registered runs the kernel's second compilation, rollout_cost_rows_kernel)
+        rows = d["ode_predictor"] and getattr(self, "_m_rows", None) is not None
+        d["kernel"] = ("rollout_cost%s_kernel<%d, %s, %d, %d, %d%s>" % (
+            "_rows" if rows else "", d["cost_id"], "true" if d["math_mode"] == _L.MATH_FAST else "false", (0, 1, 2, 3)[d["noise_kind"]],
             d["rollouts_per_lane"], d["build_variant"], ", PREDICTOR_ODE" if d["ode_predictor"] else ""))
         return d
 

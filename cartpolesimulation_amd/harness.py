@@ -121,6 +121,41 @@ class BatchedCartPoleExperiment:
         return run.finish()
 
 
+def controller_pole_mass(b, per_env=False):
+    """What the simulator's 'm_pole' attribute holds at each of the T + 1 controller calls of a schedule.ExperimentBatch with an
+    `m_pole:` updater table: the true mass at that call where the controller informer says told, the experiment's initial mass
+    otherwise (CartPole/controller_informer.py).  -> (m_ctrl, m_ctrl_env), at most one of them not None:
+      m_ctrl [T+1]        every experiment has the same mass schedule AND the same informer (the deterministic updater modes): one
+                          value per call, the handle's scalar (cpmppi_set_pole_mass)
+      m_ctrl_env [T+1,E]  ``per_env`` only: schedules or informers that differ between experiments (`mode: random`, `init_value:
+                          random`, 'switching_random'), each experiment with its OWN informer column (cpmppi_set_pole_mass_rows)
+    Without ``per_env`` such a batch yields (None, None): the controller keeps the handle's mass (with a warning where only the
+    informer differs)."""
+    mt = np.asarray(b.m_pole_table, np.float32)
+    T, E = b.n_periods, mt.shape[1]
+    calls = np.minimum(np.arange(T + 1) * b.n_ctrl, mt.shape[0] - 1)
+    inf = None if b.informed is None else np.asarray(b.informed, bool)
+    shared = inf is None or inf.ndim == 1 or bool((inf == inf[:, :1]).all())
+    if (mt == mt[:, :1]).all() and (shared or not per_env):
+        if not shared:
+            import warnings
+            warnings.warn("the informer differs between experiments ('switching_random'): the controller's one pole mass cannot follow "
+                          "it and stays the handle's; the plants follow their own tables (MPPIConfig(per_env_pole_mass=True) follows it "
+                          "per experiment)")
+            return None, None
+        told = np.ones(T + 1, bool)
+        if inf is not None:
+            col = inf[:, 0] if inf.ndim == 2 else inf
+            told = col[np.minimum(calls, len(col) - 1)]
+        return np.where(told, mt[calls, 0], mt[0, 0]).astype(np.float32), None
+    if not per_env:
+        return None, None
+    told = np.ones((T + 1, E), bool)
+    if inf is not None:
+        told = np.broadcast_to(inf if inf.ndim == 2 else inf[:, None], (len(inf), E))[np.minimum(calls, len(inf) - 1)]
+    return None, np.ascontiguousarray(np.where(told, mt[calls], mt[0]), np.float32)
+
+
 class ScheduleRun:
     """The device loop of BatchedCartPoleExperiment.run_schedule as an object that enqueues one piece at a time, so that several
     runs - env groups on their own streams, pipeline.run_schedule_groups - can be interleaved by one host thread."""
@@ -200,27 +235,18 @@ class ScheduleRun:
             self.prev_Q = eng.zeros(E)
             self.plant.update(Q_applied_out=self.prev_Q)
         # the pole MASS the controller computes with (predictor_ODE takes it from the simulator's 'm_pole' attribute at every call,
-        # predictors_customization.py:55-58; predictor_ODE_v0 does not): one value per handle, so it can follow the plant's mass only
-        # when every experiment of the batch has the same schedule (the deterministic updater modes) - told or not as the informer says
-        self.m_ctrl = None
+        # predictors_customization.py:55-58; predictor_ODE_v0 does not) - told or not as the informer says (controller_pole_mass)
+        self.m_ctrl = self.m_env_tab = self.m_env = None
         if b.m_pole_table is not None and getattr(eng.mppi, "predictor_type", "ODE_v0") == "ODE":
-            mt = np.asarray(b.m_pole_table, np.float32)
-            if (mt == mt[:, :1]).all():
-                calls = np.minimum(np.arange(T + 1) * b.n_ctrl, mt.shape[0] - 1)
-                told = np.ones(T + 1, bool)
-                shared = True
-                if b.informed is not None:
-                    inf = np.asarray(b.informed, bool)
-                    if inf.ndim == 2:
-                        shared = bool((inf == inf[:, :1]).all())
-                        inf = inf[:, 0]
-                    told = inf[np.minimum(calls, len(inf) - 1)]
-                if shared:
-                    self.m_ctrl = np.where(told, mt[calls, 0], mt[0, 0]).astype(np.float32)
-                else:
-                    import warnings
-                    warnings.warn("the informer differs between experiments ('switching_random'): the controller's one pole mass cannot follow "
-                                  "it and stays the handle's; the plants follow their own tables")
+            self.m_ctrl, m_env = controller_pole_mass(b, per_env=getattr(eng.mppi, "per_env_pole_mass", False))
+            if m_env is not None:
+                # one mass per experiment: the table stays on the device, the handle reads ONE registered [E] vector, and row c is
+                # copied into it on the launch stream before controller call c
+                self.m_env_tab = eng.tensor(m_env)
+                self.m_env = self.m_env_tab[0].clone()
+                self.m_env_constant = bool((m_env == m_env[:1]).all())
+                if optimizer is None:
+                    eng.set_pole_mass_rows(self.m_env)
         self.counter = self.graph = None
         self.per = 0
         self._prep = self._prep_plant = None                       # argument blocks built once (the launched Philox loop)
@@ -234,10 +260,15 @@ class ScheduleRun:
         return self.c < self.T
 
     def set_controller_mass(self, c, engines=None):
-        """Before controller call c: the pole mass the simulator would hand it (the launch reads it from the handle when enqueued)."""
+        """Before controller call c: the pole mass the simulator would hand it (the launch reads it from the handle when enqueued;
+        a mass per experiment: row c of the device table into the registered vector, on the launch stream)."""
         if self.m_ctrl is not None:
             for e in (engines or [self.eng]):
                 e.set_pole_mass(float(self.m_ctrl[c]))
+        elif self.m_env is not None and (c == 0 or not self.m_env_constant):
+            fixed = getattr(self.eng, "_fixed_stream_obj", None)
+            with torch.cuda.stream(fixed if fixed is not None else torch.cuda.current_stream(self.s.device)):
+                self.m_env.copy_(self.m_env_tab[c])
 
     def _control(self, c):
         eng = self.eng
@@ -250,6 +281,9 @@ class ScheduleRun:
                 vp.L = self.cur_L
             if self.m_ctrl is not None:
                 vp.m_pole = float(self.m_ctrl[c])
+            elif self.m_env is not None:
+                self.set_controller_mass(c)
+                vp.m_pole = self.m_env                              # (the device row: an optimizer with per_env_pole_mass registers it)
             if self.prev_Q is not None:
                 vp.Q_ccrc = self.prev_Q
                 setattr(vp, "Q_applied_-1", self.prev_Q)
@@ -293,6 +327,9 @@ class ScheduleRun:
             raise ValueError("an optimizer object is paced by the host: run this batch launched (graph=False)")
         if self.m_ctrl is not None and len(np.unique(self.m_ctrl)) > 1:
             raise ValueError("a captured graph replays ONE pole mass for the controller: run this batch launched (graph=False)")
+        if self.m_env is not None and not self.m_env_constant:
+            raise ValueError("a captured graph cannot step through the controller's per-experiment pole-mass table (the row would "
+                             "have to be selected on the device): run this batch launched (graph=False)")
         dev = self.s.device
         # the graph replays the handle's controller mass as it is when CAPTURED: the run's (constant) one, which may differ from
         # the mass the handle was created with (an uninformed controller; advisor, round 5)
@@ -333,6 +370,8 @@ class ScheduleRun:
         """The run's last controller call (+ the trailing simulation steps of a length that is not a whole number of periods)."""
         assert not self.periods_left
         self._control(self.T)
+        if self.m_env is not None and self.optimizer is None:
+            self.eng.set_pole_mass_rows(None)                       # (the launches enqueued keep the vector; the handle is left as found)
         if self.counter is not None:
             self.eng.plant_step(self.s, self.Q, self.tail, period_dev=self.counter, **self.plant)
         else:

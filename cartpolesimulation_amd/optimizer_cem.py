@@ -26,6 +26,7 @@ class optimizer_cem(_OptimizerBase):
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
                          intermediate_steps, control_mode="clip", shift_mode="none", math_mode=math_mode)
+        self._take_engine_flags(kwargs)
         self.cem_outer_it, self.cem_best_k = int(cem_outer_it), int(cem_best_k)
         self.cem_initial_action_stdev, self.cem_stdev_min = float(cem_initial_action_stdev), float(cem_stdev_min)
         self.warmup, self.warmup_iterations = bool(warmup), int(warmup_iterations)

@@ -117,6 +117,7 @@ class optimizer_gradient(_GradientBase):
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, initial_action_stdev,
                          10, num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
                          variable_parameters, optimizer_logging, horizon_reduce)
+        self._take_engine_flags(kwargs)
 
     def _draw(self):
         """Independent N(0, initial_action_stdev) per time-step, clipped (cpmppi_cem_sample)."""
@@ -163,6 +164,7 @@ class optimizer_rpgd(_GradientBase):
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, stdev,
                          period_interpolation_inducing_points, num_envs, cost_function_specification, cost_weights,
                          intermediate_steps, phys, device, variable_parameters, optimizer_logging, horizon_reduce)
+        self._take_engine_flags(kwargs)
 
     def _shape_samples(self, z):
         if self.distribution == "normal":

@@ -51,6 +51,7 @@ class optimizer_mppi(_OptimizerBase):
                          period_interpolation_inducing_points=int(period_interpolation_inducing_points),
                          horizon_reduce=horizon_reduce, control_mode=control_mode, shift_mode=shift_mode,
                          correction_u=correction_u, math_mode=math_mode, predictor_type=predictor_type)
+        self._take_engine_flags(kwargs)
         self.calculate_optimal_trajectory = calculate_optimal_trajectory
         self.optimal_trajectory = None
         self.u_nom = None
@@ -178,7 +179,7 @@ class optimizer_mppi(_OptimizerBase):
             self.configure()
         eng = self.engine
         if self.cfg.predictor_type == "ODE":
-            eng.apply_pole_mass_of(self.variable_parameters)      # (predictors_customization.py:55-58)
+            eng.apply_pole_mass_of(self.variable_parameters, **self._mass_rows)      # (predictors_customization.py:55-58)
         host_state = not hasattr(s, "is_cuda")
         if (host_state and self.u_nom.is_cuda and self.noise == "philox" and self.h is None and not as_tensor
                 and not self.optimizer_logging and not self.calculate_optimal_trajectory

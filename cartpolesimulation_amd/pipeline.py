@@ -214,16 +214,34 @@ def run_schedule_groups(groups: EnvGroups, batch, seed):
     step = groups.prepare(run.s_ctrl, run.u_nom, run.cur_tp, run.cur_te, L=run.cur_L, seed=seed, Q_out=run.Q, **run._prev)
     plant = eng.prepare_plant_step(run.s, run.Q, batch.n_ctrl, period=0, **run.plant)
     groups.fork()
-    if run.m_ctrl is not None and len(np.unique(run.m_ctrl)) > 1:
-        # the controller's pole mass follows the plant's (predictor_ODE): a handle parameter read when a launch is enqueued - one
-        # library call per period instead of one for the whole run
+    per_env = run.m_env is not None
+    if per_env:
+        # a mass per experiment (harness.controller_pole_mass): every group's handle reads ITS slice of the run's [E] vector, and
+        # copies its slice of row c of the table into it on its own stream - no group waits for another
+        eng.set_pole_mass_rows(None)                          # (ScheduleRun registered the vector with group 0's handle over all envs)
+        for g_eng, (e0, e1) in zip(groups.engines, groups.slices):
+            g_eng.set_pole_mass_rows(run.m_env[e0:e1])
+
+    def set_mass(c):
+        if not per_env:
+            return run.set_controller_mass(c, groups.engines)
+        for st, (e0, e1) in zip(groups.streams, groups.slices):
+            with torch.cuda.stream(st):
+                run.m_env[e0:e1].copy_(run.m_env_tab[c, e0:e1])
+
+    if (run.m_ctrl is not None and len(np.unique(run.m_ctrl)) > 1) or (per_env and not run.m_env_constant):
+        # the controller's pole mass follows the plant's (predictor_ODE): a handle parameter read when a launch is enqueued (a vector
+        # rewritten between launches) - one library call per period instead of one for the whole run
         for c in range(run.T):
-            run.set_controller_mass(c, groups.engines)
+            set_mass(c)
             groups.run(step, plant, periods=1, offset=c, period=c)
-        run.set_controller_mass(run.T, groups.engines)
+        set_mass(run.T)
     else:
-        run.set_controller_mass(0, groups.engines)
+        set_mass(0)
         groups.run(step, plant, periods=run.T, offset=0, period=0)
     groups.run(step, plant, periods=1, offset=run.T, period=run.T, n_substeps=run.tail)   # the run's last controller call (+ trailing steps)
     groups.join()
+    if per_env:
+        for g_eng in groups.engines:
+            g_eng.set_pole_mass_rows(None)
     return dict(states=run.states, dd=run.dd, Q=run.Qs, final_state=run.s, u_nom=run.u_nom, batch=batch)

@@ -16,16 +16,26 @@ from .configs import MPPIConfig, PhysicalParameters, ode_predictor_type
 from .state_utilities import STATE_INDICES, STATE_VARIABLES, CONTROL_INPUTS, create_cartpole_state  # noqa: F401
 
 
-def _engine(horizon, dt, intermediate_steps, phys, math_mode, device, predictor_type="ODE_v0"):
+def _engine(horizon, dt, intermediate_steps, phys, math_mode, device, predictor_type="ODE_v0", **flags):
+    """``flags``: further MPPIConfig fields (per_env_pole_mass)."""
     from .engine import MPPIEngine
     cfg = MPPIConfig(num_rollouts=1, mpc_horizon=max(1, int(horizon)), mpc_timestep=float(dt),
-                     intermediate_steps=int(intermediate_steps), math_mode=math_mode, predictor_type=predictor_type)
+                     intermediate_steps=int(intermediate_steps), math_mode=math_mode, predictor_type=predictor_type, **flags)
     return MPPIEngine(1, cfg, phys, device=device)
 
 
-def _pole_length(variable_parameters, phys):
+def _per_row_flags(per_env_pole_mass):
+    return {"per_env_pole_mass": True} if per_env_pole_mass else {}
+
+
+def _pole_length(variable_parameters, phys, rows=None):
+    """``rows``: a predictor built with per_env_pole_mass reads ``L`` per row too when it has that many entries, as
+    next_state_predictor_ODE broadcasts it (predictors_customization.py:51-54); otherwise the first entry."""
     if variable_parameters is not None and hasattr(variable_parameters, "L"):
-        return float(np.asarray(variable_parameters.L).reshape(-1)[0])
+        L = variable_parameters.L
+        if rows is not None and rows > 1 and int(np.prod(np.shape(L))) == rows:
+            return L
+        return float(np.asarray(L.cpu() if hasattr(L, "cpu") else L).reshape(-1)[0])
     return phys.L
 
 
@@ -35,21 +45,27 @@ class next_state_predictor_ODE_v0:
     predictor_type = "ODE_v0"
 
     def __init__(self, dt, intermediate_steps, batch_size=1, variable_parameters=None, phys=None, math_mode="precise",
-                 device=0, **kwargs):
+                 device=0, per_env_pole_mass=False, **kwargs):
         self.phys = phys or PhysicalParameters()
         self.params = self.phys
         self.variable_parameters = variable_parameters
         self.intermediate_steps = int(intermediate_steps)
         self.t_step = float(dt / float(self.intermediate_steps))
         self.s = create_cartpole_state()
-        self._eng = _engine(1, dt, intermediate_steps, self.phys, math_mode, device, self.predictor_type)
+        self._per_row = bool(per_env_pole_mass) and self.predictor_type == "ODE"
+        self._eng = _engine(1, dt, intermediate_steps, self.phys, math_mode, device, self.predictor_type,
+                            **_per_row_flags(self._per_row))
 
     def step(self, s, Q, as_tensor=False):
         assert Q.shape[0] == s.shape[0]
         assert Q.ndim == 2
         assert s.ndim == 2
-        L = _pole_length(self.variable_parameters, self.phys)
-        self._eng.apply_pole_mass_of(self.variable_parameters)
+        if self._per_row:                       # (the row count is the batch of s)
+            L = _pole_length(self.variable_parameters, self.phys, s.shape[0])
+            self._eng.apply_pole_mass_of(self.variable_parameters, rows=s.shape[0])
+        else:
+            L = _pole_length(self.variable_parameters, self.phys)
+            self._eng.apply_pole_mass_of(self.variable_parameters)
         out = self._eng.predict(s, Q[:, :1], L=L)[:, 1]
         return out if as_tensor else out.cpu().numpy()
 
@@ -72,7 +88,7 @@ class predictor_ODE_v0:
     predictor_type = "ODE_v0"
 
     def __init__(self, horizon, dt, intermediate_steps=10, batch_size=1, variable_parameters=None, phys=None,
-                 math_mode="precise", device=0, **kwargs):
+                 math_mode="precise", device=0, per_env_pole_mass=False, **kwargs):
         self.horizon = int(horizon)
         self.dt = float(dt)
         self.intermediate_steps = int(intermediate_steps)
@@ -81,7 +97,9 @@ class predictor_ODE_v0:
         self.phys = phys or PhysicalParameters()
         self.params = self.phys
         self._math_mode, self._device = math_mode, device
-        self._eng = _engine(self.horizon, dt, intermediate_steps, self.phys, math_mode, device, self.predictor_type)
+        self._per_row = bool(per_env_pole_mass) and self.predictor_type == "ODE"
+        self._eng = _engine(self.horizon, dt, intermediate_steps, self.phys, math_mode, device, self.predictor_type,
+                            **_per_row_flags(self._per_row))
         self.next_step_predictor = SimpleNamespace(params=self.phys)
 
     def predict_core(self, initial_state, Q, as_tensor=False):
@@ -94,8 +112,13 @@ class predictor_ODE_v0:
         s0 = eng.tensor(initial_state)
         if s0.dim() == 2 and s0.shape[0] == 1 and Q.shape[0] != 1:
             s0 = s0[0]
-        eng.apply_pole_mass_of(self.variable_parameters)
-        out = eng.predict(s0, Q.contiguous(), L=_pole_length(self.variable_parameters, self.phys))
+        if self._per_row:                       # (the row count is the batch of Q)
+            eng.apply_pole_mass_of(self.variable_parameters, rows=Q.shape[0])
+            L = _pole_length(self.variable_parameters, self.phys, Q.shape[0])
+        else:
+            eng.apply_pole_mass_of(self.variable_parameters)
+            L = _pole_length(self.variable_parameters, self.phys)
+        out = eng.predict(s0, Q.contiguous(), L=L)
         return out if as_tensor else out.cpu().numpy()
 
     predict = predict_core
@@ -114,7 +137,8 @@ class predictor_ODE(predictor_ODE_v0):
 class PredictorWrapper:
     """configure / predict / predict_core / update with the attributes the in-tree callers read."""
 
-    def __init__(self, phys=None, math_mode="precise", device=0):
+    def __init__(self, phys=None, math_mode="precise", device=0, per_env_pole_mass=False):
+        self._per_row = bool(per_env_pole_mass)
         self.predictor = None
         self.predictor_config = {"predictor_type": "ODE_v0", "model_name": None, "intermediate_steps": 10}
         self.predictor_type = "ODE_v0"
@@ -149,7 +173,8 @@ class PredictorWrapper:
     def _build(self):
         cls = predictor_ODE if self.predictor_type == "ODE" else predictor_ODE_v0
         self.predictor = cls(self._horizon, self.dt, self.predictor_config["intermediate_steps"], self.batch_size,
-                             self.variable_parameters, phys=self.phys, math_mode=self._math_mode, device=self._device)
+                             self.variable_parameters, phys=self.phys, math_mode=self._math_mode, device=self._device,
+                             **_per_row_flags(self._per_row))
 
     def configure(self, batch_size, horizon, dt, predictor_specification=None, variable_parameters=None, **kwargs):
         self.update_predictor_config_from_specification(predictor_specification)

@@ -375,6 +375,8 @@ def main(argv=None):
             parameters = active_parameters(yaml.safe_load(fh)["cartpole"])
         if parameters and parameters.get("seed") is None and ("controlDisturbance" in parameters or "noise" in parameters):
             parameters["seed"] = args.seed                             # (the file's own `seed:` is empty = clock)
+        # an `m_pole:` updater may give every experiment its own mass: predictor "ODE" is then told per experiment, as the reference's is
+        cfg.per_env_pole_mass = cfg.predictor_type == "ODE" and bool(parameters and parameters.get("m_pole") is not None)
     else:
         n, h, cost = args.rollouts or 3500, args.horizon or 35, args.cost or "legacy_mppi_cartpole"
         cfg = legacy_mppi_config(num_rollouts=n, mpc_horizon=h) if cost == "legacy_mppi_cartpole" \
@@ -400,6 +402,8 @@ def main(argv=None):
         over = {k: v for k, v in (("num_rollouts", args.rollouts), ("mpc_horizon", args.horizon), ("seed", seed)) if v is not None}
         if args.cost not in (None, "legacy_mppi_cartpole"):
             over["cost_function_specification"] = args.cost
+        if args.config_root and cfg.per_env_pole_mass:
+            over["per_env_pole_mass"] = True
         ctrl = controller_mpc("CartPole", {}, control_limits=([-1.0], [1.0]), config=over, phys=phys, device=device, num_envs=n_local,
                               config_root=args.config_root)
         ctrl.configure(opt_name)

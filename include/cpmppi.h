@@ -47,7 +47,8 @@ extern "C" {
                                       per-row columns (cpmppi_recording), cpmppi_launch_info.cost_plugin, CPMPPI_ERR_IO,
                                       cpmppi_comm_info, cpmppi_groups_*.  cpmppi_abi_version() reports what a loaded library was built as;
                                    5: cpmppi_comm_set_stamped (+ cpmppi_comm_info.stamped), cpmppi_groups_comm_init / cpmppi_groups_run_gather;
-                                      a caller-given rccl_path now wins over an RCCL the process has already loaded. */
+                                      a caller-given rccl_path now wins over an RCCL the process has already loaded;
+                                      cpmppi_set_pole_mass_rows (a new entry point: no layout and no existing semantics change). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -212,10 +213,21 @@ int cpmppi_last_launch(const cpmppi_handle* h, cpmppi_launch_info* out);
 int cpmppi_set_cost_weights(cpmppi_handle* h, uint32_t cost_id, const float* cost_w, uint32_t n);
 /* The pole mass every later call of this handle computes with (config.m_pole until then): predictor_ODE takes it from
  * variable_parameters.m_pole at every step (predictors_customization.py:55-58; the simulator sends 'm_pole' with every
- * controller.step, CartPole/__init__.py:509-520).  Handle-wide (one value for all envs; the pole LENGTH is the per-env
- * attribute); launches already enqueued - and captured graphs - keep the value they were enqueued with.  This is the
+ * controller.step, CartPole/__init__.py:509-520).  Handle-wide (one value for all envs; a mass per row: cpmppi_set_pole_mass_rows
+ * below); launches already enqueued - and captured graphs - keep the value they were enqueued with.  This is the
  * CONTROLLER's belief (the simulator sends m_pole_for_controller): the plant of cpmppi_plant_advance* keeps config.m_pole. */
 int cpmppi_set_pole_mass(cpmppi_handle* h, float m_pole);
+/* Per-row pole mass the ODE predictor computes with: m_pole[n], DEVICE pointer, caller-owned, read by every later launch
+ * of this handle where that call's L would be indexed (env for step / step_gather / groups / rollout_cost / rollout_cost_grad /
+ * step_host, row for predict).  NULL (n ignored) returns to the handle's scalar (cpmppi_set_pole_mass).  A call with more
+ * rows than n fails with CPMPPI_ERR_BAD_ARG and launches nothing.  Refused (BAD_ARG) on a handle whose ode_predictor is
+ * ODE_v0: predictor_ODE_v0 never reads the attribute.  GRU steps ignore it.  The plant keeps its own mass.
+ * next_state_predictor_ODE broadcasts variable_parameters.m_pole per row exactly as it does L (predictors_customization.py:51-64);
+ * a row computes bit for bit what a handle whose scalar is that row's mass computes.  A misaligned pointer is refused (BAD_ARG).
+ * Only the POINTER is taken: launches already enqueued, and captured graphs, keep the pointer they were enqueued with and read the
+ * VALUES when they run - a caller may rewrite the array between launches (stream-ordered) without calling this again.  Each handle
+ * of an env group is given the array offset by the group's first env. */
+int cpmppi_set_pole_mass_rows(cpmppi_handle* h, const float* m_pole, uint32_t n);
 
 /* a17 — device sampler: knots ~ sigma * N(0,1) from Philox4x32-10 keyed by (seed), counter (rollout, env, knot pair,
  * offset); writes knots[E,N,P] and/or the interpolated delta_u[E,N,H] (either pointer may be NULL).
@@ -381,7 +393,8 @@ int cpmppi_plant_advance_record(cpmppi_handle* h, uint32_t E, float* s, const fl
  * period_dev: c = *period_dev - 1, the device step counter of cpmppi_step_args.offset_dev (already advanced by the step); a
  * counter that is still 0 advances the plant from table row 0 WITHOUT recording or publishing.  Any log / table / out pointer may
  * be NULL.  The pole MASS the controller computes with is
- * the handle's (config.m_pole / cpmppi_set_pole_mass), whatever the plant's: a per-env controller-side mass does not exist. */
+ * the handle's (config.m_pole / cpmppi_set_pole_mass, or per env cpmppi_set_pole_mass_rows), whatever the plant's: this call neither
+ * reads nor publishes it (the caller copies the row of its own controller-mass table into the registered array between periods). */
 typedef struct {
   uint32_t E;
   float* s;                             /* [E,6] in / out */

@@ -1,0 +1,438 @@
+"""GPU: the per-row controller-side pole mass of predictor_type "ODE" (cpmppi_set_pole_mass_rows) through every kernel that
+integrates that predictor - the predictor seam against the reference's own next_state_predictor_ODE called with L[B] and m_pole[B]
+(tests/golden/ode_pole_mass.npz), the fused step, the cost-only launch and the adjoint against the handle's scalar mass BIT FOR BIT
+(a row computes what a handle with that scalar computes) and against the oracles, the C entry point's refusals, the device loop of
+the data generator with a mass schedule per experiment, and the reference-shaped seams.
+
+Tolerances are the project's existing ones: the band rule of tests/test_gpu_ode_predictor.py (restated below: the oracle's
+realisations need the row's mass), parity_util's cost / control rules with rule=PREDICTOR_ODE, tests/test_gpu_grad.py's gradient
+bound."""
+import ctypes as C
+import os
+from dataclasses import replace
+from types import SimpleNamespace
+
+import numpy as np
+import pytest
+from numpy.random import SFC64, Generator
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+from oracle import oracle_np as O  # noqa: E402  (the checker)
+from oracle import oracle_c as OC  # noqa: E402
+import parity_util as PU  # noqa: E402
+
+f32 = np.float32
+LANE_MODES = [("precise", 1), ("fast", 1), ("fast", 2)]
+M_LO, M_HI = 0.015, 0.15                 # cartpole_physical_parameters.yml: the `m_pole:` updater's range
+
+
+def engine(E, N, H, **kw):
+    from cartpolesimulation_amd.engine import MPPIEngine
+    from cartpolesimulation_amd.configs import MPPIConfig
+    return MPPIEngine(E, MPPIConfig(num_rollouts=N, mpc_horizon=H, predictor_type="ODE", **kw))
+
+
+@pytest.fixture(scope="module")
+def g(golden_dir):
+    return np.load(os.path.join(golden_dir, "ode_pole_mass.npz"))
+
+
+def one_up(a):
+    return np.nextafter(np.asarray(a, f32), f32(np.inf)).astype(f32)
+
+
+def f32_realisations(s0, Q, L, m_pole):
+    """tests/test_gpu_ode_predictor.py's f32_realisations with a mass per row: the C oracle holds ONE mass per configuration, so
+    every row is run under its own.  -> list of [B, H+1, 6]: mode C, mode A from an initial state one float32 ulp away (five columns),
+    under controls one ulp up, with float64 substeps, and three runs with every sin / cos moved to a neighbouring float32."""
+    B, H = Q.shape
+    ocfg = O.MPPIConfig(N=1, H=H, integrator="ODE")
+    fma = OC.fma_lib()
+    per_row = []
+    for i in range(B):
+        p = replace(O.DEFAULT_PARAMS, m_pole=f32(m_pole[i]))
+        cfg, s, q, Li = OC.make_config(ocfg, p), np.asarray(s0[i:i + 1], f32), Q[i:i + 1], L[i:i + 1]
+        outs = [OC.predict(cfg, s, q, L=Li, use_lib=fma)] if fma is not None else []
+        for col in (O.ANGLED_IDX, O.POSITIOND_IDX, O.POSITION_IDX, O.ANGLE_COS_IDX, O.ANGLE_SIN_IDX):
+            sp = s.copy()
+            sp[:, col] = one_up(sp[:, col])
+            outs.append(OC.predict(cfg, sp, q, L=Li))
+        outs.append(OC.predict(cfg, s, one_up(q), L=Li))
+        outs.append(OC.predict(OC.make_config(ocfg, p, mode="f64sub"), s, q, L=Li))
+        try:
+            for seed in (1, 2, 3):
+                OC.set_trig_jitter(seed)
+                outs.append(OC.predict(cfg, s, q, L=Li))
+        finally:
+            OC.set_trig_jitter(0)
+        per_row.append(outs)
+    return [np.concatenate([per_row[i][j] for i in range(B)]) for j in range(len(per_row[0]))]
+
+
+@pytest.fixture(scope="module")
+def realisations(g):
+    """Computed once for both fixtures, shared by the tests that need them, left unchanged."""
+    return {"kat": [t[:, 1] for t in f32_realisations(g["kat/s"], g["kat/Q"][:, None], g["kat/L"], g["kat/m_pole"])],
+            "roll": f32_realisations(g["roll/s0"], g["roll/Q"], g["roll/L"], g["roll/m_pole"])}
+
+
+def state_diff(a, b):
+    """a - b with the angle column compared on the circle (atan2 returns either of +-pi for the same point)."""
+    d = np.asarray(a, np.float64) - np.asarray(b, np.float64)
+    d[..., O.ANGLE_IDX] = np.angle(np.exp(1j * d[..., O.ANGLE_IDX]))
+    return d
+
+
+def assert_states_in_band(out, ref, alts, what, scale=1.0):
+    """The rule of tests/test_gpu_ode_predictor.py: every element inside band + the scatter of the oracle's rounding-level
+    variations; a row on which those disagree by more than a quarter of the band is rounding-sensitive and joins the flagged bucket
+    (capped by parity_util, and never beyond band + twice the scatter); clear rows: none outside."""
+    gap = np.zeros(np.asarray(ref).shape)
+    for a in alts:
+        gap = np.maximum(gap, np.abs(state_diff(a, ref)))
+    d = np.abs(state_diff(out, ref))
+    rows = lambda m: m.reshape(m.shape[0], -1).any(axis=1)      # noqa: E731
+    sensitive = rows(gap > 0.25 * PU.band(ref, scale))
+    PU._check(rows(d > PU.band(ref, scale) + gap), sensitive, what)
+    assert not rows(d > PU.band(ref, scale) + 2.0 * gap).any(), f"{what}: a row beyond band + twice the oracle's scatter"
+
+
+def random_envs(E, H, seed):
+    rng = Generator(SFC64(seed))
+    s0 = np.stack([O.create_cartpole_state(rng.uniform(-0.8, 0.8), rng.uniform(-3, 3), rng.uniform(-0.12, 0.12),
+                                           rng.uniform(-0.3, 0.3)) for _ in range(E)])
+    tp = rng.uniform(-0.08, 0.08, E).astype(f32)
+    Lv = rng.uniform(0.25, 0.45, E).astype(f32)
+    m = rng.uniform(M_LO, M_HI, E).astype(f32)
+    u0 = (0.3 * rng.standard_normal((E, H))).astype(f32)
+    return s0, tp, Lv, m, u0, rng
+
+
+def philox_step(eng, s0, u0, tp, Lv, seed=11, offset=4):
+    E = s0.shape[0]
+    un, S = eng.tensor(u0.copy()), eng.empty(E, eng.N)
+    Q, _ = eng.step(s0, un, tp, np.ones(E, f32), L=Lv, seed=seed, offset=offset, env_offset=0, S_out=S)
+    return Q.cpu().numpy(), un.cpu().numpy(), S.cpu().numpy()
+
+
+# ---- 1 ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("math_mode,rpl", LANE_MODES)
+def test_predict_vs_the_reference(g, realisations, math_mode, rpl):
+    """cpmppi_predict with L[B] and the registered m_pole[B] against the reference's own class: single control steps to a tenth of
+    the band, 20-step rollouts (upright and hanging rows) to band + the oracle's scatter.  The handle's default mass would not pass."""
+    eng = engine(1, 64, 20, math_mode=math_mode, rollouts_per_lane=rpl)
+    s, Q, L, m, ref = (g[f"kat/{k}"] for k in ("s", "Q", "L", "m_pole", "s_next"))
+    eng.set_pole_mass_rows(m)
+    out = eng.predict(s, Q[:, None], L=L)[:, 1].cpu().numpy()
+    assert_states_in_band(out, ref, realisations["kat"], f"kat ({math_mode})", scale=0.1)
+    s0, Qr, Lr, mr, traj_ref = (g[f"roll/{k}"] for k in ("s0", "Q", "L", "m_pole", "traj"))
+    eng.set_pole_mass_rows(mr)
+    traj = eng.predict(s0, Qr, L=Lr).cpu().numpy()
+    assert traj.shape == traj_ref.shape and np.array_equal(traj[:, 0], traj_ref[:, 0])
+    assert_states_in_band(traj, traj_ref, realisations["roll"], f"roll ({math_mode})")
+    eng.set_pole_mass_rows(None)                                   # the handle's 0.087 for every row: another trajectory
+    assert np.abs(state_diff(eng.predict(s, Q[:, None], L=L)[:, 1].cpu().numpy(), ref)).max() > 1e-3
+    assert np.abs(state_diff(eng.predict(s0, Qr, L=Lr).cpu().numpy(), traj_ref)).max() > 1e-3
+    eng.close()
+
+
+# ---- 2 ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("math_mode,rpl", LANE_MODES)
+def test_equal_rows_are_the_scalar(math_mode, rpl):
+    E, N, H = 3, 200, 12                                           # (a ragged last block)
+    eng = engine(E, N, H, math_mode=math_mode, rollouts_per_lane=rpl)
+    s0, tp, Lv, _, u0, _ = random_envs(E, H, 5)
+    m = f32(0.0431)
+    eng.set_pole_mass(m)
+    scalar = philox_step(eng, s0, u0, tp, Lv)
+    eng.set_pole_mass(0.087)                                       # (the rows, not the scalar, must carry the mass)
+    eng.set_pole_mass_rows(np.full(E, m, f32))
+    rows = philox_step(eng, s0, u0, tp, Lv)
+    for a, b, what in zip(rows, scalar, ("Q", "u_nom", "S")):
+        assert np.array_equal(a, b), what
+    eng.set_pole_mass_rows(None)
+    assert not np.array_equal(philox_step(eng, s0, u0, tp, Lv)[2], scalar[2])
+    eng.close()
+
+
+# ---- 3 ----------------------------------------------------------------------------------------------------------------------
+def _rows_match_scalar_launches(eng, s0, u0, tp, Lv, m, envs):
+    eng.set_pole_mass_rows(m)
+    rows = philox_step(eng, s0, u0, tp, Lv)
+    variant = eng.last_launch()["build_variant"]
+    eng.set_pole_mass_rows(None)
+    for e in envs:                                                 # the same launch (env index, Philox key) under the scalar m[e]
+        eng.set_pole_mass(m[e])
+        one = philox_step(eng, s0, u0, tp, Lv)
+        assert eng.last_launch()["build_variant"] == variant
+        for a, b, what in zip(rows, one, ("Q", "u_nom", "S")):
+            assert np.array_equal(a[e], b[e]), (what, e)
+    other = (envs[0] + 1) % len(m)
+    assert not np.array_equal(rows[2][other], one[2][other])       # ... and only env e agrees with the scalar m[e]
+    return variant
+
+
+@pytest.mark.parametrize("math_mode,rpl", LANE_MODES)
+def test_rows_are_independent(math_mode, rpl):
+    E, N, H = 5, 200, 12
+    eng = engine(E, N, H, math_mode=math_mode, rollouts_per_lane=rpl)
+    s0, tp, Lv, _, u0, _ = random_envs(E, H, 6)
+    m = np.asarray([0.015, 0.05, 0.087, 0.12, 0.15], f32)
+    _rows_match_scalar_launches(eng, s0, u0, tp, Lv, m, range(E))
+    eng.close()
+
+
+@pytest.mark.parametrize("math_mode,rpl", LANE_MODES)
+def test_rows_are_independent_in_the_throughput_build(math_mode, rpl):
+    """The sizes at which tests/test_gpu_ode_predictor.py's test_latency_and_throughput_builds_agree_bit_for_bit selects the
+    throughput build: 100 envs with one rollout per lane, 300 with two (N = 1024)."""
+    E, N, H = (300 if rpl == 2 else 100), 1024, 20
+    eng = engine(E, N, H, math_mode=math_mode, rollouts_per_lane=rpl)
+    s0, tp, Lv, m, u0, _ = random_envs(E, H, 7)
+    variant = _rows_match_scalar_launches(eng, s0, u0, tp, Lv, m, (0, E // 2 + 1, E - 1))
+    assert variant == 1
+    eng.close()
+
+
+# ---- 4 ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("math_mode,rpl", LANE_MODES)
+def test_fused_step_vs_the_c_oracle(math_mode, rpl):
+    """A delta_u buffer, per-env L, targets and MASS; the C oracle run per env under that env's mass."""
+    E, N, H = 4, 1000, 30
+    eng = engine(E, N, H, math_mode=math_mode, rollouts_per_lane=rpl)
+    s0, tp, Lv, _, u0, rng = random_envs(E, H, 41)
+    m = np.asarray([0.02, 0.05, 0.12, 0.15], f32)
+    te = np.ones(E, f32)
+    du = np.stack([O.sample_delta_u(rng, N, H, np.float64(eng.mppi.sigma)) for _ in range(E)])
+    eng.set_pole_mass_rows(m)
+    un, S = eng.tensor(u0.copy()), eng.empty(E, N)
+    Q, _ = eng.step(s0, un, tp, te, L=Lv, delta_u=du, S_out=S)
+    un, S, Q = un.cpu().numpy(), S.cpu().numpy(), Q.cpu().numpy()
+    mp = eng.mppi
+    ocfg = O.MPPIConfig(N=N, H=H, cc_weight=mp.cc_weight, R=mp.R, LBD=mp.LBD, NU=mp.NU, cost_id=O.COST_QBGM, integrator="ODE")
+    moved = 0.0
+    for e in range(E):
+        sl = slice(e, e + 1)
+        r = PU.c_oracle_step_with_flags(ocfg, s0[sl], u0[sl], du[sl], tp[sl], te[sl], L=Lv[sl],
+                                        params=replace(O.DEFAULT_PARAMS, m_pole=m[e]), probes=True)
+        PU.assert_costs(S[sl], r["S_a"], None, np.zeros_like(r["flags"]), f"env {e} costs", S_alt=r["S_alt"], flag_sensitive=True,
+                        rule=PU.PREDICTOR_ODE)
+        PU.assert_controls(un[sl], r["u_a"], None, f"env {e} u_new", u_alt=r["u_alt"])
+        np.testing.assert_allclose(Q[sl], r["Q_a"], atol=1e-4 + float(PU.envelope(r["u_a"], *r["u_alt"]).max()))
+        d = PU.c_oracle_step_with_flags(ocfg, s0[sl], u0[sl], du[sl], tp[sl], te[sl], L=Lv[sl])
+        moved = max(moved, float((np.abs(d["S_a"] - r["S_a"]) / np.abs(r["S_a"])).max()))
+    assert moved > 1e-3                                            # the default mass would not have passed
+    eng.close()
+
+
+# ---- 5 ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("math_mode,rpl", LANE_MODES)
+def test_cost_only_and_adjoint_launches(math_mode, rpl):
+    """cpmppi_rollout_cost and cpmppi_rollout_cost_grad (FAST: the adjoint's arithmetic) with rows: every env equals the launch under
+    that env's scalar bit for bit; one env's gradient against float64 autograd of the oracle with that env's mass (the bound of
+    tests/test_gpu_grad.py)."""
+    from oracle import oracle_torch as OT
+    E, N, H = 3, 64, 10
+    eng = engine(E, N, H, math_mode=math_mode, rollouts_per_lane=rpl)
+    s0, tp, Lv, _, _, rng = random_envs(E, H, 21)
+    m = np.asarray([0.02, 0.14, 0.05], f32)
+    te = np.ones(E, f32)
+    Qin = (0.5 * rng.standard_normal((E, N, H))).astype(f32)
+    Qin[:, :4] *= 3.0                                              # some controls beyond the limits
+    grad = math_mode == "fast"
+    eng.set_pole_mass_rows(m)
+    S_rows = eng.rollout_cost(s0, Qin, tp, te, L=Lv).cpu().numpy()
+    Sg_rows, G_rows = (x.cpu().numpy() for x in eng.rollout_cost_grad(s0, Qin, tp, te, L=Lv)) if grad else (None, None)
+    eng.set_pole_mass_rows(None)
+    for e in range(E):
+        eng.set_pole_mass(m[e])
+        assert np.array_equal(eng.rollout_cost(s0, Qin, tp, te, L=Lv).cpu().numpy()[e], S_rows[e]), e
+        if grad:
+            Sg, G = (x.cpu().numpy() for x in eng.rollout_cost_grad(s0, Qin, tp, te, L=Lv))
+            assert np.array_equal(Sg[e], Sg_rows[e]) and np.array_equal(G[e], G_rows[e]), e
+    if grad:
+        e = 1
+        p = replace(O.DEFAULT_PARAMS, m_pole=m[e])
+        J, gr = OT.cost_and_grad(O.COST_QBGM, s0[e], Qin[e], tp[e], 1.0, L=Lv[e], p=p, integrator="ODE")
+        np.testing.assert_allclose(Sg_rows[e], J, rtol=5e-4)
+        assert np.all(G_rows[e][np.abs(Qin[e]) > 1.0] == 0.0)
+        traj = O.predict_core(s0[e], np.clip(Qin[e], -1, 1), L=Lv[e], p=p, integrator="ODE")
+        scale = np.abs(gr).max(axis=1, keepdims=True) + 1e-6
+        err = (np.abs(G_rows[e] - gr) / scale).max(axis=1)
+        flagged = PU.flag_indicators(traj, "qbgm", tp[e]) | (np.abs(np.abs(Qin[e]) - 1.0) < 1e-3).any(axis=1)
+        assert not ((err >= 5e-4) & ~flagged).any() and np.median(err) < 1e-4 and not ((err >= 2e-3) & flagged).any()
+        _, g0 = OT.cost_and_grad(O.COST_QBGM, s0[e], Qin[e], tp[e], 1.0, L=Lv[e], integrator="ODE")
+        assert (np.abs(g0 - gr) / scale).max() > 5e-3              # the default mass has another gradient
+    eng.close()
+
+
+# ---- 6 ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("math_mode,rpl", LANE_MODES)
+def test_c_level_refusals(math_mode, rpl):
+    """cpmppi_set_pole_mass_rows straight through ctypes: fewer masses than a launch has rows, a misaligned pointer and a
+    predictor_ODE_v0 handle are CPMPPI_ERR_BAD_ARG with a text, nothing is launched; NULL restores the scalar result bit for bit."""
+    from cartpolesimulation_amd import _lib as L
+    from cartpolesimulation_amd.configs import MPPIConfig
+    from cartpolesimulation_amd.engine import MPPIEngine
+    E, N, H = 3, 200, 12
+    eng = engine(E, N, H, math_mode=math_mode, rollouts_per_lane=rpl)
+    lib, h = eng.lib, eng._h
+    s0, tp, Lv, m, u0, rng = random_envs(E, H, 8)
+    scalar = philox_step(eng, s0, u0, tp, Lv)
+    md = eng.tensor(m)
+    err = lambda: lib.cpmppi_last_error(h).decode()      # noqa: E731
+    s_d, tp_d, te_d = eng.tensor(s0), eng.tensor(tp), eng.tensor(np.ones(E, f32))
+    un, Q, S = eng.tensor(u0.copy()), eng.zeros(E), eng.zeros(E, N)
+    inputs, traj, grad = eng.zeros(E, N, H), eng.zeros(E, H + 1, 6), eng.zeros(E, N, H)
+
+    def step():
+        a = L.cpmppi_step_args()
+        a.E, a.s0, a.u_nom, a.target_position, a.target_equilibrium = E, s_d.data_ptr(), un.data_ptr(), tp_d.data_ptr(), te_d.data_ptr()
+        a.noise_kind, a.seed, a.offset, a.Q_out, a.S_out = L.NOISE_PHILOX, 11, 4, Q.data_ptr(), S.data_ptr()
+        return lib.cpmppi_step(h, C.byref(a), None)
+
+    assert lib.cpmppi_set_pole_mass_rows(h, C.c_void_p(md.data_ptr()), E - 1) == 0          # two masses, launches of three rows
+    assert step() == -1 and "2 pole masses" in err() and "cpmppi_step" in err()
+    assert lib.cpmppi_predict(h, E, H, s_d.data_ptr(), un.data_ptr(), None, traj.data_ptr(), None) == -1 and "cpmppi_predict" in err()
+    assert lib.cpmppi_rollout_cost(h, E, s_d.data_ptr(), inputs.data_ptr(), tp_d.data_ptr(), te_d.data_ptr(), None, S.data_ptr(), None) == -1
+    assert "cpmppi_rollout_cost" in err()
+    if math_mode == "fast":
+        assert lib.cpmppi_rollout_cost_grad(h, E, s_d.data_ptr(), inputs.data_ptr(), tp_d.data_ptr(), te_d.data_ptr(), None, None,
+                                            S.data_ptr(), grad.data_ptr(), None) == -1 and "cpmppi_rollout_cost_grad" in err()
+    assert lib.cpmppi_set_pole_mass_rows(h, C.c_void_p(md.data_ptr() + 2), E) == -1 and "misaligned" in err()
+    assert lib.cpmppi_set_pole_mass_rows(h, C.c_void_p(md.data_ptr()), 0) == -1 and "n must be" in err()
+    v0 = MPPIEngine(E, MPPIConfig(num_rollouts=N, mpc_horizon=H, math_mode=math_mode))
+    assert lib.cpmppi_set_pole_mass_rows(v0._h, C.c_void_p(md.data_ptr()), E) == -1
+    assert "predictor_ODE_v0" in lib.cpmppi_last_error(v0._h).decode()
+    assert lib.cpmppi_set_pole_mass_rows(v0._h, None, 0) == 0                                 # (clearing is always allowed)
+    v0.close()
+    torch.cuda.synchronize()
+    for t, what in ((Q, "Q"), (S, "S"), (traj, "traj"), (grad, "grad")):
+        assert not t.any().item(), what                                                       # outputs untouched
+    assert torch.equal(un, eng.tensor(u0))
+    a2 = engine(E, N, H, math_mode=math_mode, rollouts_per_lane=rpl)
+    a2.set_pole_mass_rows(md)
+    rows = philox_step(a2, s0, u0, tp, Lv)
+    assert not np.array_equal(rows[2], scalar[2])
+    assert lib.cpmppi_set_pole_mass_rows(a2._h, None, 123) == 0                               # NULL (n ignored): the scalar again
+    a2._m_rows = None
+    for a, b, what in zip(philox_step(a2, s0, u0, tp, Lv), scalar, ("Q", "u_nom", "S")):
+        assert np.array_equal(a, b), what
+    a2.close()
+    eng.close()
+
+
+# ---- 7 ----------------------------------------------------------------------------------------------------------------------
+RANDOM_M = dict(init_value="random", change_every_x_seconds=0.04, mode="random", range_random=[M_LO, M_HI], range_clip=None,
+                increment=0.002, reset_every_x_seconds="inf")
+SWITCHING_RANDOM = dict(mode="switching_random", change_to_on_after_x_seconds_off=0.06, change_to_off_after_x_seconds_on=0.08)
+
+
+def _batch(E, prm):
+    from cartpolesimulation_amd import schedule as SC
+    cfg = dict(seed=35, length_of_experiment=0.3, keep_target_equilibrium_x_seconds_up=0.1, turning_points=dict(track_relative_complexity=12),
+               random_initial_state=dict(init_limits=dict(angle=[0.0, 20.0], angleD=40.0, position=0.4, positionD=0.2)))
+    return SC.apply_parameter_schedule(SC.RandomExperimentSetter(cfg).draw(E, 79, stride=1), prm, seed=5)
+
+
+def _by_hand(eng, b, masses):
+    """The loop paced by hand: masses [T+1, E] (set_pole_mass_rows before every controller call) or None (the handle's 0.087)."""
+    E, H = b.E, eng.H
+    s, u, out = eng.tensor(b.s0).clone(), eng.zeros(E, H), []
+    m_tab = eng.tensor(b.m_pole_table)
+    for c in range(b.n_periods + 1):
+        row = int(b.rows_at(c * b.n_ctrl))
+        eng.set_pole_mass_rows(None if masses is None else masses[c])
+        Q, _ = eng.step(s, u, b.target_position[row].astype(f32), b.target_equilibrium[row].astype(f32), seed=7, offset=c)
+        out.append(Q.cpu().numpy().copy())
+        if c < b.n_periods:
+            eng.plant_step(s, Q, b.n_ctrl, dt_sim=b.dt_simulation, period=c, period_steps=b.n_ctrl, m_pole_table=m_tab)
+    eng.set_pole_mass_rows(None)
+    return np.stack(out)
+
+
+@pytest.mark.parametrize("math_mode,rpl", LANE_MODES)
+@pytest.mark.parametrize("groups", [1, 2])
+def test_device_loop_with_a_mass_schedule_per_experiment(groups, math_mode, rpl):
+    """`m_pole: mode random, init_value random` under a 'switching_random' informer: the device loop (one handle, or two env groups on
+    their own streams) hands every experiment's controller ITS mass - bit for bit the loop paced by hand, far from a controller left
+    at 0.087, which is what the same batch gives without the flag (today's behaviour)."""
+    from cartpolesimulation_amd.harness import BatchedCartPoleExperiment, ScheduleRun, controller_pole_mass
+    from cartpolesimulation_amd.pipeline import EnvGroups, run_schedule_groups
+    E, N, H = 4, 512, 20
+    b = _batch(E, dict(m_pole=RANDOM_M, inform_controller_about_parameters_change=SWITCHING_RANDOM))
+    kw = dict(math_mode=math_mode, rollouts_per_lane=rpl)
+    eng = engine(E, N, H, per_env_pole_mass=True, **kw)
+    _, m_env = controller_pole_mass(b, per_env=True)
+    assert m_env.shape == (b.n_periods + 1, E) and not (m_env == m_env[:1]).all() and not (m_env == m_env[:, :1]).all()
+
+    def loop(e, batch, graph=False):
+        if groups == 1:
+            return BatchedCartPoleExperiment(e, seed=7).run_schedule(batch, graph=graph)["Q"].cpu().numpy()
+        eg = EnvGroups(E, e.mppi, groups)
+        try:
+            res = run_schedule_groups(eg, batch, 7)
+            torch.cuda.synchronize()
+            return res["Q"].cpu().numpy()
+        finally:
+            eg.close()
+
+    Q_loop = loop(eng, b)
+    assert eng._m_rows is None                                     # the run leaves the handle without rows
+    assert np.array_equal(Q_loop, _by_hand(eng, b, m_env))
+    uninformed = _by_hand(eng, b, None)
+    assert np.abs(Q_loop - uninformed).max() > 1e-3
+    off = engine(E, N, H, **kw)                                    # flag off: the controller keeps the handle's mass
+    assert ScheduleRun(off, b, 7).m_env is None and np.array_equal(loop(off, b), uninformed)
+    off.close()
+    if groups == 1:
+        with pytest.raises(ValueError, match="per-experiment pole-mass table"):
+            BatchedCartPoleExperiment(eng, seed=7).run_schedule(b, graph=True)          # a time-varying mass cannot be captured
+        eng.set_pole_mass_rows(None)
+        const = _batch(E, dict(m_pole=dict(RANDOM_M, mode="constant")))
+        launched = loop(eng, const)
+        assert np.array_equal(loop(eng, const, graph=True), launched)
+        _, m_const = controller_pole_mass(const, per_env=True)
+        assert np.array_equal(launched, _by_hand(eng, const, m_const)) and np.abs(launched - _by_hand(eng, const, None)).max() > 1e-3
+    eng.close()
+
+
+# ---- 8 ----------------------------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("math_mode,rpl", LANE_MODES)
+def test_seams(g, realisations, math_mode, rpl):
+    """predictor_ODE.predict_core with variable_parameters.m_pole[B] and .L[B] gives the reference's rollouts (the rule of the
+    predict test); controller_mpc(config=dict(per_env_pole_mass=True)) with `mppi` and with the shipped pairing `rpgd`, three envs
+    with their own masses arriving as the simulator's 'm_pole' attribute, equals the same controller whose engine was handed the
+    rows directly, bit for bit."""
+    from cartpolesimulation_amd.controller_mpc import controller_mpc
+    from cartpolesimulation_amd.predictors import predictor_ODE
+    s0, Qr, Lr, mr, traj_ref = (g[f"roll/{k}"] for k in ("s0", "Q", "L", "m_pole", "traj"))
+    vp = SimpleNamespace(L=Lr, m_pole=mr)
+    pred = predictor_ODE(Qr.shape[1], 0.02, 10, batch_size=len(mr), variable_parameters=vp, math_mode=math_mode, per_env_pole_mass=True)
+    assert_states_in_band(pred.predict_core(s0, Qr[:, :, None]), traj_ref, realisations["roll"], f"predictor_ODE ({math_mode})")
+    E = 3
+    s, tp, Lv, m, _, _ = random_envs(E, 12, 9)
+    attrs = {"target_position": tp, "target_equilibrium": np.ones(E, f32), "L": Lv}
+
+    def controller(name, **more):
+        c = controller_mpc("CartPole", dict(attrs), control_limits=(np.array([-1.0]), np.array([1.0])), num_envs=E,
+                           config=dict(per_env_pole_mass=True, mpc_horizon=12, seed=3, math_mode=math_mode, **more))
+        c.configure(optimizer_name=name, predictor_specification="ODE")
+        assert c.optimizer.cfg.per_env_pole_mass and c.optimizer.cfg.predictor_type == "ODE"
+        return c
+
+    for name, more in (("mppi", dict(num_rollouts=256)), ("rpgd", dict(num_rollouts=16))):
+        if name == "rpgd" and math_mode != "fast":
+            continue                                               # (the adjoint is written for the FAST arithmetic)
+        a, b_, d = controller(name, **more), controller(name, **more), controller(name, **more)
+        qa = a.step(s, 0.0, {"m_pole": m})
+        assert a.optimizer.engine._m_rows is not None and a.optimizer.engine._m_rows.numel() == E
+        b_.optimizer.engine.set_pole_mass_rows(m)                  # the engine-level call; no 'm_pole' attribute
+        qb = b_.step(s, 0.0, {})
+        qd = d.step(s, 0.0, {})                                    # the default mass
+        assert qa.shape == (E, 1) and np.array_equal(qa, qb) and not np.array_equal(qa, qd), name
+        qa2 = a.step(s, 0.02, {"m_pole": np.full(E, 0.087, f32)})  # a uniform attribute: the handle's scalar, rows cleared
+        assert a.optimizer.engine._m_rows is None and np.isfinite(qa2).all()
