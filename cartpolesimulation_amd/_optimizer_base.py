@@ -50,10 +50,6 @@ class _OptimizerBase:
         self.logging_values = {}
         self.engine = None
 
-    def _take_engine_flags(self, kwargs):
-        """The MPPIConfig switches that are no optimizer's own keyword (every constructor ends in **kwargs): per_env_pole_mass."""
-        self.cfg.per_env_pole_mass = bool(kwargs.get("per_env_pole_mass", False))
-
     # -- configure ------------------------------------------------------------------------------------------------
     def configure(self, dt=None, predictor_specification=None, num_envs=None, **kwargs):
         self._configure_problem(dt, predictor_specification, num_envs)
@@ -79,7 +75,7 @@ class _OptimizerBase:
     # -- one control step -----------------------------------------------------------------------------------------
     @property
     def _mass_rows(self):
-        """apply_pole_mass_of's row count: a per-row pole mass has one entry per env."""
+        """apply_pole_mass_of's row count, one entry per env (handed over only with the flag: an engine without it takes none)."""
         return {"rows": self.num_envs} if self.cfg.per_env_pole_mass else {}
 
     def _attributes(self, E):

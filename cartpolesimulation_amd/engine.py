@@ -41,11 +41,21 @@ def _same_shape(**tensors):
 _IN_PLACE = " (it is updated in place)"
 
 
+def gpu_device(device):
+    """``device`` (an index, a name or a torch.device) as the torch.device of a GPU; refused where PyTorch-ROCm sees none."""
+    if not torch.cuda.is_available():
+        raise RuntimeError("cartpolesimulation_amd needs an MI355X (gfx950) visible to PyTorch-ROCm; there is no CPU fallback.")
+    return torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
+
+
 class MPPIEngine:
+    # what the methods read and no constructor argument sets (here, so that from_handle and a handle-less stand-in have them too)
+    _h, _borrowed = None, False                                 # from_handle: somebody else destroys the handle
+    _fixed_stream = _fixed_stream_obj = None                    # use_stream: the raw handle / the torch stream (keeps it alive)
+    _m_rows = _m_rows_own = None                                # set_pole_mass_rows: the registered tensor / the engine's own buffer
+    _m_pole_obj = None                                          # apply_pole_mass_of: the scalar object last applied
+
     def __init__(self, E, mppi: MPPIConfig = None, phys: PhysicalParameters = None, device=0):
-        if not torch.cuda.is_available():
-            raise RuntimeError("cartpolesimulation_amd needs an MI355X (gfx950) visible to PyTorch-ROCm; "
-                               "there is no CPU fallback.")
         self._init_common(E, mppi, phys, device)
         self._h = C.c_void_p()
         rc = self.lib.cpmppi_create(C.byref(self._cfg), self.device.index, C.byref(self._h))
@@ -63,20 +73,19 @@ class MPPIEngine:
         return self
 
     def _init_common(self, E, mppi, phys, device):
+        self.device = gpu_device(device)
         self.lib = _L.load()
         self.mppi = mppi or MPPIConfig()
         self.phys = phys or PhysicalParameters()
-        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
         self.E, self.N, self.H = int(E), int(self.mppi.num_rollouts), int(self.mppi.mpc_horizon)
         self.P = self.mppi.num_knots
         self._cfg = build_c_config(self.E, self.mppi, self.phys)
         self._m_pole = float(np.float32(self.phys.m_pole))
-        self._m_rows = self._m_rows_own = None                  # set_pole_mass_rows: the registered tensor / the engine's own buffer
 
     # ------------------------------------------------------------------ plumbing
     def close(self):
-        if getattr(self, "_h", None) and self._h.value:
-            if not getattr(self, "_borrowed", False):
+        if self._h is not None and self._h.value:
+            if not self._borrowed:
                 self.lib.cpmppi_destroy(self._h)
             self._h = C.c_void_p()
 
@@ -92,14 +101,20 @@ class MPPIEngine:
 
     def use_stream(self, stream):
         """Enqueue every later call of this engine on `stream` (a torch.cuda.Stream; None = torch's current stream again) -
-        env groups that run side by side each keep their own stream (pipeline.py) without a stream context per call."""
+        env groups that run side by side each keep their own stream (pipeline.py) without a stream context per call.
+        -> the stream it was fixed to before (None: none), for a caller that puts it back."""
+        previous = self._fixed_stream_obj
         self._fixed_stream = None if stream is None else C.c_void_p(stream.cuda_stream)
-        self._fixed_stream_obj = stream                              # (keeps it alive)
+        self._fixed_stream_obj = stream
+        return previous
+
+    def launch_stream(self):
+        """The torch stream this engine's launches go to: the fixed one of `use_stream`, else the device's current stream."""
+        return self._fixed_stream_obj if self._fixed_stream_obj is not None else torch.cuda.current_stream(self.device)
 
     def _stream(self):
-        fixed = getattr(self, "_fixed_stream", None)
-        if fixed is not None:
-            return fixed
+        if self._fixed_stream is not None:
+            return self._fixed_stream
         # the caller's current stream as a raw handle (torch.cuda.current_stream() builds a Stream object: ~5 us per call,
         # three calls per control step at the host seam)
         raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
@@ -125,6 +140,15 @@ class MPPIEngine:
         Q = self.tensor(Q)
         return Q[:, :, 0].contiguous() if Q.dim() == 3 else Q
 
+    def _predict_inputs(self, s0, Q):
+        """predict / gru_predict: -> (s0 [B,6] - one state [6] is given to every row -, Q [B,H], B, H)."""
+        Q = self._as_BH(Q)
+        B, H = Q.shape
+        s0 = self.tensor(s0)
+        if s0.dim() == 1:
+            s0 = s0.unsqueeze(0).expand(B, 6).contiguous()
+        return s0, Q, B, H
+
     def empty(self, *shape):
         return torch.empty(*shape, dtype=torch.float32, device=self.device)
 
@@ -134,11 +158,7 @@ class MPPIEngine:
     # ------------------------------------------------------------------ seams
     def predict(self, s0, Q, L=None, horizon=None):
         """predict_core: s0[B,6], Q[B,H] -> traj[B,H+1,6]."""
-        Q = self._as_BH(Q)
-        B, H = Q.shape
-        s0 = self.tensor(s0)
-        if s0.dim() == 1:
-            s0 = s0.unsqueeze(0).expand(B, 6).contiguous()
+        s0, Q, B, H = self._predict_inputs(s0, Q)
         if s0.shape != (B, 6):
             raise ValueError(f"s0 must be [{B},6] (or [6]), got {tuple(s0.shape)}")
         if L is not None:
@@ -182,10 +202,10 @@ class MPPIEngine:
         if m is None:
             return
         if isinstance(m, (float, int, np.floating)):            # immutable: the same object as last time means the same value
-            if m is getattr(self, "_m_pole_obj", None):
+            if m is self._m_pole_obj:
                 return
             self._m_pole_obj = m                                # (arrays / tensors may be assigned in place: converted every time)
-        per_row = getattr(self.mppi, "per_env_pole_mass", False)
+        per_row = self.mppi.per_env_pole_mass
         if per_row and torch.is_tensor(m) and m.is_cuda and m.numel() > 1:
             self._m_pole_obj = None
             return self.set_pole_mass_rows(m, rows)             # (registered as it is: no copy, no look at its values)
@@ -216,7 +236,7 @@ class MPPIEngine:
         > 0 - uploaded into a buffer of the engine's own and registered.  ``rows``: the row count the caller's launches will have;
         an array of another length is refused here (the library refuses a launch with more rows than were registered)."""
         if m is None:
-            if getattr(self, "_m_rows", None) is not None:
+            if self._m_rows is not None:
                 self._check(self.lib.cpmppi_set_pole_mass_rows(self._h, None, 0))
                 self._m_rows = None
             return
@@ -235,12 +255,12 @@ class MPPIEngine:
                 raise ValueError(f"m_pole rows must be a vector [rows], got shape {a.shape}")
             if not (np.isfinite(a).all() and (a > 0).all()):
                 raise ValueError("every pole mass must be a positive, finite number")
-            own = getattr(self, "_m_rows_own", None)
+            own = self._m_rows_own
             if own is None or own.numel() != a.size:
                 own = self._m_rows_own = self.empty(a.size)
             own.copy_(torch.from_numpy(np.ascontiguousarray(a)), non_blocking=False)
             t = own
-        cur = getattr(self, "_m_rows", None)
+        cur = self._m_rows
         if cur is None or cur.data_ptr() != t.data_ptr() or cur.numel() != t.numel():
             self._check(self.lib.cpmppi_set_pole_mass_rows(self._h, _ptr(t), t.numel()))
         self._m_rows = t
@@ -469,11 +489,7 @@ class MPPIEngine:
 
     def gru_predict(self, s0, Q, h0=None, return_hidden=False):
         """Neural predictor seam: s0[B,6] | [6], Q[B,H], h0[2,B,32] -> traj[B,H+1,6] (and final hidden [2,B,32])."""
-        Q = self._as_BH(Q)
-        B, H = Q.shape
-        s0 = self.tensor(s0)
-        if s0.dim() == 1:
-            s0 = s0.unsqueeze(0).expand(B, 6).contiguous()
+        s0, Q, B, H = self._predict_inputs(s0, Q)
         h0 = self.tensor(h0, (2, B, 32)) if h0 is not None else None
         traj = self.empty(B, H + 1, 6)
         h_out = self.empty(2, B, 32) if return_hidden else None
@@ -486,8 +502,8 @@ class MPPIEngine:
         x = self.tensor(x).reshape(-1)
         return x.expand(E).contiguous() if x.numel() == 1 else x
 
-    def rollout_cost(self, s0, inputs, target_position, target_equilibrium, L=None):
-        """inputs[E,N,H] -> S[E,N]: trajectory cost of given control sequences (no update)."""
+    def _rollout_inputs(self, s0, inputs, target_position, target_equilibrium, L):
+        """rollout_cost / rollout_cost_grad: -> (E, s0 [E,6], inputs [E,N,H], target position, target equilibrium, L or None [E])."""
         inputs = self.tensor(inputs)
         E = inputs.shape[0]
         if inputs.shape != (E, self.N, self.H):
@@ -495,6 +511,11 @@ class MPPIEngine:
         s0 = self.tensor(s0, (E, 6))
         tp, te = self._per_env(target_position, E), self._per_env(target_equilibrium, E)
         Lt = self._per_env(L, E) if L is not None else None
+        return E, s0, inputs, tp, te, Lt
+
+    def rollout_cost(self, s0, inputs, target_position, target_equilibrium, L=None):
+        """inputs[E,N,H] -> S[E,N]: trajectory cost of given control sequences (no update)."""
+        E, s0, inputs, tp, te, Lt = self._rollout_inputs(s0, inputs, target_position, target_equilibrium, L)
         S = self.empty(E, self.N)
         self._check(self.lib.cpmppi_rollout_cost(self._h, E, _ptr(s0), _ptr(inputs), _ptr(tp), _ptr(te), _ptr(Lt), _ptr(S),
                                                  self._stream()))
@@ -502,13 +523,7 @@ class MPPIEngine:
 
     def rollout_cost_grad(self, s0, inputs, target_position, target_equilibrium, L=None, previous_input=None):
         """inputs[E,N,H] -> (S[E,N], grad[E,N,H]): trajectory cost and its derivative w.r.t. the inputs."""
-        inputs = self.tensor(inputs)
-        E = inputs.shape[0]
-        if inputs.shape != (E, self.N, self.H):
-            raise ValueError(f"inputs must be [E,{self.N},{self.H}]")
-        s0 = self.tensor(s0, (E, 6))
-        tp, te = self._per_env(target_position, E), self._per_env(target_equilibrium, E)
-        Lt = self._per_env(L, E) if L is not None else None
+        E, s0, inputs, tp, te, Lt = self._rollout_inputs(s0, inputs, target_position, target_equilibrium, L)
         pi = self._per_env(previous_input, E) if previous_input is not None else None
         S, grad = self.empty(E, self.N), self.empty(E, self.N, self.H)
         self._check(self.lib.cpmppi_rollout_cost_grad(self._h, E, _ptr(s0), _ptr(inputs), _ptr(tp), _ptr(te), _ptr(Lt),
@@ -566,7 +581,7 @@ class MPPIEngine:
         self._check(self.lib.cpmppi_last_launch(self._h, C.byref(info)))
         d = {n: int(getattr(info, n)) for n, _ in info._fields_}
         # (predictor "ODE" with a per-env pole mass registered runs the kernel's second compilation, rollout_cost_rows_kernel)
-        rows = d["ode_predictor"] and getattr(self, "_m_rows", None) is not None
+        rows = d["ode_predictor"] and self._m_rows is not None
         d["kernel"] = ("rollout_cost%s_kernel<%d, %s, %d, %d, %d%s>" % (
             "_rows" if rows else "", d["cost_id"], "true" if d["math_mode"] == _L.MATH_FAST else "false", (0, 1, 2, 3)[d["noise_kind"]],
             d["rollouts_per_lane"], d["build_variant"], ", PREDICTOR_ODE" if d["ode_predictor"] else ""))

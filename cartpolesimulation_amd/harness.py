@@ -113,11 +113,8 @@ class BatchedCartPoleExperiment:
             raise ValueError("an optimizer object is paced by the host: run this batch launched (graph=False)")
         if graph and knots_fn is None and run.T > 0:
             run.capture(steps_per_graph)
-            while run.periods_left:
-                run.enqueue_next()
-        else:
-            while run.periods_left:
-                run.enqueue_next()
+        while run.periods_left:
+            run.enqueue_next()
         return run.finish()
 
 
@@ -134,8 +131,9 @@ def controller_pole_mass(b, per_env=False):
     mt = np.asarray(b.m_pole_table, np.float32)
     T, E = b.n_periods, mt.shape[1]
     calls = np.minimum(np.arange(T + 1) * b.n_ctrl, mt.shape[0] - 1)
-    inf = None if b.informed is None else np.asarray(b.informed, bool)
-    shared = inf is None or inf.ndim == 1 or bool((inf == inf[:, :1]).all())
+    inf = b.informed_table(E)
+    told = np.ones((T + 1, E), bool) if inf is None else inf[np.minimum(calls, len(inf) - 1)]
+    shared = inf is None or bool((inf == inf[:, :1]).all())
     if (mt == mt[:, :1]).all() and (shared or not per_env):
         if not shared:
             import warnings
@@ -143,24 +141,79 @@ def controller_pole_mass(b, per_env=False):
                           "it and stays the handle's; the plants follow their own tables (MPPIConfig(per_env_pole_mass=True) follows it "
                           "per experiment)")
             return None, None
-        told = np.ones(T + 1, bool)
-        if inf is not None:
-            col = inf[:, 0] if inf.ndim == 2 else inf
-            told = col[np.minimum(calls, len(col) - 1)]
-        return np.where(told, mt[calls, 0], mt[0, 0]).astype(np.float32), None
+        return np.where(told[:, 0], mt[calls, 0], mt[0, 0]).astype(np.float32), None
     if not per_env:
         return None, None
-    told = np.ones((T + 1, E), bool)
-    if inf is not None:
-        told = np.broadcast_to(inf if inf.ndim == 2 else inf[:, None], (len(inf), E))[np.minimum(calls, len(inf) - 1)]
     return None, np.ascontiguousarray(np.where(told, mt[calls], mt[0]), np.float32)
+
+
+class ControllerMass:
+    """The pole MASS the controller of a schedule run is told: predictor_ODE takes it from the simulator's 'm_pole' attribute at every
+    call (predictors_customization.py:55-58; predictor_ODE_v0 does not), told or not as the informer says (controller_pole_mass).
+    Decided on the host from the batch and the engine's MPPIConfig:
+      kind    "none" (the handle's mass stands) | "value" (`values` [T+1]: one per controller call, the handle's scalar) |
+              "rows" (`table` [T+1,E]: one row per call, a mass per experiment - MPPIConfig.per_env_pole_mass)
+      varies  it changes between calls: the host paces such a run call by call (no captured graph, one cpmppi_groups_run per period)
+    `bind` makes the device side, `apply(c)` goes before controller call c, `release` after the last one."""
+
+    def __init__(self, batch, mppi):
+        self.values = self.table = None
+        if batch.m_pole_table is not None and mppi.predictor_type == "ODE":
+            self.values, self.table = controller_pole_mass(batch, per_env=mppi.per_env_pole_mass)
+        self.kind = "value" if self.values is not None else "rows" if self.table is not None else "none"
+        per_call = self.values if self.values is not None else self.table
+        self.varies = per_call is not None and bool((per_call != per_call[:1]).any())
+        self.engines, self.slices, self.registered = [], [], False
+        self.rows = self.rows_table = None                      # "rows", bound: the registered vector [E] and `table` on the device
+
+    def bind(self, engines, slices=None, register=True):
+        """The engines whose launches read the mass - one over all envs, or env groups with their ``slices`` [(first, stop)].
+        "rows": the table stays on the device and every handle reads ITS slice of ONE registered [E] vector (``register`` False:
+        the vector is only kept filled, for an optimizer object that registers it with its own engine)."""
+        self.engines = list(engines)
+        if self.kind != "rows":
+            return
+        self.slices = list(slices) if slices is not None else [(0, self.table.shape[1])]
+        self.rows_table = self.engines[0].tensor(self.table)
+        self.rows = self.rows_table[0].clone()
+        self.registered = bool(register)
+        if register:
+            for eng, (e0, e1) in zip(self.engines, self.slices):
+                eng.set_pole_mass_rows(self.rows[e0:e1])
+
+    def apply(self, c):
+        """Before controller call c: the mass the simulator would hand it.  The scalar goes to every handle (read when the launch
+        is enqueued); of a mass per experiment every engine copies its slice of row c into the vector on the stream it launches
+        on (rows that are constant in time: once)."""
+        if self.kind == "value":
+            for eng in self.engines:
+                eng.set_pole_mass(float(self.values[c]))
+        elif self.kind == "rows" and (c == 0 or self.varies):
+            for eng, (e0, e1) in zip(self.engines, self.slices):
+                with torch.cuda.stream(eng.launch_stream()):
+                    self.rows[e0:e1].copy_(self.rows_table[c, e0:e1])
+
+    def for_optimizer(self, c):
+        """-> variable_parameters.m_pole at call c: the float, or the device row (an optimizer with per_env_pole_mass registers it)."""
+        if self.kind == "value":
+            return float(self.values[c])
+        self.apply(c)
+        return self.rows
+
+    def release(self):
+        """The handles are left as found (the launches enqueued keep the vector)."""
+        if self.registered:
+            for eng in self.engines:
+                eng.set_pole_mass_rows(None)
+            self.registered = False
 
 
 class ScheduleRun:
     """The device loop of BatchedCartPoleExperiment.run_schedule as an object that enqueues one piece at a time, so that several
     runs - env groups on their own streams, pipeline.run_schedule_groups - can be interleaved by one host thread."""
 
-    def __init__(self, engine, batch, seed, env_offset=0, knots_fn=None, u_nom0=None, optimizer=None):
+    def __init__(self, engine, batch, seed, env_offset=0, knots_fn=None, u_nom0=None, optimizer=None, bind_mass=True):
+        """``bind_mass`` False: the caller binds `self.mass` to the engines that launch (pipeline.run_schedule_groups)."""
         self.eng, self.b, self.seed, self.env_offset, self.knots_fn = engine, batch, int(seed), int(env_offset), knots_fn
         self.optimizer = optimizer
         if optimizer is not None:
@@ -181,11 +234,9 @@ class ScheduleRun:
         for tab in (L_tab, m_tab):
             if tab is not None and (b.stride != 1 or tab.shape[0] != b.n_sim + 1):
                 raise ValueError("a pole-length / pole-mass table is per simulation step: draw the batch with stride 1 (dt_save = dt_simulation)")
-        Lc_tab = None
-        if L_tab is not None and b.informed is not None:                            # what the controller is TOLD: the true length or the initial one
-            told = np.asarray(b.informed, bool)
-            Lc_tab = eng.tensor(np.where(told if told.ndim == 2 else told[:, None], np.asarray(b.L_table, np.float32),
-                                         np.asarray(b.L_table, np.float32)[0]))
+        Lc_tab, told = None, b.informed_table(E)
+        if L_tab is not None and told is not None:                                  # what the controller is TOLD: the true length or the initial one
+            Lc_tab = eng.tensor(np.where(told, np.asarray(b.L_table, np.float32), np.asarray(b.L_table, np.float32)[0]))
         self.cur_tp, self.cur_te = tp_tab[0].clone(), te_tab[0].clone()
         self.cur_L = (Lc_tab if Lc_tab is not None else L_tab)[0].clone() if L_tab is not None else (eng.tensor(b.L) if b.L is not None else None)
         self.u_nom = eng.zeros(E, eng.H) if u_nom0 is None else eng.tensor(u_nom0, (E, eng.H)).clone()
@@ -223,9 +274,7 @@ class ScheduleRun:
                 if b.stride != 1 or b.angle_offset.shape[0] != b.n_sim + 1:
                     raise ValueError("the angle-offset table is per simulation step: draw the batch with stride 1")
                 self.plant.update(angle_offset_table=torch.as_tensor(np.ascontiguousarray(b.angle_offset, np.float64), device=self.s.device))
-                if b.informed is not None:
-                    told = np.asarray(b.informed, bool)
-                    told = told if told.ndim == 2 else np.broadcast_to(told[:, None], (len(told), E))
+                if told is not None:
                     self.plant.update(informed_table=torch.as_tensor(np.ascontiguousarray(told, np.uint8), device=self.s.device))
         # the control applied in the last period = the next call's Q_ccrc / "Q_applied_-1" (CartPole/__init__.py:489, 517-518), for the
         # cost plugins that read a previous input (0 before the first update, :838)
@@ -234,21 +283,10 @@ class ScheduleRun:
         if eng.mppi.cost_function_specification in PREVIOUS_INPUT_COSTS:
             self.prev_Q = eng.zeros(E)
             self.plant.update(Q_applied_out=self.prev_Q)
-        # the pole MASS the controller computes with (predictor_ODE takes it from the simulator's 'm_pole' attribute at every call,
-        # predictors_customization.py:55-58; predictor_ODE_v0 does not) - told or not as the informer says (controller_pole_mass)
-        self.m_ctrl = self.m_env_tab = self.m_env = None
-        if b.m_pole_table is not None and getattr(eng.mppi, "predictor_type", "ODE_v0") == "ODE":
-            self.m_ctrl, m_env = controller_pole_mass(b, per_env=getattr(eng.mppi, "per_env_pole_mass", False))
-            if m_env is not None:
-                # one mass per experiment: the table stays on the device, the handle reads ONE registered [E] vector, and row c is
-                # copied into it on the launch stream before controller call c
-                self.m_env_tab = eng.tensor(m_env)
-                self.m_env = self.m_env_tab[0].clone()
-                self.m_env_constant = bool((m_env == m_env[:1]).all())
-                if optimizer is None:
-                    eng.set_pole_mass_rows(self.m_env)
-        self.counter = self.graph = None
-        self.per = 0
+        self.mass = ControllerMass(b, eng.mppi)
+        if bind_mass:                                              # (an optimizer object registers the row with its own engine)
+            self.mass.bind([eng], register=optimizer is None)
+        self.counter, self.graph, self.per = None, None, 0
         self._prep = self._prep_plant = None                       # argument blocks built once (the launched Philox loop)
 
     @property
@@ -259,16 +297,8 @@ class ScheduleRun:
     def periods_left(self):
         return self.c < self.T
 
-    def set_controller_mass(self, c, engines=None):
-        """Before controller call c: the pole mass the simulator would hand it (the launch reads it from the handle when enqueued;
-        a mass per experiment: row c of the device table into the registered vector, on the launch stream)."""
-        if self.m_ctrl is not None:
-            for e in (engines or [self.eng]):
-                e.set_pole_mass(float(self.m_ctrl[c]))
-        elif self.m_env is not None and (c == 0 or not self.m_env_constant):
-            fixed = getattr(self.eng, "_fixed_stream_obj", None)
-            with torch.cuda.stream(fixed if fixed is not None else torch.cuda.current_stream(self.s.device)):
-                self.m_env.copy_(self.m_env_tab[c])
+    m_ctrl = property(lambda self: self.mass.values)           # (host [T+1] / the registered device vector [E], or None)
+    m_env = property(lambda self: self.mass.rows)
 
     def _control(self, c):
         eng = self.eng
@@ -279,11 +309,8 @@ class ScheduleRun:
             vp.target_position, vp.target_equilibrium = self.cur_tp, self.cur_te
             if self.cur_L is not None:
                 vp.L = self.cur_L
-            if self.m_ctrl is not None:
-                vp.m_pole = float(self.m_ctrl[c])
-            elif self.m_env is not None:
-                self.set_controller_mass(c)
-                vp.m_pole = self.m_env                              # (the device row: an optimizer with per_env_pole_mass registers it)
+            if self.mass.kind != "none":
+                vp.m_pole = self.mass.for_optimizer(c)
             if self.prev_Q is not None:
                 vp.Q_ccrc = self.prev_Q
                 setattr(vp, "Q_applied_-1", self.prev_Q)
@@ -292,21 +319,25 @@ class ScheduleRun:
             self.Q.copy_(q.reshape(-1))
             return
         if c is not None:
-            self.set_controller_mass(c)
+            self.mass.apply(c)
         if self.knots_fn is not None:
-            eng.step(self.s_ctrl, self.u_nom, self.cur_tp, self.cur_te, L=self.cur_L, knots=self.knots_fn(c), Q_out=self.Q, **self._prev)
+            noise = dict(knots=self.knots_fn(c))
         elif self.counter is not None:
-            eng.step(self.s_ctrl, self.u_nom, self.cur_tp, self.cur_te, L=self.cur_L, seed=self.seed, offset_dev=self.counter,
-                     env_offset=self.env_offset, Q_out=self.Q, **self._prev)
+            noise = dict(seed=self.seed, offset_dev=self.counter, env_offset=self.env_offset)
         else:
-            eng.step(self.s_ctrl, self.u_nom, self.cur_tp, self.cur_te, L=self.cur_L, seed=self.seed, offset=c, env_offset=self.env_offset,
-                     Q_out=self.Q, **self._prev)
+            noise = dict(seed=self.seed, offset=c, env_offset=self.env_offset)
+        eng.step(self.s_ctrl, self.u_nom, self.cur_tp, self.cur_te, L=self.cur_L, Q_out=self.Q, **noise, **self._prev)
+
+    def _plant_step(self, n_substeps, c):
+        """The plant launch of control period c: the period from the host, or - captured - from the device counter."""
+        when = dict(period=c) if self.counter is None else dict(period_dev=self.counter)
+        self.eng.plant_step(self.s, self.Q, n_substeps, **when, **self.plant)
 
     def _period(self, c):
         if self.counter is None and self.knots_fn is None and self.optimizer is None:
             # the launched loop: two library calls per period on argument blocks built once (the Python-side argument handling of
             # step + plant_step is ~30 us per period - more than the GPU needs for a few dozen envs)
-            self.set_controller_mass(c)
+            self.mass.apply(c)
             if self._prep is None:
                 self._prep = self.eng.prepare_step(self.s_ctrl, self.u_nom, self.cur_tp, self.cur_te, L=self.cur_L, seed=self.seed, offset=0,
                                                    env_offset=self.env_offset, Q_out=self.Q, **self._prev)
@@ -315,34 +346,30 @@ class ScheduleRun:
             self._prep_plant.run(period=c)
             return
         self._control(c)
-        if self.counter is not None:
-            self.eng.plant_step(self.s, self.Q, self.b.n_ctrl, period_dev=self.counter, **self.plant)
-        else:
-            self.eng.plant_step(self.s, self.Q, self.b.n_ctrl, period=c, **self.plant)
+        self._plant_step(self.b.n_ctrl, c)
 
     def capture(self, steps_per_graph=10):
         """Capture `steps_per_graph` control periods as ONE HIP graph (device step counter: Philox offset = schedule row =
         recording row, no launch argument changes between periods); enqueue_next then replays it."""
         if self.optimizer is not None:
             raise ValueError("an optimizer object is paced by the host: run this batch launched (graph=False)")
-        if self.m_ctrl is not None and len(np.unique(self.m_ctrl)) > 1:
-            raise ValueError("a captured graph replays ONE pole mass for the controller: run this batch launched (graph=False)")
-        if self.m_env is not None and not self.m_env_constant:
-            raise ValueError("a captured graph cannot step through the controller's per-experiment pole-mass table (the row would "
+        if self.mass.varies:
+            raise ValueError("a captured graph replays ONE pole mass for the controller: run this batch launched (graph=False)"
+                             if self.mass.kind == "value" else
+                             "a captured graph cannot step through the controller's per-experiment pole-mass table (the row would "
                              "have to be selected on the device): run this batch launched (graph=False)")
         dev = self.s.device
         # the graph replays the handle's controller mass as it is when CAPTURED: the run's (constant) one, which may differ from
         # the mass the handle was created with (an uninformed controller; advisor, round 5)
-        self.set_controller_mass(0)
+        self.mass.apply(0)
         self.counter = torch.zeros(1, dtype=torch.int64, device=dev)              # controller calls made
-        fixed = getattr(self.eng, "_fixed_stream_obj", None)
         cap = torch.cuda.Stream(device=dev)
-        launch = fixed if fixed is not None else torch.cuda.current_stream(dev)
+        launch = self.eng.launch_stream()
         cap.wait_stream(launch)
         cap.wait_stream(torch.cuda.current_stream(dev))
         self.graph = torch.cuda.CUDAGraph()
         self.per = max(1, min(int(steps_per_graph), self.T))
-        self.eng.use_stream(cap)
+        fixed = self.eng.use_stream(cap)
         try:
             with torch.cuda.stream(cap):
                 with torch.cuda.graph(self.graph, stream=cap):
@@ -355,11 +382,7 @@ class ScheduleRun:
     def enqueue_next(self):
         """The next control period(s) of the run: one period launched, or one replay of the captured graph."""
         if self.graph is not None and self.T - self.c >= self.per:
-            fixed = getattr(self.eng, "_fixed_stream_obj", None)
-            if fixed is not None:
-                with torch.cuda.stream(fixed):
-                    self.graph.replay()
-            else:
+            with torch.cuda.stream(self.eng.launch_stream()):
                 self.graph.replay()
             self.c += self.per
         else:
@@ -370,10 +393,9 @@ class ScheduleRun:
         """The run's last controller call (+ the trailing simulation steps of a length that is not a whole number of periods)."""
         assert not self.periods_left
         self._control(self.T)
-        if self.m_env is not None and self.optimizer is None:
-            self.eng.set_pole_mass_rows(None)                       # (the launches enqueued keep the vector; the handle is left as found)
-        if self.counter is not None:
-            self.eng.plant_step(self.s, self.Q, self.tail, period_dev=self.counter, **self.plant)
-        else:
-            self.eng.plant_step(self.s, self.Q, self.tail, period=self.T, **self.plant)
+        self.mass.release()
+        self._plant_step(self.tail, self.T)
+        return self.result()
+
+    def result(self):
         return dict(states=self.states, dd=self.dd, Q=self.Qs, final_state=self.s, u_nom=self.u_nom, batch=self.b)

@@ -22,11 +22,12 @@ class optimizer_cem(_OptimizerBase):
                  mpc_horizon=35, mpc_timestep=0.02, cem_outer_it=3, cem_initial_action_stdev=0.5, num_rollouts=200,
                  cem_stdev_min=0.01, cem_best_k=40, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
-                 math_mode="fast", intermediate_steps=10, phys=None, device=0, variable_parameters=None, **kwargs):
+                 math_mode="fast", intermediate_steps=10, phys=None, device=0, variable_parameters=None, per_env_pole_mass=False,
+                 **kwargs):
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
-                         intermediate_steps, control_mode="clip", shift_mode="none", math_mode=math_mode)
-        self._take_engine_flags(kwargs)
+                         intermediate_steps, control_mode="clip", shift_mode="none", math_mode=math_mode,
+                         per_env_pole_mass=bool(per_env_pole_mass))
         self.cem_outer_it, self.cem_best_k = int(cem_outer_it), int(cem_best_k)
         self.cem_initial_action_stdev, self.cem_stdev_min = float(cem_initial_action_stdev), float(cem_stdev_min)
         self.warmup, self.warmup_iterations = bool(warmup), int(warmup_iterations)

@@ -33,13 +33,13 @@ class _GradientBase(_OptimizerBase):
 
     def __init__(self, cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, sample_stdev, period,
                  num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
-                 variable_parameters, optimizer_logging, horizon_reduce):
+                 variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass):
         # the handle's sampler draws knots ~ N(0, SQRTRHOINV / sqrt(dt)): set it to the requested stdev
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
                          intermediate_steps, control_mode="clip", shift_mode="none", math_mode="fast",
                          horizon_reduce=horizon_reduce, SQRTRHOINV=float(sample_stdev) * math.sqrt(float(mpc_timestep)),
-                         period_interpolation_inducing_points=int(period))
+                         period_interpolation_inducing_points=int(period), per_env_pole_mass=bool(per_env_pole_mass))
         self.count = 0               # control steps taken
         self.draws = 0               # sampler launches (the Philox offset)
 
@@ -109,15 +109,15 @@ class optimizer_gradient(_GradientBase):
                  adam_epsilon=1.0e-7, rtol=1.0e-3, gradient_steps=5, num_rollouts=40, initial_action_stdev=0.5,
                  gradmax_clip=5, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
-                 intermediate_steps=10, horizon_reduce="sum", phys=None, device=0, variable_parameters=None, **kwargs):
+                 intermediate_steps=10, horizon_reduce="sum", phys=None, device=0, variable_parameters=None,
+                 per_env_pole_mass=False, **kwargs):
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
         self.adam_epsilon, self.gradmax_clip, self.rtol = float(adam_epsilon), float(gradmax_clip), float(rtol)
         self.gradient_steps, self.warmup, self.warmup_iterations = int(gradient_steps), bool(warmup), int(warmup_iterations)
         self.initial_action_stdev = float(initial_action_stdev)
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, initial_action_stdev,
                          10, num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
-                         variable_parameters, optimizer_logging, horizon_reduce)
-        self._take_engine_flags(kwargs)
+                         variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass)
 
     def _draw(self):
         """Independent N(0, initial_action_stdev) per time-step, clipped (cpmppi_cem_sample)."""
@@ -149,7 +149,7 @@ class optimizer_rpgd(_GradientBase):
                  sample_whole_control_space=False, uniform_dist_max=0.8, uniform_dist_min=-0.8, shift_previous=1,
                  warmup=False, warmup_iterations=250, optimizer_logging=False, calculate_optimal_trajectory=False,
                  num_envs=1, cost_function_specification=None, cost_weights=None, intermediate_steps=10,
-                 horizon_reduce="sum", phys=None, device=0, variable_parameters=None, **kwargs):
+                 horizon_reduce="sum", phys=None, device=0, variable_parameters=None, per_env_pole_mass=False, **kwargs):
         if SAMPLING_DISTRIBUTION not in ("normal", "uniform"):
             raise ValueError(f"SAMPLING_DISTRIBUTION={SAMPLING_DISTRIBUTION!r}; expected 'normal' or 'uniform'")
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
@@ -163,8 +163,8 @@ class optimizer_rpgd(_GradientBase):
         stdev = self.sample_stdev if SAMPLING_DISTRIBUTION == "normal" else 1.0
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, stdev,
                          period_interpolation_inducing_points, num_envs, cost_function_specification, cost_weights,
-                         intermediate_steps, phys, device, variable_parameters, optimizer_logging, horizon_reduce)
-        self._take_engine_flags(kwargs)
+                         intermediate_steps, phys, device, variable_parameters, optimizer_logging, horizon_reduce,
+                         per_env_pole_mass)
 
     def _shape_samples(self, z):
         if self.distribution == "normal":

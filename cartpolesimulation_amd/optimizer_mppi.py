@@ -32,7 +32,7 @@ class optimizer_mppi(_OptimizerBase):
                  mpc_timestep=0.02, num_envs=1, noise="philox", cost_function_specification=None, cost_weights=None,
                  horizon_reduce="sum", control_mode="clip", shift_mode="repeat_last", correction_u="u_run",
                  math_mode="fast", intermediate_steps=10, phys=None, device=0, variable_parameters=None, gru_model=None,
-                 SAMPLING_TYPE="interpolated", predictor_type="ODE_v0", **kwargs):
+                 SAMPLING_TYPE="interpolated", predictor_type="ODE_v0", per_env_pole_mass=False, **kwargs):
         self.predictor, self.cost_function = predictor, cost_function
         self.lib = computation_library
         if noise not in ("philox", "sfc64"):
@@ -50,8 +50,8 @@ class optimizer_mppi(_OptimizerBase):
                          intermediate_steps, cc_weight=cc_weight, R=R, LBD=LBD, NU=NU, SQRTRHOINV=SQRTRHOINV,
                          period_interpolation_inducing_points=int(period_interpolation_inducing_points),
                          horizon_reduce=horizon_reduce, control_mode=control_mode, shift_mode=shift_mode,
-                         correction_u=correction_u, math_mode=math_mode, predictor_type=predictor_type)
-        self._take_engine_flags(kwargs)
+                         correction_u=correction_u, math_mode=math_mode, predictor_type=predictor_type,
+                         per_env_pole_mass=bool(per_env_pole_mass))
         self.calculate_optimal_trajectory = calculate_optimal_trajectory
         self.optimal_trajectory = None
         self.u_nom = None

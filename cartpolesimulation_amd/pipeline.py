@@ -14,12 +14,11 @@ Measured (profiles/r5/multistream_*.txt, wall time per step of all envs): C4 73.
 """
 import ctypes as C
 
-import numpy as np
 import torch
 
 from . import _lib as _L
 from .configs import MPPIConfig, PhysicalParameters
-from .engine import MPPIEngine, device_tensor
+from .engine import MPPIEngine, device_tensor, gpu_device
 
 
 def split_envs(E, groups):
@@ -42,11 +41,9 @@ class EnvGroups:
     def __init__(self, E, mppi: MPPIConfig = None, groups=2, phys: PhysicalParameters = None, device=0, env_offset=0):
         from .configs import build_c_config
         self.lib = _L.load()
-        if not torch.cuda.is_available():
-            raise RuntimeError("cartpolesimulation_amd needs an MI355X (gfx950) visible to PyTorch-ROCm; there is no CPU fallback.")
+        self.device = gpu_device(device)
         self.E, self.env_offset = int(E), int(env_offset)
         self.mppi, self.phys = mppi or MPPIConfig(), phys or PhysicalParameters()
-        self.device = torch.device("cuda", device if isinstance(device, int) else torch.device(device).index or 0)
         cfg = build_c_config(self.E, self.mppi, self.phys)
         self._g = C.c_void_p()
         rc = self.lib.cpmppi_groups_create(C.byref(cfg), self.device.index, int(groups), self.env_offset, C.byref(self._g))
@@ -210,38 +207,24 @@ def run_schedule_groups(groups: EnvGroups, batch, seed):
     (cpmppi_groups_run), the groups working in place on their slices of the batch's buffers.  -> the same result dict."""
     from .harness import ScheduleRun
     eng = groups.args_engine
-    run = ScheduleRun(eng, batch, seed)                        # the batch's buffers and logs, set up on the caller's stream
+    run = ScheduleRun(eng, batch, seed, bind_mass=False)      # the batch's buffers and logs, set up on the caller's stream
+    # the controller's pole mass goes to the GROUPS' handles: every one reads its slice of the run's vector and refills it on its
+    # own stream - no group waits for another
+    run.mass.bind(groups.engines, groups.slices)
     step = groups.prepare(run.s_ctrl, run.u_nom, run.cur_tp, run.cur_te, L=run.cur_L, seed=seed, Q_out=run.Q, **run._prev)
     plant = eng.prepare_plant_step(run.s, run.Q, batch.n_ctrl, period=0, **run.plant)
     groups.fork()
-    per_env = run.m_env is not None
-    if per_env:
-        # a mass per experiment (harness.controller_pole_mass): every group's handle reads ITS slice of the run's [E] vector, and
-        # copies its slice of row c of the table into it on its own stream - no group waits for another
-        eng.set_pole_mass_rows(None)                          # (ScheduleRun registered the vector with group 0's handle over all envs)
-        for g_eng, (e0, e1) in zip(groups.engines, groups.slices):
-            g_eng.set_pole_mass_rows(run.m_env[e0:e1])
-
-    def set_mass(c):
-        if not per_env:
-            return run.set_controller_mass(c, groups.engines)
-        for st, (e0, e1) in zip(groups.streams, groups.slices):
-            with torch.cuda.stream(st):
-                run.m_env[e0:e1].copy_(run.m_env_tab[c, e0:e1])
-
-    if (run.m_ctrl is not None and len(np.unique(run.m_ctrl)) > 1) or (per_env and not run.m_env_constant):
+    if run.mass.varies:
         # the controller's pole mass follows the plant's (predictor_ODE): a handle parameter read when a launch is enqueued (a vector
         # rewritten between launches) - one library call per period instead of one for the whole run
         for c in range(run.T):
-            set_mass(c)
+            run.mass.apply(c)
             groups.run(step, plant, periods=1, offset=c, period=c)
-        set_mass(run.T)
+        run.mass.apply(run.T)
     else:
-        set_mass(0)
+        run.mass.apply(0)
         groups.run(step, plant, periods=run.T, offset=0, period=0)
     groups.run(step, plant, periods=1, offset=run.T, period=run.T, n_substeps=run.tail)   # the run's last controller call (+ trailing steps)
     groups.join()
-    if per_env:
-        for g_eng in groups.engines:
-            g_eng.set_pole_mass_rows(None)
-    return dict(states=run.states, dd=run.dd, Q=run.Qs, final_state=run.s, u_nom=run.u_nom, batch=batch)
+    run.mass.release()
+    return run.result()

@@ -60,12 +60,9 @@ class next_state_predictor_ODE_v0:
         assert Q.shape[0] == s.shape[0]
         assert Q.ndim == 2
         assert s.ndim == 2
-        if self._per_row:                       # (the row count is the batch of s)
-            L = _pole_length(self.variable_parameters, self.phys, s.shape[0])
-            self._eng.apply_pole_mass_of(self.variable_parameters, rows=s.shape[0])
-        else:
-            L = _pole_length(self.variable_parameters, self.phys)
-            self._eng.apply_pole_mass_of(self.variable_parameters)
+        rows = s.shape[0]
+        L = _pole_length(self.variable_parameters, self.phys, rows if self._per_row else None)
+        self._eng.apply_pole_mass_of(self.variable_parameters, rows=rows)
         out = self._eng.predict(s, Q[:, :1], L=L)[:, 1]
         return out if as_tensor else out.cpu().numpy()
 
@@ -112,12 +109,9 @@ class predictor_ODE_v0:
         s0 = eng.tensor(initial_state)
         if s0.dim() == 2 and s0.shape[0] == 1 and Q.shape[0] != 1:
             s0 = s0[0]
-        if self._per_row:                       # (the row count is the batch of Q)
-            eng.apply_pole_mass_of(self.variable_parameters, rows=Q.shape[0])
-            L = _pole_length(self.variable_parameters, self.phys, Q.shape[0])
-        else:
-            eng.apply_pole_mass_of(self.variable_parameters)
-            L = _pole_length(self.variable_parameters, self.phys)
+        rows = Q.shape[0]
+        eng.apply_pole_mass_of(self.variable_parameters, rows=rows)
+        L = _pole_length(self.variable_parameters, self.phys, rows if self._per_row else None)
         out = eng.predict(s0, Q.contiguous(), L=L)
         return out if as_tensor else out.cpu().numpy()
 

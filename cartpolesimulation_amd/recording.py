@@ -144,8 +144,7 @@ def recording_block(result, phys, L_default=None):
         off = np.asarray(b.angle_offset, np.float64)[np.minimum(steps, b.angle_offset.shape[0] - 1)]
         out["angle_offset"] = np.ascontiguousarray(np.stack([off, np.cos(off), np.sin(off)], axis=-1))
     if b.informed is not None:                                       # the controller informer's answer in force at the row
-        told = np.asarray(b.informed, bool)[np.minimum(steps, len(b.informed) - 1)]
-        out["informed"] = np.ascontiguousarray(np.broadcast_to(told if told.ndim == 2 else told[:, None], (R, E)), dtype=np.uint8)
+        out["informed"] = np.ascontiguousarray(b.informed_table(E)[np.minimum(steps, len(b.informed) - 1)], dtype=np.uint8)
     return out
 
 

@@ -93,6 +93,13 @@ class ExperimentBatch:
     def rows_at(self, steps):
         return np.minimum(np.asarray(steps) // self.stride, self.target_position.shape[0] - 1)
 
+    def informed_table(self, E=None):
+        """`informed` as [rows, E] bool - one shared column is given to every experiment - or None (always informed)."""
+        if self.informed is None:
+            return None
+        told = np.asarray(self.informed, bool)
+        return told if told.ndim == 2 else np.broadcast_to(told[:, None], (len(told), self.E if E is None else E))
+
 
 class RandomExperimentSetter:
     """random_experiment_setter (CartPole/data_generator.py:93-218) for any number of consecutive experiments."""

@@ -177,6 +177,25 @@ def test_optimizers_and_predictors_carry_the_flag(monkeypatch):
     class Reached(Exception):
         pass
 
+    def reached(*a, **kw):
+        raise Reached
+
+    # ... and through the engine: with the flag, rows of num_envs entries are registered and another count is refused; without it
+    # the scalar route is what it was
+    for flag, m, calls in ((True, [0.05, 0.1, 0.15], [("rows", "ptr", 3)]), (False, [0.125] * 3, [("scalar", 0.125)])):
+        for cls in (optimizer_mppi, optimizer_cem, optimizer_rpgd):
+            o = cls(num_envs=3, per_env_pole_mass=flag, variable_parameters=SimpleNamespace(m_pole=np.array(m, f32)))
+            o.cfg.predictor_type = "ODE"
+            o.engine = _engine(predictor_type="ODE", per_env_pole_mass=flag)
+            o.engine.tensor = reached
+            with pytest.raises(Reached):
+                o.step(torch.zeros(3, 6))
+            assert o.engine.lib.calls == calls, (cls.__name__, flag)
+            if flag:
+                o.variable_parameters.m_pole = np.array([0.1, 0.2], f32)
+                with pytest.raises(ValueError, match="2 entries, the call has 3 rows"):
+                    o.step(torch.zeros(3, 6))
+
     made = []
 
     def fake_engine(horizon, dt, n, phys, math_mode, device, ptype="ODE_v0", **flags):
@@ -261,3 +280,98 @@ def test_uniform_schedule_keeps_the_scalar_path():
         assert controller_pole_mass(b2, per_env=False) == (None, None)
     m_ctrl, m_env = controller_pole_mass(b2, per_env=True)
     assert m_ctrl is None and np.array_equal(m_env, np.where(b2.informed[calls], b2.m_pole_table[calls], f32(0.087)))
+
+
+def test_controller_mass_is_decided_on_the_host():
+    """harness.ControllerMass, built from the batch and the engine's MPPIConfig alone (nothing is bound, no device is touched): which
+    of the two ways the controller is told its pole mass, and whether the mass changes between calls - the one rule behind "no
+    captured graph" and "one cpmppi_groups_run per period"."""
+    from cartpolesimulation_amd.configs import MPPIConfig
+    from cartpolesimulation_amd.harness import ControllerMass, controller_pole_mass
+    E = 3
+    ode, rows = MPPIConfig(predictor_type="ODE"), MPPIConfig(predictor_type="ODE", per_env_pole_mass=True)
+    inc = dict(init_value=0.087, change_every_x_seconds=0.02, mode="increase", range_random=[0.015, 0.3], range_clip=[0.015, 0.3],
+               increment=0.02, reset_every_x_seconds="inf")
+    regular = dict(mode="switching_regular", change_to_on_after_x_seconds_off=0.04, change_to_off_after_x_seconds_on=0.1)
+
+    def facts(m):
+        assert (m.values is None) == (m.kind != "value") and (m.table is None) == (m.kind != "rows")
+        assert m.engines == [] and m.rows is None and m.rows_table is None and not m.registered
+        return m.kind, m.varies
+
+    plain = _batch(E, {})
+    assert plain.m_pole_table is None
+    for cfg in (MPPIConfig(), ode, rows):
+        assert facts(ControllerMass(plain, cfg)) == ("none", False)
+    uniform = _batch(E, dict(m_pole=inc, inform_controller_about_parameters_change=regular))
+    for cfg in (ode, rows):
+        m = ControllerMass(uniform, cfg)
+        assert facts(m) == ("value", True) and np.array_equal(m.values, controller_pole_mass(uniform)[0])
+    assert facts(ControllerMass(uniform, MPPIConfig())) == ("none", False)      # predictor_ODE_v0 never reads the attribute
+    differing = _batch(E, dict(m_pole=RANDOM_M, inform_controller_about_parameters_change=SWITCHING_RANDOM))
+    m = ControllerMass(differing, rows)
+    assert facts(m) == ("rows", True) and np.array_equal(m.table, controller_pole_mass(differing, per_env=True)[1])
+    assert facts(ControllerMass(differing, ode)) == ("none", False)
+    constant = _batch(E, dict(m_pole=dict(RANDOM_M, mode="constant")))
+    m = ControllerMass(constant, rows)
+    assert facts(m) == ("rows", False) and len(np.unique(m.table[0])) == E
+    informers = _batch(E, dict(m_pole=inc, inform_controller_about_parameters_change=SWITCHING_RANDOM))
+    with pytest.warns(UserWarning, match="informer differs between experiments"):
+        assert facts(ControllerMass(informers, ode)) == ("none", False)
+    assert facts(ControllerMass(informers, rows)) == ("rows", True)
+    # a schedule that never changes the one mass: a value per call that does not vary (a graph may replay it)
+    still = ControllerMass(_batch(E, dict(m_pole=dict(inc, mode="constant"))), ode)
+    assert facts(still) == ("value", False) and (still.values == f32(0.087)).all()
+    # nothing bound: nothing to apply to and nothing to release
+    still.apply(0)
+    still.release()
+
+
+def test_controller_mass_gives_every_engine_its_slice():
+    """bind / apply / release over stand-in engines (host tensors, recorded library calls): env groups register their OWN slices -
+    no handle is ever handed the full vector -, row c is what the vector holds after apply(c), release unregisters once, and a
+    binding with register=False (a run paced by an optimizer object) keeps the vector filled without touching any handle."""
+    from cartpolesimulation_amd.configs import MPPIConfig
+    from cartpolesimulation_amd.harness import ControllerMass
+    E, slices = 5, [(0, 3), (3, 5)]
+    cfg = MPPIConfig(predictor_type="ODE", per_env_pole_mass=True)
+
+    def engines(n):
+        out = [_engine(predictor_type="ODE", per_env_pole_mass=True) for _ in range(n)]
+        for e in out:
+            e.launch_stream = lambda: None                                       # (torch.cuda.stream(None) is no context at all)
+        return out
+
+    b = _batch(E, dict(m_pole=RANDOM_M, inform_controller_about_parameters_change=SWITCHING_RANDOM))
+    m, engs = ControllerMass(b, cfg), engines(2)
+    m.bind(engs, slices)
+    assert [e.lib.calls for e in engs] == [[("rows", "ptr", 3)], [("rows", "ptr", 2)]] and m.registered
+    for c in (0, 3, b.n_periods):
+        m.apply(c)
+        assert np.array_equal(m.rows.numpy(), m.table[c]) and [len(e.lib.calls) for e in engs] == [1, 1], c
+    m.release()
+    m.release()
+    assert [e.lib.calls[1:] for e in engs] == [[("rows", None, 0)]] * 2 and not m.registered
+    # constant in time: filled at call 0 only
+    m, (one,) = ControllerMass(_batch(E, dict(m_pole=dict(RANDOM_M, mode="constant"))), cfg), engines(1)
+    m.bind([one])
+    assert one.lib.calls == [("rows", "ptr", E)] and m.slices == [(0, E)]
+    m.apply(0)
+    m.rows.zero_()
+    m.apply(1)
+    assert not m.rows.any()
+    # an optimizer object's run: the vector is kept filled, the handle is left alone; the optimizer is handed the vector itself
+    m, (one,) = ControllerMass(b, cfg), engines(1)
+    m.bind([one], register=False)
+    assert m.for_optimizer(2) is m.rows and np.array_equal(m.rows.numpy(), m.table[2])
+    m.release()
+    assert one.lib.calls == []
+    # one value per call: the scalar goes to every engine, no rows anywhere
+    inc = dict(init_value=0.087, change_every_x_seconds=0.02, mode="increase", range_random=[0.015, 0.3], range_clip=[0.015, 0.3],
+               increment=0.02, reset_every_x_seconds="inf")
+    m, engs = ControllerMass(_batch(E, dict(m_pole=inc)), cfg), engines(2)
+    m.bind(engs, slices)
+    m.apply(2)
+    m.release()
+    assert m.kind == "value" and m.rows is None and [e.lib.calls for e in engs] == [[("scalar", float(m.values[2]))]] * 2
+    assert m.for_optimizer(3) == float(m.values[3]) and [len(e.lib.calls) for e in engs] == [1, 1]
