@@ -1,5 +1,6 @@
-// cpmppi.hip — the hot path of libcpmppi.so: the handle, the MPPI step entry points and the launch dispatch of the rollout
-// kernel.   See include/cpmppi.h for the contract and cpmppi_internal.hpp for the other units of the library.
+// cpmppi.hip — the hot path of libcpmppi.so: the handle, the MPPI step entry points and the launch of the rollout kernel: the
+// build a launch gets is decided by plan_rollout (cpmppi_launch_plan.hpp, the one statement of that policy) and looked up here in
+// a table generated from the instance lists.   See include/cpmppi.h for the contract and cpmppi_internal.hpp for the other units.
 //
 // Kernel inventory
 //   rollout_cost_kernel<COST,FAST,NOISE,R,VARIANT,INTEG> / rollout_cost_rows_kernel<...>  (cpmppi_rollout.hpp, instantiated in cpmppi_rollout_*.hip; launched
@@ -25,6 +26,7 @@
 
 #include "cpmppi.h"
 #include "cpmppi_internal.hpp"
+#include "cpmppi_launch_plan.hpp"
 
 using namespace cpmppi_k;
 
@@ -43,6 +45,22 @@ CPMPPI_ODE_LATENCY_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE_ROWS)
 CPMPPI_ODE_THROUGHPUT_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE_ROWS)
 CPMPPI_ODE_LONE_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE_ROWS)
 }  // namespace cpmppi_k
+// ... and the same lists generate the launcher's lookup (find_rollout_kernel): one case per declared instantiation
+#define CPMPPI_MATCH_ROLLOUT(COST, FAST, NOISE, R, V) \
+  case rollout_key(COST, FAST, NOISE, R, V, PREDICTOR_ODE_V0): return &rollout_cost_kernel<COST, FAST, NOISE, R, V>;
+#define CPMPPI_MATCH_ROLLOUT_ODE(COST, FAST, NOISE, R, V) \
+  case rollout_key(COST, FAST, NOISE, R, V, PREDICTOR_ODE): return &rollout_cost_kernel<COST, FAST, NOISE, R, V, PREDICTOR_ODE>;
+#define CPMPPI_MATCH_ROLLOUT_ODE_ROWS(COST, FAST, NOISE, R, V) \
+  case rollout_key(COST, FAST, NOISE, R, V, PREDICTOR_ODE_ROWS): return &rollout_cost_rows_kernel<COST, FAST, NOISE, R, V, PREDICTOR_ODE>;
+
+// the launch plan's own constants (cpmppi_launch_plan.hpp includes nothing of the kernels) are the kernels'
+static_assert(cpmppi_plan::BLOCK == BLOCK && cpmppi_plan::WAVES == WAVES, "launch plan: workgroup size");
+static_assert(cpmppi_plan::INTEG_ODE_V0 == PREDICTOR_ODE_V0 && cpmppi_plan::INTEG_ODE == PREDICTOR_ODE &&
+              cpmppi_plan::INTEG_ODE_ROWS == PREDICTOR_ODE_ROWS, "launch plan: INTEG");
+static_assert(CPMPPI_COST_QBGM == COST_QBGM && CPMPPI_COST_DEFAULT == COST_DEFAULT && CPMPPI_COST_LEGACY == COST_LEGACY &&
+              CPMPPI_COST_QBG == COST_QBG && CPMPPI_NOISE_DELTA_U == NOISE_DELTA_U && CPMPPI_NOISE_KNOTS == NOISE_KNOTS &&
+              CPMPPI_NOISE_PHILOX == NOISE_PHILOX && CPMPPI_NOISE_DELTA_U_TILED == NOISE_TILED,
+              "rollout lookup: the public cost / noise ids are the kernels' template arguments");
 
 namespace {
 
@@ -60,6 +78,14 @@ __global__ void bump_counter_kernel(unsigned long long* c) { *c += 1ull; }
 
 uint32_t knot_count(uint32_t H, uint32_t period) { return (H + period - 1) / period + 1; }
 
+// A public cost id as the kernels take it: their COST template argument, and for quadratic_boundary / _nonconvex - which run on
+// default.py's kernels - the sub-mode.  (The way back, cpmppi_launch_info.cost_plugin, is the handle's cfg.cost_id itself.)
+void set_kernel_cost(Params& p, uint32_t cost_id) {
+  const bool qb = cost_id == CPMPPI_COST_QB || cost_id == CPMPPI_COST_QB_NONCONVEX;
+  p.cost_id = qb ? (uint32_t)CPMPPI_COST_DEFAULT : cost_id;
+  p.qb_mode = qb ? (cost_id == CPMPPI_COST_QB ? 1u : 2u) : 0u;
+}
+
 void fill_params(const cpmppi_config& c, Params& p) {
   memset(&p, 0, sizeof(p));
   p.E = c.E; p.N = c.N; p.H = c.H; p.S = c.S; p.period = c.period;
@@ -67,12 +93,7 @@ void fill_params(const cpmppi_config& c, Params& p) {
   p.t_step = (float)((double)c.dt / (double)c.S);      // predictors_customization_v0.py:39
   p.k = c.k; p.m_cart = c.m_cart; p.m_pole = c.m_pole; p.g = c.g; p.J_fric = c.J_fric; p.M_fric = c.M_fric;
   p.u_max = c.u_max; p.THL = c.track_half_length; p.L_default = c.L_default;
-  p.cost_id = c.cost_id;
-  p.qb_mode = 0;
-  if (c.cost_id == CPMPPI_COST_QB || c.cost_id == CPMPPI_COST_QB_NONCONVEX) {     // default.py's kernels, sub-mode in qb_mode
-    p.qb_mode = (c.cost_id == CPMPPI_COST_QB) ? 1u : 2u;
-    p.cost_id = CPMPPI_COST_DEFAULT;
-  }
+  set_kernel_cost(p, c.cost_id);
   memcpy(p.w, c.cost_w, sizeof(p.w));
   p.R = c.R; p.LBD = c.LBD; p.NU = c.NU; p.cc_weight = c.cc_weight; p.sigma = c.sigma;
   p.lo = c.action_low; p.hi = c.action_high;
@@ -101,9 +122,9 @@ __global__ __launch_bounds__(BLOCK) void fold_env_kernel(const Params p, const f
 
 // development aid (tools/variant_sweep.py, tools/dev/placement.py): the two size limits below which the straight-line builds are
 // launched and an LDS pad, overridable from the environment - in a -DCPMPPI_DEV_KNOBS build ONLY (build_variant "devknobs"), and
-// read when a handle is created, not per launch.  The shipped library has the constants: no getenv on the launch path, and no stray
-// environment variable can change which kernel production launches (advisor, round 5).
-struct DevKnobs { uint64_t lone_form_max_waves = 1024ull, latency_max_rollouts = 131071ull, lds_pad = 0; };
+// read when a handle is created, not per launch.  The shipped library has the constants of cpmppi_launch_plan.hpp: no getenv on
+// the launch path, and no stray environment variable can change which kernel production launches (advisor, round 5).
+struct DevKnobs { cpmppi_plan::RolloutLimits limits; uint64_t lds_pad = 0; };
 static DevKnobs g_knobs;
 static void refresh_dev_knobs() {
 #ifdef CPMPPI_DEV_KNOBS
@@ -111,96 +132,34 @@ static void refresh_dev_knobs() {
     const char* v = getenv(name);
     return (v && *v) ? (uint64_t)strtoull(v, nullptr, 10) : dflt;
   };
-  const DevKnobs d;
-  g_knobs.lone_form_max_waves = env_u64("CPMPPI_LONE_FORM_MAX_WAVES", d.lone_form_max_waves);
-  g_knobs.latency_max_rollouts = env_u64("CPMPPI_LATENCY_MAX_ROLLOUTS", d.latency_max_rollouts);
+  const cpmppi_plan::RolloutLimits d;
+  g_knobs.limits.lone_form_max_waves = env_u64("CPMPPI_LONE_FORM_MAX_WAVES", d.lone_form_max_waves);
+  g_knobs.limits.latency_max_rollouts = env_u64("CPMPPI_LATENCY_MAX_ROLLOUTS", d.latency_max_rollouts);
   g_knobs.lds_pad = env_u64("CPMPPI_LDS_PAD", 0);
 #endif
 }
-template <int COST, bool FAST, int R, int V, int INTEG = PREDICTOR_ODE_V0>
-hipError_t launch_rollout_noise(uint32_t noise, dim3 grid, size_t lds, hipStream_t s, const Params& p,
-                                const StepPtrs& a) {
-  switch (noise) {
-    case CPMPPI_NOISE_DELTA_U:
-      hipLaunchKernelGGL((rollout_kernel_for<COST, FAST, NOISE_DELTA_U, R, V, INTEG>()), grid, dim3(BLOCK), lds, s, p, a); break;
-    case CPMPPI_NOISE_KNOTS:
-      hipLaunchKernelGGL((rollout_kernel_for<COST, FAST, NOISE_KNOTS, R, V, INTEG>()), grid, dim3(BLOCK), lds, s, p, a); break;
-    case CPMPPI_NOISE_DELTA_U_TILED:
-      hipLaunchKernelGGL((rollout_kernel_for<COST, FAST, NOISE_TILED, R, V, INTEG>()), grid, dim3(BLOCK), lds, s, p, a); break;
-    default: {
-      // development aid (tools/dev/placement.py): CPMPPI_LDS_PAD=<bytes> of extra dynamic LDS per workgroup caps how many
-      // workgroups the dispatcher can put on one CU (160 KB each)
-      const size_t pad = (size_t)g_knobs.lds_pad;
-      if (pad) {
-        static bool raised = false;
-        if (!raised) {
-          (void)hipFuncSetAttribute(reinterpret_cast<const void*>(rollout_kernel_for<COST, FAST, NOISE_PHILOX, R, V, INTEG>()),
-                                    hipFuncAttributeMaxDynamicSharedMemorySize, (int)(lds + pad));
-          raised = true;
-        }
-      }
-      hipLaunchKernelGGL((rollout_kernel_for<COST, FAST, NOISE_PHILOX, R, V, INTEG>()), grid, dim3(BLOCK), lds + pad, s, p, a); break;
-    }
-  }
-  return hipGetLastError();
-}
 
-// Which build of the kernel a launch gets (measured on MI355X with tools/kbench.py; profiles/HISTORY.md, "Round 3 and earlier":
-// the 1.5 M crossover):
-//   one rollout per lane : latency build up to one wave per SIMD (1024 SIMDs x 64 lanes), throughput build above
-//   two rollouts per lane: mid-size build (phased horizon loop: quiet control steps and eventful ones in separate loops) up
-//                          to 1572864 rollouts - variant 3 (quiet step unrolled) while the launch has at most one wave
-//                          per SIMD, variant 2 above - and the throughput build beyond.  Phased mid-size vs throughput build,
-//                          envs x 1024 x 50: 256 envs 126 vs 133 us, 1024 envs 350 vs 355, 1536 envs 482 vs 495, 2048 envs
-//                          630 vs 636, 3072 envs 904 vs 890, 8192 envs 2.34 vs 2.29 ms
-constexpr uint64_t MID_SIZE_MAX_ROLLOUTS = 1572864ull;
-static uint64_t lone_form_max_waves() { return g_knobs.lone_form_max_waves; }
-// (round 5, tools/variant_sweep.py: between 65536 and 131072 rollouts - where the size rule still picks one rollout per lane - the
-// straight-line latency build beats the throughput build's loop: 48 x 2048 x 50 71.3 vs 79.8 us, 96 x 1024 x 50 74.9 vs 83.3)
-static uint64_t latency_max_rollouts() { return g_knobs.latency_max_rollouts; }
-template <int COST>
-hipError_t launch_rollout_math(uint32_t math, uint32_t ode, uint32_t rpl, uint32_t noise, dim3 grid, size_t lds, hipStream_t s,
-                               const Params& p, const StepPtrs& a, uint32_t* variant_out) {
-  // (the build VARIANT of the instantiation launched: 0 latency, 1 throughput, 2 mid-size phased, 3 its lone-wave form)
-#define CPMPPI_LAUNCH_V(FAST, R, V, ...) (*variant_out = (V), launch_rollout_noise<COST, FAST, R, V, ##__VA_ARGS__>(noise, grid, lds, s, p, a))
-  if (ode == CPMPPI_ODE_CROMER) {
-    // predictor_ODE has no events, hence no mid-size (phased) build: latency build up to one wave per SIMD with one rollout
-    // per lane, the throughput build otherwise.  With a per-env pole mass registered (a.m_pole): the same builds' instantiations
-    // that read it
-#define CPMPPI_LAUNCH_ODE(INTEG_)                                                                                                 \
-    do {                                                                                                                          \
-      if (math != CPMPPI_MATH_FAST) return CPMPPI_LAUNCH_V(false, 1, 1, INTEG_);                                                  \
-      if (rpl == 2)                                                                                                               \
-        return ((uint64_t)grid.x * WAVES <= 1024ull) ? CPMPPI_LAUNCH_V(true, 2, 3, INTEG_) : CPMPPI_LAUNCH_V(true, 2, 1, INTEG_); \
-      return ((uint64_t)grid.x * BLOCK <= 65536ull) ? CPMPPI_LAUNCH_V(true, 1, 0, INTEG_) : CPMPPI_LAUNCH_V(true, 1, 1, INTEG_);  \
-    } while (0)
-    if (a.m_pole) CPMPPI_LAUNCH_ODE(PREDICTOR_ODE_ROWS);
-    CPMPPI_LAUNCH_ODE(PREDICTOR_ODE);
-#undef CPMPPI_LAUNCH_ODE
+// The instantiation a plan names, looked up in the very lists that declare the instantiations above: the launcher cannot name a
+// kernel the rollout units do not define, and one listed in two units is a duplicate case.  NULL: no such build.
+using RolloutKernel = void (*)(const Params, const StepPtrs);
+constexpr uint32_t rollout_key(uint32_t cost, uint32_t fast, uint32_t noise, uint32_t r, uint32_t variant, uint32_t integ) {
+  return cost | fast << 2 | noise << 3 | (r - 1u) << 5 | variant << 6 | integ << 8;
+}
+RolloutKernel find_rollout_kernel(uint32_t cost, const cpmppi_plan::RolloutPlan& plan) {
+  switch (rollout_key(cost, plan.fast, plan.noise, plan.rpl, plan.variant, plan.integ)) {
+    CPMPPI_LATENCY_INSTANCES(CPMPPI_MATCH_ROLLOUT)
+    CPMPPI_LATENCY_BUFFER_INSTANCES(CPMPPI_MATCH_ROLLOUT)
+    CPMPPI_MID_INSTANCES(CPMPPI_MATCH_ROLLOUT)
+    CPMPPI_MID_BUFFER_INSTANCES(CPMPPI_MATCH_ROLLOUT)
+    CPMPPI_THROUGHPUT_INSTANCES(CPMPPI_MATCH_ROLLOUT)
+    CPMPPI_ODE_LATENCY_INSTANCES(CPMPPI_MATCH_ROLLOUT_ODE)
+    CPMPPI_ODE_THROUGHPUT_INSTANCES(CPMPPI_MATCH_ROLLOUT_ODE)
+    CPMPPI_ODE_LONE_INSTANCES(CPMPPI_MATCH_ROLLOUT_ODE)
+    CPMPPI_ODE_LATENCY_INSTANCES(CPMPPI_MATCH_ROLLOUT_ODE_ROWS)
+    CPMPPI_ODE_THROUGHPUT_INSTANCES(CPMPPI_MATCH_ROLLOUT_ODE_ROWS)
+    CPMPPI_ODE_LONE_INSTANCES(CPMPPI_MATCH_ROLLOUT_ODE_ROWS)
+    default: return nullptr;
   }
-  if (math == CPMPPI_MATH_FAST) {
-    // the throughput build reads its per-env constants from a.env_fold: written here, on the same stream, first
-    auto fold_first = [&]() -> hipError_t {
-      const uint32_t envs = grid.x / a.nb;
-      hipLaunchKernelGGL(fold_env_kernel, dim3((envs + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, p, a.L, a.te, a.s0,
-                         const_cast<EnvFold*>(a.env_fold), envs);
-      return hipGetLastError();
-    };
-    if (rpl == 2) {
-      const bool mid = (uint64_t)grid.x * BLOCK * 2 <= MID_SIZE_MAX_ROLLOUTS;
-      // at most one wave per SIMD (256 CUs x 4): the phased build with the quiet control step unrolled
-      if ((uint64_t)grid.x * WAVES <= lone_form_max_waves()) return CPMPPI_LAUNCH_V(true, 2, 3);
-      if (mid) return CPMPPI_LAUNCH_V(true, 2, 2);
-      if (hipError_t fe = fold_first(); fe != hipSuccess) return fe;
-      return CPMPPI_LAUNCH_V(true, 2, 1);
-    }
-    const bool small = (uint64_t)grid.x * BLOCK <= latency_max_rollouts();
-    if (small) return CPMPPI_LAUNCH_V(true, 1, 0);
-    if (hipError_t fe = fold_first(); fe != hipSuccess) return fe;
-    return CPMPPI_LAUNCH_V(true, 1, 1);
-  }
-  return CPMPPI_LAUNCH_V(false, 1, 1);
-#undef CPMPPI_LAUNCH_V
 }
 
 }  // namespace
@@ -210,22 +169,36 @@ int fail(cpmppi_handle* h, int code, const std::string& msg) {
   return code;
 }
 
-hipError_t launch_rollout(cpmppi_handle* h, const Params& prm, uint32_t rpl, uint32_t noise, dim3 grid, size_t lds,
-                          hipStream_t s, const StepPtrs& a_in) {
-  uint32_t variant = 0;
-  hipError_t e;
+cpmppi_plan::RolloutPlan plan_launch(const cpmppi_handle* h, uint32_t E, uint32_t noise_kind) {
+  return cpmppi_plan::plan_rollout(h->cfg, h->prm.P, E, noise_kind, h->m_pole_rows != nullptr, g_knobs.limits);
+}
+
+int launch_rollout(cpmppi_handle* h, const Params& prm, const cpmppi_plan::RolloutPlan& plan, hipStream_t s, const StepPtrs& a_in) {
+  const RolloutKernel kernel = find_rollout_kernel(prm.cost_id, plan);
+  if (!kernel)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "launch_rollout: no build of the rollout kernel for cost " + std::to_string(prm.cost_id) +
+                ", FAST " + std::to_string(plan.fast) + ", noise " + std::to_string(plan.noise) + ", R " + std::to_string(plan.rpl) +
+                ", variant " + std::to_string(plan.variant) + ", predictor " + std::to_string(plan.integ));
   StepPtrs a = a_in;
   a.env_fold = h->env_fold;
   a.m_pole = h->m_pole_rows;                       // (NULL on every predictor_ODE_v0 handle: cpmppi_set_pole_mass_rows refuses those)
-  switch (prm.cost_id) {
-    case CPMPPI_COST_QBGM: e = launch_rollout_math<COST_QBGM>(h->cfg.math_mode, h->cfg.ode_predictor, rpl, noise, grid, lds, s, prm, a, &variant); break;
-    case CPMPPI_COST_DEFAULT: e = launch_rollout_math<COST_DEFAULT>(h->cfg.math_mode, h->cfg.ode_predictor, rpl, noise, grid, lds, s, prm, a, &variant); break;
-    case CPMPPI_COST_QBG: e = launch_rollout_math<COST_QBG>(h->cfg.math_mode, h->cfg.ode_predictor, rpl, noise, grid, lds, s, prm, a, &variant); break;
-    default: e = launch_rollout_math<COST_LEGACY>(h->cfg.math_mode, h->cfg.ode_predictor, rpl, noise, grid, lds, s, prm, a, &variant); break;
+  if (plan.fold_first) {
+    const uint32_t envs = plan.blocks / plan.nb;
+    hipLaunchKernelGGL(fold_env_kernel, dim3((envs + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, prm, a.L, a.te, a.s0, h->env_fold, envs);
+    CPMPPI_HIP(h, hipGetLastError());
   }
-  h->last_launch = cpmppi_launch_info{prm.cost_id, h->cfg.math_mode, noise, rpl, variant, h->cfg.ode_predictor, grid.x,
-                                      prm.qb_mode == 1u ? (uint32_t)CPMPPI_COST_QB : (prm.qb_mode == 2u ? (uint32_t)CPMPPI_COST_QB_NONCONVEX : prm.cost_id)};
-  return e;
+  size_t lds = plan.lds_bytes;
+  if (g_knobs.lds_pad && plan.noise == CPMPPI_NOISE_PHILOX) {
+    // development aid (tools/dev/placement.py): CPMPPI_LDS_PAD=<bytes> of extra dynamic LDS per workgroup caps how many
+    // workgroups the dispatcher can put on one CU (160 KB each)
+    lds += (size_t)g_knobs.lds_pad;
+    (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kernel), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  }
+  hipLaunchKernelGGL(kernel, dim3(plan.blocks), dim3(BLOCK), lds, s, prm, a);
+  h->last_launch = cpmppi_launch_info{prm.cost_id, h->cfg.math_mode, plan.noise, plan.rpl, plan.variant, h->cfg.ode_predictor,
+                                      plan.blocks, h->cfg.cost_id};
+  CPMPPI_HIP(h, hipGetLastError());
+  return CPMPPI_OK;
 }
 
 int check_step(cpmppi_handle* h, const cpmppi_step_args* a) {
@@ -257,84 +230,102 @@ int check_step(cpmppi_handle* h, const cpmppi_step_args* a) {
   return CPMPPI_OK;
 }
 
-int step_impl(cpmppi_handle* h, const cpmppi_step_args* a, void* stream, uint32_t* host_ticket,
-              const cpmppi_comm::GatherTicket* gather) {
-  if (const int rc = check_step(h, a); rc != CPMPPI_OK) return rc;
-  CPMPPI_ON_DEVICE(h);
-  StepPtrs p{};
-  p.s0 = a->s0; p.u_nom = a->u_nom; p.u_prev = a->u_prev; p.x_t = a->target_position; p.te = a->target_equilibrium;
-  p.L = a->L; p.noise = a->noise; p.prev_in = a->previous_input; p.seed = a->seed; p.offset = a->offset; p.env_offset = a->env_offset;
-  p.offset_dev = (a->noise_kind == CPMPPI_NOISE_PHILOX) ? (const unsigned long long*)a->offset_dev : nullptr;
-  const uint32_t rpl = rollouts_per_lane(h, a->E);
-  p.nb = (h->cfg.N + BLOCK * rpl - 1) / (BLOCK * rpl);
-  uint32_t noise_kind = a->noise_kind;
-  const hipStream_t s = (hipStream_t)stream;
-  const bool du_space = (noise_kind == CPMPPI_NOISE_DELTA_U || noise_kind == CPMPPI_NOISE_DELTA_U_TILED);
-  p.W = du_space ? h->cfg.H : h->prm.P;
-  p.S_out = a->S_out; p.partial = h->workspace;
-  p.counter = nullptr; p.u_nom_out = a->u_nom_out ? a->u_nom_out : a->u_nom; p.Q_out = a->Q_out;
-  p.host_ticket = host_ticket;
-  p.gs = gather ? GatherSync{gather->flags, gather->publish, gather->need, gather->envs ? gather->envs : a->E} : GatherSync{nullptr, 0u, 0u, 0u};
-  hipEvent_t* ev = nullptr;
-  const uint32_t group_pos = h->profile_every ? h->profile_count++ % h->profile_every : 0;
-  const bool grouped = h->profile_every > 1;
-  if (h->profile_every && group_pos == 0) {
-    if (h->ev_used + 3 > h->ev.size()) {
-      for (int i = 0; i < 3; ++i) {
-        hipEvent_t e;
-        CPMPPI_HIP(h, hipEventCreate(&e));
-        h->ev.push_back(e);
-      }
+// ---- the event recorder of cpmppi_set_profiling: a step's launch sequence calls begin, after_rollout and end in that order ----
+// handle state: ev (triples: before the rollout kernel, after it, after the trailing kernels), ev_tail, ev_used, group_open,
+// profile_count; cpmppi_get_profile reads and resets it
+namespace {
+
+struct StepBracket {
+  hipEvent_t* ev = nullptr;      // this step's triple: profile_every == 1 only (no events inside a group)
+  uint32_t group_pos = 0;
+};
+
+int profile_begin(cpmppi_handle* h, hipStream_t s, StepBracket* b) {
+  if (!h->profile_every) return CPMPPI_OK;
+  b->group_pos = h->profile_count++ % h->profile_every;
+  if (b->group_pos != 0) return CPMPPI_OK;
+  if (h->ev_used + 3 > h->ev.size()) {
+    for (int i = 0; i < 3; ++i) {
+      hipEvent_t e;
+      CPMPPI_HIP(h, hipEventCreate(&e));
+      h->ev.push_back(e);
     }
-    ev = &h->ev[h->ev_used];
-    if (h->ev_tail.size() < h->ev.size() / 3) h->ev_tail.resize(h->ev.size() / 3, 0);
-    h->ev_used += 3;
-    h->group_open = grouped;
-    CPMPPI_HIP(h, hipEventRecord(ev[0], s));
   }
-  if (grouped) ev = nullptr;                       // (no events inside a group)
-  if (a->predictor == CPMPPI_PREDICTOR_GRU) {
-    p.nb = (h->cfg.N + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK;
-    launch_gru_rollout(h, a, p, s);
-    CPMPPI_HIP(h, hipGetLastError());
-  } else {
-    p.counter = h->fuse_finalize ? h->counters : nullptr;
-    size_t lds = (size_t)WAVES * p.W * sizeof(float);
-    p.stash = 0;
-    if (a->noise_kind == CPMPPI_NOISE_PHILOX) {                 // park the generated knots in LDS when they fit
-      const size_t park = (size_t)p.W * rpl * BLOCK * sizeof(float);
-      if (lds + park <= 32 * 1024) { p.stash = 1; lds += park; }
-    }
-    CPMPPI_HIP(h, launch_rollout(h, h->prm, rpl, noise_kind, dim3(a->E * p.nb), lds, s, p));
-  }
-  const bool separate_finalize = (p.counter == nullptr);
-  if (ev) CPMPPI_HIP(h, hipEventRecord(ev[1], s));
-  if (separate_finalize) {
-    if (du_space)
-      hipLaunchKernelGGL(finalize_kernel<false>, dim3(a->E), dim3(BLOCK), 0, s, h->prm, (const float*)h->workspace,
-                         p.nb, p.W, (const float*)a->u_nom, p.u_nom_out, a->Q_out, p.gs);
-    else
-      hipLaunchKernelGGL(finalize_kernel<true>, dim3(a->E), dim3(BLOCK), 0, s, h->prm, (const float*)h->workspace,
-                         p.nb, p.W, (const float*)a->u_nom, p.u_nom_out, a->Q_out, p.gs);
-  }
-  CPMPPI_HIP(h, hipGetLastError());
-  if (p.offset_dev) {
-    hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s, (unsigned long long*)a->offset_dev);
-    CPMPPI_HIP(h, hipGetLastError());
-  }
-  if (ev) {
+  hipEvent_t* ev = &h->ev[h->ev_used];
+  if (h->ev_tail.size() < h->ev.size() / 3) h->ev_tail.resize(h->ev.size() / 3, 0);
+  h->ev_used += 3;
+  h->group_open = h->profile_every > 1;
+  CPMPPI_HIP(h, hipEventRecord(ev[0], s));
+  if (!h->group_open) b->ev = ev;
+  return CPMPPI_OK;
+}
+
+int profile_after_rollout(cpmppi_handle* h, hipStream_t s, const StepBracket& b) {
+  if (b.ev) CPMPPI_HIP(h, hipEventRecord(b.ev[1], s));
+  return CPMPPI_OK;
+}
+
+// tail: something ran after the rollout kernel (a separate finalize, the counter bump)
+int profile_end(cpmppi_handle* h, hipStream_t s, const StepBracket& b, bool tail) {
+  if (b.ev) {
     // an event costs ~5 us on the stream: the third one only if something ran after the rollout kernel
-    const bool tail = separate_finalize || p.offset_dev;
-    h->ev_tail[(size_t)(ev - h->ev.data()) / 3] = tail ? 1 : 0;
-    if (tail) CPMPPI_HIP(h, hipEventRecord(ev[2], s));
+    h->ev_tail[(size_t)(b.ev - h->ev.data()) / 3] = tail ? 1 : 0;
+    if (tail) CPMPPI_HIP(h, hipEventRecord(b.ev[2], s));
   }
-  if (grouped && h->group_open && group_pos == h->profile_every - 1) {     // the group's last step: close the bracket
+  if (h->profile_every > 1 && h->group_open && b.group_pos == h->profile_every - 1) {     // the group's last step: close the bracket
     hipEvent_t* g = &h->ev[h->ev_used - 3];
     h->ev_tail[(h->ev_used - 3) / 3] = 0;
     CPMPPI_HIP(h, hipEventRecord(g[1], s));
     h->group_open = false;
   }
   return CPMPPI_OK;
+}
+
+}  // namespace
+
+// check -> plan -> bracket -> launch -> finalize -> bump the counter
+int step_impl(cpmppi_handle* h, const cpmppi_step_args* a, void* stream, uint32_t* host_ticket,
+              const cpmppi_comm::GatherTicket* gather) {
+  if (const int rc = check_step(h, a); rc != CPMPPI_OK) return rc;
+  CPMPPI_ON_DEVICE(h);
+  const cpmppi_plan::RolloutPlan plan = plan_launch(h, a->E, a->noise_kind);
+  const bool gru = a->predictor == CPMPPI_PREDICTOR_GRU;
+  const hipStream_t s = (hipStream_t)stream;
+  StepPtrs p{};
+  p.s0 = a->s0; p.u_nom = a->u_nom; p.u_prev = a->u_prev; p.x_t = a->target_position; p.te = a->target_equilibrium;
+  p.L = a->L; p.noise = a->noise; p.prev_in = a->previous_input; p.seed = a->seed; p.offset = a->offset; p.env_offset = a->env_offset;
+  p.offset_dev = (a->noise_kind == CPMPPI_NOISE_PHILOX) ? (const unsigned long long*)a->offset_dev : nullptr;
+  // (the GRU rollout kernel has its own block split and never parks knots; it is no part of the plan)
+  p.nb = gru ? (h->cfg.N + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK : plan.nb;
+  p.W = plan.W;
+  p.stash = gru ? 0u : plan.stash;
+  p.S_out = a->S_out; p.partial = h->workspace;
+  p.counter = (!gru && h->fuse_finalize) ? h->counters : nullptr;
+  p.u_nom_out = a->u_nom_out ? a->u_nom_out : a->u_nom; p.Q_out = a->Q_out;
+  p.host_ticket = host_ticket;
+  p.gs = gather ? GatherSync{gather->flags, gather->publish, gather->need, gather->envs ? gather->envs : a->E} : GatherSync{nullptr, 0u, 0u, 0u};
+  StepBracket bracket;
+  if (const int rc = profile_begin(h, s, &bracket); rc != CPMPPI_OK) return rc;
+  if (gru) {
+    launch_gru_rollout(h, a, p, s);
+    CPMPPI_HIP(h, hipGetLastError());
+  } else if (const int rc = launch_rollout(h, h->prm, plan, s, p); rc != CPMPPI_OK) {
+    return rc;
+  }
+  if (const int rc = profile_after_rollout(h, s, bracket); rc != CPMPPI_OK) return rc;
+  const bool separate_finalize = (p.counter == nullptr);
+  if (separate_finalize) {
+    const bool du_space = (a->noise_kind == CPMPPI_NOISE_DELTA_U || a->noise_kind == CPMPPI_NOISE_DELTA_U_TILED);
+    const auto finalize = du_space ? finalize_kernel<false> : finalize_kernel<true>;
+    hipLaunchKernelGGL(finalize, dim3(a->E), dim3(BLOCK), 0, s, h->prm, (const float*)h->workspace, p.nb, p.W,
+                       (const float*)a->u_nom, p.u_nom_out, a->Q_out, p.gs);
+  }
+  CPMPPI_HIP(h, hipGetLastError());
+  if (p.offset_dev) {
+    hipLaunchKernelGGL(bump_counter_kernel, dim3(1), dim3(1), 0, s, (unsigned long long*)a->offset_dev);
+    CPMPPI_HIP(h, hipGetLastError());
+  }
+  return profile_end(h, s, bracket, separate_finalize || p.offset_dev);
 }
 
 extern "C" {
@@ -432,12 +423,11 @@ int cpmppi_get_config(const cpmppi_handle* h, cpmppi_config* out) {
 int cpmppi_set_cost_weights(cpmppi_handle* h, uint32_t cost_id, const float* cost_w, uint32_t n) {
   if (!h || !cost_w || n > 24 || cost_id > CPMPPI_COST_QB_NONCONVEX)
     return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_cost_weights: bad argument");
-  const bool qb = cost_id == CPMPPI_COST_QB || cost_id == CPMPPI_COST_QB_NONCONVEX;   // default.py's kernels + sub-mode (fill_params)
+  const bool qb = cost_id == CPMPPI_COST_QB || cost_id == CPMPPI_COST_QB_NONCONVEX;
   if (qb && h->cfg.ode_predictor != CPMPPI_ODE_V0)
     return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_cost_weights: quadratic_boundary / _nonconvex are built for predictor_ODE_v0");
   h->cfg.cost_id = cost_id;
-  h->prm.cost_id = qb ? (uint32_t)CPMPPI_COST_DEFAULT : cost_id;
-  h->prm.qb_mode = qb ? (cost_id == CPMPPI_COST_QB ? 1u : 2u) : 0u;
+  set_kernel_cost(h->prm, cost_id);
   for (uint32_t i = 0; i < n; ++i) h->cfg.cost_w[i] = h->prm.w[i] = cost_w[i];
   return CPMPPI_OK;
 }

@@ -1,7 +1,8 @@
 // cpmppi_internal.hpp — where the translation units of libcpmppi.so meet beside the public header: the handle's layout, the
 // error and device helpers of every entry point, and the few host functions one unit calls in another.
-//   cpmppi.hip            the hot path: handle lifecycle, cpmppi_step / _step_gather / _step_host, the rollout launch dispatch,
-//                         profiling, streams
+//   cpmppi.hip            the hot path: handle lifecycle, cpmppi_step / _step_gather / _step_host, the rollout kernel lookup and
+//                         launch, profiling, streams
+//   cpmppi_launch_plan.hpp  the launch policy (which build of the rollout kernel, block split, LDS): one pure host function
 //   cpmppi_seams.hip      sampler, tiling, predictor, trajectory cost and reward-weighted-average seams
 //   cpmppi_plant.hip      the simulated plant (cpmppi_plant_*)
 //   cpmppi_optim.hip      cost-only rollouts, the adjoint, Adam / SGD steps and CEM
@@ -16,6 +17,7 @@
 #include <vector>
 #include "cpmppi.h"
 #include "cpmppi_rollout.hpp"      // (declares, never instantiates, rollout_cost_kernel: only cpmppi_rollout_*.hip define it)
+#include "cpmppi_launch_plan.hpp"
 
 namespace cpmppi_comm {
 struct CommState;                                        // cpmppi_comm.hip
@@ -133,27 +135,20 @@ void allow_large_lds(Kernel* kernel) {
 // GRU predictor (BASELINE configs[4]): 256 threads = 4 waves x 32 rollouts
 constexpr int GRU_ROLLOUTS_PER_BLOCK = 32 * cpmppi_k::WAVES;
 
-// Lane mapping: two rollouts per lane (packed float2) once the launch fills every SIMD with at least one such wave
-// (1024 SIMDs x 128 rollouts); one rollout per lane (shortest critical path) below.  Measured at 128 envs x 1024 x 50:
-// 76 us packed vs 90 us one per lane; at 64 envs the packed mapping would leave half the SIMDs empty.
-constexpr uint64_t PACKED_MIN_ROLLOUTS = 131072ull;
-inline uint32_t rollouts_per_lane(const cpmppi_handle* h, uint32_t E) {
-  if (h->cfg.math_mode != CPMPPI_MATH_FAST) return 1;
-  if (h->cfg.rollouts_per_lane != 0) return h->cfg.rollouts_per_lane;
-  return ((uint64_t)E * h->cfg.N >= PACKED_MIN_ROLLOUTS) ? 2 : 1;
-}
-
 // ---- host functions one unit calls in another -------------------------------------------------------------------------
 // cpmppi.hip.  check_step: every check of a step's argument block that needs no launch (cpmppi_groups_run_gather runs them for
 // all groups before its first launch).  step_impl: cpmppi_step, with the pinned ticket of cpmppi_step_host and / or the
 // step-gather whose finalize it takes part in (cpmppi_step_gather; cpmppi_groups_run_gather, where the ticket is shared by the
-// launches of every group).  launch_rollout: the rollout_cost_kernel instance for the handle's configuration; `prm` is the
-// kernel-argument block of THIS launch (the handle's, or a modified copy: cost-only launches).
+// launches of every group).  plan_launch: the launch plan (cpmppi_launch_plan.hpp: which build of rollout_cost_kernel, its grid,
+// block split and LDS) of E envs of this handle.  launch_rollout: launches what the plan names and records it for
+// cpmppi_last_launch; `prm` is the kernel-argument block of THIS launch (the handle's, or a modified copy: cost-only launches), and
+// the caller has filled nb, W and stash of the pointer block from the same plan.
 int check_step(cpmppi_handle* h, const cpmppi_step_args* a);
 int step_impl(cpmppi_handle* h, const cpmppi_step_args* a, void* stream, uint32_t* host_ticket,
               const cpmppi_comm::GatherTicket* gather = nullptr);
-hipError_t launch_rollout(cpmppi_handle* h, const cpmppi::Params& prm, uint32_t rpl, uint32_t noise, dim3 grid, size_t lds,
-                          hipStream_t s, const cpmppi_k::StepPtrs& a_in);
+cpmppi_plan::RolloutPlan plan_launch(const cpmppi_handle* h, uint32_t E, uint32_t noise_kind);
+int launch_rollout(cpmppi_handle* h, const cpmppi::Params& prm, const cpmppi_plan::RolloutPlan& plan, hipStream_t s,
+                   const cpmppi_k::StepPtrs& a_in);
 // cpmppi_plant.hip: every check of a plant step's argument block that needs no launch (see check_step)
 int check_plant(cpmppi_handle* h, const cpmppi_plant_args* a);
 // cpmppi_gru.hip: the fused GRU rollout kernel of a step (p.nb counted in GRU blocks); the caller checks the launch

@@ -294,17 +294,13 @@ int cpmppi_rollout_cost(cpmppi_handle* h, uint32_t E, const float* s0, const flo
   Params prm = h->prm;
   prm.shift_mode = CPMPPI_SHIFT_NONE;
   prm.cc_weight = 0.0f;
+  // (a cost-only launch: the inputs are the perturbations of a zero nominal sequence; no finalize)
+  const cpmppi_plan::RolloutPlan plan = plan_launch(h, E, CPMPPI_NOISE_DELTA_U);
   StepPtrs p{};
-  p.s0 = s0; p.u_nom = h->zeros_H; p.u_prev = nullptr; p.x_t = target_position; p.te = target_equilibrium; p.L = L;
-  p.noise = inputs; p.prev_in = nullptr; p.seed = 0; p.offset = 0; p.offset_dev = nullptr; p.env_offset = 0; p.stash = 0;
-  const uint32_t rpl = rollouts_per_lane(h, E);
-  p.nb = (h->cfg.N + BLOCK * rpl - 1) / (BLOCK * rpl);
-  p.W = h->cfg.H;
-  p.S_out = S_out; p.partial = h->workspace; p.counter = nullptr; p.u_nom_out = nullptr; p.Q_out = nullptr;
-  hipError_t e = launch_rollout(h, prm, rpl, CPMPPI_NOISE_DELTA_U, dim3(E * p.nb), (size_t)WAVES * p.W * sizeof(float),
-                                (hipStream_t)stream, p);
-  CPMPPI_HIP(h, e);
-  return CPMPPI_OK;
+  p.s0 = s0; p.u_nom = h->zeros_H; p.x_t = target_position; p.te = target_equilibrium; p.L = L; p.noise = inputs;
+  p.nb = plan.nb; p.W = plan.W; p.stash = plan.stash;
+  p.S_out = S_out; p.partial = h->workspace;
+  return launch_rollout(h, prm, plan, (hipStream_t)stream, p);
 }
 
 int cpmppi_rollout_cost_grad(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs,

@@ -88,7 +88,7 @@ struct StepPtrs {
   float* Q_out;
   uint32_t* host_ticket; // cpmppi_step_host: counter in pinned host memory, +1 (system scope) per finalized env; NULL otherwise
   GatherSync gs;
-  const EnvFold* env_fold;   // [envs of this launch] per-env constants (throughput build, FAST, predictor_ODE_v0: launch_rollout_math fills it first;
+  const EnvFold* env_fold;   // [envs of this launch] per-env constants (throughput build, FAST, predictor_ODE_v0: launch_rollout fills it first;
                              // behind the fields the latency builds were tuned with: they keep their kernarg offsets)
   const float* m_pole;       // [envs of this launch] predictor_ODE: the pole mass each env's rollouts are integrated with
                              // (cpmppi_set_pole_mass_rows); launch_rollout fills it.  Read by rollout_cost_rows_kernel only, which is
@@ -275,20 +275,15 @@ __device__ __forceinline__ void finalize_env(const Params& p, const float* parti
 #undef CPMPPI_ROLLOUT_MASS_ROWS
 #undef CPMPPI_ROLLOUT_INTEG_DEFAULT
 
-// the kernel of a launch: rollout_cost_kernel<..., INTEG>, or rollout_cost_rows_kernel<...> for INTEG = PREDICTOR_ODE_ROWS
-template <int COST, bool FAST, int NOISE, int R, int V, int INTEG>
-constexpr auto rollout_kernel_for() {
-  if constexpr (INTEG == PREDICTOR_ODE_ROWS) return &rollout_cost_rows_kernel<COST, FAST, NOISE, R, V, PREDICTOR_ODE>;
-  else return &rollout_cost_kernel<COST, FAST, NOISE, R, V, INTEG>;
-}
-
 }  // namespace cpmppi_k
 
 // Every instantiation of rollout_cost_kernel, by the translation unit that compiles it.  X(COST, FAST, NOISE, R, VARIANT).
 // The units define them with CPMPPI_DEFINE_ROLLOUT, cpmppi.hip (the hot-path unit, the only one that launches them) declares
-// ALL of them extern with CPMPPI_DECLARE_ROLLOUT — an instantiation missing there would be compiled a second time in
-// cpmppi.hip with that unit's flags, and the runtime would launch whichever copy registered last.  The other units include
-// this header (through cpmppi_internal.hpp) for StepPtrs, GatherSync and the constants only, and instantiate nothing of it.
+// ALL of them extern with CPMPPI_DECLARE_ROLLOUT and generates its kernel lookup from these same lists, so it can name no
+// instantiation that is not declared extern there (one it instantiated itself would be compiled a second time with that
+// unit's flags, and the runtime would launch whichever copy registered last); an instantiation listed in two units is a
+// duplicate case of that lookup.  The other units include this header (through cpmppi_internal.hpp) for StepPtrs, GatherSync
+// and the constants only, and instantiate nothing of it.
 #define CPMPPI_FOR_COSTS(X, FAST, NOISE, R, V) \
   X(COST_QBGM, FAST, NOISE, R, V) X(COST_DEFAULT, FAST, NOISE, R, V) X(COST_LEGACY, FAST, NOISE, R, V) X(COST_QBG, FAST, NOISE, R, V)
 #define CPMPPI_FOR_NOISES(X, FAST, R, V)                                                        \

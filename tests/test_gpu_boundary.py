@@ -391,15 +391,16 @@ def test_predict_large_launch_equals_small_launches(math_mode):
 
 
 @pytest.mark.parametrize("noise", ["philox", "knots"])
-@pytest.mark.parametrize("rpl,small_E,big_E,H", [(2, 200, 1600, 70), (2, 100, 1600, 70), (1, 32, 100, 70), (1, 32, 100, 150)])
+@pytest.mark.parametrize("rpl,small_E,big_E,H", [(2, 200, 1600, 70), (2, 100, 1600, 70), (1, 32, 129, 70), (1, 32, 129, 150)])
 def test_builds_of_the_kernel_agree_bit_for_bit(rpl, small_E, big_E, H, noise):
     """The rollout kernel exists in three builds chosen by launch size (latency / mid-size / throughput: different
     scheduling strategies, constants in scalar or vector registers, triples with rollback or not, the nominal sequence
     read from memory per control step or held in lanes and fetched with v_readlane).  An env's result must not depend on
     which build integrated it: the first envs of a large launch (throughput build: > 1.5 M rollouts with two per lane,
-    > 65 536 with one) equal, bit for bit, the same envs in a launch small enough for the mid-size (two rollouts per lane:
-    200 envs; 100 envs = at most one wave per SIMD, the build with the quiet control step unrolled) or latency (one per
-    lane) build.  The nominal sequence is nonzero and the horizon longer than 64 steps (the lanes of
+    more than 131 071 lanes with one: 129 envs x 1024 is 516 blocks) equal, bit for bit, the same envs in a launch small enough
+    for the mid-size (two rollouts per lane: 200 envs; 100 envs = at most one wave per SIMD, the build with the quiet control
+    step unrolled) or latency (one per lane) build.  The build_variant that the large and the small launch report is asserted:
+    without that the comparison goes vacuous whenever the limits move (launch_table.py).  The nominal sequence is nonzero and the horizon longer than 64 steps (the lanes of
     one register; 150: three register loads), with in-kernel noise and with knots from memory (the latency build holds
     the sequence in lanes only then)."""
     from cartpolesimulation_amd.engine import MPPIEngine
@@ -414,7 +415,7 @@ def test_builds_of_the_kernel_agree_bit_for_bit(rpl, small_E, big_E, H, noise):
     tp = rng.uniform(-0.1, 0.1, big_E).astype(f32)
     Lv = rng.uniform(0.25, 0.45, big_E).astype(f32)
     u0 = rng.uniform(-0.6, 0.6, (big_E, H)).astype(f32)
-    outs = []
+    outs, launched = [], []
     for E in (big_E, small_E):
         eng = MPPIEngine(E, cfg)
         un, S = eng.tensor(u0[:E].copy()), eng.empty(E, N)
@@ -423,8 +424,11 @@ def test_builds_of_the_kernel_agree_bit_for_bit(rpl, small_E, big_E, H, noise):
             Q, _ = eng.step(s0[:E], un, tp[:E], np.ones(E, f32), L=Lv[:E], knots=kn, S_out=S)
         else:
             Q, _ = eng.step(s0[:E], un, tp[:E], np.ones(E, f32), L=Lv[:E], seed=5, offset=3, env_offset=0, S_out=S)
+        launched.append(eng.last_launch()["build_variant"])
         outs.append((Q.cpu().numpy()[:small_E], un.cpu().numpy()[:small_E], S.cpu().numpy()[:small_E]))
         eng.close()
+    # (large launch, small launch): throughput build against mid-size / its lone-wave form / latency build
+    assert tuple(launched) == {(2, 200): (1, 2), (2, 100): (1, 3), (1, 32): (1, 0)}[rpl, small_E]
     for a, b in zip(*outs):
         assert np.array_equal(a, b)
     assert np.abs(outs[0][1] - u0[:small_E]).max() > 1e-3                   # the step did update the sequence

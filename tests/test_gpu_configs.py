@@ -135,7 +135,8 @@ def test_config_full_size(name, E, N, H, seed):
     assert np.array_equal(un2.cpu().numpy(), un_h)
     # stepped alone with the SAME lane mapping: bit-identical; with the other mapping (its intermediate substeps carry
     # the rotation differently): the same update to within the parity tolerance
-    rpl_batch = 2 if E * N >= 131072 else 1                  # the library's lane-mapping rule (cpmppi.hip PACKED_MIN_ROLLOUTS)
+    rpl_batch = eng.last_launch()["rollouts_per_lane"]       # the lane mapping the batch got (cpmppi_launch_plan.hpp)
+    assert rpl_batch in (1, 2)
     for rpl, exact in ((rpl_batch, True), (3 - rpl_batch, False)):
         small = make(1, N, H, rollouts_per_lane=rpl)
         for e in (1, E - 2):
