@@ -61,6 +61,8 @@ struct cpmppi_handle {
   void* gru16_image = nullptr;         // device copy of the f16 split image (cpmppi_gru16.hpp)
   float* grad_ckpt = nullptr;          // [H][6][E*N] check-points of cpmppi_rollout_cost_grad (allocated on first use)
   size_t grad_ckpt_floats = 0;
+  float* rpgd_ws = nullptr;            // cpmppi_rpgd_step: check-points [E][H][6][block] then gradients [E][H][block] (cpmppi_rpgd_reserve)
+  size_t rpgd_ws_floats = 0;
   cpmppi::GruNorm gru_norm;
   bool fuse_finalize = true;           // ODE path: the env's last block finalizes in-kernel (CPMPPI_FUSE_FINALIZE=0 disables)
   uint32_t profile_every = 0;          // 0 = off, 1 = every rollout kernel bracketed, n > 1 = one bracket around n steps

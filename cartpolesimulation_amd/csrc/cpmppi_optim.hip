@@ -6,6 +6,7 @@
 //   adam_step_kernel, sgd_step_kernel     gradient steps with per-rollout norm clipping and the action limits.
 //   cem_sample_kernel, cem_gmm_sample_kernel   CEM's sampler: one Gaussian per env, or a mixture of K elite-centred ones.
 //   cem_update_kernel                     top-k (bitonic sort in LDS) -> mean and stdev of the elite.
+//   rpgd_step_kernel<COST, INTEG>         the whole rpgd / gradient-tf control step, one workgroup per env (cpmppi_rpgd.hpp).
 // cpmppi_rollout_cost launches rollout_cost_kernel through launch_rollout (cpmppi.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -14,6 +15,7 @@
 #include "cpmppi.h"
 #include "cpmppi_internal.hpp"
 #include "cpmppi_grad.hpp"
+#include "cpmppi_rpgd.hpp"
 
 using namespace cpmppi_k;
 
@@ -256,6 +258,117 @@ __global__ __launch_bounds__(BLOCK) void cem_update_kernel(const Params p, const
   }
 }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The fused rpgd / gradient-tf control step (cpmppi_rpgd_step; device pieces in cpmppi_rpgd.hpp).  One workgroup = one env,
+// one lane = one plan; the block is N rounded up to whole waves, the surplus lanes only keep the barriers company.  A lane
+// carries its own row of Q, m, v through `iterations` x (adjoint sweep + Adam) and the final forward sweep: nothing crosses
+// lanes until the ranking.  Ranking: every lane counts the (key, index) pairs below its own among the N keys in LDS - the stable
+// order of cem_update_kernel.  Permutation + shift run column by column: every lane reads column k + shift of its SOURCE row,
+// the block meets, every lane writes column k of its OWN row; columns <= k are never read again, so one barrier per column.
+struct RpgdPtrs {
+  const float* s0; const float* x_t; const float* te; const float* L; const float* prev_in; const float* m_pole;
+  float* Q; float* m; float* v;
+  float* ckpt;            // [E][H][6][block]
+  float* grad;            // [E][H][block]
+  const unsigned long long* count_dev;
+  unsigned long long count, seed, draw_offset;
+  uint32_t iterations, adam_iteration, keep_k, resamp_per, shift, uniform, env_offset;
+  float lr, beta1, beta2, eps, gradmax_clip, sample_mean, uniform_lo, uniform_hi;
+  float* Q_out; float* S_out; float* plan_out; uint32_t* order_out;
+};
+
+template <int COST, int INTEG>
+__global__ __launch_bounds__(BLOCK) void rpgd_step_kernel(const Params p, const RpgdPtrs a) {
+  extern __shared__ float rpgd_lds[];               // sub[S][6][block] | key[block] | order[block]
+  const uint32_t tid = threadIdx.x, Nb = blockDim.x, env = blockIdx.x, N = p.N, H = p.H;
+  uint32_t* key = reinterpret_cast<uint32_t*>(rpgd_lds + (size_t)p.S * 6 * Nb);
+  uint32_t* order = key + Nb;
+  const bool active = tid < N;
+  const uint64_t c = a.count_dev ? (uint64_t)*a.count_dev : (uint64_t)a.count;
+  const uint64_t it0 = a.count_dev ? c * a.iterations : (uint64_t)a.adam_iteration;
+  const size_t row = ((size_t)env * N + tid) * H;
+  float S = 0.0f;
+  if (active) {
+    Params pm_;
+    if constexpr (INTEG == PREDICTOR_ODE) pm_ = with_pole_mass(p, a.m_pole ? a.m_pole[env] : p.m_pole);
+    const Params& pi = (INTEG == PREDICTOR_ODE) ? pm_ : p;
+    const EnvConst ec = make_env_const(pi, a.L ? a.L[env] : p.L_default);
+    RpgdLane w;
+    w.s0 = a.s0 + (size_t)env * 6;
+    w.Q = a.Q + row;
+    w.x_t = a.x_t[env]; w.te = a.te[env]; w.ub0 = a.prev_in ? a.prev_in[env] : 0.0f;
+    w.cos0 = cosf(w.s0[0]); w.sin0 = sinf(w.s0[0]);
+    w.scale = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? 1.0f : 1.0f / (float)(H + 1);
+    w.clip = p.control_mode == CPMPPI_CONTROL_CLIP;
+    w.stride = Nb;
+    w.ckpt = a.ckpt + (size_t)env * H * 6 * Nb + tid;
+    w.grad = a.grad + (size_t)env * H * Nb + tid;
+    w.sub = rpgd_lds + tid;
+    RpgdLr lr(a.beta1, a.beta2, it0);
+    for (uint32_t i = 1; i <= a.iterations + 1; ++i) {
+      const bool descend = i <= a.iterations;      // the last pass is the final cost: forward only
+      S = rpgd_sweep<COST, INTEG>(p, pi, ec, w, descend);
+      if (!descend) break;
+      const float lr_t = lr.next(a.lr, a.beta1, a.beta2);
+      rpgd_adam_row(H, a.Q + row, a.m + row, a.v + row, w.grad, Nb, lr_t, a.beta1, a.beta2, a.eps, a.gradmax_clip, p.lo, p.hi);
+    }
+    if (a.S_out) a.S_out[(size_t)env * N + tid] = S;
+  }
+  key[tid] = active ? cem_sort_key(S) : 0xFFFFFFFFu;
+  __syncthreads();
+  if (active) {
+    const uint32_t mine = key[tid];
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < N; ++j) {
+      const uint32_t kj = key[j];
+      rank += (kj < mine || (kj == mine && j < tid)) ? 1u : 0u;
+    }
+    order[rank] = tid;
+    if (a.order_out) a.order_out[(size_t)env * N + rank] = tid;
+  }
+  __syncthreads();
+  const float* best = a.Q + ((size_t)env * N + order[0]) * H;
+  if (tid == 0) a.Q_out[env] = best[0];
+  if (a.plan_out) for (uint32_t k = tid; k < H; k += Nb) a.plan_out[(size_t)env * H + k] = best[k];
+
+  const bool resample = a.resamp_per > 0 && a.keep_k < N && (c + 1) % a.resamp_per == 0;
+  if (!resample && a.shift == 0) return;             // (block-uniform)
+  const bool fresh = resample && tid >= a.keep_k;
+  const size_t src = ((size_t)env * N + ((resample && tid < a.keep_k) ? order[tid] : tid)) * H;
+  const uint64_t draw = a.draw_offset + (a.count_dev ? c / (a.resamp_per ? a.resamp_per : 1u) : 0ull);
+  RpgdFresh fr;
+  for (uint32_t k = 0; k < H; ++k) {
+    const uint32_t kk = k + a.shift;
+    const bool inside = kk < H;
+    const uint32_t kq = inside ? kk : H - 1;         // Q repeats its last element
+    float q = 0.0f, mk = 0.0f, vk = 0.0f;
+    if (active) {
+      if (fresh) {
+        q = rpgd_fresh(fr, p, a.seed, draw, a.env_offset + env, tid, kq, a.uniform != 0u, a.sample_mean, a.uniform_lo, a.uniform_hi);
+      } else {
+        q = a.Q[src + kq];
+        if (inside) { mk = a.m[src + kk]; vk = a.v[src + kk]; }
+      }
+    }
+    __syncthreads();
+    if (active) { a.Q[row + k] = q; a.m[row + k] = mk; a.v[row + k] = vk; }
+  }
+}
+
+__global__ void rpgd_count_kernel(unsigned long long* c) { *c += 1ull; }
+
+template <int INTEG>
+void launch_rpgd(uint32_t cost_id, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Params& p, const RpgdPtrs& a) {
+  switch (cost_id) {
+    case CPMPPI_COST_QBGM: hipLaunchKernelGGL((rpgd_step_kernel<COST_QBGM, INTEG>), grid, block, lds, st, p, a); break;
+    case CPMPPI_COST_DEFAULT: hipLaunchKernelGGL((rpgd_step_kernel<COST_DEFAULT, INTEG>), grid, block, lds, st, p, a); break;
+    default: hipLaunchKernelGGL((rpgd_step_kernel<COST_QBG, INTEG>), grid, block, lds, st, p, a); break;
+  }
+}
+
+inline uint32_t rpgd_block(const cpmppi_handle* h) { return (h->cfg.N + 63u) & ~63u; }
+inline size_t rpgd_floats(const cpmppi_handle* h, uint32_t E) { return (size_t)h->cfg.H * 7 * E * rpgd_block(h); }
+
 // rollout_grad_kernel for the handle's cost (the three costs it is built for: cpmppi_rollout_cost_grad's checks)
 template <int INTEG>
 void launch_grad(uint32_t cost_id, dim3 grid, size_t lds, hipStream_t st, const Params& p, const GradPtrs& a) {
@@ -276,6 +389,12 @@ void allow_large_lds_optim() {
   allow_large_lds(&rollout_grad_kernel<COST_QBGM, PREDICTOR_ODE>);
   allow_large_lds(&rollout_grad_kernel<COST_DEFAULT, PREDICTOR_ODE>);
   allow_large_lds(&rollout_grad_kernel<COST_QBG, PREDICTOR_ODE>);
+  allow_large_lds(&rpgd_step_kernel<COST_QBGM, PREDICTOR_ODE_V0>);
+  allow_large_lds(&rpgd_step_kernel<COST_DEFAULT, PREDICTOR_ODE_V0>);
+  allow_large_lds(&rpgd_step_kernel<COST_QBG, PREDICTOR_ODE_V0>);
+  allow_large_lds(&rpgd_step_kernel<COST_QBGM, PREDICTOR_ODE>);
+  allow_large_lds(&rpgd_step_kernel<COST_DEFAULT, PREDICTOR_ODE>);
+  allow_large_lds(&rpgd_step_kernel<COST_QBG, PREDICTOR_ODE>);
   // the CEM top-k sorts N (padded to a power of two) 8-byte records in LDS: 128 KB at N = 16384
   allow_large_lds(&cem_update_kernel);
 }
@@ -346,6 +465,86 @@ int cpmppi_adam_step(cpmppi_handle* h, uint32_t E, float* Q, const float* grad, 
                       (1.0 - pow((double)beta1, (double)iteration));
   hipLaunchKernelGGL(adam_step_kernel, dim3((unsigned)((rows + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream,
                      rows, h->cfg.H, Q, grad, m, v, (float)lr_t, beta1, beta2, epsilon, gradmax_clip, h->prm.lo, h->prm.hi);
+  return launched(h);
+}
+
+// what cpmppi_rpgd_step and cpmppi_rpgd_reserve refuse about the HANDLE (cpmppi_rollout_cost_grad's list, plus the block)
+static int rpgd_check_handle(cpmppi_handle* h, const char* who) {
+  const std::string w(who);
+  if (h->prm.cost_id == CPMPPI_COST_LEGACY) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": plugin costs only");
+  if (h->prm.qb_mode != 0u)
+    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": no adjoint for quadratic_boundary / quadratic_boundary_nonconvex "
+                                           "(built: quadratic_boundary_grad_minimal, default, quadratic_boundary_grad)");
+  if (h->cfg.math_mode != CPMPPI_MATH_FAST) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": the adjoint is written for the FAST arithmetic");
+  if (h->cfg.N > (uint32_t)BLOCK)
+    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": one workgroup per env holds at most " + std::to_string(BLOCK) + " plans (N = " +
+                                           std::to_string(h->cfg.N) + ")");
+  const size_t lds = ((size_t)h->cfg.S * 6 + 2) * rpgd_block(h) * sizeof(float);
+  if (lds > 150 * 1024) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": S too large for the LDS sub-state buffer");
+  return CPMPPI_OK;
+}
+
+int cpmppi_rpgd_reserve(cpmppi_handle* h, uint32_t E) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (E == 0 || E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_reserve: bad argument (0 < E <= config.E)");
+  if (const int rc = rpgd_check_handle(h, "cpmppi_rpgd_reserve")) return rc;
+  CPMPPI_ON_DEVICE(h);
+  const size_t need = rpgd_floats(h, E);
+  if (h->rpgd_ws_floats >= need) return CPMPPI_OK;
+  if (h->rpgd_ws) (void)hipFree(h->rpgd_ws);
+  h->rpgd_ws = nullptr; h->rpgd_ws_floats = 0;
+  CPMPPI_HIP(h, hipMalloc(&h->rpgd_ws, need * sizeof(float)));
+  h->rpgd_ws_floats = need;
+  return CPMPPI_OK;
+}
+
+int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* a, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: null argument block");
+  if (a->E == 0 || a->E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: bad argument (0 < E <= config.E)");
+  if (!a->s0 || !a->target_position || !a->target_equilibrium || !a->Q || !a->m || !a->v || !a->Q_out)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: null pointer (s0, target_position, target_equilibrium, Q, m, v and Q_out are required)");
+  for (const void* ptr : {(const void*)a->s0, (const void*)a->target_position, (const void*)a->target_equilibrium, (const void*)a->L,
+                          (const void*)a->previous_input, (const void*)a->Q, (const void*)a->m, (const void*)a->v, (const void*)a->Q_out,
+                          (const void*)a->S_out, (const void*)a->plan_out, (const void*)a->order_out})
+    if (misaligned(ptr)) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: misaligned pointer");
+  if (reinterpret_cast<uintptr_t>(a->count_dev) & 7u) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: misaligned pointer (count_dev: 8 bytes)");
+  if (a->iterations == 0) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: iterations must be > 0");
+  if (a->keep_k == 0 || a->keep_k > h->cfg.N) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: bad argument (0 < keep_k <= N)");
+  if (a->shift > h->cfg.H) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: shift exceeds the horizon");
+  if (a->distribution > CPMPPI_RPGD_UNIFORM) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: unknown distribution");
+  if (const int rc = rpgd_check_handle(h, "cpmppi_rpgd_step")) return rc;
+  if (!pole_mass_rows_cover(h, a->E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_rpgd_step", h, a->E));
+  CPMPPI_ON_DEVICE(h);
+  hipStream_t s = (hipStream_t)stream;
+  if (h->rpgd_ws_floats < rpgd_floats(h, a->E)) {
+    // no allocation inside a capture: the workspace is reserved before (cpmppi_rpgd_reserve)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    (void)hipGetLastError();
+    if (capturing)
+      return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: the stream is being captured and the workspace is not reserved "
+                                         "(call cpmppi_rpgd_reserve before the capture)");
+    if (const int rc = cpmppi_rpgd_reserve(h, a->E)) return rc;
+  }
+  const uint32_t Nb = rpgd_block(h);
+  RpgdPtrs p{};
+  p.s0 = a->s0; p.x_t = a->target_position; p.te = a->target_equilibrium; p.L = a->L; p.prev_in = a->previous_input;
+  p.m_pole = h->m_pole_rows;
+  p.Q = a->Q; p.m = a->m; p.v = a->v;
+  p.ckpt = h->rpgd_ws; p.grad = h->rpgd_ws + (size_t)h->cfg.H * 6 * a->E * Nb;
+  p.count_dev = (const unsigned long long*)a->count_dev;
+  p.count = a->count; p.seed = a->seed; p.draw_offset = a->draw_offset;
+  p.iterations = a->iterations; p.adam_iteration = a->adam_iteration; p.keep_k = a->keep_k; p.resamp_per = a->resamp_per;
+  p.shift = a->shift; p.uniform = a->distribution == CPMPPI_RPGD_UNIFORM; p.env_offset = a->env_offset;
+  p.lr = a->learning_rate; p.beta1 = a->beta1; p.beta2 = a->beta2; p.eps = a->epsilon; p.gradmax_clip = a->gradmax_clip;
+  p.sample_mean = a->sample_mean; p.uniform_lo = a->uniform_lo; p.uniform_hi = a->uniform_hi;
+  p.Q_out = a->Q_out; p.S_out = a->S_out; p.plan_out = a->plan_out; p.order_out = a->order_out;
+  const size_t lds = ((size_t)h->cfg.S * 6 + 2) * Nb * sizeof(float);
+  const auto launch = h->cfg.ode_predictor == CPMPPI_ODE_CROMER ? launch_rpgd<PREDICTOR_ODE> : launch_rpgd<PREDICTOR_ODE_V0>;
+  launch(h->prm.cost_id, dim3(a->E), dim3(Nb), lds, s, h->prm, p);
+  CPMPPI_HIP(h, hipGetLastError());
+  if (a->count_dev) hipLaunchKernelGGL(rpgd_count_kernel, dim3(1), dim3(1), 0, s, (unsigned long long*)a->count_dev);
   return launched(h);
 }
 

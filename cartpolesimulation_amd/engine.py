@@ -602,6 +602,71 @@ class MPPIEngine:
         k = min(n.value, max_steps)
         return np.array(a[:k], dtype=np.float64), np.array(b[:k], dtype=np.float64)
 
+    # ------------------------------------------------------------------ the fused rpgd / gradient-tf control step
+    def rpgd_reserve(self, E=None):
+        """cpmppi_rpgd_reserve: the workspace of ``rpgd_step`` for up to E envs (default: all).  After it the step never
+        allocates - required before a step is captured into a graph."""
+        self._check(self.lib.cpmppi_rpgd_reserve(self._h, self.E if E is None else int(E)))
+
+    def rpgd_step(self, s0, Q, m, v, target_position, target_equilibrium, L=None, previous_input=None, *, iterations,
+                  learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, gradmax_clip=0.0, keep_k=None, resamp_per=0, shift=1,
+                  distribution="normal", sample_mean=0.0, uniform_lo=0.0, uniform_hi=0.0, seed=0, draw_offset=0, env_offset=0,
+                  count=0, adam_iteration=0, count_dev=None, Q_out=None, S_out=None, plan_out=None, order_out=None,
+                  _prepare=False):
+        """cpmppi_rpgd_step: one whole rpgd / gradient-tf control step on the plans ``Q`` and the Adam moments ``m``, ``v``
+        [E,N,H], all three updated IN PLACE (include/cpmppi.h states the step).  ``count_dev``: int64 device scalar, the control
+        steps taken so far - read by the kernel in place of ``count`` / ``adam_iteration`` / ``draw_offset`` and incremented
+        after the step (graph replay).  -> (Q_out[E], S_out, plan_out, order_out), the last three as given (or None)."""
+        E = device_tensor("Q", Q, tail=(self.N, self.H), note=_IN_PLACE).shape[0]
+        if E > self.E:
+            raise ValueError(f"Q must be [E<={self.E},{self.N},{self.H}], got {tuple(Q.shape)}")
+        for name, t in (("m", m), ("v", v)):
+            if device_tensor(name, t, tail=(self.N, self.H), note=_IN_PLACE).shape[0] != E:
+                raise ValueError(f"{name} must have Q's shape")
+        if distribution not in ("normal", "uniform"):
+            raise ValueError(f"distribution={distribution!r}; expected 'normal' or 'uniform'")
+        s0 = self.tensor(s0, (E, 6))
+        tp, te = self._per_env(target_position, E), self._per_env(target_equilibrium, E)
+        Lt = self._per_env(L, E) if L is not None else None
+        prev = self._per_env(previous_input, E) if previous_input is not None else None
+        if Q_out is None:
+            Q_out = self.empty(E)
+        for name, t, dtype, tail in (("Q_out", Q_out, torch.float32, ()), ("S_out", S_out, torch.float32, (self.N,)),
+                                     ("plan_out", plan_out, torch.float32, (self.H,)), ("order_out", order_out, torch.int32, (self.N,))):
+            if t is not None and device_tensor(name, t, dtype, tail).shape[0] != E:
+                raise ValueError(f"{name} must have {E} rows")
+        a = _L.cpmppi_rpgd_args()
+        a.E = E
+        a.s0, a.target_position, a.target_equilibrium = s0.data_ptr(), tp.data_ptr(), te.data_ptr()
+        a.L = Lt.data_ptr() if Lt is not None else None
+        a.previous_input = prev.data_ptr() if prev is not None else None
+        a.Q, a.m, a.v = Q.data_ptr(), m.data_ptr(), v.data_ptr()
+        a.iterations, a.adam_iteration = int(iterations), int(adam_iteration)
+        a.learning_rate, a.beta1, a.beta2 = float(learning_rate), float(beta1), float(beta2)
+        a.epsilon, a.gradmax_clip = float(epsilon), float(gradmax_clip)
+        a.keep_k, a.resamp_per, a.shift = int(self.N if keep_k is None else keep_k), int(resamp_per), int(shift)
+        a.distribution = _L.RPGD_UNIFORM if distribution == "uniform" else _L.RPGD_NORMAL
+        a.sample_mean, a.uniform_lo, a.uniform_hi = float(sample_mean), float(uniform_lo), float(uniform_hi)
+        a.seed, a.draw_offset, a.env_offset, a.count = int(seed), int(draw_offset), int(env_offset), int(count)
+        if count_dev is not None:
+            if device_tensor("count_dev", count_dev, torch.int64).numel() != 1:
+                raise ValueError("count_dev must have one element")
+            a.count_dev = count_dev.data_ptr()
+        a.Q_out = Q_out.data_ptr()
+        a.S_out = S_out.data_ptr() if S_out is not None else None
+        a.plan_out = plan_out.data_ptr() if plan_out is not None else None
+        a.order_out = order_out.data_ptr() if order_out is not None else None
+        out = (Q_out, S_out, plan_out, order_out)
+        if _prepare:
+            return PreparedRpgdStep(self, a, (s0, tp, te, Lt, prev, Q, m, v, count_dev) + out, out)
+        self._check(self.lib.cpmppi_rpgd_step(self._h, C.byref(a), self._stream()))
+        return out
+
+    def prepare_rpgd_step(self, *args, **kwargs):
+        """The argument block of ``rpgd_step(...)`` built and validated ONCE: ``.run(count=, adam_iteration=, draw_offset=,
+        iterations=)`` updates the host counters and enqueues the launch; with ``count_dev`` nothing changes between steps."""
+        return self.rpgd_step(*args, _prepare=True, **kwargs)
+
     # ------------------------------------------------------------------ the fused hot path
     def step(self, s0, u_nom, target_position, target_equilibrium, L=None, delta_u=None, knots=None, seed=None,
              offset=0, env_offset=0, u_prev=None, Q_out=None, S_out=None, predictor="ODE_v0", h0=None,
@@ -728,3 +793,24 @@ class PreparedStep:
         else:
             e._check(e.lib.cpmppi_step(e._h, C.byref(self.args), e._stream()))
         return self.Q_out, self.S_out
+
+
+class PreparedRpgdStep:
+    """A validated cpmppi_rpgd_step argument block plus the tensors it points into (MPPIEngine.prepare_rpgd_step)."""
+
+    def __init__(self, engine, args, keep, out):
+        self.engine, self.args, self._keep, self.out = engine, args, keep, out
+
+    def run(self, count=None, adam_iteration=None, draw_offset=None, iterations=None):
+        a = self.args
+        if count is not None:
+            a.count = int(count)
+        if adam_iteration is not None:
+            a.adam_iteration = int(adam_iteration)
+        if draw_offset is not None:
+            a.draw_offset = int(draw_offset)
+        if iterations is not None:
+            a.iterations = int(iterations)
+        e = self.engine
+        e._check(e.lib.cpmppi_rpgd_step(e._h, C.byref(a), e._stream()))
+        return self.out

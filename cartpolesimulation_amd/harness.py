@@ -105,11 +105,13 @@ class BatchedCartPoleExperiment:
         ``knots_fn(c)`` (tests): perturbation knots [E,N,P] for controller call c instead of the in-kernel Philox draw.
         ``optimizer``: any of the package's optimizers configured for the batch's E envs (`controller_mpc(..., num_envs=E)
         .configure(...).optimizer`: cem, rpgd, gradient, ...) computes the controls instead of the fused MPPI step - host-paced, one
-        `optimizer.step` per control period on device tensors, the plant / schedule / recording launch unchanged."""
+        `optimizer.step` per control period on device tensors, the plant / schedule / recording launch unchanged.  A FUSED rpgd /
+        gradient optimizer (`fused=True`: one cpmppi_rpgd_step per period, its step counter on the device) is not paced by the
+        host and may be captured (``graph=True``) like the MPPI step."""
         run = ScheduleRun(self.engine, batch, self.seed, env_offset=env_offset, knots_fn=knots_fn, u_nom0=u_nom0, optimizer=optimizer)
         if batch.dt_simulation != self.dt_simulation or batch.n_ctrl != self.n_sub:
             raise ValueError("the batch was drawn for other time scales than this experiment runner's")
-        if graph and optimizer is not None:
+        if graph and optimizer is not None and not run.fused:
             raise ValueError("an optimizer object is paced by the host: run this batch launched (graph=False)")
         if graph and knots_fn is None and run.T > 0:
             run.capture(steps_per_graph)
@@ -216,6 +218,7 @@ class ScheduleRun:
         """``bind_mass`` False: the caller binds `self.mass` to the engines that launch (pipeline.run_schedule_groups)."""
         self.eng, self.b, self.seed, self.env_offset, self.knots_fn = engine, batch, int(seed), int(env_offset), knots_fn
         self.optimizer = optimizer
+        self.fused = bool(getattr(optimizer, "fused", False))      # a fused rpgd / gradient optimizer: one library call per period
         if optimizer is not None:
             if getattr(optimizer, "num_envs", batch.E) != batch.E:
                 raise ValueError(f"the optimizer is configured for {optimizer.num_envs} envs, the batch has {batch.E}")
@@ -241,6 +244,10 @@ class ScheduleRun:
         self.cur_L = (Lc_tab if Lc_tab is not None else L_tab)[0].clone() if L_tab is not None else (eng.tensor(b.L) if b.L is not None else None)
         self.u_nom = eng.zeros(E, eng.H) if u_nom0 is None else eng.tensor(u_nom0, (E, eng.H)).clone()
         self.Q = eng.empty(E)
+        if self.fused:                                             # the fused step writes its controls where the plant reads them
+            if optimizer.engine is None:
+                optimizer.configure()
+            self.Q = optimizer.controls
         self.states, self.dd, self.Qs = eng.zeros(R, E, 6), eng.zeros(R, E, 2), eng.zeros(T + 1, E)
         self.states[0] = s
         self.tail = b.n_sim - T * b.n_ctrl                                        # simulation steps after the last controller call
@@ -287,6 +294,10 @@ class ScheduleRun:
         if bind_mass:                                              # (an optimizer object registers the row with its own engine)
             self.mass.bind([eng], register=optimizer is None)
         self.counter, self.graph, self.per = None, None, 0
+        if self.fused and not optimizer.warmup:
+            # the fused step counts its control steps on the device, launched or captured: the same arithmetic either way
+            # (warm-up iterations on the first step are told by the host: such an optimizer keeps its host counters)
+            self.counter = torch.zeros(1, dtype=torch.int64, device=self.s.device)
         self._prep = self._prep_plant = None                       # argument blocks built once (the launched Philox loop)
 
     @property
@@ -309,11 +320,18 @@ class ScheduleRun:
             vp.target_position, vp.target_equilibrium = self.cur_tp, self.cur_te
             if self.cur_L is not None:
                 vp.L = self.cur_L
-            if self.mass.kind != "none":
+            if self.mass.kind != "none" and c is not None:
                 vp.m_pole = self.mass.for_optimizer(c)
             if self.prev_Q is not None:
                 vp.Q_ccrc = self.prev_Q
                 setattr(vp, "Q_applied_-1", self.prev_Q)
+            if self.fused:
+                opt = self.optimizer
+                if c is not None:                                  # (captured: applied once before the capture)
+                    opt.engine.apply_pole_mass_of(vp, **opt._mass_rows)
+                # everything on the device; the control of the period before is the one this buffer still holds
+                opt.step_device(self.s_ctrl, self.cur_tp, self.cur_te, L=self.cur_L, previous_input=self.Q, count_dev=self.counter)
+                return
             t = float(self.b.times[min(c * self.b.n_ctrl, len(self.b.times) - 1)])
             q = self.optimizer.step(self.s_ctrl, t, as_tensor=True)
             self.Q.copy_(q.reshape(-1))
@@ -351,8 +369,10 @@ class ScheduleRun:
     def capture(self, steps_per_graph=10):
         """Capture `steps_per_graph` control periods as ONE HIP graph (device step counter: Philox offset = schedule row =
         recording row, no launch argument changes between periods); enqueue_next then replays it."""
-        if self.optimizer is not None:
+        if self.optimizer is not None and not self.fused:
             raise ValueError("an optimizer object is paced by the host: run this batch launched (graph=False)")
+        if self.fused and self.counter is None:
+            raise ValueError("warmup=True needs the host to tell the first step from the others: run this batch launched (graph=False)")
         if self.mass.varies:
             raise ValueError("a captured graph replays ONE pole mass for the controller: run this batch launched (graph=False)"
                              if self.mass.kind == "value" else
@@ -362,7 +382,14 @@ class ScheduleRun:
         # the graph replays the handle's controller mass as it is when CAPTURED: the run's (constant) one, which may differ from
         # the mass the handle was created with (an uninformed controller; advisor, round 5)
         self.mass.apply(0)
-        self.counter = torch.zeros(1, dtype=torch.int64, device=dev)              # controller calls made
+        if self.fused:                                             # ... and the optimizer's own handle: its mass, its workspace
+            vp = self.optimizer.variable_parameters
+            if self.mass.kind != "none":
+                vp.m_pole = self.mass.for_optimizer(0)
+            self.optimizer.engine.apply_pole_mass_of(vp, **self.optimizer._mass_rows)
+            self.optimizer.engine.rpgd_reserve()
+        if self.counter is None:
+            self.counter = torch.zeros(1, dtype=torch.int64, device=dev)          # controller calls made
         cap = torch.cuda.Stream(device=dev)
         launch = self.eng.launch_stream()
         cap.wait_stream(launch)

@@ -19,9 +19,15 @@ pinned by anything in-tree ([recalled] in SURVEY.md Appendix B terms):
 Everything that scales with rollouts x horizon runs in HIP kernels (sampling, forward + reverse sweep, Adam, top-k);
 torch is used for the per-plan bookkeeping (gather of survivors, shift).  ``num_envs`` problem instances advance in one
 launch.
+
+``fused=True`` (off by default) makes the whole control step ONE library call, cpmppi_rpgd_step: iterations, final cost,
+choice of the best plan, resampling and shift in one kernel, the plans and moments updated in place.  ``step`` then only
+uploads the state; ``step_device`` takes device tensors and, with a device step counter, touches the host not at all - the
+form a captured closed loop replays (harness.py).  The staged path above stays what it was.
 """
 import math
 
+import numpy as np
 import torch
 
 from ._optimizer_base import _OptimizerBase
@@ -33,7 +39,7 @@ class _GradientBase(_OptimizerBase):
 
     def __init__(self, cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, sample_stdev, period,
                  num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
-                 variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass):
+                 variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused=False):
         # the handle's sampler draws knots ~ N(0, SQRTRHOINV / sqrt(dt)): set it to the requested stdev
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
@@ -42,6 +48,7 @@ class _GradientBase(_OptimizerBase):
                          period_interpolation_inducing_points=int(period), per_env_pole_mass=bool(per_env_pole_mass))
         self.count = 0               # control steps taken
         self.draws = 0               # sampler launches (the Philox offset)
+        self.fused = bool(fused)     # one cpmppi_rpgd_step per control step instead of the staged launches
 
     def _set_timestep(self, dt):
         if dt != self.cfg.mpc_timestep:          # the sampling stdev stays what the constructor was asked for
@@ -65,6 +72,12 @@ class _GradientBase(_OptimizerBase):
         self.adam_it = 0
         self.count = 0
         self._first = True
+        if self.fused:
+            eng, E = self.engine, self.num_envs
+            # what the fused step writes per control step: the controls, the final costs, the best plan (persistent buffers)
+            self._u, self._S, self._plan = eng.zeros(E), eng.empty(E, self.num_rollouts), eng.empty(E, self.mpc_horizon)
+            self._draw0 = self.draws                     # the first redraw's Philox offset (device mode counts on from it)
+            self._prepared = self._prepared_key = self._attr_host = self._attr_dev = None
 
     # -- one control step ----------------------------------------------------------------------------------------
     def _descend(self, s_t, tp, te, L, iterations):
@@ -99,6 +112,82 @@ class _GradientBase(_OptimizerBase):
         self.count += 1
         return self._result(u, single, as_tensor)
 
+    # -- the fused control step (cpmppi_rpgd_step) ----------------------------------------------------------------------
+    def _fused_plan(self):
+        """What the fused step does besides Adam: iterations, keep_k, resamp_per, shift and the redraw's distribution."""
+        raise NotImplementedError
+
+    def _fused_call(self, s, tp, te, L, previous_input, count_dev):
+        """One cpmppi_rpgd_step on device tensors.  The argument block is built once per set of buffers; with ``count_dev`` the
+        call changes nothing on the host, without it the host counters advance as the staged step's do."""
+        E = self.num_envs
+        for name, t, shape in (("s", s, (E, 6)), ("target_position", tp, (E,)), ("target_equilibrium", te, (E,)), ("L", L, (E,)),
+                               ("previous_input", previous_input, (E,))):
+            if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous()
+                                      and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on the engine's device")
+        key = tuple(0 if t is None else t.data_ptr() for t in (s, tp, te, L, previous_input, count_dev))
+        if key != self._prepared_key:
+            self._prepared = self.engine.prepare_rpgd_step(
+                s, self.Q, self.m, self.v, tp, te, L, previous_input, learning_rate=self.learning_rate,
+                beta1=self.adam_beta_1, beta2=self.adam_beta_2, epsilon=self.adam_epsilon, gradmax_clip=self.gradmax_clip,
+                seed=self.seed, draw_offset=self._draw0, count_dev=count_dev, Q_out=self._u, S_out=self._S,
+                plan_out=self._plan, **self._fused_plan())
+            self._prepared_key = key
+        if count_dev is not None:
+            self._prepared.run()
+            return self._u
+        plan = self._fused_plan()
+        iters = self.warmup_iterations if (self.warmup and self._first) else plan["iterations"]
+        self._first = False
+        self._prepared.run(count=self.count, adam_iteration=self.adam_it, draw_offset=self.draws, iterations=iters)
+        self.adam_it += iters
+        self.count += 1
+        if plan["resamp_per"] > 0 and plan["keep_k"] < self.num_rollouts and self.count % plan["resamp_per"] == 0:
+            self.draws += 1
+        return self._u
+
+    @property
+    def controls(self):
+        """The fused step's output [E]: the persistent device tensor every step writes (a closed loop's plant reads it in place)."""
+        return self._u
+
+    def step_device(self, s, target_position, target_equilibrium, L=None, previous_input=None, count_dev=None):
+        """The fused control step on DEVICE tensors: s [E,6], the per-env vectors [E] (L, previous_input: or None), and
+        optionally ``count_dev``, an int64 device scalar holding the control steps taken so far (incremented by the step).
+        Nothing is read back and nothing is uploaded, so the call can be captured into a graph (reserve the workspace with
+        ``engine.rpgd_reserve()`` and apply the pole mass before).  -> the controls [E]: a persistent device tensor that the
+        next step overwrites."""
+        if not self.fused:
+            raise ValueError(f"{type(self).__name__}.step_device needs fused=True")
+        if count_dev is not None and self.warmup:
+            raise ValueError("warmup=True runs warmup_iterations on the first step, which a device step counter cannot tell "
+                             "from the others: use the host counters (count_dev=None) or warmup=False")
+        if self.engine is None:
+            self.configure()
+        return self._fused_call(s, target_position, target_equilibrium, L, previous_input, count_dev)
+
+    def _step_fused(self, s, as_tensor):
+        if self.engine is None:
+            self.configure()
+        eng = self.engine
+        eng.apply_pole_mass_of(self.variable_parameters, **self._mass_rows)
+        s_t = eng.tensor(s)
+        single = s_t.dim() == 1
+        s_t = s_t.reshape(-1, 6)
+        E = s_t.shape[0]
+        if E != self.num_envs:
+            raise ValueError(f"optimizer configured for {self.num_envs} envs, got {E} states")
+        host = self._attributes(E)                       # uploaded only when a value has changed
+        if self._attr_host is None or not all(np.array_equal(a, b) for a, b in zip(host, self._attr_host)):
+            self._attr_host, self._attr_dev = host, tuple(eng.tensor(x) for x in host)
+        u = self._fused_call(s_t, *self._attr_dev, self._previous_input, None)
+        self._previous_input = u                         # (the step reads its env's entry before it writes it)
+        if self.optimizer_logging:
+            self.logging_values = {"Q_logged": u.cpu().numpy(), "J_logged": self._S.cpu().numpy(),
+                                   "u_logged": self._plan.cpu().numpy()}
+        return self._result(u.clone() if as_tensor else u, single, as_tensor)
+
 
 class optimizer_gradient(_GradientBase):
     """config_optimizers.yml:49-62 (gradient-tf)."""
@@ -110,14 +199,17 @@ class optimizer_gradient(_GradientBase):
                  gradmax_clip=5, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
                  intermediate_steps=10, horizon_reduce="sum", phys=None, device=0, variable_parameters=None,
-                 per_env_pole_mass=False, **kwargs):
+                 per_env_pole_mass=False, fused=False, **kwargs):
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
         self.adam_epsilon, self.gradmax_clip, self.rtol = float(adam_epsilon), float(gradmax_clip), float(rtol)
         self.gradient_steps, self.warmup, self.warmup_iterations = int(gradient_steps), bool(warmup), int(warmup_iterations)
         self.initial_action_stdev = float(initial_action_stdev)
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, initial_action_stdev,
                          10, num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
-                         variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass)
+                         variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused)
+
+    def _fused_plan(self):
+        return {"iterations": self.gradient_steps, "keep_k": self.num_rollouts, "resamp_per": 0, "shift": 1}
 
     def _draw(self):
         """Independent N(0, initial_action_stdev) per time-step, clipped (cpmppi_cem_sample)."""
@@ -129,6 +221,8 @@ class optimizer_gradient(_GradientBase):
         return Q
 
     def step(self, s, time=None, as_tensor=False):
+        if self.fused:
+            return self._step_fused(s, as_tensor)
         s_t, single, E, tp, te, L = self._begin_step(s)
         iters = self.warmup_iterations if (self.warmup and self._first) else self.gradient_steps
         self._first = False
@@ -149,7 +243,8 @@ class optimizer_rpgd(_GradientBase):
                  sample_whole_control_space=False, uniform_dist_max=0.8, uniform_dist_min=-0.8, shift_previous=1,
                  warmup=False, warmup_iterations=250, optimizer_logging=False, calculate_optimal_trajectory=False,
                  num_envs=1, cost_function_specification=None, cost_weights=None, intermediate_steps=10,
-                 horizon_reduce="sum", phys=None, device=0, variable_parameters=None, per_env_pole_mass=False, **kwargs):
+                 horizon_reduce="sum", phys=None, device=0, variable_parameters=None, per_env_pole_mass=False, fused=False,
+                 **kwargs):
         if SAMPLING_DISTRIBUTION not in ("normal", "uniform"):
             raise ValueError(f"SAMPLING_DISTRIBUTION={SAMPLING_DISTRIBUTION!r}; expected 'normal' or 'uniform'")
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
@@ -164,16 +259,27 @@ class optimizer_rpgd(_GradientBase):
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, stdev,
                          period_interpolation_inducing_points, num_envs, cost_function_specification, cost_weights,
                          intermediate_steps, phys, device, variable_parameters, optimizer_logging, horizon_reduce,
-                         per_env_pole_mass)
+                         per_env_pole_mass, fused)
+
+    def _uniform_range(self):
+        return (self.action_low, self.action_high) if self.sample_whole_control_space else \
+            (self.uniform_dist_min, self.uniform_dist_max)
+
+    def _fused_plan(self):
+        lo, hi = self._uniform_range()
+        return {"iterations": self.outer_its, "keep_k": self.opt_keep_k, "resamp_per": self.resamp_per,
+                "shift": self.shift_previous, "distribution": self.distribution, "sample_mean": self.sample_mean,
+                "uniform_lo": lo, "uniform_hi": hi}
 
     def _shape_samples(self, z):
         if self.distribution == "normal":
             return z + self.sample_mean if self.sample_mean != 0.0 else z
-        lo, hi = (self.action_low, self.action_high) if self.sample_whole_control_space else \
-            (self.uniform_dist_min, self.uniform_dist_max)
+        lo, hi = self._uniform_range()
         return lo + (hi - lo) * 0.5 * (1.0 + torch.erf(z * (1.0 / math.sqrt(2.0))))     # N(0,1) -> U(lo, hi)
 
     def step(self, s, time=None, as_tensor=False):
+        if self.fused:
+            return self._step_fused(s, as_tensor)
         s_t, single, E, tp, te, L = self._begin_step(s)
         iters = self.warmup_iterations if (self.warmup and self._first) else self.outer_its
         self._first = False

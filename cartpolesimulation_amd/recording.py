@@ -257,7 +257,9 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
     (noise_mode + the four sigmas), `vertical_angle_offset` (schedule.apply_parameter_schedule).
     ``optimizer``: one of the package's optimizer objects configured for the run's experiments (`controller_mpc(config_root=...,
     num_envs=n).configure().optimizer` - the shipped config_controllers.yml names rpgd) controls the plants instead of the fused MPPI
-    step; `engine` may then be None (the optimizer's own engine runs the plant)."""
+    step; `engine` may then be None (the optimizer's own engine runs the plant).  A staged optimizer is paced by the host
+    (graph=False); a fused rpgd / gradient optimizer (`fused=True`) may run captured (graph=True).  Env groups and the multi-GPU
+    gather stay with the MPPI step."""
     import time
     from .harness import BatchedCartPoleExperiment
     from .schedule import RandomExperimentSetter, merged_config
@@ -269,8 +271,11 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
         raise ValueError("config['seed'] is empty: the reference then seeds from the clock; give a seed for a reproducible batch")
     cseed = cartpole_seed if cartpole_seed is not None else cfg["seed"] + 1
     if optimizer is not None:
-        if int(groups) > 1 or graph:
-            raise ValueError("an optimizer object is paced by the host: groups=1, graph=False")
+        if int(groups) > 1:
+            raise ValueError("env groups run the fused MPPI step only: an optimizer object needs groups=1")
+        if graph and not getattr(optimizer, "fused", False):
+            raise ValueError("an optimizer object is paced by the host: groups=1, graph=False (a fused rpgd / gradient optimizer "
+                             "- fused=True - may be captured)")
         if getattr(optimizer, "engine", None) is None:
             from .shard import env_shard
             optimizer.configure(num_envs=env_shard(n_total, int(world), int(rank))[1])
@@ -349,6 +354,9 @@ def main(argv=None):
                     help="mppi (the fused hot path; default without --config-root) or any other optimizer of the package - cem, cem-gmm, "
                          "rpgd, gradient, ... - paced by the host; with --config-root the default is the checkout's own "
                          "config_controllers.yml `mpc: optimizer` (shipped: rpgd)")
+    ap.add_argument("--fused", action="store_true",
+                    help="rpgd / gradient: the whole control step as one library call (cpmppi_rpgd_step) and the closed loop "
+                         "captured as a graph, the step counter on the device")
     ap.add_argument("--cost", default=None,
                     choices=["legacy_mppi_cartpole", "default", "quadratic_boundary_grad_minimal", "quadratic_boundary_grad"])
     args = ap.parse_args(argv)
@@ -403,12 +411,22 @@ def main(argv=None):
             over["cost_function_specification"] = args.cost
         if args.config_root and cfg.per_env_pole_mass:
             over["per_env_pole_mass"] = True
+        if args.fused:
+            if opt_name not in ("rpgd", "rpgd-tf", "gradient", "gradient-tf"):
+                raise SystemExit(f"--fused: the fused control step is built for rpgd and gradient, not {opt_name!r}")
+            if args.groups > 1:
+                raise SystemExit("--fused: env groups run the MPPI step only (--groups 1)")
+            over["fused"] = True
         ctrl = controller_mpc("CartPole", {}, control_limits=([-1.0], [1.0]), config=over, phys=phys, device=device, num_envs=n_local,
                               config_root=args.config_root)
         ctrl.configure(opt_name)
         optimizer = ctrl.optimizer
+    if args.fused and optimizer is None:
+        raise SystemExit("--fused: the fused control step is built for rpgd and gradient, not 'mppi'")
+    # a fused optimizer runs captured unless the run cannot be (a controller pole mass that changes between calls, warm-up)
+    graph = bool(args.fused) and not optimizer.warmup
     paths = generate_dataset(eng, n_exp, out, seed=seed, rank=rank, world=world, config=dg, groups=args.groups, parameters=parameters,
-                             optimizer=optimizer,
+                             optimizer=optimizer, graph=graph,
                              secondary_experiment_index=None if args.secondary_experiment_index < 0 else args.secondary_experiment_index)
     print(f"wrote {len(paths)} recordings under {os.path.dirname(paths[0])}")
 

@@ -18,6 +18,8 @@
  *                    trajectory_rollouts :164-224, q :227-275, phi :278-303, reward_weighted_average :306-321,
  *                    initialize_perturbations :392-452)
  *                    -> cpmppi_sample() + cpmppi_step()
+ *                    optimizer_rpgd.step / optimizer_gradient.step (config_optimizers.yml:49-86), the whole control step
+ *                    -> cpmppi_rpgd_step()
  *
  * Conventions
  *   - every array argument is a caller-owned DEVICE pointer to contiguous float32 (e.g. torch.Tensor.data_ptr() of a
@@ -48,7 +50,8 @@ extern "C" {
                                       cpmppi_comm_info, cpmppi_groups_*.  cpmppi_abi_version() reports what a loaded library was built as;
                                    5: cpmppi_comm_set_stamped (+ cpmppi_comm_info.stamped), cpmppi_groups_comm_init / cpmppi_groups_run_gather;
                                       a caller-given rccl_path now wins over an RCCL the process has already loaded;
-                                      cpmppi_set_pole_mass_rows (a new entry point: no layout and no existing semantics change). */
+                                      cpmppi_set_pole_mass_rows (a new entry point: no layout and no existing semantics change);
+                                      cpmppi_rpgd_step / cpmppi_rpgd_reserve / cpmppi_rpgd_args (new entry points, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -325,6 +328,67 @@ int cpmppi_rollout_cost_grad(cpmppi_handle* h, uint32_t E, const float* s0, cons
  * clip to [action_low, action_high] (config_optimizers.yml:52-58,69-73). */
 int cpmppi_adam_step(cpmppi_handle* h, uint32_t E, float* Q, const float* grad, float* m, float* v, uint32_t iteration,
                      float learning_rate, float beta1, float beta2, float epsilon, float gradmax_clip, void* stream);
+
+/* The whole rpgd / gradient-tf control step of E envs in ONE call: no host synchronisation, no allocation, and - with
+ * count_dev - no launch argument that changes between control steps, so a captured graph of (step, plant) replays.
+ * It is cpmppi_rollout_cost_grad + cpmppi_adam_step `iterations` times, the final cost, the choice of the best plan, the
+ * resampling of rpgd and the shift, written out below.  `c` = control steps taken before this call: *count_dev if given,
+ * else count.
+ *   1. for i = 1..iterations: cost and gradient of every plan (cpmppi_rollout_cost_grad's arithmetic, previous_input and
+ *      per-env pole masses included), then cpmppi_adam_step's update with t = a + i, a = adam_iteration (host mode) or
+ *      c * iterations (device mode); lr_t = lr sqrt(1 - beta2^t) / (1 - beta1^t) is formed in double IN THE KERNEL in both modes.
+ *   2. final cost S of every plan: the adjoint kernel's forward sweep (sin / cos evaluated on every substep).
+ *   3. best = first plan in the stable order by (cost, index) of cpmppi_cem_update: torch.argmin's choice for finite costs;
+ *      where a cost is NaN it is ranked LAST, so a finite plan is chosen (torch.argmin would pick the NaN).
+ *      Q_out[env] = Q[env, best, 0]; plan_out, S_out and order_out are filled as found BEFORE steps 4 and 5.
+ *   4. if resamp_per > 0, keep_k < N and (c + 1) % resamp_per == 0: rows 0..keep_k-1 become the keep_k best plans in rank
+ *      order with their moments; rows keep_k..N-1 are redrawn with zero moments - row n gets what cpmppi_sample(seed, o,
+ *      env_offset) interpolates for rollout n (the handle's sigma and period), + sample_mean (CPMPPI_RPGD_NORMAL) or mapped
+ *      through the normal CDF to U(uniform_lo, uniform_hi) (CPMPPI_RPGD_UNIFORM), clipped to the action limits;
+ *      o = draw_offset (host mode) or draw_offset + c / resamp_per (device mode).
+ *   5. Q, m, v are shifted left by `shift`; Q repeats its last element, m and v are filled with 0.
+ *   6. with count_dev: *count_dev += 1 after the step, stream-ordered (as cpmppi_step treats offset_dev).
+ * Refused with CPMPPI_ERR_BAD_ARG: everything cpmppi_rollout_cost_grad refuses, N > 256 (one workgroup per env, one lane per
+ * plan), keep_k == 0 or > N, iterations == 0, shift > H, a NULL or misaligned required pointer, and a stream under capture
+ * while the workspace of cpmppi_rpgd_reserve is missing or too small (outside a capture the step allocates it itself).
+ * cpmppi_rpgd_reserve(h, E): allocates the workspace for steps of up to E envs (H * 7 * E * ceil64(N) floats). */
+typedef enum { CPMPPI_RPGD_NORMAL = 0, CPMPPI_RPGD_UNIFORM = 1 } cpmppi_rpgd_distribution;
+typedef struct {
+  uint32_t E;                       /* active envs in this call */
+  const float* s0;                  /* [E,6] */
+  const float* target_position;     /* [E] */
+  const float* target_equilibrium;  /* [E] */
+  const float* L;                   /* [E] pole length per env, or NULL = config.L_default */
+  const float* previous_input;      /* [E] control applied before this step, or NULL = 0 */
+  float* Q;                         /* [E,N,H] the plans, updated in place */
+  float* m;                         /* [E,N,H] Adam first moments, updated in place */
+  float* v;                         /* [E,N,H] Adam second moments, updated in place */
+  uint32_t iterations;              /* Adam iterations in this step */
+  uint32_t adam_iteration;          /* Adam iterations taken before this call (host mode) */
+  float learning_rate;
+  float beta1;
+  float beta2;
+  float epsilon;
+  float gradmax_clip;               /* <= 0: off */
+  uint32_t keep_k;                  /* keep_k == N or resamp_per == 0: never resample */
+  uint32_t resamp_per;
+  uint32_t shift;                   /* 0 .. H */
+  uint32_t distribution;            /* cpmppi_rpgd_distribution */
+  float sample_mean;
+  float uniform_lo;
+  float uniform_hi;
+  uint64_t seed;                    /* Philox key of the redraw */
+  uint64_t draw_offset;             /* Philox offset of the redraw (host mode), or of the first redraw (device mode) */
+  uint32_t env_offset;              /* global index of env 0 */
+  uint64_t count;                   /* control steps taken before this call (host mode) */
+  uint64_t* count_dev;              /* the same counter in DEVICE memory (8-byte aligned), or NULL = host mode */
+  float* Q_out;                     /* [E]   the chosen control */
+  float* S_out;                     /* [E,N] final costs, indexed by the plan rows as they are BEFORE step 4, or NULL */
+  float* plan_out;                  /* [E,H] the best plan before the shift, or NULL */
+  uint32_t* order_out;              /* [E,N] the ranking (plan rows, cheapest first), or NULL */
+} cpmppi_rpgd_args;
+int cpmppi_rpgd_reserve(cpmppi_handle* h, uint32_t E);
+int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* args, void* stream);
 
 /* Plain gradient step Q <- clip(Q - learning_rate * clip_by_norm(grad, gradmax_clip)) on Q[E,N,H] in place
  * (cem-naive-grad-tf, config_optimizers.yml:21-31). */

@@ -5,6 +5,12 @@ the controller seam (controller_mpc.configure(name) / .step), for E problem inst
   python tools/optim_bench.py [--envs 64] [--steps 30] [--predictor-specification ODE]
 (ODE = the shipped config_controllers.yml's predictor: Euler-Cromer, no edge bounce; default ODE_v0)
 Prints one JSON object per optimizer: ms per controller step (all envs), candidate plans evaluated per second.
+
+  python tools/optim_bench.py --fused [--envs 64] [--predictor-specification ODE] [--datagen 256,10]
+rpgd and gradient-tf only, staged and fused (cpmppi_rpgd_step) in the SAME process: one record each through the controller
+seam ("staged", "fused": controller.step, the control read back every step) and one for the fused step on device tensors with the
+step counter on the device ("fused_device": optimizer.step_device, no read-back).  ``--datagen E,seconds``: E experiments of that
+length through the closed loop (harness.run_schedule), launched + staged against captured + fused (rpgd, shipped sizes).
 """
 import argparse
 import json
@@ -24,11 +30,74 @@ ap = argparse.ArgumentParser()
 ap.add_argument("--envs", type=int, default=64)
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--predictor-specification", default="ODE_v0")
+ap.add_argument("--fused", action="store_true", help="rpgd and gradient-tf, staged against fused, in this one process")
+ap.add_argument("--datagen", default=None, help="with --fused: E,seconds of the closed-loop data generator, e.g. 256,10")
 args = ap.parse_args()
 E = args.envs
 rng = np.random.Generator(np.random.SFC64(3))
 s_host = np.stack([O.create_cartpole_state(rng.uniform(-0.3, 0.3), rng.uniform(-0.5, 0.5), rng.uniform(-0.05, 0.05), 0.0)
                    for _ in range(E)])
+
+
+def timed(fn, steps):
+    for _ in range(3):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps
+
+
+def fused_bench():
+    spec = args.predictor_specification
+    for name in ("gradient-tf", "rpgd"):
+        for mode in ("staged", "fused", "fused_device"):
+            ctrl = controller_mpc("CartPole", {"target_position": 0.0, "target_equilibrium": 1.0, "L": 0.395},
+                                  control_limits=([-1.0], [1.0]), num_envs=E, config=dict(seed=1, fused=mode != "staged"))
+            ctrl.configure(name, predictor_specification=spec)
+            opt = ctrl.optimizer
+            eng = opt.engine
+            s = eng.tensor(s_host)
+            if mode == "fused_device":
+                tp, te, L = eng.zeros(E), eng.zeros(E) + 1.0, eng.zeros(E) + 0.395
+                counter = torch.zeros(1, dtype=torch.int64, device=s.device)
+                dt = timed(lambda: opt.step_device(s, tp, te, L=L, previous_input=opt.controls, count_dev=counter), args.steps)
+            else:
+                dt = timed(lambda: ctrl.step(s, 0.0, {}), args.steps)
+            print(json.dumps({"bench": "controller_step", "optimizer": name, "mode": mode, "predictor": opt.cfg.predictor_type, "envs": E,
+                              "num_rollouts": opt.num_rollouts, "mpc_horizon": opt.mpc_horizon,
+                              "iterations": getattr(opt, "outer_its", getattr(opt, "gradient_steps", None)),
+                              "ms_per_controller_step": round(dt * 1e3, 4)}), flush=True)
+            eng.close()
+    if args.datagen:
+        from cartpolesimulation_amd import schedule as SC
+        from cartpolesimulation_amd.harness import BatchedCartPoleExperiment
+        n, seconds = int(args.datagen.split(",")[0]), float(args.datagen.split(",")[1])
+        cfg = dict(seed=5, length_of_experiment=seconds)
+        for mode, graph in (("launched_staged", False), ("launched_fused", False), ("captured_fused", True)):
+            ctrl = controller_mpc("CartPole", {}, control_limits=([-1.0], [1.0]), num_envs=n, config=dict(seed=1, fused=mode != "launched_staged"))
+            ctrl.configure("rpgd", predictor_specification=spec)
+            opt = ctrl.optimizer
+            best = None
+            for _ in range(2):                                  # (the first run pays the one-time costs)
+                opt.optimizer_reset()
+                b = SC.RandomExperimentSetter(cfg).draw(n, 6)
+                torch.cuda.synchronize()
+                t0 = time.perf_counter()
+                BatchedCartPoleExperiment(opt.engine, b.dt_simulation, b.dt_control, seed=0).run_schedule(b, graph=graph, optimizer=opt)
+                torch.cuda.synchronize()
+                best = time.perf_counter() - t0
+            print(json.dumps({"bench": "data_generator", "optimizer": "rpgd", "mode": mode, "predictor": opt.cfg.predictor_type,
+                              "experiments": n, "length_s": seconds, "control_periods": int(b.n_periods), "seconds": round(best, 4),
+                              "ms_per_control_period": round(best / (b.n_periods + 1) * 1e3, 4)}), flush=True)
+            opt.engine.close()
+
+
+if args.fused:
+    fused_bench()
+    sys.exit(0)
 for name in ("mppi", "cem-tf", "cem-gmm-tf", "cem-naive-grad-tf", "cem-grad-bharadhwaj-tf", "gradient-tf", "rpgd", "random-action-tf"):
     ctrl = controller_mpc("CartPole", {"target_position": 0.0, "target_equilibrium": 1.0, "L": 0.395},
                           control_limits=([-1.0], [1.0]), num_envs=E, config=dict(seed=1))
