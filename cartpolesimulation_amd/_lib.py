@@ -15,6 +15,7 @@ MATH_PRECISE, MATH_FAST = 0, 1
 ODE_V0, ODE_CROMER = 0, 1
 NOISE_DELTA_U, NOISE_KNOTS, NOISE_PHILOX, NOISE_DELTA_U_TILED = 0, 1, 2, 3
 RPGD_NORMAL, RPGD_UNIFORM = 0, 1
+CEM_REFINE_NONE, CEM_REFINE_SGD, CEM_REFINE_ADAM = 0, 1, 2
 
 EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_config", "cpmppi_set_cost_weights", "cpmppi_set_pole_mass",
            "cpmppi_sample", "cpmppi_interpolate", "cpmppi_predict", "cpmppi_trajectory_cost", "cpmppi_step",
@@ -28,7 +29,7 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_groups_create", "cpmppi_groups_destroy", "cpmppi_groups_count", "cpmppi_groups_slice", "cpmppi_groups_handle",
            "cpmppi_groups_stream", "cpmppi_groups_fork", "cpmppi_groups_join", "cpmppi_groups_run", "cpmppi_groups_last_error",
            "cpmppi_comm_set_stamped", "cpmppi_groups_comm_init", "cpmppi_groups_run_gather", "cpmppi_set_pole_mass_rows",
-           "cpmppi_rpgd_reserve", "cpmppi_rpgd_step")
+           "cpmppi_rpgd_reserve", "cpmppi_rpgd_step", "cpmppi_cem_reserve", "cpmppi_cem_step")
 COMM_ID_BYTES, COMM_SLOTS, GATHER_STAMP_FLOATS = 128, 4, 4
 
 
@@ -66,6 +67,17 @@ class cpmppi_rpgd_args(C.Structure):
                 ("seed", C.c_uint64), ("draw_offset", C.c_uint64), ("env_offset", C.c_uint32),
                 ("count", C.c_uint64), ("count_dev", C.c_void_p),
                 ("Q_out", C.c_void_p), ("S_out", C.c_void_p), ("plan_out", C.c_void_p), ("order_out", C.c_void_p)]
+
+
+class cpmppi_cem_args(C.Structure):
+    _fields_ = [("E", C.c_uint32), ("s0", C.c_void_p), ("target_position", C.c_void_p), ("target_equilibrium", C.c_void_p),
+                ("L", C.c_void_p), ("previous_input", C.c_void_p), ("mean", C.c_void_p), ("stdev", C.c_void_p),
+                ("iterations", C.c_uint32), ("best_k", C.c_uint32), ("stdev_min", C.c_float), ("refine", C.c_uint32),
+                ("learning_rate", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("epsilon", C.c_float),
+                ("gradmax_clip", C.c_float), ("shift", C.c_uint32), ("mean_fill", C.c_float), ("stdev_fill", C.c_float),
+                ("seed", C.c_uint64), ("offset", C.c_uint64), ("env_offset", C.c_uint32), ("count_dev", C.c_void_p),
+                ("Q_out", C.c_void_p), ("S_out", C.c_void_p), ("plan_out", C.c_void_p), ("samples_out", C.c_void_p),
+                ("order_out", C.c_void_p)]
 
 
 class cpmppi_gru_model(C.Structure):
@@ -165,6 +177,10 @@ def load():
     lib.cpmppi_sgd_step.argtypes = [vp, u32, vp, vp, f, f, vp]
     lib.cpmppi_rpgd_reserve.argtypes = [vp, u32]
     lib.cpmppi_rpgd_step.argtypes = [vp, C.POINTER(cpmppi_rpgd_args), vp]
+    lib.cpmppi_cem_reserve.argtypes = [vp, u32, u32]
+    lib.cpmppi_cem_reserve.restype = C.c_int
+    lib.cpmppi_cem_step.argtypes = [vp, C.POINTER(cpmppi_cem_args), vp]
+    lib.cpmppi_cem_step.restype = C.c_int
     lib.cpmppi_cem_sample.argtypes = [vp, u32, vp, vp, u64, u64, u32, vp, vp]
     lib.cpmppi_cem_update.argtypes = [vp, u32, vp, vp, u32, f, vp, vp, vp, vp]
     lib.cpmppi_tiled_floats.argtypes = [vp, u32]

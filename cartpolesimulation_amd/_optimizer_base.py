@@ -100,6 +100,70 @@ class _OptimizerBase:
         tp, te, L = (eng.tensor(x) for x in self._attributes(E))
         return s_t, single, E, tp, te, L
 
+    # -- the fused control step: one library call (the optimizers that build one set `fused` and give `_fused_call`) -------
+    _previous_input = None
+
+    def _fused_call(self, s, tp, te, L, previous_input, count_dev):
+        """One fused step on device tensors -> the controls buffer; with ``count_dev`` the host counts nothing."""
+        raise NotImplementedError
+
+    def _fused_key(self, s, tp, te, L, previous_input, count_dev):
+        """The device tensors of a fused step, checked -> what tells one set of buffers from another (an argument block is built
+        once per set)."""
+        import torch
+        E = self.num_envs
+        for name, t, shape in (("s", s, (E, 6)), ("target_position", tp, (E,)), ("target_equilibrium", te, (E,)), ("L", L, (E,)),
+                               ("previous_input", previous_input, (E,))):
+            if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous()
+                                      and tuple(t.shape) == shape):
+                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on the engine's device")
+        return tuple(0 if t is None else t.data_ptr() for t in (s, tp, te, L, previous_input, count_dev))
+
+    def reserve_fused(self):
+        """The fused step's workspace: after it a step never allocates - required before a step is captured into a graph."""
+        raise NotImplementedError
+
+    @property
+    def controls(self):
+        """The fused step's output [E]: the persistent device tensor every step writes (a closed loop's plant reads it in place)."""
+        return self._u
+
+    def step_device(self, s, target_position, target_equilibrium, L=None, previous_input=None, count_dev=None):
+        """The fused control step on DEVICE tensors: s [E,6], the per-env vectors [E] (L, previous_input: or None), and
+        optionally ``count_dev``, an int64 device scalar holding the control steps taken so far (incremented by the step).
+        Nothing is read back and nothing is uploaded, so the call can be captured into a graph (reserve the workspace with
+        ``reserve_fused()`` and apply the pole mass before).  -> the controls [E]: a persistent device tensor that the
+        next step overwrites."""
+        if not self.fused:
+            raise ValueError(f"{type(self).__name__}.step_device needs fused=True")
+        if count_dev is not None and self.warmup:
+            raise ValueError("warmup=True runs warmup_iterations on the first step, which a device step counter cannot tell "
+                             "from the others: use the host counters (count_dev=None) or warmup=False")
+        if self.engine is None:
+            self.configure()
+        return self._fused_call(s, target_position, target_equilibrium, L, previous_input, count_dev)
+
+    def _step_fused(self, s, as_tensor):
+        if self.engine is None:
+            self.configure()
+        eng = self.engine
+        eng.apply_pole_mass_of(self.variable_parameters, **self._mass_rows)
+        s_t = eng.tensor(s)
+        single = s_t.dim() == 1
+        s_t = s_t.reshape(-1, 6)
+        E = s_t.shape[0]
+        if E != self.num_envs:
+            raise ValueError(f"optimizer configured for {self.num_envs} envs, got {E} states")
+        host = self._attributes(E)                       # uploaded only when a value has changed
+        if self._attr_host is None or not all(np.array_equal(a, b) for a, b in zip(host, self._attr_host)):
+            self._attr_host, self._attr_dev = host, tuple(eng.tensor(x) for x in host)
+        u = self._fused_call(s_t, *self._attr_dev, self._previous_input, None)
+        self._previous_input = u                         # (the step reads its env's entry before it writes it)
+        if self.optimizer_logging:
+            self.logging_values = {"Q_logged": u.cpu().numpy(), "J_logged": self._S.cpu().numpy(),
+                                   "u_logged": self._plan.cpu().numpy()}
+        return self._result(u.clone() if as_tensor else u, single, as_tensor)
+
     def _result(self, u, single, as_tensor):
         """The controls u[E] (device tensor, or already on the host) as the caller wants them: the tensor itself, or a host
         array of its own, [1] for a [6] state and [E,1] for [E,6]."""

@@ -406,6 +406,7 @@ void cpmppi_destroy(cpmppi_handle* h) {
   if (h->gru16_image) (void)hipFree(h->gru16_image);
   if (h->grad_ckpt) (void)hipFree(h->grad_ckpt);
   if (h->rpgd_ws) (void)hipFree(h->rpgd_ws);
+  if (h->cem_ws) (void)hipFree(h->cem_ws);
   if (h->counters) (void)hipFree(h->counters);
   if (h->env_fold) (void)hipFree(h->env_fold);
   if (h->zeros_H) (void)hipFree(h->zeros_H);

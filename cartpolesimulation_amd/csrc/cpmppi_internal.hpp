@@ -63,6 +63,8 @@ struct cpmppi_handle {
   size_t grad_ckpt_floats = 0;
   float* rpgd_ws = nullptr;            // cpmppi_rpgd_step: check-points [E][H][6][block] then gradients [E][H][block] (cpmppi_rpgd_reserve)
   size_t rpgd_ws_floats = 0;
+  float* cem_ws = nullptr;             // cpmppi_cem_step: samples [E][H][block]; refining, + check-points, gradients, Adam moments (cpmppi_cem_reserve)
+  size_t cem_ws_floats = 0;
   cpmppi::GruNorm gru_norm;
   bool fuse_finalize = true;           // ODE path: the env's last block finalizes in-kernel (CPMPPI_FUSE_FINALIZE=0 disables)
   uint32_t profile_every = 0;          // 0 = off, 1 = every rollout kernel bracketed, n > 1 = one bracket around n steps

@@ -7,6 +7,7 @@
 //   cem_sample_kernel, cem_gmm_sample_kernel   CEM's sampler: one Gaussian per env, or a mixture of K elite-centred ones.
 //   cem_update_kernel                     top-k (bitonic sort in LDS) -> mean and stdev of the elite.
 //   rpgd_step_kernel<COST, INTEG>         the whole rpgd / gradient-tf control step, one workgroup per env (cpmppi_rpgd.hpp).
+//   cem_step_kernel<COST, INTEG, REFINE>  the whole cem / cem-naive-grad / cem-grad-bharadhwaj control step, likewise (cpmppi_cem.hpp).
 // cpmppi_rollout_cost launches rollout_cost_kernel through launch_rollout (cpmppi.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -16,6 +17,7 @@
 #include "cpmppi_internal.hpp"
 #include "cpmppi_grad.hpp"
 #include "cpmppi_rpgd.hpp"
+#include "cpmppi_cem.hpp"
 
 using namespace cpmppi_k;
 
@@ -369,6 +371,128 @@ void launch_rpgd(uint32_t cost_id, dim3 grid, dim3 block, size_t lds, hipStream_
 inline uint32_t rpgd_block(const cpmppi_handle* h) { return (h->cfg.N + 63u) & ~63u; }
 inline size_t rpgd_floats(const cpmppi_handle* h, uint32_t E) { return (size_t)h->cfg.H * 7 * E * rpgd_block(h); }
 
+// ------------------------------------------------------------------------------------------------------------------
+// The fused CEM control step (cpmppi_cem_step; device pieces in cpmppi_cem.hpp): cem-tf and, with REFINE, its two gradient
+// hybrids.  One workgroup = one env, one lane = one sample, the block and its surplus lanes as in rpgd_step_kernel.  The env's mean
+// and stdev live in LDS for the whole step; a lane's sample is a workspace column.  Per outer iteration: every lane draws its row
+// (cem_sample_kernel's statement), refines it (one adjoint sweep + sgd / Adam row update), costs it (forward sweep); the block
+// ranks the costs (the counting rank of rpgd_step_kernel = cem_update_kernel's stable order); lanes k < H refit time-step k to
+// the elite in rank order (cem_update_kernel's statements).  The barrier that opens an iteration closes the refit of the one before:
+// no sample is overwritten while a refit still reads it.
+struct CemPtrs {
+  const float* s0; const float* x_t; const float* te; const float* L; const float* prev_in; const float* m_pole;
+  float* mean; float* stdev;       // [E][H], in place
+  float* samples;                  // [E][H][block]
+  float* ckpt;                     // [E][H][6][block]   (REFINE)
+  float* grad;                     // [E][H][block]      (REFINE)
+  float* m; float* v;              // [E][H][block]      (REFINE, Adam)
+  const unsigned long long* count_dev;
+  unsigned long long seed, offset;
+  uint32_t iterations, best_k, adam, shift, env_offset;
+  float stdev_min, lr, beta1, beta2, eps, gradmax_clip, mean_fill, stdev_fill;
+  float* Q_out; float* S_out; float* plan_out; float* samples_out; uint32_t* order_out;
+};
+
+template <int COST, int INTEG, bool REFINE>
+__global__ __launch_bounds__(BLOCK) void cem_step_kernel(const Params p, const CemPtrs a) {
+  extern __shared__ float cem_step_lds[];            // REFINE: sub[S][6][block] | key[block] | order[block] | mean[H] | stdev[H]
+  const uint32_t tid = threadIdx.x, Nb = blockDim.x, env = blockIdx.x, N = p.N, H = p.H;
+  uint32_t* key = reinterpret_cast<uint32_t*>(cem_step_lds + (REFINE ? (size_t)p.S * 6 * Nb : 0));
+  uint32_t* order = key + Nb;
+  float* mu = reinterpret_cast<float*>(order + Nb);
+  float* sd = mu + H;
+  const bool active = tid < N;
+  const uint64_t base = a.offset + (a.count_dev ? (uint64_t)*a.count_dev * a.iterations : 0ull);
+  for (uint32_t k = tid; k < H; k += Nb) { mu[k] = a.mean[(size_t)env * H + k]; sd[k] = a.stdev[(size_t)env * H + k]; }
+
+  Params pm_;
+  if constexpr (INTEG == PREDICTOR_ODE) pm_ = with_pole_mass(p, a.m_pole ? a.m_pole[env] : p.m_pole);
+  const Params& pi = (INTEG == PREDICTOR_ODE) ? pm_ : p;
+  const EnvConst ec = make_env_const(pi, a.L ? a.L[env] : p.L_default);
+  const size_t col = (size_t)env * H * Nb + tid;
+  float* q = a.samples + col;
+  RpgdLane w;
+  w.s0 = a.s0 + (size_t)env * 6;
+  w.Q = q;
+  w.x_t = a.x_t[env]; w.te = a.te[env]; w.ub0 = a.prev_in ? a.prev_in[env] : 0.0f;
+  w.cos0 = cosf(w.s0[0]); w.sin0 = sinf(w.s0[0]);
+  w.scale = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? 1.0f : 1.0f / (float)(H + 1);
+  w.clip = p.control_mode == CPMPPI_CONTROL_CLIP;
+  w.stride = Nb;
+  w.ckpt = REFINE ? a.ckpt + (size_t)env * H * 6 * Nb + tid : nullptr;
+  w.grad = REFINE ? a.grad + col : nullptr;
+  w.sub = REFINE ? cem_step_lds + tid : nullptr;
+  RpgdLr lr(a.beta1, a.beta2, 0);                    // Adam counts the outer iterations of THIS control step from 1
+  if (REFINE && a.adam && active)                    // ... with fresh moments
+    for (uint32_t k = 0; k < H; ++k) { a.m[col + (size_t)k * Nb] = 0.0f; a.v[col + (size_t)k * Nb] = 0.0f; }
+
+  for (uint32_t it = 0; it < a.iterations; ++it) {
+    const bool last = it + 1 == a.iterations;
+    __syncthreads();                                 // mean / stdev of this iteration stand; the refit before is through
+    float S = 0.0f;
+    if (active) {
+      cem_sample_row(p, mu, sd, a.seed, base + it, a.env_offset + env, tid, q, Nb);
+      if constexpr (REFINE) {
+        (void)rpgd_sweep<COST, INTEG, true>(p, pi, ec, w, true);
+        if (a.adam) {
+          const float lr_t = lr.next(a.lr, a.beta1, a.beta2);
+          rpgd_adam_row<true>(H, q, a.m + col, a.v + col, w.grad, Nb, lr_t, a.beta1, a.beta2, a.eps, a.gradmax_clip, p.lo, p.hi);
+        } else {
+          cem_sgd_row(H, q, w.grad, Nb, a.lr, a.gradmax_clip, p.lo, p.hi);
+        }
+      }
+      S = rpgd_sweep<COST, INTEG, true>(p, pi, ec, w, false);
+      if (last) {
+        if (a.S_out) a.S_out[(size_t)env * N + tid] = S;
+        if (a.samples_out) {
+          float* out = a.samples_out + ((size_t)env * N + tid) * H;
+          for (uint32_t k = 0; k < H; ++k) out[k] = q[(size_t)k * Nb];
+        }
+      }
+    }
+    key[tid] = active ? cem_sort_key(S) : 0xFFFFFFFFu;
+    __syncthreads();
+    if (active) {
+      const uint32_t mine = key[tid];
+      uint32_t rank = 0;
+      for (uint32_t j = 0; j < N; ++j) {
+        const uint32_t kj = key[j];
+        rank += (kj < mine || (kj == mine && j < tid)) ? 1u : 0u;
+      }
+      order[rank] = tid;
+      if (last && a.order_out) a.order_out[(size_t)env * N + rank] = tid;
+    }
+    __syncthreads();                                 // the order, and every lane's row (global memory, block scope)
+    for (uint32_t k = tid; k < H; k += Nb)
+      cem_refit_column(a.samples + ((size_t)env * H + k) * Nb, order, a.best_k, a.stdev_min, mu[k], sd[k]);
+  }
+  __syncthreads();
+  if (tid == 0) a.Q_out[env] = mu[0];
+  for (uint32_t k = tid; k < H; k += Nb) {
+    if (a.plan_out) a.plan_out[(size_t)env * H + k] = mu[k];
+    const uint32_t kk = k + a.shift;
+    a.mean[(size_t)env * H + k] = kk < H ? mu[kk] : a.mean_fill;
+    a.stdev[(size_t)env * H + k] = kk < H ? sd[kk] : a.stdev_fill;
+  }
+}
+
+template <int INTEG, bool REFINE>
+void launch_cem(uint32_t cost_id, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Params& p, const CemPtrs& a) {
+  switch (cost_id) {
+    case CPMPPI_COST_QBGM: hipLaunchKernelGGL((cem_step_kernel<COST_QBGM, INTEG, REFINE>), grid, block, lds, st, p, a); break;
+    case CPMPPI_COST_DEFAULT: hipLaunchKernelGGL((cem_step_kernel<COST_DEFAULT, INTEG, REFINE>), grid, block, lds, st, p, a); break;
+    default: hipLaunchKernelGGL((cem_step_kernel<COST_QBG, INTEG, REFINE>), grid, block, lds, st, p, a); break;
+  }
+}
+
+// floats per env: the samples; refining, also check-points (6), gradient, and Adam's two moments
+inline size_t cem_floats(const cpmppi_handle* h, uint32_t E, bool refine) {
+  return (size_t)h->cfg.H * (refine ? 10 : 1) * E * rpgd_block(h);
+}
+inline size_t cem_lds_bytes(const cpmppi_handle* h, bool refine) {
+  return (((size_t)(refine ? h->cfg.S * 6 : 0) + 2) * rpgd_block(h) + 2 * (size_t)h->cfg.H) * sizeof(float);
+}
+
 // rollout_grad_kernel for the handle's cost (the three costs it is built for: cpmppi_rollout_cost_grad's checks)
 template <int INTEG>
 void launch_grad(uint32_t cost_id, dim3 grid, size_t lds, hipStream_t st, const Params& p, const GradPtrs& a) {
@@ -395,6 +519,12 @@ void allow_large_lds_optim() {
   allow_large_lds(&rpgd_step_kernel<COST_QBGM, PREDICTOR_ODE>);
   allow_large_lds(&rpgd_step_kernel<COST_DEFAULT, PREDICTOR_ODE>);
   allow_large_lds(&rpgd_step_kernel<COST_QBG, PREDICTOR_ODE>);
+  allow_large_lds(&cem_step_kernel<COST_QBGM, PREDICTOR_ODE_V0, true>);
+  allow_large_lds(&cem_step_kernel<COST_DEFAULT, PREDICTOR_ODE_V0, true>);
+  allow_large_lds(&cem_step_kernel<COST_QBG, PREDICTOR_ODE_V0, true>);
+  allow_large_lds(&cem_step_kernel<COST_QBGM, PREDICTOR_ODE, true>);
+  allow_large_lds(&cem_step_kernel<COST_DEFAULT, PREDICTOR_ODE, true>);
+  allow_large_lds(&cem_step_kernel<COST_QBG, PREDICTOR_ODE, true>);
   // the CEM top-k sorts N (padded to a power of two) 8-byte records in LDS: 128 KB at N = 16384
   allow_large_lds(&cem_update_kernel);
 }
@@ -543,6 +673,91 @@ int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* a, void* stream) 
   const size_t lds = ((size_t)h->cfg.S * 6 + 2) * Nb * sizeof(float);
   const auto launch = h->cfg.ode_predictor == CPMPPI_ODE_CROMER ? launch_rpgd<PREDICTOR_ODE> : launch_rpgd<PREDICTOR_ODE_V0>;
   launch(h->prm.cost_id, dim3(a->E), dim3(Nb), lds, s, h->prm, p);
+  CPMPPI_HIP(h, hipGetLastError());
+  if (a->count_dev) hipLaunchKernelGGL(rpgd_count_kernel, dim3(1), dim3(1), 0, s, (unsigned long long*)a->count_dev);
+  return launched(h);
+}
+
+// what cpmppi_cem_step and cpmppi_cem_reserve refuse about the HANDLE: rpgd_check_handle's list, the LDS bound with the refit's
+// mean and stdev on top (without refinement no sub-state buffer: S is free)
+static int cem_check_handle(cpmppi_handle* h, const char* who, bool refine) {
+  const std::string w(who);
+  if (h->prm.cost_id == CPMPPI_COST_LEGACY) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": plugin costs only");
+  if (h->prm.qb_mode != 0u)
+    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": not built for quadratic_boundary / quadratic_boundary_nonconvex "
+                                           "(built: quadratic_boundary_grad_minimal, default, quadratic_boundary_grad)");
+  if (h->cfg.math_mode != CPMPPI_MATH_FAST) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": the sweep is written for the FAST arithmetic");
+  if (h->cfg.N > (uint32_t)BLOCK)
+    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": one workgroup per env holds at most " + std::to_string(BLOCK) + " samples (N = " +
+                                           std::to_string(h->cfg.N) + ")");
+  if (cem_lds_bytes(h, refine) > 150 * 1024) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": S too large for the LDS sub-state buffer");
+  return CPMPPI_OK;
+}
+
+int cpmppi_cem_reserve(cpmppi_handle* h, uint32_t E, uint32_t refine) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (E == 0 || E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_reserve: bad argument (0 < E <= config.E)");
+  if (refine > CPMPPI_CEM_REFINE_ADAM) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_reserve: unknown refine kind");
+  if (const int rc = cem_check_handle(h, "cpmppi_cem_reserve", refine != CPMPPI_CEM_REFINE_NONE)) return rc;
+  CPMPPI_ON_DEVICE(h);
+  const size_t need = cem_floats(h, E, refine != CPMPPI_CEM_REFINE_NONE);
+  if (h->cem_ws_floats >= need) return CPMPPI_OK;
+  if (h->cem_ws) (void)hipFree(h->cem_ws);
+  h->cem_ws = nullptr; h->cem_ws_floats = 0;
+  CPMPPI_HIP(h, hipMalloc(&h->cem_ws, need * sizeof(float)));
+  h->cem_ws_floats = need;
+  return CPMPPI_OK;
+}
+
+int cpmppi_cem_step(cpmppi_handle* h, const cpmppi_cem_args* a, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: null argument block");
+  if (a->E == 0 || a->E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: bad argument (0 < E <= config.E)");
+  if (!a->s0 || !a->target_position || !a->target_equilibrium || !a->mean || !a->stdev || !a->Q_out)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: null pointer (s0, target_position, target_equilibrium, mean, stdev and Q_out are required)");
+  for (const void* ptr : {(const void*)a->s0, (const void*)a->target_position, (const void*)a->target_equilibrium, (const void*)a->L,
+                          (const void*)a->previous_input, (const void*)a->mean, (const void*)a->stdev, (const void*)a->Q_out,
+                          (const void*)a->S_out, (const void*)a->plan_out, (const void*)a->samples_out, (const void*)a->order_out})
+    if (misaligned(ptr)) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: misaligned pointer");
+  if (reinterpret_cast<uintptr_t>(a->count_dev) & 7u) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: misaligned pointer (count_dev: 8 bytes)");
+  if (a->iterations == 0) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: iterations must be > 0");
+  if (a->best_k == 0 || a->best_k > h->cfg.N) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: bad argument (0 < best_k <= N)");
+  if (a->shift > h->cfg.H) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: shift exceeds the horizon");
+  if (a->refine > CPMPPI_CEM_REFINE_ADAM) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: unknown refine kind");
+  const bool refine = a->refine != CPMPPI_CEM_REFINE_NONE;
+  if (const int rc = cem_check_handle(h, "cpmppi_cem_step", refine)) return rc;
+  if (!pole_mass_rows_cover(h, a->E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_cem_step", h, a->E));
+  CPMPPI_ON_DEVICE(h);
+  hipStream_t s = (hipStream_t)stream;
+  if (h->cem_ws_floats < cem_floats(h, a->E, refine)) {
+    // no allocation inside a capture: the workspace is reserved before (cpmppi_cem_reserve)
+    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+    const bool capturing = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+    (void)hipGetLastError();
+    if (capturing)
+      return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: the stream is being captured and the workspace is not reserved "
+                                         "(call cpmppi_cem_reserve before the capture)");
+    if (const int rc = cpmppi_cem_reserve(h, a->E, a->refine)) return rc;
+  }
+  const uint32_t Nb = rpgd_block(h);
+  const size_t plane = (size_t)h->cfg.H * a->E * Nb;           // one [E][H][block] array
+  CemPtrs p{};
+  p.s0 = a->s0; p.x_t = a->target_position; p.te = a->target_equilibrium; p.L = a->L; p.prev_in = a->previous_input;
+  p.m_pole = h->m_pole_rows;
+  p.mean = a->mean; p.stdev = a->stdev;
+  p.samples = h->cem_ws;
+  if (refine) { p.ckpt = h->cem_ws + plane; p.grad = h->cem_ws + 7 * plane; p.m = h->cem_ws + 8 * plane; p.v = h->cem_ws + 9 * plane; }
+  p.count_dev = (const unsigned long long*)a->count_dev;
+  p.seed = a->seed; p.offset = a->offset;
+  p.iterations = a->iterations; p.best_k = a->best_k; p.adam = a->refine == CPMPPI_CEM_REFINE_ADAM; p.shift = a->shift;
+  p.env_offset = a->env_offset;
+  p.stdev_min = a->stdev_min; p.lr = a->learning_rate; p.beta1 = a->beta1; p.beta2 = a->beta2; p.eps = a->epsilon;
+  p.gradmax_clip = a->gradmax_clip; p.mean_fill = a->mean_fill; p.stdev_fill = a->stdev_fill;
+  p.Q_out = a->Q_out; p.S_out = a->S_out; p.plan_out = a->plan_out; p.samples_out = a->samples_out; p.order_out = a->order_out;
+  const bool cromer = h->cfg.ode_predictor == CPMPPI_ODE_CROMER;
+  const auto launch = refine ? (cromer ? launch_cem<PREDICTOR_ODE, true> : launch_cem<PREDICTOR_ODE_V0, true>)
+                             : (cromer ? launch_cem<PREDICTOR_ODE, false> : launch_cem<PREDICTOR_ODE_V0, false>);
+  launch(h->prm.cost_id, dim3(a->E), dim3(Nb), cem_lds_bytes(h, refine), s, h->prm, p);
   CPMPPI_HIP(h, hipGetLastError());
   if (a->count_dev) hipLaunchKernelGGL(rpgd_count_kernel, dim3(1), dim3(1), 0, s, (unsigned long long*)a->count_dev);
   return launched(h);

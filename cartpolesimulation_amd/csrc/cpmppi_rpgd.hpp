@@ -11,7 +11,7 @@ namespace cpmppi {
 // What a lane's sweeps share within one control step.
 struct RpgdLane {
   const float* s0;        // [6] the env's state
-  const float* Q;         // [H] the lane's plan
+  const float* Q;         // [H] the lane's plan (QSTRIDED: [H][stride] + lane)
   float x_t, te, ub0;     // targets, the control applied before this step
   float cos0, sin0;
   float scale;
@@ -24,11 +24,13 @@ struct RpgdLane {
 
 // Cost of the lane's plan; `backward`: also its gradient -> w.grad (a run-time flag, uniform over the launch: the final cost of a
 // control step is the forward half of the one sweep the kernel holds).  `pi`: the block the integration computes with (the
-// env's own pole mass under predictor_ODE), `p`: the launch's (costs).
-template <int COST, int INTEG>
+// env's own pole mass under predictor_ODE), `p`: the launch's (costs).  QSTRIDED: the plan is a workspace column like the
+// check-points (the fused CEM step), not a row.
+template <int COST, int INTEG, bool QSTRIDED = false>
 __device__ __forceinline__ float rpgd_sweep(const Params& p, const Params& pi, const EnvConst& ec, const RpgdLane& w,
                                             bool backward) {
   const uint32_t H = p.H, S = p.S, B = w.stride;
+  auto plan = [&](uint32_t k) __attribute__((always_inline)) { return QSTRIDED ? w.Q[(size_t)k * B] : w.Q[k]; };
   const float t = p.t_step;
   auto forward_substep = [&](State<float>& s, float uK) __attribute__((always_inline)) {
     if constexpr (INTEG == PREDICTOR_ODE) substep_cromer_plain(s, uK, p.t_step, pi, ec);
@@ -46,7 +48,7 @@ __device__ __forceinline__ float rpgd_sweep(const Params& p, const Params& pi, c
       float* ck = w.ckpt + ((size_t)k * 6) * B;
       ck[0] = st.th; ck[B] = st.w; ck[2 * B] = st.c; ck[3 * B] = st.s; ck[4 * B] = st.x; ck[5 * B] = st.v;
     }
-    float ur = w.Q[k];
+    float ur = plan(k);
     if (clip) ur = clamp_(ur, p.lo, p.hi);
     if constexpr (COST == COST_QBGM) cost += stage_qbgm<float, true>(p, st.x, cosang, st.w, ur, x_t, te);
     else if constexpr (COST == COST_DEFAULT) cost += stage_default<float, true>(p, st.x, cosang, ur, x_t, te);
@@ -66,7 +68,7 @@ __device__ __forceinline__ float rpgd_sweep(const Params& p, const Params& pi, c
   for (uint32_t k = H; k-- > 0;) {
     const float* ck = w.ckpt + ((size_t)k * 6) * B;
     const State<float> st0{ck[0], ck[B], ck[2 * B], ck[3 * B], ck[4 * B], ck[5 * B]};
-    const float q = w.Q[k];
+    const float q = plan(k);
     const bool clipped = clip && (q < p.lo || q > p.hi);
     const float ur = clip ? clamp_(q, p.lo, p.hi) : q;
     const float uK = ur * ec.uK_scale;
@@ -84,7 +86,7 @@ __device__ __forceinline__ float rpgd_sweep(const Params& p, const Params& pi, c
     }
     const float ca = (k == 0) ? w.cos0 : st0.c, sa = (k == 0) ? w.sin0 : st0.s;
     float ub = w.ub0;
-    if (COST == COST_QBG && k > 0) { ub = w.Q[k - 1]; if (clip) ub = clamp_(ub, p.lo, p.hi); }
+    if (COST == COST_QBG && k > 0) { ub = plan(k - 1); if (clip) ub = clamp_(ub, p.lo, p.hi); }
     StageGrad sg;
     if constexpr (COST == COST_QBGM) sg = stage_qbgm_grad(p, st0.x, ca, st0.w, ur, x_t, te);
     else if constexpr (COST == COST_DEFAULT) sg = stage_default_grad(p, st0.x, ca, ur, x_t, te);
@@ -111,7 +113,8 @@ struct RpgdLr {
   }
 };
 
-// adam_step_kernel's update of one row, the gradient read from the lane's workspace column.
+// adam_step_kernel's update of one row, the gradient read from the lane's workspace column (ROWSTRIDED: Q, m, v as well).
+template <bool ROWSTRIDED = false>
 __device__ __forceinline__ void rpgd_adam_row(uint32_t H, float* Q, float* m, float* v, const float* grad, uint32_t stride,
                                               float lr_t, float beta1, float beta2, float eps, float gradmax_clip, float lo,
                                               float hi) {
@@ -121,10 +124,11 @@ __device__ __forceinline__ void rpgd_adam_row(uint32_t H, float* Q, float* m, fl
   const float sc = (gradmax_clip > 0.0f && nrm > gradmax_clip) ? gradmax_clip / nrm : 1.0f;
   for (uint32_t k = 0; k < H; ++k) {
     const float gk = grad[(size_t)k * stride] * sc;
-    const float mk = beta1 * m[k] + (1.0f - beta1) * gk;
-    const float vk = beta2 * v[k] + (1.0f - beta2) * gk * gk;
-    m[k] = mk; v[k] = vk;
-    Q[k] = clamp_(Q[k] - lr_t * mk / (sqrtf(vk) + eps), lo, hi);
+    const size_t i = ROWSTRIDED ? (size_t)k * stride : k;
+    const float mk = beta1 * m[i] + (1.0f - beta1) * gk;
+    const float vk = beta2 * v[i] + (1.0f - beta2) * gk * gk;
+    m[i] = mk; v[i] = vk;
+    Q[i] = clamp_(Q[i] - lr_t * mk / (sqrtf(vk) + eps), lo, hi);
   }
 }
 

@@ -667,6 +667,75 @@ class MPPIEngine:
         iterations=)`` updates the host counters and enqueues the launch; with ``count_dev`` nothing changes between steps."""
         return self.rpgd_step(*args, _prepare=True, **kwargs)
 
+    # ------------------------------------------------------------------ the fused CEM control step
+    _CEM_REFINE = {None: _L.CEM_REFINE_NONE, "none": _L.CEM_REFINE_NONE, "sgd": _L.CEM_REFINE_SGD, "adam": _L.CEM_REFINE_ADAM}
+
+    def _cem_refine(self, refine):
+        if refine not in self._CEM_REFINE:
+            raise ValueError(f"refine={refine!r}; expected None, 'sgd' or 'adam'")
+        return self._CEM_REFINE[refine]
+
+    def cem_reserve(self, E=None, refine=None):
+        """cpmppi_cem_reserve: the workspace of ``cem_step`` for up to E envs (default: all), with the check-points, gradient and
+        moments of a refining step (``refine`` 'sgd' / 'adam').  After it the step never allocates - required before a step is
+        captured into a graph."""
+        self._check(self.lib.cpmppi_cem_reserve(self._h, self.E if E is None else int(E), self._cem_refine(refine)))
+
+    def cem_step(self, s0, mean, stdev, target_position, target_equilibrium, L=None, previous_input=None, *, iterations, best_k,
+                 stdev_min, refine=None, learning_rate=0.0, beta1=0.9, beta2=0.999, epsilon=1e-8, gradmax_clip=0.0, shift=1,
+                 mean_fill=0.0, stdev_fill=0.0, seed=0, offset=0, env_offset=0, count_dev=None, Q_out=None, S_out=None,
+                 plan_out=None, samples_out=None, order_out=None, _prepare=False):
+        """cpmppi_cem_step: one whole control step of cem / cem-naive-grad (``refine='sgd'``) / cem-grad-bharadhwaj (``'adam'``) on
+        the sampling distribution ``mean``, ``stdev`` [E,H], both updated IN PLACE (include/cpmppi.h states the step).
+        ``count_dev``: int64 device scalar, the control steps taken so far - iteration i then draws at Philox offset
+        ``offset + count * iterations + i``; incremented after the step (graph replay).
+        -> (Q_out[E], S_out, plan_out, samples_out, order_out), the last four as given (or None)."""
+        E = device_tensor("mean", mean, tail=(self.H,), note=_IN_PLACE).shape[0]
+        if E > self.E:
+            raise ValueError(f"mean must be [E<={self.E},{self.H}], got {tuple(mean.shape)}")
+        if device_tensor("stdev", stdev, tail=(self.H,), note=_IN_PLACE).shape[0] != E:
+            raise ValueError("stdev must have mean's shape")
+        s0 = self.tensor(s0, (E, 6))
+        tp, te = self._per_env(target_position, E), self._per_env(target_equilibrium, E)
+        Lt = self._per_env(L, E) if L is not None else None
+        prev = self._per_env(previous_input, E) if previous_input is not None else None
+        if Q_out is None:
+            Q_out = self.empty(E)
+        for name, t, dtype, tail in (("Q_out", Q_out, torch.float32, ()), ("S_out", S_out, torch.float32, (self.N,)),
+                                     ("plan_out", plan_out, torch.float32, (self.H,)),
+                                     ("samples_out", samples_out, torch.float32, (self.N, self.H)),
+                                     ("order_out", order_out, torch.int32, (self.N,))):
+            if t is not None and device_tensor(name, t, dtype, tail).shape[0] != E:
+                raise ValueError(f"{name} must have {E} rows")
+        a = _L.cpmppi_cem_args()
+        a.E = E
+        a.s0, a.target_position, a.target_equilibrium = s0.data_ptr(), tp.data_ptr(), te.data_ptr()
+        a.L = Lt.data_ptr() if Lt is not None else None
+        a.previous_input = prev.data_ptr() if prev is not None else None
+        a.mean, a.stdev = mean.data_ptr(), stdev.data_ptr()
+        a.iterations, a.best_k, a.stdev_min, a.refine = int(iterations), int(best_k), float(stdev_min), self._cem_refine(refine)
+        a.learning_rate, a.beta1, a.beta2 = float(learning_rate), float(beta1), float(beta2)
+        a.epsilon, a.gradmax_clip = float(epsilon), float(gradmax_clip)
+        a.shift, a.mean_fill, a.stdev_fill = int(shift), float(mean_fill), float(stdev_fill)
+        a.seed, a.offset, a.env_offset = int(seed), int(offset), int(env_offset)
+        if count_dev is not None:
+            if device_tensor("count_dev", count_dev, torch.int64).numel() != 1:
+                raise ValueError("count_dev must have one element")
+            a.count_dev = count_dev.data_ptr()
+        a.Q_out = Q_out.data_ptr()
+        for name, t in (("S_out", S_out), ("plan_out", plan_out), ("samples_out", samples_out), ("order_out", order_out)):
+            setattr(a, name, t.data_ptr() if t is not None else None)
+        out = (Q_out, S_out, plan_out, samples_out, order_out)
+        if _prepare:
+            return PreparedCemStep(self, a, (s0, tp, te, Lt, prev, mean, stdev, count_dev) + out, out)
+        self._check(self.lib.cpmppi_cem_step(self._h, C.byref(a), self._stream()))
+        return out
+
+    def prepare_cem_step(self, *args, **kwargs):
+        """The argument block of ``cem_step(...)`` built and validated ONCE: ``.run(offset=, iterations=)`` updates the host's
+        Philox offset and iteration count and enqueues the launch; with ``count_dev`` nothing changes between steps."""
+        return self.cem_step(*args, _prepare=True, **kwargs)
+
     # ------------------------------------------------------------------ the fused hot path
     def step(self, s0, u_nom, target_position, target_equilibrium, L=None, delta_u=None, knots=None, seed=None,
              offset=0, env_offset=0, u_prev=None, Q_out=None, S_out=None, predictor="ODE_v0", h0=None,
@@ -813,4 +882,21 @@ class PreparedRpgdStep:
             a.iterations = int(iterations)
         e = self.engine
         e._check(e.lib.cpmppi_rpgd_step(e._h, C.byref(a), e._stream()))
+        return self.out
+
+
+class PreparedCemStep:
+    """A validated cpmppi_cem_step argument block plus the tensors it points into (MPPIEngine.prepare_cem_step)."""
+
+    def __init__(self, engine, args, keep, out):
+        self.engine, self.args, self._keep, self.out = engine, args, keep, out
+
+    def run(self, offset=None, iterations=None):
+        a = self.args
+        if offset is not None:
+            a.offset = int(offset)
+        if iterations is not None:
+            a.iterations = int(iterations)
+        e = self.engine
+        e._check(e.lib.cpmppi_cem_step(e._h, C.byref(a), e._stream()))
         return self.out

@@ -106,8 +106,8 @@ class BatchedCartPoleExperiment:
         ``optimizer``: any of the package's optimizers configured for the batch's E envs (`controller_mpc(..., num_envs=E)
         .configure(...).optimizer`: cem, rpgd, gradient, ...) computes the controls instead of the fused MPPI step - host-paced, one
         `optimizer.step` per control period on device tensors, the plant / schedule / recording launch unchanged.  A FUSED rpgd /
-        gradient optimizer (`fused=True`: one cpmppi_rpgd_step per period, its step counter on the device) is not paced by the
-        host and may be captured (``graph=True``) like the MPPI step."""
+        gradient / cem optimizer (`fused=True`: one cpmppi_rpgd_step / cpmppi_cem_step per period, its step counter on the device) is
+        not paced by the host and may be captured (``graph=True``) like the MPPI step."""
         run = ScheduleRun(self.engine, batch, self.seed, env_offset=env_offset, knots_fn=knots_fn, u_nom0=u_nom0, optimizer=optimizer)
         if batch.dt_simulation != self.dt_simulation or batch.n_ctrl != self.n_sub:
             raise ValueError("the batch was drawn for other time scales than this experiment runner's")
@@ -218,7 +218,7 @@ class ScheduleRun:
         """``bind_mass`` False: the caller binds `self.mass` to the engines that launch (pipeline.run_schedule_groups)."""
         self.eng, self.b, self.seed, self.env_offset, self.knots_fn = engine, batch, int(seed), int(env_offset), knots_fn
         self.optimizer = optimizer
-        self.fused = bool(getattr(optimizer, "fused", False))      # a fused rpgd / gradient optimizer: one library call per period
+        self.fused = bool(getattr(optimizer, "fused", False))      # a fused optimizer (rpgd, gradient, the cem family): one library call per period
         if optimizer is not None:
             if getattr(optimizer, "num_envs", batch.E) != batch.E:
                 raise ValueError(f"the optimizer is configured for {optimizer.num_envs} envs, the batch has {batch.E}")
@@ -387,7 +387,7 @@ class ScheduleRun:
             if self.mass.kind != "none":
                 vp.m_pole = self.mass.for_optimizer(0)
             self.optimizer.engine.apply_pole_mass_of(vp, **self.optimizer._mass_rows)
-            self.optimizer.engine.rpgd_reserve()
+            self.optimizer.reserve_fused()
         if self.counter is None:
             self.counter = torch.zeros(1, dtype=torch.int64, device=dev)          # controller calls made
         cap = torch.cuda.Stream(device=dev)

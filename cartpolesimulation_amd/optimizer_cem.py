@@ -6,6 +6,13 @@ itself lives in the absent Control_Toolkit submodule, so the update is the one t
 stdev to the ``cem_best_k`` cheapest, floor stdev at ``cem_stdev_min``}; apply ``mean[0]``; shift mean (append the
 mid-point of the limits) and stdev (append sqrt(0.5)).  Sampling, rollout, cost and the top-k refit all run on the GPU
 (cpmppi_cem_sample, cpmppi_rollout_cost, cpmppi_cem_update); ``num_envs`` problem instances advance in one launch.
+
+``fused=True`` (off by default; cem, cem-naive-grad and cem-grad-bharadhwaj) makes the whole control step ONE library call,
+cpmppi_cem_step: the outer iterations of sampling, refinement, cost, ranking and refit, then the shift, in one kernel, mean and
+stdev updated in place.  ``step`` then only uploads the state; ``step_device`` takes device tensors and, with a device step
+counter, touches the host not at all - the form a captured closed loop replays (harness.py).  The fused step costs its samples
+with the adjoint kernel's forward sweep (sin / cos on every substep) and hands the control of the step before to the cost
+(``previous_input``, read by quadratic_boundary_grad); the staged path above stays what it was.
 """
 import math
 
@@ -17,13 +24,14 @@ from ._optimizer_base import _OptimizerBase
 class optimizer_cem(_OptimizerBase):
     optimizer_name = "cem"
     _unknown_predictor = "the sampling optimizers run on the ODE_v0 and ODE predictors"
+    _fusable = True                  # cpmppi_cem_step is built for this class (not for cem-gmm and random-action)
 
     def __init__(self, predictor=None, cost_function=None, control_limits=None, computation_library=None, seed=None,
                  mpc_horizon=35, mpc_timestep=0.02, cem_outer_it=3, cem_initial_action_stdev=0.5, num_rollouts=200,
                  cem_stdev_min=0.01, cem_best_k=40, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
                  math_mode="fast", intermediate_steps=10, phys=None, device=0, variable_parameters=None, per_env_pole_mass=False,
-                 **kwargs):
+                 fused=False, **kwargs):
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
                          intermediate_steps, control_mode="clip", shift_mode="none", math_mode=math_mode,
@@ -32,6 +40,10 @@ class optimizer_cem(_OptimizerBase):
         self.cem_initial_action_stdev, self.cem_stdev_min = float(cem_initial_action_stdev), float(cem_stdev_min)
         self.warmup, self.warmup_iterations = bool(warmup), int(warmup_iterations)
         self.step_counter = 0
+        self.fused = bool(fused)     # one cpmppi_cem_step per control step instead of the staged launches
+        if self.fused and not self._fusable:
+            raise ValueError(f"fused=True: the fused CEM control step (cpmppi_cem_step) is built for cem, cem-naive-grad and "
+                             f"cem-grad-bharadhwaj, not for {self.optimizer_name}")
 
     def _refine(self, Q, s_t, tp, te, L):
         """Hook of the CEM + gradient hybrids: improve the samples before they are ranked."""
@@ -43,6 +55,42 @@ class optimizer_cem(_OptimizerBase):
         self.stdev = self.engine.zeros(E, H) + self.cem_initial_action_stdev
         self.step_counter = 0
         self._first = True
+        if self.fused:
+            eng = self.engine
+            # what the fused step writes per control step: the controls, the last costs, the mean before the shift
+            self._u, self._S, self._plan = eng.zeros(E), eng.empty(E, self.num_rollouts), eng.empty(E, H)
+            self._previous_input = None
+            self._prepared = self._prepared_key = self._attr_host = self._attr_dev = None
+
+    # -- the fused control step (cpmppi_cem_step) -------------------------------------------------------------------------
+    def _fused_refine(self):
+        """The hybrids: the refine kind and its hyper-parameters, as cem_step's keywords."""
+        return {}
+
+    def reserve_fused(self):
+        """The fused step's workspace (cpmppi_cem_reserve): after it a step never allocates - required before a capture."""
+        self.engine.cem_reserve(refine=self._fused_refine().get("refine"))
+
+    def _fused_call(self, s, tp, te, L, previous_input, count_dev):
+        """One cpmppi_cem_step on device tensors.  The argument block is built once per set of buffers; with ``count_dev`` the
+        call changes nothing on the host (iteration i of step c draws at Philox offset c * cem_outer_it + i), without it
+        ``step_counter`` advances by the iterations taken, as the staged step's does."""
+        key = self._fused_key(s, tp, te, L, previous_input, count_dev)
+        if key != self._prepared_key:
+            self._prepared = self.engine.prepare_cem_step(
+                s, self.dist_mue, self.stdev, tp, te, L, previous_input, iterations=self.cem_outer_it, best_k=self.cem_best_k,
+                stdev_min=self.cem_stdev_min, shift=1, mean_fill=0.5 * (self.action_low + self.action_high),
+                stdev_fill=math.sqrt(0.5), seed=self.seed, offset=0, count_dev=count_dev, Q_out=self._u, S_out=self._S,
+                plan_out=self._plan, **self._fused_refine())
+            self._prepared_key = key
+        if count_dev is not None:
+            self._prepared.run()
+            return self._u
+        iters = self.warmup_iterations if (self.warmup and self._first) else self.cem_outer_it
+        self._first = False
+        self._prepared.run(offset=self.step_counter, iterations=iters)
+        self.step_counter += iters
+        return self._u
 
     def _shift(self):
         """Mean and stdev one control step on: the mid-point of the limits / sqrt(0.5) appended.  -> that mid-point."""
@@ -52,6 +100,8 @@ class optimizer_cem(_OptimizerBase):
         return mid
 
     def step(self, s, time=None, as_tensor=False):
+        if self.fused:
+            return self._step_fused(s, as_tensor)
         s_t, single, E, tp, te, L = self._begin_step(s)
         eng = self.engine
         iters = self.warmup_iterations if (self.warmup and self._first) else self.cem_outer_it
@@ -78,6 +128,7 @@ class optimizer_cem_gmm(optimizer_cem):
     the first input of the best sequence found; the elites are shifted by one step for the next control step.
     [recalled semantics: the class lives in the absent Control_Toolkit submodule; unpinned, stated in DESIGN.md]"""
     optimizer_name = "cem-gmm"
+    _fusable = False                 # (the mixture needs the previous iteration's elites as centres)
 
     def optimizer_reset(self):
         super().optimizer_reset()
@@ -116,6 +167,9 @@ class optimizer_cem_naive_grad(optimizer_cem):
         _, G = self.engine.rollout_cost_grad(s_t, Q, tp, te, L=L)
         return self.engine.sgd_step(Q, G, self.learning_rate, self.gradmax_clip)
 
+    def _fused_refine(self):
+        return {"refine": "sgd", "learning_rate": self.learning_rate, "gradmax_clip": self.gradmax_clip}
+
 
 class optimizer_cem_grad_bharadhwaj(optimizer_cem):
     """``cem-grad-bharadhwaj-tf`` (config_optimizers.yml:32-48; Bharadhwaj et al. 2020, "Model-predictive control via
@@ -130,6 +184,10 @@ class optimizer_cem_grad_bharadhwaj(optimizer_cem):
                          cem_initial_action_stdev=cem_initial_action_stdev, cem_stdev_min=cem_stdev_min, **kwargs)
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
         self.adam_epsilon, self.gradmax_clip = float(adam_epsilon), float(gradmax_clip)
+
+    def _fused_refine(self):
+        return {"refine": "adam", "learning_rate": self.learning_rate, "beta1": self.adam_beta_1, "beta2": self.adam_beta_2,
+                "epsilon": self.adam_epsilon, "gradmax_clip": self.gradmax_clip}
 
     def step(self, s, time=None, as_tensor=False):
         self._m = self._v = None                    # fresh moments every control step
@@ -150,6 +208,7 @@ class optimizer_random_action(optimizer_cem):
     limits every control step, the first input of the cheapest one is applied; nothing is carried over.
     [recalled semantics, class absent from the tree]"""
     optimizer_name = "random-action"
+    _fusable = False
 
     def __init__(self, *args, num_rollouts=640, **kwargs):
         kwargs.pop("cem_outer_it", None)

@@ -27,7 +27,6 @@ form a captured closed loop replays (harness.py).  The staged path above stays w
 """
 import math
 
-import numpy as np
 import torch
 
 from ._optimizer_base import _OptimizerBase
@@ -90,8 +89,6 @@ class _GradientBase(_OptimizerBase):
         return eng.rollout_cost(s_t, self.Q, tp, te, L=L) if self.cfg.cost_function_specification != "quadratic_boundary_grad" \
             else eng.rollout_cost_grad(s_t, self.Q, tp, te, L=L, previous_input=self._previous_input)[0]
 
-    _previous_input = None
-
     def _shift(self, by):
         if by <= 0:
             return
@@ -117,16 +114,14 @@ class _GradientBase(_OptimizerBase):
         """What the fused step does besides Adam: iterations, keep_k, resamp_per, shift and the redraw's distribution."""
         raise NotImplementedError
 
+    def reserve_fused(self):
+        """The fused step's workspace (cpmppi_rpgd_reserve): after it a step never allocates - required before a capture."""
+        self.engine.rpgd_reserve()
+
     def _fused_call(self, s, tp, te, L, previous_input, count_dev):
         """One cpmppi_rpgd_step on device tensors.  The argument block is built once per set of buffers; with ``count_dev`` the
         call changes nothing on the host, without it the host counters advance as the staged step's do."""
-        E = self.num_envs
-        for name, t, shape in (("s", s, (E, 6)), ("target_position", tp, (E,)), ("target_equilibrium", te, (E,)), ("L", L, (E,)),
-                               ("previous_input", previous_input, (E,))):
-            if t is not None and not (torch.is_tensor(t) and t.dtype == torch.float32 and t.is_contiguous()
-                                      and tuple(t.shape) == shape):
-                raise ValueError(f"{name} must be a contiguous float32 tensor of shape {shape} on the engine's device")
-        key = tuple(0 if t is None else t.data_ptr() for t in (s, tp, te, L, previous_input, count_dev))
+        key = self._fused_key(s, tp, te, L, previous_input, count_dev)
         if key != self._prepared_key:
             self._prepared = self.engine.prepare_rpgd_step(
                 s, self.Q, self.m, self.v, tp, te, L, previous_input, learning_rate=self.learning_rate,
@@ -146,47 +141,6 @@ class _GradientBase(_OptimizerBase):
         if plan["resamp_per"] > 0 and plan["keep_k"] < self.num_rollouts and self.count % plan["resamp_per"] == 0:
             self.draws += 1
         return self._u
-
-    @property
-    def controls(self):
-        """The fused step's output [E]: the persistent device tensor every step writes (a closed loop's plant reads it in place)."""
-        return self._u
-
-    def step_device(self, s, target_position, target_equilibrium, L=None, previous_input=None, count_dev=None):
-        """The fused control step on DEVICE tensors: s [E,6], the per-env vectors [E] (L, previous_input: or None), and
-        optionally ``count_dev``, an int64 device scalar holding the control steps taken so far (incremented by the step).
-        Nothing is read back and nothing is uploaded, so the call can be captured into a graph (reserve the workspace with
-        ``engine.rpgd_reserve()`` and apply the pole mass before).  -> the controls [E]: a persistent device tensor that the
-        next step overwrites."""
-        if not self.fused:
-            raise ValueError(f"{type(self).__name__}.step_device needs fused=True")
-        if count_dev is not None and self.warmup:
-            raise ValueError("warmup=True runs warmup_iterations on the first step, which a device step counter cannot tell "
-                             "from the others: use the host counters (count_dev=None) or warmup=False")
-        if self.engine is None:
-            self.configure()
-        return self._fused_call(s, target_position, target_equilibrium, L, previous_input, count_dev)
-
-    def _step_fused(self, s, as_tensor):
-        if self.engine is None:
-            self.configure()
-        eng = self.engine
-        eng.apply_pole_mass_of(self.variable_parameters, **self._mass_rows)
-        s_t = eng.tensor(s)
-        single = s_t.dim() == 1
-        s_t = s_t.reshape(-1, 6)
-        E = s_t.shape[0]
-        if E != self.num_envs:
-            raise ValueError(f"optimizer configured for {self.num_envs} envs, got {E} states")
-        host = self._attributes(E)                       # uploaded only when a value has changed
-        if self._attr_host is None or not all(np.array_equal(a, b) for a, b in zip(host, self._attr_host)):
-            self._attr_host, self._attr_dev = host, tuple(eng.tensor(x) for x in host)
-        u = self._fused_call(s_t, *self._attr_dev, self._previous_input, None)
-        self._previous_input = u                         # (the step reads its env's entry before it writes it)
-        if self.optimizer_logging:
-            self.logging_values = {"Q_logged": u.cpu().numpy(), "J_logged": self._S.cpu().numpy(),
-                                   "u_logged": self._plan.cpu().numpy()}
-        return self._result(u.clone() if as_tensor else u, single, as_tensor)
 
 
 class optimizer_gradient(_GradientBase):

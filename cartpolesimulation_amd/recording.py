@@ -236,6 +236,11 @@ def experiment_folder(root, secondary_experiment_index=None, digits=3):
     return os.path.join(root, base + str(k), "Recordings")
 
 
+# the optimizer names whose whole control step is one library call (--fused)
+FUSED_OPTIMIZERS = ("rpgd", "rpgd-tf", "gradient", "gradient-tf", "cem", "cem-tf", "cem-naive-grad", "cem-naive-grad-tf",
+                    "cem-grad-bharadhwaj", "cem-grad-bharadhwaj-tf")
+
+
 def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, seed=None, cartpole_seed=None, L=None, native=True,
                      graph=False, secondary_experiment_index=None, controller_name="mpc", optimizer_name="mppi", title=None, groups=1,
                      rank=0, world=1, parameters=None, optimizer=None):
@@ -258,7 +263,7 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
     ``optimizer``: one of the package's optimizer objects configured for the run's experiments (`controller_mpc(config_root=...,
     num_envs=n).configure().optimizer` - the shipped config_controllers.yml names rpgd) controls the plants instead of the fused MPPI
     step; `engine` may then be None (the optimizer's own engine runs the plant).  A staged optimizer is paced by the host
-    (graph=False); a fused rpgd / gradient optimizer (`fused=True`) may run captured (graph=True).  Env groups and the multi-GPU
+    (graph=False); a fused rpgd / gradient / cem optimizer (`fused=True`) may run captured (graph=True).  Env groups and the multi-GPU
     gather stay with the MPPI step."""
     import time
     from .harness import BatchedCartPoleExperiment
@@ -274,7 +279,7 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
         if int(groups) > 1:
             raise ValueError("env groups run the fused MPPI step only: an optimizer object needs groups=1")
         if graph and not getattr(optimizer, "fused", False):
-            raise ValueError("an optimizer object is paced by the host: groups=1, graph=False (a fused rpgd / gradient optimizer "
+            raise ValueError("an optimizer object is paced by the host: groups=1, graph=False (a fused rpgd / gradient / cem optimizer "
                              "- fused=True - may be captured)")
         if getattr(optimizer, "engine", None) is None:
             from .shard import env_shard
@@ -355,8 +360,8 @@ def main(argv=None):
                          "rpgd, gradient, ... - paced by the host; with --config-root the default is the checkout's own "
                          "config_controllers.yml `mpc: optimizer` (shipped: rpgd)")
     ap.add_argument("--fused", action="store_true",
-                    help="rpgd / gradient: the whole control step as one library call (cpmppi_rpgd_step) and the closed loop "
-                         "captured as a graph, the step counter on the device")
+                    help="rpgd / gradient / cem / cem-naive-grad / cem-grad-bharadhwaj: the whole control step as one library call "
+                         "(cpmppi_rpgd_step, cpmppi_cem_step) and the closed loop captured as a graph, the step counter on the device")
     ap.add_argument("--cost", default=None,
                     choices=["legacy_mppi_cartpole", "default", "quadratic_boundary_grad_minimal", "quadratic_boundary_grad"])
     args = ap.parse_args(argv)
@@ -412,8 +417,9 @@ def main(argv=None):
         if args.config_root and cfg.per_env_pole_mass:
             over["per_env_pole_mass"] = True
         if args.fused:
-            if opt_name not in ("rpgd", "rpgd-tf", "gradient", "gradient-tf"):
-                raise SystemExit(f"--fused: the fused control step is built for rpgd and gradient, not {opt_name!r}")
+            if opt_name not in FUSED_OPTIMIZERS:
+                raise SystemExit(f"--fused: the fused control step is built for rpgd, gradient, cem, cem-naive-grad and "
+                                 f"cem-grad-bharadhwaj, not {opt_name!r}")
             if args.groups > 1:
                 raise SystemExit("--fused: env groups run the MPPI step only (--groups 1)")
             over["fused"] = True
@@ -422,7 +428,8 @@ def main(argv=None):
         ctrl.configure(opt_name)
         optimizer = ctrl.optimizer
     if args.fused and optimizer is None:
-        raise SystemExit("--fused: the fused control step is built for rpgd and gradient, not 'mppi'")
+        raise SystemExit("--fused: the fused control step is built for rpgd, gradient, cem, cem-naive-grad and "
+                         "cem-grad-bharadhwaj, not 'mppi'")
     # a fused optimizer runs captured unless the run cannot be (a controller pole mass that changes between calls, warm-up)
     graph = bool(args.fused) and not optimizer.warmup
     paths = generate_dataset(eng, n_exp, out, seed=seed, rank=rank, world=world, config=dg, groups=args.groups, parameters=parameters,

@@ -20,6 +20,8 @@
  *                    -> cpmppi_sample() + cpmppi_step()
  *                    optimizer_rpgd.step / optimizer_gradient.step (config_optimizers.yml:49-86), the whole control step
  *                    -> cpmppi_rpgd_step()
+ *                    optimizer_cem.step and its two gradient hybrids (config_optimizers.yml:1-11, 21-48), the whole control step
+ *                    -> cpmppi_cem_step()
  *
  * Conventions
  *   - every array argument is a caller-owned DEVICE pointer to contiguous float32 (e.g. torch.Tensor.data_ptr() of a
@@ -51,7 +53,8 @@ extern "C" {
                                    5: cpmppi_comm_set_stamped (+ cpmppi_comm_info.stamped), cpmppi_groups_comm_init / cpmppi_groups_run_gather;
                                       a caller-given rccl_path now wins over an RCCL the process has already loaded;
                                       cpmppi_set_pole_mass_rows (a new entry point: no layout and no existing semantics change);
-                                      cpmppi_rpgd_step / cpmppi_rpgd_reserve / cpmppi_rpgd_args (new entry points, likewise). */
+                                      cpmppi_rpgd_step / cpmppi_rpgd_reserve / cpmppi_rpgd_args (new entry points, likewise);
+                                      cpmppi_cem_step / cpmppi_cem_reserve / cpmppi_cem_args (new entry points, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -409,6 +412,64 @@ int cpmppi_cem_update(cpmppi_handle* h, uint32_t E, const float* S, const float*
  * rollout uniform over the K centres (the elite sequences of the previous iteration); component_out[E,N] may be NULL. */
 int cpmppi_cem_gmm_sample(cpmppi_handle* h, uint32_t E, const float* centres, uint32_t K, const float* stdev, uint64_t seed,
                           uint64_t offset, uint32_t env_offset, float* Q_out, uint32_t* component_out, void* stream);
+
+/* The whole control step of cem-tf, cem-naive-grad-tf and cem-grad-bharadhwaj-tf for E envs in ONE call: no host
+ * synchronisation, no allocation, and - with count_dev - no launch argument that changes between control steps, so a captured
+ * graph of (step, plant) replays.  It is cpmppi_cem_sample, (the hybrids: cpmppi_rollout_cost_grad + cpmppi_sgd_step /
+ * cpmppi_adam_step,) the cost and cpmppi_cem_update `iterations` times, then the shift, written out below.
+ * `c` = control steps taken before this call: *count_dev if given, else 0.
+ *   for i = 0 .. iterations-1, with the Philox offset o = offset + c * iterations + i:
+ *   1. samples[env, n, :] = what cpmppi_cem_sample(mean, stdev, seed, o, env_offset) draws for rollout n.
+ *   2. refine != NONE: cost gradient of every sample (cpmppi_rollout_cost_grad's arithmetic, previous_input and per-env pole
+ *      masses included), then cpmppi_sgd_step's update (SGD) or cpmppi_adam_step's (ADAM: moments zero at the start of the call,
+ *      t = i + 1, lr_t formed in double in the kernel).
+ *   3. cost S of every (refined) sample: the adjoint kernel's forward sweep (sin / cos evaluated on every substep), i.e.
+ *      cpmppi_rollout_cost_grad's S_out.
+ *   4. mean, stdev = cpmppi_cem_update(S, samples, best_k, stdev_min): the same stable order (NaN last, ties by index), the
+ *      same sums in the same order - bit for bit.
+ *   then Q_out[env] = mean[env, 0], plan_out = mean; S_out, samples_out and order_out (the whole ranking, cheapest first; its
+ *   first best_k entries are the elite) are the LAST iteration's; mean and stdev are shifted left by `shift`, the tail
+ *   filled with mean_fill and stdev_fill; with count_dev: *count_dev += 1 after the step, stream-ordered.
+ * Refused with CPMPPI_ERR_BAD_ARG: a legacy cost, quadratic_boundary / _nonconvex, PRECISE arithmetic, N > 256 (one workgroup per
+ * env, one lane per sample), refining with S beyond the LDS sub-state buffer, best_k == 0 or > N, iterations == 0, shift > H,
+ * an unknown refine kind, a NULL or misaligned required pointer, fewer registered pole-mass rows than E, and a stream under
+ * capture while the workspace of cpmppi_cem_reserve is missing or too small (outside a capture the step allocates it itself).
+ * cpmppi_cem_reserve(h, E, refine): the workspace for steps of up to E envs - H * E * ceil64(N) floats, ten times that when
+ * refining (check-points, gradient, moments). */
+typedef enum { CPMPPI_CEM_REFINE_NONE = 0, CPMPPI_CEM_REFINE_SGD = 1, CPMPPI_CEM_REFINE_ADAM = 2 } cpmppi_cem_refine;
+typedef struct {
+  uint32_t E;                       /* active envs in this call (cpmppi_cem_args) */
+  const float* s0;                  /* [E,6] */
+  const float* target_position;     /* [E] */
+  const float* target_equilibrium;  /* [E] */
+  const float* L;                   /* [E] pole length per env, or NULL = config.L_default */
+  const float* previous_input;      /* [E] control applied before this step, or NULL = 0 */
+  float* mean;                      /* [E,H] the sampling mean, updated in place */
+  float* stdev;                     /* [E,H] the sampling stdev, updated in place */
+  uint32_t iterations;              /* outer iterations in this step */
+  uint32_t best_k;                  /* elite size, 0 < best_k <= N */
+  float stdev_min;
+  uint32_t refine;                  /* cpmppi_cem_refine */
+  float learning_rate;
+  float beta1;
+  float beta2;
+  float epsilon;
+  float gradmax_clip;               /* <= 0: off */
+  uint32_t shift;                   /* 0 .. H */
+  float mean_fill;
+  float stdev_fill;
+  uint64_t seed;                    /* Philox key of the sampler */
+  uint64_t offset;                  /* Philox offset of the first iteration (host mode), or of the first step's (device mode) */
+  uint32_t env_offset;              /* global index of env 0 */
+  uint64_t* count_dev;              /* control steps taken, in DEVICE memory (8-byte aligned), or NULL = host mode */
+  float* Q_out;                     /* [E]   the control: mean[:, 0] before the shift */
+  float* S_out;                     /* [E,N] costs of the last iteration, or NULL */
+  float* plan_out;                  /* [E,H] the mean before the shift, or NULL */
+  float* samples_out;               /* [E,N,H] the (refined) samples of the last iteration, or NULL */
+  uint32_t* order_out;              /* [E,N] the last iteration's ranking (sample rows, cheapest first), or NULL */
+} cpmppi_cem_args;
+int cpmppi_cem_reserve(cpmppi_handle* h, uint32_t E, uint32_t refine);
+int cpmppi_cem_step(cpmppi_handle* h, const cpmppi_cem_args* args, void* stream);
 
 /* a16 alone: S[E,N], delta_u[E,N,H] -> weighted average [E,H] (controller_mppi_cartpole.py:306-321). */
 int cpmppi_reward_weighted_average(cpmppi_handle* h, uint32_t E, const float* S, const float* delta_u, float* out,

@@ -7,10 +7,13 @@ the controller seam (controller_mpc.configure(name) / .step), for E problem inst
 Prints one JSON object per optimizer: ms per controller step (all envs), candidate plans evaluated per second.
 
   python tools/optim_bench.py --fused [--envs 64] [--predictor-specification ODE] [--datagen 256,10]
-rpgd and gradient-tf only, staged and fused (cpmppi_rpgd_step) in the SAME process: one record each through the controller
-seam ("staged", "fused": controller.step, the control read back every step) and one for the fused step on device tensors with the
-step counter on the device ("fused_device": optimizer.step_device, no read-back).  ``--datagen E,seconds``: E experiments of that
-length through the closed loop (harness.run_schedule), launched + staged against captured + fused (rpgd, shipped sizes).
+                              [--optimizers cem-tf,cem-naive-grad-tf,cem-grad-bharadhwaj-tf] [--staged-repeats 3]
+The optimizers with a fused control step (default: gradient-tf and rpgd; the three CEM sections by name), staged and fused
+(cpmppi_rpgd_step / cpmppi_cem_step) in the SAME process: one record each through the controller seam ("staged", "fused":
+controller.step, the control read back every step) and one for the fused step on device tensors with the step counter on the device
+("fused_device": optimizer.step_device, no read-back).  ``--staged-repeats R``: the staged record R times over (its max - min
+spread is the margin a comparison allows).  ``--datagen E,seconds``: E experiments of that length through the closed loop
+(harness.run_schedule), launched + staged against captured + fused (the first of --optimizers, shipped sizes).
 """
 import argparse
 import json
@@ -31,6 +34,8 @@ ap.add_argument("--envs", type=int, default=64)
 ap.add_argument("--steps", type=int, default=30)
 ap.add_argument("--predictor-specification", default="ODE_v0")
 ap.add_argument("--fused", action="store_true", help="rpgd and gradient-tf, staged against fused, in this one process")
+ap.add_argument("--optimizers", default="gradient-tf,rpgd", help="with --fused: comma-separated optimizer names")
+ap.add_argument("--staged-repeats", type=int, default=1, help="with --fused: how many times the staged record is measured")
 ap.add_argument("--datagen", default=None, help="with --fused: E,seconds of the closed-loop data generator, e.g. 256,10")
 args = ap.parse_args()
 E = args.envs
@@ -52,8 +57,9 @@ def timed(fn, steps):
 
 def fused_bench():
     spec = args.predictor_specification
-    for name in ("gradient-tf", "rpgd"):
-        for mode in ("staged", "fused", "fused_device"):
+    names = [n for n in args.optimizers.split(",") if n]
+    for name in names:
+        for mode in ("staged",) * max(1, args.staged_repeats) + ("fused", "fused_device"):
             ctrl = controller_mpc("CartPole", {"target_position": 0.0, "target_equilibrium": 1.0, "L": 0.395},
                                   control_limits=([-1.0], [1.0]), num_envs=E, config=dict(seed=1, fused=mode != "staged"))
             ctrl.configure(name, predictor_specification=spec)
@@ -68,7 +74,7 @@ def fused_bench():
                 dt = timed(lambda: ctrl.step(s, 0.0, {}), args.steps)
             print(json.dumps({"bench": "controller_step", "optimizer": name, "mode": mode, "predictor": opt.cfg.predictor_type, "envs": E,
                               "num_rollouts": opt.num_rollouts, "mpc_horizon": opt.mpc_horizon,
-                              "iterations": getattr(opt, "outer_its", getattr(opt, "gradient_steps", None)),
+                              "iterations": getattr(opt, "outer_its", getattr(opt, "gradient_steps", getattr(opt, "cem_outer_it", None))),
                               "ms_per_controller_step": round(dt * 1e3, 4)}), flush=True)
             eng.close()
     if args.datagen:
@@ -78,7 +84,7 @@ def fused_bench():
         cfg = dict(seed=5, length_of_experiment=seconds)
         for mode, graph in (("launched_staged", False), ("launched_fused", False), ("captured_fused", True)):
             ctrl = controller_mpc("CartPole", {}, control_limits=([-1.0], [1.0]), num_envs=n, config=dict(seed=1, fused=mode != "launched_staged"))
-            ctrl.configure("rpgd", predictor_specification=spec)
+            ctrl.configure(names[0], predictor_specification=spec)
             opt = ctrl.optimizer
             best = None
             for _ in range(2):                                  # (the first run pays the one-time costs)
@@ -89,7 +95,7 @@ def fused_bench():
                 BatchedCartPoleExperiment(opt.engine, b.dt_simulation, b.dt_control, seed=0).run_schedule(b, graph=graph, optimizer=opt)
                 torch.cuda.synchronize()
                 best = time.perf_counter() - t0
-            print(json.dumps({"bench": "data_generator", "optimizer": "rpgd", "mode": mode, "predictor": opt.cfg.predictor_type,
+            print(json.dumps({"bench": "data_generator", "optimizer": names[0], "mode": mode, "predictor": opt.cfg.predictor_type,
                               "experiments": n, "length_s": seconds, "control_periods": int(b.n_periods), "seconds": round(best, 4),
                               "ms_per_control_period": round(best / (b.n_periods + 1) * 1e3, 4)}), flush=True)
             opt.engine.close()
