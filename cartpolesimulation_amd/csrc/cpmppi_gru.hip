@@ -233,6 +233,7 @@ template <int COST, int NOISE>
 void launch_gru(cpmppi_handle* h, const cpmppi_step_args* a, const StepPtrs& p, hipStream_t s) {
   const bool f16 = h->cfg.math_mode == CPMPPI_MATH_FAST && h->gru16_image != nullptr;
   const size_t lds = ((f16 ? (size_t)G16_IMAGE_BYTES / 4 : (size_t)GRU_IMAGE_FLOATS) + (size_t)WAVES * p.W) * sizeof(float);
+  // (host code that no allowed H reaches: at H = CPMPPI_MAX_HORIZON = 1024 the images need 64 640 B (FAST) and 64 416 B (PRECISE))
   if (lds > 64 * 1024) {   // long horizons with a perturbation buffer: weights image + [WAVES][H] sums
     allow_large_lds(&gru_rollout_cost_kernel<COST, NOISE, true>);
     allow_large_lds(&gru_rollout_cost_kernel<COST, NOISE, false>);

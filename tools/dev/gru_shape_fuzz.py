@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Development tool (GPU): the GRU-predictor MPPI step against the numpy GRU oracle over RANDOM shapes — envs, ragged
 rollout counts around the 32-rollout tile and the 128-rollout block, horizons, knot periods, the two supported cost
-plugins, noise source (delta_u / knots), math mode, random weights and normalisation, non-zero memory.  Rules as
+plugins, the four glue flags (control_mode, shift_mode, correction_u, horizon_reduce), action limits, noise source (delta_u /
+knots / in-kernel Philox), math mode, random weights and normalisation, non-zero memory.  Rules as
 tests/test_gpu_gru.py (1e-4 relative cost band + the oracle's own float32/float64 gap; rollouts the float32 oracle cannot
 pin to a quarter of the band are flagged).   python tools/dev/gru_shape_fuzz.py --n 60 --seed 1"""
 import argparse
@@ -33,9 +34,12 @@ for it in range(args.n):
     period = int(rng.choice([1, 3, 5, 10]))
     cost_name, cost_id = [("quadratic_boundary_grad_minimal", O.COST_QBGM), ("default", O.COST_DEFAULT)][int(rng.integers(0, 2))]
     math = str(rng.choice(["fast", "precise"]))
-    noise = str(rng.choice(["delta_u", "knots"]))
+    noise = str(rng.choice(["delta_u", "knots", "philox"]))
     scale = float(rng.choice([0.3, 0.7]))
-    desc = dict(E=E, N=N, H=H, period=period, cost=cost_name, math=math, noise=noise, scale=scale)
+    glue = dict(control_mode=str(rng.choice(["clip", "penalise"])), shift_mode=str(rng.choice(["repeat_last", "append_zero", "none"])),
+                correction_u=str(rng.choice(["u_run", "u_nom"])), horizon_reduce=str(rng.choice(["sum", "mean"])))
+    lo, hi = [(-1.0, 1.0), (-0.7, 0.9)][int(rng.integers(0, 2))]
+    desc = dict(E=E, N=N, H=H, period=period, cost=cost_name, math=math, noise=noise, scale=scale, lo=lo, hi=hi, **glue)
     try:
         u = lambda *s: (scale * rng.uniform(-1, 1, s)).astype(f32)  # noqa: E731
         model = dict(w_ih0=u(96, 6), w_hh0=u(96, 32), b_ih0=u(96), b_hh0=u(96), w_ih1=u(96, 32), w_hh1=u(96, 32), b_ih1=u(96),
@@ -43,7 +47,7 @@ for it in range(args.n):
                      in_scale=rng.uniform(0.5, 2.0, 6).astype(f32), in_shift=(0.1 * rng.uniform(-1, 1, 6)).astype(f32),
                      out_scale=rng.uniform(0.5, 1.5, 5).astype(f32), out_shift=(0.05 * rng.uniform(-1, 1, 5)).astype(f32))
         eng = MPPIEngine(E, MPPIConfig(num_rollouts=N, mpc_horizon=H, period_interpolation_inducing_points=period,
-                                       cost_function_specification=cost_name, math_mode=math))
+                                       cost_function_specification=cost_name, math_mode=math, action_low=lo, action_high=hi, **glue))
         eng.set_gru(model)
         s0 = np.stack([O.create_cartpole_state(rng.uniform(-1, 1), rng.uniform(-2, 2), rng.uniform(-0.1, 0.1), rng.uniform(-0.2, 0.2))
                        for _ in range(E)])
@@ -51,18 +55,21 @@ for it in range(args.n):
         te = np.ones(E, f32)
         u0 = (0.2 * rng.standard_normal((E, H))).astype(f32)
         h0 = (0.3 * rng.standard_normal((E, 2, 32))).astype(f32)
-        kn, du = eng.sample(seed=int(rng.integers(1, 1 << 30)), offset=it, knots=True, delta_u=True)
+        seed = int(rng.integers(1, 1 << 30))
+        kn, du = eng.sample(seed=seed, offset=it, knots=True, delta_u=True)       # (the oracle's perturbations, whatever the source)
         un = eng.tensor(u0.copy())
         S = eng.empty(E, N)
         if noise == "delta_u":
             eng.step(s0, un, tp, te, S_out=S, predictor="GRU", h0=h0, delta_u=du)
-        else:
+        elif noise == "knots":
             eng.step(s0, un, tp, te, S_out=S, predictor="GRU", h0=h0, knots=kn)
+        else:
+            eng.step(s0, un, tp, te, S_out=S, predictor="GRU", h0=h0, seed=seed, offset=it)
         Sh, uh, duh = S.cpu().numpy(), un.cpu().numpy(), du.cpu().numpy()
-        cfg = O.MPPIConfig(N=N, H=H, period=period, cost_id=cost_id)
+        cfg = O.MPPIConfig(N=N, H=H, period=period, cost_id=cost_id, **glue)
         for e in range(E):
-            ref = O.gru_mppi_step(model, s0[e], u0[e], duh[e], tp[e], te[e], cfg, h0=h0[e])
-            ref64 = O.gru_mppi_step(model, s0[e], u0[e], duh[e], tp[e], te[e], cfg, h0=h0[e], dtype=np.float64)
+            ref = O.gru_mppi_step(model, s0[e], u0[e], duh[e], tp[e], te[e], cfg, h0=h0[e], low=lo, high=hi)
+            ref64 = O.gru_mppi_step(model, s0[e], u0[e], duh[e], tp[e], te[e], cfg, h0=h0[e], low=lo, high=hi, dtype=np.float64)
             PU.assert_costs(Sh[e], ref["S"], ref64["S"], PU.flag_rounding_sensitive(ref["S"], ref64["S"]), f"env {e} costs")
             # the update is checked GIVEN the kernel's own costs (float64 soft-min of S_gpu over the same perturbations):
             # with random weights the network drives every rollout off the track, costs are ~1e9 under LBD = 100, and a
@@ -70,8 +77,11 @@ for it in range(args.n):
             # to more than that, which a comparison of u against the oracle's u would only restate
             Sg = Sh[e].astype(np.float64)
             w = np.exp(-(Sg - Sg.min()) / 100.0)
-            ush = np.concatenate([u0[e, 1:], u0[e, -1:]]).astype(np.float64)
-            u_exp = np.clip(ush + (w @ duh[e].astype(np.float64)) / w.sum(), -1.0, 1.0)
+            tail = {"repeat_last": u0[e, -1:], "append_zero": np.zeros(1, f32)}.get(glue["shift_mode"])
+            ush = (u0[e] if tail is None else np.concatenate([u0[e, 1:], tail])).astype(np.float64)
+            u_exp = ush + (w @ duh[e].astype(np.float64)) / w.sum()
+            if glue["control_mode"] == "clip":
+                u_exp = np.clip(u_exp, lo, hi)
             assert np.abs(uh[e] - u_exp).max() <= 2e-5, f"env {e} u_nom: update differs from the soft-min of the kernel's own costs by {np.abs(uh[e] - u_exp).max():.2e}"
             if np.max(PU.softmin_allowance(ref["S"], ref64["S"], duh[e], LBD=100.0)) < 1e-4 and (N < 2 or np.ptp(np.sort(ref["S"])[:2]) > 1e-4 * abs(ref["S"].min())):
                 PU.assert_controls(uh[e], ref["u_new"], ref64["u_new"], f"env {e} u_nom vs oracle")
