@@ -45,7 +45,9 @@ _ODE = [
 
 BOUNDARY_ROWS = [Row("ODE_v0", E, N, o, False, "philox", COSTS[0], *exp) for E, N, o, *exp in _V0] + \
                 [Row("ODE", E, N, o, rows, "philox", COSTS[0], *exp, False) for rows in (False, True) for E, N, o, *exp in _ODE]
-# one row per cost function (2 x 512: one rollout per lane in 4 blocks, the latency build) and per noise source other than Philox
+# one row per cost function (2 x 512: one rollout per lane in 4 blocks, the latency build) and per noise source other than Philox.
+# (NOISE_ROWS only ask WHICH kernel runs, at one build - 256 blocks, the lone-wave form: what the buffer noise sources and the other
+# costs COMPUTE in every build is held to the oracle by the matrix, rollout_matrix.py / test_gpu_rollout_matrix.py)
 COST_ROWS = [Row("ODE_v0", 2, 512, {}, False, "philox", c, 1, 1, 0, 4, False) for c in COSTS]
 NOISE_ROWS = [Row("ODE_v0", 256, 512, {}, False, n, COSTS[0], 1, 2, 3, 256, False) for n in ("knots", "delta_u", "delta_u_tiled")]
 ROWS = BOUNDARY_ROWS + COST_ROWS + NOISE_ROWS

@@ -17,6 +17,7 @@ from cartpolesimulation_amd.engine import MPPIEngine  # noqa: E402
 from cartpolesimulation_amd.configs import MPPIConfig  # noqa: E402
 from oracle import oracle_np as O  # noqa: E402
 import parity_util as PU  # noqa: E402
+import hanging_target  # noqa: E402  (beside this file)
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--n", type=int, default=100)
@@ -79,13 +80,10 @@ for it in range(args.n):
         Sh, uh, duh = Sg.cpu().numpy(), un.cpu().numpy(), du.cpu().numpy()
         for e in range(E):
             if cost_name == "default" and te[e] < 0:
-                # default.py's angle term is 20000 * te * 0.25 (1 - cos)^2: NEGATIVE for the hanging target, so a rollout's
-                # total is a difference of terms of ~1e4 per stage and a bound relative to |S| is a bound on cancellation,
-                # not on the kernel: these are compared against the magnitude of the terms (1e-5 of the largest possible stage term)
-                scale = 20000.0 * (1.0 if glue["horizon_reduce"] == "mean" else H)
-                dS = np.abs(Sh[e].astype(np.float64) - ref["S_a"][e])
-                bound = 1e-4 * np.abs(ref["S_a"][e]) + PU.envelope(ref["S_a"][e], ref["S_b"][e], *[a[e] for a in S_alt]) + 1e-5 * scale
-                assert not np.any((dS > bound) & ~ref["flags"][e]), f"env {e} costs (hanging target): {int(((dS > bound) & ~ref['flags'][e]).sum())} outside"
+                # default.py's angle term is NEGATIVE for the hanging target: compared against the magnitude of the terms
+                # (hanging_target.py beside this file; shared with tests/test_gpu_rollout_matrix.py)
+                hanging_target.assert_hanging_default_costs(Sh[e], ref["S_a"][e], ref["S_b"][e], ref["flags"][e], f"env {e} costs (hanging target)",
+                                                            S_alt=[a[e] for a in S_alt], H=H, horizon_reduce=glue["horizon_reduce"])
                 continue
             PU.assert_costs(Sh[e], ref["S_a"][e], ref["S_b"][e], ref["flags"][e], f"env {e} costs", flag_sensitive=True,
                             S_alt=[a[e] for a in S_alt], sens_rtol=(0.25e-4 if args.probes else 1e-4),
