@@ -2,6 +2,11 @@
 gets from ``controller_mpc.configure`` (control limits, seed, cost inherited from the cost-function object, MPPIConfig, engine
 bookkeeping), the ``dt`` / ``num_envs`` / predictor part of ``configure``, and the per-step prologue (state -> [E,6], per-env
 attributes) and epilogue (controls -> [1] / [E,1]).  The optimizers' own signatures, defaults and attributes are theirs.
+
+The neural predictor (``gru_model=`` / a ``GRU-6IN-32H1-32H2-5OUT*`` specification) is settled here too, for the optimizers that
+run on it - mppi in its fused step, cem, cem-gmm and random-action through the cost-only GRU rollout - and for those that refuse
+it by name: which of specification and model selects it, the model's upload, the memory ``h`` [E,2,32] per env and its hand-over
+from one control step to the next.
 """
 import os
 import time as _time
@@ -9,6 +14,13 @@ import time as _time
 import numpy as np
 
 from .configs import MPPIConfig, PhysicalParameters, ode_predictor_type
+
+
+GRU_SPECIFICATION = "GRU-6IN-32H1-32H2-5OUT"      # SI_Toolkit_ASF/config_predictors.yml:8-13: the names of the neural predictor
+
+
+def is_gru_specification(spec):
+    return spec is not None and str(spec).startswith(GRU_SPECIFICATION)
 
 
 def _vec(x, E, default):
@@ -21,11 +33,17 @@ def _vec(x, E, default):
 class _OptimizerBase:
     _cost_name_attributes = ("cost_name",)           # where a cost-function object keeps its name
     _unknown_predictor = "this optimizer runs on the ODE_v0 and ODE predictors"
+    _gru_refusal = None                               # a class that cannot run on the GRU predictor: why not (its own sentence)
 
     def __init__(self, cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                  variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
-                 intermediate_steps, **config):
-        """``config``: the remaining MPPIConfig fields, which differ from optimizer to optimizer."""
+                 intermediate_steps, gru_model=None, **config):
+        """``config``: the remaining MPPIConfig fields, which differ from optimizer to optimizer.  ``gru_model``: dict of
+        GRU-6IN-32H1-32H2-5OUT weights or a model-folder path -> the neural predictor in the rollout loop."""
+        if gru_model is not None and self._gru_refusal:
+            raise NotImplementedError(self._gru_refusal)
+        self.gru_model = gru_model
+        self.h = None                                      # its memory per env [E,2,32] (controller_mppi_cartpole.py:566-567 update)
         low, high = (-1.0, 1.0) if control_limits is None else (float(np.asarray(control_limits[0]).reshape(-1)[0]),
                                                                   float(np.asarray(control_limits[1]).reshape(-1)[0]))
         self.action_low, self.action_high = low, high
@@ -52,9 +70,50 @@ class _OptimizerBase:
 
     # -- configure ------------------------------------------------------------------------------------------------
     def configure(self, dt=None, predictor_specification=None, num_envs=None, **kwargs):
-        self._configure_problem(dt, predictor_specification, num_envs)
+        # (a GRU specification leaves the ODE integrator of the constructor alone: the network runs inside the rollout kernel)
+        self._configure_problem(dt, None if is_gru_specification(predictor_specification) else predictor_specification, num_envs)
+        neural = self._gru_selected(predictor_specification)
         self.engine = self._new_engine()
+        self._attach_gru(neural)
         self.optimizer_reset()
+
+    def _gru_selected(self, predictor_specification):
+        """Specification and ``gru_model`` together -> does the network predict?  A specification without a model and a model
+        beside an ODE specification are errors, a model alone selects the GRU; a class without a GRU path refuses both."""
+        neural = is_gru_specification(predictor_specification)
+        if (neural or self.gru_model is not None) and self._gru_refusal:
+            raise NotImplementedError(self._gru_refusal)
+        if isinstance(self.gru_model, (str, bytes)) or hasattr(self.gru_model, "__fspath__"):
+            from .model_folder import load_gru_model          # an SI_Toolkit model folder (net-info, normalisation, weights)
+            self.gru_model = load_gru_model(self.gru_model)
+        if neural and self.gru_model is None:
+            raise ValueError("a GRU predictor_specification needs gru_model=dict(weights) or a model folder path "
+                             "(no GRU model files ship in-tree)")
+        if self.gru_model is not None and not (neural or predictor_specification is None):
+            raise ValueError(f"gru_model was given but predictor_specification={predictor_specification!r} selects the ODE "
+                             "predictor: the model would be ignored")
+        return self.gru_model is not None
+
+    def _attach_gru(self, neural):
+        """The new engine gets the model, every env a zero memory; without the network there is none."""
+        if neural:
+            self.engine.set_gru(self.gru_model)
+            self.h = self.engine.zeros(self.num_envs, 2, 32)
+        else:
+            self.h = None
+
+    def _reset_memory(self):
+        if self.h is not None:
+            self.h.zero_()
+
+    def _advance_memory(self, s_t, u):
+        """Advance the network's memory with the state just seen and the control just chosen (update_internal_state): s_t [E,6],
+        u [E].  The memory travels as [E,2,32] (the rollout kernels' layout) and through gru_predict as [2,E,32]."""
+        if self.h is None:
+            return
+        _, h_new = self.engine.gru_predict(s_t, u.reshape(self.num_envs, 1), h0=self.h.transpose(0, 1).contiguous(),
+                                           return_hidden=True)
+        self.h = h_new.transpose(0, 1).contiguous()
 
     def _configure_problem(self, dt, predictor_specification, num_envs):
         if dt is not None:

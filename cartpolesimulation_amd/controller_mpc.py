@@ -9,6 +9,7 @@ from types import SimpleNamespace
 
 import numpy as np
 
+from ._optimizer_base import is_gru_specification
 from .configs import MPPIConfig, PhysicalParameters
 from .cost_functions import CostFunctionWrapper
 from .optimizer_cem import (optimizer_cem, optimizer_cem_gmm, optimizer_cem_grad_bharadhwaj, optimizer_cem_naive_grad,
@@ -144,8 +145,15 @@ class controller_mpc(template_controller):
             "quadratic_boundary_grad_minimal"
         self.controller_logging = controller_logging
         spec = predictor_specification or cfg.pop("predictor_specification", None)
-        if spec is None and cfg.get("predictor_type") == "ODE":      # (a checkout's config_controllers.yml:3 read by config_root)
+        # a checkout's config_controllers.yml:3 read by config_root names the ODE predictor as the DEFAULT: a gru_model handed over
+        # explicitly wins over it, as in `configure` for mppi; an ODE specification beside a model is an error
+        if spec is None and cfg.get("predictor_type") == "ODE" and cfg.get("gru_model") is None:
             spec = "ODE"
+        neural = is_gru_specification(spec)
+        if cfg.get("gru_model") is not None and spec is not None and not neural:
+            raise ValueError(f"gru_model was given but predictor_specification={spec!r} selects the ODE predictor")
+        if neural or cfg.get("gru_model") is not None:
+            self.predictor = None            # the network runs inside the rollout kernel; no ODE seam object
         self.cost_function_wrapper = CostFunctionWrapper()
         self.cost_function_wrapper.configure(variable_parameters=self.variable_parameters,
                                              environment_name=self.environment_name,

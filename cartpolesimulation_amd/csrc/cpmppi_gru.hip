@@ -5,7 +5,9 @@
 //   gru_predict_kernel                      predictor seam with the neural predictor: trajectories [B,H+1,6], hidden states.
 //   gru_rollout_cost_kernel<COST,NOISE,F16> the fused MPPI step with the GRU predictor: same contract as rollout_cost_kernel
 //                                           (plugin costs); launched by step_impl through launch_gru_rollout.
-// Entry points: cpmppi_set_gru, cpmppi_gru_predict; -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write
+//   gru_cost_only_kernel<COST,F16>          costs of GIVEN input plans under the GRU predictor, nothing of the MPPI update: the
+//                                           building block of the sampling optimizers (cem, cem-gmm, random-action).
+// Entry points: cpmppi_set_gru, cpmppi_gru_predict, cpmppi_rollout_cost_gru; -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write
 // g_gru_stamp_sum are this unit's).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -228,6 +230,112 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_rollout_cost_kernel(
   }
 }
 
+// Cost-only rollout with the GRU predictor: S[env][n] = get_trajectory_cost(predict_core_GRU(s0[env], inputs[env][n]), inputs[env][n]).
+// The statements of gru_rollout_cost_kernel<COST, NOISE_DELTA_U, F16> for a zero nominal sequence, no shift and cc_weight = 0 -
+// same tile mapping (32 rollouts per wave, GRU_ROLLOUTS_PER_BLOCK per workgroup, grid E x nb), same cell, same cost statements in
+// the same order - without anything that serves the MPPI update: no block minimum, no weights, no weighted sums of the noise, no
+// partials.  Dynamic LDS holds the weights image only, and after its load no wave depends on another: a wave whose 32 rollouts
+// all lie beyond N leaves at once, and there is no barrier behind the one of the image load.
+// The lane's next input does not depend on the state: it is loaded one control step ahead, off the recurrent chain.
+struct GruCostPtrs {
+  const float* s0;       // [E,6]
+  const float* inputs;   // [E,N,H]
+  const float* x_t;      // [E] target position
+  const float* te;       // [E] target equilibrium
+  const float* h0;       // [E,2,32] or NULL = 0
+  float* S_out;          // [E,N]
+  uint32_t nb;           // blocks per env
+};
+
+template <int COST, bool F16>
+__global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_cost_only_kernel(const Params p, const GruCostPtrs a, const GruNorm nm,
+                                                                              const float* __restrict__ image) {
+  extern __shared__ float lds[];                           // GRU image only
+  constexpr int IMAGE_FLOATS = F16 ? G16_IMAGE_BYTES / 4 : GRU_IMAGE_FLOATS;
+  for (int i = threadIdx.x; i < IMAGE_FLOATS; i += BLOCK) lds[i] = image[i];
+  __syncthreads();                                         // the kernel's only barrier
+  const uint32_t env = blockIdx.x / a.nb, blk = blockIdx.x % a.nb;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = lane & 31u;
+  const uint32_t row0 = blk * GRU_ROLLOUTS_PER_BLOCK + wave * 32;
+  if (row0 >= p.N) return;                                 // (wave-uniform) a tile without a rollout
+  const uint32_t n = row0 + c;
+  const bool owner = lane < 32 && n < p.N;                 // the lane that accounts for rollout n
+  const uint32_t nn = n < p.N ? n : 0;
+  const uint32_t H = p.H;
+  const float x_t = a.x_t[env], te = a.te[env];
+  const float* __restrict__ s0 = a.s0 + (size_t)env * 6;
+  const float* __restrict__ in = a.inputs + ((size_t)env * p.N + nn) * H;
+  f16v h1 = gru_load_hidden(a.h0 ? a.h0 + (size_t)env * 64 : nullptr, lane);
+  f16v h2 = gru_load_hidden(a.h0 ? a.h0 + (size_t)env * 64 + 32 : nullptr, lane);
+
+  float st[6] = {s0[0], s0[1], s0[2], s0[3], s0[4], s0[5]};
+  float cost = 0.0f;
+  float cosang = cosf(s0[0]);               // the plugins take cos(angle) of the given state at stage 0
+  f16v x;
+  GruCarry carry;
+  Gru16Carry carry16;
+  Gru16State gs;
+  const char* __restrict__ ldsb = reinterpret_cast<const char*>(lds);
+  if constexpr (F16) {
+    gs.h1 = h1; gs.h2 = h2;
+    gru16_carry_init(ldsb, gs, lane, carry16);
+  } else {
+    gru_carry_init(lds, h1, lane, carry);
+  }
+  const bool half1 = lane >= 32;
+#ifdef CPMPPI_GRU_STAMPS
+  unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0};   // (the stamps are the fused kernel's: taken and dropped here)
+  unsigned long long stamp_prev = 0;
+#endif
+  float u_next = in[0];
+  for (uint32_t k = 0; k < H; ++k) {
+    float ur = u_next;
+    if (k + 1 < H) u_next = in[k + 1];                     // in flight during this step's cell
+    if (p.control_mode == CPMPPI_CONTROL_CLIP) ur = clamp_(ur, p.lo, p.hi);
+    if constexpr (COST == COST_QBGM) cost += stage_qbgm<float, F16>(p, st[4], cosang, st[1], ur, x_t, te);
+    else cost += stage_default<float, F16>(p, st[4], cosang, ur, x_t, te);
+    if (k == 0) x = gru_input_tile(nm, s0, ur, lane);
+    else if (half1) x[1] = __builtin_fmaf(ur, nm.in_scale[0], nm.in_shift[0]);
+    float out[5];
+    if constexpr (F16) {
+#ifdef CPMPPI_GRU_STAMPS
+      const f16v o = gru16_step(ldsb, x, gs, carry16, lane, stamp_acc, stamp_prev);
+#else
+      const f16v o = gru16_step(ldsb, x, gs, carry16, lane);
+#endif
+      out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3];
+      out[4] = __shfl(o[0], (int)(c + 32u), 64);           // positionD (row 4) lives on the partner lane-half
+      if (half1) out[4] = o[0];
+    } else {
+#ifdef CPMPPI_GRU_STAMPS
+      gru_step_pipelined(lds, x, h1, h2, carry, lane, out, stamp_acc, stamp_prev);
+#else
+      gru_step_pipelined(lds, x, h1, h2, carry, lane, out);
+#endif
+    }
+    gru_output_state_fast(nm, out, st, cosang);
+    // normalised outputs are fed back unchanged: rows 0..3 on lane-half 0, row 4 (and Q, row 5) on lane-half 1
+    x[0] = half1 ? out[4] : out[0];
+    x[1] = half1 ? 0.0f : out[1];
+    x[2] = half1 ? 0.0f : out[2];
+    x[3] = half1 ? 0.0f : out[3];
+  }
+  st[0] = atan2f(st[3], st[2]);             // predictors_customization.py:121-127, needed for the terminal cost only
+  const float term = (COST == COST_DEFAULT) ? terminal_indicator<float>(p, st[0], st[4], x_t) : 0.0f;
+  const float S_total = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? (cost + term) : (cost + term) / (float)(H + 1);
+  if (owner) a.S_out[(size_t)env * p.N + n] = S_total;
+}
+
+template <int COST>
+void launch_gru_cost_only(cpmppi_handle* h, const GruCostPtrs& a, uint32_t E, hipStream_t s) {
+  const bool f16 = h->cfg.math_mode == CPMPPI_MATH_FAST && h->gru16_image != nullptr;
+  const dim3 grid(E * a.nb);
+  if (f16) hipLaunchKernelGGL((gru_cost_only_kernel<COST, true>), grid, dim3(BLOCK), (size_t)G16_IMAGE_BYTES, s, h->prm, a,
+                              h->gru_norm, (const float*)h->gru16_image);
+  else hipLaunchKernelGGL((gru_cost_only_kernel<COST, false>), grid, dim3(BLOCK), (size_t)GRU_IMAGE_FLOATS * sizeof(float), s,
+                          h->prm, a, h->gru_norm, (const float*)h->gru_image);
+}
+
 // FAST: float32-equivalent split products on the f16 matrix cores (cpmppi_gru16.hpp); PRECISE: exact f32 MFMA chains
 template <int COST, int NOISE>
 void launch_gru(cpmppi_handle* h, const cpmppi_step_args* a, const StepPtrs& p, hipStream_t s) {
@@ -382,6 +490,26 @@ int cpmppi_gru_predict(cpmppi_handle* h, uint32_t B, uint32_t horizon, const flo
   hipLaunchKernelGGL(gru_predict_kernel, dim3((B + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK), dim3(BLOCK),
                      (size_t)GRU_IMAGE_FLOATS * sizeof(float), (hipStream_t)stream, h->gru_norm,
                      (const float*)h->gru_image, B, horizon, s0, Q, h0, traj_out, h_out);
+  return launched(h);
+}
+
+int cpmppi_rollout_cost_gru(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs, const float* target_position,
+                            const float* target_equilibrium, const float* h0, float* S_out, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_gru: no model set (cpmppi_set_gru)");
+  if (E == 0 || E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_gru: E out of range");
+  if (!s0 || !inputs || !target_position || !target_equilibrium || !S_out)
+    return fail(h, CPMPPI_ERR_BAD_ARG,
+                "cpmppi_rollout_cost_gru: s0, inputs, target_position, target_equilibrium, S_out are required");
+  if ((h->prm.cost_id != CPMPPI_COST_QBGM && h->prm.cost_id != CPMPPI_COST_DEFAULT) || h->prm.qb_mode != 0u)
+    return fail(h, CPMPPI_ERR_BAD_ARG,
+                "cpmppi_rollout_cost_gru: the GRU predictor supports quadratic_boundary_grad_minimal and default");
+  CPMPPI_ON_DEVICE(h);
+  // (one launch, nothing allocated, nothing awaited: the call can be captured; no pole mass and no L - the network is the plant model)
+  const GruCostPtrs a{s0, inputs, target_position, target_equilibrium, h0, S_out,
+                      (h->cfg.N + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK};
+  if (h->prm.cost_id == CPMPPI_COST_QBGM) launch_gru_cost_only<COST_QBGM>(h, a, E, (hipStream_t)stream);
+  else launch_gru_cost_only<COST_DEFAULT>(h, a, E, (hipStream_t)stream);
   return launched(h);
 }
 

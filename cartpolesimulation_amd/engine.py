@@ -513,10 +513,24 @@ class MPPIEngine:
         Lt = self._per_env(L, E) if L is not None else None
         return E, s0, inputs, tp, te, Lt
 
-    def rollout_cost(self, s0, inputs, target_position, target_equilibrium, L=None):
-        """inputs[E,N,H] -> S[E,N]: trajectory cost of given control sequences (no update)."""
+    def rollout_cost(self, s0, inputs, target_position, target_equilibrium, L=None, predictor="ODE_v0", h0=None):
+        """inputs[E,N,H] -> S[E,N]: trajectory cost of given control sequences (no update).  ``predictor="GRU"`` rolls them out
+        with the network of ``set_gru`` (cpmppi_rollout_cost_gru): ``h0`` [E,2,32] is each env's memory, shared by its rollouts
+        (None: zeros); the network knows no pole length, so ``L`` is refused."""
+        if predictor not in ("ODE_v0", "GRU"):
+            raise ValueError("predictor must be 'ODE_v0' or 'GRU'")
+        if predictor != "GRU" and h0 is not None:
+            raise ValueError("h0 is the memory of the GRU predictor: pass predictor='GRU'")
+        if predictor == "GRU":
+            if L is not None:
+                raise ValueError("predictor='GRU' takes no L: the network is the plant model")
         E, s0, inputs, tp, te, Lt = self._rollout_inputs(s0, inputs, target_position, target_equilibrium, L)
         S = self.empty(E, self.N)
+        if predictor == "GRU":
+            h0 = self.tensor(h0, (E, 2, 32)) if h0 is not None else None
+            self._check(self.lib.cpmppi_rollout_cost_gru(self._h, E, _ptr(s0), _ptr(inputs), _ptr(tp), _ptr(te), _ptr(h0),
+                                                         _ptr(S), self._stream()))
+            return S
         self._check(self.lib.cpmppi_rollout_cost(self._h, E, _ptr(s0), _ptr(inputs), _ptr(tp), _ptr(te), _ptr(Lt), _ptr(S),
                                                  self._stream()))
         return S

@@ -13,12 +13,24 @@ stdev updated in place.  ``step`` then only uploads the state; ``step_device`` t
 counter, touches the host not at all - the form a captured closed loop replays (harness.py).  The fused step costs its samples
 with the adjoint kernel's forward sweep (sin / cos on every substep) and hands the control of the step before to the cost
 (``previous_input``, read by quadratic_boundary_grad); the staged path above stays what it was.
+
+cem, cem-gmm and random-action also run on the neural predictor (``gru_model=`` and / or a ``GRU-6IN-32H1-32H2-5OUT*``
+``predictor_specification``, under optimizer_mppi's rules): they only need the costs of given plans, which
+cpmppi_rollout_cost_gru computes with the network in the rollout loop.  Each env keeps the network's memory ``h`` [E,2,32]:
+zero after a reset, handed to every cost launch of a control step, then advanced with the state seen and the control applied.
+The two hybrids need the cost's gradient, and the GRU has no adjoint kernel: they refuse it, as does ``fused=True``
+(cpmppi_cem_step integrates the ODE).
 """
 import math
 
 import torch
 
-from ._optimizer_base import _OptimizerBase
+from ._optimizer_base import _OptimizerBase, is_gru_specification
+
+GRU_NO_ADJOINT = ("the GRU predictor has no adjoint kernel, and {} needs the gradient of the cost: it runs on the ODE_v0 and ODE "
+                  "predictors; cem, cem-gmm and random-action run on the GRU")
+GRU_NOT_FUSED = ("fused=True integrates the ODE (cpmppi_cem_step): the GRU predictor runs in the staged step of cem, cem-gmm and "
+                 "random-action, fused=False")
 
 
 class optimizer_cem(_OptimizerBase):
@@ -31,11 +43,11 @@ class optimizer_cem(_OptimizerBase):
                  cem_stdev_min=0.01, cem_best_k=40, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
                  math_mode="fast", intermediate_steps=10, phys=None, device=0, variable_parameters=None, per_env_pole_mass=False,
-                 fused=False, **kwargs):
+                 fused=False, gru_model=None, **kwargs):
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
                          intermediate_steps, control_mode="clip", shift_mode="none", math_mode=math_mode,
-                         per_env_pole_mass=bool(per_env_pole_mass))
+                         per_env_pole_mass=bool(per_env_pole_mass), gru_model=gru_model)
         self.cem_outer_it, self.cem_best_k = int(cem_outer_it), int(cem_best_k)
         self.cem_initial_action_stdev, self.cem_stdev_min = float(cem_initial_action_stdev), float(cem_stdev_min)
         self.warmup, self.warmup_iterations = bool(warmup), int(warmup_iterations)
@@ -44,6 +56,19 @@ class optimizer_cem(_OptimizerBase):
         if self.fused and not self._fusable:
             raise ValueError(f"fused=True: the fused CEM control step (cpmppi_cem_step) is built for cem, cem-naive-grad and "
                              f"cem-grad-bharadhwaj, not for {self.optimizer_name}")
+        if self.fused and gru_model is not None:
+            raise ValueError(GRU_NOT_FUSED)
+
+    def _gru_selected(self, predictor_specification):
+        if self.fused and (is_gru_specification(predictor_specification) or self.gru_model is not None):
+            raise ValueError(GRU_NOT_FUSED)
+        return super()._gru_selected(predictor_specification)
+
+    def _cost(self, s_t, Q, tp, te, L):
+        """Costs [E,N] of the plans Q [E,N,H]: under the ODE, or - with the network - under the GRU from each env's memory."""
+        if self.h is not None:
+            return self.engine.rollout_cost(s_t, Q, tp, te, predictor="GRU", h0=self.h)
+        return self.engine.rollout_cost(s_t, Q, tp, te, L=L)
 
     def _refine(self, Q, s_t, tp, te, L):
         """Hook of the CEM + gradient hybrids: improve the samples before they are ranked."""
@@ -55,6 +80,7 @@ class optimizer_cem(_OptimizerBase):
         self.stdev = self.engine.zeros(E, H) + self.cem_initial_action_stdev
         self.step_counter = 0
         self._first = True
+        self._reset_memory()
         if self.fused:
             eng = self.engine
             # what the fused step writes per control step: the controls, the last costs, the mean before the shift
@@ -109,10 +135,11 @@ class optimizer_cem(_OptimizerBase):
         for _ in range(iters):
             Q = eng.cem_sample(self.dist_mue, self.stdev, self.seed, offset=self.step_counter)
             Q = self._refine(Q, s_t, tp, te, L)
-            S = eng.rollout_cost(s_t, Q, tp, te, L=L)
+            S = self._cost(s_t, Q, tp, te, L)
             self.dist_mue, self.stdev = eng.cem_update(S, Q, self.cem_best_k, self.cem_stdev_min)
             self.step_counter += 1
         u = self.dist_mue[:, 0].clone()
+        self._advance_memory(s_t, u)
         if self.optimizer_logging:
             self.logging_values = {"Q_logged": u.cpu().numpy(), "J_logged": S.cpu().numpy(),
                                    "u_logged": self.dist_mue.cpu().numpy()}
@@ -140,11 +167,12 @@ class optimizer_cem_gmm(optimizer_cem):
         ar = torch.arange(E, device=self.dist_mue.device)[:, None]
         for _ in range(self.cem_outer_it):
             Q = eng.cem_gmm_sample(self.centres, self.stdev, self.seed, offset=self.step_counter)
-            S = eng.rollout_cost(s_t, Q, tp, te, L=L)
+            S = self._cost(s_t, Q, tp, te, L)
             self.dist_mue, self.stdev, el = eng.cem_update(S, Q, self.cem_best_k, self.cem_stdev_min, return_elites=True)
             self.centres = Q[ar, el.long()].contiguous()                # [E, K, H], cheapest first (stable order)
             self.step_counter += 1
         u = self.centres[:, 0, 0].clone()                               # first input of the best sequence
+        self._advance_memory(s_t, u)
         if self.optimizer_logging:
             self.logging_values = {"Q_logged": u.cpu().numpy(), "J_logged": S.cpu().numpy(),
                                    "u_logged": self.centres[:, 0].cpu().numpy()}
@@ -158,6 +186,7 @@ class optimizer_cem_naive_grad(optimizer_cem):
     ``Q <- clip(Q - learning_rate * clip_by_norm(dJ/dQ, gradmax_clip))`` (cpmppi_rollout_cost_grad + cpmppi_sgd_step)
     before the elites are chosen.  [recalled semantics, class absent from the tree]"""
     optimizer_name = "cem-naive-grad"
+    _gru_refusal = GRU_NO_ADJOINT.format("cem-naive-grad")
 
     def __init__(self, *args, learning_rate=0.1, gradmax_clip=10, cem_outer_it=1, cem_stdev_min=0.1, **kwargs):
         super().__init__(*args, cem_outer_it=cem_outer_it, cem_stdev_min=cem_stdev_min, **kwargs)
@@ -177,6 +206,7 @@ class optimizer_cem_grad_bharadhwaj(optimizer_cem):
     are chosen; the Adam moments belong to the sample slots and persist over the outer iterations of a control step.
     [recalled semantics, class absent from the tree]"""
     optimizer_name = "cem-grad-bharadhwaj"
+    _gru_refusal = GRU_NO_ADJOINT.format("cem-grad-bharadhwaj")
 
     def __init__(self, *args, learning_rate=0.05, adam_beta_1=0.9, adam_beta_2=0.999, adam_epsilon=1.0e-8, num_rollouts=32,
                  cem_best_k=8, cem_outer_it=2, cem_initial_action_stdev=2, cem_stdev_min=1.0e-6, gradmax_clip=5, **kwargs):
@@ -223,9 +253,10 @@ class optimizer_random_action(optimizer_cem):
         lo, hi = self.action_low, self.action_high
         Q = (lo + (hi - lo) * 0.5 * (1.0 + torch.erf(z * (1.0 / math.sqrt(2.0))))).clamp_(lo, hi).contiguous()
         self.step_counter += 1
-        S = eng.rollout_cost(s_t, Q, tp, te, L=L)
+        S = self._cost(s_t, Q, tp, te, L)
         best = torch.argmin(S, dim=1)
         u = Q[torch.arange(E, device=S.device), best, 0].clone()
+        self._advance_memory(s_t, u)
         if self.optimizer_logging:
             self.logging_values = {"Q_logged": u.cpu().numpy(), "J_logged": S.cpu().numpy()}
         return self._result(u, single, as_tensor)

@@ -35,16 +35,19 @@ from ._optimizer_base import _OptimizerBase
 class _GradientBase(_OptimizerBase):
     optimizer_name = "gradient"
     _unknown_predictor = "the adjoint kernel differentiates the ODE_v0 and ODE predictors"
+    _gru_refusal = ("the GRU predictor has no adjoint kernel, and the gradient optimizers (gradient, rpgd) need the gradient of the "
+                    "cost: they run on the ODE_v0 and ODE predictors; cem, cem-gmm and random-action run on the GRU")
 
     def __init__(self, cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, sample_stdev, period,
                  num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
-                 variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused=False):
+                 variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused=False, gru_model=None):
         # the handle's sampler draws knots ~ N(0, SQRTRHOINV / sqrt(dt)): set it to the requested stdev
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
                          intermediate_steps, control_mode="clip", shift_mode="none", math_mode="fast",
                          horizon_reduce=horizon_reduce, SQRTRHOINV=float(sample_stdev) * math.sqrt(float(mpc_timestep)),
-                         period_interpolation_inducing_points=int(period), per_env_pole_mass=bool(per_env_pole_mass))
+                         period_interpolation_inducing_points=int(period), per_env_pole_mass=bool(per_env_pole_mass),
+                         gru_model=gru_model)
         self.count = 0               # control steps taken
         self.draws = 0               # sampler launches (the Philox offset)
         self.fused = bool(fused)     # one cpmppi_rpgd_step per control step instead of the staged launches
@@ -153,14 +156,14 @@ class optimizer_gradient(_GradientBase):
                  gradmax_clip=5, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
                  intermediate_steps=10, horizon_reduce="sum", phys=None, device=0, variable_parameters=None,
-                 per_env_pole_mass=False, fused=False, **kwargs):
+                 per_env_pole_mass=False, fused=False, gru_model=None, **kwargs):
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
         self.adam_epsilon, self.gradmax_clip, self.rtol = float(adam_epsilon), float(gradmax_clip), float(rtol)
         self.gradient_steps, self.warmup, self.warmup_iterations = int(gradient_steps), bool(warmup), int(warmup_iterations)
         self.initial_action_stdev = float(initial_action_stdev)
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, initial_action_stdev,
                          10, num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
-                         variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused)
+                         variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused, gru_model)
 
     def _fused_plan(self):
         return {"iterations": self.gradient_steps, "keep_k": self.num_rollouts, "resamp_per": 0, "shift": 1}
@@ -198,7 +201,7 @@ class optimizer_rpgd(_GradientBase):
                  warmup=False, warmup_iterations=250, optimizer_logging=False, calculate_optimal_trajectory=False,
                  num_envs=1, cost_function_specification=None, cost_weights=None, intermediate_steps=10,
                  horizon_reduce="sum", phys=None, device=0, variable_parameters=None, per_env_pole_mass=False, fused=False,
-                 **kwargs):
+                 gru_model=None, **kwargs):
         if SAMPLING_DISTRIBUTION not in ("normal", "uniform"):
             raise ValueError(f"SAMPLING_DISTRIBUTION={SAMPLING_DISTRIBUTION!r}; expected 'normal' or 'uniform'")
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
@@ -213,7 +216,7 @@ class optimizer_rpgd(_GradientBase):
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, stdev,
                          period_interpolation_inducing_points, num_envs, cost_function_specification, cost_weights,
                          intermediate_steps, phys, device, variable_parameters, optimizer_logging, horizon_reduce,
-                         per_env_pole_mass, fused)
+                         per_env_pole_mass, fused, gru_model)
 
     def _uniform_range(self):
         return (self.action_low, self.action_high) if self.sample_whole_control_space else \

@@ -14,7 +14,7 @@ in ONE launch (``step`` accepts ``s[6]`` or ``s[E,6]``), and perturbations come 
 import numpy as np
 import torch
 
-from ._optimizer_base import _OptimizerBase, _vec
+from ._optimizer_base import _OptimizerBase, _vec, is_gru_specification
 from .sampling import SAMPLING_TYPES, sample_delta_u_sfc64, sample_knots_sfc64
 
 # cost plugins with a control-change-rate term against the control applied last (Q_ccrc, CartPole/__init__.py:517-518)
@@ -51,38 +51,23 @@ class optimizer_mppi(_OptimizerBase):
                          period_interpolation_inducing_points=int(period_interpolation_inducing_points),
                          horizon_reduce=horizon_reduce, control_mode=control_mode, shift_mode=shift_mode,
                          correction_u=correction_u, math_mode=math_mode, predictor_type=predictor_type,
-                         per_env_pole_mass=bool(per_env_pole_mass))
+                         per_env_pole_mass=bool(per_env_pole_mass), gru_model=gru_model)
         self.calculate_optimal_trajectory = calculate_optimal_trajectory
         self.optimal_trajectory = None
         self.u_nom = None
         self.step_counter = 0
-        self.gru_model = gru_model           # dict of GRU-6IN-32H1-32H2-5OUT weights -> neural predictor in the loop
-        self.h = None                        # its memory per env [E,2,32] (controller_mppi_cartpole.py:566-567 update)
         self._hblock = self._hview = self._dblock = self._h2d_done = self._hq = self._q_done = None
         self._prepared = self._prepared_key = None     # pinned staging of the host seam
         self._fast = None                              # single-env host call: preallocated arrays + argument objects
 
     # ------------------------------------------------------------------
     def configure(self, dt=None, predictor_specification=None, num_envs=None, **kwargs):
-        neural = predictor_specification is not None and str(predictor_specification).startswith("GRU-6IN-32H1-32H2-5OUT")
         # (a GRU specification leaves the ODE integrator of the constructor alone: the network runs inside the fused kernel)
-        self._configure_problem(dt, None if neural else predictor_specification, num_envs)
-        if isinstance(self.gru_model, (str, bytes)) or hasattr(self.gru_model, "__fspath__"):
-            from .model_folder import load_gru_model          # an SI_Toolkit model folder (net-info, normalisation, weights)
-            self.gru_model = load_gru_model(self.gru_model)
-        if neural and self.gru_model is None:
-            raise ValueError("a GRU predictor_specification needs gru_model=dict(weights) or a model folder path "
-                             "(no GRU model files ship in-tree)")
-        if self.gru_model is not None and not (neural or predictor_specification is None):
-            raise ValueError(f"gru_model was given but predictor_specification={predictor_specification!r} selects the ODE "
-                             "predictor: the model would be ignored")
+        self._configure_problem(dt, None if is_gru_specification(predictor_specification) else predictor_specification, num_envs)
+        neural = self._gru_selected(predictor_specification)
         self.engine = self._new_engine()
         E, N, H = self.num_envs, self.num_rollouts, self.mpc_horizon
-        if self.gru_model is not None and (neural or predictor_specification is None):
-            self.engine.set_gru(self.gru_model)
-            self.h = self.engine.zeros(E, 2, 32)
-        else:
-            self.h = None
+        self._attach_gru(neural)
         self.u_nom = self.engine.zeros(E, H)
         self._Q = self.engine.zeros(E)
         self._Q_host = None
@@ -107,8 +92,7 @@ class optimizer_mppi(_OptimizerBase):
         """u_nom = midpoint of the control limits; restart the noise stream."""
         if self.u_nom is not None:
             self.u_nom.fill_(0.5 * (self.action_low + self.action_high))
-        if self.h is not None:
-            self.h.zero_()
+        self._reset_memory()
         self.step_counter = 0
         self._rng = np.random.Generator(np.random.SFC64(self.seed))
 
@@ -243,11 +227,7 @@ class optimizer_mppi(_OptimizerBase):
         else:
             eng.step(s_t, self.u_nom, tp, te, L=L, Q_out=self.Q, S_out=self.S, **kw)
         self.step_counter += 1
-        if self.h is not None:
-            # advance the network's memory with the state just seen and the control just chosen (update_internal_state)
-            _, h_new = eng.gru_predict(s_t, self.Q.reshape(E, 1), h0=self.h.transpose(0, 1).contiguous(),
-                                       return_hidden=True)
-            self.h = h_new.transpose(0, 1).contiguous()
+        self._advance_memory(s_t, self.Q)
         if self.optimizer_logging:
             self.logging_values = {"Q_logged": self.Q.cpu().numpy(), "J_logged": self.S.cpu().numpy(),
                                    "u_logged": self.u_nom.cpu().numpy()}

@@ -316,6 +316,21 @@ int cpmppi_gru_predict(cpmppi_handle* h, uint32_t B, uint32_t horizon, const flo
 int cpmppi_rollout_cost(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs, const float* target_position,
                         const float* target_equilibrium, const float* L, float* S_out, void* stream);
 
+/* The same with the neural predictor in the rollout loop (cpmppi_set_gru): S[E,N] = get_trajectory_cost(predict_core_GRU(s,
+ * Q), Q) of GIVEN input sequences inputs[E,N,H] - what a cpmppi_step with predictor = CPMPPI_PREDICTOR_GRU writes into S_out
+ * when inputs are its delta_u, the nominal sequence is zero, cc_weight is 0 and nothing is shifted, without the MPPI update
+ * (no weights, no weighted sums, no finalize).  The building block of cem, cem-gmm and random-action over the GRU.
+ * h0[E,2,32] (the layout of cpmppi_step_args.h0: one memory per env, shared by its rollouts) or NULL = zeros.  The handle's
+ * control_mode applies to the inputs (clip: to [action_low, action_high]); FAST math runs the split-f16 cell, PRECISE the
+ * exact-f32 chains, as the fused step chooses them.  Reads no pole mass and no L.  ONE launch on `stream`, no allocation and
+ * no host synchronisation: the call can be captured into a graph.
+ * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned (cpmppi_last_error: "cpmppi_rollout_cost_gru: ...") when no model is
+ * set, E == 0 or E > cfg.E, a pointer other than h0 is NULL, or the handle's cost is neither quadratic_boundary_grad_minimal
+ * nor default. */
+int cpmppi_rollout_cost_gru(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs,
+                            const float* target_position, const float* target_equilibrium, const float* h0, float* S_out,
+                            void* stream);
+
 /* Rollout + plugin cost + its gradient with respect to the inputs: S[E,N] (may be NULL) and
  * grad[E,N,H] = d get_trajectory_cost(predict_core(s, Q), Q, previous_input) / d Q — what TensorFlow's GradientTape
  * hands to the gradient-based optimizers of the absent Control_Toolkit (Control_Toolkit_ASF/config_optimizers.yml:49-86,

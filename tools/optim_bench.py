@@ -14,6 +14,14 @@ controller.step, the control read back every step) and one for the fused step on
 ("fused_device": optimizer.step_device, no read-back).  ``--staged-repeats R``: the staged record R times over (its max - min
 spread is the margin a comparison allows).  ``--datagen E,seconds``: E experiments of that length through the closed loop
 (harness.run_schedule), launched + staged against captured + fused (the first of --optimizers, shipped sizes).
+
+  python tools/optim_bench.py --gru [--envs 64] [--steps 30] [--cost-only-shapes 1x200x35,64x200x35,256x200x35,256x1024x50]
+The neural predictor (GRU-6IN-32H1-32H2-5OUT, synthetic weights drawn as bench.py's C5_gru line draws them) under the three
+optimizers that run on it - cem-tf, cem-gmm-tf, random-action-tf - through the controller seam, one record each; then, per
+E x N x H of --cost-only-shapes, the cost-only launch (cpmppi_rollout_cost_gru) against the fused GRU step handed the same
+[E,N,H] as delta_u with a zero nominal sequence (cpmppi_step: the same rollouts plus the MPPI update and its finalize launch) in
+ONE process, the two alternating: device time from events around batches of back-to-back launches, the median over the rounds and
+each column's min - max scatter.
 """
 import argparse
 import json
@@ -36,6 +44,8 @@ ap.add_argument("--predictor-specification", default="ODE_v0")
 ap.add_argument("--fused", action="store_true", help="rpgd and gradient-tf, staged against fused, in this one process")
 ap.add_argument("--optimizers", default="gradient-tf,rpgd", help="with --fused: comma-separated optimizer names")
 ap.add_argument("--staged-repeats", type=int, default=1, help="with --fused: how many times the staged record is measured")
+ap.add_argument("--gru", action="store_true", help="the GRU predictor under cem-tf, cem-gmm-tf and random-action-tf; cost-only launch vs fused step")
+ap.add_argument("--cost-only-shapes", default="1x200x35,64x200x35,256x200x35,256x1024x50", help="with --gru: ExNxH,... (the last default: bench.py's C5)")
 ap.add_argument("--datagen", default=None, help="with --fused: E,seconds of the closed-loop data generator, e.g. 256,10")
 args = ap.parse_args()
 E = args.envs
@@ -101,8 +111,68 @@ def fused_bench():
             opt.engine.close()
 
 
+def synthetic_gru():
+    """bench.py's C5_gru weights: SFC64(5), U(-1, 1) / sqrt(32), no normalisation vectors."""
+    g = np.random.Generator(np.random.SFC64(5))
+    u = lambda *shape: g.uniform(-1, 1, shape).astype(np.float32) / np.sqrt(32.0, dtype=np.float32)  # noqa: E731
+    return dict(w_ih0=u(96, 6), w_hh0=u(96, 32), b_ih0=u(96), b_hh0=u(96), w_ih1=u(96, 32), w_hh1=u(96, 32), b_ih1=u(96),
+                b_hh1=u(96), w_out=u(5, 32), b_out=u(5))
+
+
+def gru_bench():
+    from cartpolesimulation_amd.configs import MPPIConfig
+    from cartpolesimulation_amd.engine import MPPIEngine
+    model = synthetic_gru()
+    for name in ("cem-tf", "cem-gmm-tf", "random-action-tf"):
+        ctrl = controller_mpc("CartPole", {"target_position": 0.0, "target_equilibrium": 1.0}, control_limits=([-1.0], [1.0]),
+                              num_envs=E, config=dict(seed=1, gru_model=model))
+        ctrl.configure(name)
+        opt = ctrl.optimizer
+        s = opt.engine.tensor(s_host)
+        dt = timed(lambda: ctrl.step(s, 0.0, {}), args.steps)
+        print(json.dumps({"bench": "controller_step", "optimizer": name, "predictor": "GRU", "envs": E, "num_rollouts": opt.num_rollouts,
+                          "mpc_horizon": opt.mpc_horizon, "iterations": opt.cem_outer_it,
+                          "ms_per_controller_step": round(dt * 1e3, 4)}), flush=True)
+        opt.engine.close()
+    rounds, batch = 12, 10
+    for shape in args.cost_only_shapes.split(","):
+        e, n, h = (int(x) for x in shape.split("x"))
+        g = np.random.Generator(np.random.SFC64(11))
+        s0 = np.stack([O.create_cartpole_state(g.uniform(-0.3, 0.3), g.uniform(-0.5, 0.5), g.uniform(-0.05, 0.05), 0.0) for _ in range(e)])
+        for math_mode in ("fast", "precise"):
+            eng = MPPIEngine(e, MPPIConfig(num_rollouts=n, mpc_horizon=h, math_mode=math_mode, cc_weight=0.0, shift_mode="none"))
+            eng.set_gru(model)
+            s, tp, te, h0 = eng.tensor(s0), eng.zeros(e), eng.zeros(e) + 1.0, eng.zeros(e, 2, 32)
+            plans = torch.clamp(0.5 * torch.randn(e, n, h, device=s.device, generator=torch.Generator(s.device).manual_seed(1)), -1.0, 1.0)
+            S, u_out = eng.empty(e, n), eng.empty(e, h)
+            fused = eng.prepare_step(s, eng.zeros(e, h), tp, te, S_out=S, predictor="GRU", h0=h0, delta_u=plans, u_nom_out=u_out)
+            launches = {"cost_only": lambda: eng.rollout_cost(s, plans, tp, te, predictor="GRU", h0=h0), "fused_step": fused.run}
+            ms = {k: [] for k in launches}
+            for r in range(rounds + 2):                           # (the first two rounds warm up)
+                for k, fn in launches.items():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    a.record()
+                    for _ in range(batch):
+                        fn()
+                    b.record()
+                    b.synchronize()
+                    if r >= 2:
+                        ms[k].append(a.elapsed_time(b) / batch)
+            rec = {"bench": "gru_cost_only", "envs": e, "num_rollouts": n, "mpc_horizon": h, "math_mode": math_mode, "rounds": rounds,
+                   "launches_per_round": batch}
+            for k, v in ms.items():
+                rec[k + "_ms"] = round(float(np.median(v)), 5)
+                rec[k + "_min_max_ms"] = [round(float(min(v)), 5), round(float(max(v)), 5)]
+            rec["cost_only_over_fused"] = round(rec["cost_only_ms"] / rec["fused_step_ms"], 4)
+            print(json.dumps(rec), flush=True)
+            eng.close()
+
+
 if args.fused:
     fused_bench()
+    sys.exit(0)
+if args.gru:
+    gru_bench()
     sys.exit(0)
 for name in ("mppi", "cem-tf", "cem-gmm-tf", "cem-naive-grad-tf", "cem-grad-bharadhwaj-tf", "gradient-tf", "rpgd", "random-action-tf"):
     ctrl = controller_mpc("CartPole", {"target_position": 0.0, "target_equilibrium": 1.0, "L": 0.395},
