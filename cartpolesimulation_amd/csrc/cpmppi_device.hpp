@@ -1266,18 +1266,28 @@ __device__ __forceinline__ void philox_normal_pair(uint64_t seed, uint64_t offse
 }
 
 // All four words of a Philox block: two Box-Muller pairs = the four consecutive knots 4q .. 4q+3 of (env, rollout).
-__device__ __forceinline__ void philox_normal_quad(uint64_t seed, uint64_t offset, uint32_t env, uint32_t rollout,
-                                                   uint32_t quad, float z[4]) {
+// `second_pair` (wave-uniform) false - a consumer that walks the knots in order and knows where the sequence ends (the rollout
+// kernel): knots 4q+2 and 4q+3 lie beyond it, their conversions, log, sqrt, sin and cos are skipped and z[2], z[3] come back as zero.
+__device__ __forceinline__ void philox_normal_quad_upto(uint64_t seed, uint64_t offset, uint32_t env, uint32_t rollout,
+                                                        uint32_t quad, bool second_pair, float z[4]) {
   uint32_t c0 = rollout, c1 = env, c2 = quad, c3 = (uint32_t)offset;
   philox4x32_10(c0, c1, c2, c3, (uint32_t)seed ^ 0x51ed270bu, (uint32_t)(seed >> 32) ^ (uint32_t)(offset >> 32));
   const float ua = (float)((c0 >> 8) + 1u) * 5.9604644775390625e-8f, ub = (float)(c1 >> 8) * 5.9604644775390625e-8f;
-  const float uc = (float)((c2 >> 8) + 1u) * 5.9604644775390625e-8f, ud = (float)(c3 >> 8) * 5.9604644775390625e-8f;
   const float ra = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(ua));
-  const float rc = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(uc));
   z[0] = ra * __builtin_amdgcn_cosf(ub);
   z[1] = ra * __builtin_amdgcn_sinf(ub);
-  z[2] = rc * __builtin_amdgcn_cosf(ud);
-  z[3] = rc * __builtin_amdgcn_sinf(ud);
+  z[2] = 0.0f; z[3] = 0.0f;
+  if (second_pair) {
+    const float uc = (float)((c2 >> 8) + 1u) * 5.9604644775390625e-8f, ud = (float)(c3 >> 8) * 5.9604644775390625e-8f;
+    const float rc = __builtin_amdgcn_sqrtf(-1.3862943611198906f * __builtin_amdgcn_logf(uc));
+    z[2] = rc * __builtin_amdgcn_cosf(ud);
+    z[3] = rc * __builtin_amdgcn_sinf(ud);
+  }
+}
+// (every other consumer - the sampler kernels, philox_knot, the reduction's regeneration - takes the whole block: one body)
+__device__ __forceinline__ void philox_normal_quad(uint64_t seed, uint64_t offset, uint32_t env, uint32_t rollout,
+                                                   uint32_t quad, float z[4]) {
+  philox_normal_quad_upto(seed, offset, env, rollout, quad, true, z);
 }
 
 // Knot j of (env, rollout) scaled by sigma (random access; sequential consumers keep the other three of the block).

@@ -121,6 +121,24 @@ __device__ __forceinline__ StepPtrs late_step_ptrs() {
   return u.s;
 }
 
+// ... and the Params argument likewise: the fields a late use names are loaded there and then instead of being kept (or spilled
+// and reloaded) through the horizon loop.  Params is the FIRST argument of the (const Params, const StepPtrs) signature, i.e. at
+// offset 0 of the kernarg segment (late_step_ptrs above relies on the same layout for the second), and what comes back is the
+// launch's argument as passed: a kernel that computes with a modified copy (predictor_ODE's `pi`, the pole mass per env) must not
+// take that copy's fields from here.  (Beside late_step_ptrs rather than in cpmppi_device.hpp: both are statements about this
+// header's kernel signature.)
+__device__ __forceinline__ Params late_params() {
+  typedef const __attribute__((address_space(4))) char* kptr;
+  kptr k = (kptr)__builtin_amdgcn_kernarg_segment_ptr();
+  asm volatile("" : "+s"(k));
+  static_assert(sizeof(Params) % 4 == 0, "kernarg layout");
+  const __attribute__((address_space(4))) uint32_t* w = (const __attribute__((address_space(4))) uint32_t*)k;
+  union { Params s; uint32_t w[sizeof(Params) / 4]; } u;
+#pragma unroll
+  for (size_t i = 0; i < sizeof(Params) / 4; ++i) u.w[i] = w[i];
+  return u.s;
+}
+
 // Nominal control for stage k after the configured shift (a18).
 __device__ __forceinline__ float shifted_nominal(const Params& p, const float* __restrict__ un, uint32_t k) {
   if (p.shift_mode == CPMPPI_SHIFT_NONE) return un[k];

@@ -169,13 +169,32 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
   bool at_edge = false;
   float run_hi_v = p.run_hi;
   if constexpr (FAST && VARIANT == 1) asm volatile("v_mov_b32 %0, %1" : "=v"(run_hi_v) : "s"(p.run_hi));
-  auto control_step = [&](uint32_t k, F du, auto eventful) __attribute__((always_inline)) {
+  // The LAST stage of the horizon (k = H - 1) under a cost without a terminal term: its stage cost and correction count, the state
+  // its integration would produce is read by nothing (S_total below: cost, corr, u_nom_sq).  The horizon drivers run their loops
+  // to H - 1 and call the stage once more with `stage_only` set - nominal fetch, clamp, stage cost, correction, no integration -
+  // from OUTSIDE the loops, whose bodies stay what they were.  `default` and the legacy cost read the end state
+  // (terminal_indicator): their kernels keep the loop to H and have no such call.
+  // (not quadratic_boundary_grad on predictor_ODE, two rollouts per lane, throughput build: with the second copy of that cost's
+  // stage these kernels go from 120-125 to 132-134 VGPRs - three waves per SIMD instead of four - and a launch that fills the
+  // device loses what the step saves or more: 8192 envs x 1024 x 50, alternating A/B, Philox 1.000, tiled buffer 1.012)
+  // (Left as they were altogether, the Philox block's skipped pair included: with the skip alone the Philox kernel measured 1.003,
+  // 31 of 32 rounds slower.)
+  constexpr bool AS_BEFORE = COST == COST_QBG && INTEG == PREDICTOR_ODE && R == 2 && VARIANT_ == 1;
+  constexpr bool LAST_STAGE_ONLY = (COST == COST_QBGM || COST == COST_QBG) && !AS_BEFORE;
+  const uint32_t H_full = LAST_STAGE_ONLY ? H - 1u : H;     // control steps that integrate (H >= 1: cpmppi_create)
+  auto control_step = [&](uint32_t k, F du, auto eventful, auto stage_only) __attribute__((always_inline)) {
+    // (`pc`: the launch's parameters as the stage reads them.  The stage-only call re-reads them from the kernarg segment
+    // (late_params): taken from `p`, its uses stretch the fields' scalar registers past the loops, and the Philox kernel of
+    // quadratic_boundary_grad, two rollouts per lane, throughput build, came out with a 20-byte scratch slot)
+    Params pl_;
+    if constexpr (decltype(stage_only)::value) pl_ = late_params();
+    const Params& pc = decltype(stage_only)::value ? pl_ : p;
     if (secp) { asm volatile("" : "+v"(du)); CPMPPI_SEC(secp, 5, st); CPMPPI_SEC(secp, 0, st); }
     float uk, upk = 0.0f;
     if constexpr (NOMINAL_IN_LANES) {
       if (__builtin_expect((k & 63u) == 0u && k != 0u, 0)) {
         const uint32_t kl = k + lane;
-        un_lane = (kl < H) ? shifted_nominal(p, un, kl) : 0.0f;
+        un_lane = (kl < H) ? shifted_nominal(pc, un, kl) : 0.0f;
       }
       uk = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(un_lane), (int)(k & 63u)));
       if constexpr (COST == COST_LEGACY) {
@@ -189,11 +208,11 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
     } else if constexpr (PREFETCH_NOMINAL) {
       uk = uk_next; upk = up_next;
       if (k + 1 < H) {
-        uk_next = shifted_nominal(p, un, k + 1);
+        uk_next = shifted_nominal(pc, un, k + 1);
         if constexpr (COST == COST_LEGACY) up_next = up[k + 1];
       }
     } else {
-      uk = shifted_nominal(p, un, k);
+      uk = shifted_nominal(pc, un, k);
       if constexpr (COST == COST_LEGACY) upk = up[k];
     }
     F ur = splat<F>(uk) + du;
@@ -201,16 +220,16 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
       // (v_med3_f32 takes ONE scalar operand: as plain kernel arguments the upper limit is copied into a vector register on
       // every control step; `run_hi_v` is that copy made once, behind an opaque asm so that it is not re-materialised)
 #pragma unroll
-      for (int i = 0; i < R; ++i) put(ur, i, __builtin_amdgcn_fmed3f(get(ur, i), p.run_lo, run_hi_v));
+      for (int i = 0; i < R; ++i) put(ur, i, __builtin_amdgcn_fmed3f(get(ur, i), pc.run_lo, run_hi_v));
     } else {
-      ur = clamp_(ur, p.run_lo, p.run_hi);
+      ur = clamp_(ur, pc.run_lo, pc.run_hi);
     }
     if constexpr (QBGM_ACC) {
       float b_nom = 0.0f;
       // (packed builds: the flag is re-formed from the kernel argument on every stage, behind an opaque copy - as a loop-invariant
       // bool the compiler keeps ONE lane mask for it and derives the negated one through a v_cndmask + v_cmp pair on every control
       // step; the latency build keeps the hoisted flag: there the three scalar instructions cost what vector ones do)
-      uint32_t correction_u_now = p.correction_u;
+      uint32_t correction_u_now = pc.correction_u;
       if constexpr (VARIANT != 0) asm volatile("" : "+s"(correction_u_now));
       const bool nom_mode = correction_u_now != CPMPPI_CORRECTION_U_RUN;
       if (__builtin_expect(nom_mode, 0)) {             // (wave-uniform; the correction takes u_nom: non-default glue)
@@ -220,19 +239,20 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
       }
       stage_qbgm_acc<F>(qf, st.x, cosang, st.w, ur, du, nom_mode, b_nom, x_t, near, cost, corr);
     } else if constexpr (COST == COST_QBGM) {
-      cost += stage_qbgm<F, FAST>(p, st.x, cosang, st.w, ur, x_t, te, near);     // (PRECISE only: FAST is QBGM_ACC)
-      corr += mppi_correction<F>(p, p.correction_u == CPMPPI_CORRECTION_U_RUN ? ur : splat<F>(uk), du);
+      cost += stage_qbgm<F, FAST>(pc, st.x, cosang, st.w, ur, x_t, te, near);     // (PRECISE only: FAST is QBGM_ACC)
+      corr += mppi_correction<F>(pc, pc.correction_u == CPMPPI_CORRECTION_U_RUN ? ur : splat<F>(uk), du);
     } else if constexpr (COST == COST_DEFAULT) {
-      cost += stage_default<F, FAST, (INTEG == PREDICTOR_ODE_V0)>(p, st.x, cosang, ur, x_t, te, u_before, qb_ccrc);
-      corr += mppi_correction<F>(p, p.correction_u == CPMPPI_CORRECTION_U_RUN ? ur : splat<F>(uk), du);
+      cost += stage_default<F, FAST, (INTEG == PREDICTOR_ODE_V0)>(pc, st.x, cosang, ur, x_t, te, u_before, qb_ccrc);
+      corr += mppi_correction<F>(pc, pc.correction_u == CPMPPI_CORRECTION_U_RUN ? ur : splat<F>(uk), du);
       if (qb_ccrc) u_before = ur;               // (quadratic_boundary's control-change-rate term; wave-uniform)
     } else if constexpr (COST == COST_QBG) {
-      cost += stage_qbg<F, FAST>(p, st.x, cosang, st.w, ur, u_before, x_t, te);
-      corr += mppi_correction<F>(p, p.correction_u == CPMPPI_CORRECTION_U_RUN ? ur : splat<F>(uk), du);
+      cost += stage_qbg<F, FAST>(pc, st.x, cosang, st.w, ur, u_before, x_t, te);
+      corr += mppi_correction<F>(pc, pc.correction_u == CPMPPI_CORRECTION_U_RUN ? ur : splat<F>(uk), du);
       u_before = ur;
     } else {
-      cost += stage_legacy<F, FAST>(p, st.x, cosang, st.w, st.v, uk, du, upk, x_t);
+      cost += stage_legacy<F, FAST>(pc, st.x, cosang, st.w, st.v, uk, du, upk, x_t);
     }
+    if constexpr (decltype(stage_only)::value) return;
     const F u = ur * splat<F>(p.u_max);     // Q2u, cartpole_equations.py:119-127
     if constexpr (INTEG == PREDICTOR_ODE) {
       if constexpr (FAST) {
@@ -264,13 +284,19 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
   };
 
   // ---- rollout over the horizon ----------------------------------------------------------------------------------
-  // phased build: `step(k, eventful)` performs control step k (fetching its perturbation itself); quiet and eventful steps
-  // in separate loops (see PHASED above)
-  auto run_phased = [&](auto&& step) __attribute__((always_inline)) {
+  // phased build: `step(k, eventful, stage_only)` performs control step k (fetching its perturbation itself); quiet and eventful steps
+  // in separate loops (see PHASED above); behind them the stage-only call for k = H - 1 (LAST_STAGE_ONLY): `last_stage()`, or -
+  // given nullptr - `step` itself with the tag set.  (nullptr rather than a second lambda that calls a NAMED step: passed that way
+  // the tiled mid-size kernels came out with 159 / 182 VGPRs instead of 128 / 161 - the step inlined through two closures.)
+  auto run_phased = [&](auto&& step, auto&& last_stage) __attribute__((always_inline)) {
     uint32_t k = 0;
-    while (k < H) {
-      for (; k < H && !at_edge; ++k) step(k, std::false_type{});
-      for (; k < H && at_edge; ++k) step(k, std::true_type{});
+    while (k < H_full) {
+      for (; k < H_full && !at_edge; ++k) step(k, std::false_type{}, std::false_type{});
+      for (; k < H_full && at_edge; ++k) step(k, std::true_type{}, std::false_type{});
+    }
+    if constexpr (LAST_STAGE_ONLY) {
+      if constexpr (std::is_same<std::decay_t<decltype(last_stage)>, std::nullptr_t>::value) step(H_full, std::false_type{}, std::true_type{});
+      else last_stage();
     }
   };
   if constexpr (NOISE == NOISE_DELTA_U) {
@@ -318,6 +344,17 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
     } else if (NBUF == 2) {
       dma(0u, 0u);
     }
+    // LAST_STAGE_ONLY: the last stage's perturbation is its word of the last tile, read where it lies in LDS.  Nothing streams in
+    // behind that tile; the walkers below have requested it (the phased one when its predecessor started), or filled it by hand.
+    auto last_stage_from_tile = [&]() __attribute__((always_inline)) {
+      const uint32_t t = ntiles - 1u, o = H_full - (streamed ? tile_start(t) : 0u);
+      if (streamed) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      const float* __restrict__ last_tile = wave_tile + (NBUF == 2 ? (t & 1u) : 0u) * TILE_FLOATS + lane * 4u + (o & 3u);
+      F du;
+#pragma unroll
+      for (int i = 0; i < R; ++i) put(du, i, last_tile[((o >> 2) * R + (uint32_t)i) * 256u]);
+      control_step(H_full, du, std::false_type{}, std::true_type{});
+    };
     if constexpr (PHASED) {
       // the same tiles, walked by control step instead of by nested tile / piece / word loops (the phased driver owns the
       // loop over k): tile t starts at step t * DTK; the quad is re-read every four columns of the tile; a last tile that
@@ -333,7 +370,7 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
 #pragma unroll
         for (int i = 0; i < R; ++i) { quad[i].x = quad[i].y; quad[i].y = quad[i].z; quad[i].z = quad[i].w; }
       };
-      run_phased([&](uint32_t k, auto eventful) __attribute__((always_inline)) {
+      run_phased([&](uint32_t k, auto eventful, auto) __attribute__((always_inline)) {
         if (k == t_next * DTK) {
           const uint32_t t = t_next;
           ks = streamed ? tile_start(t) : 0u;
@@ -354,8 +391,8 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
 #pragma unroll
         for (int i = 0; i < R; ++i) put(du, i, quad[i].x);
         shift_quad();
-        control_step(k, du, eventful);
-      });
+        control_step(k, du, eventful, std::false_type{});
+      }, last_stage_from_tile);
     } else
     for (uint32_t t = 0; t < ntiles; ++t) {
       const uint32_t ks = streamed ? tile_start(t) : 0u, k_first = t * DTK;      // (k_first > ks only in an overlapping last tile)
@@ -377,10 +414,11 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
             put(du, i, quad[i].x);
             quad[i].x = quad[i].y; quad[i].y = quad[i].z; quad[i].z = quad[i].w;
           }
-          if (k >= k_first && k < H) control_step(k, du, std::false_type{});
+          if (k >= k_first && k < H_full) control_step(k, du, std::false_type{}, std::false_type{});
         }
       }
     }
+    if constexpr (LAST_STAGE_ONLY && !PHASED) last_stage_from_tile();
   } else if constexpr (NOISE == NOISE_TILED) {
     // delta_u in the library's TILED layout [E][G = ceil(N/64)][Hq = ceil(H/4)][64 rows][4 steps] (cpmppi_sample_tiled /
     // cpmppi_tile_delta_u): lane l of row-group g reads ONE float4 per four control steps, and a wave-instruction reads
@@ -398,7 +436,7 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
 #pragma unroll
     for (int i = 0; i < R; ++i) { cur[i] = src[i][0]; nxt[i] = cur[i]; }
     if constexpr (PHASED) {
-      run_phased([&](uint32_t k, auto eventful) __attribute__((always_inline)) {
+      run_phased([&](uint32_t k, auto eventful, auto stage_only) __attribute__((always_inline)) {
         if ((k & 3u) == 0u) {                                 // a new quad: the one requested four steps ago; request the next
           const uint32_t q = k >> 2;
           if (q != 0u) {
@@ -416,15 +454,15 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
           put(du, i, cur[i].x);
           cur[i].x = cur[i].y; cur[i].y = cur[i].z; cur[i].z = cur[i].w;
         }
-        control_step(k, du, eventful);
-      });
+        control_step(k, du, eventful, stage_only);
+      }, nullptr);
     } else
     for (uint32_t q = 0; q < Hq; ++q) {
       if (q + 1 < Hq) {
 #pragma unroll
         for (int i = 0; i < R; ++i) nxt[i] = src[i][(size_t)(q + 1) * 64u];
       }
-      const uint32_t kend = (H - 4u * q < 4u) ? (H - 4u * q) : 4u;
+      const uint32_t kend = (H_full - 4u * q < 4u) ? (H_full - 4u * q) : 4u;
       for (uint32_t j = 0; j < kend; ++j) {
         F du;
 #pragma unroll
@@ -434,10 +472,18 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
           // compiler turns into a tree of scalar branches per control step
           cur[i].x = cur[i].y; cur[i].y = cur[i].z; cur[i].z = cur[i].w;
         }
-        control_step(4u * q + j, du, std::false_type{});
+        control_step(4u * q + j, du, std::false_type{}, std::false_type{});
       }
 #pragma unroll
       for (int i = 0; i < R; ++i) cur[i] = nxt[i];
+    }
+    if constexpr (LAST_STAGE_ONLY && !PHASED) {
+      // the last stage's perturbation: word (H - 1) % 4 of the last quad, which `cur` holds unshifted after the loop
+      const uint32_t w = H_full & 3u;
+      F du;
+#pragma unroll
+      for (int i = 0; i < R; ++i) put(du, i, w == 0u ? cur[i].x : (w == 1u ? cur[i].y : (w == 2u ? cur[i].z : cur[i].w)));
+      control_step(H_full, du, std::false_type{}, std::true_type{});
     }
   } else {
     // Philox: one block yields FOUR consecutive knots (4q .. 4q+3); the other three are kept until needed.  Every knot is
@@ -453,7 +499,8 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
         const uint32_t s = j & 3u;
         if (s == 0u) {
           float zq[4];
-          philox_normal_quad(a.seed, step_offset, a.env_offset + env, nn, j >> 2, zq);
+          // (a block's second Box-Muller pair is knots j + 2, j + 3: skipped when neither exists - wave-uniform)
+          philox_normal_quad_upto(a.seed, step_offset, a.env_offset + env, nn, j >> 2, AS_BEFORE || j + 2u < p.P, zq);
           z = p.sigma * zq[0];
           z_next[i][0] = p.sigma * zq[1]; z_next[i][1] = p.sigma * zq[2]; z_next[i][2] = p.sigma * zq[3];
         } else {
@@ -479,14 +526,15 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
       else slope[i] = knot_slope(z_lo[i], z_hi[i], p.period);
     }
     uint32_t ii = 0, j = 0;
-    auto horizon_step = [&](uint32_t k, auto eventful) __attribute__((always_inline)) {
+    auto horizon_step = [&](uint32_t k, auto eventful, auto stage_only) __attribute__((always_inline)) {
       F du;
 #pragma unroll
       for (int i = 0; i < R; ++i) {
         if constexpr (F32_INTERP) put(du, i, interp_from_slope32(slope32[i], z_lo[i], ii));
         else put(du, i, interp_from_slope(slope[i], z_lo[i], ii));
       }
-      control_step(k, du, eventful);
+      control_step(k, du, eventful, stage_only);
+      if constexpr (decltype(stage_only)::value) return;      // (no knot is due behind the last stage: P = (H - 1) / period + 2)
       // (the branch weight is a LAYOUT hint: the nine of ten control steps that need no new knot fall through - 1024 envs
       // -2.9 %, 256 envs -2.4 %, C3 -1.5 %; FAST only: in one PRECISE kernel the other layout left a scratch slot)
       if (FAST ? __builtin_expect(++ii == p.period, 0) : (++ii == p.period)) {
@@ -506,7 +554,7 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
       }
     };
     if constexpr (PHASED) {
-      run_phased(horizon_step);
+      run_phased(horizon_step, nullptr);
     } else if constexpr (FAST && VARIANT == 1 && !(COST == COST_DEFAULT && NOISE == NOISE_PHILOX && R == 2)) {
       // throughput build: the horizon as NESTED loops - knot segments outside, the `period` control steps between two knots
       // inside, where the segment's knot and slope are loop invariants.  The flat loop above refreshes the knots behind a
@@ -516,8 +564,10 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
       // rollouts per lane: there this form costs two more scalar registers than the file has - a 20-byte scratch slot, which
       // tests/test_abi_and_host.py refuses.)
       uint32_t k = 0;
-      for (uint32_t seg = 0; k < H; ++seg) {
-        const uint32_t kend = (H - k < p.period) ? H : k + p.period;
+      [[maybe_unused]] uint32_t i_last = 0;          // LAST_STAGE_ONLY: the last stage's place in its knot segment
+      for (uint32_t seg = 0; k < H_full; ++seg) {
+        const uint32_t kend = (H_full - k < p.period) ? H_full : k + p.period;
+        if constexpr (LAST_STAGE_ONLY) i_last = kend - k;
         for (uint32_t i2 = 0; k < kend; ++k, ++i2) {
           F du;
 #pragma unroll
@@ -525,9 +575,11 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
             if constexpr (F32_INTERP) put(du, i, interp_from_slope32(slope32[i], z_lo[i], i2));
             else put(du, i, interp_from_slope(slope[i], z_lo[i], i2));
           }
-          control_step(k, du, std::false_type{});
+          control_step(k, du, std::false_type{}, std::false_type{});
         }
-        if (k < H) {                                 // the next segment's knots (seg + 1, seg + 2)
+        // (LAST_STAGE_ONLY: a whole segment lies behind and the last stage opens the next one - H = 11, period 10)
+        if (LAST_STAGE_ONLY ? i_last == p.period : k < H) {    // the next segment's knots (seg + 1, seg + 2)
+          if constexpr (LAST_STAGE_ONLY) i_last = 0;
           const uint32_t jn = seg + 1u;
 #pragma unroll
           for (int i = 0; i < R; ++i) {
@@ -543,8 +595,18 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
           }
         }
       }
+      if constexpr (LAST_STAGE_ONLY) {
+        F du;
+#pragma unroll
+        for (int i = 0; i < R; ++i) {
+          if constexpr (F32_INTERP) put(du, i, interp_from_slope32(slope32[i], z_lo[i], i_last));
+          else put(du, i, interp_from_slope(slope[i], z_lo[i], i_last));
+        }
+        control_step(H_full, du, std::false_type{}, std::true_type{});
+      }
     } else {
-      for (uint32_t k = 0; k < H; ++k) horizon_step(k, std::false_type{});
+      for (uint32_t k = 0; k < H_full; ++k) horizon_step(k, std::false_type{}, std::false_type{});
+      if constexpr (LAST_STAGE_ONLY) horizon_step(H_full, std::false_type{}, std::true_type{});
     }
   }
 
