@@ -1,7 +1,7 @@
 // The per-lane pieces of the fused CEM control step (cem_step_kernel, cpmppi_optim.hip; contract: cpmppi_cem_step in
-// include/cpmppi.h): one lane owns one sample of one env - it draws its row, refines it (the two hybrids), and costs it with the
-// sweep of cpmppi_rpgd.hpp.  The row lives in a workspace column of the env (lane-contiguous, the block's width as the stride), as
-// the check-points and the gradient of the sweep do.
+// include/cpmppi.h): one lane owns one sample of one env - it draws its row, refines it (the two hybrids), and costs it with
+// adjoint_sweep (cpmppi_grad.hpp).  The row lives in a workspace column of the env (lane-contiguous, the block's width as the
+// stride), as the check-points and the gradient of the sweep do.
 #pragma once
 #include "cpmppi_rpgd.hpp"
 

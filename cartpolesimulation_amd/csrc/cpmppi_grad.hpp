@@ -7,6 +7,8 @@
 //   * forward = the FAST substep with the reference's per-substep wrap + sin/cos (substep_fast<float>; formulas of
 //     cartpole_equations.py:71-99,130-131,341-347, cartpole_numba.py:55-78), states check-pointed per control step;
 //   * backward = per control step, recompute the S substeps (sub-states parked in LDS), then sweep them in reverse.
+// adjoint_sweep (at the end) is that pair for one lane = one plan; rollout_grad_kernel, rpgd_step_kernel and cem_step_kernel
+// (cpmppi_optim.hip) call it and differ only in where a lane's plan, check-points, sub-states and gradient lie (SweepLane).
 // Non-smooth pieces are differentiated the way automatic differentiation of the reference's code does it: the branch
 // taken (edge bounce), derivative 1 through fmod / the wrap comparisons, 0 through indicator functions and through a
 // clipped control.
@@ -153,6 +155,116 @@ __device__ __forceinline__ StageGrad stage_qbg_grad(const Params& p, float x, fl
   g.u += 2.0f * w[6] * dc;
   g.u_before = -2.0f * w[6] * dc;
   return g;
+}
+
+// One lane's plan and where its sweep reads and writes.  Strides in floats between consecutive k (or substep, or state
+// component) of the SAME lane: the lane is already added to the base pointers.
+struct SweepLane {
+  const float* s0;        // [6] the env's state
+  const float* Q;         // [H] the lane's plan (QSTRIDED: a column like the gradient, [H][grad_stride] + lane)
+  float x_t, te, ub0;     // targets, the control applied before this step
+  float cos0, sin0;       // the plugins take cos(angle) of the given state at stage 0
+  float scale;            // horizon_reduce: 1 or 1 / (H + 1)
+  bool clip;
+  size_t ckpt_stride;     // all lanes of the launch (rollout_grad_kernel) or the block's width (the fused steps)
+  uint32_t sub_stride;    // BLOCK, or the block's width
+  uint32_t grad_stride;   // 1 (a row of grad_out), or the block's width
+  float* ckpt;            // [H][6][ckpt_stride] + lane
+  float* grad;            // [H][grad_stride] + lane
+  float* sub;             // LDS [S][6][sub_stride] + lane
+};
+
+// The per-env fields of a lane, from a kernel's pointer block `a` (s0, x_t, te, prev_in as GradPtrs, RpgdPtrs, CemPtrs name them).
+template <class Ptrs>
+__device__ __forceinline__ void sweep_lane_env(SweepLane& w, const Params& p, const Ptrs& a, uint32_t env) {
+  w.s0 = a.s0 + (size_t)env * 6;
+  w.x_t = a.x_t[env]; w.te = a.te[env]; w.ub0 = a.prev_in ? a.prev_in[env] : 0.0f;
+  w.cos0 = cosf(w.s0[0]); w.sin0 = sinf(w.s0[0]);
+  w.scale = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? 1.0f : 1.0f / (float)(p.H + 1);
+  w.clip = p.control_mode == CPMPPI_CONTROL_CLIP;
+}
+
+// Cost of the lane's plan; `backward`: also its gradient -> w.grad (a flag, not a template parameter: the final cost of a fused
+// control step is the forward half of the one sweep its kernel holds; a literal folds after inlining).  `pi`: the block the
+// integration computes with (the env's own pole mass under predictor_ODE), `p`: the launch's (costs).
+template <int COST, int INTEG, bool QSTRIDED = false>
+__device__ __forceinline__ float adjoint_sweep(const Params& p, const Params& pi, const EnvConst& ec, const SweepLane& w,
+                                               bool backward) {
+  const uint32_t H = p.H, S = p.S;
+  const size_t B = w.ckpt_stride;
+  const uint32_t Bs = w.sub_stride, Bg = w.grad_stride;
+  // (QSTRIDED: the plan has no stride of its own - it is indexed with the gradient's, which holds for the one such caller,
+  // cem_step_kernel, where samples and gradient are both [H][block] columns; a caller whose plan is laid out otherwise needs a member)
+  auto plan = [&](uint32_t k) __attribute__((always_inline)) { return QSTRIDED ? w.Q[(size_t)k * Bg] : w.Q[k]; };
+  const float t = p.t_step;
+  auto forward_substep = [&](State<float>& s, float uK) __attribute__((always_inline)) {
+    if constexpr (INTEG == PREDICTOR_ODE) substep_cromer_plain(s, uK, p.t_step, pi, ec);
+    else substep_fast<float>(s, uK, p.t_step, p, ec, p.THL);
+  };
+  const float* __restrict__ s0 = w.s0;
+  const float x_t = w.x_t, te = w.te, scale = w.scale;
+  const bool clip = w.clip;
+
+  // ---- forward, check-pointing every control step
+  State<float> st{s0[0], s0[1], s0[2], s0[3], s0[4], s0[5]};
+  float cost = 0.0f, cosang = w.cos0, u_before = w.ub0;
+  for (uint32_t k = 0; k < H; ++k) {
+    if (backward) {
+      float* ck = w.ckpt + ((size_t)k * 6) * B;
+      ck[0] = st.th; ck[B] = st.w; ck[2 * B] = st.c; ck[3 * B] = st.s; ck[4 * B] = st.x; ck[5 * B] = st.v;
+    }
+    float ur = plan(k);
+    if (clip) ur = clamp_(ur, p.lo, p.hi);
+    if constexpr (COST == COST_QBGM) cost += stage_qbgm<float, true>(p, st.x, cosang, st.w, ur, x_t, te);
+    else if constexpr (COST == COST_DEFAULT) cost += stage_default<float, true>(p, st.x, cosang, ur, x_t, te);
+    else cost += stage_qbg<float, true>(p, st.x, cosang, st.w, ur, u_before, x_t, te);
+    u_before = ur;
+    const float uK = ur * ec.uK_scale;
+    for (uint32_t s = 0; s < S; ++s) forward_substep(st, uK);
+    cosang = st.c;
+  }
+  const float term = (COST == COST_DEFAULT) ? terminal_indicator<float>(p, st.th, st.x, x_t) : 0.0f;
+  const float total = (cost + term) * scale;
+  if (!backward) return total;
+
+  // ---- backward
+  Adjoint lam{0.0f, 0.0f, 0.0f, 0.0f};              // the terminal indicator has zero derivative
+  float carry = 0.0f;                               // d stage_{k+1} / d u_k through u_before (quadratic_boundary_grad)
+  for (uint32_t k = H; k-- > 0;) {
+    const float* ck = w.ckpt + ((size_t)k * 6) * B;
+    const State<float> st0{ck[0], ck[B], ck[2 * B], ck[3 * B], ck[4 * B], ck[5 * B]};
+    const float q = plan(k);
+    const bool clipped = clip && (q < p.lo || q > p.hi);
+    const float ur = clip ? clamp_(q, p.lo, p.hi) : q;
+    const float uK = ur * ec.uK_scale;
+    State<float> s = st0;
+    for (uint32_t i = 0; i < S; ++i) {
+      float* d = w.sub + (size_t)i * 6 * Bs;
+      d[0] = s.th; d[Bs] = s.w; d[2 * Bs] = s.c; d[3 * Bs] = s.s; d[4 * Bs] = s.x; d[5 * Bs] = s.v;
+      forward_substep(s, uK);
+    }
+    float guK = 0.0f;
+    for (uint32_t i = S; i-- > 0;) {
+      const float* d = w.sub + (size_t)i * 6 * Bs;
+      const State<float> si{d[0], d[Bs], d[2 * Bs], d[3 * Bs], d[4 * Bs], d[5 * Bs]};
+      substep_reverse<(INTEG == PREDICTOR_ODE)>(si, uK, t, pi, ec, lam, guK);
+    }
+    // stage k: its own state and control
+    const float ca = (k == 0) ? w.cos0 : st0.c, sa = (k == 0) ? w.sin0 : st0.s;
+    float ub = w.ub0;
+    if (COST == COST_QBG && k > 0) { ub = plan(k - 1); if (clip) ub = clamp_(ub, p.lo, p.hi); }
+    StageGrad sg;
+    if constexpr (COST == COST_QBGM) sg = stage_qbgm_grad(p, st0.x, ca, st0.w, ur, x_t, te);
+    else if constexpr (COST == COST_DEFAULT) sg = stage_default_grad(p, st0.x, ca, ur, x_t, te);
+    else sg = stage_qbg_grad(p, st0.x, ca, st0.w, ur, ub, x_t, te);
+    lam.x = __builtin_fmaf(scale, sg.x, lam.x);
+    lam.w = __builtin_fmaf(scale, sg.w, lam.w);
+    lam.th = __builtin_fmaf(scale * sg.cosang, -sa, lam.th);
+    const float gk = __builtin_fmaf(guK, ec.uK_scale, scale * sg.u + carry);
+    carry = scale * sg.u_before;
+    w.grad[(size_t)k * Bg] = clipped ? 0.0f : gk;
+  }
+  return total;
 }
 
 }  // namespace cpmppi

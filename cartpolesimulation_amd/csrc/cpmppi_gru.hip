@@ -7,6 +7,8 @@
 //                                           (plugin costs); launched by step_impl through launch_gru_rollout.
 //   gru_cost_only_kernel<COST,F16>          costs of GIVEN input plans under the GRU predictor, nothing of the MPPI update: the
 //                                           building block of the sampling optimizers (cem, cem-gmm, random-action).
+// The two rollout kernels share one rollout (GruRollout: gru_rollout_init, gru_rollout_step, gru_rollout_total) and differ in where
+// a step's input comes from and in what becomes of the costs; gru_predict_kernel runs the exact cell (gru_step) on its own.
 // Entry points: cpmppi_set_gru, cpmppi_gru_predict, cpmppi_rollout_cost_gru; -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write
 // g_gru_stamp_sum are this unit's).
 #include <hip/hip_runtime.h>
@@ -24,9 +26,100 @@ using namespace cpmppi_k;
 
 namespace {
 
-__device__ __forceinline__ void gru_load_image(float* __restrict__ lds, const float* __restrict__ image) {
-  for (int i = threadIdx.x; i < GRU_IMAGE_FLOATS; i += BLOCK) lds[i] = image[i];
+__device__ __forceinline__ void gru_load_image(float* __restrict__ lds, const float* __restrict__ image, int floats) {
+  for (int i = threadIdx.x; i < floats; i += BLOCK) lds[i] = image[i];
   __syncthreads();
+}
+
+// The weights image of the two rollout kernels: the f16 split (FAST) or the exact f32 fragments.
+template <bool F16>
+constexpr int GRU_ROLLOUT_IMAGE_FLOATS = F16 ? G16_IMAGE_BYTES / 4 : GRU_IMAGE_FLOATS;
+
+// One rollout on its pair of lanes (c and c + 32 of a wave) through the horizon, as gru_rollout_cost_kernel and
+// gru_cost_only_kernel carry it: set-up, one control step, cost epilogue.  How a step's input is obtained is the kernel's.
+// GruRollout holds what a step changes.  What stays - the image `lds`, the env's state `s0`, the targets, `lane`, `c` = lane & 31,
+// `half1` = lane >= 32 - is handed to the three functions as plain arguments without __restrict__: as members of the state, or as
+// noalias arguments, the PRECISE horizon loop compiled to another schedule (0.3 % slower at 1 x 200 x 35); like this it is the
+// loop the kernels had with these statements written out in each of them.
+struct GruRollout {
+  float st[6];
+  float cost, cosang;
+  f16v x, h1, h2;
+  GruCarry carry;          // PRECISE
+  Gru16Carry carry16;      // FAST, with gs
+  Gru16State gs;
+};
+
+// development aid (-DCPMPPI_GRU_STAMPS): the stamp sums a step adds to.  The fused kernel publishes them; the cost-only kernel has no
+// stamps of its own and hands the cell an object it drops (the stamped cell takes no other form).  Empty in product builds.
+struct GruStamps {
+#ifdef CPMPPI_GRU_STAMPS
+  unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
+  unsigned long long prev = 0;
+#endif
+};
+
+// h1src, h2src: the env's two hidden states [32] or NULL = 0
+template <bool F16>
+__device__ __forceinline__ void gru_rollout_init(GruRollout& r, const float* lds, const float* s0, uint32_t lane,
+                                                 const float* h1src, const float* h2src) {
+  r.h1 = gru_load_hidden(h1src, lane);
+  r.h2 = gru_load_hidden(h2src, lane);
+  for (int i = 0; i < 6; ++i) r.st[i] = s0[i];
+  r.cost = 0.0f;
+  r.cosang = cosf(s0[0]);                 // the plugins take cos(angle) of the given state at stage 0
+  if constexpr (F16) {
+    r.gs.h1 = r.h1; r.gs.h2 = r.h2;
+    gru16_carry_init(reinterpret_cast<const char*>(lds), r.gs, lane, r.carry16);
+  } else {
+    gru_carry_init(lds, r.h1, lane, r.carry);
+  }
+}
+
+// Control step k with the input `ur`: clamp, stage cost, `after_stage(ur)` (what else the kernel accumulates from the clamped
+// input), then the cell, the output state and the feedback.
+template <int COST, bool F16, class AfterStage>
+__device__ __forceinline__ void gru_rollout_step(GruRollout& r, const float* lds, const float* s0, float x_t, float te,
+                                                 uint32_t lane, uint32_t c, bool half1, const Params& p, const GruNorm& nm,
+                                                 uint32_t k, float ur, GruStamps& stamps, AfterStage&& after_stage) {
+  if (p.control_mode == CPMPPI_CONTROL_CLIP) ur = clamp_(ur, p.lo, p.hi);
+  if constexpr (COST == COST_QBGM) r.cost += stage_qbgm<float, F16>(p, r.st[4], r.cosang, r.st[1], ur, x_t, te);
+  else r.cost += stage_default<float, F16>(p, r.st[4], r.cosang, ur, x_t, te);
+  after_stage(ur);
+  if (k == 0) r.x = gru_input_tile(nm, s0, ur, lane);
+  else if (half1) r.x[1] = __builtin_fmaf(ur, nm.in_scale[0], nm.in_shift[0]);
+  float out[5];
+  if constexpr (F16) {
+    const char* ldsb = reinterpret_cast<const char*>(lds);
+#ifdef CPMPPI_GRU_STAMPS
+    const f16v o = gru16_step(ldsb, r.x, r.gs, r.carry16, lane, stamps.acc, stamps.prev);
+#else
+    const f16v o = gru16_step(ldsb, r.x, r.gs, r.carry16, lane);
+#endif
+    out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3];
+    out[4] = __shfl(o[0], (int)(c + 32u), 64);           // positionD (row 4) lives on the partner lane-half
+    if (half1) out[4] = o[0];
+  } else {
+#ifdef CPMPPI_GRU_STAMPS
+    gru_step_pipelined(lds, r.x, r.h1, r.h2, r.carry, lane, out, stamps.acc, stamps.prev);
+#else
+    gru_step_pipelined(lds, r.x, r.h1, r.h2, r.carry, lane, out);
+#endif
+  }
+  gru_output_state_fast(nm, out, r.st, r.cosang);
+  // normalised outputs are fed back unchanged: rows 0..3 on lane-half 0, row 4 (and Q, row 5) on lane-half 1
+  r.x[0] = half1 ? out[4] : out[0];
+  r.x[1] = half1 ? 0.0f : out[1];
+  r.x[2] = half1 ? 0.0f : out[2];
+  r.x[3] = half1 ? 0.0f : out[3];
+}
+
+// The rollout's cost after the last step: stage costs + terminal cost, reduced over the horizon.
+template <int COST>
+__device__ __forceinline__ float gru_rollout_total(GruRollout& r, float x_t, const Params& p) {
+  r.st[0] = atan2f(r.st[3], r.st[2]);       // predictors_customization.py:121-127, needed for the terminal cost only
+  const float term = (COST == COST_DEFAULT) ? terminal_indicator<float>(p, r.st[0], r.st[4], x_t) : 0.0f;
+  return (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? (r.cost + term) : (r.cost + term) / (float)(p.H + 1);
 }
 
 // predictor seam with the neural predictor: s0[B,6], Q[B,H], h0[2,B,32] or NULL -> traj[B,H+1,6], h_out[2,B,32] or NULL
@@ -37,7 +130,7 @@ __global__ __launch_bounds__(BLOCK, 1) void gru_predict_kernel(const GruNorm nm,
                                                             const float* __restrict__ Q, const float* __restrict__ h0,
                                                             float* __restrict__ traj, float* __restrict__ h_out) {
   extern __shared__ float lds[];
-  gru_load_image(lds, image);
+  gru_load_image(lds, image, GRU_IMAGE_FLOATS);
   const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, c = lane & 31u;
   const size_t b = (size_t)blockIdx.x * GRU_ROLLOUTS_PER_BLOCK + wave * 32 + c;
   const bool valid = b < B;
@@ -75,9 +168,8 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_rollout_cost_kernel(
                                                                  const float* __restrict__ h0) {
   extern __shared__ float lds[];                           // GRU image, then [WAVES][W] weighted sums
   __shared__ float red[2 * WAVES];
-  constexpr int IMAGE_FLOATS = F16 ? G16_IMAGE_BYTES / 4 : GRU_IMAGE_FLOATS;
-  for (int i = threadIdx.x; i < IMAGE_FLOATS; i += BLOCK) lds[i] = image[i];
-  __syncthreads();
+  constexpr int IMAGE_FLOATS = GRU_ROLLOUT_IMAGE_FLOATS<F16>;
+  gru_load_image(lds, image, IMAGE_FLOATS);
   float* bsum = lds + IMAGE_FLOATS;
   const uint32_t env = blockIdx.x / a.nb, blk = blockIdx.x % a.nb;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = lane & 31u;
@@ -90,8 +182,9 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_rollout_cost_kernel(
   const float x_t = a.x_t[env], te = a.te[env];
   const float* __restrict__ s0 = a.s0 + (size_t)env * 6;
   const float* __restrict__ un = a.u_nom + (size_t)env * H;
-  f16v h1 = gru_load_hidden(h0 ? h0 + (size_t)env * 64 : nullptr, lane);
-  f16v h2 = gru_load_hidden(h0 ? h0 + (size_t)env * 64 + 32 : nullptr, lane);
+  GruRollout ro;
+  gru_rollout_init<F16>(ro, lds, s0, lane, h0 ? h0 + (size_t)env * 64 : nullptr, h0 ? h0 + (size_t)env * 64 + 32 : nullptr);
+  const bool half1 = lane >= 32;
 
   auto knot = [&](uint32_t j) __attribute__((always_inline)) -> float {
     if constexpr (NOISE == NOISE_KNOTS) return a.noise[((size_t)env * p.N + nn) * p.P + j];
@@ -100,25 +193,10 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_rollout_cost_kernel(
   float z_lo = 0.0f, z_hi = 0.0f;
   if constexpr (NOISE != NOISE_DELTA_U) { z_lo = knot(0); z_hi = knot(1); }
   uint32_t ii = 0, j = 0;
-
-  float st[6] = {s0[0], s0[1], s0[2], s0[3], s0[4], s0[5]};
-  float cost = 0.0f, corr = 0.0f;
-  float cosang = cosf(s0[0]);               // the plugins take cos(angle) of the given state at stage 0
-  f16v x;
-  GruCarry carry;
-  Gru16Carry carry16;
-  Gru16State gs;
-  const char* __restrict__ ldsb = reinterpret_cast<const char*>(lds);
-  if constexpr (F16) {
-    gs.h1 = h1; gs.h2 = h2;
-    gru16_carry_init(ldsb, gs, lane, carry16);
-  } else {
-    gru_carry_init(lds, h1, lane, carry);
-  }
-  const bool half1 = lane >= 32;
+  float corr = 0.0f;
+  GruStamps stamps;
 #ifdef CPMPPI_GRU_STAMPS
-  unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long stamp_prev = __builtin_amdgcn_s_memtime();
+  stamps.prev = __builtin_amdgcn_s_memtime();
 #endif
   for (uint32_t k = 0; k < H; ++k) {
     float du;
@@ -128,35 +206,9 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_rollout_cost_kernel(
     else du = interp_knots(z_lo, z_hi, ii, p.period);
     const float uk = shifted_nominal(p, un, k);
     float ur = uk + du;
-    if (p.control_mode == CPMPPI_CONTROL_CLIP) ur = clamp_(ur, p.lo, p.hi);
-    if constexpr (COST == COST_QBGM) cost += stage_qbgm<float, F16>(p, st[4], cosang, st[1], ur, x_t, te);
-    else cost += stage_default<float, F16>(p, st[4], cosang, ur, x_t, te);
-    corr += mppi_correction<float>(p, p.correction_u == CPMPPI_CORRECTION_U_RUN ? ur : uk, du);
-    if (k == 0) x = gru_input_tile(nm, s0, ur, lane);
-    else if (half1) x[1] = __builtin_fmaf(ur, nm.in_scale[0], nm.in_shift[0]);
-    float out[5];
-    if constexpr (F16) {
-#ifdef CPMPPI_GRU_STAMPS
-      const f16v o = gru16_step(ldsb, x, gs, carry16, lane, stamp_acc, stamp_prev);
-#else
-      const f16v o = gru16_step(ldsb, x, gs, carry16, lane);
-#endif
-      out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3];
-      out[4] = __shfl(o[0], (int)(c + 32u), 64);           // positionD (row 4) lives on the partner lane-half
-      if (half1) out[4] = o[0];
-    } else {
-#ifdef CPMPPI_GRU_STAMPS
-      gru_step_pipelined(lds, x, h1, h2, carry, lane, out, stamp_acc, stamp_prev);
-#else
-      gru_step_pipelined(lds, x, h1, h2, carry, lane, out);
-#endif
-    }
-    gru_output_state_fast(nm, out, st, cosang);
-    // normalised outputs are fed back unchanged: rows 0..3 on lane-half 0, row 4 (and Q, row 5) on lane-half 1
-    x[0] = half1 ? out[4] : out[0];
-    x[1] = half1 ? 0.0f : out[1];
-    x[2] = half1 ? 0.0f : out[2];
-    x[3] = half1 ? 0.0f : out[3];
+    gru_rollout_step<COST, F16>(ro, lds, s0, x_t, te, lane, c, half1, p, nm, k, ur, stamps, [&](float u) __attribute__((always_inline)) {
+      corr += mppi_correction<float>(p, p.correction_u == CPMPPI_CORRECTION_U_RUN ? u : uk, du);
+    });
     if constexpr (NOISE != NOISE_DELTA_U) {
       if (++ii == p.period) {
         ii = 0; ++j;
@@ -165,15 +217,12 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_rollout_cost_kernel(
       }
     }
   }
-  st[0] = atan2f(st[3], st[2]);             // predictors_customization.py:121-127, needed for the terminal cost only
 #ifdef CPMPPI_GRU_STAMPS
   if (lane == 0)
-    for (int i = 0; i < 6; ++i) atomicAdd(&g_gru_stamp_sum[i], stamp_acc[i]);
+    for (int i = 0; i < 6; ++i) atomicAdd(&g_gru_stamp_sum[i], stamps.acc[i]);
   if (lane == 0) atomicAdd(&g_gru_stamp_sum[6], 1ull);
 #endif
-  const float term = (COST == COST_DEFAULT) ? terminal_indicator<float>(p, st[0], st[4], x_t) : 0.0f;
-  float S_total = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? (cost + term) : (cost + term) / (float)(H + 1);
-  S_total += corr;
+  const float S_total = gru_rollout_total<COST>(ro, x_t, p) + corr;
   if (a.S_out && owner) a.S_out[(size_t)env * p.N + n] = S_total;
 
   const float m_w = wave_min(owner ? S_total : INFINITY);
@@ -231,9 +280,9 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_rollout_cost_kernel(
 }
 
 // Cost-only rollout with the GRU predictor: S[env][n] = get_trajectory_cost(predict_core_GRU(s0[env], inputs[env][n]), inputs[env][n]).
-// The statements of gru_rollout_cost_kernel<COST, NOISE_DELTA_U, F16> for a zero nominal sequence, no shift and cc_weight = 0 -
-// same tile mapping (32 rollouts per wave, GRU_ROLLOUTS_PER_BLOCK per workgroup, grid E x nb), same cell, same cost statements in
-// the same order - without anything that serves the MPPI update: no block minimum, no weights, no weighted sums of the noise, no
+// What gru_rollout_cost_kernel<COST, NOISE_DELTA_U, F16> computes for a zero nominal sequence, no shift and cc_weight = 0 - same
+// tile mapping (32 rollouts per wave, GRU_ROLLOUTS_PER_BLOCK per workgroup, grid E x nb) and the same GruRollout set-up, step and
+// epilogue - without anything that serves the MPPI update: no block minimum, no weights, no weighted sums of the noise, no
 // partials.  Dynamic LDS holds the weights image only, and after its load no wave depends on another: a wave whose 32 rollouts
 // all lie beyond N leaves at once, and there is no barrier behind the one of the image load.
 // The lane's next input does not depend on the state: it is loaded one control step ahead, off the recurrent chain.
@@ -251,9 +300,7 @@ template <int COST, bool F16>
 __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_cost_only_kernel(const Params p, const GruCostPtrs a, const GruNorm nm,
                                                                               const float* __restrict__ image) {
   extern __shared__ float lds[];                           // GRU image only
-  constexpr int IMAGE_FLOATS = F16 ? G16_IMAGE_BYTES / 4 : GRU_IMAGE_FLOATS;
-  for (int i = threadIdx.x; i < IMAGE_FLOATS; i += BLOCK) lds[i] = image[i];
-  __syncthreads();                                         // the kernel's only barrier
+  gru_load_image(lds, image, GRU_ROLLOUT_IMAGE_FLOATS<F16>);   // the kernel's only barrier
   const uint32_t env = blockIdx.x / a.nb, blk = blockIdx.x % a.nb;
   const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = lane & 31u;
   const uint32_t row0 = blk * GRU_ROLLOUTS_PER_BLOCK + wave * 32;
@@ -265,70 +312,26 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_cost_only_kernel(con
   const float x_t = a.x_t[env], te = a.te[env];
   const float* __restrict__ s0 = a.s0 + (size_t)env * 6;
   const float* __restrict__ in = a.inputs + ((size_t)env * p.N + nn) * H;
-  f16v h1 = gru_load_hidden(a.h0 ? a.h0 + (size_t)env * 64 : nullptr, lane);
-  f16v h2 = gru_load_hidden(a.h0 ? a.h0 + (size_t)env * 64 + 32 : nullptr, lane);
-
-  float st[6] = {s0[0], s0[1], s0[2], s0[3], s0[4], s0[5]};
-  float cost = 0.0f;
-  float cosang = cosf(s0[0]);               // the plugins take cos(angle) of the given state at stage 0
-  f16v x;
-  GruCarry carry;
-  Gru16Carry carry16;
-  Gru16State gs;
-  const char* __restrict__ ldsb = reinterpret_cast<const char*>(lds);
-  if constexpr (F16) {
-    gs.h1 = h1; gs.h2 = h2;
-    gru16_carry_init(ldsb, gs, lane, carry16);
-  } else {
-    gru_carry_init(lds, h1, lane, carry);
-  }
+  GruRollout ro;
+  gru_rollout_init<F16>(ro, lds, s0, lane, a.h0 ? a.h0 + (size_t)env * 64 : nullptr, a.h0 ? a.h0 + (size_t)env * 64 + 32 : nullptr);
   const bool half1 = lane >= 32;
-#ifdef CPMPPI_GRU_STAMPS
-  unsigned long long stamp_acc[6] = {0, 0, 0, 0, 0, 0};   // (the stamps are the fused kernel's: taken and dropped here)
-  unsigned long long stamp_prev = 0;
-#endif
+  GruStamps none;
   float u_next = in[0];
   for (uint32_t k = 0; k < H; ++k) {
-    float ur = u_next;
+    const float ur = u_next;
     if (k + 1 < H) u_next = in[k + 1];                     // in flight during this step's cell
-    if (p.control_mode == CPMPPI_CONTROL_CLIP) ur = clamp_(ur, p.lo, p.hi);
-    if constexpr (COST == COST_QBGM) cost += stage_qbgm<float, F16>(p, st[4], cosang, st[1], ur, x_t, te);
-    else cost += stage_default<float, F16>(p, st[4], cosang, ur, x_t, te);
-    if (k == 0) x = gru_input_tile(nm, s0, ur, lane);
-    else if (half1) x[1] = __builtin_fmaf(ur, nm.in_scale[0], nm.in_shift[0]);
-    float out[5];
-    if constexpr (F16) {
-#ifdef CPMPPI_GRU_STAMPS
-      const f16v o = gru16_step(ldsb, x, gs, carry16, lane, stamp_acc, stamp_prev);
-#else
-      const f16v o = gru16_step(ldsb, x, gs, carry16, lane);
-#endif
-      out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3];
-      out[4] = __shfl(o[0], (int)(c + 32u), 64);           // positionD (row 4) lives on the partner lane-half
-      if (half1) out[4] = o[0];
-    } else {
-#ifdef CPMPPI_GRU_STAMPS
-      gru_step_pipelined(lds, x, h1, h2, carry, lane, out, stamp_acc, stamp_prev);
-#else
-      gru_step_pipelined(lds, x, h1, h2, carry, lane, out);
-#endif
-    }
-    gru_output_state_fast(nm, out, st, cosang);
-    // normalised outputs are fed back unchanged: rows 0..3 on lane-half 0, row 4 (and Q, row 5) on lane-half 1
-    x[0] = half1 ? out[4] : out[0];
-    x[1] = half1 ? 0.0f : out[1];
-    x[2] = half1 ? 0.0f : out[2];
-    x[3] = half1 ? 0.0f : out[3];
+    gru_rollout_step<COST, F16>(ro, lds, s0, x_t, te, lane, c, half1, p, nm, k, ur, none, [](float) {});
   }
-  st[0] = atan2f(st[3], st[2]);             // predictors_customization.py:121-127, needed for the terminal cost only
-  const float term = (COST == COST_DEFAULT) ? terminal_indicator<float>(p, st[0], st[4], x_t) : 0.0f;
-  const float S_total = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? (cost + term) : (cost + term) / (float)(H + 1);
+  const float S_total = gru_rollout_total<COST>(ro, x_t, p);
   if (owner) a.S_out[(size_t)env * p.N + n] = S_total;
 }
 
+// FAST: float32-equivalent split products on the f16 matrix cores (cpmppi_gru16.hpp); PRECISE: exact f32 MFMA chains
+inline bool gru_runs_f16(const cpmppi_handle* h) { return h->cfg.math_mode == CPMPPI_MATH_FAST && h->gru16_image != nullptr; }
+
 template <int COST>
 void launch_gru_cost_only(cpmppi_handle* h, const GruCostPtrs& a, uint32_t E, hipStream_t s) {
-  const bool f16 = h->cfg.math_mode == CPMPPI_MATH_FAST && h->gru16_image != nullptr;
+  const bool f16 = gru_runs_f16(h);
   const dim3 grid(E * a.nb);
   if (f16) hipLaunchKernelGGL((gru_cost_only_kernel<COST, true>), grid, dim3(BLOCK), (size_t)G16_IMAGE_BYTES, s, h->prm, a,
                               h->gru_norm, (const float*)h->gru16_image);
@@ -336,10 +339,9 @@ void launch_gru_cost_only(cpmppi_handle* h, const GruCostPtrs& a, uint32_t E, hi
                           h->prm, a, h->gru_norm, (const float*)h->gru_image);
 }
 
-// FAST: float32-equivalent split products on the f16 matrix cores (cpmppi_gru16.hpp); PRECISE: exact f32 MFMA chains
 template <int COST, int NOISE>
 void launch_gru(cpmppi_handle* h, const cpmppi_step_args* a, const StepPtrs& p, hipStream_t s) {
-  const bool f16 = h->cfg.math_mode == CPMPPI_MATH_FAST && h->gru16_image != nullptr;
+  const bool f16 = gru_runs_f16(h);
   const size_t lds = ((f16 ? (size_t)G16_IMAGE_BYTES / 4 : (size_t)GRU_IMAGE_FLOATS) + (size_t)WAVES * p.W) * sizeof(float);
   // (host code that no allowed H reaches: at H = CPMPPI_MAX_HORIZON = 1024 the images need 64 640 B (FAST) and 64 416 B (PRECISE))
   if (lds > 64 * 1024) {   // long horizons with a perturbation buffer: weights image + [WAVES][H] sums

@@ -2,16 +2,18 @@
 // rollout + cost, Adam / SGD steps on input sequences, and CEM's sampler and elite update.   Contract: include/cpmppi.h.
 //
 // Kernel inventory
-//   rollout_grad_kernel<COST, INTEG>      rollout + plugin cost + its gradient w.r.t. the inputs (cpmppi_grad.hpp).
+//   rollout_grad_kernel<COST, INTEG>      rollout + plugin cost + its gradient w.r.t. the inputs, one lane per (env, rollout).
 //   adam_step_kernel, sgd_step_kernel     gradient steps with per-rollout norm clipping and the action limits.
 //   cem_sample_kernel, cem_gmm_sample_kernel   CEM's sampler: one Gaussian per env, or a mixture of K elite-centred ones.
 //   cem_update_kernel                     top-k (bitonic sort in LDS) -> mean and stdev of the elite.
 //   rpgd_step_kernel<COST, INTEG>         the whole rpgd / gradient-tf control step, one workgroup per env (cpmppi_rpgd.hpp).
 //   cem_step_kernel<COST, INTEG, REFINE>  the whole cem / cem-naive-grad / cem-grad-bharadhwaj control step, likewise (cpmppi_cem.hpp).
-// cpmppi_rollout_cost launches rollout_cost_kernel through launch_rollout (cpmppi.hip).
+// The three templated kernels run the one adjoint sweep of cpmppi_grad.hpp (adjoint_sweep over a SweepLane); the two fused steps
+// rank their costs with rank_costs.  cpmppi_rollout_cost launches rollout_cost_kernel through launch_rollout (cpmppi.hip).
 #include <hip/hip_runtime.h>
 #include <math.h>
 #include <string>
+#include <type_traits>
 
 #include "cpmppi.h"
 #include "cpmppi_internal.hpp"
@@ -23,8 +25,19 @@ using namespace cpmppi_k;
 
 namespace {
 
+// The kernels below are built for the three costs with an adjoint; `f` gets the handle's as a compile-time constant:
+//   with_cost(id, [&](auto cost) { constexpr int COST = decltype(cost)::value; ... });
+template <class F>
+void with_cost(uint32_t cost_id, F&& f) {
+  switch (cost_id) {
+    case CPMPPI_COST_QBGM: f(std::integral_constant<int, COST_QBGM>{}); break;
+    case CPMPPI_COST_DEFAULT: f(std::integral_constant<int, COST_DEFAULT>{}); break;
+    default: f(std::integral_constant<int, COST_QBG>{}); break;
+  }
+}
+
 // ------------------------------------------------------------------------------------------------------------------
-// Rollout + plugin cost + its gradient w.r.t. the inputs (cpmppi_grad.hpp).  One lane = one (env, rollout) of the
+// Rollout + plugin cost + its gradient w.r.t. the inputs (adjoint_sweep, cpmppi_grad.hpp).  One lane = one (env, rollout) of the
 // flattened [E*N] axis (the gradient optimizers run 16-40 rollouts per env, config_optimizers.yml:60,75: a block per
 // env would idle), so per-env quantities are per-lane here.  Check-points ckpt[H][6][E*N] (lane-contiguous) hold the
 // state at every control step; sub[S][6][BLOCK] in LDS holds the sub-states of the control step being reversed.
@@ -42,83 +55,21 @@ __global__ __launch_bounds__(BLOCK) void rollout_grad_kernel(const Params p, con
   const size_t g = (size_t)blockIdx.x * BLOCK + tid;
   if (g >= B) return;                               // (no block-level barrier below)
   const uint32_t env = (uint32_t)(g / p.N);
-  const uint32_t H = p.H, S = p.S;
-  const float t = p.t_step;
   // `pi`: the block the integration and its adjoint compute with - predictor_ODE: the env's own pole mass in place (the costs
   // never read the mass)
   Params pm_;
   if constexpr (INTEG == PREDICTOR_ODE) pm_ = with_pole_mass(p, a.m_pole ? a.m_pole[env] : p.m_pole);
   const Params& pi = (INTEG == PREDICTOR_ODE) ? pm_ : p;
-  auto forward_substep = [&](State<float>& s, float uK, const EnvConst& e) __attribute__((always_inline)) {
-    if constexpr (INTEG == PREDICTOR_ODE) substep_cromer_plain(s, uK, p.t_step, pi, e);
-    else substep_fast<float>(s, uK, p.t_step, p, e, p.THL);
-  };
   const EnvConst ec = make_env_const(pi, a.L ? a.L[env] : p.L_default);
-  const float x_t = a.x_t[env], te = a.te[env];
-  const float* __restrict__ s0 = a.s0 + (size_t)env * 6;
-  const float* __restrict__ Q = a.Q + g * H;
-  const float cos0 = cosf(s0[0]), sin0 = sinf(s0[0]);   // the plugins take cos(angle) of the given state at stage 0
-  const float ub0 = a.prev_in ? a.prev_in[env] : 0.0f;
-  const bool clip = p.control_mode == CPMPPI_CONTROL_CLIP;
-  const float scale = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? 1.0f : 1.0f / (float)(H + 1);
-
-  // ---- forward, check-pointing every control step -------------------------------------------------------------
-  State<float> st{s0[0], s0[1], s0[2], s0[3], s0[4], s0[5]};
-  float cost = 0.0f, cosang = cos0, u_before = ub0;
-  for (uint32_t k = 0; k < H; ++k) {
-    float* __restrict__ ck = a.ckpt + ((size_t)k * 6) * B + g;
-    ck[0] = st.th; ck[B] = st.w; ck[2 * B] = st.c; ck[3 * B] = st.s; ck[4 * B] = st.x; ck[5 * B] = st.v;
-    float ur = Q[k];
-    if (clip) ur = clamp_(ur, p.lo, p.hi);
-    if constexpr (COST == COST_QBGM) cost += stage_qbgm<float, true>(p, st.x, cosang, st.w, ur, x_t, te);
-    else if constexpr (COST == COST_DEFAULT) cost += stage_default<float, true>(p, st.x, cosang, ur, x_t, te);
-    else cost += stage_qbg<float, true>(p, st.x, cosang, st.w, ur, u_before, x_t, te);
-    u_before = ur;
-    const float uK = ur * ec.uK_scale;
-    for (uint32_t s = 0; s < S; ++s) forward_substep(st, uK, ec);
-    cosang = st.c;
-  }
-  const float term = (COST == COST_DEFAULT) ? terminal_indicator<float>(p, st.th, st.x, x_t) : 0.0f;
-  if (a.S_out) a.S_out[g] = (cost + term) * scale;
-
-  // ---- backward --------------------------------------------------------------------------------------------------
-  Adjoint lam{0.0f, 0.0f, 0.0f, 0.0f};              // the terminal indicator has zero derivative
-  float carry = 0.0f;                               // d stage_{k+1} / d u_k through u_before (quadratic_boundary_grad)
-  float* __restrict__ my = sub_states + tid;
-  for (uint32_t k = H; k-- > 0;) {
-    const float* __restrict__ ck = a.ckpt + ((size_t)k * 6) * B + g;
-    const State<float> st0{ck[0], ck[B], ck[2 * B], ck[3 * B], ck[4 * B], ck[5 * B]};
-    const float q = Q[k];
-    const bool clipped = clip && (q < p.lo || q > p.hi);
-    const float ur = clip ? clamp_(q, p.lo, p.hi) : q;
-    const float uK = ur * ec.uK_scale;
-    State<float> s = st0;
-    for (uint32_t i = 0; i < S; ++i) {
-      float* __restrict__ d = my + (size_t)i * 6 * BLOCK;
-      d[0] = s.th; d[BLOCK] = s.w; d[2 * BLOCK] = s.c; d[3 * BLOCK] = s.s; d[4 * BLOCK] = s.x; d[5 * BLOCK] = s.v;
-      forward_substep(s, uK, ec);
-    }
-    float guK = 0.0f;
-    for (uint32_t i = S; i-- > 0;) {
-      const float* __restrict__ d = my + (size_t)i * 6 * BLOCK;
-      const State<float> si{d[0], d[BLOCK], d[2 * BLOCK], d[3 * BLOCK], d[4 * BLOCK], d[5 * BLOCK]};
-      substep_reverse<(INTEG == PREDICTOR_ODE)>(si, uK, t, pi, ec, lam, guK);
-    }
-    // stage k: its own state and control
-    const float ca = (k == 0) ? cos0 : st0.c, sa = (k == 0) ? sin0 : st0.s;
-    float ub = ub0;
-    if (COST == COST_QBG && k > 0) { ub = Q[k - 1]; if (clip) ub = clamp_(ub, p.lo, p.hi); }
-    StageGrad sg;
-    if constexpr (COST == COST_QBGM) sg = stage_qbgm_grad(p, st0.x, ca, st0.w, ur, x_t, te);
-    else if constexpr (COST == COST_DEFAULT) sg = stage_default_grad(p, st0.x, ca, ur, x_t, te);
-    else sg = stage_qbg_grad(p, st0.x, ca, st0.w, ur, ub, x_t, te);
-    lam.x = __builtin_fmaf(scale, sg.x, lam.x);
-    lam.w = __builtin_fmaf(scale, sg.w, lam.w);
-    lam.th = __builtin_fmaf(scale * sg.cosang, -sa, lam.th);
-    const float gk = __builtin_fmaf(guK, ec.uK_scale, scale * sg.u + carry);
-    carry = scale * sg.u_before;
-    a.grad[g * H + k] = clipped ? 0.0f : gk;
-  }
+  SweepLane w;
+  sweep_lane_env(w, p, a, env);
+  w.Q = a.Q + g * p.H;
+  w.ckpt_stride = B; w.sub_stride = BLOCK; w.grad_stride = 1;
+  w.ckpt = a.ckpt + g;
+  w.grad = a.grad + g * p.H;
+  w.sub = sub_states + tid;
+  const float S = adjoint_sweep<COST, INTEG>(p, pi, ec, w, true);
+  if (a.S_out) a.S_out[g] = S;
 }
 
 // Adam on input sequences with per-rollout gradient-norm clipping (tf.clip_by_norm over the horizon) and the final
@@ -218,6 +169,27 @@ __device__ __forceinline__ uint32_t cem_sort_key(float s) {
   return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
 }
 
+// The same order for a block that holds one cost per lane (the fused steps: N <= blockDim.x): every active lane counts the
+// (key, index) pairs below its own among the N keys in LDS and writes order[rank] = tid - and, when `publish`, order_out[env][rank] (order_out:
+// [E][N] or NULL).  Every lane of the block calls it; order[] stands when it returns.
+__device__ __forceinline__ void rank_costs(uint32_t* key, uint32_t* order, float S, bool active, uint32_t N, uint32_t env,
+                                           uint32_t* order_out, bool publish) {
+  const uint32_t tid = threadIdx.x;
+  key[tid] = active ? cem_sort_key(S) : 0xFFFFFFFFu;
+  __syncthreads();
+  if (active) {
+    const uint32_t mine = key[tid];
+    uint32_t rank = 0;
+    for (uint32_t j = 0; j < N; ++j) {
+      const uint32_t kj = key[j];
+      rank += (kj < mine || (kj == mine && j < tid)) ? 1u : 0u;
+    }
+    order[rank] = tid;
+    if (publish && order_out) order_out[(size_t)env * N + rank] = tid;
+  }
+  __syncthreads();
+}
+
 __global__ __launch_bounds__(BLOCK) void cem_update_kernel(const Params p, const float* __restrict__ S,
                                                            const float* __restrict__ Q, uint32_t best_k, float stdev_min,
                                                            uint32_t Np, float* __restrict__ mean_out,
@@ -264,9 +236,9 @@ __global__ __launch_bounds__(BLOCK) void cem_update_kernel(const Params p, const
 // The fused rpgd / gradient-tf control step (cpmppi_rpgd_step; device pieces in cpmppi_rpgd.hpp).  One workgroup = one env,
 // one lane = one plan; the block is N rounded up to whole waves, the surplus lanes only keep the barriers company.  A lane
 // carries its own row of Q, m, v through `iterations` x (adjoint sweep + Adam) and the final forward sweep: nothing crosses
-// lanes until the ranking.  Ranking: every lane counts the (key, index) pairs below its own among the N keys in LDS - the stable
-// order of cem_update_kernel.  Permutation + shift run column by column: every lane reads column k + shift of its SOURCE row,
-// the block meets, every lane writes column k of its OWN row; columns <= k are never read again, so one barrier per column.
+// lanes until the ranking (rank_costs: the stable order of cem_update_kernel).  Permutation + shift run column by column: every
+// lane reads column k + shift of its SOURCE row, the block meets, every lane writes column k of its OWN row; columns <= k are
+// never read again, so one barrier per column.
 struct RpgdPtrs {
   const float* s0; const float* x_t; const float* te; const float* L; const float* prev_in; const float* m_pole;
   float* Q; float* m; float* v;
@@ -295,40 +267,24 @@ __global__ __launch_bounds__(BLOCK) void rpgd_step_kernel(const Params p, const 
     if constexpr (INTEG == PREDICTOR_ODE) pm_ = with_pole_mass(p, a.m_pole ? a.m_pole[env] : p.m_pole);
     const Params& pi = (INTEG == PREDICTOR_ODE) ? pm_ : p;
     const EnvConst ec = make_env_const(pi, a.L ? a.L[env] : p.L_default);
-    RpgdLane w;
-    w.s0 = a.s0 + (size_t)env * 6;
+    SweepLane w;
+    sweep_lane_env(w, p, a, env);
     w.Q = a.Q + row;
-    w.x_t = a.x_t[env]; w.te = a.te[env]; w.ub0 = a.prev_in ? a.prev_in[env] : 0.0f;
-    w.cos0 = cosf(w.s0[0]); w.sin0 = sinf(w.s0[0]);
-    w.scale = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? 1.0f : 1.0f / (float)(H + 1);
-    w.clip = p.control_mode == CPMPPI_CONTROL_CLIP;
-    w.stride = Nb;
+    w.ckpt_stride = w.sub_stride = w.grad_stride = Nb;
     w.ckpt = a.ckpt + (size_t)env * H * 6 * Nb + tid;
     w.grad = a.grad + (size_t)env * H * Nb + tid;
     w.sub = rpgd_lds + tid;
     RpgdLr lr(a.beta1, a.beta2, it0);
     for (uint32_t i = 1; i <= a.iterations + 1; ++i) {
       const bool descend = i <= a.iterations;      // the last pass is the final cost: forward only
-      S = rpgd_sweep<COST, INTEG>(p, pi, ec, w, descend);
+      S = adjoint_sweep<COST, INTEG>(p, pi, ec, w, descend);
       if (!descend) break;
       const float lr_t = lr.next(a.lr, a.beta1, a.beta2);
       rpgd_adam_row(H, a.Q + row, a.m + row, a.v + row, w.grad, Nb, lr_t, a.beta1, a.beta2, a.eps, a.gradmax_clip, p.lo, p.hi);
     }
     if (a.S_out) a.S_out[(size_t)env * N + tid] = S;
   }
-  key[tid] = active ? cem_sort_key(S) : 0xFFFFFFFFu;
-  __syncthreads();
-  if (active) {
-    const uint32_t mine = key[tid];
-    uint32_t rank = 0;
-    for (uint32_t j = 0; j < N; ++j) {
-      const uint32_t kj = key[j];
-      rank += (kj < mine || (kj == mine && j < tid)) ? 1u : 0u;
-    }
-    order[rank] = tid;
-    if (a.order_out) a.order_out[(size_t)env * N + rank] = tid;
-  }
-  __syncthreads();
+  rank_costs(key, order, S, active, N, env, a.order_out, true);
   const float* best = a.Q + ((size_t)env * N + order[0]) * H;
   if (tid == 0) a.Q_out[env] = best[0];
   if (a.plan_out) for (uint32_t k = tid; k < H; k += Nb) a.plan_out[(size_t)env * H + k] = best[k];
@@ -361,24 +317,23 @@ __global__ void rpgd_count_kernel(unsigned long long* c) { *c += 1ull; }
 
 template <int INTEG>
 void launch_rpgd(uint32_t cost_id, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Params& p, const RpgdPtrs& a) {
-  switch (cost_id) {
-    case CPMPPI_COST_QBGM: hipLaunchKernelGGL((rpgd_step_kernel<COST_QBGM, INTEG>), grid, block, lds, st, p, a); break;
-    case CPMPPI_COST_DEFAULT: hipLaunchKernelGGL((rpgd_step_kernel<COST_DEFAULT, INTEG>), grid, block, lds, st, p, a); break;
-    default: hipLaunchKernelGGL((rpgd_step_kernel<COST_QBG, INTEG>), grid, block, lds, st, p, a); break;
-  }
+  with_cost(cost_id, [&](auto cost) {
+    hipLaunchKernelGGL((rpgd_step_kernel<decltype(cost)::value, INTEG>), grid, block, lds, st, p, a);
+  });
 }
 
 inline uint32_t rpgd_block(const cpmppi_handle* h) { return (h->cfg.N + 63u) & ~63u; }
 inline size_t rpgd_floats(const cpmppi_handle* h, uint32_t E) { return (size_t)h->cfg.H * 7 * E * rpgd_block(h); }
+inline size_t rpgd_lds_bytes(const cpmppi_handle* h) { return ((size_t)h->cfg.S * 6 + 2) * rpgd_block(h) * sizeof(float); }
 
 // ------------------------------------------------------------------------------------------------------------------
 // The fused CEM control step (cpmppi_cem_step; device pieces in cpmppi_cem.hpp): cem-tf and, with REFINE, its two gradient
 // hybrids.  One workgroup = one env, one lane = one sample, the block and its surplus lanes as in rpgd_step_kernel.  The env's mean
 // and stdev live in LDS for the whole step; a lane's sample is a workspace column.  Per outer iteration: every lane draws its row
 // (cem_sample_kernel's statement), refines it (one adjoint sweep + sgd / Adam row update), costs it (forward sweep); the block
-// ranks the costs (the counting rank of rpgd_step_kernel = cem_update_kernel's stable order); lanes k < H refit time-step k to
-// the elite in rank order (cem_update_kernel's statements).  The barrier that opens an iteration closes the refit of the one before:
-// no sample is overwritten while a refit still reads it.
+// ranks the costs (rank_costs = cem_update_kernel's stable order); lanes k < H refit time-step k to the elite in rank order
+// (cem_update_kernel's statements).  The barrier that opens an iteration closes the refit of the one before: no sample is
+// overwritten while a refit still reads it.
 struct CemPtrs {
   const float* s0; const float* x_t; const float* te; const float* L; const float* prev_in; const float* m_pole;
   float* mean; float* stdev;       // [E][H], in place
@@ -411,14 +366,10 @@ __global__ __launch_bounds__(BLOCK) void cem_step_kernel(const Params p, const C
   const EnvConst ec = make_env_const(pi, a.L ? a.L[env] : p.L_default);
   const size_t col = (size_t)env * H * Nb + tid;
   float* q = a.samples + col;
-  RpgdLane w;
-  w.s0 = a.s0 + (size_t)env * 6;
+  SweepLane w;
+  sweep_lane_env(w, p, a, env);
   w.Q = q;
-  w.x_t = a.x_t[env]; w.te = a.te[env]; w.ub0 = a.prev_in ? a.prev_in[env] : 0.0f;
-  w.cos0 = cosf(w.s0[0]); w.sin0 = sinf(w.s0[0]);
-  w.scale = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? 1.0f : 1.0f / (float)(H + 1);
-  w.clip = p.control_mode == CPMPPI_CONTROL_CLIP;
-  w.stride = Nb;
+  w.ckpt_stride = w.sub_stride = w.grad_stride = Nb;
   w.ckpt = REFINE ? a.ckpt + (size_t)env * H * 6 * Nb + tid : nullptr;
   w.grad = REFINE ? a.grad + col : nullptr;
   w.sub = REFINE ? cem_step_lds + tid : nullptr;
@@ -433,7 +384,7 @@ __global__ __launch_bounds__(BLOCK) void cem_step_kernel(const Params p, const C
     if (active) {
       cem_sample_row(p, mu, sd, a.seed, base + it, a.env_offset + env, tid, q, Nb);
       if constexpr (REFINE) {
-        (void)rpgd_sweep<COST, INTEG, true>(p, pi, ec, w, true);
+        (void)adjoint_sweep<COST, INTEG, true>(p, pi, ec, w, true);
         if (a.adam) {
           const float lr_t = lr.next(a.lr, a.beta1, a.beta2);
           rpgd_adam_row<true>(H, q, a.m + col, a.v + col, w.grad, Nb, lr_t, a.beta1, a.beta2, a.eps, a.gradmax_clip, p.lo, p.hi);
@@ -441,7 +392,7 @@ __global__ __launch_bounds__(BLOCK) void cem_step_kernel(const Params p, const C
           cem_sgd_row(H, q, w.grad, Nb, a.lr, a.gradmax_clip, p.lo, p.hi);
         }
       }
-      S = rpgd_sweep<COST, INTEG, true>(p, pi, ec, w, false);
+      S = adjoint_sweep<COST, INTEG, true>(p, pi, ec, w, false);
       if (last) {
         if (a.S_out) a.S_out[(size_t)env * N + tid] = S;
         if (a.samples_out) {
@@ -450,19 +401,8 @@ __global__ __launch_bounds__(BLOCK) void cem_step_kernel(const Params p, const C
         }
       }
     }
-    key[tid] = active ? cem_sort_key(S) : 0xFFFFFFFFu;
-    __syncthreads();
-    if (active) {
-      const uint32_t mine = key[tid];
-      uint32_t rank = 0;
-      for (uint32_t j = 0; j < N; ++j) {
-        const uint32_t kj = key[j];
-        rank += (kj < mine || (kj == mine && j < tid)) ? 1u : 0u;
-      }
-      order[rank] = tid;
-      if (last && a.order_out) a.order_out[(size_t)env * N + rank] = tid;
-    }
-    __syncthreads();                                 // the order, and every lane's row (global memory, block scope)
+    // (its closing barrier: the order, and every lane's row - global memory, block scope)
+    rank_costs(key, order, S, active, N, env, a.order_out, last);
     for (uint32_t k = tid; k < H; k += Nb)
       cem_refit_column(a.samples + ((size_t)env * H + k) * Nb, order, a.best_k, a.stdev_min, mu[k], sd[k]);
   }
@@ -478,11 +418,9 @@ __global__ __launch_bounds__(BLOCK) void cem_step_kernel(const Params p, const C
 
 template <int INTEG, bool REFINE>
 void launch_cem(uint32_t cost_id, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Params& p, const CemPtrs& a) {
-  switch (cost_id) {
-    case CPMPPI_COST_QBGM: hipLaunchKernelGGL((cem_step_kernel<COST_QBGM, INTEG, REFINE>), grid, block, lds, st, p, a); break;
-    case CPMPPI_COST_DEFAULT: hipLaunchKernelGGL((cem_step_kernel<COST_DEFAULT, INTEG, REFINE>), grid, block, lds, st, p, a); break;
-    default: hipLaunchKernelGGL((cem_step_kernel<COST_QBG, INTEG, REFINE>), grid, block, lds, st, p, a); break;
-  }
+  with_cost(cost_id, [&](auto cost) {
+    hipLaunchKernelGGL((cem_step_kernel<decltype(cost)::value, INTEG, REFINE>), grid, block, lds, st, p, a);
+  });
 }
 
 // floats per env: the samples; refining, also check-points (6), gradient, and Adam's two moments
@@ -493,38 +431,29 @@ inline size_t cem_lds_bytes(const cpmppi_handle* h, bool refine) {
   return (((size_t)(refine ? h->cfg.S * 6 : 0) + 2) * rpgd_block(h) + 2 * (size_t)h->cfg.H) * sizeof(float);
 }
 
-// rollout_grad_kernel for the handle's cost (the three costs it is built for: cpmppi_rollout_cost_grad's checks)
+// rollout_grad_kernel for the handle's cost (the three costs it is built for: sweep_check_handle)
 template <int INTEG>
 void launch_grad(uint32_t cost_id, dim3 grid, size_t lds, hipStream_t st, const Params& p, const GradPtrs& a) {
-  switch (cost_id) {
-    case CPMPPI_COST_QBGM: hipLaunchKernelGGL((rollout_grad_kernel<COST_QBGM, INTEG>), grid, dim3(BLOCK), lds, st, p, a); break;
-    case CPMPPI_COST_DEFAULT: hipLaunchKernelGGL((rollout_grad_kernel<COST_DEFAULT, INTEG>), grid, dim3(BLOCK), lds, st, p, a); break;
-    default: hipLaunchKernelGGL((rollout_grad_kernel<COST_QBG, INTEG>), grid, dim3(BLOCK), lds, st, p, a); break;
-  }
+  with_cost(cost_id, [&](auto cost) {
+    hipLaunchKernelGGL((rollout_grad_kernel<decltype(cost)::value, INTEG>), grid, dim3(BLOCK), lds, st, p, a);
+  });
 }
 
 }  // namespace
 
 void allow_large_lds_optim() {
-  // the adjoint kernel parks S x 6 x 256 sub-states in LDS (61 KB at S = 10; more substeps need the opt-in as well)
-  allow_large_lds(&rollout_grad_kernel<COST_QBGM>);
-  allow_large_lds(&rollout_grad_kernel<COST_DEFAULT>);
-  allow_large_lds(&rollout_grad_kernel<COST_QBG>);
-  allow_large_lds(&rollout_grad_kernel<COST_QBGM, PREDICTOR_ODE>);
-  allow_large_lds(&rollout_grad_kernel<COST_DEFAULT, PREDICTOR_ODE>);
-  allow_large_lds(&rollout_grad_kernel<COST_QBG, PREDICTOR_ODE>);
-  allow_large_lds(&rpgd_step_kernel<COST_QBGM, PREDICTOR_ODE_V0>);
-  allow_large_lds(&rpgd_step_kernel<COST_DEFAULT, PREDICTOR_ODE_V0>);
-  allow_large_lds(&rpgd_step_kernel<COST_QBG, PREDICTOR_ODE_V0>);
-  allow_large_lds(&rpgd_step_kernel<COST_QBGM, PREDICTOR_ODE>);
-  allow_large_lds(&rpgd_step_kernel<COST_DEFAULT, PREDICTOR_ODE>);
-  allow_large_lds(&rpgd_step_kernel<COST_QBG, PREDICTOR_ODE>);
-  allow_large_lds(&cem_step_kernel<COST_QBGM, PREDICTOR_ODE_V0, true>);
-  allow_large_lds(&cem_step_kernel<COST_DEFAULT, PREDICTOR_ODE_V0, true>);
-  allow_large_lds(&cem_step_kernel<COST_QBG, PREDICTOR_ODE_V0, true>);
-  allow_large_lds(&cem_step_kernel<COST_QBGM, PREDICTOR_ODE, true>);
-  allow_large_lds(&cem_step_kernel<COST_DEFAULT, PREDICTOR_ODE, true>);
-  allow_large_lds(&cem_step_kernel<COST_QBG, PREDICTOR_ODE, true>);
+  // every kernel that runs the adjoint parks S x 6 sub-states per lane in LDS (61 KB at S = 10 and 256 lanes; more substeps
+  // need the opt-in as well)
+  for (const uint32_t cost_id : {CPMPPI_COST_QBGM, CPMPPI_COST_DEFAULT, CPMPPI_COST_QBG})
+    with_cost(cost_id, [](auto cost) {
+      constexpr int COST = decltype(cost)::value;
+      allow_large_lds(&rollout_grad_kernel<COST, PREDICTOR_ODE_V0>);
+      allow_large_lds(&rollout_grad_kernel<COST, PREDICTOR_ODE>);
+      allow_large_lds(&rpgd_step_kernel<COST, PREDICTOR_ODE_V0>);
+      allow_large_lds(&rpgd_step_kernel<COST, PREDICTOR_ODE>);
+      allow_large_lds(&cem_step_kernel<COST, PREDICTOR_ODE_V0, true>);
+      allow_large_lds(&cem_step_kernel<COST, PREDICTOR_ODE, true>);
+    });
   // the CEM top-k sorts N (padded to a power of two) 8-byte records in LDS: 128 KB at N = 16384
   allow_large_lds(&cem_update_kernel);
 }
@@ -552,31 +481,72 @@ int cpmppi_rollout_cost(cpmppi_handle* h, uint32_t E, const float* s0, const flo
   return launch_rollout(h, prm, plan, (hipStream_t)stream, p);
 }
 
+// What the entry points that run the adjoint sweep refuse about the HANDLE, in two parts (cpmppi_rollout_cost_grad asks for the
+// pole-mass rows between them): the cost and the arithmetic, then the launch's shape - N <= BLOCK for the one-workgroup-per-env
+// steps, and `lds`, the launch's dynamic LDS bytes.  The three families word the refusals their own way.
+struct SweepWords {
+  const char* unbuilt;     // "<who>: <unbuilt> quadratic_boundary / ..."
+  const char* subject;     // "<who>: <subject> is written for the FAST arithmetic"
+  const char* rows;        // what a lane of a one-workgroup-per-env step holds; NULL: the flat launch, any N
+  const char* lds_hint;    // behind "S too large for the LDS sub-state buffer"
+};
+constexpr SweepWords GRAD_WORDS{"no adjoint for", "the adjoint", nullptr, " (<= 25)"};
+constexpr SweepWords RPGD_WORDS{"no adjoint for", "the adjoint", "plans", ""};
+constexpr SweepWords CEM_WORDS{"not built for", "the sweep", "samples", ""};       // (cem also runs without the adjoint)
+
+static int sweep_check_handle(cpmppi_handle* h, const char* who, const SweepWords& words) {
+  const std::string w(who);
+  if (h->prm.cost_id == CPMPPI_COST_LEGACY) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": plugin costs only");
+  if (h->prm.qb_mode != 0u)
+    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": " + words.unbuilt + " quadratic_boundary / quadratic_boundary_nonconvex "
+                                           "(built: quadratic_boundary_grad_minimal, default, quadratic_boundary_grad)");
+  if (h->cfg.math_mode != CPMPPI_MATH_FAST)
+    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": " + words.subject + " is written for the FAST arithmetic");
+  return CPMPPI_OK;
+}
+
+static int sweep_check_shape(cpmppi_handle* h, const char* who, const SweepWords& words, size_t lds) {
+  const std::string w(who);
+  if (words.rows && h->cfg.N > (uint32_t)BLOCK)
+    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": one workgroup per env holds at most " + std::to_string(BLOCK) + " " + words.rows +
+                                           " (N = " + std::to_string(h->cfg.N) + ")");
+  if (lds > 150 * 1024) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": S too large for the LDS sub-state buffer" + words.lds_hint);
+  return CPMPPI_OK;
+}
+
+// Grows a device workspace of the handle to `need` floats (the contents are not kept).
+static int grow_workspace(cpmppi_handle* h, float*& ws, size_t& floats, size_t need) {
+  if (floats >= need) return CPMPPI_OK;
+  if (ws) (void)hipFree(ws);
+  ws = nullptr; floats = 0;
+  CPMPPI_HIP(h, hipMalloc(&ws, need * sizeof(float)));
+  floats = need;
+  return CPMPPI_OK;
+}
+
+// No allocation inside a capture: a step whose workspace is not reserved (`reserve`: the call that does it) is refused there.
+static int refuse_unreserved_capture(cpmppi_handle* h, hipStream_t s, const char* who, const char* reserve) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  const bool capturing = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+  (void)hipGetLastError();
+  if (!capturing) return CPMPPI_OK;
+  return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": the stream is being captured and the workspace is not reserved (call " +
+                                         reserve + " before the capture)");
+}
+
 int cpmppi_rollout_cost_grad(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs,
                              const float* target_position, const float* target_equilibrium, const float* L,
                              const float* previous_input, float* S_out, float* grad_out, void* stream) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
   if (E == 0 || E > h->cfg.E || !s0 || !inputs || !target_position || !target_equilibrium || !grad_out)
     return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: bad argument");
-  if (h->prm.cost_id == CPMPPI_COST_LEGACY)
-    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: plugin costs only");
-  if (h->prm.qb_mode != 0u)
-    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: no adjoint for quadratic_boundary / quadratic_boundary_nonconvex "
-                                       "(built: quadratic_boundary_grad_minimal, default, quadratic_boundary_grad)");
-  if (h->cfg.math_mode != CPMPPI_MATH_FAST)
-    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: the adjoint is written for the FAST arithmetic");
-  if (!pole_mass_rows_cover(h, E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_rollout_cost_grad", h, E));
   const size_t lds = (size_t)h->cfg.S * 6 * BLOCK * sizeof(float);
-  if (lds > 150 * 1024) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_grad: S too large for the LDS sub-state buffer (<= 25)");
+  if (const int rc = sweep_check_handle(h, "cpmppi_rollout_cost_grad", GRAD_WORDS)) return rc;
+  if (!pole_mass_rows_cover(h, E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_rollout_cost_grad", h, E));
+  if (const int rc = sweep_check_shape(h, "cpmppi_rollout_cost_grad", GRAD_WORDS, lds)) return rc;
   CPMPPI_ON_DEVICE(h);
   const size_t B = (size_t)E * h->cfg.N;
-  const size_t need = (size_t)h->cfg.H * 6 * (size_t)h->cfg.E * h->cfg.N;
-  if (h->grad_ckpt_floats < need) {
-    if (h->grad_ckpt) (void)hipFree(h->grad_ckpt);
-    h->grad_ckpt = nullptr; h->grad_ckpt_floats = 0;
-    CPMPPI_HIP(h, hipMalloc(&h->grad_ckpt, need * sizeof(float)));
-    h->grad_ckpt_floats = need;
-  }
+  if (const int rc = grow_workspace(h, h->grad_ckpt, h->grad_ckpt_floats, (size_t)h->cfg.H * 6 * (size_t)h->cfg.E * h->cfg.N)) return rc;
   GradPtrs a{s0, inputs, target_position, target_equilibrium, L, previous_input, h->grad_ckpt, S_out, grad_out, E, h->m_pole_rows};
   const auto launch = h->cfg.ode_predictor == CPMPPI_ODE_CROMER ? launch_grad<PREDICTOR_ODE> : launch_grad<PREDICTOR_ODE_V0>;
   launch(h->prm.cost_id, dim3((unsigned)((B + BLOCK - 1) / BLOCK)), lds, (hipStream_t)stream, h->prm, a);
@@ -598,34 +568,13 @@ int cpmppi_adam_step(cpmppi_handle* h, uint32_t E, float* Q, const float* grad, 
   return launched(h);
 }
 
-// what cpmppi_rpgd_step and cpmppi_rpgd_reserve refuse about the HANDLE (cpmppi_rollout_cost_grad's list, plus the block)
-static int rpgd_check_handle(cpmppi_handle* h, const char* who) {
-  const std::string w(who);
-  if (h->prm.cost_id == CPMPPI_COST_LEGACY) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": plugin costs only");
-  if (h->prm.qb_mode != 0u)
-    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": no adjoint for quadratic_boundary / quadratic_boundary_nonconvex "
-                                           "(built: quadratic_boundary_grad_minimal, default, quadratic_boundary_grad)");
-  if (h->cfg.math_mode != CPMPPI_MATH_FAST) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": the adjoint is written for the FAST arithmetic");
-  if (h->cfg.N > (uint32_t)BLOCK)
-    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": one workgroup per env holds at most " + std::to_string(BLOCK) + " plans (N = " +
-                                           std::to_string(h->cfg.N) + ")");
-  const size_t lds = ((size_t)h->cfg.S * 6 + 2) * rpgd_block(h) * sizeof(float);
-  if (lds > 150 * 1024) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": S too large for the LDS sub-state buffer");
-  return CPMPPI_OK;
-}
-
 int cpmppi_rpgd_reserve(cpmppi_handle* h, uint32_t E) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
   if (E == 0 || E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_reserve: bad argument (0 < E <= config.E)");
-  if (const int rc = rpgd_check_handle(h, "cpmppi_rpgd_reserve")) return rc;
+  if (const int rc = sweep_check_handle(h, "cpmppi_rpgd_reserve", RPGD_WORDS)) return rc;
+  if (const int rc = sweep_check_shape(h, "cpmppi_rpgd_reserve", RPGD_WORDS, rpgd_lds_bytes(h))) return rc;
   CPMPPI_ON_DEVICE(h);
-  const size_t need = rpgd_floats(h, E);
-  if (h->rpgd_ws_floats >= need) return CPMPPI_OK;
-  if (h->rpgd_ws) (void)hipFree(h->rpgd_ws);
-  h->rpgd_ws = nullptr; h->rpgd_ws_floats = 0;
-  CPMPPI_HIP(h, hipMalloc(&h->rpgd_ws, need * sizeof(float)));
-  h->rpgd_ws_floats = need;
-  return CPMPPI_OK;
+  return grow_workspace(h, h->rpgd_ws, h->rpgd_ws_floats, rpgd_floats(h, E));
 }
 
 int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* a, void* stream) {
@@ -643,18 +592,13 @@ int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* a, void* stream) 
   if (a->keep_k == 0 || a->keep_k > h->cfg.N) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: bad argument (0 < keep_k <= N)");
   if (a->shift > h->cfg.H) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: shift exceeds the horizon");
   if (a->distribution > CPMPPI_RPGD_UNIFORM) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: unknown distribution");
-  if (const int rc = rpgd_check_handle(h, "cpmppi_rpgd_step")) return rc;
+  if (const int rc = sweep_check_handle(h, "cpmppi_rpgd_step", RPGD_WORDS)) return rc;
+  if (const int rc = sweep_check_shape(h, "cpmppi_rpgd_step", RPGD_WORDS, rpgd_lds_bytes(h))) return rc;
   if (!pole_mass_rows_cover(h, a->E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_rpgd_step", h, a->E));
   CPMPPI_ON_DEVICE(h);
   hipStream_t s = (hipStream_t)stream;
   if (h->rpgd_ws_floats < rpgd_floats(h, a->E)) {
-    // no allocation inside a capture: the workspace is reserved before (cpmppi_rpgd_reserve)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    (void)hipGetLastError();
-    if (capturing)
-      return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: the stream is being captured and the workspace is not reserved "
-                                         "(call cpmppi_rpgd_reserve before the capture)");
+    if (const int rc = refuse_unreserved_capture(h, s, "cpmppi_rpgd_step", "cpmppi_rpgd_reserve")) return rc;
     if (const int rc = cpmppi_rpgd_reserve(h, a->E)) return rc;
   }
   const uint32_t Nb = rpgd_block(h);
@@ -670,43 +614,22 @@ int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* a, void* stream) 
   p.lr = a->learning_rate; p.beta1 = a->beta1; p.beta2 = a->beta2; p.eps = a->epsilon; p.gradmax_clip = a->gradmax_clip;
   p.sample_mean = a->sample_mean; p.uniform_lo = a->uniform_lo; p.uniform_hi = a->uniform_hi;
   p.Q_out = a->Q_out; p.S_out = a->S_out; p.plan_out = a->plan_out; p.order_out = a->order_out;
-  const size_t lds = ((size_t)h->cfg.S * 6 + 2) * Nb * sizeof(float);
   const auto launch = h->cfg.ode_predictor == CPMPPI_ODE_CROMER ? launch_rpgd<PREDICTOR_ODE> : launch_rpgd<PREDICTOR_ODE_V0>;
-  launch(h->prm.cost_id, dim3(a->E), dim3(Nb), lds, s, h->prm, p);
+  launch(h->prm.cost_id, dim3(a->E), dim3(Nb), rpgd_lds_bytes(h), s, h->prm, p);
   CPMPPI_HIP(h, hipGetLastError());
   if (a->count_dev) hipLaunchKernelGGL(rpgd_count_kernel, dim3(1), dim3(1), 0, s, (unsigned long long*)a->count_dev);
   return launched(h);
-}
-
-// what cpmppi_cem_step and cpmppi_cem_reserve refuse about the HANDLE: rpgd_check_handle's list, the LDS bound with the refit's
-// mean and stdev on top (without refinement no sub-state buffer: S is free)
-static int cem_check_handle(cpmppi_handle* h, const char* who, bool refine) {
-  const std::string w(who);
-  if (h->prm.cost_id == CPMPPI_COST_LEGACY) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": plugin costs only");
-  if (h->prm.qb_mode != 0u)
-    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": not built for quadratic_boundary / quadratic_boundary_nonconvex "
-                                           "(built: quadratic_boundary_grad_minimal, default, quadratic_boundary_grad)");
-  if (h->cfg.math_mode != CPMPPI_MATH_FAST) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": the sweep is written for the FAST arithmetic");
-  if (h->cfg.N > (uint32_t)BLOCK)
-    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": one workgroup per env holds at most " + std::to_string(BLOCK) + " samples (N = " +
-                                           std::to_string(h->cfg.N) + ")");
-  if (cem_lds_bytes(h, refine) > 150 * 1024) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": S too large for the LDS sub-state buffer");
-  return CPMPPI_OK;
 }
 
 int cpmppi_cem_reserve(cpmppi_handle* h, uint32_t E, uint32_t refine) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
   if (E == 0 || E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_reserve: bad argument (0 < E <= config.E)");
   if (refine > CPMPPI_CEM_REFINE_ADAM) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_reserve: unknown refine kind");
-  if (const int rc = cem_check_handle(h, "cpmppi_cem_reserve", refine != CPMPPI_CEM_REFINE_NONE)) return rc;
+  const bool refining = refine != CPMPPI_CEM_REFINE_NONE;
+  if (const int rc = sweep_check_handle(h, "cpmppi_cem_reserve", CEM_WORDS)) return rc;
+  if (const int rc = sweep_check_shape(h, "cpmppi_cem_reserve", CEM_WORDS, cem_lds_bytes(h, refining))) return rc;
   CPMPPI_ON_DEVICE(h);
-  const size_t need = cem_floats(h, E, refine != CPMPPI_CEM_REFINE_NONE);
-  if (h->cem_ws_floats >= need) return CPMPPI_OK;
-  if (h->cem_ws) (void)hipFree(h->cem_ws);
-  h->cem_ws = nullptr; h->cem_ws_floats = 0;
-  CPMPPI_HIP(h, hipMalloc(&h->cem_ws, need * sizeof(float)));
-  h->cem_ws_floats = need;
-  return CPMPPI_OK;
+  return grow_workspace(h, h->cem_ws, h->cem_ws_floats, cem_floats(h, E, refining));
 }
 
 int cpmppi_cem_step(cpmppi_handle* h, const cpmppi_cem_args* a, void* stream) {
@@ -725,18 +648,13 @@ int cpmppi_cem_step(cpmppi_handle* h, const cpmppi_cem_args* a, void* stream) {
   if (a->shift > h->cfg.H) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: shift exceeds the horizon");
   if (a->refine > CPMPPI_CEM_REFINE_ADAM) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: unknown refine kind");
   const bool refine = a->refine != CPMPPI_CEM_REFINE_NONE;
-  if (const int rc = cem_check_handle(h, "cpmppi_cem_step", refine)) return rc;
+  if (const int rc = sweep_check_handle(h, "cpmppi_cem_step", CEM_WORDS)) return rc;
+  if (const int rc = sweep_check_shape(h, "cpmppi_cem_step", CEM_WORDS, cem_lds_bytes(h, refine))) return rc;
   if (!pole_mass_rows_cover(h, a->E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_cem_step", h, a->E));
   CPMPPI_ON_DEVICE(h);
   hipStream_t s = (hipStream_t)stream;
   if (h->cem_ws_floats < cem_floats(h, a->E, refine)) {
-    // no allocation inside a capture: the workspace is reserved before (cpmppi_cem_reserve)
-    hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-    const bool capturing = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-    (void)hipGetLastError();
-    if (capturing)
-      return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_step: the stream is being captured and the workspace is not reserved "
-                                         "(call cpmppi_cem_reserve before the capture)");
+    if (const int rc = refuse_unreserved_capture(h, s, "cpmppi_cem_step", "cpmppi_cem_reserve")) return rc;
     if (const int rc = cpmppi_cem_reserve(h, a->E, a->refine)) return rc;
   }
   const uint32_t Nb = rpgd_block(h);
