@@ -29,7 +29,8 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_groups_create", "cpmppi_groups_destroy", "cpmppi_groups_count", "cpmppi_groups_slice", "cpmppi_groups_handle",
            "cpmppi_groups_stream", "cpmppi_groups_fork", "cpmppi_groups_join", "cpmppi_groups_run", "cpmppi_groups_last_error",
            "cpmppi_comm_set_stamped", "cpmppi_groups_comm_init", "cpmppi_groups_run_gather", "cpmppi_set_pole_mass_rows",
-           "cpmppi_rpgd_reserve", "cpmppi_rpgd_step", "cpmppi_cem_reserve", "cpmppi_cem_step", "cpmppi_rollout_cost_gru")
+           "cpmppi_rpgd_reserve", "cpmppi_rpgd_step", "cpmppi_cem_reserve", "cpmppi_cem_step", "cpmppi_rollout_cost_gru",
+           "cpmppi_rollout_cost_grad_gru")
 COMM_ID_BYTES, COMM_SLOTS, GATHER_STAMP_FLOATS = 128, 4, 4
 
 
@@ -173,6 +174,7 @@ def load():
     lib.cpmppi_gru_predict.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost_gru.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
+    lib.cpmppi_rollout_cost_grad_gru.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost_grad.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_adam_step.argtypes = [vp, u32, vp, vp, vp, vp, u32, f, f, f, f, f, vp]
     lib.cpmppi_sgd_step.argtypes = [vp, u32, vp, vp, f, f, vp]

@@ -4,8 +4,9 @@ bookkeeping), the ``dt`` / ``num_envs`` / predictor part of ``configure``, and t
 attributes) and epilogue (controls -> [1] / [E,1]).  The optimizers' own signatures, defaults and attributes are theirs.
 
 The neural predictor (``gru_model=`` / a ``GRU-6IN-32H1-32H2-5OUT*`` specification) is settled here too, for the optimizers that
-run on it - mppi in its fused step, cem, cem-gmm and random-action through the cost-only GRU rollout - and for those that refuse
-it by name: which of specification and model selects it, the model's upload, the memory ``h`` [E,2,32] per env and its hand-over
+run on it - mppi in its fused step, cem, cem-gmm and random-action through the cost-only GRU rollout, the gradient family
+(gradient, rpgd, cem-naive-grad, cem-grad-bharadhwaj) through the GRU adjoint when asked with ``gru_adjoint=True`` - and for
+those that refuse it by name: which of specification and model selects it, the model's upload, the memory ``h`` [E,2,32] per env and its hand-over
 from one control step to the next.
 """
 import os
@@ -37,10 +38,13 @@ class _OptimizerBase:
 
     def __init__(self, cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                  variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
-                 intermediate_steps, gru_model=None, **config):
+                 intermediate_steps, gru_model=None, gru_adjoint=False, **config):
         """``config``: the remaining MPPIConfig fields, which differ from optimizer to optimizer.  ``gru_model``: dict of
-        GRU-6IN-32H1-32H2-5OUT weights or a model-folder path -> the neural predictor in the rollout loop."""
-        if gru_model is not None and self._gru_refusal:
+        GRU-6IN-32H1-32H2-5OUT weights or a model-folder path -> the neural predictor in the rollout loop.  ``gru_adjoint``:
+        the opt-in of a class that needs the cost's gradient (one with a ``_gru_refusal``) to the GRU adjoint,
+        cpmppi_rollout_cost_grad_gru; without it such a class refuses the network as before."""
+        self.gru_adjoint = bool(gru_adjoint)
+        if gru_model is not None and self._gru_refusal and not self.gru_adjoint:
             raise NotImplementedError(self._gru_refusal)
         self.gru_model = gru_model
         self.h = None                                      # its memory per env [E,2,32] (controller_mppi_cartpole.py:566-567 update)
@@ -81,7 +85,7 @@ class _OptimizerBase:
         """Specification and ``gru_model`` together -> does the network predict?  A specification without a model and a model
         beside an ODE specification are errors, a model alone selects the GRU; a class without a GRU path refuses both."""
         neural = is_gru_specification(predictor_specification)
-        if (neural or self.gru_model is not None) and self._gru_refusal:
+        if (neural or self.gru_model is not None) and self._gru_refusal and not self.gru_adjoint:
             raise NotImplementedError(self._gru_refusal)
         if isinstance(self.gru_model, (str, bytes)) or hasattr(self.gru_model, "__fspath__"):
             from .model_folder import load_gru_model          # an SI_Toolkit model folder (net-info, normalisation, weights)
@@ -93,6 +97,18 @@ class _OptimizerBase:
             raise ValueError(f"gru_model was given but predictor_specification={predictor_specification!r} selects the ODE "
                              "predictor: the model would be ignored")
         return self.gru_model is not None
+
+    def _check_gru_adjoint(self, fused):
+        """What ``gru_adjoint=True`` cannot be combined with (the gradient family's constructors ask): the fused control steps
+        and the one cost of the ODE adjoint that the GRU kernels do not have."""
+        if not self.gru_adjoint:
+            return
+        if fused:
+            raise ValueError("gru_adjoint=True with fused=True: cpmppi_rpgd_step and cpmppi_cem_step integrate the ODE; the GRU "
+                             "adjoint (cpmppi_rollout_cost_grad_gru) runs in the staged step, fused=False")
+        if self.cfg.cost_function_specification == "quadratic_boundary_grad":
+            raise ValueError("gru_adjoint=True with quadratic_boundary_grad: the GRU kernels are built for "
+                             "quadratic_boundary_grad_minimal and default")
 
     def _attach_gru(self, neural):
         """The new engine gets the model, every env a zero memory; without the network there is none."""

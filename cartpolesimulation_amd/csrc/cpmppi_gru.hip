@@ -7,9 +7,13 @@
 //                                           (plugin costs); launched by step_impl through launch_gru_rollout.
 //   gru_cost_only_kernel<COST,F16>          costs of GIVEN input plans under the GRU predictor, nothing of the MPPI update: the
 //                                           building block of the sampling optimizers (cem, cem-gmm, random-action).
-// The two rollout kernels share one rollout (GruRollout: gru_rollout_init, gru_rollout_step, gru_rollout_total) and differ in where
+//   gru_grad_forward_kernel<COST,F16>       the cost-only rollout that also parks, per control step, what the reverse sweep needs;
+//   gru_grad_reverse_kernel<COST>           the reverse sweep through head, layer 2 and layer 1 (exact f32 MFMA on a transposed weights
+//                                           image): d cost / d inputs of GIVEN plans - the building block of gradient, rpgd and the
+//                                           CEM + gradient hybrids over the GRU (gru_adjoint=True).
+// The rollout kernels share one rollout (GruRollout: gru_rollout_init, gru_rollout_step, gru_rollout_total) and differ in where
 // a step's input comes from and in what becomes of the costs; gru_predict_kernel runs the exact cell (gru_step) on its own.
-// Entry points: cpmppi_set_gru, cpmppi_gru_predict, cpmppi_rollout_cost_gru; -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write
+// Entry points: cpmppi_set_gru, cpmppi_gru_predict, cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru; -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write
 // g_gru_stamp_sum are this unit's).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -21,6 +25,7 @@
 #include "cpmppi_internal.hpp"
 #include "cpmppi_gru.hpp"
 #include "cpmppi_gru16.hpp"
+#include "cpmppi_grad.hpp"       // (stage_qbgm_grad, stage_default_grad)
 
 using namespace cpmppi_k;
 
@@ -339,6 +344,253 @@ void launch_gru_cost_only(cpmppi_handle* h, const GruCostPtrs& a, uint32_t E, hi
                           h->prm, a, h->gru_norm, (const float*)h->gru_image);
 }
 
+// ---- cost and gradient: cpmppi_rollout_cost_grad_gru = gru_grad_forward_kernel, then gru_grad_reverse_kernel, on one stream.
+// Two launches rather than one kernel that swaps its LDS image between the sweeps: each keeps the cost-only kernel's shape (one
+// barrier, behind the image load; a wave without a rollout leaves at once) and the forward half IS the cost-only kernel plus
+// its check-point stores.  The sweeps meet in global memory either way.
+struct GruGradPtrs {
+  const float* s0;       // [E,6]
+  const float* inputs;   // [E,N,H]
+  const float* x_t;      // [E] target position
+  const float* te;       // [E] target equilibrium
+  const float* h0;       // [E,2,32] or NULL = 0
+  float* S_out;          // [E,N] or NULL
+  float* grad;           // [E,N,H]
+  float* ckpt;           // [H][rows][GRU_CKPT_FLOATS]: after control step k, hidden tiles and fed-back outputs of every rollout
+  size_t rows;           // E N of this launch
+  uint32_t nb;           // blocks per env
+};
+constexpr size_t GRU_GRAD_REVERSE_LDS = ((size_t)GRU_IMAGE_FLOATS + GRU_T_IMAGE_FLOATS) * sizeof(float);   // 98 208 B: opt-in
+
+typedef float f4v __attribute__((ext_vector_type(4)));
+
+// A lane's 16 registers of a hidden tile <-> 16 consecutive floats of a check-point (4 x 16 bytes).
+__device__ __forceinline__ void gru_park_tile(float* dst, const f16v& h) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) reinterpret_cast<f4v*>(dst)[q] = f4v{h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]};
+}
+__device__ __forceinline__ f16v gru_fetch_tile(const float* src) {
+  f16v h;
+#pragma unroll
+  for (int q = 0; q < 4; ++q) {
+    const f4v t = reinterpret_cast<const f4v*>(src)[q];
+    h[4 * q] = t.x; h[4 * q + 1] = t.y; h[4 * q + 2] = t.z; h[4 * q + 3] = t.w;
+  }
+  return h;
+}
+
+// Forward sweep: gru_cost_only_kernel (same set-up, step and epilogue, in the handle's math mode) that parks, after every control
+// step but the last, what the reverse sweep starts from - the last step's cell produces a state that no stage costs.
+template <int COST, bool F16>
+__global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_grad_forward_kernel(const Params p, const GruGradPtrs a, const GruNorm nm,
+                                                                                 const float* __restrict__ image) {
+  extern __shared__ float lds[];                           // GRU image only
+  gru_load_image(lds, image, GRU_ROLLOUT_IMAGE_FLOATS<F16>);   // the kernel's only barrier
+  const uint32_t env = blockIdx.x / a.nb, blk = blockIdx.x % a.nb;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = lane & 31u;
+  const uint32_t row0 = blk * GRU_ROLLOUTS_PER_BLOCK + wave * 32;
+  if (row0 >= p.N) return;                                 // (wave-uniform) a tile without a rollout
+  const uint32_t n = row0 + c;
+  const bool live = n < p.N, owner = lane < 32 && live;
+  const uint32_t nn = live ? n : 0;
+  const uint32_t H = p.H;
+  const float x_t = a.x_t[env], te = a.te[env];
+  const float* __restrict__ s0 = a.s0 + (size_t)env * 6;
+  const float* __restrict__ in = a.inputs + ((size_t)env * p.N + nn) * H;
+  GruRollout ro;
+  gru_rollout_init<F16>(ro, lds, s0, lane, a.h0 ? a.h0 + (size_t)env * 64 : nullptr, a.h0 ? a.h0 + (size_t)env * 64 + 32 : nullptr);
+  const bool half1 = lane >= 32;
+  float* ck = a.ckpt + ((size_t)env * p.N + nn) * GRU_CKPT_FLOATS;        // the rollout's check-point of step 0
+  const size_t ck_step = a.rows * GRU_CKPT_FLOATS;
+  GruStamps none;
+  float u_next = in[0];
+  for (uint32_t k = 0; k < H; ++k) {
+    const float ur = u_next;
+    if (k + 1 < H) u_next = in[k + 1];                     // in flight during this step's cell
+    gru_rollout_step<COST, F16>(ro, lds, s0, x_t, te, lane, c, half1, p, nm, k, ur, none, [](float) {});
+    if (k + 1 < H && live) {                               // rows >= N are never written
+      gru_park_tile(ck + (half1 ? 16 : 0), F16 ? ro.gs.h1 : ro.h1);
+      gru_park_tile(ck + 32 + (half1 ? 16 : 0), F16 ? ro.gs.h2 : ro.h2);
+      if (!half1) *reinterpret_cast<f4v*>(ck + 64) = f4v{ro.x[0], ro.x[1], ro.x[2], ro.x[3]};
+      else ck[68] = ro.x[0];
+    }
+    ck += ck_step;
+  }
+  const float S_total = gru_rollout_total<COST>(ro, x_t, p);
+  if (a.S_out && owner) a.S_out[(size_t)env * p.N + n] = S_total;
+}
+
+// One GRU layer of the reverse sweep for the wave's 32 rollouts.  Recomputes the layer's gates (exact f32, the order of gru_layer)
+// from its input tile x (KX k-steps) and the hidden tile hp the step began with, then turns dh - in: the adjoint of the step's
+// new hidden state, out: the direct part z * dh of the adjoint of hp - into the adjoints of the four pre-activation tiles: r, z,
+// n's input part and n's hidden part.
+template <int KX>
+__device__ __forceinline__ void gru_layer_reverse(const float* lds, int fx, int fh, int b0, const f16v& x, const f16v& hp,
+                                                  uint32_t lane, f16v& dh, f16v& dar, f16v& daz, f16v& danx, f16v& danh) {
+  f16v ar = gru_mm<KX>(gru_bias_v(lds, b0 + 0, lane), lds + (fx + 0 * KX) * 64, x, lane);
+  f16v az = gru_mm<KX>(gru_bias_v(lds, b0 + 1, lane), lds + (fx + 1 * KX) * 64, x, lane);
+  const f16v anx = gru_mm<KX>(gru_bias_v(lds, b0 + 2, lane), lds + (fx + 2 * KX) * 64, x, lane);
+  ar = gru_mm<16>(ar, lds + (fh + 0) * 64, hp, lane);
+  az = gru_mm<16>(az, lds + (fh + 16) * 64, hp, lane);
+  const f16v anh = gru_mm<16>(gru_bias_v(lds, b0 + 3, lane), lds + (fh + 32) * 64, hp, lane);
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const float r = gru_sigmoid(ar[v]);
+    const float z = gru_sigmoid(az[v]);
+    const float n = gru_tanh(__builtin_fmaf(r, anh[v], anx[v]));
+    const float d = dh[v];
+    const float dn = d * (1.0f - z);                          // h = (1 - z) n + z hp
+    const float dz = d * (hp[v] - n);
+    const float dan = dn * __builtin_fmaf(-n, n, 1.0f);       // n = tanh(anx + r anh)
+    danx[v] = dan;
+    danh[v] = dan * r;
+    dar[v] = (dan * anh[v]) * (r * (1.0f - r));
+    daz[v] = dz * (z * (1.0f - z));
+    dh[v] = d * z;
+  }
+}
+
+// Reverse sweep, exact-f32 MFMA in both math modes.  Per control step k = H-2 .. 0 (the cell of step H-1 feeds no cost), from the
+// check-points of steps k (outputs, layer-1 hidden tile) and k-1 (both hidden tiles, outputs = the input features; k = 0: the
+// env's memory and state): head adjoint, layer-2 cell, layer-1 cell, each layer's gates recomputed right before its adjoint.
+// Row 5 of the input adjoint is d/dQ[k]; rows 0..4 are the feedback into the outputs of step k-1, which also collect the
+// partials of stage k through the de-normalisation.  LDS: the forward f32 image (gates) and the transposed one.  A column
+// beyond N repeats the env's rollout 0 and is never written.
+template <int COST>
+__global__ __launch_bounds__(BLOCK, 1) void gru_grad_reverse_kernel(const Params p, const GruGradPtrs a, const GruNorm nm,
+                                                                    const float* __restrict__ image,
+                                                                    const float* __restrict__ image_t) {
+  extern __shared__ float lds[];                           // forward f32 image, then the transposed image
+  float* ldst = lds + GRU_IMAGE_FLOATS;
+  for (int i = threadIdx.x; i < GRU_T_IMAGE_FLOATS; i += BLOCK) ldst[i] = image_t[i];
+  gru_load_image(lds, image, GRU_IMAGE_FLOATS);            // the kernel's only barrier
+  const uint32_t env = blockIdx.x / a.nb, blk = blockIdx.x % a.nb;
+  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = lane & 31u;
+  const uint32_t row0 = blk * GRU_ROLLOUTS_PER_BLOCK + wave * 32;
+  if (row0 >= p.N) return;                                 // (wave-uniform) a tile without a rollout
+  const uint32_t n = row0 + c;
+  const bool live = n < p.N, half1 = lane >= 32, owner = !half1 && live;
+  const uint32_t nn = live ? n : 0;
+  const uint32_t H = p.H;
+  const float x_t = a.x_t[env], te = a.te[env];
+  const float* __restrict__ s0 = a.s0 + (size_t)env * 6;
+  const float* __restrict__ in = a.inputs + ((size_t)env * p.N + nn) * H;
+  float* __restrict__ g = a.grad + ((size_t)env * p.N + nn) * H;
+  const size_t ck_step = a.rows * GRU_CKPT_FLOATS;
+  const uint32_t hoff = half1 ? 16u : 0u;                  // the lane's 16 slots inside a hidden tile
+  const float scale = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? 1.0f : 1.0f / (float)(p.H + 1);
+  const bool clip = p.control_mode == CPMPPI_CONTROL_CLIP;
+  auto stage_u = [&](float u) __attribute__((always_inline)) -> float {      // d stage / d u: the direct control term
+    if constexpr (COST == COST_QBGM) return stage_qbgm_grad(p, 0.0f, 1.0f, 0.0f, u, x_t, te).u;
+    else return stage_default_grad(p, 0.0f, 1.0f, u, x_t, te).u;
+  };
+  {                                                        // the last input: its cell is never costed
+    const float q = in[H - 1];
+    const bool clipped = clip && (q < p.lo || q > p.hi);
+    if (owner) g[H - 1] = clipped ? 0.0f : scale * stage_u(q);
+  }
+  if (H < 2) return;
+
+  f16v dh1, dh2;                                           // adjoints of the hidden tiles behind step k
+#pragma unroll
+  for (int v = 0; v < 16; ++v) { dh1[v] = 0.0f; dh2[v] = 0.0f; }
+  float dfb[4] = {0.0f, 0.0f, 0.0f, 0.0f};                 // feedback: adjoint of step k's outputs through the input tile of step k + 1
+  const float* ck = a.ckpt + ((size_t)env * p.N + nn) * GRU_CKPT_FLOATS + (size_t)(H - 2) * ck_step;   // check-point of step k
+  for (uint32_t k = H - 1; k-- > 0; ck -= ck_step) {
+    const float* ckp = ck - ck_step;                       // check-point of step k - 1 (k = 0: not read)
+    const float q = in[k];
+    const bool clipped = clip && (q < p.lo || q > p.hi);
+    const float ur = clip ? clamp_(q, p.lo, p.hi) : q;
+    // ---- outputs of step k = state of stage k + 1: its partials through the de-normalisation, plus the feedback
+    f16v gout;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) gout[v] = 0.0f;
+    {
+      const f4v o = *reinterpret_cast<const f4v*>(ck + 64);
+      const float w_ang = __builtin_fmaf(o.x, nm.out_scale[0], nm.out_shift[0]);
+      const float ca = __builtin_fmaf(o.y, nm.out_scale[1], nm.out_shift[1]);
+      const float sa = __builtin_fmaf(o.z, nm.out_scale[2], nm.out_shift[2]);
+      const float x = __builtin_fmaf(o.w, nm.out_scale[3], nm.out_shift[3]);
+      const float rr = __builtin_fmaf(ca, ca, sa * sa);
+      const float ir = rr > 0.0f ? __builtin_amdgcn_rsqf(rr) : 0.0f;
+      const float cosang = rr > 0.0f ? ca * ir : 1.0f;     // cos(atan2(s, c)) = c / |(c, s)|, differentiated through both
+      const float ir3 = ir * ir * ir;
+      StageGrad sg;
+      if constexpr (COST == COST_QBGM) sg = stage_qbgm_grad(p, x, cosang, w_ang, 0.0f, x_t, te);
+      else sg = stage_default_grad(p, x, cosang, 0.0f, x_t, te);
+      const float gc = scale * sg.cosang;
+      if (!half1) {
+        gout[0] = __builtin_fmaf(scale * sg.w, nm.out_scale[0], dfb[0]);
+        gout[1] = __builtin_fmaf(gc * (sa * sa * ir3), nm.out_scale[1], dfb[1]);
+        gout[2] = __builtin_fmaf(gc * (-(ca * sa) * ir3), nm.out_scale[2], dfb[2]);
+        gout[3] = __builtin_fmaf(scale * sg.x, nm.out_scale[3], dfb[3]);
+      } else {
+        gout[0] = dfb[0];                                  // positionD (row 4): no stage costs it
+      }
+    }
+    f16v dar, daz, danx, danh;
+    // ---- head adjoint, then the layer-2 cell: input = the layer-1 hidden tile of step k, hidden = layer 2's of step k - 1
+    {
+      const f16v h1 = gru_fetch_tile(ck + hoff);
+      const f16v h2p = k ? gru_fetch_tile(ckp + 32 + hoff) : gru_load_hidden(a.h0 ? a.h0 + (size_t)env * 64 + 32 : nullptr, lane);
+      dh2 = gru_mm<4>(dh2, ldst + GT_HEAD * 64, gout, lane);
+      gru_layer_reverse<16>(lds, GF_L2X, GF_L2H, 4, h1, h2p, lane, dh2, dar, daz, danx, danh);
+    }
+    dh1 = gru_mm<16>(dh1, ldst + (GT_L2X + 0) * 64, dar, lane);
+    dh1 = gru_mm<16>(dh1, ldst + (GT_L2X + 16) * 64, daz, lane);
+    dh1 = gru_mm<16>(dh1, ldst + (GT_L2X + 32) * 64, danx, lane);
+    dh2 = gru_mm<16>(dh2, ldst + (GT_L2H + 0) * 64, dar, lane);
+    dh2 = gru_mm<16>(dh2, ldst + (GT_L2H + 16) * 64, daz, lane);
+    dh2 = gru_mm<16>(dh2, ldst + (GT_L2H + 32) * 64, danh, lane);
+    __builtin_amdgcn_sched_barrier(0);
+    // ---- the layer-1 cell: input = the step's feature tile, hidden = layer 1's of step k - 1
+    {
+      f16v xt;
+      if (k == 0) {
+        xt = gru_input_tile(nm, s0, ur, lane);
+      } else {
+#pragma unroll
+        for (int v = 0; v < 16; ++v) xt[v] = 0.0f;
+        if (!half1) {
+          const f4v o = *reinterpret_cast<const f4v*>(ckp + 64);
+          xt[0] = o.x; xt[1] = o.y; xt[2] = o.z; xt[3] = o.w;
+        } else {
+          xt[0] = ckp[68];
+          xt[1] = __builtin_fmaf(ur, nm.in_scale[0], nm.in_shift[0]);
+        }
+      }
+      const f16v h1p = k ? gru_fetch_tile(ckp + hoff) : gru_load_hidden(a.h0 ? a.h0 + (size_t)env * 64 : nullptr, lane);
+      gru_layer_reverse<4>(lds, GF_L1X, GF_L1H, 0, xt, h1p, lane, dh1, dar, daz, danx, danh);
+    }
+    // ---- the input adjoint (rows 0..4: feedback, row 5: d/dQ) and the hidden adjoint
+    f16v dx;
+#pragma unroll
+    for (int v = 0; v < 16; ++v) dx[v] = 0.0f;
+    dx = gru_mm<16>(dx, ldst + (GT_L1X + 0) * 64, dar, lane);
+    dx = gru_mm<16>(dx, ldst + (GT_L1X + 16) * 64, daz, lane);
+    dx = gru_mm<16>(dx, ldst + (GT_L1X + 32) * 64, danx, lane);
+    dh1 = gru_mm<16>(dh1, ldst + (GT_L1H + 0) * 64, dar, lane);
+    dh1 = gru_mm<16>(dh1, ldst + (GT_L1H + 16) * 64, daz, lane);
+    dh1 = gru_mm<16>(dh1, ldst + (GT_L1H + 32) * 64, danh, lane);
+    dfb[0] = dx[0]; dfb[1] = dx[1]; dfb[2] = dx[2]; dfb[3] = dx[3];          // (lane-half 1: [0] = row 4; [1..3] are not read)
+    const float dq = __shfl(dx[1], (int)(c + 32u), 64);                       // row 5 lives on the partner lane-half
+    if (owner) g[k] = clipped ? 0.0f : __builtin_fmaf(dq, nm.in_scale[0], scale * stage_u(ur));
+    __builtin_amdgcn_sched_barrier(0);
+  }
+}
+
+template <int COST>
+void launch_gru_grad(cpmppi_handle* h, const GruGradPtrs& a, uint32_t E, hipStream_t s) {
+  const bool f16 = gru_runs_f16(h);
+  const dim3 grid(E * a.nb);
+  if (f16) hipLaunchKernelGGL((gru_grad_forward_kernel<COST, true>), grid, dim3(BLOCK), (size_t)G16_IMAGE_BYTES, s, h->prm, a,
+                              h->gru_norm, (const float*)h->gru16_image);
+  else hipLaunchKernelGGL((gru_grad_forward_kernel<COST, false>), grid, dim3(BLOCK), (size_t)GRU_IMAGE_FLOATS * sizeof(float), s,
+                          h->prm, a, h->gru_norm, (const float*)h->gru_image);
+  hipLaunchKernelGGL((gru_grad_reverse_kernel<COST>), grid, dim3(BLOCK), GRU_GRAD_REVERSE_LDS, s, h->prm, a, h->gru_norm,
+                     (const float*)h->gru_image, (const float*)h->gru_t_image);
+}
+
 template <int COST, int NOISE>
 void launch_gru(cpmppi_handle* h, const cpmppi_step_args* a, const StepPtrs& p, hipStream_t s) {
   const bool f16 = gru_runs_f16(h);
@@ -474,9 +726,32 @@ int cpmppi_set_gru(cpmppi_handle* h, const cpmppi_gru_model* m) try {
         bv[8 * 32 + hf * 16 + v] = r < 5 ? m->b_out[r] : 0.0f;
       }
   }
+  // ---- transposed image of the reverse sweep (cpmppi_gru.hpp, GT_*): fragment s of W^T holds W[unit(s, lane half)][lane % 32]
+  std::vector<float> imgt((size_t)GRU_T_IMAGE_FLOATS, 0.0f);
+  auto fragt = [&](int f) { return imgt.data() + (size_t)f * 64; };
+  for (int g = 0; g < 3; ++g)
+    for (int s = 0; s < 16; ++s)
+      for (int l = 0; l < 64; ++l) {
+        const size_t unit = (size_t)(g * 32 + gru_tile_row(s, l >> 5));
+        const int mrow = l & 31;
+        const int col = mrow < 8 ? xcol(mrow) : -1;
+        fragt(GT_L1X + g * 16 + s)[l] = col < 0 ? 0.0f : m->w_ih[0][unit * 6 + col];
+        fragt(GT_L1H + g * 16 + s)[l] = m->w_hh[0][unit * 32 + mrow];
+        fragt(GT_L2X + g * 16 + s)[l] = m->w_ih[1][unit * 32 + mrow];
+        fragt(GT_L2H + g * 16 + s)[l] = m->w_hh[1][unit * 32 + mrow];
+      }
+  for (int s = 0; s < 4; ++s)
+    for (int l = 0; l < 64; ++l) {
+      const int o = gru_tile_row(s, l >> 5);
+      fragt(GT_HEAD + s)[l] = o < 5 ? m->w_out[(size_t)o * 32 + (l & 31)] : 0.0f;
+    }
   CPMPPI_ON_DEVICE(h);
   if (!h->gru_image) CPMPPI_HIP(h, hipMalloc(&h->gru_image, img.size() * sizeof(float)));
   CPMPPI_HIP(h, hipMemcpy(h->gru_image, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
+  if (!h->gru_t_image) CPMPPI_HIP(h, hipMalloc(&h->gru_t_image, imgt.size() * sizeof(float)));
+  CPMPPI_HIP(h, hipMemcpy(h->gru_t_image, imgt.data(), imgt.size() * sizeof(float), hipMemcpyHostToDevice));
+  allow_large_lds(&gru_grad_reverse_kernel<COST_QBGM>);      // both images in LDS: beyond the default 64 KB
+  allow_large_lds(&gru_grad_reverse_kernel<COST_DEFAULT>);
   if (!h->gru16_image) CPMPPI_HIP(h, hipMalloc(&h->gru16_image, img16.size()));
   CPMPPI_HIP(h, hipMemcpy(h->gru16_image, img16.data(), img16.size(), hipMemcpyHostToDevice));
   return CPMPPI_OK;
@@ -512,6 +787,30 @@ int cpmppi_rollout_cost_gru(cpmppi_handle* h, uint32_t E, const float* s0, const
                       (h->cfg.N + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK};
   if (h->prm.cost_id == CPMPPI_COST_QBGM) launch_gru_cost_only<COST_QBGM>(h, a, E, (hipStream_t)stream);
   else launch_gru_cost_only<COST_DEFAULT>(h, a, E, (hipStream_t)stream);
+  return launched(h);
+}
+
+int cpmppi_rollout_cost_grad_gru(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs, const float* target_position,
+                                 const float* target_equilibrium, const float* h0, float* S_out, float* grad_out, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  const char* who = "cpmppi_rollout_cost_grad_gru";
+  if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": no model set (cpmppi_set_gru)");
+  if (E == 0 || E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": E out of range");
+  if (!s0 || !inputs || !target_position || !target_equilibrium || !grad_out)
+    return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": s0, inputs, target_position, target_equilibrium, grad_out are required");
+  if ((h->prm.cost_id != CPMPPI_COST_QBGM && h->prm.cost_id != CPMPPI_COST_DEFAULT) || h->prm.qb_mode != 0u)
+    return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": the GRU predictor supports quadratic_boundary_grad_minimal and default");
+  CPMPPI_ON_DEVICE(h);
+  // check-points of the handle's largest launch; allocated on first use, never inside a capture
+  const size_t need = (size_t)h->cfg.H * GRU_CKPT_FLOATS * (size_t)h->cfg.E * h->cfg.N;
+  if (h->gru_grad_ws_floats < need) {
+    if (const int rc = refuse_unreserved_capture(h, (hipStream_t)stream, who, "cpmppi_rollout_cost_grad_gru once")) return rc;
+    if (const int rc = grow_workspace(h, h->gru_grad_ws, h->gru_grad_ws_floats, need)) return rc;
+  }
+  const GruGradPtrs a{s0, inputs, target_position, target_equilibrium, h0, S_out, grad_out, h->gru_grad_ws, (size_t)E * h->cfg.N,
+                      (h->cfg.N + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK};
+  if (h->prm.cost_id == CPMPPI_COST_QBGM) launch_gru_grad<COST_QBGM>(h, a, E, (hipStream_t)stream);
+  else launch_gru_grad<COST_DEFAULT>(h, a, E, (hipStream_t)stream);
   return launched(h);
 }
 

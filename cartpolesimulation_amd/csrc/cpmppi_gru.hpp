@@ -44,6 +44,25 @@ constexpr int GV_HEAD = GV_BIAS + 8 * 32;       // [2][5][16]: w_out[o][row(v, h
 constexpr int GV_HEADB = GV_HEAD + 2 * 5 * 16;  // b_out[5] (+3 pad)
 constexpr int GRU_IMAGE_FLOATS = GV_HEADB + 8;
 
+// The TRANSPOSED image of the reverse sweep (gru_grad_reverse_kernel): dX[K x rollouts] = W^T[K x units] * dA[units x rollouts].
+// An adjoint tile dA has the accumulator layout, so it is the B operand as it stands (k-step s = register s); fragment s of a
+// transposed matrix holds, for lane l, W[unit = gru_tile_row(s, l / 32)][l % 32] - the same fragment form and the same tile-row
+// permutation of the k order as above, with the roles of a weight's two indices swapped.  Result rows: the 32 hidden units, or
+// (GT_L1X) the 8 rows of the input tile, or - as k - (GT_HEAD) the 8 rows of the output tile.
+enum : int {
+  GT_L1X = 0,            // 3 gates x 16 k-steps   (result rows 0..7: d feature tile; row 5 = d Q)
+  GT_L1H = 48,           // 3 x 16
+  GT_L2X = 96,           // 3 x 16   (result = d layer-1 hidden tile)
+  GT_L2H = 144,          // 3 x 16
+  GT_HEAD = 192,         // 4 k-steps (the output tile's rows 0..7, 0..4 real): d h2 from d outputs
+  GT_COUNT = 196
+};
+constexpr int GRU_T_IMAGE_FLOATS = GT_COUNT * 64;
+// What the forward sweep of cpmppi_rollout_cost_grad_gru parks per rollout and control step for the reverse: both hidden tiles
+// (slot = 16 * lane half + register, layer 2 behind layer 1: a lane's 16 registers are 64 consecutive bytes) and, from slot 64,
+// the five normalised outputs that are fed back - 69 floats, padded to a multiple of 16 bytes.
+constexpr int GRU_CKPT_FLOATS = 72;
+
 // row of a 32x32 accumulator tile held by (register v, lane half hf)
 __host__ __device__ inline int gru_tile_row(int v, int hf) { return (v & 3) + 8 * (v >> 2) + 4 * hf; }
 

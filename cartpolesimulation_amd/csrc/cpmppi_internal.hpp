@@ -59,6 +59,9 @@ struct cpmppi_handle {
   float* dev_stage = nullptr;          // device [cfg.E * 10], allocated on first use
   float* gru_image = nullptr;          // device copy of the LDS fragment image (cpmppi_set_gru)
   void* gru16_image = nullptr;         // device copy of the f16 split image (cpmppi_gru16.hpp)
+  float* gru_t_image = nullptr;        // device copy of the transposed fragment image (the reverse sweep of cpmppi_rollout_cost_grad_gru)
+  float* gru_grad_ws = nullptr;        // [H][GRU_CKPT_FLOATS][E*N] check-points of cpmppi_rollout_cost_grad_gru (allocated on first use)
+  size_t gru_grad_ws_floats = 0;
   float* grad_ckpt = nullptr;          // [H][6][E*N] check-points of cpmppi_rollout_cost_grad (allocated on first use)
   size_t grad_ckpt_floats = 0;
   float* rpgd_ws = nullptr;            // cpmppi_rpgd_step: check-points [E][H][6][block] then gradients [E][H][block] (cpmppi_rpgd_reserve)
@@ -127,6 +130,26 @@ inline std::string pole_mass_rows_short(const char* who, const cpmppi_handle* h,
 inline int launched(cpmppi_handle* h) {
   CPMPPI_HIP(h, hipGetLastError());
   return CPMPPI_OK;
+}
+
+// Grows a device workspace of the handle to `need` floats (the contents are not kept).
+inline int grow_workspace(cpmppi_handle* h, float*& ws, size_t& floats, size_t need) {
+  if (floats >= need) return CPMPPI_OK;
+  if (ws) (void)hipFree(ws);
+  ws = nullptr; floats = 0;
+  CPMPPI_HIP(h, hipMalloc(&ws, need * sizeof(float)));
+  floats = need;
+  return CPMPPI_OK;
+}
+
+// No allocation inside a capture: a step whose workspace is not reserved (`reserve`: the call that does it) is refused there.
+inline int refuse_unreserved_capture(cpmppi_handle* h, hipStream_t s, const char* who, const char* reserve) {
+  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
+  const bool capturing = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
+  (void)hipGetLastError();
+  if (!capturing) return CPMPPI_OK;
+  return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": the stream is being captured and the workspace is not reserved (call " +
+                                         reserve + " before the capture)");
 }
 
 // a kernel whose dynamic LDS may exceed the default 64 KB opts in to SAMPLER_LDS_MAX

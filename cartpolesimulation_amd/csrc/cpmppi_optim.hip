@@ -514,25 +514,8 @@ static int sweep_check_shape(cpmppi_handle* h, const char* who, const SweepWords
   return CPMPPI_OK;
 }
 
-// Grows a device workspace of the handle to `need` floats (the contents are not kept).
-static int grow_workspace(cpmppi_handle* h, float*& ws, size_t& floats, size_t need) {
-  if (floats >= need) return CPMPPI_OK;
-  if (ws) (void)hipFree(ws);
-  ws = nullptr; floats = 0;
-  CPMPPI_HIP(h, hipMalloc(&ws, need * sizeof(float)));
-  floats = need;
-  return CPMPPI_OK;
-}
-
-// No allocation inside a capture: a step whose workspace is not reserved (`reserve`: the call that does it) is refused there.
-static int refuse_unreserved_capture(cpmppi_handle* h, hipStream_t s, const char* who, const char* reserve) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  const bool capturing = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-  (void)hipGetLastError();
-  if (!capturing) return CPMPPI_OK;
-  return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": the stream is being captured and the workspace is not reserved (call " +
-                                         reserve + " before the capture)");
-}
+// (grow_workspace and refuse_unreserved_capture, which the entry points below share with cpmppi_rollout_cost_grad_gru, are in
+// cpmppi_internal.hpp)
 
 int cpmppi_rollout_cost_grad(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs,
                              const float* target_position, const float* target_equilibrium, const float* L,

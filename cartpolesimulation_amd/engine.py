@@ -535,11 +535,30 @@ class MPPIEngine:
                                                  self._stream()))
         return S
 
-    def rollout_cost_grad(self, s0, inputs, target_position, target_equilibrium, L=None, previous_input=None):
-        """inputs[E,N,H] -> (S[E,N], grad[E,N,H]): trajectory cost and its derivative w.r.t. the inputs."""
+    def rollout_cost_grad(self, s0, inputs, target_position, target_equilibrium, L=None, previous_input=None, predictor="ODE_v0",
+                          h0=None):
+        """inputs[E,N,H] -> (S[E,N], grad[E,N,H]): trajectory cost and its derivative w.r.t. the inputs.  ``predictor="GRU"``
+        differentiates the rollout through the network of ``set_gru`` (cpmppi_rollout_cost_grad_gru): ``h0`` [E,2,32] is each
+        env's memory (None: zeros); the network knows no pole length and its two costs read no previous input, so ``L`` and
+        ``previous_input`` are refused."""
+        if predictor not in ("ODE_v0", "GRU"):
+            raise ValueError("predictor must be 'ODE_v0' or 'GRU'")
+        if predictor != "GRU" and h0 is not None:
+            raise ValueError("h0 is the memory of the GRU predictor: pass predictor='GRU'")
+        if predictor == "GRU":
+            if L is not None:
+                raise ValueError("predictor='GRU' takes no L: the network is the plant model")
+            if previous_input is not None:
+                raise ValueError("predictor='GRU' takes no previous_input: neither of its costs (quadratic_boundary_grad_minimal, "
+                                 "default) reads the control applied before")
         E, s0, inputs, tp, te, Lt = self._rollout_inputs(s0, inputs, target_position, target_equilibrium, L)
-        pi = self._per_env(previous_input, E) if previous_input is not None else None
         S, grad = self.empty(E, self.N), self.empty(E, self.N, self.H)
+        if predictor == "GRU":
+            h0 = self.tensor(h0, (E, 2, 32)) if h0 is not None else None
+            self._check(self.lib.cpmppi_rollout_cost_grad_gru(self._h, E, _ptr(s0), _ptr(inputs), _ptr(tp), _ptr(te), _ptr(h0),
+                                                              _ptr(S), _ptr(grad), self._stream()))
+            return S, grad
+        pi = self._per_env(previous_input, E) if previous_input is not None else None
         self._check(self.lib.cpmppi_rollout_cost_grad(self._h, E, _ptr(s0), _ptr(inputs), _ptr(tp), _ptr(te), _ptr(Lt),
                                                       _ptr(pi), _ptr(S), _ptr(grad), self._stream()))
         return S, grad

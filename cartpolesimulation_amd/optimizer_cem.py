@@ -18,8 +18,9 @@ cem, cem-gmm and random-action also run on the neural predictor (``gru_model=`` 
 ``predictor_specification``, under optimizer_mppi's rules): they only need the costs of given plans, which
 cpmppi_rollout_cost_gru computes with the network in the rollout loop.  Each env keeps the network's memory ``h`` [E,2,32]:
 zero after a reset, handed to every cost launch of a control step, then advanced with the state seen and the control applied.
-The two hybrids need the cost's gradient, and the GRU has no adjoint kernel: they refuse it, as does ``fused=True``
-(cpmppi_cem_step integrates the ODE).
+The two hybrids need the cost's gradient: they refuse the network unless asked with ``gru_adjoint=True``, which makes their
+refinement cpmppi_rollout_cost_grad_gru from the same memory; ``fused=True`` refuses it either way (cpmppi_cem_step integrates
+the ODE, and has no adjoint kernel for the GRU).
 """
 import math
 
@@ -27,8 +28,9 @@ import torch
 
 from ._optimizer_base import _OptimizerBase, is_gru_specification
 
-GRU_NO_ADJOINT = ("the GRU predictor has no adjoint kernel, and {} needs the gradient of the cost: it runs on the ODE_v0 and ODE "
-                  "predictors; cem, cem-gmm and random-action run on the GRU")
+GRU_NO_ADJOINT = ("{} needs the gradient of the cost and runs on the ODE_v0 and ODE predictors by default (the fused step has no adjoint "
+                  "kernel for the GRU predictor): pass gru_adjoint=True to differentiate through the network in the staged step "
+                  "(cpmppi_rollout_cost_grad_gru); cem, cem-gmm and random-action run on the GRU without it")
 GRU_NOT_FUSED = ("fused=True integrates the ODE (cpmppi_cem_step): the GRU predictor runs in the staged step of cem, cem-gmm and "
                  "random-action, fused=False")
 
@@ -43,11 +45,11 @@ class optimizer_cem(_OptimizerBase):
                  cem_stdev_min=0.01, cem_best_k=40, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
                  math_mode="fast", intermediate_steps=10, phys=None, device=0, variable_parameters=None, per_env_pole_mass=False,
-                 fused=False, gru_model=None, **kwargs):
+                 fused=False, gru_model=None, gru_adjoint=False, **kwargs):
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
                          intermediate_steps, control_mode="clip", shift_mode="none", math_mode=math_mode,
-                         per_env_pole_mass=bool(per_env_pole_mass), gru_model=gru_model)
+                         per_env_pole_mass=bool(per_env_pole_mass), gru_model=gru_model, gru_adjoint=gru_adjoint)
         self.cem_outer_it, self.cem_best_k = int(cem_outer_it), int(cem_best_k)
         self.cem_initial_action_stdev, self.cem_stdev_min = float(cem_initial_action_stdev), float(cem_stdev_min)
         self.warmup, self.warmup_iterations = bool(warmup), int(warmup_iterations)
@@ -56,6 +58,8 @@ class optimizer_cem(_OptimizerBase):
         if self.fused and not self._fusable:
             raise ValueError(f"fused=True: the fused CEM control step (cpmppi_cem_step) is built for cem, cem-naive-grad and "
                              f"cem-grad-bharadhwaj, not for {self.optimizer_name}")
+        if self._gru_refusal:        # (the hybrids: what their opt-in to the GRU adjoint cannot be combined with)
+            self._check_gru_adjoint(self.fused)
         if self.fused and gru_model is not None:
             raise ValueError(GRU_NOT_FUSED)
 
@@ -73,6 +77,12 @@ class optimizer_cem(_OptimizerBase):
     def _refine(self, Q, s_t, tp, te, L):
         """Hook of the CEM + gradient hybrids: improve the samples before they are ranked."""
         return Q
+
+    def _gradient(self, s_t, Q, tp, te, L):
+        """d cost / d Q [E,N,H] of the samples, under the predictor _cost uses (the hybrids' refinement)."""
+        if self.h is not None:
+            return self.engine.rollout_cost_grad(s_t, Q, tp, te, predictor="GRU", h0=self.h)[1]
+        return self.engine.rollout_cost_grad(s_t, Q, tp, te, L=L)[1]
 
     def optimizer_reset(self):
         E, H = self.num_envs, self.mpc_horizon
@@ -193,7 +203,7 @@ class optimizer_cem_naive_grad(optimizer_cem):
         self.learning_rate, self.gradmax_clip = float(learning_rate), float(gradmax_clip)
 
     def _refine(self, Q, s_t, tp, te, L):
-        _, G = self.engine.rollout_cost_grad(s_t, Q, tp, te, L=L)
+        G = self._gradient(s_t, Q, tp, te, L)
         return self.engine.sgd_step(Q, G, self.learning_rate, self.gradmax_clip)
 
     def _fused_refine(self):
@@ -227,7 +237,7 @@ class optimizer_cem_grad_bharadhwaj(optimizer_cem):
     def _refine(self, Q, s_t, tp, te, L):
         if self._m is None:
             self._m, self._v = torch.zeros_like(Q), torch.zeros_like(Q)
-        _, G = self.engine.rollout_cost_grad(s_t, Q, tp, te, L=L)
+        G = self._gradient(s_t, Q, tp, te, L)
         self._it += 1
         return self.engine.adam_step(Q, G, self._m, self._v, self._it, self.learning_rate, self.adam_beta_1, self.adam_beta_2,
                                      self.adam_epsilon, self.gradmax_clip)

@@ -24,6 +24,13 @@ launch.
 choice of the best plan, resampling and shift in one kernel, the plans and moments updated in place.  ``step`` then only
 uploads the state; ``step_device`` takes device tensors and, with a device step counter, touches the host not at all - the
 form a captured closed loop replays (harness.py).  The staged path above stays what it was.
+
+``gru_adjoint=True`` (off by default) lets both run on the neural predictor (``gru_model=`` and / or a
+``GRU-6IN-32H1-32H2-5OUT*`` ``predictor_specification``, under optimizer_mppi's rules): every gradient launch of a control step is
+cpmppi_rollout_cost_grad_gru and every cost launch cpmppi_rollout_cost_gru, from each env's memory ``h`` [E,2,32], which is zero
+after a reset and advances once per control step with the state seen and the control applied.  Without the flag the network is
+refused by name, as before; with it, ``fused=True`` (cpmppi_rpgd_step integrates the ODE) and quadratic_boundary_grad (no such
+cost in the GRU kernels) are.
 """
 import math
 
@@ -35,22 +42,26 @@ from ._optimizer_base import _OptimizerBase
 class _GradientBase(_OptimizerBase):
     optimizer_name = "gradient"
     _unknown_predictor = "the adjoint kernel differentiates the ODE_v0 and ODE predictors"
-    _gru_refusal = ("the GRU predictor has no adjoint kernel, and the gradient optimizers (gradient, rpgd) need the gradient of the "
-                    "cost: they run on the ODE_v0 and ODE predictors; cem, cem-gmm and random-action run on the GRU")
+    _gru_refusal = ("the gradient optimizers (gradient, rpgd) need the gradient of the cost and run on the ODE_v0 and ODE predictors "
+                    "by default (the fused step has no adjoint kernel for the GRU predictor): pass gru_adjoint=True to differentiate "
+                    "through the network in the staged step (cpmppi_rollout_cost_grad_gru); cem, cem-gmm and random-action run "
+                    "on the GRU without it")
 
     def __init__(self, cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, sample_stdev, period,
                  num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
-                 variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused=False, gru_model=None):
+                 variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused=False, gru_model=None,
+                 gru_adjoint=False):
         # the handle's sampler draws knots ~ N(0, SQRTRHOINV / sqrt(dt)): set it to the requested stdev
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
                          intermediate_steps, control_mode="clip", shift_mode="none", math_mode="fast",
                          horizon_reduce=horizon_reduce, SQRTRHOINV=float(sample_stdev) * math.sqrt(float(mpc_timestep)),
                          period_interpolation_inducing_points=int(period), per_env_pole_mass=bool(per_env_pole_mass),
-                         gru_model=gru_model)
+                         gru_model=gru_model, gru_adjoint=gru_adjoint)
         self.count = 0               # control steps taken
         self.draws = 0               # sampler launches (the Philox offset)
         self.fused = bool(fused)     # one cpmppi_rpgd_step per control step instead of the staged launches
+        self._check_gru_adjoint(self.fused)
 
     def _set_timestep(self, dt):
         if dt != self.cfg.mpc_timestep:          # the sampling stdev stays what the constructor was asked for
@@ -74,6 +85,7 @@ class _GradientBase(_OptimizerBase):
         self.adam_it = 0
         self.count = 0
         self._first = True
+        self._reset_memory()
         if self.fused:
             eng, E = self.engine, self.num_envs
             # what the fused step writes per control step: the controls, the final costs, the best plan (persistent buffers)
@@ -84,11 +96,17 @@ class _GradientBase(_OptimizerBase):
     # -- one control step ----------------------------------------------------------------------------------------
     def _descend(self, s_t, tp, te, L, iterations):
         eng = self.engine
+        if self.h is not None:       # gru_adjoint: every gradient and cost launch of the step under the network, from the env's memory
+            kw = dict(predictor="GRU", h0=self.h)
+        else:
+            kw = dict(L=L, previous_input=self._previous_input)
         for _ in range(iterations):
-            _, G = eng.rollout_cost_grad(s_t, self.Q, tp, te, L=L, previous_input=self._previous_input)
+            _, G = eng.rollout_cost_grad(s_t, self.Q, tp, te, **kw)
             self.adam_it += 1
             eng.adam_step(self.Q, G, self.m, self.v, self.adam_it, self.learning_rate, self.adam_beta_1, self.adam_beta_2,
                           self.adam_epsilon, self.gradmax_clip)
+        if self.h is not None:
+            return eng.rollout_cost(s_t, self.Q, tp, te, **kw)
         return eng.rollout_cost(s_t, self.Q, tp, te, L=L) if self.cfg.cost_function_specification != "quadratic_boundary_grad" \
             else eng.rollout_cost_grad(s_t, self.Q, tp, te, L=L, previous_input=self._previous_input)[0]
 
@@ -100,12 +118,13 @@ class _GradientBase(_OptimizerBase):
             tail = x[:, :, -1:].expand(-1, -1, by) if name == "Q" else torch.zeros_like(x[:, :, :by])
             setattr(self, name, torch.cat([x[:, :, by:], tail], dim=2).contiguous())
 
-    def _finish(self, S, single, as_tensor):
+    def _finish(self, S, single, as_tensor, s_t):
         E = S.shape[0]
         best = torch.argmin(S, dim=1)
         rows = torch.arange(E, device=S.device)
         u = self.Q[rows, best, 0].clone()
         self._previous_input = u.clone()
+        self._advance_memory(s_t, u)                     # (the network's memory, once per control step, from the control applied)
         if self.optimizer_logging:
             self.logging_values = {"Q_logged": u.cpu().numpy(), "J_logged": S.cpu().numpy(),
                                    "u_logged": self.Q[rows, best].cpu().numpy()}
@@ -156,14 +175,14 @@ class optimizer_gradient(_GradientBase):
                  gradmax_clip=5, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
                  intermediate_steps=10, horizon_reduce="sum", phys=None, device=0, variable_parameters=None,
-                 per_env_pole_mass=False, fused=False, gru_model=None, **kwargs):
+                 per_env_pole_mass=False, fused=False, gru_model=None, gru_adjoint=False, **kwargs):
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
         self.adam_epsilon, self.gradmax_clip, self.rtol = float(adam_epsilon), float(gradmax_clip), float(rtol)
         self.gradient_steps, self.warmup, self.warmup_iterations = int(gradient_steps), bool(warmup), int(warmup_iterations)
         self.initial_action_stdev = float(initial_action_stdev)
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, initial_action_stdev,
                          10, num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
-                         variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused, gru_model)
+                         variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused, gru_model, gru_adjoint)
 
     def _fused_plan(self):
         return {"iterations": self.gradient_steps, "keep_k": self.num_rollouts, "resamp_per": 0, "shift": 1}
@@ -184,7 +203,7 @@ class optimizer_gradient(_GradientBase):
         iters = self.warmup_iterations if (self.warmup and self._first) else self.gradient_steps
         self._first = False
         S = self._descend(s_t, tp, te, L, iters)
-        out = self._finish(S, single, as_tensor)
+        out = self._finish(S, single, as_tensor, s_t)
         self._shift(1)
         return out
 
@@ -201,7 +220,7 @@ class optimizer_rpgd(_GradientBase):
                  warmup=False, warmup_iterations=250, optimizer_logging=False, calculate_optimal_trajectory=False,
                  num_envs=1, cost_function_specification=None, cost_weights=None, intermediate_steps=10,
                  horizon_reduce="sum", phys=None, device=0, variable_parameters=None, per_env_pole_mass=False, fused=False,
-                 gru_model=None, **kwargs):
+                 gru_model=None, gru_adjoint=False, **kwargs):
         if SAMPLING_DISTRIBUTION not in ("normal", "uniform"):
             raise ValueError(f"SAMPLING_DISTRIBUTION={SAMPLING_DISTRIBUTION!r}; expected 'normal' or 'uniform'")
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
@@ -216,7 +235,7 @@ class optimizer_rpgd(_GradientBase):
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, stdev,
                          period_interpolation_inducing_points, num_envs, cost_function_specification, cost_weights,
                          intermediate_steps, phys, device, variable_parameters, optimizer_logging, horizon_reduce,
-                         per_env_pole_mass, fused, gru_model)
+                         per_env_pole_mass, fused, gru_model, gru_adjoint)
 
     def _uniform_range(self):
         return (self.action_low, self.action_high) if self.sample_whole_control_space else \
@@ -241,7 +260,7 @@ class optimizer_rpgd(_GradientBase):
         iters = self.warmup_iterations if (self.warmup and self._first) else self.outer_its
         self._first = False
         S = self._descend(s_t, tp, te, L, iters)
-        out = self._finish(S, single, as_tensor)
+        out = self._finish(S, single, as_tensor, s_t)
         if self.resamp_per > 0 and self.count % self.resamp_per == 0 and self.opt_keep_k < self.num_rollouts:
             # survivors: the opt_keep_k cheapest plans (stable top-k on the device), moments kept; the rest re-drawn
             _, _, elite = self.engine.cem_update(S, self.Q, self.opt_keep_k, 0.0, return_elites=True)

@@ -331,6 +331,29 @@ int cpmppi_rollout_cost_gru(cpmppi_handle* h, uint32_t E, const float* s0, const
                             const float* target_position, const float* target_equilibrium, const float* h0, float* S_out,
                             void* stream);
 
+/* cpmppi_rollout_cost_gru and the gradient of its costs with respect to the inputs: S[E,N] (may be NULL) and
+ * grad[E,N,H] = d get_trajectory_cost(predict_core_GRU(s, Q), Q) / d Q - what the gradient optimizers (gradient-tf, rpgd, the
+ * CEM + gradient hybrids) need of the neural predictor.  The function differentiated is exactly the one
+ * cpmppi_rollout_cost_gru evaluates (same h0[E,2,32] or NULL, the same two costs, horizon_reduce and clamp); non-smooth pieces
+ * follow cpmppi_rollout_cost_grad: 0 through a clipped control and through the indicator terms of `default` (its terminal cost
+ * and therefore atan2 included); cos(angle) = c / sqrt(c^2 + s^2) is differentiated through both network outputs; the stage-0
+ * cos(angle) comes from s0 and carries no gradient.
+ * Two launches on `stream`.  (1) Forward sweep: the cost-only rollout in the handle's math mode (FAST: split f16, PRECISE:
+ * exact f32) - S_out is bit-identical to cpmppi_rollout_cost_gru's - which parks, after every control step but the last, both
+ * hidden tiles and the five fed-back outputs of every rollout: 69 floats per rollout and step, padded to 72 (16-byte accesses);
+ * the gates are not stored.  (2) Reverse sweep, exact-f32
+ * MFMA in BOTH math modes over a transposed weights image that cpmppi_set_gru builds beside the other two: per step, from the
+ * last to the first, head adjoint, then each layer's gates recomputed from the check-points right before its cell adjoint: layer-2 cell,
+ * layer-1 cell; the Q row of the input adjoint is the gradient, its five feature rows are the feedback into the step before.
+ * Workspace: H * 72 * cfg.E * cfg.N floats ([H][E N][72]), allocated on first use; under stream capture a call that would have to allocate is
+ * refused - call once before the capture, after that the call can be captured.
+ * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned (cpmppi_last_error: "cpmppi_rollout_cost_grad_gru: ...") when no model
+ * is set, E == 0 or E > cfg.E, a pointer other than h0 and S_out is NULL, or the handle's cost is neither
+ * quadratic_boundary_grad_minimal nor default. */
+int cpmppi_rollout_cost_grad_gru(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs,
+                                 const float* target_position, const float* target_equilibrium, const float* h0,
+                                 float* S_out, float* grad_out, void* stream);
+
 /* Rollout + plugin cost + its gradient with respect to the inputs: S[E,N] (may be NULL) and
  * grad[E,N,H] = d get_trajectory_cost(predict_core(s, Q), Q, previous_input) / d Q — what TensorFlow's GradientTape
  * hands to the gradient-based optimizers of the absent Control_Toolkit (Control_Toolkit_ASF/config_optimizers.yml:49-86,

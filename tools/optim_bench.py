@@ -22,6 +22,12 @@ E x N x H of --cost-only-shapes, the cost-only launch (cpmppi_rollout_cost_gru) 
 [E,N,H] as delta_u with a zero nominal sequence (cpmppi_step: the same rollouts plus the MPPI update and its finalize launch) in
 ONE process, the two alternating: device time from events around batches of back-to-back launches, the median over the rounds and
 each column's min - max scatter.
+
+  python tools/optim_bench.py --gru-grad [--steps 30] [--grad-shapes 1x16x35,64x16x35,1x40x35,64x40x35]
+The GRU adjoint (same synthetic weights).  Per E x N x H of --grad-shapes (default: the rpgd and gradient-tf sizes at 1 and 64
+envs) and math mode, cpmppi_rollout_cost_grad_gru against cpmppi_rollout_cost_gru on the same plans, alternating in one process as
+above (ms per launch, the ratio); then rpgd and gradient-tf through the controller seam over the GRU (``gru_adjoint=True``) and over
+the ODE, alternating, at 1 and 64 envs and both math modes of the GRU kernels.
 """
 import argparse
 import json
@@ -46,6 +52,8 @@ ap.add_argument("--optimizers", default="gradient-tf,rpgd", help="with --fused: 
 ap.add_argument("--staged-repeats", type=int, default=1, help="with --fused: how many times the staged record is measured")
 ap.add_argument("--gru", action="store_true", help="the GRU predictor under cem-tf, cem-gmm-tf and random-action-tf; cost-only launch vs fused step")
 ap.add_argument("--cost-only-shapes", default="1x200x35,64x200x35,256x200x35,256x1024x50", help="with --gru: ExNxH,... (the last default: bench.py's C5)")
+ap.add_argument("--gru-grad", action="store_true", help="the GRU adjoint: gradient launch vs cost-only launch; rpgd and gradient-tf over the GRU vs the ODE")
+ap.add_argument("--grad-shapes", default="1x16x35,64x16x35,1x40x35,64x40x35", help="with --gru-grad: ExNxH,...")
 ap.add_argument("--datagen", default=None, help="with --fused: E,seconds of the closed-loop data generator, e.g. 256,10")
 args = ap.parse_args()
 E = args.envs
@@ -168,8 +176,91 @@ def gru_bench():
             eng.close()
 
 
+def alternating(launches, rounds=12, batch=10):
+    """Device ms per launch of each entry of `launches`, the entries alternating: {name: [ms per round]} (two warm-up rounds)."""
+    ms = {k: [] for k in launches}
+    for r in range(rounds + 2):
+        for k, fn in launches.items():
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(batch):
+                fn()
+            b.record()
+            b.synchronize()
+            if r >= 2:
+                ms[k].append(a.elapsed_time(b) / batch)
+    return ms
+
+
+def gru_grad_bench():
+    from cartpolesimulation_amd.configs import MPPIConfig
+    from cartpolesimulation_amd.engine import MPPIEngine
+    model = synthetic_gru()
+    rounds, batch = 12, 10
+    for shape in args.grad_shapes.split(","):
+        e, n, h = (int(x) for x in shape.split("x"))
+        g = np.random.Generator(np.random.SFC64(11))
+        s0 = np.stack([O.create_cartpole_state(g.uniform(-0.3, 0.3), g.uniform(-0.5, 0.5), g.uniform(-0.05, 0.05), 0.0) for _ in range(e)])
+        for math_mode in ("fast", "precise"):
+            eng = MPPIEngine(e, MPPIConfig(num_rollouts=n, mpc_horizon=h, math_mode=math_mode, cc_weight=0.0, shift_mode="none"))
+            eng.set_gru(model)
+            s, tp, te, h0 = eng.tensor(s0), eng.zeros(e), eng.zeros(e) + 1.0, eng.zeros(e, 2, 32)
+            plans = torch.clamp(0.5 * torch.randn(e, n, h, device=s.device, generator=torch.Generator(s.device).manual_seed(1)), -1.0, 1.0)
+            ms = alternating({"cost_only": lambda: eng.rollout_cost(s, plans, tp, te, predictor="GRU", h0=h0),
+                              "cost_grad": lambda: eng.rollout_cost_grad(s, plans, tp, te, predictor="GRU", h0=h0)}, rounds, batch)
+            rec = {"bench": "gru_cost_grad", "envs": e, "num_rollouts": n, "mpc_horizon": h, "math_mode": math_mode, "rounds": rounds,
+                   "launches_per_round": batch}
+            for k, v in ms.items():
+                rec[k + "_ms"] = round(float(np.median(v)), 5)
+                rec[k + "_min_max_ms"] = [round(float(min(v)), 5), round(float(max(v)), 5)]
+            rec["cost_grad_over_cost_only"] = round(rec["cost_grad_ms"] / rec["cost_only_ms"], 4)
+            print(json.dumps(rec), flush=True)
+            eng.close()
+    for name in ("rpgd", "gradient-tf"):
+        for e in (1, 64):
+            s_e = s_host[np.arange(e) % s_host.shape[0]]
+            for math_mode in ("fast", "precise"):
+                ctrls = {}
+                for predictor, extra in (("GRU", dict(gru_model=model, gru_adjoint=True)), ("ODE", {})):
+                    # (the ODE adjoint is written for the FAST arithmetic: its column is the same in both rows of a pair)
+                    ctrl = controller_mpc("CartPole", {"target_position": 0.0, "target_equilibrium": 1.0, "L": 0.395},
+                                          control_limits=([-1.0], [1.0]), num_envs=e, config=dict(seed=1, **extra))
+                    ctrl.configure(name, predictor_specification=None if predictor == "GRU" else "ODE")
+                    if predictor == "GRU":                       # the GRU kernels' math mode is the handle's
+                        opt = ctrl.optimizer
+                        opt.engine.close()
+                        opt.cfg.math_mode = math_mode
+                        opt.configure()
+                    ctrls[predictor] = ctrl
+                states = {k: c.optimizer.engine.tensor(s_e) for k, c in ctrls.items()}
+                wall = {k: [] for k in ctrls}
+                for r in range(rounds + 2):
+                    for k, c in ctrls.items():
+                        torch.cuda.synchronize()
+                        t0 = time.perf_counter()
+                        for _ in range(batch):
+                            c.step(states[k], 0.0, {})
+                        torch.cuda.synchronize()
+                        if r >= 2:
+                            wall[k].append((time.perf_counter() - t0) / batch * 1e3)
+                opt = ctrls["GRU"].optimizer
+                rec = {"bench": "controller_step_gru_adjoint", "optimizer": name, "envs": e, "num_rollouts": opt.num_rollouts,
+                       "mpc_horizon": opt.mpc_horizon, "math_mode": opt.cfg.math_mode,
+                       "iterations": getattr(opt, "outer_its", getattr(opt, "gradient_steps", None))}
+                for k, v in wall.items():
+                    rec[k.lower() + "_ms_per_controller_step"] = round(float(np.median(v)), 4)
+                    rec[k.lower() + "_min_max_ms"] = [round(float(min(v)), 4), round(float(max(v)), 4)]
+                rec["gru_over_ode"] = round(rec["gru_ms_per_controller_step"] / rec["ode_ms_per_controller_step"], 4)
+                print(json.dumps(rec), flush=True)
+                for c in ctrls.values():
+                    c.optimizer.engine.close()
+
+
 if args.fused:
     fused_bench()
+    sys.exit(0)
+if args.gru_grad:
+    gru_grad_bench()
     sys.exit(0)
 if args.gru:
     gru_bench()
