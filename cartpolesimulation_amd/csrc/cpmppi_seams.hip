@@ -329,7 +329,8 @@ int check_sampler(cpmppi_handle* h, const std::string& fn, uint32_t E, bool args
   if (E == 0 || E > h->cfg.E || !args_ok) return fail(h, CPMPPI_ERR_BAD_ARG, fn + bad_arg);
   if (!aligned) return fail(h, CPMPPI_ERR_ALIGN, fn + unaligned);
   if ((size_t)BLOCK * (h->prm.P + 1) * sizeof(float) > SAMPLER_LDS_MAX)
-    return fail(h, CPMPPI_ERR_BAD_ARG, fn + ": more than 154 knots per rollout are not supported");
+    return fail(h, CPMPPI_ERR_BAD_ARG, fn + ": more than " + std::to_string(SAMPLER_LDS_MAX / (BLOCK * sizeof(float)) - 1) +
+                                           " knots per rollout are not supported");
   return CPMPPI_OK;
 }
 

@@ -390,6 +390,90 @@ def test_predict_large_launch_equals_small_launches(math_mode):
     eng.close()
 
 
+STAGED_B = 65536 + 4391                  # above the staging threshold, ragged: the last block has 135 live lanes
+# rows of a staged launch that are also compared with the oracle: the first 64, the 64 straddling row 65536, the last 64
+STAGED_ANCHORS = np.r_[0:64, 65536 - 32:65536 + 32, STAGED_B - 64:STAGED_B]
+
+
+def _staged_predict_inputs(H):
+    """The draws of test_predict_large_launch_equals_small_launches at another horizon, plus a pole mass per row."""
+    from test_gpu_pole_mass_rows import M_HI, M_LO
+    B = STAGED_B
+    rng = Generator(SFC64(31 + H))
+    ang = rng.uniform(-np.pi, np.pi, B)
+    s = np.zeros((B, 6), f32)
+    s[:, 0], s[:, 1], s[:, 2], s[:, 3] = ang, rng.uniform(-8, 8, B), np.cos(ang), np.sin(ang)
+    s[:, 4], s[:, 5] = rng.uniform(-0.19, 0.19, B), rng.uniform(-0.6, 0.6, B)
+    Q = rng.uniform(-1, 1, (B, H)).astype(f32)
+    return s, Q, rng.uniform(0.25, 0.45, B).astype(f32), rng.uniform(M_LO, M_HI, B).astype(f32)
+
+
+def _large_and_half_launches(eng, s, Q, Lv, m=None):
+    """-> (one launch over all rows, two launches of half the rows each - below the staging threshold - over the same rows), with the
+    matching slices of the per-row pole masses registered."""
+    B, half = Q.shape[0], Q.shape[0] // 2
+    if m is not None:
+        eng.set_pole_mass_rows(m)
+    big = eng.predict(s, Q, L=Lv).cpu().numpy()
+    parts = []
+    for sl in (slice(0, half), slice(half, B)):
+        if m is not None:
+            eng.set_pole_mass_rows(m[sl])
+        parts.append(eng.predict(s[sl], Q[sl], L=Lv[sl]).cpu().numpy())
+    return big, np.concatenate(parts)
+
+
+@pytest.mark.parametrize("math_mode", ["fast", "precise"])
+def test_predict_staged_launch_predictor_ode_reads_the_rows_masses(math_mode):
+    """predict_kernel<*, STAGED, PREDICTOR_ODE> (both math modes): B > 65536 with a pole length AND a registered pole mass per row,
+    H = 17 (two full 8-step staging chunks plus one step).  The large launch equals, bit for bit, two half launches (direct stores)
+    with the matching slices of the masses registered; it differs from the same launch under the handle's scalar mass in every row
+    whose mass is not the handle's to 1e-4 (so Mp[b] is read, in the last, partly idle block too); and 192 of its rows - the first 64, the 64 straddling row 65536, the
+    last 64 - meet the C oracle run with the row's own L and mass, under the band rule of test_gpu_pole_mass_rows.py."""
+    from dataclasses import replace
+    from oracle import oracle_c as OC
+    from test_gpu_pole_mass_rows import assert_states_in_band, f32_realisations
+    from cartpolesimulation_amd.engine import MPPIEngine
+    from cartpolesimulation_amd.configs import MPPIConfig
+    B, H = STAGED_B, 17
+    s, Q, Lv, m = _staged_predict_inputs(H)
+    eng = MPPIEngine(1, MPPIConfig(num_rollouts=64, mpc_horizon=H, math_mode=math_mode, predictor_type="ODE"))
+    big, small = _large_and_half_launches(eng, s, Q, Lv, m)
+    assert big.shape == (B, H + 1, 6) and np.array_equal(big.view(np.uint32), small.view(np.uint32))
+    assert np.array_equal(big[:, 0], s)
+    eng.set_pole_mass_rows(None)
+    scalar = eng.predict(s, Q, L=Lv).cpu().numpy()
+    far = np.abs(m - f32(0.087)) > 1e-4                                # (masses from [0.015, 0.15]; the handle's is 0.087)
+    assert far.mean() > 0.99 and far[-135:].sum() > 100 and (big[far, 1:] != scalar[far, 1:]).any(axis=(1, 2)).all()
+    eng.close()
+    rows = STAGED_ANCHORS
+    ocfg = O.MPPIConfig(N=1, H=H, integrator="ODE")
+    ref = np.concatenate([OC.predict(OC.make_config(ocfg, replace(O.DEFAULT_PARAMS, m_pole=f32(m[b]))), s[b:b + 1], Q[b:b + 1],
+                                     L=Lv[b:b + 1]) for b in rows])
+    assert_states_in_band(big[rows], ref, f32_realisations(s[rows], Q[rows], Lv[rows], m[rows]), f"staged ODE rows ({math_mode})")
+    assert np.abs(scalar[rows] - ref).max() > 1e-3                    # the handle's mass would not pass
+
+
+@pytest.mark.parametrize("H", [8, 1])
+def test_predict_staged_launch_chunk_edges(H):
+    """The staged stores of predictor_ODE_v0 (FAST) at H == the 8-step staging chunk and at H = 1 (less than one chunk), ragged B:
+    bit-equal to two half launches, and the 192 anchor rows against the oracle's two reference arithmetics under parity_util's
+    state rule (as test_predictor_seam)."""
+    from cartpolesimulation_amd.engine import MPPIEngine
+    from cartpolesimulation_amd.configs import MPPIConfig
+    B = STAGED_B
+    s, Q, Lv, _ = _staged_predict_inputs(H)
+    eng = MPPIEngine(1, MPPIConfig(num_rollouts=64, mpc_horizon=H, math_mode="fast"))
+    big, small = _large_and_half_launches(eng, s, Q, Lv)
+    assert big.shape == (B, H + 1, 6) and np.array_equal(big.view(np.uint32), small.view(np.uint32))
+    assert np.array_equal(big[:, 0], s)
+    eng.close()
+    rows = STAGED_ANCHORS
+    ref_a = O.predict_core(s[rows], Q[rows], L=Lv[rows])
+    ref_b = O.predict_core(s[rows], Q[rows], L=Lv[rows], mode="f64sub")
+    PU.assert_states(big[rows], ref_a, ref_b, PU.flag_discontinuities(ref_a), f"staged ODE_v0 rows, H = {H}")
+
+
 @pytest.mark.parametrize("noise", ["philox", "knots"])
 @pytest.mark.parametrize("rpl,small_E,big_E,H", [(2, 200, 1600, 70), (2, 100, 1600, 70), (1, 32, 129, 70), (1, 32, 129, 150)])
 def test_builds_of_the_kernel_agree_bit_for_bit(rpl, small_E, big_E, H, noise):

@@ -437,7 +437,8 @@ def test_limits_and_bad_arguments():
     q = Q.cpu().numpy()
     assert np.isfinite(q).all() and len(np.unique(np.round(q, 7))) > E * 0.9
     # the device sampler stages [256][P+1] knots in LDS: 101 knots (H = 100, one per step) fit the 160 KB of gfx950 and
-    # match the oracle's interpolation; more than 154 per rollout -> clean error, not a crash
+    # match the oracle's interpolation; more than 158 per rollout ([256][159] floats are the 159 KB the check admits; the boundary itself:
+    # tests/test_gpu_seams.py) -> clean error, not a crash
     e3 = engine(1, 8, 100, period_interpolation_inducing_points=1)
     kn3, du3 = e3.sample(seed=1, knots=True, delta_u=True)
     np.testing.assert_allclose(du3.cpu().numpy()[0], O.interpolate_knots(kn3.cpu().numpy()[0], 100, period=1), atol=2e-7)
