@@ -30,7 +30,7 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_groups_stream", "cpmppi_groups_fork", "cpmppi_groups_join", "cpmppi_groups_run", "cpmppi_groups_last_error",
            "cpmppi_comm_set_stamped", "cpmppi_groups_comm_init", "cpmppi_groups_run_gather", "cpmppi_set_pole_mass_rows",
            "cpmppi_rpgd_reserve", "cpmppi_rpgd_step", "cpmppi_cem_reserve", "cpmppi_cem_step", "cpmppi_rollout_cost_gru",
-           "cpmppi_rollout_cost_grad_gru")
+           "cpmppi_rollout_cost_grad_gru", "cpmppi_gru_advance")
 COMM_ID_BYTES, COMM_SLOTS, GATHER_STAMP_FLOATS = 128, 4, 4
 
 
@@ -172,6 +172,7 @@ def load():
     lib.cpmppi_get_profile.argtypes = [vp, C.POINTER(f), C.POINTER(f), u32, C.POINTER(u32)]
     lib.cpmppi_set_gru.argtypes = [vp, C.POINTER(cpmppi_gru_model)]
     lib.cpmppi_gru_predict.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, vp]
+    lib.cpmppi_gru_advance.argtypes = [vp, u32, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost_gru.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost_grad_gru.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]

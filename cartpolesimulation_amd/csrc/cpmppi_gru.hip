@@ -3,6 +3,8 @@
 //
 // Kernel inventory
 //   gru_predict_kernel                      predictor seam with the neural predictor: trajectories [B,H+1,6], hidden states.
+//   gru_advance_kernel                      one exact cell step on (state seen, control chosen), in place on h[E,2,32]: the memory
+//                                           hand-over between two control periods of the device loop.
 //   gru_rollout_cost_kernel<COST,NOISE,F16> the fused MPPI step with the GRU predictor: same contract as rollout_cost_kernel
 //                                           (plugin costs); launched by step_impl through launch_gru_rollout.
 //   gru_cost_only_kernel<COST,F16>          costs of GIVEN input plans under the GRU predictor, nothing of the MPPI update: the
@@ -13,7 +15,7 @@
 //                                           CEM + gradient hybrids over the GRU (gru_adjoint=True).
 // The rollout kernels share one rollout (GruRollout: gru_rollout_init, gru_rollout_step, gru_rollout_total) and differ in where
 // a step's input comes from and in what becomes of the costs; gru_predict_kernel runs the exact cell (gru_step) on its own.
-// Entry points: cpmppi_set_gru, cpmppi_gru_predict, cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru; -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write
+// Entry points: cpmppi_set_gru, cpmppi_gru_predict, cpmppi_gru_advance, cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru; -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write
 // g_gru_stamp_sum are this unit's).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -162,6 +164,35 @@ __global__ __launch_bounds__(BLOCK, 1) void gru_predict_kernel(const GruNorm nm,
     for (int v = 0; v < 16; ++v) {
       h_out[bb * 32 + gru_tile_row(v, lane >> 5)] = h1[v];
       h_out[((size_t)B + bb) * 32 + gru_tile_row(v, lane >> 5)] = h2[v];
+    }
+  }
+}
+
+// The memory hand-over of the device loop: h_io[E,2,32] (the rollout kernels' layout) <- hidden states after ONE exact cell step
+// on (s[E,6], Q[E]), in place.  gru_predict_kernel's mapping (env e on lanes c and c + 32 of a wave, one wave per SIMD for the
+// same reason) and its cell, so what it stores is what that kernel writes to h_out for B = E, H = 1; the head's result is
+// dropped, nothing is de-normalised.  In place is safe: all of a live env's loads precede its stores in its own wave, and no
+// other wave stores to its rows.  A lane beyond E repeats row 0, which block 0 may be rewriting at that moment: what it then
+// computes is undefined but never stored (an MFMA column depends on its own column only, so it reaches no live env either).
+__global__ __launch_bounds__(BLOCK, 1) void gru_advance_kernel(const GruNorm nm, const float* __restrict__ image, uint32_t E,
+                                                            const float* __restrict__ s, const float* __restrict__ Q,
+                                                            float* h_io) {
+  extern __shared__ float lds[];
+  gru_load_image(lds, image, GRU_IMAGE_FLOATS);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, c = lane & 31u;
+  const size_t e = (size_t)blockIdx.x * GRU_ROLLOUTS_PER_BLOCK + wave * 32 + c;
+  const bool valid = e < E;
+  const size_t ee = valid ? e : 0;
+  float* hrow = h_io + ee * 64;
+  f16v h1 = gru_load_hidden(hrow, lane);
+  f16v h2 = gru_load_hidden(hrow + 32, lane);
+  const f16v x = gru_input_tile(nm, s + ee * 6, Q[ee], lane);
+  (void)gru_step(lds, x, h1, h2, lane);
+  if (valid) {
+#pragma unroll
+    for (int v = 0; v < 16; ++v) {
+      hrow[gru_tile_row(v, lane >> 5)] = h1[v];
+      hrow[32 + gru_tile_row(v, lane >> 5)] = h2[v];
     }
   }
 }
@@ -767,6 +798,19 @@ int cpmppi_gru_predict(cpmppi_handle* h, uint32_t B, uint32_t horizon, const flo
   hipLaunchKernelGGL(gru_predict_kernel, dim3((B + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK), dim3(BLOCK),
                      (size_t)GRU_IMAGE_FLOATS * sizeof(float), (hipStream_t)stream, h->gru_norm,
                      (const float*)h->gru_image, B, horizon, s0, Q, h0, traj_out, h_out);
+  return launched(h);
+}
+
+int cpmppi_gru_advance(cpmppi_handle* h, uint32_t E, const float* s, const float* Q, float* h_io, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_advance: no model set (cpmppi_set_gru)");
+  if (E == 0 || E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_advance: E out of range");
+  if (!s || !Q || !h_io) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_advance: s, Q, h_io are required");
+  CPMPPI_ON_DEVICE(h);
+  // (one launch, nothing allocated, nothing awaited: the call can be captured)
+  hipLaunchKernelGGL(gru_advance_kernel, dim3((E + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK), dim3(BLOCK),
+                     (size_t)GRU_IMAGE_FLOATS * sizeof(float), (hipStream_t)stream, h->gru_norm, (const float*)h->gru_image, E, s,
+                     Q, h_io);
   return launched(h);
 }
 

@@ -54,6 +54,7 @@ class MPPIEngine:
     _fixed_stream = _fixed_stream_obj = None                    # use_stream: the raw handle / the torch stream (keeps it alive)
     _m_rows = _m_rows_own = None                                # set_pole_mass_rows: the registered tensor / the engine's own buffer
     _m_pole_obj = None                                          # apply_pole_mass_of: the scalar object last applied
+    has_gru = False                                             # set_gru: a network is attached
 
     def __init__(self, E, mppi: MPPIConfig = None, phys: PhysicalParameters = None, device=0):
         self._init_common(E, mppi, phys, device)
@@ -496,6 +497,19 @@ class MPPIEngine:
         self._check(self.lib.cpmppi_gru_predict(self._h, B, H, _ptr(s0), _ptr(Q), _ptr(h0), _ptr(traj), _ptr(h_out),
                                                 self._stream()))
         return (traj, h_out) if return_hidden else traj
+
+    def gru_advance(self, s, Q, h):
+        """cpmppi_gru_advance: each env's memory ``h`` [E,2,32] (the layout ``step(h0=...)`` reads) moved on IN PLACE by one cell
+        step on the state seen ``s`` [E,6] and the control chosen ``Q`` [E] - the hand-over between two control periods
+        (update_internal_state).  All three are contiguous float32 tensors on the device; one launch, nothing allocated, so the
+        call can be captured.  -> ``h``."""
+        E = device_tensor("h", h, tail=(2, 32), note=_IN_PLACE).shape[0]
+        if device_tensor("s", s, tail=(6,)).shape[0] != E or device_tensor("Q", Q).shape != (E,):
+            raise ValueError(f"s must be [{E},6] and Q [{E}] for h [{E},2,32]")
+        if E == 0 or E > self.E:
+            raise ValueError(f"h must be [0<E<={self.E},2,32], got {tuple(h.shape)}")
+        self._check(self.lib.cpmppi_gru_advance(self._h, E, _ptr(s), _ptr(Q), _ptr(h), self._stream()))
+        return h
 
     # ------------------------------------------------------------------ cost-only launch and CEM (SURVEY §8f N4)
     def _per_env(self, x, E):

@@ -4,7 +4,9 @@ This is the build's counterpart of the reference's experiment loop (run_data_gen
 CartPole/data_generator.py:259-367 -> CartPole.run_cartpole_random_experiment, CartPole/__init__.py:659-735, whose
 inner update_state loop is :283-324): every control period the controller sees the state and holds Q for
 dt_control / dt_simulation plant steps.  Plant (cpmppi_plant_advance) and controller (cpmppi_step) both run on the
-GPU and no value crosses PCIe inside the loop; the simulator's measurement chain (latency, measurement noise, vertical angle offset:
+GPU and no value crosses PCIe inside the loop.  With ``predictor="GRU"`` the controller's plant model is the network of
+``engine.set_gru`` and a third launch sits between the two: cpmppi_gru_advance moves each env's memory on with the state the controller
+saw and the control it chose (update_internal_state, controller_mppi_cartpole.py:566-567).  The simulator's measurement chain (latency, measurement noise, vertical angle offset:
 cartpole_physical_parameters.yml:18-28, all off as shipped), its additive control disturbance (:13-15, amplitude 0 as shipped) and its
 parameter updaters / controller informer (:29-52) come as tables of the batch (schedule.apply_parameter_schedule).
 
@@ -34,6 +36,33 @@ def generate_random_initial_states(E, rng, track_half_length=0.198, init_limits=
     return s
 
 
+PREDICTORS = ("ODE_v0", "GRU")
+
+
+def check_predictor(engine, predictor, h0=None, optimizer=None, knots_fn=None):
+    """The controller's plant model in the device loop: "ODE_v0" (the engine's equations) or "GRU" (the network of set_gru, whose
+    memory the loop hands from period to period).  ValueError for what the loop cannot run."""
+    if predictor not in PREDICTORS:
+        raise ValueError(f"predictor must be one of {PREDICTORS}, got {predictor!r}")
+    if predictor != "GRU":
+        if h0 is not None:
+            raise ValueError("h0 is the memory of the GRU predictor: pass predictor='GRU'")
+        return False
+    if not getattr(engine, "has_gru", False):
+        raise ValueError("predictor='GRU' needs a network: the engine has no model (engine.set_gru)")
+    if optimizer is not None:
+        raise ValueError("predictor='GRU' is the fused MPPI step over the network; an optimizer= object carries its own predictor "
+                         "and memory (gru_model=): give one or the other")
+    if knots_fn is not None:
+        raise ValueError("predictor='GRU' draws its perturbations in the kernel (Philox): knots_fn is not supported with it")
+    return True
+
+
+def gru_memory(engine, E, h0):
+    """The network's memory a run starts from: zeros [E,2,32], or a copy of ``h0`` (the run advances its own)."""
+    return engine.zeros(E, 2, 32) if h0 is None else engine.tensor(h0, (E, 2, 32)).clone()
+
+
 class BatchedCartPoleExperiment:
     def __init__(self, engine, dt_simulation=0.002, dt_control=0.02, seed=0):
         self.engine = engine
@@ -42,9 +71,13 @@ class BatchedCartPoleExperiment:
         self.seed = int(seed)
 
     def run(self, s0, n_control_steps, target_position=0.0, target_equilibrium=1.0, L=None, record=True,
-            env_offset=0, graph=False, steps_per_graph=10):
-        """-> dict(states[T+1,E,6], Q[T,E]) as device tensors (only if ``record``), final state, final u_nom."""
+            env_offset=0, graph=False, steps_per_graph=10, predictor="ODE_v0", h0=None):
+        """-> dict(states[T+1,E,6], Q[T,E]) as device tensors (only if ``record``), final state, final u_nom.
+        ``predictor="GRU"``: the controller rolls out with the engine's network from each env's memory ``h0`` [E,2,32] (None: zeros),
+        which cpmppi_gru_advance moves on every period with (state seen, control chosen) - three launches per control period; the
+        result gains ``memory`` [E,2,32], the memory after the last period.  ``L`` still goes to the plant; the network knows none."""
         eng = self.engine
+        gru = check_predictor(eng, predictor, h0)
         s = eng.tensor(s0).clone()
         E = s.shape[0]
         tp = eng.tensor(np.broadcast_to(np.asarray(target_position, dtype=np.float32), (E,)).copy())
@@ -56,15 +89,27 @@ class BatchedCartPoleExperiment:
         Qs = eng.empty(n_control_steps, E) if record else None
         if record:
             states[0] = s
+        h = gru_memory(eng, E, h0) if gru else None
         if graph:
-            return self._run_graph(s, u_nom, Q, tp, te, Lt, states, Qs, n_control_steps, env_offset, int(steps_per_graph))
+            return self._run_graph(s, u_nom, Q, tp, te, Lt, states, Qs, n_control_steps, env_offset, int(steps_per_graph), h)
         for t in range(n_control_steps):
-            eng.step(s, u_nom, tp, te, L=Lt, seed=self.seed, offset=t, env_offset=env_offset, Q_out=Q)
+            if gru:
+                eng.step(s, u_nom, tp, te, seed=self.seed, offset=t, env_offset=env_offset, Q_out=Q, predictor="GRU", h0=h)
+                eng.gru_advance(s, Q, h)                       # before the plant moves s: the state the controller saw
+            else:
+                eng.step(s, u_nom, tp, te, L=Lt, seed=self.seed, offset=t, env_offset=env_offset, Q_out=Q)
             # plant + this period's row of the recording in ONE launch (two kernels per control step in all)
             eng.plant_advance(s, Q, L=Lt, n_substeps=self.n_sub, dt_sim=self.dt_simulation, states_log=states, Q_log=Qs, row=t)
-        return dict(states=states, Q=Qs, final_state=s, u_nom=u_nom)
+        return self._result(states, Qs, s, u_nom, h)
 
-    def _run_graph(self, s, u_nom, Q, tp, te, Lt, states, Qs, n_control_steps, env_offset, per_graph):
+    @staticmethod
+    def _result(states, Qs, s, u_nom, h):
+        res = dict(states=states, Q=Qs, final_state=s, u_nom=u_nom)
+        if h is not None:
+            res["memory"] = h
+        return res
+
+    def _run_graph(self, s, u_nom, Q, tp, te, Lt, states, Qs, n_control_steps, env_offset, per_graph, h=None):
         """The same loop as ONE captured HIP graph of `per_graph` control steps, replayed: controller step (Philox counter in device
         memory, `offset_dev`), plant + recording at the row the same counter names — no launch argument changes between steps, the
         host only enqueues replays (the launch-bound case: few envs, ~70 us of GPU work per control step)."""
@@ -73,7 +118,11 @@ class BatchedCartPoleExperiment:
                                                                               # = recording row (after the step: + 1)
 
         def one_step():
-            eng.step(s, u_nom, tp, te, L=Lt, seed=self.seed, offset_dev=counter, env_offset=env_offset, Q_out=Q)
+            if h is not None:
+                eng.step(s, u_nom, tp, te, seed=self.seed, offset_dev=counter, env_offset=env_offset, Q_out=Q, predictor="GRU", h0=h)
+                eng.gru_advance(s, Q, h)
+            else:
+                eng.step(s, u_nom, tp, te, L=Lt, seed=self.seed, offset_dev=counter, env_offset=env_offset, Q_out=Q)
             eng.plant_advance(s, Q, L=Lt, n_substeps=self.n_sub, dt_sim=self.dt_simulation, states_log=states, Q_log=Qs,
                               row_dev=counter)
 
@@ -90,10 +139,11 @@ class BatchedCartPoleExperiment:
             g.replay()
         for _ in range(n_control_steps % per_graph):          # the remainder, launched directly with the same device counter
             one_step()
-        return dict(states=states, Q=Qs, final_state=s, u_nom=u_nom)
+        return self._result(states, Qs, s, u_nom, h)
 
     # ------------------------------------------------------------------ the data generator's experiments (moving targets)
-    def run_schedule(self, batch, env_offset=0, graph=False, steps_per_graph=10, knots_fn=None, u_nom0=None, optimizer=None):
+    def run_schedule(self, batch, env_offset=0, graph=False, steps_per_graph=10, knots_fn=None, u_nom0=None, optimizer=None,
+                     predictor="ODE_v0", h0=None):
         """Run the E experiments of a schedule.ExperimentBatch to their end: CartPole.run_cartpole_random_experiment
         (CartPole/__init__.py:659-735) for all of them at once.  Per control period two launches - the fused MPPI step, reading
         the period's target position / equilibrium (/ pole length) from three [E] vectors, and cpmppi_plant_step, which advances
@@ -107,8 +157,14 @@ class BatchedCartPoleExperiment:
         .configure(...).optimizer`: cem, rpgd, gradient, ...) computes the controls instead of the fused MPPI step - host-paced, one
         `optimizer.step` per control period on device tensors, the plant / schedule / recording launch unchanged.  A FUSED rpgd /
         gradient / cem optimizer (`fused=True`: one cpmppi_rpgd_step / cpmppi_cem_step per period, its step counter on the device) is
-        not paced by the host and may be captured (``graph=True``) like the MPPI step."""
-        run = ScheduleRun(self.engine, batch, self.seed, env_offset=env_offset, knots_fn=knots_fn, u_nom0=u_nom0, optimizer=optimizer)
+        not paced by the host and may be captured (``graph=True``) like the MPPI step.
+        ``predictor="GRU"``: the fused MPPI step over the engine's network (set_gru) - per control period three launches, the step
+        from each experiment's memory ``h0`` [E,2,32] (None: zeros), cpmppi_gru_advance on (the MEASURED state the controller was
+        given, the control it chose), the plant; launched or captured.  The result gains ``memory``, the memory after every
+        controller call made (the final one included).  Not with ``optimizer=`` (such an object carries its own network and
+        memory) and not with ``knots_fn``."""
+        run = ScheduleRun(self.engine, batch, self.seed, env_offset=env_offset, knots_fn=knots_fn, u_nom0=u_nom0, optimizer=optimizer,
+                          predictor=predictor, h0=h0)
         if batch.dt_simulation != self.dt_simulation or batch.n_ctrl != self.n_sub:
             raise ValueError("the batch was drawn for other time scales than this experiment runner's")
         if graph and optimizer is not None and not run.fused:
@@ -158,9 +214,10 @@ class ControllerMass:
       varies  it changes between calls: the host paces such a run call by call (no captured graph, one cpmppi_groups_run per period)
     `bind` makes the device side, `apply(c)` goes before controller call c, `release` after the last one."""
 
-    def __init__(self, batch, mppi):
+    def __init__(self, batch, mppi, network=False):
+        """``network``: the controller rolls out with the GRU, which reads no pole mass - kind "none" whatever the batch's table."""
         self.values = self.table = None
-        if batch.m_pole_table is not None and mppi.predictor_type == "ODE":
+        if batch.m_pole_table is not None and mppi.predictor_type == "ODE" and not network:
             self.values, self.table = controller_pole_mass(batch, per_env=mppi.per_env_pole_mass)
         self.kind = "value" if self.values is not None else "rows" if self.table is not None else "none"
         per_call = self.values if self.values is not None else self.table
@@ -214,10 +271,13 @@ class ScheduleRun:
     """The device loop of BatchedCartPoleExperiment.run_schedule as an object that enqueues one piece at a time, so that several
     runs - env groups on their own streams, pipeline.run_schedule_groups - can be interleaved by one host thread."""
 
-    def __init__(self, engine, batch, seed, env_offset=0, knots_fn=None, u_nom0=None, optimizer=None, bind_mass=True):
+    def __init__(self, engine, batch, seed, env_offset=0, knots_fn=None, u_nom0=None, optimizer=None, bind_mass=True,
+                 predictor="ODE_v0", h0=None):
         """``bind_mass`` False: the caller binds `self.mass` to the engines that launch (pipeline.run_schedule_groups)."""
         self.eng, self.b, self.seed, self.env_offset, self.knots_fn = engine, batch, int(seed), int(env_offset), knots_fn
         self.optimizer = optimizer
+        self.gru = check_predictor(engine, predictor, h0, optimizer, knots_fn)
+        self.h = gru_memory(engine, batch.E, h0) if self.gru else None     # the network's memory [E,2,32], advanced in place
         self.fused = bool(getattr(optimizer, "fused", False))      # a fused optimizer (rpgd, gradient, the cem family): one library call per period
         if optimizer is not None:
             if getattr(optimizer, "num_envs", batch.E) != batch.E:
@@ -290,7 +350,7 @@ class ScheduleRun:
         if eng.mppi.cost_function_specification in PREVIOUS_INPUT_COSTS:
             self.prev_Q = eng.zeros(E)
             self.plant.update(Q_applied_out=self.prev_Q)
-        self.mass = ControllerMass(b, eng.mppi)
+        self.mass = ControllerMass(b, eng.mppi, network=self.gru)
         if bind_mass:                                              # (an optimizer object registers the row with its own engine)
             self.mass.bind([eng], register=optimizer is None)
         self.counter, self.graph, self.per = None, None, 0
@@ -303,6 +363,16 @@ class ScheduleRun:
     @property
     def _prev(self):
         return {} if self.prev_Q is None else {"previous_input": self.prev_Q}
+
+    @property
+    def _model(self):
+        """What tells the fused step its plant model: the pole length the controller is told, or the network and its memory."""
+        return dict(predictor="GRU", h0=self.h) if self.gru else dict(L=self.cur_L)
+
+    def _advance_memory(self):
+        """Behind a GRU step, before the plant launch refills s_ctrl: the memory moves on with what the controller saw and chose."""
+        if self.gru:
+            self.eng.gru_advance(self.s_ctrl, self.Q, self.h)
 
     @property
     def periods_left(self):
@@ -344,7 +414,8 @@ class ScheduleRun:
             noise = dict(seed=self.seed, offset_dev=self.counter, env_offset=self.env_offset)
         else:
             noise = dict(seed=self.seed, offset=c, env_offset=self.env_offset)
-        eng.step(self.s_ctrl, self.u_nom, self.cur_tp, self.cur_te, L=self.cur_L, Q_out=self.Q, **noise, **self._prev)
+        eng.step(self.s_ctrl, self.u_nom, self.cur_tp, self.cur_te, Q_out=self.Q, **self._model, **noise, **self._prev)
+        self._advance_memory()
 
     def _plant_step(self, n_substeps, c):
         """The plant launch of control period c: the period from the host, or - captured - from the device counter."""
@@ -353,14 +424,15 @@ class ScheduleRun:
 
     def _period(self, c):
         if self.counter is None and self.knots_fn is None and self.optimizer is None:
-            # the launched loop: two library calls per period on argument blocks built once (the Python-side argument handling of
+            # the launched loop: two library calls per period (three with the network) on argument blocks built once (the Python-side argument handling of
             # step + plant_step is ~30 us per period - more than the GPU needs for a few dozen envs)
             self.mass.apply(c)
             if self._prep is None:
-                self._prep = self.eng.prepare_step(self.s_ctrl, self.u_nom, self.cur_tp, self.cur_te, L=self.cur_L, seed=self.seed, offset=0,
-                                                   env_offset=self.env_offset, Q_out=self.Q, **self._prev)
+                self._prep = self.eng.prepare_step(self.s_ctrl, self.u_nom, self.cur_tp, self.cur_te, seed=self.seed, offset=0,
+                                                   env_offset=self.env_offset, Q_out=self.Q, **self._model, **self._prev)
                 self._prep_plant = self.eng.prepare_plant_step(self.s, self.Q, self.b.n_ctrl, period=0, **self.plant)
             self._prep.run(offset=c)
+            self._advance_memory()
             self._prep_plant.run(period=c)
             return
         self._control(c)
@@ -425,4 +497,7 @@ class ScheduleRun:
         return self.result()
 
     def result(self):
-        return dict(states=self.states, dd=self.dd, Q=self.Qs, final_state=self.s, u_nom=self.u_nom, batch=self.b)
+        res = dict(states=self.states, dd=self.dd, Q=self.Qs, final_state=self.s, u_nom=self.u_nom, batch=self.b)
+        if self.gru:
+            res["memory"] = self.h
+        return res

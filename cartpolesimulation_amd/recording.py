@@ -243,7 +243,7 @@ FUSED_OPTIMIZERS = ("rpgd", "rpgd-tf", "gradient", "gradient-tf", "cem", "cem-tf
 
 def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, seed=None, cartpole_seed=None, L=None, native=True,
                      graph=False, secondary_experiment_index=None, controller_name="mpc", optimizer_name="mppi", title=None, groups=1,
-                     rank=0, world=1, parameters=None, optimizer=None):
+                     rank=0, world=1, parameters=None, optimizer=None, gru_model=None):
     """Batched run_data_generator: ``config`` = config_data_gen.yml as a dict (or overrides of the shipped file, see
     schedule.merged_config) - length_of_experiment, the three dt, the random initial state, the target trace's turning points
     and interpolation types, the target-equilibrium dwell times, number_of_experiments, ML_Pipeline_mode / split.  All
@@ -264,7 +264,12 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
     num_envs=n).configure().optimizer` - the shipped config_controllers.yml names rpgd) controls the plants instead of the fused MPPI
     step; `engine` may then be None (the optimizer's own engine runs the plant).  A staged optimizer is paced by the host
     (graph=False); a fused rpgd / gradient / cem optimizer (`fused=True`) may run captured (graph=True).  Env groups and the multi-GPU
-    gather stay with the MPPI step."""
+    gather stay with the MPPI step.
+    ``gru_model``: the weights dict of ``MPPIEngine.set_gru`` or a ``GRU-6IN-32H1-32H2-5OUT-*`` model folder
+    (model_folder.load_gru_model) - the fused MPPI step rolls out with that network instead of the equations, its memory handed
+    from control period to control period on the device (harness.run_schedule(predictor="GRU")); launched or captured
+    (``graph=True``).  The header's optimizer line then names the predictor.  Not with ``groups`` > 1 (the env groups' period loop
+    knows no memory hand-over) and not with ``optimizer=`` (an optimizer object is given its network as ``gru_model=`` itself)."""
     import time
     from .harness import BatchedCartPoleExperiment
     from .schedule import RandomExperimentSetter, merged_config
@@ -275,6 +280,17 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
     if cfg.get("seed") is None:
         raise ValueError("config['seed'] is empty: the reference then seeds from the clock; give a seed for a reproducible batch")
     cseed = cartpole_seed if cartpole_seed is not None else cfg["seed"] + 1
+    if gru_model is not None:
+        if int(groups) > 1:
+            raise ValueError("gru_model: env groups run the MPPI step without the memory hand-over of the network: groups=1")
+        if optimizer is not None:
+            raise ValueError("gru_model goes with the fused MPPI step: an optimizer= object takes its network itself (gru_model= of "
+                             "its configuration)")
+        if isinstance(gru_model, (str, os.PathLike)):
+            from .model_folder import load_gru_model
+            gru_model = load_gru_model(os.fspath(gru_model))
+        engine.set_gru(gru_model)
+        optimizer_name = f"{optimizer_name} (predictor: GRU)"
     if optimizer is not None:
         if int(groups) > 1:
             raise ValueError("env groups run the fused MPPI step only: an optimizer object needs groups=1")
@@ -314,7 +330,8 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
             eg.close()
     else:
         exp = BatchedCartPoleExperiment(engine, batch.dt_simulation, batch.dt_control, seed=cfg["seed"])
-        res = exp.run_schedule(batch, graph=graph, env_offset=_first, optimizer=optimizer)
+        res = exp.run_schedule(batch, graph=graph, env_offset=_first, optimizer=optimizer,
+                               **(dict(predictor="GRU") if gru_model is not None else {}))
         torch.cuda.synchronize()
     per_call = (time.perf_counter() - t0) / (batch.n_periods + 1)   # what Q_update_time can honestly say: wall time per controller update of the batch
     phys = engine.phys
@@ -362,6 +379,11 @@ def main(argv=None):
     ap.add_argument("--fused", action="store_true",
                     help="rpgd / gradient / cem / cem-naive-grad / cem-grad-bharadhwaj: the whole control step as one library call "
                          "(cpmppi_rpgd_step, cpmppi_cem_step) and the closed loop captured as a graph, the step counter on the device")
+    ap.add_argument("--gru-model", default=None, metavar="FOLDER",
+                    help="a GRU-6IN-32H1-32H2-5OUT-* model folder: the MPPI step rolls out with that network (its memory stays on the "
+                         "device from period to period); costs quadratic_boundary_grad_minimal and default, --groups 1")
+    ap.add_argument("--graph", action="store_true",
+                    help="mppi: the closed loop captured as a graph of control periods, replayed (the step counter on the device)")
     ap.add_argument("--cost", default=None,
                     choices=["legacy_mppi_cartpole", "default", "quadratic_boundary_grad_minimal", "quadratic_boundary_grad"])
     args = ap.parse_args(argv)
@@ -390,7 +412,9 @@ def main(argv=None):
         # an `m_pole:` updater may give every experiment its own mass: predictor "ODE" is then told per experiment, as the reference's is
         cfg.per_env_pole_mass = cfg.predictor_type == "ODE" and bool(parameters and parameters.get("m_pole") is not None)
     else:
-        n, h, cost = args.rollouts or 3500, args.horizon or 35, args.cost or "legacy_mppi_cartpole"
+        # (the network runs under the two plugin costs only: with --gru-model the default is the first of them)
+        default_cost = "quadratic_boundary_grad_minimal" if args.gru_model is not None else "legacy_mppi_cartpole"
+        n, h, cost = args.rollouts or 3500, args.horizon or 35, args.cost or default_cost
         cfg = legacy_mppi_config(num_rollouts=n, mpc_horizon=h) if cost == "legacy_mppi_cartpole" \
             else MPPIConfig(num_rollouts=n, mpc_horizon=h, cost_function_specification=cost)
         dg = dict(length_of_experiment=10.0, dt=dict(saving=0.02), number_of_experiments=64)
@@ -431,9 +455,13 @@ def main(argv=None):
         raise SystemExit("--fused: the fused control step is built for rpgd, gradient, cem, cem-naive-grad and "
                          "cem-grad-bharadhwaj, not 'mppi'")
     # a fused optimizer runs captured unless the run cannot be (a controller pole mass that changes between calls, warm-up)
-    graph = bool(args.fused) and not optimizer.warmup
+    if args.graph and optimizer is not None and not args.fused:
+        raise SystemExit(f"--graph: {opt_name!r} as a staged optimizer is paced by the host (mppi, or --fused, can be captured)")
+    graph = (bool(args.fused) and not optimizer.warmup) or (bool(args.graph) and optimizer is None)
+    if args.gru_model is not None and optimizer is not None:
+        raise SystemExit(f"--gru-model: the network in the device loop is built for the fused MPPI step (--optimizer mppi), not {opt_name!r}")
     paths = generate_dataset(eng, n_exp, out, seed=seed, rank=rank, world=world, config=dg, groups=args.groups, parameters=parameters,
-                             optimizer=optimizer, graph=graph,
+                             optimizer=optimizer, graph=graph, gru_model=args.gru_model,
                              secondary_experiment_index=None if args.secondary_experiment_index < 0 else args.secondary_experiment_index)
     print(f"wrote {len(paths)} recordings under {os.path.dirname(paths[0])}")
 

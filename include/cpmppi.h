@@ -54,7 +54,8 @@ extern "C" {
                                       a caller-given rccl_path now wins over an RCCL the process has already loaded;
                                       cpmppi_set_pole_mass_rows (a new entry point: no layout and no existing semantics change);
                                       cpmppi_rpgd_step / cpmppi_rpgd_reserve / cpmppi_rpgd_args (new entry points, likewise);
-                                      cpmppi_cem_step / cpmppi_cem_reserve / cpmppi_cem_args (new entry points, likewise). */
+                                      cpmppi_cem_step / cpmppi_cem_reserve / cpmppi_cem_args (new entry points, likewise);
+                                      cpmppi_gru_advance (a new entry point, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -309,6 +310,16 @@ int cpmppi_set_gru(cpmppi_handle* h, const cpmppi_gru_model* model);
  * traj[B,H+1,6], h_out[2,B,32] or NULL (device pointers). */
 int cpmppi_gru_predict(cpmppi_handle* h, uint32_t B, uint32_t horizon, const float* s0, const float* Q, const float* h0,
                        float* traj_out, float* h_out, void* stream);
+
+/* Advance each env's GRU memory by one control step, in place: h_io[E,2,32] (the layout of cpmppi_step_args.h0)
+ * <- hidden states after one cell step on (s[E,6], Q[E]) - update_internal_state of the reference
+ * (Control_Toolkit_ASF/Controllers/controller_mppi_cartpole.py:566-567) for every env at once.  Exact-f32 chain in both math
+ * modes: the value cpmppi_gru_predict(B = E, horizon = 1, h0 = transpose(h_io)) writes to h_out, bit for bit.
+ * ONE launch on `stream`, no allocation, no host synchronisation: can be captured.  With it a neural control period of the device
+ * loop is cpmppi_step(predictor = CPMPPI_PREDICTOR_GRU, h0 = h_io), cpmppi_gru_advance, cpmppi_plant_step.
+ * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned (cpmppi_last_error: "cpmppi_gru_advance: ...") when no model is set,
+ * E == 0 or E > cfg.E, or a pointer is NULL. */
+int cpmppi_gru_advance(cpmppi_handle* h, uint32_t E, const float* s, const float* Q, float* h_io, void* stream);
 
 /* Rollout + cost only (no update): per-rollout trajectory cost S[E,N] of GIVEN input sequences inputs[E,N,H] under the
  * handle's plugin cost — cost_function.get_trajectory_cost(predictor.predict_core(s, Q), Q) fused; the building block of

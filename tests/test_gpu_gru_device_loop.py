@@ -1,0 +1,170 @@
+"""GPU: the learned model in the device loop - BatchedCartPoleExperiment.run / run_schedule(predictor="GRU") and
+generate_dataset(gru_model=...): per control period the fused GRU step, cpmppi_gru_advance (the memory's hand-over), the plant.
+
+The reference of every statement is a loop composed from calls that existed before the hand-over did: eng.step(predictor="GRU",
+h0=h), the optimizers' hand-over through the predict seam (h [E,2,32] -> [2,E,32], gru_predict over one step, back), the plant
+launch - same seed, same Philox offsets.  The device loop computes the same statements on the same inputs (the advance is the
+predict seam's cell bit for bit, tests/test_gpu_gru_advance.py), so everything is compared bit for bit: states, controls, nominal
+sequences, memory; launched against captured likewise.  The one oracle comparison - the memory after T periods against
+oracle_np.gru_predict iterated over the recorded (state, control) pairs - uses the project's hidden-state rule 1e-4 + |oracle32 -
+oracle64|.
+"""
+import functools
+import os
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+torch = pytest.importorskip("torch")
+
+from oracle import oracle_np as O  # noqa: E402
+
+f32 = np.float32
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "gru_c5.npz")
+N, H, T = 64, 6, 4
+
+
+@functools.lru_cache(maxsize=None)
+def golden_model():
+    g = np.load(GOLDEN)
+    return {k: g[k] for k in g.files if k not in ("s0", "Q", "h0", "traj", "h_final")}
+
+
+def engine(E, n=N, h=H, **kw):
+    from cartpolesimulation_amd.engine import MPPIEngine
+    from cartpolesimulation_amd.configs import MPPIConfig
+    eng = MPPIEngine(E, MPPIConfig(num_rollouts=n, mpc_horizon=h, **kw))
+    eng.set_gru(golden_model())
+    return eng
+
+
+def hand_over(eng, s, Q, h):
+    """The optimizers' memory hand-over (_OptimizerBase._advance_memory): through the predict seam, with the transposes."""
+    E = h.shape[0]
+    _, h_new = eng.gru_predict(s, Q.reshape(E, 1), h0=h.transpose(0, 1).contiguous(), return_hidden=True)
+    h.copy_(h_new.transpose(0, 1))
+
+
+def host(res, keys):
+    return {k: res[k].cpu().numpy() for k in keys}
+
+
+def same(a, b, what):
+    for k in a:
+        assert np.array_equal(a[k].view(np.uint32), b[k].view(np.uint32)), f"{what}: {k} differs, worst {np.abs(a[k] - b[k]).max():.3e}"
+
+
+@pytest.mark.parametrize("math_mode", ["fast", "precise"])
+@pytest.mark.parametrize("cost", ["quadratic_boundary_grad_minimal", "default"])
+@pytest.mark.parametrize("E", [3, 130])
+def test_run_with_the_network_equals_the_composed_loop(E, cost, math_mode):
+    """run(predictor="GRU") over 4 control periods, 3 envs and 130 (a second block of the advance with two live rows): launched ==
+    the composed loop == captured (steps_per_graph = 3: one replay and one remainder step); a given memory moves the first control;
+    the memory follows the oracle's recurrence over the recorded states and controls."""
+    from cartpolesimulation_amd.harness import BatchedCartPoleExperiment, generate_random_initial_states
+    eng = engine(E, cost_function_specification=cost, math_mode=math_mode)
+    rng = np.random.Generator(np.random.SFC64(17 + E))
+    s0 = generate_random_initial_states(E, rng)
+    tp = rng.uniform(-0.1, 0.1, E).astype(f32)
+    L = np.linspace(0.3, 0.45, E).astype(f32)
+    exp = BatchedCartPoleExperiment(eng, seed=5)
+    keys = ("states", "Q", "u_nom", "memory", "final_state")
+    launched = host(exp.run(s0, T, target_position=tp, L=L, env_offset=2, predictor="GRU"), keys)
+    assert launched["memory"].shape == (E, 2, 32)
+
+    s, u, h, Q = eng.tensor(s0).clone(), eng.zeros(E, H), eng.zeros(E, 2, 32), eng.empty(E)
+    tp_t, te_t, L_t = eng.tensor(tp), eng.tensor(np.ones(E, f32)), eng.tensor(L)
+    states, Qs = eng.empty(T + 1, E, 6), eng.empty(T, E)
+    states[0] = s
+    for t in range(T):
+        eng.step(s, u, tp_t, te_t, seed=5, offset=t, env_offset=2, Q_out=Q, predictor="GRU", h0=h)
+        hand_over(eng, s, Q, h)
+        eng.plant_advance(s, Q, L=L_t, n_substeps=exp.n_sub, dt_sim=exp.dt_simulation, states_log=states, Q_log=Qs, row=t)
+    composed = dict(states=states.cpu().numpy(), Q=Qs.cpu().numpy(), u_nom=u.cpu().numpy(), memory=h.cpu().numpy(),
+                    final_state=s.cpu().numpy())
+    same(launched, composed, "launched vs composed")
+    assert np.abs(launched["Q"]).max() > 0.01 and np.abs(launched["memory"]).max() > 0.01
+
+    captured = host(exp.run(s0, T, target_position=tp, L=L, env_offset=2, predictor="GRU", graph=True, steps_per_graph=3), keys)
+    same(launched, captured, "launched vs captured")
+
+    h0 = (0.5 * rng.standard_normal((E, 2, 32))).astype(f32)
+    given = host(exp.run(s0, 1, target_position=tp, L=L, env_offset=2, predictor="GRU", h0=h0), keys)
+    assert np.any(given["Q"][0] != launched["Q"][0]), "the memory handed in is not read"
+
+    h32, h64 = np.zeros((2, E, 32), f32), np.zeros((2, E, 32), np.float64)
+    for t in range(T):
+        h32 = O.gru_predict(golden_model(), launched["states"][t], launched["Q"][t][:, None], h32)[1]
+        h64 = O.gru_predict(golden_model(), launched["states"][t], launched["Q"][t][:, None], h64, dtype=np.float64)[1]
+    d, gap = np.abs(launched["memory"] - h32.transpose(1, 0, 2)), np.abs(h32 - h64).transpose(1, 0, 2)
+    assert np.all(d <= 1e-4 + gap), f"memory off the oracle's recurrence by {d.max():.2e}"
+    eng.close()
+
+
+def test_run_schedule_with_the_network_feeds_the_measured_state_to_the_memory():
+    """run_schedule(batch, predictor="GRU") with latency and measurement noise on (the controller does not see the true state) and a
+    length of 6.5 control periods: launched == captured == the composed loop that hands the MEASURED state to the memory; the
+    composed loop that hands it the true state differs."""
+    from cartpolesimulation_amd import schedule as SC
+    from cartpolesimulation_amd.harness import BatchedCartPoleExperiment, ScheduleRun
+    E, n, h = 4, 128, 8
+    cfg = dict(seed=51, length_of_experiment=0.13, dt=dict(saving=0.004), keep_target_equilibrium_x_seconds_up=0.05,
+               turning_points=dict(track_relative_complexity=12),
+               random_initial_state=dict(init_limits=dict(angle=[0.0, 20.0], angleD=40.0, position=0.4, positionD=0.2)))
+    prm = dict(latency=0.005, seed=14,
+               noise=dict(noise_mode="ON", sigma_angle=0.01, sigma_position=0.002, sigma_angleD=0.2, sigma_positionD=0.02))
+    b = SC.apply_parameter_schedule(SC.RandomExperimentSetter(cfg).draw(E, 93), prm, seed=94)
+    assert b.n_sim > b.n_periods * b.n_ctrl and b.measurement_noise is not None and b.latency > 0
+    eng = engine(E, n, h)
+    exp = BatchedCartPoleExperiment(eng, seed=9)
+    keys = ("states", "dd", "Q", "u_nom", "memory", "final_state")
+    launched = host(exp.run_schedule(b, predictor="GRU"), keys)
+    captured = host(exp.run_schedule(b, predictor="GRU", graph=True, steps_per_graph=4), keys)
+    same(launched, captured, "launched vs captured")
+
+    def composed(measured):
+        run = ScheduleRun(eng, b, 9)                              # the batch's buffers, tables and plant arguments; never stepped itself
+        mem = eng.zeros(E, 2, 32)
+        for c in range(b.n_periods + 1):
+            eng.step(run.s_ctrl, run.u_nom, run.cur_tp, run.cur_te, seed=9, offset=c, Q_out=run.Q, predictor="GRU", h0=mem)
+            hand_over(eng, run.s_ctrl if measured else run.s, run.Q, mem)
+            eng.plant_step(run.s, run.Q, b.n_ctrl if c < b.n_periods else run.tail, period=c, **run.plant)
+        out = host(run.result(), ("states", "dd", "Q", "u_nom", "final_state"))
+        out["memory"] = mem.cpu().numpy()
+        return out
+
+    by_hand = composed(True)
+    same({k: launched[k] for k in by_hand}, by_hand, "launched vs composed")
+    true_state = composed(False)
+    assert not np.array_equal(true_state["memory"], launched["memory"]) and not np.array_equal(true_state["Q"], launched["Q"])
+    assert launched["Q"].shape == (b.n_periods + 1, E) and np.abs(launched["Q"]).max() > 0.01
+    eng.close()
+
+
+def test_generate_dataset_with_a_network_launched_and_captured(tmp_path):
+    """generate_dataset(gru_model=...) for 2 experiments of 0.2 s: the recordings of the launched and of the captured loop are the
+    same bytes - comment block, column names and every field but those of the last column, Q_update_time, which holds the run's
+    wall-clock time per controller update (the one column no two runs share; tests/test_recording.py drops it likewise)."""
+    from cartpolesimulation_amd import recording as R
+    eng = engine(2, 128, 8)
+    cfg = dict(length_of_experiment=0.2, dt=dict(saving=0.01), keep_target_equilibrium_x_seconds_up=0.1,
+               turning_points=dict(track_relative_complexity=10),
+               random_initial_state=dict(init_limits=dict(angle=[0.0, 10.0], angleD=20.0, position=0.3, positionD=0.1)))
+
+    def without_wall_clock(path):
+        lines = open(path, "rb").read().splitlines()
+        assert len(lines) > 40
+        return [ln if ln.startswith(b"#") else ln.rsplit(b",", 1)[0] for ln in lines]
+
+    files = {}
+    for graph in (False, True):
+        paths = R.generate_dataset(eng, 2, str(tmp_path / ("graph" if graph else "launched")), config=cfg, seed=3,
+                                   gru_model=golden_model(), graph=graph, title="network in the device loop")
+        assert len(paths) == 2
+        files[graph] = [without_wall_clock(p) for p in paths]
+    assert files[False] == files[True]
+    head = b"\n".join(files[False][0][:40])
+    assert b"MPC Optimizer: mppi (predictor: GRU)" in head
+    assert files[False][0] != files[False][1]
+    eng.close()
