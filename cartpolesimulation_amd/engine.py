@@ -4,6 +4,7 @@ All array arguments are float32 ROCm tensors (numpy arrays are uploaded); every 
 stream of the engine's device, so ``torch.cuda.Event`` brackets the kernels correctly.
 """
 import ctypes as C
+import functools
 
 import numpy as np
 import torch
@@ -39,6 +40,72 @@ def _same_shape(**tensors):
 
 
 _IN_PLACE = " (it is updated in place)"
+# the caller's current stream as a raw handle (torch.cuda.current_stream() builds a Stream object: ~5 us per call, three calls per
+# control step at the host seam)
+_RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None)
+
+
+def _run_once(build):
+    """An entry point of MPPIEngine from its builder ``_build_<name>``, whose signature and description are the entry point's:
+    build the call, run it once, -> its result.  (``prepare_<name>`` is the other half: build, return the call.)"""
+    @functools.wraps(build)
+    def entry(self, *args, **kwargs):
+        return build(self, *args, **kwargs).run()
+    entry.__name__ = build.__name__[len("_build_"):]
+    entry.__qualname__ = build.__qualname__.replace(build.__name__, entry.__name__)
+    return entry
+
+
+def _addr(t):
+    """What a pointer field of an argument block is set to: the tensor's address, None (a null pointer) for None."""
+    return None if t is None else t.data_ptr()
+
+
+def _counter(name, t):
+    """-> the address of `t`, a step counter kept on the device (int64, one element; graph replay); None for None."""
+    if t is not None and device_tensor(name, t, torch.int64).numel() != 1:
+        raise ValueError(f"{name} must have one element")
+    return _addr(t)
+
+
+def _is_gru(predictor):
+    if predictor not in ("ODE_v0", "GRU"):
+        raise ValueError("predictor must be 'ODE_v0' or 'GRU'")
+    return predictor == "GRU"
+
+
+def _rollout_is_gru(predictor, h0, L, previous_input=None):
+    """rollout_cost / rollout_cost_grad: -> whether the network of set_gru rolls out; it alone has a memory, and it knows no pole
+    length and (its two costs) no previous input."""
+    gru = _is_gru(predictor)
+    if not gru and h0 is not None:
+        raise ValueError("h0 is the memory of the GRU predictor: pass predictor='GRU'")
+    if gru and L is not None:
+        raise ValueError("predictor='GRU' takes no L: the network is the plant model")
+    if gru and previous_input is not None:
+        raise ValueError("predictor='GRU' takes no previous_input: neither of its costs (quadratic_boundary_grad_minimal, "
+                         "default) reads the control applied before")
+    return gru
+
+
+def _set_adam(a, learning_rate, beta1, beta2, epsilon, gradmax_clip):
+    """The Adam / SGD hyper-parameters of a cpmppi_rpgd_args or cpmppi_cem_args block."""
+    a.learning_rate, a.beta1, a.beta2 = float(learning_rate), float(beta1), float(beta2)
+    a.epsilon, a.gradmax_clip = float(epsilon), float(gradmax_clip)
+
+
+# plant_step's optional device tensors: field -> (shape after the leading axis, "E" standing for the env count; None: a vector
+# [E]; dtype)
+_PLANT_TENSORS = {
+    "states_log": (("E", 6), torch.float32), "dd_log": (("E", 2), torch.float32), "Q_log": (("E",), torch.float32),
+    "target_position_table": (("E",), torch.float32), "target_equilibrium_table": (("E",), torch.float32),
+    "L_table": (("E",), torch.float32), "m_pole_table": (("E",), torch.float32), "L_controller_table": (("E",), torch.float32),
+    "Q_disturbance_table": (("E",), torch.float32), "s_measured": ((6,), torch.float32),
+    "state_history": (("E", 6), torch.float32), "measurement_noise_table": (("E", 4), torch.float32),
+    "angle_offset_table": (("E",), torch.float64), "informed_table": (("E",), torch.uint8),
+    "Q_applied_out": (None, torch.float32), "target_position_out": (None, torch.float32),
+    "target_equilibrium_out": (None, torch.float32), "L_out": (None, torch.float32),
+}
 
 
 def gpu_device(device):
@@ -116,11 +183,8 @@ class MPPIEngine:
     def _stream(self):
         if self._fixed_stream is not None:
             return self._fixed_stream
-        # the caller's current stream as a raw handle (torch.cuda.current_stream() builds a Stream object: ~5 us per call,
-        # three calls per control step at the host seam)
-        raw = getattr(torch._C, "_cuda_getCurrentRawStream", None)
-        if raw is not None:
-            return C.c_void_p(raw(self.device.index))
+        if _RAW_STREAM is not None:
+            return C.c_void_p(_RAW_STREAM(self.device.index))
         return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
 
     def tensor(self, x, shape=None):
@@ -130,7 +194,8 @@ class MPPIEngine:
         if not torch.is_tensor(x):
             x = torch.as_tensor(np.ascontiguousarray(np.asarray(x, dtype=np.float32)))
         elif x.dtype == torch.float32 and x.device == self.device and x.is_contiguous():
-            return x if shape is None else x.reshape(shape)      # (the common case inside optimizer loops: nothing to convert)
+            # (the common case inside optimizer loops: nothing to convert, and no view to make of a tensor of that shape)
+            return x if shape is None or x.shape == shape else x.reshape(shape)
         x = x.to(device=self.device, dtype=torch.float32).contiguous()
         if shape is not None:
             x = x.reshape(shape)
@@ -359,12 +424,12 @@ class MPPIEngine:
                                                          _ptr(row_dev), self._stream()))
         return s
 
-    def plant_step(self, s, Q, n_substeps, dt_sim=0.002, period=0, period_dev=None, period_steps=None, L=None, states_log=None,
-                   dd_log=None, save_every=None, Q_log=None, target_position_table=None, target_equilibrium_table=None,
-                   L_table=None, sched_stride=1, target_position_out=None, target_equilibrium_out=None, L_out=None, m_pole=None,
-                   m_pole_table=None, L_controller_table=None, Q_disturbance_table=None, Q_bias=0.0, Q_applied_out=None,
-                   s_measured=None, state_history=None, latency=0.0, measurement_noise_table=None, angle_offset_table=None,
-                   informed_table=None, _prepare=False):
+    def _build_plant_step(self, s, Q, n_substeps, dt_sim=0.002, period=0, period_dev=None, period_steps=None, L=None,
+                          states_log=None, dd_log=None, save_every=None, Q_log=None, target_position_table=None,
+                          target_equilibrium_table=None, L_table=None, sched_stride=1, target_position_out=None,
+                          target_equilibrium_out=None, L_out=None, m_pole=None, m_pole_table=None, L_controller_table=None,
+                          Q_disturbance_table=None, Q_bias=0.0, Q_applied_out=None, s_measured=None, state_history=None, latency=0.0,
+                          measurement_noise_table=None, angle_offset_table=None, informed_table=None):
         """cpmppi_plant_step: one control period of the simulated cartpoles with the experiment schedule and the recording in the
         same launch (include/cpmppi.h).  ``s`` [E,6] in place under held ``Q`` [E]; logs ``states_log`` [rows,E,6], ``dd_log``
         [rows,E,2], ``Q_log`` [periods,E]; schedule tables [sched_rows,E] sampled every ``sched_stride`` simulation steps; ``*_out``
@@ -376,87 +441,87 @@ class MPPIEngine:
         The measurement chain (CartPole.add_noise_and_latency): ``s_measured`` [E,6] receives what the next controller call sees -
         the state ``latency`` seconds back (``state_history`` [>= latency / dt_sim + 2, E, 6], zeros with cos = 1 before the run),
         plus ``measurement_noise_table`` [calls,E,4], plus ``angle_offset_table`` [sched_rows,E] float64 on the angle (taken out again
-        where ``informed_table`` [sched_rows,E] uint8 says so; None = everywhere)."""
+        where ``informed_table`` [sched_rows,E] uint8 says so; None = everywhere).  -> ``s``."""
         E = device_tensor("s", s, note=_IN_PLACE).shape[0]
-
-        def dev(name, t, tail, dtype=torch.float32):
-            return None if t is None else device_tensor(name, t, dtype, tail)
-
         a = _L.cpmppi_plant_args()
         Q = self.tensor(Q).reshape(E)
         Lt = self.tensor(L).reshape(E) if L is not None else None
-        a.E, a.s, a.Q, a.L = E, s.data_ptr(), Q.data_ptr(), (Lt.data_ptr() if Lt is not None else None)
+        keep = [s, Q, Lt, period_dev]
+
+        def dev(point=True, **tensors):
+            """Check the optional tensors given by field name against _PLANT_TENSORS, keep them and (`point`) put their addresses
+            into the block.  -> them (a vector [E] as [E,1]), in the order given."""
+            got = []
+            for name, t in tensors.items():
+                if t is not None:
+                    tail, dtype = _PLANT_TENSORS[name]
+                    if tail is None:
+                        t, tail = t.reshape(E, 1), (1,)
+                    device_tensor(name, t, dtype, tuple(E if x == "E" else x for x in tail))
+                    keep.append(t)
+                    if point:
+                        setattr(a, name, t.data_ptr())
+                got.append(t)
+            return got
+
+        a.E, a.s, a.Q, a.L = E, s.data_ptr(), Q.data_ptr(), _addr(Lt)
         a.n_substeps, a.period_steps, a.dt_sim = int(n_substeps), int(period_steps if period_steps is not None else n_substeps), float(dt_sim)
         a.period = int(period)
         if period_dev is not None:
             a.period_dev = device_tensor("period_dev", period_dev, torch.int64).data_ptr()
-        states_log, dd_log, Q_log = dev("states_log", states_log, (E, 6)), dev("dd_log", dd_log, (E, 2)), dev("Q_log", Q_log, (E,))
+        states_log, dd_log, Q_log = dev(states_log=states_log, dd_log=dd_log, Q_log=Q_log)
         rows = [t.shape[0] for t in (states_log, dd_log) if t is not None]
-        a.states_log = states_log.data_ptr() if states_log is not None else None
-        a.dd_log = dd_log.data_ptr() if dd_log is not None else None
         a.save_rows = min(rows) if rows else 0
         a.save_every = int(save_every) if save_every else 0
         if Q_log is not None:
-            a.Q_log, a.ctrl_rows = Q_log.data_ptr(), Q_log.shape[0]
+            a.ctrl_rows = Q_log.shape[0]
             if period_dev is None and not 0 <= int(period) < Q_log.shape[0]:
                 raise IndexError(f"period {period} outside Q_log")
-        tabs = [dev(n, t, (E,)) for n, t in (("target_position_table", target_position_table),
-                                             ("target_equilibrium_table", target_equilibrium_table), ("L_table", L_table),
-                                             ("m_pole_table", m_pole_table), ("L_controller_table", L_controller_table))]
+        tabs = dev(target_position_table=target_position_table, target_equilibrium_table=target_equilibrium_table, L_table=L_table,
+                   m_pole_table=m_pole_table, L_controller_table=L_controller_table)
         sched = [t.shape[0] for t in tabs if t is not None]
         if sched and min(sched) != max(sched):
             raise ValueError("the schedule tables must have the same number of rows")
-        (a.target_position_table, a.target_equilibrium_table, a.L_table, a.m_pole_table,
-         a.L_controller_table) = [t.data_ptr() if t is not None else None for t in tabs]
-        qd = dev("Q_disturbance_table", Q_disturbance_table, (E,))
+        qd, = dev(Q_disturbance_table=Q_disturbance_table)
         if qd is not None:
             if Q_log is not None and qd.shape[0] != Q_log.shape[0]:
                 raise ValueError("Q_disturbance_table and Q_log must have the same number of rows (one per controller call)")
-            a.Q_disturbance_table, a.ctrl_rows, a.Q_bias = qd.data_ptr(), qd.shape[0], float(Q_bias)
-        sm = dev("s_measured", s_measured, (6,))
+            a.ctrl_rows, a.Q_bias = qd.shape[0], float(Q_bias)
+        sm, = dev(s_measured=s_measured)
         if sm is not None and sm.shape[0] != E:
             raise ValueError("s_measured must be [E,6]")
-        hist = dev("state_history", state_history, (E, 6))
-        nz = dev("measurement_noise_table", measurement_noise_table, (E, 4))
-        off = dev("angle_offset_table", angle_offset_table, (E,), torch.float64)
-        inf = dev("informed_table", informed_table, (E,), torch.uint8)
+        # the rest of the measurement chain is checked always and read only with s_measured
+        hist, nz, off, inf = dev(point=sm is not None, state_history=state_history, measurement_noise_table=measurement_noise_table,
+                                 angle_offset_table=angle_offset_table, informed_table=informed_table)
         if sm is not None:
             steps = float(latency) / float(dt_sim)
             a.latency_steps = int(steps)
             a.latency_frac = steps - int(steps)
-            a.s_measured = sm.data_ptr()
             if hist is not None:
-                a.state_history, a.history_len = hist.data_ptr(), hist.shape[0]
+                a.history_len = hist.shape[0]
             if nz is not None:
                 if Q_log is not None and nz.shape[0] != Q_log.shape[0]:
                     raise ValueError("measurement_noise_table and Q_log must have the same number of rows (one per controller call)")
-                a.measurement_noise_table, a.ctrl_rows = nz.data_ptr(), nz.shape[0]
+                a.ctrl_rows = nz.shape[0]
             for t in (off, inf):
                 if t is not None:
                     if sched and t.shape[0] != sched[0]:
                         raise ValueError("the schedule tables must have the same number of rows")
                     sched.append(t.shape[0])
-            a.angle_offset_table = off.data_ptr() if off is not None else None
-            a.informed_table = inf.data_ptr() if inf is not None else None
-        qa = dev("Q_applied_out", Q_applied_out.reshape(E, 1) if Q_applied_out is not None else None, (1,))
-        a.Q_applied_out = qa.data_ptr() if qa is not None else None
+        dev(Q_applied_out=Q_applied_out)
         mt = self.tensor(m_pole).reshape(E) if m_pole is not None else None
-        a.m_pole = mt.data_ptr() if mt is not None else None
+        keep.append(mt)
+        a.m_pole = _addr(mt)
         a.sched_rows, a.sched_stride = (sched[0] if sched else 0), int(sched_stride)
-        outs = [dev(n, t.reshape(E, 1) if t is not None else None, (1,)) for n, t in (
-            ("target_position_out", target_position_out), ("target_equilibrium_out", target_equilibrium_out), ("L_out", L_out))]
-        a.target_position_out, a.target_equilibrium_out, a.L_out = [t.data_ptr() if t is not None else None for t in outs]
-        keep = (s, Q, Lt, mt, qd, qa, sm, hist, nz, off, inf, period_dev, states_log, dd_log, Q_log, tabs, outs)
-        if _prepare:
-            return PreparedPlantStep(self, a, keep)
-        self._check(self.lib.cpmppi_plant_step(self._h, C.byref(a), self._stream()))
-        del keep
-        return s
+        dev(target_position_out=target_position_out, target_equilibrium_out=target_equilibrium_out, L_out=L_out)
+        return PreparedCall(self, self.lib.cpmppi_plant_step, a, keep, s, ("period", "n_substeps"))
+
+    plant_step = _run_once(_build_plant_step)
 
     def prepare_plant_step(self, *args, **kwargs):
         """The argument block of ``plant_step(...)`` built and validated ONCE (a closed loop calls it every control period with the
         same buffers): ``.run(period=..., n_substeps=...)`` only updates those two fields and enqueues the launch."""
-        return self.plant_step(*args, _prepare=True, **kwargs)
+        return self._build_plant_step(*args, **kwargs)
 
     # ------------------------------------------------------------------ GRU predictor (BASELINE configs[4])
     GRU_KEYS = ("w_ih0", "w_hh0", "b_ih0", "b_hh0", "w_ih1", "w_hh1", "b_ih1", "b_hh1", "w_out", "b_out")
@@ -513,35 +578,52 @@ class MPPIEngine:
 
     # ------------------------------------------------------------------ cost-only launch and CEM
     def _per_env(self, x, E):
-        x = self.tensor(x).reshape(-1)
+        x = self.tensor(x)
+        if x.dim() != 1:
+            x = x.reshape(-1)
         return x.expand(E).contiguous() if x.numel() == 1 else x
 
-    def _rollout_inputs(self, s0, inputs, target_position, target_equilibrium, L):
-        """rollout_cost / rollout_cost_grad: -> (E, s0 [E,6], inputs [E,N,H], target position, target equilibrium, L or None [E])."""
+    def _control_inputs(self, E, s0, target_position, target_equilibrium, L, previous_input, block=None):
+        """The per-env inputs of a control step, from whatever the caller gave: -> (s0 [E,6], target position [E], target
+        equilibrium [E], L [E] or None, previous input [E] or None); their addresses and E go into the fields of those names of
+        ``block``, the argument block of a fused step."""
+        s0, tp, te = self.tensor(s0, (E, 6)), self._per_env(target_position, E), self._per_env(target_equilibrium, E)
+        Lt = None if L is None else self._per_env(L, E)
+        prev = None if previous_input is None else self._per_env(previous_input, E)
+        if block is not None:
+            block.E, block.s0, block.target_position, block.target_equilibrium = E, s0.data_ptr(), tp.data_ptr(), te.data_ptr()
+            block.L, block.previous_input = _addr(Lt), _addr(prev)
+        return s0, tp, te, Lt, prev
+
+    def _outputs(self, block, E, Q_out, **optional):
+        """The per-env outputs of a fused rpgd / cem step: ``Q_out`` [E] (None: allocated here) and the optional ones by field
+        name, each one given [E, *tail] of its dtype; their addresses go into ``block``.  -> them all, in the order given."""
+        table = {"Q_out": (torch.float32, ()), "S_out": (torch.float32, (self.N,)), "plan_out": (torch.float32, (self.H,)),
+                 "samples_out": (torch.float32, (self.N, self.H)), "order_out": (torch.int32, (self.N,))}
+        out = dict(Q_out=self.empty(E) if Q_out is None else Q_out, **optional)
+        for name, t in out.items():
+            if t is not None and device_tensor(name, t, *table[name]).shape[0] != E:
+                raise ValueError(f"{name} must have {E} rows")
+            setattr(block, name, _addr(t))
+        return tuple(out.values())
+
+    def _rollout_inputs(self, s0, inputs, target_position, target_equilibrium, L, previous_input=None):
+        """rollout_cost / rollout_cost_grad: -> (E, inputs [E,N,H], then what _control_inputs gives)."""
         inputs = self.tensor(inputs)
         E = inputs.shape[0]
         if inputs.shape != (E, self.N, self.H):
             raise ValueError(f"inputs must be [E,{self.N},{self.H}]")
-        s0 = self.tensor(s0, (E, 6))
-        tp, te = self._per_env(target_position, E), self._per_env(target_equilibrium, E)
-        Lt = self._per_env(L, E) if L is not None else None
-        return E, s0, inputs, tp, te, Lt
+        return (E, inputs) + self._control_inputs(E, s0, target_position, target_equilibrium, L, previous_input)
 
     def rollout_cost(self, s0, inputs, target_position, target_equilibrium, L=None, predictor="ODE_v0", h0=None):
         """inputs[E,N,H] -> S[E,N]: trajectory cost of given control sequences (no update).  ``predictor="GRU"`` rolls them out
         with the network of ``set_gru`` (cpmppi_rollout_cost_gru): ``h0`` [E,2,32] is each env's memory, shared by its rollouts
         (None: zeros); the network knows no pole length, so ``L`` is refused."""
-        if predictor not in ("ODE_v0", "GRU"):
-            raise ValueError("predictor must be 'ODE_v0' or 'GRU'")
-        if predictor != "GRU" and h0 is not None:
-            raise ValueError("h0 is the memory of the GRU predictor: pass predictor='GRU'")
-        if predictor == "GRU":
-            if L is not None:
-                raise ValueError("predictor='GRU' takes no L: the network is the plant model")
-        E, s0, inputs, tp, te, Lt = self._rollout_inputs(s0, inputs, target_position, target_equilibrium, L)
+        gru = _rollout_is_gru(predictor, h0, L)
+        E, inputs, s0, tp, te, Lt, _ = self._rollout_inputs(s0, inputs, target_position, target_equilibrium, L)
         S = self.empty(E, self.N)
-        if predictor == "GRU":
-            h0 = self.tensor(h0, (E, 2, 32)) if h0 is not None else None
+        if gru:
+            h0 = self.tensor(h0, (E, 2, 32))
             self._check(self.lib.cpmppi_rollout_cost_gru(self._h, E, _ptr(s0), _ptr(inputs), _ptr(tp), _ptr(te), _ptr(h0),
                                                          _ptr(S), self._stream()))
             return S
@@ -555,24 +637,14 @@ class MPPIEngine:
         differentiates the rollout through the network of ``set_gru`` (cpmppi_rollout_cost_grad_gru): ``h0`` [E,2,32] is each
         env's memory (None: zeros); the network knows no pole length and its two costs read no previous input, so ``L`` and
         ``previous_input`` are refused."""
-        if predictor not in ("ODE_v0", "GRU"):
-            raise ValueError("predictor must be 'ODE_v0' or 'GRU'")
-        if predictor != "GRU" and h0 is not None:
-            raise ValueError("h0 is the memory of the GRU predictor: pass predictor='GRU'")
-        if predictor == "GRU":
-            if L is not None:
-                raise ValueError("predictor='GRU' takes no L: the network is the plant model")
-            if previous_input is not None:
-                raise ValueError("predictor='GRU' takes no previous_input: neither of its costs (quadratic_boundary_grad_minimal, "
-                                 "default) reads the control applied before")
-        E, s0, inputs, tp, te, Lt = self._rollout_inputs(s0, inputs, target_position, target_equilibrium, L)
+        gru = _rollout_is_gru(predictor, h0, L, previous_input)
+        E, inputs, s0, tp, te, Lt, pi = self._rollout_inputs(s0, inputs, target_position, target_equilibrium, L, previous_input)
         S, grad = self.empty(E, self.N), self.empty(E, self.N, self.H)
-        if predictor == "GRU":
-            h0 = self.tensor(h0, (E, 2, 32)) if h0 is not None else None
+        if gru:
+            h0 = self.tensor(h0, (E, 2, 32))
             self._check(self.lib.cpmppi_rollout_cost_grad_gru(self._h, E, _ptr(s0), _ptr(inputs), _ptr(tp), _ptr(te), _ptr(h0),
                                                               _ptr(S), _ptr(grad), self._stream()))
             return S, grad
-        pi = self._per_env(previous_input, E) if previous_input is not None else None
         self._check(self.lib.cpmppi_rollout_cost_grad(self._h, E, _ptr(s0), _ptr(inputs), _ptr(tp), _ptr(te), _ptr(Lt),
                                                       _ptr(pi), _ptr(S), _ptr(grad), self._stream()))
         return S, grad
@@ -655,11 +727,11 @@ class MPPIEngine:
         allocates - required before a step is captured into a graph."""
         self._check(self.lib.cpmppi_rpgd_reserve(self._h, self.E if E is None else int(E)))
 
-    def rpgd_step(self, s0, Q, m, v, target_position, target_equilibrium, L=None, previous_input=None, *, iterations,
-                  learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, gradmax_clip=0.0, keep_k=None, resamp_per=0, shift=1,
-                  distribution="normal", sample_mean=0.0, uniform_lo=0.0, uniform_hi=0.0, seed=0, draw_offset=0, env_offset=0,
-                  count=0, adam_iteration=0, count_dev=None, Q_out=None, S_out=None, plan_out=None, order_out=None,
-                  _prepare=False):
+    def _build_rpgd_step(self, s0, Q, m, v, target_position, target_equilibrium, L=None, previous_input=None, *, iterations,
+                         learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, gradmax_clip=0.0, keep_k=None, resamp_per=0, shift=1,
+                         distribution="normal", sample_mean=0.0, uniform_lo=0.0, uniform_hi=0.0, seed=0, draw_offset=0,
+                         env_offset=0, count=0, adam_iteration=0, count_dev=None, Q_out=None, S_out=None, plan_out=None,
+                         order_out=None):
         """cpmppi_rpgd_step: one whole rpgd / gradient-tf control step on the plans ``Q`` and the Adam moments ``m``, ``v``
         [E,N,H], all three updated IN PLACE (include/cpmppi.h states the step).  ``count_dev``: int64 device scalar, the control
         steps taken so far - read by the kernel in place of ``count`` / ``adam_iteration`` / ``draw_offset`` and incremented
@@ -672,47 +744,26 @@ class MPPIEngine:
                 raise ValueError(f"{name} must have Q's shape")
         if distribution not in ("normal", "uniform"):
             raise ValueError(f"distribution={distribution!r}; expected 'normal' or 'uniform'")
-        s0 = self.tensor(s0, (E, 6))
-        tp, te = self._per_env(target_position, E), self._per_env(target_equilibrium, E)
-        Lt = self._per_env(L, E) if L is not None else None
-        prev = self._per_env(previous_input, E) if previous_input is not None else None
-        if Q_out is None:
-            Q_out = self.empty(E)
-        for name, t, dtype, tail in (("Q_out", Q_out, torch.float32, ()), ("S_out", S_out, torch.float32, (self.N,)),
-                                     ("plan_out", plan_out, torch.float32, (self.H,)), ("order_out", order_out, torch.int32, (self.N,))):
-            if t is not None and device_tensor(name, t, dtype, tail).shape[0] != E:
-                raise ValueError(f"{name} must have {E} rows")
         a = _L.cpmppi_rpgd_args()
-        a.E = E
-        a.s0, a.target_position, a.target_equilibrium = s0.data_ptr(), tp.data_ptr(), te.data_ptr()
-        a.L = Lt.data_ptr() if Lt is not None else None
-        a.previous_input = prev.data_ptr() if prev is not None else None
+        inputs = self._control_inputs(E, s0, target_position, target_equilibrium, L, previous_input, a)
+        out = self._outputs(a, E, Q_out, S_out=S_out, plan_out=plan_out, order_out=order_out)
         a.Q, a.m, a.v = Q.data_ptr(), m.data_ptr(), v.data_ptr()
         a.iterations, a.adam_iteration = int(iterations), int(adam_iteration)
-        a.learning_rate, a.beta1, a.beta2 = float(learning_rate), float(beta1), float(beta2)
-        a.epsilon, a.gradmax_clip = float(epsilon), float(gradmax_clip)
+        _set_adam(a, learning_rate, beta1, beta2, epsilon, gradmax_clip)
         a.keep_k, a.resamp_per, a.shift = int(self.N if keep_k is None else keep_k), int(resamp_per), int(shift)
         a.distribution = _L.RPGD_UNIFORM if distribution == "uniform" else _L.RPGD_NORMAL
         a.sample_mean, a.uniform_lo, a.uniform_hi = float(sample_mean), float(uniform_lo), float(uniform_hi)
         a.seed, a.draw_offset, a.env_offset, a.count = int(seed), int(draw_offset), int(env_offset), int(count)
-        if count_dev is not None:
-            if device_tensor("count_dev", count_dev, torch.int64).numel() != 1:
-                raise ValueError("count_dev must have one element")
-            a.count_dev = count_dev.data_ptr()
-        a.Q_out = Q_out.data_ptr()
-        a.S_out = S_out.data_ptr() if S_out is not None else None
-        a.plan_out = plan_out.data_ptr() if plan_out is not None else None
-        a.order_out = order_out.data_ptr() if order_out is not None else None
-        out = (Q_out, S_out, plan_out, order_out)
-        if _prepare:
-            return PreparedRpgdStep(self, a, (s0, tp, te, Lt, prev, Q, m, v, count_dev) + out, out)
-        self._check(self.lib.cpmppi_rpgd_step(self._h, C.byref(a), self._stream()))
-        return out
+        a.count_dev = _counter("count_dev", count_dev)
+        return PreparedCall(self, self.lib.cpmppi_rpgd_step, a, inputs + (Q, m, v, count_dev) + out, out,
+                            ("count", "adam_iteration", "draw_offset", "iterations"))
+
+    rpgd_step = _run_once(_build_rpgd_step)
 
     def prepare_rpgd_step(self, *args, **kwargs):
         """The argument block of ``rpgd_step(...)`` built and validated ONCE: ``.run(count=, adam_iteration=, draw_offset=,
         iterations=)`` updates the host counters and enqueues the launch; with ``count_dev`` nothing changes between steps."""
-        return self.rpgd_step(*args, _prepare=True, **kwargs)
+        return self._build_rpgd_step(*args, **kwargs)
 
     # ------------------------------------------------------------------ the fused CEM control step
     _CEM_REFINE = {None: _L.CEM_REFINE_NONE, "none": _L.CEM_REFINE_NONE, "sgd": _L.CEM_REFINE_SGD, "adam": _L.CEM_REFINE_ADAM}
@@ -728,10 +779,10 @@ class MPPIEngine:
         captured into a graph."""
         self._check(self.lib.cpmppi_cem_reserve(self._h, self.E if E is None else int(E), self._cem_refine(refine)))
 
-    def cem_step(self, s0, mean, stdev, target_position, target_equilibrium, L=None, previous_input=None, *, iterations, best_k,
-                 stdev_min, refine=None, learning_rate=0.0, beta1=0.9, beta2=0.999, epsilon=1e-8, gradmax_clip=0.0, shift=1,
-                 mean_fill=0.0, stdev_fill=0.0, seed=0, offset=0, env_offset=0, count_dev=None, Q_out=None, S_out=None,
-                 plan_out=None, samples_out=None, order_out=None, _prepare=False):
+    def _build_cem_step(self, s0, mean, stdev, target_position, target_equilibrium, L=None, previous_input=None, *, iterations,
+                        best_k, stdev_min, refine=None, learning_rate=0.0, beta1=0.9, beta2=0.999, epsilon=1e-8, gradmax_clip=0.0,
+                        shift=1, mean_fill=0.0, stdev_fill=0.0, seed=0, offset=0, env_offset=0, count_dev=None, Q_out=None,
+                        S_out=None, plan_out=None, samples_out=None, order_out=None):
         """cpmppi_cem_step: one whole control step of cem / cem-naive-grad (``refine='sgd'``) / cem-grad-bharadhwaj (``'adam'``) on
         the sampling distribution ``mean``, ``stdev`` [E,H], both updated IN PLACE (include/cpmppi.h states the step).
         ``count_dev``: int64 device scalar, the control steps taken so far - iteration i then draws at Philox offset
@@ -742,51 +793,28 @@ class MPPIEngine:
             raise ValueError(f"mean must be [E<={self.E},{self.H}], got {tuple(mean.shape)}")
         if device_tensor("stdev", stdev, tail=(self.H,), note=_IN_PLACE).shape[0] != E:
             raise ValueError("stdev must have mean's shape")
-        s0 = self.tensor(s0, (E, 6))
-        tp, te = self._per_env(target_position, E), self._per_env(target_equilibrium, E)
-        Lt = self._per_env(L, E) if L is not None else None
-        prev = self._per_env(previous_input, E) if previous_input is not None else None
-        if Q_out is None:
-            Q_out = self.empty(E)
-        for name, t, dtype, tail in (("Q_out", Q_out, torch.float32, ()), ("S_out", S_out, torch.float32, (self.N,)),
-                                     ("plan_out", plan_out, torch.float32, (self.H,)),
-                                     ("samples_out", samples_out, torch.float32, (self.N, self.H)),
-                                     ("order_out", order_out, torch.int32, (self.N,))):
-            if t is not None and device_tensor(name, t, dtype, tail).shape[0] != E:
-                raise ValueError(f"{name} must have {E} rows")
         a = _L.cpmppi_cem_args()
-        a.E = E
-        a.s0, a.target_position, a.target_equilibrium = s0.data_ptr(), tp.data_ptr(), te.data_ptr()
-        a.L = Lt.data_ptr() if Lt is not None else None
-        a.previous_input = prev.data_ptr() if prev is not None else None
+        inputs = self._control_inputs(E, s0, target_position, target_equilibrium, L, previous_input, a)
+        out = self._outputs(a, E, Q_out, S_out=S_out, plan_out=plan_out, samples_out=samples_out, order_out=order_out)
         a.mean, a.stdev = mean.data_ptr(), stdev.data_ptr()
         a.iterations, a.best_k, a.stdev_min, a.refine = int(iterations), int(best_k), float(stdev_min), self._cem_refine(refine)
-        a.learning_rate, a.beta1, a.beta2 = float(learning_rate), float(beta1), float(beta2)
-        a.epsilon, a.gradmax_clip = float(epsilon), float(gradmax_clip)
+        _set_adam(a, learning_rate, beta1, beta2, epsilon, gradmax_clip)
         a.shift, a.mean_fill, a.stdev_fill = int(shift), float(mean_fill), float(stdev_fill)
         a.seed, a.offset, a.env_offset = int(seed), int(offset), int(env_offset)
-        if count_dev is not None:
-            if device_tensor("count_dev", count_dev, torch.int64).numel() != 1:
-                raise ValueError("count_dev must have one element")
-            a.count_dev = count_dev.data_ptr()
-        a.Q_out = Q_out.data_ptr()
-        for name, t in (("S_out", S_out), ("plan_out", plan_out), ("samples_out", samples_out), ("order_out", order_out)):
-            setattr(a, name, t.data_ptr() if t is not None else None)
-        out = (Q_out, S_out, plan_out, samples_out, order_out)
-        if _prepare:
-            return PreparedCemStep(self, a, (s0, tp, te, Lt, prev, mean, stdev, count_dev) + out, out)
-        self._check(self.lib.cpmppi_cem_step(self._h, C.byref(a), self._stream()))
-        return out
+        a.count_dev = _counter("count_dev", count_dev)
+        return PreparedCall(self, self.lib.cpmppi_cem_step, a, inputs + (mean, stdev, count_dev) + out, out, ("offset", "iterations"))
+
+    cem_step = _run_once(_build_cem_step)
 
     def prepare_cem_step(self, *args, **kwargs):
         """The argument block of ``cem_step(...)`` built and validated ONCE: ``.run(offset=, iterations=)`` updates the host's
         Philox offset and iteration count and enqueues the launch; with ``count_dev`` nothing changes between steps."""
-        return self.cem_step(*args, _prepare=True, **kwargs)
+        return self._build_cem_step(*args, **kwargs)
 
     # ------------------------------------------------------------------ the fused hot path
     def step(self, s0, u_nom, target_position, target_equilibrium, L=None, delta_u=None, knots=None, seed=None,
              offset=0, env_offset=0, u_prev=None, Q_out=None, S_out=None, predictor="ODE_v0", h0=None,
-             previous_input=None, offset_dev=None, delta_u_tiled=None, u_nom_out=None, gather_into=None, _prepare=False):
+             previous_input=None, offset_dev=None, delta_u_tiled=None, u_nom_out=None, gather_into=None):
         """One MPPI optimizer step for E envs.  ``u_nom`` [E,H] is updated IN PLACE, or — with ``u_nom_out`` [E,H] — only
         read, the updated sequence going to ``u_nom_out`` (two buffers used alternately: shard.NativeGather).
 
@@ -796,6 +824,14 @@ class MPPIEngine:
         all-gather of the sequences it writes, ordered on the device, nothing but the kernel on the launch stream.
         Returns (Q_out[E], S_out or None).
         """
+        return self._build_step(s0, u_nom, target_position, target_equilibrium, L, delta_u, knots, seed, offset, env_offset, u_prev,
+                                Q_out, S_out, predictor, h0, previous_input, offset_dev, delta_u_tiled,
+                                u_nom_out).run(gather_into=gather_into)
+
+    def _build_step(self, s0, u_nom, target_position, target_equilibrium, L=None, delta_u=None, knots=None, seed=None, offset=0,
+                    env_offset=0, u_prev=None, Q_out=None, S_out=None, predictor="ODE_v0", h0=None, previous_input=None,
+                    offset_dev=None, delta_u_tiled=None, u_nom_out=None):
+        """step's arguments (all but ``gather_into``, which is ``run``'s), validated, as the prepared call that runs them."""
         E = device_tensor("u_nom", u_nom, note=_IN_PLACE).shape[0]
         if u_nom.shape != (E, self.H) or E > self.E:
             raise ValueError(f"u_nom must be [E<={self.E},{self.H}], got {tuple(u_nom.shape)}")
@@ -803,9 +839,7 @@ class MPPIEngine:
         if sum(given) != 1:
             raise ValueError("give exactly one of delta_u, knots, seed, delta_u_tiled")
         a = _L.cpmppi_step_args()
-        s0 = self.tensor(s0, (E, 6))
-        tp, te = self._per_env(target_position, E), self._per_env(target_equilibrium, E)
-        Lt = self._per_env(L, E) if L is not None else None
+        inputs = self._control_inputs(E, s0, target_position, target_equilibrium, L, previous_input, a)
         noise = None
         if delta_u_tiled is not None:
             noise = device_tensor("delta_u_tiled", delta_u_tiled)
@@ -821,41 +855,21 @@ class MPPIEngine:
         else:
             a.noise_kind = _L.NOISE_PHILOX
             a.seed, a.offset, a.env_offset = int(seed), int(offset), int(env_offset)
-        u_prev = self.tensor(u_prev, (E, self.H)) if u_prev is not None else None
+        u_prev = self.tensor(u_prev, (E, self.H))
         if Q_out is None:
             Q_out = self.empty(E)
-        a.E = E
-        a.s0, a.u_nom, a.u_prev = s0.data_ptr(), u_nom.data_ptr(), (u_prev.data_ptr() if u_prev is not None else None)
-        a.target_position, a.target_equilibrium = tp.data_ptr(), te.data_ptr()
-        a.L = Lt.data_ptr() if Lt is not None else None
-        a.noise = noise.data_ptr() if noise is not None else None
-        a.Q_out = Q_out.data_ptr()
-        a.S_out = S_out.data_ptr() if S_out is not None else None
-        if predictor not in ("ODE_v0", "GRU"):
-            raise ValueError("predictor must be 'ODE_v0' or 'GRU'")
-        a.predictor = _L.PREDICTOR_GRU if predictor == "GRU" else _L.PREDICTOR_ODE_V0
-        h0 = self.tensor(h0, (E, 2, 32)) if h0 is not None else None
-        a.h0 = h0.data_ptr() if h0 is not None else None
-        previous_input = self._per_env(previous_input, E) if previous_input is not None else None
-        a.previous_input = previous_input.data_ptr() if previous_input is not None else None
+        a.u_nom, a.u_prev, a.noise = u_nom.data_ptr(), _addr(u_prev), _addr(noise)
+        a.Q_out, a.S_out = Q_out.data_ptr(), _addr(S_out)
+        a.predictor = _L.PREDICTOR_GRU if _is_gru(predictor) else _L.PREDICTOR_ODE_V0
+        h0 = self.tensor(h0, (E, 2, 32))
+        a.h0 = _addr(h0)
         if u_nom_out is not None:
             if device_tensor("u_nom_out", u_nom_out).shape != u_nom.shape:
                 raise ValueError("u_nom_out must have u_nom's shape")
             a.u_nom_out = u_nom_out.data_ptr()
-        if offset_dev is not None:           # int64 device scalar: Philox step counter kept on the device (graph replay)
-            if device_tensor("offset_dev", offset_dev, torch.int64).numel() != 1:
-                raise ValueError("offset_dev must have one element")
-            a.offset_dev = offset_dev.data_ptr()
-        if _prepare:
-            # every tensor the argument block points into is kept alive by the returned object
-            return PreparedStep(self, a, (s0, u_nom, tp, te, Lt, noise, u_prev, Q_out, S_out, h0, previous_input, offset_dev, u_nom_out),
-                                Q_out, S_out)
-        if gather_into is not None:
-            self._check(self.lib.cpmppi_step_gather(self._h, C.byref(a), gather_into.data_ptr(), self._stream()))
-        else:
-            self._check(self.lib.cpmppi_step(self._h, C.byref(a), self._stream()))
-        # keep the temporaries alive until the launch is enqueued (stream-ordered frees are safe in torch's allocator)
-        return Q_out, S_out
+        a.offset_dev = _counter("offset_dev", offset_dev)         # the Philox step counter kept on the device
+        return PreparedCall(self, self.lib.cpmppi_step, a, inputs + (u_nom, noise, u_prev, Q_out, S_out, h0, offset_dev, u_nom_out),
+                            (Q_out, S_out), ("offset",), gather=self.lib.cpmppi_step_gather)
 
     def step_host(self, s0, u_nom, target_position, target_equilibrium, L, seed, offset, Q_host, env_offset=0):
         """cpmppi_step_host: float32 numpy arrays on the HOST for the state [E,6], the per-env vectors [E] and the result
@@ -876,74 +890,49 @@ class MPPIEngine:
         """The argument block of ``step(...)`` built and validated ONCE, for callers whose buffers persist from step to step
         (the host seam's staging block, a closed loop): ``.run(offset=...)`` only updates the Philox step counter and
         enqueues the launch - the per-call argument handling of ``step`` is ~10 us of a 55 us control step."""
-        return self.step(*args, _prepare=True, **kwargs)
+        return self._build_step(*args, **kwargs)
 
 
-class PreparedPlantStep:
-    """A validated cpmppi_plant_step argument block plus the tensors it points into (MPPIEngine.prepare_plant_step)."""
+class PreparedCall:
+    """One entry point of the library that takes an argument block, ready to be enqueued any number of times
+    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_cem_step).  ``args`` is the live ctypes block,
+    validated when it was built, and ``ref`` the reference to it that the library is handed; ``keep`` holds the tensors it
+    points into; ``enqueue`` is the entry point, ``enqueue(handle, ref, stream)``.  ``result`` is what the call returns: the
+    outputs of a control step - ``out``, whose first two are ``Q_out`` and ``S_out`` - or the plant's state."""
 
-    def __init__(self, engine, args, keep):
-        self.engine, self.args, self._keep = engine, args, keep
+    def __init__(self, engine, enqueue, args, keep, result, fields, gather=None):
+        self.engine, self.enqueue, self.args, self.keep, self.result = engine, enqueue, args, keep, result
+        self.fields, self._gather = fields, gather
+        self.ref = C.byref(args)
 
-    def run(self, period=None, n_substeps=None):
-        if period is not None:
-            self.args.period = int(period)
-        if n_substeps is not None:
-            self.args.n_substeps = int(n_substeps)
+    out = property(lambda self: self.result)
+    Q_out = property(lambda self: self.result[0])
+    S_out = property(lambda self: self.result[1])
+
+    def set(self, **fields):
+        """The counters of the block that change from call to call, by field name: each one given (not None) is set, as an int."""
+        for name in fields:
+            if name not in self.fields:
+                raise TypeError(f"{name!r}: only {', '.join(self.fields)} can be set on this call")
+        for name, value in fields.items():
+            if value is not None:
+                setattr(self.args, name, int(value))
+
+    def run(self, gather_into=None, **fields):
+        """`set(**fields)`, enqueue on the engine's stream, -> ``result``.  ``gather_into`` (the MPPI step alone): through
+        cpmppi_step_gather, which takes that tensor's address after the block."""
+        if fields:                                   # (`set` once more, in line: a call less on the path of every control step)
+            for name in fields:
+                if name not in self.fields:
+                    raise TypeError(f"{name!r}: only {', '.join(self.fields)} can be set on this call")
+            for name, value in fields.items():
+                if value is not None:
+                    setattr(self.args, name, int(value))
         e = self.engine
-        e._check(e.lib.cpmppi_plant_step(e._h, C.byref(self.args), e._stream()))
-
-
-class PreparedStep:
-    """A validated cpmppi_step argument block plus the tensors it points into (MPPIEngine.prepare_step)."""
-
-    def __init__(self, engine, args, keep, Q_out, S_out):
-        self.engine, self.args, self._keep, self.Q_out, self.S_out = engine, args, keep, Q_out, S_out
-
-    def run(self, offset=None, gather_into=None):
-        if offset is not None:
-            self.args.offset = int(offset)
-        e = self.engine
-        if gather_into is not None:
-            e._check(e.lib.cpmppi_step_gather(e._h, C.byref(self.args), gather_into.data_ptr(), e._stream()))
+        if gather_into is None:
+            e._check(self.enqueue(e._h, self.ref, e._stream()))
+        elif self._gather is None:
+            raise TypeError("gather_into: only the MPPI step has a gathering entry point")
         else:
-            e._check(e.lib.cpmppi_step(e._h, C.byref(self.args), e._stream()))
-        return self.Q_out, self.S_out
-
-
-class PreparedRpgdStep:
-    """A validated cpmppi_rpgd_step argument block plus the tensors it points into (MPPIEngine.prepare_rpgd_step)."""
-
-    def __init__(self, engine, args, keep, out):
-        self.engine, self.args, self._keep, self.out = engine, args, keep, out
-
-    def run(self, count=None, adam_iteration=None, draw_offset=None, iterations=None):
-        a = self.args
-        if count is not None:
-            a.count = int(count)
-        if adam_iteration is not None:
-            a.adam_iteration = int(adam_iteration)
-        if draw_offset is not None:
-            a.draw_offset = int(draw_offset)
-        if iterations is not None:
-            a.iterations = int(iterations)
-        e = self.engine
-        e._check(e.lib.cpmppi_rpgd_step(e._h, C.byref(a), e._stream()))
-        return self.out
-
-
-class PreparedCemStep:
-    """A validated cpmppi_cem_step argument block plus the tensors it points into (MPPIEngine.prepare_cem_step)."""
-
-    def __init__(self, engine, args, keep, out):
-        self.engine, self.args, self._keep, self.out = engine, args, keep, out
-
-    def run(self, offset=None, iterations=None):
-        a = self.args
-        if offset is not None:
-            a.offset = int(offset)
-        if iterations is not None:
-            a.iterations = int(iterations)
-        e = self.engine
-        e._check(e.lib.cpmppi_cem_step(e._h, C.byref(a), e._stream()))
-        return self.out
+            e._check(self._gather(e._h, self.ref, gather_into.data_ptr(), e._stream()))
+        return self.result

@@ -82,8 +82,8 @@ class EnvGroups:
         self._check(self.lib.cpmppi_groups_join(self._g, self._cur()))
 
     def prepare(self, s0, u_nom, target_position, target_equilibrium, L=None, seed=0, Q_out=None, S_out=None, **kw):
-        """-> ONE PreparedStep over the full [E, ...] device tensors (in-kernel Philox noise keyed by the global env index), to be
-        handed to `run`."""
+        """-> ONE prepared step (engine.PreparedCall) over the full [E, ...] device tensors (in-kernel Philox noise keyed by the
+        global env index), to be handed to `run`."""
         if Q_out is None:
             Q_out = torch.empty(self.E, dtype=torch.float32, device=self.device)
         return self.args_engine.prepare_step(s0, u_nom, target_position, target_equilibrium, L=L, seed=seed, offset=0, env_offset=0,
@@ -113,24 +113,23 @@ class EnvGroups:
 
     def run(self, step=None, plant=None, periods=1, offset=0, period=0, n_substeps=None, gather_into=None):
         """cpmppi_groups_run: `periods` control periods of every group enqueued from C, round robin - step (Philox step counter
-        offset + k) and, if given, plant step (period + k).  `step` / `plant`: PreparedStep / PreparedPlantStep over the full arrays.
+        offset + k) and, if given, plant step (period + k).  `step` / `plant`: the prepared calls of `prepare` / of the args
+        engine's `prepare_plant_step`, over the full arrays.
         `gather_into` [world, E*H (+ stamp words)]: cpmppi_groups_run_gather - one all-gather of u_nom[E, H] per period too."""
         sa = pa = None
         if step is not None:
-            step.args.offset = int(offset)
-            sa = C.byref(step.args)
+            step.set(offset=offset)
+            sa = step.ref
         if plant is not None:
-            plant.args.period = int(period)
-            if n_substeps is not None:
-                plant.args.n_substeps = int(n_substeps)
-            pa = C.byref(plant.args)
+            plant.set(period=period, n_substeps=n_substeps)
+            pa = plant.ref
         if gather_into is not None:
             self._check(self.lib.cpmppi_groups_run_gather(self._g, sa, pa, int(periods), gather_into.data_ptr()))
             return
         self._check(self.lib.cpmppi_groups_run(self._g, sa, pa, int(periods)))
 
     def prepare_step(self, s0, u_nom, target_position, target_equilibrium, L=None, seed=0, Q_out=None, S_out=None, **kw):
-        """-> one PreparedStep per GROUP over the slices of the given [E, ...] device tensors (for callers that pace the groups
+        """-> one prepared step per GROUP over the slices of the given [E, ...] device tensors (for callers that pace the groups
         themselves; `prepare` + `run` is the one-call form)."""
         E = self.E
         for name, t in (("s0", s0), ("u_nom", u_nom), ("target_position", target_position), ("target_equilibrium", target_equilibrium)):
@@ -148,11 +147,11 @@ class EnvGroups:
     def overlap(self, step, steps=20):
         """Do the groups really run side by side?  `steps` steps of every group one group after the other, then all together:
         -> sum of the groups' times alone / time together (1.0 = serialised on one hardware queue, ~G = perfect overlap).
-        `step`: a PreparedStep over the full arrays (`prepare`)."""
+        `step`: the prepared step over the full arrays (`prepare`)."""
         import time
         preps = []
         a = step.args
-        keep = step._keep
+        keep = step.keep                                               # (the tensors the groups' blocks point into as well)
         for eng, (e0, e1) in zip(self.engines, self.slices):          # the same launches, one group at a time
             b = type(a)()
             C.memmove(C.byref(b), C.byref(a), C.sizeof(a))
@@ -174,7 +173,7 @@ class EnvGroups:
             for i in range(steps):
                 for eng, b in which:
                     b.offset = 10_000 + i
-                    eng._check(eng.lib.cpmppi_step(eng._h, C.byref(b), eng._stream()))
+                    eng._check(step.enqueue(eng._h, C.byref(b), eng._stream()))
             torch.cuda.synchronize(self.device)
             return time.perf_counter() - t0
 
