@@ -30,7 +30,7 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_groups_stream", "cpmppi_groups_fork", "cpmppi_groups_join", "cpmppi_groups_run", "cpmppi_groups_last_error",
            "cpmppi_comm_set_stamped", "cpmppi_groups_comm_init", "cpmppi_groups_run_gather", "cpmppi_set_pole_mass_rows",
            "cpmppi_rpgd_reserve", "cpmppi_rpgd_step", "cpmppi_cem_reserve", "cpmppi_cem_step", "cpmppi_rollout_cost_gru",
-           "cpmppi_rollout_cost_grad_gru", "cpmppi_gru_advance")
+           "cpmppi_rollout_cost_grad_gru", "cpmppi_gru_advance", "cpmppi_gru_washout", "cpmppi_brunton")
 COMM_ID_BYTES, COMM_SLOTS, GATHER_STAMP_FLOATS = 128, 4, 4
 
 
@@ -79,6 +79,12 @@ class cpmppi_cem_args(C.Structure):
                 ("seed", C.c_uint64), ("offset", C.c_uint64), ("env_offset", C.c_uint32), ("count_dev", C.c_void_p),
                 ("Q_out", C.c_void_p), ("S_out", C.c_void_p), ("plan_out", C.c_void_p), ("samples_out", C.c_void_p),
                 ("order_out", C.c_void_p)]
+
+
+class cpmppi_brunton_args(C.Structure):
+    _fields_ = [("R", C.c_uint32), ("T", C.c_uint32), ("start", C.c_uint32), ("count", C.c_uint32), ("horizon", C.c_uint32),
+                ("predictor", C.c_uint32), ("states", C.c_void_p), ("Q", C.c_void_p), ("L", C.c_void_p), ("h_rows", C.c_void_p),
+                ("stats_out", C.c_void_p), ("pred_out", C.c_void_p)]
 
 
 class cpmppi_gru_model(C.Structure):
@@ -173,6 +179,8 @@ def load():
     lib.cpmppi_set_gru.argtypes = [vp, C.POINTER(cpmppi_gru_model)]
     lib.cpmppi_gru_predict.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_gru_advance.argtypes = [vp, u32, vp, vp, vp, vp]
+    lib.cpmppi_gru_washout.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
+    lib.cpmppi_brunton.argtypes = [vp, C.POINTER(cpmppi_brunton_args), vp]
     lib.cpmppi_rollout_cost.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost_gru.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost_grad_gru.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -5,6 +5,9 @@
 //   gru_predict_kernel                      predictor seam with the neural predictor: trajectories [B,H+1,6], hidden states.
 //   gru_advance_kernel                      one exact cell step on (state seen, control chosen), in place on h[E,2,32]: the memory
 //                                           hand-over between two control periods of the device loop.
+//   gru_washout_kernel                      that step along whole recordings, every row's memory kept: h_rows[R,T,2,32] (cpmppi_gru_washout).
+//   gru_brunton_kernel                      Brunton test with the neural predictor (cpmppi_brunton, cpmppi_seams.hip): gru_predict_kernel's
+//                                           rollout from every start row of the recordings, per-wave error statistics per horizon step.
 //   gru_rollout_cost_kernel<COST,NOISE,F16> the fused MPPI step with the GRU predictor: same contract as rollout_cost_kernel
 //                                           (plugin costs); launched by step_impl through launch_gru_rollout.
 //   gru_cost_only_kernel<COST,F16>          costs of GIVEN input plans under the GRU predictor, nothing of the MPPI update: the
@@ -15,7 +18,7 @@
 //                                           CEM + gradient hybrids over the GRU (gru_adjoint=True).
 // The rollout kernels share one rollout (GruRollout: gru_rollout_init, gru_rollout_step, gru_rollout_total) and differ in where
 // a step's input comes from and in what becomes of the costs; gru_predict_kernel runs the exact cell (gru_step) on its own.
-// Entry points: cpmppi_set_gru, cpmppi_gru_predict, cpmppi_gru_advance, cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru; -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write
+// Entry points: cpmppi_set_gru, cpmppi_gru_predict, cpmppi_gru_advance, cpmppi_gru_washout, cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru; -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write
 // g_gru_stamp_sum are this unit's).
 #include <hip/hip_runtime.h>
 #include <math.h>
@@ -194,6 +197,96 @@ __global__ __launch_bounds__(BLOCK, 1) void gru_advance_kernel(const GruNorm nm,
       hrow[gru_tile_row(v, lane >> 5)] = h1[v];
       hrow[32 + gru_tile_row(v, lane >> 5)] = h2[v];
     }
+  }
+}
+
+// A lane's registers of both hidden tiles -> one memory row [2,32] (the layout of cpmppi_step_args.h0).
+__device__ __forceinline__ void gru_store_memory(float* hrow, const f16v& h1, const f16v& h2, uint32_t lane) {
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    hrow[gru_tile_row(v, lane >> 5)] = h1[v];
+    hrow[32 + gru_tile_row(v, lane >> 5)] = h2[v];
+  }
+}
+
+// The memory along recordings (update_before_predicting of the reference's Brunton test): h_rows[r,0] = h0[r] (NULL: zeros),
+// h_rows[r,t+1] = the memory after ONE exact cell step on (states[r,t], Q[r,t]) from h_rows[r,t] - what T-1 successive
+// cpmppi_gru_advance calls leave, bit for bit: gru_advance_kernel's mapping (recording r on lanes c and c + 32 of a wave, one wave
+// per SIMD) and its cell, with the memory kept in registers between the rows instead of going through h_io.  The next row's state
+// and control do not depend on the cell: they are loaded one row ahead.  A wave without a recording leaves behind the image
+// load's barrier, the kernel's only one; a lane beyond R in a live wave repeats recording 0 and stores nothing.
+__global__ __launch_bounds__(BLOCK, 1) void gru_washout_kernel(const GruNorm nm, const float* __restrict__ image, uint32_t R,
+                                                            uint32_t T, const float* __restrict__ states,
+                                                            const float* __restrict__ Q, const float* __restrict__ h0,
+                                                            float* __restrict__ h_rows) {
+  extern __shared__ float lds[];
+  gru_load_image(lds, image, GRU_IMAGE_FLOATS);
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, c = lane & 31u;
+  const size_t r0 = (size_t)blockIdx.x * GRU_ROLLOUTS_PER_BLOCK + wave * 32;
+  if (r0 >= R) return;                                     // (wave-uniform) a tile without a recording
+  const bool valid = r0 + c < R;
+  const size_t rr = valid ? r0 + c : 0;
+  f16v h1 = gru_load_hidden(h0 ? h0 + rr * 64 : nullptr, lane);
+  f16v h2 = gru_load_hidden(h0 ? h0 + rr * 64 + 32 : nullptr, lane);
+  const float* __restrict__ s = states + rr * T * 6;
+  const float* __restrict__ q = Q + rr * T;
+  float* hrow = h_rows + rr * T * 64;
+  if (valid) gru_store_memory(hrow, h1, h2, lane);
+  float sn[6] = {s[0], s[1], s[2], s[3], s[4], s[5]};
+  float qn = q[0];
+  for (uint32_t t = 0; t + 1 < T; ++t) {
+    const f16v x = gru_input_tile(nm, sn, qn, lane);
+    if (t + 2 < T) {                                       // in flight during this row's cell
+#pragma unroll
+      for (int i = 0; i < 6; ++i) sn[i] = s[(size_t)(t + 1) * 6 + i];
+      qn = q[t + 1];
+    }
+    (void)gru_step(lds, x, h1, h2, lane);
+    hrow += 64;
+    if (valid) gru_store_memory(hrow, h1, h2, lane);
+  }
+}
+
+// Brunton test with the neural predictor: gru_predict_kernel's mapping (32 starts per wave on lanes c and c + 32, one wave per
+// SIMD) and its exact-f32 cell, begun at states[r,t] with the memory h_rows[r,t] (NULL: zeros) and fed the RECORDED controls
+// Q[r,t+k]; after step k the de-normalised state (gru_output_state: angle = atan2(sin, cos), as in the seam) is compared with
+// states[r,t+k+1] (brunton_errors).  The states live on lanes 0..31; the other half and the lanes beyond the last start enter the
+// statistics as zeros.  One partial row per WAVE, written by its lane 0 with plain stores: after the image load no wave depends
+// on another, so a wave whose 32 starts all lie beyond the last one leaves at once - there is no second barrier it could be
+// missed at, and no row of the partials for it (brunton_gru_rows counts the live waves, which are the first ones).
+__global__ __launch_bounds__(BLOCK, 1) void gru_brunton_kernel(const GruNorm nm, const float* __restrict__ image,
+                                                            const BruntonArgs a) {
+  extern __shared__ float lds[];
+  gru_load_image(lds, image, GRU_IMAGE_FLOATS);            // the kernel's only barrier
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, c = lane & 31u;
+  const size_t starts = (size_t)a.R * a.count;
+  const size_t wave_row = (size_t)blockIdx.x * WAVES + wave;
+  const size_t b0 = wave_row * 32;
+  if (b0 >= starts) return;                                // (wave-uniform) a tile without a start
+  const bool valid = b0 + c < starts;
+  const size_t b = valid ? b0 + c : 0;
+  const size_t row = (b / a.count) * a.T + a.start + b % a.count;          // (r, t) in the series
+  const float* s = a.states + row * 6;
+  f16v h1 = gru_load_hidden(a.h_rows ? a.h_rows + row * 64 : nullptr, lane);
+  f16v h2 = gru_load_hidden(a.h_rows ? a.h_rows + row * 64 + 32 : nullptr, lane);
+  f16v x = gru_input_tile(nm, s, a.Q[row], lane);
+  const bool owner = valid && lane < 32;                   // the lane that accounts for start b
+  float* o = a.pred ? a.pred + b * (size_t)(a.horizon + 1) * 6 : nullptr;
+  if (o && owner) for (int i = 0; i < 6; ++i) o[i] = s[i];
+  float* __restrict__ out = a.partials + wave_row * a.horizon * BRUNTON_STATS;
+  for (uint32_t k = 0; k < a.horizon; ++k) {
+    const f16v y = gru_step(lds, x, h1, h2, lane);
+    float st[6];
+    gru_output_state(nm, y, lane, st);
+    if (o && owner) {
+      o += 6;
+      for (int i = 0; i < 6; ++i) o[i] = st[i];
+    }
+    float e[6];
+    brunton_errors(st, a.states + (row + k + 1) * 6, e);
+    brunton_wave_stats(e, owner, lane == 0, out + (size_t)k * BRUNTON_STATS);
+    x = y;                                                 // normalised outputs are fed back unchanged
+    if (lane >= 32 && k + 1 < a.horizon) x[1] = __builtin_fmaf(a.Q[row + k + 1], nm.in_scale[0], nm.in_shift[0]);
   }
 }
 
@@ -640,6 +733,12 @@ void launch_gru(cpmppi_handle* h, const cpmppi_step_args* a, const StepPtrs& p, 
 
 }  // namespace
 
+void launch_gru_brunton(cpmppi_handle* h, const BruntonArgs& a, hipStream_t s) {
+  const size_t waves = brunton_gru_rows((size_t)a.R * a.count);
+  hipLaunchKernelGGL(gru_brunton_kernel, dim3((unsigned)((waves + WAVES - 1) / WAVES)), dim3(BLOCK),
+                     (size_t)GRU_IMAGE_FLOATS * sizeof(float), s, h->gru_norm, (const float*)h->gru_image, a);
+}
+
 void launch_gru_rollout(cpmppi_handle* h, const cpmppi_step_args* a, const StepPtrs& p, hipStream_t s) {
   const bool q = h->prm.cost_id == CPMPPI_COST_QBGM;
   if (a->noise_kind == CPMPPI_NOISE_DELTA_U) { if (q) launch_gru<COST_QBGM, NOISE_DELTA_U>(h, a, p, s); else launch_gru<COST_DEFAULT, NOISE_DELTA_U>(h, a, p, s); }
@@ -811,6 +910,22 @@ int cpmppi_gru_advance(cpmppi_handle* h, uint32_t E, const float* s, const float
   hipLaunchKernelGGL(gru_advance_kernel, dim3((E + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK), dim3(BLOCK),
                      (size_t)GRU_IMAGE_FLOATS * sizeof(float), (hipStream_t)stream, h->gru_norm, (const float*)h->gru_image, E, s,
                      Q, h_io);
+  return launched(h);
+}
+
+int cpmppi_gru_washout(cpmppi_handle* h, uint32_t R, uint32_t T, const float* states, const float* Q, const float* h0,
+                       float* h_rows_out, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_washout: no model set (cpmppi_set_gru)");
+  if (R == 0 || T == 0) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_washout: R and T must be at least 1");
+  if (!states || !Q || !h_rows_out) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_washout: states, Q, h_rows_out are required");
+  if (misaligned(states) || misaligned(Q) || misaligned(h0) || misaligned(h_rows_out))
+    return fail(h, CPMPPI_ERR_ALIGN, "cpmppi_gru_washout: misaligned pointer");
+  CPMPPI_ON_DEVICE(h);
+  // (one launch, nothing allocated, nothing awaited: the call can be captured)
+  hipLaunchKernelGGL(gru_washout_kernel, dim3((R + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK), dim3(BLOCK),
+                     (size_t)GRU_IMAGE_FLOATS * sizeof(float), (hipStream_t)stream, h->gru_norm, (const float*)h->gru_image, R, T,
+                     states, Q, h0, h_rows_out);
   return launched(h);
 }
 

@@ -62,6 +62,8 @@ struct cpmppi_handle {
   float* gru_t_image = nullptr;        // device copy of the transposed fragment image (the reverse sweep of cpmppi_rollout_cost_grad_gru)
   float* gru_grad_ws = nullptr;        // [H][GRU_CKPT_FLOATS][E*N] check-points of cpmppi_rollout_cost_grad_gru (allocated on first use)
   size_t gru_grad_ws_floats = 0;
+  float* brunton_ws = nullptr;         // [rows][horizon][6][3] partial statistics of cpmppi_brunton (allocated on first use, grown on demand)
+  size_t brunton_ws_floats = 0;
   float* grad_ckpt = nullptr;          // [H][6][E*N] check-points of cpmppi_rollout_cost_grad (allocated on first use)
   size_t grad_ckpt_floats = 0;
   float* rpgd_ws = nullptr;            // cpmppi_rpgd_step: check-points [E][H][6][block] then gradients [E][H][block] (cpmppi_rpgd_reserve)
@@ -180,6 +182,10 @@ int launch_rollout(cpmppi_handle* h, const cpmppi::Params& prm, const cpmppi_pla
 int check_plant(cpmppi_handle* h, const cpmppi_plant_args* a);
 // cpmppi_gru.hip: the fused GRU rollout kernel of a step (p.nb counted in GRU blocks); the caller checks the launch
 void launch_gru_rollout(cpmppi_handle* h, const cpmppi_step_args* a, const cpmppi_k::StepPtrs& p, hipStream_t s);
+// cpmppi_gru.hip: the Brunton test's GRU kernel (one partial row per wave of 32 starts: brunton_gru_rows of them); the caller
+// has checked the arguments, checks the launch and reduces the partial rows
+inline size_t brunton_gru_rows(size_t starts) { return (starts + 31) / 32; }
+void launch_gru_brunton(cpmppi_handle* h, const cpmppi::BruntonArgs& a, hipStream_t s);
 // called by cpmppi_create: the LDS opt-ins of the kernels of cpmppi_seams.hip and cpmppi_optim.hip
 void allow_large_lds_seams();
 void allow_large_lds_optim();

@@ -7,6 +7,9 @@
 //   sample_tiled_kernel                   a17 straight into the TILED perturbation layout (cpmppi_sample_tiled).
 //   tile_kernel                           delta_u in the reference layout -> tiled (cpmppi_tile_delta_u).
 //   predict_kernel<FAST, STAGED, INTEG>   predictor seam: trajectories [B,H+1,6] (stores staged through LDS for large launches).
+//   brunton_kernel<FAST, INTEG>           Brunton test (cpmppi_brunton): every start row of the recordings rolled forward on the recorded
+//                                         controls with predict_kernel's control step; per-workgroup error statistics per horizon step.
+//   brunton_finalize_kernel               the partial statistics of the ODE or the GRU kernel (cpmppi_gru.hip) reduced in float64.
 //   trajectory_cost_kernel                cost seam on materialised trajectories.
 //   rwa_kernel                            a16 on given (S, delta_u).
 #include <hip/hip_runtime.h>
@@ -221,6 +224,66 @@ __global__ __launch_bounds__(BLOCK) void predict_kernel(const Params p0, uint32_
   }
 }
 
+// Brunton test with an in-tree ODE predictor: the open-loop prediction error over recordings, per horizon step.  One lane per
+// start (r, t): it begins at states[r,t], integrates `horizon` control steps on the RECORDED controls Q[r,t+k] - read where the
+// series lies, no window tensor - with predict_kernel's own control step (predict_control_step: the two kernels agree by
+// construction), and after step k compares with states[r,t+k+1] (brunton_errors).  The workgroup's (sum |e|, sum e^2, max |e|)
+// per feature - wave_sum / wave_max, then the four waves through LDS as (w0 + w1) + (w2 + w3) - go to its own row of the
+// partials with plain stores: no atomics, the same bits run to run.  `red` is double-buffered by the parity of k, so one barrier
+// per step orders both the waves' stores before the combining read and that read before the stores of step k + 2.  Idle lanes
+// of the last workgroup shadow the last start (they stay for the barriers) and enter the statistics as zeros.
+// The pole mass is the handle's: per-row masses (cpmppi_set_pole_mass_rows) are the predict seam's.
+template <bool FAST, int INTEG>
+__global__ __launch_bounds__(BLOCK) void brunton_kernel(const Params p, const BruntonArgs a) {
+  __shared__ float red[2][WAVES][BRUNTON_STATS];
+  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6;
+  const size_t starts = (size_t)a.R * a.count;
+  const size_t b_raw = (size_t)blockIdx.x * BLOCK + threadIdx.x;
+  const bool live = b_raw < starts;
+  const size_t b = live ? b_raw : starts - 1;
+  const size_t row = (b / a.count) * a.T + a.start + b % a.count;          // (r, t) in the series
+  const EnvConst ec = make_env_const(p, a.L ? a.L[row] : p.L_default);
+  const float* s = a.states + row * 6;
+  State<float> st{s[0], s[1], s[2], s[3], s[4], s[5]};
+  float* o = a.pred ? a.pred + b * (size_t)(a.horizon + 1) * 6 : nullptr;
+  if (o && live) { o[0] = st.th; o[1] = st.w; o[2] = st.c; o[3] = st.s; o[4] = st.x; o[5] = st.v; }
+  float* __restrict__ out = a.partials + (size_t)blockIdx.x * a.horizon * BRUNTON_STATS;
+  for (uint32_t k = 0; k < a.horizon; ++k) {
+    predict_control_step<FAST, false, INTEG>(st, a.Q[row + k], p, ec);
+    const float pred[6] = {st.th, st.w, st.c, st.s, st.x, st.v};
+    if (o && live) {
+      o += 6;
+#pragma unroll
+      for (int f = 0; f < 6; ++f) o[f] = pred[f];
+    }
+    float e[6];
+    brunton_errors(pred, a.states + (row + k + 1) * 6, e);
+    brunton_wave_stats(e, live, lane == 0, red[k & 1u][wave]);
+    __syncthreads();
+    if (threadIdx.x < (uint32_t)BRUNTON_STATS) {
+      const float (*r)[BRUNTON_STATS] = red[k & 1u];
+      const uint32_t i = threadIdx.x;
+      out[(size_t)k * BRUNTON_STATS + i] = (i % 3u == 2u) ? fmaxf(fmaxf(r[0][i], r[1][i]), fmaxf(r[2][i], r[3][i]))
+                                                          : (r[0][i] + r[1][i]) + (r[2][i] + r[3][i]);
+    }
+  }
+}
+
+// partials[rows][horizon][6][3] -> stats[horizon][6][3]: one thread per statistic walks the partial rows first to last in
+// float64 (sums) or takes their maximum - a fixed order, whatever the launch's shape.
+__global__ __launch_bounds__(BLOCK) void brunton_finalize_kernel(const float* __restrict__ partials, uint32_t rows,
+                                                                 uint32_t per_row, double* __restrict__ stats) {
+  const uint32_t i = blockIdx.x * BLOCK + threadIdx.x;
+  if (i >= per_row) return;
+  const bool is_max = i % 3u == 2u;
+  double acc = 0.0;
+  for (uint32_t r = 0; r < rows; ++r) {
+    const double v = (double)partials[(size_t)r * per_row + i];
+    acc = is_max ? fmax(acc, v) : acc + v;
+  }
+  stats[i] = acc;
+}
+
 // cost seam on materialised trajectories
 // Cost seam.  traj[B,H+1,6] and inputs[B,H] are the reference's tensors (row-major per rollout): lane = time-step, a
 // wave walks its rows — a row's 24(H+1) bytes are read by consecutive lanes (coalesced) instead of 64 rows 1224 bytes
@@ -352,6 +415,11 @@ void launch_predict(bool staged, dim3 grid, hipStream_t st, const Params& p, uin
   else hipLaunchKernelGGL((predict_kernel<FAST, false, INTEG>), grid, dim3(BLOCK), 0, st, p, B, H, s0, Q, L, traj, m_pole);
 }
 
+template <bool FAST, int INTEG>
+void launch_brunton(dim3 grid, hipStream_t st, const Params& p, const BruntonArgs& a) {
+  hipLaunchKernelGGL((brunton_kernel<FAST, INTEG>), grid, dim3(BLOCK), 0, st, p, a);
+}
+
 }  // namespace
 
 void allow_large_lds_seams() {
@@ -423,6 +491,50 @@ int cpmppi_predict(cpmppi_handle* h, uint32_t B, uint32_t horizon, const float* 
   const auto launch = fast ? (cromer ? launch_predict<true, PREDICTOR_ODE> : launch_predict<true, PREDICTOR_ODE_V0>)
                            : (cromer ? launch_predict<false, PREDICTOR_ODE> : launch_predict<false, PREDICTOR_ODE_V0>);
   launch(staged, dim3((B + BLOCK - 1) / BLOCK), (hipStream_t)stream, h->prm, B, horizon, s0, Q, L, traj_out, h->m_pole_rows);
+  return launched(h);
+}
+
+int cpmppi_brunton(cpmppi_handle* h, const cpmppi_brunton_args* a, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  const auto refuse = [&](const std::string& why) { return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_brunton: " + why); };
+  if (!a) return refuse("no argument block");
+  if (!a->states || !a->Q || !a->stats_out) return refuse("states, Q, stats_out are required");
+  if (a->R == 0 || a->count == 0 || a->horizon == 0) return refuse("R, count and horizon must be at least 1");
+  if (a->horizon > h->cfg.H)
+    return refuse("horizon " + std::to_string(a->horizon) + " is longer than the handle's (" + std::to_string(h->cfg.H) + ")");
+  if ((uint64_t)a->start + a->count + a->horizon > (uint64_t)a->T)
+    return refuse("start + count + horizon = " + std::to_string((uint64_t)a->start + a->count + a->horizon) +
+                  " rows, a recording has T = " + std::to_string(a->T));
+  const bool gru = a->predictor == CPMPPI_PREDICTOR_GRU;
+  if (!gru && a->predictor != CPMPPI_PREDICTOR_ODE_V0) return refuse("unknown predictor " + std::to_string(a->predictor));
+  if (gru && !h->gru_image) return refuse("no model set (cpmppi_set_gru)");
+  if (gru && a->L) return refuse("the GRU predictor takes no L: the network is the plant model");
+  if (!gru && a->h_rows) return refuse("h_rows is the memory of the GRU predictor");
+  const size_t starts = (size_t)a->R * a->count;
+  const size_t rows = gru ? brunton_gru_rows(starts) : (starts + BLOCK - 1) / BLOCK;
+  if (rows > 0x7fffffffull) return refuse("too many starts for one launch");
+  if (misaligned(a->states) || misaligned(a->Q) || misaligned(a->L) || misaligned(a->h_rows) || misaligned(a->pred_out) ||
+      (reinterpret_cast<uintptr_t>(a->stats_out) & 7u) != 0)
+    return fail(h, CPMPPI_ERR_ALIGN, "cpmppi_brunton: misaligned pointer");
+  CPMPPI_ON_DEVICE(h);
+  // one partial row per workgroup (ODE) or wave (GRU); allocated on first use and grown on demand, never inside a capture
+  const size_t per_row = (size_t)a->horizon * BRUNTON_STATS, need = rows * per_row;
+  if (h->brunton_ws_floats < need) {
+    if (const int rc = refuse_unreserved_capture(h, (hipStream_t)stream, "cpmppi_brunton", "cpmppi_brunton once")) return rc;
+    if (const int rc = grow_workspace(h, h->brunton_ws, h->brunton_ws_floats, need)) return rc;
+  }
+  const BruntonArgs k{a->states, a->Q, a->L, a->h_rows, h->brunton_ws, a->pred_out, a->R, a->T, a->start, a->count, a->horizon};
+  if (gru) {
+    launch_gru_brunton(h, k, (hipStream_t)stream);
+  } else {
+    const bool fast = h->cfg.math_mode == CPMPPI_MATH_FAST, cromer = h->cfg.ode_predictor == CPMPPI_ODE_CROMER;
+    const auto launch = fast ? (cromer ? launch_brunton<true, PREDICTOR_ODE> : launch_brunton<true, PREDICTOR_ODE_V0>)
+                             : (cromer ? launch_brunton<false, PREDICTOR_ODE> : launch_brunton<false, PREDICTOR_ODE_V0>);
+    launch(dim3((unsigned)rows), (hipStream_t)stream, h->prm, k);
+  }
+  CPMPPI_HIP(h, hipGetLastError());
+  hipLaunchKernelGGL(brunton_finalize_kernel, dim3((unsigned)((per_row + BLOCK - 1) / BLOCK)), dim3(BLOCK), 0, (hipStream_t)stream,
+                     (const float*)h->brunton_ws, (uint32_t)rows, (uint32_t)per_row, a->stats_out);
   return launched(h);
 }
 

@@ -576,6 +576,77 @@ class MPPIEngine:
         self._check(self.lib.cpmppi_gru_advance(self._h, E, _ptr(s), _ptr(Q), _ptr(h), self._stream()))
         return h
 
+    # ------------------------------------------------------------------ Brunton test: predictor error over recordings
+    def _recordings(self, states, Q):
+        """brunton / gru_washout: -> (states [R,T,6], Q [R,T], R, T) on the device."""
+        states, Q = self.tensor(states), self.tensor(Q)
+        if states.dim() != 3 or states.shape[2] != 6 or states.shape[0] == 0 or states.shape[1] == 0:
+            raise ValueError(f"states must be [R,T,6] with R, T >= 1, got {tuple(states.shape)}")
+        R, T = states.shape[0], states.shape[1]
+        if Q.dim() == 3 and Q.shape[2] == 1:                    # (the reference's [.., 1] control axis)
+            Q = Q[:, :, 0].contiguous()
+        if Q.shape != (R, T):
+            raise ValueError(f"Q must be [{R},{T}] for states [{R},{T},6], got {tuple(Q.shape)}")
+        return states, Q, R, T
+
+    def gru_washout(self, states, Q, h0=None, out=None):
+        """cpmppi_gru_washout: the network's memory along recordings ``states`` [R,T,6], ``Q`` [R,T] - row 0 holds ``h0`` [R,2,32]
+        (None: zeros), row t+1 the memory after one cell step on (states[:,t], Q[:,t]): what T-1 ``gru_advance`` calls leave, bit
+        for bit, in one launch.  -> ``out`` [R,T,2,32] (None: allocated here), the ``h_rows`` of ``brunton``."""
+        states, Q, R, T = self._recordings(states, Q)
+        h0 = self.tensor(h0, (R, 2, 32)) if h0 is not None else None
+        if out is None:
+            out = self.empty(R, T, 2, 32)
+        elif device_tensor("out", out, tail=(T, 2, 32)).shape[0] != R:
+            raise ValueError(f"out must be [{R},{T},2,32], got {tuple(out.shape)}")
+        self._check(self.lib.cpmppi_gru_washout(self._h, R, T, _ptr(states), _ptr(Q), _ptr(h0), _ptr(out), self._stream()))
+        return out
+
+    def _build_brunton(self, states, Q, L=None, *, horizon, start=0, count=None, predictor="ODE_v0", h_rows=None, stats_out=None,
+                       pred_out=None, return_predictions=False):
+        """cpmppi_brunton: the open-loop error of a predictor over recordings ``states`` [R,T,6], ``Q`` [R,T] (include/cpmppi.h
+        states the test).  From each of the ``count`` rows from ``start`` on (None: every start whose whole ``horizon`` lies inside
+        the recording) the predictor is rolled forward on the recorded controls.  ``predictor="ODE_v0"``: the engine's ODE
+        predictor, ``L`` [R,T] the pole length per row (None: the config's); ``"GRU"``: the network of ``set_gru`` with the memory
+        ``h_rows`` [R,T,2,32] of ``gru_washout`` (None: zeros); it knows no pole length, so ``L`` is refused.
+        -> (stats [horizon,6,3] float64 on the device: sum |e|, sum e^2, max |e| per horizon step and feature over the R*count
+        starts; predictions [R*count,horizon+1,6] - ``pred_out``, or allocated with ``return_predictions`` - else None)."""
+        gru = _is_gru(predictor)
+        if gru and L is not None:
+            raise ValueError("predictor='GRU' takes no L: the network is the plant model")
+        if not gru and h_rows is not None:
+            raise ValueError("h_rows is the memory of the GRU predictor: pass predictor='GRU'")
+        states, Q, R, T = self._recordings(states, Q)
+        horizon, start = int(horizon), int(start)
+        count = T - start - horizon if count is None else int(count)
+        if not 1 <= horizon <= self.H:
+            raise ValueError(f"horizon must be in 1..{self.H} (the engine's mpc_horizon), got {horizon}")
+        if start < 0 or count < 1 or start + count + horizon > T:
+            raise ValueError(f"start {start} + count {count} + horizon {horizon} must lie inside the recording's {T} rows, count >= 1")
+        L = self.tensor(L, (R, T)) if L is not None else None
+        h_rows = self.tensor(h_rows, (R, T, 2, 32)) if h_rows is not None else None
+        if stats_out is None:
+            stats_out = torch.empty(horizon, 6, 3, dtype=torch.float64, device=self.device)
+        elif device_tensor("stats_out", stats_out, torch.float64, (6, 3)).shape[0] != horizon:
+            raise ValueError(f"stats_out must be [{horizon},6,3]")
+        if pred_out is None and return_predictions:
+            pred_out = self.empty(R * count, horizon + 1, 6)
+        elif pred_out is not None and device_tensor("pred_out", pred_out, tail=(horizon + 1, 6)).shape[0] != R * count:
+            raise ValueError(f"pred_out must be [{R * count},{horizon + 1},6]")
+        a = _L.cpmppi_brunton_args()
+        a.R, a.T, a.start, a.count, a.horizon = R, T, start, count, horizon
+        a.predictor = _L.PREDICTOR_GRU if gru else _L.PREDICTOR_ODE_V0
+        a.states, a.Q, a.L, a.h_rows = states.data_ptr(), Q.data_ptr(), _addr(L), _addr(h_rows)
+        a.stats_out, a.pred_out = stats_out.data_ptr(), _addr(pred_out)
+        return PreparedCall(self, self.lib.cpmppi_brunton, a, (states, Q, L, h_rows, stats_out, pred_out), (stats_out, pred_out), ())
+
+    brunton = _run_once(_build_brunton)
+
+    def prepare_brunton(self, *args, **kwargs):
+        """The argument block of ``brunton(...)`` built and validated ONCE: ``.run()`` enqueues the two launches again on the same
+        buffers (a benchmark loop, a capture - after one plain run, which allocates the workspace)."""
+        return self._build_brunton(*args, **kwargs)
+
     # ------------------------------------------------------------------ cost-only launch and CEM (SURVEY §8f N4)
     def _per_env(self, x, E):
         x = self.tensor(x)
@@ -895,10 +966,11 @@ class MPPIEngine:
 
 class PreparedCall:
     """One entry point of the library that takes an argument block, ready to be enqueued any number of times
-    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_cem_step).  ``args`` is the live ctypes block,
-    validated when it was built, and ``ref`` the reference to it that the library is handed; ``keep`` holds the tensors it
-    points into; ``enqueue`` is the entry point, ``enqueue(handle, ref, stream)``.  ``result`` is what the call returns: the
-    outputs of a control step - ``out``, whose first two are ``Q_out`` and ``S_out`` - or the plant's state."""
+    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_cem_step / prepare_brunton).  ``args`` is the live
+    ctypes block, validated when it was built, and ``ref`` the reference to it that the library is handed; ``keep`` holds the
+    tensors it points into; ``enqueue`` is the entry point, ``enqueue(handle, ref, stream)``.  ``result`` is what the call returns:
+    the outputs of a control step - ``out``, whose first two are ``Q_out`` and ``S_out`` -, the plant's state, or the Brunton
+    test's (statistics, predictions)."""
 
     def __init__(self, engine, enqueue, args, keep, result, fields, gather=None):
         self.engine, self.enqueue, self.args, self.keep, self.result = engine, enqueue, args, keep, result

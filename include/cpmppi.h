@@ -55,7 +55,8 @@ extern "C" {
                                       cpmppi_set_pole_mass_rows (a new entry point: no layout and no existing semantics change);
                                       cpmppi_rpgd_step / cpmppi_rpgd_reserve / cpmppi_rpgd_args (new entry points, likewise);
                                       cpmppi_cem_step / cpmppi_cem_reserve / cpmppi_cem_args (new entry points, likewise);
-                                      cpmppi_gru_advance (a new entry point, likewise). */
+                                      cpmppi_gru_advance (a new entry point, likewise);
+                                      cpmppi_brunton / cpmppi_brunton_args, cpmppi_gru_washout (new entry points, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -320,6 +321,45 @@ int cpmppi_gru_predict(cpmppi_handle* h, uint32_t B, uint32_t horizon, const flo
  * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned (cpmppi_last_error: "cpmppi_gru_advance: ...") when no model is set,
  * E == 0 or E > cfg.E, or a pointer is NULL. */
 int cpmppi_gru_advance(cpmppi_handle* h, uint32_t E, const float* s, const float* Q, float* h_io, void* stream);
+
+/* The GRU memory along R recordings of T rows each (update_before_predicting of the reference's Brunton test):
+ * h_rows_out[R,T,2,32] with h_rows_out[r,0] = h0[r] (h0[R,2,32], NULL = zeros) and h_rows_out[r,t+1] = the memory after one
+ * exact cell step on (states[r,t], Q[r,t]) from h_rows_out[r,t] - bit for bit what T-1 successive cpmppi_gru_advance calls
+ * leave in h_io.  states[R,T,6], Q[R,T]; device pointers.  ONE launch on `stream`, no allocation: can be captured.
+ * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned ("cpmppi_gru_washout: ...") when no model is set, R == 0, T == 0 or a
+ * required pointer is NULL. */
+int cpmppi_gru_washout(cpmppi_handle* h, uint32_t R, uint32_t T, const float* states, const float* Q, const float* h0,
+                       float* h_rows_out, void* stream);
+
+/* Brunton test (SI_Toolkit_ASF/Run/A3_Run_Brunton_Test.py, config_testing.yml): the open-loop error of a predictor over
+ * recordings.  From every start row t = start .. start+count-1 of each of R recordings of T rows the predictor is rolled forward
+ * `horizon` control steps on the RECORDED controls Q[r,t+k], beginning at states[r,t]; the state after step k is compared with
+ * states[r,t+k+1].  Error per feature, in state order, in float32: e = predicted - recorded, the angle's wrapped afterwards,
+ * e - 2 pi rint(e / 2 pi).  stats_out[horizon,6,3] (DEVICE doubles): (sum |e|, sum e^2, max |e|) over all R*count starts, horizon
+ * step k+1 at index k - reduced in a fixed order without atomics: the same bits from run to run.  pred_out (optional)
+ * [R*count,horizon+1,6]: the predictions, [b,0] the start state, b = r*count + (t-start): what cpmppi_predict /
+ * cpmppi_gru_predict return for the materialised windows, bit for bit.
+ * predictor CPMPPI_PREDICTOR_ODE_V0: the handle's ODE predictor in the handle's math mode, pole length L[r,t] of the start row or
+ * config.L_default, pole mass the handle's (cpmppi_set_pole_mass_rows is not read).  CPMPPI_PREDICTOR_GRU: the network of
+ * cpmppi_set_gru (exact-f32 cell) with the memory h_rows[r,t] of the start row (cpmppi_gru_washout; NULL = zeros everywhere).
+ * Two launches on `stream`; the workspace of partial sums is allocated on first use and grown on demand - a capture that
+ * would have to allocate is refused (run the call once before capturing).
+ * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned ("cpmppi_brunton: ...") for a NULL required pointer; R, count or
+ * horizon == 0; horizon > config.H; start + count + horizon > T; an unknown predictor; the GRU without a model; L with the GRU;
+ * h_rows without it. */
+typedef struct {
+  uint32_t R, T;                 /* recordings, rows of each */
+  uint32_t start, count;         /* start rows start .. start+count-1 of every recording */
+  uint32_t horizon;              /* control steps predicted from each start (test_max_horizon) */
+  uint32_t predictor;            /* CPMPPI_PREDICTOR_ODE_V0 or CPMPPI_PREDICTOR_GRU */
+  const float* states;           /* [R,T,6] */
+  const float* Q;                /* [R,T] */
+  const float* L;                /* [R,T] or NULL (ODE only) */
+  const float* h_rows;           /* [R,T,2,32] or NULL (GRU only) */
+  double* stats_out;             /* [horizon,6,3] */
+  float* pred_out;               /* [R*count,horizon+1,6] or NULL */
+} cpmppi_brunton_args;
+int cpmppi_brunton(cpmppi_handle* h, const cpmppi_brunton_args* args, void* stream);
 
 /* Rollout + cost only (no update): per-rollout trajectory cost S[E,N] of GIVEN input sequences inputs[E,N,H] under the
  * handle's plugin cost — cost_function.get_trajectory_cost(predictor.predict_core(s, Q), Q) fused; the building block of
