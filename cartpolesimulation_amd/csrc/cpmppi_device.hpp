@@ -1367,7 +1367,7 @@ __device__ __forceinline__ float wave_max(float v) {
   return fmaxf(fmaxf(row_lane_(v, 0), row_lane_(v, 16)), fmaxf(row_lane_(v, 32), row_lane_(v, 48)));
 }
 
-// ---- Brunton test (cpmppi_brunton): what its ODE kernel (cpmppi_seams.hip) and its GRU kernel (cpmppi_gru.hip) share ----------
+// ---- Brunton test (cpmppi_brunton): what its ODE kernel (cpmppi_seams.hip) and its GRU kernel (cpmppi_gru_seam.hip) share ----------
 // A start is row t = start + i of recording r; b = r * count + i numbers the starts.  partials[rows][horizon][6][3]: per horizon
 // step and feature (sum |e|, sum e^2, max |e|) over the starts of one partial row - a workgroup of the ODE kernel, a wave of the
 // GRU kernel - written with plain stores by the row's owner and reduced over the rows in a fixed order (brunton_finalize_kernel).

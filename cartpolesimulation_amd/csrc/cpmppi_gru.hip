@@ -1,45 +1,21 @@
-// cpmppi_gru.hip — the GRU predictor (BASELINE configs[4]): model upload, its predictor seam, and the fused MPPI step with it.
+// cpmppi_gru.hip — the GRU predictor (BASELINE configs[4]) inside the optimizers: the kernels that share one rollout, GruRollout.
 // The cell and its mapping onto the matrix cores: cpmppi_gru.hpp (exact f32 MFMA chains) and cpmppi_gru16.hpp (f16 split).
-//
-// Kernel inventory
-//   gru_predict_kernel                      predictor seam with the neural predictor: trajectories [B,H+1,6], hidden states.
-//   gru_advance_kernel                      one exact cell step on (state seen, control chosen), in place on h[E,2,32]: the memory
-//                                           hand-over between two control periods of the device loop.
-//   gru_washout_kernel                      that step along whole recordings, every row's memory kept: h_rows[R,T,2,32] (cpmppi_gru_washout).
-//   gru_brunton_kernel                      Brunton test with the neural predictor (cpmppi_brunton, cpmppi_seams.hip): gru_predict_kernel's
-//                                           rollout from every start row of the recordings, per-wave error statistics per horizon step.
+// The model upload is cpmppi_gru_model.hip, the exact-cell seams are cpmppi_gru_seam.hip, the reverse sweep is cpmppi_gru_adjoint.hip.
 //   gru_rollout_cost_kernel<COST,NOISE,F16> the fused MPPI step with the GRU predictor: same contract as rollout_cost_kernel
 //                                           (plugin costs); launched by step_impl through launch_gru_rollout.
 //   gru_cost_only_kernel<COST,F16>          costs of GIVEN input plans under the GRU predictor, nothing of the MPPI update: the
 //                                           building block of the sampling optimizers (cem, cem-gmm, random-action).
-//   gru_grad_forward_kernel<COST,F16>       the cost-only rollout that also parks, per control step, what the reverse sweep needs;
-//   gru_grad_reverse_kernel<COST>           the reverse sweep through head, layer 2 and layer 1 (exact f32 MFMA on a transposed weights
-//                                           image): d cost / d inputs of GIVEN plans - the building block of gradient, rpgd and the
-//                                           CEM + gradient hybrids over the GRU (gru_adjoint=True).
-// The rollout kernels share one rollout (GruRollout: gru_rollout_init, gru_rollout_step, gru_rollout_total) and differ in where
-// a step's input comes from and in what becomes of the costs; gru_predict_kernel runs the exact cell (gru_step) on its own.
-// Entry points: cpmppi_set_gru, cpmppi_gru_predict, cpmppi_gru_advance, cpmppi_gru_washout, cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru; -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write
-// g_gru_stamp_sum are this unit's).
-#include <hip/hip_runtime.h>
-#include <math.h>
-#include <exception>
-#include <string>
-#include <vector>
-
-#include "cpmppi.h"
-#include "cpmppi_internal.hpp"
-#include "cpmppi_gru.hpp"
-#include "cpmppi_gru16.hpp"
-#include "cpmppi_grad.hpp"       // (stage_qbgm_grad, stage_default_grad)
+//   gru_grad_forward_kernel<COST,F16>       the cost-only rollout that also parks, per control step, what the reverse sweep
+//                                           (gru_grad_reverse_kernel, cpmppi_gru_adjoint.hip) needs.
+// They share one rollout (GruRollout: gru_rollout_init, gru_rollout_step, gru_rollout_total) and differ in where a step's input
+// comes from and in what becomes of the costs.  Entry points: cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru;
+// -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write g_gru_stamp_sum are this unit's).
+#include <type_traits>
+#include "cpmppi_gru16.hpp"      // (and cpmppi_gru.hpp, cpmppi_internal.hpp)
 
 using namespace cpmppi_k;
 
 namespace {
-
-__device__ __forceinline__ void gru_load_image(float* __restrict__ lds, const float* __restrict__ image, int floats) {
-  for (int i = threadIdx.x; i < floats; i += BLOCK) lds[i] = image[i];
-  __syncthreads();
-}
 
 // The weights image of the two rollout kernels: the f16 split (FAST) or the exact f32 fragments.
 template <bool F16>
@@ -62,6 +38,9 @@ struct GruRollout {
 
 // development aid (-DCPMPPI_GRU_STAMPS): the stamp sums a step adds to.  The fused kernel publishes them; the cost-only kernel has no
 // stamps of its own and hands the cell an object it drops (the stamped cell takes no other form).  Empty in product builds.
+#ifdef CPMPPI_GRU_STAMPS
+__device__ unsigned long long g_gru_stamp_sum[8];
+#endif
 struct GruStamps {
 #ifdef CPMPPI_GRU_STAMPS
   unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
@@ -130,164 +109,6 @@ __device__ __forceinline__ float gru_rollout_total(GruRollout& r, float x_t, con
   r.st[0] = atan2f(r.st[3], r.st[2]);       // predictors_customization.py:121-127, needed for the terminal cost only
   const float term = (COST == COST_DEFAULT) ? terminal_indicator<float>(p, r.st[0], r.st[4], x_t) : 0.0f;
   return (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? (r.cost + term) : (r.cost + term) / (float)(p.H + 1);
-}
-
-// predictor seam with the neural predictor: s0[B,6], Q[B,H], h0[2,B,32] or NULL -> traj[B,H+1,6], h_out[2,B,32] or NULL
-// (one wave per SIMD: the exact-f32 MFMA chain of gru_step with all its fragment loads in flight wants more than 256 registers -
-// compiled for two waves per SIMD it spilled 38 of them to a 156-byte scratch slot; the seam is bound by the matrix pipe either way)
-__global__ __launch_bounds__(BLOCK, 1) void gru_predict_kernel(const GruNorm nm, const float* __restrict__ image, uint32_t B,
-                                                            uint32_t H, const float* __restrict__ s0,
-                                                            const float* __restrict__ Q, const float* __restrict__ h0,
-                                                            float* __restrict__ traj, float* __restrict__ h_out) {
-  extern __shared__ float lds[];
-  gru_load_image(lds, image, GRU_IMAGE_FLOATS);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, c = lane & 31u;
-  const size_t b = (size_t)blockIdx.x * GRU_ROLLOUTS_PER_BLOCK + wave * 32 + c;
-  const bool valid = b < B;
-  const size_t bb = valid ? b : 0;
-  const float* s = s0 + bb * 6;
-  f16v h1 = gru_load_hidden(h0 ? h0 + bb * 32 : nullptr, lane);
-  f16v h2 = gru_load_hidden(h0 ? h0 + ((size_t)B + bb) * 32 : nullptr, lane);
-  f16v x = gru_input_tile(nm, s, Q[bb * H], lane);
-  float* o = traj + bb * (size_t)(H + 1) * 6;
-  if (valid && lane < 32) for (int i = 0; i < 6; ++i) o[i] = s[i];
-  for (uint32_t k = 0; k < H; ++k) {
-    const f16v out = gru_step(lds, x, h1, h2, lane);
-    float st[6];
-    gru_output_state(nm, out, lane, st);
-    if (valid && lane < 32) {
-      o += 6;
-      for (int i = 0; i < 6; ++i) o[i] = st[i];
-    }
-    x = out;                                               // normalised outputs are fed back unchanged
-    if (lane >= 32 && k + 1 < H) x[1] = __builtin_fmaf(Q[bb * H + k + 1], nm.in_scale[0], nm.in_shift[0]);
-  }
-  if (h_out && valid) {
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      h_out[bb * 32 + gru_tile_row(v, lane >> 5)] = h1[v];
-      h_out[((size_t)B + bb) * 32 + gru_tile_row(v, lane >> 5)] = h2[v];
-    }
-  }
-}
-
-// The memory hand-over of the device loop: h_io[E,2,32] (the rollout kernels' layout) <- hidden states after ONE exact cell step
-// on (s[E,6], Q[E]), in place.  gru_predict_kernel's mapping (env e on lanes c and c + 32 of a wave, one wave per SIMD for the
-// same reason) and its cell, so what it stores is what that kernel writes to h_out for B = E, H = 1; the head's result is
-// dropped, nothing is de-normalised.  In place is safe: all of a live env's loads precede its stores in its own wave, and no
-// other wave stores to its rows.  A lane beyond E repeats row 0, which block 0 may be rewriting at that moment: what it then
-// computes is undefined but never stored (an MFMA column depends on its own column only, so it reaches no live env either).
-__global__ __launch_bounds__(BLOCK, 1) void gru_advance_kernel(const GruNorm nm, const float* __restrict__ image, uint32_t E,
-                                                            const float* __restrict__ s, const float* __restrict__ Q,
-                                                            float* h_io) {
-  extern __shared__ float lds[];
-  gru_load_image(lds, image, GRU_IMAGE_FLOATS);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, c = lane & 31u;
-  const size_t e = (size_t)blockIdx.x * GRU_ROLLOUTS_PER_BLOCK + wave * 32 + c;
-  const bool valid = e < E;
-  const size_t ee = valid ? e : 0;
-  float* hrow = h_io + ee * 64;
-  f16v h1 = gru_load_hidden(hrow, lane);
-  f16v h2 = gru_load_hidden(hrow + 32, lane);
-  const f16v x = gru_input_tile(nm, s + ee * 6, Q[ee], lane);
-  (void)gru_step(lds, x, h1, h2, lane);
-  if (valid) {
-#pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      hrow[gru_tile_row(v, lane >> 5)] = h1[v];
-      hrow[32 + gru_tile_row(v, lane >> 5)] = h2[v];
-    }
-  }
-}
-
-// A lane's registers of both hidden tiles -> one memory row [2,32] (the layout of cpmppi_step_args.h0).
-__device__ __forceinline__ void gru_store_memory(float* hrow, const f16v& h1, const f16v& h2, uint32_t lane) {
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    hrow[gru_tile_row(v, lane >> 5)] = h1[v];
-    hrow[32 + gru_tile_row(v, lane >> 5)] = h2[v];
-  }
-}
-
-// The memory along recordings (update_before_predicting of the reference's Brunton test): h_rows[r,0] = h0[r] (NULL: zeros),
-// h_rows[r,t+1] = the memory after ONE exact cell step on (states[r,t], Q[r,t]) from h_rows[r,t] - what T-1 successive
-// cpmppi_gru_advance calls leave, bit for bit: gru_advance_kernel's mapping (recording r on lanes c and c + 32 of a wave, one wave
-// per SIMD) and its cell, with the memory kept in registers between the rows instead of going through h_io.  The next row's state
-// and control do not depend on the cell: they are loaded one row ahead.  A wave without a recording leaves behind the image
-// load's barrier, the kernel's only one; a lane beyond R in a live wave repeats recording 0 and stores nothing.
-__global__ __launch_bounds__(BLOCK, 1) void gru_washout_kernel(const GruNorm nm, const float* __restrict__ image, uint32_t R,
-                                                            uint32_t T, const float* __restrict__ states,
-                                                            const float* __restrict__ Q, const float* __restrict__ h0,
-                                                            float* __restrict__ h_rows) {
-  extern __shared__ float lds[];
-  gru_load_image(lds, image, GRU_IMAGE_FLOATS);
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, c = lane & 31u;
-  const size_t r0 = (size_t)blockIdx.x * GRU_ROLLOUTS_PER_BLOCK + wave * 32;
-  if (r0 >= R) return;                                     // (wave-uniform) a tile without a recording
-  const bool valid = r0 + c < R;
-  const size_t rr = valid ? r0 + c : 0;
-  f16v h1 = gru_load_hidden(h0 ? h0 + rr * 64 : nullptr, lane);
-  f16v h2 = gru_load_hidden(h0 ? h0 + rr * 64 + 32 : nullptr, lane);
-  const float* __restrict__ s = states + rr * T * 6;
-  const float* __restrict__ q = Q + rr * T;
-  float* hrow = h_rows + rr * T * 64;
-  if (valid) gru_store_memory(hrow, h1, h2, lane);
-  float sn[6] = {s[0], s[1], s[2], s[3], s[4], s[5]};
-  float qn = q[0];
-  for (uint32_t t = 0; t + 1 < T; ++t) {
-    const f16v x = gru_input_tile(nm, sn, qn, lane);
-    if (t + 2 < T) {                                       // in flight during this row's cell
-#pragma unroll
-      for (int i = 0; i < 6; ++i) sn[i] = s[(size_t)(t + 1) * 6 + i];
-      qn = q[t + 1];
-    }
-    (void)gru_step(lds, x, h1, h2, lane);
-    hrow += 64;
-    if (valid) gru_store_memory(hrow, h1, h2, lane);
-  }
-}
-
-// Brunton test with the neural predictor: gru_predict_kernel's mapping (32 starts per wave on lanes c and c + 32, one wave per
-// SIMD) and its exact-f32 cell, begun at states[r,t] with the memory h_rows[r,t] (NULL: zeros) and fed the RECORDED controls
-// Q[r,t+k]; after step k the de-normalised state (gru_output_state: angle = atan2(sin, cos), as in the seam) is compared with
-// states[r,t+k+1] (brunton_errors).  The states live on lanes 0..31; the other half and the lanes beyond the last start enter the
-// statistics as zeros.  One partial row per WAVE, written by its lane 0 with plain stores: after the image load no wave depends
-// on another, so a wave whose 32 starts all lie beyond the last one leaves at once - there is no second barrier it could be
-// missed at, and no row of the partials for it (brunton_gru_rows counts the live waves, which are the first ones).
-__global__ __launch_bounds__(BLOCK, 1) void gru_brunton_kernel(const GruNorm nm, const float* __restrict__ image,
-                                                            const BruntonArgs a) {
-  extern __shared__ float lds[];
-  gru_load_image(lds, image, GRU_IMAGE_FLOATS);            // the kernel's only barrier
-  const uint32_t lane = threadIdx.x & 63u, wave = threadIdx.x >> 6, c = lane & 31u;
-  const size_t starts = (size_t)a.R * a.count;
-  const size_t wave_row = (size_t)blockIdx.x * WAVES + wave;
-  const size_t b0 = wave_row * 32;
-  if (b0 >= starts) return;                                // (wave-uniform) a tile without a start
-  const bool valid = b0 + c < starts;
-  const size_t b = valid ? b0 + c : 0;
-  const size_t row = (b / a.count) * a.T + a.start + b % a.count;          // (r, t) in the series
-  const float* s = a.states + row * 6;
-  f16v h1 = gru_load_hidden(a.h_rows ? a.h_rows + row * 64 : nullptr, lane);
-  f16v h2 = gru_load_hidden(a.h_rows ? a.h_rows + row * 64 + 32 : nullptr, lane);
-  f16v x = gru_input_tile(nm, s, a.Q[row], lane);
-  const bool owner = valid && lane < 32;                   // the lane that accounts for start b
-  float* o = a.pred ? a.pred + b * (size_t)(a.horizon + 1) * 6 : nullptr;
-  if (o && owner) for (int i = 0; i < 6; ++i) o[i] = s[i];
-  float* __restrict__ out = a.partials + wave_row * a.horizon * BRUNTON_STATS;
-  for (uint32_t k = 0; k < a.horizon; ++k) {
-    const f16v y = gru_step(lds, x, h1, h2, lane);
-    float st[6];
-    gru_output_state(nm, y, lane, st);
-    if (o && owner) {
-      o += 6;
-      for (int i = 0; i < 6; ++i) o[i] = st[i];
-    }
-    float e[6];
-    brunton_errors(st, a.states + (row + k + 1) * 6, e);
-    brunton_wave_stats(e, owner, lane == 0, out + (size_t)k * BRUNTON_STATS);
-    x = y;                                                 // normalised outputs are fed back unchanged
-    if (lane >= 32 && k + 1 < a.horizon) x[1] = __builtin_fmaf(a.Q[row + k + 1], nm.in_scale[0], nm.in_shift[0]);
-  }
 }
 
 // Fused MPPI step with the GRU predictor: same contract as rollout_cost_kernel (plugin costs), h0[E,2,32] or NULL.
@@ -415,16 +236,6 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_rollout_cost_kernel(
 // partials.  Dynamic LDS holds the weights image only, and after its load no wave depends on another: a wave whose 32 rollouts
 // all lie beyond N leaves at once, and there is no barrier behind the one of the image load.
 // The lane's next input does not depend on the state: it is loaded one control step ahead, off the recurrent chain.
-struct GruCostPtrs {
-  const float* s0;       // [E,6]
-  const float* inputs;   // [E,N,H]
-  const float* x_t;      // [E] target position
-  const float* te;       // [E] target equilibrium
-  const float* h0;       // [E,2,32] or NULL = 0
-  float* S_out;          // [E,N]
-  uint32_t nb;           // blocks per env
-};
-
 template <int COST, bool F16>
 __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_cost_only_kernel(const Params p, const GruCostPtrs a, const GruNorm nm,
                                                                               const float* __restrict__ image) {
@@ -455,56 +266,12 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_cost_only_kernel(con
   if (owner) a.S_out[(size_t)env * p.N + n] = S_total;
 }
 
-// FAST: float32-equivalent split products on the f16 matrix cores (cpmppi_gru16.hpp); PRECISE: exact f32 MFMA chains
-inline bool gru_runs_f16(const cpmppi_handle* h) { return h->cfg.math_mode == CPMPPI_MATH_FAST && h->gru16_image != nullptr; }
-
-template <int COST>
-void launch_gru_cost_only(cpmppi_handle* h, const GruCostPtrs& a, uint32_t E, hipStream_t s) {
-  const bool f16 = gru_runs_f16(h);
-  const dim3 grid(E * a.nb);
-  if (f16) hipLaunchKernelGGL((gru_cost_only_kernel<COST, true>), grid, dim3(BLOCK), (size_t)G16_IMAGE_BYTES, s, h->prm, a,
-                              h->gru_norm, (const float*)h->gru16_image);
-  else hipLaunchKernelGGL((gru_cost_only_kernel<COST, false>), grid, dim3(BLOCK), (size_t)GRU_IMAGE_FLOATS * sizeof(float), s,
-                          h->prm, a, h->gru_norm, (const float*)h->gru_image);
-}
-
-// ---- cost and gradient: cpmppi_rollout_cost_grad_gru = gru_grad_forward_kernel, then gru_grad_reverse_kernel, on one stream.
-// Two launches rather than one kernel that swaps its LDS image between the sweeps: each keeps the cost-only kernel's shape (one
-// barrier, behind the image load; a wave without a rollout leaves at once) and the forward half IS the cost-only kernel plus
-// its check-point stores.  The sweeps meet in global memory either way.
-struct GruGradPtrs {
-  const float* s0;       // [E,6]
-  const float* inputs;   // [E,N,H]
-  const float* x_t;      // [E] target position
-  const float* te;       // [E] target equilibrium
-  const float* h0;       // [E,2,32] or NULL = 0
-  float* S_out;          // [E,N] or NULL
-  float* grad;           // [E,N,H]
-  float* ckpt;           // [H][rows][GRU_CKPT_FLOATS]: after control step k, hidden tiles and fed-back outputs of every rollout
-  size_t rows;           // E N of this launch
-  uint32_t nb;           // blocks per env
-};
-constexpr size_t GRU_GRAD_REVERSE_LDS = ((size_t)GRU_IMAGE_FLOATS + GRU_T_IMAGE_FLOATS) * sizeof(float);   // 98 208 B: opt-in
-
-typedef float f4v __attribute__((ext_vector_type(4)));
-
-// A lane's 16 registers of a hidden tile <-> 16 consecutive floats of a check-point (4 x 16 bytes).
-__device__ __forceinline__ void gru_park_tile(float* dst, const f16v& h) {
-#pragma unroll
-  for (int q = 0; q < 4; ++q) reinterpret_cast<f4v*>(dst)[q] = f4v{h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]};
-}
-__device__ __forceinline__ f16v gru_fetch_tile(const float* src) {
-  f16v h;
-#pragma unroll
-  for (int q = 0; q < 4; ++q) {
-    const f4v t = reinterpret_cast<const f4v*>(src)[q];
-    h[4 * q] = t.x; h[4 * q + 1] = t.y; h[4 * q + 2] = t.z; h[4 * q + 3] = t.w;
-  }
-  return h;
-}
-
-// Forward sweep: gru_cost_only_kernel (same set-up, step and epilogue, in the handle's math mode) that parks, after every control
-// step but the last, what the reverse sweep starts from - the last step's cell produces a state that no stage costs.
+// Forward sweep of cpmppi_rollout_cost_grad_gru: gru_cost_only_kernel (same set-up, step and epilogue, in the handle's math mode) that
+// parks, after every control step but the last, what the reverse sweep (gru_grad_reverse_kernel, cpmppi_gru_adjoint.hip) starts from -
+// the last step's cell produces a state that no stage costs.  Two launches rather than one kernel that swaps its LDS image between the
+// sweeps: each keeps the cost-only kernel's shape, and the sweeps meet in global memory either way.
+// (A copy of the kernel above and not one body under `if constexpr`: behind two wrappers the hidden-state loads of the prologue
+// compile to other code, and the FAST cost-only launch measured 0.4 - 0.5 % slower at its three smallest shapes: profiles/HISTORY.md, r15.)
 template <int COST, bool F16>
 __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_grad_forward_kernel(const Params p, const GruGradPtrs a, const GruNorm nm,
                                                                                  const float* __restrict__ image) {
@@ -544,421 +311,67 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_grad_forward_kernel(
   if (a.S_out && owner) a.S_out[(size_t)env * p.N + n] = S_total;
 }
 
-// One GRU layer of the reverse sweep for the wave's 32 rollouts.  Recomputes the layer's gates (exact f32, the order of gru_layer)
-// from its input tile x (KX k-steps) and the hidden tile hp the step began with, then turns dh - in: the adjoint of the step's
-// new hidden state, out: the direct part z * dh of the adjoint of hp - into the adjoints of the four pre-activation tiles: r, z,
-// n's input part and n's hidden part.
-template <int KX>
-__device__ __forceinline__ void gru_layer_reverse(const float* lds, int fx, int fh, int b0, const f16v& x, const f16v& hp,
-                                                  uint32_t lane, f16v& dh, f16v& dar, f16v& daz, f16v& danx, f16v& danh) {
-  f16v ar = gru_mm<KX>(gru_bias_v(lds, b0 + 0, lane), lds + (fx + 0 * KX) * 64, x, lane);
-  f16v az = gru_mm<KX>(gru_bias_v(lds, b0 + 1, lane), lds + (fx + 1 * KX) * 64, x, lane);
-  const f16v anx = gru_mm<KX>(gru_bias_v(lds, b0 + 2, lane), lds + (fx + 2 * KX) * 64, x, lane);
-  ar = gru_mm<16>(ar, lds + (fh + 0) * 64, hp, lane);
-  az = gru_mm<16>(az, lds + (fh + 16) * 64, hp, lane);
-  const f16v anh = gru_mm<16>(gru_bias_v(lds, b0 + 3, lane), lds + (fh + 32) * 64, hp, lane);
-#pragma unroll
-  for (int v = 0; v < 16; ++v) {
-    const float r = gru_sigmoid(ar[v]);
-    const float z = gru_sigmoid(az[v]);
-    const float n = gru_tanh(__builtin_fmaf(r, anh[v], anx[v]));
-    const float d = dh[v];
-    const float dn = d * (1.0f - z);                          // h = (1 - z) n + z hp
-    const float dz = d * (hp[v] - n);
-    const float dan = dn * __builtin_fmaf(-n, n, 1.0f);       // n = tanh(anx + r anh)
-    danx[v] = dan;
-    danh[v] = dan * r;
-    dar[v] = (dan * anh[v]) * (r * (1.0f - r));
-    daz[v] = dz * (z * (1.0f - z));
-    dh[v] = d * z;
-  }
+// f(cost, f16) with the handle's cost plugin and math mode as compile-time constants (std::integral_constant).  FAST:
+// float32-equivalent split products on the f16 matrix cores (cpmppi_gru16.hpp); PRECISE: exact f32 MFMA chains.
+template <class F>
+void gru_dispatch(const cpmppi_handle* h, F&& f) {
+  const bool q = h->prm.cost_id == CPMPPI_COST_QBGM;
+  const std::integral_constant<int, COST_QBGM> Q;
+  const std::integral_constant<int, COST_DEFAULT> D;
+  if (h->cfg.math_mode == CPMPPI_MATH_FAST && h->gru16_image) q ? f(Q, std::true_type{}) : f(D, std::true_type{});
+  else q ? f(Q, std::false_type{}) : f(D, std::false_type{});
 }
 
-// Reverse sweep, exact-f32 MFMA in both math modes.  Per control step k = H-2 .. 0 (the cell of step H-1 feeds no cost), from the
-// check-points of steps k (outputs, layer-1 hidden tile) and k-1 (both hidden tiles, outputs = the input features; k = 0: the
-// env's memory and state): head adjoint, layer-2 cell, layer-1 cell, each layer's gates recomputed right before its adjoint.
-// Row 5 of the input adjoint is d/dQ[k]; rows 0..4 are the feedback into the outputs of step k-1, which also collect the
-// partials of stage k through the de-normalisation.  LDS: the forward f32 image (gates) and the transposed one.  A column
-// beyond N repeats the env's rollout 0 and is never written.
-template <int COST>
-__global__ __launch_bounds__(BLOCK, 1) void gru_grad_reverse_kernel(const Params p, const GruGradPtrs a, const GruNorm nm,
-                                                                    const float* __restrict__ image,
-                                                                    const float* __restrict__ image_t) {
-  extern __shared__ float lds[];                           // forward f32 image, then the transposed image
-  float* ldst = lds + GRU_IMAGE_FLOATS;
-  for (int i = threadIdx.x; i < GRU_T_IMAGE_FLOATS; i += BLOCK) ldst[i] = image_t[i];
-  gru_load_image(lds, image, GRU_IMAGE_FLOATS);            // the kernel's only barrier
-  const uint32_t env = blockIdx.x / a.nb, blk = blockIdx.x % a.nb;
-  const uint32_t tid = threadIdx.x, lane = tid & 63u, wave = tid >> 6, c = lane & 31u;
-  const uint32_t row0 = blk * GRU_ROLLOUTS_PER_BLOCK + wave * 32;
-  if (row0 >= p.N) return;                                 // (wave-uniform) a tile without a rollout
-  const uint32_t n = row0 + c;
-  const bool live = n < p.N, half1 = lane >= 32, owner = !half1 && live;
-  const uint32_t nn = live ? n : 0;
-  const uint32_t H = p.H;
-  const float x_t = a.x_t[env], te = a.te[env];
-  const float* __restrict__ s0 = a.s0 + (size_t)env * 6;
-  const float* __restrict__ in = a.inputs + ((size_t)env * p.N + nn) * H;
-  float* __restrict__ g = a.grad + ((size_t)env * p.N + nn) * H;
-  const size_t ck_step = a.rows * GRU_CKPT_FLOATS;
-  const uint32_t hoff = half1 ? 16u : 0u;                  // the lane's 16 slots inside a hidden tile
-  const float scale = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? 1.0f : 1.0f / (float)(p.H + 1);
-  const bool clip = p.control_mode == CPMPPI_CONTROL_CLIP;
-  auto stage_u = [&](float u) __attribute__((always_inline)) -> float {      // d stage / d u: the direct control term
-    if constexpr (COST == COST_QBGM) return stage_qbgm_grad(p, 0.0f, 1.0f, 0.0f, u, x_t, te).u;
-    else return stage_default_grad(p, 0.0f, 1.0f, u, x_t, te).u;
-  };
-  {                                                        // the last input: its cell is never costed
-    const float q = in[H - 1];
-    const bool clipped = clip && (q < p.lo || q > p.hi);
-    if (owner) g[H - 1] = clipped ? 0.0f : scale * stage_u(q);
-  }
-  if (H < 2) return;
-
-  f16v dh1, dh2;                                           // adjoints of the hidden tiles behind step k
-#pragma unroll
-  for (int v = 0; v < 16; ++v) { dh1[v] = 0.0f; dh2[v] = 0.0f; }
-  float dfb[4] = {0.0f, 0.0f, 0.0f, 0.0f};                 // feedback: adjoint of step k's outputs through the input tile of step k + 1
-  const float* ck = a.ckpt + ((size_t)env * p.N + nn) * GRU_CKPT_FLOATS + (size_t)(H - 2) * ck_step;   // check-point of step k
-  for (uint32_t k = H - 1; k-- > 0; ck -= ck_step) {
-    const float* ckp = ck - ck_step;                       // check-point of step k - 1 (k = 0: not read)
-    const float q = in[k];
-    const bool clipped = clip && (q < p.lo || q > p.hi);
-    const float ur = clip ? clamp_(q, p.lo, p.hi) : q;
-    // ---- outputs of step k = state of stage k + 1: its partials through the de-normalisation, plus the feedback
-    f16v gout;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) gout[v] = 0.0f;
-    {
-      const f4v o = *reinterpret_cast<const f4v*>(ck + 64);
-      const float w_ang = __builtin_fmaf(o.x, nm.out_scale[0], nm.out_shift[0]);
-      const float ca = __builtin_fmaf(o.y, nm.out_scale[1], nm.out_shift[1]);
-      const float sa = __builtin_fmaf(o.z, nm.out_scale[2], nm.out_shift[2]);
-      const float x = __builtin_fmaf(o.w, nm.out_scale[3], nm.out_shift[3]);
-      const float rr = __builtin_fmaf(ca, ca, sa * sa);
-      const float ir = rr > 0.0f ? __builtin_amdgcn_rsqf(rr) : 0.0f;
-      const float cosang = rr > 0.0f ? ca * ir : 1.0f;     // cos(atan2(s, c)) = c / |(c, s)|, differentiated through both
-      const float ir3 = ir * ir * ir;
-      StageGrad sg;
-      if constexpr (COST == COST_QBGM) sg = stage_qbgm_grad(p, x, cosang, w_ang, 0.0f, x_t, te);
-      else sg = stage_default_grad(p, x, cosang, 0.0f, x_t, te);
-      const float gc = scale * sg.cosang;
-      if (!half1) {
-        gout[0] = __builtin_fmaf(scale * sg.w, nm.out_scale[0], dfb[0]);
-        gout[1] = __builtin_fmaf(gc * (sa * sa * ir3), nm.out_scale[1], dfb[1]);
-        gout[2] = __builtin_fmaf(gc * (-(ca * sa) * ir3), nm.out_scale[2], dfb[2]);
-        gout[3] = __builtin_fmaf(scale * sg.x, nm.out_scale[3], dfb[3]);
-      } else {
-        gout[0] = dfb[0];                                  // positionD (row 4): no stage costs it
-      }
-    }
-    f16v dar, daz, danx, danh;
-    // ---- head adjoint, then the layer-2 cell: input = the layer-1 hidden tile of step k, hidden = layer 2's of step k - 1
-    {
-      const f16v h1 = gru_fetch_tile(ck + hoff);
-      const f16v h2p = k ? gru_fetch_tile(ckp + 32 + hoff) : gru_load_hidden(a.h0 ? a.h0 + (size_t)env * 64 + 32 : nullptr, lane);
-      dh2 = gru_mm<4>(dh2, ldst + GT_HEAD * 64, gout, lane);
-      gru_layer_reverse<16>(lds, GF_L2X, GF_L2H, 4, h1, h2p, lane, dh2, dar, daz, danx, danh);
-    }
-    dh1 = gru_mm<16>(dh1, ldst + (GT_L2X + 0) * 64, dar, lane);
-    dh1 = gru_mm<16>(dh1, ldst + (GT_L2X + 16) * 64, daz, lane);
-    dh1 = gru_mm<16>(dh1, ldst + (GT_L2X + 32) * 64, danx, lane);
-    dh2 = gru_mm<16>(dh2, ldst + (GT_L2H + 0) * 64, dar, lane);
-    dh2 = gru_mm<16>(dh2, ldst + (GT_L2H + 16) * 64, daz, lane);
-    dh2 = gru_mm<16>(dh2, ldst + (GT_L2H + 32) * 64, danh, lane);
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- the layer-1 cell: input = the step's feature tile, hidden = layer 1's of step k - 1
-    {
-      f16v xt;
-      if (k == 0) {
-        xt = gru_input_tile(nm, s0, ur, lane);
-      } else {
-#pragma unroll
-        for (int v = 0; v < 16; ++v) xt[v] = 0.0f;
-        if (!half1) {
-          const f4v o = *reinterpret_cast<const f4v*>(ckp + 64);
-          xt[0] = o.x; xt[1] = o.y; xt[2] = o.z; xt[3] = o.w;
-        } else {
-          xt[0] = ckp[68];
-          xt[1] = __builtin_fmaf(ur, nm.in_scale[0], nm.in_shift[0]);
-        }
-      }
-      const f16v h1p = k ? gru_fetch_tile(ckp + hoff) : gru_load_hidden(a.h0 ? a.h0 + (size_t)env * 64 : nullptr, lane);
-      gru_layer_reverse<4>(lds, GF_L1X, GF_L1H, 0, xt, h1p, lane, dh1, dar, daz, danx, danh);
-    }
-    // ---- the input adjoint (rows 0..4: feedback, row 5: d/dQ) and the hidden adjoint
-    f16v dx;
-#pragma unroll
-    for (int v = 0; v < 16; ++v) dx[v] = 0.0f;
-    dx = gru_mm<16>(dx, ldst + (GT_L1X + 0) * 64, dar, lane);
-    dx = gru_mm<16>(dx, ldst + (GT_L1X + 16) * 64, daz, lane);
-    dx = gru_mm<16>(dx, ldst + (GT_L1X + 32) * 64, danx, lane);
-    dh1 = gru_mm<16>(dh1, ldst + (GT_L1H + 0) * 64, dar, lane);
-    dh1 = gru_mm<16>(dh1, ldst + (GT_L1H + 16) * 64, daz, lane);
-    dh1 = gru_mm<16>(dh1, ldst + (GT_L1H + 32) * 64, danh, lane);
-    dfb[0] = dx[0]; dfb[1] = dx[1]; dfb[2] = dx[2]; dfb[3] = dx[3];          // (lane-half 1: [0] = row 4; [1..3] are not read)
-    const float dq = __shfl(dx[1], (int)(c + 32u), 64);                       // row 5 lives on the partner lane-half
-    if (owner) g[k] = clipped ? 0.0f : __builtin_fmaf(dq, nm.in_scale[0], scale * stage_u(ur));
-    __builtin_amdgcn_sched_barrier(0);
-  }
-}
-
-template <int COST>
-void launch_gru_grad(cpmppi_handle* h, const GruGradPtrs& a, uint32_t E, hipStream_t s) {
-  const bool f16 = gru_runs_f16(h);
-  const dim3 grid(E * a.nb);
-  if (f16) hipLaunchKernelGGL((gru_grad_forward_kernel<COST, true>), grid, dim3(BLOCK), (size_t)G16_IMAGE_BYTES, s, h->prm, a,
-                              h->gru_norm, (const float*)h->gru16_image);
-  else hipLaunchKernelGGL((gru_grad_forward_kernel<COST, false>), grid, dim3(BLOCK), (size_t)GRU_IMAGE_FLOATS * sizeof(float), s,
-                          h->prm, a, h->gru_norm, (const float*)h->gru_image);
-  hipLaunchKernelGGL((gru_grad_reverse_kernel<COST>), grid, dim3(BLOCK), GRU_GRAD_REVERSE_LDS, s, h->prm, a, h->gru_norm,
-                     (const float*)h->gru_image, (const float*)h->gru_t_image);
-}
-
-template <int COST, int NOISE>
-void launch_gru(cpmppi_handle* h, const cpmppi_step_args* a, const StepPtrs& p, hipStream_t s) {
-  const bool f16 = gru_runs_f16(h);
-  const size_t lds = ((f16 ? (size_t)G16_IMAGE_BYTES / 4 : (size_t)GRU_IMAGE_FLOATS) + (size_t)WAVES * p.W) * sizeof(float);
-  // (host code that no allowed H reaches: at H = CPMPPI_MAX_HORIZON = 1024 the images need 64 640 B (FAST) and 64 416 B (PRECISE))
-  if (lds > 64 * 1024) {   // long horizons with a perturbation buffer: weights image + [WAVES][H] sums
-    allow_large_lds(&gru_rollout_cost_kernel<COST, NOISE, true>);
-    allow_large_lds(&gru_rollout_cost_kernel<COST, NOISE, false>);
-  }
-  const dim3 grid(a->E * p.nb);
-  if (f16) hipLaunchKernelGGL((gru_rollout_cost_kernel<COST, NOISE, true>), grid, dim3(BLOCK), lds, s, h->prm, p,
-                              h->gru_norm, (const float*)h->gru16_image, a->h0);
-  else hipLaunchKernelGGL((gru_rollout_cost_kernel<COST, NOISE, false>), grid, dim3(BLOCK), lds, s, h->prm, p,
-                          h->gru_norm, (const float*)h->gru_image, a->h0);
+// One launch of a rollout kernel (Params, ptrs, GruNorm, image, tail...) on the weights image of its math mode, with `lds_extra`
+// bytes of dynamic LDS behind the image.
+template <bool F16, class Kernel, class Ptrs, class... Tail>
+void launch_gru_kernel(cpmppi_handle* h, Kernel kernel, uint32_t blocks, size_t lds_extra, hipStream_t s, const Ptrs& a, Tail... tail) {
+  hipLaunchKernelGGL(kernel, dim3(blocks), dim3(BLOCK), GRU_ROLLOUT_IMAGE_FLOATS<F16> * sizeof(float) + lds_extra, s, h->prm, a,
+                     h->gru_norm, (const float*)(F16 ? h->gru16_image : h->gru_image), tail...);
 }
 
 }  // namespace
 
-void launch_gru_brunton(cpmppi_handle* h, const BruntonArgs& a, hipStream_t s) {
-  const size_t waves = brunton_gru_rows((size_t)a.R * a.count);
-  hipLaunchKernelGGL(gru_brunton_kernel, dim3((unsigned)((waves + WAVES - 1) / WAVES)), dim3(BLOCK),
-                     (size_t)GRU_IMAGE_FLOATS * sizeof(float), s, h->gru_norm, (const float*)h->gru_image, a);
-}
-
 void launch_gru_rollout(cpmppi_handle* h, const cpmppi_step_args* a, const StepPtrs& p, hipStream_t s) {
-  const bool q = h->prm.cost_id == CPMPPI_COST_QBGM;
-  if (a->noise_kind == CPMPPI_NOISE_DELTA_U) { if (q) launch_gru<COST_QBGM, NOISE_DELTA_U>(h, a, p, s); else launch_gru<COST_DEFAULT, NOISE_DELTA_U>(h, a, p, s); }
-  else if (a->noise_kind == CPMPPI_NOISE_KNOTS) { if (q) launch_gru<COST_QBGM, NOISE_KNOTS>(h, a, p, s); else launch_gru<COST_DEFAULT, NOISE_KNOTS>(h, a, p, s); }
-  else { if (q) launch_gru<COST_QBGM, NOISE_PHILOX>(h, a, p, s); else launch_gru<COST_DEFAULT, NOISE_PHILOX>(h, a, p, s); }
+  const size_t sums = (size_t)WAVES * p.W * sizeof(float);   // [WAVES][W] weighted sums behind the image
+  gru_dispatch(h, [&](auto cost, auto f16) {
+    constexpr int COST = decltype(cost)::value; constexpr bool F16 = decltype(f16)::value;
+    auto launch = [&](auto kernel) {   // (the opt-in: host code that no allowed H reaches - H = 1024 needs 64 640 B (FAST), 64 416 B)
+      if (GRU_ROLLOUT_IMAGE_FLOATS<F16> * sizeof(float) + sums > 64 * 1024) allow_large_lds(kernel);
+      launch_gru_kernel<F16>(h, kernel, a->E * p.nb, sums, s, p, a->h0);
+    };
+    if (a->noise_kind == CPMPPI_NOISE_DELTA_U) launch(&gru_rollout_cost_kernel<COST, NOISE_DELTA_U, F16>);
+    else if (a->noise_kind == CPMPPI_NOISE_KNOTS) launch(&gru_rollout_cost_kernel<COST, NOISE_KNOTS, F16>);
+    else launch(&gru_rollout_cost_kernel<COST, NOISE_PHILOX, F16>);
+  });
 }
 
 extern "C" {
 
-int cpmppi_set_gru(cpmppi_handle* h, const cpmppi_gru_model* m) try {
-  if (!h) return CPMPPI_ERR_BAD_ARG;
-  if (!m || m->hidden != 32 || m->layers != 2 || m->inputs != 6 || m->outputs != 5)
-    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_gru: only GRU-6IN-32H1-32H2-5OUT is built");
-  for (int l = 0; l < 2; ++l)
-    if (!m->w_ih[l] || !m->w_hh[l] || !m->b_ih[l] || !m->b_hh[l]) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_gru: null weights");
-  if (!m->w_out || !m->b_out) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_gru: null head weights");
-  std::vector<float> img((size_t)GRU_IMAGE_FLOATS, 0.0f);
-  auto frag = [&](int f) { return img.data() + (size_t)f * 64; };
-  // x-tile row r -> network input column: rows 0..4 = the 5 state features (inputs 1..5), row 5 = Q (input 0)
-  auto xcol = [](int r) { return r < 5 ? r + 1 : (r == 5 ? 0 : -1); };
-  for (int g = 0; g < 3; ++g) {
-    for (int s = 0; s < 4; ++s)
-      for (int l = 0; l < 64; ++l) {
-        const int col = xcol(gru_tile_row(s, l >> 5));
-        frag(GF_L1X + g * 4 + s)[l] = col < 0 ? 0.0f : m->w_ih[0][(size_t)(g * 32 + (l & 31)) * 6 + col];
-      }
-    for (int s = 0; s < 16; ++s)
-      for (int l = 0; l < 64; ++l) {
-        const int k = gru_tile_row(s, l >> 5);
-        const size_t row = (size_t)(g * 32 + (l & 31));
-        frag(GF_L1H + g * 16 + s)[l] = m->w_hh[0][row * 32 + k];
-        frag(GF_L2X + g * 16 + s)[l] = m->w_ih[1][row * 32 + k];
-        frag(GF_L2H + g * 16 + s)[l] = m->w_hh[1][row * 32 + k];
-      }
-  }
-  for (int layer = 0; layer < 2; ++layer) {
-    const int fb = layer == 0 ? GF_L1B : GF_L2B;
-    for (int l = 0; l < 32; ++l) {                           // lane-half 0 carries the bias (k = 0), half 1 zeros
-      frag(fb + 0)[l] = m->b_ih[layer][l] + m->b_hh[layer][l];
-      frag(fb + 1)[l] = m->b_ih[layer][32 + l] + m->b_hh[layer][32 + l];
-      frag(fb + 2)[l] = m->b_ih[layer][64 + l];
-      frag(fb + 3)[l] = m->b_hh[layer][64 + l];
-    }
-  }
-  for (int s = 0; s < 16; ++s)
-    for (int l = 0; l < 64; ++l)
-      frag(GF_DW + s)[l] = (l & 31) < 5 ? m->w_out[(size_t)(l & 31) * 32 + gru_tile_row(s, l >> 5)] : 0.0f;
-  for (int l = 0; l < 5; ++l) frag(GF_DB)[l] = m->b_out[l];
-  // plain vectors of the fused rollout kernel (biases as accumulator tiles, dense head on the VALU)
-  for (int layer = 0; layer < 2; ++layer)
-    for (int hf = 0; hf < 2; ++hf)
-      for (int v = 0; v < 16; ++v) {
-        const int r = gru_tile_row(v, hf);
-        float* b = img.data() + GV_BIAS + (size_t)layer * 4 * 32 + hf * 16 + v;
-        b[0 * 32] = m->b_ih[layer][r] + m->b_hh[layer][r];
-        b[1 * 32] = m->b_ih[layer][32 + r] + m->b_hh[layer][32 + r];
-        b[2 * 32] = m->b_ih[layer][64 + r];
-        b[3 * 32] = m->b_hh[layer][64 + r];
-      }
-  for (int hf = 0; hf < 2; ++hf)
-    for (int o = 0; o < 5; ++o)
-      for (int v = 0; v < 16; ++v)
-        img[GV_HEAD + (size_t)hf * 80 + o * 16 + v] = m->w_out[(size_t)o * 32 + gru_tile_row(v, hf)];
-  for (int o = 0; o < 5; ++o) img[GV_HEADB + o] = m->b_out[o];
-  for (int i = 0; i < 6; ++i) {
-    h->gru_norm.in_scale[i] = m->in_scale ? m->in_scale[i] : 1.0f;
-    h->gru_norm.in_shift[i] = m->in_shift ? m->in_shift[i] : 0.0f;
-  }
-  for (int i = 0; i < 5; ++i) {
-    h->gru_norm.out_scale[i] = m->out_scale ? m->out_scale[i] : 1.0f;
-    h->gru_norm.out_shift[i] = m->out_shift ? m->out_shift[i] : 0.0f;
-  }
-  // ---- f16 split image (cpmppi_gru16.hpp): fragment f holds, for lane l and t = 0..7, the weight of output row l%32
-  // against k-slot (block b, lane half l/32, t) = tile register v = 8b + t of that half
-  std::vector<unsigned char> img16((size_t)G16_IMAGE_BYTES, 0);
-  bool in_range = true;
-  auto put16 = [&](int f, int lane, int t, float w) {
-    const _Float16 hi = (_Float16)w;
-    const _Float16 lo = (_Float16)(w - (float)hi);
-    if (!(fabsf(w) < 60000.0f)) in_range = false;
-    reinterpret_cast<_Float16*>(img16.data() + (size_t)f * G16_FRAG_BYTES + lane * 16)[t] = hi;
-    reinterpret_cast<_Float16*>(img16.data() + (size_t)(f + 1) * G16_FRAG_BYTES + lane * 16)[t] = lo;
-  };
-  // gate rows pre-scaled so that the gates need no multiply before v_exp_f32 (gru16_gates_overlapped): r, z by -log2(e), n by 2 log2(e)
-  const double LOG2E = 1.4426950408889634;
-  const double gate_scale[3] = {-LOG2E, -LOG2E, 2.0 * LOG2E};
-  auto sc = [&](int g, float w) { return (float)(gate_scale[g] * (double)w); };
-  for (int g = 0; g < 3; ++g)
-    for (int l = 0; l < 64; ++l)
-      for (int tt = 0; tt < 8; ++tt) {
-        const size_t row = (size_t)(g * 32 + (l & 31));
-        const int col = xcol(gru_tile_row(tt, l >> 5));                       // x tile registers 0..7
-        put16(HF_L1X + g * 2, l, tt, (col < 0 || tt >= 4) ? 0.0f : sc(g, m->w_ih[0][row * 6 + col]));
-        for (int b = 0; b < 2; ++b) {
-          const int k = gru_tile_row(8 * b + tt, l >> 5);
-          put16(HF_L1H + (g * 2 + b) * 2, l, tt, sc(g, m->w_hh[0][row * 32 + k]));
-          put16(HF_L2X + (g * 2 + b) * 2, l, tt, sc(g, m->w_ih[1][row * 32 + k]));
-          put16(HF_L2H + (g * 2 + b) * 2, l, tt, sc(g, m->w_hh[1][row * 32 + k]));
-        }
-      }
-  for (int b = 0; b < 2; ++b)
-    for (int l = 0; l < 64; ++l)
-      for (int tt = 0; tt < 8; ++tt)
-        put16(HF_HEAD + b * 2, l, tt, (l & 31) < 5 ? m->w_out[(size_t)(l & 31) * 32 + gru_tile_row(8 * b + tt, l >> 5)] : 0.0f);
-  if (!in_range) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_gru: weights beyond the f16 range");
-  {
-    float* bv = reinterpret_cast<float*>(img16.data() + G16_BIAS_OFF);
-    for (int i = 0; i < 8 * 32; ++i) {                                        // the same 8 gate-bias tiles, scaled alike
-      const int kind = (i / 32) % 4;                                          // r, z, n_x, n_h
-      bv[i] = (float)(gate_scale[kind < 2 ? kind : 2] * (double)img[GV_BIAS + i]);
-    }
-    for (int hf = 0; hf < 2; ++hf)
-      for (int v = 0; v < 16; ++v) {
-        const int r = gru_tile_row(v, hf);
-        bv[8 * 32 + hf * 16 + v] = r < 5 ? m->b_out[r] : 0.0f;
-      }
-  }
-  // ---- transposed image of the reverse sweep (cpmppi_gru.hpp, GT_*): fragment s of W^T holds W[unit(s, lane half)][lane % 32]
-  std::vector<float> imgt((size_t)GRU_T_IMAGE_FLOATS, 0.0f);
-  auto fragt = [&](int f) { return imgt.data() + (size_t)f * 64; };
-  for (int g = 0; g < 3; ++g)
-    for (int s = 0; s < 16; ++s)
-      for (int l = 0; l < 64; ++l) {
-        const size_t unit = (size_t)(g * 32 + gru_tile_row(s, l >> 5));
-        const int mrow = l & 31;
-        const int col = mrow < 8 ? xcol(mrow) : -1;
-        fragt(GT_L1X + g * 16 + s)[l] = col < 0 ? 0.0f : m->w_ih[0][unit * 6 + col];
-        fragt(GT_L1H + g * 16 + s)[l] = m->w_hh[0][unit * 32 + mrow];
-        fragt(GT_L2X + g * 16 + s)[l] = m->w_ih[1][unit * 32 + mrow];
-        fragt(GT_L2H + g * 16 + s)[l] = m->w_hh[1][unit * 32 + mrow];
-      }
-  for (int s = 0; s < 4; ++s)
-    for (int l = 0; l < 64; ++l) {
-      const int o = gru_tile_row(s, l >> 5);
-      fragt(GT_HEAD + s)[l] = o < 5 ? m->w_out[(size_t)o * 32 + (l & 31)] : 0.0f;
-    }
-  CPMPPI_ON_DEVICE(h);
-  if (!h->gru_image) CPMPPI_HIP(h, hipMalloc(&h->gru_image, img.size() * sizeof(float)));
-  CPMPPI_HIP(h, hipMemcpy(h->gru_image, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (!h->gru_t_image) CPMPPI_HIP(h, hipMalloc(&h->gru_t_image, imgt.size() * sizeof(float)));
-  CPMPPI_HIP(h, hipMemcpy(h->gru_t_image, imgt.data(), imgt.size() * sizeof(float), hipMemcpyHostToDevice));
-  allow_large_lds(&gru_grad_reverse_kernel<COST_QBGM>);      // both images in LDS: beyond the default 64 KB
-  allow_large_lds(&gru_grad_reverse_kernel<COST_DEFAULT>);
-  if (!h->gru16_image) CPMPPI_HIP(h, hipMalloc(&h->gru16_image, img16.size()));
-  CPMPPI_HIP(h, hipMemcpy(h->gru16_image, img16.data(), img16.size(), hipMemcpyHostToDevice));
-  return CPMPPI_OK;
-} catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }   // (no C++ exception leaves the C ABI)
-
-int cpmppi_gru_predict(cpmppi_handle* h, uint32_t B, uint32_t horizon, const float* s0, const float* Q, const float* h0,
-                       float* traj_out, float* h_out, void* stream) {
-  if (!h) return CPMPPI_ERR_BAD_ARG;
-  if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_predict: no model set (cpmppi_set_gru)");
-  if (horizon == 0) horizon = h->cfg.H;
-  if (B == 0 || !s0 || !Q || !traj_out) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_predict: bad argument");
-  CPMPPI_ON_DEVICE(h);
-  hipLaunchKernelGGL(gru_predict_kernel, dim3((B + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK), dim3(BLOCK),
-                     (size_t)GRU_IMAGE_FLOATS * sizeof(float), (hipStream_t)stream, h->gru_norm,
-                     (const float*)h->gru_image, B, horizon, s0, Q, h0, traj_out, h_out);
-  return launched(h);
-}
-
-int cpmppi_gru_advance(cpmppi_handle* h, uint32_t E, const float* s, const float* Q, float* h_io, void* stream) {
-  if (!h) return CPMPPI_ERR_BAD_ARG;
-  if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_advance: no model set (cpmppi_set_gru)");
-  if (E == 0 || E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_advance: E out of range");
-  if (!s || !Q || !h_io) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_advance: s, Q, h_io are required");
-  CPMPPI_ON_DEVICE(h);
-  // (one launch, nothing allocated, nothing awaited: the call can be captured)
-  hipLaunchKernelGGL(gru_advance_kernel, dim3((E + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK), dim3(BLOCK),
-                     (size_t)GRU_IMAGE_FLOATS * sizeof(float), (hipStream_t)stream, h->gru_norm, (const float*)h->gru_image, E, s,
-                     Q, h_io);
-  return launched(h);
-}
-
-int cpmppi_gru_washout(cpmppi_handle* h, uint32_t R, uint32_t T, const float* states, const float* Q, const float* h0,
-                       float* h_rows_out, void* stream) {
-  if (!h) return CPMPPI_ERR_BAD_ARG;
-  if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_washout: no model set (cpmppi_set_gru)");
-  if (R == 0 || T == 0) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_washout: R and T must be at least 1");
-  if (!states || !Q || !h_rows_out) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_washout: states, Q, h_rows_out are required");
-  if (misaligned(states) || misaligned(Q) || misaligned(h0) || misaligned(h_rows_out))
-    return fail(h, CPMPPI_ERR_ALIGN, "cpmppi_gru_washout: misaligned pointer");
-  CPMPPI_ON_DEVICE(h);
-  // (one launch, nothing allocated, nothing awaited: the call can be captured)
-  hipLaunchKernelGGL(gru_washout_kernel, dim3((R + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK), dim3(BLOCK),
-                     (size_t)GRU_IMAGE_FLOATS * sizeof(float), (hipStream_t)stream, h->gru_norm, (const float*)h->gru_image, R, T,
-                     states, Q, h0, h_rows_out);
-  return launched(h);
-}
-
 int cpmppi_rollout_cost_gru(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs, const float* target_position,
                             const float* target_equilibrium, const float* h0, float* S_out, void* stream) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
-  if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_gru: no model set (cpmppi_set_gru)");
-  if (E == 0 || E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost_gru: E out of range");
-  if (!s0 || !inputs || !target_position || !target_equilibrium || !S_out)
-    return fail(h, CPMPPI_ERR_BAD_ARG,
-                "cpmppi_rollout_cost_gru: s0, inputs, target_position, target_equilibrium, S_out are required");
-  if ((h->prm.cost_id != CPMPPI_COST_QBGM && h->prm.cost_id != CPMPPI_COST_DEFAULT) || h->prm.qb_mode != 0u)
-    return fail(h, CPMPPI_ERR_BAD_ARG,
-                "cpmppi_rollout_cost_gru: the GRU predictor supports quadratic_boundary_grad_minimal and default");
+  if (const int rc = gru_refusal(h, "cpmppi_rollout_cost_gru", E != 0 && E <= h->cfg.E, "E out of range",
+                                 s0 && inputs && target_position && target_equilibrium && S_out,
+                                 "s0, inputs, target_position, target_equilibrium, S_out are required", true)) return rc;
   CPMPPI_ON_DEVICE(h);
   // (one launch, nothing allocated, nothing awaited: the call can be captured; no pole mass and no L - the network is the plant model)
-  const GruCostPtrs a{s0, inputs, target_position, target_equilibrium, h0, S_out,
+  const GruCostPtrs a{{s0, inputs, target_position, target_equilibrium, h0, S_out},
                       (h->cfg.N + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK};
-  if (h->prm.cost_id == CPMPPI_COST_QBGM) launch_gru_cost_only<COST_QBGM>(h, a, E, (hipStream_t)stream);
-  else launch_gru_cost_only<COST_DEFAULT>(h, a, E, (hipStream_t)stream);
+  gru_dispatch(h, [&](auto cost, auto f16) {
+    launch_gru_kernel<f16.value>(h, &gru_cost_only_kernel<cost.value, f16.value>, E * a.nb, 0, (hipStream_t)stream, a);
+  });
   return launched(h);
 }
 
+// cost and gradient: gru_grad_forward_kernel, then gru_grad_reverse_kernel (cpmppi_gru_adjoint.hip), on one stream
 int cpmppi_rollout_cost_grad_gru(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs, const float* target_position,
                                  const float* target_equilibrium, const float* h0, float* S_out, float* grad_out, void* stream) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
   const char* who = "cpmppi_rollout_cost_grad_gru";
-  if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": no model set (cpmppi_set_gru)");
-  if (E == 0 || E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": E out of range");
-  if (!s0 || !inputs || !target_position || !target_equilibrium || !grad_out)
-    return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": s0, inputs, target_position, target_equilibrium, grad_out are required");
-  if ((h->prm.cost_id != CPMPPI_COST_QBGM && h->prm.cost_id != CPMPPI_COST_DEFAULT) || h->prm.qb_mode != 0u)
-    return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": the GRU predictor supports quadratic_boundary_grad_minimal and default");
+  if (const int rc = gru_refusal(h, who, E != 0 && E <= h->cfg.E, "E out of range",
+                                 s0 && inputs && target_position && target_equilibrium && grad_out,
+                                 "s0, inputs, target_position, target_equilibrium, grad_out are required", true)) return rc;
   CPMPPI_ON_DEVICE(h);
   // check-points of the handle's largest launch; allocated on first use, never inside a capture
   const size_t need = (size_t)h->cfg.H * GRU_CKPT_FLOATS * (size_t)h->cfg.E * h->cfg.N;
@@ -966,10 +379,11 @@ int cpmppi_rollout_cost_grad_gru(cpmppi_handle* h, uint32_t E, const float* s0, 
     if (const int rc = refuse_unreserved_capture(h, (hipStream_t)stream, who, "cpmppi_rollout_cost_grad_gru once")) return rc;
     if (const int rc = grow_workspace(h, h->gru_grad_ws, h->gru_grad_ws_floats, need)) return rc;
   }
-  const GruGradPtrs a{s0, inputs, target_position, target_equilibrium, h0, S_out, grad_out, h->gru_grad_ws, (size_t)E * h->cfg.N,
-                      (h->cfg.N + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK};
-  if (h->prm.cost_id == CPMPPI_COST_QBGM) launch_gru_grad<COST_QBGM>(h, a, E, (hipStream_t)stream);
-  else launch_gru_grad<COST_DEFAULT>(h, a, E, (hipStream_t)stream);
+  const GruGradPtrs a = gru_grad_ptrs(h, E, s0, inputs, target_position, target_equilibrium, h0, S_out, grad_out);
+  gru_dispatch(h, [&](auto cost, auto f16) {
+    launch_gru_kernel<f16.value>(h, &gru_grad_forward_kernel<cost.value, f16.value>, E * a.nb, 0, (hipStream_t)stream, a);
+  });
+  launch_gru_grad_reverse(h, E, s0, inputs, target_position, target_equilibrium, h0, grad_out, (hipStream_t)stream);
   return launched(h);
 }
 

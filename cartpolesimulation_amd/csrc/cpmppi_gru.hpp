@@ -19,6 +19,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "cpmppi_device.hpp"     // (GruNorm)
+#include "cpmppi_internal.hpp"   // (the handle, BLOCK: what the GRU units share, at the end)
 
 namespace cpmppi {
 
@@ -74,9 +75,7 @@ __device__ __forceinline__ f16v gru_mm(f16v acc, const float* __restrict__ frag,
 }
 
 __device__ __forceinline__ f16v gru_bias(const float* __restrict__ frag, uint32_t lane) {
-  f16v z;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) z[v] = 0.0f;
+  const f16v z = 0.0f;
   return __builtin_amdgcn_mfma_f32_32x32x2f32(frag[lane], 1.0f, z, 0, 0, 0);
 }
 
@@ -127,7 +126,6 @@ __device__ __forceinline__ f16v gru_step(const float* __restrict__ lds, const f1
 // gru_step only in that the hidden products enter an accumulator before the input products.
 // development aid (-DCPMPPI_GRU_STAMPS): s_memtime at the phase boundaries of a step, summed per wave
 #ifdef CPMPPI_GRU_STAMPS
-__device__ unsigned long long g_gru_stamp_sum[8];
 #define GRU_STAMP(i)                                                                   \
   do {                                                                                 \
     __builtin_amdgcn_sched_barrier(0);                                                 \
@@ -144,17 +142,26 @@ struct GruCarry {
   f16v ar, az, anh;      // layer-1 pre-activations so far: bias + W_hh1 h1 for the coming step
 };
 
-// bias vector b (0..7) as an accumulator tile: acc[v] = bias[row(v, lane half)]
-__device__ __forceinline__ f16v gru_bias_v(const float* __restrict__ lds, int b, uint32_t lane) {
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  const f4* __restrict__ src = reinterpret_cast<const f4*>(lds + GV_BIAS + b * 32 + (lane >> 5) * 16);
-  f16v z;
+typedef float f4v __attribute__((ext_vector_type(4)));
+
+// A lane's 16 registers of a tile <-> 16 consecutive floats (4 x 16 bytes): a check-point in global memory, a bias vector in LDS.
+__device__ __forceinline__ void gru_park_tile(float* dst, const f16v& h) {
+#pragma unroll
+  for (int q = 0; q < 4; ++q) reinterpret_cast<f4v*>(dst)[q] = f4v{h[4 * q], h[4 * q + 1], h[4 * q + 2], h[4 * q + 3]};
+}
+__device__ __forceinline__ f16v gru_fetch_tile(const float* src) {
+  f16v h;
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
-    const f4 t = src[q];
-    z[4 * q + 0] = t.x; z[4 * q + 1] = t.y; z[4 * q + 2] = t.z; z[4 * q + 3] = t.w;
+    const f4v t = reinterpret_cast<const f4v*>(src)[q];
+    h[4 * q] = t.x; h[4 * q + 1] = t.y; h[4 * q + 2] = t.z; h[4 * q + 3] = t.w;
   }
-  return z;
+  return h;
+}
+
+// bias vector b (0..7) as an accumulator tile: acc[v] = bias[row(v, lane half)]
+__device__ __forceinline__ f16v gru_bias_v(const float* __restrict__ lds, int b, uint32_t lane) {
+  return gru_fetch_tile(lds + GV_BIAS + b * 32 + (lane >> 5) * 16);
 }
 
 // dense head on the VALU: every lane sums its 16 rows, the two halves are added across lanes; out[0..4] on ALL lanes
@@ -186,21 +193,13 @@ __device__ __forceinline__ void gru_gates_overlapped(const f16v& ar, const f16v&
   for (int v = 0; v < 16; ++v) {
     float n0 = 0.0f, n1 = 0.0f, n2 = 0.0f;
     if (v + 1 < 16) { n0 = f[(v + 1) * 64]; n1 = f[(16 + v + 1) * 64]; n2 = f[(32 + v + 1) * 64]; }
-#ifndef GRU_EXP_NOMFMA
     pr = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, X[v], pr, 0, 0, 0);
     pz = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, X[v], pz, 0, 0, 0);
     pn = __builtin_amdgcn_mfma_f32_32x32x2f32(a2, X[v], pn, 0, 0, 0);
-#else
-    pr[v] += a0; pz[v] += a1; pn[v] += a2;
-#endif
-#ifndef GRU_EXP_NOGATES
     const float r = gru_sigmoid(ar[v]);
     const float z = gru_sigmoid(az[v]);
     const float n = gru_tanh(__builtin_fmaf(r, anh[v], anx[v]));
     h[v] = __builtin_fmaf(z, h[v] - n, n);                    // (1-z)*n + z*h
-#else
-    h[v] = __builtin_fmaf(ar[v], az[v], anx[v] + anh[v]) * 1e-3f;
-#endif
     a0 = n0; a1 = n1; a2 = n2;
     __builtin_amdgcn_sched_barrier(0);
   }
@@ -260,9 +259,7 @@ __device__ __forceinline__ f16v gru_load_hidden(const float* __restrict__ hsrc, 
 
 // Feature tile of step 0 from a state (angle, angleD, cos, sin, position, positionD) and the first control.
 __device__ __forceinline__ f16v gru_input_tile(const GruNorm& nm, const float* __restrict__ s, float Q, uint32_t lane) {
-  f16v x;
-#pragma unroll
-  for (int v = 0; v < 16; ++v) x[v] = 0.0f;
+  f16v x = 0.0f;
   if ((lane >> 5) == 0) {
     x[0] = __builtin_fmaf(s[1], nm.in_scale[1], nm.in_shift[1]);      // angleD
     x[1] = __builtin_fmaf(s[2], nm.in_scale[2], nm.in_shift[2]);      // angle_cos
@@ -288,3 +285,51 @@ __device__ __forceinline__ void gru_output_state(const GruNorm& nm, const f16v& 
 }
 
 }  // namespace cpmppi
+
+// ---- what more than one GRU unit needs (cpmppi_gru.hip, cpmppi_gru_seam.hip, cpmppi_gru_adjoint.hip) ------------------------------
+// What the entry points refuse before they launch, in this order: no model, a size out of range, a required pointer missing and,
+// where the entry point costs the rollouts, a cost plugin the GRU kernels are not built for.
+inline int gru_refusal(cpmppi_handle* h, const char* who, bool size_ok, const char* size_msg, bool ptrs_ok, const char* ptrs_msg,
+                       bool costs = false) {
+  const std::string w = std::string(who) + ": ";
+  if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, w + "no model set (cpmppi_set_gru)");
+  if (!size_ok) return fail(h, CPMPPI_ERR_BAD_ARG, w + size_msg);
+  if (!ptrs_ok) return fail(h, CPMPPI_ERR_BAD_ARG, w + ptrs_msg);
+  if (costs && ((h->prm.cost_id != CPMPPI_COST_QBGM && h->prm.cost_id != CPMPPI_COST_DEFAULT) || h->prm.qb_mode != 0u))
+    return fail(h, CPMPPI_ERR_BAD_ARG, w + "the GRU predictor supports quadratic_boundary_grad_minimal and default");
+  return CPMPPI_OK;
+}
+
+// The device side, in an anonymous namespace as the kernels of every unit are: a kernel's symbol names the types of its arguments.
+namespace {
+using cpmppi::f16v;
+
+__device__ __forceinline__ void gru_load_image(float* __restrict__ lds, const float* __restrict__ image, int floats) {
+  for (int i = threadIdx.x; i < floats; i += cpmppi_k::BLOCK) lds[i] = image[i];
+  __syncthreads();
+}
+
+// The pointer block of the launches that cost GIVEN plans, and what the cost-only kernels and the two sweeps of the gradient
+// (gru_grad_forward_kernel, cpmppi_gru.hip, then gru_grad_reverse_kernel, cpmppi_gru_adjoint.hip: gru_grad_ptrs in each) add to it.
+struct GruPlanPtrs {
+  const float* s0;       // [E,6]
+  const float* inputs;   // [E,N,H]
+  const float* x_t;      // [E] target position
+  const float* te;       // [E] target equilibrium
+  const float* h0;       // [E,2,32] or NULL = 0
+  float* S_out;          // [E,N] (gradient launches: or NULL)
+};
+struct GruCostPtrs : GruPlanPtrs { uint32_t nb; };   // blocks per env
+struct GruGradPtrs : GruPlanPtrs {
+  float* grad;           // [E,N,H]
+  float* ckpt;           // [H][rows][GRU_CKPT_FLOATS]: after control step k, hidden tiles and fed-back outputs of every rollout
+  size_t rows;           // E N of this launch
+  uint32_t nb;           // blocks per env
+};
+inline GruGradPtrs gru_grad_ptrs(const cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs, const float* x_t,
+                                 const float* te, const float* h0, float* S_out, float* grad) {
+  return GruGradPtrs{{s0, inputs, x_t, te, h0, S_out}, grad, h->gru_grad_ws, (size_t)E * h->cfg.N,
+                     (h->cfg.N + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK};
+}
+
+}  // namespace

@@ -6,7 +6,10 @@
 //   cpmppi_seams.hip      sampler, tiling, predictor, trajectory cost and reward-weighted-average seams
 //   cpmppi_plant.hip      the simulated plant (cpmppi_plant_*)
 //   cpmppi_optim.hip      cost-only rollouts, the adjoint, Adam / SGD steps and CEM
-//   cpmppi_gru.hip        the GRU predictor (model upload, its seam, its fused rollout launch)
+//   cpmppi_gru.hip        the GRU predictor in the optimizers: the fused MPPI step, cost-only rollouts, the gradient's forward sweep
+//   cpmppi_gru_seam.hip   its exact-cell seams: predict, advance, washout, the Brunton test's kernel
+//   cpmppi_gru_adjoint.hip  the gradient's reverse sweep
+//   cpmppi_gru_model.hip  host code only: cpmppi_set_gru packs and uploads the three weight images
 //   cpmppi_comm.hip, cpmppi_groups.hip, cpmppi_io.hip   host code only: the collective, env groups, the recording writer
 //   cpmppi_rollout_*.hip  the instances of rollout_cost_kernel, each unit with its own compiler flags
 // Kernels stay in an anonymous namespace of the unit that launches them; units call each other through host functions only.
@@ -182,7 +185,12 @@ int launch_rollout(cpmppi_handle* h, const cpmppi::Params& prm, const cpmppi_pla
 int check_plant(cpmppi_handle* h, const cpmppi_plant_args* a);
 // cpmppi_gru.hip: the fused GRU rollout kernel of a step (p.nb counted in GRU blocks); the caller checks the launch
 void launch_gru_rollout(cpmppi_handle* h, const cpmppi_step_args* a, const cpmppi_k::StepPtrs& p, hipStream_t s);
-// cpmppi_gru.hip: the Brunton test's GRU kernel (one partial row per wave of 32 starts: brunton_gru_rows of them); the caller
+// cpmppi_gru_adjoint.hip: the reverse sweep of cpmppi_rollout_cost_grad_gru behind its forward sweep (cpmppi_gru.hip), whose
+// arguments these are and whose check-points, in the handle's workspace, it reads; and the LDS opt-in of its kernels (cpmppi_set_gru)
+void launch_gru_grad_reverse(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs, const float* x_t, const float* te,
+                             const float* h0, float* grad, hipStream_t s);
+void allow_large_lds_gru_adjoint();
+// cpmppi_gru_seam.hip: the Brunton test's GRU kernel (one partial row per wave of 32 starts: brunton_gru_rows of them); the caller
 // has checked the arguments, checks the launch and reduces the partial rows
 inline size_t brunton_gru_rows(size_t starts) { return (starts + 31) / 32; }
 void launch_gru_brunton(cpmppi_handle* h, const cpmppi::BruntonArgs& a, hipStream_t s);

@@ -9,7 +9,7 @@
 //   predict_kernel<FAST, STAGED, INTEG>   predictor seam: trajectories [B,H+1,6] (stores staged through LDS for large launches).
 //   brunton_kernel<FAST, INTEG>           Brunton test (cpmppi_brunton): every start row of the recordings rolled forward on the recorded
 //                                         controls with predict_kernel's control step; per-workgroup error statistics per horizon step.
-//   brunton_finalize_kernel               the partial statistics of the ODE or the GRU kernel (cpmppi_gru.hip) reduced in float64.
+//   brunton_finalize_kernel               the partial statistics of the ODE or the GRU kernel (cpmppi_gru_seam.hip) reduced in float64.
 //   trajectory_cost_kernel                cost seam on materialised trajectories.
 //   rwa_kernel                            a16 on given (S, delta_u).
 #include <hip/hip_runtime.h>

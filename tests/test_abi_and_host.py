@@ -235,6 +235,23 @@ def test_rollout_kernels_have_no_scratch_and_no_vgpr_spills():
             assert k["vgpr_count"] + k["agpr_count"] <= 128, (k["name"], k["vgpr_count"])
 
 
+def test_the_built_library_compared_with_itself_by_name_has_no_difference(capsys):
+    """tools/code_objects.py --diff --by-name, how a change that moves kernels between translation units is checked: every kernel
+    of kernels() is found by name with a code range of its own, and a library does not differ from itself."""
+    sys.path.insert(0, os.path.join(ROOT, "tools"))
+    import code_objects
+    if not os.path.exists(os.path.join(code_objects.LLVM_BIN, "llvm-readelf")):
+        pytest.skip("no llvm-readelf")
+    from cartpolesimulation_amd import _lib
+    listed = code_objects.kernels(_lib.LIB_PATH)
+    code = code_objects.kernel_code(_lib.LIB_PATH)
+    assert len(code) == len(listed) == len(code_objects.kernels_by_name(_lib.LIB_PATH)) > 0
+    assert all(len(c) > 0 for c in code.values())
+    assert code_objects.diff_by_name(_lib.LIB_PATH, _lib.LIB_PATH) == 0
+    n = len(listed)
+    assert f"kernels by name: {n} / {n}, {n} identical; no difference" in capsys.readouterr().out
+
+
 def test_the_stand_in_collective_library_exports_what_the_communicator_binds():
     """tests/fake_rccl/libfake_rccl.so (test infrastructure for the two-process GPU tests) exports exactly the symbols
     csrc/cpmppi_comm.hip looks up with dlsym, and draws ids only it accepts - no GPU call here."""

@@ -5,6 +5,10 @@
   python tools/code_objects.py [path/to/libcpmppi.so] [name-substring]
   python tools/code_objects.py --diff a.so b.so     same device code?  one line per code object for its .text bytes, every
                                                     difference of the kernels() tables; exit status 1 on any difference
+  python tools/code_objects.py --diff --by-name a.so b.so   the same question kernel by kernel, whatever unit a kernel sits in
+                                                    (after a unit was split or merged): the bytes of every kernel symbol's own
+                                                    code and its table without `unit`, the kernels only one side has; also what
+                                                    --diff does by itself when the two libraries differ in their number of units
 
 `kernels(path)` -> list of dicts {name, vgpr_count, agpr_count, sgpr_count, sgpr_spill_count, vgpr_spill_count,
 private_segment_fixed_size (scratch bytes per lane), group_segment_fixed_size (static LDS), unit (index of the code object)}.
@@ -96,8 +100,71 @@ def diff(so_a, so_b, sections=(".text",)):
     return bad
 
 
+def kernel_code(so_path):
+    """{(kernel name, occurrence): the bytes of the kernel symbol's own range in .text}.  Units that instantiate the same template
+    in an anonymous namespace hold kernels of one name: they are numbered in unit order, as kernels_by_name numbers them."""
+    res, seen = {}, {}
+    for elf in code_objects(so_path):
+        with tempfile.NamedTemporaryFile(suffix=".elf") as f:
+            f.write(elf)
+            f.flush()
+            txt = subprocess.run([os.path.join(LLVM_BIN, "llvm-readelf"), "-S", "-s", "-W", f.name], check=True,
+                                 capture_output=True, text=True).stdout
+        m = re.search(r"\] \.text\s+PROGBITS\s+([0-9a-f]+) ([0-9a-f]+) ([0-9a-f]+)", txt)
+        if not m:
+            continue
+        addr, off, size = (int(x, 16) for x in m.groups())
+        kds = set(re.findall(r"\s(\S+)\.kd$", txt, re.M))
+        funcs = {}                          # (.dynsym and .symtab list a kernel twice)
+        for value, n, name in re.findall(r"^\s*\d+: ([0-9a-f]+)\s+(\d+) FUNC\s+\S+\s+\S+\s+\d+ (\S+)$", txt, re.M):
+            if name in kds:
+                funcs[name] = (int(value, 16), int(n))
+        for name, (value, n) in sorted(funcs.items(), key=lambda kv: kv[1]):
+            assert addr <= value and value + n <= addr + size, name
+            i = seen[name] = seen.get(name, -1) + 1
+            res[(name, i)] = elf[off + value - addr:off + value - addr + n]
+    return res
+
+
+def kernels_by_name(so_path):
+    """kernels() keyed by (name, occurrence in unit order), without the `unit` field."""
+    res, seen = {}, {}
+    for k in kernels(so_path):
+        i = seen[k["name"]] = seen.get(k["name"], -1) + 1
+        res[(k["name"], i)] = {key: v for key, v in k.items() if key != "unit"}
+    return res
+
+
+def diff_by_name(so_a, so_b):
+    """Compare two libraries kernel by kernel, whichever code object holds a kernel; the number of differences."""
+    ca, cb, ka, kb = kernel_code(so_a), kernel_code(so_b), kernels_by_name(so_a), kernels_by_name(so_b)
+    bad = same = 0
+    ta, tb = ([section(e) for e in code_objects(so)] for so in (so_a, so_b))
+    print(f"code objects: {len(ta)} / {len(tb)}; .text of {sum(t in tb for t in ta)} of the first's found byte for byte in the second")
+    for key in sorted(set(ka) | set(kb)):
+        tag = key[0] + (f" #{key[1]}" if key[1] else "")
+        if key not in ka or key not in kb:
+            bad += 1
+            print(f"{tag}: only in {'the first' if key in ka else 'the second'}")
+        elif ca.get(key) is None or cb.get(key) is None:
+            bad += 1
+            print(f"{tag}: no function symbol")
+        elif ca[key] != cb[key] or ka[key] != kb[key]:
+            bad += 1
+            print(f"{tag}: code {'identical' if ca[key] == cb[key] else 'DIFFERENT'} ({len(ca[key])} / {len(cb[key])} bytes)"
+                  + ("" if ka[key] == kb[key] else f"; {ka[key]} / {kb[key]}"))
+        else:
+            same += 1
+    print(f"kernels by name: {len(ka)} / {len(kb)}, {same} identical; {'no difference' if not bad else str(bad) + ' differences'}")
+    return bad
+
+
 if __name__ == "__main__":
+    if len(sys.argv) == 5 and sys.argv[1:3] == ["--diff", "--by-name"]:
+        sys.exit(1 if diff_by_name(sys.argv[3], sys.argv[4]) else 0)
     if len(sys.argv) == 4 and sys.argv[1] == "--diff":
+        if len(code_objects(sys.argv[2])) != len(code_objects(sys.argv[3])):
+            sys.exit(1 if diff_by_name(sys.argv[2], sys.argv[3]) else 0)
         sys.exit(1 if diff(sys.argv[2], sys.argv[3]) else 0)
     path = sys.argv[1] if len(sys.argv) > 1 and sys.argv[1] else os.path.join(ROOT, "cartpolesimulation_amd", "libcpmppi.so")
     flt = sys.argv[2] if len(sys.argv) > 2 else ""
