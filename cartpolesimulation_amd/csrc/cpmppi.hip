@@ -27,11 +27,16 @@
 #include "cpmppi.h"
 #include "cpmppi_internal.hpp"
 #include "cpmppi_launch_plan.hpp"
+#include "cpmppi_cost.hpp"          // (EnvFold and its makers: fold_env_kernel)
+// the rollout kernels are launched here and defined elsewhere: this unit sees their declarations and the instance lists, not
+// the definition (cpmppi_rollout.hpp)
+#define CPMPPI_ROLLOUT_DECLARATIONS_ONLY
+#include "cpmppi_rollout.hpp"
 
 using namespace cpmppi_k;
 
-// rollout_cost_kernel is instantiated in the cpmppi_rollout_*.hip units, each with its own compiler flags; nothing of it may
-// be instantiated here
+// rollout_cost_kernel is instantiated in the cpmppi_rollout_*.hip units, each with its own compiler flags; nothing of it can
+// be instantiated here (no definition in sight), and every instantiation the lookup below names is declared extern
 namespace cpmppi_k {
 CPMPPI_LATENCY_INSTANCES(CPMPPI_DECLARE_ROLLOUT)
 CPMPPI_LATENCY_BUFFER_INSTANCES(CPMPPI_DECLARE_ROLLOUT)
@@ -104,7 +109,7 @@ void fill_params(const cpmppi_config& c, Params& p) {
   p.interp_f32 = (c.math_mode == CPMPPI_MATH_FAST) ? 1u : 0u;
 }
 
-// Per-env constants of the throughput build (EnvFold, cpmppi_device.hpp): one lane per env, the very device functions the
+// Per-env constants of the throughput build (EnvFold, cpmppi_cost.hpp): one lane per env, the very device functions the
 // other builds call in their prologues.  Runs in front of every throughput-build launch on the same stream (L, the targets and
 // s0 are the caller's device arrays and may change between any two steps): ~2 us against launches of a millisecond and more.
 __global__ __launch_bounds__(BLOCK) void fold_env_kernel(const Params p, const float* __restrict__ L, const float* __restrict__ te,

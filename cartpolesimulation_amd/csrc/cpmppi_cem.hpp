@@ -3,6 +3,7 @@
 // adjoint_sweep (cpmppi_grad.hpp).  The row lives in a workspace column of the env (lane-contiguous, the block's width as the
 // stride), as the check-points and the gradient of the sweep do.
 #pragma once
+#include "cpmppi_philox.hpp"
 #include "cpmppi_rpgd.hpp"
 
 namespace cpmppi {

@@ -147,7 +147,7 @@ struct CommState {
 
 // Fallback waiter (no stream memory operations), side stream, one lane: posts "gathers completed = post" (the all-gather in
 // front of it on the stream has finished) and then holds the stream until the rollout kernel's last finalizing block has
-// published step `need` (finalize_env, cpmppi_rollout.hpp).  A wait that gives up raises the error for device and host; the
+// published step `need` (finalize_env, cpmppi_step.hpp).  A wait that gives up raises the error for device and host; the
 // all-gather behind it then sends whatever the buffer holds - the error tells every consumer not to use it.
 // (`other`: the second flag block of a communicator shared by env groups, or NULL - completions go to both, the step `need` is
 // published in the block of its parity, an error is raised in both.  `stamp`: cpmppi_comm_set_stamped - what stamp_kernel does,
@@ -225,7 +225,7 @@ __global__ void delay_kernel(unsigned long long ticks) {
   while (__builtin_amdgcn_s_memrealtime() - t0 < ticks) __builtin_amdgcn_s_sleep(64);
 }
 
-// words [4..11] of the flag block: what only the kernels' slow paths read (GatherSync in cpmppi_rollout.hpp) - the signal
+// words [4..11] of the flag block: what only the kernels' slow paths read (GatherSync in cpmppi_step.hpp) - the signal
 // memory's address (0 = fallback waiter), the pinned error word's address, the timeout in 100 MHz ticks, and the OTHER block's
 // address (env groups: a finalize whose wait gives up raises the error in both blocks, as every other writer of it does; 0 = one block)
 constexpr int FLAG_WORDS = 16;

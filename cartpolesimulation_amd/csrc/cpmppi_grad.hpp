@@ -13,7 +13,10 @@
 // taken (edge bounce), derivative 1 through fmod / the wrap comparisons, 0 through indicator functions and through a
 // clipped control.
 #pragma once
-#include "cpmppi_device.hpp"
+#include "cpmppi.h"
+#include "cpmppi_params.hpp"
+#include "cpmppi_ode.hpp"
+#include "cpmppi_cost.hpp"
 
 namespace cpmppi {
 

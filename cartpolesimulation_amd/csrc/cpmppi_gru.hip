@@ -11,6 +11,9 @@
 // comes from and in what becomes of the costs.  Entry points: cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru;
 // -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write g_gru_stamp_sum are this unit's).
 #include <type_traits>
+#include "cpmppi_cost.hpp"
+#include "cpmppi_philox.hpp"
+#include "cpmppi_wave.hpp"
 #include "cpmppi_gru16.hpp"      // (and cpmppi_gru.hpp, cpmppi_internal.hpp)
 
 using namespace cpmppi_k;

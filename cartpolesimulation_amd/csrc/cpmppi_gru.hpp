@@ -18,8 +18,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
-#include "cpmppi_device.hpp"     // (GruNorm)
-#include "cpmppi_internal.hpp"   // (the handle, BLOCK: what the GRU units share, at the end)
+#include "cpmppi_internal.hpp"   // (GruNorm; the handle, BLOCK: what the GRU units share, at the end)
 
 namespace cpmppi {
 

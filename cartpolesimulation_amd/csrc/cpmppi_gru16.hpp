@@ -17,6 +17,7 @@
 // product's B operand by conversion alone — registers 0..7 feed block 0, registers 8..15 block 1, no data movement.
 // (operand layout checked on the device by tools/dev/mfma16_layout.hip)
 #pragma once
+#include "cpmppi_params.hpp"     // (f2 and its arithmetic helpers)
 #include "cpmppi_gru.hpp"
 
 namespace cpmppi {

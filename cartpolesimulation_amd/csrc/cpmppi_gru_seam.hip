@@ -9,6 +9,7 @@
 // stores: one loop with a per-step sink, gru_store_memory in all three and one tile set-up were measured and not kept - each moved
 // the code of kernels it did not touch, and cpmppi_gru_advance went from 12.4 to 14.5 us (profiles/HISTORY.md, r15).
 // Entry points: cpmppi_gru_predict, cpmppi_gru_advance, cpmppi_gru_washout; launch_gru_brunton for cpmppi_brunton (cpmppi_seams.hip).
+#include "cpmppi_brunton.hpp"
 #include "cpmppi_gru.hpp"        // (and cpmppi_internal.hpp)
 
 using namespace cpmppi_k;

@@ -12,6 +12,17 @@
 //   cpmppi_gru_model.hip  host code only: cpmppi_set_gru packs and uploads the three weight images
 //   cpmppi_comm.hip, cpmppi_groups.hip, cpmppi_io.hip   host code only: the collective, env groups, the recording writer
 //   cpmppi_rollout_*.hip  the instances of rollout_cost_kernel, each unit with its own compiler flags
+// The headers underneath, one per subject, each included by name where it is used (there is no umbrella header):
+//   cpmppi_params.hpp     Params, EnvConst, the kernels' template-argument ids, State, the float / float2 helpers
+//   cpmppi_step.hpp       what the units share about a step: BLOCK / WAVES, StepPtrs, GatherSync, shifted_nominal, finalize_env
+//   cpmppi_rollout.hpp    the rollout kernel (+ cpmppi_rollout_kernel.inc): the cpmppi_rollout_*.hip units, and - declarations and
+//                         instance lists only - cpmppi.hip; no other unit includes it
+//   cpmppi_ode.hpp, cpmppi_cost.hpp, cpmppi_philox.hpp, cpmppi_wave.hpp   the integrators, the stage costs and their folds, the noise
+//                         stream and knot interpolation, the wave reductions: the kernel units that use them, never the host-only ones
+//   cpmppi_brunton.hpp    the Brunton test's arguments and statistics: cpmppi_seams.hip and cpmppi_gru_seam.hip only
+//   cpmppi_debug.hpp      the diagnostic builds' counters and stamps (no-ops in the product build)
+//   cpmppi_grad.hpp, cpmppi_rpgd.hpp, cpmppi_cem.hpp (cpmppi_optim.hip), cpmppi_gru.hpp, cpmppi_gru16.hpp (the GRU units)
+// This header includes cpmppi_params.hpp and cpmppi_step.hpp, and forward-declares what the handle only points to.
 // Kernels stay in an anonymous namespace of the unit that launches them; units call each other through host functions only.
 #pragma once
 #include <hip/hip_runtime.h>
@@ -19,7 +30,8 @@
 #include <string>
 #include <vector>
 #include "cpmppi.h"
-#include "cpmppi_rollout.hpp"      // (declares, never instantiates, rollout_cost_kernel: only cpmppi_rollout_*.hip define it)
+#include "cpmppi_params.hpp"
+#include "cpmppi_step.hpp"         // (no kernel: cpmppi_rollout.hpp is for the units that instantiate or launch rollout_cost_kernel)
 #include "cpmppi_launch_plan.hpp"
 
 namespace cpmppi_comm {
@@ -30,7 +42,7 @@ void destroy(CommState* c);                              // called by cpmppi_des
 // the step launch -> enqueue_gather (side stream: wait for the published step, ncclAllGather, post completion)
 struct GatherTicket {
   unsigned* flags;        // device words: [0] envs finalized, [1] steps published, [2] gathers completed, [3] error, [4..9] the
-                          // slow paths' pointers and the timeout (GatherSync, cpmppi_rollout.hpp)
+                          // slow paths' pointers and the timeout (GatherSync, cpmppi_step.hpp)
   unsigned publish, need;
   unsigned envs;          // envs that publish the step together: 0 = the launch's own (one handle); env groups: all groups' envs
 };
@@ -42,6 +54,16 @@ int enqueue_guard(cpmppi_handle* h, const GatherTicket& t, unsigned envs, void* 
 void poison(CommState* c);                   // a partly enqueued step-gather: error state until cpmppi_comm_sync (which resets the counters)
 int comm_error_pending(cpmppi_handle* h);    // a device-side wait timed out or a step-gather was poisoned (sticky until cpmppi_comm_sync)
 }  // namespace cpmppi_comm
+
+namespace cpmppi {
+struct EnvFold;          // cpmppi_cost.hpp
+struct BruntonArgs;      // cpmppi_brunton.hpp
+
+// The GRU predictor's input / output normalisation (cpmppi_gru.hpp); here because the handle holds one by value.
+struct GruNorm {         // normalised = x*scale + shift ; order Q, angleD, angle_cos, angle_sin, position, positionD
+  float in_scale[6], in_shift[6], out_scale[5], out_shift[5];
+};
+}  // namespace cpmppi
 
 struct cpmppi_handle {
   cpmppi_config cfg;

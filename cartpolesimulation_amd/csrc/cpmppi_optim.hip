@@ -17,6 +17,7 @@
 
 #include "cpmppi.h"
 #include "cpmppi_internal.hpp"
+#include "cpmppi_philox.hpp"
 #include "cpmppi_grad.hpp"
 #include "cpmppi_rpgd.hpp"
 #include "cpmppi_cem.hpp"

@@ -10,6 +10,7 @@
 
 #include "cpmppi.h"
 #include "cpmppi_internal.hpp"
+#include "cpmppi_ode.hpp"
 
 using namespace cpmppi_k;
 

@@ -1,7 +1,7 @@
 // cpmppi_rollout_kernel.inc - the DEFINITION of the rollout kernel, included by cpmppi_rollout.hpp once per kernel name (that header
-// documents the template arguments and sets the three macros): CPMPPI_ROLLOUT_KERNEL the function's name, CPMPPI_ROLLOUT_MASS_ROWS
-// whether predictor_ODE's pole mass is read per env (cpmppi_set_pole_mass_rows), CPMPPI_ROLLOUT_INTEG_DEFAULT the default of INTEG.
-template <int COST, bool FAST, int NOISE, int R, int VARIANT_, int INTEG CPMPPI_ROLLOUT_INTEG_DEFAULT>
+// documents the template arguments, declares both kernels - INTEG's default is on the declaration - and sets the two macros):
+// CPMPPI_ROLLOUT_KERNEL the function's name, CPMPPI_ROLLOUT_MASS_ROWS whether predictor_ODE's pole mass is read per env (cpmppi_set_pole_mass_rows).
+template <int COST, bool FAST, int NOISE, int R, int VARIANT_, int INTEG>
 __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const Params p, const StepPtrs a) {
   constexpr bool MASS_ROWS = CPMPPI_ROLLOUT_MASS_ROWS;
   static_assert(!MASS_ROWS || INTEG == PREDICTOR_ODE, "only predictor_ODE reads the pole mass attribute");

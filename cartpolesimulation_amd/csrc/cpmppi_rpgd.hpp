@@ -3,6 +3,7 @@
 // it through the sweep, the Adam update and the redraw.  The sweep's check-points and gradient are a workspace slice of the env,
 // lane-contiguous with the block's width as the stride.
 #pragma once
+#include "cpmppi_philox.hpp"
 #include "cpmppi_grad.hpp"
 
 namespace cpmppi {

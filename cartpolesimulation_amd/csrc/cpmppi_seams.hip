@@ -18,6 +18,11 @@
 
 #include "cpmppi.h"
 #include "cpmppi_internal.hpp"
+#include "cpmppi_ode.hpp"
+#include "cpmppi_cost.hpp"
+#include "cpmppi_philox.hpp"
+#include "cpmppi_wave.hpp"
+#include "cpmppi_brunton.hpp"
 
 using namespace cpmppi_k;
 
@@ -152,7 +157,7 @@ constexpr int PRED_KS = 8;
 constexpr int PRED_ROW = PRED_KS * 6 + 1;
 // STAGED = false: every lane stores its own states directly — the shorter path for launches that do not fill the chip
 // (1024 rollouts: 59 us against 82 us staged; 262144 rollouts: 416 us against 280 us staged).
-// INTEG: the in-tree ODE predictor (cpmppi_device.hpp: PREDICTOR_ODE_V0 | PREDICTOR_ODE).
+// INTEG: the in-tree ODE predictor (cpmppi_params.hpp: PREDICTOR_ODE_V0 | PREDICTOR_ODE).
 template <bool FAST, bool STAGED, int INTEG = PREDICTOR_ODE_V0>
 __device__ __forceinline__ void predict_control_step(State<float>& st, float Qk, const Params& p, const EnvConst& ec) {
   if constexpr (INTEG == PREDICTOR_ODE) {

@@ -8,7 +8,7 @@ generator exists for throughput only - but a bench line that says "Philox4x32-10
     1.x `philox4x32_R(10, ctr, key)`: ten rounds of (hi, lo) = M * c with M0 = 0xD2511F53 on c0 and M1 = 0xCD9E8D57 on c2, output
     (hi1 ^ c1 ^ k0, lo1, hi0 ^ c3 ^ k1, lo0), key bumped by (0x9E3779B9, 0xBB67AE85) between rounds - checked against the known-answer
     vectors Random123 ships (tests/test_oracle_philox.py);
-  * the sampler's counter / key layout and its Box-Muller (cartpolesimulation_amd/csrc/cpmppi_device.hpp, philox_normal_quad /
+  * the sampler's counter / key layout and its Box-Muller (cartpolesimulation_amd/csrc/cpmppi_philox.hpp, philox_normal_quad /
     philox_normal_pair): counter = (rollout, GLOBAL env index, knot quad, low word of the step counter), key = (seed_lo ^ 0x51ed270b,
     seed_hi ^ high word of the step counter); words -> uniforms ua, uc in (0, 1] and ub, ud in [0, 1) with 24 bits each; knots
     4q .. 4q+3 = sigma * (ra cos 2 pi ub, ra sin 2 pi ub, rc cos 2 pi ud, rc sin 2 pi ud), r = sqrt(-2 ln u).
@@ -77,7 +77,7 @@ def knots(seed, offset, env_offset, E, N, P, sigma):
 
 
 # --------------------------------------------------------------------------------------------------------------------
-# The CEM samplers' stream (cpmppi_device.hpp, philox_normal_pair; cpmppi_optim.hip, cem_sample_kernel / cem_gmm_sample_kernel):
+# The CEM samplers' stream (cpmppi_philox.hpp, philox_normal_pair; cpmppi_optim.hip, cem_sample_kernel / cem_gmm_sample_kernel):
 # counter = (rollout, GLOBAL env index, step pair, low word of the offset), key = (seed_lo, seed_hi ^ high word of the offset) - NO
 # XOR constant on the low key word, and only words 0 and 1 of the block are used: time-steps 2 pair and 2 pair + 1 are
 # r (cos 2 pi u2, sin 2 pi u2), r = sqrt(-2 ln u1), with the 24-bit uniforms of _uniforms.

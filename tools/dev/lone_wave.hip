@@ -1,5 +1,5 @@
 // Micro-benchmark (development tool): what the rollout kernel's own control-step code costs a wave as a function of the
-// waves that share its SIMD - the pieces of `control_step_fast<f2>` (cpmppi_device.hpp) and of the triples-with-rollback
+// waves that share its SIMD - the pieces of `control_step_fast<f2>` (cpmppi_ode.hpp) and of the triples-with-rollback
 // control step it replaced (rows "triple ...") timed in isolation, with the
 // product's compiler flags, on 1 / 2 / 4 waves per SIMD.  Answers: is a lone wave (BASELINE C4: one packed wave per SIMD)
 // bound by issue (~5 cycles per packed instruction), by dependent latency (~9), or by something else?
@@ -12,7 +12,7 @@
 // issue-rate facts.
 //   hipcc -O3 --offload-arch=gfx950 -std=c++17 -I include -I cartpolesimulation_amd/csrc -mllvm -amdgpu-sched-strategy=iterative-ilp
 //         -mllvm -disable-vector-combine tools/dev/lone_wave.hip -o build_variants/lone_wave
-#include "cpmppi_device.hpp"
+#include "cpmppi_ode.hpp"       // (and cpmppi_params.hpp)
 #include <stdio.h>
 #include <string.h>
 #include <math.h>
@@ -213,7 +213,7 @@ __global__ __launch_bounds__(256) void k1(const float* in, float* out, Params p,
       const uint64_t fired = __builtin_amdgcn_fcmpf(mx, ph.THL, 3) | __builtin_amdgcn_fcmpf(md, ROT_LIMIT_LO, 2);
       if (__builtin_expect(fired != 0, 0)) break;
     } else {
-      substep_fast<float, true, false>(st, uK, t, ph, eh, nearlim);
+      substep_fast<float, false>(st, uK, t, ph, eh, nearlim);
       uK = -uK;
     }
   }
