@@ -90,56 +90,29 @@ class BatchedCartPoleExperiment:
         if record:
             states[0] = s
         h = gru_memory(eng, E, h0) if gru else None
-        if graph:
-            return self._run_graph(s, u_nom, Q, tp, te, Lt, states, Qs, n_control_steps, env_offset, int(steps_per_graph), h)
-        for t in range(n_control_steps):
-            if gru:
-                eng.step(s, u_nom, tp, te, seed=self.seed, offset=t, env_offset=env_offset, Q_out=Q, predictor="GRU", h0=h)
-                eng.gru_advance(s, Q, h)                       # before the plant moves s: the state the controller saw
-            else:
-                eng.step(s, u_nom, tp, te, L=Lt, seed=self.seed, offset=t, env_offset=env_offset, Q_out=Q)
-            # plant + this period's row of the recording in ONE launch (two kernels per control step in all)
-            eng.plant_advance(s, Q, L=Lt, n_substeps=self.n_sub, dt_sim=self.dt_simulation, states_log=states, Q_log=Qs, row=t)
-        return self._result(states, Qs, s, u_nom, h)
+        L_model = None if gru else Lt                          # (the network knows no pole length)
+        # captured, the period is named by a counter in device memory (Philox step counter = control step index = recording row;
+        # after the step: + 1), so that no launch argument changes between steps; launched, by the host's t
+        counter = torch.zeros(1, dtype=torch.int64, device=s.device) if graph else None
+        seed, n_sub, dt_sim = self.seed, self.n_sub, self.dt_simulation
 
-    @staticmethod
-    def _result(states, Qs, s, u_nom, h):
+        def period(t):                                         # (plain keywords: the host's time per period is the launched loop's pace)
+            eng.step(s, u_nom, tp, te, L=L_model, seed=seed, offset=t if counter is None else 0, offset_dev=counter, env_offset=env_offset,
+                     Q_out=Q, predictor=predictor, h0=h)
+            if gru:
+                eng.gru_advance(s, Q, h)                       # before the plant moves s: the state the controller saw
+            # plant + this period's row of the recording in ONE launch (two kernels per control step in all)
+            eng.plant_advance(s, Q, L=Lt, n_substeps=n_sub, dt_sim=dt_sim, states_log=states, Q_log=Qs,
+                              row=t if counter is None else 0, row_dev=counter)
+
+        loop = PeriodLoop(eng, n_control_steps)
+        if graph:                                              # the launch-bound case: few envs, ~70 us of GPU work per control step
+            loop.capture(period, steps_per_graph, s.device)
+        loop.enqueue_rest(period)
         res = dict(states=states, Q=Qs, final_state=s, u_nom=u_nom)
-        if h is not None:
+        if gru:
             res["memory"] = h
         return res
-
-    def _run_graph(self, s, u_nom, Q, tp, te, Lt, states, Qs, n_control_steps, env_offset, per_graph, h=None):
-        """The same loop as ONE captured HIP graph of `per_graph` control steps, replayed: controller step (Philox counter in device
-        memory, `offset_dev`), plant + recording at the row the same counter names — no launch argument changes between steps, the
-        host only enqueues replays (the launch-bound case: few envs, ~70 us of GPU work per control step)."""
-        eng = self.engine
-        counter = torch.zeros(1, dtype=torch.int64, device=s.device)          # Philox step counter = control step index
-                                                                              # = recording row (after the step: + 1)
-
-        def one_step():
-            if h is not None:
-                eng.step(s, u_nom, tp, te, seed=self.seed, offset_dev=counter, env_offset=env_offset, Q_out=Q, predictor="GRU", h0=h)
-                eng.gru_advance(s, Q, h)
-            else:
-                eng.step(s, u_nom, tp, te, L=Lt, seed=self.seed, offset_dev=counter, env_offset=env_offset, Q_out=Q)
-            eng.plant_advance(s, Q, L=Lt, n_substeps=self.n_sub, dt_sim=self.dt_simulation, states_log=states, Q_log=Qs,
-                              row_dev=counter)
-
-        side = torch.cuda.Stream(device=s.device)
-        side.wait_stream(torch.cuda.current_stream(s.device))
-        g = torch.cuda.CUDAGraph()
-        per_graph = max(1, min(per_graph, n_control_steps))
-        with torch.cuda.stream(side):
-            with torch.cuda.graph(g, stream=side):
-                for _ in range(per_graph):
-                    one_step()
-        torch.cuda.current_stream(s.device).wait_stream(side)
-        for _ in range(n_control_steps // per_graph):
-            g.replay()
-        for _ in range(n_control_steps % per_graph):          # the remainder, launched directly with the same device counter
-            one_step()
-        return self._result(states, Qs, s, u_nom, h)
 
     # ------------------------------------------------------------------ the data generator's experiments (moving targets)
     def run_schedule(self, batch, env_offset=0, graph=False, steps_per_graph=10, knots_fn=None, u_nom0=None, optimizer=None,
@@ -167,12 +140,11 @@ class BatchedCartPoleExperiment:
                           predictor=predictor, h0=h0)
         if batch.dt_simulation != self.dt_simulation or batch.n_ctrl != self.n_sub:
             raise ValueError("the batch was drawn for other time scales than this experiment runner's")
-        if graph and optimizer is not None and not run.fused:
-            raise ValueError("an optimizer object is paced by the host: run this batch launched (graph=False)")
+        if graph and run.controller.cannot_capture:
+            raise ValueError(run.controller.cannot_capture)
         if graph and knots_fn is None and run.T > 0:
             run.capture(steps_per_graph)
-        while run.periods_left:
-            run.enqueue_next()
+        run.loop.enqueue_rest(run._period)
         return run.finish()
 
 
@@ -267,27 +239,68 @@ class ControllerMass:
             self.registered = False
 
 
-class ScheduleRun:
-    """The device loop of BatchedCartPoleExperiment.run_schedule as an object that enqueues one piece at a time, so that several
-    runs - env groups on their own streams, pipeline.run_schedule_groups - can be interleaved by one host thread."""
+class PeriodLoop:
+    """`T` control periods of a device loop, enqueued by one host thread: the caller's ``period(c)`` launches period c; after
+    `capture`, `steps_per_graph` periods at a time are replays of ONE HIP graph and only the rest is launched.  The body captured is
+    ``period(None)``: it names its period by a counter in device memory, so that no launch argument changes between replays.
+    (The body is handed in with every call, not kept: a loop that held a bound method of the run that holds the loop would be a
+    reference cycle, and a captured graph must be freed when its run is dropped, not by the cycle collector during a later capture.)"""
 
-    def __init__(self, engine, batch, seed, env_offset=0, knots_fn=None, u_nom0=None, optimizer=None, bind_mass=True,
-                 predictor="ODE_v0", h0=None):
-        """``bind_mass`` False: the caller binds `self.mass` to the engines that launch (pipeline.run_schedule_groups)."""
-        self.eng, self.b, self.seed, self.env_offset, self.knots_fn = engine, batch, int(seed), int(env_offset), knots_fn
-        self.optimizer = optimizer
-        self.gru = check_predictor(engine, predictor, h0, optimizer, knots_fn)
-        self.h = gru_memory(engine, batch.E, h0) if self.gru else None     # the network's memory [E,2,32], advanced in place
-        self.fused = bool(getattr(optimizer, "fused", False))      # a fused optimizer (rpgd, gradient, the cem family): one library call per period
-        if optimizer is not None:
-            if getattr(optimizer, "num_envs", batch.E) != batch.E:
-                raise ValueError(f"the optimizer is configured for {optimizer.num_envs} envs, the batch has {batch.E}")
-            if getattr(optimizer, "variable_parameters", None) is None:
-                from types import SimpleNamespace
-                optimizer.variable_parameters = SimpleNamespace()
+    def __init__(self, engine, T):
+        self.eng, self.T, self.c = engine, int(T), 0
+        self.graph, self.per = None, 0
+
+    def capture(self, period, steps_per_graph, device):
+        """On a side stream that waits for what the launch stream holds; the launch stream then waits for the capture."""
+        cap = torch.cuda.Stream(device=device)
+        launch = self.eng.launch_stream()
+        cap.wait_stream(launch)
+        cap.wait_stream(torch.cuda.current_stream(device))
+        self.graph = torch.cuda.CUDAGraph()
+        self.per = max(1, min(int(steps_per_graph), self.T))
+        fixed = self.eng.use_stream(cap)
+        try:
+            with torch.cuda.stream(cap):
+                with torch.cuda.graph(self.graph, stream=cap):
+                    for _ in range(self.per):
+                        period(None)
+        finally:
+            self.eng.use_stream(fixed)
+        launch.wait_stream(cap)
+
+    def _replay(self):
+        """One replay of the captured graph, if there is one and a whole one still fits.  -> whether"""
+        if self.graph is None or self.T - self.c < self.per:
+            return False
+        with torch.cuda.stream(self.eng.launch_stream()):
+            self.graph.replay()
+        self.c += self.per
+        return True
+
+    def enqueue_next(self, period):
+        """The next control period(s): one replay, else one period launched (a driver that interleaves several runs)."""
+        if not self._replay():
+            period(self.c)
+            self.c += 1
+
+    def enqueue_rest(self, period):
+        """All that is left: the replays, then the remainder launched (nothing but the body between two periods)."""
+        while self._replay():
+            pass
+        for c in range(self.c, self.T):
+            period(c)
+        self.c = self.T
+
+
+class ScheduleBuffers:
+    """What a schedule run derives from its batch alone: the states, the vectors the controller reads and the plant refills, the
+    logs, the schedule tables on the device and the plant launch's keyword arguments (`plant`).  It holds no controller and binds no
+    pole mass: ScheduleRun steps one, pipeline.run_schedule_groups hands one to the env groups."""
+
+    def __init__(self, engine, batch, u_nom0=None):
         eng, b = engine, batch
         E, T = b.E, b.n_periods
-        self.T, self.c = T, 0
+        self.b, self.T = b, T
         R = b.n_sim // b.n_save + 1
         self.s = s = eng.tensor(b.s0).clone()
         tp_tab = eng.tensor(b.target_position.astype(np.float32))                 # the controller computes in float32
@@ -303,11 +316,7 @@ class ScheduleRun:
         self.cur_tp, self.cur_te = tp_tab[0].clone(), te_tab[0].clone()
         self.cur_L = (Lc_tab if Lc_tab is not None else L_tab)[0].clone() if L_tab is not None else (eng.tensor(b.L) if b.L is not None else None)
         self.u_nom = eng.zeros(E, eng.H) if u_nom0 is None else eng.tensor(u_nom0, (E, eng.H)).clone()
-        self.Q = eng.empty(E)
-        if self.fused:                                             # the fused step writes its controls where the plant reads them
-            if optimizer.engine is None:
-                optimizer.configure()
-            self.Q = optimizer.controls
+        self.Q = eng.empty(E)                                      # the controls: the controller writes them, the plant reads them
         self.states, self.dd, self.Qs = eng.zeros(R, E, 6), eng.zeros(R, E, 2), eng.zeros(T + 1, E)
         self.states[0] = s
         self.tail = b.n_sim - T * b.n_ctrl                                        # simulation steps after the last controller call
@@ -346,158 +355,209 @@ class ScheduleRun:
         # the control applied in the last period = the next call's Q_ccrc / "Q_applied_-1" (CartPole/__init__.py:489, 517-518), for the
         # cost plugins that read a previous input (0 before the first update, :838)
         from .optimizer_mppi import PREVIOUS_INPUT_COSTS
-        self.prev_Q = None
+        self.previous_input = {}                                   # (a keyword of the controller call)
         if eng.mppi.cost_function_specification in PREVIOUS_INPUT_COSTS:
-            self.prev_Q = eng.zeros(E)
-            self.plant.update(Q_applied_out=self.prev_Q)
-        self.mass = ControllerMass(b, eng.mppi, network=self.gru)
-        if bind_mass:                                              # (an optimizer object registers the row with its own engine)
-            self.mass.bind([eng], register=optimizer is None)
-        self.counter, self.graph, self.per = None, None, 0
-        if self.fused and not optimizer.warmup:
-            # the fused step counts its control steps on the device, launched or captured: the same arithmetic either way
-            # (warm-up iterations on the first step are told by the host: such an optimizer keeps its host counters)
-            self.counter = torch.zeros(1, dtype=torch.int64, device=self.s.device)
-        self._prep = self._prep_plant = None                       # argument blocks built once (the launched Philox loop)
+            self.previous_input = dict(previous_input=eng.zeros(E))
+            self.plant.update(Q_applied_out=self.previous_input["previous_input"])
 
-    @property
-    def _prev(self):
-        return {} if self.prev_Q is None else {"previous_input": self.prev_Q}
+    def prepare_plant(self, engine):
+        """-> the plant launch of one control period as a prepared call: `.run(period=c)`; `n_substeps=` for a run's last steps."""
+        return engine.prepare_plant_step(self.s, self.Q, self.b.n_ctrl, period=0, **self.plant)
 
-    @property
-    def _model(self):
-        """What tells the fused step its plant model: the pole length the controller is told, or the network and its memory."""
-        return dict(predictor="GRU", h0=self.h) if self.gru else dict(L=self.cur_L)
+    def result(self):
+        return dict(states=self.states, dd=self.dd, Q=self.Qs, final_state=self.s, u_nom=self.u_nom, batch=self.b)
 
-    def _advance_memory(self):
-        """Behind a GRU step, before the plant launch refills s_ctrl: the memory moves on with what the controller saw and chose."""
-        if self.gru:
-            self.eng.gru_advance(self.s_ctrl, self.Q, self.h)
 
-    @property
-    def periods_left(self):
-        return self.c < self.T
+# The controller of a schedule run, one class per kind.  ScheduleRun asks three things of it: `control(c)` enqueues controller call c
+# (None under capture: the call is named by `counter`, the device's count of the calls made - None while the host counts),
+# `before_capture()` does what must happen once before the loop is captured, and `cannot_capture` says why it cannot be (or None; a
+# kind that never can has no `before_capture`).
 
-    m_ctrl = property(lambda self: self.mass.values)           # (host [T+1] / the registered device vector [E], or None)
-    m_env = property(lambda self: self.mass.rows)
+class FusedMppiStep:
+    """The fused MPPI step over the engine's equations or - ``memory`` [E,2,32], advanced in place - over its network.  The
+    perturbations come from ``knots_fn(c)`` (tests), from Philox at the host's offset c, or at the device counter."""
+    cannot_capture = None
 
-    def _control(self, c):
-        eng = self.eng
-        if self.optimizer is not None:
-            # what the simulator hands controller.step (CartPole/__init__.py:509-520), as attributes of the optimizer's
-            # variable_parameters; the optimizer returns the controls as a device tensor
-            vp = self.optimizer.variable_parameters
-            vp.target_position, vp.target_equilibrium = self.cur_tp, self.cur_te
-            if self.cur_L is not None:
-                vp.L = self.cur_L
-            if self.mass.kind != "none" and c is not None:
-                vp.m_pole = self.mass.for_optimizer(c)
-            if self.prev_Q is not None:
-                vp.Q_ccrc = self.prev_Q
-                setattr(vp, "Q_applied_-1", self.prev_Q)
-            if self.fused:
-                opt = self.optimizer
-                if c is not None:                                  # (captured: applied once before the capture)
-                    opt.engine.apply_pole_mass_of(vp, **opt._mass_rows)
-                # everything on the device; the control of the period before is the one this buffer still holds
-                opt.step_device(self.s_ctrl, self.cur_tp, self.cur_te, L=self.cur_L, previous_input=self.Q, count_dev=self.counter)
-                return
-            t = float(self.b.times[min(c * self.b.n_ctrl, len(self.b.times) - 1)])
-            q = self.optimizer.step(self.s_ctrl, t, as_tensor=True)
-            self.Q.copy_(q.reshape(-1))
-            return
+    def __init__(self, engine, buffers, mass, seed, env_offset, knots_fn, memory):
+        self.eng, self.buf, self.mass, self.knots_fn, self.memory = engine, buffers, mass, knots_fn, memory
+        self.philox = dict(seed=int(seed), env_offset=int(env_offset))
+        self.counter = self.step = None
+
+    def _arguments(self):
+        """(Read when a call is built: a test may still re-point the vectors of the buffers before the first period.)"""
+        buf = self.buf
+        model = dict(L=buf.cur_L) if self.memory is None else dict(predictor="GRU", h0=self.memory)
+        return (buf.s_ctrl, buf.u_nom, buf.cur_tp, buf.cur_te), dict(Q_out=buf.Q, **model, **buf.previous_input)
+
+    def control(self, c):
         if c is not None:
             self.mass.apply(c)
-        if self.knots_fn is not None:
-            noise = dict(knots=self.knots_fn(c))
-        elif self.counter is not None:
-            noise = dict(seed=self.seed, offset_dev=self.counter, env_offset=self.env_offset)
+        if self.step is not None:
+            self.step.run(offset=c)
+        elif self.knots_fn is None and self.counter is None:
+            # the launched loop: the argument block is built once (the Python-side argument handling of step + plant_step is
+            # ~30 us per period - more than the GPU needs for a few dozen envs); per period mass.apply, this and the plant's
+            args, kw = self._arguments()
+            self.step = self.eng.prepare_step(*args, offset=0, **self.philox, **kw)
+            self.step.run(offset=c)
         else:
-            noise = dict(seed=self.seed, offset=c, env_offset=self.env_offset)
-        eng.step(self.s_ctrl, self.u_nom, self.cur_tp, self.cur_te, Q_out=self.Q, **self._model, **noise, **self._prev)
-        self._advance_memory()
+            args, kw = self._arguments()
+            noise = dict(knots=self.knots_fn(c)) if self.knots_fn is not None else dict(offset_dev=self.counter, **self.philox)
+            self.eng.step(*args, **noise, **kw)
+        if self.memory is not None:
+            # before the plant launch refills s_ctrl: the memory moves on with what the controller saw and chose
+            self.eng.gru_advance(self.buf.s_ctrl, self.buf.Q, self.memory)
 
-    def _plant_step(self, n_substeps, c):
-        """The plant launch of control period c: the period from the host, or - captured - from the device counter."""
-        when = dict(period=c) if self.counter is None else dict(period_dev=self.counter)
-        self.eng.plant_step(self.s, self.Q, n_substeps, **when, **self.plant)
+    def before_capture(self):
+        self.counter = torch.zeros(1, dtype=torch.int64, device=self.buf.s.device)
+        self.step = None                                           # (built for the host's offset)
+
+
+def _tell_optimizer(optimizer, buffers, mass, c):
+    """What the simulator hands controller.step (CartPole/__init__.py:509-520), as attributes of the optimizer's variable_parameters
+    (the pole mass of call c; None under capture: it stays).  -> them."""
+    vp = optimizer.variable_parameters
+    vp.target_position, vp.target_equilibrium = buffers.cur_tp, buffers.cur_te
+    if buffers.cur_L is not None:
+        vp.L = buffers.cur_L
+    if mass.kind != "none" and c is not None:
+        vp.m_pole = mass.for_optimizer(c)
+    for prev_Q in buffers.previous_input.values():
+        vp.Q_ccrc = prev_Q
+        setattr(vp, "Q_applied_-1", prev_Q)
+    return vp
+
+
+class HostPacedOptimizer:
+    """One of the package's optimizer objects: one `optimizer.step` per control period on device tensors, which returns the
+    controls as a device tensor."""
+    cannot_capture = "an optimizer object is paced by the host: run this batch launched (graph=False)"
+    counter = None
+
+    def __init__(self, optimizer, buffers, mass):
+        self.opt, self.buf, self.mass = optimizer, buffers, mass
+
+    def control(self, c):
+        b = self.buf.b
+        _tell_optimizer(self.opt, self.buf, self.mass, c)
+        t = float(b.times[min(c * b.n_ctrl, len(b.times) - 1)])
+        self.buf.Q.copy_(self.opt.step(self.buf.s_ctrl, t, as_tensor=True).reshape(-1))
+
+
+class FusedOptimizer:
+    """A fused optimizer object (rpgd, gradient, the cem family with `fused=True`): one library call per period, everything on the
+    device.  It counts its control steps on the device, launched or captured: the same arithmetic either way - unless it warms up:
+    the first step's extra iterations are told by the host, and such an optimizer keeps its host counters."""
+    cannot_capture = None
+
+    def __init__(self, optimizer, buffers, mass):
+        self.opt, self.buf, self.mass = optimizer, buffers, mass
+        if optimizer.engine is None:
+            optimizer.configure()
+        buffers.Q = optimizer.controls                             # the fused step writes its controls where the plant reads them
+        self.counter = None if optimizer.warmup else torch.zeros(1, dtype=torch.int64, device=buffers.s.device)
+        if optimizer.warmup:
+            self.cannot_capture = "warmup=True needs the host to tell the first step from the others: run this batch launched (graph=False)"
+
+    def control(self, c):
+        opt, buf = self.opt, self.buf
+        vp = _tell_optimizer(opt, buf, self.mass, c)
+        if c is not None:                                          # (captured: applied once before the capture)
+            opt.engine.apply_pole_mass_of(vp, **opt._mass_rows)
+        # the control of the period before is the one this buffer still holds
+        opt.step_device(buf.s_ctrl, buf.cur_tp, buf.cur_te, L=buf.cur_L, previous_input=buf.Q, count_dev=self.counter)
+
+    def before_capture(self):
+        """The optimizer's own handle: its mass, its workspace."""
+        opt, vp = self.opt, self.opt.variable_parameters
+        if self.mass.kind != "none":
+            vp.m_pole = self.mass.for_optimizer(0)
+        opt.engine.apply_pole_mass_of(vp, **opt._mass_rows)
+        opt.reserve_fused()
+
+
+def optimizer_controller(optimizer):
+    """-> the controller kind that runs this optimizer object."""
+    return FusedOptimizer if getattr(optimizer, "fused", False) else HostPacedOptimizer
+
+
+class ScheduleRun:
+    """The device loop of BatchedCartPoleExperiment.run_schedule as an object that enqueues one piece at a time, so that several
+    runs can be interleaved by one host thread: the batch's `buffers`, the `controller` that computes the controls, the `mass` it is
+    told, and the `loop` that launches or replays the periods."""
+
+    def __init__(self, engine, batch, seed, env_offset=0, knots_fn=None, u_nom0=None, optimizer=None, predictor="ODE_v0", h0=None):
+        gru = check_predictor(engine, predictor, h0, optimizer, knots_fn)
+        if optimizer is not None:
+            if getattr(optimizer, "num_envs", batch.E) != batch.E:
+                raise ValueError(f"the optimizer is configured for {optimizer.num_envs} envs, the batch has {batch.E}")
+            if getattr(optimizer, "variable_parameters", None) is None:
+                from types import SimpleNamespace
+                optimizer.variable_parameters = SimpleNamespace()
+        self.eng = engine
+        self.buffers = buf = ScheduleBuffers(engine, batch, u_nom0)
+        self.T, self.tail = buf.T, buf.tail
+        self.mass = ControllerMass(batch, engine.mppi, network=gru)
+        self.mass.bind([engine], register=optimizer is None)       # (an optimizer object registers the row with its own engine)
+        self.memory = gru_memory(engine, batch.E, h0) if gru else None
+        if optimizer is None:
+            self.controller = FusedMppiStep(engine, buf, self.mass, seed, env_offset, knots_fn, self.memory)
+        else:
+            self.controller = optimizer_controller(optimizer)(optimizer, buf, self.mass)
+        self.fused = isinstance(self.controller, FusedOptimizer)
+        self.loop = PeriodLoop(engine, self.T)
+        self._plant = None                                         # the plant launch at the host's period: built once
+
+    Q = property(lambda self: self.buffers.Q)
+    counter = property(lambda self: self.controller.counter)
+    periods_left = property(lambda self: self.loop.c < self.T)
+
+    def _plant_step(self, c, **last):
+        """The plant launch of control period c, named by the host or by the device counter (``n_substeps=``: the run's last steps)."""
+        counter = self.controller.counter
+        if counter is not None:
+            buf = self.buffers
+            self.eng.plant_step(buf.s, buf.Q, last.get("n_substeps", buf.b.n_ctrl), period_dev=counter, **buf.plant)
+            return
+        if self._plant is None:
+            self._plant = self.buffers.prepare_plant(self.eng)
+        self._plant.run(period=c, **last)
 
     def _period(self, c):
-        if self.counter is None and self.knots_fn is None and self.optimizer is None:
-            # the launched loop: two library calls per period (three with the network) on argument blocks built once (the Python-side argument handling of
-            # step + plant_step is ~30 us per period - more than the GPU needs for a few dozen envs)
-            self.mass.apply(c)
-            if self._prep is None:
-                self._prep = self.eng.prepare_step(self.s_ctrl, self.u_nom, self.cur_tp, self.cur_te, seed=self.seed, offset=0,
-                                                   env_offset=self.env_offset, Q_out=self.Q, **self._model, **self._prev)
-                self._prep_plant = self.eng.prepare_plant_step(self.s, self.Q, self.b.n_ctrl, period=0, **self.plant)
-            self._prep.run(offset=c)
-            self._advance_memory()
-            self._prep_plant.run(period=c)
-            return
-        self._control(c)
-        self._plant_step(self.b.n_ctrl, c)
+        self.controller.control(c)
+        self._plant_step(c)
 
     def capture(self, steps_per_graph=10):
         """Capture `steps_per_graph` control periods as ONE HIP graph (device step counter: Philox offset = schedule row =
         recording row, no launch argument changes between periods); enqueue_next then replays it."""
-        if self.optimizer is not None and not self.fused:
-            raise ValueError("an optimizer object is paced by the host: run this batch launched (graph=False)")
-        if self.fused and self.counter is None:
-            raise ValueError("warmup=True needs the host to tell the first step from the others: run this batch launched (graph=False)")
-        if self.mass.varies:
-            raise ValueError("a captured graph replays ONE pole mass for the controller: run this batch launched (graph=False)"
-                             if self.mass.kind == "value" else
-                             "a captured graph cannot step through the controller's per-experiment pole-mass table (the row would "
-                             "have to be selected on the device): run this batch launched (graph=False)")
-        dev = self.s.device
+        why = self.controller.cannot_capture
+        if why is None and self.mass.varies:
+            why = ("a captured graph replays ONE pole mass for the controller: run this batch launched (graph=False)"
+                   if self.mass.kind == "value" else
+                   "a captured graph cannot step through the controller's per-experiment pole-mass table (the row would "
+                   "have to be selected on the device): run this batch launched (graph=False)")
+        if why is not None:
+            raise ValueError(why)
         # the graph replays the handle's controller mass as it is when CAPTURED: the run's (constant) one, which may differ from
         # the mass the handle was created with (an uninformed controller; advisor, round 5)
         self.mass.apply(0)
-        if self.fused:                                             # ... and the optimizer's own handle: its mass, its workspace
-            vp = self.optimizer.variable_parameters
-            if self.mass.kind != "none":
-                vp.m_pole = self.mass.for_optimizer(0)
-            self.optimizer.engine.apply_pole_mass_of(vp, **self.optimizer._mass_rows)
-            self.optimizer.reserve_fused()
-        if self.counter is None:
-            self.counter = torch.zeros(1, dtype=torch.int64, device=dev)          # controller calls made
-        cap = torch.cuda.Stream(device=dev)
-        launch = self.eng.launch_stream()
-        cap.wait_stream(launch)
-        cap.wait_stream(torch.cuda.current_stream(dev))
-        self.graph = torch.cuda.CUDAGraph()
-        self.per = max(1, min(int(steps_per_graph), self.T))
-        fixed = self.eng.use_stream(cap)
-        try:
-            with torch.cuda.stream(cap):
-                with torch.cuda.graph(self.graph, stream=cap):
-                    for _ in range(self.per):
-                        self._period(None)
-        finally:
-            self.eng.use_stream(fixed)
-        launch.wait_stream(cap)
+        self.controller.before_capture()
+        self.loop.capture(self._period, steps_per_graph, self.buffers.s.device)
 
     def enqueue_next(self):
         """The next control period(s) of the run: one period launched, or one replay of the captured graph."""
-        if self.graph is not None and self.T - self.c >= self.per:
-            with torch.cuda.stream(self.eng.launch_stream()):
-                self.graph.replay()
-            self.c += self.per
-        else:
-            self._period(self.c)
-            self.c += 1
+        self.loop.enqueue_next(self._period)
 
     def finish(self):
         """The run's last controller call (+ the trailing simulation steps of a length that is not a whole number of periods)."""
         assert not self.periods_left
-        self._control(self.T)
+        self.controller.control(self.T)
         self.mass.release()
-        self._plant_step(self.tail, self.T)
+        self._plant_step(self.T, n_substeps=self.tail)
         return self.result()
 
     def result(self):
-        res = dict(states=self.states, dd=self.dd, Q=self.Qs, final_state=self.s, u_nom=self.u_nom, batch=self.b)
-        if self.gru:
-            res["memory"] = self.h
+        res = self.buffers.result()
+        if self.memory is not None:
+            res["memory"] = self.memory
         return res

@@ -204,26 +204,27 @@ def run_schedule_groups(groups: EnvGroups, batch, seed):
     """harness.BatchedCartPoleExperiment.run_schedule with the experiments split over the env groups: every group runs its own
     chain of (controller step, plant step) launches on its own stream; ALL periods of ALL groups are enqueued by one library call
     (cpmppi_groups_run), the groups working in place on their slices of the batch's buffers.  -> the same result dict."""
-    from .harness import ScheduleRun
+    from .harness import ControllerMass, ScheduleBuffers
     eng = groups.args_engine
-    run = ScheduleRun(eng, batch, seed, bind_mass=False)      # the batch's buffers and logs, set up on the caller's stream
+    buf = ScheduleBuffers(eng, batch)                          # the batch's buffers and logs, set up on the caller's stream
     # the controller's pole mass goes to the GROUPS' handles: every one reads its slice of the run's vector and refills it on its
     # own stream - no group waits for another
-    run.mass.bind(groups.engines, groups.slices)
-    step = groups.prepare(run.s_ctrl, run.u_nom, run.cur_tp, run.cur_te, L=run.cur_L, seed=seed, Q_out=run.Q, **run._prev)
-    plant = eng.prepare_plant_step(run.s, run.Q, batch.n_ctrl, period=0, **run.plant)
+    mass = ControllerMass(batch, eng.mppi)
+    mass.bind(groups.engines, groups.slices)
+    step = groups.prepare(buf.s_ctrl, buf.u_nom, buf.cur_tp, buf.cur_te, L=buf.cur_L, seed=seed, Q_out=buf.Q, **buf.previous_input)
+    plant = buf.prepare_plant(eng)
     groups.fork()
-    if run.mass.varies:
+    if mass.varies:
         # the controller's pole mass follows the plant's (predictor_ODE): a handle parameter read when a launch is enqueued (a vector
         # rewritten between launches) - one library call per period instead of one for the whole run
-        for c in range(run.T):
-            run.mass.apply(c)
+        for c in range(buf.T):
+            mass.apply(c)
             groups.run(step, plant, periods=1, offset=c, period=c)
-        run.mass.apply(run.T)
+        mass.apply(buf.T)
     else:
-        run.mass.apply(0)
-        groups.run(step, plant, periods=run.T, offset=0, period=0)
-    groups.run(step, plant, periods=1, offset=run.T, period=run.T, n_substeps=run.tail)   # the run's last controller call (+ trailing steps)
+        mass.apply(0)
+        groups.run(step, plant, periods=buf.T, offset=0, period=0)
+    groups.run(step, plant, periods=1, offset=buf.T, period=buf.T, n_substeps=buf.tail)   # the run's last controller call (+ trailing steps)
     groups.join()
-    run.mass.release()
-    return run.result()
+    mass.release()
+    return buf.result()

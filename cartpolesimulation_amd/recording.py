@@ -294,9 +294,9 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
     if optimizer is not None:
         if int(groups) > 1:
             raise ValueError("env groups run the fused MPPI step only: an optimizer object needs groups=1")
-        if graph and not getattr(optimizer, "fused", False):
-            raise ValueError("an optimizer object is paced by the host: groups=1, graph=False (a fused rpgd / gradient / cem optimizer "
-                             "- fused=True - may be captured)")
+        from .harness import optimizer_controller
+        if graph and optimizer_controller(optimizer).cannot_capture:    # (before anything is drawn: the run itself would refuse too)
+            raise ValueError(optimizer_controller(optimizer).cannot_capture)
         if getattr(optimizer, "engine", None) is None:
             from .shard import env_shard
             optimizer.configure(num_envs=env_shard(n_total, int(world), int(rank))[1])

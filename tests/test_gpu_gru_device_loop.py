@@ -107,7 +107,7 @@ def test_run_schedule_with_the_network_feeds_the_measured_state_to_the_memory():
     length of 6.5 control periods: launched == captured == the composed loop that hands the MEASURED state to the memory; the
     composed loop that hands it the true state differs."""
     from cartpolesimulation_amd import schedule as SC
-    from cartpolesimulation_amd.harness import BatchedCartPoleExperiment, ScheduleRun
+    from cartpolesimulation_amd.harness import BatchedCartPoleExperiment, ScheduleBuffers
     E, n, h = 4, 128, 8
     cfg = dict(seed=51, length_of_experiment=0.13, dt=dict(saving=0.004), keep_target_equilibrium_x_seconds_up=0.05,
                turning_points=dict(track_relative_complexity=12),
@@ -124,7 +124,7 @@ def test_run_schedule_with_the_network_feeds_the_measured_state_to_the_memory():
     same(launched, captured, "launched vs captured")
 
     def composed(measured):
-        run = ScheduleRun(eng, b, 9)                              # the batch's buffers, tables and plant arguments; never stepped itself
+        run = ScheduleBuffers(eng, b)                             # the batch's buffers, tables and plant arguments; never stepped itself
         mem = eng.zeros(E, 2, 32)
         for c in range(b.n_periods + 1):
             eng.step(run.s_ctrl, run.u_nom, run.cur_tp, run.cur_te, seed=9, offset=c, Q_out=run.Q, predictor="GRU", h0=mem)

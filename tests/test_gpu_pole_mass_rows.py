@@ -386,7 +386,7 @@ def test_device_loop_with_a_mass_schedule_per_experiment(groups, math_mode, rpl)
     uninformed = _by_hand(eng, b, None)
     assert np.abs(Q_loop - uninformed).max() > 1e-3
     off = engine(E, N, H, **kw)                                    # flag off: the controller keeps the handle's mass
-    assert ScheduleRun(off, b, 7).m_env is None and np.array_equal(loop(off, b), uninformed)
+    assert ScheduleRun(off, b, 7).mass.rows is None and np.array_equal(loop(off, b), uninformed)
     off.close()
     if groups == 1:
         with pytest.raises(ValueError, match="per-experiment pole-mass table"):

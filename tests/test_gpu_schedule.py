@@ -360,8 +360,8 @@ def test_reference_experiment_with_a_changing_pole_length_on_the_device_loop(g):
     run = ScheduleRun(eng, b, 0, knots_fn=knots, u_nom0=un)
     # the legacy controller ignores the pole length it is told (its predictor is configured without variable_parameters,
     # controller_mppi_cartpole.py:51-52): the controller's L vector is pinned to the default, the PLANT follows the table
-    run.plant["L_out"] = None
-    run.cur_L = None
+    run.buffers.plant["L_out"] = None
+    run.buffers.cur_L = None
     while run.periods_left:
         run.enqueue_next()
     res = run.finish()
@@ -430,8 +430,8 @@ def test_reference_experiment_with_changing_pole_mass_and_a_switching_informer_o
         run = ScheduleRun(eng, batch, 0, knots_fn=knots, u_nom0=un)
         # the legacy controller ignores the pole length it is told (controller_mppi_cartpole.py:51-52): its L stays the default;
         # the published vector is kept aside and compared with what the reference's calls were handed
-        handed = run.cur_L
-        run.cur_L = None
+        handed = run.buffers.cur_L
+        run.buffers.cur_L = None
         told_L = [float(handed.cpu().numpy()[0])] if handed is not None else []
         while run.periods_left:
             run.enqueue_next()
@@ -647,10 +647,10 @@ def test_reference_experiment_with_the_measurement_chain_on_the_device_loop(g):
         un = eng.zeros(1, H)
         eng.step(g[f"{key}/call/s"][0][None], un, float(g[f"{key}/call/tp"][0]), 1.0, knots=knots(0))
         run = ScheduleRun(eng, batch, 0, knots_fn=knots, u_nom0=un)
-        seen = [run.s_ctrl.cpu().numpy()[0].copy()]
+        seen = [run.buffers.s_ctrl.cpu().numpy()[0].copy()]
         while run.periods_left:
             run.enqueue_next()
-            seen.append(run.s_ctrl.cpu().numpy()[0].copy())
+            seen.append(run.buffers.s_ctrl.cpu().numpy()[0].copy())
         return run.finish(), np.array(seen)
 
     res, seen = run_with(b)
@@ -804,7 +804,7 @@ def test_controller_pole_mass_follows_a_uniform_schedule_with_predictor_ODE(grou
     run = ScheduleRun(eng, b, 7)
     calls = np.arange(b.n_periods + 1) * b.n_ctrl
     want = np.where(b.informed[calls, 0], b.m_pole_table[calls, 0], np.float32(0.087)).astype(f32)
-    assert np.array_equal(run.m_ctrl, want) and len(np.unique(want)) > 4 and (want == np.float32(0.087)).sum() >= 3
+    assert np.array_equal(run.mass.values, want) and len(np.unique(want)) > 4 and (want == np.float32(0.087)).sum() >= 3
     if groups == 1:
         res = BatchedCartPoleExperiment(eng, seed=7).run_schedule(b)
     else:
@@ -831,7 +831,7 @@ def test_controller_pole_mass_follows_a_uniform_schedule_with_predictor_ODE(grou
         BatchedCartPoleExperiment(eng, seed=7).run_schedule(b, graph=True)              # a graph replays one mass
     eng.set_pole_mass(0.087)
     v0 = MPPIEngine(E, MPPIConfig(num_rollouts=N, mpc_horizon=H))
-    assert ScheduleRun(v0, b, 7).m_ctrl is None                                          # predictor_ODE_v0 never reads the attribute
+    assert ScheduleRun(v0, b, 7).mass.values is None                                    # predictor_ODE_v0 never reads the attribute
     v0.close()
     if groups > 1:
         eg.close()
