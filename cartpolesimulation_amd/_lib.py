@@ -30,7 +30,11 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_groups_stream", "cpmppi_groups_fork", "cpmppi_groups_join", "cpmppi_groups_run", "cpmppi_groups_last_error",
            "cpmppi_comm_set_stamped", "cpmppi_groups_comm_init", "cpmppi_groups_run_gather", "cpmppi_set_pole_mass_rows",
            "cpmppi_rpgd_reserve", "cpmppi_rpgd_step", "cpmppi_cem_reserve", "cpmppi_cem_step", "cpmppi_rollout_cost_gru",
-           "cpmppi_rollout_cost_grad_gru", "cpmppi_gru_advance", "cpmppi_gru_washout", "cpmppi_brunton")
+           "cpmppi_rollout_cost_grad_gru", "cpmppi_gru_advance", "cpmppi_gru_washout", "cpmppi_brunton",
+           "cpmppi_score_runs", "cpmppi_set_tuning_rows")
+TUNING_ROW_FLOATS, TUNING_LBD, TUNING_SIGMA = 16, 7, 8
+SCORE_FLOATS = 5
+SCORE_COLUMNS = ("mean_abs_distance", "mean_abs_angle_deg", "mean_Q_squared", "stable_share", "first_stable_row")
 COMM_ID_BYTES, COMM_SLOTS, GATHER_STAMP_FLOATS = 128, 4, 4
 
 
@@ -85,6 +89,14 @@ class cpmppi_brunton_args(C.Structure):
     _fields_ = [("R", C.c_uint32), ("T", C.c_uint32), ("start", C.c_uint32), ("count", C.c_uint32), ("horizon", C.c_uint32),
                 ("predictor", C.c_uint32), ("states", C.c_void_p), ("Q", C.c_void_p), ("L", C.c_void_p), ("h_rows", C.c_void_p),
                 ("stats_out", C.c_void_p), ("pred_out", C.c_void_p)]
+
+
+class cpmppi_score_args(C.Structure):
+    _fields_ = [("E", C.c_uint32), ("row_envs", C.c_uint32), ("rows", C.c_uint32), ("first_row", C.c_uint32), ("last_row", C.c_uint32),
+                ("q_rows", C.c_uint32), ("q_first", C.c_uint32), ("q_last", C.c_uint32), ("save_every", C.c_uint32),
+                ("sched_stride", C.c_uint32), ("sched_rows", C.c_uint64), ("states", C.c_void_p),
+                ("target_position_table", C.c_void_p), ("target_position", C.c_void_p), ("target_position_value", C.c_float),
+                ("Q", C.c_void_p), ("score_out", C.c_void_p)]
 
 
 class cpmppi_gru_model(C.Structure):
@@ -165,6 +177,7 @@ def load():
     lib.cpmppi_set_cost_weights.argtypes = [vp, u32, C.POINTER(f), u32]
     lib.cpmppi_set_pole_mass.argtypes = [vp, f]
     lib.cpmppi_set_pole_mass_rows.argtypes = [vp, vp, u32]
+    lib.cpmppi_set_tuning_rows.argtypes = [vp, vp, u32]
     lib.cpmppi_sample.argtypes = [vp, u32, u64, u64, u32, vp, vp, vp]
     lib.cpmppi_interpolate.argtypes = [vp, u32, vp, vp, vp]
     lib.cpmppi_predict.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
@@ -181,6 +194,7 @@ def load():
     lib.cpmppi_gru_advance.argtypes = [vp, u32, vp, vp, vp, vp]
     lib.cpmppi_gru_washout.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
     lib.cpmppi_brunton.argtypes = [vp, C.POINTER(cpmppi_brunton_args), vp]
+    lib.cpmppi_score_runs.argtypes = [vp, C.POINTER(cpmppi_score_args), vp]
     lib.cpmppi_rollout_cost.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost_gru.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost_grad_gru.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -159,6 +159,35 @@ def legacy_mppi_config(**kw):
     return MPPIConfig(**base)
 
 
+TUNING_COLUMNS = tuple(COST_WEIGHTS["quadratic_boundary_grad_minimal"][1]) + ("LBD", "SQRTRHOINV")
+
+
+def tuning_rows(mppi: MPPIConfig, E, **columns):
+    """The per-env controller tuning of ``MPPIEngine.set_tuning_rows`` -> float32 [E, 16]: a row holds the seven entries of
+    quadratic_boundary_grad_minimal's cost vector in cost_vector's order, LBD and sigma = SQRTRHOINV / sqrt(mpc_timestep), and zero
+    padding.  Every named column - a key of that cost's COST_WEIGHTS list, ``LBD`` or ``SQRTRHOINV`` - is one value per env (or a
+    scalar for all); the others take the configuration's value."""
+    if mppi.cost_function_specification != "quadratic_boundary_grad_minimal":
+        raise ValueError("tuning rows hold the cost vector of quadratic_boundary_grad_minimal, not "
+                         f"{mppi.cost_function_specification!r}")
+    unknown = [k for k in columns if k not in TUNING_COLUMNS]
+    if unknown:
+        raise ValueError(f"unknown tuning column(s) {', '.join(map(repr, unknown))}; available: {', '.join(TUNING_COLUMNS)}")
+    E = int(E)
+    _, w = cost_vector(mppi.cost_function_specification, mppi.cost_weights)
+    rows = np.zeros((E, L.TUNING_ROW_FLOATS), np.float32)
+    for i, (name, default) in enumerate(zip(TUNING_COLUMNS, list(w[:7]) + [mppi.LBD, mppi.SQRTRHOINV])):
+        col = np.asarray(columns.get(name, default), np.float64)
+        if col.ndim > 1 or (col.ndim == 1 and col.shape[0] != E):
+            raise ValueError(f"tuning column {name!r} must be a scalar or one value per env ({E}), got shape {col.shape}")
+        if name == "SQRTRHOINV":                       # the sampler's knot std-dev, formed as MPPIConfig.sigma forms it
+            col = col * (1 / np.sqrt(mppi.mpc_timestep))
+        rows[:, i] = col
+    if not (rows[:, L.TUNING_LBD] > 0).all():
+        raise ValueError("LBD must be positive in every row")
+    return rows
+
+
 def build_c_config(E, mppi: MPPIConfig, phys: PhysicalParameters = None):
     phys = phys or PhysicalParameters()
     c = L.cpmppi_config()

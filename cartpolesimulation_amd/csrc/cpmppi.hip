@@ -7,11 +7,12 @@
 //                                         here by launch_rollout) one lane = R rollouts, 6-float state + held control + running
 //                                         cost in VGPRs; per-env data wave-uniform (SGPR); block-level soft-min partials
 //                                         {min S, sum e, sum e*du[.]}; the env's last block finalizes in-kernel.
-//   fold_env_kernel                       per-env constants of the throughput build, in front of each of its launches.
+//   fold_env_kernel / fold_env_tuned_kernel  per-env constants of the throughput build, in front of each of its launches.
 //   finalize_kernel<KNOT_SPACE>           merges the per-block partials of one env (rescaled to the env-wide minimum),
 //                                         applies shift / update / clip, writes u_nom and Q (launches without the fused finalize).
+//   finalize_tuned_kernel                 ... of a launch with per-env tuning rows: the soft-min's LBD from the env's row.
 //   bump_counter_kernel                   advances a device-resident Philox step counter.
-// Entry points: cpmppi_create / _destroy / _get_config / _set_cost_weights / _set_pole_mass / _set_pole_mass_rows / _last_error / _last_launch /
+// Entry points: cpmppi_create / _destroy / _get_config / _set_cost_weights / _set_pole_mass / _set_pole_mass_rows / _set_tuning_rows / _last_error / _last_launch /
 // _version / _abi_version; cpmppi_step / _step_gather / _step_host; cpmppi_set_profiling / _get_profile,
 // cpmppi_debug_host_times; cpmppi_stream_create / _destroy.
 #include <hip/hip_runtime.h>
@@ -49,6 +50,9 @@ CPMPPI_ODE_LONE_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE)
 CPMPPI_ODE_LATENCY_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE_ROWS)
 CPMPPI_ODE_THROUGHPUT_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE_ROWS)
 CPMPPI_ODE_LONE_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE_ROWS)
+CPMPPI_TUNED_LATENCY_INSTANCES(CPMPPI_DECLARE_ROLLOUT_TUNED)
+CPMPPI_TUNED_MID_INSTANCES(CPMPPI_DECLARE_ROLLOUT_TUNED)
+CPMPPI_TUNED_THROUGHPUT_INSTANCES(CPMPPI_DECLARE_ROLLOUT_TUNED)
 }  // namespace cpmppi_k
 // ... and the same lists generate the launcher's lookup (find_rollout_kernel): one case per declared instantiation
 #define CPMPPI_MATCH_ROLLOUT(COST, FAST, NOISE, R, V) \
@@ -57,6 +61,8 @@ CPMPPI_ODE_LONE_INSTANCES(CPMPPI_DECLARE_ROLLOUT_ODE_ROWS)
   case rollout_key(COST, FAST, NOISE, R, V, PREDICTOR_ODE): return &rollout_cost_kernel<COST, FAST, NOISE, R, V, PREDICTOR_ODE>;
 #define CPMPPI_MATCH_ROLLOUT_ODE_ROWS(COST, FAST, NOISE, R, V) \
   case rollout_key(COST, FAST, NOISE, R, V, PREDICTOR_ODE_ROWS): return &rollout_cost_rows_kernel<COST, FAST, NOISE, R, V, PREDICTOR_ODE>;
+#define CPMPPI_MATCH_ROLLOUT_TUNED(COST, FAST, NOISE, R, V, INTEG) \
+  case rollout_key(COST, FAST, NOISE, R, V, INTEG, 1u): return &rollout_cost_tuned_kernel<COST, FAST, NOISE, R, V, INTEG>;
 
 // the launch plan's own constants (cpmppi_launch_plan.hpp includes nothing of the kernels) are the kernels'
 static_assert(cpmppi_plan::BLOCK == BLOCK && cpmppi_plan::WAVES == WAVES, "launch plan: workgroup size");
@@ -76,6 +82,16 @@ __global__ __launch_bounds__(BLOCK) void finalize_kernel(const Params p, const f
                                                          uint32_t nb, uint32_t W, const float* u_nom, float* u_nom_out,
                                                          float* __restrict__ Q_out, const GatherSync gs) {
   finalize_env<KNOT_SPACE, false>(p, partial, nb, W, u_nom, u_nom_out, Q_out, blockIdx.x, nullptr, gs);
+}
+// ... after a launch with per-env tuning rows (cpmppi_set_tuning_rows; Philox noise, hence knot space): the block partials were
+// scaled with the ROW's LBD, so the merge takes it from the row as well (with_tuning, as the fused finalize of the tuned rollout
+// kernel does).  A sibling, not an argument: finalize_kernel stays the code it was.
+__global__ __launch_bounds__(BLOCK) void finalize_tuned_kernel(const Params p, const float* __restrict__ partial,
+                                                               uint32_t nb, uint32_t W, const float* u_nom, float* u_nom_out,
+                                                               float* __restrict__ Q_out, const GatherSync gs,
+                                                               const float* tuning) {
+  const Params pe = with_tuning(p, tuning + (size_t)blockIdx.x * TUNING_ROW_FLOATS);
+  finalize_env<true, false>(pe, partial, nb, W, u_nom, u_nom_out, Q_out, blockIdx.x, nullptr, gs);
 }
 
 // advances a device-resident Philox step counter after a step that used it (stream-ordered; graph-replayable)
@@ -124,6 +140,23 @@ __global__ __launch_bounds__(BLOCK) void fold_env_kernel(const Params p, const f
   f.nearlim = __builtin_fminf(p.w[6], 1.0f) * p.THL;
   out[env] = f;
 }
+// ... and of a launch with per-env tuning rows (cpmppi_set_tuning_rows): the same folds from the launch's block with the env's
+// row in place (with_tuning_lane), so that the block holds what a handle with that row's scalars would fold.  A sibling, not a
+// flag: fold_env_kernel stays the code it was.
+__global__ __launch_bounds__(BLOCK) void fold_env_tuned_kernel(const Params p, const float* __restrict__ L, const float* __restrict__ te,
+                                                               const float* __restrict__ s0, const float* __restrict__ tuning,
+                                                               EnvFold* __restrict__ out, uint32_t envs) {
+  const uint32_t env = blockIdx.x * BLOCK + threadIdx.x;
+  if (env >= envs) return;
+  const Params q = with_tuning_lane(p, tuning + (size_t)env * TUNING_ROW_FLOATS);
+  EnvFold f;
+  f.ec = make_env_const(p, L ? L[env] : p.L_default);
+  f.qf = make_qbgm_folded_lane(q, te[env]);
+  f.cos0 = cosf(s0[(size_t)env * 6]);
+  f.inv_period = 1.0f / (float)p.period;
+  f.nearlim = __builtin_fminf(q.w[6], 1.0f) * p.THL;
+  out[env] = f;
+}
 
 // development aid (tools/variant_sweep.py, tools/dev/placement.py): the two size limits below which the straight-line builds are
 // launched and an LDS pad, overridable from the environment - in a -DCPMPPI_DEV_KNOBS build ONLY (build_variant "devknobs"), and
@@ -147,11 +180,12 @@ static void refresh_dev_knobs() {
 // The instantiation a plan names, looked up in the very lists that declare the instantiations above: the launcher cannot name a
 // kernel the rollout units do not define, and one listed in two units is a duplicate case.  NULL: no such build.
 using RolloutKernel = void (*)(const Params, const StepPtrs);
-constexpr uint32_t rollout_key(uint32_t cost, uint32_t fast, uint32_t noise, uint32_t r, uint32_t variant, uint32_t integ) {
-  return cost | fast << 2 | noise << 3 | (r - 1u) << 5 | variant << 6 | integ << 8;
+constexpr uint32_t rollout_key(uint32_t cost, uint32_t fast, uint32_t noise, uint32_t r, uint32_t variant, uint32_t integ,
+                               uint32_t tuned = 0u) {
+  return cost | fast << 2 | noise << 3 | (r - 1u) << 5 | variant << 6 | integ << 8 | tuned << 10;
 }
 RolloutKernel find_rollout_kernel(uint32_t cost, const cpmppi_plan::RolloutPlan& plan) {
-  switch (rollout_key(cost, plan.fast, plan.noise, plan.rpl, plan.variant, plan.integ)) {
+  switch (rollout_key(cost, plan.fast, plan.noise, plan.rpl, plan.variant, plan.integ, plan.tuned ? 1u : 0u)) {
     CPMPPI_LATENCY_INSTANCES(CPMPPI_MATCH_ROLLOUT)
     CPMPPI_LATENCY_BUFFER_INSTANCES(CPMPPI_MATCH_ROLLOUT)
     CPMPPI_MID_INSTANCES(CPMPPI_MATCH_ROLLOUT)
@@ -163,6 +197,9 @@ RolloutKernel find_rollout_kernel(uint32_t cost, const cpmppi_plan::RolloutPlan&
     CPMPPI_ODE_LATENCY_INSTANCES(CPMPPI_MATCH_ROLLOUT_ODE_ROWS)
     CPMPPI_ODE_THROUGHPUT_INSTANCES(CPMPPI_MATCH_ROLLOUT_ODE_ROWS)
     CPMPPI_ODE_LONE_INSTANCES(CPMPPI_MATCH_ROLLOUT_ODE_ROWS)
+    CPMPPI_TUNED_LATENCY_INSTANCES(CPMPPI_MATCH_ROLLOUT_TUNED)
+    CPMPPI_TUNED_MID_INSTANCES(CPMPPI_MATCH_ROLLOUT_TUNED)
+    CPMPPI_TUNED_THROUGHPUT_INSTANCES(CPMPPI_MATCH_ROLLOUT_TUNED)
     default: return nullptr;
   }
 }
@@ -175,7 +212,7 @@ int fail(cpmppi_handle* h, int code, const std::string& msg) {
 }
 
 cpmppi_plan::RolloutPlan plan_launch(const cpmppi_handle* h, uint32_t E, uint32_t noise_kind) {
-  return cpmppi_plan::plan_rollout(h->cfg, h->prm.P, E, noise_kind, h->m_pole_rows != nullptr, g_knobs.limits);
+  return cpmppi_plan::plan_rollout(h->cfg, h->prm.P, E, noise_kind, h->m_pole_rows != nullptr, g_knobs.limits, h->tuning_rows != nullptr);
 }
 
 int launch_rollout(cpmppi_handle* h, const Params& prm, const cpmppi_plan::RolloutPlan& plan, hipStream_t s, const StepPtrs& a_in) {
@@ -183,11 +220,18 @@ int launch_rollout(cpmppi_handle* h, const Params& prm, const cpmppi_plan::Rollo
   if (!kernel)
     return fail(h, CPMPPI_ERR_BAD_ARG, "launch_rollout: no build of the rollout kernel for cost " + std::to_string(prm.cost_id) +
                 ", FAST " + std::to_string(plan.fast) + ", noise " + std::to_string(plan.noise) + ", R " + std::to_string(plan.rpl) +
-                ", variant " + std::to_string(plan.variant) + ", predictor " + std::to_string(plan.integ));
+                ", variant " + std::to_string(plan.variant) + ", predictor " + std::to_string(plan.integ) +
+                (plan.tuned ? ", tuning rows" : ""));
   StepPtrs a = a_in;
   a.env_fold = h->env_fold;
   a.m_pole = h->m_pole_rows;                       // (NULL on every predictor_ODE_v0 handle: cpmppi_set_pole_mass_rows refuses those)
-  if (plan.fold_first) {
+  if (plan.tuned) a.tuning = h->tuning_rows;       // (the slot of m_pole: cpmppi_set_tuning_rows and _set_pole_mass_rows exclude each other)
+  if (plan.fold_first && plan.tuned) {
+    const uint32_t envs = plan.blocks / plan.nb;
+    hipLaunchKernelGGL(fold_env_tuned_kernel, dim3((envs + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, prm, a.L, a.te, a.s0, a.tuning,
+                       h->env_fold, envs);
+    CPMPPI_HIP(h, hipGetLastError());
+  } else if (plan.fold_first) {
     const uint32_t envs = plan.blocks / plan.nb;
     hipLaunchKernelGGL(fold_env_kernel, dim3((envs + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, s, prm, a.L, a.te, a.s0, h->env_fold, envs);
     CPMPPI_HIP(h, hipGetLastError());
@@ -225,6 +269,16 @@ int check_step(cpmppi_handle* h, const cpmppi_step_args* a) {
   // (every check that can fail comes BEFORE the event recorder is touched: a failed step must not leave a half-recorded
   // bracket behind for cpmppi_get_profile)
   if (a->predictor > CPMPPI_PREDICTOR_GRU) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_step: unknown predictor");
+  if (h->tuning_rows) {                            // cpmppi_set_tuning_rows: the fused ODE step with in-kernel Philox noise reads them
+    if (a->predictor == CPMPPI_PREDICTOR_GRU)
+      return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_step: per-env tuning rows are registered (cpmppi_set_tuning_rows): not with the GRU predictor");
+    if (a->noise_kind != CPMPPI_NOISE_PHILOX)
+      return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_step: per-env tuning rows are registered (cpmppi_set_tuning_rows): the noise must be "
+                                         "CPMPPI_NOISE_PHILOX (a row holds the sampler's sigma)");
+    if (a->E > h->tuning_rows_n)
+      return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_step: " + std::to_string(a->E) + " envs, but cpmppi_set_tuning_rows registered " +
+                                         std::to_string(h->tuning_rows_n) + " rows");
+  }
   if (a->predictor == CPMPPI_PREDICTOR_GRU) {
     if (!h->gru_image) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_step: predictor GRU requested but no model set (cpmppi_set_gru)");
     if ((h->prm.cost_id != CPMPPI_COST_QBGM && h->prm.cost_id != CPMPPI_COST_DEFAULT) || h->prm.qb_mode != 0u)
@@ -322,8 +376,12 @@ int step_impl(cpmppi_handle* h, const cpmppi_step_args* a, void* stream, uint32_
   if (separate_finalize) {
     const bool du_space = (a->noise_kind == CPMPPI_NOISE_DELTA_U || a->noise_kind == CPMPPI_NOISE_DELTA_U_TILED);
     const auto finalize = du_space ? finalize_kernel<false> : finalize_kernel<true>;
-    hipLaunchKernelGGL(finalize, dim3(a->E), dim3(BLOCK), 0, s, h->prm, (const float*)h->workspace, p.nb, p.W,
-                       (const float*)a->u_nom, p.u_nom_out, a->Q_out, p.gs);
+    if (!gru && plan.tuned)                        // (check_step: Philox noise, and rows for every env of the launch)
+      hipLaunchKernelGGL(finalize_tuned_kernel, dim3(a->E), dim3(BLOCK), 0, s, h->prm, (const float*)h->workspace, p.nb, p.W,
+                         (const float*)a->u_nom, p.u_nom_out, a->Q_out, p.gs, h->tuning_rows);
+    else
+      hipLaunchKernelGGL(finalize, dim3(a->E), dim3(BLOCK), 0, s, h->prm, (const float*)h->workspace, p.nb, p.W,
+                         (const float*)a->u_nom, p.u_nom_out, a->Q_out, p.gs);
   }
   CPMPPI_HIP(h, hipGetLastError());
   if (p.offset_dev) {
@@ -436,6 +494,9 @@ int cpmppi_set_cost_weights(cpmppi_handle* h, uint32_t cost_id, const float* cos
   const bool qb = cost_id == CPMPPI_COST_QB || cost_id == CPMPPI_COST_QB_NONCONVEX;
   if (qb && h->cfg.ode_predictor != CPMPPI_ODE_V0)
     return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_cost_weights: quadratic_boundary / _nonconvex are built for predictor_ODE_v0");
+  if (h->tuning_rows && cost_id != CPMPPI_COST_QBGM)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_cost_weights: per-env tuning rows are registered (cpmppi_set_tuning_rows), which "
+                                       "hold the cost vector of quadratic_boundary_grad_minimal");
   h->cfg.cost_id = cost_id;
   set_kernel_cost(h->prm, cost_id);
   for (uint32_t i = 0; i < n; ++i) h->cfg.cost_w[i] = h->prm.w[i] = cost_w[i];
@@ -459,6 +520,9 @@ int cpmppi_set_pole_mass_rows(cpmppi_handle* h, const float* m_pole, uint32_t n)
     h->m_pole_rows_n = 0;
     return CPMPPI_OK;
   }
+  if (h->tuning_rows)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_pole_mass_rows: per-env tuning rows are registered (cpmppi_set_tuning_rows); "
+                                       "the two are not built to be combined");
   if (h->cfg.ode_predictor != CPMPPI_ODE_CROMER)
     return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_pole_mass_rows: predictor_ODE_v0 does not read the pole mass attribute "
                                        "(a per-row mass needs ode_predictor = CPMPPI_ODE_CROMER)");
@@ -468,6 +532,25 @@ int cpmppi_set_pole_mass_rows(cpmppi_handle* h, const float* m_pole, uint32_t n)
   // with a copy node in front) may rewrite the array between launches without calling this again
   h->m_pole_rows = m_pole;
   h->m_pole_rows_n = n;
+  return CPMPPI_OK;
+}
+
+int cpmppi_set_tuning_rows(cpmppi_handle* h, const float* rows, uint32_t n) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!rows) {                                     // back to the handle's scalars
+    h->tuning_rows = nullptr;
+    h->tuning_rows_n = 0;
+    return CPMPPI_OK;
+  }
+  const auto refuse = [&](const char* why) { return fail(h, CPMPPI_ERR_BAD_ARG, std::string("cpmppi_set_tuning_rows: ") + why); };
+  if (h->cfg.cost_id != CPMPPI_COST_QBGM) return refuse("a row holds the cost vector of quadratic_boundary_grad_minimal: the handle has another cost plugin");
+  if (h->m_pole_rows) return refuse("per-row pole masses are registered (cpmppi_set_pole_mass_rows); the two are not built to be combined");
+  if (n == 0) return refuse("n must be > 0 with a non-null array");
+  if ((reinterpret_cast<uintptr_t>(rows) & (CPMPPI_TUNING_ROW_FLOATS * sizeof(float) - 1u)) != 0)
+    return refuse("misaligned pointer (rows are 64 bytes and 64-byte aligned)");
+  // only the POINTER is taken (as cpmppi_set_pole_mass_rows): the kernels of every later launch read the values when they run
+  h->tuning_rows = rows;
+  h->tuning_rows_n = n;
   return CPMPPI_OK;
 }
 

@@ -218,7 +218,8 @@ int run_impl(cpmppi_groups* g, const cpmppi_step_args* step, const cpmppi_plant_
   // not discovered in the middle of a period whose other launches are already out.
   for (size_t i = 0; i < g->g.size(); ++i) {
     cpmppi_handle* h = g->g[i].h;
-    int rc = step ? check_step(h, &sa[i]) : CPMPPI_OK;
+    int rc = refuse_tuning_rows(h, "cpmppi_groups_run");       // (a group's rows would have to be offset like its pole masses)
+    if (rc == CPMPPI_OK && step) rc = check_step(h, &sa[i]);
     if (rc == CPMPPI_OK && plant && periods) {
       cpmppi_plant_args last = pa[i];
       last.period = plant->period + (periods - 1u);

@@ -354,6 +354,7 @@ extern "C" {
 int cpmppi_rollout_cost_gru(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs, const float* target_position,
                             const float* target_equilibrium, const float* h0, float* S_out, void* stream) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (const int rc = refuse_tuning_rows(h, "cpmppi_rollout_cost_gru")) return rc;      // (before the model is looked for, as cpmppi_step)
   if (const int rc = gru_refusal(h, "cpmppi_rollout_cost_gru", E != 0 && E <= h->cfg.E, "E out of range",
                                  s0 && inputs && target_position && target_equilibrium && S_out,
                                  "s0, inputs, target_position, target_equilibrium, S_out are required", true)) return rc;
@@ -372,6 +373,7 @@ int cpmppi_rollout_cost_grad_gru(cpmppi_handle* h, uint32_t E, const float* s0, 
                                  const float* target_equilibrium, const float* h0, float* S_out, float* grad_out, void* stream) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
   const char* who = "cpmppi_rollout_cost_grad_gru";
+  if (const int rc = refuse_tuning_rows(h, who)) return rc;
   if (const int rc = gru_refusal(h, who, E != 0 && E <= h->cfg.E, "E out of range",
                                  s0 && inputs && target_position && target_equilibrium && grad_out,
                                  "s0, inputs, target_position, target_equilibrium, grad_out are required", true)) return rc;

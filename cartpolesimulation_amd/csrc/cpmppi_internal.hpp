@@ -6,6 +6,7 @@
 //   cpmppi_seams.hip      sampler, tiling, predictor, trajectory cost and reward-weighted-average seams
 //   cpmppi_plant.hip      the simulated plant (cpmppi_plant_*)
 //   cpmppi_optim.hip      cost-only rollouts, the adjoint, Adam / SGD steps and CEM
+//   cpmppi_score.hip      the score of a recording per env (cpmppi_score_runs)
 //   cpmppi_gru.hip        the GRU predictor in the optimizers: the fused MPPI step, cost-only rollouts, the gradient's forward sweep
 //   cpmppi_gru_seam.hip   its exact-cell seams: predict, advance, washout, the Brunton test's kernel
 //   cpmppi_gru_adjoint.hip  the gradient's reverse sweep
@@ -106,6 +107,8 @@ struct cpmppi_handle {
   cpmppi_comm::CommState* comm = nullptr;   // RCCL communicator + side stream of cpmppi_comm_* (cpmppi_comm.hip)
   const float* m_pole_rows = nullptr;  // cpmppi_set_pole_mass_rows: the caller's DEVICE array of per-row controller-side pole masses (predictor_ODE), or NULL
   uint32_t m_pole_rows_n = 0;          // ... and how many rows it holds
+  const float* tuning_rows = nullptr;  // cpmppi_set_tuning_rows: the caller's DEVICE array [n][CPMPPI_TUNING_ROW_FLOATS] of per-env controller tunings, or NULL
+  uint32_t tuning_rows_n = 0;          // ... and how many rows it holds
   float plant_m_pole = 0.0f;           // the pole mass of the simulated PLANT (cfg.m_pole at creation; cpmppi_set_pole_mass does not touch it)
   cpmppi_launch_info last_launch = {0, 0, 0, 0, 0, 0, 0};   // cpmppi_last_launch: the instantiation the last rollout launch used
 };
@@ -151,6 +154,15 @@ inline bool pole_mass_rows_cover(const cpmppi_handle* h, uint32_t rows) { return
 inline std::string pole_mass_rows_short(const char* who, const cpmppi_handle* h, uint32_t rows) {
   return std::string(who) + ": " + std::to_string(rows) + " rows, but cpmppi_set_pole_mass_rows registered " +
          std::to_string(h->m_pole_rows_n) + " pole masses";
+}
+
+// cpmppi_set_tuning_rows: the rows are read by the fused ODE MPPI step alone (and the finalize kernel behind it); every other entry
+// point whose kernels read the cost vector, LBD or sigma of the handle's block refuses by name while rows are registered (it would
+// silently compute with the handle's scalars): the list is in cpmppi.h.
+inline int refuse_tuning_rows(cpmppi_handle* h, const char* who) {
+  if (!h->tuning_rows) return CPMPPI_OK;
+  return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": per-env tuning rows are registered (cpmppi_set_tuning_rows), which only the "
+                                         "fused ODE cpmppi_step reads; unregister them first (NULL)");
 }
 
 // the end of an entry point that has just launched a kernel: CPMPPI_OK, or the launch's error

@@ -52,19 +52,23 @@ struct RolloutPlan {
   uint32_t nb, blocks;                  // blocks per env, grid.x
   uint32_t W, lds_bytes, stash;         // width of the weighted-sum vector, dynamic LDS, Philox knots parked in LDS
   bool fold_first;                      // fold_env_kernel runs in front (throughput build, FAST, predictor_ODE_v0)
+  bool tuned;                           // rollout_cost_tuned_kernel: the cost weights, LBD and sigma per env (cpmppi_set_tuning_rows)
 };
 
 // The plan of a launch of E envs of a handle configured as `cfg` (P = its knot count), perturbations of `noise_kind`; mass_rows:
 // a per-env pole mass is registered (predictor_ODE only: cpmppi_set_pole_mass_rows refuses predictor_ODE_v0 handles).
 // A cost-only launch (cpmppi_rollout_cost) is noise_kind = CPMPPI_NOISE_DELTA_U: W = H, nothing parked.
+// tuning_rows: per-env tuning rows are registered (cpmppi_set_tuning_rows) - the same build, block split and LDS, from the tuned
+// kernel's table (and, in front of the throughput build, the fold kernel that folds from the rows).
 //   one rollout per lane : latency build while small, throughput build above
 //   two rollouts per lane: predictor_ODE_v0: mid-size build - variant 3 while the launch has at most one wave per SIMD, variant 2
 //                          above - and the throughput build beyond; predictor_ODE has no events, hence no mid-size (phased)
 //                          build: its lone-wave form up to one wave per SIMD, the throughput build otherwise
 //   PRECISE              : one rollout per lane, throughput build, whatever cfg.rollouts_per_lane says
 inline RolloutPlan plan_rollout(const cpmppi_config& cfg, uint32_t P, uint32_t E, uint32_t noise_kind, bool mass_rows,
-                                const RolloutLimits& lim = RolloutLimits{}) {
+                                const RolloutLimits& lim = RolloutLimits{}, bool tuning_rows = false) {
   RolloutPlan r{};
+  r.tuned = tuning_rows;
   r.fast = (cfg.math_mode == CPMPPI_MATH_FAST) ? 1u : 0u;
   r.noise = noise_kind;
   r.rpl = 1;

@@ -469,6 +469,7 @@ int cpmppi_rollout_cost(cpmppi_handle* h, uint32_t E, const float* s0, const flo
   if (h->prm.cost_id == CPMPPI_COST_LEGACY)
     return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rollout_cost: plugin costs only");
   if (!pole_mass_rows_cover(h, E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_rollout_cost", h, E));
+  if (const int rc = refuse_tuning_rows(h, "cpmppi_rollout_cost")) return rc;
   CPMPPI_ON_DEVICE(h);
   Params prm = h->prm;
   prm.shift_mode = CPMPPI_SHIFT_NONE;
@@ -527,6 +528,7 @@ int cpmppi_rollout_cost_grad(cpmppi_handle* h, uint32_t E, const float* s0, cons
   const size_t lds = (size_t)h->cfg.S * 6 * BLOCK * sizeof(float);
   if (const int rc = sweep_check_handle(h, "cpmppi_rollout_cost_grad", GRAD_WORDS)) return rc;
   if (!pole_mass_rows_cover(h, E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_rollout_cost_grad", h, E));
+  if (const int rc = refuse_tuning_rows(h, "cpmppi_rollout_cost_grad")) return rc;
   if (const int rc = sweep_check_shape(h, "cpmppi_rollout_cost_grad", GRAD_WORDS, lds)) return rc;
   CPMPPI_ON_DEVICE(h);
   const size_t B = (size_t)E * h->cfg.N;
@@ -579,6 +581,7 @@ int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* a, void* stream) 
   if (const int rc = sweep_check_handle(h, "cpmppi_rpgd_step", RPGD_WORDS)) return rc;
   if (const int rc = sweep_check_shape(h, "cpmppi_rpgd_step", RPGD_WORDS, rpgd_lds_bytes(h))) return rc;
   if (!pole_mass_rows_cover(h, a->E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_rpgd_step", h, a->E));
+  if (const int rc = refuse_tuning_rows(h, "cpmppi_rpgd_step")) return rc;
   CPMPPI_ON_DEVICE(h);
   hipStream_t s = (hipStream_t)stream;
   if (h->rpgd_ws_floats < rpgd_floats(h, a->E)) {
@@ -635,6 +638,7 @@ int cpmppi_cem_step(cpmppi_handle* h, const cpmppi_cem_args* a, void* stream) {
   if (const int rc = sweep_check_handle(h, "cpmppi_cem_step", CEM_WORDS)) return rc;
   if (const int rc = sweep_check_shape(h, "cpmppi_cem_step", CEM_WORDS, cem_lds_bytes(h, refine))) return rc;
   if (!pole_mass_rows_cover(h, a->E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_cem_step", h, a->E));
+  if (const int rc = refuse_tuning_rows(h, "cpmppi_cem_step")) return rc;
   CPMPPI_ON_DEVICE(h);
   hipStream_t s = (hipStream_t)stream;
   if (h->cem_ws_floats < cem_floats(h, a->E, refine)) {

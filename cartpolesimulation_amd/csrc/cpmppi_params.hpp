@@ -96,6 +96,34 @@ __device__ __forceinline__ Params with_pole_mass(const Params& p, float m_pole) 
   return q;
 }
 
+// The per-env controller tuning (cpmppi_set_tuning_rows): one row of TUNING_ROW_FLOATS per env - the seven entries of
+// quadratic_boundary_grad_minimal's cost vector in cpmppi_set_cost_weights order, LBD, sigma, padding to 64 bytes (a row's scalar
+// loads never straddle a cache line).  with_tuning: the launch's argument block with the ROW's nine values in the handle's place.
+// The copy then goes where the launch's own block went - the cost folds, the stage cost, the sampler's scale, the soft-min - so a
+// row computes, instruction for instruction, what a handle with those scalars computes (only the fields those read survive the
+// copy).  The row is read through the constant address space: wave-uniform scalar loads wherever in the kernel the copy is
+// formed (the array is read-only for the launch); uniform_ pins the values as it does everywhere else.
+constexpr uint32_t TUNING_ROW_FLOATS = 16, TUNING_LBD = 7, TUNING_SIGMA = 8;
+__device__ __forceinline__ float uniform_(float x);
+__device__ __forceinline__ Params with_tuning(const Params& p, const float* row) {
+  const __attribute__((address_space(4))) float* r = (const __attribute__((address_space(4))) float*)(uintptr_t)row;
+  Params q = p;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) q.w[i] = uniform_(r[i]);
+  q.LBD = uniform_(r[TUNING_LBD]);
+  q.sigma = uniform_(r[TUNING_SIGMA]);
+  return q;
+}
+// (`_lane`: every lane its own row - the per-env fold kernel of the throughput build)
+__device__ __forceinline__ Params with_tuning_lane(const Params& p, const float* __restrict__ row) {
+  Params q = p;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) q.w[i] = row[i];
+  q.LBD = row[TUNING_LBD];
+  q.sigma = row[TUNING_SIGMA];
+  return q;
+}
+
 // For kernels where the env (hence L) is the same for the whole wave: pin every field to an SGPR.  Field by field — the
 // first version walked the struct through a float pointer, which kept it in a 28-byte private (scratch) slot per lane:
 // 117 MB of scratch stores per 8192-env launch.

@@ -33,6 +33,10 @@ template <int COST, bool FAST, int NOISE, int R, int VARIANT, int INTEG = PREDIC
 __global__ void rollout_cost_kernel(const Params p, const StepPtrs a);
 template <int COST, bool FAST, int NOISE, int R, int VARIANT, int INTEG = PREDICTOR_ODE>
 __global__ void rollout_cost_rows_kernel(const Params p, const StepPtrs a);
+// ... and a third: rollout_cost_tuned_kernel, the cost weights, LBD and sigma read PER ENV (cpmppi_set_tuning_rows), launched only
+// while such rows are registered - quadratic_boundary_grad_minimal with Philox noise, both ODE predictors.
+template <int COST, bool FAST, int NOISE, int R, int VARIANT, int INTEG = PREDICTOR_ODE_V0>
+__global__ void rollout_cost_tuned_kernel(const Params p, const StepPtrs a);
 
 }  // namespace cpmppi_k
 
@@ -92,6 +96,7 @@ __device__ __forceinline__ Params late_params() {
 
 #define CPMPPI_ROLLOUT_KERNEL rollout_cost_kernel
 #define CPMPPI_ROLLOUT_MASS_ROWS false
+#define CPMPPI_ROLLOUT_TUNING_ROWS false
 #include "cpmppi_rollout_kernel.inc"
 #undef CPMPPI_ROLLOUT_KERNEL
 #undef CPMPPI_ROLLOUT_MASS_ROWS
@@ -100,6 +105,14 @@ __device__ __forceinline__ Params late_params() {
 #include "cpmppi_rollout_kernel.inc"
 #undef CPMPPI_ROLLOUT_KERNEL
 #undef CPMPPI_ROLLOUT_MASS_ROWS
+#undef CPMPPI_ROLLOUT_TUNING_ROWS
+#define CPMPPI_ROLLOUT_KERNEL rollout_cost_tuned_kernel
+#define CPMPPI_ROLLOUT_MASS_ROWS false
+#define CPMPPI_ROLLOUT_TUNING_ROWS true
+#include "cpmppi_rollout_kernel.inc"
+#undef CPMPPI_ROLLOUT_KERNEL
+#undef CPMPPI_ROLLOUT_MASS_ROWS
+#undef CPMPPI_ROLLOUT_TUNING_ROWS
 
 }  // namespace cpmppi_k
 #endif  // CPMPPI_ROLLOUT_DECLARATIONS_ONLY
@@ -141,6 +154,21 @@ __device__ __forceinline__ Params late_params() {
   CPMPPI_FOR_NOISES(X, true, 1, 1) CPMPPI_FOR_NOISES(X, false, 1, 1) CPMPPI_FOR_NOISES(X, true, 2, 1)
 // (two rollouts per lane in a launch of at most one wave per SIMD: the substeps as straight-line code, raised wave priority)
 #define CPMPPI_ODE_LONE_INSTANCES(X) CPMPPI_FOR_NOISES(X, true, 2, 3)
+// the tuned kernel (cpmppi_set_tuning_rows): quadratic_boundary_grad_minimal x Philox in every build the plan can select, three
+// units with the flags of the untuned units of the same builds.  X(COST, FAST, NOISE, R, VARIANT, INTEG)
+#define CPMPPI_TUNED_LATENCY_INSTANCES(X) \
+  X(COST_QBGM, true, NOISE_PHILOX, 1, 0, PREDICTOR_ODE_V0) X(COST_QBGM, true, NOISE_PHILOX, 1, 0, PREDICTOR_ODE)
+#define CPMPPI_TUNED_MID_INSTANCES(X) \
+  X(COST_QBGM, true, NOISE_PHILOX, 2, 2, PREDICTOR_ODE_V0) X(COST_QBGM, true, NOISE_PHILOX, 2, 3, PREDICTOR_ODE_V0)
+#define CPMPPI_TUNED_THROUGHPUT_INSTANCES(X)                                                                        \
+  X(COST_QBGM, true, NOISE_PHILOX, 1, 1, PREDICTOR_ODE_V0) X(COST_QBGM, false, NOISE_PHILOX, 1, 1, PREDICTOR_ODE_V0) \
+  X(COST_QBGM, true, NOISE_PHILOX, 2, 1, PREDICTOR_ODE_V0)                                                           \
+  X(COST_QBGM, true, NOISE_PHILOX, 1, 1, PREDICTOR_ODE) X(COST_QBGM, false, NOISE_PHILOX, 1, 1, PREDICTOR_ODE)       \
+  X(COST_QBGM, true, NOISE_PHILOX, 2, 1, PREDICTOR_ODE) X(COST_QBGM, true, NOISE_PHILOX, 2, 3, PREDICTOR_ODE)
+#define CPMPPI_DEFINE_ROLLOUT_TUNED(COST, FAST, NOISE, R, V, INTEG) \
+  template __global__ void rollout_cost_tuned_kernel<COST, FAST, NOISE, R, V, INTEG>(const Params, const StepPtrs);
+#define CPMPPI_DECLARE_ROLLOUT_TUNED(COST, FAST, NOISE, R, V, INTEG) \
+  extern template __global__ void rollout_cost_tuned_kernel<COST, FAST, NOISE, R, V, INTEG>(const Params, const StepPtrs);
 #define CPMPPI_DEFINE_ROLLOUT_ODE(COST, FAST, NOISE, R, V) \
   template __global__ void rollout_cost_kernel<COST, FAST, NOISE, R, V, PREDICTOR_ODE>(const Params, const StepPtrs);
 #define CPMPPI_DECLARE_ROLLOUT_ODE(COST, FAST, NOISE, R, V) \

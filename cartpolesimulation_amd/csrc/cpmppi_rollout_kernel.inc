@@ -1,10 +1,14 @@
 // cpmppi_rollout_kernel.inc - the DEFINITION of the rollout kernel, included by cpmppi_rollout.hpp once per kernel name (that header
 // documents the template arguments, declares both kernels - INTEG's default is on the declaration - and sets the two macros):
-// CPMPPI_ROLLOUT_KERNEL the function's name, CPMPPI_ROLLOUT_MASS_ROWS whether predictor_ODE's pole mass is read per env (cpmppi_set_pole_mass_rows).
+// CPMPPI_ROLLOUT_KERNEL the function's name, CPMPPI_ROLLOUT_MASS_ROWS whether predictor_ODE's pole mass is read per env (cpmppi_set_pole_mass_rows),
+// CPMPPI_ROLLOUT_TUNING_ROWS whether the cost weights, LBD and sigma are read per env (cpmppi_set_tuning_rows).
 template <int COST, bool FAST, int NOISE, int R, int VARIANT_, int INTEG>
 __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const Params p, const StepPtrs a) {
   constexpr bool MASS_ROWS = CPMPPI_ROLLOUT_MASS_ROWS;
   static_assert(!MASS_ROWS || INTEG == PREDICTOR_ODE, "only predictor_ODE reads the pole mass attribute");
+  constexpr bool TUNED = CPMPPI_ROLLOUT_TUNING_ROWS;
+  static_assert(!TUNED || (COST == COST_QBGM && NOISE == NOISE_PHILOX && !MASS_ROWS),
+                "tuning rows: quadratic_boundary_grad_minimal with in-kernel Philox noise, and not beside pole-mass rows");
   static_assert(INTEG == PREDICTOR_ODE_V0 || VARIANT_ != 2, "predictor_ODE: latency / throughput builds and the lone-wave form of the latter");
   // VARIANT_ 3 = the mid-size build for launches of at most ONE wave per SIMD: VARIANT 2 with the quiet control step's nine
   // substeps as straight-line code (a lone wave pays ~50 cycles per taken branch: C4 80.1 -> 77.4 us; with two or more waves
@@ -76,6 +80,17 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
   Params pm_;
   if constexpr (MASS_ROWS) pm_ = with_pole_mass(p, uniform_(a.m_pole[env]));
   const Params& pi = MASS_ROWS ? pm_ : p;
+  // The controller's tuning per env (cpmppi_set_tuning_rows): `pq`, the block the COST FOLDS, the stage cost and the sampler's scale
+  // compute with, is the launch's with the env's row in place; the epilogue forms its own copy (`pe`), and so does the stage-only
+  // call, so that no row value stays live through the horizon loop for them.  Everywhere else `pq` is `p`.
+  // (chosen by the preprocessor, so that the other two kernels see `p` under another name and nothing else: with an unused local
+  // beside it - the form `pi` has - five untuned kernels of the throughput unit came out with other register assignments, and with
+  // a helper that takes the pointer block by reference every pole-mass-rows kernel changed)
+#if CPMPPI_ROLLOUT_TUNING_ROWS
+  const Params pq = with_tuning(p, a.tuning + (size_t)env * TUNING_ROW_FLOATS);
+#else
+  const Params& pq = p;
+#endif
   if constexpr (!ENV_FOLD) {
     const float L = a.L ? a.L[env] : p.L_default;
     ec_ = make_env_const_uniform(pi, L);
@@ -127,13 +142,13 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
   // threshold).  The flag comes out of the previous control step's last substep, whose one pair of edge compares tests
   // against this coarser limit (substep_fast); stage 0 is the initial state all rollouts share.  Other costs: the limit
   // is the edge itself and the flag is unused.
-  const QbgmFolded qf = ENV_FOLD ? qf_ : make_qbgm_folded(p, te);
+  const QbgmFolded qf = ENV_FOLD ? qf_ : make_qbgm_folded(pq, te);
   // quadratic_boundary_grad_minimal, FAST: stage cost and correction term accumulated term by term with FMAs (stage_qbgm_acc)
   constexpr bool QBGM_ACC = FAST && COST == COST_QBGM;
   // (not in the latency build: there the flag's compare -> scalar branch hand-over sits on the lone wave's critical path
   // once per control step - measured 56 -> 66 us for a single env - while the eight instructions it saves are hidden)
   constexpr bool TRACK_NEAR = FAST && COST == COST_QBGM && VARIANT != 0;
-  const float nearlim = (ENV_FOLD && TRACK_NEAR) ? nearlim_ : uniform_(TRACK_NEAR ? __builtin_fminf(p.w[6], 1.0f) * p.THL : p.THL);
+  const float nearlim = (ENV_FOLD && TRACK_NEAR) ? nearlim_ : uniform_(TRACK_NEAR ? __builtin_fminf(pq.w[6], 1.0f) * p.THL : p.THL);
   bool near = !TRACK_NEAR || !(__builtin_fabsf(s0[4]) < nearlim);
 
   // Latency build: the nominal control (and the legacy cost's previous sequence) of step k + 1 is requested while step k
@@ -187,8 +202,12 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
     // (late_params): taken from `p`, its uses stretch the fields' scalar registers past the loops, and the Philox kernel of
     // quadratic_boundary_grad, two rollouts per lane, throughput build, came out with a 20-byte scratch slot)
     Params pl_;
-    if constexpr (decltype(stage_only)::value) pl_ = late_params();
-    const Params& pc = decltype(stage_only)::value ? pl_ : p;
+    if constexpr (decltype(stage_only)::value) {
+      pl_ = late_params();
+      // (what comes back is the launch's argument as passed: the tuned kernel puts the env's row in place again)
+      if constexpr (TUNED) pl_ = with_tuning(pl_, late_step_ptrs().tuning + (size_t)env * TUNING_ROW_FLOATS);
+    }
+    const Params& pc = decltype(stage_only)::value ? pl_ : pq;
     if (secp) { asm volatile("" : "+v"(du)); CPMPPI_SEC(secp, 5, st); CPMPPI_SEC(secp, 0, st); }
     float uk, upk = 0.0f;
     if constexpr (NOMINAL_IN_LANES) {
@@ -501,8 +520,8 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
           float zq[4];
           // (a block's second Box-Muller pair is knots j + 2, j + 3: skipped when neither exists - wave-uniform)
           philox_normal_quad_upto(a.seed, step_offset, a.env_offset + env, nn, j >> 2, AS_BEFORE || j + 2u < p.P, zq);
-          z = p.sigma * zq[0];
-          z_next[i][0] = p.sigma * zq[1]; z_next[i][1] = p.sigma * zq[2]; z_next[i][2] = p.sigma * zq[3];
+          z = pq.sigma * zq[0];
+          z_next[i][0] = pq.sigma * zq[1]; z_next[i][1] = pq.sigma * zq[2]; z_next[i][2] = pq.sigma * zq[3];
         } else {
           z = (s == 1u) ? z_next[i][0] : ((s == 2u) ? z_next[i][1] : z_next[i][2]);
         }
@@ -626,6 +645,11 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
   // them at kernel entry and keeps ~20 more scalar registers live through the horizon loop, which the packed builds pay
   // for with SGPR spills (v_writelane / v_readlane) inside the loop.
   const StepPtrs la = late_step_ptrs();
+#if CPMPPI_ROLLOUT_TUNING_ROWS
+  const Params pe = with_tuning(p, la.tuning + (size_t)env * TUNING_ROW_FLOATS);      // (the soft-min's LBD, the regenerated knots' sigma)
+#else
+  const Params& pe = p;
+#endif
   // ---- per-rollout total cost ------------------------------------------------------------------------------------
   F S_total;
   if constexpr (COST == COST_LEGACY) {
@@ -657,7 +681,7 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
   float e[R], e_l = 0.0f;
 #pragma unroll
   for (int i = 0; i < R; ++i) {
-    e[i] = valid[i] ? expf((-1.0f / p.LBD) * (get(S_total, i) - m_b)) : 0.0f;
+    e[i] = valid[i] ? expf((-1.0f / pe.LBD) * (get(S_total, i) - m_b)) : 0.0f;
     e_l += e[i];
   }
   const float a_w = wave_sum(e_l);
@@ -672,7 +696,7 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
 #pragma unroll
       for (int i = 0; i < R; ++i)
         v += e[i] * (la.stash ? kstash[(j * R + i) * BLOCK]
-                             : philox_knot(a.seed, step_offset, a.env_offset + env, valid[i] ? n[i] : 0, j, p.sigma));
+                             : philox_knot(a.seed, step_offset, a.env_offset + env, valid[i] ? n[i] : 0, j, pe.sigma));
       v = wave_sum(v);
       if (lane == 0) my_bsum[j] = v;
     }
@@ -799,7 +823,7 @@ __global__ __launch_bounds__(BLOCK, MIN_WAVES) void CPMPPI_ROLLOUT_KERNEL(const 
         __hip_atomic_store(la.counter + env, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // ready for the next launch
       }
       __syncthreads();
-      finalize_env<(NOISE == NOISE_KNOTS || NOISE == NOISE_PHILOX), true>(p, la.partial, la.nb, W, la.u_nom, la.u_nom_out, la.Q_out, env, la.host_ticket, la.gs);
+      finalize_env<(NOISE == NOISE_KNOTS || NOISE == NOISE_PHILOX), true>(pe, la.partial, la.nb, W, la.u_nom, la.u_nom_out, la.Q_out, env, la.host_ticket, la.gs);
     }
   }
   CPMPPI_DBG_STAMP(3);

@@ -439,6 +439,7 @@ int cpmppi_sample(cpmppi_handle* h, uint32_t E, uint64_t seed, uint64_t offset, 
   if (const int rc = check_sampler(h, "cpmppi_sample", E, knots_out || delta_u_out, ": E out of range or no output buffer",
                                    !misaligned(knots_out) && !misaligned(delta_u_out), ": misaligned"); rc != CPMPPI_OK)
     return rc;
+  if (const int rc = refuse_tuning_rows(h, "cpmppi_sample")) return rc;       // (it would draw with the handle's sigma, not the rows')
   return launch_sample(h, E, seed, offset, env_offset, nullptr, knots_out, delta_u_out, stream);
 }
 
@@ -460,6 +461,8 @@ int cpmppi_sample_tiled(cpmppi_handle* h, uint32_t E, uint64_t seed, uint64_t of
                                    (reinterpret_cast<uintptr_t>(tiled_out) & 15u) == 0 && !misaligned(knots_in),
                                    ": tiled_out must be 16-byte aligned"); rc != CPMPPI_OK)
     return rc;
+  if (!knots_in)                                   // (given knots are only interpolated and tiled: no sigma is read)
+    if (const int rc = refuse_tuning_rows(h, "cpmppi_sample_tiled")) return rc;
   CPMPPI_ON_DEVICE(h);
   const size_t groups = (size_t)E * ((h->cfg.N + 63u) / 64u);
   hipLaunchKernelGGL(sample_tiled_kernel, dim3((unsigned)((groups + WAVES - 1) / WAVES)), dim3(BLOCK),
@@ -488,6 +491,7 @@ int cpmppi_predict(cpmppi_handle* h, uint32_t B, uint32_t horizon, const float* 
   if (misaligned(s0) || misaligned(Q) || misaligned(L) || misaligned(traj_out))
     return fail(h, CPMPPI_ERR_ALIGN, "cpmppi_predict: misaligned pointer");
   if (!pole_mass_rows_cover(h, B)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_predict", h, B));
+  if (const int rc = refuse_tuning_rows(h, "cpmppi_predict")) return rc;
   CPMPPI_ON_DEVICE(h);
   // stores staged through LDS once the launch puts more than one wave on every SIMD (below that the direct stores'
   // shorter path wins: measured 59 vs 82 us at 1024 rollouts, 416 vs 280 us at 262144)
@@ -552,6 +556,7 @@ int cpmppi_trajectory_cost(cpmppi_handle* h, uint32_t B, uint32_t horizon, const
     return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_trajectory_cost: bad argument");
   if (h->prm.cost_id == CPMPPI_COST_LEGACY && !u_nom)
     return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_trajectory_cost: legacy cost needs u_nom");
+  if (const int rc = refuse_tuning_rows(h, "cpmppi_trajectory_cost")) return rc;
   CPMPPI_ON_DEVICE(h);
   // rows per wave: one for the reference's call shape (a few thousand rollouts: spread them over the chip), up to 64
   // once there are more rows than ~8 waves per SIMD can take one each
@@ -568,6 +573,7 @@ int cpmppi_reward_weighted_average(cpmppi_handle* h, uint32_t E, const float* S,
                                    void* stream) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
   if (E == 0 || !S || !delta_u || !out) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_reward_weighted_average: bad argument");
+  if (const int rc = refuse_tuning_rows(h, "cpmppi_reward_weighted_average")) return rc;   // (the soft-min with the handle's LBD)
   CPMPPI_ON_DEVICE(h);
   hipLaunchKernelGGL(rwa_kernel, dim3(E), dim3(BLOCK), 0, (hipStream_t)stream, h->prm, S, delta_u, out);
   return launched(h);

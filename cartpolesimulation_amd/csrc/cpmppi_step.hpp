@@ -90,9 +90,14 @@ struct StepPtrs {
   GatherSync gs;
   const EnvFold* env_fold;   // [envs of this launch] per-env constants (throughput build, FAST, predictor_ODE_v0: launch_rollout fills it first;
                              // behind the fields the latency builds were tuned with: they keep their kernarg offsets)
+  union {                    // (one slot: the two registrations exclude each other, and a block that grew would move the kernel
+                             // arguments BEHIND it - the GRU kernels' - and with them those kernels' code)
   const float* m_pole;       // [envs of this launch] predictor_ODE: the pole mass each env's rollouts are integrated with
                              // (cpmppi_set_pole_mass_rows); launch_rollout fills it.  Read by rollout_cost_rows_kernel only, which is
                              // launched only when it is set
+  const float* tuning;       // [envs of this launch][TUNING_ROW_FLOATS] the per-env controller tuning (cpmppi_set_tuning_rows);
+                             // launch_rollout fills it.  Read by rollout_cost_tuned_kernel only, launched only when it is set
+  };
 };
 
 // Nominal control for stage k after the configured shift (a18).

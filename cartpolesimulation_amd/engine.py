@@ -121,6 +121,7 @@ class MPPIEngine:
     _fixed_stream = _fixed_stream_obj = None                    # use_stream: the raw handle / the torch stream (keeps it alive)
     _m_rows = _m_rows_own = None                                # set_pole_mass_rows: the registered tensor / the engine's own buffer
     _m_pole_obj = None                                          # apply_pole_mass_of: the scalar object last applied
+    _tuning = None                                              # set_tuning_rows: the registered tensor
     has_gru = False                                             # set_gru: a network is attached
 
     def __init__(self, E, mppi: MPPIConfig = None, phys: PhysicalParameters = None, device=0):
@@ -330,6 +331,25 @@ class MPPIEngine:
         if cur is None or cur.data_ptr() != t.data_ptr() or cur.numel() != t.numel():
             self._check(self.lib.cpmppi_set_pole_mass_rows(self._h, _ptr(t), t.numel()))
         self._m_rows = t
+
+    def set_tuning_rows(self, rows):
+        """cpmppi_set_tuning_rows: the controller's tuning PER ENV - quadratic_boundary_grad_minimal's seven cost entries, LBD and
+        sigma, one row of ``_lib.TUNING_ROW_FLOATS`` floats per env (``configs.tuning_rows`` packs them) - read by every later fused
+        ODE step with Philox noise where that step indexes L.  ``None``: back to the engine's configuration.  A contiguous float32
+        tensor [rows, 16] on the engine's device is registered AS IT IS - no copy; every later launch (and every replay of a
+        captured one) reads its values when it runs, so it may be rewritten in place (stream-ordered) and must outlive the
+        launches; the engine keeps a reference.  A host array is uploaded first."""
+        if rows is None:
+            if self._tuning is not None:
+                self._check(self.lib.cpmppi_set_tuning_rows(self._h, None, 0))
+                self._tuning = None
+            return None
+        t = self.tensor(rows)
+        if t.dim() != 2 or t.shape[1] != _L.TUNING_ROW_FLOATS or t.shape[0] == 0:
+            raise ValueError(f"tuning rows must be [rows, {_L.TUNING_ROW_FLOATS}] (configs.tuning_rows), got {tuple(t.shape)}")
+        self._check(self.lib.cpmppi_set_tuning_rows(self._h, _ptr(t), t.shape[0]))
+        self._tuning = t
+        return t
 
     def sample(self, seed, offset=0, env_offset=0, E=None, knots=True, delta_u=False):
         E = self.E if E is None else int(E)
@@ -647,6 +667,65 @@ class MPPIEngine:
         buffers (a benchmark loop, a capture - after one plain run, which allocates the workspace)."""
         return self._build_brunton(*args, **kwargs)
 
+    # ------------------------------------------------------------------ score of a recording, per env
+    def _build_score_runs(self, states, Q=None, *, target_position=0.0, target_position_table=None, save_every=1, sched_stride=1,
+                          period_steps=None, first_row=0, last_row=None, out=None):
+        """cpmppi_score_runs: the device loop's logs ``states`` [R,E,6] (and ``Q`` [calls,E]) scored per env where they lie
+        (include/cpmppi.h states the five numbers; ``_lib.SCORE_COLUMNS`` names them) -> ``out`` [E,5] on the device.
+        The target of saved row r: ``target_position_table`` [rows,E] (row r * save_every // sched_stride, the last one beyond the
+        end: a schedule run's table), else ``target_position``, a scalar or one value per env.  ``first_row`` / ``last_row``
+        restrict the rows scored (to drop the swing-up); the mean of Q^2 then runs over the controller calls made at those rows'
+        simulation steps, call c at step c * ``period_steps`` (None: ``save_every`` - one saved row per call, as ``run`` records)."""
+        states = self.tensor(states)
+        if states.dim() != 3 or states.shape[2] != 6 or states.shape[0] == 0 or states.shape[1] == 0:
+            raise ValueError(f"states must be [R,E,6] with R, E >= 1, got {tuple(states.shape)}")
+        R, E = states.shape[0], states.shape[1]
+        first_row, last_row = int(first_row), R if last_row is None else int(last_row)
+        if not 0 <= first_row < last_row <= R:
+            raise ValueError(f"first_row {first_row}, last_row {last_row}: a non-empty window inside the recording's {R} rows")
+        save_every, sched_stride = int(save_every), int(sched_stride)
+        period_steps = save_every if period_steps is None else int(period_steps)
+        if min(save_every, sched_stride, period_steps) < 1:
+            raise ValueError("save_every, sched_stride and period_steps are numbers of simulation steps: at least 1")
+        a = _L.cpmppi_score_args()
+        a.E, a.row_envs, a.rows, a.first_row, a.last_row = E, E, R, first_row, last_row
+        a.save_every, a.sched_stride = save_every, sched_stride
+        a.states = states.data_ptr()
+        tp = None
+        if target_position_table is not None:
+            tp = self.tensor(target_position_table)
+            if tp.dim() != 2 or tp.shape[0] == 0 or tp.shape[1] != E:
+                raise ValueError(f"target_position_table must be [rows,{E}], got {tuple(tp.shape)}")
+            a.target_position_table, a.sched_rows = tp.data_ptr(), tp.shape[0]
+        elif np.ndim(target_position) == 0 and not torch.is_tensor(target_position):
+            a.target_position_value = float(target_position)
+        else:
+            tp = self.tensor(target_position, (E,))
+            a.target_position = tp.data_ptr()
+        if Q is not None:
+            Q = self.tensor(Q)
+            if Q.dim() != 2 or Q.shape[0] == 0 or Q.shape[1] != E:
+                raise ValueError(f"Q must be [calls,{E}], got {tuple(Q.shape)}")
+            calls = Q.shape[0]
+            q_first = -(-first_row * save_every // period_steps)             # the first call at or after the window's first step
+            q_last = min(-(-last_row * save_every // period_steps), calls)
+            if q_first >= q_last:
+                raise ValueError(f"no controller call of Q's {calls} falls into rows {first_row}..{last_row - 1}")
+            a.Q, a.q_rows, a.q_first, a.q_last = Q.data_ptr(), calls, q_first, q_last
+        if out is None:
+            out = self.empty(E, _L.SCORE_FLOATS)
+        elif device_tensor("out", out, tail=(_L.SCORE_FLOATS,)).shape[0] != E:
+            raise ValueError(f"out must be [{E},{_L.SCORE_FLOATS}]")
+        a.score_out = out.data_ptr()
+        return PreparedCall(self, self.lib.cpmppi_score_runs, a, (states, Q, tp, out), out, ())
+
+    score_runs = _run_once(_build_score_runs)
+
+    def prepare_score_runs(self, *args, **kwargs):
+        """The argument block of ``score_runs(...)`` built and validated ONCE: ``.run()`` enqueues the launch again on the same
+        buffers (a captured loop that ends with its own score)."""
+        return self._build_score_runs(*args, **kwargs)
+
     # ------------------------------------------------------------------ cost-only launch and CEM (SURVEY §8f N4)
     def _per_env(self, x, E):
         x = self.tensor(x)
@@ -770,10 +849,11 @@ class MPPIEngine:
         info = _L.cpmppi_launch_info()
         self._check(self.lib.cpmppi_last_launch(self._h, C.byref(info)))
         d = {n: int(getattr(info, n)) for n, _ in info._fields_}
-        # (predictor "ODE" with a per-env pole mass registered runs the kernel's second compilation, rollout_cost_rows_kernel)
+        # (predictor "ODE" with a per-env pole mass registered runs the kernel's second compilation, rollout_cost_rows_kernel; with
+        # tuning rows registered either predictor runs the third, rollout_cost_tuned_kernel)
         rows = d["ode_predictor"] and self._m_rows is not None
         d["kernel"] = ("rollout_cost%s_kernel<%d, %s, %d, %d, %d%s>" % (
-            "_rows" if rows else "", d["cost_id"], "true" if d["math_mode"] == _L.MATH_FAST else "false", (0, 1, 2, 3)[d["noise_kind"]],
+            "_rows" if rows else ("_tuned" if self._tuning is not None else ""), d["cost_id"], "true" if d["math_mode"] == _L.MATH_FAST else "false", (0, 1, 2, 3)[d["noise_kind"]],
             d["rollouts_per_lane"], d["build_variant"], ", PREDICTOR_ODE" if d["ode_predictor"] else ""))
         return d
 

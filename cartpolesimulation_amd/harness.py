@@ -58,6 +58,19 @@ def check_predictor(engine, predictor, h0=None, optimizer=None, knots_fn=None):
     return True
 
 
+def check_tuning(tuning, optimizer=None, predictor="ODE_v0", knots_fn=None):
+    """``tuning=`` of run / run_schedule: the per-env rows (configs.tuning_rows) are read by the fused ODE MPPI step with its own
+    Philox noise - ValueError, naming the conflict, for anything else that was asked for beside them."""
+    if tuning is None:
+        return
+    if optimizer is not None:
+        raise ValueError("tuning= and optimizer=: the tuning rows are read by the fused MPPI step, not by an optimizer object")
+    if predictor == "GRU":
+        raise ValueError("tuning= and predictor='GRU': the tuning rows are read by the ODE predictors' fused MPPI step")
+    if knots_fn is not None:
+        raise ValueError("tuning= and knots_fn: a row holds the sampler's sigma, so the step draws its own Philox noise")
+
+
 def gru_memory(engine, E, h0):
     """The network's memory a run starts from: zeros [E,2,32], or a copy of ``h0`` (the run advances its own)."""
     return engine.zeros(E, 2, 32) if h0 is None else engine.tensor(h0, (E, 2, 32)).clone()
@@ -71,15 +84,20 @@ class BatchedCartPoleExperiment:
         self.seed = int(seed)
 
     def run(self, s0, n_control_steps, target_position=0.0, target_equilibrium=1.0, L=None, record=True,
-            env_offset=0, graph=False, steps_per_graph=10, predictor="ODE_v0", h0=None):
+            env_offset=0, graph=False, steps_per_graph=10, predictor="ODE_v0", h0=None, tuning=None):
         """-> dict(states[T+1,E,6], Q[T,E]) as device tensors (only if ``record``), final state, final u_nom.
+        ``tuning`` [E,16] (configs.tuning_rows): the controller's cost weights, LBD and sigma per env (MPPIEngine.set_tuning_rows),
+        registered for this run - launched or captured - and taken off the handle afterwards; the result keeps the tensor.
         ``predictor="GRU"``: the controller rolls out with the engine's network from each env's memory ``h0`` [E,2,32] (None: zeros),
         which cpmppi_gru_advance moves on every period with (state seen, control chosen) - three launches per control period; the
         result gains ``memory`` [E,2,32], the memory after the last period.  ``L`` still goes to the plant; the network knows none."""
         eng = self.engine
+        check_tuning(tuning, predictor=predictor)
         gru = check_predictor(eng, predictor, h0)
         s = eng.tensor(s0).clone()
         E = s.shape[0]
+        if tuning is not None and tuple(np.shape(tuning))[:1] != (E,):
+            raise ValueError(f"tuning must hold one row per env ({E}), got shape {tuple(np.shape(tuning))}")
         tp = eng.tensor(np.broadcast_to(np.asarray(target_position, dtype=np.float32), (E,)).copy())
         te = eng.tensor(np.broadcast_to(np.asarray(target_equilibrium, dtype=np.float32), (E,)).copy())
         Lt = None if L is None else eng.tensor(np.broadcast_to(np.asarray(L, dtype=np.float32), (E,)).copy())
@@ -106,17 +124,24 @@ class BatchedCartPoleExperiment:
                               row=t if counter is None else 0, row_dev=counter)
 
         loop = PeriodLoop(eng, n_control_steps)
-        if graph:                                              # the launch-bound case: few envs, ~70 us of GPU work per control step
-            loop.capture(period, steps_per_graph, s.device)
-        loop.enqueue_rest(period)
+        rows = None if tuning is None else eng.set_tuning_rows(tuning)
+        try:
+            if graph:                                          # the launch-bound case: few envs, ~70 us of GPU work per control step
+                loop.capture(period, steps_per_graph, s.device)
+            loop.enqueue_rest(period)
+        finally:
+            if rows is not None:                               # (a launch, and a captured one, keeps the pointer it was enqueued with)
+                eng.set_tuning_rows(None)
         res = dict(states=states, Q=Qs, final_state=s, u_nom=u_nom)
+        if rows is not None:
+            res["tuning"] = rows
         if gru:
             res["memory"] = h
         return res
 
     # ------------------------------------------------------------------ the data generator's experiments (moving targets)
     def run_schedule(self, batch, env_offset=0, graph=False, steps_per_graph=10, knots_fn=None, u_nom0=None, optimizer=None,
-                     predictor="ODE_v0", h0=None):
+                     predictor="ODE_v0", h0=None, tuning=None):
         """Run the E experiments of a schedule.ExperimentBatch to their end: CartPole.run_cartpole_random_experiment
         (CartPole/__init__.py:659-735) for all of them at once.  Per control period two launches - the fused MPPI step, reading
         the period's target position / equilibrium (/ pole length) from three [E] vectors, and cpmppi_plant_step, which advances
@@ -135,17 +160,33 @@ class BatchedCartPoleExperiment:
         from each experiment's memory ``h0`` [E,2,32] (None: zeros), cpmppi_gru_advance on (the MEASURED state the controller was
         given, the control it chose), the plant; launched or captured.  The result gains ``memory``, the memory after every
         controller call made (the final one included).  Not with ``optimizer=`` (such an object carries its own network and
-        memory) and not with ``knots_fn``."""
+        memory) and not with ``knots_fn``.
+        ``tuning`` [E,16] (configs.tuning_rows): the controller's cost weights, LBD and sigma per experiment, registered with the
+        engine for this run (launched or captured) and taken off it afterwards; the result keeps the tensor and, for
+        MPPIEngine.score_runs, the loop's device table of target positions (``target_position_table``).  Not with
+        ``optimizer=``, ``predictor="GRU"`` or ``knots_fn`` (ValueError)."""
+        check_tuning(tuning, optimizer, predictor, knots_fn)
+        if tuning is not None and tuple(np.shape(tuning))[:1] != (batch.E,):
+            raise ValueError(f"tuning must hold one row per experiment ({batch.E}), got shape {tuple(np.shape(tuning))}")
         run = ScheduleRun(self.engine, batch, self.seed, env_offset=env_offset, knots_fn=knots_fn, u_nom0=u_nom0, optimizer=optimizer,
                           predictor=predictor, h0=h0)
         if batch.dt_simulation != self.dt_simulation or batch.n_ctrl != self.n_sub:
             raise ValueError("the batch was drawn for other time scales than this experiment runner's")
         if graph and run.controller.cannot_capture:
             raise ValueError(run.controller.cannot_capture)
-        if graph and knots_fn is None and run.T > 0:
-            run.capture(steps_per_graph)
-        run.loop.enqueue_rest(run._period)
-        return run.finish()
+        rows = None if tuning is None else self.engine.set_tuning_rows(tuning)
+        try:
+            if graph and knots_fn is None and run.T > 0:
+                run.capture(steps_per_graph)
+            run.loop.enqueue_rest(run._period)
+            res = run.finish()
+        finally:
+            if rows is not None:                                # (a launch, and a captured one, keeps the pointer it was enqueued with)
+                self.engine.set_tuning_rows(None)
+        if rows is not None:
+            res["tuning"] = rows
+            res["target_position_table"] = run.buffers.plant["target_position_table"]     # (the loop's own table, for score_runs)
+        return res
 
 
 def controller_pole_mass(b, per_env=False):

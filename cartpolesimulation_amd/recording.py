@@ -208,6 +208,36 @@ def write_recordings_native(paths, block, phys, header, title=None, q_update_tim
     return list(paths)
 
 
+# ------------------------------------------------------------------------------------------------ score of a recording
+SCORE_COLUMNS = ("mean_abs_distance", "mean_abs_angle_deg", "mean_Q_squared", "stable_share", "first_stable_row")
+STABLE_ANGLE = f32(np.pi / 5.0)          # TARGET_ANGLE_UP, CartPole/CheckStabilized.py:7, compared in float32 (:24)
+
+
+def score_rows(states, target_position, Q=None, first_row=0, last_row=None, q_first=0, q_last=None):
+    """cpmppi_score_runs restated in numpy, float64: ``states`` [R,E,6], ``target_position`` [R,E] (or anything that broadcasts
+    to it: the target of every saved row), ``Q`` [calls,E] or None -> [E,5] in the order of SCORE_COLUMNS.  The first two are what
+    the reference's simulator prints after an experiment (CartPole/__init__.py:727-729), over the rows first_row <= r < last_row;
+    the mean of Q^2 over the calls q_first <= c < q_last; the share of rows with |angle| < pi / 5 and the first row from which
+    that holds to the window's end (R if the window's last row is outside it)."""
+    states = np.asarray(states)
+    R, E = states.shape[:2]
+    last_row = R if last_row is None else int(last_row)
+    rows = slice(int(first_row), last_row)
+    angle, position = states[rows, :, 0], states[rows, :, 4].astype(np.float64)
+    target = np.broadcast_to(np.asarray(target_position, np.float64), (R, E))[rows]
+    out = np.zeros((E, len(SCORE_COLUMNS)))
+    out[:, 0] = np.mean(np.abs(position - target), axis=0)
+    out[:, 1] = np.mean(np.abs(angle.astype(np.float64)), axis=0) * 180.0 / np.pi
+    if Q is not None:
+        q = np.asarray(Q, np.float64)[int(q_first):q_last]
+        out[:, 2] = np.mean(q * q, axis=0)
+    inside = np.abs(angle.astype(f32)) < STABLE_ANGLE
+    out[:, 3] = np.mean(inside, axis=0)
+    after = np.where(inside, 0, np.arange(rows.start, last_row)[:, None] + 1).max(axis=0)
+    out[:, 4] = np.where(after < last_row, np.maximum(after, rows.start), R)
+    return out
+
+
 # ------------------------------------------------------------------------------------------------ the data generator
 def dataset_paths(n, out_dir, ml_pipeline=False, split=(0.8, 0.1), secondary_experiment_index=None, digits=3):
     """The files run_data_generator gives its experiments (CartPole/data_generator.py:290-322 + csv_logger.py:61-91): all are

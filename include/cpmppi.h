@@ -56,7 +56,8 @@ extern "C" {
                                       cpmppi_rpgd_step / cpmppi_rpgd_reserve / cpmppi_rpgd_args (new entry points, likewise);
                                       cpmppi_cem_step / cpmppi_cem_reserve / cpmppi_cem_args (new entry points, likewise);
                                       cpmppi_gru_advance (a new entry point, likewise);
-                                      cpmppi_brunton / cpmppi_brunton_args, cpmppi_gru_washout (new entry points, likewise). */
+                                      cpmppi_brunton / cpmppi_brunton_args, cpmppi_gru_washout (new entry points, likewise);
+                                      cpmppi_score_runs / cpmppi_score_args, cpmppi_set_tuning_rows (new entry points, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -236,6 +237,28 @@ int cpmppi_set_pole_mass(cpmppi_handle* h, float m_pole);
  * VALUES when they run - a caller may rewrite the array between launches (stream-ordered) without calling this again.  Each handle
  * of an env group is given the array offset by the group's first env. */
 int cpmppi_set_pole_mass_rows(cpmppi_handle* h, const float* m_pole, uint32_t n);
+/* Per-env controller tuning of the fused MPPI step: rows[n][CPMPPI_TUNING_ROW_FLOATS], DEVICE pointer, caller-owned, 64-byte
+ * aligned, read by every later cpmppi_step / cpmppi_step_gather / cpmppi_step_host of this handle at the env index where that
+ * call indexes L.  A row holds the seven entries of quadratic_boundary_grad_minimal's cost vector in cpmppi_set_cost_weights
+ * order (dd_weight, db_weight, ep_weight, ekp_weight, cc_weight, R, permissible_track_fraction - the sliders of the reference's
+ * GUI/_ControllerGUI_MPPIOptionsWindow.py), then LBD ([CPMPPI_TUNING_LBD]) and sigma = SQRTRHOINV / sqrt(dt)
+ * ([CPMPPI_TUNING_SIGMA]); the other floats pad the row to 64 bytes and are not read.  The optimizer's own R, NU, cc_weight and
+ * the control limits stay the handle's.  NULL (n ignored) returns to the handle's scalars.  An env computes bit for bit what a
+ * handle whose scalars are its row computes (the same build of the rollout kernel, compiled a second time with the nine values
+ * read per env through wave-uniform loads; the throughput build's per-env fold reads the row).  Only the POINTER is taken:
+ * launches already enqueued, and captured graphs, keep the pointer they were enqueued with and read the VALUES when they run - a
+ * caller may rewrite the array between launches and between replays (stream-ordered) without calling this again.
+ * Refused (CPMPPI_ERR_BAD_ARG, "cpmppi_set_tuning_rows: ...", nothing changes): n == 0 with a non-null pointer, a misaligned
+ * pointer, a handle whose cost plugin is not quadratic_boundary_grad_minimal, a handle with pole-mass rows registered
+ * (cpmppi_set_pole_mass_rows refuses the reverse).  While rows are registered a step with more envs than n, with a noise_kind other
+ * than CPMPPI_NOISE_PHILOX or with the GRU predictor is refused (nothing launched, outputs untouched), and so are, by name,
+ * cpmppi_rollout_cost, cpmppi_rollout_cost_grad, cpmppi_rpgd_step, cpmppi_cem_step, cpmppi_predict, cpmppi_trajectory_cost,
+ * cpmppi_groups_run / _run_gather, cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru, the samplers that draw with the
+ * handle's sigma (cpmppi_sample, and cpmppi_sample_tiled without knots_in), cpmppi_reward_weighted_average, and cpmppi_set_cost_weights with another cost plugin.
+ * A handle without the fused finalize (CPMPPI_FUSE_FINALIZE=0) merges an env's block partials with the row's LBD as well. */
+#define CPMPPI_TUNING_ROW_FLOATS 16u
+enum { CPMPPI_TUNING_LBD = 7, CPMPPI_TUNING_SIGMA = 8 };
+int cpmppi_set_tuning_rows(cpmppi_handle* h, const float* rows, uint32_t n);
 
 /* a17 — device sampler: knots ~ sigma * N(0,1) from Philox4x32-10 keyed by (seed), counter (rollout, env, knot pair,
  * offset); writes knots[E,N,P] and/or the interpolated delta_u[E,N,H] (either pointer may be NULL).
@@ -360,6 +383,47 @@ typedef struct {
   float* pred_out;               /* [R*count,horizon+1,6] or NULL */
 } cpmppi_brunton_args;
 int cpmppi_brunton(cpmppi_handle* h, const cpmppi_brunton_args* args, void* stream);
+
+/* Score of a recording, per env, reduced on the device: the two numbers the reference's simulator prints after every experiment
+ * (CartPole/__init__.py:727-729) and three more, from the device loop's logs where they lie (cpmppi_plant_step /
+ * cpmppi_plant_advance_record: states_log, the target-position table, Q_log).  Over the saved rows r of the window
+ * first_row <= r < last_row (last_row = 0: rows) it writes score_out[env][CPMPPI_SCORE_FLOATS]:
+ *   [CPMPPI_SCORE_MEAN_ABS_DISTANCE]   mean |position - target_position|                                  (:727)
+ *   [CPMPPI_SCORE_MEAN_ABS_ANGLE_DEG]  mean |angle| * 180 / pi                                            (:728)
+ *   [CPMPPI_SCORE_MEAN_Q_SQUARED]      mean Q^2 over the controller calls q_first <= c < q_last (q_last = 0: q_rows); 0 without Q
+ *   [CPMPPI_SCORE_STABLE_SHARE]        the share of the window's rows with |angle| < pi / 5, compared in float32 as the reference
+ *                                      compares (TARGET_ANGLE_UP, CartPole/CheckStabilized.py:7,24)
+ *   [CPMPPI_SCORE_FIRST_STABLE_ROW]    the first saved row of the window from which |angle| < pi / 5 holds to the window's end,
+ *                                      `rows` if the window's last row is outside that angle (a NaN angle is outside it)
+ * The target of saved row r: row min(r * save_every / sched_stride, sched_rows - 1) of target_position_table (the rule of
+ * cpmppi_plant_step; save_every, sched_stride 0 = 1), else target_position[env], else the scalar target_position_value.
+ * Every term is formed and summed in float64 - rows r = first_row + w, + w + W, ... by wave w of the W waves of a workgroup, the
+ * waves' sums added in wave order through LDS - and rounded to float32 once: no atomics, the same bits from run to run.  Lanes
+ * run along envs (the logs are env-contiguous).  ONE launch on `stream` for any E and rows, no allocation, no host synchronisation:
+ * can be captured.  Reads no configuration of the handle (its device and error text only).
+ * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned ("cpmppi_score_runs: ...") for a NULL states or score_out; E or rows == 0;
+ * row_envs != 0 and < E; an empty or reversed window, or one that ends beyond rows (likewise Q's against q_rows); a table without
+ * sched_rows; more than 2^24 rows.  A misaligned pointer is CPMPPI_ERR_ALIGN. */
+#define CPMPPI_SCORE_FLOATS 5u
+enum { CPMPPI_SCORE_MEAN_ABS_DISTANCE = 0, CPMPPI_SCORE_MEAN_ABS_ANGLE_DEG = 1, CPMPPI_SCORE_MEAN_Q_SQUARED = 2,
+       CPMPPI_SCORE_STABLE_SHARE = 3, CPMPPI_SCORE_FIRST_STABLE_ROW = 4 };
+typedef struct {
+  uint32_t E;                           /* envs scored */
+  uint32_t row_envs;                    /* envs per ROW of the logs and the table (0 = E), as in cpmppi_plant_args */
+  uint32_t rows;                        /* saved rows of states */
+  uint32_t first_row, last_row;         /* the window of saved rows; last_row 0 = rows */
+  uint32_t q_rows;                      /* rows of Q (controller calls) */
+  uint32_t q_first, q_last;             /* the window of controller calls; q_last 0 = q_rows */
+  uint32_t save_every, sched_stride;    /* simulation steps per saved row / per table row */
+  uint64_t sched_rows;                  /* rows of target_position_table */
+  const float* states;                  /* [rows][row_envs][6] */
+  const float* target_position_table;   /* [sched_rows][row_envs], or NULL */
+  const float* target_position;         /* [E] without a table, or NULL */
+  float target_position_value;          /* the target without either */
+  const float* Q;                       /* [q_rows][row_envs], or NULL */
+  float* score_out;                     /* [E][CPMPPI_SCORE_FLOATS] */
+} cpmppi_score_args;
+int cpmppi_score_runs(cpmppi_handle* h, const cpmppi_score_args* args, void* stream);
 
 /* Rollout + cost only (no update): per-rollout trajectory cost S[E,N] of GIVEN input sequences inputs[E,N,H] under the
  * handle's plugin cost — cost_function.get_trajectory_cost(predictor.predict_core(s, Q), Q) fused; the building block of

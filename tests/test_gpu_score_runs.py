@@ -1,0 +1,145 @@
+"""GPU: cpmppi_score_runs - the score of a recording per env, reduced on the device - on the logs of ONE recorded closed-loop run
+(70 envs, 1031 rows: shared by every case, never modified), sliced to one env / one row / a ragged second workgroup, with a scalar
+target, a target per env and a schedule table, with and without a window; and on a hand-made history for the stabilisation test.
+
+Bound of the four means: rows * 2^-24 relative to the sum of the absolute terms - the bound of a float32 summation of `rows` terms
+(the kernel sums in float64 and rounds once, so it sits at one rounding); the terms are non-negative, so the sum of their absolute
+values is the sum itself and the bound reads rows * 2^-24 * mean.  The first stable row is exact; two runs give the same bits."""
+import ctypes as C
+
+import numpy as np
+import pytest
+
+pytestmark = pytest.mark.gpu
+
+torch = pytest.importorskip("torch")
+
+from cartpolesimulation_amd import _lib as L  # noqa: E402
+from cartpolesimulation_amd.recording import STABLE_ANGLE, score_rows  # noqa: E402
+
+f32 = np.float32
+E_ALL, ROWS_ALL = 70, 1031
+
+
+@pytest.fixture(scope="module")
+def eng():
+    from cartpolesimulation_amd.engine import MPPIEngine
+    from cartpolesimulation_amd.configs import MPPIConfig
+    return MPPIEngine(E_ALL, MPPIConfig(num_rollouts=64, mpc_horizon=10))
+
+
+@pytest.fixture(scope="module")
+def run(eng):
+    """One launched device loop of 1030 control periods: states [1031,70,6], Q [1030,70] on the device, the per-env targets."""
+    from cartpolesimulation_amd.harness import BatchedCartPoleExperiment, generate_random_initial_states
+    rng = np.random.default_rng(7)
+    s0 = generate_random_initial_states(E_ALL, rng)
+    target = rng.uniform(-0.1, 0.1, E_ALL).astype(f32)
+    res = BatchedCartPoleExperiment(eng, seed=3).run(s0, ROWS_ALL - 1, target_position=target)
+    torch.cuda.synchronize()
+    return dict(states=res["states"], Q=res["Q"], target=target, states_np=res["states"].cpu().numpy(), Q_np=res["Q"].cpu().numpy())
+
+
+def check(got, ref, rows, q_rows):
+    got = got.cpu().numpy().astype(np.float64)
+    for col, n in ((0, rows), (1, rows), (2, q_rows), (3, rows)):
+        err, bound = np.abs(got[:, col] - ref[:, col]), n * 2.0 ** -24 * np.abs(ref[:, col])
+        print(f"{L.SCORE_COLUMNS[col]}: max error {err.max():.3e}, bound there {bound[err.argmax()]:.3e}")
+        assert np.all(err <= bound), (L.SCORE_COLUMNS[col], err.max())
+    assert np.array_equal(got[:, 4], ref[:, 4])
+
+
+@pytest.mark.parametrize("E", [1, E_ALL])
+@pytest.mark.parametrize("R", [1, 257, ROWS_ALL])
+def test_score_of_a_recorded_run(eng, run, E, R):
+    states, tgt = run["states"][:R, :E].contiguous(), run["target"][:E]
+    Q = run["Q"][:max(R - 1, 1), :E].contiguous()                         # (R rows were saved by R - 1 controller calls)
+    calls = Q.shape[0]
+    got = eng.score_runs(states, Q, target_position=tgt)
+    assert got.shape == (E, L.SCORE_FLOATS)
+    check(got, score_rows(run["states_np"][:R, :E], tgt, run["Q_np"][:calls, :E]), R, calls)
+    assert torch.equal(got, eng.score_runs(states, Q, target_position=tgt))          # the same bits from run to run
+    # a scalar target (the device's is a float32, like the controller's), no Q
+    got = eng.score_runs(states, target_position=0.05)
+    ref = score_rows(run["states_np"][:R, :E], f32(0.05))
+    check(got, ref, R, 1)
+    assert torch.all(got[:, 2] == 0)
+    if R < 3:
+        return
+    # a window that drops the first third and the last row: the calls made at its rows
+    a, b = R // 3, R - 1
+    got = eng.score_runs(states, Q, target_position=tgt, first_row=a, last_row=b)
+    check(got, score_rows(run["states_np"][:R, :E], tgt, run["Q_np"][:calls, :E], a, b, a, b), b - a, b - a)
+
+
+def test_target_table_with_the_schedule_s_strides(eng, run):
+    """Saved every 3 simulation steps, a table row every 2, the table shorter than the run: row min(3 r // 2, rows - 1); calls every 6."""
+    R, E = 257, E_ALL
+    states = run["states"][:R].contiguous()
+    Q = run["Q"][:129].contiguous()
+    table = np.random.default_rng(1).uniform(-0.15, 0.15, (300, E)).astype(f32)
+    rows = np.minimum(np.arange(R) * 3 // 2, 299)
+    got = eng.score_runs(states, Q, target_position_table=table, save_every=3, sched_stride=2, period_steps=6)
+    check(got, score_rows(run["states_np"][:R], table[rows], run["Q_np"][:129]), R, 129)
+    # window rows 10..199 = simulation steps 30..597: the calls at steps 30, 36, ..., 594
+    got = eng.score_runs(states, Q, target_position_table=table, save_every=3, sched_stride=2, period_steps=6, first_row=10, last_row=200)
+    check(got, score_rows(run["states_np"][:R], table[rows], run["Q_np"][:129], 10, 200, 5, 100), 190, 95)
+
+
+def test_the_stabilisation_test_on_a_hand_made_history(eng):
+    """Angles around the float32 threshold, a NaN, an env that never settles, one that always is, one that leaves at the very end;
+    1000 rows, so that every wave of the workgroup holds some."""
+    R, E = 1000, 6
+    rng = np.random.default_rng(5)
+    angle = rng.uniform(-0.5, 0.5, (R, E)).astype(f32)                    # inside pi / 5
+    angle[:400, 0] = 2.0; angle[400, 0] = STABLE_ANGLE                    # noqa: E702  the threshold itself is outside: first stable row 401
+    angle[:, 1] = 3.0                                                     # never
+    angle[R - 1, 3] = -1.0                                                # leaves in the last row
+    angle[777, 4] = np.nan                                                # a NaN is outside
+    angle[123, 5] = -np.nextafter(STABLE_ANGLE, f32(0))                   # the largest angle inside
+    states = np.zeros((R, E, 6), f32)
+    states[:, :, 0], states[:, :, 4] = angle, rng.uniform(-0.2, 0.2, (R, E))
+    got = eng.score_runs(states).cpu().numpy()
+    assert list(got[:, 4]) == [401, R, 0, R, 778, 0]
+    assert list(got[:, 3]) == [f32(599 / 1000), 0, 1, f32(999 / 1000), f32(999 / 1000), 1]
+    assert np.isnan(got[4, 1]) and not np.isnan(got[[0, 1, 2, 3, 5], :]).any()
+    ref = score_rows(states, 0.0)
+    assert np.array_equal(ref[:, 4], got[:, 4])
+    got = eng.score_runs(states, first_row=500, last_row=778).cpu().numpy()          # a window that ends on the NaN row
+    assert list(got[:, 4]) == [500, R, 500, 500, R, 500]
+
+
+def test_c_level_slices_and_refusals(eng, run):
+    """row_envs: envs 0..4 of the 70-wide logs, scored in place, are the whole score's first rows bit for bit.  Every refusal
+    names the call, launches nothing and leaves the output untouched."""
+    R = 257
+    states, Q = run["states"][:R].contiguous(), run["Q"][:R - 1].contiguous()
+    tgt = eng.tensor(run["target"])
+    whole = eng.score_runs(states, Q, target_position=tgt)
+    out = torch.full((5, L.SCORE_FLOATS), -7.0, device=states.device)
+
+    def block(**over):
+        a = L.cpmppi_score_args()
+        a.E, a.row_envs, a.rows, a.q_rows = 5, E_ALL, R, R - 1
+        a.states, a.Q, a.target_position, a.score_out = states.data_ptr(), Q.data_ptr(), tgt.data_ptr(), out.data_ptr()
+        for k, v in over.items():
+            setattr(a, k, v)
+        return a
+
+    def call(a):
+        rc = eng.lib.cpmppi_score_runs(eng._h, C.byref(a) if a is not None else None, eng._stream())
+        torch.cuda.synchronize()
+        return rc, eng.lib.cpmppi_last_error(eng._h).decode()
+
+    refused = [(None, -1), (block(states=None), -1), (block(score_out=None), -1), (block(E=0), -1), (block(rows=0), -1),
+               (block(rows=(1 << 24) + 1), -1), (block(row_envs=4), -1), (block(first_row=R), -1), (block(first_row=9, last_row=9), -1),
+               (block(last_row=R + 1), -1), (block(q_first=R - 1), -1), (block(q_last=R), -1),
+               (block(target_position_table=tgt.data_ptr()), -1), (block(states=states.data_ptr() + 2), -5),
+               (block(score_out=out.data_ptr() + 1), -5)]
+    for a, code in refused:
+        rc, text = call(a)
+        assert rc == code and text.startswith("cpmppi_score_runs: "), (rc, text)
+        assert torch.all(out == -7.0)
+    rc, text = call(block())
+    assert rc == 0, text
+    assert torch.equal(out, whole[:5])
