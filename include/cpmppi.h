@@ -669,8 +669,14 @@ int cpmppi_plant_advance_record(cpmppi_handle* h, uint32_t E, float* s, const fl
  *      target_position / target_equilibrium / L, :509-520) - point cpmppi_step_args.target_position / target_equilibrium / L there.
  * n_substeps = 0 records only (1. and 2.: the run's last controller call is followed by no plant step, :690-716).
  * period_dev: c = *period_dev - 1, the device step counter of cpmppi_step_args.offset_dev (already advanced by the step); a
- * counter that is still 0 advances the plant from table row 0 WITHOUT recording or publishing.  Any log / table / out pointer may
- * be NULL.  The pole MASS the controller computes with is
+ * counter that is still 0 advances the plant from table row 0 WITHOUT recording or publishing: the state is that of a host-named
+ * period 0 without a disturbance row, and Q_log, states_log, dd_log, state_history, the three *_out and s_measured are left as they
+ * are.  Q_applied_out is written all the same (= Q): it is no schedule value but the control this launch drove the plant by, which
+ * is what the next controller call is to be handed whatever the counter said (Q_ccrc = Q_applied, CartPole/__init__.py:493).
+ * A counter past the recording (c >= ctrl_rows, saved rows >= save_rows) advances the plant with the tables' LAST row and adds no
+ * disturbance or noise row; it writes no log, and still keeps the ring, publishes the *_out (the last row) and s_measured, and
+ * writes Q_applied_out = Q: a graph replayed beyond the recording's end never reads or writes outside the buffers.  Any log /
+ * table / out pointer may be NULL.  The pole MASS the controller computes with is
  * the handle's (config.m_pole / cpmppi_set_pole_mass, or per env cpmppi_set_pole_mass_rows), whatever the plant's: this call neither
  * reads nor publishes it (the caller copies the row of its own controller-mass table into the registered array between periods). */
 typedef struct {

@@ -86,6 +86,31 @@ def test_target_table_with_the_schedule_s_strides(eng, run):
     check(got, score_rows(run["states_np"][:R], table[rows], run["Q_np"][:129], 10, 200, 5, 100), 190, 95)
 
 
+@pytest.mark.parametrize("save_every,sched_stride,narrow", [(2 ** 24 + 1, 2 ** 23, False), (3 * 2 ** 22, 2 ** 21, True)])
+def test_target_table_row_with_large_strides_in_64_and_32_bits(eng, run, save_every, sched_stride, narrow):
+    """The table row of saved row r is r * save_every // sched_stride, clamped to the table's last row.  The kernel forms the product
+    in 32 bits when rows * save_every fits (`narrow`) and in 64 bits otherwise: 257 rows saved every 2^24 + 1 steps do not fit -
+    a 32-bit product would wrap at r = 256 and read table row 0 where the clamp gives row 299; saved every 3 * 2^22 steps they do
+    (row 6 r).  Both against score_rows with the rows picked on the host, and each case can tell the other form's mistake apart."""
+    R, E = 257, E_ALL
+    assert (R * save_every < 2 ** 32) == narrow and (R - 1) * save_every >= 2 ** 31
+    states = run["states"][:R].contiguous()
+    table = np.random.default_rng(2).uniform(-0.15, 0.15, (300, E)).astype(f32)
+    r = np.arange(R, dtype=np.uint64)
+    rows = np.minimum(r * np.uint64(save_every) // np.uint64(sched_stride), np.uint64(299)).astype(np.int64)
+    assert rows[-1] == 299 and rows[1] == (6 if narrow else 2) and len(np.unique(rows)) > 40
+    got = eng.score_runs(states, target_position_table=table, save_every=save_every, sched_stride=sched_stride)
+    ref = score_rows(run["states_np"][:R], table[rows])
+    check(got, ref, R, 1)
+    if not narrow:
+        # teeth: the rows a product wrapped to 32 bits names differ in the last row alone, and the mean distance computed with them
+        # lies far outside the bound (for all but the few envs whose cart is as far from one target as from the other)
+        wrapped = np.minimum((r * np.uint64(save_every) % np.uint64(2 ** 32)) // np.uint64(sched_stride), np.uint64(299)).astype(np.int64)
+        assert np.array_equal(wrapped[:-1], rows[:-1]) and wrapped[-1] == 0
+        wrong = score_rows(run["states_np"][:R], table[wrapped])
+        assert (np.abs(wrong[:, 0] - ref[:, 0]) > 4 * R * 2.0 ** -24 * np.abs(ref[:, 0])).sum() >= E // 2
+
+
 def test_the_stabilisation_test_on_a_hand_made_history(eng):
     """Angles around the float32 threshold, a NaN, an env that never settles, one that always is, one that leaves at the very end;
     1000 rows, so that every wave of the workgroup holds some."""
