@@ -31,7 +31,7 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_comm_set_stamped", "cpmppi_groups_comm_init", "cpmppi_groups_run_gather", "cpmppi_set_pole_mass_rows",
            "cpmppi_rpgd_reserve", "cpmppi_rpgd_step", "cpmppi_cem_reserve", "cpmppi_cem_step", "cpmppi_rollout_cost_gru",
            "cpmppi_rollout_cost_grad_gru", "cpmppi_gru_advance", "cpmppi_gru_washout", "cpmppi_brunton",
-           "cpmppi_score_runs", "cpmppi_set_tuning_rows")
+           "cpmppi_score_runs", "cpmppi_set_tuning_rows", "cpmppi_replay_step")
 TUNING_ROW_FLOATS, TUNING_LBD, TUNING_SIGMA = 16, 7, 8
 SCORE_FLOATS = 5
 SCORE_COLUMNS = ("mean_abs_distance", "mean_abs_angle_deg", "mean_Q_squared", "stable_share", "first_stable_row")
@@ -97,6 +97,16 @@ class cpmppi_score_args(C.Structure):
                 ("sched_stride", C.c_uint32), ("sched_rows", C.c_uint64), ("states", C.c_void_p),
                 ("target_position_table", C.c_void_p), ("target_position", C.c_void_p), ("target_position_value", C.c_float),
                 ("Q", C.c_void_p), ("score_out", C.c_void_p)]
+
+
+class cpmppi_replay_args(C.Structure):
+    _fields_ = [("R", C.c_uint32), ("T", C.c_uint32), ("K", C.c_uint32), ("H", C.c_uint32), ("prime", C.c_uint32),
+                ("period", C.c_uint64), ("period_dev", C.c_void_p), ("rows", C.c_void_p), ("rows_host", C.c_void_p),
+                ("states", C.c_void_p), ("target_position", C.c_void_p), ("target_equilibrium", C.c_void_p), ("L", C.c_void_p),
+                ("previous_input", C.c_void_p), ("Q", C.c_void_p), ("Q_mean_out", C.c_void_p), ("Q_std_out", C.c_void_p),
+                ("Q_all_out", C.c_void_p), ("s_out", C.c_void_p), ("target_position_out", C.c_void_p),
+                ("target_equilibrium_out", C.c_void_p), ("L_out", C.c_void_p), ("previous_input_out", C.c_void_p),
+                ("u_nom_reset", C.c_void_p)]
 
 
 class cpmppi_gru_model(C.Structure):
@@ -195,6 +205,7 @@ def load():
     lib.cpmppi_gru_washout.argtypes = [vp, u32, u32, vp, vp, vp, vp, vp]
     lib.cpmppi_brunton.argtypes = [vp, C.POINTER(cpmppi_brunton_args), vp]
     lib.cpmppi_score_runs.argtypes = [vp, C.POINTER(cpmppi_score_args), vp]
+    lib.cpmppi_replay_step.argtypes = [vp, C.POINTER(cpmppi_replay_args), vp]
     lib.cpmppi_rollout_cost.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost_gru.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp]
     lib.cpmppi_rollout_cost_grad_gru.argtypes = [vp, u32, vp, vp, vp, vp, vp, vp, vp, vp]

@@ -7,6 +7,7 @@
 //   cpmppi_plant.hip      the simulated plant (cpmppi_plant_*)
 //   cpmppi_optim.hip      cost-only rollouts, the adjoint, Adam / SGD steps and CEM
 //   cpmppi_score.hip      the score of a recording per env (cpmppi_score_runs)
+//   cpmppi_replay.hip     control along recorded trajectories: the recorded row in the plant's place (cpmppi_replay_step)
 //   cpmppi_gru.hip        the GRU predictor in the optimizers: the fused MPPI step, cost-only rollouts, the gradient's forward sweep
 //   cpmppi_gru_seam.hip   its exact-cell seams: predict, advance, washout, the Brunton test's kernel
 //   cpmppi_gru_adjoint.hip  the gradient's reverse sweep

@@ -726,6 +726,72 @@ class MPPIEngine:
         buffers (a captured loop that ends with its own score)."""
         return self._build_score_runs(*args, **kwargs)
 
+    # ------------------------------------------------------------------ control along recorded trajectories
+    _REPLAY_COLUMNS = ("target_position", "target_equilibrium", "L", "previous_input")
+
+    def _build_replay_step(self, states, rows, Q, K, *, period=0, period_dev=None, prime=False, rows_dev=None, target_position=None,
+                           target_equilibrium=None, L=None, previous_input=None, Q_mean_out=None, Q_std_out=None, Q_all_out=None,
+                           s_out=None, target_position_out=None, target_equilibrium_out=None, L_out=None, previous_input_out=None,
+                           u_nom_reset=None):
+        """cpmppi_replay_step: one control period ``period`` along recordings, in the plant's place (include/cpmppi.h states the
+        call).  ``states`` [R,T,6] and the optional columns [R,T] on the device; ``rows`` [R] the recordings' true lengths on the
+        HOST (``rows_dev``: the same as an int32 device tensor, else uploaded here); ``Q`` [R*K] the controls of the ``K`` copies of
+        every recording, env r*K + k.  Collected at row ``period``: ``Q_mean_out`` / ``Q_std_out`` [R,T], ``Q_all_out`` [T,R*K];
+        published from the next row: ``s_out`` [R*K,6] and the ``*_out`` [R*K]; ``u_nom_reset`` [R*K,H] is zero-filled.
+        ``prime``: publish row 0 and collect nothing.  ``period_dev``: the step's int64 device counter, already advanced.
+        -> (Q_mean_out, Q_std_out) as given."""
+        states = device_tensor("states", states, tail=None)
+        if states.dim() != 3 or states.shape[2] != 6 or states.shape[0] == 0 or states.shape[1] == 0:
+            raise ValueError(f"states must be [R,T,6] with R, T >= 1, got {tuple(states.shape)}")
+        R, T, K = states.shape[0], states.shape[1], int(K)
+        E = R * K
+        if K < 1 or E > self.E:
+            raise ValueError(f"{R} recordings x {K} evaluations: between 1 and the engine's {self.E} envs")
+        rows_host = np.ascontiguousarray(np.asarray(rows).reshape(-1), dtype=np.uint32)
+        if rows_host.shape != (R,):
+            raise ValueError(f"rows must hold one length per recording ({R}), got {rows_host.size}")
+        if rows_dev is None:
+            rows_dev = torch.as_tensor(rows_host.astype(np.int32)).to(self.device)
+        elif device_tensor("rows_dev", rows_dev, torch.int32).shape != (R,):
+            raise ValueError(f"rows_dev must be [{R}]")
+        a = _L.cpmppi_replay_args()
+        a.R, a.T, a.K, a.prime, a.period = R, T, K, int(bool(prime)), int(period)
+        a.period_dev = _counter("period_dev", period_dev)
+        a.rows, a.rows_host, a.states = rows_dev.data_ptr(), rows_host.ctypes.data, states.data_ptr()
+        keep = [states, rows_host, rows_dev, period_dev]
+
+        def point(name, t, shape):
+            if t is not None:
+                if not (is_dense(t) and t.is_cuda and tuple(t.shape) == shape):
+                    raise ValueError(f"{name} must be a contiguous float32 ROCm tensor {list(shape)}, got {tuple(getattr(t, 'shape', ()))}")
+                keep.append(t)
+                setattr(a, name, t.data_ptr())
+
+        columns = dict(target_position=target_position, target_equilibrium=target_equilibrium, L=L, previous_input=previous_input)
+        outs = dict(target_position_out=target_position_out, target_equilibrium_out=target_equilibrium_out, L_out=L_out,
+                    previous_input_out=previous_input_out)
+        for name in self._REPLAY_COLUMNS:
+            point(name, columns[name], (R, T))
+            if outs[name + "_out"] is not None and columns[name] is None:
+                raise ValueError(f"{name}_out needs the recorded column {name}")
+            point(name + "_out", outs[name + "_out"], (E,))
+        point("Q", Q, (E,))
+        point("Q_mean_out", Q_mean_out, (R, T))
+        point("Q_std_out", Q_std_out, (R, T))
+        point("Q_all_out", Q_all_out, (T, E))
+        point("s_out", s_out, (E, 6))
+        if u_nom_reset is not None:
+            a.H = u_nom_reset.shape[1] if torch.is_tensor(u_nom_reset) and u_nom_reset.dim() == 2 else 0
+            point("u_nom_reset", u_nom_reset, (E, a.H))
+        return PreparedCall(self, self.lib.cpmppi_replay_step, a, keep, (Q_mean_out, Q_std_out), ("period", "prime"))
+
+    replay_step = _run_once(_build_replay_step)
+
+    def prepare_replay_step(self, *args, **kwargs):
+        """The argument block of ``replay_step(...)`` built and validated ONCE: ``.run(period=, prime=)`` updates those two fields and
+        enqueues the launch; with ``period_dev`` nothing changes between periods."""
+        return self._build_replay_step(*args, **kwargs)
+
     # ------------------------------------------------------------------ cost-only launch and CEM (SURVEY §8f N4)
     def _per_env(self, x, E):
         x = self.tensor(x)

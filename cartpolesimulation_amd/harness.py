@@ -491,8 +491,10 @@ class FusedOptimizer:
     the first step's extra iterations are told by the host, and such an optimizer keeps its host counters."""
     cannot_capture = None
 
-    def __init__(self, optimizer, buffers, mass):
-        self.opt, self.buf, self.mass = optimizer, buffers, mass
+    def __init__(self, optimizer, buffers, mass, previous_input=None):
+        """``previous_input`` [E]: where the control applied in the period before stands, if not in the controls buffer itself (a
+        loop along recordings: the recorded column)."""
+        self.opt, self.buf, self.mass, self.previous_input = optimizer, buffers, mass, previous_input
         if optimizer.engine is None:
             optimizer.configure()
         buffers.Q = optimizer.controls                             # the fused step writes its controls where the plant reads them
@@ -506,7 +508,8 @@ class FusedOptimizer:
         if c is not None:                                          # (captured: applied once before the capture)
             opt.engine.apply_pole_mass_of(vp, **opt._mass_rows)
         # the control of the period before is the one this buffer still holds
-        opt.step_device(buf.s_ctrl, buf.cur_tp, buf.cur_te, L=buf.cur_L, previous_input=buf.Q, count_dev=self.counter)
+        previous = buf.Q if self.previous_input is None else self.previous_input
+        opt.step_device(buf.s_ctrl, buf.cur_tp, buf.cur_te, L=buf.cur_L, previous_input=previous, count_dev=self.counter)
 
     def before_capture(self):
         """The optimizer's own handle: its mass, its workspace."""
@@ -602,3 +605,154 @@ class ScheduleRun:
         if self.memory is not None:
             res["memory"] = self.memory
         return res
+
+
+# ---- control along recorded trajectories: the recorded row stands where the plant's stands -------------------------------------------
+REPLAY_REFUSALS = {
+    "gru": "control along recordings does not serve the GRU predictor: its memory along a recording needs the washout rows "
+           "published per period (predictor must be an ODE one)",
+    "host_paced": "control along recordings needs a controller that stays on the device: an optimizer object is paced by the host "
+                  "(the fused MPPI step, or rpgd with fused=True)",
+    "cold_optimizer": "warm_start=False is served by the fused MPPI step alone: an optimizer object keeps its plans, moments and "
+                      "counters between rows",
+}
+
+
+class ReplayBuffers:
+    """What a loop along recordings derives from the recordings alone: ``states`` [R,T,6] and the columns [R,T] on the device,
+    their true lengths ``rows`` [R], and for the E = R*K envs (env r*K + k: the copies of a recording are contiguous) the vectors
+    the controller reads and cpmppi_replay_step refills, the controls, the plans and the results - the mean [R,T] and standard
+    deviation [R,T] over a recording's copies, NaN past its end, and with ``keep_evals`` every control [T,E].  It has the
+    attributes the controller kinds read off ScheduleBuffers (s, s_ctrl, cur_tp, cur_te, cur_L, Q, u_nom, previous_input).
+    ``previous`` [R,T]: the recorded control applied before each row; a cost that reads a previous input needs it."""
+
+    def __init__(self, engine, states, rows, K, target_position, target_equilibrium, L=None, previous=None, keep_evals=False):
+        eng = engine
+        self.states = eng.tensor(states)
+        if self.states.dim() != 3 or self.states.shape[2] != 6:
+            raise ValueError(f"states must be [R,T,6], got {tuple(self.states.shape)}")
+        R, T = self.states.shape[0], self.states.shape[1]
+        self.R, self.T, self.K, self.E = R, T, int(K), R * int(K)
+        self.rows = np.ascontiguousarray(np.asarray(rows).reshape(-1), np.uint32)
+        if self.rows.shape != (R,) or self.rows.min() < 1 or self.rows.max() > T:
+            raise ValueError(f"rows must hold a length in 1..{T} for each of the {R} recordings")
+        self.rows_dev = torch.as_tensor(self.rows.astype(np.int32)).to(self.states.device)
+        E, nan = self.E, float("nan")
+        self.columns = dict(target_position=eng.tensor(target_position, (R, T)), target_equilibrium=eng.tensor(target_equilibrium, (R, T)),
+                            L=eng.tensor(L, (R, T)), previous_input=eng.tensor(previous, (R, T)))
+        self.s = self.s_ctrl = eng.zeros(E, 6)
+        self.cur_tp, self.cur_te = eng.zeros(E), eng.zeros(E)
+        self.cur_L = eng.zeros(E) if L is not None else None
+        self.previous = eng.zeros(E)                               # (without a recorded column: 0, as before a run's first update)
+        self.u_nom, self.Q = eng.zeros(E, eng.H), eng.zeros(E)
+        self.Q_mean, self.Q_std = eng.empty(R, T).fill_(nan), eng.empty(R, T).fill_(nan)
+        self.Q_all = eng.empty(T, E).fill_(nan) if keep_evals else None
+        from .optimizer_mppi import PREVIOUS_INPUT_COSTS
+        self.previous_input = {}                                   # (a keyword of the controller call)
+        if eng.mppi.cost_function_specification in PREVIOUS_INPUT_COSTS:
+            if previous is None:
+                raise ValueError(f"the cost {eng.mppi.cost_function_specification!r} reads the control applied before each row: the "
+                                 "recordings must carry it (Q_ccrc / Q_applied_-1)")
+            self.previous_input = dict(previous_input=self.previous)
+
+    def replay_arguments(self, warm_start=True):
+        """-> (positional, keyword) arguments of engine.replay_step for these buffers (read when a call is built: a fused optimizer
+        has put its own controls buffer in by then)."""
+        c = self.columns
+        kw = dict(rows_dev=self.rows_dev, target_position=c["target_position"], target_equilibrium=c["target_equilibrium"], L=c["L"],
+                  previous_input=c["previous_input"], Q_mean_out=self.Q_mean, Q_std_out=self.Q_std, Q_all_out=self.Q_all,
+                  s_out=self.s, target_position_out=self.cur_tp, target_equilibrium_out=self.cur_te, L_out=self.cur_L,
+                  previous_input_out=self.previous if c["previous_input"] is not None else None,
+                  u_nom_reset=None if warm_start else self.u_nom)
+        return (self.states, self.rows, self.Q, self.K), kw
+
+    def result(self):
+        R, T, K = self.R, self.T, self.K
+        res = dict(Q=self.Q_mean, Q_std=self.Q_std, rows=self.rows, u_nom=self.u_nom)
+        if self.Q_all is not None:
+            res["Q_evals"] = self.Q_all.reshape(T, R, K)
+        return res
+
+
+class ReplayRun:
+    """The device loop along recordings: prime (row 0 goes to the controller), then per period the controller call and ONE
+    cpmppi_replay_step, which collects the row's controls and publishes the next row - launched, or `steps_per_graph` periods at a
+    time as replays of one HIP graph.  The controller kinds and PeriodLoop are ScheduleRun's; the semantics are this package's own
+    (include/cpmppi.h, cpmppi_replay_args): every copy of a recording is an independent controller instance, its env index feeds
+    Philox, the Philox offset of row c is c, and the plan is carried from row to row unless ``warm_start`` is False."""
+
+    def __init__(self, engine, buffers, seed, env_offset=0, optimizer=None, warm_start=True, predictor="ODE_v0"):
+        if predictor == "GRU":
+            raise ValueError(REPLAY_REFUSALS["gru"])
+        check_predictor(engine, predictor, None, optimizer, None)
+        if optimizer is not None:
+            if not getattr(optimizer, "fused", False):
+                raise ValueError(REPLAY_REFUSALS["host_paced"])
+            if not warm_start:
+                raise ValueError(REPLAY_REFUSALS["cold_optimizer"])
+            if getattr(optimizer, "num_envs", buffers.E) != buffers.E:
+                raise ValueError(f"the optimizer is configured for {optimizer.num_envs} envs, the recordings x evaluations are {buffers.E}")
+            if getattr(optimizer, "variable_parameters", None) is None:
+                from types import SimpleNamespace
+                optimizer.variable_parameters = SimpleNamespace()
+        from types import SimpleNamespace
+        self.eng, self.buffers, self.warm_start = engine, buffers, bool(warm_start)
+        self.T = buffers.T
+        self.mass = ControllerMass(SimpleNamespace(m_pole_table=None), engine.mppi)      # (a recording tells no controller-side mass)
+        if optimizer is None:
+            self.controller = FusedMppiStep(engine, buffers, self.mass, seed, env_offset, None, None)
+        else:
+            self.controller = FusedOptimizer(optimizer, buffers, self.mass, previous_input=buffers.previous)
+        self.loop = PeriodLoop(engine, self.T)
+        self._by_host = self._by_counter = None                    # the replay launch, named either way: built once each
+        self.primed = False
+
+    periods_left = property(lambda self: self.loop.c < self.T)
+
+    def _prepare(self, **named):
+        args, kw = self.buffers.replay_arguments(self.warm_start)
+        return self.eng.prepare_replay_step(*args, **named, **kw)
+
+    def prime(self):
+        """Row 0 of every recording to the vectors the controller reads: once, before controller call 0."""
+        if self._by_host is None:
+            self._by_host = self._prepare(period=0)
+        self._by_host.run(period=0, prime=1)
+        self.primed = True
+
+    def _replay_step(self, c):
+        counter = self.controller.counter
+        if counter is not None:
+            if self._by_counter is None:
+                self._by_counter = self._prepare(period_dev=counter)
+            self._by_counter.run()
+            return
+        if self._by_host is None:
+            self._by_host = self._prepare(period=0)
+        self._by_host.run(period=c, prime=0)
+
+    def _period(self, c):
+        self.controller.control(c)
+        self._replay_step(c)
+
+    def capture(self, steps_per_graph=10):
+        why = self.controller.cannot_capture
+        if why is not None:
+            raise ValueError(why)
+        self.mass.apply(0)
+        self.controller.before_capture()
+        self.loop.capture(self._period, steps_per_graph, self.buffers.s.device)
+
+    def run(self, graph=False, steps_per_graph=10):
+        """All of it -> `result()`."""
+        if graph and self.controller.cannot_capture:
+            raise ValueError(self.controller.cannot_capture)
+        if not self.primed:
+            self.prime()
+        if graph and self.T > 0:
+            self.capture(steps_per_graph)
+        self.loop.enqueue_rest(self._period)
+        return self.result()
+
+    def result(self):
+        return self.buffers.result()

@@ -425,6 +425,60 @@ typedef struct {
 } cpmppi_score_args;
 int cpmppi_score_runs(cpmppi_handle* h, const cpmppi_score_args* args, void* stream);
 
+/* Control along recorded trajectories (SI_Toolkit_ASF/Run/PreprocessData_Add_Control_Along_Trajectories.py; fanned out over 120
+ * single-CPU jobs by others/EulerClusterScripts/ControllerAlongTrajectories.sh): a controller's output along recordings that exist
+ * already.  This call stands where cpmppi_plant_step stands in the device loop: it hands the controller the RECORDED row where the
+ * plant would hand it the simulated one, and reduces the evaluations of a row to one number.  The upstream transformation
+ * (SI_Toolkit.data_preprocessing.transform_dataset) is not part of the reference checkout, so the semantics here are this
+ * library's own.
+ * R recordings padded to T rows, rows[r] their true lengths; K evaluations (independent controller instances) per recording:
+ * env e = r*K + k, E = R*K, the copies of a recording contiguous.  Inputs in the layout of cpmppi_brunton.
+ * One call = one control period c, ONE kernel:
+ *   collect  for every recording with c < rows[r]: Q_mean_out[r*T + c] = mean over k of Q[r*K + k]; Q_std_out[r*T + c] = the sample
+ *            standard deviation (divisor K - 1; 0 for K == 1); Q_all_out[c][E] = Q as found.  Rows at or past rows[r] are not
+ *            written.  Mean and deviation are formed in float64 by ONE wave per recording, in a fixed order without atomics -
+ *            lane l adds Q[r*K + l], Q[r*K + l + 64], ... in ascending k; the 64 lane sums are added by a butterfly (each lane adds
+ *            lane l^32's sum, then l^16's, l^8's, l^4's, l^2's, l^1's); mean = sum / K; the deviation is a second pass in the same
+ *            order over (Q - mean)^2, sqrt(sum / (K - 1)) - and each is rounded to float32 once: the same bits from run to run,
+ *            for any K.
+ *   publish  for all K copies of r, from row p = min(c + 1, rows[r] - 1) of the recording: s_out[e][6], target_position_out[e],
+ *            target_equilibrium_out[e], L_out[e], previous_input_out[e] (the recorded Q_ccrc / "Q_applied_-1": point the step's
+ *            previous_input there) - what controller call c + 1 reads.  A period past the longest recording keeps publishing
+ *            last rows and collects nothing: a graph replayed beyond the end reads and writes nothing outside the buffers.
+ *   prime    (prime != 0) publishes row 0 and collects nothing: called once before controller call 0.
+ *   reset    u_nom_reset[E,H] given: zero-filled, so that every row is solved from a cold plan (any H).
+ * period_dev: c = *period_dev - 1 under the rule of cpmppi_plant_step (the step's counter, already advanced); a counter that is
+ * still 0 names no controller call made: the call then behaves as a prime call (row 0 published, nothing collected).
+ * No allocation, no host synchronisation: can be captured.  Reads no configuration of the handle but config.E.
+ * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned ("cpmppi_replay_step: ...") for a NULL states, Q, rows or rows_host; R, T
+ * or K == 0; R*K > config.E; a rows_host[r] of 0 or above T; no output at all; an output without its input column; u_nom_reset
+ * without H.  A misaligned pointer is CPMPPI_ERR_ALIGN. */
+typedef struct {
+  uint32_t R, T, K;                     /* recordings, rows of each (padded), evaluations per recording */
+  uint32_t H;                           /* columns of u_nom_reset */
+  uint32_t prime;                       /* != 0: publish row 0, collect nothing */
+  uint64_t period;                      /* c */
+  const void* period_dev;               /* or NULL */
+  const uint32_t* rows;                 /* [R] DEVICE: the true lengths, 1..T (the kernel clamps what it reads to that range) */
+  const uint32_t* rows_host;            /* [R] HOST: the same lengths, checked by every call */
+  const float* states;                  /* [R,T,6] */
+  const float* target_position;         /* [R,T] or NULL */
+  const float* target_equilibrium;      /* [R,T] or NULL */
+  const float* L;                       /* [R,T] or NULL */
+  const float* previous_input;          /* [R,T] or NULL */
+  const float* Q;                       /* [E] the controls of controller call c */
+  float* Q_mean_out;                    /* [R,T] or NULL */
+  float* Q_std_out;                     /* [R,T] or NULL */
+  float* Q_all_out;                     /* [T][E] or NULL */
+  float* s_out;                         /* [E,6] or NULL */
+  float* target_position_out;           /* [E] or NULL */
+  float* target_equilibrium_out;        /* [E] or NULL */
+  float* L_out;                         /* [E] or NULL */
+  float* previous_input_out;            /* [E] or NULL */
+  float* u_nom_reset;                   /* [E,H] or NULL */
+} cpmppi_replay_args;
+int cpmppi_replay_step(cpmppi_handle* h, const cpmppi_replay_args* args, void* stream);
+
 /* Rollout + cost only (no update): per-rollout trajectory cost S[E,N] of GIVEN input sequences inputs[E,N,H] under the
  * handle's plugin cost — cost_function.get_trajectory_cost(predictor.predict_core(s, Q), Q) fused; the building block of
  * the sampling optimizers that are not MPPI. */
