@@ -27,13 +27,15 @@ def _cell(x, h, w_ih, w_hh, b_ih, b_hh):
     return (1.0 - z) * n + z * h
 
 
-def gru_predict(model, s0, Q, h0=None):
+def gru_predict(model, s0, Q, h0=None, dtype=f64):
     """oracle_np.gru_predict on float64 torch tensors: s0 [6], Q [N,H] (tensor), h0 [2,32] or None ->
-    traj[k][component] (k = 0..H, each a tensor [N]; the form oracle_torch.trajectory_cost takes)."""
+    traj[k][component] (k = 0..H, each a tensor [N]; the form oracle_torch.trajectory_cost takes).  ``dtype=torch.float32``: the
+    same statements on float32 tensors (Q float32 too) - a float32 realisation of the reference, to judge its conditioning."""
     N, H = Q.shape
-    m = {k: torch.tensor(np.asarray(v, dtype=np.float64)) for k, v in model.items()}
-    s = torch.tensor(np.asarray(s0, dtype=f32).astype(np.float64))
-    h = [torch.zeros(N, 32, dtype=f64) if h0 is None else torch.tensor(np.asarray(h0, f32)[layer].astype(np.float64)).repeat(N, 1)
+    npd = np.float64 if dtype == f64 else np.float32
+    m = {k: torch.tensor(np.asarray(v, dtype=npd)) for k, v in model.items()}
+    s = torch.tensor(np.asarray(s0, dtype=f32).astype(npd))
+    h = [torch.zeros(N, 32, dtype=dtype) if h0 is None else torch.tensor(np.asarray(h0, f32)[layer].astype(npd)).repeat(N, 1)
          for layer in range(2)]
     feat0 = torch.stack([s[O.ANGLED_IDX], s[O.ANGLE_COS_IDX], s[O.ANGLE_SIN_IDX], s[O.POSITION_IDX], s[O.POSITIOND_IDX]])
     feat = (feat0 * m["in_scale"][1:] + m["in_shift"][1:]).repeat(N, 1)
@@ -54,12 +56,12 @@ def gru_predict(model, s0, Q, h0=None):
 
 
 def cost_and_grad(model, cost, s0, Q, target_position, target_equilibrium=1.0, h0=None, horizon_reduce="sum", clip=(-1.0, 1.0),
-                  dtype=np.float64):
+                  dtype=np.float64, eval_dtype=f64):
     """numpy in / numpy out: (cost [N], grad [N,H], traj [N,H+1,6]) of one env in float64; ``dtype=np.float32`` only rounds the
-    results (the evaluation stays double)."""
-    Qt = torch.tensor(np.asarray(Q, dtype=np.float64), requires_grad=True)
+    results (the evaluation stays double); ``eval_dtype=torch.float32`` evaluates the network and its adjoint in float32."""
+    Qt = torch.tensor(np.asarray(Q, dtype=np.float64 if eval_dtype == f64 else np.float32), requires_grad=True)
     Qa = Qt.clamp(clip[0], clip[1]) if clip is not None else Qt
-    traj = gru_predict(model, s0, Qa, h0)
+    traj = gru_predict(model, s0, Qa, h0, eval_dtype)
     J = OT.trajectory_cost(COSTS[cost], traj, Qa, target_position, target_equilibrium, horizon_reduce)
     (g,) = torch.autograd.grad(J.sum(), Qt)
     tr = torch.stack([torch.stack(st, dim=1) for st in traj], dim=1).detach().numpy()
@@ -89,21 +91,29 @@ def case_inputs(E, N, H):
     return out
 
 
-@functools.lru_cache(maxsize=None)
-def case_reference(model_name, cost, E, N, H, with_h0, reduce):
-    """-> (J [E,N], g [E,N,H], flagged [E,N]) in float64.  Flagged: PU.flag_indicators on the oracle's trajectory, or an input
-    within 1e-3 of a control limit."""
+def reference_of(model_name, cost, s0, tp, te, h0, Q, reduce, clip=(-1.0, 1.0)):
+    """One env -> (J [N], g [N,H], flagged [N]) in float64 under target equilibrium `te` and control limits `clip` (None: the
+    inputs are not clipped, control_mode "penalise").  Flagged: PU.flag_indicators on the oracle's trajectory, or an input within
+    1e-3 of a control limit."""
     import parity_util as PU
     from test_gpu_gru_edges import model_of
+    N = Q.shape[0]
+    J, g, _ = cost_and_grad(model_of(model_name), cost, s0, Q, tp, te, h0, reduce, clip)
+    h0b = np.repeat(h0[:, None, :], N, axis=1) if h0 is not None else None
+    Qa = Q if clip is None else np.clip(Q, f32(clip[0]), f32(clip[1]))
+    traj = O.gru_predict(model_of(model_name), s0, Qa, h0b, dtype=np.float64)[0]
+    f = PU.flag_indicators(traj, COST_FLAG_NAMES[cost], tp)
+    if clip is not None:
+        f = f | ((np.abs(Q - f32(clip[0])) < 1e-3) | (np.abs(Q - f32(clip[1])) < 1e-3)).any(axis=1)
+    return J, g, f
+
+
+@functools.lru_cache(maxsize=None)
+def case_reference(model_name, cost, E, N, H, with_h0, reduce, te=1.0):
+    """-> (J [E,N], g [E,N,H], flagged [E,N]) in float64 (reference_of per env of case_inputs; `te`: every env's target equilibrium)."""
     s0, tp, h0, Q = case_inputs(E, N, H)
-    J, g, fl = [], [], []
-    for e in range(E):
-        Je, ge, _ = cost_and_grad(model_of(model_name), cost, s0[e], Q[e], tp[e], 1.0, h0[e] if with_h0 else None, reduce)
-        h0b = np.repeat(h0[e][:, None, :], N, axis=1) if with_h0 else None
-        traj = O.gru_predict(model_of(model_name), s0[e], np.clip(Q[e], -1, 1), h0b, dtype=np.float64)[0]
-        f = PU.flag_indicators(traj, COST_FLAG_NAMES[cost], tp[e]) | (np.abs(np.abs(Q[e]) - 1.0) < 1e-3).any(axis=1)
-        J.append(Je); g.append(ge); fl.append(f)
-    out = (np.stack(J), np.stack(g), np.stack(fl))
+    per_env = [reference_of(model_name, cost, s0[e], tp[e], te, h0[e] if with_h0 else None, Q[e], reduce) for e in range(E)]
+    out = tuple(np.stack(x) for x in zip(*per_env))
     for x in out:
         x.setflags(write=False)
     return out

@@ -87,10 +87,10 @@ def oracle_cfg(N, H, period=10, cost="quadratic_boundary_grad_minimal", **flags)
     return O.MPPIConfig(N=N, H=H, period=period, cost_id=COSTS[cost], **flags)
 
 
-def oracle_pair(model, s, u0, du, tp, cfg, h0, low=-1.0, high=1.0):
-    """The oracle's GRU MPPI step for one env in float32 and float64."""
-    a = O.gru_mppi_step(model_of(model), s, u0, du, f32(tp), f32(1.0), cfg, h0=h0, low=low, high=high)
-    b = O.gru_mppi_step(model_of(model), s, u0, du, f32(tp), f32(1.0), cfg, h0=h0, low=low, high=high, dtype=np.float64)
+def oracle_pair(model, s, u0, du, tp, cfg, h0, low=-1.0, high=1.0, te=1.0):
+    """The oracle's GRU MPPI step for one env in float32 and float64 (te: that env's target equilibrium)."""
+    a = O.gru_mppi_step(model_of(model), s, u0, du, f32(tp), f32(te), cfg, h0=h0, low=low, high=high)
+    b = O.gru_mppi_step(model_of(model), s, u0, du, f32(tp), f32(te), cfg, h0=h0, low=low, high=high, dtype=np.float64)
     return a, b
 
 
@@ -101,11 +101,25 @@ def cost_flags(ref32, ref64, cost, tp):
     return fl
 
 
-def check_env(S, un, Q, ref32, ref64, du, cost, tp, what):
-    """One env of a step against the oracle pair under the module's bounds -> (worst excess of a clear rollout, worst |u_nom - u32|)."""
-    fl = cost_flags(ref32, ref64, cost, tp)
-    assert fl.mean() <= 0.05, f"{what}: {int(fl.sum())} of {fl.size} rollouts flagged"
-    b = PU.assert_costs(S, ref32["S"], ref64["S"], fl, f"{what} costs")
+def hanging_default(cost, te):
+    """default.py's cost with the hanging target: its angle term is negative, and rollout_matrix.buckets hands the verdict on
+    such costs to tools/dev/hanging_target.py."""
+    return cost == "default" and te < 0
+
+
+def check_env(S, un, Q, ref32, ref64, du, cost, tp, what, te=1.0, horizon_reduce="sum"):
+    """One env of a step against the oracle pair under the module's bounds -> (worst excess of a clear rollout, worst |u_nom - u32|).
+    `default` with te < 0: the costs' verdict is hanging_default_buckets, as in rollout_matrix.buckets (flags: the indicators)."""
+    if hanging_default(cost, te):
+        from rollout_matrix import hanging_target
+        fl = PU.flag_indicators(ref32["traj"], "default", tp)
+        assert fl.mean() <= 0.05, f"{what}: {int(fl.sum())} of {fl.size} rollouts flagged"
+        b = hanging_target().assert_hanging_default_costs(S, ref32["S"], ref64["S"], fl, f"{what} costs (hanging target)",
+                                                          H=du.shape[1], horizon_reduce=horizon_reduce)
+    else:
+        fl = cost_flags(ref32, ref64, cost, tp)
+        assert fl.mean() <= 0.05, f"{what}: {int(fl.sum())} of {fl.size} rollouts flagged"
+        b = PU.assert_costs(S, ref32["S"], ref64["S"], fl, f"{what} costs")
     allow = PU.softmin_allowance(ref32["S"], ref64["S"], du, LBD=100.0)
     PU.assert_controls(un, ref32["u_new"], ref64["u_new"], f"{what} u_nom", allowance=allow)
     PU.assert_controls(Q, ref32["Q"], ref64["Q"], f"{what} Q", allowance=allow[0])
