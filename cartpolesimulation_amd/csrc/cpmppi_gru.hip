@@ -7,13 +7,16 @@
 //                                           building block of the sampling optimizers (cem, cem-gmm, random-action).
 //   gru_grad_forward_kernel<COST,F16>       the cost-only rollout that also parks, per control step, what the reverse sweep
 //                                           (gru_grad_reverse_kernel, cpmppi_gru_adjoint.hip) needs.
+//   gru_cem_step_kernel<COST,F16>           the whole cem control step over the network, one workgroup per env: the cost-only
+//                                           rollout between cem_step_kernel's sampler, ranking and refit (cpmppi_cem.hpp).
 // They share one rollout (GruRollout: gru_rollout_init, gru_rollout_step, gru_rollout_total) and differ in where a step's input
-// comes from and in what becomes of the costs.  Entry points: cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru;
+// comes from and in what becomes of the costs.  Entry points: cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru, cpmppi_cem_step_gru;
 // -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write g_gru_stamp_sum are this unit's).
 #include <type_traits>
 #include "cpmppi_cost.hpp"
 #include "cpmppi_philox.hpp"
 #include "cpmppi_wave.hpp"
+#include "cpmppi_cem.hpp"        // the sampler's statement, the ranking and the refit of the fused CEM step
 #include "cpmppi_gru16.hpp"      // (and cpmppi_gru.hpp, cpmppi_internal.hpp)
 
 using namespace cpmppi_k;
@@ -314,6 +317,90 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_grad_forward_kernel(
   if (a.S_out && owner) a.S_out[(size_t)env * p.N + n] = S_total;
 }
 
+// The fused CEM control step over the GRU predictor (cpmppi_cem_step_gru): what cem_step_kernel (cpmppi_optim.hip) is over the
+// ODE, with gru_cost_only_kernel's rollout in the place of the forward sweep.  One workgroup = one env, all outer iterations in
+// the one launch; the block is one wave per 32 samples (N <= GRU_CEM_ROLLOUTS: at most 8 waves, two per SIMD - the register
+// budget GRU_MIN_WAVES compiles these bodies for), so every wave has a rollout and the whole population runs in one pass.
+// Per iteration: lane n < N draws row n (cem_sample_row: cem_sample_kernel's statement) into the env's workspace column n,
+// lane-contiguous as cem_step_kernel's; the block meets; rollout n runs on lanes (c, c + 32) of wave n / 32 from h0[env] - the
+// calls gru_cost_only_kernel makes, the next input loaded one control step ahead - ; the owner lanes rank the costs
+// (rank_costs_at: cem_update_kernel's stable order, the keys in LDS); lanes k < H refit time-step k (cem_refit_column).  The
+// barrier that opens an iteration closes the refit of the one before.  Mean and stdev live in LDS for the whole step.
+// Dynamic LDS: the weights image | key[256] | order[256] | mean[H] | stdev[H].  Unlike the cost-only kernel this one has barriers
+// behind the image load: no wave leaves before the end, and the lanes of a wave's tile beyond N roll out sample 0 unaccounted.
+constexpr int GRU_CEM_ROLLOUTS = 256;
+constexpr int GRU_CEM_BLOCK = 2 * GRU_CEM_ROLLOUTS;
+struct GruCemPtrs {
+  const float* s0; const float* x_t; const float* te;
+  const float* h0;                 // [E,2,32] or NULL = 0
+  float* mean; float* stdev;       // [E][H], in place
+  float* samples;                  // [E][H][stride]
+  const unsigned long long* count_dev;
+  unsigned long long seed, offset;
+  uint32_t iterations, best_k, shift, env_offset, stride;
+  float stdev_min, mean_fill, stdev_fill;
+  float* Q_out; float* S_out; float* plan_out; float* samples_out; uint32_t* order_out;
+};
+
+template <int COST, bool F16>
+__global__ __launch_bounds__(GRU_CEM_BLOCK, GRU_MIN_WAVES) void gru_cem_step_kernel(const Params p, const GruCemPtrs a, const GruNorm nm,
+                                                                                     const float* __restrict__ image) {
+  extern __shared__ float lds[];
+  constexpr int IMAGE_FLOATS = GRU_ROLLOUT_IMAGE_FLOATS<F16>;
+  const uint32_t tid = threadIdx.x, Nt = blockDim.x, env = blockIdx.x, N = p.N, H = p.H, Nb = a.stride;
+  uint32_t* key = reinterpret_cast<uint32_t*>(lds + IMAGE_FLOATS);
+  uint32_t* order = key + GRU_CEM_ROLLOUTS;
+  float* mu = reinterpret_cast<float*>(order + GRU_CEM_ROLLOUTS);
+  float* sd = mu + H;
+  for (uint32_t i = tid; i < (uint32_t)IMAGE_FLOATS; i += Nt) lds[i] = image[i];
+  for (uint32_t k = tid; k < H; k += Nt) { mu[k] = a.mean[(size_t)env * H + k]; sd[k] = a.stdev[(size_t)env * H + k]; }
+  const uint32_t lane = tid & 63u, c = lane & 31u;
+  const uint32_t n = (tid >> 6) * 32 + c;                  // the rollout of this lane pair
+  const bool owner = lane < 32 && n < N;                   // the lane that accounts for rollout n
+  const uint32_t nn = n < N ? n : 0;
+  const bool half1 = lane >= 32;
+  const uint64_t base = a.offset + (a.count_dev ? (uint64_t)*a.count_dev * a.iterations : 0ull);
+  const float x_t = a.x_t[env], te = a.te[env];
+  const float* __restrict__ s0 = a.s0 + (size_t)env * 6;
+  const float* h1src = a.h0 ? a.h0 + (size_t)env * 64 : nullptr;
+  float* cols = a.samples + (size_t)env * H * Nb;          // the env's samples [H][Nb]
+  const float* in = cols + nn;
+  GruStamps none;
+
+  for (uint32_t it = 0; it < a.iterations; ++it) {
+    const bool last = it + 1 == a.iterations;
+    __syncthreads();                                       // image, mean / stdev of this iteration stand; the refit before is through
+    if (tid < N) {
+      cem_sample_row(p, mu, sd, a.seed, base + it, a.env_offset + env, tid, cols + tid, Nb);
+      if (last && a.samples_out) {
+        float* out = a.samples_out + ((size_t)env * N + tid) * H;
+        for (uint32_t k = 0; k < H; ++k) out[k] = cols[(size_t)k * Nb + tid];
+      }
+    }
+    __syncthreads();                                       // every row stands (global memory, block scope)
+    GruRollout ro;
+    gru_rollout_init<F16>(ro, lds, s0, lane, h1src, h1src ? h1src + 32 : nullptr);
+    float u_next = in[0];
+    for (uint32_t k = 0; k < H; ++k) {
+      const float ur = u_next;
+      if (k + 1 < H) u_next = in[(size_t)(k + 1) * Nb];    // in flight during this step's cell
+      gru_rollout_step<COST, F16>(ro, lds, s0, x_t, te, lane, c, half1, p, nm, k, ur, none, [](float) {});
+    }
+    const float S_total = gru_rollout_total<COST>(ro, x_t, p);
+    if (last && a.S_out && owner) a.S_out[(size_t)env * N + n] = S_total;
+    rank_costs_at(key, order, n, S_total, owner, N, env, a.order_out, last);
+    for (uint32_t k = tid; k < H; k += Nt) cem_refit_column(cols + (size_t)k * Nb, order, a.best_k, a.stdev_min, mu[k], sd[k]);
+  }
+  __syncthreads();
+  if (tid == 0) a.Q_out[env] = mu[0];
+  for (uint32_t k = tid; k < H; k += Nt) {
+    if (a.plan_out) a.plan_out[(size_t)env * H + k] = mu[k];
+    const uint32_t kk = k + a.shift;
+    a.mean[(size_t)env * H + k] = kk < H ? mu[kk] : a.mean_fill;
+    a.stdev[(size_t)env * H + k] = kk < H ? sd[kk] : a.stdev_fill;
+  }
+}
+
 // f(cost, f16) with the handle's cost plugin and math mode as compile-time constants (std::integral_constant).  FAST:
 // float32-equivalent split products on the f16 matrix cores (cpmppi_gru16.hpp); PRECISE: exact f32 MFMA chains.
 template <class F>
@@ -389,6 +476,58 @@ int cpmppi_rollout_cost_grad_gru(cpmppi_handle* h, uint32_t E, const float* s0, 
     launch_gru_kernel<f16.value>(h, &gru_grad_forward_kernel<cost.value, f16.value>, E * a.nb, 0, (hipStream_t)stream, a);
   });
   launch_gru_grad_reverse(h, E, s0, inputs, target_position, target_equilibrium, h0, grad_out, (hipStream_t)stream);
+  return launched(h);
+}
+
+// the whole cem control step over the network: gru_cem_step_kernel, then the step counter
+int cpmppi_cem_step_gru(cpmppi_handle* h, const cpmppi_cem_gru_args* a, void* stream) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  const char* who = "cpmppi_cem_step_gru";
+  const std::string w = std::string(who) + ": ";
+  if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, w + "null argument block");
+  if (const int rc = refuse_tuning_rows(h, who)) return rc;
+  if (const int rc = gru_refusal(h, who, a->E != 0 && a->E <= h->cfg.E, "bad argument (0 < E <= config.E)",
+                                 a->s0 && a->target_position && a->target_equilibrium && a->mean && a->stdev && a->Q_out,
+                                 "null pointer (s0, target_position, target_equilibrium, mean, stdev and Q_out are required)", true))
+    return rc;
+  for (const void* ptr : {(const void*)a->s0, (const void*)a->target_position, (const void*)a->target_equilibrium, (const void*)a->h0,
+                          (const void*)a->mean, (const void*)a->stdev, (const void*)a->Q_out, (const void*)a->S_out,
+                          (const void*)a->plan_out, (const void*)a->samples_out, (const void*)a->order_out})
+    if (misaligned(ptr)) return fail(h, CPMPPI_ERR_BAD_ARG, w + "misaligned pointer");
+  if (reinterpret_cast<uintptr_t>(a->count_dev) & 7u) return fail(h, CPMPPI_ERR_BAD_ARG, w + "misaligned pointer (count_dev: 8 bytes)");
+  if (a->iterations == 0) return fail(h, CPMPPI_ERR_BAD_ARG, w + "iterations must be > 0");
+  if (a->best_k == 0 || a->best_k > h->cfg.N) return fail(h, CPMPPI_ERR_BAD_ARG, w + "bad argument (0 < best_k <= N)");
+  if (a->shift > h->cfg.H) return fail(h, CPMPPI_ERR_BAD_ARG, w + "shift exceeds the horizon");
+  if (h->cfg.N > (uint32_t)GRU_CEM_ROLLOUTS)
+    return fail(h, CPMPPI_ERR_BAD_ARG, w + "one workgroup per env holds at most " + std::to_string(GRU_CEM_ROLLOUTS) +
+                                           " samples (N = " + std::to_string(h->cfg.N) + ")");
+  CPMPPI_ON_DEVICE(h);
+  hipStream_t s = (hipStream_t)stream;
+  const size_t need = cem_floats(h, a->E, false);              // cpmppi_cem_reserve(h, E, CPMPPI_CEM_REFINE_NONE)'s
+  if (h->cem_ws_floats < need) {
+    if (const int rc = refuse_unreserved_capture(h, s, who, "cpmppi_cem_reserve")) return rc;
+    if (const int rc = grow_workspace(h, h->cem_ws, h->cem_ws_floats, need)) return rc;
+  }
+  GruCemPtrs p{};
+  p.s0 = a->s0; p.x_t = a->target_position; p.te = a->target_equilibrium; p.h0 = a->h0;
+  p.mean = a->mean; p.stdev = a->stdev; p.samples = h->cem_ws;
+  p.count_dev = (const unsigned long long*)a->count_dev;
+  p.seed = a->seed; p.offset = a->offset;
+  p.iterations = a->iterations; p.best_k = a->best_k; p.shift = a->shift; p.env_offset = a->env_offset; p.stride = rpgd_block(h);
+  p.stdev_min = a->stdev_min; p.mean_fill = a->mean_fill; p.stdev_fill = a->stdev_fill;
+  p.Q_out = a->Q_out; p.S_out = a->S_out; p.plan_out = a->plan_out; p.samples_out = a->samples_out; p.order_out = a->order_out;
+  const uint32_t threads = 64u * ((h->cfg.N + 31u) / 32u);     // one wave per 32 samples: <= GRU_CEM_BLOCK
+  const size_t tail = (2 * (size_t)GRU_CEM_ROLLOUTS + 2 * (size_t)h->cfg.H) * sizeof(float);   // key, order | mean, stdev
+  gru_dispatch(h, [&](auto cost, auto f16) {
+    constexpr int COST = decltype(cost)::value; constexpr bool F16 = decltype(f16)::value;
+    const size_t lds = GRU_ROLLOUT_IMAGE_FLOATS<F16> * sizeof(float) + tail;
+    static_assert(GRU_ROLLOUT_IMAGE_FLOATS<F16> * sizeof(float) + (2 * GRU_CEM_ROLLOUTS + 2 * CPMPPI_MAX_HORIZON) * sizeof(float) <=
+                  64 * 1024, "the step's LDS stays under the default limit at every allowed H (58 496 B at H = 1024, FAST)");
+    hipLaunchKernelGGL((gru_cem_step_kernel<COST, F16>), dim3(a->E), dim3(threads), lds, s, h->prm, p, h->gru_norm,
+                       (const float*)(F16 ? h->gru16_image : h->gru_image));
+  });
+  CPMPPI_HIP(h, hipGetLastError());
+  if (a->count_dev) launch_step_count((unsigned long long*)a->count_dev, s);
   return launched(h);
 }
 

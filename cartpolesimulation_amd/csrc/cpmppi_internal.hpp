@@ -8,7 +8,8 @@
 //   cpmppi_optim.hip      cost-only rollouts, the adjoint, Adam / SGD steps and CEM
 //   cpmppi_score.hip      the score of a recording per env (cpmppi_score_runs)
 //   cpmppi_replay.hip     control along recorded trajectories: the recorded row in the plant's place (cpmppi_replay_step)
-//   cpmppi_gru.hip        the GRU predictor in the optimizers: the fused MPPI step, cost-only rollouts, the gradient's forward sweep
+//   cpmppi_gru.hip        the GRU predictor in the optimizers: the fused MPPI step, cost-only rollouts, the gradient's forward sweep,
+//                         the fused CEM step (cpmppi_cem_step_gru)
 //   cpmppi_gru_seam.hip   its exact-cell seams: predict, advance, washout, the Brunton test's kernel
 //   cpmppi_gru_adjoint.hip  the gradient's reverse sweep
 //   cpmppi_gru_model.hip  host code only: cpmppi_set_gru packs and uploads the three weight images
@@ -23,7 +24,8 @@
 //                         stream and knot interpolation, the wave reductions: the kernel units that use them, never the host-only ones
 //   cpmppi_brunton.hpp    the Brunton test's arguments and statistics: cpmppi_seams.hip and cpmppi_gru_seam.hip only
 //   cpmppi_debug.hpp      the diagnostic builds' counters and stamps (no-ops in the product build)
-//   cpmppi_grad.hpp, cpmppi_rpgd.hpp, cpmppi_cem.hpp (cpmppi_optim.hip), cpmppi_gru.hpp, cpmppi_gru16.hpp (the GRU units)
+//   cpmppi_grad.hpp, cpmppi_rpgd.hpp (cpmppi_optim.hip), cpmppi_cem.hpp (cpmppi_optim.hip and - sampler, ranking, refit - cpmppi_gru.hip),
+//   cpmppi_gru.hpp, cpmppi_gru16.hpp (the GRU units)
 // This header includes cpmppi_params.hpp and cpmppi_step.hpp, and forward-declares what the handle only points to.
 // Kernels stay in an anonymous namespace of the unit that launches them; units call each other through host functions only.
 #pragma once
@@ -202,6 +204,14 @@ void allow_large_lds(Kernel* kernel) {
 // GRU predictor (BASELINE configs[4]): 256 threads = 4 waves x 32 rollouts
 constexpr int GRU_ROLLOUTS_PER_BLOCK = 32 * cpmppi_k::WAVES;
 
+// The one-workgroup-per-env control steps (cpmppi_rpgd_step, cpmppi_cem_step, cpmppi_cem_step_gru): the row width of their
+// workspaces - N rounded up to whole waves, a lane per plan / sample - and the floats of the CEM steps' workspace for E envs: the
+// samples; refining, also check-points (6), gradient, and Adam's two moments.
+inline uint32_t rpgd_block(const cpmppi_handle* h) { return (h->cfg.N + 63u) & ~63u; }
+inline size_t cem_floats(const cpmppi_handle* h, uint32_t E, bool refine) {
+  return (size_t)h->cfg.H * (refine ? 10 : 1) * E * rpgd_block(h);
+}
+
 // ---- host functions one unit calls in another -------------------------------------------------------------------------
 // cpmppi.hip.  check_step: every check of a step's argument block that needs no launch (cpmppi_groups_run_gather runs them for
 // all groups before its first launch).  step_impl: cpmppi_step, with the pinned ticket of cpmppi_step_host and / or the
@@ -229,6 +239,8 @@ void allow_large_lds_gru_adjoint();
 // has checked the arguments, checks the launch and reduces the partial rows
 inline size_t brunton_gru_rows(size_t starts) { return (starts + 31) / 32; }
 void launch_gru_brunton(cpmppi_handle* h, const cpmppi::BruntonArgs& a, hipStream_t s);
+// cpmppi_optim.hip: *count_dev += 1 behind a fused control step, stream-ordered (one launch of one lane); the caller checks the launch
+void launch_step_count(unsigned long long* count_dev, hipStream_t s);
 // called by cpmppi_create: the LDS opt-ins of the kernels of cpmppi_seams.hip and cpmppi_optim.hip
 void allow_large_lds_seams();
 void allow_large_lds_optim();

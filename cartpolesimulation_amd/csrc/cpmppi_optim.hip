@@ -158,39 +158,7 @@ __global__ __launch_bounds__(BLOCK) void cem_gmm_sample_kernel(const Params p, u
 
 // One block per env: sort (S, index) ascending with a bitonic network in LDS (ties by index = stable argsort), then
 // mean and population standard deviation of the best_k input sequences per time-step, stdev floored at stdev_min.
-// The order is numpy's: -inf < finite < +inf < NaN, -0.0 == +0.0 (ties by index), padding after everything - so that
-// idx[i] < N for every i < best_k <= N whatever S holds.  A float comparison is no order once a key is NaN (the network
-// would leave an arbitrary permutation, padded indices included), so the keys are order-preserving uint32 images of
-// the costs: -0.0 -> +0.0, every NaN -> 0x7FC00000, then all bits flipped if the sign bit is set, else the
-// sign bit set; the padding is 0xFFFFFFFF, which no image equals (the canonical NaN maps to 0xFFC00000).
-__device__ __forceinline__ uint32_t cem_sort_key(float s) {
-  uint32_t b = __float_as_uint(s);
-  if (b == 0x80000000u) b = 0u;                          // -0.0 -> +0.0 (on the bits: independent of the denormal mode)
-  if ((b & 0x7FFFFFFFu) > 0x7F800000u) b = 0x7FC00000u;  // every NaN -> the canonical one, above +inf's image
-  return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
-}
-
-// The same order for a block that holds one cost per lane (the fused steps: N <= blockDim.x): every active lane counts the
-// (key, index) pairs below its own among the N keys in LDS and writes order[rank] = tid - and, when `publish`, order_out[env][rank] (order_out:
-// [E][N] or NULL).  Every lane of the block calls it; order[] stands when it returns.
-__device__ __forceinline__ void rank_costs(uint32_t* key, uint32_t* order, float S, bool active, uint32_t N, uint32_t env,
-                                           uint32_t* order_out, bool publish) {
-  const uint32_t tid = threadIdx.x;
-  key[tid] = active ? cem_sort_key(S) : 0xFFFFFFFFu;
-  __syncthreads();
-  if (active) {
-    const uint32_t mine = key[tid];
-    uint32_t rank = 0;
-    for (uint32_t j = 0; j < N; ++j) {
-      const uint32_t kj = key[j];
-      rank += (kj < mine || (kj == mine && j < tid)) ? 1u : 0u;
-    }
-    order[rank] = tid;
-    if (publish && order_out) order_out[(size_t)env * N + rank] = tid;
-  }
-  __syncthreads();
-}
-
+// The order and its keys: cem_sort_key (cpmppi_cem.hpp), which the fused steps rank with as well (rank_costs).
 __global__ __launch_bounds__(BLOCK) void cem_update_kernel(const Params p, const float* __restrict__ S,
                                                            const float* __restrict__ Q, uint32_t best_k, float stdev_min,
                                                            uint32_t Np, float* __restrict__ mean_out,
@@ -323,7 +291,6 @@ void launch_rpgd(uint32_t cost_id, dim3 grid, dim3 block, size_t lds, hipStream_
   });
 }
 
-inline uint32_t rpgd_block(const cpmppi_handle* h) { return (h->cfg.N + 63u) & ~63u; }
 inline size_t rpgd_floats(const cpmppi_handle* h, uint32_t E) { return (size_t)h->cfg.H * 7 * E * rpgd_block(h); }
 inline size_t rpgd_lds_bytes(const cpmppi_handle* h) { return ((size_t)h->cfg.S * 6 + 2) * rpgd_block(h) * sizeof(float); }
 
@@ -424,10 +391,6 @@ void launch_cem(uint32_t cost_id, dim3 grid, dim3 block, size_t lds, hipStream_t
   });
 }
 
-// floats per env: the samples; refining, also check-points (6), gradient, and Adam's two moments
-inline size_t cem_floats(const cpmppi_handle* h, uint32_t E, bool refine) {
-  return (size_t)h->cfg.H * (refine ? 10 : 1) * E * rpgd_block(h);
-}
 inline size_t cem_lds_bytes(const cpmppi_handle* h, bool refine) {
   return (((size_t)(refine ? h->cfg.S * 6 : 0) + 2) * rpgd_block(h) + 2 * (size_t)h->cfg.H) * sizeof(float);
 }
@@ -441,6 +404,10 @@ void launch_grad(uint32_t cost_id, dim3 grid, size_t lds, hipStream_t st, const 
 }
 
 }  // namespace
+
+void launch_step_count(unsigned long long* count_dev, hipStream_t s) {
+  hipLaunchKernelGGL(rpgd_count_kernel, dim3(1), dim3(1), 0, s, count_dev);
+}
 
 void allow_large_lds_optim() {
   // every kernel that runs the adjoint parks S x 6 sub-states per lane in LDS (61 KB at S = 10 and 256 lanes; more substeps
@@ -604,7 +571,7 @@ int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* a, void* stream) 
   const auto launch = h->cfg.ode_predictor == CPMPPI_ODE_CROMER ? launch_rpgd<PREDICTOR_ODE> : launch_rpgd<PREDICTOR_ODE_V0>;
   launch(h->prm.cost_id, dim3(a->E), dim3(Nb), rpgd_lds_bytes(h), s, h->prm, p);
   CPMPPI_HIP(h, hipGetLastError());
-  if (a->count_dev) hipLaunchKernelGGL(rpgd_count_kernel, dim3(1), dim3(1), 0, s, (unsigned long long*)a->count_dev);
+  if (a->count_dev) launch_step_count((unsigned long long*)a->count_dev, s);
   return launched(h);
 }
 
@@ -613,7 +580,9 @@ int cpmppi_cem_reserve(cpmppi_handle* h, uint32_t E, uint32_t refine) {
   if (E == 0 || E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_reserve: bad argument (0 < E <= config.E)");
   if (refine > CPMPPI_CEM_REFINE_ADAM) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_cem_reserve: unknown refine kind");
   const bool refining = refine != CPMPPI_CEM_REFINE_NONE;
-  if (const int rc = sweep_check_handle(h, "cpmppi_cem_reserve", CEM_WORDS)) return rc;
+  // (a handle with a network reserves the samples for cpmppi_cem_step_gru, which has both math modes and checks its costs itself)
+  if (refining || !h->gru_image)
+    if (const int rc = sweep_check_handle(h, "cpmppi_cem_reserve", CEM_WORDS)) return rc;
   if (const int rc = sweep_check_shape(h, "cpmppi_cem_reserve", CEM_WORDS, cem_lds_bytes(h, refining))) return rc;
   CPMPPI_ON_DEVICE(h);
   return grow_workspace(h, h->cem_ws, h->cem_ws_floats, cem_floats(h, E, refining));
@@ -665,7 +634,7 @@ int cpmppi_cem_step(cpmppi_handle* h, const cpmppi_cem_args* a, void* stream) {
                              : (cromer ? launch_cem<PREDICTOR_ODE, false> : launch_cem<PREDICTOR_ODE_V0, false>);
   launch(h->prm.cost_id, dim3(a->E), dim3(Nb), cem_lds_bytes(h, refine), s, h->prm, p);
   CPMPPI_HIP(h, hipGetLastError());
-  if (a->count_dev) hipLaunchKernelGGL(rpgd_count_kernel, dim3(1), dim3(1), 0, s, (unsigned long long*)a->count_dev);
+  if (a->count_dev) launch_step_count((unsigned long long*)a->count_dev, s);
   return launched(h);
 }
 

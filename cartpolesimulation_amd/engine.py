@@ -1028,6 +1028,38 @@ class MPPIEngine:
         Philox offset and iteration count and enqueues the launch; with ``count_dev`` nothing changes between steps."""
         return self._build_cem_step(*args, **kwargs)
 
+    def _build_cem_step_gru(self, s0, mean, stdev, target_position, target_equilibrium, h0=None, *, iterations, best_k, stdev_min,
+                            shift=1, mean_fill=0.0, stdev_fill=0.0, seed=0, offset=0, env_offset=0, count_dev=None, Q_out=None,
+                            S_out=None, plan_out=None, samples_out=None, order_out=None):
+        """cpmppi_cem_step_gru: one whole cem control step with the network of ``set_gru`` in the rollout loop, on the sampling
+        distribution ``mean``, ``stdev`` [E,H], both updated IN PLACE (include/cpmppi.h states the step).  ``h0`` [E,2,32]: each
+        env's memory, shared by its samples (None: zeros) - read, not advanced: ``gru_advance`` hands it on.  ``count_dev`` as
+        ``cem_step``'s.  -> (Q_out[E], S_out, plan_out, samples_out, order_out), the last four as given (or None)."""
+        E = device_tensor("mean", mean, tail=(self.H,), note=_IN_PLACE).shape[0]
+        if E > self.E:
+            raise ValueError(f"mean must be [E<={self.E},{self.H}], got {tuple(mean.shape)}")
+        if device_tensor("stdev", stdev, tail=(self.H,), note=_IN_PLACE).shape[0] != E:
+            raise ValueError("stdev must have mean's shape")
+        a = _L.cpmppi_cem_gru_args()
+        inputs = self._control_inputs(E, s0, target_position, target_equilibrium, None, None)[:3]
+        a.E, a.s0, a.target_position, a.target_equilibrium = (E,) + tuple(t.data_ptr() for t in inputs)
+        h0 = self.tensor(h0, (E, 2, 32))
+        a.h0 = _addr(h0)
+        out = self._outputs(a, E, Q_out, S_out=S_out, plan_out=plan_out, samples_out=samples_out, order_out=order_out)
+        a.mean, a.stdev = mean.data_ptr(), stdev.data_ptr()
+        a.iterations, a.best_k, a.stdev_min = int(iterations), int(best_k), float(stdev_min)
+        a.shift, a.mean_fill, a.stdev_fill = int(shift), float(mean_fill), float(stdev_fill)
+        a.seed, a.offset, a.env_offset = int(seed), int(offset), int(env_offset)
+        a.count_dev = _counter("count_dev", count_dev)
+        return PreparedCall(self, self.lib.cpmppi_cem_step_gru, a, inputs + (h0, mean, stdev, count_dev) + out, out,
+                            ("offset", "iterations"))
+
+    cem_step_gru = _run_once(_build_cem_step_gru)
+
+    def prepare_cem_step_gru(self, *args, **kwargs):
+        """The argument block of ``cem_step_gru(...)`` built and validated ONCE, as ``prepare_cem_step``'s."""
+        return self._build_cem_step_gru(*args, **kwargs)
+
     # ------------------------------------------------------------------ the fused hot path
     def step(self, s0, u_nom, target_position, target_equilibrium, L=None, delta_u=None, knots=None, seed=None,
              offset=0, env_offset=0, u_prev=None, Q_out=None, S_out=None, predictor="ODE_v0", h0=None,
@@ -1112,7 +1144,7 @@ class MPPIEngine:
 
 class PreparedCall:
     """One entry point of the library that takes an argument block, ready to be enqueued any number of times
-    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_cem_step / prepare_brunton).  ``args`` is the live
+    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_cem_step / prepare_cem_step_gru / prepare_brunton).  ``args`` is the live
     ctypes block, validated when it was built, and ``ref`` the reference to it that the library is handed; ``keep`` holds the
     tensors it points into; ``enqueue`` is the entry point, ``enqueue(handle, ref, stream)``.  ``result`` is what the call returns:
     the outputs of a control step - ``out``, whose first two are ``Q_out`` and ``S_out`` -, the plant's state, or the Brunton

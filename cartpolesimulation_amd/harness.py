@@ -155,7 +155,9 @@ class BatchedCartPoleExperiment:
         .configure(...).optimizer`: cem, rpgd, gradient, ...) computes the controls instead of the fused MPPI step - host-paced, one
         `optimizer.step` per control period on device tensors, the plant / schedule / recording launch unchanged.  A FUSED rpgd /
         gradient / cem optimizer (`fused=True`: one cpmppi_rpgd_step / cpmppi_cem_step per period, its step counter on the device) is
-        not paced by the host and may be captured (``graph=True``) like the MPPI step.
+        not paced by the host and may be captured (``graph=True``) like the MPPI step; so is cem over the network
+        (`optimizer_cem(gru_model=..., gru_fused=True)`: cpmppi_cem_step_gru + cpmppi_gru_advance per period, the memory the
+        optimizer's own).  An optimizer object that runs the network reads no pole mass: a varying mass table paces no such run.
         ``predictor="GRU"``: the fused MPPI step over the engine's network (set_gru) - per control period three launches, the step
         from each experiment's memory ``h0`` [E,2,32] (None: zeros), cpmppi_gru_advance on (the MEASURED state the controller was
         given, the control it chose), the plant; launched or captured.  The result gains ``memory``, the memory after every
@@ -541,7 +543,9 @@ class ScheduleRun:
         self.eng = engine
         self.buffers = buf = ScheduleBuffers(engine, batch, u_nom0)
         self.T, self.tail = buf.T, buf.tail
-        self.mass = ControllerMass(batch, engine.mppi, network=gru)
+        # (an optimizer object that runs the network - gru_model=, its memory `h` once configured - reads no pole mass either)
+        network = gru or getattr(optimizer, "h", None) is not None or getattr(optimizer, "gru_model", None) is not None
+        self.mass = ControllerMass(batch, engine.mppi, network=network)
         self.mass.bind([engine], register=optimizer is None)       # (an optimizer object registers the row with its own engine)
         self.memory = gru_memory(engine, batch.E, h0) if gru else None
         if optimizer is None:
@@ -686,6 +690,8 @@ class ReplayRun:
             raise ValueError(REPLAY_REFUSALS["gru"])
         check_predictor(engine, predictor, None, optimizer, None)
         if optimizer is not None:
+            if getattr(optimizer, "h", None) is not None or getattr(optimizer, "gru_model", None) is not None:
+                raise ValueError(REPLAY_REFUSALS["gru"])
             if not getattr(optimizer, "fused", False):
                 raise ValueError(REPLAY_REFUSALS["host_paced"])
             if not warm_start:

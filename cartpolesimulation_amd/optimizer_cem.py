@@ -21,6 +21,13 @@ zero after a reset, handed to every cost launch of a control step, then advanced
 The two hybrids need the cost's gradient: they refuse the network unless asked with ``gru_adjoint=True``, which makes their
 refinement cpmppi_rollout_cost_grad_gru from the same memory; ``fused=True`` refuses it either way (cpmppi_cem_step integrates
 the ODE, and has no adjoint kernel for the GRU).
+
+``gru_fused=True`` (cem alone; needs the network) is the fused step over the network: ONE cpmppi_cem_step_gru per control step -
+sampling, the GRU rollouts from each env's memory, ranking and refit for all outer iterations in one kernel, bit for bit what the
+staged step above computes - followed by cpmppi_gru_advance, which moves the memory on in place with the state seen and the
+control chosen.  The object is then a fused one (``fused`` is true, ``step_device``, a device step counter): the closed loop over
+a learned model launches, or replays as a captured graph, like the fused ODE step's (harness.py).  cem-gmm and random-action are
+not fusable and the two hybrids have no fused GRU adjoint: they refuse the flag by name.
 """
 import math
 
@@ -33,19 +40,31 @@ GRU_NO_ADJOINT = ("{} needs the gradient of the cost and runs on the ODE_v0 and 
                   "(cpmppi_rollout_cost_grad_gru); cem, cem-gmm and random-action run on the GRU without it")
 GRU_NOT_FUSED = ("fused=True integrates the ODE (cpmppi_cem_step): the GRU predictor runs in the staged step of cem, cem-gmm and "
                  "random-action, fused=False")
+GRU_FUSED_ONLY_CEM = ("gru_fused=True: the fused CEM control step over the GRU predictor (cpmppi_cem_step_gru) is built for cem, "
+                      "not for {}: {}")
+GRU_FUSED_OR_FUSED = ("gru_fused=True and fused=True: fused=True is the step that integrates the ODE (cpmppi_cem_step), gru_fused=True "
+                      "the one over the network (cpmppi_cem_step_gru): give one of them")
+GRU_FUSED_NEEDS_MODEL = ("gru_fused=True is the fused step over the GRU predictor: it needs gru_model= (weights or a model folder) "
+                         "and / or a GRU-6IN-32H1-32H2-5OUT predictor_specification")
+_NO_FUSED_GRU_ADJOINT = ("there is no fused GRU adjoint; gru_adjoint=True differentiates through the network in the staged step")
 
 
 class optimizer_cem(_OptimizerBase):
     optimizer_name = "cem"
     _unknown_predictor = "the sampling optimizers run on the ODE_v0 and ODE predictors"
     _fusable = True                  # cpmppi_cem_step is built for this class (not for cem-gmm and random-action)
+    _gru_fused_refusal = None        # why cpmppi_cem_step_gru cannot run this class (cem alone has none)
 
     def __init__(self, predictor=None, cost_function=None, control_limits=None, computation_library=None, seed=None,
                  mpc_horizon=35, mpc_timestep=0.02, cem_outer_it=3, cem_initial_action_stdev=0.5, num_rollouts=200,
                  cem_stdev_min=0.01, cem_best_k=40, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
                  math_mode="fast", intermediate_steps=10, phys=None, device=0, variable_parameters=None, per_env_pole_mass=False,
-                 fused=False, gru_model=None, gru_adjoint=False, **kwargs):
+                 fused=False, gru_model=None, gru_adjoint=False, gru_fused=False, **kwargs):
+        if gru_fused and self._gru_fused_refusal:
+            raise ValueError(GRU_FUSED_ONLY_CEM.format(self.optimizer_name, self._gru_fused_refusal))
+        if gru_fused and fused:
+            raise ValueError(GRU_FUSED_OR_FUSED)
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
                          intermediate_steps, control_mode="clip", shift_mode="none", math_mode=math_mode,
@@ -62,11 +81,16 @@ class optimizer_cem(_OptimizerBase):
             self._check_gru_adjoint(self.fused)
         if self.fused and gru_model is not None:
             raise ValueError(GRU_NOT_FUSED)
+        self.gru_fused = bool(gru_fused)   # one cpmppi_cem_step_gru + cpmppi_gru_advance per control step: a fused object as well
+        self.fused = self.fused or self.gru_fused
 
     def _gru_selected(self, predictor_specification):
-        if self.fused and (is_gru_specification(predictor_specification) or self.gru_model is not None):
+        if self.fused and not self.gru_fused and (is_gru_specification(predictor_specification) or self.gru_model is not None):
             raise ValueError(GRU_NOT_FUSED)
-        return super()._gru_selected(predictor_specification)
+        neural = super()._gru_selected(predictor_specification)
+        if self.gru_fused and not neural:
+            raise ValueError(GRU_FUSED_NEEDS_MODEL)
+        return neural
 
     def _cost(self, s_t, Q, tp, te, L):
         """Costs [E,N] of the plans Q [E,N,H]: under the ODE, or - with the network - under the GRU from each env's memory."""
@@ -110,22 +134,32 @@ class optimizer_cem(_OptimizerBase):
     def _fused_call(self, s, tp, te, L, previous_input, count_dev):
         """One cpmppi_cem_step on device tensors.  The argument block is built once per set of buffers; with ``count_dev`` the
         call changes nothing on the host (iteration i of step c draws at Philox offset c * cem_outer_it + i), without it
-        ``step_counter`` advances by the iterations taken, as the staged step's does."""
+        ``step_counter`` advances by the iterations taken, as the staged step's does.
+        ``gru_fused``: one cpmppi_cem_step_gru from the memory ``h`` - the network knows no pole length and its costs read no
+        previous input, so ``L`` and ``previous_input`` go unread -, then cpmppi_gru_advance on (the state seen, the control
+        chosen): the memory is handed on the same way by ``step``, ``step_device`` and the device loop."""
+        if self.gru_fused:
+            L = previous_input = None
         key = self._fused_key(s, tp, te, L, previous_input, count_dev)
         if key != self._prepared_key:
-            self._prepared = self.engine.prepare_cem_step(
-                s, self.dist_mue, self.stdev, tp, te, L, previous_input, iterations=self.cem_outer_it, best_k=self.cem_best_k,
-                stdev_min=self.cem_stdev_min, shift=1, mean_fill=0.5 * (self.action_low + self.action_high),
-                stdev_fill=math.sqrt(0.5), seed=self.seed, offset=0, count_dev=count_dev, Q_out=self._u, S_out=self._S,
-                plan_out=self._plan, **self._fused_refine())
+            common = dict(iterations=self.cem_outer_it, best_k=self.cem_best_k, stdev_min=self.cem_stdev_min, shift=1,
+                          mean_fill=0.5 * (self.action_low + self.action_high), stdev_fill=math.sqrt(0.5), seed=self.seed, offset=0,
+                          count_dev=count_dev, Q_out=self._u, S_out=self._S, plan_out=self._plan)
+            if self.gru_fused:
+                self._prepared = self.engine.prepare_cem_step_gru(s, self.dist_mue, self.stdev, tp, te, self.h, **common)
+            else:
+                self._prepared = self.engine.prepare_cem_step(s, self.dist_mue, self.stdev, tp, te, L, previous_input, **common,
+                                                              **self._fused_refine())
             self._prepared_key = key
         if count_dev is not None:
             self._prepared.run()
-            return self._u
-        iters = self.warmup_iterations if (self.warmup and self._first) else self.cem_outer_it
-        self._first = False
-        self._prepared.run(offset=self.step_counter, iterations=iters)
-        self.step_counter += iters
+        else:
+            iters = self.warmup_iterations if (self.warmup and self._first) else self.cem_outer_it
+            self._first = False
+            self._prepared.run(offset=self.step_counter, iterations=iters)
+            self.step_counter += iters
+        if self.gru_fused:
+            self.engine.gru_advance(s, self._u, self.h)
         return self._u
 
     def _shift(self):
@@ -166,6 +200,7 @@ class optimizer_cem_gmm(optimizer_cem):
     [recalled semantics: the class lives in the absent Control_Toolkit submodule; unpinned, stated in DESIGN.md]"""
     optimizer_name = "cem-gmm"
     _fusable = False                 # (the mixture needs the previous iteration's elites as centres)
+    _gru_fused_refusal = "cem-gmm is not fusable (the mixture needs the previous iteration's elites as centres)"
 
     def optimizer_reset(self):
         super().optimizer_reset()
@@ -197,6 +232,7 @@ class optimizer_cem_naive_grad(optimizer_cem):
     before the elites are chosen.  [recalled semantics, class absent from the tree]"""
     optimizer_name = "cem-naive-grad"
     _gru_refusal = GRU_NO_ADJOINT.format("cem-naive-grad")
+    _gru_fused_refusal = _NO_FUSED_GRU_ADJOINT
 
     def __init__(self, *args, learning_rate=0.1, gradmax_clip=10, cem_outer_it=1, cem_stdev_min=0.1, **kwargs):
         super().__init__(*args, cem_outer_it=cem_outer_it, cem_stdev_min=cem_stdev_min, **kwargs)
@@ -217,6 +253,7 @@ class optimizer_cem_grad_bharadhwaj(optimizer_cem):
     [recalled semantics, class absent from the tree]"""
     optimizer_name = "cem-grad-bharadhwaj"
     _gru_refusal = GRU_NO_ADJOINT.format("cem-grad-bharadhwaj")
+    _gru_fused_refusal = _NO_FUSED_GRU_ADJOINT
 
     def __init__(self, *args, learning_rate=0.05, adam_beta_1=0.9, adam_beta_2=0.999, adam_epsilon=1.0e-8, num_rollouts=32,
                  cem_best_k=8, cem_outer_it=2, cem_initial_action_stdev=2, cem_stdev_min=1.0e-6, gradmax_clip=5, **kwargs):
@@ -249,6 +286,7 @@ class optimizer_random_action(optimizer_cem):
     [recalled semantics, class absent from the tree]"""
     optimizer_name = "random-action"
     _fusable = False
+    _gru_fused_refusal = "random-action is not fusable (it draws uniform plans and keeps no distribution)"
 
     def __init__(self, *args, num_rollouts=640, **kwargs):
         kwargs.pop("cem_outer_it", None)

@@ -293,8 +293,8 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
     ``optimizer``: one of the package's optimizer objects configured for the run's experiments (`controller_mpc(config_root=...,
     num_envs=n).configure().optimizer` - the shipped config_controllers.yml names rpgd) controls the plants instead of the fused MPPI
     step; `engine` may then be None (the optimizer's own engine runs the plant).  A staged optimizer is paced by the host
-    (graph=False); a fused rpgd / gradient / cem optimizer (`fused=True`) may run captured (graph=True).  Env groups and the multi-GPU
-    gather stay with the MPPI step.
+    (graph=False); a fused rpgd / gradient / cem optimizer (`fused=True`) may run captured (graph=True), and so may cem over a
+    learned model, `optimizer_cem(gru_model=..., gru_fused=True)`.  Env groups and the multi-GPU gather stay with the MPPI step.
     ``gru_model``: the weights dict of ``MPPIEngine.set_gru`` or a ``GRU-6IN-32H1-32H2-5OUT-*`` model folder
     (model_folder.load_gru_model) - the fused MPPI step rolls out with that network instead of the equations, its memory handed
     from control period to control period on the device (harness.run_schedule(predictor="GRU")); launched or captured
@@ -410,7 +410,8 @@ def main(argv=None):
                     help="rpgd / gradient / cem / cem-naive-grad / cem-grad-bharadhwaj: the whole control step as one library call "
                          "(cpmppi_rpgd_step, cpmppi_cem_step) and the closed loop captured as a graph, the step counter on the device")
     ap.add_argument("--gru-model", default=None, metavar="FOLDER",
-                    help="a GRU-6IN-32H1-32H2-5OUT-* model folder: the MPPI step rolls out with that network (its memory stays on the "
+                    help="a GRU-6IN-32H1-32H2-5OUT-* model folder: the MPPI step - or, with --optimizer cem --fused, the fused CEM step "
+                         "(cpmppi_cem_step_gru) - rolls out with that network (its memory stays on the "
                          "device from period to period); costs quadratic_boundary_grad_minimal and default, --groups 1")
     ap.add_argument("--graph", action="store_true",
                     help="mppi: the closed loop captured as a graph of control periods, replayed (the step counter on the device)")
@@ -461,6 +462,8 @@ def main(argv=None):
     from .shard import env_shard
     n_local, device = env_shard(n_exp, world, rank)[1], int(os.environ.get("LOCAL_RANK", "0"))
     eng = None
+    # --optimizer cem --fused --gru-model FOLDER: the optimizer object takes the network itself (gru_model=, gru_fused=True)
+    gru_cem = args.gru_model is not None and bool(args.fused) and opt_name in ("cem", "cem-tf")
     if opt_name == "mppi":
         eng = MPPIEngine(n_local, cfg, phys=phys, device=device)
     else:                                                          # another optimizer of the package, built as controller_mpc builds it
@@ -476,7 +479,10 @@ def main(argv=None):
                                  f"cem-grad-bharadhwaj, not {opt_name!r}")
             if args.groups > 1:
                 raise SystemExit("--fused: env groups run the MPPI step only (--groups 1)")
-            over["fused"] = True
+            if gru_cem:                                                # cem over the network: cpmppi_cem_step_gru + cpmppi_gru_advance
+                over.update(gru_model=args.gru_model, gru_fused=True)
+            else:
+                over["fused"] = True
         ctrl = controller_mpc("CartPole", {}, control_limits=([-1.0], [1.0]), config=over, phys=phys, device=device, num_envs=n_local,
                               config_root=args.config_root)
         ctrl.configure(opt_name)
@@ -488,10 +494,10 @@ def main(argv=None):
     if args.graph and optimizer is not None and not args.fused:
         raise SystemExit(f"--graph: {opt_name!r} as a staged optimizer is paced by the host (mppi, or --fused, can be captured)")
     graph = (bool(args.fused) and not optimizer.warmup) or (bool(args.graph) and optimizer is None)
-    if args.gru_model is not None and optimizer is not None:
+    if args.gru_model is not None and optimizer is not None and not gru_cem:
         raise SystemExit(f"--gru-model: the network in the device loop is built for the fused MPPI step (--optimizer mppi), not {opt_name!r}")
     paths = generate_dataset(eng, n_exp, out, seed=seed, rank=rank, world=world, config=dg, groups=args.groups, parameters=parameters,
-                             optimizer=optimizer, graph=graph, gru_model=args.gru_model,
+                             optimizer=optimizer, graph=graph, gru_model=None if gru_cem else args.gru_model,
                              secondary_experiment_index=None if args.secondary_experiment_index < 0 else args.secondary_experiment_index)
     print(f"wrote {len(paths)} recordings under {os.path.dirname(paths[0])}")
 

@@ -55,6 +55,7 @@ extern "C" {
                                       cpmppi_set_pole_mass_rows (a new entry point: no layout and no existing semantics change);
                                       cpmppi_rpgd_step / cpmppi_rpgd_reserve / cpmppi_rpgd_args (new entry points, likewise);
                                       cpmppi_cem_step / cpmppi_cem_reserve / cpmppi_cem_args (new entry points, likewise);
+                                      cpmppi_cem_step_gru / cpmppi_cem_gru_args (a new entry point, likewise);
                                       cpmppi_gru_advance (a new entry point, likewise);
                                       cpmppi_brunton / cpmppi_brunton_args, cpmppi_gru_washout (new entry points, likewise);
                                       cpmppi_score_runs / cpmppi_score_args, cpmppi_set_tuning_rows (new entry points, likewise). */
@@ -677,6 +678,55 @@ typedef struct {
 } cpmppi_cem_args;
 int cpmppi_cem_reserve(cpmppi_handle* h, uint32_t E, uint32_t refine);
 int cpmppi_cem_step(cpmppi_handle* h, const cpmppi_cem_args* args, void* stream);
+
+/* The whole control step of cem-tf over the NEURAL predictor (cpmppi_set_gru) for E envs in ONE call: cpmppi_cem_step with
+ * cpmppi_rollout_cost_gru in the place of the ODE sweep, without the hybrids' refinement - no host synchronisation, no
+ * allocation, and - with count_dev - no launch argument that changes between control steps.  It is cpmppi_cem_sample,
+ * cpmppi_rollout_cost_gru and cpmppi_cem_update `iterations` times, then the shift, bit for bit:
+ * `c` = control steps taken before this call: *count_dev if given, else 0.
+ *   for i = 0 .. iterations-1, with the Philox offset o = offset + c * iterations + i:
+ *   1. samples[env, n, :] = what cpmppi_cem_sample(mean, stdev, seed, o, env_offset) draws for rollout n.
+ *   2. S = cpmppi_rollout_cost_gru(s0, samples, target_position, target_equilibrium, h0): every rollout of an env from the
+ *      env's memory h0[env] (NULL: zeros), in the handle's math mode (FAST: split f16, PRECISE: exact f32), control_mode applied.
+ *   3. mean, stdev = cpmppi_cem_update(S, samples, best_k, stdev_min): the same stable order (NaN last, ties by index), the
+ *      same sums in the same order.
+ *   then Q_out[env] = mean[env, 0], plan_out = mean; S_out, samples_out and order_out (the whole ranking, cheapest first; its
+ *   first best_k entries are the elite) are the LAST iteration's; mean and stdev are shifted left by `shift`, the tail
+ *   filled with mean_fill and stdev_fill; with count_dev: *count_dev += 1 after the step, stream-ordered.
+ * h0 is read, not written: the memory is handed on by cpmppi_gru_advance, so the closed loop is cpmppi_cem_step_gru,
+ * cpmppi_gru_advance(s0, Q_out, h0), cpmppi_plant_step - three calls whose arguments never change.  Reads no pole mass and no L.
+ * One workgroup per env, a pair of lanes per sample (at most 8 waves); the workspace is cpmppi_cem_reserve(h, E,
+ * CPMPPI_CEM_REFINE_NONE)'s - on a handle with a model that call accepts both math modes.
+ * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned (cpmppi_last_error: "cpmppi_cem_step_gru: ...") for: per-env tuning
+ * rows registered, no model set, E == 0 or E > config.E, a NULL s0, target_position, target_equilibrium, mean, stdev or Q_out, a
+ * cost other than quadratic_boundary_grad_minimal and default, a misaligned pointer, iterations == 0, best_k == 0 or > N,
+ * shift > H, N > 256, and a stream under capture while the workspace of cpmppi_cem_reserve is missing or too small (outside a
+ * capture the step allocates it itself). */
+typedef struct {
+  uint32_t E;                       /* active envs in this call (cpmppi_cem_gru_args) */
+  const float* s0;                  /* [E,6] */
+  const float* target_position;     /* [E] */
+  const float* target_equilibrium;  /* [E] */
+  const float* h0;                  /* [E,2,32] the network's memory per env, or NULL = zeros; read, not written */
+  float* mean;                      /* [E,H] the sampling mean, updated in place */
+  float* stdev;                     /* [E,H] the sampling stdev, updated in place */
+  uint32_t iterations;              /* outer iterations in this step */
+  uint32_t best_k;                  /* elite size, 0 < best_k <= N */
+  float stdev_min;
+  uint32_t shift;                   /* 0 .. H */
+  float mean_fill;
+  float stdev_fill;
+  uint64_t seed;                    /* Philox key of the sampler */
+  uint64_t offset;                  /* Philox offset of the first iteration (host mode), or of the first step's (device mode) */
+  uint32_t env_offset;              /* global index of env 0 */
+  uint64_t* count_dev;              /* control steps taken, in DEVICE memory (8-byte aligned), or NULL = host mode */
+  float* Q_out;                     /* [E]   the control: mean[:, 0] before the shift */
+  float* S_out;                     /* [E,N] costs of the last iteration, or NULL */
+  float* plan_out;                  /* [E,H] the mean before the shift, or NULL */
+  float* samples_out;               /* [E,N,H] the samples of the last iteration, or NULL */
+  uint32_t* order_out;              /* [E,N] the last iteration's ranking (sample rows, cheapest first), or NULL */
+} cpmppi_cem_gru_args;
+int cpmppi_cem_step_gru(cpmppi_handle* h, const cpmppi_cem_gru_args* args, void* stream);
 
 /* a16 alone: S[E,N], delta_u[E,N,H] -> weighted average [E,H] (controller_mppi_cartpole.py:306-321). */
 int cpmppi_reward_weighted_average(cpmppi_handle* h, uint32_t E, const float* S, const float* delta_u, float* out,

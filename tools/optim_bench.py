@@ -21,7 +21,12 @@ optimizers that run on it - cem-tf, cem-gmm-tf, random-action-tf - through the c
 E x N x H of --cost-only-shapes, the cost-only launch (cpmppi_rollout_cost_gru) against the fused GRU step handed the same
 [E,N,H] as delta_u with a zero nominal sequence (cpmppi_step: the same rollouts plus the MPPI update and its finalize launch) in
 ONE process, the two alternating: device time from events around batches of back-to-back launches, the median over the rounds and
-each column's min - max scatter.
+each column's min - max scatter.  Last, per E x N x H of --cem-shapes and math mode, the cem control step over the network, staged
+(optimizer_cem(gru_model=...).step: cem_outer_it x (cem_sample, cpmppi_rollout_cost_gru, cem_update), the shift, the memory through
+the predict seam) against fused (gru_fused=True: cpmppi_cem_step_gru + cpmppi_gru_advance), alternating in this one process:
+"fused" through the same ``step`` on the same device state, "fused_device" through ``step_device`` with the step counter on the
+device; per control step the device time between two events around a batch of steps and the wall time of the batch, medians over
+the rounds with min and max, and whether the fused step stays within the staged median + the staged runs' own min - max spread.
 
   python tools/optim_bench.py --gru-grad [--steps 30] [--grad-shapes 1x16x35,64x16x35,1x40x35,64x40x35]
 The GRU adjoint (same synthetic weights).  Per E x N x H of --grad-shapes (default: the rpgd and gradient-tf sizes at 1 and 64
@@ -52,6 +57,7 @@ ap.add_argument("--optimizers", default="gradient-tf,rpgd", help="with --fused: 
 ap.add_argument("--staged-repeats", type=int, default=1, help="with --fused: how many times the staged record is measured")
 ap.add_argument("--gru", action="store_true", help="the GRU predictor under cem-tf, cem-gmm-tf and random-action-tf; cost-only launch vs fused step")
 ap.add_argument("--cost-only-shapes", default="1x200x35,64x200x35,256x200x35,256x1024x50", help="with --gru: ExNxH,... (the last default: bench.py's C5)")
+ap.add_argument("--cem-shapes", default="1x200x35,64x200x35,256x200x35", help="with --gru: ExNxH,... of the staged / fused cem step (3 iterations)")
 ap.add_argument("--gru-grad", action="store_true", help="the GRU adjoint: gradient launch vs cost-only launch; rpgd and gradient-tf over the GRU vs the ODE")
 ap.add_argument("--grad-shapes", default="1x16x35,64x16x35,1x40x35,64x40x35", help="with --gru-grad: ExNxH,...")
 ap.add_argument("--datagen", default=None, help="with --fused: E,seconds of the closed-loop data generator, e.g. 256,10")
@@ -143,7 +149,7 @@ def gru_bench():
                           "ms_per_controller_step": round(dt * 1e3, 4)}), flush=True)
         opt.engine.close()
     rounds, batch = 12, 10
-    for shape in args.cost_only_shapes.split(","):
+    for shape in filter(None, args.cost_only_shapes.split(",")):
         e, n, h = (int(x) for x in shape.split("x"))
         g = np.random.Generator(np.random.SFC64(11))
         s0 = np.stack([O.create_cartpole_state(g.uniform(-0.3, 0.3), g.uniform(-0.5, 0.5), g.uniform(-0.05, 0.05), 0.0) for _ in range(e)])
@@ -174,6 +180,60 @@ def gru_bench():
             rec["cost_only_over_fused"] = round(rec["cost_only_ms"] / rec["fused_step_ms"], 4)
             print(json.dumps(rec), flush=True)
             eng.close()
+
+
+def gru_cem_bench():
+    """The cem control step over the network, staged against fused, alternating in one process (the module docstring)."""
+    from types import SimpleNamespace
+    from cartpolesimulation_amd.optimizer_cem import optimizer_cem
+    model = synthetic_gru()
+    rounds, batch = 12, 10
+    for shape in filter(None, args.cem_shapes.split(",")):
+        e, n, h = (int(x) for x in shape.split("x"))
+        g = np.random.Generator(np.random.SFC64(11))
+        s0 = np.stack([O.create_cartpole_state(g.uniform(-0.3, 0.3), g.uniform(-0.5, 0.5), g.uniform(-0.05, 0.05), 0.0) for _ in range(e)])
+        for math_mode in ("fast", "precise"):
+            opts = {}
+            for mode in ("staged", "fused", "fused_device"):
+                vp = SimpleNamespace(target_position=np.zeros(e, np.float32), target_equilibrium=np.ones(e, np.float32))
+                opts[mode] = optimizer_cem(control_limits=([-1.0], [1.0]), seed=1, num_envs=e, num_rollouts=n, mpc_horizon=h, cem_outer_it=3,
+                                           math_mode=math_mode, gru_model=model, gru_fused=mode != "staged", variable_parameters=vp)
+                opts[mode].configure()
+            states = {k: o.engine.tensor(s0) for k, o in opts.items()}
+            dev = opts["fused_device"]
+            tp, te = dev.engine.zeros(e), dev.engine.zeros(e) + 1.0
+            counter = torch.zeros(1, dtype=torch.int64, device=tp.device)
+            steps = {"staged": lambda: opts["staged"].step(states["staged"], as_tensor=True),
+                     "fused": lambda: opts["fused"].step(states["fused"], as_tensor=True),
+                     "fused_device": lambda: dev.step_device(states["fused_device"], tp, te, count_dev=counter)}
+            device_ms, wall_ms = {k: [] for k in steps}, {k: [] for k in steps}
+            for r in range(rounds + 2):                           # (the first two rounds warm up)
+                for k, fn in steps.items():
+                    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                    torch.cuda.synchronize()
+                    t0 = time.perf_counter()
+                    a.record()
+                    for _ in range(batch):
+                        fn()
+                    b.record()
+                    b.synchronize()
+                    if r >= 2:
+                        wall_ms[k].append((time.perf_counter() - t0) / batch * 1e3)
+                        device_ms[k].append(a.elapsed_time(b) / batch)
+            rec = {"bench": "gru_cem_step", "envs": e, "num_rollouts": n, "mpc_horizon": h, "iterations": 3, "math_mode": math_mode,
+                   "rounds": rounds, "steps_per_round": batch}
+            for k in steps:
+                for what, v in (("device", device_ms[k]), ("wall", wall_ms[k])):
+                    rec[f"{k}_{what}_ms"] = round(float(np.median(v)), 5)
+                    rec[f"{k}_{what}_min_max_ms"] = [round(float(min(v)), 5), round(float(max(v)), 5)]
+            for what in ("device", "wall"):
+                lo, hi = rec[f"staged_{what}_min_max_ms"]
+                for k in ("fused", "fused_device"):
+                    rec[f"{k}_over_staged_{what}"] = round(rec[f"{k}_{what}_ms"] / rec[f"staged_{what}_ms"], 4)
+                    rec[f"{k}_within_staged_spread_{what}"] = bool(rec[f"{k}_{what}_ms"] <= rec[f"staged_{what}_ms"] + (hi - lo))
+            print(json.dumps(rec), flush=True)
+            for o in opts.values():
+                o.engine.close()
 
 
 def alternating(launches, rounds=12, batch=10):
@@ -264,6 +324,7 @@ if args.gru_grad:
     sys.exit(0)
 if args.gru:
     gru_bench()
+    gru_cem_bench()
     sys.exit(0)
 for name in ("mppi", "cem-tf", "cem-gmm-tf", "cem-naive-grad-tf", "cem-grad-bharadhwaj-tf", "gradient-tf", "rpgd", "random-action-tf"):
     ctrl = controller_mpc("CartPole", {"target_position": 0.0, "target_equilibrium": 1.0, "L": 0.395},
