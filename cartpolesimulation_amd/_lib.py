@@ -31,7 +31,8 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_comm_set_stamped", "cpmppi_groups_comm_init", "cpmppi_groups_run_gather", "cpmppi_set_pole_mass_rows",
            "cpmppi_rpgd_reserve", "cpmppi_rpgd_step", "cpmppi_cem_reserve", "cpmppi_cem_step", "cpmppi_rollout_cost_gru",
            "cpmppi_rollout_cost_grad_gru", "cpmppi_gru_advance", "cpmppi_gru_washout", "cpmppi_brunton",
-           "cpmppi_score_runs", "cpmppi_set_tuning_rows", "cpmppi_replay_step", "cpmppi_cem_step_gru")
+           "cpmppi_score_runs", "cpmppi_set_tuning_rows", "cpmppi_replay_step", "cpmppi_cem_step_gru",
+           "cpmppi_rpgd_step_gru", "cpmppi_rpgd_gru_reserve")
 TUNING_ROW_FLOATS, TUNING_LBD, TUNING_SIGMA = 16, 7, 8
 SCORE_FLOATS = 5
 SCORE_COLUMNS = ("mean_abs_distance", "mean_abs_angle_deg", "mean_Q_squared", "stable_share", "first_stable_row")
@@ -83,6 +84,17 @@ class cpmppi_cem_args(C.Structure):
                 ("seed", C.c_uint64), ("offset", C.c_uint64), ("env_offset", C.c_uint32), ("count_dev", C.c_void_p),
                 ("Q_out", C.c_void_p), ("S_out", C.c_void_p), ("plan_out", C.c_void_p), ("samples_out", C.c_void_p),
                 ("order_out", C.c_void_p)]
+
+
+class cpmppi_rpgd_gru_args(C.Structure):            # cpmppi_rpgd_args without L and previous_input, + h0
+    _fields_ = [("E", C.c_uint32), ("s0", C.c_void_p), ("target_position", C.c_void_p), ("target_equilibrium", C.c_void_p),
+                ("h0", C.c_void_p), ("Q", C.c_void_p), ("m", C.c_void_p), ("v", C.c_void_p),
+                ("iterations", C.c_uint32), ("adam_iteration", C.c_uint32), ("learning_rate", C.c_float), ("beta1", C.c_float),
+                ("beta2", C.c_float), ("epsilon", C.c_float), ("gradmax_clip", C.c_float), ("keep_k", C.c_uint32),
+                ("resamp_per", C.c_uint32), ("shift", C.c_uint32), ("distribution", C.c_uint32), ("sample_mean", C.c_float),
+                ("uniform_lo", C.c_float), ("uniform_hi", C.c_float), ("seed", C.c_uint64), ("draw_offset", C.c_uint64),
+                ("env_offset", C.c_uint32), ("count", C.c_uint64), ("count_dev", C.c_void_p), ("Q_out", C.c_void_p),
+                ("S_out", C.c_void_p), ("plan_out", C.c_void_p), ("order_out", C.c_void_p)]
 
 
 class cpmppi_cem_gru_args(C.Structure):
@@ -230,6 +242,10 @@ def load():
     lib.cpmppi_cem_step.restype = C.c_int
     lib.cpmppi_cem_step_gru.argtypes = [vp, C.POINTER(cpmppi_cem_gru_args), vp]
     lib.cpmppi_cem_step_gru.restype = C.c_int
+    lib.cpmppi_rpgd_gru_reserve.argtypes = [vp, u32]
+    lib.cpmppi_rpgd_gru_reserve.restype = C.c_int
+    lib.cpmppi_rpgd_step_gru.argtypes = [vp, C.POINTER(cpmppi_rpgd_gru_args), vp]
+    lib.cpmppi_rpgd_step_gru.restype = C.c_int
     lib.cpmppi_cem_sample.argtypes = [vp, u32, vp, vp, u64, u64, u32, vp, vp]
     lib.cpmppi_cem_update.argtypes = [vp, u32, vp, vp, u32, f, vp, vp, vp, vp]
     lib.cpmppi_tiled_floats.argtypes = [vp, u32]

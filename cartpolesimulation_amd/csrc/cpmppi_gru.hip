@@ -9,113 +9,23 @@
 //                                           (gru_grad_reverse_kernel, cpmppi_gru_adjoint.hip) needs.
 //   gru_cem_step_kernel<COST,F16>           the whole cem control step over the network, one workgroup per env: the cost-only
 //                                           rollout between cem_step_kernel's sampler, ranking and refit (cpmppi_cem.hpp).
-// They share one rollout (GruRollout: gru_rollout_init, gru_rollout_step, gru_rollout_total) and differ in where a step's input
+// They share one rollout (GruRollout: gru_rollout_init, gru_rollout_step, gru_rollout_total - cpmppi_gru_rollout.hpp, which the fused
+// rpgd step of cpmppi_gru_rpgd.hip includes as well) and differ in where a step's input
 // comes from and in what becomes of the costs.  Entry points: cpmppi_rollout_cost_gru, cpmppi_rollout_cost_grad_gru, cpmppi_cem_step_gru;
 // -DCPMPPI_GRU_STAMPS: cpmppi_debug_gru_stamps (the kernels that write g_gru_stamp_sum are this unit's).
-#include <type_traits>
-#include "cpmppi_cost.hpp"
 #include "cpmppi_philox.hpp"
 #include "cpmppi_wave.hpp"
 #include "cpmppi_cem.hpp"        // the sampler's statement, the ranking and the refit of the fused CEM step
-#include "cpmppi_gru16.hpp"      // (and cpmppi_gru.hpp, cpmppi_internal.hpp)
+#include "cpmppi_gru_rollout.hpp"   // GruRollout, gru_dispatch (and cpmppi_cost.hpp, cpmppi_gru16.hpp, cpmppi_gru.hpp, cpmppi_internal.hpp)
 
 using namespace cpmppi_k;
 
 namespace {
 
-// The weights image of the two rollout kernels: the f16 split (FAST) or the exact f32 fragments.
-template <bool F16>
-constexpr int GRU_ROLLOUT_IMAGE_FLOATS = F16 ? G16_IMAGE_BYTES / 4 : GRU_IMAGE_FLOATS;
-
-// One rollout on its pair of lanes (c and c + 32 of a wave) through the horizon, as gru_rollout_cost_kernel and
-// gru_cost_only_kernel carry it: set-up, one control step, cost epilogue.  How a step's input is obtained is the kernel's.
-// GruRollout holds what a step changes.  What stays - the image `lds`, the env's state `s0`, the targets, `lane`, `c` = lane & 31,
-// `half1` = lane >= 32 - is handed to the three functions as plain arguments without __restrict__: as members of the state, or as
-// noalias arguments, the PRECISE horizon loop compiled to another schedule (0.3 % slower at 1 x 200 x 35); like this it is the
-// loop the kernels had with these statements written out in each of them.
-struct GruRollout {
-  float st[6];
-  float cost, cosang;
-  f16v x, h1, h2;
-  GruCarry carry;          // PRECISE
-  Gru16Carry carry16;      // FAST, with gs
-  Gru16State gs;
-};
-
-// development aid (-DCPMPPI_GRU_STAMPS): the stamp sums a step adds to.  The fused kernel publishes them; the cost-only kernel has no
-// stamps of its own and hands the cell an object it drops (the stamped cell takes no other form).  Empty in product builds.
+// development aid (-DCPMPPI_GRU_STAMPS): the stamp sums the fused MPPI kernel publishes (GruStamps: cpmppi_gru_rollout.hpp)
 #ifdef CPMPPI_GRU_STAMPS
 __device__ unsigned long long g_gru_stamp_sum[8];
 #endif
-struct GruStamps {
-#ifdef CPMPPI_GRU_STAMPS
-  unsigned long long acc[6] = {0, 0, 0, 0, 0, 0};
-  unsigned long long prev = 0;
-#endif
-};
-
-// h1src, h2src: the env's two hidden states [32] or NULL = 0
-template <bool F16>
-__device__ __forceinline__ void gru_rollout_init(GruRollout& r, const float* lds, const float* s0, uint32_t lane,
-                                                 const float* h1src, const float* h2src) {
-  r.h1 = gru_load_hidden(h1src, lane);
-  r.h2 = gru_load_hidden(h2src, lane);
-  for (int i = 0; i < 6; ++i) r.st[i] = s0[i];
-  r.cost = 0.0f;
-  r.cosang = cosf(s0[0]);                 // the plugins take cos(angle) of the given state at stage 0
-  if constexpr (F16) {
-    r.gs.h1 = r.h1; r.gs.h2 = r.h2;
-    gru16_carry_init(reinterpret_cast<const char*>(lds), r.gs, lane, r.carry16);
-  } else {
-    gru_carry_init(lds, r.h1, lane, r.carry);
-  }
-}
-
-// Control step k with the input `ur`: clamp, stage cost, `after_stage(ur)` (what else the kernel accumulates from the clamped
-// input), then the cell, the output state and the feedback.
-template <int COST, bool F16, class AfterStage>
-__device__ __forceinline__ void gru_rollout_step(GruRollout& r, const float* lds, const float* s0, float x_t, float te,
-                                                 uint32_t lane, uint32_t c, bool half1, const Params& p, const GruNorm& nm,
-                                                 uint32_t k, float ur, GruStamps& stamps, AfterStage&& after_stage) {
-  if (p.control_mode == CPMPPI_CONTROL_CLIP) ur = clamp_(ur, p.lo, p.hi);
-  if constexpr (COST == COST_QBGM) r.cost += stage_qbgm<float, F16>(p, r.st[4], r.cosang, r.st[1], ur, x_t, te);
-  else r.cost += stage_default<float, F16>(p, r.st[4], r.cosang, ur, x_t, te);
-  after_stage(ur);
-  if (k == 0) r.x = gru_input_tile(nm, s0, ur, lane);
-  else if (half1) r.x[1] = __builtin_fmaf(ur, nm.in_scale[0], nm.in_shift[0]);
-  float out[5];
-  if constexpr (F16) {
-    const char* ldsb = reinterpret_cast<const char*>(lds);
-#ifdef CPMPPI_GRU_STAMPS
-    const f16v o = gru16_step(ldsb, r.x, r.gs, r.carry16, lane, stamps.acc, stamps.prev);
-#else
-    const f16v o = gru16_step(ldsb, r.x, r.gs, r.carry16, lane);
-#endif
-    out[0] = o[0]; out[1] = o[1]; out[2] = o[2]; out[3] = o[3];
-    out[4] = __shfl(o[0], (int)(c + 32u), 64);           // positionD (row 4) lives on the partner lane-half
-    if (half1) out[4] = o[0];
-  } else {
-#ifdef CPMPPI_GRU_STAMPS
-    gru_step_pipelined(lds, r.x, r.h1, r.h2, r.carry, lane, out, stamps.acc, stamps.prev);
-#else
-    gru_step_pipelined(lds, r.x, r.h1, r.h2, r.carry, lane, out);
-#endif
-  }
-  gru_output_state_fast(nm, out, r.st, r.cosang);
-  // normalised outputs are fed back unchanged: rows 0..3 on lane-half 0, row 4 (and Q, row 5) on lane-half 1
-  r.x[0] = half1 ? out[4] : out[0];
-  r.x[1] = half1 ? 0.0f : out[1];
-  r.x[2] = half1 ? 0.0f : out[2];
-  r.x[3] = half1 ? 0.0f : out[3];
-}
-
-// The rollout's cost after the last step: stage costs + terminal cost, reduced over the horizon.
-template <int COST>
-__device__ __forceinline__ float gru_rollout_total(GruRollout& r, float x_t, const Params& p) {
-  r.st[0] = atan2f(r.st[3], r.st[2]);       // predictors_customization.py:121-127, needed for the terminal cost only
-  const float term = (COST == COST_DEFAULT) ? terminal_indicator<float>(p, r.st[0], r.st[4], x_t) : 0.0f;
-  return (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? (r.cost + term) : (r.cost + term) / (float)(p.H + 1);
-}
 
 // Fused MPPI step with the GRU predictor: same contract as rollout_cost_kernel (plugin costs), h0[E,2,32] or NULL.
 template <int COST, int NOISE, bool F16>
@@ -305,12 +215,7 @@ __global__ __launch_bounds__(BLOCK, GRU_MIN_WAVES) void gru_grad_forward_kernel(
     const float ur = u_next;
     if (k + 1 < H) u_next = in[k + 1];                     // in flight during this step's cell
     gru_rollout_step<COST, F16>(ro, lds, s0, x_t, te, lane, c, half1, p, nm, k, ur, none, [](float) {});
-    if (k + 1 < H && live) {                               // rows >= N are never written
-      gru_park_tile(ck + (half1 ? 16 : 0), F16 ? ro.gs.h1 : ro.h1);
-      gru_park_tile(ck + 32 + (half1 ? 16 : 0), F16 ? ro.gs.h2 : ro.h2);
-      if (!half1) *reinterpret_cast<f4v*>(ck + 64) = f4v{ro.x[0], ro.x[1], ro.x[2], ro.x[3]};
-      else ck[68] = ro.x[0];
-    }
+    if (k + 1 < H && live) gru_rollout_park<F16>(ro, ck, half1);   // rows >= N are never written
     ck += ck_step;
   }
   const float S_total = gru_rollout_total<COST>(ro, x_t, p);
@@ -399,17 +304,6 @@ __global__ __launch_bounds__(GRU_CEM_BLOCK, GRU_MIN_WAVES) void gru_cem_step_ker
     a.mean[(size_t)env * H + k] = kk < H ? mu[kk] : a.mean_fill;
     a.stdev[(size_t)env * H + k] = kk < H ? sd[kk] : a.stdev_fill;
   }
-}
-
-// f(cost, f16) with the handle's cost plugin and math mode as compile-time constants (std::integral_constant).  FAST:
-// float32-equivalent split products on the f16 matrix cores (cpmppi_gru16.hpp); PRECISE: exact f32 MFMA chains.
-template <class F>
-void gru_dispatch(const cpmppi_handle* h, F&& f) {
-  const bool q = h->prm.cost_id == CPMPPI_COST_QBGM;
-  const std::integral_constant<int, COST_QBGM> Q;
-  const std::integral_constant<int, COST_DEFAULT> D;
-  if (h->cfg.math_mode == CPMPPI_MATH_FAST && h->gru16_image) q ? f(Q, std::true_type{}) : f(D, std::true_type{});
-  else q ? f(Q, std::false_type{}) : f(D, std::false_type{});
 }
 
 // One launch of a rollout kernel (Params, ptrs, GruNorm, image, tail...) on the weights image of its math mode, with `lds_extra`

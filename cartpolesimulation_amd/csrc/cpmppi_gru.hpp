@@ -285,7 +285,7 @@ __device__ __forceinline__ void gru_output_state(const GruNorm& nm, const f16v& 
 
 }  // namespace cpmppi
 
-// ---- what more than one GRU unit needs (cpmppi_gru.hip, cpmppi_gru_seam.hip, cpmppi_gru_adjoint.hip) ------------------------------
+// ---- what more than one GRU unit needs (cpmppi_gru.hip, cpmppi_gru_seam.hip, cpmppi_gru_adjoint.hip, cpmppi_gru_rpgd.hip) ------------------------------
 // What the entry points refuse before they launch, in this order: no model, a size out of range, a required pointer missing and,
 // where the entry point costs the rollouts, a cost plugin the GRU kernels are not built for.
 inline int gru_refusal(cpmppi_handle* h, const char* who, bool size_ok, const char* size_msg, bool ptrs_ok, const char* ptrs_msg,

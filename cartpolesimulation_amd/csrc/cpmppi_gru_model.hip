@@ -153,6 +153,7 @@ int cpmppi_set_gru(cpmppi_handle* h, const cpmppi_gru_model* m) try {
   if (!h->gru_t_image) CPMPPI_HIP(h, hipMalloc(&h->gru_t_image, imgt.size() * sizeof(float)));
   CPMPPI_HIP(h, hipMemcpy(h->gru_t_image, imgt.data(), imgt.size() * sizeof(float), hipMemcpyHostToDevice));
   allow_large_lds_gru_adjoint();      // (both images in LDS: beyond the default 64 KB)
+  allow_large_lds_gru_rpgd();         // (... and the fused rpgd step keeps the rollout's image beside them)
   if (!h->gru16_image) CPMPPI_HIP(h, hipMalloc(&h->gru16_image, img16.size()));
   CPMPPI_HIP(h, hipMemcpy(h->gru16_image, img16.data(), img16.size(), hipMemcpyHostToDevice));
   return CPMPPI_OK;

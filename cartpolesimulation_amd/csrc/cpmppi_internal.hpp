@@ -12,6 +12,8 @@
 //                         the fused CEM step (cpmppi_cem_step_gru)
 //   cpmppi_gru_seam.hip   its exact-cell seams: predict, advance, washout, the Brunton test's kernel
 //   cpmppi_gru_adjoint.hip  the gradient's reverse sweep
+//   cpmppi_gru_rpgd.hip   the fused rpgd / gradient-tf step over the GRU predictor (cpmppi_rpgd_step_gru): forward sweep, reverse sweep,
+//                         Adam, ranking, resampling and shift in one kernel
 //   cpmppi_gru_model.hip  host code only: cpmppi_set_gru packs and uploads the three weight images
 //   cpmppi_comm.hip, cpmppi_groups.hip, cpmppi_io.hip   host code only: the collective, env groups, the recording writer
 //   cpmppi_rollout_*.hip  the instances of rollout_cost_kernel, each unit with its own compiler flags
@@ -24,8 +26,9 @@
 //                         stream and knot interpolation, the wave reductions: the kernel units that use them, never the host-only ones
 //   cpmppi_brunton.hpp    the Brunton test's arguments and statistics: cpmppi_seams.hip and cpmppi_gru_seam.hip only
 //   cpmppi_debug.hpp      the diagnostic builds' counters and stamps (no-ops in the product build)
-//   cpmppi_grad.hpp, cpmppi_rpgd.hpp (cpmppi_optim.hip), cpmppi_cem.hpp (cpmppi_optim.hip and - sampler, ranking, refit - cpmppi_gru.hip),
-//   cpmppi_gru.hpp, cpmppi_gru16.hpp (the GRU units)
+//   cpmppi_grad.hpp, cpmppi_rpgd.hpp (cpmppi_optim.hip, cpmppi_gru_rpgd.hip), cpmppi_cem.hpp (cpmppi_optim.hip and - sampler, ranking,
+//   refit - cpmppi_gru.hip, cpmppi_gru_rpgd.hip), cpmppi_gru.hpp, cpmppi_gru16.hpp (the GRU units), cpmppi_gru_rollout.hpp (GruRollout:
+//   cpmppi_gru.hip, cpmppi_gru_rpgd.hip), cpmppi_gru_reverse.hpp (the reverse sweep: cpmppi_gru_adjoint.hip, cpmppi_gru_rpgd.hip)
 // This header includes cpmppi_params.hpp and cpmppi_step.hpp, and forward-declares what the handle only points to.
 // Kernels stay in an anonymous namespace of the unit that launches them; units call each other through host functions only.
 #pragma once
@@ -89,7 +92,8 @@ struct cpmppi_handle {
   float* gru_image = nullptr;          // device copy of the LDS fragment image (cpmppi_set_gru)
   void* gru16_image = nullptr;         // device copy of the f16 split image (cpmppi_gru16.hpp)
   float* gru_t_image = nullptr;        // device copy of the transposed fragment image (the reverse sweep of cpmppi_rollout_cost_grad_gru)
-  float* gru_grad_ws = nullptr;        // [H][GRU_CKPT_FLOATS][E*N] check-points of cpmppi_rollout_cost_grad_gru (allocated on first use)
+  float* gru_grad_ws = nullptr;        // [H][GRU_CKPT_FLOATS][E*N] check-points of cpmppi_rollout_cost_grad_gru (allocated on first use);
+                                       // cpmppi_rpgd_gru_reserve: the same, then the gradient [E*N][H] of cpmppi_rpgd_step_gru
   size_t gru_grad_ws_floats = 0;
   float* brunton_ws = nullptr;         // [rows][horizon][6][3] partial statistics of cpmppi_brunton (allocated on first use, grown on demand)
   size_t brunton_ws_floats = 0;
@@ -204,7 +208,8 @@ void allow_large_lds(Kernel* kernel) {
 // GRU predictor (BASELINE configs[4]): 256 threads = 4 waves x 32 rollouts
 constexpr int GRU_ROLLOUTS_PER_BLOCK = 32 * cpmppi_k::WAVES;
 
-// The one-workgroup-per-env control steps (cpmppi_rpgd_step, cpmppi_cem_step, cpmppi_cem_step_gru): the row width of their
+// The one-workgroup-per-env control steps (cpmppi_rpgd_step, cpmppi_cem_step, cpmppi_cem_step_gru; not cpmppi_rpgd_step_gru, whose rows
+// are the staged adjoint's): the row width of their
 // workspaces - N rounded up to whole waves, a lane per plan / sample - and the floats of the CEM steps' workspace for E envs: the
 // samples; refining, also check-points (6), gradient, and Adam's two moments.
 inline uint32_t rpgd_block(const cpmppi_handle* h) { return (h->cfg.N + 63u) & ~63u; }
@@ -235,6 +240,8 @@ void launch_gru_rollout(cpmppi_handle* h, const cpmppi_step_args* a, const cpmpp
 void launch_gru_grad_reverse(cpmppi_handle* h, uint32_t E, const float* s0, const float* inputs, const float* x_t, const float* te,
                              const float* h0, float* grad, hipStream_t s);
 void allow_large_lds_gru_adjoint();
+// cpmppi_gru_rpgd.hip: the LDS opt-in of the fused rpgd / gradient step over the network (cpmppi_set_gru)
+void allow_large_lds_gru_rpgd();
 // cpmppi_gru_seam.hip: the Brunton test's GRU kernel (one partial row per wave of 32 starts: brunton_gru_rows of them); the caller
 // has checked the arguments, checks the launch and reduces the partial rows
 inline size_t brunton_gru_rows(size_t starts) { return (starts + 31) / 32; }

@@ -205,9 +205,7 @@ __global__ __launch_bounds__(BLOCK) void cem_update_kernel(const Params p, const
 // The fused rpgd / gradient-tf control step (cpmppi_rpgd_step; device pieces in cpmppi_rpgd.hpp).  One workgroup = one env,
 // one lane = one plan; the block is N rounded up to whole waves, the surplus lanes only keep the barriers company.  A lane
 // carries its own row of Q, m, v through `iterations` x (adjoint sweep + Adam) and the final forward sweep: nothing crosses
-// lanes until the ranking (rank_costs: the stable order of cem_update_kernel).  Permutation + shift run column by column: every
-// lane reads column k + shift of its SOURCE row, the block meets, every lane writes column k of its OWN row; columns <= k are
-// never read again, so one barrier per column.
+// lanes until the ranking (rank_costs: the stable order of cem_update_kernel).  Permutation + shift: rpgd_permute_shift.
 struct RpgdPtrs {
   const float* s0; const float* x_t; const float* te; const float* L; const float* prev_in; const float* m_pole;
   float* Q; float* m; float* v;
@@ -258,28 +256,7 @@ __global__ __launch_bounds__(BLOCK) void rpgd_step_kernel(const Params p, const 
   if (tid == 0) a.Q_out[env] = best[0];
   if (a.plan_out) for (uint32_t k = tid; k < H; k += Nb) a.plan_out[(size_t)env * H + k] = best[k];
 
-  const bool resample = a.resamp_per > 0 && a.keep_k < N && (c + 1) % a.resamp_per == 0;
-  if (!resample && a.shift == 0) return;             // (block-uniform)
-  const bool fresh = resample && tid >= a.keep_k;
-  const size_t src = ((size_t)env * N + ((resample && tid < a.keep_k) ? order[tid] : tid)) * H;
-  const uint64_t draw = a.draw_offset + (a.count_dev ? c / (a.resamp_per ? a.resamp_per : 1u) : 0ull);
-  RpgdFresh fr;
-  for (uint32_t k = 0; k < H; ++k) {
-    const uint32_t kk = k + a.shift;
-    const bool inside = kk < H;
-    const uint32_t kq = inside ? kk : H - 1;         // Q repeats its last element
-    float q = 0.0f, mk = 0.0f, vk = 0.0f;
-    if (active) {
-      if (fresh) {
-        q = rpgd_fresh(fr, p, a.seed, draw, a.env_offset + env, tid, kq, a.uniform != 0u, a.sample_mean, a.uniform_lo, a.uniform_hi);
-      } else {
-        q = a.Q[src + kq];
-        if (inside) { mk = a.m[src + kk]; vk = a.v[src + kk]; }
-      }
-    }
-    __syncthreads();
-    if (active) { a.Q[row + k] = q; a.m[row + k] = mk; a.v[row + k] = vk; }
-  }
+  rpgd_permute_shift(p, a, env, tid, active, c, order);
 }
 
 __global__ void rpgd_count_kernel(unsigned long long* c) { *c += 1ull; }

@@ -1,5 +1,5 @@
-// The per-lane pieces of the fused rpgd / gradient-tf control step (rpgd_step_kernel, cpmppi_optim.hip; contract:
-// cpmppi_rpgd_step in include/cpmppi.h) beside the adjoint sweep of cpmppi_grad.hpp: one lane owns one plan of one env and carries
+// The per-lane pieces of the fused rpgd / gradient-tf control steps (rpgd_step_kernel, cpmppi_optim.hip; contract:
+// cpmppi_rpgd_step in include/cpmppi.h - and gru_rpgd_step_kernel, cpmppi_gru_rpgd.hip, over the GRU predictor: cpmppi_rpgd_step_gru) beside the adjoint sweep of cpmppi_grad.hpp: one lane owns one plan of one env and carries
 // it through the sweep, the Adam update and the redraw.  The sweep's check-points and gradient are a workspace slice of the env,
 // lane-contiguous with the block's width as the stride.
 #pragma once
@@ -65,6 +65,41 @@ __device__ __forceinline__ float rpgd_fresh(RpgdFresh& f, const Params& p, uint6
     q = (mean != 0.0f) ? z + mean : z;
   }
   return clamp_(q, p.lo, p.hi);
+}
+
+// What follows the ranking in a fused rpgd / gradient step (rpgd_step_kernel; gru_rpgd_step_kernel, cpmppi_gru_rpgd.hip), for the
+// lane that owns plan row `tid` of `env` (`active`: tid < N) - every lane of the block calls it.  `a`: the kernel's pointer block
+// (Q, m, v, keep_k, resamp_per, shift, the redraw's fields as RpgdPtrs names them), `c` the control steps taken before this one,
+// order[]: the ranking.  The survivor permutation, the redraw and the shift run column by column: every lane reads column
+// k + shift of its SOURCE row, the block meets, every lane writes column k of its OWN row; columns <= k are never read again, so
+// one barrier per column.  (Block-uniform: without a resampling and a shift nothing is done and no barrier is met.)
+template <class Ptrs>
+__device__ __forceinline__ void rpgd_permute_shift(const Params& p, const Ptrs& a, uint32_t env, uint32_t tid, bool active,
+                                                   uint64_t c, const uint32_t* order) {
+  const uint32_t N = p.N, H = p.H;
+  const size_t row = ((size_t)env * N + tid) * H;
+  const bool resample = a.resamp_per > 0 && a.keep_k < N && (c + 1) % a.resamp_per == 0;
+  if (!resample && a.shift == 0) return;             // (block-uniform)
+  const bool fresh = resample && tid >= a.keep_k;
+  const size_t src = ((size_t)env * N + ((resample && tid < a.keep_k) ? order[tid] : tid)) * H;
+  const uint64_t draw = a.draw_offset + (a.count_dev ? c / (a.resamp_per ? a.resamp_per : 1u) : 0ull);
+  RpgdFresh fr;
+  for (uint32_t k = 0; k < H; ++k) {
+    const uint32_t kk = k + a.shift;
+    const bool inside = kk < H;
+    const uint32_t kq = inside ? kk : H - 1;         // Q repeats its last element
+    float q = 0.0f, mk = 0.0f, vk = 0.0f;
+    if (active) {
+      if (fresh) {
+        q = rpgd_fresh(fr, p, a.seed, draw, a.env_offset + env, tid, kq, a.uniform != 0u, a.sample_mean, a.uniform_lo, a.uniform_hi);
+      } else {
+        q = a.Q[src + kq];
+        if (inside) { mk = a.m[src + kk]; vk = a.v[src + kk]; }
+      }
+    }
+    __syncthreads();
+    if (active) { a.Q[row + k] = q; a.m[row + k] = mk; a.v[row + k] = vk; }
+  }
 }
 
 }  // namespace cpmppi

@@ -982,6 +982,52 @@ class MPPIEngine:
         iterations=)`` updates the host counters and enqueues the launch; with ``count_dev`` nothing changes between steps."""
         return self._build_rpgd_step(*args, **kwargs)
 
+    def rpgd_gru_reserve(self, E=None):
+        """cpmppi_rpgd_gru_reserve: the workspace of ``rpgd_step_gru`` (check-points and gradient of the handle's largest launch;
+        E, default all envs, is checked).  After it the step never allocates - required before a step is captured into a graph."""
+        self._check(self.lib.cpmppi_rpgd_gru_reserve(self._h, self.E if E is None else int(E)))
+
+    def _build_rpgd_step_gru(self, s0, Q, m, v, target_position, target_equilibrium, h0=None, *, iterations, learning_rate,
+                             beta1=0.9, beta2=0.999, epsilon=1e-8, gradmax_clip=0.0, keep_k=None, resamp_per=0, shift=1,
+                             distribution="normal", sample_mean=0.0, uniform_lo=0.0, uniform_hi=0.0, seed=0, draw_offset=0,
+                             env_offset=0, count=0, adam_iteration=0, count_dev=None, Q_out=None, S_out=None, plan_out=None,
+                             order_out=None):
+        """cpmppi_rpgd_step_gru: one whole rpgd / gradient-tf control step with the network of ``set_gru`` in the rollout loop and
+        its adjoint in the gradient, on the plans ``Q`` and the Adam moments ``m``, ``v`` [E,N,H], all three updated IN PLACE
+        (include/cpmppi.h states the step; N <= 128).  ``h0`` [E,2,32]: each env's memory, shared by its plans (None: zeros) -
+        read, not advanced: ``gru_advance`` hands it on.  ``count_dev`` and the host counters as ``rpgd_step``'s.
+        -> (Q_out[E], S_out, plan_out, order_out), the last three as given (or None)."""
+        E = device_tensor("Q", Q, tail=(self.N, self.H), note=_IN_PLACE).shape[0]
+        if E > self.E:
+            raise ValueError(f"Q must be [E<={self.E},{self.N},{self.H}], got {tuple(Q.shape)}")
+        for name, t in (("m", m), ("v", v)):
+            if device_tensor(name, t, tail=(self.N, self.H), note=_IN_PLACE).shape[0] != E:
+                raise ValueError(f"{name} must have Q's shape")
+        if distribution not in ("normal", "uniform"):
+            raise ValueError(f"distribution={distribution!r}; expected 'normal' or 'uniform'")
+        a = _L.cpmppi_rpgd_gru_args()
+        inputs = self._control_inputs(E, s0, target_position, target_equilibrium, None, None)[:3]
+        a.E, a.s0, a.target_position, a.target_equilibrium = (E,) + tuple(t.data_ptr() for t in inputs)
+        h0 = self.tensor(h0, (E, 2, 32))
+        a.h0 = _addr(h0)
+        out = self._outputs(a, E, Q_out, S_out=S_out, plan_out=plan_out, order_out=order_out)
+        a.Q, a.m, a.v = Q.data_ptr(), m.data_ptr(), v.data_ptr()
+        a.iterations, a.adam_iteration = int(iterations), int(adam_iteration)
+        _set_adam(a, learning_rate, beta1, beta2, epsilon, gradmax_clip)
+        a.keep_k, a.resamp_per, a.shift = int(self.N if keep_k is None else keep_k), int(resamp_per), int(shift)
+        a.distribution = _L.RPGD_UNIFORM if distribution == "uniform" else _L.RPGD_NORMAL
+        a.sample_mean, a.uniform_lo, a.uniform_hi = float(sample_mean), float(uniform_lo), float(uniform_hi)
+        a.seed, a.draw_offset, a.env_offset, a.count = int(seed), int(draw_offset), int(env_offset), int(count)
+        a.count_dev = _counter("count_dev", count_dev)
+        return PreparedCall(self, self.lib.cpmppi_rpgd_step_gru, a, inputs + (h0, Q, m, v, count_dev) + out, out,
+                            ("count", "adam_iteration", "draw_offset", "iterations"))
+
+    rpgd_step_gru = _run_once(_build_rpgd_step_gru)
+
+    def prepare_rpgd_step_gru(self, *args, **kwargs):
+        """The argument block of ``rpgd_step_gru(...)`` built and validated ONCE, as ``prepare_rpgd_step``'s."""
+        return self._build_rpgd_step_gru(*args, **kwargs)
+
     # ------------------------------------------------------------------ the fused CEM control step
     _CEM_REFINE = {None: _L.CEM_REFINE_NONE, "none": _L.CEM_REFINE_NONE, "sgd": _L.CEM_REFINE_SGD, "adam": _L.CEM_REFINE_ADAM}
 
@@ -1144,7 +1190,7 @@ class MPPIEngine:
 
 class PreparedCall:
     """One entry point of the library that takes an argument block, ready to be enqueued any number of times
-    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_cem_step / prepare_cem_step_gru / prepare_brunton).  ``args`` is the live
+    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_rpgd_step_gru / prepare_cem_step / prepare_cem_step_gru / prepare_brunton).  ``args`` is the live
     ctypes block, validated when it was built, and ``ref`` the reference to it that the library is handed; ``keep`` holds the
     tensors it points into; ``enqueue`` is the entry point, ``enqueue(handle, ref, stream)``.  ``result`` is what the call returns:
     the outputs of a control step - ``out``, whose first two are ``Q_out`` and ``S_out`` -, the plant's state, or the Brunton

@@ -157,7 +157,8 @@ class BatchedCartPoleExperiment:
         gradient / cem optimizer (`fused=True`: one cpmppi_rpgd_step / cpmppi_cem_step per period, its step counter on the device) is
         not paced by the host and may be captured (``graph=True``) like the MPPI step; so is cem over the network
         (`optimizer_cem(gru_model=..., gru_fused=True)`: cpmppi_cem_step_gru + cpmppi_gru_advance per period, the memory the
-        optimizer's own).  An optimizer object that runs the network reads no pole mass: a varying mass table paces no such run.
+        optimizer's own), and rpgd and gradient over it (`optimizer_rpgd / optimizer_gradient(gru_model=..., gru_fused=True)`:
+        cpmppi_rpgd_step_gru + cpmppi_gru_advance).  An optimizer object that runs the network reads no pole mass: a varying mass table paces no such run.
         ``predictor="GRU"``: the fused MPPI step over the engine's network (set_gru) - per control period three launches, the step
         from each experiment's memory ``h0`` [E,2,32] (None: zeros), cpmppi_gru_advance on (the MEASURED state the controller was
         given, the control it chose), the plant; launched or captured.  The result gains ``memory``, the memory after every

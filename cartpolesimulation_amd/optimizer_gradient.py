@@ -31,12 +31,24 @@ cpmppi_rollout_cost_grad_gru and every cost launch cpmppi_rollout_cost_gru, from
 after a reset and advances once per control step with the state seen and the control applied.  Without the flag the network is
 refused by name, as before; with it, ``fused=True`` (cpmppi_rpgd_step integrates the ODE) and quadratic_boundary_grad (no such
 cost in the GRU kernels) are.
+
+``gru_fused=True`` (off by default; needs the network) is the fused step over the network: ONE cpmppi_rpgd_step_gru per control
+step - every iteration's forward sweep from each env's memory, reverse sweep and Adam row, then the final costs, the ranking, the
+resampling and the shift in one kernel, what the staged ``gru_adjoint=True`` step computes - followed by cpmppi_gru_advance, which
+moves the memory on in place with the state seen and the control chosen.  The flag is itself the opt-in to the adjoint
+(``gru_adjoint=True`` beside it changes nothing) and makes the object a fused one (``fused`` is true, ``step_device``, a device
+step counter): the closed loop of the shipped controller over a learned model launches, or replays as a captured graph, like
+the fused ODE step's (harness.py).  At most 128 plans per env; quadratic_boundary_grad is refused as under ``gru_adjoint=True``.
 """
 import math
 
 import torch
 
 from ._optimizer_base import _OptimizerBase
+from .optimizer_cem import GRU_FUSED_NEEDS_MODEL
+
+GRU_FUSED_OR_FUSED = ("gru_fused=True and fused=True: fused=True is the step that integrates the ODE (cpmppi_rpgd_step), gru_fused=True "
+                      "the one over the network (cpmppi_rpgd_step_gru): give one of them")
 
 
 class _GradientBase(_OptimizerBase):
@@ -50,18 +62,28 @@ class _GradientBase(_OptimizerBase):
     def __init__(self, cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, sample_stdev, period,
                  num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
                  variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused=False, gru_model=None,
-                 gru_adjoint=False):
+                 gru_adjoint=False, gru_fused=False):
+        if gru_fused and fused:
+            raise ValueError(GRU_FUSED_OR_FUSED)
         # the handle's sampler draws knots ~ N(0, SQRTRHOINV / sqrt(dt)): set it to the requested stdev
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
                          intermediate_steps, control_mode="clip", shift_mode="none", math_mode="fast",
                          horizon_reduce=horizon_reduce, SQRTRHOINV=float(sample_stdev) * math.sqrt(float(mpc_timestep)),
                          period_interpolation_inducing_points=int(period), per_env_pole_mass=bool(per_env_pole_mass),
-                         gru_model=gru_model, gru_adjoint=gru_adjoint)
+                         gru_model=gru_model, gru_adjoint=bool(gru_adjoint) or bool(gru_fused))   # (gru_fused: itself the opt-in)
         self.count = 0               # control steps taken
         self.draws = 0               # sampler launches (the Philox offset)
         self.fused = bool(fused)     # one cpmppi_rpgd_step per control step instead of the staged launches
         self._check_gru_adjoint(self.fused)
+        self.gru_fused = bool(gru_fused)   # one cpmppi_rpgd_step_gru + cpmppi_gru_advance per control step: a fused object as well
+        self.fused = self.fused or self.gru_fused
+
+    def _gru_selected(self, predictor_specification):
+        neural = super()._gru_selected(predictor_specification)
+        if self.gru_fused and not neural:
+            raise ValueError(GRU_FUSED_NEEDS_MODEL)
+        return neural
 
     def _set_timestep(self, dt):
         if dt != self.cfg.mpc_timestep:          # the sampling stdev stays what the constructor was asked for
@@ -137,31 +159,44 @@ class _GradientBase(_OptimizerBase):
         raise NotImplementedError
 
     def reserve_fused(self):
-        """The fused step's workspace (cpmppi_rpgd_reserve): after it a step never allocates - required before a capture."""
-        self.engine.rpgd_reserve()
+        """The fused step's workspace (cpmppi_rpgd_reserve; over the network cpmppi_rpgd_gru_reserve): after it a step never
+        allocates - required before a capture."""
+        if self.gru_fused:
+            self.engine.rpgd_gru_reserve()
+        else:
+            self.engine.rpgd_reserve()
 
     def _fused_call(self, s, tp, te, L, previous_input, count_dev):
         """One cpmppi_rpgd_step on device tensors.  The argument block is built once per set of buffers; with ``count_dev`` the
-        call changes nothing on the host, without it the host counters advance as the staged step's do."""
+        call changes nothing on the host, without it the host counters advance as the staged step's do.
+        ``gru_fused``: one cpmppi_rpgd_step_gru from the memory ``h`` - the network knows no pole length and its costs read no
+        previous input, so ``L`` and ``previous_input`` go unread -, then cpmppi_gru_advance on (the state seen, the control
+        chosen): the memory is handed on the same way by ``step``, ``step_device`` and the device loop."""
+        if self.gru_fused:
+            L = previous_input = None
         key = self._fused_key(s, tp, te, L, previous_input, count_dev)
         if key != self._prepared_key:
-            self._prepared = self.engine.prepare_rpgd_step(
-                s, self.Q, self.m, self.v, tp, te, L, previous_input, learning_rate=self.learning_rate,
-                beta1=self.adam_beta_1, beta2=self.adam_beta_2, epsilon=self.adam_epsilon, gradmax_clip=self.gradmax_clip,
-                seed=self.seed, draw_offset=self._draw0, count_dev=count_dev, Q_out=self._u, S_out=self._S,
-                plan_out=self._plan, **self._fused_plan())
+            common = dict(learning_rate=self.learning_rate, beta1=self.adam_beta_1, beta2=self.adam_beta_2,
+                          epsilon=self.adam_epsilon, gradmax_clip=self.gradmax_clip, seed=self.seed, draw_offset=self._draw0,
+                          count_dev=count_dev, Q_out=self._u, S_out=self._S, plan_out=self._plan, **self._fused_plan())
+            if self.gru_fused:
+                self._prepared = self.engine.prepare_rpgd_step_gru(s, self.Q, self.m, self.v, tp, te, self.h, **common)
+            else:
+                self._prepared = self.engine.prepare_rpgd_step(s, self.Q, self.m, self.v, tp, te, L, previous_input, **common)
             self._prepared_key = key
         if count_dev is not None:
             self._prepared.run()
-            return self._u
-        plan = self._fused_plan()
-        iters = self.warmup_iterations if (self.warmup and self._first) else plan["iterations"]
-        self._first = False
-        self._prepared.run(count=self.count, adam_iteration=self.adam_it, draw_offset=self.draws, iterations=iters)
-        self.adam_it += iters
-        self.count += 1
-        if plan["resamp_per"] > 0 and plan["keep_k"] < self.num_rollouts and self.count % plan["resamp_per"] == 0:
-            self.draws += 1
+        else:
+            plan = self._fused_plan()
+            iters = self.warmup_iterations if (self.warmup and self._first) else plan["iterations"]
+            self._first = False
+            self._prepared.run(count=self.count, adam_iteration=self.adam_it, draw_offset=self.draws, iterations=iters)
+            self.adam_it += iters
+            self.count += 1
+            if plan["resamp_per"] > 0 and plan["keep_k"] < self.num_rollouts and self.count % plan["resamp_per"] == 0:
+                self.draws += 1
+        if self.gru_fused:
+            self.engine.gru_advance(s, self._u, self.h)
         return self._u
 
 
@@ -175,14 +210,15 @@ class optimizer_gradient(_GradientBase):
                  gradmax_clip=5, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
                  intermediate_steps=10, horizon_reduce="sum", phys=None, device=0, variable_parameters=None,
-                 per_env_pole_mass=False, fused=False, gru_model=None, gru_adjoint=False, **kwargs):
+                 per_env_pole_mass=False, fused=False, gru_model=None, gru_adjoint=False, gru_fused=False, **kwargs):
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
         self.adam_epsilon, self.gradmax_clip, self.rtol = float(adam_epsilon), float(gradmax_clip), float(rtol)
         self.gradient_steps, self.warmup, self.warmup_iterations = int(gradient_steps), bool(warmup), int(warmup_iterations)
         self.initial_action_stdev = float(initial_action_stdev)
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, initial_action_stdev,
                          10, num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
-                         variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused, gru_model, gru_adjoint)
+                         variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused, gru_model, gru_adjoint,
+                         gru_fused)
 
     def _fused_plan(self):
         return {"iterations": self.gradient_steps, "keep_k": self.num_rollouts, "resamp_per": 0, "shift": 1}
@@ -220,7 +256,7 @@ class optimizer_rpgd(_GradientBase):
                  warmup=False, warmup_iterations=250, optimizer_logging=False, calculate_optimal_trajectory=False,
                  num_envs=1, cost_function_specification=None, cost_weights=None, intermediate_steps=10,
                  horizon_reduce="sum", phys=None, device=0, variable_parameters=None, per_env_pole_mass=False, fused=False,
-                 gru_model=None, gru_adjoint=False, **kwargs):
+                 gru_model=None, gru_adjoint=False, gru_fused=False, **kwargs):
         if SAMPLING_DISTRIBUTION not in ("normal", "uniform"):
             raise ValueError(f"SAMPLING_DISTRIBUTION={SAMPLING_DISTRIBUTION!r}; expected 'normal' or 'uniform'")
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
@@ -235,7 +271,7 @@ class optimizer_rpgd(_GradientBase):
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, stdev,
                          period_interpolation_inducing_points, num_envs, cost_function_specification, cost_weights,
                          intermediate_steps, phys, device, variable_parameters, optimizer_logging, horizon_reduce,
-                         per_env_pole_mass, fused, gru_model, gru_adjoint)
+                         per_env_pole_mass, fused, gru_model, gru_adjoint, gru_fused)
 
     def _uniform_range(self):
         return (self.action_low, self.action_high) if self.sample_whole_control_space else \

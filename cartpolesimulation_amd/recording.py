@@ -269,6 +269,8 @@ def experiment_folder(root, secondary_experiment_index=None, digits=3):
 # the optimizer names whose whole control step is one library call (--fused)
 FUSED_OPTIMIZERS = ("rpgd", "rpgd-tf", "gradient", "gradient-tf", "cem", "cem-tf", "cem-naive-grad", "cem-naive-grad-tf",
                     "cem-grad-bharadhwaj", "cem-grad-bharadhwaj-tf")
+# ... and those with a fused step over the GRU predictor (--gru-fused --gru-model FOLDER): cpmppi_rpgd_step_gru, cpmppi_cem_step_gru
+GRU_FUSED_OPTIMIZERS = ("rpgd", "rpgd-tf", "gradient", "gradient-tf", "cem", "cem-tf")
 
 
 def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, seed=None, cartpole_seed=None, L=None, native=True,
@@ -293,8 +295,9 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
     ``optimizer``: one of the package's optimizer objects configured for the run's experiments (`controller_mpc(config_root=...,
     num_envs=n).configure().optimizer` - the shipped config_controllers.yml names rpgd) controls the plants instead of the fused MPPI
     step; `engine` may then be None (the optimizer's own engine runs the plant).  A staged optimizer is paced by the host
-    (graph=False); a fused rpgd / gradient / cem optimizer (`fused=True`) may run captured (graph=True), and so may cem over a
-    learned model, `optimizer_cem(gru_model=..., gru_fused=True)`.  Env groups and the multi-GPU gather stay with the MPPI step.
+    (graph=False); a fused rpgd / gradient / cem optimizer (`fused=True`) may run captured (graph=True), and so may cem, rpgd and
+    gradient over a learned model, `optimizer_cem(gru_model=..., gru_fused=True)`, `optimizer_rpgd(gru_model=..., gru_fused=True)`,
+    `optimizer_gradient(gru_model=..., gru_fused=True)`.  Env groups and the multi-GPU gather stay with the MPPI step.
     ``gru_model``: the weights dict of ``MPPIEngine.set_gru`` or a ``GRU-6IN-32H1-32H2-5OUT-*`` model folder
     (model_folder.load_gru_model) - the fused MPPI step rolls out with that network instead of the equations, its memory handed
     from control period to control period on the device (harness.run_schedule(predictor="GRU")); launched or captured
@@ -411,8 +414,14 @@ def main(argv=None):
                          "(cpmppi_rpgd_step, cpmppi_cem_step) and the closed loop captured as a graph, the step counter on the device")
     ap.add_argument("--gru-model", default=None, metavar="FOLDER",
                     help="a GRU-6IN-32H1-32H2-5OUT-* model folder: the MPPI step - or, with --optimizer cem --fused, the fused CEM step "
-                         "(cpmppi_cem_step_gru) - rolls out with that network (its memory stays on the "
+                         "(cpmppi_cem_step_gru); with --gru-fused, the fused rpgd / gradient / cem step over the network - rolls out "
+                         "with that network (its memory stays on the "
                          "device from period to period); costs quadratic_boundary_grad_minimal and default, --groups 1")
+    ap.add_argument("--gru-fused", action="store_true",
+                    help="rpgd / gradient / cem with --gru-model FOLDER: the whole control step over the network as one library call "
+                         "(cpmppi_rpgd_step_gru: forward sweep, GRU adjoint, Adam, ranking, resampling, shift; cpmppi_cem_step_gru) "
+                         "and the closed loop captured as a graph; with --config-root the checkout's own optimizer (shipped: rpgd). "
+                         "(--fused is the step that integrates the ODE: beside --gru-model it serves cem alone.)")
     ap.add_argument("--graph", action="store_true",
                     help="mppi: the closed loop captured as a graph of control periods, replayed (the step counter on the device)")
     ap.add_argument("--cost", default=None,
@@ -464,6 +473,18 @@ def main(argv=None):
     eng = None
     # --optimizer cem --fused --gru-model FOLDER: the optimizer object takes the network itself (gru_model=, gru_fused=True)
     gru_cem = args.gru_model is not None and bool(args.fused) and opt_name in ("cem", "cem-tf")
+    if args.gru_fused:                                             # rpgd, gradient and cem over the network: gru_model=, gru_fused=True
+        if args.gru_model is None:
+            raise SystemExit("--gru-fused: the fused step over the network needs --gru-model FOLDER")
+        if args.fused:
+            raise SystemExit("--gru-fused and --fused: --fused is the step that integrates the ODE, --gru-fused the one over the "
+                             "network: give one of them")
+        if opt_name not in GRU_FUSED_OPTIMIZERS:
+            raise SystemExit(f"--gru-fused: the fused control step over the network is built for rpgd, gradient and cem, not {opt_name!r}")
+        if args.groups > 1:
+            raise SystemExit("--gru-fused: env groups run the MPPI step only (--groups 1)")
+    gru_opt = gru_cem or bool(args.gru_fused)                      # the optimizer object takes the network itself
+    fused = bool(args.fused) or bool(args.gru_fused)
     if opt_name == "mppi":
         eng = MPPIEngine(n_local, cfg, phys=phys, device=device)
     else:                                                          # another optimizer of the package, built as controller_mpc builds it
@@ -483,6 +504,8 @@ def main(argv=None):
                 over.update(gru_model=args.gru_model, gru_fused=True)
             else:
                 over["fused"] = True
+        if args.gru_fused:
+            over.update(gru_model=args.gru_model, gru_fused=True)
         ctrl = controller_mpc("CartPole", {}, control_limits=([-1.0], [1.0]), config=over, phys=phys, device=device, num_envs=n_local,
                               config_root=args.config_root)
         ctrl.configure(opt_name)
@@ -491,13 +514,13 @@ def main(argv=None):
         raise SystemExit("--fused: the fused control step is built for rpgd, gradient, cem, cem-naive-grad and "
                          "cem-grad-bharadhwaj, not 'mppi'")
     # a fused optimizer runs captured unless the run cannot be (a controller pole mass that changes between calls, warm-up)
-    if args.graph and optimizer is not None and not args.fused:
+    if args.graph and optimizer is not None and not fused:
         raise SystemExit(f"--graph: {opt_name!r} as a staged optimizer is paced by the host (mppi, or --fused, can be captured)")
-    graph = (bool(args.fused) and not optimizer.warmup) or (bool(args.graph) and optimizer is None)
-    if args.gru_model is not None and optimizer is not None and not gru_cem:
+    graph = (fused and not optimizer.warmup) or (bool(args.graph) and optimizer is None)
+    if args.gru_model is not None and optimizer is not None and not gru_opt:
         raise SystemExit(f"--gru-model: the network in the device loop is built for the fused MPPI step (--optimizer mppi), not {opt_name!r}")
     paths = generate_dataset(eng, n_exp, out, seed=seed, rank=rank, world=world, config=dg, groups=args.groups, parameters=parameters,
-                             optimizer=optimizer, graph=graph, gru_model=None if gru_cem else args.gru_model,
+                             optimizer=optimizer, graph=graph, gru_model=None if gru_opt else args.gru_model,
                              secondary_experiment_index=None if args.secondary_experiment_index < 0 else args.secondary_experiment_index)
     print(f"wrote {len(paths)} recordings under {os.path.dirname(paths[0])}")
 

@@ -56,6 +56,7 @@ extern "C" {
                                       cpmppi_rpgd_step / cpmppi_rpgd_reserve / cpmppi_rpgd_args (new entry points, likewise);
                                       cpmppi_cem_step / cpmppi_cem_reserve / cpmppi_cem_args (new entry points, likewise);
                                       cpmppi_cem_step_gru / cpmppi_cem_gru_args (a new entry point, likewise);
+                                      cpmppi_rpgd_step_gru / cpmppi_rpgd_gru_reserve / cpmppi_rpgd_gru_args (new entry points, likewise);
                                       cpmppi_gru_advance (a new entry point, likewise);
                                       cpmppi_brunton / cpmppi_brunton_args, cpmppi_gru_washout (new entry points, likewise);
                                       cpmppi_score_runs / cpmppi_score_args, cpmppi_set_tuning_rows (new entry points, likewise). */
@@ -727,6 +728,70 @@ typedef struct {
   uint32_t* order_out;              /* [E,N] the last iteration's ranking (sample rows, cheapest first), or NULL */
 } cpmppi_cem_gru_args;
 int cpmppi_cem_step_gru(cpmppi_handle* h, const cpmppi_cem_gru_args* args, void* stream);
+
+/* The whole rpgd / gradient-tf control step over the NEURAL predictor (cpmppi_set_gru) for E envs in ONE call: cpmppi_rpgd_step
+ * with the network in the place of the ODE - no host synchronisation, no allocation, and - with count_dev - no launch argument
+ * that changes between control steps, so a captured graph of (step, cpmppi_gru_advance, plant) replays.  It is
+ * cpmppi_rollout_cost_grad_gru + cpmppi_adam_step `iterations` times, cpmppi_rollout_cost_gru, the choice of the best plan, the
+ * resampling of rpgd and the shift.  `c` = control steps taken before this call: *count_dev if given, else count.
+ *   1. for i = 1..iterations: cost gradient of every plan - the forward sweep in the handle's math mode (FAST: split f16,
+ *      PRECISE: exact f32) from the env's memory h0[env] (NULL: zeros), the check-points parked as cpmppi_rollout_cost_grad_gru parks
+ *      them, then its exact-f32 reverse sweep - and cpmppi_adam_step's update with t = a + i, a = adam_iteration (host mode) or
+ *      c * iterations (device mode); lr_t is formed in double in the kernel, as cpmppi_rpgd_step forms it.
+ *   2. final cost S of every plan: cpmppi_rollout_cost_gru's rollout.
+ *   3. - 6. the ranking, Q_out / plan_out / S_out / order_out, the resampling, the shift and the step counter: steps 3 to 6 of
+ *      cpmppi_rpgd_step, word for word.
+ * Every quantity equals the composition of those entry points bit for bit, except that lr_t carries the powers of beta from
+ * iteration to iteration where cpmppi_adam_step calls pow() (the statement cpmppi_rpgd_step has as well).
+ * h0 is read, not written: the memory is handed on by cpmppi_gru_advance, so the closed loop is cpmppi_rpgd_step_gru,
+ * cpmppi_gru_advance(s0, Q_out, h0), cpmppi_plant_step - three calls whose arguments never change.  Reads no pole mass, no L and no
+ * previous input (neither cost of the GRU kernels has a term in it).
+ * One workgroup per env (gru_rpgd_step_kernel), plan n on a pair of lanes of wave n / 32, one wave per 32 plans; the reverse sweep
+ * needs one wave per SIMD, so N <= 128.  Workspace: cpmppi_rpgd_gru_reserve(h, E) - the check-points of
+ * cpmppi_rollout_cost_grad_gru (the same buffer: H * 72 * cfg.E * cfg.N floats) and behind them the gradient, H * cfg.E * cfg.N
+ * floats; E is checked, the size is that of the handle's largest launch.
+ * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned (cpmppi_last_error: "cpmppi_rpgd_step_gru: ...") for: per-env tuning
+ * rows registered, no model set, E == 0 or E > config.E, a NULL s0, target_position, target_equilibrium, Q, m, v or Q_out, a cost
+ * other than quadratic_boundary_grad_minimal and default, a misaligned pointer (count_dev: 8 bytes), iterations == 0, keep_k == 0
+ * or > N, shift > H, an unknown distribution, N > 128, and a stream under capture while the workspace of cpmppi_rpgd_gru_reserve
+ * is missing or too small (outside a capture the step allocates it itself).  cpmppi_rpgd_gru_reserve refuses a handle without a
+ * model, E out of range, such a cost and N > 128 in the same words under its own name.
+ * The block is cpmppi_rpgd_args without L and previous_input, with h0 in their place. */
+typedef struct {
+  uint32_t E;                       /* active envs in this call (cpmppi_rpgd_gru_args) */
+  const float* s0;                  /* [E,6] */
+  const float* target_position;     /* [E] */
+  const float* target_equilibrium;  /* [E] */
+  const float* h0;                  /* [E,2,32] the network's memory per env, or NULL = zeros; read, not written */
+  float* Q;                         /* [E,N,H] the plans, updated in place */
+  float* m;                         /* [E,N,H] Adam first moments, updated in place */
+  float* v;                         /* [E,N,H] Adam second moments, updated in place */
+  uint32_t iterations;              /* Adam iterations in this step */
+  uint32_t adam_iteration;          /* Adam iterations taken before this call (host mode) */
+  float learning_rate;
+  float beta1;
+  float beta2;
+  float epsilon;
+  float gradmax_clip;               /* <= 0: off */
+  uint32_t keep_k;                  /* keep_k == N or resamp_per == 0: never resample */
+  uint32_t resamp_per;
+  uint32_t shift;                   /* 0 .. H */
+  uint32_t distribution;            /* cpmppi_rpgd_distribution */
+  float sample_mean;
+  float uniform_lo;
+  float uniform_hi;
+  uint64_t seed;                    /* Philox key of the redraw */
+  uint64_t draw_offset;             /* Philox offset of the redraw (host mode), or of the first redraw (device mode) */
+  uint32_t env_offset;              /* global index of env 0 */
+  uint64_t count;                   /* control steps taken before this call (host mode) */
+  uint64_t* count_dev;              /* the same counter in DEVICE memory (8-byte aligned), or NULL = host mode */
+  float* Q_out;                     /* [E]   the chosen control */
+  float* S_out;                     /* [E,N] final costs, indexed by the plan rows as they are BEFORE the resampling, or NULL */
+  float* plan_out;                  /* [E,H] the best plan before the shift, or NULL */
+  uint32_t* order_out;              /* [E,N] the ranking (plan rows, cheapest first), or NULL */
+} cpmppi_rpgd_gru_args;
+int cpmppi_rpgd_gru_reserve(cpmppi_handle* h, uint32_t E);
+int cpmppi_rpgd_step_gru(cpmppi_handle* h, const cpmppi_rpgd_gru_args* args, void* stream);
 
 /* a16 alone: S[E,N], delta_u[E,N,H] -> weighted average [E,H] (controller_mppi_cartpole.py:306-321). */
 int cpmppi_reward_weighted_average(cpmppi_handle* h, uint32_t E, const float* S, const float* delta_u, float* out,

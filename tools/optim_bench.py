@@ -28,6 +28,12 @@ the predict seam) against fused (gru_fused=True: cpmppi_cem_step_gru + cpmppi_gr
 device; per control step the device time between two events around a batch of steps and the wall time of the batch, medians over
 the rounds with min and max, and whether the fused step stays within the staged median + the staged runs' own min - max spread.
 
+  python tools/optim_bench.py --gru-rpgd [--rpgd-shapes 1x16x35x4,64x16x35x4,256x16x35x4,1x40x35x5,64x40x35x5,256x40x35x5]
+The same comparison for rpgd (N = 16) and gradient-tf over the network, per E x N x H x iterations and math mode: staged
+(``gru_adjoint=True``: iterations x (cpmppi_rollout_cost_grad_gru = two launches, cpmppi_adam_step), cpmppi_rollout_cost_gru, top-k
+and torch glue, the memory through the predict seam) against fused (``gru_fused=True``: cpmppi_rpgd_step_gru + cpmppi_gru_advance),
+the same three columns and the same verdict.
+
   python tools/optim_bench.py --gru-grad [--steps 30] [--grad-shapes 1x16x35,64x16x35,1x40x35,64x40x35]
 The GRU adjoint (same synthetic weights).  Per E x N x H of --grad-shapes (default: the rpgd and gradient-tf sizes at 1 and 64
 envs) and math mode, cpmppi_rollout_cost_grad_gru against cpmppi_rollout_cost_gru on the same plans, alternating in one process as
@@ -58,6 +64,9 @@ ap.add_argument("--staged-repeats", type=int, default=1, help="with --fused: how
 ap.add_argument("--gru", action="store_true", help="the GRU predictor under cem-tf, cem-gmm-tf and random-action-tf; cost-only launch vs fused step")
 ap.add_argument("--cost-only-shapes", default="1x200x35,64x200x35,256x200x35,256x1024x50", help="with --gru: ExNxH,... (the last default: bench.py's C5)")
 ap.add_argument("--cem-shapes", default="1x200x35,64x200x35,256x200x35", help="with --gru: ExNxH,... of the staged / fused cem step (3 iterations)")
+ap.add_argument("--gru-rpgd", action="store_true", help="rpgd and gradient-tf over the GRU predictor: the staged step (gru_adjoint) against the fused one (gru_fused)")
+ap.add_argument("--rpgd-shapes", default="1x16x35x4,64x16x35x4,256x16x35x4,1x40x35x5,64x40x35x5,256x40x35x5",
+                help="with --gru-rpgd: ExNxHxiterations,... (N = 16: rpgd, otherwise gradient-tf)")
 ap.add_argument("--gru-grad", action="store_true", help="the GRU adjoint: gradient launch vs cost-only launch; rpgd and gradient-tf over the GRU vs the ODE")
 ap.add_argument("--grad-shapes", default="1x16x35,64x16x35,1x40x35,64x40x35", help="with --gru-grad: ExNxH,...")
 ap.add_argument("--datagen", default=None, help="with --fused: E,seconds of the closed-loop data generator, e.g. 256,10")
@@ -184,20 +193,48 @@ def gru_bench():
 
 def gru_cem_bench():
     """The cem control step over the network, staged against fused, alternating in one process (the module docstring)."""
-    from types import SimpleNamespace
     from cartpolesimulation_amd.optimizer_cem import optimizer_cem
     model = synthetic_gru()
+
+    def make(mode, e, n, h, math_mode, vp):
+        return optimizer_cem(control_limits=([-1.0], [1.0]), seed=1, num_envs=e, num_rollouts=n, mpc_horizon=h, cem_outer_it=3,
+                             math_mode=math_mode, gru_model=model, gru_fused=mode != "staged", variable_parameters=vp)
+
+    gru_step_bench("gru_cem_step", filter(None, args.cem_shapes.split(",")), make)
+
+
+def gru_rpgd_bench():
+    """The rpgd / gradient control step over the network, staged (gru_adjoint=True) against fused (gru_fused=True: cpmppi_rpgd_step_gru
+    + cpmppi_gru_advance), alternating in one process as the cem step above; a shape E x N x H x iterations with N = 16 is rpgd's
+    (resamp_per 10, three quarters kept), any other gradient-tf's."""
+    from cartpolesimulation_amd.optimizer_gradient import optimizer_gradient, optimizer_rpgd
+    model = synthetic_gru()
+
+    def make(mode, e, n, h, math_mode, vp, iterations):
+        flag = dict(gru_adjoint=True) if mode == "staged" else dict(gru_fused=True)
+        common = dict(control_limits=([-1.0], [1.0]), seed=1, num_envs=e, num_rollouts=n, mpc_horizon=h, gru_model=model,
+                      variable_parameters=vp, **flag)
+        opt = optimizer_rpgd(outer_its=iterations, **common) if n == 16 else optimizer_gradient(gradient_steps=iterations, **common)
+        opt.cfg.math_mode = math_mode                         # (the GRU kernels' math mode is the handle's)
+        return opt
+
+    gru_step_bench("gru_rpgd_step", filter(None, args.rpgd_shapes.split(",")), make)
+
+
+def gru_step_bench(bench, shapes, make):
+    """A control step over the network, staged against fused, alternating in one process (the module docstring): `make(mode, E, N,
+    H, math mode, variable parameters[, iterations])` builds the optimizer of a mode; a shape is E x N x H[x iterations]."""
+    from types import SimpleNamespace
     rounds, batch = 12, 10
-    for shape in filter(None, args.cem_shapes.split(",")):
-        e, n, h = (int(x) for x in shape.split("x"))
+    for shape in shapes:
+        e, n, h, *more = (int(x) for x in shape.split("x"))
         g = np.random.Generator(np.random.SFC64(11))
         s0 = np.stack([O.create_cartpole_state(g.uniform(-0.3, 0.3), g.uniform(-0.5, 0.5), g.uniform(-0.05, 0.05), 0.0) for _ in range(e)])
         for math_mode in ("fast", "precise"):
             opts = {}
             for mode in ("staged", "fused", "fused_device"):
                 vp = SimpleNamespace(target_position=np.zeros(e, np.float32), target_equilibrium=np.ones(e, np.float32))
-                opts[mode] = optimizer_cem(control_limits=([-1.0], [1.0]), seed=1, num_envs=e, num_rollouts=n, mpc_horizon=h, cem_outer_it=3,
-                                           math_mode=math_mode, gru_model=model, gru_fused=mode != "staged", variable_parameters=vp)
+                opts[mode] = make(mode, e, n, h, math_mode, vp, *more)
                 opts[mode].configure()
             states = {k: o.engine.tensor(s0) for k, o in opts.items()}
             dev = opts["fused_device"]
@@ -220,8 +257,8 @@ def gru_cem_bench():
                     if r >= 2:
                         wall_ms[k].append((time.perf_counter() - t0) / batch * 1e3)
                         device_ms[k].append(a.elapsed_time(b) / batch)
-            rec = {"bench": "gru_cem_step", "envs": e, "num_rollouts": n, "mpc_horizon": h, "iterations": 3, "math_mode": math_mode,
-                   "rounds": rounds, "steps_per_round": batch}
+            rec = {"bench": bench, "optimizer": dev.optimizer_name, "envs": e, "num_rollouts": n, "mpc_horizon": h,
+                   "iterations": more[0] if more else 3, "math_mode": math_mode, "rounds": rounds, "steps_per_round": batch}
             for k in steps:
                 for what, v in (("device", device_ms[k]), ("wall", wall_ms[k])):
                     rec[f"{k}_{what}_ms"] = round(float(np.median(v)), 5)
@@ -321,6 +358,9 @@ if args.fused:
     sys.exit(0)
 if args.gru_grad:
     gru_grad_bench()
+    sys.exit(0)
+if args.gru_rpgd:
+    gru_rpgd_bench()
     sys.exit(0)
 if args.gru:
     gru_bench()
