@@ -32,8 +32,9 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_rpgd_reserve", "cpmppi_rpgd_step", "cpmppi_cem_reserve", "cpmppi_cem_step", "cpmppi_rollout_cost_gru",
            "cpmppi_rollout_cost_grad_gru", "cpmppi_gru_advance", "cpmppi_gru_washout", "cpmppi_brunton",
            "cpmppi_score_runs", "cpmppi_set_tuning_rows", "cpmppi_replay_step", "cpmppi_cem_step_gru",
-           "cpmppi_rpgd_step_gru", "cpmppi_rpgd_gru_reserve")
+           "cpmppi_rpgd_step_gru", "cpmppi_rpgd_gru_reserve", "cpmppi_rpgd_step_rows")
 TUNING_ROW_FLOATS, TUNING_LBD, TUNING_SIGMA = 16, 7, 8
+RPGD_ROW_LR, RPGD_ROW_GRADMAX_CLIP = 7, 8            # cpmppi_rpgd_step_rows: the same row, these two behind the seven cost entries
 SCORE_FLOATS = 5
 SCORE_COLUMNS = ("mean_abs_distance", "mean_abs_angle_deg", "mean_Q_squared", "stable_share", "first_stable_row")
 COMM_ID_BYTES, COMM_SLOTS, GATHER_STAMP_FLOATS = 128, 4, 4
@@ -236,6 +237,7 @@ def load():
     lib.cpmppi_sgd_step.argtypes = [vp, u32, vp, vp, f, f, vp]
     lib.cpmppi_rpgd_reserve.argtypes = [vp, u32]
     lib.cpmppi_rpgd_step.argtypes = [vp, C.POINTER(cpmppi_rpgd_args), vp]
+    lib.cpmppi_rpgd_step_rows.argtypes = [vp, C.POINTER(cpmppi_rpgd_args), vp, u32, vp]
     lib.cpmppi_cem_reserve.argtypes = [vp, u32, u32]
     lib.cpmppi_cem_reserve.restype = C.c_int
     lib.cpmppi_cem_step.argtypes = [vp, C.POINTER(cpmppi_cem_args), vp]

@@ -188,6 +188,34 @@ def tuning_rows(mppi: MPPIConfig, E, **columns):
     return rows
 
 
+RPGD_ROW_COLUMNS = tuple(COST_WEIGHTS["quadratic_boundary_grad_minimal"][1]) + ("learning_rate", "gradmax_clip")
+
+
+def rpgd_rows(config: MPPIConfig, E, learning_rate, gradmax_clip, **columns):
+    """The per-env rows of the fused rpgd / gradient step (``optimizer_rpgd(fused=True, rows=...)``, cpmppi_rpgd_step_rows) ->
+    float32 [E, 16]: a row holds the seven entries of quadratic_boundary_grad_minimal's cost vector in cost_vector's order, Adam's
+    learning rate and the gradient-norm clip (<= 0: off), and zero padding.  ``learning_rate`` and ``gradmax_clip`` are the
+    optimizer's own (no configuration holds them) and always given; every other named column - a key of that cost's COST_WEIGHTS
+    list - takes the configuration's value when it is not.  Each column is one value per env, or a scalar for all.  The sampling
+    width is no column: the plans are drawn with the handle's."""
+    if config.cost_function_specification != "quadratic_boundary_grad_minimal":
+        raise ValueError("rpgd rows hold the cost vector of quadratic_boundary_grad_minimal, not "
+                         f"{config.cost_function_specification!r}")
+    unknown = [k for k in columns if k not in RPGD_ROW_COLUMNS]
+    if unknown:
+        raise ValueError(f"unknown rpgd row column(s) {', '.join(map(repr, unknown))}; available: {', '.join(RPGD_ROW_COLUMNS)}")
+    E = int(E)
+    _, w = cost_vector(config.cost_function_specification, config.cost_weights)
+    rows = np.zeros((E, L.TUNING_ROW_FLOATS), np.float32)
+    columns = dict(zip(RPGD_ROW_COLUMNS, w[:7]), **columns, learning_rate=learning_rate, gradmax_clip=gradmax_clip)
+    for i, name in enumerate(RPGD_ROW_COLUMNS):
+        col = np.asarray(columns[name], np.float64)
+        if col.ndim > 1 or (col.ndim == 1 and col.shape[0] != E):
+            raise ValueError(f"rpgd row column {name!r} must be a scalar or one value per env ({E}), got shape {col.shape}")
+        rows[:, i] = col
+    return rows
+
+
 def build_c_config(E, mppi: MPPIConfig, phys: PhysicalParameters = None):
     phys = phys or PhysicalParameters()
     c = L.cpmppi_config()

@@ -125,21 +125,26 @@ class controller_mpc(template_controller):
                                         variable_parameters=self.variable_parameters, **cfg)
         self.optimizer.configure(dt=opt_probe.mpc_timestep, predictor_specification=spec)
 
+    def optimizer_section(self, cls):
+        """The constructor keywords of optimizer class ``cls`` as this controller is configured (the sweep builds its optimizer from
+        them as well)."""
+        if self._yaml is None:
+            return dict(self.config_optimizer)
+        # with a checkout: THIS optimizer's section of config_optimizers.yml (the class's constructor keywords are its keys),
+        # the controller-level keys of config_controllers.yml `mpc:`, then the caller's overrides
+        sections = self._yaml["optimizers"]
+        name = cls.optimizer_name
+        cfg = dict(sections.get(name) or sections.get(name + "-tf") or {})
+        ctrl = self._yaml["controllers"]["mpc"]
+        cost_name = ctrl.get("cost_function_specification") or self._yaml["cost"]["cost_function_name_default"]
+        cfg.update(cost_function_specification=cost_name, cost_weights=dict(self._yaml["cost"]["CartPole"].get(cost_name, {})),
+                   predictor_type=self.config_optimizer.get("predictor_type", "ODE_v0"),
+                   intermediate_steps=self.config_optimizer.get("intermediate_steps", 10))
+        cfg.update(self._user_config)
+        return cfg
+
     def _configure_other(self, cls, predictor_specification, cost_function_specification, controller_logging, **kwargs):
-        if self._yaml is not None:
-            # with a checkout: THIS optimizer's section of config_optimizers.yml (the class's constructor keywords are its keys),
-            # the controller-level keys of config_controllers.yml `mpc:`, then the caller's overrides
-            sections = self._yaml["optimizers"]
-            name = cls.optimizer_name
-            cfg = dict(sections.get(name) or sections.get(name + "-tf") or {})
-            ctrl = self._yaml["controllers"]["mpc"]
-            cost_name = ctrl.get("cost_function_specification") or self._yaml["cost"]["cost_function_name_default"]
-            cfg.update(cost_function_specification=cost_name, cost_weights=dict(self._yaml["cost"]["CartPole"].get(cost_name, {})),
-                       predictor_type=self.config_optimizer.get("predictor_type", "ODE_v0"),
-                       intermediate_steps=self.config_optimizer.get("intermediate_steps", 10))
-            cfg.update(self._user_config)
-        else:
-            cfg = dict(self.config_optimizer)
+        cfg = self.optimizer_section(cls)
         cfg.update(kwargs)
         cost_name = cost_function_specification or cfg.pop("cost_function_specification", None) or \
             "quadratic_boundary_grad_minimal"

@@ -6,7 +6,8 @@
 //   adam_step_kernel, sgd_step_kernel     gradient steps with per-rollout norm clipping and the action limits.
 //   cem_sample_kernel, cem_gmm_sample_kernel   CEM's sampler: one Gaussian per env, or a mixture of K elite-centred ones.
 //   cem_update_kernel                     top-k (bitonic sort in LDS) -> mean and stdev of the elite.
-//   rpgd_step_kernel<COST, INTEG>         the whole rpgd / gradient-tf control step, one workgroup per env (cpmppi_rpgd.hpp).
+//   rpgd_step_kernel<COST, INTEG, ROWS>   the whole rpgd / gradient-tf control step, one workgroup per env (cpmppi_rpgd.hpp); ROWS: the
+//                                         cost weights, learning rate and gradient clip per env (cpmppi_rpgd_step_rows).
 //   cem_step_kernel<COST, INTEG, REFINE>  the whole cem / cem-naive-grad / cem-grad-bharadhwaj control step, likewise (cpmppi_cem.hpp).
 // The three templated kernels run the one adjoint sweep of cpmppi_grad.hpp (adjoint_sweep over a SweepLane); the two fused steps
 // rank their costs with rank_costs.  cpmppi_rollout_cost launches rollout_cost_kernel through launch_rollout (cpmppi.hip).
@@ -218,8 +219,14 @@ struct RpgdPtrs {
   float* Q_out; float* S_out; float* plan_out; uint32_t* order_out;
 };
 
-template <int COST, int INTEG>
-__global__ __launch_bounds__(BLOCK) void rpgd_step_kernel(const Params p, const RpgdPtrs a) {
+// ROWS (cpmppi_rpgd_step_rows): the cost weights, Adam's learning rate and the gradient clip read PER ENV - the pointer block grows
+// by the rows' address, which the plain kernels' block, and with it their code, never sees.
+struct RpgdRowPtrs : RpgdPtrs {
+  const float* rows;      // [E][TUNING_ROW_FLOATS]
+};
+
+template <int COST, int INTEG, bool ROWS = false>
+__global__ __launch_bounds__(BLOCK) void rpgd_step_kernel(const Params p, const std::conditional_t<ROWS, RpgdRowPtrs, RpgdPtrs> a) {
   extern __shared__ float rpgd_lds[];               // sub[S][6][block] | key[block] | order[block]
   const uint32_t tid = threadIdx.x, Nb = blockDim.x, env = blockIdx.x, N = p.N, H = p.H;
   uint32_t* key = reinterpret_cast<uint32_t*>(rpgd_lds + (size_t)p.S * 6 * Nb);
@@ -229,10 +236,21 @@ __global__ __launch_bounds__(BLOCK) void rpgd_step_kernel(const Params p, const 
   const uint64_t it0 = a.count_dev ? c * a.iterations : (uint64_t)a.adam_iteration;
   const size_t row = ((size_t)env * N + tid) * H;
   float S = 0.0f;
+  // `pc`: the block the COSTS compute with - ROWS: the env's row in place (block-uniform: one workgroup = one env), read once, here;
+  // the pole mass then goes into THAT block, so pole-mass rows and these rows combine.  The ranking and the redraw keep `p`.
+  Params pq_;
+  float lr0 = a.lr, clip = a.gradmax_clip;
+  if constexpr (ROWS) {
+    const float* r = a.rows + (size_t)env * TUNING_ROW_FLOATS;
+    pq_ = with_rpgd_row(p, r);
+    lr0 = rpgd_row_value(r, RPGD_ROW_LR);
+    clip = rpgd_row_value(r, RPGD_ROW_GRADMAX_CLIP);
+  }
+  const Params& pc = ROWS ? pq_ : p;
   if (active) {
     Params pm_;
-    if constexpr (INTEG == PREDICTOR_ODE) pm_ = with_pole_mass(p, a.m_pole ? a.m_pole[env] : p.m_pole);
-    const Params& pi = (INTEG == PREDICTOR_ODE) ? pm_ : p;
+    if constexpr (INTEG == PREDICTOR_ODE) pm_ = with_pole_mass(pc, a.m_pole ? a.m_pole[env] : p.m_pole);
+    const Params& pi = (INTEG == PREDICTOR_ODE) ? pm_ : pc;
     const EnvConst ec = make_env_const(pi, a.L ? a.L[env] : p.L_default);
     SweepLane w;
     sweep_lane_env(w, p, a, env);
@@ -244,10 +262,10 @@ __global__ __launch_bounds__(BLOCK) void rpgd_step_kernel(const Params p, const 
     RpgdLr lr(a.beta1, a.beta2, it0);
     for (uint32_t i = 1; i <= a.iterations + 1; ++i) {
       const bool descend = i <= a.iterations;      // the last pass is the final cost: forward only
-      S = adjoint_sweep<COST, INTEG>(p, pi, ec, w, descend);
+      S = adjoint_sweep<COST, INTEG>(pc, pi, ec, w, descend);
       if (!descend) break;
-      const float lr_t = lr.next(a.lr, a.beta1, a.beta2);
-      rpgd_adam_row(H, a.Q + row, a.m + row, a.v + row, w.grad, Nb, lr_t, a.beta1, a.beta2, a.eps, a.gradmax_clip, p.lo, p.hi);
+      const float lr_t = lr.next(lr0, a.beta1, a.beta2);
+      rpgd_adam_row(H, a.Q + row, a.m + row, a.v + row, w.grad, Nb, lr_t, a.beta1, a.beta2, a.eps, clip, p.lo, p.hi);
     }
     if (a.S_out) a.S_out[(size_t)env * N + tid] = S;
   }
@@ -266,6 +284,11 @@ void launch_rpgd(uint32_t cost_id, dim3 grid, dim3 block, size_t lds, hipStream_
   with_cost(cost_id, [&](auto cost) {
     hipLaunchKernelGGL((rpgd_step_kernel<decltype(cost)::value, INTEG>), grid, block, lds, st, p, a);
   });
+}
+// ... and with per-env rows: quadratic_boundary_grad_minimal, whose cost vector a row holds (the entry point has checked)
+template <int INTEG>
+void launch_rpgd_rows(dim3 grid, dim3 block, size_t lds, hipStream_t st, const Params& p, const RpgdRowPtrs& a) {
+  hipLaunchKernelGGL((rpgd_step_kernel<COST_QBGM, INTEG, true>), grid, block, lds, st, p, a);
 }
 
 inline size_t rpgd_floats(const cpmppi_handle* h, uint32_t E) { return (size_t)h->cfg.H * 7 * E * rpgd_block(h); }
@@ -399,6 +422,8 @@ void allow_large_lds_optim() {
       allow_large_lds(&cem_step_kernel<COST, PREDICTOR_ODE_V0, true>);
       allow_large_lds(&cem_step_kernel<COST, PREDICTOR_ODE, true>);
     });
+  allow_large_lds(&rpgd_step_kernel<COST_QBGM, PREDICTOR_ODE_V0, true>);
+  allow_large_lds(&rpgd_step_kernel<COST_QBGM, PREDICTOR_ODE, true>);
   // the CEM top-k sorts N (padded to a power of two) 8-byte records in LDS: 128 KB at N = 16384
   allow_large_lds(&cem_update_kernel);
 }
@@ -507,29 +532,42 @@ int cpmppi_rpgd_reserve(cpmppi_handle* h, uint32_t E) {
   return grow_workspace(h, h->rpgd_ws, h->rpgd_ws_floats, rpgd_floats(h, E));
 }
 
-int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* a, void* stream) {
+// cpmppi_rpgd_step and cpmppi_rpgd_step_rows: one body that checks and launches.  `who`: the caller's name, which every refusal
+// begins with; `with_rows`: the second one, whose `rows` [n_rows][CPMPPI_TUNING_ROW_FLOATS] the kernel reads per env.
+static int rpgd_step_impl(cpmppi_handle* h, const cpmppi_rpgd_args* a, void* stream, const char* who, bool with_rows,
+                          const float* rows, uint32_t n_rows) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
-  if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: null argument block");
-  if (a->E == 0 || a->E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: bad argument (0 < E <= config.E)");
+  const std::string w(who);
+  if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": null argument block");
+  if (a->E == 0 || a->E > h->cfg.E) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": bad argument (0 < E <= config.E)");
   if (!a->s0 || !a->target_position || !a->target_equilibrium || !a->Q || !a->m || !a->v || !a->Q_out)
-    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: null pointer (s0, target_position, target_equilibrium, Q, m, v and Q_out are required)");
+    return fail(h, CPMPPI_ERR_BAD_ARG, w + ": null pointer (s0, target_position, target_equilibrium, Q, m, v and Q_out are required)");
   for (const void* ptr : {(const void*)a->s0, (const void*)a->target_position, (const void*)a->target_equilibrium, (const void*)a->L,
                           (const void*)a->previous_input, (const void*)a->Q, (const void*)a->m, (const void*)a->v, (const void*)a->Q_out,
                           (const void*)a->S_out, (const void*)a->plan_out, (const void*)a->order_out})
-    if (misaligned(ptr)) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: misaligned pointer");
-  if (reinterpret_cast<uintptr_t>(a->count_dev) & 7u) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: misaligned pointer (count_dev: 8 bytes)");
-  if (a->iterations == 0) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: iterations must be > 0");
-  if (a->keep_k == 0 || a->keep_k > h->cfg.N) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: bad argument (0 < keep_k <= N)");
-  if (a->shift > h->cfg.H) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: shift exceeds the horizon");
-  if (a->distribution > CPMPPI_RPGD_UNIFORM) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step: unknown distribution");
-  if (const int rc = sweep_check_handle(h, "cpmppi_rpgd_step", RPGD_WORDS)) return rc;
-  if (const int rc = sweep_check_shape(h, "cpmppi_rpgd_step", RPGD_WORDS, rpgd_lds_bytes(h))) return rc;
-  if (!pole_mass_rows_cover(h, a->E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short("cpmppi_rpgd_step", h, a->E));
-  if (const int rc = refuse_tuning_rows(h, "cpmppi_rpgd_step")) return rc;
+    if (misaligned(ptr)) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": misaligned pointer");
+  if (reinterpret_cast<uintptr_t>(a->count_dev) & 7u) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": misaligned pointer (count_dev: 8 bytes)");
+  if (a->iterations == 0) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": iterations must be > 0");
+  if (a->keep_k == 0 || a->keep_k > h->cfg.N) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": bad argument (0 < keep_k <= N)");
+  if (a->shift > h->cfg.H) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": shift exceeds the horizon");
+  if (a->distribution > CPMPPI_RPGD_UNIFORM) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": unknown distribution");
+  if (const int rc = sweep_check_handle(h, who, RPGD_WORDS)) return rc;
+  if (const int rc = sweep_check_shape(h, who, RPGD_WORDS, rpgd_lds_bytes(h))) return rc;
+  if (!pole_mass_rows_cover(h, a->E)) return fail(h, CPMPPI_ERR_BAD_ARG, pole_mass_rows_short(who, h, a->E));
+  if (with_rows) {
+    if (!rows) return fail(h, CPMPPI_ERR_BAD_ARG, w + ": null pointer (rows)");
+    if ((reinterpret_cast<uintptr_t>(rows) & (CPMPPI_TUNING_ROW_FLOATS * sizeof(float) - 1u)) != 0)
+      return fail(h, CPMPPI_ERR_BAD_ARG, w + ": misaligned pointer (rows are 64 bytes and 64-byte aligned)");
+    if (n_rows < a->E)
+      return fail(h, CPMPPI_ERR_BAD_ARG, w + ": " + std::to_string(a->E) + " envs, but rows holds " + std::to_string(n_rows) + " rows");
+    if (h->cfg.cost_id != CPMPPI_COST_QBGM)
+      return fail(h, CPMPPI_ERR_BAD_ARG, w + ": a row holds the cost vector of quadratic_boundary_grad_minimal: the handle has another cost plugin");
+  }
+  if (const int rc = refuse_tuning_rows(h, who)) return rc;
   CPMPPI_ON_DEVICE(h);
   hipStream_t s = (hipStream_t)stream;
   if (h->rpgd_ws_floats < rpgd_floats(h, a->E)) {
-    if (const int rc = refuse_unreserved_capture(h, s, "cpmppi_rpgd_step", "cpmppi_rpgd_reserve")) return rc;
+    if (const int rc = refuse_unreserved_capture(h, s, who, "cpmppi_rpgd_reserve")) return rc;
     if (const int rc = cpmppi_rpgd_reserve(h, a->E)) return rc;
   }
   const uint32_t Nb = rpgd_block(h);
@@ -545,11 +583,28 @@ int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* a, void* stream) 
   p.lr = a->learning_rate; p.beta1 = a->beta1; p.beta2 = a->beta2; p.eps = a->epsilon; p.gradmax_clip = a->gradmax_clip;
   p.sample_mean = a->sample_mean; p.uniform_lo = a->uniform_lo; p.uniform_hi = a->uniform_hi;
   p.Q_out = a->Q_out; p.S_out = a->S_out; p.plan_out = a->plan_out; p.order_out = a->order_out;
-  const auto launch = h->cfg.ode_predictor == CPMPPI_ODE_CROMER ? launch_rpgd<PREDICTOR_ODE> : launch_rpgd<PREDICTOR_ODE_V0>;
-  launch(h->prm.cost_id, dim3(a->E), dim3(Nb), rpgd_lds_bytes(h), s, h->prm, p);
+  const bool cromer = h->cfg.ode_predictor == CPMPPI_ODE_CROMER;
+  if (with_rows) {
+    RpgdRowPtrs pr{};
+    static_cast<RpgdPtrs&>(pr) = p;
+    pr.rows = rows;
+    const auto launch = cromer ? launch_rpgd_rows<PREDICTOR_ODE> : launch_rpgd_rows<PREDICTOR_ODE_V0>;
+    launch(dim3(a->E), dim3(Nb), rpgd_lds_bytes(h), s, h->prm, pr);
+  } else {
+    const auto launch = cromer ? launch_rpgd<PREDICTOR_ODE> : launch_rpgd<PREDICTOR_ODE_V0>;
+    launch(h->prm.cost_id, dim3(a->E), dim3(Nb), rpgd_lds_bytes(h), s, h->prm, p);
+  }
   CPMPPI_HIP(h, hipGetLastError());
   if (a->count_dev) launch_step_count((unsigned long long*)a->count_dev, s);
   return launched(h);
+}
+
+int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* a, void* stream) {
+  return rpgd_step_impl(h, a, stream, "cpmppi_rpgd_step", false, nullptr, 0);
+}
+
+int cpmppi_rpgd_step_rows(cpmppi_handle* h, const cpmppi_rpgd_args* a, const float* rows, uint32_t n_rows, void* stream) {
+  return rpgd_step_impl(h, a, stream, "cpmppi_rpgd_step_rows", true, rows, n_rows);
 }
 
 int cpmppi_cem_reserve(cpmppi_handle* h, uint32_t E, uint32_t refine) {

@@ -123,6 +123,22 @@ __device__ __forceinline__ Params with_tuning_lane(const Params& p, const float*
   q.sigma = row[TUNING_SIGMA];
   return q;
 }
+// The per-env rows of the fused rpgd / gradient-tf step (cpmppi_rpgd_step_rows): the same 64-byte row and the same seven cost
+// entries; where the MPPI row holds LBD and sigma this one holds Adam's learning rate and the gradient-norm clip, which are no
+// fields of Params (rpgd_row_value reads them).  with_rpgd_row: the launch's block with the ROW's cost entries in the handle's
+// place - all that with_tuning puts there for the cost; LBD (no soft-min in this step) and sigma (the redraw matches
+// cpmppi_sample, which draws with the handle's) stay the launch's.  A sibling of with_tuning, which is left as it was.
+constexpr uint32_t RPGD_ROW_LR = 7, RPGD_ROW_GRADMAX_CLIP = 8;
+__device__ __forceinline__ float rpgd_row_value(const float* row, uint32_t i) {
+  const __attribute__((address_space(4))) float* r = (const __attribute__((address_space(4))) float*)(uintptr_t)row;
+  return uniform_(r[i]);
+}
+__device__ __forceinline__ Params with_rpgd_row(const Params& p, const float* row) {
+  Params q = p;
+#pragma unroll
+  for (int i = 0; i < 7; ++i) q.w[i] = rpgd_row_value(row, i);
+  return q;
+}
 
 // For kernels where the env (hence L) is the same for the whole wave: pin every field to an SGPR.  Field by field — the
 // first version walked the struct through a float pointer, which kept it in a 28-byte private (scratch) slot per lane:

@@ -948,11 +948,14 @@ class MPPIEngine:
                          learning_rate, beta1=0.9, beta2=0.999, epsilon=1e-8, gradmax_clip=0.0, keep_k=None, resamp_per=0, shift=1,
                          distribution="normal", sample_mean=0.0, uniform_lo=0.0, uniform_hi=0.0, seed=0, draw_offset=0,
                          env_offset=0, count=0, adam_iteration=0, count_dev=None, Q_out=None, S_out=None, plan_out=None,
-                         order_out=None):
+                         order_out=None, rows=None):
         """cpmppi_rpgd_step: one whole rpgd / gradient-tf control step on the plans ``Q`` and the Adam moments ``m``, ``v``
         [E,N,H], all three updated IN PLACE (include/cpmppi.h states the step).  ``count_dev``: int64 device scalar, the control
         steps taken so far - read by the kernel in place of ``count`` / ``adam_iteration`` / ``draw_offset`` and incremented
-        after the step (graph replay).  -> (Q_out[E], S_out, plan_out, order_out), the last three as given (or None)."""
+        after the step (graph replay).  ``rows``: cpmppi_rpgd_step_rows instead - a contiguous float32 device tensor [>= E, 16]
+        (``configs.rpgd_rows``) with each env's cost weights, learning rate and gradient clip, taken AS IT IS: every launch and
+        replay reads its values when it runs, and ``learning_rate`` / ``gradmax_clip`` go unread.
+        -> (Q_out[E], S_out, plan_out, order_out), the last three as given (or None)."""
         E = device_tensor("Q", Q, tail=(self.N, self.H), note=_IN_PLACE).shape[0]
         if E > self.E:
             raise ValueError(f"Q must be [E<={self.E},{self.N},{self.H}], got {tuple(Q.shape)}")
@@ -972,7 +975,15 @@ class MPPIEngine:
         a.sample_mean, a.uniform_lo, a.uniform_hi = float(sample_mean), float(uniform_lo), float(uniform_hi)
         a.seed, a.draw_offset, a.env_offset, a.count = int(seed), int(draw_offset), int(env_offset), int(count)
         a.count_dev = _counter("count_dev", count_dev)
-        return PreparedCall(self, self.lib.cpmppi_rpgd_step, a, inputs + (Q, m, v, count_dev) + out, out,
+        enqueue = self.lib.cpmppi_rpgd_step
+        if rows is not None:
+            if device_tensor("rows", rows, tail=(_L.TUNING_ROW_FLOATS,)).shape[0] < E:
+                raise ValueError(f"rows must hold a row per env ({E}), got {rows.shape[0]}")
+            step_rows, rows_at, n_rows = self.lib.cpmppi_rpgd_step_rows, C.c_void_p(rows.data_ptr()), rows.shape[0]
+
+            def enqueue(handle, ref, stream):        # (the block goes first, as in every entry point a PreparedCall enqueues)
+                return step_rows(handle, ref, rows_at, n_rows, stream)
+        return PreparedCall(self, enqueue, a, inputs + (Q, m, v, count_dev, rows) + out, out,
                             ("count", "adam_iteration", "draw_offset", "iterations"))
 
     rpgd_step = _run_once(_build_rpgd_step)

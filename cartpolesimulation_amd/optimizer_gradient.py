@@ -39,14 +39,29 @@ moves the memory on in place with the state seen and the control chosen.  The fl
 (``gru_adjoint=True`` beside it changes nothing) and makes the object a fused one (``fused`` is true, ``step_device``, a device
 step counter): the closed loop of the shipped controller over a learned model launches, or replays as a captured graph, like
 the fused ODE step's (harness.py).  At most 128 plans per env; quadratic_boundary_grad is refused as under ``gru_adjoint=True``.
+
+``rows=`` (with ``fused=True``; ``configs.rpgd_rows`` packs them) gives every env its OWN controller setting: a float32 array
+[num_envs, 16] holding, per env, quadratic_boundary_grad_minimal's seven cost weights, Adam's learning rate and the gradient clip.
+The fused step is then cpmppi_rpgd_step_rows, and the constructor's ``learning_rate`` and ``gradmax_clip`` (and the cost weights of
+the handle) are unused for the step.  The rows live on as the device tensor ``self.rows``, which every launch and every replay of a
+captured loop reads when it runs: rewrite it in place to change the settings.  They travel inside the object, so ``capture()``,
+``run_schedule(optimizer=...)``, ``generate_dataset(optimizer=...)`` and ``along_trajectories`` take it as any fused optimizer.
+The sampling width stays one value per optimizer (``sample_stdev`` / ``initial_action_stdev``): the plans are drawn with the
+handle's.  Refused by name: ``rows`` with the staged step (its launches read the handle's scalars), with the network
+(``gru_model`` / ``gru_fused``), in another shape, or with another cost.
 """
 import math
 
 import torch
 
-from ._optimizer_base import _OptimizerBase
+from ._lib import TUNING_ROW_FLOATS
+from ._optimizer_base import _OptimizerBase, is_gru_specification
 from .optimizer_cem import GRU_FUSED_NEEDS_MODEL
 
+ROWS_NEED_FUSED = ("rows= needs fused=True: the staged step's launches (cpmppi_rollout_cost_grad, cpmppi_adam_step) read the handle's "
+                   "scalars; the fused step reads a row per env (cpmppi_rpgd_step_rows)")
+ROWS_OR_GRU = ("rows= with gru_model / gru_fused: the fused step over the network (cpmppi_rpgd_step_gru) reads no rows; per-env rows "
+               "are built for the ODE predictors")
 GRU_FUSED_OR_FUSED = ("gru_fused=True and fused=True: fused=True is the step that integrates the ODE (cpmppi_rpgd_step), gru_fused=True "
                       "the one over the network (cpmppi_rpgd_step_gru): give one of them")
 
@@ -62,9 +77,13 @@ class _GradientBase(_OptimizerBase):
     def __init__(self, cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, sample_stdev, period,
                  num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
                  variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused=False, gru_model=None,
-                 gru_adjoint=False, gru_fused=False):
+                 gru_adjoint=False, gru_fused=False, rows=None):
         if gru_fused and fused:
             raise ValueError(GRU_FUSED_OR_FUSED)
+        if rows is not None and (gru_model is not None or gru_fused):
+            raise ValueError(ROWS_OR_GRU)
+        if rows is not None and not fused:
+            raise ValueError(ROWS_NEED_FUSED)
         # the handle's sampler draws knots ~ N(0, SQRTRHOINV / sqrt(dt)): set it to the requested stdev
         super().__init__(cost_function, control_limits, seed, num_envs, cost_function_specification, cost_weights,
                          variable_parameters, phys, device, optimizer_logging, mpc_horizon, mpc_timestep, num_rollouts,
@@ -78,6 +97,24 @@ class _GradientBase(_OptimizerBase):
         self._check_gru_adjoint(self.fused)
         self.gru_fused = bool(gru_fused)   # one cpmppi_rpgd_step_gru + cpmppi_gru_advance per control step: a fused object as well
         self.fused = self.fused or self.gru_fused
+        self.rows = self._check_rows(rows)   # [num_envs, 16] per-env settings of the fused step; on the engine's device from configure() on
+
+    def _check_rows(self, rows):
+        if rows is None:
+            return None
+        if self.cfg.cost_function_specification != "quadratic_boundary_grad_minimal":
+            raise ValueError("rows= holds the cost vector of quadratic_boundary_grad_minimal, not "
+                             f"{self.cfg.cost_function_specification!r}")
+        if tuple(rows.shape) != (self.num_envs, TUNING_ROW_FLOATS):
+            raise ValueError(f"rows must be [num_envs={self.num_envs}, {TUNING_ROW_FLOATS}] (configs.rpgd_rows), got {tuple(rows.shape)}")
+        return rows
+
+    def configure(self, dt=None, predictor_specification=None, num_envs=None, **kwargs):
+        if self.rows is not None and is_gru_specification(predictor_specification):
+            raise ValueError(ROWS_OR_GRU)
+        super().configure(dt=dt, predictor_specification=predictor_specification, num_envs=num_envs, **kwargs)
+        if self.rows is not None:
+            self.rows = self.engine.tensor(self._check_rows(self.rows))  # (the env count may be configure's)
 
     def _gru_selected(self, predictor_specification):
         neural = super()._gru_selected(predictor_specification)
@@ -182,6 +219,8 @@ class _GradientBase(_OptimizerBase):
             if self.gru_fused:
                 self._prepared = self.engine.prepare_rpgd_step_gru(s, self.Q, self.m, self.v, tp, te, self.h, **common)
             else:
+                if self.rows is not None:
+                    common["rows"] = self.rows
                 self._prepared = self.engine.prepare_rpgd_step(s, self.Q, self.m, self.v, tp, te, L, previous_input, **common)
             self._prepared_key = key
         if count_dev is not None:
@@ -210,7 +249,7 @@ class optimizer_gradient(_GradientBase):
                  gradmax_clip=5, warmup=False, warmup_iterations=250, optimizer_logging=False,
                  calculate_optimal_trajectory=False, num_envs=1, cost_function_specification=None, cost_weights=None,
                  intermediate_steps=10, horizon_reduce="sum", phys=None, device=0, variable_parameters=None,
-                 per_env_pole_mass=False, fused=False, gru_model=None, gru_adjoint=False, gru_fused=False, **kwargs):
+                 per_env_pole_mass=False, fused=False, gru_model=None, gru_adjoint=False, gru_fused=False, rows=None, **kwargs):
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
         self.adam_epsilon, self.gradmax_clip, self.rtol = float(adam_epsilon), float(gradmax_clip), float(rtol)
         self.gradient_steps, self.warmup, self.warmup_iterations = int(gradient_steps), bool(warmup), int(warmup_iterations)
@@ -218,7 +257,7 @@ class optimizer_gradient(_GradientBase):
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, initial_action_stdev,
                          10, num_envs, cost_function_specification, cost_weights, intermediate_steps, phys, device,
                          variable_parameters, optimizer_logging, horizon_reduce, per_env_pole_mass, fused, gru_model, gru_adjoint,
-                         gru_fused)
+                         gru_fused, rows)
 
     def _fused_plan(self):
         return {"iterations": self.gradient_steps, "keep_k": self.num_rollouts, "resamp_per": 0, "shift": 1}
@@ -256,7 +295,7 @@ class optimizer_rpgd(_GradientBase):
                  warmup=False, warmup_iterations=250, optimizer_logging=False, calculate_optimal_trajectory=False,
                  num_envs=1, cost_function_specification=None, cost_weights=None, intermediate_steps=10,
                  horizon_reduce="sum", phys=None, device=0, variable_parameters=None, per_env_pole_mass=False, fused=False,
-                 gru_model=None, gru_adjoint=False, gru_fused=False, **kwargs):
+                 gru_model=None, gru_adjoint=False, gru_fused=False, rows=None, **kwargs):
         if SAMPLING_DISTRIBUTION not in ("normal", "uniform"):
             raise ValueError(f"SAMPLING_DISTRIBUTION={SAMPLING_DISTRIBUTION!r}; expected 'normal' or 'uniform'")
         self.learning_rate, self.adam_beta_1, self.adam_beta_2 = float(learning_rate), float(adam_beta_1), float(adam_beta_2)
@@ -271,7 +310,7 @@ class optimizer_rpgd(_GradientBase):
         super().__init__(cost_function, control_limits, seed, mpc_horizon, mpc_timestep, num_rollouts, stdev,
                          period_interpolation_inducing_points, num_envs, cost_function_specification, cost_weights,
                          intermediate_steps, phys, device, variable_parameters, optimizer_logging, horizon_reduce,
-                         per_env_pole_mass, fused, gru_model, gru_adjoint, gru_fused)
+                         per_env_pole_mass, fused, gru_model, gru_adjoint, gru_fused, rows)
 
     def _uniform_range(self):
         return (self.action_low, self.action_high) if self.sample_whole_control_space else \

@@ -59,7 +59,8 @@ extern "C" {
                                       cpmppi_rpgd_step_gru / cpmppi_rpgd_gru_reserve / cpmppi_rpgd_gru_args (new entry points, likewise);
                                       cpmppi_gru_advance (a new entry point, likewise);
                                       cpmppi_brunton / cpmppi_brunton_args, cpmppi_gru_washout (new entry points, likewise);
-                                      cpmppi_score_runs / cpmppi_score_args, cpmppi_set_tuning_rows (new entry points, likewise). */
+                                      cpmppi_score_runs / cpmppi_score_args, cpmppi_set_tuning_rows (new entry points, likewise);
+                                      cpmppi_rpgd_step_rows (a new entry point, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -601,6 +602,25 @@ typedef struct {
 } cpmppi_rpgd_args;
 int cpmppi_rpgd_reserve(cpmppi_handle* h, uint32_t E);
 int cpmppi_rpgd_step(cpmppi_handle* h, const cpmppi_rpgd_args* args, void* stream);
+
+/* cpmppi_rpgd_step with the controller's tuning PER ENV: rows[n_rows][CPMPPI_TUNING_ROW_FLOATS], DEVICE pointer, caller-owned,
+ * 64-byte aligned, indexed by the env index with which the call indexes L.  Entries 0-6 of a row are
+ * quadratic_boundary_grad_minimal's cost vector in cpmppi_set_cost_weights order (as a row of cpmppi_set_tuning_rows), entry
+ * CPMPPI_RPGD_ROW_LR Adam's learning rate and entry CPMPPI_RPGD_ROW_GRADMAX_CLIP the gradient-norm clip (<= 0: off); the other
+ * floats pad the row to 64 bytes and are not read.  args->learning_rate and args->gradmax_clip are not read.
+ * An env computes bit for bit what cpmppi_rpgd_step computes on a handle whose cost weights are its row, with that row's learning
+ * rate and clip in the argument block (rpgd_step_kernel compiled a second time, the nine values read per env through wave-uniform
+ * loads; with cpmppi_set_pole_mass_rows registered the env's pole mass is read as well).  The redraw of step 4 keeps the handle's
+ * sigma, as cpmppi_sample does, which draws the first plans.
+ * The call is stateless: nothing is registered on the handle.  Only the POINTER is fixed by a launch or a capture - the VALUES
+ * are read when the kernel runs, so a caller may rewrite the array between launches and between replays (stream-ordered).
+ * Otherwise the contract is cpmppi_rpgd_step's: count_dev, the workspace of cpmppi_rpgd_reserve under capture, the step counter.
+ * Refused (CPMPPI_ERR_BAD_ARG, "cpmppi_rpgd_step_rows: ...", nothing launched, outputs untouched): everything cpmppi_rpgd_step
+ * refuses, rows == NULL, a misaligned rows, n_rows < args->E, a handle whose cost plugin is not quadratic_boundary_grad_minimal,
+ * and a handle with rows of cpmppi_set_tuning_rows registered (those are the MPPI step's). */
+#define CPMPPI_RPGD_ROW_LR 7
+#define CPMPPI_RPGD_ROW_GRADMAX_CLIP 8
+int cpmppi_rpgd_step_rows(cpmppi_handle* h, const cpmppi_rpgd_args* args, const float* rows, uint32_t n_rows, void* stream);
 
 /* Plain gradient step Q <- clip(Q - learning_rate * clip_by_norm(grad, gradmax_clip)) on Q[E,N,H] in place
  * (cem-naive-grad-tf, config_optimizers.yml:21-31). */

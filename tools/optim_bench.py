@@ -34,6 +34,14 @@ The same comparison for rpgd (N = 16) and gradient-tf over the network, per E x 
 and torch glue, the memory through the predict seam) against fused (``gru_fused=True``: cpmppi_rpgd_step_gru + cpmppi_gru_advance),
 the same three columns and the same verdict.
 
+  python tools/optim_bench.py --rows [--rows-shapes 1x16x35x4,64x16x35x4,256x16x35x4,1x40x35x5,64x40x35x5,256x40x35x5]
+The fused ODE step with a row per env (cpmppi_rpgd_step_rows) against the plain fused step (cpmppi_rpgd_step), per E x N x H x
+iterations (N = 16: rpgd, otherwise gradient-tf) and predictor: two optimizers of one seed, the rows equal to the scalars so that the
+work is the same, ``step_device`` with the step counter on the device, the two alternating in this one process - and with them a
+second plain optimizer ("plain_again": the plain step on another engine's buffers, the control of the comparison); device time per
+control step from events around batches of steps, medians over the rounds with min and max, and whether the rows step stays within
+the plain median + the plain runs' own min - max spread.
+
   python tools/optim_bench.py --gru-grad [--steps 30] [--grad-shapes 1x16x35,64x16x35,1x40x35,64x40x35]
 The GRU adjoint (same synthetic weights).  Per E x N x H of --grad-shapes (default: the rpgd and gradient-tf sizes at 1 and 64
 envs) and math mode, cpmppi_rollout_cost_grad_gru against cpmppi_rollout_cost_gru on the same plans, alternating in one process as
@@ -67,6 +75,9 @@ ap.add_argument("--cem-shapes", default="1x200x35,64x200x35,256x200x35", help="w
 ap.add_argument("--gru-rpgd", action="store_true", help="rpgd and gradient-tf over the GRU predictor: the staged step (gru_adjoint) against the fused one (gru_fused)")
 ap.add_argument("--rpgd-shapes", default="1x16x35x4,64x16x35x4,256x16x35x4,1x40x35x5,64x40x35x5,256x40x35x5",
                 help="with --gru-rpgd: ExNxHxiterations,... (N = 16: rpgd, otherwise gradient-tf)")
+ap.add_argument("--rows", action="store_true", help="the fused ODE rpgd / gradient step: a row per env (cpmppi_rpgd_step_rows) against the plain step")
+ap.add_argument("--rows-shapes", default="1x16x35x4,64x16x35x4,256x16x35x4,1x40x35x5,64x40x35x5,256x40x35x5",
+                help="with --rows: ExNxHxiterations,... (N = 16: rpgd, otherwise gradient-tf)")
 ap.add_argument("--gru-grad", action="store_true", help="the GRU adjoint: gradient launch vs cost-only launch; rpgd and gradient-tf over the GRU vs the ODE")
 ap.add_argument("--grad-shapes", default="1x16x35,64x16x35,1x40x35,64x40x35", help="with --gru-grad: ExNxH,...")
 ap.add_argument("--datagen", default=None, help="with --fused: E,seconds of the closed-loop data generator, e.g. 256,10")
@@ -273,6 +284,50 @@ def gru_step_bench(bench, shapes, make):
                 o.engine.close()
 
 
+def rows_bench():
+    """The fused ODE step, plain against a row per env (the module docstring)."""
+    from cartpolesimulation_amd.configs import rpgd_rows
+    from cartpolesimulation_amd.optimizer_gradient import optimizer_gradient, optimizer_rpgd
+    rounds, batch = 12, 10
+    for shape in filter(None, args.rows_shapes.split(",")):
+        e, n, h, iterations = (int(x) for x in shape.split("x"))
+        g = np.random.Generator(np.random.SFC64(11))
+        s0 = np.stack([O.create_cartpole_state(g.uniform(-0.3, 0.3), g.uniform(-0.5, 0.5), g.uniform(-0.05, 0.05), 0.0) for _ in range(e)])
+        for spec in ("ODE_v0", "ODE"):
+            opts = {}
+            for mode in ("plain", "rows", "plain_again"):        # (a second plain optimizer: what another set of buffers costs)
+                common = dict(control_limits=([-1.0], [1.0]), seed=1, num_envs=e, num_rollouts=n, mpc_horizon=h, fused=True)
+                if mode == "rows":                               # the plain optimizer's scalars, per env: the same work
+                    plain = opts["plain"]
+                    common["rows"] = rpgd_rows(plain.cfg, e, plain.learning_rate, plain.gradmax_clip)
+                opt = optimizer_rpgd(outer_its=iterations, **common) if n == 16 else optimizer_gradient(gradient_steps=iterations, **common)
+                opt.configure(predictor_specification=spec)
+                opt.reserve_fused()
+                opts[mode] = opt
+            steps = {}
+            for mode, opt in opts.items():
+                eng = opt.engine
+                s, tp, te, L = eng.tensor(s0), eng.zeros(e), eng.zeros(e) + 1.0, eng.zeros(e) + 0.395
+                counter = torch.zeros(1, dtype=torch.int64, device=s.device)
+                steps[mode] = (lambda opt=opt, s=s, tp=tp, te=te, L=L, counter=counter:
+                               opt.step_device(s, tp, te, L=L, previous_input=opt.controls, count_dev=counter))
+            ms = alternating(steps, rounds, batch)
+            torch.cuda.synchronize()
+            assert torch.equal(opts["plain"].Q, opts["rows"].Q) and torch.equal(opts["plain"].Q, opts["plain_again"].Q)   # (the same steps, to the bit)
+            rec = {"bench": "rpgd_step_rows", "optimizer": opts["rows"].optimizer_name, "predictor": spec, "envs": e, "num_rollouts": n,
+                   "mpc_horizon": h, "iterations": iterations, "rounds": rounds, "steps_per_round": batch}
+            for k, v in ms.items():
+                rec[k + "_ms"] = round(float(np.median(v)), 5)
+                rec[k + "_min_max_ms"] = [round(float(min(v)), 5), round(float(max(v)), 5)]
+            lo, hi = rec["plain_min_max_ms"]
+            rec["rows_over_plain"] = round(rec["rows_ms"] / rec["plain_ms"], 4)
+            rec["rows_within_plain_spread"] = bool(rec["rows_ms"] <= rec["plain_ms"] + (hi - lo))
+            rec["plain_again_over_plain"] = round(rec["plain_again_ms"] / rec["plain_ms"], 4)
+            print(json.dumps(rec), flush=True)
+            for o in opts.values():
+                o.engine.close()
+
+
 def alternating(launches, rounds=12, batch=10):
     """Device ms per launch of each entry of `launches`, the entries alternating: {name: [ms per round]} (two warm-up rounds)."""
     ms = {k: [] for k in launches}
@@ -355,6 +410,9 @@ def gru_grad_bench():
 
 if args.fused:
     fused_bench()
+    sys.exit(0)
+if args.rows:
+    rows_bench()
     sys.exit(0)
 if args.gru_grad:
     gru_grad_bench()
