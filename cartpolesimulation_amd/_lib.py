@@ -32,7 +32,10 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_rpgd_reserve", "cpmppi_rpgd_step", "cpmppi_cem_reserve", "cpmppi_cem_step", "cpmppi_rollout_cost_gru",
            "cpmppi_rollout_cost_grad_gru", "cpmppi_gru_advance", "cpmppi_gru_washout", "cpmppi_brunton",
            "cpmppi_score_runs", "cpmppi_set_tuning_rows", "cpmppi_replay_step", "cpmppi_cem_step_gru",
-           "cpmppi_rpgd_step_gru", "cpmppi_rpgd_gru_reserve", "cpmppi_rpgd_step_rows")
+           "cpmppi_rpgd_step_gru", "cpmppi_rpgd_gru_reserve", "cpmppi_rpgd_step_rows",
+           "cpmppi_gru_train_reserve", "cpmppi_gru_loss_grad", "cpmppi_gru_train_begin", "cpmppi_gru_train_step",
+           "cpmppi_gru_train_get")
+GRU_PARAMS = 10341                                   # CPMPPI_GRU_PARAMS: the flat parameter vector of the training entry points
 TUNING_ROW_FLOATS, TUNING_LBD, TUNING_SIGMA = 16, 7, 8
 RPGD_ROW_LR, RPGD_ROW_GRADMAX_CLIP = 7, 8            # cpmppi_rpgd_step_rows: the same row, these two behind the seven cost entries
 SCORE_FLOATS = 5
@@ -112,6 +115,12 @@ class cpmppi_brunton_args(C.Structure):
     _fields_ = [("R", C.c_uint32), ("T", C.c_uint32), ("start", C.c_uint32), ("count", C.c_uint32), ("horizon", C.c_uint32),
                 ("predictor", C.c_uint32), ("states", C.c_void_p), ("Q", C.c_void_p), ("L", C.c_void_p), ("h_rows", C.c_void_p),
                 ("stats_out", C.c_void_p), ("pred_out", C.c_void_p)]
+
+
+class cpmppi_gru_loss_args(C.Structure):
+    _fields_ = [("B", C.c_uint32), ("R", C.c_uint32), ("T", C.c_uint32), ("wash_out", C.c_uint32), ("post_wash_out", C.c_uint32),
+                ("shift_labels", C.c_uint32), ("states", C.c_void_p), ("Q", C.c_void_p), ("windows", C.c_void_p),
+                ("windows_host", C.c_void_p), ("loss_out", C.c_void_p), ("grad_out", C.c_void_p)]
 
 
 class cpmppi_score_args(C.Structure):
@@ -248,6 +257,11 @@ def load():
     lib.cpmppi_rpgd_gru_reserve.restype = C.c_int
     lib.cpmppi_rpgd_step_gru.argtypes = [vp, C.POINTER(cpmppi_rpgd_gru_args), vp]
     lib.cpmppi_rpgd_step_gru.restype = C.c_int
+    lib.cpmppi_gru_train_reserve.argtypes = [vp, u32, u32]
+    lib.cpmppi_gru_loss_grad.argtypes = [vp, C.POINTER(cpmppi_gru_loss_args), vp]
+    lib.cpmppi_gru_train_begin.argtypes = [vp]
+    lib.cpmppi_gru_train_step.argtypes = [vp, C.POINTER(cpmppi_gru_loss_args), f, f, f, f, vp]
+    lib.cpmppi_gru_train_get.argtypes = [vp, C.POINTER(f)]
     lib.cpmppi_cem_sample.argtypes = [vp, u32, vp, vp, u64, u64, u32, vp, vp]
     lib.cpmppi_cem_update.argtypes = [vp, u32, vp, vp, u32, f, vp, vp, vp, vp]
     lib.cpmppi_tiled_floats.argtypes = [vp, u32]

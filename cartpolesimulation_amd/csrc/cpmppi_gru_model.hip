@@ -123,7 +123,54 @@ void pack_transposed_image(const cpmppi_gru_model* m, float* imgt) {
     }
 }
 
+// The flat parameter vector (CPMPPI_GRU_PARAMS, the order of cpmppi_gru_model's fields) and a model that points into one.
+constexpr size_t FLAT_SIZES[10] = {96 * 6, 96 * 32, 96, 96, 96 * 32, 96 * 32, 96, 96, 5 * 32, 5};
+cpmppi_gru_model flat_model(const float* p) {
+  cpmppi_gru_model m{};
+  m.inputs = 6; m.hidden = 32; m.layers = 2; m.outputs = 5;
+  for (int l = 0; l < 2; ++l) {
+    m.w_ih[l] = p; p += FLAT_SIZES[4 * l + 0];
+    m.w_hh[l] = p; p += FLAT_SIZES[4 * l + 1];
+    m.b_ih[l] = p; p += FLAT_SIZES[4 * l + 2];
+    m.b_hh[l] = p; p += FLAT_SIZES[4 * l + 3];
+  }
+  m.w_out = p; p += FLAT_SIZES[8];
+  m.b_out = p;
+  return m;
+}
+void flatten_model(const cpmppi_gru_model* m, std::vector<float>& flat) {
+  const float* src[10] = {m->w_ih[0], m->w_hh[0], m->b_ih[0], m->b_hh[0], m->w_ih[1], m->w_hh[1], m->b_ih[1], m->b_hh[1], m->w_out, m->b_out};
+  flat.clear();
+  for (int i = 0; i < 10; ++i) flat.insert(flat.end(), src[i], src[i] + FLAT_SIZES[i]);
+}
+
 }  // namespace
+
+// The two packers run twice over weights that name themselves - parameter i holds i + 1 (exact in float32), once with every b_hh
+// zero and once with the b_hh alone - so a float of an image reads back which parameter it is (0: none), and a gate bias that is
+// the sum b_ih + b_hh reads back one term per run.
+void gru_image_sources(std::vector<int32_t>& src) {
+  const size_t P = CPMPPI_GRU_PARAMS, n = (size_t)GRU_IMAGE_FLOATS + GRU_T_IMAGE_FLOATS;
+  std::vector<float> flat[2] = {std::vector<float>(P, 0.0f), std::vector<float>(P, 0.0f)};
+  size_t at = 0;
+  for (int i = 0; i < 10; ++i) {
+    const bool hh = i == 3 || i == 7;                      // b_hh0, b_hh1
+    for (size_t k = 0; k < FLAT_SIZES[i]; ++k, ++at) flat[hh ? 1 : 0][at] = (float)(at + 1);
+  }
+  std::vector<float> img[2];
+  for (int run = 0; run < 2; ++run) {
+    img[run].assign(n, 0.0f);
+    const cpmppi_gru_model m = flat_model(flat[run].data());
+    pack_f32_image(&m, img[run].data());
+    pack_transposed_image(&m, img[run].data() + GRU_IMAGE_FLOATS);
+  }
+  src.assign(2 * n, -1);
+  for (size_t i = 0; i < n; ++i) {
+    int k = 0;
+    for (int run = 0; run < 2; ++run)
+      if (img[run][i] != 0.0f) src[2 * i + k++] = (int32_t)img[run][i] - 1;
+  }
+}
 
 extern "C" {
 
@@ -156,6 +203,7 @@ int cpmppi_set_gru(cpmppi_handle* h, const cpmppi_gru_model* m) try {
   allow_large_lds_gru_rpgd();         // (... and the fused rpgd step keeps the rollout's image beside them)
   if (!h->gru16_image) CPMPPI_HIP(h, hipMalloc(&h->gru16_image, img16.size()));
   CPMPPI_HIP(h, hipMemcpy(h->gru16_image, img16.data(), img16.size(), hipMemcpyHostToDevice));
+  flatten_model(m, h->gru_params);    // (what cpmppi_gru_train_begin starts from)
   return CPMPPI_OK;
 } catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }   // (no C++ exception leaves the C ABI)
 

@@ -14,6 +14,8 @@
 //   cpmppi_gru_adjoint.hip  the gradient's reverse sweep
 //   cpmppi_gru_rpgd.hip   the fused rpgd / gradient-tf step over the GRU predictor (cpmppi_rpgd_step_gru): forward sweep, reverse sweep,
 //                         Adam, ranking, resampling and shift in one kernel
+//   cpmppi_gru_train.hip  training on recordings: teacher-forced loss, BPTT weight gradient, Adam and the image rebuild on the device
+//                         (cpmppi_gru_loss_grad, cpmppi_gru_train_*)
 //   cpmppi_gru_model.hip  host code only: cpmppi_set_gru packs and uploads the three weight images
 //   cpmppi_comm.hip, cpmppi_groups.hip, cpmppi_io.hip   host code only: the collective, env groups, the recording writer
 //   cpmppi_rollout_*.hip  the instances of rollout_cost_kernel, each unit with its own compiler flags
@@ -104,6 +106,8 @@ struct cpmppi_handle {
   float* cem_ws = nullptr;             // cpmppi_cem_step: samples [E][H][block]; refining, + check-points, gradients, Adam moments (cpmppi_cem_reserve)
   size_t cem_ws_floats = 0;
   cpmppi::GruNorm gru_norm;
+  std::vector<float> gru_params;       // the weights of the last cpmppi_set_gru in the flat order of CPMPPI_GRU_PARAMS (cpmppi_gru_train_begin)
+  struct GruTrain* gru_train = nullptr;  // training on recordings (cpmppi_gru_train.hip): workspace, master copy, moments; or none yet
   bool fuse_finalize = true;           // ODE path: the env's last block finalizes in-kernel (CPMPPI_FUSE_FINALIZE=0 disables)
   uint32_t profile_every = 0;          // 0 = off, 1 = every rollout kernel bracketed, n > 1 = one bracket around n steps
   uint32_t profile_count = 0;
@@ -242,6 +246,12 @@ void launch_gru_grad_reverse(cpmppi_handle* h, uint32_t E, const float* s0, cons
 void allow_large_lds_gru_adjoint();
 // cpmppi_gru_rpgd.hip: the LDS opt-in of the fused rpgd / gradient step over the network (cpmppi_set_gru)
 void allow_large_lds_gru_rpgd();
+// cpmppi_gru_model.hip: where every float of the exact-f32 image and, behind it, of the transposed image comes from, read off
+// pack_f32_image / pack_transposed_image themselves: src[2 * i], src[2 * i + 1] = indices into the flat parameter vector whose sum
+// the float is (-1: none; both -1: zero) - the table of the on-device rebuild (cpmppi_gru_train.hip)
+void gru_image_sources(std::vector<int32_t>& src);
+// cpmppi_gru_train.hip: frees what training allocated (cpmppi_destroy)
+void gru_train_destroy(cpmppi_handle* h);
 // cpmppi_gru_seam.hip: the Brunton test's GRU kernel (one partial row per wave of 32 starts: brunton_gru_rows of them); the caller
 // has checked the arguments, checks the launch and reduces the partial rows
 inline size_t brunton_gru_rows(size_t starts) { return (starts + 31) / 32; }

@@ -667,6 +667,105 @@ class MPPIEngine:
         buffers (a benchmark loop, a capture - after one plain run, which allocates the workspace)."""
         return self._build_brunton(*args, **kwargs)
 
+    # ------------------------------------------------------------------ training the GRU predictor on recordings
+    def _gru_loss_args(self, states, Q, windows, wash_out, post_wash_out, shift_labels, loss_out=None, grad_out=None, grad=True):
+        """The argument block of cpmppi_gru_loss_grad / cpmppi_gru_train_step, checked: -> (block, what it points into, loss_out,
+        grad_out).  ``windows`` [B,2] integers (r, t0) on the HOST: uploaded here, and handed to the library as its host copy."""
+        if not self.has_gru:
+            raise ValueError("no model set: call set_gru first")
+        states, Q, R, T = self._recordings(states, Q)
+        W, P, shift = int(wash_out), int(post_wash_out), int(shift_labels)
+        if W < 0 or P < 1 or shift < 0:
+            raise ValueError(f"wash_out >= 0, post_wash_out >= 1 and shift_labels >= 0, got {W}, {P}, {shift}")
+        w = np.asarray(windows.cpu() if torch.is_tensor(windows) else windows)
+        if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] == 0 or not np.issubdtype(w.dtype, np.integer):
+            raise ValueError(f"windows must be integers [B,2] = (recording, first row) with B >= 1, got {w.dtype} {w.shape}")
+        if w.min() < 0 or w[:, 0].max() >= R or w[:, 1].max() + W + P - 1 + shift > T - 1:
+            raise ValueError(f"every window (r, t0) must satisfy r < {R} and t0 + {W} + {P} - 1 + {shift} <= {T - 1}")
+        w_host = np.ascontiguousarray(w, dtype=np.uint32)
+        w_dev = torch.as_tensor(w_host.astype(np.int32)).to(self.device)
+        if loss_out is None:
+            loss_out = torch.empty(1, dtype=torch.float64, device=self.device)
+        elif device_tensor("loss_out", loss_out, torch.float64).numel() != 1:
+            raise ValueError("loss_out must have one element")
+        if grad and grad_out is None:
+            grad_out = self.empty(_L.GRU_PARAMS)
+        elif grad_out is not None and (not grad or device_tensor("grad_out", grad_out).shape != (_L.GRU_PARAMS,)):
+            raise ValueError(f"grad_out must be [{_L.GRU_PARAMS}] (and grad=True)")
+        a = _L.cpmppi_gru_loss_args()
+        a.B, a.R, a.T, a.wash_out, a.post_wash_out, a.shift_labels = w.shape[0], R, T, W, P, shift
+        a.states, a.Q, a.windows, a.windows_host = states.data_ptr(), Q.data_ptr(), w_dev.data_ptr(), w_host.ctypes.data
+        a.loss_out, a.grad_out = loss_out.data_ptr(), _addr(grad_out)
+        return a, (states, Q, w_dev, w_host, loss_out, grad_out), loss_out, grad_out
+
+    def gru_train_reserve(self, B, rows):
+        """cpmppi_gru_train_reserve: the workspace of ``gru_loss_grad`` / ``gru_train_step`` for ``B`` windows of ``rows`` = wash_out +
+        post_wash_out rows, so that a later call can be captured."""
+        self._check(self.lib.cpmppi_gru_train_reserve(self._h, int(B), int(rows)))
+
+    def _build_gru_loss_grad(self, states, Q, windows, wash_out, post_wash_out, shift_labels=1, grad=True, *, loss_out=None,
+                             grad_out=None):
+        """cpmppi_gru_loss_grad: the teacher-forced loss of the model of ``set_gru`` over ``windows`` [B,2] = (recording, first row)
+        of ``states`` [R,T,6], ``Q`` [R,T] (include/cpmppi.h states it): the memory starts at zero, ``wash_out`` rows build it,
+        ``post_wash_out`` rows are scored against the normalised features ``shift_labels`` rows on.
+        -> (loss [1] float64 on the device, gradient [10341] in the flat order of ``GRU_KEYS`` - None with ``grad=False``, the
+        loss alone, bit for bit the loss of the gradient call)."""
+        a, keep, loss_out, grad_out = self._gru_loss_args(states, Q, windows, wash_out, post_wash_out, shift_labels, loss_out,
+                                                          grad_out, grad)
+        return PreparedCall(self, self.lib.cpmppi_gru_loss_grad, a, keep, (loss_out, grad_out), ())
+
+    gru_loss_grad = _run_once(_build_gru_loss_grad)
+
+    def prepare_gru_loss_grad(self, *args, **kwargs):
+        """The argument block of ``gru_loss_grad(...)`` built and validated ONCE: ``.run()`` enqueues the launches again on the same
+        buffers (a capture - after one plain run or ``gru_train_reserve``, which allocate the workspace)."""
+        return self._build_gru_loss_grad(*args, **kwargs)
+
+    def gru_train_begin(self):
+        """cpmppi_gru_train_begin: training starts from the model of the last ``set_gru`` - a master copy on the device, Adam's
+        moments and step counter zero."""
+        if not self.has_gru:
+            raise ValueError("no model set: call set_gru first")
+        self._check(self.lib.cpmppi_gru_train_begin(self._h))
+
+    def gru_train_step(self, states, Q, windows, wash_out, post_wash_out, shift_labels=1, *, lr, beta1=0.9, beta2=0.999,
+                       eps=1e-8, loss_out=None):
+        """cpmppi_gru_train_step: the loss and gradient of ``gru_loss_grad`` over this batch of ``windows``, one Adam update of the
+        master copy and the rebuild of the exact-f32 weight images, all on the device.  -> the batch's loss BEFORE the update,
+        [1] float64 on the device."""
+        a, keep, loss_out, _ = self._gru_loss_args(states, Q, windows, wash_out, post_wash_out, shift_labels, loss_out, None, False)
+        self._check(self.lib.cpmppi_gru_train_step(self._h, C.byref(a), float(lr), float(beta1), float(beta2), float(eps),
+                                                   self._stream()))
+        self._train_keep = keep                       # (the launches read the batch after this call returns)
+        return loss_out
+
+    def gru_train_get(self):
+        """cpmppi_gru_train_get: the trained weights as the dict ``set_gru`` takes (weights only; the normalisation is the
+        caller's).  Synchronous."""
+        flat = np.empty(_L.GRU_PARAMS, np.float32)
+        self._check(self.lib.cpmppi_gru_train_get(self._h, flat.ctypes.data_as(C.POINTER(C.c_float))))
+        return self.gru_unflatten(flat)
+
+    GRU_SHAPES = ((96, 6), (96, 32), (96,), (96,), (96, 32), (96, 32), (96,), (96,), (5, 32), (5,))
+
+    @classmethod
+    def gru_unflatten(cls, flat):
+        """The flat parameter vector [10341] of the training entry points -> {key: array} in the order and shapes of ``GRU_KEYS``."""
+        flat = np.asarray(flat)
+        if flat.shape != (_L.GRU_PARAMS,):
+            raise ValueError(f"the flat parameter vector has {_L.GRU_PARAMS} entries, got {flat.shape}")
+        out, at = {}, 0
+        for k, shp in zip(cls.GRU_KEYS, cls.GRU_SHAPES):
+            n = int(np.prod(shp))
+            out[k] = flat[at:at + n].reshape(shp).copy()
+            at += n
+        return out
+
+    @classmethod
+    def gru_flatten(cls, model):
+        """{key: array} -> the flat float32 parameter vector [10341]."""
+        return np.concatenate([np.asarray(model[k], np.float32).reshape(-1) for k in cls.GRU_KEYS])
+
     # ------------------------------------------------------------------ score of a recording, per env
     def _build_score_runs(self, states, Q=None, *, target_position=0.0, target_position_table=None, save_every=1, sched_stride=1,
                           period_steps=None, first_row=0, last_row=None, out=None):
@@ -1201,7 +1300,7 @@ class MPPIEngine:
 
 class PreparedCall:
     """One entry point of the library that takes an argument block, ready to be enqueued any number of times
-    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_rpgd_step_gru / prepare_cem_step / prepare_cem_step_gru / prepare_brunton).  ``args`` is the live
+    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_rpgd_step_gru / prepare_cem_step / prepare_cem_step_gru / prepare_brunton / prepare_gru_loss_grad).  ``args`` is the live
     ctypes block, validated when it was built, and ``ref`` the reference to it that the library is handed; ``keep`` holds the
     tensors it points into; ``enqueue`` is the entry point, ``enqueue(handle, ref, stream)``.  ``result`` is what the call returns:
     the outputs of a control step - ``out``, whose first two are ``Q_out`` and ``S_out`` -, the plant's state, or the Brunton

@@ -60,7 +60,9 @@ extern "C" {
                                       cpmppi_gru_advance (a new entry point, likewise);
                                       cpmppi_brunton / cpmppi_brunton_args, cpmppi_gru_washout (new entry points, likewise);
                                       cpmppi_score_runs / cpmppi_score_args, cpmppi_set_tuning_rows (new entry points, likewise);
-                                      cpmppi_rpgd_step_rows (a new entry point, likewise). */
+                                      cpmppi_rpgd_step_rows (a new entry point, likewise);
+                                      cpmppi_gru_loss_grad / cpmppi_gru_loss_args, cpmppi_gru_train_reserve / _begin / _step / _get
+                                      (new entry points, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -481,6 +483,57 @@ typedef struct {
   float* u_nom_reset;                   /* [E,H] or NULL */
 } cpmppi_replay_args;
 int cpmppi_replay_step(cpmppi_handle* h, const cpmppi_replay_args* args, void* stream);
+
+/* Training the GRU predictor on recordings (SI_Toolkit_ASF/Run/A2_Train_Network.py with config_training.yml; the training code
+ * itself is not part of the reference checkout, so the semantics here are this library's own): the teacher-forced loss of the
+ * handle's model over windows of recordings, its gradient by back-propagation through time, and Adam on the device.
+ * The parameters are ONE flat float32 vector of CPMPPI_GRU_PARAMS floats in the torch.nn.GRU order of cpmppi_gru_model:
+ *   w_ih0[96,6] w_hh0[96,32] b_ih0[96] b_hh0[96] w_ih1[96,32] w_hh1[96,32] b_ih1[96] b_hh1[96] w_out[5,32] b_out[5].
+ *
+ * cpmppi_gru_loss_grad: B windows (r, t0) of W + P rows each, W = wash_out, P = post_wash_out, over recordings in the layout of
+ * cpmppi_brunton.  Per window the memory starts at zero and rows t0 .. t0+W+P-1 are fed AS RECORDED - the normalised
+ * (Q, angleD, angle_cos, angle_sin, position, positionD); nothing is fed back.  The loss is the mean over B x P x 5 of the squared
+ * difference between the head's normalised output at window row j >= W and the label (x - out_shift) / out_scale of the features
+ * x of recorded row t0 + j + shift_labels.  loss_out: one DEVICE double.  grad_out[CPMPPI_GRU_PARAMS] (DEVICE): d loss / d
+ * parameters in the flat order, or NULL for the loss alone (validation), which equals the loss of a gradient call bit for bit.
+ * Exact-f32 cell and exact-f32 MFMA throughout; every reduction runs in a fixed order without atomics: the same bits from run to
+ * run.  Launches on `stream`: forward sweep, loss; with a gradient also the reverse sweep, the weight-gradient contraction and its
+ * reduction.  The workspace (check-points and adjoints of every (row, window)) is reserved by cpmppi_gru_train_reserve(h, B, rows)
+ * for windows of up to `rows` = W + P rows, or on first use - a capture that would have to allocate is refused.
+ * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned ("cpmppi_gru_loss_grad: ...") when no model is set; states, Q, windows,
+ * windows_host or loss_out is NULL; B, R, T or post_wash_out is 0; a host window lies outside r < R,
+ * t0 + W + P - 1 + shift_labels <= T - 1.  A misaligned pointer is CPMPPI_ERR_ALIGN.
+ *
+ * cpmppi_gru_train_begin: a device master copy of the handle's model (the weights of the last cpmppi_set_gru) in the flat order,
+ * both Adam moments zero, the device step counter 0; the two float32 images below are rebuilt from it.  Synchronous.
+ * cpmppi_gru_train_step: (1) cpmppi_gru_loss_grad into the handle's own gradient buffer (loss_args->grad_out is not read),
+ * (2) one bias-corrected Adam update of the master copy, t = the device counter + 1, formed in float64 and stored as float32:
+ *     m = b1 m + (1-b1) g, v = b2 v + (1-b2) g^2, p -= lr (m / (1-b1^t)) / (sqrt(v / (1-b2^t)) + eps),
+ * (3) the rebuild ON THE DEVICE of the two float32 weight images the training kernels read - the fragment image and the
+ * transposed image of the exact-f32 cell - bit for bit what cpmppi_set_gru builds on the host for the same weights.  The f16 image
+ * of the fused rollout kernels keeps the model of the last cpmppi_set_gru: a trained model reaches them through
+ * cpmppi_gru_train_get and cpmppi_set_gru.  No host synchronisation: capturable after a reserving call.
+ * CPMPPI_ERR_BAD_ARG ("cpmppi_gru_train_step: ...") without cpmppi_gru_train_begin, and what cpmppi_gru_loss_grad refuses.
+ * cpmppi_gru_train_get: the master copy -> params_host[CPMPPI_GRU_PARAMS], synchronously. */
+#define CPMPPI_GRU_PARAMS 10341u
+typedef struct {
+  uint32_t B;                           /* windows */
+  uint32_t R, T;                        /* recordings, rows of each */
+  uint32_t wash_out, post_wash_out;     /* W rows that only build the memory, then P >= 1 rows that are scored */
+  uint32_t shift_labels;                /* the label of a row lies this many rows on (1 for a dynamics model) */
+  const float* states;                  /* [R,T,6] */
+  const float* Q;                       /* [R,T] */
+  const uint32_t* windows;              /* [B][2] DEVICE: (r, t0) */
+  const uint32_t* windows_host;         /* [B][2] HOST: the same, checked by every call */
+  double* loss_out;                     /* DEVICE, one double */
+  float* grad_out;                      /* [CPMPPI_GRU_PARAMS] DEVICE, or NULL */
+} cpmppi_gru_loss_args;
+int cpmppi_gru_train_reserve(cpmppi_handle* h, uint32_t B, uint32_t rows);
+int cpmppi_gru_loss_grad(cpmppi_handle* h, const cpmppi_gru_loss_args* args, void* stream);
+int cpmppi_gru_train_begin(cpmppi_handle* h);
+int cpmppi_gru_train_step(cpmppi_handle* h, const cpmppi_gru_loss_args* args, float lr, float beta1, float beta2, float eps,
+                          void* stream);
+int cpmppi_gru_train_get(cpmppi_handle* h, float* params_host);
 
 /* Rollout + cost only (no update): per-rollout trajectory cost S[E,N] of GIVEN input sequences inputs[E,N,H] under the
  * handle's plugin cost — cost_function.get_trajectory_cost(predictor.predict_core(s, Q), Q) fused; the building block of
