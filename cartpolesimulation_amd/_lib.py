@@ -34,7 +34,7 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_score_runs", "cpmppi_set_tuning_rows", "cpmppi_replay_step", "cpmppi_cem_step_gru",
            "cpmppi_rpgd_step_gru", "cpmppi_rpgd_gru_reserve", "cpmppi_rpgd_step_rows",
            "cpmppi_gru_train_reserve", "cpmppi_gru_loss_grad", "cpmppi_gru_train_begin", "cpmppi_gru_train_step",
-           "cpmppi_gru_train_get")
+           "cpmppi_gru_train_get", "cpmppi_gru_rollout_loss_grad", "cpmppi_gru_rollout_train_step")
 GRU_PARAMS = 10341                                   # CPMPPI_GRU_PARAMS: the flat parameter vector of the training entry points
 TUNING_ROW_FLOATS, TUNING_LBD, TUNING_SIGMA = 16, 7, 8
 RPGD_ROW_LR, RPGD_ROW_GRADMAX_CLIP = 7, 8            # cpmppi_rpgd_step_rows: the same row, these two behind the seven cost entries
@@ -262,6 +262,8 @@ def load():
     lib.cpmppi_gru_train_begin.argtypes = [vp]
     lib.cpmppi_gru_train_step.argtypes = [vp, C.POINTER(cpmppi_gru_loss_args), f, f, f, f, vp]
     lib.cpmppi_gru_train_get.argtypes = [vp, C.POINTER(f)]
+    lib.cpmppi_gru_rollout_loss_grad.argtypes = [vp, C.POINTER(cpmppi_gru_loss_args), vp]
+    lib.cpmppi_gru_rollout_train_step.argtypes = [vp, C.POINTER(cpmppi_gru_loss_args), f, f, f, f, vp]
     lib.cpmppi_cem_sample.argtypes = [vp, u32, vp, vp, u64, u64, u32, vp, vp]
     lib.cpmppi_cem_update.argtypes = [vp, u32, vp, vp, u32, f, vp, vp, vp, vp]
     lib.cpmppi_tiled_floats.argtypes = [vp, u32]

@@ -1,14 +1,18 @@
-// cpmppi_gru_train.hip — training the GRU predictor on recordings (cpmppi_gru_loss_grad, cpmppi_gru_train_*): the teacher-forced loss
-// over windows of recordings, its gradient with respect to the weights by back-propagation through time, Adam and the rebuild of the
-// two float32 weight images on the device.  Small kernels, one job each, no float atomics; every sum runs in a fixed order.
-//   gru_train_forward_kernel<STORE>   gru_washout_kernel's mapping (32 windows per wave on lanes c and c + 32, one wave per SIMD, the
-//                                     exact-f32 gru_step cell) from a zero memory over the window's W + P recorded rows.  Per wave a
-//                                     partial loss; STORE: per (row, window) a check-point - both hidden tiles, the head adjoint
-//                                     2 (y - label) / (B P 5) (0 on wash-out rows) and the input tile.
+// cpmppi_gru_train.hip — training the GRU predictor on recordings (cpmppi_gru_loss_grad, cpmppi_gru_rollout_loss_grad,
+// cpmppi_gru_train_*): the loss over windows of recordings - teacher-forced, or through the open-loop rollout the predictor is used
+// in -, its gradient with respect to the weights by back-propagation through time, Adam and the rebuild of the two float32 weight
+// images on the device.  Small kernels, one job each, no float atomics; every sum runs in a fixed order.
+//   gru_train_forward_kernel<STORE, ROLLOUT>
+//                                     gru_washout_kernel's mapping (32 windows per wave on lanes c and c + 32, one wave per SIMD, the
+//                                     exact-f32 gru_step cell) from a zero memory over the window's W + P rows: recorded rows, or
+//                                     (ROLLOUT) behind row W the head's outputs of the row before with the recorded control.  Per
+//                                     wave a partial loss; STORE: per (row, window) a check-point - both hidden tiles, the head adjoint
+//                                     2 (y - label) / (B P 5) (0 on wash-out rows) and the input tile the cell consumed.
 //   gru_loss_finalize_kernel          the waves' partial losses summed in float64 -> loss_out.
-//   gru_train_reverse_kernel          rows last to first: gru_layer_reverse per layer on both images in LDS (98 208 B, opt-in); there
-//                                     is no feedback path and no cost stage.  Writes the eight pre-activation adjoint tiles per
-//                                     (row, window).
+//   gru_train_reverse_kernel<ROLLOUT> rows last to first: gru_layer_reverse per layer on both images in LDS (98 208 B, opt-in); there
+//                                     is no cost stage.  Writes the eight pre-activation adjoint tiles per (row, window).  ROLLOUT:
+//                                     the feedback path of gru_reverse_steps - rows 0..4 of the input adjoint of a fed-back row join
+//                                     the head adjoint of the row before, in the check-point.
 //   gru_wgrad_kernel                  dW = sum over (row, window) of da (x) input per matrix and gate on v_mfma_f32_32x32x2_f32 with
 //                                     the WINDOW as the contraction index: check-points and adjoints lie [row][window][unit], so a
 //                                     lane loads its A and B operands as they stand.  One wave per (product, slice of the (row, window
@@ -81,7 +85,9 @@ __device__ __forceinline__ f16v zero_tile() {
 
 // Window first + c of the wave's tile on lanes c and c + 32; a lane beyond B repeats window 0, adds nothing to the loss and parks a
 // zero head adjoint (its adjoints are stored as zeros by the reverse sweep, so the contraction may read whole tiles).
-template <bool STORE>
+// ROLLOUT: rows j > W take input rows 0..4 from the head's normalised output of row j - 1, unchanged (gru_predict_kernel's rule), and
+// row 5 from the recorded Q[t0 + j]; the check-point's input tile is the tile the cell consumed.
+template <bool STORE, bool ROLLOUT>
 __global__ __launch_bounds__(BLOCK, 1) void gru_train_forward_kernel(const cpmppi::GruNorm nm, const float* __restrict__ image,
                                                                      const GruTrainArgs a) {
   extern __shared__ float lds[];
@@ -97,9 +103,17 @@ __global__ __launch_bounds__(BLOCK, 1) void gru_train_forward_kernel(const cpmpp
   f16v h1 = zero_tile(), h2 = zero_tile();
   float acc = 0.0f;
   float* ck = STORE ? a.ckpt + (first + c) * CK : nullptr;
+  f16v fed = zero_tile();                                  // ROLLOUT: the outputs of the row before
   for (uint32_t j = 0; j < a.L; ++j) {
-    const f16v x = cpmppi::gru_input_tile(nm, s + (size_t)j * 6, q[j], lane);
+    f16v x;
+    if (ROLLOUT && j > a.W) {                              // (wave-uniform)
+      x = fed;
+      if (hf) x[1] = __builtin_fmaf(q[j], nm.in_scale[0], nm.in_shift[0]);
+    } else {
+      x = cpmppi::gru_input_tile(nm, s + (size_t)j * 6, q[j], lane);
+    }
     const f16v y = cpmppi::gru_step(lds, x, h1, h2, lane);
+    if constexpr (ROLLOUT) fed = y;
     cpmppi::f4v d = {0.0f, 0.0f, 0.0f, 0.0f};
     if (j >= a.W && valid) {
       const float* __restrict__ lab = s + (size_t)(j + a.shift) * 6;
@@ -143,6 +157,10 @@ __global__ __launch_bounds__(64) void gru_loss_finalize_kernel(const double* __r
 
 // The forward kernel's mapping.  Per row, last to first: head adjoint (parked by the forward sweep) -> layer 2 -> layer 1, each
 // layer's gates recomputed from its check-pointed input and previous hidden tile (zeros before row 0) right before its adjoint.
+// ROLLOUT: the feedback adjoint as gru_reverse_steps forms it - behind a row j > W the input adjoint dx = W_ih0^T (da_r, da_z, da_nx),
+// whose rows 0..4 (lane-half 0 carries rows 0..3, lane-half 1 row 4) join the head adjoint of row j - 1; the sum is parked in the
+// check-point, where gru_wgrad_kernel reads the head adjoint.  The input adjoints of rows <= W and the Q row are dropped.
+template <bool ROLLOUT>
 __global__ __launch_bounds__(BLOCK, 1) void gru_train_reverse_kernel(const float* __restrict__ image, const float* __restrict__ image_t,
                                                                      const GruTrainArgs a) {
   extern __shared__ float lds[];                           // forward f32 image, then the transposed image
@@ -156,6 +174,7 @@ __global__ __launch_bounds__(BLOCK, 1) void gru_train_reverse_kernel(const float
   const size_t col = first + c;
   f16v dh1 = zero_tile(), dh2 = zero_tile();               // adjoints of the hidden tiles behind row j
   const f16v zero = zero_tile();
+  float dfb[4] = {0.0f, 0.0f, 0.0f, 0.0f};                 // ROLLOUT: adjoint of row j's outputs through the input tile of row j + 1
   for (uint32_t j = a.L; j-- > 0;) {
     const float* ck = a.ckpt + ((size_t)j * a.Bp + col) * CK;
     const float* ckp = ck - (size_t)a.Bp * CK;             // row j - 1 (j = 0: not read)
@@ -164,6 +183,12 @@ __global__ __launch_bounds__(BLOCK, 1) void gru_train_reverse_kernel(const float
     {
       const cpmppi::f4v d = *reinterpret_cast<const cpmppi::f4v*>(ck + CK_DY + 4 * hf);
       gout[0] = d.x; gout[1] = d.y; gout[2] = d.z; gout[3] = d.w;
+      if constexpr (ROLLOUT) {
+        gout[0] += dfb[0];                                 // (lane-half 1: [0] = row 4; [1..3] are not read)
+        if (!hf) { gout[1] += dfb[1]; gout[2] += dfb[2]; gout[3] += dfb[3]; }
+        *reinterpret_cast<cpmppi::f4v*>(a.ckpt + ((size_t)j * a.Bp + col) * CK + CK_DY + 4 * hf) =
+            cpmppi::f4v{gout[0], gout[1], gout[2], gout[3]};
+      }
     }
     f16v dar, daz, danx, danh;
     {
@@ -197,6 +222,15 @@ __global__ __launch_bounds__(BLOCK, 1) void gru_train_reverse_kernel(const float
     dh1 = cpmppi::gru_mm<16>(dh1, ldst + (cpmppi::GT_L1H + 0) * 64, dar, lane);
     dh1 = cpmppi::gru_mm<16>(dh1, ldst + (cpmppi::GT_L1H + 16) * 64, daz, lane);
     dh1 = cpmppi::gru_mm<16>(dh1, ldst + (cpmppi::GT_L1H + 32) * 64, danh, lane);
+    if constexpr (ROLLOUT) {
+      f16v dx = zero;
+      if (j > a.W) {                                       // (wave-uniform) the row's input tile was fed back
+        dx = cpmppi::gru_mm<16>(dx, ldst + (cpmppi::GT_L1X + 0) * 64, dar, lane);
+        dx = cpmppi::gru_mm<16>(dx, ldst + (cpmppi::GT_L1X + 16) * 64, daz, lane);
+        dx = cpmppi::gru_mm<16>(dx, ldst + (cpmppi::GT_L1X + 32) * 64, danx, lane);
+      }
+      dfb[0] = dx[0]; dfb[1] = dx[1]; dfb[2] = dx[2]; dfb[3] = dx[3];
+    }
     __builtin_amdgcn_sched_barrier(0);
   }
 }
@@ -342,17 +376,22 @@ int ensure(cpmppi_handle* h, size_t need, hipStream_t s, const char* who) {
     gradient_sources(tab.data() + 2 * N_IMG);
     CPMPPI_HIP(h, hipMalloc(&st->tables, tab.size() * sizeof(int32_t)));
     CPMPPI_HIP(h, hipMemcpy(st->tables, tab.data(), tab.size() * sizeof(int32_t), hipMemcpyHostToDevice));
-    allow_large_lds(&gru_train_reverse_kernel);
+    allow_large_lds(&gru_train_reverse_kernel<false>);
+    allow_large_lds(&gru_train_reverse_kernel<true>);
   }
   return grow_workspace(h, st->ws, st->ws_floats, need);
 }
 
-// What cpmppi_gru_loss_grad refuses before it launches (cpmppi.h lists it), in `who`'s name.
-int check_loss_args(cpmppi_handle* h, const cpmppi_gru_loss_args* a, const char* who) {
+// What cpmppi_gru_loss_grad refuses before it launches (cpmppi.h lists it), in `who`'s name; `rollout`: and a label that is not the
+// next row, which could not be fed back.
+int check_loss_args(cpmppi_handle* h, const cpmppi_gru_loss_args* a, bool rollout, const char* who) {
   if (const int rc = gru_refusal(h, who, a->B != 0 && a->R != 0 && a->T != 0 && a->post_wash_out != 0,
                                  "B, R, T and post_wash_out must be at least 1",
                                  a->states && a->Q && a->windows && a->windows_host && a->loss_out,
                                  "states, Q, windows, windows_host and loss_out are required")) return rc;
+  if (rollout && a->shift_labels != 1)
+    return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": shift_labels must be 1 (the output of a row is the input of the next), got " +
+                                           std::to_string(a->shift_labels));
   if (misaligned(a->states) || misaligned(a->Q) || misaligned(a->windows) || misaligned(a->windows_host) || misaligned(a->grad_out) ||
       (reinterpret_cast<uintptr_t>(a->loss_out) & 7u) != 0)
     return fail(h, CPMPPI_ERR_ALIGN, std::string(who) + ": misaligned pointer");
@@ -367,8 +406,9 @@ int check_loss_args(cpmppi_handle* h, const cpmppi_gru_loss_args* a, const char*
   return CPMPPI_OK;                                        // (every window fits, so wash_out + post_wash_out <= T: no overflow below)
 }
 
-// The launches of one loss (and gradient into `grad`, or NULL) on `s`; the arguments are checked and the workspace is large enough.
-void launch_loss_grad(cpmppi_handle* h, const cpmppi_gru_loss_args* a, float* grad, hipStream_t s) {
+// The launches of one loss (and gradient into `grad`, or NULL) on `s`, teacher-forced or through the open-loop `rollout`; the
+// arguments are checked and the workspace is large enough.
+void launch_loss_grad(cpmppi_handle* h, const cpmppi_gru_loss_args* a, float* grad, bool rollout, hipStream_t s) {
   GruTrain* st = h->gru_train;
   const uint32_t Bp = round32(a->B), L = a->wash_out + a->post_wash_out, wave_tiles = Bp / 32;
   double* loss_part = reinterpret_cast<double*>(st->ws);
@@ -379,12 +419,13 @@ void launch_loss_grad(cpmppi_handle* h, const cpmppi_gru_loss_args* a, float* gr
                        grad ? ckpt : nullptr, grad ? ckpt + (size_t)L * Bp * CK : nullptr, loss_part};
   const dim3 grid((a->B + GRU_ROLLOUTS_PER_BLOCK - 1) / GRU_ROLLOUTS_PER_BLOCK);
   const size_t lds = (size_t)GRU_IMAGE_FLOATS * sizeof(float);
-  const auto forward = grad ? &gru_train_forward_kernel<true> : &gru_train_forward_kernel<false>;
+  const auto forward = rollout ? (grad ? &gru_train_forward_kernel<true, true> : &gru_train_forward_kernel<false, true>)
+                               : (grad ? &gru_train_forward_kernel<true, false> : &gru_train_forward_kernel<false, false>);
   hipLaunchKernelGGL(forward, grid, dim3(BLOCK), lds, s, h->gru_norm, (const float*)h->gru_image, k);
   hipLaunchKernelGGL(gru_loss_finalize_kernel, dim3(1), dim3(64), 0, s, (const double*)loss_part, (a->B + 31u) / 32u, count, a->loss_out);
   if (!grad) return;
-  hipLaunchKernelGGL(gru_train_reverse_kernel, grid, dim3(BLOCK), REVERSE_LDS, s, (const float*)h->gru_image,
-                     (const float*)h->gru_t_image, k);
+  hipLaunchKernelGGL(rollout ? &gru_train_reverse_kernel<true> : &gru_train_reverse_kernel<false>, grid, dim3(BLOCK), REVERSE_LDS, s,
+                     (const float*)h->gru_image, (const float*)h->gru_t_image, k);
   const uint64_t tiles = (uint64_t)L * wave_tiles;
   uint64_t per_slice = (tiles + WG_MAX_SLICES - 1) / WG_MAX_SLICES;
   if (per_slice < WG_MIN_TILES) per_slice = WG_MIN_TILES;
@@ -394,13 +435,21 @@ void launch_loss_grad(cpmppi_handle* h, const cpmppi_gru_loss_args* a, float* gr
                      slices, (const int32_t*)(st->tables + 2 * N_IMG), grad);
 }
 
-int loss_grad_impl(cpmppi_handle* h, const cpmppi_gru_loss_args* a, float* grad, hipStream_t s, const char* who) {
-  if (const int rc = check_loss_args(h, a, who)) return rc;
+int loss_grad_impl(cpmppi_handle* h, const cpmppi_gru_loss_args* a, float* grad, bool rollout, hipStream_t s, const char* who) {
+  if (const int rc = check_loss_args(h, a, rollout, who)) return rc;
   const uint64_t tiles = (uint64_t)(a->wash_out + a->post_wash_out) * (round32(a->B) / 32);
   if (tiles > 0xffffffffull) return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": too many (row, window) tiles");
   if (const int rc = ensure(h, need_floats(a->B, a->wash_out + a->post_wash_out, grad != nullptr), s, who)) return rc;
-  launch_loss_grad(h, a, grad, s);
+  launch_loss_grad(h, a, grad, rollout, s);
   return launched(h);
+}
+
+// cpmppi_gru_loss_grad and cpmppi_gru_rollout_loss_grad, in `who`'s name.
+int loss_grad_entry(cpmppi_handle* h, const cpmppi_gru_loss_args* a, bool rollout, void* stream, const char* who) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": null argument block");
+  CPMPPI_ON_DEVICE(h);
+  return loss_grad_impl(h, a, a->grad_out, rollout, (hipStream_t)stream, who);
 }
 
 void launch_adam_repack(cpmppi_handle* h, float lr, float beta1, float beta2, float eps, int update, hipStream_t s) {
@@ -409,6 +458,20 @@ void launch_adam_repack(cpmppi_handle* h, float lr, float beta1, float beta2, fl
   hipLaunchKernelGGL(gru_adam_repack_kernel, dim3(1), dim3(REPACK_BLOCK), 0, s, p, p + CPMPPI_GRU_PARAMS, p + 2 * CPMPPI_GRU_PARAMS,
                      (const float*)(p + 3 * CPMPPI_GRU_PARAMS), st->step, lr, beta1, beta2, eps, update, (const int32_t*)st->tables,
                      h->gru_image, h->gru_t_image);
+}
+
+// cpmppi_gru_train_step and cpmppi_gru_rollout_train_step, in `who`'s name.
+int train_step_entry(cpmppi_handle* h, const cpmppi_gru_loss_args* a, bool rollout, float lr, float beta1, float beta2, float eps,
+                     void* stream, const char* who) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": null argument block");
+  if (!h->gru_train || !h->gru_train->begun)
+    return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": call cpmppi_gru_train_begin first");
+  CPMPPI_ON_DEVICE(h);
+  if (const int rc = loss_grad_impl(h, a, h->gru_train->master + 3 * (size_t)CPMPPI_GRU_PARAMS, rollout, (hipStream_t)stream, who))
+    return rc;
+  launch_adam_repack(h, lr, beta1, beta2, eps, 1, (hipStream_t)stream);
+  return launched(h);
 }
 
 }  // namespace
@@ -434,10 +497,11 @@ int cpmppi_gru_train_reserve(cpmppi_handle* h, uint32_t B, uint32_t rows) try {
 } catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }   // (no C++ exception leaves the C ABI)
 
 int cpmppi_gru_loss_grad(cpmppi_handle* h, const cpmppi_gru_loss_args* a, void* stream) try {
-  if (!h) return CPMPPI_ERR_BAD_ARG;
-  if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_loss_grad: null argument block");
-  CPMPPI_ON_DEVICE(h);
-  return loss_grad_impl(h, a, a->grad_out, (hipStream_t)stream, "cpmppi_gru_loss_grad");
+  return loss_grad_entry(h, a, false, stream, "cpmppi_gru_loss_grad");
+} catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }
+
+int cpmppi_gru_rollout_loss_grad(cpmppi_handle* h, const cpmppi_gru_loss_args* a, void* stream) try {
+  return loss_grad_entry(h, a, true, stream, "cpmppi_gru_rollout_loss_grad");
 } catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }
 
 int cpmppi_gru_train_begin(cpmppi_handle* h) try {
@@ -463,15 +527,12 @@ int cpmppi_gru_train_begin(cpmppi_handle* h) try {
 
 int cpmppi_gru_train_step(cpmppi_handle* h, const cpmppi_gru_loss_args* a, float lr, float beta1, float beta2, float eps,
                           void* stream) try {
-  if (!h) return CPMPPI_ERR_BAD_ARG;
-  if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_train_step: null argument block");
-  if (!h->gru_train || !h->gru_train->begun)
-    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_train_step: call cpmppi_gru_train_begin first");
-  CPMPPI_ON_DEVICE(h);
-  if (const int rc = loss_grad_impl(h, a, h->gru_train->master + 3 * (size_t)CPMPPI_GRU_PARAMS, (hipStream_t)stream,
-                                    "cpmppi_gru_train_step")) return rc;
-  launch_adam_repack(h, lr, beta1, beta2, eps, 1, (hipStream_t)stream);
-  return launched(h);
+  return train_step_entry(h, a, false, lr, beta1, beta2, eps, stream, "cpmppi_gru_train_step");
+} catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }
+
+int cpmppi_gru_rollout_train_step(cpmppi_handle* h, const cpmppi_gru_loss_args* a, float lr, float beta1, float beta2, float eps,
+                                  void* stream) try {
+  return train_step_entry(h, a, true, lr, beta1, beta2, eps, stream, "cpmppi_gru_rollout_train_step");
 } catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }
 
 int cpmppi_gru_train_get(cpmppi_handle* h, float* params_host) {

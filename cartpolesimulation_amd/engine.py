@@ -668,15 +668,19 @@ class MPPIEngine:
         return self._build_brunton(*args, **kwargs)
 
     # ------------------------------------------------------------------ training the GRU predictor on recordings
-    def _gru_loss_args(self, states, Q, windows, wash_out, post_wash_out, shift_labels, loss_out=None, grad_out=None, grad=True):
-        """The argument block of cpmppi_gru_loss_grad / cpmppi_gru_train_step, checked: -> (block, what it points into, loss_out,
-        grad_out).  ``windows`` [B,2] integers (r, t0) on the HOST: uploaded here, and handed to the library as its host copy."""
+    def _gru_loss_args(self, states, Q, windows, wash_out, post_wash_out, shift_labels, loss_out=None, grad_out=None, grad=True,
+                       rollout=False):
+        """The argument block of cpmppi_gru_loss_grad / cpmppi_gru_train_step and their ``rollout`` siblings, checked: -> (block,
+        what it points into, loss_out, grad_out).  ``windows`` [B,2] integers (r, t0) on the HOST: uploaded here, and handed to the
+        library as its host copy."""
         if not self.has_gru:
             raise ValueError("no model set: call set_gru first")
         states, Q, R, T = self._recordings(states, Q)
         W, P, shift = int(wash_out), int(post_wash_out), int(shift_labels)
         if W < 0 or P < 1 or shift < 0:
             raise ValueError(f"wash_out >= 0, post_wash_out >= 1 and shift_labels >= 0, got {W}, {P}, {shift}")
+        if rollout and shift != 1:
+            raise ValueError(f"rollout: shift_labels must be 1 (the output of a row is the input of the next), got {shift}")
         w = np.asarray(windows.cpu() if torch.is_tensor(windows) else windows)
         if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] == 0 or not np.issubdtype(w.dtype, np.integer):
             raise ValueError(f"windows must be integers [B,2] = (recording, first row) with B >= 1, got {w.dtype} {w.shape}")
@@ -704,15 +708,18 @@ class MPPIEngine:
         self._check(self.lib.cpmppi_gru_train_reserve(self._h, int(B), int(rows)))
 
     def _build_gru_loss_grad(self, states, Q, windows, wash_out, post_wash_out, shift_labels=1, grad=True, *, loss_out=None,
-                             grad_out=None):
+                             grad_out=None, rollout=False):
         """cpmppi_gru_loss_grad: the teacher-forced loss of the model of ``set_gru`` over ``windows`` [B,2] = (recording, first row)
         of ``states`` [R,T,6], ``Q`` [R,T] (include/cpmppi.h states it): the memory starts at zero, ``wash_out`` rows build it,
-        ``post_wash_out`` rows are scored against the normalised features ``shift_labels`` rows on.
+        ``post_wash_out`` rows are scored against the normalised features ``shift_labels`` rows on.  ``rollout``:
+        cpmppi_gru_rollout_loss_grad - behind the first scored row the model's own normalised outputs are fed back with the recorded
+        controls, as ``gru_predict`` runs it (``shift_labels`` must be 1), and the gradient runs through the feedback.
         -> (loss [1] float64 on the device, gradient [10341] in the flat order of ``GRU_KEYS`` - None with ``grad=False``, the
         loss alone, bit for bit the loss of the gradient call)."""
         a, keep, loss_out, grad_out = self._gru_loss_args(states, Q, windows, wash_out, post_wash_out, shift_labels, loss_out,
-                                                          grad_out, grad)
-        return PreparedCall(self, self.lib.cpmppi_gru_loss_grad, a, keep, (loss_out, grad_out), ())
+                                                          grad_out, grad, rollout)
+        fn = self.lib.cpmppi_gru_rollout_loss_grad if rollout else self.lib.cpmppi_gru_loss_grad
+        return PreparedCall(self, fn, a, keep, (loss_out, grad_out), ())
 
     gru_loss_grad = _run_once(_build_gru_loss_grad)
 
@@ -729,13 +736,14 @@ class MPPIEngine:
         self._check(self.lib.cpmppi_gru_train_begin(self._h))
 
     def gru_train_step(self, states, Q, windows, wash_out, post_wash_out, shift_labels=1, *, lr, beta1=0.9, beta2=0.999,
-                       eps=1e-8, loss_out=None):
-        """cpmppi_gru_train_step: the loss and gradient of ``gru_loss_grad`` over this batch of ``windows``, one Adam update of the
-        master copy and the rebuild of the exact-f32 weight images, all on the device.  -> the batch's loss BEFORE the update,
-        [1] float64 on the device."""
-        a, keep, loss_out, _ = self._gru_loss_args(states, Q, windows, wash_out, post_wash_out, shift_labels, loss_out, None, False)
-        self._check(self.lib.cpmppi_gru_train_step(self._h, C.byref(a), float(lr), float(beta1), float(beta2), float(eps),
-                                                   self._stream()))
+                       eps=1e-8, loss_out=None, rollout=False):
+        """cpmppi_gru_train_step (``rollout``: cpmppi_gru_rollout_train_step): the loss and gradient of ``gru_loss_grad`` over this
+        batch of ``windows``, one Adam update of the master copy and the rebuild of the exact-f32 weight images, all on the device.
+        Steps of both kinds may alternate.  -> the batch's loss BEFORE the update, [1] float64 on the device."""
+        a, keep, loss_out, _ = self._gru_loss_args(states, Q, windows, wash_out, post_wash_out, shift_labels, loss_out, None, False,
+                                                   rollout)
+        fn = self.lib.cpmppi_gru_rollout_train_step if rollout else self.lib.cpmppi_gru_train_step
+        self._check(fn(self._h, C.byref(a), float(lr), float(beta1), float(beta2), float(eps), self._stream()))
         self._train_keep = keep                       # (the launches read the batch after this call returns)
         return loss_out
 

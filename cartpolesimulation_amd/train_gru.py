@@ -16,12 +16,21 @@ loss, learning-rate schedule - are therefore THIS PACKAGE'S OWN, chosen to match
 The loss, its gradient (back-propagation through time), Adam and the rebuild of the kernels' weight images run on the device
 (``MPPIEngine.gru_train_step``: cpmppi_gru_train_step); the host draws batches and keeps the schedule.
 
+Two training modes.  Teacher forced (the default): every row of a window is fed as recorded, the one-step map is fitted.  Open-loop
+rollout (``rollout=True``, ``--rollout``: cpmppi_gru_rollout_train_step): the wash-out and the first scored row are fed as recorded,
+every later row takes the model's own normalised outputs of the row before with the recorded control - the free run that
+``gru_predict``, the Brunton test and the controllers put a trained model through -, and the gradient runs through that feedback;
+``SHIFT_LABELS`` must be 1.  ``post_wash_out`` may then be a sequence, one horizon per epoch, the last entry repeating (the usual
+horizon curriculum, ``--post-wash-out-schedule 5,10,20``); validation always scores the last entry.  The expected use is to
+fine-tune a teacher-forced model: ``--init FOLDER`` starts from a model folder and keeps its normalisation.
+
 Built for GRU-6IN-32H1-32H2-5OUT, the dynamics model (Q and five state features in, the five features of the next row out).  Not
-built, and refused by name where a user can ask: other network sizes or cell types, Dense nets, training through the autoregressive
-rollout, a non-zero start memory, the regularisation / pruning / quantisation / series-modification / filter keys of
-config_training.yml, several models per launch, env groups and multi-GPU.
+built, and refused by name where a user can ask: other network sizes or cell types, Dense nets, gradient-norm clipping, scheduled
+sampling (fed-back and recorded rows mixed at random), a non-zero start memory, the regularisation / pruning / quantisation /
+series-modification / filter keys of config_training.yml, several models per launch, env groups and multi-GPU.
 
   python -m cartpolesimulation_amd.train_gru --recordings DIR --out FOLDER --net GRU-32H1-32H2 --dynamics-model [--config-root CHECKOUT]
+                                             [--rollout] [--post-wash-out-schedule 5,10,20] [--init FOLDER]
 """
 import os
 
@@ -84,6 +93,25 @@ def initial_weights(seed):
     return {key: rng.uniform(-k, k, size=shp).astype(f32) for key, shp in zip(GRU_KEYS, GRU_SHAPES)}
 
 
+def horizon_schedule(post_wash_out):
+    """``post_wash_out`` as train_gru takes it - one P, a sequence with one P per epoch, or the command line's "5,10,20" - -> the
+    tuple of P per epoch; the last entry repeats (``horizon_of_epoch``)."""
+    if isinstance(post_wash_out, str):
+        parts = [x.strip() for x in post_wash_out.split(",")]
+        if not all(x.isdigit() for x in parts):
+            raise ValueError(f"post_wash_out schedule {post_wash_out!r}: comma-separated whole numbers, e.g. 5,10,20")
+        post_wash_out = [int(x) for x in parts]
+    sched = tuple(int(p) for p in np.atleast_1d(np.asarray(post_wash_out)).reshape(-1))
+    if not sched or min(sched) < 1:
+        raise ValueError(f"post_wash_out must be at least 1 in every epoch, got {sched}")
+    return sched
+
+
+def horizon_of_epoch(schedule, epoch):
+    """The P of ``epoch`` (from 0): the schedule's entry, its last one beyond the end."""
+    return schedule[min(int(epoch), len(schedule) - 1)]
+
+
 def _check_model(model):
     for key, shp in zip(GRU_KEYS, GRU_SHAPES):
         if key not in model or np.shape(model[key]) != shp:
@@ -92,14 +120,21 @@ def _check_model(model):
 
 def train_gru(engine, states, Q, lengths=None, *, epochs, batch_size, lr, seed, wash_out, post_wash_out, shift_labels=1,
               validation=None, init=None, reduce_lr_on_plateau=True, patience=2, decrease_factor=0.5, minimal_lr=1e-7,
-              min_delta=1e-6, beta1=0.9, beta2=0.999, eps=1e-7, validation_batch=4096, log=None):
+              min_delta=1e-6, beta1=0.9, beta2=0.999, eps=1e-7, validation_batch=4096, log=None, rollout=False):
     """Train GRU-6IN-32H1-32H2-5OUT on ``states`` [R,T,6], ``Q`` [R,T] (``lengths`` [R]: the recordings' true lengths, None = T)
     with ``engine`` (an ``MPPIEngine``; its model is replaced).  ``init``: the model dict to start from - weights in the order of
     ``GRU_KEYS``, and the normalisation if it carries one; None: ``initial_weights(seed)``.  Without a normalisation in ``init`` it
     is ``normalization_from_recordings`` of the training data.  ``validation`` = (states, Q, lengths or None) is scored after every
     epoch through the loss-only call.  ``eps`` defaults to Keras's Adam epsilon.  The module docstring states batches and schedule.
-    -> (the model dict ``MPPIEngine.set_gru`` takes, which the engine holds on return; history = dict(loss, val_loss, lr: one
-    entry per epoch, batch_loss: every step's loss in order))."""
+    ``rollout``: every training step and the validation loss run through the open-loop rollout (``shift_labels`` must be 1).
+    ``post_wash_out``: one P, or a sequence with one P per epoch whose last entry repeats; the windows are remade when P changes, the
+    workspace is reserved once for the largest P, validation always scores the last entry.
+    -> (the model dict ``MPPIEngine.set_gru`` takes, which the engine holds on return; history = dict(loss, val_loss, lr,
+    post_wash_out: one entry per epoch, batch_loss: every step's loss in order))."""
+    rollout = bool(rollout)
+    if rollout and int(shift_labels) != 1:
+        raise ValueError(f"rollout: shift_labels must be 1 (the output of a row is the input of the next), got {shift_labels}")
+    schedule = horizon_schedule(post_wash_out)
     import torch
     states, Q = np.ascontiguousarray(states, f32), np.ascontiguousarray(Q, f32)
     if states.ndim != 3 or states.shape[2] != 6 or Q.shape != states.shape[:2]:
@@ -111,9 +146,10 @@ def train_gru(engine, states, Q, lengths=None, *, epochs, batch_size, lr, seed, 
     epochs, batch_size = int(epochs), int(batch_size)
     if epochs < 1 or batch_size < 1:
         raise ValueError("epochs and batch_size must be at least 1")
-    windows = make_windows(lengths, wash_out, post_wash_out, shift_labels)
-    if len(windows) == 0:
-        raise ValueError(f"no recording holds a window of {wash_out} + {post_wash_out} rows with its labels {shift_labels} rows on")
+    by_horizon = {p: make_windows(lengths, wash_out, p, shift_labels) for p in sorted(set(schedule[:epochs]))}
+    for p, w in by_horizon.items():
+        if len(w) == 0:
+            raise ValueError(f"no recording holds a window of {wash_out} + {p} rows with its labels {shift_labels} rows on")
     model = dict(init) if init is not None else initial_weights(seed)
     _check_model(model)
     norm = {k: np.asarray(model[k], f32) for k in NORM_KEYS if model.get(k) is not None}
@@ -127,16 +163,19 @@ def train_gru(engine, states, Q, lengths=None, *, epochs, batch_size, lr, seed, 
     if validation is not None:
         vs, vq = np.ascontiguousarray(validation[0], f32), np.ascontiguousarray(validation[1], f32)
         vl = validation[2] if len(validation) > 2 and validation[2] is not None else np.full(vq.shape[0], vq.shape[1])
-        vw = make_windows(vl, wash_out, post_wash_out, shift_labels)
+        vw = make_windows(vl, wash_out, schedule[-1], shift_labels)
         if len(vw) == 0:
             raise ValueError("the validation recordings hold no window")
         val = engine.tensor(vs), engine.tensor(vq), vw
+    if len(schedule) > 1:
+        widest = max(batch_size, min(int(validation_batch), len(val[2])) if val is not None else 0)
+        engine.gru_train_reserve(widest, int(wash_out) + max(schedule))
 
     def validate():
         total, losses, sizes = 0.0, [], []
         for i in range(0, len(val[2]), int(validation_batch)):
             w = val[2][i:i + int(validation_batch)]
-            loss, _ = engine.gru_loss_grad(val[0], val[1], w, wash_out, post_wash_out, shift_labels, grad=False)
+            loss, _ = engine.gru_loss_grad(val[0], val[1], w, wash_out, schedule[-1], shift_labels, grad=False, rollout=rollout)
             losses.append(loss)
             sizes.append(len(w))
         for loss, n in zip(torch.cat(losses).cpu().numpy(), sizes):
@@ -145,19 +184,22 @@ def train_gru(engine, states, Q, lengths=None, *, epochs, batch_size, lr, seed, 
 
     rng = np.random.default_rng(seed)
     rate, best, wait = float(lr), np.inf, 0
-    history = dict(loss=[], val_loss=[], lr=[], batch_loss=[])
+    history = dict(loss=[], val_loss=[], lr=[], batch_loss=[], post_wash_out=[])
     for epoch in range(epochs):
+        horizon = horizon_of_epoch(schedule, epoch)
+        windows = by_horizon[horizon]
         order = rng.permutation(len(windows))
         steps = -(-len(order) // batch_size)
         losses = torch.empty(steps, dtype=torch.float64, device=engine.device)
         for i in range(steps):
             batch = windows[order[i * batch_size:(i + 1) * batch_size]]
-            engine.gru_train_step(s_dev, q_dev, batch, wash_out, post_wash_out, shift_labels, lr=rate, beta1=beta1, beta2=beta2,
-                                  eps=eps, loss_out=losses[i:i + 1])
+            engine.gru_train_step(s_dev, q_dev, batch, wash_out, horizon, shift_labels, lr=rate, beta1=beta1, beta2=beta2,
+                                  eps=eps, loss_out=losses[i:i + 1], rollout=rollout)
         batch_loss = losses.cpu().numpy()
         history["batch_loss"] += [float(x) for x in batch_loss]
         history["loss"].append(float(batch_loss.mean()))
         history["lr"].append(rate)
+        history["post_wash_out"].append(horizon)
         monitored = history["loss"][-1]
         if val is not None:
             history["val_loss"].append(validate())
@@ -253,6 +295,36 @@ def training_settings(config, net=None, dynamics_model=False, **overrides):
     return out, bool(t.get("NORMALIZE", True))
 
 
+def run_settings(settings, normalize, rollout=False, schedule=None, init_folder=None):
+    """What the command line adds to ``training_settings``: -> (the keyword arguments of ``train_gru`` with ``rollout`` and, from
+    ``schedule`` ("5,10,20"), ``post_wash_out`` as a sequence; the model to start from - the one of ``init_folder`` with its
+    normalisation, else ``initial_weights(seed)``, with the identity normalisation unless ``normalize``; the entries of the
+    net-info file)."""
+    settings = dict(settings, rollout=bool(rollout))
+    if schedule is not None:
+        settings["post_wash_out"] = horizon_schedule(schedule)
+    sched = horizon_schedule(settings["post_wash_out"])
+    if rollout and int(settings["shift_labels"]) != 1:
+        raise ValueError(f"--rollout: shift_labels must be 1 (the output of a row is the input of the next), got "
+                         f"{settings['shift_labels']}")
+    if init_folder is not None:
+        from .model_folder import load_gru_model
+        init = dict(load_gru_model(os.fspath(init_folder)))
+        _check_model(init)
+        if any(init.get(k) is None for k in NORM_KEYS):       # (a folder with NORMALIZE False: the identity, not the recordings')
+            init.update(in_scale=np.ones(6, f32), in_shift=np.zeros(6, f32), out_scale=np.ones(5, f32), out_shift=np.zeros(5, f32))
+    else:
+        init = initial_weights(settings["seed"])
+        if not normalize:
+            init.update(in_scale=np.ones(6, f32), in_shift=np.zeros(6, f32), out_scale=np.ones(5, f32), out_shift=np.zeros(5, f32))
+    info = {"WASH OUT LENGTH": settings["wash_out"], "POST WASH OUT LENGTH": sched[-1],
+            "POST WASH OUT SCHEDULE": ", ".join(str(p) for p in sched), "SHIFT LABELS": settings["shift_labels"],
+            "TRAINING MODE": "open-loop rollout" if rollout else "teacher forced"}
+    if init_folder is not None:
+        info["PARENT NET"] = os.path.abspath(os.fspath(init_folder))
+    return settings, init, info
+
+
 def load_recordings_folder(folder):
     """Every recording CSV of ``folder`` (``brunton.load_recording``) -> (states [R,T,6], Q [R,T] padded with zeros to the longest,
     lengths [R], the file names)."""
@@ -270,7 +342,8 @@ def load_recordings_folder(folder):
 
 
 def main(argv=None):
-    """python -m cartpolesimulation_amd.train_gru --recordings DIR --out FOLDER --net GRU-32H1-32H2 --dynamics-model [--config-root CHECKOUT]"""
+    """python -m cartpolesimulation_amd.train_gru --recordings DIR --out FOLDER --net GRU-32H1-32H2 --dynamics-model [--config-root CHECKOUT]
+    [--rollout] [--post-wash-out-schedule 5,10,20] [--init FOLDER]"""
     import argparse
     import yaml
     ap = argparse.ArgumentParser(description="Train the GRU predictor on recordings, on MI355X "
@@ -288,6 +361,12 @@ def main(argv=None):
     for flag, typ in (("--epochs", int), ("--batch-size", int), ("--seed", int), ("--lr", float), ("--wash-out", int),
                       ("--post-wash-out", int), ("--shift-labels", int)):
         ap.add_argument(flag, type=typ, default=None, help="instead of the file's value")
+    ap.add_argument("--rollout", action="store_true",
+                    help="train through the open-loop rollout: behind the first scored row the model's own outputs are fed back")
+    ap.add_argument("--post-wash-out-schedule", default=None, metavar="P,P,...",
+                    help="one POST_WASH_OUT_LEN per epoch, the last entry repeating (e.g. 5,10,20), instead of --post-wash-out")
+    ap.add_argument("--init", default=None, metavar="FOLDER",
+                    help="fine-tune the model of this folder, with its normalisation, instead of fresh weights")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
     path = args.config_training or (os.path.join(args.config_root, "SI_Toolkit_ASF", "config_training.yml") if args.config_root else None)
@@ -299,6 +378,8 @@ def main(argv=None):
         settings, normalize = training_settings(config, net=args.net, dynamics_model=args.dynamics_model, epochs=args.epochs,
                                                 batch_size=args.batch_size, seed=args.seed, lr=args.lr, wash_out=args.wash_out,
                                                 post_wash_out=args.post_wash_out, shift_labels=args.shift_labels)
+        settings, init, info = run_settings(settings, normalize, rollout=args.rollout, schedule=args.post_wash_out_schedule,
+                                            init_folder=args.init)
     except ValueError as e:
         raise SystemExit(f"train_gru: {e}")
     states, Q, lengths, names = load_recordings_folder(args.recordings)
@@ -306,15 +387,9 @@ def main(argv=None):
     from .configs import MPPIConfig
     from .engine import MPPIEngine
     engine = MPPIEngine(1, MPPIConfig(num_rollouts=1, mpc_horizon=2), device=args.device)
-    init = initial_weights(settings["seed"])
-    if not normalize:
-        init.update(in_scale=np.ones(6, f32), in_shift=np.zeros(6, f32), out_scale=np.ones(5, f32), out_shift=np.zeros(5, f32))
     model, history = train_gru(engine, states, Q, lengths, validation=validation, init=init, log=print, **settings)
     engine.close()
-    folder = write_model_folder(args.out, model, info={"WASH OUT LENGTH": settings["wash_out"],
-                                                       "POST WASH OUT LENGTH": settings["post_wash_out"],
-                                                       "SHIFT LABELS": settings["shift_labels"],
-                                                       "TRAINING_FILES": os.path.abspath(args.recordings)})
+    folder = write_model_folder(args.out, model, info={**info, "TRAINING_FILES": os.path.abspath(args.recordings)})
     print(f"trained on {len(names)} recordings, final loss {history['loss'][-1]:.6e}; model folder: {folder}")
     return model, history
 

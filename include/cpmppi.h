@@ -62,7 +62,8 @@ extern "C" {
                                       cpmppi_score_runs / cpmppi_score_args, cpmppi_set_tuning_rows (new entry points, likewise);
                                       cpmppi_rpgd_step_rows (a new entry point, likewise);
                                       cpmppi_gru_loss_grad / cpmppi_gru_loss_args, cpmppi_gru_train_reserve / _begin / _step / _get
-                                      (new entry points, likewise). */
+                                      (new entry points, likewise);
+                                      cpmppi_gru_rollout_loss_grad / cpmppi_gru_rollout_train_step (new entry points, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -514,7 +515,22 @@ int cpmppi_replay_step(cpmppi_handle* h, const cpmppi_replay_args* args, void* s
  * of the fused rollout kernels keeps the model of the last cpmppi_set_gru: a trained model reaches them through
  * cpmppi_gru_train_get and cpmppi_set_gru.  No host synchronisation: capturable after a reserving call.
  * CPMPPI_ERR_BAD_ARG ("cpmppi_gru_train_step: ...") without cpmppi_gru_train_begin, and what cpmppi_gru_loss_grad refuses.
- * cpmppi_gru_train_get: the master copy -> params_host[CPMPPI_GRU_PARAMS], synchronously. */
+ * cpmppi_gru_train_get: the master copy -> params_host[CPMPPI_GRU_PARAMS], synchronously.
+ *
+ * cpmppi_gru_rollout_loss_grad: the same loss THROUGH THE OPEN-LOOP ROLLOUT, which is how every consumer of a trained model runs it
+ * (cpmppi_gru_predict, cpmppi_brunton, the control steps).  The same argument block, windows (r, t0) of W + P rows, zero start
+ * memory and recording layout.  Rows j <= W are fed as recorded: the wash-out is teacher-forced and row W, the first scored row, is
+ * the recorded start row, as in the Brunton test.  Rows j > W take input rows 0..4 (angleD .. positionD) from the head's NORMALISED
+ * OUTPUT of row j - 1, unchanged - the rule of cpmppi_gru_predict, not a de-normalise / re-normalise round trip - and row 5 from the
+ * recorded Q[t0 + j] normalised with in_scale[0], in_shift[0].  The loss is the teacher-forced one: the mean over B x P x 5 of
+ * (y_j - (features of row t0 + j + 1 - out_shift) / out_scale)^2 for j >= W.  shift_labels must be 1: the output of row j is the
+ * input of row j + 1.  grad_out: d loss / d all CPMPPI_GRU_PARAMS parameters through the feedback - the head adjoint of row j,
+ * W <= j < W + P - 1, is its own 2 (y - label) / (B P 5) plus rows 0..4 of the input adjoint of row j + 1; the input adjoints of
+ * rows <= W and of the Q row are dropped.  With P = 1 nothing is fed back and the loss is cpmppi_gru_loss_grad's bit for bit.
+ * The same launches, workspace (cpmppi_gru_train_reserve, unchanged in size), determinism and capture rule as cpmppi_gru_loss_grad.
+ * Refused ("cpmppi_gru_rollout_loss_grad: ..."), nothing launched: what cpmppi_gru_loss_grad refuses, and shift_labels != 1.
+ * cpmppi_gru_rollout_train_step: cpmppi_gru_train_step with that loss and gradient ("cpmppi_gru_rollout_train_step: ...").  Steps of
+ * both kinds may alternate on one master copy and one Adam state; cpmppi_gru_train_begin / _get serve both. */
 #define CPMPPI_GRU_PARAMS 10341u
 typedef struct {
   uint32_t B;                           /* windows */
@@ -534,6 +550,9 @@ int cpmppi_gru_train_begin(cpmppi_handle* h);
 int cpmppi_gru_train_step(cpmppi_handle* h, const cpmppi_gru_loss_args* args, float lr, float beta1, float beta2, float eps,
                           void* stream);
 int cpmppi_gru_train_get(cpmppi_handle* h, float* params_host);
+int cpmppi_gru_rollout_loss_grad(cpmppi_handle* h, const cpmppi_gru_loss_args* args, void* stream);
+int cpmppi_gru_rollout_train_step(cpmppi_handle* h, const cpmppi_gru_loss_args* args, float lr, float beta1, float beta2, float eps,
+                                  void* stream);
 
 /* Rollout + cost only (no update): per-rollout trajectory cost S[E,N] of GIVEN input sequences inputs[E,N,H] under the
  * handle's plugin cost — cost_function.get_trajectory_cost(predictor.predict_core(s, Q), Q) fused; the building block of

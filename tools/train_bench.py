@@ -4,6 +4,11 @@ loss, reverse sweep, weight-gradient contraction, Adam and the image rebuild - s
 torch.optim.Adam in float32 on the same device and shape.
 
   python tools/train_bench.py [--batches 64,4096] [--wash-out 10] [--post-wash-out 50] [--steps 20] [--rounds 5] [--out FILE.json]
+  python tools/train_bench.py --rollout ...     the step through the open-loop rollout (cpmppi_gru_rollout_train_step) against the
+                                                teacher-forced step, alternating round by round in one process: the ratio of the
+                                                medians against the bar 352 / 304 (the reverse sweeps' MFMAs per row) plus the
+                                                teacher-forced rounds' own min - max scatter; for information a float32 torch loop
+                                                doing the same rollout training (the cell called row by row)
 
 Both forms run in ONE process and alternate round by round; a round is ``--steps`` back-to-back steps between two device events
 (device time per step) inside a host clock that ends in a synchronise (wall time per step: what a training loop pays, the
@@ -74,6 +79,50 @@ def stats(x):
     return dict(median=float(np.median(x)), min=float(np.min(x)), max=float(np.max(x)))
 
 
+def rollout_record(args, eng, s_dev, q_dev, w, W, P, lr, net, opt, x, lab):
+    """One shape of --rollout: the rollout step and the teacher-forced step of the library alternating, then the torch loop."""
+    dev = eng.device
+    loss_out = torch.empty(1, dtype=torch.float64, device=dev)
+    forced = lambda: eng.gru_train_step(s_dev, q_dev, w, W, P, lr=lr, loss_out=loss_out)                  # noqa: E731
+    rolled = lambda: eng.gru_train_step(s_dev, q_dev, w, W, P, lr=lr, loss_out=loss_out, rollout=True)    # noqa: E731
+
+    def theirs():
+        opt.zero_grad(set_to_none=True)
+        out, h = net.gru(x[:, :W + 1])
+        y = net.head(out)[:, W:]
+        ys = [y]
+        for j in range(W + 1, W + P):
+            out, h = net.gru(torch.cat([x[:, j:j + 1, :1], y], dim=2), h)
+            y = net.head(out)
+            ys.append(y)
+        loss = ((torch.cat(ys, dim=1) - lab) ** 2).mean()
+        loss.backward()
+        opt.step()
+        return loss
+
+    first = (float(rolled().cpu()[0]), float(forced().cpu()[0]))
+    timed(rolled, args.steps, dev)
+    timed(forced, args.steps, dev)
+    t_rolled, t_forced = [], []
+    for _ in range(args.rounds):
+        t_rolled.append(timed(rolled, args.steps, dev))
+        t_forced.append(timed(forced, args.steps, dev))
+    timed(theirs, 2, dev)
+    t_theirs = [timed(theirs, args.steps, dev) for _ in range(2)]
+    rec = dict(B=len(w), wash_out=W, post_wash_out=P, steps_per_round=args.steps, rounds=args.rounds, first_loss_rollout=first[0],
+               first_loss_teacher_forced=first[1],
+               rollout_device_ms=stats([t[0] for t in t_rolled]), rollout_wall_ms=stats([t[1] for t in t_rolled]),
+               teacher_forced_device_ms=stats([t[0] for t in t_forced]), teacher_forced_wall_ms=stats([t[1] for t in t_forced]),
+               torch_rollout_wall_ms=stats([t[1] for t in t_theirs]))
+    tf = rec["teacher_forced_device_ms"]
+    rec["rollout_over_teacher_forced_device"] = rec["rollout_device_ms"]["median"] / tf["median"]
+    rec["bar"] = 352.0 / 304.0 + (tf["max"] - tf["min"]) / tf["median"]
+    rec["within_bar"] = bool(rec["rollout_over_teacher_forced_device"] <= rec["bar"])
+    rec["torch_over_library_wall"] = rec["torch_rollout_wall_ms"]["median"] / rec["rollout_wall_ms"]["median"]
+    print(json.dumps(rec), flush=True)
+    return rec
+
+
 def main(argv=None):
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
     ap.add_argument("--batches", default="64,4096")
@@ -81,6 +130,7 @@ def main(argv=None):
     ap.add_argument("--post-wash-out", type=int, default=50)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--rounds", type=int, default=5)
+    ap.add_argument("--rollout", action="store_true", help="time the rollout step against the teacher-forced step")
     ap.add_argument("--native-rnn", action="store_true", help="torch.backends.cudnn.enabled = False: torch's own cell kernels")
     ap.add_argument("--out", default=None)
     args = ap.parse_args(argv)
@@ -121,6 +171,9 @@ def main(argv=None):
             opt.step()
             return loss
 
+        if args.rollout:
+            results.append(rollout_record(args, eng, s_dev, q_dev, w, W, P, lr, net, opt, x, lab))
+            continue
         first = (float(ours().cpu()[0]), float(theirs().detach().cpu()))                              # the same loss, to start with
         timed(ours, args.steps, dev)
         timed(theirs, args.steps, dev)
