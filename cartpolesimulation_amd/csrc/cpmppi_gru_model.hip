@@ -204,6 +204,7 @@ int cpmppi_set_gru(cpmppi_handle* h, const cpmppi_gru_model* m) try {
   if (!h->gru16_image) CPMPPI_HIP(h, hipMalloc(&h->gru16_image, img16.size()));
   CPMPPI_HIP(h, hipMemcpy(h->gru16_image, img16.data(), img16.size(), hipMemcpyHostToDevice));
   flatten_model(m, h->gru_params);    // (what cpmppi_gru_train_begin starts from)
+  gru_train_end(h);                   // (a master copy of the model before this one must not be stepped on: cpmppi_gru_train_begin again)
   return CPMPPI_OK;
 } catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }   // (no C++ exception leaves the C ABI)
 

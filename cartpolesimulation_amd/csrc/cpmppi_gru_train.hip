@@ -487,6 +487,10 @@ void gru_train_destroy(cpmppi_handle* h) {
   h->gru_train = nullptr;
 }
 
+void gru_train_end(cpmppi_handle* h) {
+  if (h->gru_train) h->gru_train->begun = false;           // the workspace and the tables stay: they do not depend on the model
+}
+
 extern "C" {
 
 int cpmppi_gru_train_reserve(cpmppi_handle* h, uint32_t B, uint32_t rows) try {

@@ -250,8 +250,10 @@ void allow_large_lds_gru_rpgd();
 // pack_f32_image / pack_transposed_image themselves: src[2 * i], src[2 * i + 1] = indices into the flat parameter vector whose sum
 // the float is (-1: none; both -1: zero) - the table of the on-device rebuild (cpmppi_gru_train.hip)
 void gru_image_sources(std::vector<int32_t>& src);
-// cpmppi_gru_train.hip: frees what training allocated (cpmppi_destroy)
+// cpmppi_gru_train.hip: frees what training allocated (cpmppi_destroy); ends a training run, whose master copy, moments and step
+// counter belong to the model before this one - the step and get entry points refuse until cpmppi_gru_train_begin (cpmppi_set_gru)
 void gru_train_destroy(cpmppi_handle* h);
+void gru_train_end(cpmppi_handle* h);
 // cpmppi_gru_seam.hip: the Brunton test's GRU kernel (one partial row per wave of 32 starts: brunton_gru_rows of them); the caller
 // has checked the arguments, checks the launch and reduces the partial rows
 inline size_t brunton_gru_rows(size_t starts) { return (starts + 31) / 32; }

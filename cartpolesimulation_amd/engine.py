@@ -549,7 +549,9 @@ class MPPIEngine:
     def set_gru(self, model):
         """Attach a GRU-6IN-32H1-32H2-5OUT model: dict of float32 arrays in the torch.nn.GRU layout
         (w_ih0[96,6], w_hh0[96,32], b_ih0[96], b_hh0[96], w_ih1[96,32], w_hh1, b_ih1, b_hh1, w_out[5,32], b_out[5]) and
-        optional in_scale/in_shift[6], out_scale/out_shift[5]."""
+        optional in_scale/in_shift[6], out_scale/out_shift[5].  A training run on this engine (``gru_train_begin``) ends here: its
+        master copy and Adam state belong to the model before this one, so ``gru_train_step`` and ``gru_train_get`` are refused
+        until ``gru_train_begin`` starts a run from this model."""
         shapes = dict(w_ih0=(96, 6), w_hh0=(96, 32), b_ih0=(96,), b_hh0=(96,), w_ih1=(96, 32), w_hh1=(96, 32),
                       b_ih1=(96,), b_hh1=(96,), w_out=(5, 32), b_out=(5,), in_scale=(6,), in_shift=(6,),
                       out_scale=(5,), out_shift=(5,))
@@ -730,7 +732,8 @@ class MPPIEngine:
 
     def gru_train_begin(self):
         """cpmppi_gru_train_begin: training starts from the model of the last ``set_gru`` - a master copy on the device, Adam's
-        moments and step counter zero."""
+        moments and step counter zero.  The run lasts until the next ``set_gru``, which ends it: call this again to train the
+        model set then."""
         if not self.has_gru:
             raise ValueError("no model set: call set_gru first")
         self._check(self.lib.cpmppi_gru_train_begin(self._h))

@@ -516,6 +516,12 @@ int cpmppi_replay_step(cpmppi_handle* h, const cpmppi_replay_args* args, void* s
  * cpmppi_gru_train_get and cpmppi_set_gru.  No host synchronisation: capturable after a reserving call.
  * CPMPPI_ERR_BAD_ARG ("cpmppi_gru_train_step: ...") without cpmppi_gru_train_begin, and what cpmppi_gru_loss_grad refuses.
  * cpmppi_gru_train_get: the master copy -> params_host[CPMPPI_GRU_PARAMS], synchronously.
+ * cpmppi_set_gru ENDS a training run: the master copy, the moments and the counter belong to the model before it.  Until the next
+ * cpmppi_gru_train_begin - which starts a run from the model just set - cpmppi_gru_train_step, cpmppi_gru_rollout_train_step and
+ * cpmppi_gru_train_get return CPMPPI_ERR_BAD_ARG ("...: call cpmppi_gru_train_begin first"), launch nothing and leave the images
+ * of the model just set as they are.  cpmppi_gru_loss_grad and its rollout sibling need no run and read the model just set.
+ * (A step captured into a graph before cpmppi_set_gru is not the library's to refuse at replay: capture it again after the new
+ * cpmppi_gru_train_begin.)
  *
  * cpmppi_gru_rollout_loss_grad: the same loss THROUGH THE OPEN-LOOP ROLLOUT, which is how every consumer of a trained model runs it
  * (cpmppi_gru_predict, cpmppi_brunton, the control steps).  The same argument block, windows (r, t0) of W + P rows, zero start
