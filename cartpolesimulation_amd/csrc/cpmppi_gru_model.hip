@@ -181,29 +181,57 @@ int cpmppi_set_gru(cpmppi_handle* h, const cpmppi_gru_model* m) try {
   for (int l = 0; l < 2; ++l)
     if (!m->w_ih[l] || !m->w_hh[l] || !m->b_ih[l] || !m->b_hh[l]) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_gru: null weights");
   if (!m->w_out || !m->b_out) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_gru: null head weights");
-  std::vector<float> img((size_t)GRU_IMAGE_FLOATS, 0.0f), imgt((size_t)GRU_T_IMAGE_FLOATS, 0.0f);
-  std::vector<unsigned char> img16((size_t)G16_IMAGE_BYTES, 0);
-  pack_f32_image(m, img.data());
+  // Everything that can refuse the model comes first and touches locals only: a refused call leaves the handle - the three images,
+  // the normalisation, gru_params and a training run - exactly as it found them.  (The normalisation vectors may be NULL: identity.)
+  const struct { const char* name; const float* p; size_t n; } tensors[14] = {
+      {"w_ih0", m->w_ih[0], 96 * 6}, {"w_hh0", m->w_hh[0], 96 * 32}, {"b_ih0", m->b_ih[0], 96},
+      {"b_hh0", m->b_hh[0], 96},     {"w_ih1", m->w_ih[1], 96 * 32}, {"w_hh1", m->w_hh[1], 96 * 32},
+      {"b_ih1", m->b_ih[1], 96},     {"b_hh1", m->b_hh[1], 96},     {"w_out", m->w_out, 5 * 32},
+      {"b_out", m->b_out, 5},        {"in_scale", m->in_scale, 6},   {"in_shift", m->in_shift, 6},
+      {"out_scale", m->out_scale, 5}, {"out_shift", m->out_shift, 5}};
+  for (const auto& t : tensors)
+    for (size_t i = 0; t.p && i < t.n; ++i)
+      if (!isfinite(t.p[i])) return fail(h, CPMPPI_ERR_BAD_ARG, std::string("cpmppi_set_gru: non-finite value in ") + t.name);
+  cpmppi::GruNorm norm;
   for (int i = 0; i < 6; ++i) {
-    h->gru_norm.in_scale[i] = m->in_scale ? m->in_scale[i] : 1.0f;
-    h->gru_norm.in_shift[i] = m->in_shift ? m->in_shift[i] : 0.0f;
+    norm.in_scale[i] = m->in_scale ? m->in_scale[i] : 1.0f;
+    norm.in_shift[i] = m->in_shift ? m->in_shift[i] : 0.0f;
   }
   for (int i = 0; i < 5; ++i) {
-    h->gru_norm.out_scale[i] = m->out_scale ? m->out_scale[i] : 1.0f;
-    h->gru_norm.out_shift[i] = m->out_shift ? m->out_shift[i] : 0.0f;
+    norm.out_scale[i] = m->out_scale ? m->out_scale[i] : 1.0f;
+    norm.out_shift[i] = m->out_shift ? m->out_shift[i] : 0.0f;
   }
+  std::vector<float> img((size_t)GRU_IMAGE_FLOATS, 0.0f), imgt((size_t)GRU_T_IMAGE_FLOATS, 0.0f), flat;
+  std::vector<unsigned char> img16((size_t)G16_IMAGE_BYTES, 0);
+  pack_f32_image(m, img.data());
   if (!pack_f16_image(m, img.data(), img16.data())) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_set_gru: weights beyond the f16 range");
   pack_transposed_image(m, imgt.data());
+  flatten_model(m, flat);
   CPMPPI_ON_DEVICE(h);
-  if (!h->gru_image) CPMPPI_HIP(h, hipMalloc(&h->gru_image, img.size() * sizeof(float)));
-  CPMPPI_HIP(h, hipMemcpy(h->gru_image, img.data(), img.size() * sizeof(float), hipMemcpyHostToDevice));
-  if (!h->gru_t_image) CPMPPI_HIP(h, hipMalloc(&h->gru_t_image, imgt.size() * sizeof(float)));
-  CPMPPI_HIP(h, hipMemcpy(h->gru_t_image, imgt.data(), imgt.size() * sizeof(float), hipMemcpyHostToDevice));
+  // ... then the device buffers a first call needs, all three or none: `gru_image` is what every entry point reads as "a model is set"
+  void* fresh[3] = {nullptr, nullptr, nullptr};
+  const size_t bytes[3] = {img.size() * sizeof(float), imgt.size() * sizeof(float), img16.size()};
+  const bool have[3] = {h->gru_image != nullptr, h->gru_t_image != nullptr, h->gru16_image != nullptr};
+  for (int i = 0; i < 3; ++i)
+    if (!have[i]) {
+      const hipError_t e = hipMalloc(&fresh[i], bytes[i]);
+      if (e != hipSuccess) {
+        for (int k = 0; k < i; ++k)
+          if (fresh[k]) (void)hipFree(fresh[k]);
+        return fail(h, CPMPPI_ERR_HIP, std::string("cpmppi_set_gru: hipMalloc: ") + hipGetErrorString(e));
+      }
+    }
+  // ... and only now the handle changes: buffers, uploads, normalisation, the flat copy and the end of a training run together
+  if (!have[0]) h->gru_image = (float*)fresh[0];
+  if (!have[1]) h->gru_t_image = (float*)fresh[1];
+  if (!have[2]) h->gru16_image = fresh[2];
+  CPMPPI_HIP(h, hipMemcpy(h->gru_image, img.data(), bytes[0], hipMemcpyHostToDevice));
+  CPMPPI_HIP(h, hipMemcpy(h->gru_t_image, imgt.data(), bytes[1], hipMemcpyHostToDevice));
+  CPMPPI_HIP(h, hipMemcpy(h->gru16_image, img16.data(), bytes[2], hipMemcpyHostToDevice));
   allow_large_lds_gru_adjoint();      // (both images in LDS: beyond the default 64 KB)
   allow_large_lds_gru_rpgd();         // (... and the fused rpgd step keeps the rollout's image beside them)
-  if (!h->gru16_image) CPMPPI_HIP(h, hipMalloc(&h->gru16_image, img16.size()));
-  CPMPPI_HIP(h, hipMemcpy(h->gru16_image, img16.data(), img16.size(), hipMemcpyHostToDevice));
-  flatten_model(m, h->gru_params);    // (what cpmppi_gru_train_begin starts from)
+  h->gru_norm = norm;
+  h->gru_params.swap(flat);           // (what cpmppi_gru_train_begin starts from)
   gru_train_end(h);                   // (a master copy of the model before this one must not be stepped on: cpmppi_gru_train_begin again)
   return CPMPPI_OK;
 } catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }   // (no C++ exception leaves the C ABI)

@@ -551,7 +551,14 @@ class MPPIEngine:
         (w_ih0[96,6], w_hh0[96,32], b_ih0[96], b_hh0[96], w_ih1[96,32], w_hh1, b_ih1, b_hh1, w_out[5,32], b_out[5]) and
         optional in_scale/in_shift[6], out_scale/out_shift[5].  A training run on this engine (``gru_train_begin``) ends here: its
         master copy and Adam state belong to the model before this one, so ``gru_train_step`` and ``gru_train_get`` are refused
-        until ``gru_train_begin`` starts a run from this model."""
+        until ``gru_train_begin`` starts a run from this model.
+
+        ``CpmppiError`` ("cpmppi_set_gru: ...") for a NaN or an infinity in any of the fourteen arrays ("non-finite value in
+        <key>") and for a weight beyond what the f16 image of the FAST kernels stores ("weights beyond the f16 range"): the
+        largest accepted magnitude is 41588.83 in the r and z rows of w_ih / w_hh, 20794.414 in their n rows (the rows are stored
+        pre-scaled by log2(e) and 2 log2(e)) and 59999.996 in w_out.  A refused call changes nothing: the engine keeps the model
+        it held - ``has_gru`` stays as it was - and a training run goes on.  FAST kernels need every normalised input and every
+        fed-back output within +-65504 (beyond it they give NaN where PRECISE stays finite); nothing checks that at run time."""
         shapes = dict(w_ih0=(96, 6), w_hh0=(96, 32), b_ih0=(96,), b_hh0=(96,), w_ih1=(96, 32), w_hh1=(96, 32),
                       b_ih1=(96,), b_hh1=(96,), w_out=(5, 32), b_out=(5,), in_scale=(6,), in_shift=(6,),
                       out_scale=(5,), out_shift=(5,))

@@ -332,7 +332,23 @@ int cpmppi_step_host(cpmppi_handle* h, uint32_t E, const float* s0, const float*
 int cpmppi_set_profiling(cpmppi_handle* h, int enable);
 int cpmppi_get_profile(cpmppi_handle* h, float* rollout_ms, float* finalize_ms, uint32_t max_steps, uint32_t* n_steps);
 
-/* Attach / replace the GRU model of a handle (synchronous upload; not for the launch path). */
+/* Attach / replace the GRU model of a handle (synchronous upload; not for the launch path).  The model is packed into three weight
+ * images: the exact-f32 fragments with their plain vectors, the transposed fragments of the reverse sweeps, and the f16 split image
+ * of the FAST kernels (every weight as hi = f16(w), lo = f16(w - hi)).
+ * Refused with CPMPPI_ERR_BAD_ARG ("cpmppi_set_gru: ..."):
+ *   "non-finite value in <tensor>": a NaN or an infinity in any of the ten weight tensors or of the four normalisation vectors;
+ *   "weights beyond the f16 range": a value v STORED in the f16 image with !(|v| < 60000).  Gate rows are stored pre-scaled - r and
+ *     z by -log2(e), n by 2 log2(e) - so the largest accepted float32 magnitude of a weight of w_ih / w_hh differs per gate:
+ *     41588.83 (r, z), 20794.414 (n); of the head w_out, stored as it is, 59999.996.  Biases are kept in float32: finite is all
+ *     they need be.  (Measured on the MI355X with one entry per matrix and gate at 0.9 of its limit in a model of scale 0.3: FAST
+ *     and PRECISE both conform to the float32 / float64 oracle under the cost and control rules of the tests: DESIGN 8, N5.)
+ * A refusal changes nothing: the handle keeps the three images, the normalisation and the flat parameters of the model it held
+ * (none, if none was set: the GRU entry points go on refusing with "no model set"), and a training run goes on.  Everything that
+ * can refuse is checked on host copies before the handle or the device is touched.
+ * The f16 split carries an OPERAND only within +-65504: a normalised input x * in_scale + in_shift, a fed-back head output or a
+ * memory entry beyond that splits into hi = inf, lo = -inf and the FAST products are NaN, where the exact-f32 kernels stay finite.
+ * The memory lies in [-1, 1]; inputs and outputs are the caller's to keep inside (a normalised control of 6.0e4 is confirmed to
+ * agree with the oracle in both modes).  Nothing checks it at run time. */
 int cpmppi_set_gru(cpmppi_handle* h, const cpmppi_gru_model* model);
 
 /* Predictor seam with the neural predictor (predictor_autoregressive_neural; augmentation angle = atan2(sin, cos),
@@ -511,12 +527,16 @@ int cpmppi_replay_step(cpmppi_handle* h, const cpmppi_replay_args* args, void* s
  * (2) one bias-corrected Adam update of the master copy, t = the device counter + 1, formed in float64 and stored as float32:
  *     m = b1 m + (1-b1) g, v = b2 v + (1-b2) g^2, p -= lr (m / (1-b1^t)) / (sqrt(v / (1-b2^t)) + eps),
  * (3) the rebuild ON THE DEVICE of the two float32 weight images the training kernels read - the fragment image and the
- * transposed image of the exact-f32 cell - bit for bit what cpmppi_set_gru builds on the host for the same weights.  The f16 image
- * of the fused rollout kernels keeps the model of the last cpmppi_set_gru: a trained model reaches them through
- * cpmppi_gru_train_get and cpmppi_set_gru.  No host synchronisation: capturable after a reserving call.
+ * transposed image of the exact-f32 cell - bit for bit what cpmppi_set_gru builds on the host for the same weights, the plain
+ * vectors (gate biases, head) of the PRECISE fused kernels included.  The f16 image of the FAST kernels keeps the model of the last
+ * cpmppi_set_gru: a trained model reaches them through cpmppi_gru_train_get and cpmppi_set_gru.  So during a run a PRECISE handle
+ * rolls out, costs and differentiates the TRAINED model, a FAST handle's fused steps and cpmppi_rollout_cost_gru the model of the
+ * last cpmppi_set_gru - and a FAST cpmppi_rollout_cost_grad_gru mixes the two (its forward sweep reads the f16 image, its reverse
+ * sweep the float32 images): do not use it between cpmppi_gru_train_begin and the next cpmppi_set_gru.
+ * No host synchronisation: capturable after a reserving call.
  * CPMPPI_ERR_BAD_ARG ("cpmppi_gru_train_step: ...") without cpmppi_gru_train_begin, and what cpmppi_gru_loss_grad refuses.
  * cpmppi_gru_train_get: the master copy -> params_host[CPMPPI_GRU_PARAMS], synchronously.
- * cpmppi_set_gru ENDS a training run: the master copy, the moments and the counter belong to the model before it.  Until the next
+ * A successful cpmppi_set_gru ENDS a training run (a refused one leaves it alone): the master copy, the moments and the counter belong to the model before it.  Until the next
  * cpmppi_gru_train_begin - which starts a run from the model just set - cpmppi_gru_train_step, cpmppi_gru_rollout_train_step and
  * cpmppi_gru_train_get return CPMPPI_ERR_BAD_ARG ("...: call cpmppi_gru_train_begin first"), launch nothing and leave the images
  * of the model just set as they are.  cpmppi_gru_loss_grad and its rollout sibling need no run and read the model just set.
