@@ -34,7 +34,11 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_score_runs", "cpmppi_set_tuning_rows", "cpmppi_replay_step", "cpmppi_cem_step_gru",
            "cpmppi_rpgd_step_gru", "cpmppi_rpgd_gru_reserve", "cpmppi_rpgd_step_rows",
            "cpmppi_gru_train_reserve", "cpmppi_gru_loss_grad", "cpmppi_gru_train_begin", "cpmppi_gru_train_step",
-           "cpmppi_gru_train_get", "cpmppi_gru_rollout_loss_grad", "cpmppi_gru_rollout_train_step")
+           "cpmppi_gru_train_get", "cpmppi_gru_rollout_loss_grad", "cpmppi_gru_rollout_train_step",
+           "cpmppi_ode_fit_reserve", "cpmppi_ode_fit_loss_grad", "cpmppi_ode_fit_begin", "cpmppi_ode_fit_set_theta",
+           "cpmppi_ode_fit_step", "cpmppi_ode_fit_get")
+ODE_FIT_PARAMS = 8                                   # CPMPPI_ODE_FIT_PARAMS, in this order (bit i of a `trainable` mask)
+ODE_FIT_NAMES = ("k", "m_cart", "m_pole", "g", "J_fric", "M_fric", "u_max", "L")
 GRU_PARAMS = 10341                                   # CPMPPI_GRU_PARAMS: the flat parameter vector of the training entry points
 TUNING_ROW_FLOATS, TUNING_LBD, TUNING_SIGMA = 16, 7, 8
 RPGD_ROW_LR, RPGD_ROW_GRADMAX_CLIP = 7, 8            # cpmppi_rpgd_step_rows: the same row, these two behind the seven cost entries
@@ -121,6 +125,12 @@ class cpmppi_gru_loss_args(C.Structure):
     _fields_ = [("B", C.c_uint32), ("R", C.c_uint32), ("T", C.c_uint32), ("wash_out", C.c_uint32), ("post_wash_out", C.c_uint32),
                 ("shift_labels", C.c_uint32), ("states", C.c_void_p), ("Q", C.c_void_p), ("windows", C.c_void_p),
                 ("windows_host", C.c_void_p), ("loss_out", C.c_void_p), ("grad_out", C.c_void_p)]
+
+
+class cpmppi_ode_fit_args(C.Structure):
+    _fields_ = [("B", C.c_uint32), ("R", C.c_uint32), ("T", C.c_uint32), ("horizon", C.c_uint32), ("trainable", C.c_uint32),
+                ("states", C.c_void_p), ("Q", C.c_void_p), ("L", C.c_void_p), ("windows", C.c_void_p), ("windows_host", C.c_void_p),
+                ("feature_scale", C.c_float * 5), ("loss_out", C.c_void_p), ("grad_out", C.c_void_p), ("per_window_out", C.c_void_p)]
 
 
 class cpmppi_score_args(C.Structure):
@@ -264,6 +274,12 @@ def load():
     lib.cpmppi_gru_train_get.argtypes = [vp, C.POINTER(f)]
     lib.cpmppi_gru_rollout_loss_grad.argtypes = [vp, C.POINTER(cpmppi_gru_loss_args), vp]
     lib.cpmppi_gru_rollout_train_step.argtypes = [vp, C.POINTER(cpmppi_gru_loss_args), f, f, f, f, vp]
+    lib.cpmppi_ode_fit_reserve.argtypes = [vp, u32]
+    lib.cpmppi_ode_fit_loss_grad.argtypes = [vp, C.POINTER(cpmppi_ode_fit_args), vp]
+    lib.cpmppi_ode_fit_begin.argtypes = [vp]
+    lib.cpmppi_ode_fit_set_theta.argtypes = [vp, C.POINTER(f)]
+    lib.cpmppi_ode_fit_step.argtypes = [vp, C.POINTER(cpmppi_ode_fit_args), f, f, f, f, vp]
+    lib.cpmppi_ode_fit_get.argtypes = [vp, C.POINTER(f), C.POINTER(f)]
     lib.cpmppi_cem_sample.argtypes = [vp, u32, vp, vp, u64, u64, u32, vp, vp]
     lib.cpmppi_cem_update.argtypes = [vp, u32, vp, vp, u32, f, vp, vp, vp, vp]
     lib.cpmppi_tiled_floats.argtypes = [vp, u32]

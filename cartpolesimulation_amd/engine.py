@@ -676,6 +676,126 @@ class MPPIEngine:
         buffers (a benchmark loop, a capture - after one plain run, which allocates the workspace)."""
         return self._build_brunton(*args, **kwargs)
 
+    # ------------------------------------------------------------------ fitting the ODE predictor's physical parameters
+    @staticmethod
+    def ode_fit_mask(trainable):
+        """Names out of ``_lib.ODE_FIT_NAMES`` (one, or a sequence; or the bit mask itself) -> the ``trainable`` bit mask."""
+        if isinstance(trainable, (int, np.integer)):
+            mask = int(trainable)
+        else:
+            names = (trainable,) if isinstance(trainable, str) else tuple(trainable)
+            unknown = [n for n in names if n not in _L.ODE_FIT_NAMES]
+            if unknown:
+                raise ValueError(f"trainable {unknown}: the parameters a fit can train are {', '.join(_L.ODE_FIT_NAMES)} "
+                                 "(TrackHalfLength is not offered: only the bounce test reads it)")
+            mask = sum({1 << _L.ODE_FIT_NAMES.index(n) for n in names})
+        if not 0 < mask < (1 << _L.ODE_FIT_PARAMS):
+            raise ValueError(f"trainable: a non-empty set of {', '.join(_L.ODE_FIT_NAMES)}, got {trainable!r}")
+        return mask
+
+    def _ode_fit_args(self, states, Q, windows, horizon, trainable, feature_scale, L=None, loss_out=None, grad_out=None, grad=True,
+                      per_window_out=None):
+        """The argument block of cpmppi_ode_fit_loss_grad / cpmppi_ode_fit_step, checked: -> (block, what it points into, loss_out,
+        grad_out).  ``windows`` [B,2] integers (r, t0) on the HOST: uploaded here, and handed to the library as its host copy."""
+        states, Q, R, T = self._recordings(states, Q)
+        horizon, mask = int(horizon), self.ode_fit_mask(trainable)
+        if not 1 <= horizon <= self.H:
+            raise ValueError(f"horizon must be in 1..{self.H} (the engine's mpc_horizon), got {horizon}")
+        w = np.asarray(windows.cpu() if torch.is_tensor(windows) else windows)
+        if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] == 0 or not np.issubdtype(w.dtype, np.integer):
+            raise ValueError(f"windows must be integers [B,2] = (recording, first row) with B >= 1, got {w.dtype} {w.shape}")
+        if w.min() < 0 or w[:, 0].max() >= R or w[:, 1].max() + horizon > T - 1:
+            raise ValueError(f"every window (r, t0) must satisfy r < {R} and t0 + {horizon} <= {T - 1}")
+        scale = np.asarray(feature_scale, np.float32).reshape(-1)
+        if scale.shape != (5,) or not np.isfinite(scale).all():
+            raise ValueError("feature_scale must hold five finite numbers (angleD, angle_cos, angle_sin, position, positionD)")
+        if L is not None and (mask >> _L.ODE_FIT_NAMES.index("L")) & 1:
+            raise ValueError("L is trainable and L rows are given: the rows would replace the parameter")
+        L = self.tensor(L, (R, T)) if L is not None else None
+        B = w.shape[0]
+        w_host = np.ascontiguousarray(w, dtype=np.uint32)
+        w_dev = torch.as_tensor(w_host.astype(np.int32)).to(self.device)
+        if loss_out is None:
+            loss_out = torch.empty(1, dtype=torch.float64, device=self.device)
+        elif device_tensor("loss_out", loss_out, torch.float64).numel() != 1:
+            raise ValueError("loss_out must have one element")
+        if grad and grad_out is None:
+            grad_out = torch.empty(_L.ODE_FIT_PARAMS, dtype=torch.float64, device=self.device)
+        elif grad_out is not None and (not grad or device_tensor("grad_out", grad_out, torch.float64).shape != (_L.ODE_FIT_PARAMS,)):
+            raise ValueError(f"grad_out must be float64 [{_L.ODE_FIT_PARAMS}] (and grad=True)")
+        if per_window_out is not None and device_tensor("per_window_out", per_window_out, tail=(1 + _L.ODE_FIT_PARAMS,)).shape[0] != B:
+            raise ValueError(f"per_window_out must be [{B},{1 + _L.ODE_FIT_PARAMS}]")
+        a = _L.cpmppi_ode_fit_args()
+        a.B, a.R, a.T, a.horizon, a.trainable = B, R, T, horizon, mask
+        a.states, a.Q, a.L, a.windows, a.windows_host = states.data_ptr(), Q.data_ptr(), _addr(L), w_dev.data_ptr(), w_host.ctypes.data
+        a.feature_scale = (C.c_float * 5)(*scale.tolist())
+        a.loss_out, a.grad_out, a.per_window_out = loss_out.data_ptr(), _addr(grad_out), _addr(per_window_out)
+        return a, (states, Q, L, w_dev, w_host, loss_out, grad_out, per_window_out), loss_out, grad_out
+
+    def ode_fit_reserve(self, B):
+        """cpmppi_ode_fit_reserve: the workspace of ``ode_fit_loss_grad`` / ``ode_fit_step`` for up to ``B`` windows, so that a later
+        call can be captured."""
+        self._check(self.lib.cpmppi_ode_fit_reserve(self._h, int(B)))
+
+    def _build_ode_fit_loss_grad(self, states, Q, windows, horizon, trainable=("u_max",), feature_scale=(1.0,) * 5, L=None, grad=True, *,
+                                 loss_out=None, grad_out=None, per_window_out=None):
+        """cpmppi_ode_fit_loss_grad: the open-loop error of the engine's ODE predictor over ``windows`` [B,2] = (recording, first row)
+        of ``states`` [R,T,6], ``Q`` [R,T] (include/cpmppi.h states it) - the mean over B x ``horizon`` x 5 of the squared error of
+        angleD, angle_cos, angle_sin, position, positionD times ``feature_scale`` - at the fit's running parameters (the engine's own
+        before ``ode_fit_begin``), and its derivative with respect to theta, p = base exp(theta), of the ``trainable`` parameters.
+        -> (loss [1] float64 on the device, d loss / d theta [8] float64 in the order of ``_lib.ODE_FIT_NAMES`` - None with
+        ``grad=False``, the loss alone, bit for bit the loss of the gradient call)."""
+        a, keep, loss_out, grad_out = self._ode_fit_args(states, Q, windows, horizon, trainable, feature_scale, L, loss_out, grad_out,
+                                                         grad, per_window_out)
+        return PreparedCall(self, self.lib.cpmppi_ode_fit_loss_grad, a, keep, (loss_out, grad_out), ())
+
+    ode_fit_loss_grad = _run_once(_build_ode_fit_loss_grad)
+
+    def prepare_ode_fit_loss_grad(self, *args, **kwargs):
+        """The argument block of ``ode_fit_loss_grad(...)`` built and validated ONCE: ``.run()`` enqueues the two launches again on the
+        same buffers (a capture - after one plain run or ``ode_fit_reserve``, which allocate the workspace)."""
+        return self._build_ode_fit_loss_grad(*args, **kwargs)
+
+    def ode_fit_begin(self):
+        """cpmppi_ode_fit_begin: a fit starts from the engine's own physical parameters (with its scalar pole mass) - theta, Adam's
+        moments and the step counter zero.  The engine's physics is never changed by a fit."""
+        self._check(self.lib.cpmppi_ode_fit_begin(self._h))
+
+    def ode_fit_set_theta(self, theta):
+        """cpmppi_ode_fit_set_theta: theta [8] in the order of ``_lib.ODE_FIT_NAMES``; p = base exp(theta) follows on the device."""
+        t = np.ascontiguousarray(np.asarray(theta, np.float32).reshape(-1))
+        if t.shape != (_L.ODE_FIT_PARAMS,):
+            raise ValueError(f"theta must hold {_L.ODE_FIT_PARAMS} numbers ({', '.join(_L.ODE_FIT_NAMES)})")
+        self._check(self.lib.cpmppi_ode_fit_set_theta(self._h, t.ctypes.data_as(C.POINTER(C.c_float))))
+
+    def _build_ode_fit_step(self, states, Q, windows, horizon, trainable=("u_max",), feature_scale=(1.0,) * 5, L=None, *, lr, beta1=0.9,
+                            beta2=0.999, eps=1e-8, loss_out=None):
+        """cpmppi_ode_fit_step: the loss and gradient of ``ode_fit_loss_grad`` over this batch of ``windows``, one Adam update of the
+        trainable theta and the rewrite of the parameters the next step reads, all on the device.
+        -> the batch's loss BEFORE the update, [1] float64 on the device."""
+        a, keep, loss_out, _ = self._ode_fit_args(states, Q, windows, horizon, trainable, feature_scale, L, loss_out, None, False)
+        lib, hyper = self.lib, (float(lr), float(beta1), float(beta2), float(eps))
+        return PreparedCall(self, lambda h, ref, stream: lib.cpmppi_ode_fit_step(h, ref, *hyper, stream), a, keep, loss_out, ())
+
+    def ode_fit_step(self, *args, **kwargs):
+        """``_build_ode_fit_step``'s call, run once: -> the batch's loss before the update."""
+        call = self._build_ode_fit_step(*args, **kwargs)
+        self._fit_keep = call.keep                    # (the launches read the batch after this call returns)
+        return call.run()
+
+    def prepare_ode_fit_step(self, *args, **kwargs):
+        """The argument block of ``ode_fit_step(...)`` built and validated ONCE: every ``.run()`` is one more Adam step on the same
+        batch and buffers (a benchmark loop, a capture - after ``ode_fit_reserve``)."""
+        return self._build_ode_fit_step(*args, **kwargs)
+
+    def ode_fit_get(self):
+        """cpmppi_ode_fit_get: -> (the fit's parameters p [8], theta [8]), float32 numpy in the order of ``_lib.ODE_FIT_NAMES``.
+        Synchronous."""
+        p, theta = np.empty(_L.ODE_FIT_PARAMS, np.float32), np.empty(_L.ODE_FIT_PARAMS, np.float32)
+        fp = C.POINTER(C.c_float)
+        self._check(self.lib.cpmppi_ode_fit_get(self._h, p.ctypes.data_as(fp), theta.ctypes.data_as(fp)))
+        return p, theta
+
     # ------------------------------------------------------------------ training the GRU predictor on recordings
     def _gru_loss_args(self, states, Q, windows, wash_out, post_wash_out, shift_labels, loss_out=None, grad_out=None, grad=True,
                        rollout=False):
@@ -1318,7 +1438,7 @@ class MPPIEngine:
 
 class PreparedCall:
     """One entry point of the library that takes an argument block, ready to be enqueued any number of times
-    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_rpgd_step_gru / prepare_cem_step / prepare_cem_step_gru / prepare_brunton / prepare_gru_loss_grad).  ``args`` is the live
+    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_rpgd_step_gru / prepare_cem_step / prepare_cem_step_gru / prepare_brunton / prepare_gru_loss_grad / prepare_ode_fit_loss_grad / prepare_ode_fit_step).  ``args`` is the live
     ctypes block, validated when it was built, and ``ref`` the reference to it that the library is handed; ``keep`` holds the
     tensors it points into; ``enqueue`` is the entry point, ``enqueue(handle, ref, stream)``.  ``result`` is what the call returns:
     the outputs of a control step - ``out``, whose first two are ``Q_out`` and ``S_out`` -, the plant's state, or the Brunton

@@ -112,6 +112,19 @@ def horizon_of_epoch(schedule, epoch):
     return schedule[min(int(epoch), len(schedule) - 1)]
 
 
+def plateau_rule(monitored, best, wait, rate, reduce_lr_on_plateau, patience, decrease_factor, minimal_lr, min_delta):
+    """``LR.REDUCE_LR_ON_PLATEAU`` after one epoch (shared with fit_ode): an improvement of the monitored loss by more than
+    ``min_delta`` resets the wait; otherwise, with the rule on, ``patience`` such epochs multiply the rate by ``decrease_factor``
+    (not below ``minimal_lr``).  -> (best, wait, rate)."""
+    if monitored < best - float(min_delta):
+        return monitored, 0, rate
+    if reduce_lr_on_plateau:
+        wait += 1
+        if wait >= int(patience):
+            rate, wait = max(rate * float(decrease_factor), float(minimal_lr)), 0
+    return best, wait, rate
+
+
 def _check_model(model):
     for key, shp in zip(GRU_KEYS, GRU_SHAPES):
         if key not in model or np.shape(model[key]) != shp:
@@ -207,12 +220,8 @@ def train_gru(engine, states, Q, lengths=None, *, epochs, batch_size, lr, seed, 
         if log is not None:
             log(f"epoch {epoch + 1}/{epochs}: loss {history['loss'][-1]:.6e}"
                 + (f", val_loss {history['val_loss'][-1]:.6e}" if val is not None else "") + f", lr {rate:.3e}")
-        if monitored < best - float(min_delta):
-            best, wait = monitored, 0
-        elif reduce_lr_on_plateau:
-            wait += 1
-            if wait >= int(patience):
-                rate, wait = max(rate * float(decrease_factor), float(minimal_lr)), 0
+        best, wait, rate = plateau_rule(monitored, best, wait, rate, reduce_lr_on_plateau, patience, decrease_factor, minimal_lr,
+                                        min_delta)
     trained = {**engine.gru_train_get(), **norm}
     engine.set_gru(trained)            # (the rollout kernels' split-f16 image is built, and range-checked, on the host)
     return trained, history
@@ -251,6 +260,25 @@ def write_model_folder(folder, model, name=None, info=None):
 _DYNAMICS = dict(control_inputs=["Q"], state_inputs=list(KERNEL_INPUTS[1:]), outputs=list(KERNEL_OUTPUTS))
 
 
+def refuse_unbuilt_sections(config):
+    """The keys of config_training.yml that neither trainer of this package (train_gru, fit_ode) is built for, refused by name
+    where they are activated: on-the-fly data generation, NNI, regularisation, quantisation, pruning, series modification, filters."""
+    t = dict(config.get("training_default") or {})
+    if t.get("ON_FLY_DATA_GENERATION"):
+        raise ValueError("training_default.ON_FLY_DATA_GENERATION: not built (generate recordings first: generate_dataset)")
+    if t.get("USE_NNI"):
+        raise ValueError("training_default.USE_NNI: not built")
+    for section in ("REGULARIZATION", "QUANTIZATION", "PRUNING"):
+        if (config.get(section) or {}).get("ACTIVATED"):
+            raise ValueError(f"{section}.ACTIVATED: not built (the loss is the mean squared error alone, the weights float32)")
+    mode = (config.get("CONFIG_SERIES_MODIFICATION") or {}).get("MODE")
+    noise = ((config.get("CONFIG_SERIES_MODIFICATION") or {}).get("NOISE_LEVEL") or {}).get("FEATURES", 0.0)
+    if (mode not in (None, "None")) or noise:
+        raise ValueError(f"CONFIG_SERIES_MODIFICATION (MODE {mode!r}, NOISE_LEVEL.FEATURES {noise}): not built")
+    if config.get("FILTERS"):
+        raise ValueError("FILTERS: not built (filter the recordings before training)")
+
+
 def training_settings(config, net=None, dynamics_model=False, **overrides):
     """config_training.yml as a dict -> the keyword arguments of ``train_gru`` (EPOCHS, BATCH_SIZE, SEED, LR.*, WASH_OUT_LEN,
     POST_WASH_OUT_LEN, SHIFT_LABELS; ``overrides``: the same by ``train_gru``'s names, None = the file's) and ``normalize``.  What the
@@ -270,19 +298,7 @@ def training_settings(config, net=None, dynamics_model=False, **overrides):
     for key in ("setpoint_inputs", "translation_invariant_variables"):
         if t.get(key):
             raise ValueError(f"training_default.{key} = {t[key]}: not built (the dynamics model has none)")
-    if t.get("ON_FLY_DATA_GENERATION"):
-        raise ValueError("training_default.ON_FLY_DATA_GENERATION: not built (generate recordings first: generate_dataset)")
-    if t.get("USE_NNI"):
-        raise ValueError("training_default.USE_NNI: not built")
-    for section in ("REGULARIZATION", "QUANTIZATION", "PRUNING"):
-        if (config.get(section) or {}).get("ACTIVATED"):
-            raise ValueError(f"{section}.ACTIVATED: not built (the loss is the mean squared error alone, the weights float32)")
-    mode = (config.get("CONFIG_SERIES_MODIFICATION") or {}).get("MODE")
-    noise = ((config.get("CONFIG_SERIES_MODIFICATION") or {}).get("NOISE_LEVEL") or {}).get("FEATURES", 0.0)
-    if (mode not in (None, "None")) or noise:
-        raise ValueError(f"CONFIG_SERIES_MODIFICATION (MODE {mode!r}, NOISE_LEVEL.FEATURES {noise}): not built")
-    if config.get("FILTERS"):
-        raise ValueError("FILTERS: not built (filter the recordings before training)")
+    refuse_unbuilt_sections(config)
     lr = t.get("LR") or {}
     out = dict(epochs=t.get("EPOCHS", 30), batch_size=t.get("BATCH_SIZE", 64), seed=t.get("SEED", 0), lr=lr.get("INITIAL", 2e-3),
                reduce_lr_on_plateau=bool(lr.get("REDUCE_LR_ON_PLATEAU", True)), patience=lr.get("PATIENCE", 2),

@@ -63,7 +63,9 @@ extern "C" {
                                       cpmppi_rpgd_step_rows (a new entry point, likewise);
                                       cpmppi_gru_loss_grad / cpmppi_gru_loss_args, cpmppi_gru_train_reserve / _begin / _step / _get
                                       (new entry points, likewise);
-                                      cpmppi_gru_rollout_loss_grad / cpmppi_gru_rollout_train_step (new entry points, likewise). */
+                                      cpmppi_gru_rollout_loss_grad / cpmppi_gru_rollout_train_step (new entry points, likewise);
+                                      cpmppi_ode_fit_loss_grad / cpmppi_ode_fit_args, cpmppi_ode_fit_reserve / _begin / _set_theta /
+                                      _step / _get (new entry points, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -579,6 +581,70 @@ int cpmppi_gru_train_get(cpmppi_handle* h, float* params_host);
 int cpmppi_gru_rollout_loss_grad(cpmppi_handle* h, const cpmppi_gru_loss_args* args, void* stream);
 int cpmppi_gru_rollout_train_step(cpmppi_handle* h, const cpmppi_gru_loss_args* args, float lr, float beta1, float beta2, float eps,
                                   void* stream);
+
+/* Fitting the ODE predictor's PHYSICAL PARAMETERS to recordings (SI_Toolkit_ASF/ToolkitCustomization/Modules/ODE_module.py, the
+ * "fake network" Custom-ODE_module-ODEModel of config_training.yml whose weights are the cartpole's parameters; the training code
+ * itself is not part of the reference checkout, so windows, loss, parametrisation and schedule are this library's own).
+ * The parameters are CPMPPI_ODE_FIT_PARAMS = 8 floats in the order  k, m_cart, m_pole, g, J_fric, M_fric, u_max, L ; bit i of
+ * `trainable` selects parameter i.  TrackHalfLength is not offered: only the edge-bounce test reads it, and the derivative of the
+ * open-loop error with respect to it is zero almost everywhere.
+ *
+ * cpmppi_ode_fit_loss_grad: B windows (r, t0) over recordings in the layout of cpmppi_brunton.  A window starts at states[r,t0]
+ * and integrates `horizon` control steps on the RECORDED controls Q[r,t0+j] with the plain substep of the handle's math mode and ODE
+ * predictor (wrap + sin / cos on every substep: what cpmppi_rollout_cost_grad differentiates); step j predicts row t0+j+1.  The loss
+ * is the mean over B x horizon x 5 of ((predicted - recorded) * feature_scale[f])^2, f = angleD, angle_cos, angle_sin, position,
+ * positionD (the angle itself is not scored: a wrap taken differently costs nothing).  The derivative is carried FORWARD with the
+ * state (tangents of angle, angleD, position, positionD per trained parameter); the branch taken decides it through the edge
+ * bounce, which reads L directly, and it is 1 through fmod, the wrap and atan2(sin, cos).  The parameters are the running ones of a
+ * fit (below) or, before cpmppi_ode_fit_begin, the handle's own with its scalar pole mass; L[R,T], when given, is the pole length
+ * per start row as in cpmppi_brunton and replaces parameter 7.
+ * loss_out: one DEVICE double.  grad_out[8] DEVICE doubles: d loss / d theta_i = p_i d loss / d p_i (see cpmppi_ode_fit_begin;
+ * exactly 0 for a parameter that is not trainable), or NULL for the loss alone, which equals the loss of a gradient call with the
+ * same `trainable` bit for bit.  per_window_out[B][1+8] DEVICE floats, or NULL: per window the sum over its steps and features of
+ * the squared scaled error and that sum's derivative d / d p_i - neither divided by B x horizon x 5 nor multiplied by p_i.
+ * No atomics: a workgroup writes its own row of partial sums, a second kernel walks the rows in a fixed order in float64 - the same
+ * bits from run to run.  The workspace is reserved by cpmppi_ode_fit_reserve(h, B) for up to B windows, or on first use - a capture
+ * that would have to allocate is refused.
+ * Nothing is launched and CPMPPI_ERR_BAD_ARG is returned ("cpmppi_ode_fit_loss_grad: ...") for a NULL states, Q, windows,
+ * windows_host or loss_out; B, R, T or horizon equal to 0; horizon > config.H; a host window outside r < R, t0 + horizon <= T - 1;
+ * an empty or unknown `trainable` mask; a trainable parameter whose base value is <= 0; trainable L together with L rows; per-row
+ * pole masses registered on the handle (cpmppi_set_pole_mass_rows).  A misaligned pointer is CPMPPI_ERR_ALIGN.
+ *
+ * cpmppi_ode_fit_begin: a fit starts.  base_i = the handle's configuration with its scalar pole mass (L: L_default);
+ * p_i = base_i * exp(theta_i) with theta = 0 - the parameters span five decades, must stay positive, and one learning rate has to
+ * serve them all -; both Adam moments and the device step counter are zero.  Synchronous.
+ * cpmppi_ode_fit_set_theta: theta <- theta_host[8] and p = (float)(base * exp((double)theta)) on the device; the moments and the
+ * counter stay.  Synchronous.
+ * cpmppi_ode_fit_step: (1) the loss and d loss / d theta of cpmppi_ode_fit_loss_grad into the handle's own buffer (grad_out is
+ * not read), (2) per trainable parameter the bias-corrected Adam update of theta stated at cpmppi_gru_train_step, t = the device
+ * counter + 1, formed in float64 and stored as float32, (3) p = (float)(base * exp((double)theta)) rewritten for the next step's
+ * kernel.  A parameter that is not trainable keeps theta and p bit for bit.  No host synchronisation: capturable after a reserving
+ * call.  cpmppi_ode_fit_get: p -> params_host[8], theta -> theta_host[8] (either may be NULL), synchronously.
+ * cpmppi_ode_fit_step, _get and _set_theta before cpmppi_ode_fit_begin: CPMPPI_ERR_BAD_ARG ("...: call cpmppi_ode_fit_begin
+ * first").  The handle's own physics is never changed: a fitted model reaches the other kernels through a new handle. */
+#define CPMPPI_ODE_FIT_PARAMS 8u
+typedef struct {
+  uint32_t B;                           /* windows */
+  uint32_t R, T;                        /* recordings, rows of each */
+  uint32_t horizon;                     /* control steps per window, 1..config.H */
+  uint32_t trainable;                   /* bit i: parameter i of k, m_cart, m_pole, g, J_fric, M_fric, u_max, L */
+  const float* states;                  /* [R,T,6] */
+  const float* Q;                       /* [R,T] */
+  const float* L;                       /* [R,T] pole length per start row, or NULL = parameter 7 */
+  const uint32_t* windows;              /* [B][2] DEVICE: (r, t0) */
+  const uint32_t* windows_host;         /* [B][2] HOST: the same, checked by every call */
+  float feature_scale[5];               /* angleD, angle_cos, angle_sin, position, positionD */
+  double* loss_out;                     /* DEVICE, one double */
+  double* grad_out;                     /* [8] DEVICE: d loss / d theta, or NULL */
+  float* per_window_out;                /* [B][1+8] DEVICE, or NULL */
+} cpmppi_ode_fit_args;
+int cpmppi_ode_fit_reserve(cpmppi_handle* h, uint32_t B);
+int cpmppi_ode_fit_loss_grad(cpmppi_handle* h, const cpmppi_ode_fit_args* args, void* stream);
+int cpmppi_ode_fit_begin(cpmppi_handle* h);
+int cpmppi_ode_fit_set_theta(cpmppi_handle* h, const float* theta_host);
+int cpmppi_ode_fit_step(cpmppi_handle* h, const cpmppi_ode_fit_args* args, float lr, float beta1, float beta2, float eps,
+                        void* stream);
+int cpmppi_ode_fit_get(cpmppi_handle* h, float* params_host, float* theta_host);
 
 /* Rollout + cost only (no update): per-rollout trajectory cost S[E,N] of GIVEN input sequences inputs[E,N,H] under the
  * handle's plugin cost — cost_function.get_trajectory_cost(predictor.predict_core(s, Q), Q) fused; the building block of
