@@ -25,6 +25,7 @@
 // The forward kernel stores the head ADJOINT where the issue that asked for it suggested the head output: the reverse sweep and the
 // head's weight gradient need nothing else of the output, and the label is then formed once.
 #include "cpmppi_gru_reverse.hpp"   // (and cpmppi_gru.hpp, cpmppi_grad.hpp, cpmppi_internal.hpp)
+#include "cpmppi_train.hpp"
 
 using namespace cpmppi_k;
 
@@ -306,16 +307,9 @@ __global__ __launch_bounds__(REPACK_BLOCK) void gru_adam_repack_kernel(float* ma
   unsigned long long t = 0;
   if (update) {
     t = *step + 1;
-    const double b1 = beta1, b2 = beta2;
-    const double c1 = 1.0 - pow(b1, (double)t), c2 = 1.0 - pow(b2, (double)t);
-    for (uint32_t p = tid; p < CPMPPI_GRU_PARAMS; p += REPACK_BLOCK) {
-      const double g = grad[p];
-      const double m = b1 * (double)mom1[p] + (1.0 - b1) * g;
-      const double v = b2 * (double)mom2[p] + (1.0 - b2) * g * g;
-      mom1[p] = (float)m;
-      mom2[p] = (float)v;
-      master[p] = (float)((double)master[p] - (double)lr * (m / c1) / (sqrt(v / c2) + (double)eps));
-    }
+    const AdamStep adam(beta1, beta2, lr, eps, t);
+    for (uint32_t p = tid; p < CPMPPI_GRU_PARAMS; p += REPACK_BLOCK)
+      master[p] = (float)adam(mom1[p], mom2[p], (double)grad[p], master[p]);
   }
   __syncthreads();                                         // the master copy is whole; every lane has read *step
   if (update && tid == 0) *step = t;
@@ -356,17 +350,10 @@ void gradient_sources(int32_t* src) {
   for (int o = 0; o < 5; ++o) put(21, o, 0);
 }
 
-bool capturing(hipStream_t s) {
-  hipStreamCaptureStatus cap = hipStreamCaptureStatusNone;
-  const bool yes = s && hipStreamIsCapturing(s, &cap) == hipSuccess && cap != hipStreamCaptureStatusNone;
-  (void)hipGetLastError();
-  return yes;
-}
-
 // The handle's training state with a workspace of `need` floats: allocated on first use, never inside a capture.
 int ensure(cpmppi_handle* h, size_t need, hipStream_t s, const char* who) {
   if (h->gru_train && h->gru_train->tables && h->gru_train->ws_floats >= need) return CPMPPI_OK;
-  if (capturing(s)) return refuse_unreserved_capture(h, s, who, "cpmppi_gru_train_reserve");
+  if (const int rc = refuse_unreserved_capture(h, s, who, "cpmppi_gru_train_reserve")) return rc;
   if (!h->gru_train) h->gru_train = new GruTrain();
   GruTrain* st = h->gru_train;
   if (!st->tables) {
@@ -393,17 +380,11 @@ int check_loss_args(cpmppi_handle* h, const cpmppi_gru_loss_args* a, bool rollou
     return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": shift_labels must be 1 (the output of a row is the input of the next), got " +
                                            std::to_string(a->shift_labels));
   if (misaligned(a->states) || misaligned(a->Q) || misaligned(a->windows) || misaligned(a->windows_host) || misaligned(a->grad_out) ||
-      (reinterpret_cast<uintptr_t>(a->loss_out) & 7u) != 0)
+      misaligned8(a->loss_out))
     return fail(h, CPMPPI_ERR_ALIGN, std::string(who) + ": misaligned pointer");
-  const uint64_t span = (uint64_t)a->wash_out + a->post_wash_out + a->shift_labels;      // rows from t0 to the last label, inclusive
-  for (uint32_t b = 0; b < a->B; ++b) {
-    const uint64_t r = a->windows_host[2 * b], t0 = a->windows_host[2 * b + 1];
-    if (r >= a->R || t0 + span > (uint64_t)a->T)
-      return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": window " + std::to_string(b) + " = (" + std::to_string(r) + ", " +
-                                             std::to_string(t0) + ") lies outside r < R, t0 + wash_out + post_wash_out - 1 + "
-                                             "shift_labels <= T - 1");
-  }
-  return CPMPPI_OK;                                        // (every window fits, so wash_out + post_wash_out <= T: no overflow below)
+  // rows from t0 to the last label, inclusive (every window fits, so wash_out + post_wash_out <= T: no overflow below)
+  return check_windows(h, who, a->windows_host, a->B, a->R, a->T, (uint64_t)a->wash_out + a->post_wash_out + a->shift_labels,
+                       "r < R, t0 + wash_out + post_wash_out - 1 + shift_labels <= T - 1");
 }
 
 // The launches of one loss (and gradient into `grad`, or NULL) on `s`, teacher-forced or through the open-loop `rollout`; the
@@ -465,8 +446,7 @@ int train_step_entry(cpmppi_handle* h, const cpmppi_gru_loss_args* a, bool rollo
                      void* stream, const char* who) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
   if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": null argument block");
-  if (!h->gru_train || !h->gru_train->begun)
-    return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": call cpmppi_gru_train_begin first");
+  if (const int rc = begun_or_refuse(h, who, h->gru_train && h->gru_train->begun, "cpmppi_gru_train_begin")) return rc;
   CPMPPI_ON_DEVICE(h);
   if (const int rc = loss_grad_impl(h, a, h->gru_train->master + 3 * (size_t)CPMPPI_GRU_PARAMS, rollout, (hipStream_t)stream, who))
     return rc;
@@ -542,8 +522,7 @@ int cpmppi_gru_rollout_train_step(cpmppi_handle* h, const cpmppi_gru_loss_args* 
 int cpmppi_gru_train_get(cpmppi_handle* h, float* params_host) {
   if (!h) return CPMPPI_ERR_BAD_ARG;
   if (!params_host) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_train_get: params_host is required");
-  if (!h->gru_train || !h->gru_train->begun)
-    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_gru_train_get: call cpmppi_gru_train_begin first");
+  if (const int rc = begun_or_refuse(h, "cpmppi_gru_train_get", h->gru_train && h->gru_train->begun, "cpmppi_gru_train_begin")) return rc;
   CPMPPI_ON_DEVICE(h);
   CPMPPI_HIP(h, hipDeviceSynchronize());
   CPMPPI_HIP(h, hipMemcpy(params_host, h->gru_train->master, (size_t)CPMPPI_GRU_PARAMS * sizeof(float), hipMemcpyDeviceToHost));

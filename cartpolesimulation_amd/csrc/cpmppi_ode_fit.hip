@@ -23,6 +23,7 @@
 #include "cpmppi_ode.hpp"
 #include "cpmppi_grad.hpp"
 #include "cpmppi_wave.hpp"
+#include "cpmppi_train.hpp"
 
 using namespace cpmppi_k;
 
@@ -284,13 +285,8 @@ __global__ __launch_bounds__(64) void ode_fit_finalize_kernel(const float* __res
   const double g = trained ? (double)pi * acc : 0.0;
   if (grad_out) grad_out[i] = g;
   if (update && trained) {
-    const double b1 = beta1, b2 = beta2;
-    const double c1 = 1.0 - pow(b1, (double)t), c2 = 1.0 - pow(b2, (double)t);
-    const double m = b1 * (double)block[BLK_M + i] + (1.0 - b1) * g;
-    const double v = b2 * (double)block[BLK_V + i] + (1.0 - b2) * g * g;
-    block[BLK_M + i] = (float)m;
-    block[BLK_V + i] = (float)v;
-    const float theta = (float)((double)block[BLK_THETA + i] - (double)lr * (m / c1) / (sqrt(v / c2) + (double)eps));
+    const AdamStep adam(beta1, beta2, lr, eps, t);
+    const float theta = (float)adam(block[BLK_M + i], block[BLK_V + i], g, block[BLK_THETA + i]);
     block[BLK_THETA + i] = theta;
     block[BLK_P + i] = (float)((double)block[BLK_BASE + i] * exp((double)theta));
   }
@@ -353,16 +349,9 @@ int check_args(cpmppi_handle* h, const cpmppi_ode_fit_args* a, const char* who) 
       return refuse(std::string("trainable parameter ") + names[i] + " has the base value " + std::to_string(b[i]) +
                     ": p = base exp(theta) needs base > 0");
   if (misaligned(a->states) || misaligned(a->Q) || misaligned(a->L) || misaligned(a->windows) || misaligned(a->windows_host) ||
-      misaligned(a->per_window_out) || (reinterpret_cast<uintptr_t>(a->loss_out) & 7u) != 0 ||
-      (reinterpret_cast<uintptr_t>(a->grad_out) & 7u) != 0)
+      misaligned(a->per_window_out) || misaligned8(a->loss_out) || misaligned8(a->grad_out))
     return fail(h, CPMPPI_ERR_ALIGN, std::string(who) + ": misaligned pointer");
-  for (uint32_t w = 0; w < a->B; ++w) {
-    const uint64_t r = a->windows_host[2 * w], t0 = a->windows_host[2 * w + 1];
-    if (r >= a->R || t0 + a->horizon > (uint64_t)a->T - 1)
-      return refuse("window " + std::to_string(w) + " = (" + std::to_string(r) + ", " + std::to_string(t0) +
-                    ") lies outside r < R, t0 + horizon <= T - 1");
-  }
-  return CPMPPI_OK;
+  return check_windows(h, who, a->windows_host, a->B, a->R, a->T, (uint64_t)a->horizon + 1, "r < R, t0 + horizon <= T - 1");
 }
 
 void launch_finalize(cpmppi_handle* h, uint32_t rows, double count, float* block, uint32_t trainable, double* loss_out,
@@ -397,8 +386,7 @@ int loss_grad_impl(cpmppi_handle* h, const cpmppi_ode_fit_args* a, double* grad,
 }
 
 int not_begun(cpmppi_handle* h, const char* who) {
-  if (h->ode_fit && h->ode_fit->begun) return CPMPPI_OK;
-  return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": call cpmppi_ode_fit_begin first");
+  return begun_or_refuse(h, who, h->ode_fit && h->ode_fit->begun, "cpmppi_ode_fit_begin");
 }
 
 // p = (float)(base exp(theta)) on the device, synchronously (cpmppi_ode_fit_begin, cpmppi_ode_fit_set_theta).

@@ -11,6 +11,7 @@ import torch
 
 from . import _lib as _L
 from .configs import MPPIConfig, PhysicalParameters, build_c_config, cost_vector
+from .model_folder import GRU_KEYS, GRU_SHAPES
 
 
 def _ptr(t):
@@ -123,6 +124,7 @@ class MPPIEngine:
     _m_pole_obj = None                                          # apply_pole_mass_of: the scalar object last applied
     _tuning = None                                              # set_tuning_rows: the registered tensor
     has_gru = False                                             # set_gru: a network is attached
+    _train_keep = _fit_keep = (None, None)                      # gru_train_step / ode_fit_step: the last two batches (_run_keeping)
 
     def __init__(self, E, mppi: MPPIConfig = None, phys: PhysicalParameters = None, device=0):
         self._init_common(E, mppi, phys, device)
@@ -544,7 +546,7 @@ class MPPIEngine:
         return self._build_plant_step(*args, **kwargs)
 
     # ------------------------------------------------------------------ GRU predictor (BASELINE configs[4])
-    GRU_KEYS = ("w_ih0", "w_hh0", "b_ih0", "b_hh0", "w_ih1", "w_hh1", "b_ih1", "b_hh1", "w_out", "b_out")
+    GRU_KEYS, GRU_SHAPES = GRU_KEYS, GRU_SHAPES                  # (model_folder's: the order of the flat parameter vector)
 
     def set_gru(self, model):
         """Attach a GRU-6IN-32H1-32H2-5OUT model: dict of float32 arrays in the torch.nn.GRU layout
@@ -559,9 +561,7 @@ class MPPIEngine:
         pre-scaled by log2(e) and 2 log2(e)) and 59999.996 in w_out.  A refused call changes nothing: the engine keeps the model
         it held - ``has_gru`` stays as it was - and a training run goes on.  FAST kernels need every normalised input and every
         fed-back output within +-65504 (beyond it they give NaN where PRECISE stays finite); nothing checks that at run time."""
-        shapes = dict(w_ih0=(96, 6), w_hh0=(96, 32), b_ih0=(96,), b_hh0=(96,), w_ih1=(96, 32), w_hh1=(96, 32),
-                      b_ih1=(96,), b_hh1=(96,), w_out=(5, 32), b_out=(5,), in_scale=(6,), in_shift=(6,),
-                      out_scale=(5,), out_shift=(5,))
+        shapes = dict(zip(GRU_KEYS, GRU_SHAPES), in_scale=(6,), in_shift=(6,), out_scale=(5,), out_shift=(5,))
         keep = {}
         for k, shp in shapes.items():
             if k in model and model[k] is not None:
@@ -693,6 +693,35 @@ class MPPIEngine:
             raise ValueError(f"trainable: a non-empty set of {', '.join(_L.ODE_FIT_NAMES)}, got {trainable!r}")
         return mask
 
+    def _window_batch(self, windows, R, T, rows_behind, rule):
+        """``windows`` [B,2] integers (r, t0) on the HOST, each with ``rows_behind`` rows behind t0 inside its recording (``rule``: the
+        caller's words for that sum) -> (the uint32 host copy the library checks, its int32 upload, B)."""
+        w = np.asarray(windows.cpu() if torch.is_tensor(windows) else windows)
+        if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] == 0 or not np.issubdtype(w.dtype, np.integer):
+            raise ValueError(f"windows must be integers [B,2] = (recording, first row) with B >= 1, got {w.dtype} {w.shape}")
+        if w.min() < 0 or w[:, 0].max() >= R or w[:, 1].max() + rows_behind > T - 1:
+            raise ValueError(f"every window (r, t0) must satisfy r < {R} and t0 + {rule} <= {T - 1}")
+        w_host = np.ascontiguousarray(w, dtype=np.uint32)
+        return w_host, torch.as_tensor(w_host.astype(np.int32)).to(self.device), w.shape[0]
+
+    def _loss_outputs(self, loss_out, grad_out, grad, n, dtype):
+        """-> (``loss_out``: float64, one element; ``grad_out``: ``dtype`` [n], None with ``grad=False``), allocated here when None."""
+        if loss_out is None:
+            loss_out = torch.empty(1, dtype=torch.float64, device=self.device)
+        elif device_tensor("loss_out", loss_out, torch.float64).numel() != 1:
+            raise ValueError("loss_out must have one element")
+        if grad and grad_out is None:
+            grad_out = torch.empty(n, dtype=dtype, device=self.device)
+        elif grad_out is not None and (not grad or device_tensor("grad_out", grad_out, dtype).shape != (n,)):
+            raise ValueError(f"grad_out must be {'float64 ' if dtype == torch.float64 else ''}[{n}] (and grad=True)")
+        return loss_out, grad_out
+
+    def _run_keeping(self, slot, call):
+        """``call.run()``, its batch held in ``slot`` beside the one of the call before: the launches read a batch after the Python
+        call returns, and a refused call must not free the batch of the launches still in flight."""
+        setattr(self, slot, (getattr(self, slot)[1], call.keep))
+        return call.run()
+
     def _ode_fit_args(self, states, Q, windows, horizon, trainable, feature_scale, L=None, loss_out=None, grad_out=None, grad=True,
                       per_window_out=None):
         """The argument block of cpmppi_ode_fit_loss_grad / cpmppi_ode_fit_step, checked: -> (block, what it points into, loss_out,
@@ -701,28 +730,14 @@ class MPPIEngine:
         horizon, mask = int(horizon), self.ode_fit_mask(trainable)
         if not 1 <= horizon <= self.H:
             raise ValueError(f"horizon must be in 1..{self.H} (the engine's mpc_horizon), got {horizon}")
-        w = np.asarray(windows.cpu() if torch.is_tensor(windows) else windows)
-        if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] == 0 or not np.issubdtype(w.dtype, np.integer):
-            raise ValueError(f"windows must be integers [B,2] = (recording, first row) with B >= 1, got {w.dtype} {w.shape}")
-        if w.min() < 0 or w[:, 0].max() >= R or w[:, 1].max() + horizon > T - 1:
-            raise ValueError(f"every window (r, t0) must satisfy r < {R} and t0 + {horizon} <= {T - 1}")
+        w_host, w_dev, B = self._window_batch(windows, R, T, horizon, horizon)
         scale = np.asarray(feature_scale, np.float32).reshape(-1)
         if scale.shape != (5,) or not np.isfinite(scale).all():
             raise ValueError("feature_scale must hold five finite numbers (angleD, angle_cos, angle_sin, position, positionD)")
         if L is not None and (mask >> _L.ODE_FIT_NAMES.index("L")) & 1:
             raise ValueError("L is trainable and L rows are given: the rows would replace the parameter")
         L = self.tensor(L, (R, T)) if L is not None else None
-        B = w.shape[0]
-        w_host = np.ascontiguousarray(w, dtype=np.uint32)
-        w_dev = torch.as_tensor(w_host.astype(np.int32)).to(self.device)
-        if loss_out is None:
-            loss_out = torch.empty(1, dtype=torch.float64, device=self.device)
-        elif device_tensor("loss_out", loss_out, torch.float64).numel() != 1:
-            raise ValueError("loss_out must have one element")
-        if grad and grad_out is None:
-            grad_out = torch.empty(_L.ODE_FIT_PARAMS, dtype=torch.float64, device=self.device)
-        elif grad_out is not None and (not grad or device_tensor("grad_out", grad_out, torch.float64).shape != (_L.ODE_FIT_PARAMS,)):
-            raise ValueError(f"grad_out must be float64 [{_L.ODE_FIT_PARAMS}] (and grad=True)")
+        loss_out, grad_out = self._loss_outputs(loss_out, grad_out, grad, _L.ODE_FIT_PARAMS, torch.float64)
         if per_window_out is not None and device_tensor("per_window_out", per_window_out, tail=(1 + _L.ODE_FIT_PARAMS,)).shape[0] != B:
             raise ValueError(f"per_window_out must be [{B},{1 + _L.ODE_FIT_PARAMS}]")
         a = _L.cpmppi_ode_fit_args()
@@ -779,9 +794,7 @@ class MPPIEngine:
 
     def ode_fit_step(self, *args, **kwargs):
         """``_build_ode_fit_step``'s call, run once: -> the batch's loss before the update."""
-        call = self._build_ode_fit_step(*args, **kwargs)
-        self._fit_keep = call.keep                    # (the launches read the batch after this call returns)
-        return call.run()
+        return self._run_keeping("_fit_keep", self._build_ode_fit_step(*args, **kwargs))
 
     def prepare_ode_fit_step(self, *args, **kwargs):
         """The argument block of ``ode_fit_step(...)`` built and validated ONCE: every ``.run()`` is one more Adam step on the same
@@ -810,23 +823,10 @@ class MPPIEngine:
             raise ValueError(f"wash_out >= 0, post_wash_out >= 1 and shift_labels >= 0, got {W}, {P}, {shift}")
         if rollout and shift != 1:
             raise ValueError(f"rollout: shift_labels must be 1 (the output of a row is the input of the next), got {shift}")
-        w = np.asarray(windows.cpu() if torch.is_tensor(windows) else windows)
-        if w.ndim != 2 or w.shape[1] != 2 or w.shape[0] == 0 or not np.issubdtype(w.dtype, np.integer):
-            raise ValueError(f"windows must be integers [B,2] = (recording, first row) with B >= 1, got {w.dtype} {w.shape}")
-        if w.min() < 0 or w[:, 0].max() >= R or w[:, 1].max() + W + P - 1 + shift > T - 1:
-            raise ValueError(f"every window (r, t0) must satisfy r < {R} and t0 + {W} + {P} - 1 + {shift} <= {T - 1}")
-        w_host = np.ascontiguousarray(w, dtype=np.uint32)
-        w_dev = torch.as_tensor(w_host.astype(np.int32)).to(self.device)
-        if loss_out is None:
-            loss_out = torch.empty(1, dtype=torch.float64, device=self.device)
-        elif device_tensor("loss_out", loss_out, torch.float64).numel() != 1:
-            raise ValueError("loss_out must have one element")
-        if grad and grad_out is None:
-            grad_out = self.empty(_L.GRU_PARAMS)
-        elif grad_out is not None and (not grad or device_tensor("grad_out", grad_out).shape != (_L.GRU_PARAMS,)):
-            raise ValueError(f"grad_out must be [{_L.GRU_PARAMS}] (and grad=True)")
+        w_host, w_dev, B = self._window_batch(windows, R, T, W + P - 1 + shift, f"{W} + {P} - 1 + {shift}")
+        loss_out, grad_out = self._loss_outputs(loss_out, grad_out, grad, _L.GRU_PARAMS, torch.float32)
         a = _L.cpmppi_gru_loss_args()
-        a.B, a.R, a.T, a.wash_out, a.post_wash_out, a.shift_labels = w.shape[0], R, T, W, P, shift
+        a.B, a.R, a.T, a.wash_out, a.post_wash_out, a.shift_labels = B, R, T, W, P, shift
         a.states, a.Q, a.windows, a.windows_host = states.data_ptr(), Q.data_ptr(), w_dev.data_ptr(), w_host.ctypes.data
         a.loss_out, a.grad_out = loss_out.data_ptr(), _addr(grad_out)
         return a, (states, Q, w_dev, w_host, loss_out, grad_out), loss_out, grad_out
@@ -865,17 +865,20 @@ class MPPIEngine:
             raise ValueError("no model set: call set_gru first")
         self._check(self.lib.cpmppi_gru_train_begin(self._h))
 
-    def gru_train_step(self, states, Q, windows, wash_out, post_wash_out, shift_labels=1, *, lr, beta1=0.9, beta2=0.999,
-                       eps=1e-8, loss_out=None, rollout=False):
+    def _build_gru_train_step(self, states, Q, windows, wash_out, post_wash_out, shift_labels=1, *, lr, beta1=0.9, beta2=0.999,
+                              eps=1e-8, loss_out=None, rollout=False):
         """cpmppi_gru_train_step (``rollout``: cpmppi_gru_rollout_train_step): the loss and gradient of ``gru_loss_grad`` over this
         batch of ``windows``, one Adam update of the master copy and the rebuild of the exact-f32 weight images, all on the device.
         Steps of both kinds may alternate.  -> the batch's loss BEFORE the update, [1] float64 on the device."""
         a, keep, loss_out, _ = self._gru_loss_args(states, Q, windows, wash_out, post_wash_out, shift_labels, loss_out, None, False,
                                                    rollout)
         fn = self.lib.cpmppi_gru_rollout_train_step if rollout else self.lib.cpmppi_gru_train_step
-        self._check(fn(self._h, C.byref(a), float(lr), float(beta1), float(beta2), float(eps), self._stream()))
-        self._train_keep = keep                       # (the launches read the batch after this call returns)
-        return loss_out
+        hyper = (float(lr), float(beta1), float(beta2), float(eps))
+        return PreparedCall(self, lambda h, ref, stream: fn(h, ref, *hyper, stream), a, keep, loss_out, ())
+
+    def gru_train_step(self, *args, **kwargs):
+        """``_build_gru_train_step``'s call, run once: -> the batch's loss before the update."""
+        return self._run_keeping("_train_keep", self._build_gru_train_step(*args, **kwargs))
 
     def gru_train_get(self):
         """cpmppi_gru_train_get: the trained weights as the dict ``set_gru`` takes (weights only; the normalisation is the
@@ -883,8 +886,6 @@ class MPPIEngine:
         flat = np.empty(_L.GRU_PARAMS, np.float32)
         self._check(self.lib.cpmppi_gru_train_get(self._h, flat.ctypes.data_as(C.POINTER(C.c_float))))
         return self.gru_unflatten(flat)
-
-    GRU_SHAPES = ((96, 6), (96, 32), (96,), (96,), (96, 32), (96, 32), (96,), (96,), (5, 32), (5,))
 
     @classmethod
     def gru_unflatten(cls, flat):

@@ -35,8 +35,9 @@ import numpy as np
 
 from ._lib import ODE_FIT_NAMES
 from .configs import PhysicalParameters
-from .train_gru import (load_recordings_folder, make_windows, normalization_from_recordings, plateau_rule,
-                        refuse_unbuilt_sections)
+from ._training import (check_recordings, load_recordings_folder, make_windows, plateau_rule,  # noqa: F401  (and re-exported)
+                        refuse_unbuilt_sections, run_epochs, schedule_settings)
+from .train_gru import normalization_from_recordings
 
 f32 = np.float32
 NET_NAME = "Custom-ODE_module-ODEModel"
@@ -60,18 +61,8 @@ def fit_ode(engine, states, Q, lengths=None, *, trainable=("u_max",), horizon, e
     states windows, loss, parametrisation and schedule.
     -> (the engine's PhysicalParameters with the fitted values; history = dict(loss, val_loss, lr: one entry per epoch, batch_loss:
     every step's loss in order, theta, parameters: the final values by name))."""
-    import torch
-    states, Q = np.ascontiguousarray(states, f32), np.ascontiguousarray(Q, f32)
-    if states.ndim != 3 or states.shape[2] != 6 or Q.shape != states.shape[:2]:
-        raise ValueError(f"states must be [R,T,6] and Q [R,T], got {states.shape} and {Q.shape}")
-    R, T = Q.shape
-    lengths = np.full(R, T) if lengths is None else np.asarray(lengths).reshape(-1)
-    if lengths.shape != (R,) or lengths.min() < 0 or lengths.max() > T:
-        raise ValueError(f"lengths must hold one length 0..{T} per recording ({R})")
-    epochs, batch_size, horizon = int(epochs), int(batch_size), int(horizon)
-    if epochs < 1 or batch_size < 1:
-        raise ValueError("epochs and batch_size must be at least 1")
-    mask = engine.ode_fit_mask(trainable)
+    states, Q, lengths, epochs, batch_size = check_recordings(states, Q, lengths, epochs, batch_size)
+    horizon, mask = int(horizon), engine.ode_fit_mask(trainable)
     windows = make_windows(lengths, 0, horizon, 1)
     if len(windows) == 0:
         raise ValueError(f"no recording holds a window of a start row and {horizon} rows after it")
@@ -79,8 +70,8 @@ def fit_ode(engine, states, Q, lengths=None, *, trainable=("u_max",), horizon, e
         feature_scale = normalization_from_recordings(states, Q, lengths)["in_scale"][1:]
     scale = np.asarray(feature_scale, f32).reshape(-1)
     s_dev, q_dev = engine.tensor(states), engine.tensor(Q)
-    l_dev = engine.tensor(L, (R, T)) if L is not None else None
-    val = None
+    l_dev = engine.tensor(L, Q.shape) if L is not None else None
+    loss_of = vw = None
     if validation is not None:
         vs, vq = np.ascontiguousarray(validation[0], f32), np.ascontiguousarray(validation[1], f32)
         vl = validation[2] if len(validation) > 2 and validation[2] is not None else np.full(vq.shape[0], vq.shape[1])
@@ -89,44 +80,17 @@ def fit_ode(engine, states, Q, lengths=None, *, trainable=("u_max",), horizon, e
             raise ValueError("the validation recordings hold no window")
         if L is not None:
             raise ValueError("validation with L rows is not built: validate with the pole length as a parameter")
-        val = engine.tensor(vs), engine.tensor(vq), vw
+        vs, vq = engine.tensor(vs), engine.tensor(vq)
+        loss_of = lambda w: engine.ode_fit_loss_grad(vs, vq, w, horizon, mask, scale, grad=False)[0]  # noqa: E731
     engine.ode_fit_begin()
 
-    def validate():
-        total, losses, sizes = 0.0, [], []
-        for i in range(0, len(val[2]), int(validation_batch)):
-            w = val[2][i:i + int(validation_batch)]
-            loss, _ = engine.ode_fit_loss_grad(val[0], val[1], w, horizon, mask, scale, grad=False)
-            losses.append(loss)
-            sizes.append(len(w))
-        for loss, n in zip(torch.cat(losses).cpu().numpy(), sizes):
-            total += float(loss) * n
-        return total / len(val[2])
+    def step(batch, rate, loss_out, _):
+        engine.ode_fit_step(s_dev, q_dev, batch, horizon, mask, scale, l_dev, lr=rate, beta1=beta1, beta2=beta2, eps=eps,
+                            loss_out=loss_out)
 
-    rng = np.random.default_rng(seed)
-    rate, best, wait = float(lr), np.inf, 0
-    history = dict(loss=[], val_loss=[], lr=[], batch_loss=[])
-    for epoch in range(epochs):
-        order = rng.permutation(len(windows))
-        steps = -(-len(order) // batch_size)
-        losses = torch.empty(steps, dtype=torch.float64, device=engine.device)
-        for i in range(steps):
-            batch = windows[order[i * batch_size:(i + 1) * batch_size]]
-            engine.ode_fit_step(s_dev, q_dev, batch, horizon, mask, scale, l_dev, lr=rate, beta1=beta1, beta2=beta2, eps=eps,
-                                loss_out=losses[i:i + 1])
-        batch_loss = losses.cpu().numpy()
-        history["batch_loss"] += [float(x) for x in batch_loss]
-        history["loss"].append(float(batch_loss.mean()))
-        history["lr"].append(rate)
-        monitored = history["loss"][-1]
-        if val is not None:
-            history["val_loss"].append(validate())
-            monitored = history["val_loss"][-1]
-        if log is not None:
-            log(f"epoch {epoch + 1}/{epochs}: loss {history['loss'][-1]:.6e}"
-                + (f", val_loss {history['val_loss'][-1]:.6e}" if val is not None else "") + f", lr {rate:.3e}")
-        best, wait, rate = plateau_rule(monitored, best, wait, rate, reduce_lr_on_plateau, patience, decrease_factor, minimal_lr,
-                                        min_delta)
+    history, _ = run_epochs(
+        engine.device, lambda epoch: (windows, None), step, loss_of, vw, epochs=epochs, batch_size=batch_size, seed=seed, lr=lr, log=log,
+        plateau=(reduce_lr_on_plateau, patience, decrease_factor, minimal_lr, min_delta), validation_batch=validation_batch)
     p, theta = engine.ode_fit_get()
     history["theta"] = {n: float(v) for n, v in zip(ODE_FIT_NAMES, theta)}
     history["parameters"] = {n: float(v) for n, v in zip(ODE_FIT_NAMES, p)}
@@ -181,11 +145,7 @@ def fit_settings(config, net=None, feature_scale=None, **overrides):
         raise ValueError("training_default.NORMALIZE is off and no feature_scale is given: the loss weighs the five features by the "
                          "min-max scale of the recordings (NORMALIZE) or by an explicit --feature-scale")
     refuse_unbuilt_sections(config)
-    lr = t.get("LR") or {}
-    out = dict(epochs=t.get("EPOCHS", 30), batch_size=t.get("BATCH_SIZE", 64), seed=t.get("SEED", 0), lr=lr.get("INITIAL", 2e-3),
-               reduce_lr_on_plateau=bool(lr.get("REDUCE_LR_ON_PLATEAU", True)), patience=lr.get("PATIENCE", 2),
-               decrease_factor=lr.get("DECREASE_FACTOR", 0.5), minimal_lr=lr.get("MINIMAL", 1e-7), min_delta=lr.get("MIN_DELTA", 1e-6),
-               horizon=t.get("POST_WASH_OUT_LEN", 1), feature_scale=feature_scale)
+    out = dict(schedule_settings(config), horizon=t.get("POST_WASH_OUT_LEN", 1), feature_scale=feature_scale)
     out.update({k: v for k, v in overrides.items() if v is not None})
     if int(out["horizon"]) < 1:
         raise ValueError(f"horizon (POST_WASH_OUT_LEN) must be at least 1, got {out['horizon']}")

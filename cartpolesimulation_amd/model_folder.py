@@ -25,6 +25,9 @@ import numpy as np
 # the kernel's fixed feature order (cpmppi_gru.hpp): inputs and outputs of GRU-6IN-32H1-32H2-5OUT
 KERNEL_INPUTS = ("Q", "angleD", "angle_cos", "angle_sin", "position", "positionD")
 KERNEL_OUTPUTS = ("angleD", "angle_cos", "angle_sin", "position", "positionD")
+# its weights in the torch.nn.GRU layout: the keys of ``MPPIEngine.set_gru``, in the order of the flat parameter vector [10341]
+GRU_KEYS = ("w_ih0", "w_hh0", "b_ih0", "b_hh0", "w_ih1", "w_hh1", "b_ih1", "b_hh1", "w_out", "b_out")
+GRU_SHAPES = ((96, 6), (96, 32), (96,), (96,), (96, 32), (96, 32), (96,), (96,), (5, 32), (5,))
 
 
 def read_net_info(folder):

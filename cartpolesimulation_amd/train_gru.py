@@ -36,29 +36,15 @@ import os
 
 import numpy as np
 
-from .model_folder import KERNEL_INPUTS, KERNEL_OUTPUTS
+from ._training import (check_recordings, load_recordings_folder, make_windows, plateau_rule,  # noqa: F401  (and re-exported)
+                        refuse_unbuilt_sections, run_epochs, schedule_settings)
+from .model_folder import GRU_KEYS, GRU_SHAPES, KERNEL_INPUTS, KERNEL_OUTPUTS
 
 f32 = np.float32
 NET_NAME = "GRU-32H1-32H2"
-GRU_KEYS = ("w_ih0", "w_hh0", "b_ih0", "b_hh0", "w_ih1", "w_hh1", "b_ih1", "b_hh1", "w_out", "b_out")
-GRU_SHAPES = ((96, 6), (96, 32), (96,), (96,), (96, 32), (96, 32), (96,), (96,), (5, 32), (5,))
 NORM_KEYS = ("in_scale", "in_shift", "out_scale", "out_shift")
 # column of states [.., 6] = (angle, angleD, angle_cos, angle_sin, position, positionD) of every output feature
 _STATE_COLUMNS = (1, 2, 3, 4, 5)
-
-
-def make_windows(lengths, wash_out, post_wash_out, shift_labels=1):
-    """Every legal window (r, t0) of recordings with ``lengths`` rows: t0 + wash_out + post_wash_out - 1 + shift_labels <= length - 1.
-    -> int64 [n,2], recordings in order and t0 ascending; a recording too short for one window has none."""
-    W, P, shift = int(wash_out), int(post_wash_out), int(shift_labels)
-    if W < 0 or P < 1 or shift < 0:
-        raise ValueError(f"wash_out >= 0, post_wash_out >= 1 and shift_labels >= 0, got {W}, {P}, {shift}")
-    out = []
-    for r, n in enumerate(np.asarray(lengths).reshape(-1)):
-        starts = int(n) - (W + P - 1 + shift)
-        if starts > 0:
-            out.append(np.stack([np.full(starts, r, np.int64), np.arange(starts, dtype=np.int64)], axis=1))
-    return np.concatenate(out) if out else np.zeros((0, 2), np.int64)
 
 
 def normalization_from_recordings(states, Q, lengths=None):
@@ -112,19 +98,6 @@ def horizon_of_epoch(schedule, epoch):
     return schedule[min(int(epoch), len(schedule) - 1)]
 
 
-def plateau_rule(monitored, best, wait, rate, reduce_lr_on_plateau, patience, decrease_factor, minimal_lr, min_delta):
-    """``LR.REDUCE_LR_ON_PLATEAU`` after one epoch (shared with fit_ode): an improvement of the monitored loss by more than
-    ``min_delta`` resets the wait; otherwise, with the rule on, ``patience`` such epochs multiply the rate by ``decrease_factor``
-    (not below ``minimal_lr``).  -> (best, wait, rate)."""
-    if monitored < best - float(min_delta):
-        return monitored, 0, rate
-    if reduce_lr_on_plateau:
-        wait += 1
-        if wait >= int(patience):
-            rate, wait = max(rate * float(decrease_factor), float(minimal_lr)), 0
-    return best, wait, rate
-
-
 def _check_model(model):
     for key, shp in zip(GRU_KEYS, GRU_SHAPES):
         if key not in model or np.shape(model[key]) != shp:
@@ -148,17 +121,7 @@ def train_gru(engine, states, Q, lengths=None, *, epochs, batch_size, lr, seed, 
     if rollout and int(shift_labels) != 1:
         raise ValueError(f"rollout: shift_labels must be 1 (the output of a row is the input of the next), got {shift_labels}")
     schedule = horizon_schedule(post_wash_out)
-    import torch
-    states, Q = np.ascontiguousarray(states, f32), np.ascontiguousarray(Q, f32)
-    if states.ndim != 3 or states.shape[2] != 6 or Q.shape != states.shape[:2]:
-        raise ValueError(f"states must be [R,T,6] and Q [R,T], got {states.shape} and {Q.shape}")
-    R, T = Q.shape
-    lengths = np.full(R, T) if lengths is None else np.asarray(lengths).reshape(-1)
-    if lengths.shape != (R,) or lengths.min() < 0 or lengths.max() > T:
-        raise ValueError(f"lengths must hold one length 0..{T} per recording ({R})")
-    epochs, batch_size = int(epochs), int(batch_size)
-    if epochs < 1 or batch_size < 1:
-        raise ValueError("epochs and batch_size must be at least 1")
+    states, Q, lengths, epochs, batch_size = check_recordings(states, Q, lengths, epochs, batch_size)
     by_horizon = {p: make_windows(lengths, wash_out, p, shift_labels) for p in sorted(set(schedule[:epochs]))}
     for p, w in by_horizon.items():
         if len(w) == 0:
@@ -172,56 +135,29 @@ def train_gru(engine, states, Q, lengths=None, *, epochs, batch_size, lr, seed, 
     engine.set_gru(model)
     engine.gru_train_begin()
     s_dev, q_dev = engine.tensor(states), engine.tensor(Q)
-    val = None
+    loss_of = vw = None
     if validation is not None:
         vs, vq = np.ascontiguousarray(validation[0], f32), np.ascontiguousarray(validation[1], f32)
         vl = validation[2] if len(validation) > 2 and validation[2] is not None else np.full(vq.shape[0], vq.shape[1])
         vw = make_windows(vl, wash_out, schedule[-1], shift_labels)
         if len(vw) == 0:
             raise ValueError("the validation recordings hold no window")
-        val = engine.tensor(vs), engine.tensor(vq), vw
+        vs, vq = engine.tensor(vs), engine.tensor(vq)
+        loss_of = lambda w: engine.gru_loss_grad(vs, vq, w, wash_out, schedule[-1], shift_labels, grad=False,  # noqa: E731
+                                                 rollout=rollout)[0]
     if len(schedule) > 1:
-        widest = max(batch_size, min(int(validation_batch), len(val[2])) if val is not None else 0)
+        widest = max(batch_size, min(int(validation_batch), len(vw)) if vw is not None else 0)
         engine.gru_train_reserve(widest, int(wash_out) + max(schedule))
 
-    def validate():
-        total, losses, sizes = 0.0, [], []
-        for i in range(0, len(val[2]), int(validation_batch)):
-            w = val[2][i:i + int(validation_batch)]
-            loss, _ = engine.gru_loss_grad(val[0], val[1], w, wash_out, schedule[-1], shift_labels, grad=False, rollout=rollout)
-            losses.append(loss)
-            sizes.append(len(w))
-        for loss, n in zip(torch.cat(losses).cpu().numpy(), sizes):
-            total += float(loss) * n
-        return total / len(val[2])
+    def step(batch, rate, loss_out, horizon):
+        engine.gru_train_step(s_dev, q_dev, batch, wash_out, horizon, shift_labels, lr=rate, beta1=beta1, beta2=beta2, eps=eps,
+                              loss_out=loss_out, rollout=rollout)
 
-    rng = np.random.default_rng(seed)
-    rate, best, wait = float(lr), np.inf, 0
-    history = dict(loss=[], val_loss=[], lr=[], batch_loss=[], post_wash_out=[])
-    for epoch in range(epochs):
-        horizon = horizon_of_epoch(schedule, epoch)
-        windows = by_horizon[horizon]
-        order = rng.permutation(len(windows))
-        steps = -(-len(order) // batch_size)
-        losses = torch.empty(steps, dtype=torch.float64, device=engine.device)
-        for i in range(steps):
-            batch = windows[order[i * batch_size:(i + 1) * batch_size]]
-            engine.gru_train_step(s_dev, q_dev, batch, wash_out, horizon, shift_labels, lr=rate, beta1=beta1, beta2=beta2,
-                                  eps=eps, loss_out=losses[i:i + 1], rollout=rollout)
-        batch_loss = losses.cpu().numpy()
-        history["batch_loss"] += [float(x) for x in batch_loss]
-        history["loss"].append(float(batch_loss.mean()))
-        history["lr"].append(rate)
-        history["post_wash_out"].append(horizon)
-        monitored = history["loss"][-1]
-        if val is not None:
-            history["val_loss"].append(validate())
-            monitored = history["val_loss"][-1]
-        if log is not None:
-            log(f"epoch {epoch + 1}/{epochs}: loss {history['loss'][-1]:.6e}"
-                + (f", val_loss {history['val_loss'][-1]:.6e}" if val is not None else "") + f", lr {rate:.3e}")
-        best, wait, rate = plateau_rule(monitored, best, wait, rate, reduce_lr_on_plateau, patience, decrease_factor, minimal_lr,
-                                        min_delta)
+    per_epoch = [(by_horizon[p], p) for p in (horizon_of_epoch(schedule, epoch) for epoch in range(epochs))]
+    history, horizons = run_epochs(
+        engine.device, per_epoch.__getitem__, step, loss_of, vw, epochs=epochs, batch_size=batch_size, seed=seed, lr=lr, log=log,
+        plateau=(reduce_lr_on_plateau, patience, decrease_factor, minimal_lr, min_delta), validation_batch=validation_batch)
+    history["post_wash_out"] = horizons
     trained = {**engine.gru_train_get(), **norm}
     engine.set_gru(trained)            # (the rollout kernels' split-f16 image is built, and range-checked, on the host)
     return trained, history
@@ -260,25 +196,6 @@ def write_model_folder(folder, model, name=None, info=None):
 _DYNAMICS = dict(control_inputs=["Q"], state_inputs=list(KERNEL_INPUTS[1:]), outputs=list(KERNEL_OUTPUTS))
 
 
-def refuse_unbuilt_sections(config):
-    """The keys of config_training.yml that neither trainer of this package (train_gru, fit_ode) is built for, refused by name
-    where they are activated: on-the-fly data generation, NNI, regularisation, quantisation, pruning, series modification, filters."""
-    t = dict(config.get("training_default") or {})
-    if t.get("ON_FLY_DATA_GENERATION"):
-        raise ValueError("training_default.ON_FLY_DATA_GENERATION: not built (generate recordings first: generate_dataset)")
-    if t.get("USE_NNI"):
-        raise ValueError("training_default.USE_NNI: not built")
-    for section in ("REGULARIZATION", "QUANTIZATION", "PRUNING"):
-        if (config.get(section) or {}).get("ACTIVATED"):
-            raise ValueError(f"{section}.ACTIVATED: not built (the loss is the mean squared error alone, the weights float32)")
-    mode = (config.get("CONFIG_SERIES_MODIFICATION") or {}).get("MODE")
-    noise = ((config.get("CONFIG_SERIES_MODIFICATION") or {}).get("NOISE_LEVEL") or {}).get("FEATURES", 0.0)
-    if (mode not in (None, "None")) or noise:
-        raise ValueError(f"CONFIG_SERIES_MODIFICATION (MODE {mode!r}, NOISE_LEVEL.FEATURES {noise}): not built")
-    if config.get("FILTERS"):
-        raise ValueError("FILTERS: not built (filter the recordings before training)")
-
-
 def training_settings(config, net=None, dynamics_model=False, **overrides):
     """config_training.yml as a dict -> the keyword arguments of ``train_gru`` (EPOCHS, BATCH_SIZE, SEED, LR.*, WASH_OUT_LEN,
     POST_WASH_OUT_LEN, SHIFT_LABELS; ``overrides``: the same by ``train_gru``'s names, None = the file's) and ``normalize``.  What the
@@ -299,11 +216,8 @@ def training_settings(config, net=None, dynamics_model=False, **overrides):
         if t.get(key):
             raise ValueError(f"training_default.{key} = {t[key]}: not built (the dynamics model has none)")
     refuse_unbuilt_sections(config)
-    lr = t.get("LR") or {}
-    out = dict(epochs=t.get("EPOCHS", 30), batch_size=t.get("BATCH_SIZE", 64), seed=t.get("SEED", 0), lr=lr.get("INITIAL", 2e-3),
-               reduce_lr_on_plateau=bool(lr.get("REDUCE_LR_ON_PLATEAU", True)), patience=lr.get("PATIENCE", 2),
-               decrease_factor=lr.get("DECREASE_FACTOR", 0.5), minimal_lr=lr.get("MINIMAL", 1e-7), min_delta=lr.get("MIN_DELTA", 1e-6),
-               wash_out=t.get("WASH_OUT_LEN", 0), post_wash_out=t.get("POST_WASH_OUT_LEN", 1), shift_labels=t.get("SHIFT_LABELS", 1))
+    out = dict(schedule_settings(config), wash_out=t.get("WASH_OUT_LEN", 0), post_wash_out=t.get("POST_WASH_OUT_LEN", 1),
+               shift_labels=t.get("SHIFT_LABELS", 1))
     out.update({k: v for k, v in overrides.items() if v is not None})
     if int(out["shift_labels"]) == 0:
         raise ValueError("SHIFT_LABELS 0 with the dynamics model's features trains the identity map (the shipped value belongs to the "
@@ -339,22 +253,6 @@ def run_settings(settings, normalize, rollout=False, schedule=None, init_folder=
     if init_folder is not None:
         info["PARENT NET"] = os.path.abspath(os.fspath(init_folder))
     return settings, init, info
-
-
-def load_recordings_folder(folder):
-    """Every recording CSV of ``folder`` (``brunton.load_recording``) -> (states [R,T,6], Q [R,T] padded with zeros to the longest,
-    lengths [R], the file names)."""
-    from .brunton import FEATURES, load_recording
-    names = sorted(n for n in os.listdir(folder) if n.endswith(".csv"))
-    if not names:
-        raise ValueError(f"{folder}: no recording (*.csv)")
-    cols = [load_recording(os.path.join(folder, n)) for n in names]
-    lengths = np.array([len(c["Q"]) for c in cols])
-    states, Q = np.zeros((len(cols), lengths.max(), 6), f32), np.zeros((len(cols), lengths.max()), f32)
-    for r, c in enumerate(cols):
-        states[r, :lengths[r]] = np.stack([c[f] for f in FEATURES], axis=-1)
-        Q[r, :lengths[r]] = c["Q"]
-    return states, Q, lengths, names
 
 
 def main(argv=None):
