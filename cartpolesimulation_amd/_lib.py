@@ -36,7 +36,10 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_gru_train_reserve", "cpmppi_gru_loss_grad", "cpmppi_gru_train_begin", "cpmppi_gru_train_step",
            "cpmppi_gru_train_get", "cpmppi_gru_rollout_loss_grad", "cpmppi_gru_rollout_train_step",
            "cpmppi_ode_fit_reserve", "cpmppi_ode_fit_loss_grad", "cpmppi_ode_fit_begin", "cpmppi_ode_fit_set_theta",
-           "cpmppi_ode_fit_step", "cpmppi_ode_fit_get")
+           "cpmppi_ode_fit_step", "cpmppi_ode_fit_get",
+           "cpmppi_set_dense", "cpmppi_dense_control", "cpmppi_dense_train_reserve", "cpmppi_dense_loss_grad",
+           "cpmppi_dense_train_begin", "cpmppi_dense_train_step", "cpmppi_dense_train_get")
+DENSE_PARAMS = 1345                                  # CPMPPI_DENSE_PARAMS: the flat parameter vector of the neural imitator
 ODE_FIT_PARAMS = 8                                   # CPMPPI_ODE_FIT_PARAMS, in this order (bit i of a `trainable` mask)
 ODE_FIT_NAMES = ("k", "m_cart", "m_pole", "g", "J_fric", "M_fric", "u_max", "L")
 GRU_PARAMS = 10341                                   # CPMPPI_GRU_PARAMS: the flat parameter vector of the training entry points
@@ -131,6 +134,23 @@ class cpmppi_ode_fit_args(C.Structure):
     _fields_ = [("B", C.c_uint32), ("R", C.c_uint32), ("T", C.c_uint32), ("horizon", C.c_uint32), ("trainable", C.c_uint32),
                 ("states", C.c_void_p), ("Q", C.c_void_p), ("L", C.c_void_p), ("windows", C.c_void_p), ("windows_host", C.c_void_p),
                 ("feature_scale", C.c_float * 5), ("loss_out", C.c_void_p), ("grad_out", C.c_void_p), ("per_window_out", C.c_void_p)]
+
+
+class cpmppi_dense_model(C.Structure):
+    _FP = C.POINTER(C.c_float)
+    _fields_ = [("w1", _FP), ("b1", _FP), ("w2", _FP), ("b2", _FP), ("w3", _FP), ("b3", _FP),
+                ("in_scale", _FP), ("in_shift", _FP), ("out_scale", _FP), ("out_shift", _FP)]
+
+
+class cpmppi_dense_control_args(C.Structure):
+    _fields_ = [("E", C.c_uint32), ("s", C.c_void_p), ("target_position", C.c_void_p), ("target_equilibrium", C.c_void_p),
+                ("Q_out", C.c_void_p), ("y_out", C.c_void_p), ("count_dev", C.c_void_p)]
+
+
+class cpmppi_dense_loss_args(C.Structure):
+    _fields_ = [("B", C.c_uint32), ("R", C.c_uint32), ("T", C.c_uint32), ("post_wash_out", C.c_uint32), ("shift_labels", C.c_uint32),
+                ("states", C.c_void_p), ("target_position", C.c_void_p), ("target_equilibrium", C.c_void_p), ("labels", C.c_void_p),
+                ("windows", C.c_void_p), ("windows_host", C.c_void_p), ("loss_out", C.c_void_p), ("grad_out", C.c_void_p)]
 
 
 class cpmppi_score_args(C.Structure):
@@ -280,6 +300,13 @@ def load():
     lib.cpmppi_ode_fit_set_theta.argtypes = [vp, C.POINTER(f)]
     lib.cpmppi_ode_fit_step.argtypes = [vp, C.POINTER(cpmppi_ode_fit_args), f, f, f, f, vp]
     lib.cpmppi_ode_fit_get.argtypes = [vp, C.POINTER(f), C.POINTER(f)]
+    lib.cpmppi_set_dense.argtypes = [vp, C.POINTER(cpmppi_dense_model)]
+    lib.cpmppi_dense_control.argtypes = [vp, C.POINTER(cpmppi_dense_control_args), vp]
+    lib.cpmppi_dense_train_reserve.argtypes = [vp, u32]
+    lib.cpmppi_dense_loss_grad.argtypes = [vp, C.POINTER(cpmppi_dense_loss_args), vp]
+    lib.cpmppi_dense_train_begin.argtypes = [vp]
+    lib.cpmppi_dense_train_step.argtypes = [vp, C.POINTER(cpmppi_dense_loss_args), f, f, f, f, vp]
+    lib.cpmppi_dense_train_get.argtypes = [vp, C.POINTER(f)]
     lib.cpmppi_cem_sample.argtypes = [vp, u32, vp, vp, u64, u64, u32, vp, vp]
     lib.cpmppi_cem_update.argtypes = [vp, u32, vp, vp, u32, f, vp, vp, vp, vp]
     lib.cpmppi_tiled_floats.argtypes = [vp, u32]

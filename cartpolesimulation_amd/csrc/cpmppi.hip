@@ -471,6 +471,7 @@ void cpmppi_destroy(cpmppi_handle* h) {
   if (h->gru_grad_ws) (void)hipFree(h->gru_grad_ws);
   gru_train_destroy(h);
   ode_fit_destroy(h);
+  dense_destroy(h);
   if (h->brunton_ws) (void)hipFree(h->brunton_ws);
   if (h->grad_ckpt) (void)hipFree(h->grad_ckpt);
   if (h->rpgd_ws) (void)hipFree(h->rpgd_ws);

@@ -18,6 +18,8 @@
 //                         (cpmppi_gru_loss_grad, cpmppi_gru_train_*)
 //   cpmppi_ode_fit.hip    fitting the ODE predictor's physical parameters to recordings: open-loop loss, forward-mode gradient, Adam
 //                         on the device (cpmppi_ode_fit_*)
+//   cpmppi_dense.hip      the neural imitator (Dense-7IN-32H1-32H2-1OUT): the control kernel, loss and gradient over recordings with the
+//                         batch contraction on MFMA, Adam on the device (cpmppi_set_dense, cpmppi_dense_*)
 //   cpmppi_gru_model.hip  host code only: cpmppi_set_gru packs and uploads the three weight images
 //   cpmppi_comm.hip, cpmppi_groups.hip, cpmppi_io.hip   host code only: the collective, env groups, the recording writer
 //   cpmppi_rollout_*.hip  the instances of rollout_cost_kernel, each unit with its own compiler flags
@@ -111,6 +113,7 @@ struct cpmppi_handle {
   std::vector<float> gru_params;       // the weights of the last cpmppi_set_gru in the flat order of CPMPPI_GRU_PARAMS (cpmppi_gru_train_begin)
   struct GruTrain* gru_train = nullptr;  // training on recordings (cpmppi_gru_train.hip): workspace, master copy, moments; or none yet
   struct OdeFit* ode_fit = nullptr;    // fitting the physical parameters (cpmppi_ode_fit.hip): partial rows, parameter block, Adam state; or none yet
+  struct DenseNet* dense = nullptr;    // the neural imitator (cpmppi_dense.hip): parameter vector, normalisation, partial rows, Adam state; or none yet
   bool fuse_finalize = true;           // ODE path: the env's last block finalizes in-kernel (CPMPPI_FUSE_FINALIZE=0 disables)
   uint32_t profile_every = 0;          // 0 = off, 1 = every rollout kernel bracketed, n > 1 = one bracket around n steps
   uint32_t profile_count = 0;
@@ -259,6 +262,8 @@ void gru_train_destroy(cpmppi_handle* h);
 void gru_train_end(cpmppi_handle* h);
 // cpmppi_ode_fit.hip: frees what a fit of the physical parameters allocated (cpmppi_destroy)
 void ode_fit_destroy(cpmppi_handle* h);
+// cpmppi_dense.hip: frees what the neural imitator allocated (cpmppi_destroy)
+void dense_destroy(cpmppi_handle* h);
 // cpmppi_gru_seam.hip: the Brunton test's GRU kernel (one partial row per wave of 32 starts: brunton_gru_rows of them); the caller
 // has checked the arguments, checks the launch and reduces the partial rows
 inline size_t brunton_gru_rows(size_t starts) { return (starts + 31) / 32; }

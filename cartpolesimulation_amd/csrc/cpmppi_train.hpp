@@ -1,5 +1,5 @@
-// cpmppi_train.hpp — what the two training units share (cpmppi_gru_train.hip, cpmppi_ode_fit.hip; nothing else includes it): Adam's
-// update, the host check of a batch of windows, and the two refusals both word alike.
+// cpmppi_train.hpp — what the three training units share (cpmppi_gru_train.hip, cpmppi_ode_fit.hip, cpmppi_dense.hip; nothing else includes it): Adam's
+// update, the host check of a batch of windows, and the two refusals they word alike.
 #pragma once
 #include <math.h>
 #include "cpmppi_internal.hpp"

@@ -11,7 +11,7 @@ import torch
 
 from . import _lib as _L
 from .configs import MPPIConfig, PhysicalParameters, build_c_config, cost_vector
-from .model_folder import GRU_KEYS, GRU_SHAPES
+from .model_folder import DENSE_KEYS, DENSE_SHAPES, GRU_KEYS, GRU_SHAPES
 
 
 def _ptr(t):
@@ -124,7 +124,8 @@ class MPPIEngine:
     _m_pole_obj = None                                          # apply_pole_mass_of: the scalar object last applied
     _tuning = None                                              # set_tuning_rows: the registered tensor
     has_gru = False                                             # set_gru: a network is attached
-    _train_keep = _fit_keep = (None, None)                      # gru_train_step / ode_fit_step: the last two batches (_run_keeping)
+    has_dense = False                                           # set_dense: the neural imitator is attached
+    _train_keep = _fit_keep = _dense_keep = (None, None)        # gru_train_step / ode_fit_step / dense_train_step: the last two batches (_run_keeping)
 
     def __init__(self, E, mppi: MPPIConfig = None, phys: PhysicalParameters = None, device=0):
         self._init_common(E, mppi, phys, device)
@@ -809,6 +810,155 @@ class MPPIEngine:
         self._check(self.lib.cpmppi_ode_fit_get(self._h, p.ctypes.data_as(fp), theta.ctypes.data_as(fp)))
         return p, theta
 
+    # ------------------------------------------------------------------ the neural imitator (Dense-7IN-32H1-32H2-1OUT)
+    def set_dense(self, model):
+        """cpmppi_set_dense: ``model`` = {w1 [32,7], b1 [32], w2 [32,32], b2 [32], w3 [1,32], b3 [1]} in the torch.nn.Linear layout
+        with the input columns in the order of ``model_folder.DENSE_INPUTS``, and optionally in_scale / in_shift [7], out_scale /
+        out_shift [1] (x_n = in_scale x + in_shift, Q = out_scale y + out_shift; identity when absent) - what
+        ``model_folder.load_dense_model`` returns.  The library refuses a non-finite value by name; a refused call changes nothing -
+        ``has_dense`` stays as it was and a training run goes on; a successful one ends a training run."""
+        shapes = dict(zip(DENSE_KEYS, DENSE_SHAPES), in_scale=(7,), in_shift=(7,), out_scale=(1,), out_shift=(1,))
+        keep = {}
+        for k, shp in shapes.items():
+            if model.get(k) is not None:
+                a = np.ascontiguousarray(np.asarray(model[k].detach().cpu() if torch.is_tensor(model[k]) else model[k], dtype=np.float32))
+                if a.shape != shp:
+                    raise ValueError(f"Dense weight {k} must have shape {shp}, got {a.shape}")
+                keep[k] = a
+            elif k in DENSE_KEYS:
+                raise ValueError(f"Dense weight {k} missing")
+        m = _L.cpmppi_dense_model()
+        for k in shapes:
+            setattr(m, k, keep[k].ctypes.data_as(C.POINTER(C.c_float)) if k in keep else None)
+        self._check(self.lib.cpmppi_set_dense(self._h, C.byref(m)))
+        self.has_dense = True
+
+    def _need_dense(self):
+        if not self.has_dense:
+            raise ValueError("no model set: call set_dense first")
+
+    def _build_dense_control(self, s, target_position, target_equilibrium, *, Q_out=None, y_out=None, count_dev=None):
+        """cpmppi_dense_control: the imitator's control of every env, ``Q_out`` [E] = clip(out_scale y + out_shift, -1, 1), from the
+        states ``s`` [E,6] and the targets [E] (device tensors; one launch, nothing allocated by the library).  ``y_out`` [E]: the
+        head's normalised output.  ``count_dev``: an int64 device counter advanced by one behind the step (a captured loop).
+        -> (Q_out, y_out)."""
+        self._need_dense()
+        E = device_tensor("s", s, tail=(6,)).shape[0]
+        if E == 0:
+            raise ValueError("s must be [E,6] with E >= 1")
+        for name, t in (("target_position", target_position), ("target_equilibrium", target_equilibrium)):
+            if device_tensor(name, t).shape != (E,):
+                raise ValueError(f"{name} must be [{E}] for s [{E},6]")
+        if Q_out is None:
+            Q_out = self.empty(E)
+        for name, t in (("Q_out", Q_out), ("y_out", y_out)):
+            if t is not None and device_tensor(name, t).shape != (E,):
+                raise ValueError(f"{name} must be [{E}]")
+        a = _L.cpmppi_dense_control_args()
+        a.E, a.s, a.target_position, a.target_equilibrium = E, s.data_ptr(), target_position.data_ptr(), target_equilibrium.data_ptr()
+        a.Q_out, a.y_out, a.count_dev = Q_out.data_ptr(), _addr(y_out), _counter("count_dev", count_dev)
+        return PreparedCall(self, self.lib.cpmppi_dense_control, a, (s, target_position, target_equilibrium, Q_out, y_out, count_dev),
+                            (Q_out, y_out), ())
+
+    dense_control = _run_once(_build_dense_control)
+
+    def prepare_dense_control(self, *args, **kwargs):
+        """The argument block of ``dense_control(...)`` built and validated ONCE: ``.run()`` enqueues the launch again on the same
+        buffers (the device loop, a capture)."""
+        return self._build_dense_control(*args, **kwargs)
+
+    def _dense_loss_args(self, states, target_position, target_equilibrium, labels, windows, post_wash_out, shift_labels,
+                         loss_out=None, grad_out=None, grad=True):
+        """The argument block of cpmppi_dense_loss_grad / cpmppi_dense_train_step, checked: -> (block, what it points into, loss_out,
+        grad_out).  ``windows`` [B,2] integers (r, t0) on the HOST: uploaded here, and handed to the library as its host copy."""
+        self._need_dense()
+        states, labels, R, T = self._recordings(states, labels)
+        tp, te = self.tensor(target_position), self.tensor(target_equilibrium)
+        if tp.shape != (R, T) or te.shape != (R, T):
+            raise ValueError(f"target_position and target_equilibrium must be [{R},{T}] for states [{R},{T},6]")
+        P, shift = int(post_wash_out), int(shift_labels)
+        if P < 1 or shift < 0:
+            raise ValueError(f"post_wash_out >= 1 and shift_labels >= 0, got {P}, {shift}")
+        w_host, w_dev, B = self._window_batch(windows, R, T, P - 1 + shift, f"{P} - 1 + {shift}")
+        loss_out, grad_out = self._loss_outputs(loss_out, grad_out, grad, _L.DENSE_PARAMS, torch.float32)
+        a = _L.cpmppi_dense_loss_args()
+        a.B, a.R, a.T, a.post_wash_out, a.shift_labels = B, R, T, P, shift
+        a.states, a.target_position, a.target_equilibrium, a.labels = states.data_ptr(), tp.data_ptr(), te.data_ptr(), labels.data_ptr()
+        a.windows, a.windows_host = w_dev.data_ptr(), w_host.ctypes.data
+        a.loss_out, a.grad_out = loss_out.data_ptr(), _addr(grad_out)
+        return a, (states, tp, te, labels, w_dev, w_host, loss_out, grad_out), loss_out, grad_out
+
+    def dense_train_reserve(self, samples):
+        """cpmppi_dense_train_reserve: the partial rows of ``dense_loss_grad`` / ``dense_train_step`` for up to ``samples`` = windows x
+        post_wash_out samples, so that a later call can be captured."""
+        self._check(self.lib.cpmppi_dense_train_reserve(self._h, int(samples)))
+
+    def _build_dense_loss_grad(self, states, target_position, target_equilibrium, labels, windows, post_wash_out=1, shift_labels=0,
+                               grad=True, *, loss_out=None, grad_out=None):
+        """cpmppi_dense_loss_grad: the imitator's mean squared error over ``windows`` [B,2] = (recording, first row) of
+        ``post_wash_out`` rows of ``states`` [R,T,6], ``target_position``, ``target_equilibrium``, ``labels`` [R,T] - every row one
+        sample, scored against the normalised label ``shift_labels`` rows on (include/cpmppi.h states it).
+        -> (loss [1] float64 on the device, gradient [1345] in the flat order of ``DENSE_KEYS`` - None with ``grad=False``, the loss
+        alone, bit for bit the loss of the gradient call)."""
+        a, keep, loss_out, grad_out = self._dense_loss_args(states, target_position, target_equilibrium, labels, windows,
+                                                            post_wash_out, shift_labels, loss_out, grad_out, grad)
+        return PreparedCall(self, self.lib.cpmppi_dense_loss_grad, a, keep, (loss_out, grad_out), ())
+
+    dense_loss_grad = _run_once(_build_dense_loss_grad)
+
+    def prepare_dense_loss_grad(self, *args, **kwargs):
+        """The argument block of ``dense_loss_grad(...)`` built and validated ONCE (a capture - after ``dense_train_reserve``)."""
+        return self._build_dense_loss_grad(*args, **kwargs)
+
+    def dense_train_begin(self):
+        """cpmppi_dense_train_begin: training starts from the model of the last ``set_dense`` - Adam's moments and step counter zero.
+        The run lasts until the next ``set_dense``, which ends it."""
+        self._need_dense()
+        self._check(self.lib.cpmppi_dense_train_begin(self._h))
+
+    def _build_dense_train_step(self, states, target_position, target_equilibrium, labels, windows, post_wash_out=1, shift_labels=0, *,
+                                lr, beta1=0.9, beta2=0.999, eps=1e-8, loss_out=None):
+        """cpmppi_dense_train_step: the loss and gradient of ``dense_loss_grad`` over this batch of ``windows`` and one Adam update of
+        the parameter vector in place, two launches.  -> the batch's loss BEFORE the update, [1] float64 on the device."""
+        a, keep, loss_out, _ = self._dense_loss_args(states, target_position, target_equilibrium, labels, windows, post_wash_out,
+                                                     shift_labels, loss_out, None, False)
+        lib, hyper = self.lib, (float(lr), float(beta1), float(beta2), float(eps))
+        return PreparedCall(self, lambda h, ref, stream: lib.cpmppi_dense_train_step(h, ref, *hyper, stream), a, keep, loss_out, ())
+
+    def dense_train_step(self, *args, **kwargs):
+        """``_build_dense_train_step``'s call, run once: -> the batch's loss before the update."""
+        return self._run_keeping("_dense_keep", self._build_dense_train_step(*args, **kwargs))
+
+    def prepare_dense_train_step(self, *args, **kwargs):
+        """The argument block of ``dense_train_step(...)`` built and validated ONCE: every ``.run()`` is one more Adam step on the same
+        batch and buffers (a benchmark loop, a capture - after ``dense_train_reserve``)."""
+        return self._build_dense_train_step(*args, **kwargs)
+
+    def dense_train_get(self):
+        """cpmppi_dense_train_get: the trained weights as the dict ``set_dense`` takes (weights only; the normalisation is the
+        caller's).  Synchronous."""
+        flat = np.empty(_L.DENSE_PARAMS, np.float32)
+        self._check(self.lib.cpmppi_dense_train_get(self._h, flat.ctypes.data_as(C.POINTER(C.c_float))))
+        return self.dense_unflatten(flat)
+
+    @staticmethod
+    def dense_unflatten(flat):
+        """The flat parameter vector [1345] -> {key: array} in the order and shapes of ``DENSE_KEYS``."""
+        flat = np.asarray(flat)
+        if flat.shape != (_L.DENSE_PARAMS,):
+            raise ValueError(f"the flat parameter vector has {_L.DENSE_PARAMS} entries, got {flat.shape}")
+        out, at = {}, 0
+        for k, shp in zip(DENSE_KEYS, DENSE_SHAPES):
+            n = int(np.prod(shp))
+            out[k] = flat[at:at + n].reshape(shp).copy()
+            at += n
+        return out
+
+    @staticmethod
+    def dense_flatten(model):
+        """{key: array} -> the flat float32 parameter vector [1345]."""
+        return np.concatenate([np.asarray(model[k], np.float32).reshape(-1) for k in DENSE_KEYS])
+
     # ------------------------------------------------------------------ training the GRU predictor on recordings
     def _gru_loss_args(self, states, Q, windows, wash_out, post_wash_out, shift_labels, loss_out=None, grad_out=None, grad=True,
                        rollout=False):
@@ -1439,7 +1589,7 @@ class MPPIEngine:
 
 class PreparedCall:
     """One entry point of the library that takes an argument block, ready to be enqueued any number of times
-    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_rpgd_step_gru / prepare_cem_step / prepare_cem_step_gru / prepare_brunton / prepare_gru_loss_grad / prepare_ode_fit_loss_grad / prepare_ode_fit_step).  ``args`` is the live
+    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_rpgd_step_gru / prepare_cem_step / prepare_cem_step_gru / prepare_brunton / prepare_gru_loss_grad / prepare_ode_fit_loss_grad / prepare_ode_fit_step / prepare_dense_control / prepare_dense_loss_grad / prepare_dense_train_step).  ``args`` is the live
     ctypes block, validated when it was built, and ``ref`` the reference to it that the library is handed; ``keep`` holds the
     tensors it points into; ``enqueue`` is the entry point, ``enqueue(handle, ref, stream)``.  ``result`` is what the call returns:
     the outputs of a control step - ``out``, whose first two are ``Q_out`` and ``S_out`` -, the plant's state, or the Brunton

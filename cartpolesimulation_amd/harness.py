@@ -15,6 +15,8 @@ generator's random experiments (schedule.ExperimentBatch): the target position f
 target equilibrium flips on its dwell times, tabulated on the host and read by the device loop at its own step counter
 (cpmppi_plant_step), with rows saved every dt_save whatever the control period.
 """
+import os
+
 import numpy as np
 import torch
 
@@ -69,6 +71,28 @@ def check_tuning(tuning, optimizer=None, predictor="ODE_v0", knots_fn=None):
         raise ValueError("tuning= and predictor='GRU': the tuning rows are read by the ODE predictors' fused MPPI step")
     if knots_fn is not None:
         raise ValueError("tuning= and knots_fn: a row holds the sampler's sigma, so the step draws its own Philox noise")
+
+
+def check_imitator(imitator, optimizer=None, predictor="ODE_v0", h0=None, knots_fn=None, tuning=None):
+    """``imitator=`` of run_schedule: the neural imitator computes the controls in the MPC's place, so everything that configures the
+    MPC is refused beside it by name.  -> the model dict ``MPPIEngine.set_dense`` takes (a folder is read with
+    ``model_folder.load_dense_model``), or None."""
+    if imitator is None:
+        return None
+    if optimizer is not None:
+        raise ValueError("imitator= and optimizer=: the imitator is the controller; an optimizer object is another one")
+    if predictor == "GRU":
+        raise ValueError("imitator= and predictor='GRU': the imitator rolls nothing out and has no predictor")
+    if h0 is not None:
+        raise ValueError("imitator= and h0: the memory belongs to the GRU predictor; a Dense net has none")
+    if knots_fn is not None:
+        raise ValueError("imitator= and knots_fn: the imitator draws no perturbations")
+    if tuning is not None:
+        raise ValueError("imitator= and tuning=: the tuning rows are read by the fused MPPI step, not by the imitator")
+    if isinstance(imitator, (str, os.PathLike)):
+        from .model_folder import load_dense_model
+        return load_dense_model(os.fspath(imitator))
+    return imitator
 
 
 def gru_memory(engine, E, h0):
@@ -141,7 +165,7 @@ class BatchedCartPoleExperiment:
 
     # ------------------------------------------------------------------ the data generator's experiments (moving targets)
     def run_schedule(self, batch, env_offset=0, graph=False, steps_per_graph=10, knots_fn=None, u_nom0=None, optimizer=None,
-                     predictor="ODE_v0", h0=None, tuning=None):
+                     predictor="ODE_v0", h0=None, tuning=None, imitator=None):
         """Run the E experiments of a schedule.ExperimentBatch to their end: CartPole.run_cartpole_random_experiment
         (CartPole/__init__.py:659-735) for all of them at once.  Per control period two launches - the fused MPPI step, reading
         the period's target position / equilibrium (/ pole length) from three [E] vectors, and cpmppi_plant_step, which advances
@@ -167,12 +191,18 @@ class BatchedCartPoleExperiment:
         ``tuning`` [E,16] (configs.tuning_rows): the controller's cost weights, LBD and sigma per experiment, registered with the
         engine for this run (launched or captured) and taken off it afterwards; the result keeps the tensor and, for
         MPPIEngine.score_runs, the loop's device table of target positions (``target_position_table``).  Not with
-        ``optimizer=``, ``predictor="GRU"`` or ``knots_fn`` (ValueError)."""
+        ``optimizer=``, ``predictor="GRU"`` or ``knots_fn`` (ValueError).
+        ``imitator``: the neural imitator of the MPC - a model dict (``MPPIEngine.set_dense``) or a model folder
+        (``model_folder.load_dense_model``) - computes the controls instead: one cpmppi_dense_control per period on the state the
+        controller is shown and the period's targets, then the plant; launched or captured; schedule tables, measurement chain,
+        disturbance and ``score_runs`` apply unchanged.  Not with ``optimizer=``, ``predictor="GRU"``, ``gru_model=``, ``h0``,
+        ``knots_fn`` or ``tuning=`` (ValueError by name).  The engine keeps the model."""
+        imitator = check_imitator(imitator, optimizer, predictor, h0, knots_fn, tuning)
         check_tuning(tuning, optimizer, predictor, knots_fn)
         if tuning is not None and tuple(np.shape(tuning))[:1] != (batch.E,):
             raise ValueError(f"tuning must hold one row per experiment ({batch.E}), got shape {tuple(np.shape(tuning))}")
         run = ScheduleRun(self.engine, batch, self.seed, env_offset=env_offset, knots_fn=knots_fn, u_nom0=u_nom0, optimizer=optimizer,
-                          predictor=predictor, h0=h0)
+                          predictor=predictor, h0=h0, imitator=imitator)
         if batch.dt_simulation != self.dt_simulation or batch.n_ctrl != self.n_sub:
             raise ValueError("the batch was drawn for other time scales than this experiment runner's")
         if graph and run.controller.cannot_capture:
@@ -457,6 +487,28 @@ class FusedMppiStep:
         self.step = None                                           # (built for the host's offset)
 
 
+class ImitatorController:
+    """The neural imitator (Dense-7IN-32H1-32H2-1OUT, ``MPPIEngine.set_dense``) in the MPC's place: one cpmppi_dense_control per
+    control period on the state the controller is shown and the period's targets -> the controls the plant reads.  It reads no pole
+    mass, no pole length and no previous input.  Captured, the call carries a device counter, which it advances and the plant launch
+    reads as its period."""
+    cannot_capture = None
+
+    def __init__(self, engine, buffers):
+        self.eng, self.buf = engine, buffers
+        self.counter = self.call = None
+
+    def control(self, c):
+        if self.call is None:                                      # (built once: the buffers persist; a test may re-point them before)
+            buf = self.buf
+            self.call = self.eng.prepare_dense_control(buf.s_ctrl, buf.cur_tp, buf.cur_te, Q_out=buf.Q, count_dev=self.counter)
+        self.call.run()
+
+    def before_capture(self):
+        self.counter = torch.zeros(1, dtype=torch.int64, device=self.buf.s.device)
+        self.call = None                                           # (built without the counter)
+
+
 def _tell_optimizer(optimizer, buffers, mass, c):
     """What the simulator hands controller.step (CartPole/__init__.py:509-520), as attributes of the optimizer's variable_parameters
     (the pole mass of call c; None under capture: it stays).  -> them."""
@@ -533,7 +585,10 @@ class ScheduleRun:
     runs can be interleaved by one host thread: the batch's `buffers`, the `controller` that computes the controls, the `mass` it is
     told, and the `loop` that launches or replays the periods."""
 
-    def __init__(self, engine, batch, seed, env_offset=0, knots_fn=None, u_nom0=None, optimizer=None, predictor="ODE_v0", h0=None):
+    def __init__(self, engine, batch, seed, env_offset=0, knots_fn=None, u_nom0=None, optimizer=None, predictor="ODE_v0", h0=None,
+                 imitator=None):
+        """``imitator``: the model dict of the neural imitator (``check_imitator`` has refused what cannot stand beside it); the engine
+        takes it (``set_dense``) and it computes the controls."""
         gru = check_predictor(engine, predictor, h0, optimizer, knots_fn)
         if optimizer is not None:
             if getattr(optimizer, "num_envs", batch.E) != batch.E:
@@ -545,11 +600,15 @@ class ScheduleRun:
         self.buffers = buf = ScheduleBuffers(engine, batch, u_nom0)
         self.T, self.tail = buf.T, buf.tail
         # (an optimizer object that runs the network - gru_model=, its memory `h` once configured - reads no pole mass either)
-        network = gru or getattr(optimizer, "h", None) is not None or getattr(optimizer, "gru_model", None) is not None
+        network = (gru or imitator is not None or getattr(optimizer, "h", None) is not None
+                   or getattr(optimizer, "gru_model", None) is not None)
         self.mass = ControllerMass(batch, engine.mppi, network=network)
         self.mass.bind([engine], register=optimizer is None)       # (an optimizer object registers the row with its own engine)
         self.memory = gru_memory(engine, batch.E, h0) if gru else None
-        if optimizer is None:
+        if imitator is not None:
+            engine.set_dense(imitator)
+            self.controller = ImitatorController(engine, buf)
+        elif optimizer is None:
             self.controller = FusedMppiStep(engine, buf, self.mass, seed, env_offset, knots_fn, self.memory)
         else:
             self.controller = optimizer_controller(optimizer)(optimizer, buf, self.mass)

@@ -28,6 +28,12 @@ KERNEL_OUTPUTS = ("angleD", "angle_cos", "angle_sin", "position", "positionD")
 # its weights in the torch.nn.GRU layout: the keys of ``MPPIEngine.set_gru``, in the order of the flat parameter vector [10341]
 GRU_KEYS = ("w_ih0", "w_hh0", "b_ih0", "b_hh0", "w_ih1", "w_hh1", "b_ih1", "b_hh1", "w_out", "b_out")
 GRU_SHAPES = ((96, 6), (96, 32), (96,), (96,), (96, 32), (96, 32), (96,), (96,), (5, 32), (5,))
+# the neural imitator Dense-7IN-32H1-32H2-1OUT (cpmppi_dense.hip): its inputs in the kernel's order - the shipped folder's - and its
+# weights in the torch.nn.Linear layout: the keys of ``MPPIEngine.set_dense``, in the order of the flat parameter vector [1345]
+DENSE_NET_NAME = "Dense-32H1-32H2"
+DENSE_INPUTS = ("angleD", "angle_cos", "angle_sin", "position", "positionD", "target_equilibrium", "target_position")
+DENSE_KEYS = ("w1", "b1", "w2", "b2", "w3", "b3")
+DENSE_SHAPES = ((32, 7), (32,), (32, 32), (32,), (1, 32), (1,))
 
 
 def read_net_info(folder):
@@ -183,4 +189,77 @@ def load_gru_model(folder):
     for k in ("in_scale", "in_shift", "out_scale", "out_shift"):
         if k in w:                                                  # weights.npz may carry them directly (kernel order)
             model[k] = w[k]
+    return model
+
+
+def keras_dense_weights_to_model(arrays):
+    """``model.get_weights()`` of the Keras network Dense(32, tanh) -> Dense(32, tanh) -> Dense(1) - [kernel [in,out], bias] x 3,
+    applied as ``x @ kernel`` - into the torch.nn.Linear layout ([out,in]) of ``MPPIEngine.set_dense``."""
+    arrays = [np.asarray(a, dtype=np.float32) for a in arrays]
+    if len(arrays) != 6:
+        raise ValueError(f"expected 6 arrays (3 x [kernel, bias]), got {len(arrays)}")
+    model = {}
+    for l, (wk, bk) in enumerate((("w1", "b1"), ("w2", "b2"), ("w3", "b3"))):
+        k, b = arrays[2 * l], arrays[2 * l + 1]
+        want = DENSE_SHAPES[2 * l]
+        if k.shape != want[::-1] or b.shape != (want[0],):
+            raise NotImplementedError(f"Dense layer {l}: kernel {k.shape}, bias {b.shape}; the HIP imitator is built for "
+                                      f"Dense-7IN-32H1-32H2-1OUT (kernel {want[::-1]})")
+        model[wk], model[bk] = np.ascontiguousarray(k.T), b
+    return model
+
+
+def _dense_weights(folder, source=None):
+    """The weights of a Dense-7IN-32H1-32H2-1OUT folder in the layout of ``set_dense``, input columns in the FOLDER's order, from
+    ``weights.npz`` (the keys of ``DENSE_KEYS``: what ``train_imitator.write_model_folder`` writes), the ``.keras`` archive or the
+    ``ckpt.ckpt`` pair - the first one present, or the one ``source`` names ("npz", "keras", "ckpt")."""
+    npz = os.path.join(folder, "weights.npz")
+    keras = sorted(f for f in os.listdir(folder) if f.endswith(".keras"))
+    ckpt = os.path.exists(os.path.join(folder, "ckpt.ckpt.index"))
+    have = {"npz": os.path.exists(npz), "keras": bool(keras), "ckpt": ckpt}
+    if source is not None and (source not in have or not have[source]):
+        raise FileNotFoundError(f"{folder}: no weights of the kind {source!r} (npz: weights.npz, keras: <name>.keras, ckpt: ckpt.ckpt.index + data)")
+    source = source or next((k for k in ("npz", "keras", "ckpt") if have[k]), None)
+    if source == "npz":
+        z = dict(np.load(npz))
+        missing = [k for k in DENSE_KEYS if k not in z]
+        if missing:
+            raise ValueError(f"{npz}: no array {missing} (the keys are {', '.join(DENSE_KEYS)})")
+        return z
+    if source == "keras":
+        from .hdf5_min import read_keras_weights
+        arrays, owners = read_keras_weights(os.path.join(folder, keras[0]))
+        classes = [c for _, c in owners]
+        if classes != ["Dense", "Dense", "Dense"]:
+            raise NotImplementedError(f"{folder}/{keras[0]}: layers with variables are {classes}; the HIP imitator implements "
+                                      "Dense -> Dense -> Dense (Dense-7IN-32H1-32H2-1OUT)")
+        return keras_dense_weights_to_model(arrays)
+    if source == "ckpt":
+        from .tf_bundle_min import read_keras_checkpoint_weights
+        return keras_dense_weights_to_model(read_keras_checkpoint_weights(os.path.join(folder, "ckpt.ckpt")))
+    raise FileNotFoundError(f"{folder}: no weights.npz, <name>.keras or ckpt.ckpt.index + data")
+
+
+def load_dense_model(folder, source=None):
+    """A ``Dense-7IN-32H1-32H2-1OUT-*`` folder - the neural imitator the reference ships under GymlikeCartPole/ - -> the dict
+    ``MPPIEngine.set_dense`` takes: weights in the torch.nn.Linear layout with the input columns permuted to ``DENSE_INPUTS``, the
+    normalisation as in_scale / in_shift [7], out_scale / out_shift [1] in that order.  ``source``: read the weights from that
+    container alone ("npz", "keras", "ckpt"; None: the first present).  The hidden layers are tanh, the head linear
+    (C_implementation/network.c); anything else than this one network is refused by name."""
+    info = read_net_info(folder)
+    if info.get("type", "").strip() != "Dense" or info.get("net_name", "").strip() != DENSE_NET_NAME:
+        raise NotImplementedError(f"{folder}: TYPE {info.get('type')!r}, NET NAME {info.get('net_name')!r}; the HIP imitator is built "
+                                  f"for TYPE 'Dense', NET NAME {DENSE_NET_NAME!r} (7 inputs, 1 output) alone")
+    if sorted(info["inputs"]) != sorted(DENSE_INPUTS) or len(info["outputs"]) != 1:
+        raise NotImplementedError(f"{folder}: features {info['inputs']} -> {info['outputs']}; built for {DENSE_INPUTS} -> one control")
+    pin = [info["inputs"].index(f) for f in DENSE_INPUTS]           # kernel column i  <- model column pin[i]
+    w = {k: np.asarray(v, dtype=np.float32) for k, v in _dense_weights(folder, source).items()}
+    for k, shp in zip(DENSE_KEYS, DENSE_SHAPES):
+        if w[k].shape != shp:
+            raise NotImplementedError(f"{folder}: weight {k} has shape {w[k].shape}; built for {shp} (Dense-7IN-32H1-32H2-1OUT)")
+    model = {k: w[k] for k in DENSE_KEYS}
+    model["w1"] = np.ascontiguousarray(w["w1"][:, pin])
+    if str(info.get("normalize", "True")).strip().lower() != "false":
+        nm = read_normalization(folder, info)
+        model.update(in_scale=nm["a"][pin], in_shift=nm["b"][pin], out_scale=nm["A"], out_shift=nm["B"])
     return model

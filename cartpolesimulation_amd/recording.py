@@ -275,7 +275,7 @@ GRU_FUSED_OPTIMIZERS = ("rpgd", "rpgd-tf", "gradient", "gradient-tf", "cem", "ce
 
 def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, seed=None, cartpole_seed=None, L=None, native=True,
                      graph=False, secondary_experiment_index=None, controller_name="mpc", optimizer_name="mppi", title=None, groups=1,
-                     rank=0, world=1, parameters=None, optimizer=None, gru_model=None):
+                     rank=0, world=1, parameters=None, optimizer=None, gru_model=None, imitator=None):
     """Batched run_data_generator: ``config`` = config_data_gen.yml as a dict (or overrides of the shipped file, see
     schedule.merged_config) - length_of_experiment, the three dt, the random initial state, the target trace's turning points
     and interpolation types, the target-equilibrium dwell times, number_of_experiments, ML_Pipeline_mode / split.  All
@@ -302,7 +302,11 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
     (model_folder.load_gru_model) - the fused MPPI step rolls out with that network instead of the equations, its memory handed
     from control period to control period on the device (harness.run_schedule(predictor="GRU")); launched or captured
     (``graph=True``).  The header's optimizer line then names the predictor.  Not with ``groups`` > 1 (the env groups' period loop
-    knows no memory hand-over) and not with ``optimizer=`` (an optimizer object is given its network as ``gru_model=`` itself)."""
+    knows no memory hand-over) and not with ``optimizer=`` (an optimizer object is given its network as ``gru_model=`` itself).
+    ``imitator``: the model dict of ``MPPIEngine.set_dense`` or a ``Dense-7IN-32H1-32H2-1OUT-*`` model folder
+    (model_folder.load_dense_model) - the neural imitator controls the plants in the MPC's place, one cpmppi_dense_control per
+    control period (harness.run_schedule(imitator=...)); launched or captured.  The header names the controller
+    "neural-imitator".  Not with ``optimizer=``, ``gru_model=``, ``groups`` > 1 or ``world`` > 1."""
     import time
     from .harness import BatchedCartPoleExperiment
     from .schedule import RandomExperimentSetter, merged_config
@@ -313,6 +317,16 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
     if cfg.get("seed") is None:
         raise ValueError("config['seed'] is empty: the reference then seeds from the clock; give a seed for a reproducible batch")
     cseed = cartpole_seed if cartpole_seed is not None else cfg["seed"] + 1
+    if imitator is not None:
+        if gru_model is not None:
+            raise ValueError("imitator= and gru_model=: the imitator rolls nothing out and has no predictor")
+        if optimizer is not None:
+            raise ValueError("imitator= and optimizer=: the imitator is the controller; an optimizer object is another one")
+        if int(groups) > 1 or int(world) > 1:
+            raise ValueError("imitator: env groups and the multi-GPU run serve the MPPI step: groups=1, world=1")
+        from .harness import check_imitator
+        imitator = check_imitator(imitator)
+        controller_name, optimizer_name = "neural-imitator", "none"
     if gru_model is not None:
         if int(groups) > 1:
             raise ValueError("gru_model: env groups run the MPPI step without the memory hand-over of the network: groups=1")
@@ -363,7 +377,7 @@ def generate_dataset(engine, num_experiments=None, out_dir=None, config=None, se
             eg.close()
     else:
         exp = BatchedCartPoleExperiment(engine, batch.dt_simulation, batch.dt_control, seed=cfg["seed"])
-        res = exp.run_schedule(batch, graph=graph, env_offset=_first, optimizer=optimizer,
+        res = exp.run_schedule(batch, graph=graph, env_offset=_first, optimizer=optimizer, imitator=imitator,
                                **(dict(predictor="GRU") if gru_model is not None else {}))
         torch.cuda.synchronize()
     per_call = (time.perf_counter() - t0) / (batch.n_periods + 1)   # what Q_update_time can honestly say: wall time per controller update of the batch
@@ -422,13 +436,25 @@ def main(argv=None):
                          "(cpmppi_rpgd_step_gru: forward sweep, GRU adjoint, Adam, ranking, resampling, shift; cpmppi_cem_step_gru) "
                          "and the closed loop captured as a graph; with --config-root the checkout's own optimizer (shipped: rpgd). "
                          "(--fused is the step that integrates the ODE: beside --gru-model it serves cem alone.)")
+    ap.add_argument("--imitator", default=None, metavar="FOLDER",
+                    help="a Dense-7IN-32H1-32H2-1OUT-* model folder (train_imitator writes one; the reference ships one under "
+                         "GymlikeCartPole/): the neural imitator controls the plants in the MPC's place, one forward pass per control "
+                         "period (cpmppi_dense_control); with --graph the loop is captured; not with --optimizer, --fused, --gru-model, "
+                         "--gru-fused or --groups > 1")
     ap.add_argument("--graph", action="store_true",
                     help="mppi: the closed loop captured as a graph of control periods, replayed (the step counter on the device)")
     ap.add_argument("--cost", default=None,
                     choices=["legacy_mppi_cartpole", "default", "quadratic_boundary_grad_minimal", "quadratic_boundary_grad"])
     args = ap.parse_args(argv)
     phys, parameters, dg, optimizer = None, None, {}, None
-    opt_name = args.optimizer
+    if args.imitator is not None:
+        for flag, given in (("--optimizer", args.optimizer is not None), ("--fused", args.fused), ("--gru-model", args.gru_model is not None),
+                            ("--gru-fused", args.gru_fused), ("--groups > 1", args.groups > 1),
+                            ("WORLD_SIZE > 1", int(os.environ.get("WORLD_SIZE", "1")) > 1)):
+            if given:
+                raise SystemExit(f"--imitator and {flag}: the imitator is the controller - it has no optimizer and no predictor, and env "
+                                 "groups and the multi-GPU run serve the MPPI step")
+    opt_name = "mppi" if args.imitator is not None else args.optimizer      # (the engine that runs the plant)
     if args.config_root and opt_name is None:
         import yaml as _yaml
         with open(os.path.join(args.config_root, "Control_Toolkit_ASF", "config_controllers.yml")) as fh:
@@ -520,7 +546,7 @@ def main(argv=None):
     if args.gru_model is not None and optimizer is not None and not gru_opt:
         raise SystemExit(f"--gru-model: the network in the device loop is built for the fused MPPI step (--optimizer mppi), not {opt_name!r}")
     paths = generate_dataset(eng, n_exp, out, seed=seed, rank=rank, world=world, config=dg, groups=args.groups, parameters=parameters,
-                             optimizer=optimizer, graph=graph, gru_model=None if gru_opt else args.gru_model,
+                             optimizer=optimizer, graph=graph, gru_model=None if gru_opt else args.gru_model, imitator=args.imitator,
                              secondary_experiment_index=None if args.secondary_experiment_index < 0 else args.secondary_experiment_index)
     print(f"wrote {len(paths)} recordings under {os.path.dirname(paths[0])}")
 

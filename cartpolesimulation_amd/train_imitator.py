@@ -1,0 +1,292 @@
+"""Training the neural imitator of the MPC on recordings, on the device (reference: SI_Toolkit_ASF/Run/A2_Train_Network.py with
+SI_Toolkit_ASF/config_training.yml AS SHIPPED: NET_NAME Dense-32H1-32H2, seven inputs, the output Q_calculated).
+
+The network is the one the reference ships trained under GymlikeCartPole/Dense-7IN-32H1-32H2-1OUT-0/: position, positionD,
+angle_cos, angle_sin, angleD, target_equilibrium, target_position -> the controller's output, two tanh layers of 32 units and a
+linear head (C_implementation/network.c).  Its training target is the column ``along_trajectories`` writes, Q_calculated_offline:
+the chain is  along_trajectories -> train_imitator -> recording --imitator FOLDER  (INTEGRATION.md).
+
+SI_Toolkit is a submodule that the reference checkout does not carry, so the semantics - windows, normalisation, loss, schedule - are
+THIS PACKAGE'S OWN, chosen to match what the configuration keys say, and shared with ``train_gru`` (its docstring states batches and
+the learning-rate schedule):
+
+* a window is ``POST_WASH_OUT_LEN`` consecutive rows of one recording; the network has no memory, so every row is one sample, scored
+  against the label ``SHIFT_LABELS`` rows on (mean squared error of the normalised values); ``WASH_OUT_LEN`` must be 0;
+* normalisation is min-max to [-1, 1] over the training recordings for the five state features and the label
+  (``train_gru.normalization_from_recordings``'s rule); a TARGET column that never varies (target_equilibrium often does not) gets the
+  identity (a = 1, b = 0); a state feature or label that never varies is refused by name;
+* fresh weights are uniform in +-1/sqrt(fan_in) from ``numpy.random.default_rng(seed)``.
+
+The loss, its gradient and Adam run on the device in two launches per step (``MPPIEngine.dense_train_step``).
+
+Built for Dense-7IN-32H1-32H2-1OUT alone.  Not built, refused by name where a user can ask: other layer sizes, activations or
+feature lists, a Dense dynamics model inside an optimizer, regularisation / pruning / quantisation / series modification / filters,
+several models per launch, env groups and multi-GPU.
+
+  python -m cartpolesimulation_amd.train_imitator --recordings DIR --out FOLDER --config-root CHECKOUT
+                                                  [--label-column Q_calculated_offline] [--validation DIR] [--init FOLDER]
+"""
+import os
+
+import numpy as np
+
+from ._training import make_windows, plateau_rule, refuse_unbuilt_sections, run_epochs, schedule_settings  # noqa: F401  (re-exported)
+from .model_folder import DENSE_INPUTS, DENSE_KEYS, DENSE_NET_NAME, DENSE_SHAPES
+
+f32 = np.float32
+NET_NAME = DENSE_NET_NAME
+NORM_KEYS = ("in_scale", "in_shift", "out_scale", "out_shift")
+LABEL_COLUMN = "Q_calculated_offline"        # what along_trajectories writes; config_training.yml calls the output Q_calculated
+CONFIG_OUTPUTS = ("Q_calculated", "Q_calculated_offline")
+# column of states [.., 6] = (angle, angleD, angle_cos, angle_sin, position, positionD) of the five state inputs
+_STATE_COLUMNS = (1, 2, 3, 4, 5)
+
+
+def check_recordings(states, target_position, target_equilibrium, labels, lengths=None):
+    """-> (states [R,T,6], target_position, target_equilibrium, labels [R,T] as float32, lengths [R] - None: T each)."""
+    states = np.ascontiguousarray(states, f32)
+    if states.ndim != 3 or states.shape[2] != 6:
+        raise ValueError(f"states must be [R,T,6], got {states.shape}")
+    R, T = states.shape[:2]
+    cols = []
+    for name, c in (("target_position", target_position), ("target_equilibrium", target_equilibrium), ("labels", labels)):
+        c = np.ascontiguousarray(c, f32)
+        if c.shape != (R, T):
+            raise ValueError(f"{name} must be [{R},{T}] for states [{R},{T},6], got {c.shape}")
+        cols.append(c)
+    lengths = np.full(R, T) if lengths is None else np.asarray(lengths).reshape(-1)
+    if lengths.shape != (R,) or lengths.min() < 0 or lengths.max() > T:
+        raise ValueError(f"lengths must hold one length 0..{T} per recording ({R})")
+    return (states, *cols, lengths)
+
+
+def normalization_from_recordings(states, target_position, target_equilibrium, labels, lengths=None):
+    """Min-max normalisation to [-1, 1] (normalised = a x + b, a = 2 / (max - min), b = -(max + min) / (max - min); the label's
+    inverse Q = A y + B, A = (max - min) / 2, B = (max + min) / 2) over the rows before ``lengths[r]``.  A target column that never
+    varies gets a = 1, b = 0; a state feature or the label that never varies is refused by name.
+    -> dict(in_scale, in_shift [7] in the order of ``model_folder.DENSE_INPUTS``, out_scale, out_shift [1]), float32."""
+    states, tp, te, labels, lengths = check_recordings(states, target_position, target_equilibrium, labels, lengths)
+    keep = np.arange(states.shape[1])[None, :] < lengths[:, None]
+    if not keep.any():
+        raise ValueError("no rows")
+    cols = [states[:, :, c][keep].astype(np.float64) for c in _STATE_COLUMNS] + [te[keep].astype(np.float64), tp[keep].astype(np.float64),
+                                                                                 labels[keep].astype(np.float64)]
+    lo, hi = np.array([c.min() for c in cols]), np.array([c.max() for c in cols])
+    names = DENSE_INPUTS + ("the label",)
+    flat = [names[i] for i in (0, 1, 2, 3, 4, 7) if not hi[i] > lo[i]]
+    if flat:
+        raise ValueError(f"feature(s) {flat} never vary over the recordings: min-max normalisation is undefined")
+    varies = hi > lo
+    span = np.where(varies, hi - lo, 1.0)
+    a, b = np.where(varies, 2.0 / span, 1.0), np.where(varies, -(hi + lo) / span, 0.0)
+    return dict(in_scale=a[:7].astype(f32), in_shift=b[:7].astype(f32),
+                out_scale=np.array([(hi[7] - lo[7]) / 2.0], f32), out_shift=np.array([(hi[7] + lo[7]) / 2.0], f32))
+
+
+def initial_weights(seed):
+    """A fresh Dense-7IN-32H1-32H2-1OUT: every weight and bias uniform in +-1/sqrt(fan_in) (the torch.nn.Linear rule) from
+    ``numpy.random.default_rng(seed)``, in the order of ``DENSE_KEYS``."""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for key, shp in zip(DENSE_KEYS, DENSE_SHAPES):
+        k = 1.0 / np.sqrt(7.0 if key in ("w1", "b1") else 32.0)
+        out[key] = rng.uniform(-k, k, size=shp).astype(f32)
+    return out
+
+
+def _check_model(model):
+    for key, shp in zip(DENSE_KEYS, DENSE_SHAPES):
+        if key not in model or np.shape(model[key]) != shp:
+            raise ValueError(f"model: weight {key} must have shape {shp} (Dense-7IN-32H1-32H2-1OUT is the network built)")
+
+
+def train_imitator(engine, states, target_position, target_equilibrium, labels, lengths=None, *, epochs, batch_size, lr, seed,
+                   post_wash_out=1, shift_labels=0, validation=None, init=None, reduce_lr_on_plateau=True, patience=2,
+                   decrease_factor=0.5, minimal_lr=1e-7, min_delta=1e-6, beta1=0.9, beta2=0.999, eps=1e-7, validation_batch=4096,
+                   log=None):
+    """Train Dense-7IN-32H1-32H2-1OUT on ``states`` [R,T,6], ``target_position``, ``target_equilibrium``, ``labels`` [R,T]
+    (``lengths`` [R]: the recordings' true lengths, None = T) with ``engine`` (an ``MPPIEngine``; its imitator is replaced).
+    ``init``: the model dict to start from - weights in the order of ``DENSE_KEYS``, and the normalisation if it carries one; None:
+    ``initial_weights(seed)``.  Without a normalisation in ``init`` it is ``normalization_from_recordings`` of the training data.
+    ``validation`` = (states, target_position, target_equilibrium, labels, lengths or None) is scored after every epoch through the
+    loss-only call.  ``eps`` defaults to Keras's Adam epsilon.
+    -> (the model dict ``MPPIEngine.set_dense`` takes, which the engine holds on return; history = dict(loss, val_loss, lr: one
+    entry per epoch, batch_loss: every step's loss in order))."""
+    states, tp, te, labels, lengths = check_recordings(states, target_position, target_equilibrium, labels, lengths)
+    epochs, batch_size = int(epochs), int(batch_size)
+    if epochs < 1 or batch_size < 1:
+        raise ValueError("epochs and batch_size must be at least 1")
+    windows = make_windows(lengths, 0, post_wash_out, shift_labels)
+    if len(windows) == 0:
+        raise ValueError(f"no recording holds a window of {post_wash_out} rows with its labels {shift_labels} rows on")
+    model = dict(init) if init is not None else initial_weights(seed)
+    _check_model(model)
+    norm = {k: np.asarray(model[k], f32) for k in NORM_KEYS if model.get(k) is not None}
+    if len(norm) != 4:
+        norm = normalization_from_recordings(states, tp, te, labels, lengths)
+    model = {**{k: np.asarray(model[k], f32) for k in DENSE_KEYS}, **norm}
+    engine.set_dense(model)
+    engine.dense_train_begin()
+    dev = tuple(engine.tensor(x) for x in (states, tp, te, labels))
+    loss_of = vw = None
+    if validation is not None:
+        vs, vtp, vte, vlab, vl = check_recordings(*validation[:4], validation[4] if len(validation) > 4 else None)
+        vw = make_windows(vl, 0, post_wash_out, shift_labels)
+        if len(vw) == 0:
+            raise ValueError("the validation recordings hold no window")
+        vdev = tuple(engine.tensor(x) for x in (vs, vtp, vte, vlab))
+        loss_of = lambda w: engine.dense_loss_grad(*vdev, w, post_wash_out, shift_labels, grad=False)[0]  # noqa: E731
+
+    def step(batch, rate, loss_out, tag):
+        engine.dense_train_step(*dev, batch, post_wash_out, shift_labels, lr=rate, beta1=beta1, beta2=beta2, eps=eps, loss_out=loss_out)
+
+    history, _ = run_epochs(engine.device, lambda epoch: (windows, None), step, loss_of, vw, epochs=epochs, batch_size=batch_size,
+                            seed=seed, lr=lr, log=log, validation_batch=validation_batch,
+                            plateau=(reduce_lr_on_plateau, patience, decrease_factor, minimal_lr, min_delta))
+    trained = {**engine.dense_train_get(), **norm}
+    engine.set_dense(trained)          # (ends the run: the engine holds the trained model as any other)
+    return trained, history
+
+
+def write_model_folder(folder, model, name=None, info=None):
+    """A model folder in the format ``model_folder.load_dense_model`` reads, for which it returns the arrays of ``model`` bit for
+    bit: the net-info file ``<name>.txt`` (``name`` None: the folder's own name), the four normalisation CSVs (identity where
+    ``model`` has none) and ``weights.npz`` with the weights in the order of ``DENSE_KEYS``, inputs in the kernel's order.
+    ``info``: further ``KEY: value`` entries of the net-info file.  -> the folder."""
+    _check_model(model)
+    folder = os.path.abspath(os.fspath(folder))
+    name = name or os.path.basename(folder.rstrip(os.sep))
+    os.makedirs(folder, exist_ok=True)
+    normalize = all(model.get(k) is not None for k in NORM_KEYS)
+    entries = {"LIBRARY": "cartpolesimulation_amd", "NET NAME": NET_NAME, "NET FULL NAME": name,
+               "INPUTS": ", ".join(DENSE_INPUTS), "OUTPUTS": LABEL_COLUMN, "TYPE": "Dense",
+               "NORMALIZE": str(normalize), "PARENT NET": "Network trained from scratch"}
+    entries.update({str(k).upper(): str(v) for k, v in (info or {}).items()})
+    with open(os.path.join(folder, name + ".txt"), "w") as fh:
+        for key, value in entries.items():
+            fh.write(f"{key}:\n{value}\n\n")
+    vectors = (("normalization_vec_a.csv", "in_scale", 7, 1.0), ("normalization_vec_b.csv", "in_shift", 7, 0.0),
+               ("denormalization_vec_A.csv", "out_scale", 1, 1.0), ("denormalization_vec_B.csv", "out_shift", 1, 0.0))
+    for fname, key, n, fill in vectors:
+        v = np.asarray(model[key], f32).reshape(-1) if normalize else np.full(n, fill, f32)
+        if v.shape != (n,):
+            raise ValueError(f"model: {key} must have {n} entries")
+        with open(os.path.join(folder, fname), "w") as fh:      # (repr of the float32's double: read back exactly)
+            fh.write(",".join(repr(float(x)) for x in v) + "\n")
+    np.savez(os.path.join(folder, "weights.npz"), **{k: np.asarray(model[k], f32) for k in DENSE_KEYS})
+    return folder
+
+
+# ---------------------------------------------------------------------------------------------------------------- command line
+def training_settings(config, net=None, **overrides):
+    """config_training.yml as a dict -> (the keyword arguments of ``train_imitator``: EPOCHS, BATCH_SIZE, SEED, LR.*,
+    POST_WASH_OUT_LEN, SHIFT_LABELS - ``overrides``: the same by ``train_imitator``'s names, None = the file's -, ``normalize``).
+    The shipped file is taken as it stands.  Refused by name: a net other than Dense-32H1-32H2, inputs other than the seven of
+    ``model_folder.DENSE_INPUTS`` (in any order, split between control / state / setpoint inputs as the file likes), an output other
+    than the one control Q_calculated / Q_calculated_offline, a wash-out, translation-invariant variables, and the activated
+    regularisation, pruning, quantisation, series-modification, filter and on-the-fly keys."""
+    t = dict(config.get("training_default") or {})
+    net = net or (config.get("modeling") or {}).get("NET_NAME")
+    if net != NET_NAME:
+        raise ValueError(f"net {net!r}: the imitator's trainer is built for {NET_NAME} (Dense-7IN-32H1-32H2-1OUT) alone - no other "
+                         "layer sizes, activations or cell types (train_gru trains GRU-32H1-32H2, fit_ode the ODE's parameters)")
+    inputs = [*(t.get("control_inputs") or []), *(t.get("state_inputs") or []), *(t.get("setpoint_inputs") or [])]
+    if sorted(inputs) != sorted(DENSE_INPUTS):
+        raise ValueError(f"inputs {inputs}: the imitator is built for the seven inputs {list(DENSE_INPUTS)}")
+    outputs = list(t.get("outputs") or [])
+    if len(outputs) != 1 or outputs[0] not in CONFIG_OUTPUTS:
+        raise ValueError(f"outputs {outputs}: the imitator has one output, the controller's Q ({' / '.join(CONFIG_OUTPUTS)})")
+    if t.get("translation_invariant_variables"):
+        raise ValueError(f"training_default.translation_invariant_variables = {t['translation_invariant_variables']}: not built")
+    if int(t.get("WASH_OUT_LEN", 0)) != 0:
+        raise ValueError(f"WASH_OUT_LEN = {t['WASH_OUT_LEN']}: a Dense net has no memory to wash out; set it to 0")
+    refuse_unbuilt_sections(config)
+    out = dict(schedule_settings(config), post_wash_out=t.get("POST_WASH_OUT_LEN", 1), shift_labels=t.get("SHIFT_LABELS", 0))
+    out.update({k: v for k, v in overrides.items() if v is not None})
+    if int(out["post_wash_out"]) < 1 or int(out["shift_labels"]) < 0:
+        raise ValueError(f"post_wash_out >= 1 and shift_labels >= 0, got {out['post_wash_out']}, {out['shift_labels']}")
+    return out, bool(t.get("NORMALIZE", True))
+
+
+def identity_normalization():
+    return dict(in_scale=np.ones(7, f32), in_shift=np.zeros(7, f32), out_scale=np.ones(1, f32), out_shift=np.zeros(1, f32))
+
+
+def load_recordings_folder(folder, label_column=LABEL_COLUMN):
+    """Every recording CSV of ``folder`` (``along_trajectories.load_columns``) -> (states [R,T,6], target_position,
+    target_equilibrium, labels [R,T] padded with zeros to the longest, lengths [R], the file names).  A file without
+    ``label_column`` is refused by name."""
+    from .along_trajectories import FEATURES, load_columns
+    names = sorted(n for n in os.listdir(folder) if n.endswith(".csv"))
+    if not names:
+        raise ValueError(f"{folder}: no recording (*.csv)")
+    wanted = ["target_position", "target_equilibrium", label_column]
+    cols = [load_columns(os.path.join(folder, n), wanted) for n in names]
+    lengths = np.array([len(c[label_column]) for c in cols])
+    R, T = len(cols), int(lengths.max())
+    states = np.zeros((R, T, 6), f32)
+    tp, te, labels = np.zeros((R, T), f32), np.zeros((R, T), f32), np.zeros((R, T), f32)
+    for r, c in enumerate(cols):
+        n = lengths[r]
+        states[r, :n] = np.stack([c[f] for f in FEATURES], axis=-1)
+        tp[r, :n], te[r, :n], labels[r, :n] = c["target_position"], c["target_equilibrium"], c[label_column]
+    return states, tp, te, labels, lengths, names
+
+
+def main(argv=None):
+    """python -m cartpolesimulation_amd.train_imitator --recordings DIR --out FOLDER --config-root CHECKOUT
+    [--label-column Q_calculated_offline] [--validation DIR] [--init FOLDER]"""
+    import argparse
+    import yaml
+    ap = argparse.ArgumentParser(description="Train the neural imitator (Dense-7IN-32H1-32H2-1OUT) on relabelled recordings, on MI355X "
+                                             "(reference: SI_Toolkit_ASF/Run/A2_Train_Network.py, config_training.yml as shipped)")
+    ap.add_argument("--recordings", required=True, metavar="DIR", help="a folder of recording CSVs with the label column (along_trajectories writes them)")
+    ap.add_argument("--validation", default=None, metavar="DIR", help="a folder of recordings scored after every epoch")
+    ap.add_argument("--out", required=True, metavar="FOLDER", help="the model folder to write (e.g. .../Dense-7IN-32H1-32H2-1OUT-0)")
+    ap.add_argument("--config-root", default=None, metavar="CHECKOUT",
+                    help="a CartPoleSimulation checkout: SI_Toolkit_ASF/config_training.yml, taken as shipped; without it its values")
+    ap.add_argument("--config-training", default=None, metavar="FILE", help="a config_training.yml elsewhere than in the checkout")
+    ap.add_argument("--label-column", default=LABEL_COLUMN, help="the column to imitate (default: what along_trajectories writes)")
+    for flag, typ in (("--epochs", int), ("--batch-size", int), ("--seed", int), ("--lr", float), ("--post-wash-out", int),
+                      ("--shift-labels", int)):
+        ap.add_argument(flag, type=typ, default=None, help="instead of the file's value")
+    ap.add_argument("--init", default=None, metavar="FOLDER", help="fine-tune the model of this folder, with its normalisation")
+    ap.add_argument("--device", type=int, default=0)
+    args = ap.parse_args(argv)
+    path = args.config_training or (os.path.join(args.config_root, "SI_Toolkit_ASF", "config_training.yml") if args.config_root else None)
+    config = {"modeling": {"NET_NAME": NET_NAME},
+              "training_default": {"state_inputs": list(DENSE_INPUTS), "outputs": ["Q_calculated"], "SEED": 1873, "SHIFT_LABELS": 0}}
+    if path is not None:
+        with open(path) as fh:
+            config = yaml.safe_load(fh) or {}
+    try:
+        settings, normalize = training_settings(config, epochs=args.epochs, batch_size=args.batch_size, seed=args.seed, lr=args.lr,
+                                                post_wash_out=args.post_wash_out, shift_labels=args.shift_labels)
+    except ValueError as e:
+        raise SystemExit(f"train_imitator: {e}")
+    info = {"WASH OUT LENGTH": 0, "POST WASH OUT LENGTH": settings["post_wash_out"], "SHIFT LABELS": settings["shift_labels"],
+            "TRAINING_FILES": os.path.abspath(args.recordings)}
+    if args.init is not None:
+        from .model_folder import load_dense_model
+        init = dict(load_dense_model(os.fspath(args.init)))
+        if any(init.get(k) is None for k in NORM_KEYS):       # (a folder with NORMALIZE False: the identity, not the recordings')
+            init.update(identity_normalization())
+        info["PARENT NET"] = os.path.abspath(os.fspath(args.init))
+    else:
+        init = initial_weights(settings["seed"])
+        if not normalize:
+            init.update(identity_normalization())
+    *train, lengths, names = load_recordings_folder(args.recordings, args.label_column)
+    validation = load_recordings_folder(args.validation, args.label_column)[:5] if args.validation else None
+    from .configs import MPPIConfig
+    from .engine import MPPIEngine
+    engine = MPPIEngine(1, MPPIConfig(num_rollouts=1, mpc_horizon=2), device=args.device)
+    model, history = train_imitator(engine, *train, lengths, validation=validation, init=init, log=print, **settings)
+    engine.close()
+    folder = write_model_folder(args.out, model, info=info)
+    print(f"trained on {len(names)} recordings, final loss {history['loss'][-1]:.6e}; model folder: {folder}")
+    return model, history
+
+
+if __name__ == "__main__":
+    main()

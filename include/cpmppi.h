@@ -65,7 +65,10 @@ extern "C" {
                                       (new entry points, likewise);
                                       cpmppi_gru_rollout_loss_grad / cpmppi_gru_rollout_train_step (new entry points, likewise);
                                       cpmppi_ode_fit_loss_grad / cpmppi_ode_fit_args, cpmppi_ode_fit_reserve / _begin / _set_theta /
-                                      _step / _get (new entry points, likewise). */
+                                      _step / _get (new entry points, likewise);
+                                      cpmppi_set_dense / cpmppi_dense_model, cpmppi_dense_control / cpmppi_dense_control_args,
+                                      cpmppi_dense_loss_grad / cpmppi_dense_loss_args, cpmppi_dense_train_reserve / _begin / _step /
+                                      _get (new entry points, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -645,6 +648,102 @@ int cpmppi_ode_fit_set_theta(cpmppi_handle* h, const float* theta_host);
 int cpmppi_ode_fit_step(cpmppi_handle* h, const cpmppi_ode_fit_args* args, float lr, float beta1, float beta2, float eps,
                         void* stream);
 int cpmppi_ode_fit_get(cpmppi_handle* h, float* params_host, float* theta_host);
+
+/* The NEURAL IMITATOR of the MPC: the one Dense network the reference ships (GymlikeCartPole/Dense-7IN-32H1-32H2-1OUT-0/, forward
+ * pass C_implementation/network.c; config_training.yml configures its training as shipped) as a controller and its training on
+ * recordings.  7 inputs -> 32 tanh -> 32 tanh -> 1 linear output.  The reference's controller_neural_imitator lives in a submodule
+ * that is absent from the reference checkout, and so does the training code: the semantics below - the feature order, the clip of
+ * the control, windows, loss and schedule - are THIS LIBRARY'S OWN.  Other layer sizes, activations, several models per launch and a
+ * Dense dynamics model inside an optimizer are not built.
+ * The parameters are ONE flat float32 DEVICE vector of CPMPPI_DENSE_PARAMS = 1345 floats in torch.nn.Linear order ([out,in]):
+ *   w1[32,7] b1[32] w2[32,32] b2[32] w3[1,32] b3[1].
+ * The 7 inputs in the shipped folder's (alphabetical) order: angleD, angle_cos, angle_sin, position, positionD,
+ * target_equilibrium, target_position.  Normalisation: x_n = in_scale x + in_shift per input; Q = out_scale y + out_shift for the
+ * head's output y.  That vector is the only image: the control kernel and the training kernels read it as it stands and Adam
+ * updates it in place - nothing is repacked.  tanh is the one of the exact-f32 GRU cell: 1 - 2 / (exp(2x) + 1).
+ *
+ * cpmppi_set_dense: HOST pointers; in_scale / in_shift [7] and out_scale / out_shift [1] may be NULL (identity).  Everything that
+ * can refuse runs on host copies before the handle changes - a NULL weight array, a non-finite value in any of the eight arrays
+ * (CPMPPI_ERR_BAD_ARG, "cpmppi_set_dense: ...") -: a refused call leaves the model held, the bits of cpmppi_dense_control and a
+ * live training run as they were.  A successful call ENDS a training run (as cpmppi_set_gru does).  Synchronous.
+ *
+ * cpmppi_dense_control: one control per env, Q_out[e] = clamp(out_scale y + out_shift, -1, 1), from the state s[E,6] in this
+ * library's layout (angle, angleD, angle_cos, angle_sin, position, positionD; the angle itself is not an input) and the env's
+ * targets.  y_out[E], optional: the head's normalised output y before de-normalisation and clip.  A NaN in an env's inputs gives
+ * a NaN control in that env (the clamp passes it on) and touches no other env.  With count_dev: *count_dev += 1 after the step,
+ * stream-ordered, exactly as cpmppi_rpgd_step documents it - a captured graph of (control, plant step with period_dev) replays.
+ * One launch (a lane per env; the weights arrive wave-uniform through the constant address space), no host synchronisation, no
+ * allocation.  Refused ("cpmppi_dense_control: ..."), nothing launched: no model set; E == 0; a NULL s, target_position,
+ * target_equilibrium or Q_out; a misaligned pointer (CPMPPI_ERR_ALIGN; count_dev: 8 bytes).
+ *
+ * cpmppi_dense_loss_grad: B windows (r, t0) of P = post_wash_out rows over recordings states[R,T,6], target_position[R,T],
+ * target_equilibrium[R,T], labels[R,T].  The network has no memory, so a window is P independent samples: sample (b, j) reads the
+ * inputs of row t0 + j and the label of row t0 + j + shift_labels.  loss = the mean over the B P samples of
+ * (y - (label - out_shift) / out_scale)^2.  loss_out: one DEVICE double.  grad_out[CPMPPI_DENSE_PARAMS] DEVICE floats: d loss / d
+ * parameters in the flat order, or NULL for the loss alone (validation), which equals the loss of a gradient call bit for bit.
+ * Two launches: (1) forward, backward and, per workgroup of 128 samples, its own row of partial sums written with plain stores - the
+ * contraction over the samples (d w2 = sum dz2 (x) h1, likewise d w1, d w3 and the bias sums against ones) on
+ * v_mfma_f32_32x32x2_f32 in exact f32 with the sample as the contraction index; (2) one workgroup walks the rows first to last in
+ * float64 and scales by 2 / (B P).  No atomics, every sum in a fixed order: the same bits from run to run, whatever ran before.
+ * The rows are reserved by cpmppi_dense_train_reserve(h, samples) for calls of up to `samples` = B P, or on first use - a capture
+ * that would have to allocate is refused.
+ * Refused ("cpmppi_dense_loss_grad: ..."), nothing launched: no model set; a NULL states, target_position, target_equilibrium,
+ * labels, windows, windows_host or loss_out; B, R, T or post_wash_out equal to 0; more than 2^31 samples; a host window outside
+ * r < R, t0 + P - 1 + shift_labels <= T - 1.  A misaligned pointer is CPMPPI_ERR_ALIGN.
+ *
+ * cpmppi_dense_train_begin: a run starts from the model held: both Adam moments and the device step counter zero.  Synchronous.
+ * cpmppi_dense_train_step: launch (1) of cpmppi_dense_loss_grad (grad_out is not read), then launch (2) which also applies the
+ * bias-corrected Adam update stated at cpmppi_gru_train_step to the parameter vector IN PLACE, t = the device counter + 1, the
+ * gradient and the update formed in float64, moments and parameters stored as float32.  A parameter whose gradient is exactly 0 and
+ * whose moments are 0 keeps its bits.  From the next launch on cpmppi_dense_control runs the trained model.  No host
+ * synchronisation: capturable after a reserving call.  loss_out: the batch's loss BEFORE the update.
+ * cpmppi_dense_train_get: the parameter vector -> params_host[CPMPPI_DENSE_PARAMS], synchronously.
+ * cpmppi_dense_train_step and _get before cpmppi_dense_train_begin, or after a successful cpmppi_set_dense:
+ * CPMPPI_ERR_BAD_ARG ("...: call cpmppi_dense_train_begin first"), nothing launched. */
+#define CPMPPI_DENSE_PARAMS 1345u
+typedef struct {
+  const float* w1;                      /* [32,7]  HOST, rows = units, columns in the input order above */
+  const float* b1;                      /* [32] */
+  const float* w2;                      /* [32,32] */
+  const float* b2;                      /* [32] */
+  const float* w3;                      /* [1,32] */
+  const float* b3;                      /* [1] */
+  const float* in_scale;                /* [7] or NULL (1) */
+  const float* in_shift;                /* [7] or NULL (0) */
+  const float* out_scale;               /* [1] or NULL (1) */
+  const float* out_shift;               /* [1] or NULL (0) */
+} cpmppi_dense_model;
+typedef struct {
+  uint32_t E;                           /* envs */
+  const float* s;                       /* [E,6] */
+  const float* target_position;         /* [E] */
+  const float* target_equilibrium;      /* [E] */
+  float* Q_out;                         /* [E] */
+  float* y_out;                         /* [E] or NULL */
+  unsigned long long* count_dev;        /* DEVICE counter advanced by one behind the step, or NULL */
+} cpmppi_dense_control_args;
+typedef struct {
+  uint32_t B;                           /* windows */
+  uint32_t R, T;                        /* recordings, rows of each */
+  uint32_t post_wash_out;               /* P >= 1 rows per window, each one sample */
+  uint32_t shift_labels;                /* the label of a row lies this many rows on (0 for an imitator) */
+  const float* states;                  /* [R,T,6] */
+  const float* target_position;         /* [R,T] */
+  const float* target_equilibrium;      /* [R,T] */
+  const float* labels;                  /* [R,T] the control to imitate */
+  const uint32_t* windows;              /* [B][2] DEVICE: (r, t0) */
+  const uint32_t* windows_host;         /* [B][2] HOST: the same, checked by every call */
+  double* loss_out;                     /* DEVICE, one double */
+  float* grad_out;                      /* [CPMPPI_DENSE_PARAMS] DEVICE, or NULL */
+} cpmppi_dense_loss_args;
+int cpmppi_set_dense(cpmppi_handle* h, const cpmppi_dense_model* model);
+int cpmppi_dense_control(cpmppi_handle* h, const cpmppi_dense_control_args* args, void* stream);
+int cpmppi_dense_train_reserve(cpmppi_handle* h, uint32_t samples);
+int cpmppi_dense_loss_grad(cpmppi_handle* h, const cpmppi_dense_loss_args* args, void* stream);
+int cpmppi_dense_train_begin(cpmppi_handle* h);
+int cpmppi_dense_train_step(cpmppi_handle* h, const cpmppi_dense_loss_args* args, float lr, float beta1, float beta2, float eps,
+                            void* stream);
+int cpmppi_dense_train_get(cpmppi_handle* h, float* params_host);
 
 /* Rollout + cost only (no update): per-rollout trajectory cost S[E,N] of GIVEN input sequences inputs[E,N,H] under the
  * handle's plugin cost — cost_function.get_trajectory_cost(predictor.predict_core(s, Q), Q) fused; the building block of
