@@ -10,6 +10,8 @@
 //                               across the workgroup's tiles.  The workgroup writes its own row of the partials with plain stores.
 //   dense_finalize_kernel       ONE workgroup walks the partial rows first to last in float64: loss, gradient; with `update` Adam on
 //                               the parameter vector in place.
+//   dagger_step_kernel          one lane = one env (cpmppi_dagger_step): the control kernel's forward body on the live parameter
+//                               vector, one Philox block for the gate, the applied control, the sample into the trainer's tensors.
 // The parameter vector is the only image of the weights.  Every kernel reads it through the constant address space: the index is
 // wave-uniform, so a weight arrives as a scalar-load operand of the lane's FMA - no LDS staging, no barrier in front of the first
 // layer, and the 5.4 KB vector stays in the scalar cache for every wave of the launch (DESIGN.md N7 records the choice).
@@ -23,6 +25,7 @@
 #include "cpmppi_gru.hpp"          // (gru_tanh, f16v, gru_tile_row: the exact-f32 cell's tanh and the MFMA accumulator layout)
 #include "cpmppi_wave.hpp"
 #include "cpmppi_train.hpp"
+#include "cpmppi_philox.hpp"       // (philox4x32_10: the gate of dagger_step_kernel)
 
 using namespace cpmppi_k;
 using cpmppi::f16v;
@@ -89,6 +92,51 @@ __global__ __launch_bounds__(BLOCK) void dense_control_kernel(const DenseNorm nm
   const float q = __builtin_fmaf(nm.out_scale, y, nm.out_shift);
   a.Q_out[e] = q > 1.0f ? 1.0f : (q < -1.0f ? -1.0f : q);   // (both comparisons are false for a NaN: it passes)
   if (a.y_out) a.y_out[e] = y;
+}
+
+// sum + d * d in two roundings, as a host evaluation of the recurrence forms it (no FMA: cpmppi.h promises these bits)
+__device__ __forceinline__ double add_square(double sum, double d) {
+#pragma clang fp contract(off)
+  const double sq = d * d;
+  return sum + sq;
+}
+
+// One DAgger control period, a lane per env: the imitator's control (the body of dense_control_kernel), the gate's Philox block,
+// the applied control, the sample into row (r0 + e, c) of the trainer's tensors, the disagreement.  Nothing is shared between lanes.
+__global__ __launch_bounds__(BLOCK) void dagger_step_kernel(const DenseNorm nm, const float* params, const cpmppi_dagger_args a) {
+  const uint32_t e = blockIdx.x * BLOCK + threadIdx.x;
+  if (e >= a.E) return;
+  // the period: the host's, or the device counter's (already advanced by the expert's step); a counter still 0 counts as period 0
+  uint64_t c = a.period;
+  if (a.period_dev) {
+    const uint64_t cnt = (uint64_t)*a.period_dev;
+    c = cnt ? cnt - 1u : 0u;
+  }
+  const float* se = a.s + (size_t)e * 6;
+  const float te = a.target_equilibrium[e], tp = a.target_position[e], q_exp = a.Q_expert[e];
+  float x[NIN], h1[NH], h2[NH];
+  dense_inputs(nm, se, te, tp, x);
+  const float y = dense_forward(constant_(params), x, h1, h2);
+  const float q = __builtin_fmaf(nm.out_scale, y, nm.out_shift);
+  const float q_imi = q > 1.0f ? 1.0f : (q < -1.0f ? -1.0f : q);
+  // the gate: rollout index 0xFFFFFFFF is no rollout's, so the block is none of the sampler's; the sampler's key
+  uint32_t c0 = 0xFFFFFFFFu, c1 = a.env_offset + e, c2 = 0u, c3 = (uint32_t)c;
+  cpmppi::philox4x32_10(c0, c1, c2, c3, (uint32_t)a.seed ^ 0x51ed270bu, (uint32_t)(a.seed >> 32) ^ (uint32_t)(c >> 32));
+  const float ub = (float)(c1 >> 8) * 5.9604644775390625e-8f;          // [0, 1), 24 bits
+  const bool expert = ub < a.beta[e];                                  // (false for a NaN beta)
+  a.Q_out[e] = expert ? q_exp : q_imi;
+  if (c < (uint64_t)a.T) {
+    const size_t row = (size_t)(a.r0 + e) * a.T + (size_t)c;
+    float* so = a.states + row * 6;
+#pragma unroll
+    for (int k = 0; k < 6; ++k) so[k] = se[k];
+    a.rec_target_position[row] = tp;
+    a.rec_target_equilibrium[row] = te;
+    a.labels[row] = q_exp;
+    if (a.imitator_out) a.imitator_out[row] = q_imi;
+    if (a.gate_out) a.gate_out[row] = expert ? 1u : 0u;
+    if (a.sq_err) a.sq_err[e] = add_square(a.sq_err[e], (double)q_imi - (double)q_exp);   // (of the samples recorded: past the end, none)
+  }
 }
 
 struct DenseLossArgs {
@@ -378,6 +426,36 @@ int cpmppi_dense_control(cpmppi_handle* h, const cpmppi_dense_control_args* a, v
   CPMPPI_ON_DEVICE(h);
   const DenseNet* st = h->dense;
   hipLaunchKernelGGL(dense_control_kernel, dim3((a->E + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)stream, st->norm,
+                     (const float*)st->state, *a);
+  return launched(h);
+} catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }
+
+int cpmppi_dagger_step(cpmppi_handle* h, const cpmppi_dagger_args* a, void* stream) try {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  const char* who = "cpmppi_dagger_step";
+  const auto refuse = [&](const std::string& why) { return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": " + why); };
+  if (!a) return refuse("no argument block");
+  if (!has_model(h)) return no_model(h, who);
+  if (a->E == 0) return refuse("E must be at least 1");
+  if (a->E > h->cfg.E) return refuse(std::to_string(a->E) + " envs, the handle has " + std::to_string(h->cfg.E));
+  if (!a->s || !a->target_position || !a->target_equilibrium || !a->Q_expert || !a->beta || !a->Q_out)
+    return refuse("s, target_position, target_equilibrium, Q_expert, beta and Q_out are required");
+  if (!a->states || !a->rec_target_position || !a->rec_target_equilibrium || !a->labels)
+    return refuse("the dataset's states, rec_target_position, rec_target_equilibrium and labels are required");
+  if (a->R == 0 || a->T == 0) return refuse("R and T must be at least 1");
+  if ((uint64_t)a->r0 + a->E > a->R)
+    return refuse("recordings r0 .. r0 + E - 1 = " + std::to_string(a->r0) + " .. " + std::to_string((uint64_t)a->r0 + a->E - 1) +
+                  " do not lie in the dataset's " + std::to_string(a->R));
+  if (a->Q_out < a->Q_expert + a->E && a->Q_expert < a->Q_out + a->E)
+    return refuse("Q_out overlaps Q_expert (the label is the expert's control, whichever of the two drives)");
+  if (misaligned(a->s) || misaligned(a->target_position) || misaligned(a->target_equilibrium) || misaligned(a->Q_expert) ||
+      misaligned(a->beta) || misaligned(a->Q_out) || misaligned(a->states) || misaligned(a->rec_target_position) ||
+      misaligned(a->rec_target_equilibrium) || misaligned(a->labels) || misaligned(a->imitator_out) || misaligned8(a->sq_err) ||
+      misaligned8(a->period_dev))
+    return fail(h, CPMPPI_ERR_ALIGN, std::string(who) + ": misaligned pointer");
+  CPMPPI_ON_DEVICE(h);
+  const DenseNet* st = h->dense;
+  hipLaunchKernelGGL(dagger_step_kernel, dim3((a->E + BLOCK - 1) / BLOCK), dim3(BLOCK), 0, (hipStream_t)stream, st->norm,
                      (const float*)st->state, *a);
   return launched(h);
 } catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }

@@ -19,7 +19,8 @@
 //   cpmppi_ode_fit.hip    fitting the ODE predictor's physical parameters to recordings: open-loop loss, forward-mode gradient, Adam
 //                         on the device (cpmppi_ode_fit_*)
 //   cpmppi_dense.hip      the neural imitator (Dense-7IN-32H1-32H2-1OUT): the control kernel, loss and gradient over recordings with the
-//                         batch contraction on MFMA, Adam on the device (cpmppi_set_dense, cpmppi_dense_*)
+//                         batch contraction on MFMA, Adam on the device (cpmppi_set_dense, cpmppi_dense_*); the DAgger control period
+//                         on the same forward body (cpmppi_dagger_step)
 //   cpmppi_gru_model.hip  host code only: cpmppi_set_gru packs and uploads the three weight images
 //   cpmppi_comm.hip, cpmppi_groups.hip, cpmppi_io.hip   host code only: the collective, env groups, the recording writer
 //   cpmppi_rollout_*.hip  the instances of rollout_cost_kernel, each unit with its own compiler flags

@@ -867,6 +867,56 @@ class MPPIEngine:
         buffers (the device loop, a capture)."""
         return self._build_dense_control(*args, **kwargs)
 
+    def _build_dagger_step(self, s, target_position, target_equilibrium, Q_expert, beta, Q_out, states, rec_target_position,
+                           rec_target_equilibrium, labels, *, r0=0, seed=0, env_offset=0, period=0, period_dev=None,
+                           imitator_out=None, gate_out=None, sq_err=None):
+        """cpmppi_dagger_step: one DAgger control period for every env (include/cpmppi.h states it) - the imitator's control of
+        ``s`` [E,6] and the targets [E], the coin of ``beta`` [E] (Philox: ``seed``, ``env_offset``, the period), ``Q_out`` [E] =
+        ``Q_expert`` where the expert drives and the imitator's control elsewhere, and the sample into row (``r0`` + e, period) of
+        the dataset ``states`` [R,T,6], ``rec_target_position``, ``rec_target_equilibrium``, ``labels`` [R,T] (``labels`` <-
+        ``Q_expert``).  Optional: ``imitator_out`` [R,T], ``gate_out`` [R,T] uint8, ``sq_err`` [E] float64 (accumulated).  The
+        period is ``period``, or ``period_dev`` - 1: an int64 device counter the expert's step has advanced already.  Every tensor
+        on the device; one launch, nothing allocated.  -> Q_out."""
+        self._need_dense()
+        E = device_tensor("s", s, tail=(6,)).shape[0]
+        if E == 0:
+            raise ValueError("s must be [E,6] with E >= 1")
+        for name, t in (("target_position", target_position), ("target_equilibrium", target_equilibrium), ("Q_expert", Q_expert),
+                        ("beta", beta), ("Q_out", Q_out)):
+            if device_tensor(name, t).shape != (E,):
+                raise ValueError(f"{name} must be [{E}] for s [{E},6]")
+        if device_tensor("states", states).dim() != 3 or states.shape[2] != 6:
+            raise ValueError("states must be [R,T,6]")
+        R, T = states.shape[:2]
+        for name, t, dtype in (("rec_target_position", rec_target_position, torch.float32),
+                               ("rec_target_equilibrium", rec_target_equilibrium, torch.float32), ("labels", labels, torch.float32),
+                               ("imitator_out", imitator_out, torch.float32), ("gate_out", gate_out, torch.uint8)):
+            optional = name in ("imitator_out", "gate_out")
+            if not (optional and t is None) and device_tensor(name, t, dtype).shape != (R, T):
+                raise ValueError(f"{name} must be [{R},{T}] for states [{R},{T},6]")
+        if sq_err is not None and device_tensor("sq_err", sq_err, torch.float64).shape != (E,):
+            raise ValueError(f"sq_err must be [{E}] float64")
+        r0, period = int(r0), int(period)
+        if r0 < 0 or period < 0:
+            raise ValueError("r0 and period must not be negative")
+        a = _L.cpmppi_dagger_args()
+        a.E, a.s, a.target_position, a.target_equilibrium = E, s.data_ptr(), target_position.data_ptr(), target_equilibrium.data_ptr()
+        a.Q_expert, a.beta, a.Q_out = Q_expert.data_ptr(), beta.data_ptr(), Q_out.data_ptr()
+        a.seed, a.env_offset, a.period, a.period_dev = int(seed), int(env_offset), period, _counter("period_dev", period_dev)
+        a.R, a.T, a.r0 = R, T, r0
+        a.states, a.rec_target_position, a.rec_target_equilibrium = states.data_ptr(), rec_target_position.data_ptr(), rec_target_equilibrium.data_ptr()
+        a.labels, a.imitator_out, a.gate_out, a.sq_err = labels.data_ptr(), _addr(imitator_out), _addr(gate_out), _addr(sq_err)
+        keep = (s, target_position, target_equilibrium, Q_expert, beta, Q_out, period_dev, states, rec_target_position,
+                rec_target_equilibrium, labels, imitator_out, gate_out, sq_err)
+        return PreparedCall(self, self.lib.cpmppi_dagger_step, a, keep, Q_out, ("period",))
+
+    dagger_step = _run_once(_build_dagger_step)
+
+    def prepare_dagger_step(self, *args, **kwargs):
+        """The argument block of ``dagger_step(...)`` built and validated ONCE: ``.run(period=c)`` names the period and enqueues the
+        launch again on the same buffers (the device loop; a capture, with ``period_dev``)."""
+        return self._build_dagger_step(*args, **kwargs)
+
     def _dense_loss_args(self, states, target_position, target_equilibrium, labels, windows, post_wash_out, shift_labels,
                          loss_out=None, grad_out=None, grad=True):
         """The argument block of cpmppi_dense_loss_grad / cpmppi_dense_train_step, checked: -> (block, what it points into, loss_out,
@@ -1589,7 +1639,7 @@ class MPPIEngine:
 
 class PreparedCall:
     """One entry point of the library that takes an argument block, ready to be enqueued any number of times
-    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_rpgd_step_gru / prepare_cem_step / prepare_cem_step_gru / prepare_brunton / prepare_gru_loss_grad / prepare_ode_fit_loss_grad / prepare_ode_fit_step / prepare_dense_control / prepare_dense_loss_grad / prepare_dense_train_step).  ``args`` is the live
+    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_rpgd_step_gru / prepare_cem_step / prepare_cem_step_gru / prepare_brunton / prepare_gru_loss_grad / prepare_ode_fit_loss_grad / prepare_ode_fit_step / prepare_dense_control / prepare_dagger_step / prepare_dense_loss_grad / prepare_dense_train_step).  ``args`` is the live
     ctypes block, validated when it was built, and ``ref`` the reference to it that the library is handed; ``keep`` holds the
     tensors it points into; ``enqueue`` is the entry point, ``enqueue(handle, ref, stream)``.  ``result`` is what the call returns:
     the outputs of a control step - ``out``, whose first two are ``Q_out`` and ``S_out`` -, the plant's state, or the Brunton

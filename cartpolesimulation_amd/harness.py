@@ -95,6 +95,52 @@ def check_imitator(imitator, optimizer=None, predictor="ODE_v0", h0=None, knots_
     return imitator
 
 
+ENGINE_MODEL = "engine-model"   # imitator= beside dagger=: the Dense model the engine holds as it stands (a training run goes on)
+
+
+def check_dagger(dagger, batch, imitator, optimizer=None, predictor="ODE_v0", h0=None, knots_fn=None, tuning=None):
+    """``dagger=dict(dataset=, beta=, seed=)`` of run_schedule: an expert of the device loop labels every state and the imitator -
+    or the coin of ``beta`` - drives.  Refused by name: everything the loop is not built for.  -> (the model dict for
+    ``MPPIEngine.set_dense`` or ENGINE_MODEL, the dataset, beta as float32 [E], the gate's seed)."""
+    if imitator is None:
+        raise ValueError("dagger= needs imitator=: the model that drives where the expert does not (a model dict, a model folder, or "
+                         "harness.ENGINE_MODEL for the one the engine holds)")
+    unknown = set(dagger) - {"dataset", "beta", "seed"}
+    if unknown or "dataset" not in dagger or "beta" not in dagger:
+        raise ValueError(f"dagger= takes dataset=, beta= and seed= (default 0), got {sorted(dagger)}")
+    if predictor == "GRU":
+        raise ValueError("dagger= and predictor='GRU': the GRU predictor as the expert is not built (its memory would have to follow "
+                         "the applied control)")
+    if h0 is not None:
+        raise ValueError("dagger= and h0: the memory belongs to the GRU predictor, which is not built as the expert")
+    if knots_fn is not None:
+        raise ValueError("dagger= and knots_fn: the expert draws its own Philox noise on the device")
+    if tuning is not None:
+        raise ValueError("dagger= and tuning=: per-env tuning rows of the expert are not built")
+    if optimizer is not None:
+        if getattr(optimizer, "gru_model", None) is not None or getattr(optimizer, "h", None) is not None:
+            raise ValueError("dagger= and an optimizer with gru_model=: a GRU-model optimizer as the expert is not built")
+        if not getattr(optimizer, "fused", False):
+            raise ValueError("dagger= and a host-paced optimizer=: the expert must stay on the device (the fused MPPI step, or rpgd / "
+                             "gradient with fused=True)")
+    dataset = dagger["dataset"]
+    if not isinstance(dataset, DaggerDataset):
+        raise ValueError("dagger=: dataset must be a harness.DaggerDataset")
+    if dataset.T != batch.n_periods + 1:
+        raise ValueError(f"dagger=: the dataset has {dataset.T} rows per recording, the batch makes {batch.n_periods + 1} controller "
+                         f"calls (n_periods + 1)")
+    beta = np.asarray(dagger["beta"], np.float32)
+    if beta.shape not in ((), (batch.E,)):
+        raise ValueError(f"dagger=: beta must be a scalar or [{batch.E}], got shape {beta.shape}")
+    beta = np.ascontiguousarray(np.broadcast_to(beta, (batch.E,)))
+    if isinstance(imitator, str) and imitator == ENGINE_MODEL:
+        imitator = ENGINE_MODEL
+    elif isinstance(imitator, (str, os.PathLike)):
+        from .model_folder import load_dense_model
+        imitator = load_dense_model(os.fspath(imitator))
+    return imitator, dataset, beta, int(dagger.get("seed", 0))
+
+
 def gru_memory(engine, E, h0):
     """The network's memory a run starts from: zeros [E,2,32], or a copy of ``h0`` (the run advances its own)."""
     return engine.zeros(E, 2, 32) if h0 is None else engine.tensor(h0, (E, 2, 32)).clone()
@@ -165,7 +211,7 @@ class BatchedCartPoleExperiment:
 
     # ------------------------------------------------------------------ the data generator's experiments (moving targets)
     def run_schedule(self, batch, env_offset=0, graph=False, steps_per_graph=10, knots_fn=None, u_nom0=None, optimizer=None,
-                     predictor="ODE_v0", h0=None, tuning=None, imitator=None):
+                     predictor="ODE_v0", h0=None, tuning=None, imitator=None, dagger=None):
         """Run the E experiments of a schedule.ExperimentBatch to their end: CartPole.run_cartpole_random_experiment
         (CartPole/__init__.py:659-735) for all of them at once.  Per control period two launches - the fused MPPI step, reading
         the period's target position / equilibrium (/ pole length) from three [E] vectors, and cpmppi_plant_step, which advances
@@ -196,13 +242,24 @@ class BatchedCartPoleExperiment:
         (``model_folder.load_dense_model``) - computes the controls instead: one cpmppi_dense_control per period on the state the
         controller is shown and the period's targets, then the plant; launched or captured; schedule tables, measurement chain,
         disturbance and ``score_runs`` apply unchanged.  Not with ``optimizer=``, ``predictor="GRU"``, ``gru_model=``, ``h0``,
-        ``knots_fn`` or ``tuning=`` (ValueError by name).  The engine keeps the model."""
-        imitator = check_imitator(imitator, optimizer, predictor, h0, knots_fn, tuning)
+        ``knots_fn`` or ``tuning=`` (ValueError by name).  The engine keeps the model.
+        ``dagger=dict(dataset=, beta=, seed=)``, only together with ``imitator=`` (DaggerController): the MPC - the fused MPPI step,
+        or a FUSED ``optimizer=`` - is the expert that labels every state the controller is shown, and per experiment and period it
+        drives with probability ``beta`` (a scalar or [E]; the coin is Philox of ``seed``), the imitator otherwise; every call's
+        sample lands in ``dataset`` (a DaggerDataset with n_periods + 1 rows per recording, E recordings reserved by this run).
+        ``imitator=harness.ENGINE_MODEL``: the model the engine holds as it stands (a training run goes on).  The result gains
+        ``Q_expert`` [E], the expert's last control, and ``recordings`` = (first, stop) of the dataset.  Not with
+        ``predictor="GRU"``, ``h0``, an optimizer with ``gru_model=``, a host-paced optimizer, ``knots_fn`` or ``tuning=``."""
+        if dagger is not None:
+            dagger = check_dagger(dagger, batch, imitator, optimizer, predictor, h0, knots_fn, tuning)
+            imitator = dagger[0]
+        else:
+            imitator = check_imitator(imitator, optimizer, predictor, h0, knots_fn, tuning)
         check_tuning(tuning, optimizer, predictor, knots_fn)
         if tuning is not None and tuple(np.shape(tuning))[:1] != (batch.E,):
             raise ValueError(f"tuning must hold one row per experiment ({batch.E}), got shape {tuple(np.shape(tuning))}")
         run = ScheduleRun(self.engine, batch, self.seed, env_offset=env_offset, knots_fn=knots_fn, u_nom0=u_nom0, optimizer=optimizer,
-                          predictor=predictor, h0=h0, imitator=imitator)
+                          predictor=predictor, h0=h0, imitator=imitator, dagger=dagger)
         if batch.dt_simulation != self.dt_simulation or batch.n_ctrl != self.n_sub:
             raise ValueError("the batch was drawn for other time scales than this experiment runner's")
         if graph and run.controller.cannot_capture:
@@ -509,6 +566,90 @@ class ImitatorController:
         self.call = None                                           # (built without the counter)
 
 
+class DaggerDataset:
+    """The aggregated dataset of DAgger on the device, in the layout ``MPPIEngine.dense_train_step`` reads where it lies:
+    ``states`` [R,T,6], ``target_position``, ``target_equilibrium``, ``labels`` [R,T] (the expert's controls), and beside them
+    ``imitator`` [R,T] (the imitator's controls), ``gate`` [R,T] uint8 (1 where the expert drove) and ``sq_err`` [R] float64 (per
+    recording the sum over its rows of (imitator - expert)^2).  ``filled``: the recordings written so far; a run of E experiments
+    reserves the next E."""
+
+    def __init__(self, engine, recordings, rows):
+        R, T = int(recordings), int(rows)
+        if R < 1 or T < 1:
+            raise ValueError(f"DaggerDataset needs at least one recording and one row, got {R} x {T}")
+        self.R, self.T, self.filled = R, T, 0
+        self.states = engine.zeros(R, T, 6)
+        self.target_position, self.target_equilibrium = engine.zeros(R, T), engine.zeros(R, T)
+        self.labels, self.imitator = engine.zeros(R, T), engine.zeros(R, T)
+        self.gate = torch.zeros(R, T, dtype=torch.uint8, device=self.states.device)
+        self.sq_err = torch.zeros(R, dtype=torch.float64, device=self.states.device)
+
+    tensors = property(lambda self: (self.states, self.target_position, self.target_equilibrium, self.labels))
+
+    def reserve(self, E):
+        """-> the first of the next ``E`` recordings, which are the caller's from now on."""
+        E = int(E)
+        if E < 1 or self.filled + E > self.R:
+            raise ValueError(f"DaggerDataset is full: {self.filled} of its {self.R} recordings are written, {E} more do not fit")
+        r0 = self.filled
+        self.filled += E
+        return r0
+
+
+class ExpertBuffers:
+    """The buffers of a schedule run as the expert of a DAgger run sees them: everything the run's own, but ``Q`` - a private buffer
+    for the expert's controls, so that the run's ``Q`` is left to the applied ones."""
+
+    def __init__(self, buffers):
+        self._buffers = buffers
+        self.Q = buffers.Q.clone()
+
+    def __getattr__(self, name):                                   # (only what the instance itself does not hold)
+        return getattr(self.__dict__["_buffers"], name)
+
+
+class DaggerController:
+    """DAgger in the device loop: the ``expert`` - a FusedMppiStep over the engine's equations or a FusedOptimizer, built on
+    ExpertBuffers so that its controls go to a private ``Q_expert`` - computes its control of every period, then one
+    cpmppi_dagger_step computes the imitator's, tosses the coin of ``beta`` [E], writes the applied control where the plant reads it
+    (its ``Q_log`` and ``Q_applied_out`` therefore see the applied control) and the sample - the state shown, the targets, the
+    expert's control as the label - into recordings ``r0 .. r0 + E - 1`` of the ``dataset``.
+    The expert's plan stays warm-started from ITS OWN previous solution whoever drove, as ``control_along_trajectories(
+    warm_start=True)`` does for rows it did not drive; a cost that reads the previous input is handed the applied one.
+    Captured if the expert can be: the dagger step reads the period off the expert's device counter."""
+
+    def __init__(self, engine, buffers, expert, expert_buffers, dataset, beta, seed, env_offset=0):
+        self.eng, self.buf, self.expert, self.dataset = engine, buffers, expert, dataset
+        E = buffers.s.shape[0]
+        if buffers.Q is expert_buffers.Q:                          # (never: the expert writes a buffer of its own)
+            raise ValueError("the expert must write its own controls buffer")
+        self.Q_expert = expert_buffers.Q
+        if isinstance(expert, FusedOptimizer):
+            buffers.Q.copy_(self.Q_expert)                         # (what the first call reads as the control applied before it)
+            expert.previous_input = buffers.Q
+        self.beta = engine.tensor(np.ascontiguousarray(beta, np.float32))
+        self.seed, self.env_offset = int(seed), int(env_offset)
+        self.r0 = dataset.reserve(E)
+        self.call = None
+
+    cannot_capture = property(lambda self: self.expert.cannot_capture)
+    counter = property(lambda self: self.expert.counter)
+
+    def control(self, c):
+        self.expert.control(c)
+        if self.call is None:                                      # (built once: the buffers persist)
+            buf, d = self.buf, self.dataset
+            self.call = self.eng.prepare_dagger_step(
+                buf.s_ctrl, buf.cur_tp, buf.cur_te, self.Q_expert, self.beta, buf.Q, *d.tensors, r0=self.r0, seed=self.seed,
+                env_offset=self.env_offset, period_dev=self.expert.counter, imitator_out=d.imitator, gate_out=d.gate,
+                sq_err=d.sq_err[self.r0:self.r0 + buf.s.shape[0]])
+        self.call.run(period=c)                                    # (None under capture: the device counter names it)
+
+    def before_capture(self):
+        self.expert.before_capture()
+        self.call = None                                           # (built without the counter)
+
+
 def _tell_optimizer(optimizer, buffers, mass, c):
     """What the simulator hands controller.step (CartPole/__init__.py:509-520), as attributes of the optimizer's variable_parameters
     (the pole mass of call c; None under capture: it stays).  -> them."""
@@ -586,9 +727,10 @@ class ScheduleRun:
     told, and the `loop` that launches or replays the periods."""
 
     def __init__(self, engine, batch, seed, env_offset=0, knots_fn=None, u_nom0=None, optimizer=None, predictor="ODE_v0", h0=None,
-                 imitator=None):
+                 imitator=None, dagger=None):
         """``imitator``: the model dict of the neural imitator (``check_imitator`` has refused what cannot stand beside it); the engine
-        takes it (``set_dense``) and it computes the controls."""
+        takes it (``set_dense``) and it computes the controls.  ``dagger``: what ``check_dagger`` returns - the MPC is the expert of
+        a DaggerController, and ``imitator`` may be ENGINE_MODEL (nothing is set)."""
         gru = check_predictor(engine, predictor, h0, optimizer, knots_fn)
         if optimizer is not None:
             if getattr(optimizer, "num_envs", batch.E) != batch.E:
@@ -600,18 +742,22 @@ class ScheduleRun:
         self.buffers = buf = ScheduleBuffers(engine, batch, u_nom0)
         self.T, self.tail = buf.T, buf.tail
         # (an optimizer object that runs the network - gru_model=, its memory `h` once configured - reads no pole mass either)
-        network = (gru or imitator is not None or getattr(optimizer, "h", None) is not None
+        network = (gru or (imitator is not None and dagger is None) or getattr(optimizer, "h", None) is not None
                    or getattr(optimizer, "gru_model", None) is not None)
         self.mass = ControllerMass(batch, engine.mppi, network=network)
         self.mass.bind([engine], register=optimizer is None)       # (an optimizer object registers the row with its own engine)
         self.memory = gru_memory(engine, batch.E, h0) if gru else None
-        if imitator is not None:
+        mpc = buf if dagger is None else ExpertBuffers(buf)        # what the MPC writes its controls into
+        if imitator is not None and imitator is not ENGINE_MODEL:
             engine.set_dense(imitator)
+        if imitator is not None and dagger is None:
             self.controller = ImitatorController(engine, buf)
         elif optimizer is None:
-            self.controller = FusedMppiStep(engine, buf, self.mass, seed, env_offset, knots_fn, self.memory)
+            self.controller = FusedMppiStep(engine, mpc, self.mass, seed, env_offset, knots_fn, self.memory)
         else:
-            self.controller = optimizer_controller(optimizer)(optimizer, buf, self.mass)
+            self.controller = optimizer_controller(optimizer)(optimizer, mpc, self.mass)
+        if dagger is not None:
+            self.controller = DaggerController(engine, buf, self.controller, mpc, *dagger[1:], env_offset=env_offset)
         self.fused = isinstance(self.controller, FusedOptimizer)
         self.loop = PeriodLoop(engine, self.T)
         self._plant = None                                         # the plant launch at the host's period: built once
@@ -668,6 +814,9 @@ class ScheduleRun:
         res = self.buffers.result()
         if self.memory is not None:
             res["memory"] = self.memory
+        if isinstance(self.controller, DaggerController):
+            res["Q_expert"] = self.controller.Q_expert
+            res["recordings"] = (self.controller.r0, self.controller.r0 + self.buffers.s.shape[0])
         return res
 
 

@@ -25,6 +25,16 @@ several models per launch, env groups and multi-GPU.
 
   python -m cartpolesimulation_amd.train_imitator --recordings DIR --out FOLDER --config-root CHECKOUT
                                                   [--label-column Q_calculated_offline] [--validation DIR] [--init FOLDER]
+
+``dagger`` closes that chain on the device (DAgger, Ross et al. 2011: the reference does its rounds by hand - run, relabel with
+PreprocessData_Add_Control_Along_Trajectories.py, retrain): per iteration the MPC labels every state of fresh experiments and, with
+probability beta, drives them, the imitator otherwise (cpmppi_dagger_step, harness.DaggerController); the samples land in the layout
+the trainer reads, and the Adam steps follow on the aggregate where it lies.  Schedule, windows (single rows drawn uniformly) and the
+fixed normalisation are again THIS PACKAGE'S OWN.  Not built: the GRU predictor or a GRU-model optimizer as the expert, env groups
+and several GPUs, beta per episode, sample weighting or eviction.
+
+  python -m cartpolesimulation_amd.train_imitator --dagger ITERATIONS --beta 1,0.5,0.25,0 --experiments E --steps-per-iteration K
+                                                  --config-root CHECKOUT --out FOLDER [--optimizer rpgd] [--init FOLDER] [--graph]
 """
 import os
 
@@ -71,7 +81,13 @@ def normalization_from_recordings(states, target_position, target_equilibrium, l
         raise ValueError("no rows")
     cols = [states[:, :, c][keep].astype(np.float64) for c in _STATE_COLUMNS] + [te[keep].astype(np.float64), tp[keep].astype(np.float64),
                                                                                  labels[keep].astype(np.float64)]
-    lo, hi = np.array([c.min() for c in cols]), np.array([c.max() for c in cols])
+    return normalization_from_extrema(np.array([c.min() for c in cols]), np.array([c.max() for c in cols]))
+
+
+def normalization_from_extrema(lo, hi):
+    """``normalization_from_recordings`` from the minima and maxima [8] alone: the seven inputs in the order of
+    ``model_folder.DENSE_INPUTS``, then the label."""
+    lo, hi = np.asarray(lo, np.float64), np.asarray(hi, np.float64)
     names = DENSE_INPUTS + ("the label",)
     flat = [names[i] for i in (0, 1, 2, 3, 4, 7) if not hi[i] > lo[i]]
     if flat:
@@ -145,6 +161,121 @@ def train_imitator(engine, states, target_position, target_equilibrium, labels, 
                             plateau=(reduce_lr_on_plateau, patience, decrease_factor, minimal_lr, min_delta))
     trained = {**engine.dense_train_get(), **norm}
     engine.set_dense(trained)          # (ends the run: the engine holds the trained model as any other)
+    return trained, history
+
+
+# ---------------------------------------------------------------------------------------------------------------- DAgger
+def beta_schedule(beta, iterations):
+    """The probability that the expert drives, per iteration: a number (every iteration), a sequence of at most ``iterations``
+    numbers (the last one is kept for the iterations behind it) or the command line's text "1,0.5,0.25,0".  Every entry finite and
+    in [0, 1].  -> a list of ``iterations`` floats."""
+    iterations = int(iterations)
+    if iterations < 1:
+        raise ValueError(f"iterations must be at least 1, got {iterations}")
+    if isinstance(beta, str):
+        try:
+            beta = [float(x) for x in beta.split(",")]
+        except ValueError:
+            raise ValueError(f"beta {beta!r}: numbers separated by commas, e.g. 1,0.5,0.25,0") from None
+    values = [float(x) for x in np.asarray(beta, np.float64).reshape(-1)]
+    if not values or len(values) > iterations:
+        raise ValueError(f"beta holds {len(values)} entries for {iterations} iterations: one, or at most one per iteration")
+    if not all(np.isfinite(v) and 0.0 <= v <= 1.0 for v in values):
+        raise ValueError(f"beta {values}: every entry is a probability in [0, 1]")
+    return values + [values[-1]] * (iterations - len(values))
+
+
+def normalization_from_dataset(dataset, first, stop):
+    """``normalization_from_recordings`` over recordings ``first .. stop - 1`` of a ``harness.DaggerDataset``: the sixteen extrema
+    are reduced on the device, and they alone come down."""
+    import torch
+    s = dataset.states[first:stop].reshape(-1, 6)
+    cols = torch.cat([s[:, 1:6], dataset.target_equilibrium[first:stop].reshape(-1, 1), dataset.target_position[first:stop].reshape(-1, 1),
+                      dataset.labels[first:stop].reshape(-1, 1)], dim=1)
+    ext = torch.stack([cols.min(dim=0).values, cols.max(dim=0).values]).cpu().numpy()
+    return normalization_from_extrema(ext[0], ext[1])
+
+
+def dagger(engine, setter_config, *, experiments, iterations, beta, steps_per_iteration, batch_size, lr, seed, init=None, optimizer=None,
+           graph=False, log=None, beta1=0.9, beta2=0.999, eps=1e-7):
+    """DAgger (Ross, Gordon, Bagnell 2011) for Dense-7IN-32H1-32H2-1OUT, the loop closed on the device.  Per iteration i:
+    ``experiments`` fresh random experiments (``schedule.RandomExperimentSetter(setter_config).draw(experiments, seed + i)``) run
+    through ``run_schedule(dagger=...)`` - the MPC of ``engine`` (its fused MPPI step; ``optimizer``: a fused rpgd / gradient object
+    configured for as many envs) labels every state and drives with probability ``beta[i]`` (``beta_schedule``), the imitator as
+    trained so far otherwise -, their samples land in the next recordings of ONE ``harness.DaggerDataset``, and
+    ``steps_per_iteration`` Adam steps follow on batches of ``batch_size`` rows drawn on the host uniformly over all rows of all
+    recordings filled so far (``numpy.random.default_rng(seed)``).  The dataset is trained where it lies: it never leaves the device.
+    The normalisation is fixed ONCE: ``init``'s if it carries one, else the min-max of iteration 0's recordings
+    (``normalization_from_dataset``), which must then run with beta = 1 - its states do not depend on the net, and its columns
+    ``imitator`` / ``sq_err`` are re-evaluated with the normalised initial net.  Adam's moments and step counter persist across the
+    iterations (one ``dense_train_begin``).  ``graph``: the runs are captured.
+    -> (the model dict ``MPPIEngine.set_dense`` takes, which the engine holds on return; history = dict(beta, disagreement - the mean
+    over the iteration's samples of (imitator - expert)^2 on the states visited -, expert_share - of its periods the expert drove -,
+    batch_loss [iterations][steps], scores [iterations][experiments,5] - ``MPPIEngine.score_runs`` of its runs -, normalization,
+    dataset: the DaggerDataset))."""
+    import torch
+    from . import schedule as SC
+    from .harness import ENGINE_MODEL, BatchedCartPoleExperiment, DaggerDataset
+    E, iterations, steps, B = int(experiments), int(iterations), int(steps_per_iteration), int(batch_size)
+    betas = beta_schedule(beta, iterations)
+    if E < 1 or steps < 1 or B < 1:
+        raise ValueError("experiments, steps_per_iteration and batch_size must be at least 1")
+    if optimizer is not None and not getattr(optimizer, "fused", False):
+        raise ValueError("dagger: a host-paced optimizer cannot be the expert (the fused MPPI step, or rpgd / gradient with fused=True)")
+    model = dict(init) if init is not None else initial_weights(seed)
+    _check_model(model)
+    norm = {k: np.asarray(model[k], f32) for k in NORM_KEYS if model.get(k) is not None}
+    if len(norm) != 4:
+        norm = None
+        if betas[0] != 1.0:
+            raise ValueError(f"dagger: without a normalisation in init, iteration 0's recordings fix it and must be the expert's own: "
+                             f"beta[0] must be 1, got {betas[0]}")
+    weights = {k: np.asarray(model[k], f32) for k in DENSE_KEYS}
+    setter = SC.RandomExperimentSetter(setter_config)
+    rng = np.random.default_rng(seed)
+    dataset = None
+    history = dict(beta=betas, disagreement=[], expert_share=[], batch_loss=[], scores=[])
+    for i in range(iterations):
+        batch = setter.draw(E, int(seed) + i)
+        T = batch.n_periods + 1
+        if dataset is None:
+            dataset = DaggerDataset(engine, iterations * E, T)
+            engine.set_dense({**weights, **(norm or identity_normalization())})
+            engine.dense_train_reserve(B)
+            if norm is not None:
+                engine.dense_train_begin()
+        exp = BatchedCartPoleExperiment(engine, dt_simulation=batch.dt_simulation, dt_control=batch.dt_control, seed=int(seed) + i)
+        if optimizer is not None and getattr(optimizer, "engine", None) is not None:
+            optimizer.optimizer_reset()                              # (plans, moments and counters of the runs before)
+        res = exp.run_schedule(batch, optimizer=optimizer, graph=graph, imitator=ENGINE_MODEL,
+                               dagger=dict(dataset=dataset, beta=betas[i], seed=int(seed) + i))
+        r0, r1 = res["recordings"]
+        if norm is None:                                             # iteration 0 fixes the normalisation, and the run begins
+            norm = normalization_from_dataset(dataset, r0, r1)
+            engine.set_dense({**weights, **norm})
+            engine.dense_train_begin()
+            q = engine.dense_control(dataset.states[r0:r1].reshape(-1, 6), dataset.target_position[r0:r1].reshape(-1),
+                                     dataset.target_equilibrium[r0:r1].reshape(-1))[0].reshape(r1 - r0, T)
+            dataset.imitator[r0:r1] = q
+            dataset.sq_err[r0:r1] = ((q.double() - dataset.labels[r0:r1].double()) ** 2).sum(dim=1)
+        summary = torch.stack([dataset.sq_err[r0:r1].sum() / (E * T), dataset.gate[r0:r1].double().mean()])
+        scores = engine.score_runs(res["states"], res["Q"], target_position_table=batch.target_position, save_every=batch.n_save,
+                                   sched_stride=batch.stride, period_steps=batch.n_ctrl)
+        losses = torch.empty(steps, dtype=torch.float64, device=engine.device)
+        for k in range(steps):
+            windows = np.stack([rng.integers(0, r1, B), rng.integers(0, T, B)], axis=1)
+            engine.dense_train_step(*dataset.tensors, windows, 1, 0, lr=lr, beta1=beta1, beta2=beta2, eps=eps, loss_out=losses[k:k + 1])
+        disagreement, share = (float(x) for x in summary.cpu().numpy())
+        history["disagreement"].append(disagreement)
+        history["expert_share"].append(share)
+        history["batch_loss"].append([float(x) for x in losses.cpu().numpy()])
+        history["scores"].append(scores.cpu().numpy())
+        if log is not None:
+            log(f"iteration {i + 1}/{iterations}: beta {betas[i]:g}, expert drove {share:.3f}, disagreement {disagreement:.6e}, "
+                f"loss {history['batch_loss'][-1][0]:.6e} -> {history['batch_loss'][-1][-1]:.6e}")
+    trained = {**engine.dense_train_get(), **norm}
+    engine.set_dense(trained)              # (ends the run: the engine holds the trained model as any other)
+    history.update(normalization=norm, dataset=dataset)
     return trained, history
 
 
@@ -233,14 +364,70 @@ def load_recordings_folder(folder, label_column=LABEL_COLUMN):
     return states, tp, te, labels, lengths, names
 
 
+def check_command_line(args):
+    """What the two modes of the command line exclude, refused by name (SystemExit) before anything is read."""
+    if args.dagger is None:
+        if args.recordings is None:
+            raise SystemExit("train_imitator: --recordings DIR (or --dagger ITERATIONS) is required")
+        for flag, given in (("--experiments", args.experiments is not None), ("--steps-per-iteration", args.steps_per_iteration is not None),
+                            ("--optimizer", args.optimizer is not None), ("--graph", args.graph)):
+            if given:
+                raise SystemExit(f"train_imitator: {flag} belongs to --dagger")
+        return
+    for flag, given in (("--recordings", args.recordings is not None), ("--validation", args.validation is not None)):
+        if given:
+            raise SystemExit(f"train_imitator: --dagger and {flag}: DAgger gathers its own recordings on the device")
+    if args.config_root is None:
+        raise SystemExit("train_imitator: --dagger needs --config-root CHECKOUT (the data generator's and the controller's configuration)")
+    try:
+        beta_schedule(args.beta, args.dagger)
+    except ValueError as e:
+        raise SystemExit(f"train_imitator: --beta: {e}")
+
+
+def dagger_command(args, settings, init):
+    """``--dagger``: the engine and the expert from the checkout's configuration, as ``recording.main`` builds them -> ``dagger(...)``."""
+    from .configs import load_reference_yaml, mppi_config_from_yaml
+    from .engine import MPPIEngine
+    phys, cfgs = load_reference_yaml(args.config_root)
+    dg = dict(cfgs["data_gen"])
+    E = args.experiments if args.experiments is not None else int(dg.get("number_of_experiments", 64))
+    optimizer = None
+    if args.optimizer == "rpgd":
+        from .controller_mpc import controller_mpc
+        ctrl = controller_mpc("CartPole", {}, control_limits=([-1.0], [1.0]), config=dict(fused=True, seed=settings["seed"]), phys=phys,
+                              device=args.device, num_envs=E, config_root=args.config_root)
+        ctrl.configure("rpgd")
+        optimizer, engine = ctrl.optimizer, ctrl.optimizer.engine
+    else:
+        engine = MPPIEngine(E, mppi_config_from_yaml(cfgs), phys=phys, device=args.device)
+    steps = args.steps_per_iteration if args.steps_per_iteration is not None else 256
+    try:
+        return dagger(engine, dg, experiments=E, iterations=args.dagger, beta=args.beta, steps_per_iteration=steps,
+                      batch_size=settings["batch_size"], lr=settings["lr"], seed=settings["seed"], init=init, optimizer=optimizer,
+                      graph=args.graph, log=print)
+    finally:
+        engine.close()
+
+
 def main(argv=None):
     """python -m cartpolesimulation_amd.train_imitator --recordings DIR --out FOLDER --config-root CHECKOUT
-    [--label-column Q_calculated_offline] [--validation DIR] [--init FOLDER]"""
+    [--label-column Q_calculated_offline] [--validation DIR] [--init FOLDER]
+    python -m cartpolesimulation_amd.train_imitator --dagger ITERATIONS --beta 1,0.5,0.25,0 --experiments E --steps-per-iteration K
+    --config-root CHECKOUT --out FOLDER [--optimizer rpgd] [--init FOLDER] [--graph]"""
     import argparse
     import yaml
     ap = argparse.ArgumentParser(description="Train the neural imitator (Dense-7IN-32H1-32H2-1OUT) on relabelled recordings, on MI355X "
                                              "(reference: SI_Toolkit_ASF/Run/A2_Train_Network.py, config_training.yml as shipped)")
-    ap.add_argument("--recordings", required=True, metavar="DIR", help="a folder of recording CSVs with the label column (along_trajectories writes them)")
+    ap.add_argument("--recordings", default=None, metavar="DIR", help="a folder of recording CSVs with the label column (along_trajectories writes them)")
+    ap.add_argument("--dagger", type=int, default=None, metavar="ITERATIONS",
+                    help="DAgger instead of recordings: this many rounds of (run the experiments with the MPC labelling and, with "
+                         "probability beta, driving; train on everything gathered so far), all on the device; needs --config-root")
+    ap.add_argument("--beta", default="1,0.5,0.25,0", help="--dagger: the expert's share per iteration, the last one kept (default 1,0.5,0.25,0)")
+    ap.add_argument("--experiments", type=int, default=None, metavar="E", help="--dagger: experiments per iteration (default: the data generator's)")
+    ap.add_argument("--steps-per-iteration", type=int, default=None, metavar="K", help="--dagger: Adam steps after every iteration's runs")
+    ap.add_argument("--optimizer", default=None, choices=["mppi", "rpgd"], help="--dagger: the expert (rpgd: the fused step; default mppi)")
+    ap.add_argument("--graph", action="store_true", help="--dagger: the runs captured as graphs of control periods")
     ap.add_argument("--validation", default=None, metavar="DIR", help="a folder of recordings scored after every epoch")
     ap.add_argument("--out", required=True, metavar="FOLDER", help="the model folder to write (e.g. .../Dense-7IN-32H1-32H2-1OUT-0)")
     ap.add_argument("--config-root", default=None, metavar="CHECKOUT",
@@ -253,6 +440,7 @@ def main(argv=None):
     ap.add_argument("--init", default=None, metavar="FOLDER", help="fine-tune the model of this folder, with its normalisation")
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
+    check_command_line(args)
     path = args.config_training or (os.path.join(args.config_root, "SI_Toolkit_ASF", "config_training.yml") if args.config_root else None)
     config = {"modeling": {"NET_NAME": NET_NAME},
               "training_default": {"state_inputs": list(DENSE_INPUTS), "outputs": ["Q_calculated"], "SEED": 1873, "SHIFT_LABELS": 0}}
@@ -265,7 +453,7 @@ def main(argv=None):
     except ValueError as e:
         raise SystemExit(f"train_imitator: {e}")
     info = {"WASH OUT LENGTH": 0, "POST WASH OUT LENGTH": settings["post_wash_out"], "SHIFT LABELS": settings["shift_labels"],
-            "TRAINING_FILES": os.path.abspath(args.recordings)}
+            "TRAINING_FILES": f"DAgger, {args.dagger} iterations" if args.dagger is not None else os.path.abspath(args.recordings)}
     if args.init is not None:
         from .model_folder import load_dense_model
         init = dict(load_dense_model(os.fspath(args.init)))
@@ -276,6 +464,12 @@ def main(argv=None):
         init = initial_weights(settings["seed"])
         if not normalize:
             init.update(identity_normalization())
+    if args.dagger is not None:
+        model, history = dagger_command(args, settings, init)
+        folder = write_model_folder(args.out, model, info=info)
+        print(f"DAgger: {args.dagger} iterations, disagreement {history['disagreement'][0]:.6e} -> "
+              f"{history['disagreement'][-1]:.6e}; model folder: {folder}")
+        return model, history
     *train, lengths, names = load_recordings_folder(args.recordings, args.label_column)
     validation = load_recordings_folder(args.validation, args.label_column)[:5] if args.validation else None
     from .configs import MPPIConfig

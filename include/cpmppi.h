@@ -68,7 +68,8 @@ extern "C" {
                                       _step / _get (new entry points, likewise);
                                       cpmppi_set_dense / cpmppi_dense_model, cpmppi_dense_control / cpmppi_dense_control_args,
                                       cpmppi_dense_loss_grad / cpmppi_dense_loss_args, cpmppi_dense_train_reserve / _begin / _step /
-                                      _get (new entry points, likewise). */
+                                      _get (new entry points, likewise);
+                                      cpmppi_dagger_step / cpmppi_dagger_args (a new entry point, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -744,6 +745,54 @@ int cpmppi_dense_train_begin(cpmppi_handle* h);
 int cpmppi_dense_train_step(cpmppi_handle* h, const cpmppi_dense_loss_args* args, float lr, float beta1, float beta2, float eps,
                             void* stream);
 int cpmppi_dense_train_get(cpmppi_handle* h, float* params_host);
+
+/* DAgger (Ross, Gordon, Bagnell 2011) for the neural imitator: one control period in which the EXPERT labels the state and the
+ * imitator - or, per env and period, a coin that favours the expert with probability beta - drives.  cpmppi_dagger_step is ONE
+ * launch, a lane per env, enqueued after the expert's step of the period (the fused cpmppi_step, cpmppi_rpgd_step, ... writing
+ * Q_expert) and before the plant launch (reading Q_out).  Per env e, in this order:
+ *  1. Q_imi = what cpmppi_dense_control gives for s[e], target_position[e], target_equilibrium[e], bit for bit (one forward body,
+ *     on the live parameter vector: a cpmppi_dense_train_step enqueued before this call is seen by it).
+ *  2. The gate: one Philox4x32-10 block with the counter (0xFFFFFFFF, env_offset + e, 0, low word of c) - no rollout has that
+ *     index, so the block is none of the sampler's - and the sampler's key (low word of seed ^ 0x51ed270b, high word of seed ^ high
+ *     word of c).  ub = (word 1 >> 8) 2^-24 in [0, 1); the expert drives iff ub < beta[e]: always for beta = 1, never for
+ *     beta <= 0 or a NaN.
+ *  3. Q_out[e] = the expert drives ? Q_expert[e] : Q_imi.  No arithmetic on the chosen value: a NaN passes, in its env only.
+ *  4. Only if c < T, row (r0 + e, c) of the dataset - exactly the tensors cpmppi_dense_loss_args reads - is written:
+ *     states <- s[e], rec_target_position / rec_target_equilibrium <- the two targets, labels <- Q_expert[e]; and, where given,
+ *     imitator_out <- Q_imi, gate_out <- 0 / 1.  For c >= T the control is still computed and nothing else is written: a captured
+ *     graph replayed past the end touches nothing outside the buffers.
+ *  5. With sq_err, for a sample that was recorded (c < T): d = (double)Q_imi - (double)Q_expert; sq_err[e] = sq_err[e] + d * d (two
+ *     roundings, a plain load and store by the env's own lane, no atomics): the on-policy disagreement over the env's recording,
+ *     summed by the caller.  Past the end nothing changes anywhere but Q_out.
+ * c is `period`, or with period_dev *period_dev - 1: the expert's step has already advanced the counter (the rule of
+ * cpmppi_replay_step / cpmppi_plant_step).  The host cannot see that counter, so one still at 0 is not refused here: on the device
+ * the call is then treated as c = 0.  The kernel does not advance the counter.  No allocation, no host synchronisation: capturable.
+ * Refused ("cpmppi_dagger_step: ..."), nothing launched, CPMPPI_ERR_BAD_ARG: no model set (cpmppi_set_dense); E == 0 or
+ * E > config.E; a NULL s, target_position, target_equilibrium, Q_expert, beta, Q_out, states, rec_target_position,
+ * rec_target_equilibrium or labels; R or T equal to 0; r0 + E > R; Q_out overlapping Q_expert.  A misaligned pointer is
+ * CPMPPI_ERR_ALIGN (sq_err and period_dev: 8 bytes). */
+typedef struct {
+  uint32_t E;                           /* envs */
+  const float* s;                       /* [E,6] the state the controllers are shown */
+  const float* target_position;         /* [E] */
+  const float* target_equilibrium;      /* [E] */
+  const float* Q_expert;                /* [E] the expert's control of this period */
+  const float* beta;                    /* [E] DEVICE: the probability that the expert drives */
+  uint64_t seed;                        /* the gate's Philox key */
+  uint32_t env_offset;                  /* global index of env 0 */
+  uint64_t period;                      /* c, unless period_dev is given */
+  const unsigned long long* period_dev; /* DEVICE counter already advanced by the expert's step (c = *period_dev - 1), or NULL */
+  float* Q_out;                         /* [E] the applied control */
+  uint32_t R, T, r0;                    /* the dataset: recordings, rows of each - env e writes recording r0 + e */
+  float* states;                        /* [R,T,6] */
+  float* rec_target_position;           /* [R,T] */
+  float* rec_target_equilibrium;        /* [R,T] */
+  float* labels;                        /* [R,T] */
+  float* imitator_out;                  /* [R,T] or NULL */
+  uint8_t* gate_out;                    /* [R,T] or NULL: 1 where the expert drove */
+  double* sq_err;                       /* [E] DEVICE, accumulated, or NULL */
+} cpmppi_dagger_args;
+int cpmppi_dagger_step(cpmppi_handle* h, const cpmppi_dagger_args* args, void* stream);
 
 /* Rollout + cost only (no update): per-rollout trajectory cost S[E,N] of GIVEN input sequences inputs[E,N,H] under the
  * handle's plugin cost — cost_function.get_trajectory_cost(predictor.predict_core(s, Q), Q) fused; the building block of
