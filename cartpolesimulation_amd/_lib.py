@@ -38,7 +38,9 @@ EXPORTS = ("cpmppi_create", "cpmppi_destroy", "cpmppi_last_error", "cpmppi_get_c
            "cpmppi_ode_fit_reserve", "cpmppi_ode_fit_loss_grad", "cpmppi_ode_fit_begin", "cpmppi_ode_fit_set_theta",
            "cpmppi_ode_fit_step", "cpmppi_ode_fit_get",
            "cpmppi_set_dense", "cpmppi_dense_control", "cpmppi_dense_train_reserve", "cpmppi_dense_loss_grad",
-           "cpmppi_dense_train_begin", "cpmppi_dense_train_step", "cpmppi_dense_train_get", "cpmppi_dagger_step")
+           "cpmppi_dense_train_begin", "cpmppi_dense_train_step", "cpmppi_dense_train_get", "cpmppi_dagger_step",
+           "cpmppi_dense_policy_reserve", "cpmppi_dense_policy_loss_grad", "cpmppi_dense_policy_train_step",
+           "cpmppi_dense_policy_ckpt_floats", "cpmppi_dense_policy_ckpt_copy")
 DENSE_PARAMS = 1345                                  # CPMPPI_DENSE_PARAMS: the flat parameter vector of the neural imitator
 ODE_FIT_PARAMS = 8                                   # CPMPPI_ODE_FIT_PARAMS, in this order (bit i of a `trainable` mask)
 ODE_FIT_NAMES = ("k", "m_cart", "m_pole", "g", "J_fric", "M_fric", "u_max", "L")
@@ -151,6 +153,13 @@ class cpmppi_dense_loss_args(C.Structure):
     _fields_ = [("B", C.c_uint32), ("R", C.c_uint32), ("T", C.c_uint32), ("post_wash_out", C.c_uint32), ("shift_labels", C.c_uint32),
                 ("states", C.c_void_p), ("target_position", C.c_void_p), ("target_equilibrium", C.c_void_p), ("labels", C.c_void_p),
                 ("windows", C.c_void_p), ("windows_host", C.c_void_p), ("loss_out", C.c_void_p), ("grad_out", C.c_void_p)]
+
+
+class cpmppi_dense_policy_args(C.Structure):
+    _fields_ = [("B", C.c_uint32), ("R", C.c_uint32), ("T", C.c_uint32), ("horizon", C.c_uint32),
+                ("states", C.c_void_p), ("target_position", C.c_void_p), ("target_equilibrium", C.c_void_p), ("L", C.c_void_p),
+                ("windows", C.c_void_p), ("windows_host", C.c_void_p), ("loss_out", C.c_void_p), ("grad_out", C.c_void_p),
+                ("cost_out", C.c_void_p), ("Q_out", C.c_void_p)]
 
 
 class cpmppi_dagger_args(C.Structure):
@@ -317,6 +326,11 @@ def load():
     lib.cpmppi_dense_train_step.argtypes = [vp, C.POINTER(cpmppi_dense_loss_args), f, f, f, f, vp]
     lib.cpmppi_dense_train_get.argtypes = [vp, C.POINTER(f)]
     lib.cpmppi_dagger_step.argtypes = [vp, C.POINTER(cpmppi_dagger_args), vp]
+    lib.cpmppi_dense_policy_reserve.argtypes = [vp, u32, u32]
+    lib.cpmppi_dense_policy_loss_grad.argtypes = [vp, C.POINTER(cpmppi_dense_policy_args), vp]
+    lib.cpmppi_dense_policy_train_step.argtypes = [vp, C.POINTER(cpmppi_dense_policy_args), f, f, f, f, f, vp]
+    lib.cpmppi_dense_policy_ckpt_floats.argtypes, lib.cpmppi_dense_policy_ckpt_floats.restype = [vp], C.c_uint64
+    lib.cpmppi_dense_policy_ckpt_copy.argtypes = [vp, C.POINTER(f), C.c_uint64, C.c_int]
     lib.cpmppi_cem_sample.argtypes = [vp, u32, vp, vp, u64, u64, u32, vp, vp]
     lib.cpmppi_cem_update.argtypes = [vp, u32, vp, vp, u32, f, vp, vp, vp, vp]
     lib.cpmppi_tiled_floats.argtypes = [vp, u32]

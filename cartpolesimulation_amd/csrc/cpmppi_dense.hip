@@ -9,7 +9,11 @@
 //                               contraction index, two per MFMA, as in gru_wgrad_kernel) into three accumulator tiles that live
 //                               across the workgroup's tiles.  The workgroup writes its own row of the partials with plain stores.
 //   dense_finalize_kernel       ONE workgroup walks the partial rows first to last in float64: loss, gradient; with `update` Adam on
-//                               the parameter vector in place.
+//                               the parameter vector in place.  `guard`: the cost steps - norm clip, and no update from a non-finite
+//                               loss or norm.
+//   dense_policy_kernel<COST, INTEG, GRAD>   fine-tuning on the task cost (cpmppi_dense_policy_*): the closed loop net -> ODE plant
+//                               per lane, its cost, and with GRAD the reverse sweep of cpmppi_grad.hpp per control step feeding the
+//                               same backward body and tile contraction as dense_grad_kernel.
 //   dagger_step_kernel          one lane = one env (cpmppi_dagger_step): the control kernel's forward body on the live parameter
 //                               vector, one Philox block for the gate, the applied control, the sample into the trainer's tensors.
 // The parameter vector is the only image of the weights.  Every kernel reads it through the constant address space: the index is
@@ -26,6 +30,7 @@
 #include "cpmppi_wave.hpp"
 #include "cpmppi_train.hpp"
 #include "cpmppi_philox.hpp"       // (philox4x32_10: the gate of dagger_step_kernel)
+#include "cpmppi_grad.hpp"         // (substep_reverse, stage_*_grad, the plain substeps: dense_policy_kernel)
 
 using namespace cpmppi_k;
 using cpmppi::f16v;
@@ -152,11 +157,92 @@ struct DenseLossArgs {
 
 __device__ __forceinline__ f16v mfma_(float a, float b, f16v acc) { return __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, acc, 0, 0, 0); }
 
+// Where a tile of 64 samples is parked for the contraction over them (LDS of the one wave).
+struct DenseTile {
+  float* dz1; float* dz2; float* h1; float* h2;   // [TILE][LDS_STRIDE]
+  float* x;                                       // [TILE][8]: the seven inputs and the bias column
+  float* e;                                       // [TILE] the head adjoint
+};
+
+// The backward pass of the lane's sample from `e` = d (the sum) / d y, as dense_grad_kernel forms it, parked into the lane's row
+// of the tile; dx = W1^T dz1: the adjoint of the seven normalised inputs (dense_policy_kernel).
+__device__ __forceinline__ void dense_backward_park(wptr w, const DenseTile& t, uint32_t lane, float e, const float (&x)[NIN],
+                                                    const float (&h1)[NH], const float (&h2)[NH], float (&dx)[NIN]) {
+  float dz2[NH], dz1[NH];
+#pragma unroll
+  for (int i = 0; i < NH; ++i) dz2[i] = (e * w[OFF_W3 + i]) * __builtin_fmaf(-h2[i], h2[i], 1.0f);
+#pragma unroll
+  for (int k = 0; k < NH; ++k) dz1[k] = 0.0f;
+#pragma unroll
+  for (int i = 0; i < NH; ++i) {
+#pragma unroll
+    for (int k = 0; k < NH; ++k) dz1[k] = __builtin_fmaf(w[OFF_W2 + i * NH + k], dz2[i], dz1[k]);
+  }
+#pragma unroll
+  for (int k = 0; k < NH; ++k) {
+    dz1[k] = dz1[k] * __builtin_fmaf(-h1[k], h1[k], 1.0f);
+    t.dz1[lane * LDS_STRIDE + k] = dz1[k];
+    t.dz2[lane * LDS_STRIDE + k] = dz2[k];
+    t.h1[lane * LDS_STRIDE + k] = h1[k];
+    t.h2[lane * LDS_STRIDE + k] = h2[k];
+  }
+#pragma unroll
+  for (int k = 0; k < NIN; ++k) t.x[lane * 8 + k] = x[k];
+  t.x[lane * 8 + NIN] = 1.0f;                                        // the bias column of layer 1
+  t.e[lane] = e;
+#pragma unroll
+  for (int k = 0; k < NIN; ++k) dx[k] = 0.0f;
+#pragma unroll
+  for (int i = 0; i < NH; ++i) {
+#pragma unroll
+    for (int k = 0; k < NIN; ++k) dx[k] = __builtin_fmaf(w[OFF_W1 + i * NIN + k], dz1[i], dx[k]);
+  }
+}
+
+// The parked tile contracted over its 64 samples into the three accumulator tiles (between two barriers of the caller's).
+// D[i][n] += sum over the tile's samples of A[sample][i] B[sample][n]; k-step ks contracts samples 2 ks and 2 ks + 1, the
+// lane half supplies one each; lane % 32 is A's row i and B's column n.
+//   acc1: dz1 x (x0..x6, 1)   -> d w1 [i][0..6], d b1 [i] in column 7
+//   acc2: dz2 x h1            -> d w2 [i][n]
+//   acc3: dz2 x e_0 + h2 x (e of the sample) e_1 + (e of the sample) x e_2
+//                             -> d b2 [i] in column 0, d w3 [i] in column 1, d b3 in column 2 (every row alike)
+__device__ __forceinline__ void dense_contract_tile(const DenseTile& t, uint32_t m, uint32_t hf, f16v& acc1, f16v& acc2, f16v& acc3) {
+  const float one0 = m == 0 ? 1.0f : 0.0f, one2 = m == 2 ? 1.0f : 0.0f;
+#pragma unroll 4
+  for (int ks = 0; ks < TILE / 2; ++ks) {
+    const int smp = 2 * ks + (int)hf;
+    const float a1 = t.dz1[smp * LDS_STRIDE + m], a2 = t.dz2[smp * LDS_STRIDE + m];
+    const float bh1 = t.h1[smp * LDS_STRIDE + m], ah2 = t.h2[smp * LDS_STRIDE + m];
+    const float bx = m < 8u ? t.x[smp * 8 + m] : 0.0f;
+    const float es = t.e[smp];
+    acc1 = mfma_(a1, bx, acc1);
+    acc2 = mfma_(a2, bh1, acc2);
+    acc3 = mfma_(a2, one0, acc3);
+    acc3 = mfma_(ah2, m == 1u ? es : 0.0f, acc3);
+    acc3 = mfma_(es, one2, acc3);
+  }
+}
+
+// The three accumulator tiles -> the workgroup's partial row, in the flat order.
+__device__ __forceinline__ void dense_store_row(float* out, uint32_t m, uint32_t hf, const f16v& acc1, const f16v& acc2, const f16v& acc3) {
+#pragma unroll
+  for (int v = 0; v < 16; ++v) {
+    const int i = cpmppi::gru_tile_row(v, (int)hf);
+    out[OFF_W2 + i * NH + m] = acc2[v];
+    if (m < (uint32_t)NIN) out[OFF_W1 + i * NIN + m] = acc1[v];
+    if (m == (uint32_t)NIN) out[OFF_B1 + i] = acc1[v];
+    if (m == 0) out[OFF_B2 + i] = acc3[v];
+    if (m == 1) out[OFF_W3 + i] = acc3[v];
+    if (m == 2 && i == 0) out[OFF_B3] = acc3[v];
+  }
+}
+
 template <bool GRAD>
 __global__ __launch_bounds__(TILE) void dense_grad_kernel(const DenseNorm nm, const DenseLossArgs a) {
   __shared__ float sh_dz1[GRAD ? TILE * LDS_STRIDE : 1], sh_dz2[GRAD ? TILE * LDS_STRIDE : 1];
   __shared__ float sh_h1[GRAD ? TILE * LDS_STRIDE : 1], sh_h2[GRAD ? TILE * LDS_STRIDE : 1];
   __shared__ float sh_x[GRAD ? TILE * 8 : 1], sh_e[GRAD ? TILE : 1];
+  const DenseTile park{sh_dz1, sh_dz2, sh_h1, sh_h2, sh_x, sh_e};
   const uint32_t lane = threadIdx.x, m = lane & 31u, hf = lane >> 5;
   const wptr w = constant_(a.params);
   f16v acc1 = 0.0f, acc2 = 0.0f, acc3 = 0.0f;
@@ -180,6 +266,8 @@ __global__ __launch_bounds__(TILE) void dense_grad_kernel(const DenseNorm nm, co
     const float e = live ? y - target : 0.0f;                        // d loss / d y = 2 e / N: the finalize kernel scales
     loss = __builtin_fmaf(e, e, loss);
     if constexpr (GRAD) {
+      // (dense_backward_park's arithmetic, kept in line: behind a call the compiler merges this kernel's weight loads into
+      // 8-dword scalar loads and spills 639 SGPRs where this form spills 47 - DESIGN.md N9)
       float dz2[NH], dh1[NH];
 #pragma unroll
       for (int i = 0; i < NH; ++i) dz2[i] = (e * w[OFF_W3 + i]) * __builtin_fmaf(-h2[i], h2[i], 1.0f);
@@ -202,56 +290,176 @@ __global__ __launch_bounds__(TILE) void dense_grad_kernel(const DenseNorm nm, co
       sh_x[lane * 8 + NIN] = 1.0f;                                   // the bias column of layer 1
       sh_e[lane] = e;
       __syncthreads();
-      // D[i][n] += sum over the tile's samples of A[sample][i] B[sample][n]; k-step ks contracts samples 2 ks and 2 ks + 1, the
-      // lane half supplies one each; lane % 32 is A's row i and B's column n.
-      //   acc1: dz1 x (x0..x6, 1)   -> d w1 [i][0..6], d b1 [i] in column 7
-      //   acc2: dz2 x h1            -> d w2 [i][n]
-      //   acc3: dz2 x e_0 + h2 x (e of the sample) e_1 + (e of the sample) x e_2
-      //                             -> d b2 [i] in column 0, d w3 [i] in column 1, d b3 in column 2 (every row alike)
-      const float one0 = m == 0 ? 1.0f : 0.0f, one2 = m == 2 ? 1.0f : 0.0f;
-#pragma unroll 4
-      for (int ks = 0; ks < TILE / 2; ++ks) {
-        const int smp = 2 * ks + (int)hf;
-        const float a1 = sh_dz1[smp * LDS_STRIDE + m], a2 = sh_dz2[smp * LDS_STRIDE + m];
-        const float bh1 = sh_h1[smp * LDS_STRIDE + m], ah2 = sh_h2[smp * LDS_STRIDE + m];
-        const float bx = m < 8u ? sh_x[smp * 8 + m] : 0.0f;
-        const float es = sh_e[smp];
-        acc1 = mfma_(a1, bx, acc1);
-        acc2 = mfma_(a2, bh1, acc2);
-        acc3 = mfma_(a2, one0, acc3);
-        acc3 = mfma_(ah2, m == 1u ? es : 0.0f, acc3);
-        acc3 = mfma_(es, one2, acc3);
-      }
+      dense_contract_tile(park, m, hf, acc1, acc2, acc3);
       __syncthreads();                                               // the tile is read: the next one may be parked
     }
   }
   float* out = a.partials + (size_t)blockIdx.x * ROW;
   const float wl = wave_sum(loss);
   if (lane == 0) out[LOSS_COL] = wl;
-  if constexpr (GRAD) {
+  if constexpr (GRAD) dense_store_row(out, m, hf, acc1, acc2, acc3);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Fine-tuning on the task cost through the ODE plant (cpmppi_dense_policy_*): the closed loop net -> clip -> S substeps of the
+// handle's predictor over `p.H` control steps from a recorded row, its plugin cost, and the derivative of the batch's mean cost
+// with respect to the parameter vector.  One lane = one start state, one workgroup = ONE wave = one partial row.
+//   forward   the body of dense_control_kernel per control step, the stage cost and the plain substeps of adjoint_sweep
+//             (cpmppi_grad.hpp); GRAD: s_k check-pointed per control step, lane-contiguous as SweepLane::ckpt is.
+//   backward  k = H-1 .. 0: the check-point, the net's forward pass again, the S sub-states into LDS and substep_reverse over
+//             them, the stage gradient; e_k = d J / d y_k (0 where the control was clipped) takes the MSE residual's place in
+//             dense_backward_park / dense_contract_tile, the accumulators living across all H steps; W1^T dz1 goes back into the
+//             state's adjoint through in_scale (angle_cos / angle_sin: through -sin / +cos into the angle's).
+struct PolicyArgs {
+  const float* states;     // [R,T,6]
+  const float* tp;         // [R,T]
+  const float* te;         // [R,T]
+  const float* L;          // [R] or NULL
+  const uint32_t* windows; // [B][2]
+  const float* params;     // [NPAR]
+  float* partials;         // [gridDim.x][ROW]
+  float* ckpt;             // [H][6][gridDim.x * TILE]
+  float* cost_out;         // [B] or NULL
+  float* Q_out;            // [B][H] or NULL
+  uint32_t B, R, T;
+};
+
+template <int COST, int INTEG, bool GRAD>
+__global__ __launch_bounds__(TILE) void dense_policy_kernel(const DenseNorm nm, const cpmppi::Params p, const PolicyArgs a) {
+  using namespace cpmppi;
+  __shared__ float sh_dz1[GRAD ? TILE * LDS_STRIDE : 1], sh_dz2[GRAD ? TILE * LDS_STRIDE : 1];
+  __shared__ float sh_h1[GRAD ? TILE * LDS_STRIDE : 1], sh_h2[GRAD ? TILE * LDS_STRIDE : 1];
+  __shared__ float sh_x[GRAD ? TILE * 8 : 1], sh_e[GRAD ? TILE : 1];
+  extern __shared__ float sub_states[];                              // GRAD: [S][6][TILE]
+  const DenseTile park{sh_dz1, sh_dz2, sh_h1, sh_h2, sh_x, sh_e};
+  const uint32_t lane = threadIdx.x, m = lane & 31u, hf = lane >> 5;
+  const wptr w = constant_(a.params);
+  const uint32_t H = p.H, S = p.S;
+  const size_t lanes = (size_t)gridDim.x * TILE;
+  const size_t b = (size_t)blockIdx.x * TILE + lane;
+  const bool live = b < a.B;
+  // a lane beyond the batch runs the loop from the upright rest state; it writes nothing and its head adjoint is 0
+  float s0[6] = {0.0f, 0.0f, 1.0f, 0.0f, 0.0f, 0.0f}, te = 0.0f, x_t = 0.0f, L = p.L_default;
+  if (live) {
+    // (the device copy of the windows is clamped into the recordings, as in dense_grad_kernel)
+    const uint32_t wr = min(a.windows[2 * b], a.R - 1u), wt = min(a.windows[2 * b + 1], a.T - 1u);
+    const size_t row = (size_t)wr * a.T + wt;
 #pragma unroll
-    for (int v = 0; v < 16; ++v) {
-      const int i = cpmppi::gru_tile_row(v, (int)hf);
-      out[OFF_W2 + i * NH + m] = acc2[v];
-      if (m < (uint32_t)NIN) out[OFF_W1 + i * NIN + m] = acc1[v];
-      if (m == (uint32_t)NIN) out[OFF_B1 + i] = acc1[v];
-      if (m == 0) out[OFF_B2 + i] = acc3[v];
-      if (m == 1) out[OFF_W3 + i] = acc3[v];
-      if (m == 2 && i == 0) out[OFF_B3] = acc3[v];
+    for (int i = 0; i < 6; ++i) s0[i] = a.states[row * 6 + i];
+    te = a.te[row]; x_t = a.tp[row];
+    if (a.L) L = a.L[wr];
+  }
+  const EnvConst ec = make_env_const(p, L);
+  const float t = p.t_step;
+  const float scale = (p.horizon_reduce == CPMPPI_REDUCE_SUM) ? 1.0f : 1.0f / (float)(p.H + 1);
+  const float cos0 = cosf(s0[0]);                                    // the plugins take cos(angle) of the given state at stage 0
+  auto forward_substep = [&](State<float>& s, float uK) __attribute__((always_inline)) {
+    if constexpr (INTEG == PREDICTOR_ODE) substep_cromer_plain(s, uK, t, p, ec);
+    else substep_fast<float>(s, uK, t, p, ec, p.THL);
+  };
+  // q_k and the net's activations at the state `s`
+  auto policy = [&](const State<float>& s, float (&x)[NIN], float (&h1)[NH], float (&h2)[NH]) __attribute__((always_inline)) {
+    const float sv[6] = {s.th, s.w, s.c, s.s, s.x, s.v};
+    dense_inputs(nm, sv, te, x_t, x);
+    const float y = dense_forward(w, x, h1, h2);
+    return __builtin_fmaf(nm.out_scale, y, nm.out_shift);
+  };
+
+  // ---- forward, check-pointing every control step
+  State<float> st{s0[0], s0[1], s0[2], s0[3], s0[4], s0[5]};
+  float cost = 0.0f, cosang = cos0;
+  for (uint32_t k = 0; k < H; ++k) {
+    if constexpr (GRAD) {
+      float* ck = a.ckpt + ((size_t)k * 6) * lanes + b;
+      ck[0] = st.th; ck[lanes] = st.w; ck[2 * lanes] = st.c; ck[3 * lanes] = st.s; ck[4 * lanes] = st.x; ck[5 * lanes] = st.v;
     }
+    float x[NIN], h1[NH], h2[NH];
+    const float q = policy(st, x, h1, h2);
+    const float ur = q > 1.0f ? 1.0f : (q < -1.0f ? -1.0f : q);      // (the bits of dense_control_kernel; a NaN passes)
+    if (live && a.Q_out) a.Q_out[b * H + k] = ur;
+    if constexpr (COST == COST_QBGM) cost += stage_qbgm<float, true>(p, st.x, cosang, st.w, ur, x_t, te);
+    else cost += stage_default<float, true>(p, st.x, cosang, ur, x_t, te);
+    const float uK = ur * ec.uK_scale;
+    for (uint32_t s = 0; s < S; ++s) forward_substep(st, uK);
+    cosang = st.c;
+  }
+  const float term = (COST == COST_DEFAULT) ? terminal_indicator<float>(p, st.th, st.x, x_t) : 0.0f;
+  const float total = (cost + term) * scale;
+  if (live && a.cost_out) a.cost_out[b] = total;
+  float* out = a.partials + (size_t)blockIdx.x * ROW;
+  const float wl = wave_sum(live ? total : 0.0f);
+  if (lane == 0) out[LOSS_COL] = wl;
+
+  // ---- backward
+  if constexpr (GRAD) {
+    f16v acc1 = 0.0f, acc2 = 0.0f, acc3 = 0.0f;
+    float* sub = sub_states + lane;
+    Adjoint lam{0.0f, 0.0f, 0.0f, 0.0f};                             // the terminal indicator has zero derivative
+    for (uint32_t k = H; k-- > 0;) {
+      const float* ck = a.ckpt + ((size_t)k * 6) * lanes + b;
+      const State<float> st0{ck[0], ck[lanes], ck[2 * lanes], ck[3 * lanes], ck[4 * lanes], ck[5 * lanes]};
+      float x[NIN], h1[NH], h2[NH];
+      const float q = policy(st0, x, h1, h2);
+      const bool clipped = q < -1.0f || q > 1.0f;
+      const float ur = q > 1.0f ? 1.0f : (q < -1.0f ? -1.0f : q);
+      const float uK = ur * ec.uK_scale;
+      State<float> s = st0;
+      for (uint32_t i = 0; i < S; ++i) {
+        float* d = sub + (size_t)i * 6 * TILE;
+        d[0] = s.th; d[TILE] = s.w; d[2 * TILE] = s.c; d[3 * TILE] = s.s; d[4 * TILE] = s.x; d[5 * TILE] = s.v;
+        forward_substep(s, uK);
+      }
+      float guK = 0.0f;
+      for (uint32_t i = S; i-- > 0;) {
+        const float* d = sub + (size_t)i * 6 * TILE;
+        const State<float> si{d[0], d[TILE], d[2 * TILE], d[3 * TILE], d[4 * TILE], d[5 * TILE]};
+        substep_reverse<(INTEG == PREDICTOR_ODE)>(si, uK, t, p, ec, lam, guK);
+      }
+      // stage k: its own state and control, as adjoint_sweep adds them
+      const float ca = (k == 0) ? cos0 : st0.c;
+      StageGrad sg;
+      if constexpr (COST == COST_QBGM) sg = stage_qbgm_grad(p, st0.x, ca, st0.w, ur, x_t, te);
+      else sg = stage_default_grad(p, st0.x, ca, ur, x_t, te);
+      lam.x = __builtin_fmaf(scale, sg.x, lam.x);
+      lam.w = __builtin_fmaf(scale, sg.w, lam.w);
+      lam.th = __builtin_fmaf(scale * sg.cosang, -st0.s, lam.th);
+      const float gk = __builtin_fmaf(guK, ec.uK_scale, scale * sg.u);
+      const float e = (live && !clipped) ? gk * nm.out_scale : 0.0f;  // d J / d y_k
+      float dx[NIN];
+      dense_backward_park(w, park, lane, e, x, h1, h2, dx);
+      __syncthreads();
+      dense_contract_tile(park, m, hf, acc1, acc2, acc3);
+      __syncthreads();                                               // the tile is read: the next step may be parked
+      // u_k is a function of s_k: the inputs' adjoint joins the state's (the stage-0 state's adjoint has no reader)
+      lam.w = __builtin_fmaf(nm.in_scale[0], dx[0], lam.w);
+      lam.th = __builtin_fmaf(nm.in_scale[1] * dx[1], -st0.s, lam.th);
+      lam.th = __builtin_fmaf(nm.in_scale[2] * dx[2], st0.c, lam.th);
+      lam.x = __builtin_fmaf(nm.in_scale[3], dx[3], lam.x);
+      lam.v = __builtin_fmaf(nm.in_scale[4], dx[4], lam.v);
+    }
+    dense_store_row(out, m, hf, acc1, acc2, acc3);
   }
 }
 
 // ONE workgroup; lane p owns column p of the partial rows (and column p + FIN_BLOCK), which it walks first to last in float64.
 // Column LOSS_COL: loss = sum / count.  A parameter's column (with_grad): g = 2 sum / count -> grad_out; update != 0: Adam on the
 // parameter in place with t = *step + 1 (cpmppi.h states the update; float64 arithmetic, moments and parameter stored as float32),
-// then *step = t.  state: params[NPAR] | m[NPAR] | v[NPAR].
+// then *step = t.  state: params[NPAR] | m[NPAR] | v[NPAR].  `gscale`: what a column's sum is scaled by - 2 / count for the mean
+// squared error, 1 / count for the mean cost.
+// `guard` != 0 (the cost steps, cpmppi_dense_policy_*; a launch argument, so the unit keeps one finalize kernel): the scaled
+// gradient waits in LDS for its global 2-norm - the squares added
+// per lane (column p, then p + FIN_BLOCK), then over the lanes in a halving tree: a fixed order -, is scaled by
+// min(1, clip_norm / norm) (clip_norm <= 0: off), and parameters, moments and counter move only if the loss and the norm are finite.
 __global__ __launch_bounds__(FIN_BLOCK) void dense_finalize_kernel(const float* __restrict__ partials, uint32_t rows, double count,
-                                                                   float* state, double* __restrict__ loss_out,
+                                                                   double gscale, float* state, double* __restrict__ loss_out,
                                                                    float* __restrict__ grad_out, unsigned long long* step, float lr,
-                                                                   float beta1, float beta2, float eps, int update, int with_grad) {
+                                                                   float beta1, float beta2, float eps, float clip_norm, int update,
+                                                                   int with_grad, int guard) {
+  __shared__ double sh_g[2 * FIN_BLOCK], sh_sq[FIN_BLOCK], sh_loss[1];                             // (guard alone)
+  const bool guarded = guard != 0;
   const unsigned long long t = update ? *step + 1 : 0;
   __syncthreads();                                                   // every lane has read *step
+  if (guarded) sh_g[threadIdx.x] = sh_g[threadIdx.x + FIN_BLOCK] = 0.0;
   for (uint32_t p = threadIdx.x; p < (uint32_t)ROW; p += FIN_BLOCK) {
     if (p != (uint32_t)LOSS_COL && !with_grad) continue;
     const float* col = partials + p;
@@ -267,15 +475,45 @@ __global__ __launch_bounds__(FIN_BLOCK) void dense_finalize_kernel(const float* 
     for (; r < rows; ++r) acc += (double)col[(size_t)r * ROW];
     if (p == (uint32_t)LOSS_COL) {
       *loss_out = acc / count;
-      if (update) *step = t;
+      if (guarded) sh_loss[0] = acc / count;
+      else if (update) *step = t;
       continue;
     }
-    const double g = acc * (2.0 / count);
-    if (grad_out) grad_out[p] = (float)g;
-    if (update) {
-      const AdamStep adam(beta1, beta2, lr, eps, t);
-      state[p] = (float)adam(state[NPAR + p], state[2 * NPAR + p], g, state[p]);
+    const double g = acc * gscale;
+    if (guarded) {
+      sh_g[p] = g;
+    } else {
+      if (grad_out) grad_out[p] = (float)g;
+      if (update) {
+        const AdamStep adam(beta1, beta2, lr, eps, t);
+        state[p] = (float)adam(state[NPAR + p], state[2 * NPAR + p], g, state[p]);
+      }
     }
+  }
+  if (guarded) {
+    {
+#pragma clang fp contract(off)
+      const double g0 = sh_g[threadIdx.x], g1 = sh_g[threadIdx.x + FIN_BLOCK];   // (own stores; zero beyond the gradient)
+      const double q0 = g0 * g0, q1 = g1 * g1;
+      sh_sq[threadIdx.x] = q0 + q1;
+    }
+    __syncthreads();
+    for (uint32_t half = FIN_BLOCK / 2; half > 0; half >>= 1) {
+      if (threadIdx.x < half) sh_sq[threadIdx.x] += sh_sq[threadIdx.x + half];
+      __syncthreads();
+    }
+    const double norm = sqrt(sh_sq[0]), loss = sh_loss[0];
+    const bool finite = fabs(loss) < (double)INFINITY && fabs(norm) < (double)INFINITY;
+    const double sc = (clip_norm > 0.0f && norm > (double)clip_norm) ? (double)clip_norm / norm : 1.0;
+    for (uint32_t p = threadIdx.x; p < (uint32_t)NPAR && with_grad; p += FIN_BLOCK) {
+      const double g = sh_g[p] * sc;
+      if (grad_out) grad_out[p] = (float)g;
+      if (update && finite) {
+        const AdamStep adam(beta1, beta2, lr, eps, t);
+        state[p] = (float)adam(state[NPAR + p], state[2 * NPAR + p], g, state[p]);
+      }
+    }
+    if (threadIdx.x == 0 && update && finite) *step = t;
   }
 }
 
@@ -286,6 +524,8 @@ struct DenseNet {
   float* state = nullptr;
   float* ws = nullptr;                 // [rows][ROW] partial sums, one row per workgroup
   size_t ws_floats = 0;
+  float* ckpt = nullptr;               // [horizon][6][rows * TILE] check-points of cpmppi_dense_policy_* (cpmppi_dense_policy_reserve)
+  size_t ckpt_floats = 0;
   unsigned long long* step = nullptr;
   DenseNorm norm = {};
   bool set = false, begun = false;
@@ -294,24 +534,32 @@ struct DenseNet {
 namespace {
 
 size_t grad_rows(uint64_t samples) { return (size_t)((samples + WG_SAMPLES - 1) / WG_SAMPLES); }
+size_t policy_rows(uint64_t B) { return (size_t)((B + TILE - 1) / TILE); }      // a start state per lane, a row per wave
 
 DenseNet* net(cpmppi_handle* h) {
   if (!h->dense) h->dense = new DenseNet();
   return h->dense;
 }
 
-// Partial rows for `samples` samples and the step counter: allocated on first use, never inside a capture.
-int ensure(cpmppi_handle* h, uint64_t samples, hipStream_t s, const char* who) {
-  const size_t need = grad_rows(samples) * ROW;
+// `rows` partial rows, `ckpt_floats` check-point floats and the step counter: allocated on first use, never inside a capture
+// (`reserve`: the call that does it beforehand).
+int ensure_rows(cpmppi_handle* h, size_t rows, size_t ckpt_floats, hipStream_t s, const char* who, const char* reserve) {
+  const size_t need = rows * ROW;
   DenseNet* st = h->dense;
-  if (st && st->step && st->ws_floats >= need) return CPMPPI_OK;
-  if (const int rc = refuse_unreserved_capture(h, s, who, "cpmppi_dense_train_reserve")) return rc;
+  if (st && st->step && st->ws_floats >= need && st->ckpt_floats >= ckpt_floats) return CPMPPI_OK;
+  if (const int rc = refuse_unreserved_capture(h, s, who, reserve)) return rc;
   st = net(h);
   if (!st->step) {
     CPMPPI_HIP(h, hipMalloc(&st->step, sizeof(unsigned long long)));
     CPMPPI_HIP(h, hipMemset(st->step, 0, sizeof(unsigned long long)));
   }
-  return grow_workspace(h, st->ws, st->ws_floats, need);
+  if (const int rc = grow_workspace(h, st->ws, st->ws_floats, need)) return rc;
+  return grow_workspace(h, st->ckpt, st->ckpt_floats, ckpt_floats);
+}
+
+// Partial rows for `samples` samples of the recordings loss.
+int ensure(cpmppi_handle* h, uint64_t samples, hipStream_t s, const char* who) {
+  return ensure_rows(h, grad_rows(samples), 0, s, who, "cpmppi_dense_train_reserve");
 }
 
 bool has_model(const cpmppi_handle* h) { return h->dense && h->dense->set; }
@@ -349,13 +597,83 @@ int loss_grad_impl(cpmppi_handle* h, const cpmppi_dense_loss_args* a, float* gra
                         (uint32_t)N, a->R, a->T, a->post_wash_out, a->shift_labels};
   hipLaunchKernelGGL(with_grad ? &dense_grad_kernel<true> : &dense_grad_kernel<false>, dim3(rows), dim3(TILE), 0, s, st->norm, k);
   CPMPPI_HIP(h, hipGetLastError());
-  hipLaunchKernelGGL(dense_finalize_kernel, dim3(1), dim3(FIN_BLOCK), 0, s, (const float*)st->ws, rows, (double)N, st->state,
-                     a->loss_out, grad, st->step, lr, beta1, beta2, eps, update, with_grad ? 1 : 0);
+  hipLaunchKernelGGL(dense_finalize_kernel, dim3(1), dim3(FIN_BLOCK), 0, s, (const float*)st->ws, rows, (double)N,
+                     2.0 / (double)N, st->state, a->loss_out, grad, st->step, lr, beta1, beta2, eps, 0.0f, update, with_grad ? 1 : 0, 0);
   return launched(h);
 }
 
 int not_begun(cpmppi_handle* h, const char* who) {
   return begun_or_refuse(h, who, has_model(h) && h->dense->begun, "cpmppi_dense_train_begin");
+}
+
+// dense_policy_kernel's LDS: the parked tile (static) and the S x 6 sub-states per lane (dynamic) share the default 64 KB.
+constexpr size_t POLICY_TILE_LDS = (size_t)(4 * TILE * LDS_STRIDE + TILE * 8 + TILE) * sizeof(float);
+constexpr uint32_t POLICY_S_MAX = (uint32_t)((64 * 1024 - POLICY_TILE_LDS) / (6 * TILE * sizeof(float)));
+
+// What the cost steps refuse about the HANDLE (cpmppi.h lists it), in `who`'s name.
+int check_policy_handle(cpmppi_handle* h, const char* who) {
+  const auto refuse = [&](const std::string& why) { return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": " + why); };
+  if (!has_model(h)) return no_model(h, who);
+  if (h->gru_image)
+    return refuse("the handle's predictor is the GRU (cpmppi_set_gru): the differentiated plant is ODE_v0 or ODE");
+  if ((h->prm.cost_id != CPMPPI_COST_QBGM && h->prm.cost_id != CPMPPI_COST_DEFAULT) || h->prm.qb_mode != 0u)
+    return refuse("the cost is differentiated for quadratic_boundary_grad_minimal and default alone");
+  if (h->cfg.math_mode != CPMPPI_MATH_FAST) return refuse("the adjoint is written for the FAST arithmetic");
+  if (const int rc = refuse_tuning_rows(h, who)) return rc;
+  if (h->m_pole_rows) return refuse("per-row pole masses are registered (cpmppi_set_pole_mass_rows): the plant has the handle's pole mass");
+  if (h->cfg.S > POLICY_S_MAX)
+    return refuse("S too large for the LDS sub-state buffer (<= " + std::to_string(POLICY_S_MAX) + ")");
+  return CPMPPI_OK;
+}
+
+int check_policy_args(cpmppi_handle* h, const cpmppi_dense_policy_args* a, const char* who) {
+  const auto refuse = [&](const std::string& why) { return fail(h, CPMPPI_ERR_BAD_ARG, std::string(who) + ": " + why); };
+  if (const int rc = check_policy_handle(h, who)) return rc;
+  if (!a->states || !a->target_position || !a->target_equilibrium || !a->windows || !a->windows_host || !a->loss_out)
+    return refuse("states, target_position, target_equilibrium, windows, windows_host and loss_out are required");
+  if (a->B == 0 || a->R == 0 || a->T == 0 || a->horizon == 0) return refuse("B, R, T and horizon must be at least 1");
+  if (a->horizon > CPMPPI_MAX_HORIZON)
+    return refuse("horizon " + std::to_string(a->horizon) + ": at most " + std::to_string(CPMPPI_MAX_HORIZON));
+  if (misaligned(a->states) || misaligned(a->target_position) || misaligned(a->target_equilibrium) || misaligned(a->L) ||
+      misaligned(a->windows) || misaligned(a->windows_host) || misaligned(a->grad_out) || misaligned(a->cost_out) ||
+      misaligned(a->Q_out) || misaligned8(a->loss_out))
+    return fail(h, CPMPPI_ERR_ALIGN, std::string(who) + ": misaligned pointer");
+  return check_windows(h, who, a->windows_host, a->B, a->R, a->T, 1, "r < R, t0 <= T - 1");
+}
+
+size_t policy_ckpt_floats(uint64_t B, uint32_t horizon) { return (size_t)horizon * 6 * policy_rows(B) * TILE; }
+
+template <int COST, int INTEG>
+void launch_policy(bool grad, dim3 grid, size_t lds, hipStream_t s, const DenseNorm& nm, const cpmppi::Params& p, const PolicyArgs& k) {
+  if (grad) hipLaunchKernelGGL((dense_policy_kernel<COST, INTEG, true>), grid, dim3(TILE), lds, s, nm, p, k);
+  else hipLaunchKernelGGL((dense_policy_kernel<COST, INTEG, false>), grid, dim3(TILE), 0, s, nm, p, k);
+}
+
+// The mean cost (and its gradient into `grad`, or NULL) on `s`; `update`: and the clipped, guarded Adam.  Checks, workspace, the
+// two launches.
+int policy_impl(cpmppi_handle* h, const cpmppi_dense_policy_args* a, float* grad, int update, float lr, float beta1, float beta2,
+                float eps, float clip_norm, hipStream_t s, const char* who) {
+  if (const int rc = check_policy_args(h, a, who)) return rc;
+  const bool with_grad = grad || update;
+  const size_t rows = policy_rows(a->B);
+  if (const int rc = ensure_rows(h, rows, with_grad ? policy_ckpt_floats(a->B, a->horizon) : 0, s, who, "cpmppi_dense_policy_reserve"))
+    return rc;
+  DenseNet* st = h->dense;
+  cpmppi::Params p = h->prm;
+  p.H = a->horizon;                                                  // (the mean's 1 / (H + 1) is this call's horizon's)
+  const PolicyArgs k{a->states, a->target_position, a->target_equilibrium, a->L, a->windows, st->state, st->ws, st->ckpt,
+                     a->cost_out, a->Q_out, a->B, a->R, a->T};
+  const size_t lds = (size_t)h->cfg.S * 6 * TILE * sizeof(float);
+  const bool cromer = h->cfg.ode_predictor == CPMPPI_ODE_CROMER;
+  const auto launch = h->prm.cost_id == CPMPPI_COST_QBGM
+                          ? (cromer ? launch_policy<cpmppi::COST_QBGM, cpmppi::PREDICTOR_ODE> : launch_policy<cpmppi::COST_QBGM, cpmppi::PREDICTOR_ODE_V0>)
+                          : (cromer ? launch_policy<cpmppi::COST_DEFAULT, cpmppi::PREDICTOR_ODE> : launch_policy<cpmppi::COST_DEFAULT, cpmppi::PREDICTOR_ODE_V0>);
+  launch(with_grad, dim3((unsigned)rows), lds, s, st->norm, p, k);
+  CPMPPI_HIP(h, hipGetLastError());
+  hipLaunchKernelGGL(dense_finalize_kernel, dim3(1), dim3(FIN_BLOCK), 0, s, (const float*)st->ws, (uint32_t)rows, (double)a->B,
+                     1.0 / (double)a->B, st->state, a->loss_out, grad, st->step, lr, beta1, beta2, eps, clip_norm, update,
+                     with_grad ? 1 : 0, 1);
+  return launched(h);
 }
 
 }  // namespace
@@ -365,6 +683,7 @@ void dense_destroy(cpmppi_handle* h) {
   if (!st) return;
   if (st->state) (void)hipFree(st->state);
   if (st->ws) (void)hipFree(st->ws);
+  if (st->ckpt) (void)hipFree(st->ckpt);
   if (st->step) (void)hipFree(st->step);
   delete st;
   h->dense = nullptr;
@@ -496,6 +815,50 @@ int cpmppi_dense_train_step(cpmppi_handle* h, const cpmppi_dense_loss_args* a, f
   CPMPPI_ON_DEVICE(h);
   return loss_grad_impl(h, a, nullptr, 1, lr, beta1, beta2, eps, (hipStream_t)stream, "cpmppi_dense_train_step");
 } catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }
+
+int cpmppi_dense_policy_reserve(cpmppi_handle* h, uint32_t B, uint32_t horizon) try {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (B == 0 || horizon == 0 || horizon > CPMPPI_MAX_HORIZON)
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_dense_policy_reserve: B and horizon must be at least 1, horizon at most " +
+                                           std::to_string(CPMPPI_MAX_HORIZON));
+  CPMPPI_ON_DEVICE(h);
+  return ensure_rows(h, policy_rows(B), policy_ckpt_floats(B, horizon), nullptr, "cpmppi_dense_policy_reserve",
+                     "cpmppi_dense_policy_reserve");
+} catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }
+
+int cpmppi_dense_policy_loss_grad(cpmppi_handle* h, const cpmppi_dense_policy_args* a, void* stream) try {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_dense_policy_loss_grad: no argument block");
+  CPMPPI_ON_DEVICE(h);
+  return policy_impl(h, a, a->grad_out, 0, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, (hipStream_t)stream, "cpmppi_dense_policy_loss_grad");
+} catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }
+
+int cpmppi_dense_policy_train_step(cpmppi_handle* h, const cpmppi_dense_policy_args* a, float lr, float beta1, float beta2, float eps,
+                                   float clip_norm, void* stream) try {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!a) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_dense_policy_train_step: no argument block");
+  if (!has_model(h)) return no_model(h, "cpmppi_dense_policy_train_step");
+  if (const int rc = not_begun(h, "cpmppi_dense_policy_train_step")) return rc;
+  CPMPPI_ON_DEVICE(h);
+  return policy_impl(h, a, nullptr, 1, lr, beta1, beta2, eps, clip_norm, (hipStream_t)stream, "cpmppi_dense_policy_train_step");
+} catch (const std::exception&) { return CPMPPI_ERR_NOMEM; }
+
+uint64_t cpmppi_dense_policy_ckpt_floats(cpmppi_handle* h) { return h && h->dense ? (uint64_t)h->dense->ckpt_floats : 0; }
+
+int cpmppi_dense_policy_ckpt_copy(cpmppi_handle* h, float* host, uint64_t floats, int to_device) {
+  if (!h) return CPMPPI_ERR_BAD_ARG;
+  if (!host) return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_dense_policy_ckpt_copy: host is required");
+  if (floats > cpmppi_dense_policy_ckpt_floats(h))
+    return fail(h, CPMPPI_ERR_BAD_ARG, "cpmppi_dense_policy_ckpt_copy: " + std::to_string(floats) + " floats, " +
+                                           std::to_string(cpmppi_dense_policy_ckpt_floats(h)) + " are reserved");
+  if (floats == 0) return CPMPPI_OK;
+  CPMPPI_ON_DEVICE(h);
+  CPMPPI_HIP(h, hipDeviceSynchronize());
+  if (to_device) CPMPPI_HIP(h, hipMemcpy(h->dense->ckpt, host, (size_t)floats * sizeof(float), hipMemcpyHostToDevice));
+  else CPMPPI_HIP(h, hipMemcpy(host, h->dense->ckpt, (size_t)floats * sizeof(float), hipMemcpyDeviceToHost));
+  CPMPPI_HIP(h, hipDeviceSynchronize());
+  return CPMPPI_OK;
+}
 
 int cpmppi_dense_train_get(cpmppi_handle* h, float* params_host) {
   if (!h) return CPMPPI_ERR_BAD_ARG;

@@ -984,6 +984,94 @@ class MPPIEngine:
         batch and buffers (a benchmark loop, a capture - after ``dense_train_reserve``)."""
         return self._build_dense_train_step(*args, **kwargs)
 
+    # ------------------------------------------------------------------ fine-tuning the imitator on the task cost through the ODE plant
+    def _dense_policy_args(self, states, target_position, target_equilibrium, windows, horizon, pole_lengths=None, loss_out=None,
+                           grad_out=None, grad=True, cost_out=None, Q_out=None):
+        """The argument block of cpmppi_dense_policy_loss_grad / cpmppi_dense_policy_train_step, checked: -> (block, what it points
+        into, loss_out, grad_out).  ``windows`` [B,2] integers (r, t0) on the HOST - a window is ONE row, the start state: uploaded
+        here, and handed to the library as its host copy."""
+        self._need_dense()
+        if self.has_gru:
+            raise ValueError("the engine holds a GRU predictor (set_gru): the GRU as the differentiated plant is not built - the cost "
+                             "is differentiated through ODE_v0 or ODE")
+        states = self.tensor(states)
+        if states.dim() != 3 or states.shape[2] != 6 or states.shape[0] == 0 or states.shape[1] == 0:
+            raise ValueError(f"states must be [R,T,6] with R, T >= 1, got {tuple(states.shape)}")
+        R, T = states.shape[0], states.shape[1]
+        tp, te = self.tensor(target_position), self.tensor(target_equilibrium)
+        if tp.shape != (R, T) or te.shape != (R, T):
+            raise ValueError(f"target_position and target_equilibrium must be [{R},{T}] for states [{R},{T},6]")
+        horizon = int(horizon)
+        if not 1 <= horizon <= 1024:
+            raise ValueError(f"horizon must be in 1..1024, got {horizon}")
+        w_host, w_dev, B = self._window_batch(windows, R, T, 0, "0")
+        L = self.tensor(pole_lengths, (R,)) if pole_lengths is not None else None
+        loss_out, grad_out = self._loss_outputs(loss_out, grad_out, grad, _L.DENSE_PARAMS, torch.float32)
+        for name, t, shape in (("cost_out", cost_out, (B,)), ("Q_out", Q_out, (B, horizon))):
+            if t is not None and device_tensor(name, t).shape != shape:
+                raise ValueError(f"{name} must be {list(shape)}")
+        a = _L.cpmppi_dense_policy_args()
+        a.B, a.R, a.T, a.horizon = B, R, T, horizon
+        a.states, a.target_position, a.target_equilibrium, a.L = states.data_ptr(), tp.data_ptr(), te.data_ptr(), _addr(L)
+        a.windows, a.windows_host = w_dev.data_ptr(), w_host.ctypes.data
+        a.loss_out, a.grad_out, a.cost_out, a.Q_out = loss_out.data_ptr(), _addr(grad_out), _addr(cost_out), _addr(Q_out)
+        return a, (states, tp, te, L, w_dev, w_host, loss_out, grad_out, cost_out, Q_out), loss_out, grad_out
+
+    def dense_policy_reserve(self, B, horizon):
+        """cpmppi_dense_policy_reserve: check-points and partial rows of ``dense_policy_loss_grad`` / ``dense_policy_train_step`` for
+        up to ``B`` start states and that ``horizon``, so that a later call can be captured."""
+        self._check(self.lib.cpmppi_dense_policy_reserve(self._h, int(B), int(horizon)))
+
+    def dense_policy_ckpt(self, fill=None):
+        """Test aid (cpmppi_dense_policy_ckpt_floats / _ckpt_copy): the reserved check-point workspace of the cost steps, which is
+        the handle's own -> its floats as a host array (synchronous); ``fill``: first every one of them is set to that value."""
+        n = int(self.lib.cpmppi_dense_policy_ckpt_floats(self._h))
+        host = np.empty(n, np.float32)
+        if fill is not None:
+            host[:] = fill
+        if n:
+            self._check(self.lib.cpmppi_dense_policy_ckpt_copy(self._h, host.ctypes.data_as(C.POINTER(C.c_float)), n, int(fill is not None)))
+        return host
+
+    def _build_dense_policy_loss_grad(self, states, target_position, target_equilibrium, windows, horizon, pole_lengths=None, grad=True, *,
+                                      loss_out=None, grad_out=None, cost_out=None, Q_out=None):
+        """cpmppi_dense_policy_loss_grad: the mean over ``windows`` [B,2] = (recording, row) of the closed-loop trajectory cost - from
+        the state ``states`` [R,T,6] at that row the imitator drives the engine's ODE predictor for ``horizon`` control steps under
+        the row's targets, scored by the engine's cost (include/cpmppi.h states it) - and its derivative with respect to the 1345
+        parameters.  ``pole_lengths`` [R]: the pole length per recording.  ``cost_out`` [B]: every start state's cost; ``Q_out``
+        [B,horizon]: the controls.
+        -> (loss [1] float64 on the device, gradient [1345] in the flat order of ``DENSE_KEYS`` - None with ``grad=False``, the loss
+        alone, bit for bit the loss of the gradient call)."""
+        a, keep, loss_out, grad_out = self._dense_policy_args(states, target_position, target_equilibrium, windows, horizon, pole_lengths,
+                                                              loss_out, grad_out, grad, cost_out, Q_out)
+        return PreparedCall(self, self.lib.cpmppi_dense_policy_loss_grad, a, keep, (loss_out, grad_out), ())
+
+    dense_policy_loss_grad = _run_once(_build_dense_policy_loss_grad)
+
+    def prepare_dense_policy_loss_grad(self, *args, **kwargs):
+        """The argument block of ``dense_policy_loss_grad(...)`` built and validated ONCE (a capture - after ``dense_policy_reserve``)."""
+        return self._build_dense_policy_loss_grad(*args, **kwargs)
+
+    def _build_dense_policy_train_step(self, states, target_position, target_equilibrium, windows, horizon, pole_lengths=None, *, lr,
+                                       beta1=0.9, beta2=0.999, eps=1e-8, clip_norm=0.0, loss_out=None):
+        """cpmppi_dense_policy_train_step: the loss and gradient of ``dense_policy_loss_grad`` over this batch, the gradient scaled to
+        the global norm ``clip_norm`` (<= 0: off) and one Adam update of the parameter vector in place - in the run of
+        ``dense_train_begin``, whose moments and counter ``dense_train_step`` shares.  A non-finite loss or norm leaves the
+        parameters, the moments and the counter alone.  -> the batch's loss BEFORE the update, [1] float64 on the device."""
+        a, keep, loss_out, _ = self._dense_policy_args(states, target_position, target_equilibrium, windows, horizon, pole_lengths, loss_out,
+                                                       None, False)
+        lib, hyper = self.lib, (float(lr), float(beta1), float(beta2), float(eps), float(clip_norm))
+        return PreparedCall(self, lambda h, ref, stream: lib.cpmppi_dense_policy_train_step(h, ref, *hyper, stream), a, keep, loss_out, ())
+
+    def dense_policy_train_step(self, *args, **kwargs):
+        """``_build_dense_policy_train_step``'s call, run once: -> the batch's loss before the update."""
+        return self._run_keeping("_dense_keep", self._build_dense_policy_train_step(*args, **kwargs))
+
+    def prepare_dense_policy_train_step(self, *args, **kwargs):
+        """The argument block of ``dense_policy_train_step(...)`` built and validated ONCE: every ``.run()`` is one more step on the
+        same batch and buffers (a benchmark loop, a capture - after ``dense_policy_reserve``)."""
+        return self._build_dense_policy_train_step(*args, **kwargs)
+
     def dense_train_get(self):
         """cpmppi_dense_train_get: the trained weights as the dict ``set_dense`` takes (weights only; the normalisation is the
         caller's).  Synchronous."""
@@ -1639,7 +1727,7 @@ class MPPIEngine:
 
 class PreparedCall:
     """One entry point of the library that takes an argument block, ready to be enqueued any number of times
-    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_rpgd_step_gru / prepare_cem_step / prepare_cem_step_gru / prepare_brunton / prepare_gru_loss_grad / prepare_ode_fit_loss_grad / prepare_ode_fit_step / prepare_dense_control / prepare_dagger_step / prepare_dense_loss_grad / prepare_dense_train_step).  ``args`` is the live
+    (MPPIEngine.prepare_step / prepare_plant_step / prepare_rpgd_step / prepare_rpgd_step_gru / prepare_cem_step / prepare_cem_step_gru / prepare_brunton / prepare_gru_loss_grad / prepare_ode_fit_loss_grad / prepare_ode_fit_step / prepare_dense_control / prepare_dagger_step / prepare_dense_loss_grad / prepare_dense_train_step / prepare_dense_policy_loss_grad / prepare_dense_policy_train_step).  ``args`` is the live
     ctypes block, validated when it was built, and ``ref`` the reference to it that the library is handed; ``keep`` holds the
     tensors it points into; ``enqueue`` is the entry point, ``enqueue(handle, ref, stream)``.  ``result`` is what the call returns:
     the outputs of a control step - ``out``, whose first two are ``Q_out`` and ``S_out`` -, the plant's state, or the Brunton

@@ -164,6 +164,57 @@ def train_imitator(engine, states, target_position, target_equilibrium, labels, 
     return trained, history
 
 
+# ---------------------------------------------------------------------------------------------------------------- the task cost
+def finetune_on_cost(engine, states, target_position, target_equilibrium, lengths=None, *, horizon, epochs, batch_size, lr, clip_norm,
+                     seed, init, validation=None, pole_lengths=None, beta1=0.9, beta2=0.999, eps=1e-7, validation_batch=4096, log=None):
+    """Fine-tune the model ``init`` (weights and normalisation: a clone, or what ``dagger`` returns) on the cost the MPC minimises:
+    every row of ``states`` [R,T,6] with its ``target_position`` / ``target_equilibrium`` [R,T] is a start state from which the net
+    drives ``engine``'s ODE predictor for ``horizon`` control steps, scored by ``engine``'s cost; Adam follows the exact gradient of
+    the batch's mean cost (``MPPIEngine.dense_policy_train_step``), clipped to the global norm ``clip_norm`` (<= 0: off).  The three
+    tensors may be a ``harness.DaggerDataset``'s, where they lie on the device.  ``lengths`` [R]: the recordings' true lengths (None
+    = T); ``pole_lengths`` [R]: the pole length per recording (None: the engine's).  ``validation`` = (states, target_position,
+    target_equilibrium, lengths or None) is scored after every epoch through the loss-only call.  No label is read: the net is not
+    told what the MPC did.  A batch whose loss or gradient norm is not finite changes nothing (its loss is recorded as it is).
+    -> (the model dict ``MPPIEngine.set_dense`` takes, which the engine holds on return; history as ``train_imitator``'s)."""
+    import torch
+    epochs, batch_size = int(epochs), int(batch_size)
+    if epochs < 1 or batch_size < 1:
+        raise ValueError("epochs and batch_size must be at least 1")
+    _check_model(init)
+    norm = {k: np.asarray(init[k], f32) for k in NORM_KEYS if init.get(k) is not None}
+    if len(norm) != 4:
+        raise ValueError("init must carry its normalisation (in_scale, in_shift, out_scale, out_shift): fine-tuning starts from a trained model")
+
+    def recordings(s, tp, te, n):
+        s = s if torch.is_tensor(s) else np.ascontiguousarray(s, f32)
+        R, T = s.shape[0], s.shape[1]
+        n = np.full(R, T) if n is None else np.asarray(n).reshape(-1)
+        if tuple(s.shape[2:]) != (6,) or tuple(tp.shape) != (R, T) or tuple(te.shape) != (R, T) or n.shape != (R,) or n.min() < 0 or n.max() > T:
+            raise ValueError("states must be [R,T,6], target_position and target_equilibrium [R,T], lengths one length 0..T per recording")
+        windows = make_windows(n, 0, 1, 0)
+        if len(windows) == 0:
+            raise ValueError("the recordings hold no row")
+        return tuple(engine.tensor(x) for x in (s, tp, te)), windows
+
+    dev, windows = recordings(states, target_position, target_equilibrium, lengths)
+    engine.set_dense({**{k: np.asarray(init[k], f32) for k in DENSE_KEYS}, **norm})
+    engine.dense_train_begin()
+    loss_of = vw = None
+    if validation is not None:
+        vdev, vw = recordings(*validation[:3], validation[3] if len(validation) > 3 else None)
+        loss_of = lambda w: engine.dense_policy_loss_grad(*vdev, w, horizon, pole_lengths, grad=False)[0]  # noqa: E731
+
+    def step(batch, rate, loss_out, tag):
+        engine.dense_policy_train_step(*dev, batch, horizon, pole_lengths, lr=rate, beta1=beta1, beta2=beta2, eps=eps,
+                                       clip_norm=clip_norm, loss_out=loss_out)
+
+    history, _ = run_epochs(engine.device, lambda epoch: (windows, None), step, loss_of, vw, epochs=epochs, batch_size=batch_size,
+                            seed=seed, lr=lr, log=log, validation_batch=validation_batch, plateau=(False, 0, 1.0, 0.0, 0.0))
+    trained = {**engine.dense_train_get(), **norm}
+    engine.set_dense(trained)          # (ends the run: the engine holds the trained model as any other)
+    return trained, history
+
+
 # ---------------------------------------------------------------------------------------------------------------- DAgger
 def beta_schedule(beta, iterations):
     """The probability that the expert drives, per iteration: a number (every iteration), a sequence of at most ``iterations``
@@ -346,26 +397,42 @@ def identity_normalization():
 def load_recordings_folder(folder, label_column=LABEL_COLUMN):
     """Every recording CSV of ``folder`` (``along_trajectories.load_columns``) -> (states [R,T,6], target_position,
     target_equilibrium, labels [R,T] padded with zeros to the longest, lengths [R], the file names).  A file without
-    ``label_column`` is refused by name."""
+    ``label_column`` is refused by name; ``label_column`` None: no label is read (``labels`` stays zero).  The lengths are those of
+    the target_position column."""
     from .along_trajectories import FEATURES, load_columns
     names = sorted(n for n in os.listdir(folder) if n.endswith(".csv"))
     if not names:
         raise ValueError(f"{folder}: no recording (*.csv)")
-    wanted = ["target_position", "target_equilibrium", label_column]
+    wanted = ["target_position", "target_equilibrium"] + ([label_column] if label_column is not None else [])
     cols = [load_columns(os.path.join(folder, n), wanted) for n in names]
-    lengths = np.array([len(c[label_column]) for c in cols])
+    lengths = np.array([len(c["target_position"]) for c in cols])
     R, T = len(cols), int(lengths.max())
     states = np.zeros((R, T, 6), f32)
     tp, te, labels = np.zeros((R, T), f32), np.zeros((R, T), f32), np.zeros((R, T), f32)
     for r, c in enumerate(cols):
         n = lengths[r]
         states[r, :n] = np.stack([c[f] for f in FEATURES], axis=-1)
-        tp[r, :n], te[r, :n], labels[r, :n] = c["target_position"], c["target_equilibrium"], c[label_column]
+        tp[r, :n], te[r, :n] = c["target_position"], c["target_equilibrium"]
+        if label_column is not None:
+            labels[r, :n] = c[label_column]
     return states, tp, te, labels, lengths, names
 
 
 def check_command_line(args):
     """What the two modes of the command line exclude, refused by name (SystemExit) before anything is read."""
+    if args.finetune_cost:
+        for flag, given in (("--init FOLDER", args.init is None), ("--recordings DIR", args.recordings is None),
+                            ("--horizon H", args.horizon is None), ("--config-root CHECKOUT", args.config_root is None)):
+            if given:
+                raise SystemExit(f"train_imitator: --finetune-cost needs {flag}")
+        if args.dagger is not None:
+            raise SystemExit("train_imitator: --finetune-cost and --dagger are two runs: the second takes the first's folder as --init")
+        for flag, given in (("--label-column", args.label_column is not None), ("--post-wash-out", args.post_wash_out is not None),
+                            ("--shift-labels", args.shift_labels is not None)):
+            if given:
+                raise SystemExit(f"train_imitator: --finetune-cost reads no label: {flag} belongs to the training on recordings")
+    elif args.horizon is not None or args.clip_norm is not None:
+        raise SystemExit("train_imitator: --horizon and --clip-norm belong to --finetune-cost")
     if args.dagger is None:
         if args.recordings is None:
             raise SystemExit("train_imitator: --recordings DIR (or --dagger ITERATIONS) is required")
@@ -410,11 +477,34 @@ def dagger_command(args, settings, init):
         engine.close()
 
 
+def finetune_command(args, settings, init):
+    """``--finetune-cost``: the engine - predictor, cost, dt, substeps, physics - from the checkout's configuration; every row of
+    the recordings (no control or label column is read) is a start state -> ``finetune_on_cost(...)``."""
+    from .configs import load_reference_yaml, mppi_config_from_yaml
+    from .engine import MPPIEngine
+    phys, cfgs = load_reference_yaml(args.config_root)
+    states, tp, te, _, lengths, names = load_recordings_folder(args.recordings, None)
+    validation = None
+    if args.validation:
+        vs, vtp, vte, _, vl, _ = load_recordings_folder(args.validation, None)
+        validation = (vs, vtp, vte, vl)
+    engine = MPPIEngine(1, mppi_config_from_yaml(cfgs), phys=phys, device=args.device)
+    try:
+        model, history = finetune_on_cost(engine, states, tp, te, lengths, horizon=args.horizon, epochs=settings["epochs"],
+                                          batch_size=settings["batch_size"], lr=settings["lr"], seed=settings["seed"], init=init,
+                                          clip_norm=args.clip_norm if args.clip_norm is not None else 10.0, validation=validation, log=print)
+    finally:
+        engine.close()
+    return model, history, names
+
+
 def main(argv=None):
     """python -m cartpolesimulation_amd.train_imitator --recordings DIR --out FOLDER --config-root CHECKOUT
     [--label-column Q_calculated_offline] [--validation DIR] [--init FOLDER]
     python -m cartpolesimulation_amd.train_imitator --dagger ITERATIONS --beta 1,0.5,0.25,0 --experiments E --steps-per-iteration K
-    --config-root CHECKOUT --out FOLDER [--optimizer rpgd] [--init FOLDER] [--graph]"""
+    --config-root CHECKOUT --out FOLDER [--optimizer rpgd] [--init FOLDER] [--graph]
+    python -m cartpolesimulation_amd.train_imitator --finetune-cost --init FOLDER --recordings DIR --horizon H [--clip-norm C]
+    --out FOLDER --config-root CHECKOUT [--validation DIR]"""
     import argparse
     import yaml
     ap = argparse.ArgumentParser(description="Train the neural imitator (Dense-7IN-32H1-32H2-1OUT) on relabelled recordings, on MI355X "
@@ -428,12 +518,17 @@ def main(argv=None):
     ap.add_argument("--steps-per-iteration", type=int, default=None, metavar="K", help="--dagger: Adam steps after every iteration's runs")
     ap.add_argument("--optimizer", default=None, choices=["mppi", "rpgd"], help="--dagger: the expert (rpgd: the fused step; default mppi)")
     ap.add_argument("--graph", action="store_true", help="--dagger: the runs captured as graphs of control periods")
+    ap.add_argument("--finetune-cost", action="store_true",
+                    help="fine-tune --init on the task cost instead of labels: from every row of --recordings the net drives the "
+                         "configured ODE predictor for --horizon control steps, scored by the configured cost; needs --config-root")
+    ap.add_argument("--horizon", type=int, default=None, metavar="H", help="--finetune-cost: control steps of the differentiated closed loop")
+    ap.add_argument("--clip-norm", type=float, default=None, metavar="C", help="--finetune-cost: the gradient's global norm is clipped to this (default 10; 0: off)")
     ap.add_argument("--validation", default=None, metavar="DIR", help="a folder of recordings scored after every epoch")
     ap.add_argument("--out", required=True, metavar="FOLDER", help="the model folder to write (e.g. .../Dense-7IN-32H1-32H2-1OUT-0)")
     ap.add_argument("--config-root", default=None, metavar="CHECKOUT",
                     help="a CartPoleSimulation checkout: SI_Toolkit_ASF/config_training.yml, taken as shipped; without it its values")
     ap.add_argument("--config-training", default=None, metavar="FILE", help="a config_training.yml elsewhere than in the checkout")
-    ap.add_argument("--label-column", default=LABEL_COLUMN, help="the column to imitate (default: what along_trajectories writes)")
+    ap.add_argument("--label-column", default=None, help=f"the column to imitate (default: what along_trajectories writes, {LABEL_COLUMN})")
     for flag, typ in (("--epochs", int), ("--batch-size", int), ("--seed", int), ("--lr", float), ("--post-wash-out", int),
                       ("--shift-labels", int)):
         ap.add_argument(flag, type=typ, default=None, help="instead of the file's value")
@@ -441,6 +536,7 @@ def main(argv=None):
     ap.add_argument("--device", type=int, default=0)
     args = ap.parse_args(argv)
     check_command_line(args)
+    label_column = args.label_column or LABEL_COLUMN
     path = args.config_training or (os.path.join(args.config_root, "SI_Toolkit_ASF", "config_training.yml") if args.config_root else None)
     config = {"modeling": {"NET_NAME": NET_NAME},
               "training_default": {"state_inputs": list(DENSE_INPUTS), "outputs": ["Q_calculated"], "SEED": 1873, "SHIFT_LABELS": 0}}
@@ -470,8 +566,15 @@ def main(argv=None):
         print(f"DAgger: {args.dagger} iterations, disagreement {history['disagreement'][0]:.6e} -> "
               f"{history['disagreement'][-1]:.6e}; model folder: {folder}")
         return model, history
-    *train, lengths, names = load_recordings_folder(args.recordings, args.label_column)
-    validation = load_recordings_folder(args.validation, args.label_column)[:5] if args.validation else None
+    if args.finetune_cost:
+        info["TRAINING_FILES"] = f"task cost over {args.horizon} control steps from the rows of {os.path.abspath(args.recordings)}"
+        model, history, names = finetune_command(args, settings, init)
+        folder = write_model_folder(args.out, model, info=info)
+        print(f"fine-tuned on the cost from the rows of {len(names)} recordings, loss {history['loss'][0]:.6e} -> "
+              f"{history['loss'][-1]:.6e}; model folder: {folder}")
+        return model, history
+    *train, lengths, names = load_recordings_folder(args.recordings, label_column)
+    validation = load_recordings_folder(args.validation, label_column)[:5] if args.validation else None
     from .configs import MPPIConfig
     from .engine import MPPIEngine
     engine = MPPIEngine(1, MPPIConfig(num_rollouts=1, mpc_horizon=2), device=args.device)

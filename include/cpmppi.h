@@ -69,7 +69,9 @@ extern "C" {
                                       cpmppi_set_dense / cpmppi_dense_model, cpmppi_dense_control / cpmppi_dense_control_args,
                                       cpmppi_dense_loss_grad / cpmppi_dense_loss_args, cpmppi_dense_train_reserve / _begin / _step /
                                       _get (new entry points, likewise);
-                                      cpmppi_dagger_step / cpmppi_dagger_args (a new entry point, likewise). */
+                                      cpmppi_dagger_step / cpmppi_dagger_args (a new entry point, likewise);
+                                      cpmppi_dense_policy_reserve / _loss_grad / _train_step, cpmppi_dense_policy_args,
+                                      cpmppi_dense_policy_ckpt_floats / _ckpt_copy (new entry points, likewise). */
 #define CPMPPI_STATE_DIM 6u
 #define CPMPPI_MAX_HORIZON 1024u
 
@@ -745,6 +747,76 @@ int cpmppi_dense_train_begin(cpmppi_handle* h);
 int cpmppi_dense_train_step(cpmppi_handle* h, const cpmppi_dense_loss_args* args, float lr, float beta1, float beta2, float eps,
                             void* stream);
 int cpmppi_dense_train_get(cpmppi_handle* h, float* params_host);
+
+/* FINE-TUNING the neural imitator ON THE TASK COST through the ODE plant: the exact derivative of the closed-loop trajectory cost
+ * - the net drives the handle's ODE predictor, the handle's plugin cost scores the trajectory - with respect to the 1345
+ * parameters.  The reference trains its controller net with PPO from stable-baselines3 (GymlikeCartPole/Train_RL_Cartpole.py, a
+ * score-function estimator over 500 000 CPU steps); this library holds the reverse sweep of both ODE predictors and of the plugin
+ * costs (cpmppi_rollout_cost_grad) and the net's backward pass (cpmppi_dense_loss_grad), and composes them.  The semantics are
+ * THIS LIBRARY'S OWN.
+ * The handle's predictor is ODE_v0 or ODE, its cost quadratic_boundary_grad_minimal or default; dt, the substep count S,
+ * horizon_reduce and the physical parameters are the handle's.  Recordings states[R,T,6], target_position[R,T],
+ * target_equilibrium[R,T]; a batch is B windows (r, t0), each needing ONE row.  For window b, with s_0 = states[r,t0] and the two
+ * targets of that row held over the horizon, for k = 0 .. horizon-1:
+ *   x_k = the 7 normalised inputs of (s_k, target_equilibrium, target_position); y_k = the net's output; q_k = out_scale y_k +
+ *   out_shift; u_k = clamp(q_k, -1, 1) - the bits cpmppi_dense_control gives for that state; the stage cost is that of (s_k, u_k);
+ *   s_{k+1} = S substeps of the predictor in the plain form cpmppi_rollout_cost_grad integrates (stage 0 takes cos(angle) of the
+ *   given state, as there).
+ * J_b = scale (sum of the stage costs + the terminal cost), scale = 1 or 1 / (horizon + 1) by horizon_reduce, exactly what
+ * cpmppi_rollout_cost_grad returns for the plan u_0 .. u_{horizon-1} from s_0 on a handle whose H is `horizon`.
+ * loss = (1 / B) sum_b J_b.  grad_out: d loss / d parameters in the flat order.  Non-smooth pieces as cpmppi_rollout_cost_grad
+ * differentiates them: the branch taken at the bounce, derivative 1 through the wrap, 0 through indicators and through a clipped
+ * control - a step whose q_k lies outside [-1, 1] passes nothing back through the net at that step.  L[R], optional: the pole
+ * length per recording (NULL: the handle's); the pole mass is the handle's.  cost_out[B], optional: J_b.  Q_out[B,horizon],
+ * optional: the u_k.  The sensitivity of the closed loop grows fast with the horizon (an unstable plant under a net that does not
+ * stabilise it yet): float32 gradients are meaningful for short horizons, and the train step guards itself (below).
+ * Two launches: (1) a lane per start state, ONE wave per workgroup: forward with s_k check-pointed per control step, then for
+ * k = horizon-1 .. 0 the substeps' reverse sweep, the stage gradient and the net's backward pass with d J / d y_k in the place of
+ * the MSE residual, contracted over the wave's 64 samples on v_mfma_f32_32x32x2_f32 into accumulators that live across all steps;
+ * one partial row per workgroup, plain stores.  (2) cpmppi_dense_loss_grad's finalize launch with the scale 1 / B.  No atomics, no
+ * host synchronisation, every sum in a fixed order: the same bits from run to run, whatever ran before.  grad_out == NULL: the
+ * loss alone, bit for bit the loss of a gradient call.
+ * cpmppi_dense_policy_reserve(h, B, horizon): check-points and partial rows for calls of up to B windows and that horizon; they
+ * are otherwise allocated on first use, and a capture that would have to allocate is refused.
+ * cpmppi_dense_policy_train_step: launch (1), then a finalize launch that walks the partial rows in float64 in fixed order, forms
+ * the gradient's global 2-norm over the 1345 entries in a fixed order, scales the gradient by min(1, clip_norm / norm)
+ * (clip_norm <= 0: off) and applies the Adam update of cpmppi_dense_train_step to the live parameter vector in place.  The run is
+ * the one cpmppi_dense_train_begin starts: moments and counter are shared with cpmppi_dense_train_step, so MSE steps and cost
+ * steps may alternate.  If the loss or the norm is not finite, parameters, moments and the step counter keep their bits;
+ * loss_out still carries the non-finite value.  loss_out: the loss BEFORE the update.  grad_out is not read.
+ * Refused ("cpmppi_dense_policy_...: ..."), nothing launched, CPMPPI_ERR_BAD_ARG: no model set; _train_step before
+ * cpmppi_dense_train_begin; a NULL states, target_position, target_equilibrium, windows, windows_host or loss_out; B, R, T or
+ * horizon equal to 0 (horizon > CPMPPI_MAX_HORIZON); a host window outside r < R, t0 <= T - 1; a handle that holds a GRU model
+ * (cpmppi_set_gru: the GRU as the differentiated plant is not built); a cost other than the two above; a math mode other than
+ * FAST; per-env tuning rows or pole-mass rows registered; S beyond the LDS sub-state buffer.  A misaligned pointer is
+ * CPMPPI_ERR_ALIGN (loss_out: 8 bytes).  Not built: measurement noise, latency or control disturbance inside the differentiated
+ * rollout, stochastic policies, other net sizes. */
+typedef struct {
+  uint32_t B;                           /* windows = start states */
+  uint32_t R, T;                        /* recordings, rows of each */
+  uint32_t horizon;                     /* control steps of the closed loop */
+  const float* states;                  /* [R,T,6] */
+  const float* target_position;         /* [R,T] */
+  const float* target_equilibrium;      /* [R,T] */
+  const float* L;                       /* [R] pole length per recording, or NULL (the handle's) */
+  const uint32_t* windows;              /* [B][2] DEVICE: (r, t0) */
+  const uint32_t* windows_host;         /* [B][2] HOST: the same, checked by every call */
+  double* loss_out;                     /* DEVICE, one double */
+  float* grad_out;                      /* [CPMPPI_DENSE_PARAMS] DEVICE, or NULL */
+  float* cost_out;                      /* [B] DEVICE, or NULL: J_b */
+  float* Q_out;                         /* [B,horizon] DEVICE, or NULL: the controls u_k */
+} cpmppi_dense_policy_args;
+int cpmppi_dense_policy_reserve(cpmppi_handle* h, uint32_t B, uint32_t horizon);
+int cpmppi_dense_policy_loss_grad(cpmppi_handle* h, const cpmppi_dense_policy_args* args, void* stream);
+int cpmppi_dense_policy_train_step(cpmppi_handle* h, const cpmppi_dense_policy_args* args, float lr, float beta1, float beta2,
+                                   float eps, float clip_norm, void* stream);
+/* Test aid: the check-point workspace of the calls above is the handle's own, so a test cannot fence it from outside.
+ * cpmppi_dense_policy_ckpt_floats: how many floats are reserved (0 before the first reserving call).
+ * cpmppi_dense_policy_ckpt_copy: the first `floats` of them <- host[floats] (to_device != 0) or -> host[floats], synchronously (the
+ * device is synchronised before and after).  A launch of `rows` = ceil(B / 64) workgroups and `horizon` steps writes and reads
+ * exactly the first horizon * 6 * rows * 64 floats.  Refused (CPMPPI_ERR_BAD_ARG): a NULL host, more floats than are reserved. */
+uint64_t cpmppi_dense_policy_ckpt_floats(cpmppi_handle* h);
+int cpmppi_dense_policy_ckpt_copy(cpmppi_handle* h, float* host, uint64_t floats, int to_device);
 
 /* DAgger (Ross, Gordon, Bagnell 2011) for the neural imitator: one control period in which the EXPERT labels the state and the
  * imitator - or, per env and period, a coin that favours the expert with probability beta - drives.  cpmppi_dagger_step is ONE
